@@ -171,6 +171,33 @@ def cpu_threads():
     return max(1, min(16, len(os.sched_getaffinity(0)), os.cpu_count() or 1))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes `arrays` (name -> tensor) as directory/<name>.npy, float64 kept, everything else as float32, `limit` bytes in all.
+    The budget is shared out smallest array first: an array that fits its share is written whole, a larger one as a flat sample of
+    its elements at positions drawn with a fixed seed (sorted, repeats dropped) -- the same arguments give the same positions, so
+    two builds still compare element for element."""
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        t = torch.as_tensor(v).detach().cpu()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).numpy()
+    left = limit - 4096 * len(host)              # 4 KB per file for the .npy header
+    notes = []
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(host) - i)
+        if a.nbytes > share:
+            n = share // a.itemsize
+            notes.append(f"{name}: a seeded sample of {n} of its {a.size} elements")
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, n))]
+        left -= a.nbytes
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+    log(f"[bench] outputs of the last timed step -> {directory}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in host.items())
+        + (f" ({'; '.join(notes)})" if notes else ""))
+
+
 # ------------------------------------------------------------------------------------------------------
 def build_vocoder(args, world, rank, dev):
     from indextts_amd import weights
@@ -183,12 +210,15 @@ def build_vocoder(args, world, rank, dev):
     mel = torch.from_numpy(weights.synth_mel(f"bench/mel/rank{rank}", B, cfg.num_mels, Tm)).to(dev)
     n_samples = Tm * cfg.total_upsample
     gathered = [torch.empty(B, 1, n_samples, device=dev) for _ in range(world)] if (world > 1 and rank == 0) else None
+    received = {}
 
     def step():
         wav = voc(mel)
         if world > 1:
             dist.gather(wav, gathered, dst=0)
+        received["wav"] = wav
         return wav
+    step.outputs = lambda: {"wav": torch.cat(gathered) if gathered is not None else received["wav"]}
 
     def profiled():
         voc(mel)
@@ -251,13 +281,16 @@ def build_pipeline(args, world, rank, dev):
     def noise_rows(idx):        # CFM noise of the utterances `idx` (global indices; all inside this rank's shard)
         return noise[[i - lo_r for i in idx]]
 
+    received = {}               # the waveforms the caller of the step received, latest retired batch (rank 0: the whole job's)
+
     def step_sequential(last=False):
         if world > 1:
             sh = ShardedSynthesizer(tts, batch_size=16)
             h = sh.begin(text_all.tolist() if rank == 0 else None, cond_dev if rank == 0 else None, shapes, max_mel_tokens=M, noise_fn=noise_rows)
-            sh.finish(h)
+            received["wavs"] = sh.finish(h)
             return h["local"][0]
-        return tts.synthesize_batch(text, cond_dev, max_mel_tokens=M, noise=noise)[0]
+        received["wavs"] = tts.synthesize_batch(text, cond_dev, max_mel_tokens=M, noise=noise)
+        return received["wavs"][0]
 
     # Software pipeline ACROSS steps (default; indextts_amd/serving.py): `--decode-lanes` decode chains of consecutive batches in
     # flight at once -- latency-bound chains of 125 small launches per token that leave most CUs idle and interleave almost for
@@ -282,9 +315,10 @@ def build_pipeline(args, world, rank, dev):
 
     def retire(job):
         if sharder is not None:
-            sharder.finish(job)                        # gather to rank 0 + original order (collectives on the main thread)
+            received["wavs"] = sharder.finish(job)     # gather to rank 0 + original order (collectives on the main thread)
             return job["local"][0]
-        return job.result()[0]
+        received["wavs"] = job.result()
+        return received["wavs"][0]
 
     def step_pipelined(last=False):
         out = retire(pending.pop(0)) if len(pending) * per_step >= in_flight else None
@@ -421,6 +455,13 @@ def build_pipeline(args, world, rank, dev):
                             + ("; decode jobs and acoustic jobs take turns on the chip (exclusive)" if args.exclusive else "")
                             + "; every batch inside the timed region")
     step.flush = (lambda: None) if args.no_overlap else flush
+
+    def outputs():              # the [1, n] waveforms of the step, zero-padded into one array, and their lengths
+        w = [x.reshape(-1) for x in received["wavs"]]
+        n = max(x.numel() for x in w)
+        return {"wavs": torch.stack([torch.nn.functional.pad(x, (0, n - x.numel())) for x in w]),
+                "wav_lengths": torch.tensor([x.numel() for x in w], dtype=torch.float64)}
+    step.outputs = outputs
     nref = 16 if world > 1 else len(text)        # multi-rank: a shard goes through the pipeline in batches of 16
     step.reference = lambda: tts.synthesize_batch(text[:nref], cond_dev, max_mel_tokens=M, noise=noise[:nref])[0]
     step.flushed = flushed
@@ -469,11 +510,13 @@ def build_prompt_or_infer(args, world, rank, dev):
     spk = PromptAudio(_prompt_audio("bench/p16", 16000, secs), _prompt_audio("bench/p22", 22050, secs))
     emo = PromptAudio(_prompt_audio("bench/e16", 16000, secs))
     warnings.filterwarnings("ignore", category=RuntimeWarning)
+    received = {}
     if args.workload == "prompt":
         def step():
             feats = tts.prompt_encoders.encode(spk, emo)
-            c = PromptConditioning.from_features(tts.gpt, feats, emo_alpha=0.7)
+            c = received["cond"] = PromptConditioning.from_features(tts.gpt, feats, emo_alpha=0.7)
             return c.spk_cond_latent
+        step.outputs = lambda: {f: getattr(received["cond"], f) for f in PromptConditioning.FIELDS}
         desc = {"workload": f"prompt block (SURVEY 8f1): {secs:.0f} s speaker prompt + {secs:.0f} s emotion prompt -> PromptConditioning, full-size encoders "
                             "(w2v-bert-2.0 17 layers, RepCodec, CAMPPlus, mel, length regulator, conformer 6x512 + perceiver, emotion pair)",
                 "prompt_seconds": secs, "unit_note": "value = prompt encodes per second; ms_per_step = cache-miss latency of one request"}
@@ -485,7 +528,9 @@ def build_prompt_or_infer(args, world, rank, dev):
     def step():
         sr, a = tts.infer(spk, seg, None, emo_audio_prompt=emo, emo_alpha=0.7, **G)
         audio["s"] = a.shape[0] / sr
-        return torch.from_numpy(a.astype(np.float32))
+        received["wav"] = torch.from_numpy(a.astype(np.float32))
+        return received["wav"]
+    step.outputs = lambda: {"wav": received["wav"]}
     step()      # cold call: fills the prompt caches (its latency = the prompt workload's + one warm call)
     desc = {"workload": f"IndexTTS2.infer() reference defaults (infer_v2.py:714-722: beam-sample, num_beams 3, top_p 0.8, top_k 30, temperature 0.8, "
                         f"rep-penalty 10): ONE sentence of {args.text_tokens} text tokens, B = 1, {M} codes, warm prompt cache",
@@ -567,7 +612,12 @@ def main() -> int:
                          "CPU baseline / parity leg rounds the same way")
     ap.add_argument("--gemm", default="bf16x3", choices=["bf16x3", "f32"],
                     help="arithmetic of the GEMM-shaped passes (s2mel, latent pass): split-bf16 (default) or exact fp32 MFMA")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: larger outputs as a seeded sample of their elements); the same arguments give the same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(sys.argv[1:], args.gpus)
     longform = args.workload == "longform"
@@ -592,6 +642,8 @@ def main() -> int:
     if args.workload == "pipeline" and not longform and not args.batch and world >= 8:
         args.batch = 32       # BASELINE configs[3]: 256 utterances sharded data-parallel over 8 GPUs
     assert torch.cuda.is_available(), "bench.py needs the MI355X (no CPU fallback for the HIP path)"
+    # the random draws of the sampled workloads (infer_default: beam-sample, CFM noise) are inputs too: fixed, like the seeded synthetic ones
+    torch.manual_seed(0)
     # rehearsal knobs for a one-GPU box (the multi-rank code path end to end, ranks sharing the card over gloo):
     #   IDXTTS_DIST_BACKEND=gloo IDXTTS_FORCE_DEVICE=0 python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2
     backend = os.environ.get("IDXTTS_DIST_BACKEND", "nccl")
@@ -649,6 +701,8 @@ def main() -> int:
         elapsed = float(tmax.item())
     assert torch.isfinite(out).all()
     log(f"[bench] rank {rank}: {args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.outputs())
     if getattr(getattr(step, "pipe", None), "trace", None):
         for kind, a, b, rows in sorted(step.pipe.trace, key=lambda r: r[1]):
             if b >= t_start:

@@ -5,15 +5,16 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_contract():
+def test_bench_json_contract(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "4",
-           "--codes", "24", "--text-tokens", "40", "--prompt-frames", "120", "--cpu-codes", "64"]
+           "--codes", "24", "--text-tokens", "40", "--prompt-frames", "120", "--cpu-codes", "64", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -52,3 +53,7 @@ def test_bench_json_contract():
         assert cb["codes_first_difference_step"] is not None and cb["oracle_score_margin_at_that_step"] <= 2 * par["bf16"]["logit_bound"]
     em = d["exact_mode"]
     assert em["gpt_kv"] == "f32" and em["value"] > 0 and em["codes_match_rate"] >= 0.97 and em["max_abs_logit_diff"] <= em["logit_bound"]
+    # --dump-outputs: the last timed step's waveforms (4 utterances of exactly 24 codes = 41 mel frames x 256 samples)
+    wavs, lens = np.load(tmp_path / "out" / "wavs.npy"), np.load(tmp_path / "out" / "wav_lengths.npy")
+    assert wavs.dtype == np.float32 and wavs.shape == (4, 41 * 256) and np.isfinite(wavs).all() and np.abs(wavs).max() > 0
+    assert lens.dtype == np.float64 and lens.tolist() == [41 * 256] * 4
