@@ -136,9 +136,11 @@ struct CondBuf {
   size_t bytes;
 };
 
-int embed_ksplit(int M, int D, int K) {
+// The K partition of the embed GEMM is a function of D and K alone (the split a single 128-row tile would get): a row's partial
+// sums, and the order the row norm adds them in, must not depend on how many rows the batch has beside it.
+int embed_ksplit(int D, int K) {
   const int ksteps = cdiv(cdiv(K, 16), 2);
-  const int tiles = cdiv(M, 128) * cdiv(D, 128);
+  const int tiles = cdiv(D, 128);
   int ks = std::max(1, std::min(64, 512 / std::max(1, tiles)));
   ks = std::min(ks, ksteps);
   const int per = cdiv(ksteps, ks);
@@ -152,7 +154,7 @@ CondBuf carve(const CondModel& m, void* ws, int B, int T) {
   b.T2 = (T - 3) / 2 + 1;
   const size_t M = (size_t)B * b.T2, Mc = (size_t)B * (n + b.T2), Ml = (size_t)B * n;
   const int K = D * m.F2;
-  b.ksplit = embed_ksplit((int)M, D, K);
+  b.ksplit = embed_ksplit(D, K);
   Carver k(ws);
   b.a = k.take<float>(M * K);
   b.slab = k.take<float>((size_t)b.ksplit * M * D);
