@@ -274,6 +274,36 @@ size_t idxtts_gpt_beam_workspace_bytes(const idxtts_ctx* ctx, int B, int num_bea
 int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
                              float repetition_penalty, const idxtts_beam* beam, long long* codes, int* n_steps, void* workspace,
                              size_t workspace_bytes, int use_graph, void* stream);
+/* ---- GPT decode session (continuous batching) ----
+ * Stands in for the accel engine's per-sequence bookkeeping -- `context_lens` per sequence in the decode step and a KV allocation per
+ * sequence that is taken when a sequence is admitted and given back when it finishes (accel_engine.py:154-212,
+ * KVCacheManager.allocate / remove_seq in kv_manager.py:130-202) -- with a fixed set of `slots` decode rows, one KV region each.
+ * Greedy only (the semantics of idxtts_gpt_generate).  A slot retires when it samples stop_mel_token (recorded) or at its own cap;
+ * rows keep stepping on their own, so requests can be admitted into free slots between steps.
+ * Determinism: a request's codes equal, bit for bit, row 0 of idxtts_gpt_generate on `slots` copies of its prompt with no left
+ * padding (for a bf16 KV cache in split-bf16 GEMM mode: a reference batch of slots * (P + 1) >= 256 prefill rows), whatever else is in
+ * flight, whenever it was admitted and whichever slot it has.  Results can depend on `slots` (decode attention key split, decode GEMV).
+ * The caller owns the workspace (idxtts_gpt_session_workspace_bytes); the session lives in it until _release or the next _init on
+ * it.  The KV format and the GEMM mode must stay as they were at _init. */
+size_t idxtts_gpt_session_workspace_bytes(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens);
+/* Prepares the workspace: every slot free.  max_prompt: longest prompt (P, the `tts_embeddings` rows) a request may have;
+ * max_new_tokens: largest per-request cap. */
+int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* Admits n requests into the free slots slot_ids (HOST int32 [n]): inputs_embeds device [n][ld_rows][d], request b's prompt in its
+ * first prompt_lens[b] rows (HOST int32 [n], 1 .. max_prompt); max_new_tokens: HOST int32 [n] caps (1 .. max_new_tokens of _init).
+ * Runs their prefill and first token. */
+int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                             const int* slot_ids, const int* max_new_tokens, void* workspace, void* stream);
+/* Runs n_steps decode steps for every live slot (a captured hipGraph is replayed when use_graph), then reports the slots that hold a
+ * finished request not read yet: finished_slots HOST int32 [slots] (may be NULL), *n_finished. */
+int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* finished_slots, int* n_finished, void* workspace,
+                            void* stream);
+/* Copies a finished slot's codes (up to and including the stop token) to codes (device int64, >= *n_codes entries: at most
+ * max_new_tokens), sets *n_codes (host) and frees the slot. */
+int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_codes, void* workspace, void* stream);
+/* Forgets the session on this workspace (and its captured step); the caller may then free or reuse the workspace. */
+int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace);
 /* Latent pass: full causal forward over emb [B][S][d]; latent[b][i] = final_norm(ln_f(h[b][mel_start + i])), i < M.
  * pad_left: optional HOST int32 [B], leading rows of each sequence that are padding (masked as keys), so rows with
  * shorter texts can share a batch and still reproduce the reference's per-utterance (B=1) result. */

@@ -438,6 +438,50 @@ int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const 
   API_END
 }
 
+size_t idxtts_gpt_session_workspace_bytes(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens) {
+  if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
+  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
+  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens) : 0;
+}
+
+int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                             const int* slot_ids, const int* max_new_tokens, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* finished_slots, int* n_finished, void* workspace,
+                            void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_step(workspace, n_steps, use_graph, finished_slots, n_finished, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_codes, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_read(workspace, slot, codes, n_codes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_release(workspace);
+  API_END
+}
+
 int idxtts_gpt_latent(idxtts_ctx* ctx, const float* emb, const int* pad_left, int B, int S, int mel_start, int M, float* latent,
                       void* workspace, size_t workspace_bytes, void* stream) {
   API_BEGIN

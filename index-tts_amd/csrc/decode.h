@@ -10,6 +10,16 @@ struct DecodeState {   // device-resident per-generation scalars (replay-friendl
   unsigned arrive;   // workgroups of the fused sample + embed + advance launch that have finished (0 between launches)
 };
 
+// One row of a decode session (continuous batching, gpt.hip "decode session"): every slot carries its own step scalars, so rows
+// can be admitted and retired between steps while the captured step graph stays valid.
+struct SlotState {
+  int pos;        // keys already cached for this slot (= KV index of the token being processed)
+  int mel_pos;    // mel_pos_embedding row of that token (0, 2, 3, 4, ... as in DecodeState)
+  int step;       // column of `codes` the sampler writes next; once the slot has ended: the number of codes it produced
+  int max_step;   // token cap of the request in this slot
+  int live;       // 1 while the slot decodes; cleared by the sampler on the stop token or at max_step (0 = free or ended)
+};
+
 struct DecodeAttnArgs {
   const float* qkv_part = nullptr; int parts = 0; int part_rows = 0;   // [parts][part_rows][3d] c_attn split-K slab
   const float* qkv_bias = nullptr;                                      // [3d]
@@ -29,6 +39,9 @@ struct DecodeAttnArgs {
   int nsplit = 1;
   float* part = nullptr;        // [B][H][nsplit][66]
   unsigned* cnt = nullptr;      // [B][H] arrival counters: 0 on entry, left at 0
+  // Decode session: per-row positions slot[b].pos instead of st->pos; a row whose slot is not live returns at once (zero output,
+  // no KV traffic).  The key split keeps its rule: pieces start at the row's first key, nsplit = decode_attn_nsplit(B, H).
+  const SlotState* slot = nullptr;
 };
 int decode_attn_nsplit(int B, int H);
 int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream);
@@ -59,6 +72,12 @@ struct SampleArgs {
   } embed;
 };
 int sample_greedy_forward(const SampleArgs& a, hipStream_t stream);
+// Greedy sampler of a decode session (always the fused tail: a.embed.x_row or a.embed.x_frag set; a.st / a.embed.st_rw unused,
+// a.finished unused): one workgroup per slot -- slot_ids[i] for i < n, or every slot 0..a.B-1 when slot_ids is null.  A slot that is
+// not live returns at once.  Otherwise it samples row `slot` of the logits, writes codes[slot][step], updates seen, and either ends the
+// slot (stop token or step + 1 == max_step: live = 0, step = codes produced) or writes the slot's next input row with mel_pos + 1 and
+// advances its own pos / mel_pos / step.
+int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_ids, int n, hipStream_t stream);
 
 // Multinomial sampling of the next token (HF _sample, transformers_generation_utils.py:3222-3250, with the warpers of
 // 1036-1044): repetition penalty -> / temperature -> top-k (ties at the threshold kept) -> top-p (ascending sort, softmax,
@@ -96,6 +115,18 @@ int advance_state(DecodeState* st, hipStream_t stream);
 // qkv [B][S][3d] -> caches, positions [0, S).  kv16: the caches hold bf16 and the k / v columns of qkv are rounded IN PLACE, so the
 // prefill attention that follows sees exactly the keys and values later steps read from the cache
 int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, int H, int S, int Smax, int d, hipStream_t stream);
+// Decode-session admission: the same for a right-padded prefill of n rows whose cache rows are the slots slot_ids[b]: positions
+// [0, len[b]) of row b go to slot slot_ids[b] (kcache / vcache laid out for `slots` rows); k / v columns rounded in place for kv16
+int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
+                   const int* len, hipStream_t stream);
+// Decode-session admission, input rows of the prefill: x[b][s] = emb[b][s] for s < P[b] (emb [n][ld_rows][d]), mel_emb[start] +
+// mel_pos[0] at s = P[b], 0 after it (right padding); every row S long
+int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P, int n, int S, int d, const float* mel_emb,
+                          const float* mel_pos, int start_token, hipStream_t stream);
+// Decode-session admission, per admitted row b: reset slot slot_ids[b] -- seen row = {1, start_token}, state {pos = P[b], mel_pos = 1,
+// step = 0, max_step = cap[b], live = 1} -- and copy the prefill's last valid row x[b][P[b]] (x [n][S][d]) to x_last[slot]
+int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
+                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream);
 constexpr int GATHER_MAX_TABLES = 5;
 struct GatherArgs {
   float* out = nullptr; int ld_out = 0; int d = 0;

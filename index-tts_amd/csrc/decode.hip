@@ -86,7 +86,15 @@ __device__ __forceinline__ void decode_attn_finish(const DecodeAttnArgs& p, cons
 
 // NT threads per workgroup: NT / 16 key groups in the P.V phase, NT keys per pass of the score phase.  512 threads at <= 128
 // VGPRs (two workgroups per CU) halve the number of dependent load -> use passes of the 256-thread form.
-template <int NT>
+// Output of a row whose session slot is not live: zeros, written once per (row, head)
+__device__ __forceinline__ void decode_attn_dead(const DecodeAttnArgs& p, const int b, const int h, const int z, const int tid) {
+  if (z != 0 || tid >= 64) return;
+  if (p.out_row) p.out_row[(size_t)b * p.d + h * 64 + tid] = 0.f;
+  else p.out[frag_index(b, h * 64 + tid, p.d >> 4)] = 0.f;
+}
+
+// SLOTS: decode session (DecodeAttnArgs::slot) -- the row's own position, dead rows return at once
+template <int NT, bool SLOTS>
 __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(const DecodeAttnArgs p) {
   constexpr int NW = NT / 64, NG = NT / 16;
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -98,7 +106,13 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(co
   float* pr = sm + 256 + NG * 64;   // [Smax] scores / probabilities
 
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int pos = p.st->pos;                  // index of the token being processed = keys already cached
+  int pos;                                    // index of the token being processed = keys already cached
+  if constexpr (SLOTS) {
+    if (!p.slot[b].live) { decode_attn_dead(p, b, h, blockIdx.z, tid); return; }
+    pos = p.slot[b].pos;
+  } else {
+    pos = p.st->pos;
+  }
   const int d = p.d, Smax = p.Smax;
   float* kc = static_cast<float*>(p.kcache) + (size_t)(b * p.H + h) * 16 * Smax * 4;
   float* vc = static_cast<float*>(p.vcache) + (size_t)(b * p.H + h) * Smax * 64;
@@ -245,7 +259,7 @@ __device__ __forceinline__ unsigned bf16_rne_bits(float f) {
 __device__ __forceinline__ float bf16_round_f32(float f) { return __uint_as_float(bf16_rne_bits(f) << 16); }
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-template <int NT>
+template <int NT, bool SLOTS>
 __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(const DecodeAttnArgs p) {
   constexpr int NW = NT / 64, NG = NT / 8;
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -257,7 +271,13 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(
   float* pr = sm + 256 + NG * 64;   // [Smax] scores / probabilities
 
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int pos = p.st->pos;
+  int pos;
+  if constexpr (SLOTS) {
+    if (!p.slot[b].live) { decode_attn_dead(p, b, h, blockIdx.z, tid); return; }
+    pos = p.slot[b].pos;
+  } else {
+    pos = p.st->pos;
+  }
   const int d = p.d, Smax = p.Smax;
   u32x4* const kc = static_cast<u32x4*>(p.kcache) + (size_t)(b * p.H + h) * 8 * Smax;      // granule (c, s) at c * Smax + s
   u32x4* const vc = static_cast<u32x4*>(p.vcache) + (size_t)(b * p.H + h) * Smax * 8;      // granule (s, c) at s * 8 + c
@@ -415,23 +435,31 @@ int decode_attn_nsplit(int B, int H) {
 }
 
 int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
-  IDX_CHECK(a.qkv_part && a.kcache && a.vcache && (a.out || a.out_row) && a.st, "null pointer");
+  IDX_CHECK(a.qkv_part && a.kcache && a.vcache && (a.out || a.out_row) && (a.st || a.slot), "null pointer");
   IDX_CHECK(a.d == a.H * 64, "head_dim must be 64");
   constexpr int nt = 512;      // 512 threads measured 4 % faster than 256 (profiles/README.md)
   const size_t lds = (size_t)(256 + (nt / (a.kv16 ? 8 : 16)) * 64 + a.Smax) * sizeof(float);
   IDX_CHECK(lds <= 128 * 1024, "Smax too large for the LDS score buffer");
   static bool attr_set = false;
   if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn16_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_kernel<512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn16_kernel<512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_kernel<512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn16_kernel<512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     attr_set = true;
   }
   IDX_CHECK(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.cnt)), "key split: 1..16 pieces, partial buffer and counters");
   // algorithmic bytes: K and V of every cached position, all heads: B * S * 2 * d * (4 | 2) (S as the host knows it: pos_hint)
   static const int cat = prof_register("decode_attn_kernel"), cat16 = prof_register("decode_attn16_kernel");
   ProfScope prof(a.kv16 ? cat16 : cat, stream, 0.0, (a.kv16 ? 4.0 : 8.0) * a.B * (double)a.pos_hint * a.d);
-  if (a.kv16) hipLaunchKernelGGL(decode_attn16_kernel<512>, dim3(a.H, a.B, a.nsplit), dim3(512), lds, stream, a);
-  else hipLaunchKernelGGL(decode_attn_kernel<512>, dim3(a.H, a.B, a.nsplit), dim3(512), lds, stream, a);
+  const dim3 grid(a.H, a.B, a.nsplit);
+  if (a.slot) {
+    if (a.kv16) hipLaunchKernelGGL((decode_attn16_kernel<512, true>), grid, dim3(512), lds, stream, a);
+    else hipLaunchKernelGGL((decode_attn_kernel<512, true>), grid, dim3(512), lds, stream, a);
+  } else {
+    if (a.kv16) hipLaunchKernelGGL((decode_attn16_kernel<512, false>), grid, dim3(512), lds, stream, a);
+    else hipLaunchKernelGGL((decode_attn_kernel<512, false>), grid, dim3(512), lds, stream, a);
+  }
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -458,6 +486,57 @@ __device__ __forceinline__ void embed_row_pl(float* x_row, float* x_stats, const
       if ((e & 15) == 0) *reinterpret_cast<float2*>(&x_stats[((size_t)(e >> 4) * R + b) * 2]) = make_float2(mean, q);
     }
   }
+}
+
+// Row b of the greedy sampler (sample_greedy_kernel's reduction, for the session sampler below): logits (split-K partial sum + bias, optionally recorded) -> repetition penalty -> argmax, the first
+// maximum on ties.  The result is valid in thread 0 only (rv / ri: [16] of shared scratch).
+__device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int b, const int tid, float* rv, int* ri, float& best_out,
+                                                  int& bidx_out) {
+  const int wave = tid >> 6, lane = tid & 63;
+  const int V = p.V;
+  float best = -INFINITY;
+  int bidx = 0x7fffffff;
+  const unsigned char* seen = p.seen + (size_t)b * V;
+  const size_t sst = (size_t)p.part_rows * V;
+  const float* prow = p.part + (size_t)b * V;
+  for (int v0 = tid; v0 < V; v0 += 4096) {       // 4 vocabulary entries per trip, all their slab loads in flight together
+    float l4[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int v = v0 + 1024 * u;
+      l4[u] = (v < V && p.bias) ? p.bias[v] : 0.0f;
+    }
+    for (int s = 0; s < p.parts; ++s) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int v = v0 + 1024 * u;
+        if (v < V) l4[u] += prow[(size_t)s * sst + v];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int v = v0 + 1024 * u;
+      if (v >= V) continue;
+      float l = l4[u];
+      if (p.logits_out) p.logits_out[(size_t)b * V + v] = l;
+      if (seen[v]) l = l < 0.f ? l * p.penalty : l / p.penalty;
+      if (l > best) { best = l; bidx = v; }      // ascending v per thread: strict > keeps the first maximum
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bidx, off);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  if (lane == 0) { rv[wave] = best; ri[wave] = bidx; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 16; ++w)
+      if (rv[w] > best || (rv[w] == best && ri[w] < bidx)) { best = rv[w]; bidx = ri[w]; }
+  }
+  best_out = best;
+  bidx_out = bidx;
 }
 
 __global__ __launch_bounds__(1024) void sample_greedy_kernel(const SampleArgs p) {
@@ -541,6 +620,53 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream) {
   static const int cat = prof_register("sample_greedy_kernel");
   ProfScope prof(cat, stream, 0.0, 4.0 * a.B * (double)a.V * (a.parts + 1));
   hipLaunchKernelGGL(sample_greedy_kernel, dim3(a.B), dim3(1024), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// -------------------------------------------------------------------------------------------------
+// Decode session (continuous batching): the greedy tail with per-slot state (SlotState, decode.h)
+__global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, SlotState* slots, const int* slot_ids) {
+  __shared__ float rv[16];
+  __shared__ int ri[16];
+  __shared__ int s_tok, s_mp, s_end;
+  const int b = slot_ids ? slot_ids[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
+  SlotState* const ss = slots + b;
+  if (!ss->live) return;      // free or ended slot: nothing is read or written (workgroup-uniform)
+  float best;
+  int bidx;
+  greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
+  if (tid == 0) {
+    const int tok = bidx, step = ss->step;
+    p.codes[(size_t)b * p.codes_ld + step] = tok;
+    p.seen[(size_t)b * p.V + tok] = 1;
+    p.cur_tok[b] = tok;
+    s_tok = tok;
+    s_mp = ss->mel_pos + 1;
+    s_end = tok == p.stop_token || step + 1 >= ss->max_step;
+  }
+  __syncthreads();
+  if (s_end) {      // the stop token (recorded) or the slot's cap: the slot retires; step = codes produced
+    if (tid == 0) { ss->step += 1; ss->live = 0; }
+    return;
+  }
+  if (p.embed.x_frag) {
+    const int d = p.embed.d, tok = s_tok;
+    for (int e = tid; e < d; e += 1024) p.embed.x_frag[frag_index(b, e, d >> 4)] = p.embed.mel_emb[(size_t)tok * d + e] + p.embed.mel_pos[(size_t)s_mp * d + e];
+  } else {
+    embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, s_tok, s_mp, tid);
+  }
+  if (tid == 0) { ss->pos += 1; ss->mel_pos += 1; ss->step += 1; }      // this slot's scalars: nobody else reads them in this launch
+}
+
+int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_ids, int n, hipStream_t stream) {
+  IDX_CHECK(a.part && a.seen && a.codes && a.cur_tok && slots && (a.embed.x_row || a.embed.x_frag) && a.embed.mel_emb && a.embed.mel_pos,
+            "null pointer");
+  IDX_CHECK(!a.forced && !a.logits_out, "decode sessions are greedy only");
+  if (n <= 0) return 0;
+  static const int cat = prof_register("sample_slots_kernel");
+  ProfScope prof(cat, stream, 0.0, 4.0 * n * (double)a.V * (a.parts + 1));
+  hipLaunchKernelGGL(sample_slots_kernel, dim3(n), dim3(1024), 0, stream, a, slots, slot_ids);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -757,6 +883,88 @@ int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, in
   ProfScope prof(cat, stream, 0.0, (kv16 ? 28.0 : 16.0) * B * (double)S * d);
   if (kv16) hipLaunchKernelGGL(kv_store_prefill_kernel<true>, dim3(S, B), dim3(256), 0, stream, qkv, kcache, vcache, B, H, S, Smax, d);
   else hipLaunchKernelGGL(kv_store_prefill_kernel<false>, dim3(S, B), dim3(256), 0, stream, qkv, kcache, vcache, B, H, S, Smax, d);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// decode-session admission: prefill row b (right-padded, S positions) -> the cache rows of slot slot_ids[b], positions [0, len[b])
+template <bool KV16>
+__global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* kcache, void* vcache, int H, int S, int Smax, int d,
+                                                             const int* slot_ids, const int* len) {
+  const int s = blockIdx.x, b = blockIdx.y;
+  const int slot = slot_ids[b];
+  const bool keep = s < len[b];
+  float* row = qkv + ((size_t)b * S + s) * 3 * d;
+  for (int col = threadIdx.x; col < d; col += 256) {
+    const int h = col >> 6, dd = col & 63;
+    if (KV16) {      // every row is rounded (as kv_store_prefill does): the prefill attention sees the cached values
+      const unsigned kb = bf16_rne_bits(row[d + col]), vb = bf16_rne_bits(row[2 * d + col]);
+      if (keep) {
+        static_cast<unsigned short*>(kcache)[(((size_t)(slot * H + h) * 8 + (dd >> 3)) * Smax + s) * 8 + (dd & 7)] = (unsigned short)kb;
+        static_cast<unsigned short*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = (unsigned short)vb;
+      }
+      row[d + col] = __uint_as_float(kb << 16);
+      row[2 * d + col] = __uint_as_float(vb << 16);
+    } else if (keep) {
+      static_cast<float*>(kcache)[(((size_t)(slot * H + h) * 16 + (dd >> 2)) * Smax + s) * 4 + (dd & 3)] = row[d + col];
+      static_cast<float*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = row[2 * d + col];
+    }
+  }
+}
+
+int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
+                   const int* len, hipStream_t stream) {
+  IDX_CHECK(S <= Smax, "prefill longer than the cache");
+  IDX_CHECK(slot_ids && len, "null pointer");
+  if (n <= 0) return 0;
+  static const int cat = prof_register("kv_store_slots_kernel");
+  ProfScope prof(cat, stream, 0.0, (kv16 ? 28.0 : 16.0) * n * (double)S * d);
+  if (kv16) hipLaunchKernelGGL(kv_store_slots_kernel<true>, dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len);
+  else hipLaunchKernelGGL(kv_store_slots_kernel<false>, dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// decode-session admission: the right-padded prefill input (the same values generate() builds for an unpadded row)
+__global__ __launch_bounds__(256) void session_prefill_input_kernel(float* x, const float* emb, int ld_rows, const int* P, int S, int d,
+                                                                    const float* mel_emb, const float* mel_pos, int start_token) {
+  const int s = blockIdx.x, b = blockIdx.y, Pb = P[b];
+  float* out = x + ((size_t)b * S + s) * d;
+  for (int e = threadIdx.x; e < d; e += 256) {
+    float v = 0.f;
+    if (s < Pb) v = emb[((size_t)b * ld_rows + s) * d + e];
+    else if (s == Pb) { v += mel_emb[(size_t)start_token * d + e]; v += mel_pos[e]; }      // gather_sum_rows' order (generate)
+    out[e] = v;
+  }
+}
+
+int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P, int n, int S, int d, const float* mel_emb,
+                          const float* mel_pos, int start_token, hipStream_t stream) {
+  IDX_CHECK(x && emb && P && mel_emb && mel_pos, "null pointer");
+  if (n <= 0) return 0;
+  static const int cat = prof_register("session_prefill_input_kernel");
+  ProfScope prof(cat, stream, 0.0, 8.0 * n * (double)S * d);
+  hipLaunchKernelGGL(session_prefill_input_kernel, dim3(S, n), dim3(256), 0, stream, x, emb, ld_rows, P, S, d, mel_emb, mel_pos, start_token);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// decode-session admission: reset the admitted slots, stage the prefill's last valid row of each for the first-token head
+__global__ __launch_bounds__(256) void session_reset_slots_kernel(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last,
+                                                                  const float* x, int S, int d, const int* slot_ids, const int* P, const int* cap) {
+  const int b = blockIdx.x, slot = slot_ids[b], Pb = P[b];
+  unsigned char* sr = seen + (size_t)slot * V;
+  for (int v = threadIdx.x; v < V; v += 256) sr[v] = (v == 1 || v == start_token) ? 1 : 0;      // input_ids = [1 ... 1, start]
+  const float* src = x + ((size_t)b * S + Pb) * d;
+  for (int e = threadIdx.x; e < d; e += 256) x_last[(size_t)slot * d + e] = src[e];
+  if (threadIdx.x == 0) slots[slot] = SlotState{Pb, 1, 0, cap[b], 1};
+}
+
+int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
+                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream) {
+  IDX_CHECK(slots && seen && x_last && x && slot_ids && P && cap, "null pointer");
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(session_reset_slots_kernel, dim3(n), dim3(256), 0, stream, slots, seen, V, start_token, x_last, x, S, d, slot_ids, P, cap);
   IDX_LAUNCH_CHECK();
   return 0;
 }

@@ -1,5 +1,6 @@
 #pragma once
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -44,6 +45,7 @@ struct GPTModel : ModelBase {
   std::atomic<unsigned> oob_next{0};
   ~GPTModel() override {
     for (GraphSlot& g : graph_cache) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
+    for (auto& kv : sessions) kv.second.drop_graph();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 
@@ -62,6 +64,7 @@ struct GPTModel : ModelBase {
     DecodeState* state;
     long long* codes;                         // [B][max_new] generated codes of the call in flight (copied to the caller's tensor at the end)
     size_t bytes;
+    SlotState* slots = nullptr;               // decode session only (carve_session): per-row step scalars; the step uses them, not `state`
   };
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
@@ -81,9 +84,14 @@ struct GPTModel : ModelBase {
   //   (ln_g, ln_b, W, b) of c_attn / c_fc -> (1, 0, Q(diag(ln_g) W), ln_b . W + b);  c_proj, mlp.c_proj, mel_head -> Q(W).
   // Every consumer (prefill, latent pass, decode) is then packed from these tensors, so they all run the SAME model.
   int quantize_weights(std::map<std::string, HostTensor>& t, int fmt);
-  Buffers carve(void* ws, int B, int S, int max_new) const;
+  // prefill_rows: rows of the prefill / latent activations (0 = B * S)
+  Buffers carve(void* ws, int B, int S, int max_new, size_t prefill_rows = 0) const;
   size_t workspace_bytes(int B, int S, int max_new) const;
-  int layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st);
+  struct KvScatter {      // decode-session admission: prefill row b's positions [0, len[b]) go to the cache rows of slot slot_ids[b]
+    const int* slot_ids = nullptr; const int* len = nullptr; int n = 0; int slots = 0;
+  };
+  int layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter = nullptr);
+  int head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st);      // ln_f -> final_norm -> mel_head
   int head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, long long* codes, int codes_ld,
                       float* logits_out, hipStream_t st);
   int decode_step(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base, hipStream_t st);
@@ -101,6 +109,42 @@ struct GPTModel : ModelBase {
                     long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st);
   int latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws, size_t ws_bytes,
              hipStream_t st);
+
+  // ---- decode session (continuous batching): `slots` decode rows with one KV region each; requests are admitted into free slots
+  // between steps, every slot advances on its own (SlotState), a slot ends on the stop token or its own cap and is read out.  Greedy
+  // only.  A row's codes equal row 0 of generate() on `slots` copies of it (pad_left 0): every kernel on its path is chosen from the
+  // session's properties (slots, KV format, GEMM mode) alone, never from how many rows are admitted at once.
+  struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
+    int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv16 = 0, gemm_mode = 0;
+    size_t ws_bytes = 0;
+    std::vector<char> busy;           // admitted and not yet read
+    bool warm = false;                // one step has run eagerly (first-use function attributes are set outside a capture)
+    int geom = -1;                    // decode geometry the graph was captured under
+    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+    void drop_graph() {
+      if (exec) (void)hipGraphExecDestroy(exec);
+      if (graph) (void)hipGraphDestroy(graph);
+      exec = nullptr; graph = nullptr;
+    }
+  };
+  std::map<void*, Session> sessions;
+  std::mutex session_mu;
+  struct SessionBuffers {
+    Buffers w;                        // decode buffers for `slots` rows (w.slots set) + the admission prefill's activations
+    float* x_last;                    // [slots][d] last valid prefill row of each admitted request (first-token head input)
+    int *ids, *plen, *klen, *cap;     // admission staging: slot ids, prompt lengths (prefill rows: -1 = padding row), P + 1, caps
+    size_t bytes;
+  };
+  size_t session_prefill_rows(int slots, int max_prompt) const { return (size_t)slots * (max_prompt + 1) + 256; }
+  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new) const;
+  size_t session_workspace_bytes(int slots, int max_prompt, int max_new) const;
+  Session* find_session(void* ws);
+  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st);
+  int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
+                    const int* max_new, hipStream_t st);
+  int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
+  int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
+  int session_release(void* ws);
   int embed(float* out, int rows, const int* text_ids, const int* text_pos_idx, const int* mel_ids, const int* mel_pos_idx,
             const float* extra, const int* extra_idx, hipStream_t st);
 };

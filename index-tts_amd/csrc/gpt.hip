@@ -242,11 +242,11 @@ struct Carver {
   }
 };
 
-GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new) const {
+GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new, size_t prefill_rows) const {
   const int d = cfg.model_dim, V = cfg.number_mel_codes, L = cfg.layers;
   Buffers b;
   Carver c(ws);
-  const size_t rows = (size_t)B * S;
+  const size_t rows = prefill_rows ? prefill_rows : (size_t)B * S;
   b.x = c.take<float>(rows * d);
   b.h = c.take<float>(rows * d);
   b.qkv = c.take<float>(rows * 3 * d);
@@ -290,7 +290,7 @@ GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new) const {
 size_t GPTModel::workspace_bytes(int B, int S, int max_new) const { return carve(nullptr, B, S, max_new).bytes; }
 
 // one transformer layer over M = B*S token rows (prefill / latent pass)
-int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st) {
+int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter) {
   // The prefill (store_kv) that fills an fp32 KV cache feeds an exact greedy decode: exact fp32 MFMA.  With a bf16 cache its keys and
   // values are rounded to 8 bits on the way in (relative 2^-9), which buries the split-bf16 GEMM's 2^-16 product error: that prefill
   // runs like the latent pass, mode-dependent (split-bf16 by default, 3-4 x the exact kernel's rate).
@@ -304,7 +304,11 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   GemmArgs g;
   g.x = w.h; g.ldx = d; g.y = w.qkv; g.ldy = 3 * d; g.M = M;
   if (mm(L.attn_l, g)) return 1;
-  if (store_kv) {
+  if (store_kv && scatter) {      // decode-session admission: the rows go to their slots' cache regions
+    const size_t per_layer = kv_layer_bytes(scatter->slots, w.Smax);
+    if (kv_store_slots(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, scatter->n, cfg.heads, S, w.Smax, d,
+                       scatter->slot_ids, scatter->len, st)) return 1;
+  } else if (store_kv) {
     const size_t per_layer = kv_layer_bytes(B, w.Smax);
     if (kv_store_prefill(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, B, cfg.heads, S, w.Smax, d, st)) return 1;
   }
@@ -337,9 +341,8 @@ thread_local int tl_prof_pos = 0;
 static thread_local const long long* tl_forced = nullptr;      // teacher-forced generation in flight: [B][max_new] tokens fed back instead of the argmax
 static thread_local int tl_forced_ld = 0;      // keys the eager decode step in flight reads (0 while a captured graph replays)
 
-// head on B rows: ln_f -> final_norm (one rows_norm launch, output as fragment images) -> mel_head -> greedy sampler
-int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, long long* codes,
-                              int codes_ld, float* logits_out, hipStream_t st) {
+// head on B rows: ln_f -> final_norm (one rows_norm launch, output as fragment images) -> mel_head -> w.logits
+int GPTModel::head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st) {
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
   const bool pl = use_pl(B);
   RowsNormArgs n;
@@ -356,12 +359,26 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
     hv.xf = w.hd; hv.rows = B; hv.bias = head_b; hv.y = w.logits; hv.ldy = V;
     if (gemv_fx_forward(head_g, hv, st)) return 1;
   }
+  return 0;
+}
+
+// head on B rows -> greedy sampler (or the sampling / beam stages of the generation in flight)
+int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, long long* codes,
+                              int codes_ld, float* logits_out, hipStream_t st) {
+  const int V = cfg.number_mel_codes, d = cfg.model_dim;
+  const bool pl = use_pl(B);
+  if (head_logits(w, B, x, ldx, x_frag, st)) return 1;
   if (tl_beam) return beam_scores_forward(*tl_beam, st) || beam_select_forward(*tl_beam, st) || beam_reorder_forward(*tl_beam, st);
   SampleArgs s;
   s.part = w.logits; s.parts = 1; s.part_rows = B; s.bias = nullptr; s.logits_out = logits_out;
   s.seen = w.seen; s.finished = w.finished; s.codes = codes; s.codes_ld = codes_ld; s.cur_tok = w.cur_tok;
   s.st = w.state; s.B = B; s.V = V; s.stop_token = cfg.stop_mel_token; s.penalty = penalty;
   s.forced = tl_forced; s.forced_ld = tl_forced_ld;
+  if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
+    if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
+    s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d;
+    return sample_slots_forward(s, w.slots, nullptr, B, st);
+  }
   if (fused_tail(B)) {      // the sampler's workgroups also write the next step's input and advance the step scalars
     if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
     s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d; s.embed.st_rw = w.state;
@@ -390,7 +407,7 @@ bool GPTModel::fused_tail(int B) const { (void)B; return samp.mode == 0 && !tl_b
 int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base, hipStream_t st) {
   const int d = cfg.model_dim, T = d / 16;
   const size_t per_layer = kv_layer_bytes(B, w.Smax);
-  const bool fused = fused_tail(B);
+  const bool fused = w.slots || fused_tail(B);
   if (!fused && embed_step_pl(w.xrow, w.stats, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
     const GPTLayer& L = layers[li];
@@ -402,7 +419,7 @@ int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, long long* 
     da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
     da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out_row = w.attrow; da.kstart = w.kstart;
     da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
-    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt;
+    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
     da.pos_hint = tl_prof_pos;
     if (decode_attn_forward(da, st)) return 1;
     GemvPLArgs pa;      // x += c_proj(attn) + b (in place: a lane reads and writes only its own elements of x), + the row statistics of the new x
@@ -427,7 +444,7 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, long long* cod
   if (use_pl(B)) return decode_step_pl(w, B, penalty, codes, codes_ld, logits_base, st);
   const int d = cfg.model_dim;
   const size_t per_layer = kv_layer_bytes(B, w.Smax);
-  const bool fused = fused_tail(B);      // greedy: the previous step's sampler has written this step's x and advanced the step scalars
+  const bool fused = w.slots || fused_tail(B);      // greedy: the previous step's sampler has written this step's x and advanced the step scalars
   if (!fused && embed_step(w.xd, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
     const GPTLayer& L = layers[li];
@@ -438,7 +455,7 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, long long* cod
     da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
     da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out = w.attd; da.kstart = w.kstart;
     da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
-    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt;
+    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
     da.pos_hint = tl_prof_pos;
     if (decode_attn_forward(da, st)) return 1;
     GemvFXArgs pa;      // x += c_proj(attn) + b  (in place: a thread reads and writes only its own element of x)
@@ -633,6 +650,194 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   }
   if (every_row_stops && !forced) n_steps = worst;      // forced: every step that ran is reported (codes = the rows' own choices)
   *n_steps_out = n_steps;
+  return 0;
+}
+
+// ---- decode session (continuous batching; gpt.h) ----
+// Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
+// activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
+// the staged last prefill rows and the admission's index arrays.
+GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new) const {
+  SessionBuffers sb;
+  sb.w = carve(ws, slots, max_prompt + 1, max_new, session_prefill_rows(slots, max_prompt));
+  Carver c(ws);
+  c.off = sb.w.bytes;
+  sb.w.slots = c.take<SlotState>(slots);
+  sb.x_last = c.take<float>((size_t)slots * cfg.model_dim);
+  const size_t pre = session_prefill_rows(slots, max_prompt);
+  sb.ids = c.take<int>(slots);
+  sb.plen = c.take<int>(pre);
+  sb.klen = c.take<int>(slots);
+  sb.cap = c.take<int>(slots);
+  sb.bytes = (c.off + 255) & ~(size_t)255;
+  return sb;
+}
+
+size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new) const {
+  return carve_session(nullptr, slots, max_prompt, max_new).bytes;
+}
+
+GPTModel::Session* GPTModel::find_session(void* ws) {
+  std::lock_guard<std::mutex> l(session_mu);
+  auto it = sessions.find(ws);
+  return it == sessions.end() ? nullptr : &it->second;
+}
+
+int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st) {
+  IDX_CHECK(ws, "null workspace");
+  IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
+  IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new);
+  const Buffers& w = sb.w;
+  const int d = cfg.model_dim;
+  IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
+  IDX_HIP(hipMemsetAsync(w.ksb_cnt, 0, (size_t)cdiv(d, 16) * sizeof(unsigned), st));
+  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, (size_t)slots * cfg.heads * sizeof(unsigned), st));
+  IDX_HIP(hipMemsetAsync(static_cast<char*>(ws) + w.frag_off, 0, w.frag_bytes, st));   // padding rows of the fragment images
+  IDX_HIP(hipMemsetAsync(w.slots, 0, slots * sizeof(SlotState), st));                // every slot free
+  IDX_HIP(hipMemsetAsync(sb.x_last, 0, (size_t)slots * d * sizeof(float), st));
+  IDX_HIP(hipMemsetAsync(w.xrow, 0, (size_t)slots * d * sizeof(float), st));
+  std::lock_guard<std::mutex> l(session_mu);
+  Session& s = sessions[ws];
+  s.drop_graph();
+  s = Session();
+  s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv16 = kv_fmt; s.gemm_mode = get_gemm_mode();
+  s.ws_bytes = ws_bytes;
+  s.busy.assign(slots, 0);
+  return 0;
+}
+
+int GPTModel::session_release(void* ws) {
+  std::lock_guard<std::mutex> l(session_mu);
+  auto it = sessions.find(ws);
+  IDX_CHECK(it != sessions.end(), "no decode session on this workspace");
+  it->second.drop_graph();
+  sessions.erase(it);
+  return 0;
+}
+
+int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
+                            const int* caps, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(inputs_embeds && prompt_lens && slot_ids && caps, "null pointer");
+  IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots rows");
+  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  GenScope gen_scope(this);
+  int pmax = 0;
+  std::vector<char> taken(s.slots, 0);
+  for (int b = 0; b < n; ++b) {
+    IDX_CHECK(slot_ids[b] >= 0 && slot_ids[b] < s.slots, "slot id out of range");
+    IDX_CHECK(!s.busy[slot_ids[b]] && !taken[slot_ids[b]], "slot is not free");
+    taken[slot_ids[b]] = 1;
+    IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
+    IDX_CHECK(caps[b] >= 1 && caps[b] <= s.max_new, "token cap out of range (1 .. max_new)");
+    pmax = std::max(pmax, prompt_lens[b]);
+  }
+  const int d = cfg.model_dim, V = cfg.number_mel_codes;
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  const Buffers& w = sb.w;
+  // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
+  // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
+  // exact kernel; with a bf16 cache in split-bf16 mode gemm_forward takes the split-bf16 kernel from 256 rows on, so the prefill is padded
+  // with zero rows (b >= n) to at least 256 rows -- every admission then runs the kernel a generate() batch of >= 256 prefill rows runs.
+  const int S = pmax + 1;
+  int rows = n;
+  if (kv_fmt && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
+  IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
+  std::vector<int> stage((size_t)3 * s.slots + rows, 0);      // ids | klen | cap | plen (one copy)
+  for (int b = 0; b < n; ++b) {
+    stage[b] = slot_ids[b];
+    stage[s.slots + b] = prompt_lens[b] + 1;
+    stage[2 * s.slots + b] = caps[b];
+  }
+  for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
+  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
+
+  if (session_prefill_input(w.x, inputs_embeds, ld_rows, sb.plen, rows, S, d, mel_emb, mel_pos, cfg.start_mel_token, st)) return 1;
+  KvScatter sc;
+  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots;
+  for (int li = 0; li < cfg.layers; ++li)
+    if (layer_full(li, w, rows, S, nullptr, true, st, &sc)) return 1;
+  if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, n, st)) return 1;
+  // first token of each admitted row: the head on all `slots` rows (the GEMV use_pl(slots) selects, as a generate() of `slots` rows),
+  // sampled for the admitted slots only; the sampler writes their first decode input
+  if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
+  SampleArgs sa;
+  sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
+  sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
+  if (use_pl(s.slots)) { sa.embed.x_row = w.xrow; sa.embed.x_stats = w.stats; } else sa.embed.x_frag = w.xd;
+  sa.embed.mel_emb = mel_emb; sa.embed.mel_pos = mel_pos; sa.embed.d = d;
+  if (sample_slots_forward(sa, w.slots, sb.ids, n, st)) return 1;
+  for (int b = 0; b < n; ++b) s.busy[slot_ids[b]] = 1;
+  return 0;
+}
+
+int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(n_steps >= 0, "n_steps");
+  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  GenScope gen_scope(this);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  const Buffers& w = sb.w;
+  const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
+  if (s.exec && s.geom != geom) s.drop_graph();
+  IDX_CHECK(st != nullptr || !use_graph, "graph replay needs a stream other than the legacy default stream");
+  const bool graph_ok = use_graph && !prof_enabled();
+  for (int k = 0; k < n_steps; ++k) {
+    if (graph_ok && s.warm && !s.exec) {
+      // every per-step value lives on the device (SlotState, seen, the input rows): admissions between replays keep the graph valid
+      IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+      const int rc = decode_step(w, s.slots, s.penalty, w.codes, s.max_new, nullptr, st);
+      hipGraph_t g = nullptr;
+      hipError_t e = hipStreamEndCapture(st, &g);
+      if (rc) { if (g) (void)hipGraphDestroy(g); return 1; }
+      IDX_HIP(e);
+      s.graph = g;
+      IDX_HIP(hipGraphInstantiate(&s.exec, s.graph, nullptr, nullptr, 0));
+      s.geom = geom;
+    }
+    if (graph_ok && s.exec) {
+      IDX_HIP(hipGraphLaunch(s.exec, st));
+    } else {
+      if (decode_step(w, s.slots, s.penalty, w.codes, s.max_new, nullptr, st)) return 1;
+      s.warm = true;
+    }
+  }
+  std::vector<SlotState> hs(s.slots);
+  IDX_HIP(hipMemcpyAsync(hs.data(), w.slots, s.slots * sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  int nf = 0;
+  for (int i = 0; i < s.slots; ++i)
+    if (s.busy[i] && !hs[i].live) { if (finished_slots) finished_slots[nf] = i; ++nf; }
+  if (n_finished) *n_finished = nf;
+  return 0;
+}
+
+int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(codes && n_codes, "null pointer");
+  IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  SlotState hs;
+  IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(!hs.live, "slot is still decoding");
+  IDX_CHECK(hs.step >= 1 && hs.step <= s.max_new, "slot state corrupt");
+  IDX_HIP(hipMemcpyAsync(codes, sb.w.codes + (size_t)slot * s.max_new, (size_t)hs.step * sizeof(long long), hipMemcpyDeviceToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  *n_codes = hs.step;
+  s.busy[slot] = 0;
   return 0;
 }
 

@@ -23,6 +23,8 @@ SYMBOLS = [
     "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
     "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
     "idxtts_gpt_beam_workspace_bytes", "idxtts_gpt_generate_beam",
+    "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
+    "idxtts_gpt_session_read", "idxtts_gpt_session_release",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_emovec_merge",
@@ -152,6 +154,13 @@ def load() -> ctypes.CDLL:
     lib.idxtts_gpt_beam_workspace_bytes.restype = c_size_t
     lib.idxtts_gpt_generate_beam.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, POINTER(BeamC), c_void_p,
                                              POINTER(c_int), c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_gpt_session_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    lib.idxtts_gpt_session_workspace_bytes.restype = c_size_t
+    lib.idxtts_gpt_session_init.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_gpt_session_admit.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_step.argtypes = [c_void_p, c_int, c_int, c_void_p, POINTER(c_int), c_void_p, c_void_p]
+    lib.idxtts_gpt_session_read.argtypes = [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p, c_void_p]
+    lib.idxtts_gpt_session_release.argtypes = [c_void_p, c_void_p]
     lib.idxtts_gpt_latent.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_s2mel_create.argtypes = [POINTER(S2MelConfigC), POINTER(c_void_p)]
     lib.idxtts_s2mel_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]

@@ -213,6 +213,23 @@ class UnifiedVoice:
         fake[:, -1] = cfg.start_mel_token
         return fake, emb.view(B, P, cfg.model_dim), torch.from_numpy(mask)
 
+    def prompt_rows(self, conditional_latents: torch.Tensor, text_inputs: torch.Tensor):
+        """prepare_gpt_inputs per row, without the left padding: a list of [P_b, d] prompt embeddings (what a decode session
+        admits; generate() on a row with attention_mask=None sees the same prompt)."""
+        _, emb, mask = self.prepare_gpt_inputs(conditional_latents, text_inputs)
+        pads = (mask[:, :-1] == 0).sum(1).tolist()
+        return [emb[i, int(p):] for i, p in enumerate(pads)]
+
+    def decode_session(self, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0, do_sample: bool = False,
+                       num_beams: int = 1, use_graph: bool = True) -> "DecodeSession":
+        """Continuous batching: `slots` greedy decode rows, one KV region each, that requests enter and leave between steps
+        (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt."""
+        if do_sample:
+            raise ValueError("decode sessions are greedy only: do_sample=True is not supported (use generate())")
+        if num_beams != 1:
+            raise ValueError("decode sessions are greedy only: beam search is not supported (use generate_beam())")
+        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph)
+
     # ------------------------------------------------------------------------------------------
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 100, temperature: float = 1.0, top_k: int = 50,
                  top_p: float = 1.0, stop_tokens=None, attention_mask: Optional[torch.Tensor] = None,
@@ -437,5 +454,118 @@ class UnifiedVoice:
         try:
             if getattr(self, "_h", None):
                 _lib.load().idxtts_ctx_destroy(self._h)
+        except Exception:
+            pass
+
+
+class DecodeSession:
+    """A fixed set of greedy decode rows ("slots") with one KV region each, on one HIP stream (the current stream at creation, or a
+    stream of its own when that is the legacy default stream, which cannot be captured):
+      * admit(rows, caps) runs the prefill and first token of new requests in free slots and returns their slot ids;
+      * step(n) runs n decode steps of every live slot and returns the slots whose request has finished;
+      * take(slot) returns that request's codes (up to and including the stop token, or `cap` codes) and frees the slot.
+    Every slot has its own positions, cap and finished state, so requests of any prompt length, prompt and cap share a session.
+    Determinism: a request's codes equal, bit for bit, row 0 of UnifiedVoice.generate on `slots` copies of its prompt
+    (attention_mask=None) with max_new_tokens = its cap -- whatever else is in flight, when it was admitted and which slot it has.
+    With a bf16 KV cache in split-bf16 GEMM mode that reference batch needs slots * (P + 1) >= 256 prefill rows (or the exact
+    GEMM mode).  Results can depend on `slots`: the decode attention's key split and the decode GEMV are chosen from it."""
+
+    def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
+                 use_graph: bool = True):
+        self.gpt = gpt
+        self.slots, self.max_prompt, self.max_new = int(slots), int(max_prompt), int(max_new)
+        self.use_graph = bool(use_graph)
+        self._lib = _lib.load()
+        self.stream = torch.cuda.current_stream(gpt.device)
+        if self.stream.cuda_stream == 0:        # the legacy default stream cannot be captured: a stream of the session's own
+            self.stream = torch.cuda.Stream(device=gpt.device)
+            self.stream.wait_stream(torch.cuda.current_stream(gpt.device))
+        need = int(self._lib.idxtts_gpt_session_workspace_bytes(gpt._h, self.slots, self.max_prompt, self.max_new))
+        if need == 0:
+            raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
+        with torch.cuda.stream(self.stream):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=gpt.device)
+            _lib.check(self._lib.idxtts_gpt_session_init(gpt._h, self.slots, self.max_prompt, self.max_new, float(repetition_penalty),
+                                                         _lib.ptr(self._ws), need, self._sp()))
+        self._busy = [False] * self.slots
+        self._done = set()
+
+    def _sp(self) -> c_void_p:
+        return c_void_p(self.stream.cuda_stream)
+
+    @property
+    def free_slots(self):
+        return [i for i, b in enumerate(self._busy) if not b]
+
+    @property
+    def live_slots(self):
+        return [i for i, b in enumerate(self._busy) if b and i not in self._done]
+
+    def admit(self, inputs_embeds_rows, max_new_each) -> list:
+        """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int)."""
+        rows = [r.to(self.gpt.device, torch.float32) for r in inputs_embeds_rows]
+        n = len(rows)
+        if n == 0:
+            return []
+        caps = [int(max_new_each)] * n if isinstance(max_new_each, int) else [int(c) for c in max_new_each]
+        if len(caps) != n:
+            raise ValueError("one cap per row")
+        free = self.free_slots
+        if n > len(free):
+            raise RuntimeError(f"{n} rows but {len(free)} free slots")
+        d = self.gpt.cfg.model_dim
+        plen = [int(r.shape[0]) for r in rows]
+        for r, p, c in zip(rows, plen, caps):
+            if r.dim() != 2 or r.shape[1] != d or not 1 <= p <= self.max_prompt:
+                raise ValueError(f"a prompt row must be [P, {d}] with 1 <= P <= {self.max_prompt}")
+            if not 1 <= c <= self.max_new:
+                raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        ids = free[:n]
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
+        with torch.cuda.stream(self.stream):
+            pm = max(plen)
+            emb = torch.zeros(n, pm, d, device=self.gpt.device, dtype=torch.float32)
+            for i, r in enumerate(rows):
+                emb[i, : plen[i]] = r
+            h_p, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, ids, caps))
+            _lib.check(self._lib.idxtts_gpt_session_admit(
+                self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
+                h_caps.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
+        for i in ids:
+            self._busy[i] = True
+        return ids
+
+    def step(self, n: int = 1) -> list:
+        """n decode steps of every live slot; returns every slot whose request has finished and is not taken yet."""
+        fin = np.zeros(self.slots, np.int32)
+        nf = ctypes.c_int(0)
+        steps = int(n) if self.live_slots else 0
+        _lib.check(self._lib.idxtts_gpt_session_step(self.gpt._h, steps, int(self.use_graph), fin.ctypes.data_as(c_void_p),
+                                                     ctypes.byref(nf), _lib.ptr(self._ws), self._sp()))
+        done = [int(x) for x in fin[: nf.value]]
+        self._done.update(done)
+        return done
+
+    def take(self, slot: int) -> torch.Tensor:
+        """The codes of the finished request in `slot` (LongTensor on the device); the slot is free again."""
+        n = ctypes.c_int(0)
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(self.max_new, dtype=torch.long, device=self.gpt.device)
+            _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(slot), _lib.ptr(out), ctypes.byref(n), _lib.ptr(self._ws),
+                                                         self._sp()))
+        self._busy[slot] = False
+        self._done.discard(slot)
+        return out[: n.value]
+
+    def close(self) -> None:
+        if getattr(self, "_ws", None) is not None:
+            self.stream.synchronize()
+            self._lib.idxtts_gpt_session_release(self.gpt._h, _lib.ptr(self._ws))
+            self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass

@@ -272,3 +272,226 @@ class BatchPipeline:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class _Job:
+    """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed")
+
+
+class ContinuousPipeline:
+    """Continuous (iteration-level) batching of the GPT decode: each of `decode_lanes` lanes owns one decode session of `slots` rows
+    (`UnifiedVoice.decode_session`) on its own stream and host thread.  A lane admits waiting utterances into its free slots --
+    utterances of different requests, prompts and text widths share a session -- steps `poll_steps` steps at a time and collects
+    the rows that have finished (stop token or the request's own `max_mel_tokens`), so a short row no longer holds its slot while
+    the longest row of a static batch runs on.  Once every row of a request is decoded, the request goes through the existing
+    path behind the decode: `gpt_stage(text, cond, codes=...)` (trim + latent pass) and `acoustic_stage` on an acoustic worker.
+
+    Greedy only.  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on `slots` copies of each of its utterances
+    (gpt.DecodeSession), whatever else shares the session; they can differ from `BatchPipeline` / `synthesize_batch` results, whose
+    decode batch is the request itself (the decode attention's key split and the decode GEMV are chosen by row count).  An error
+    (say, a bad token id) fails the offending request's Future only.
+
+    session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
+
+    def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
+                 repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
+                 session_factory=None):
+        if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1:
+            raise ValueError("slots, decode_lanes, acoustic_workers and poll_steps must be >= 1")
+        g = tts.cfg.gpt
+        self.tts = tts
+        self.device = torch.device(tts.device)
+        self.slots, self.poll_steps, self.repetition_penalty = slots, poll_steps, float(repetition_penalty)
+        self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
+        self.max_new = int(max_new or g.max_mel_tokens)
+        self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty))
+        self._cuda = self.device.type == "cuda"
+        self._cv = threading.Condition()
+        self._waiting = collections.deque()     # (job, utterance index) not admitted yet
+        self._closing = False
+        self._streams = []
+        self._tls = threading.local()
+        self._acoustic = concurrent.futures.ThreadPoolExecutor(max_workers=acoustic_workers, thread_name_prefix="idxtts-acoustic")
+        self._alive = decode_lanes
+        self._lanes = [threading.Thread(target=self._lane, name=f"idxtts-session-{i}", daemon=True) for i in range(decode_lanes)]
+        for t in self._lanes:
+            t.start()
+
+    def _new_stream(self):
+        if not self._cuda:
+            return None
+        s = torch.cuda.Stream(device=self.device)
+        with self._cv:
+            self._streams.append(s)
+        return s
+
+    def _on(self, s):
+        return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
+
+    def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
+               repetition_penalty: float = 10.0, sampling: Optional[dict] = None) -> concurrent.futures.Future:
+        """BatchPipeline.submit's contract (a Future of the list of waveforms), greedy only; max_mel_tokens caps each row."""
+        if sampling:
+            raise ValueError("ContinuousPipeline decodes greedily; use BatchPipeline for sampling")
+        if float(repetition_penalty) != self.repetition_penalty:
+            raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
+        if not 1 <= int(max_mel_tokens) <= self.max_new:
+            raise ValueError(f"max_mel_tokens must be in 1 .. {self.max_new}")
+        j = _Job()
+        j.text, j.cond, j.max_mel_tokens, j.noise = torch.as_tensor(text_tokens), cond, int(max_mel_tokens), noise
+        B = int(j.text.shape[0])
+        j.codes, j.left, j.failed = [None] * B, B, False
+        j.done = concurrent.futures.Future()
+        j.caller = torch.cuda.current_stream(self.device) if self._cuda else None
+        j.ready = None
+        if self._cuda:
+            j.ready = torch.cuda.Event()
+            j.ready.record(j.caller)
+        with self._cv:
+            if self._closing or self._alive == 0:
+                raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
+            self._waiting.extend((j, i) for i in range(B))
+            self._cv.notify_all()
+        return j.done
+
+    @staticmethod
+    def _fail(j: _Job, e: BaseException) -> None:
+        j.failed = True
+        if not j.done.done():
+            j.done.set_exception(e)
+
+    def _prompt_rows(self, j: _Job, idx):
+        """The [P, d] prompts of utterances `idx` of a job (prepare_gpt_inputs, unpadded), on the current stream."""
+        if j.ready is not None:
+            torch.cuda.current_stream(self.device).wait_event(j.ready)
+        c = j.cond.to(self.device)
+        lat = c.spk_cond_latent if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent[idx]
+        emo = c.emo_vec if c.emo_vec.shape[0] == 1 else c.emo_vec[idx]
+        conds = self.tts.gpt.conds_latent(lat, emo)
+        return self.tts.gpt.prompt_rows(conds, j.text[idx])
+
+    def _admit(self, sess, in_slot) -> None:
+        with self._cv:
+            take = []
+            while self._waiting and len(take) < len(sess.free_slots):
+                j, i = self._waiting.popleft()
+                if not j.failed:
+                    take.append((j, i))
+        by_job = collections.OrderedDict()
+        for j, i in take:
+            by_job.setdefault(id(j), (j, []))[1].append(i)
+        rows, caps, owners = [], [], []
+        for j, idx in by_job.values():
+            try:
+                rs = self._prompt_rows(j, idx)
+                if any(int(r.shape[0]) > self.max_prompt for r in rs):
+                    raise ValueError(f"prompt longer than the pipeline's max_prompt ({self.max_prompt})")
+            except BaseException as e:       # noqa: BLE001 -- the request's own error (bad token id, too long)
+                self._fail(j, e)
+                continue
+            rows.extend(rs)
+            caps.extend([j.max_mel_tokens] * len(idx))
+            owners.extend((j, i) for i in idx)
+        if rows:
+            try:
+                got = sess.admit(rows, caps)
+            except BaseException as e:       # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
+                for j, _ in owners:
+                    self._fail(j, e)
+                return
+            for s, o in zip(got, owners):
+                in_slot[s] = o
+
+    def _collect(self, sess, in_slot, finished) -> None:
+        for s in finished:
+            j, i = in_slot.pop(s)
+            codes = sess.take(s).cpu()
+            if j.failed:
+                continue
+            j.codes[i] = codes
+            j.left -= 1
+            if j.left == 0:
+                self._acoustic.submit(self._acoustic_job, j)
+
+    def _lane(self):
+        sess, in_slot = None, {}
+        try:
+            if self._cuda:
+                torch.cuda.set_device(self.device)
+            stream = self._new_stream()
+            with self._on(stream):
+                sess = self._factory(self.max_prompt, self.max_new)
+                while True:
+                    with self._cv:
+                        while not self._waiting and not in_slot and not self._closing:
+                            self._cv.wait()
+                        if self._closing and not self._waiting and not in_slot:
+                            break
+                    if sess.free_slots:
+                        self._admit(sess, in_slot)
+                    if in_slot:
+                        self._collect(sess, in_slot, sess.step(self.poll_steps))
+        except BaseException as e:              # noqa: BLE001 -- a session failure: the requests in its slots fail (and the waiting
+            pending = list(in_slot.values())    # ones too when no other lane is left to take them)
+            with self._cv:
+                self._alive -= 1
+                if self._alive == 0:
+                    pending += list(self._waiting)
+                    self._waiting.clear()
+            for j, _ in pending:
+                self._fail(j, e)
+            return
+        finally:
+            if sess is not None:
+                sess.close()
+        with self._cv:
+            self._alive -= 1
+
+    def _acoustic_job(self, j: _Job):
+        try:
+            if self._cuda:
+                torch.cuda.set_device(self.device)
+            sa = getattr(self._tls, "stream", None)
+            if sa is None:
+                sa = self._tls.stream = self._new_stream()
+            stop = self.tts.cfg.gpt.stop_mel_token
+            n = max(int(c.shape[0]) for c in j.codes)
+            codes = torch.full((len(j.codes), n), stop, dtype=torch.long)
+            for i, c in enumerate(j.codes):
+                codes[i, : c.shape[0]] = c
+            with self._on(sa):
+                if j.ready is not None:
+                    sa.wait_event(j.ready)
+                st = self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens, repetition_penalty=self.repetition_penalty,
+                                        codes=codes)
+                wavs = self.tts.acoustic_stage(st, noise=j.noise)
+                if sa is not None:
+                    sa.synchronize()
+            if j.caller is not None:
+                for w in wavs:                  # allocated on the worker's stream, consumed on the caller's
+                    w.record_stream(j.caller)
+            j.done.set_result(wavs)
+        except BaseException as e:              # noqa: BLE001
+            self._fail(j, e)
+
+    def close(self):
+        with self._cv:
+            self._closing = True
+            self._cv.notify_all()
+        for t in self._lanes:
+            t.join()
+        self._acoustic.shutdown(wait=True)
+        if self._cuda:
+            from . import _lib
+            with torch.cuda.device(self.device):
+                for s in self._streams:
+                    s.synchronize()
+                    _lib.release_stream(s)
+        self._streams = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

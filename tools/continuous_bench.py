@@ -1,0 +1,102 @@
+"""ContinuousPipeline against BatchPipeline at equal decode width, full-size model with synthetic weights (bf16 GPT weights and KV).
+
+Two workloads over the same utterances (configs[2]-shaped: 128 text tokens, 689-frame prompt, EOS suppressed so that lengths are
+exactly the caps):
+  (a) fixed: every utterance 512 codes -- BatchPipeline takes requests of 16 utterances, ContinuousPipeline the same requests;
+  (b) ragged: utterance caps drawn with a fixed seed from 256..768 codes.  ContinuousPipeline takes one request per utterance with
+      its own cap; BatchPipeline takes the same utterances as requests of 16 whose cap is the longest of the 16 (a static batch decodes
+      until its longest row is done).  Throughput counts the audio of the utterances' own caps for both (for BatchPipeline the
+      acoustic stage also renders the padding codes: an upper bound of its cost where rows would stop on their own).
+The two pipelines alternate, every shape is warmed up first, and each is repeated so the spread is known.  Prints one JSON line.
+
+    python tools/continuous_bench.py [--utterances 64] [--reps 3]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "index-tts_amd")]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--utterances", type=int, default=64)
+    ap.add_argument("--slots", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--poll-steps", type=int, default=16)
+    args = ap.parse_args()
+    from indextts_amd import synth, weights
+    from indextts_amd.config import PipelineConfig
+    from indextts_amd.infer_v2 import IndexTTS2, PromptConditioning
+    from indextts_amd.serving import BatchPipeline, ContinuousPipeline
+    warnings.filterwarnings("ignore", category=RuntimeWarning)
+    dev = torch.device("cuda:0")
+    cfg = PipelineConfig()
+    wg = weights.synth_gpt_weights(cfg.gpt, tag="bench/gpt")
+    wg["mel_head.bias"][cfg.gpt.stop_mel_token] = -1e4
+    ws = weights.synth_s2mel_weights(cfg.s2mel, tag="bench/s2mel")
+    wv = weights.synth_bigvgan_weights(cfg.bigvgan, tag="bench/bigvgan")
+    tts = IndexTTS2.from_state_dicts(cfg, wg, ws, wv, device=dev, gpt_weight_format="bf16", gpt_kv_format="bf16")
+    Tp, L, W, N = 689, 128, args.slots, args.utterances
+    cond = PromptConditioning.synthetic(cfg, prompt_frames=Tp, tag="bench/prompt").to(dev)
+    text = torch.from_numpy(synth.integers("cbench/text", (N, L), 2, cfg.gpt.number_text_tokens))
+    rng = np.random.default_rng(7)
+    caps = {"fixed": [512] * N, "ragged": [int(c) for c in rng.integers(256, 769, N)]}
+    frame_s = cfg.bigvgan.total_upsample / cfg.bigvgan.sampling_rate
+
+    def noise(k, rows, M):
+        return torch.from_numpy(synth.uniform(f"cbench/noise/{k}", (rows, cfg.s2mel.in_channels, Tp + int(M * cfg.code_to_frame)), 1.7)).to(dev)
+
+    jobs = {}
+    for wl, cp in caps.items():
+        static = []          # BatchPipeline: requests of W utterances, cap = the longest
+        for g in range(0, N, W):
+            M = max(cp[g:g + W])
+            static.append((text[g:g + W], M, noise(f"{wl}/s{g}", len(cp[g:g + W]), M)))
+        if wl == "fixed":
+            cont = static
+        else:                # ContinuousPipeline: one request per utterance, its own cap
+            cont = [(text[i:i + 1], cp[i], noise(f"{wl}/c{i}", 1, cp[i])) for i in range(N)]
+        jobs[wl] = {"batch": static, "continuous": cont,
+                    "audio_s": sum(int(c * cfg.code_to_frame) for c in cp) * frame_s}
+
+    pipes = {"batch": lambda: BatchPipeline(tts, decode_lanes=1),
+             "continuous": lambda: ContinuousPipeline(tts, slots=W, decode_lanes=1, poll_steps=args.poll_steps, max_new=800)}
+
+    def run(kind, wl):
+        with pipes[kind]() as pipe:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            futs = [pipe.submit(t, cond, max_mel_tokens=M, noise=z) for t, M, z in jobs[wl][kind]]
+            for f in futs:
+                f.result()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+    out = {"utterances": N, "slots": W, "text_tokens": L, "prompt_frames": Tp, "reps": args.reps, "poll_steps": args.poll_steps}
+    for wl in caps:
+        for kind in pipes:          # warm-up: every shape (prefill widths, graphs, acoustic lengths) once
+            run(kind, wl)
+        rates = {k: [] for k in pipes}
+        for _ in range(args.reps):
+            for kind in pipes:      # alternated
+                rates[kind].append(jobs[wl]["audio_s"] / run(kind, wl))
+        out[wl] = {k: {"audio_s_per_s_median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))} for k, v in rates.items()}
+        out[wl]["continuous_over_batch"] = out[wl]["continuous"]["audio_s_per_s_median"] / out[wl]["batch"]["audio_s_per_s_median"]
+        out[wl]["audio_s"] = jobs[wl]["audio_s"]
+        print(f"[continuous_bench] {wl}: {json.dumps(out[wl])}", file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
