@@ -278,7 +278,8 @@ int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const 
  * Stands in for the accel engine's per-sequence bookkeeping -- `context_lens` per sequence in the decode step and a KV allocation per
  * sequence that is taken when a sequence is admitted and given back when it finishes (accel_engine.py:154-212,
  * KVCacheManager.allocate / remove_seq in kv_manager.py:130-202) -- with a fixed set of `slots` decode rows, one KV region each.
- * Greedy only (the semantics of idxtts_gpt_generate).  A slot retires when it samples stop_mel_token (recorded) or at its own cap;
+ * Greedy (the semantics of idxtts_gpt_generate) unless initialised with IDXTTS_SESSION_SAMPLED (see _admit_sampled).  A slot retires
+ * when it samples stop_mel_token (recorded) or at its own cap;
  * rows keep stepping on their own, so requests can be admitted into free slots between steps.
  * Determinism: a request's codes equal, bit for bit, row 0 of idxtts_gpt_generate on `slots` copies of its prompt with no left
  * padding (for a bf16 KV cache in split-bf16 GEMM mode: a reference batch of slots * (P + 1) >= 256 prefill rows), whatever else is in
@@ -295,6 +296,23 @@ int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_
  * Runs their prefill and first token. */
 int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                              const int* slot_ids, const int* max_new_tokens, void* workspace, void* stream);
+/* Sampled sessions: _workspace_bytes_ex / _init_ex with flags = IDXTTS_SESSION_SAMPLED add a per-slot sampler table; flags = 0 is
+ * exactly _workspace_bytes / _init.  A sampled session's step samples every slot with its own request's idxtts_sampling. */
+#define IDXTTS_SESSION_SAMPLED 1
+size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags);
+int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* _admit on a sampled session with a sampler per row: per_row HOST [n] (idxtts_sampling; mode 0 = greedy, bit-identical to the same
+ * row in a greedy session).  exp_noise: NULL, or device fp32 [max_new_tokens[b]][V] that the caller keeps alive until the slot is read
+ * (row t = the draws of the request's step t); with NULL the draws come from `seed`, the stream row 0 of a `slots`-row
+ * idxtts_gpt_generate_sampled uses.  Determinism: a sampled request's codes equal, bit for bit, row 0 of idxtts_gpt_generate_sampled
+ * with the same sampler on `slots` copies of its prompt (exp_noise: whose row 0 of every step is the request's row), under the greedy
+ * rule's conditions above.  Every row is checked first (mode 0 / 1 / 2, temperature > 0, top_p < 1 needs 0 < top_k <= 1024): a bad
+ * row refuses the whole call, no slot taken.  Refused on a greedy session.  The repetition penalty is the session's (HF mode applies
+ * it, the accel sampler does not). _admit on a sampled session admits greedy rows. */
+int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                     const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_row, void* workspace,
+                                     void* stream);
 /* Runs n_steps decode steps for every live slot (a captured hipGraph is replayed when use_graph), then reports the slots that hold a
  * finished request not read yet: finished_slots HOST int32 [slots] (may be NULL), *n_finished. */
 int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* finished_slots, int* n_finished, void* workspace,

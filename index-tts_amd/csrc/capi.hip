@@ -452,11 +452,39 @@ int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_
   API_END
 }
 
+size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags) {
+  if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
+  if (flags & ~IDXTTS_SESSION_SAMPLED) return 0;
+  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
+  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, (flags & IDXTTS_SESSION_SAMPLED) != 0) : 0;
+}
+
+int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(!(flags & ~IDXTTS_SESSION_SAMPLED), "unknown session flags");
+  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
+                         (flags & IDXTTS_SESSION_SAMPLED) != 0);
+  API_END
+}
+
 int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                              const int* slot_ids, const int* max_new_tokens, void* workspace, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
   return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                     const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_row, void* workspace,
+                                     void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(per_row, "null pointer");
+  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
+                          per_row);
   API_END
 }
 

@@ -110,6 +110,19 @@ struct SampleWarpArgs {
   unsigned long long seed = 0;
 };
 int sample_warp_forward(const SampleWarpArgs& a, hipStream_t stream);
+// Per-request sampler of a sampled decode session: one row per slot, in the session workspace (idxtts_sampling's values)
+struct SlotSampling {
+  int mode;                      // 0 greedy (sample_slots_forward's rule), SAMPLE_HF, SAMPLE_ACCEL
+  float temperature;
+  int top_k;
+  float top_p;
+  unsigned long long seed;       // draws when exp_noise is null: exp1_draw(seed, (t * B + 0) * V + v) at the slot's step t
+  const float* exp_noise;        // the request's draws [max_step][V] (row t at step t), or null
+};
+// sample_slots_forward with each slot's own sampler samp[slot] (a.parts must be 1): mode 0 rows are bit-identical to
+// sample_slots_forward, HF / accel rows to row 0 of sample_warp_forward on an a.B-row generation with the same draws
+int sample_slots_warp_forward(const SampleArgs& a, SlotState* slots, const SlotSampling* samp, const int* slot_ids, int n,
+                              hipStream_t stream);
 
 int advance_state(DecodeState* st, hipStream_t stream);
 // qkv [B][S][3d] -> caches, positions [0, S).  kv16: the caches hold bf16 and the k / v columns of qkv are rounded IN PLACE, so the

@@ -626,18 +626,13 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream) {
 
 // -------------------------------------------------------------------------------------------------
 // Decode session (continuous batching): the greedy tail with per-slot state (SlotState, decode.h)
-__global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, SlotState* slots, const int* slot_ids) {
-  __shared__ float rv[16];
-  __shared__ int ri[16];
-  __shared__ int s_tok, s_mp, s_end;
-  const int b = slot_ids ? slot_ids[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
-  SlotState* const ss = slots + b;
-  if (!ss->live) return;      // free or ended slot: nothing is read or written (workgroup-uniform)
-  float best;
-  int bidx;
-  greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
+
+// The tail of a session sampler, once thread 0 holds the slot's token: record it, then end the slot (stop token or cap) or write its
+// next input row and advance its own scalars.  s_tok / s_mp / s_end: shared scratch.
+__device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const ss, const int b, const int tid, const int token, int& s_tok,
+                                          int& s_mp, int& s_end) {
   if (tid == 0) {
-    const int tok = bidx, step = ss->step;
+    const int tok = token, step = ss->step;
     p.codes[(size_t)b * p.codes_ld + step] = tok;
     p.seen[(size_t)b * p.V + tok] = 1;
     p.cur_tok[b] = tok;
@@ -657,6 +652,19 @@ __global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, 
     embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, s_tok, s_mp, tid);
   }
   if (tid == 0) { ss->pos += 1; ss->mel_pos += 1; ss->step += 1; }      // this slot's scalars: nobody else reads them in this launch
+}
+
+__global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, SlotState* slots, const int* slot_ids) {
+  __shared__ float rv[16];
+  __shared__ int ri[16];
+  __shared__ int s_tok, s_mp, s_end;
+  const int b = slot_ids ? slot_ids[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
+  SlotState* const ss = slots + b;
+  if (!ss->live) return;      // free or ended slot: nothing is read or written (workgroup-uniform)
+  float best;
+  int bidx;
+  greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
+  slot_tail(p, ss, b, tid, bidx, s_tok, s_mp, s_end);
 }
 
 int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_ids, int n, hipStream_t stream) {
@@ -693,22 +701,16 @@ __device__ __forceinline__ void block_argmax(float& v, int& i, float* rv, int* r
     if (rv[w] > v || (rv[w] == v && ri[w] < i)) { v = rv[w]; i = ri[w]; }
 }
 
-__global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs q) {
-  const SampleArgs& p = q.base;
-  __shared__ float rv[16];
-  __shared__ int ri[16];
-  __shared__ float sval[SW_CAP];
-  __shared__ int sidx[SW_CAP];
-  __shared__ float sorted_v[SW_CAP];
-  __shared__ int sorted_i[SW_CAP];
-  __shared__ int s_count, s_keep_from;
-  __shared__ float s_sum;
-  const int b = blockIdx.x, tid = threadIdx.x;
+// Row b of the warped sampler (parts = 1; the penalty in HF mode only): the token, valid in every thread.  The draw for id v is
+// exp1_draw(noise, seed, nbase + v).  rv / ri: [16], sval / sidx / sorted_v / sorted_i: [SW_CAP] of shared scratch.
+__device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, const int mode, const float temperature, const int top_k,
+                                              const float top_p, const float* noise, const unsigned long long seed, const size_t nbase,
+                                              const int tid, float* rv, int* ri, float* sval, int* sidx, float* sorted_v, int* sorted_i,
+                                              int& s_count, int& s_keep_from, float& s_sum) {
   const int V = p.V;
   const unsigned char* seen = p.seen + (size_t)b * V;
   const float* prow = p.part + (size_t)b * V;
-  const size_t nbase = ((size_t)p.st->step * p.B + b) * V;
-  auto draw = [&](int v) { return exp1_draw(q.exp_noise, q.seed, nbase + v); };
+  auto draw = [&](int v) { return exp1_draw(noise, seed, nbase + v); };
 
   // ---- scores: logits -> (repetition penalty) -> / temperature ----
   float sc[SW_NPT];
@@ -719,16 +721,16 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
     if (v < V) {
       l = prow[v] + (p.bias ? p.bias[v] : 0.0f);
       if (p.logits_out) p.logits_out[(size_t)b * V + v] = l;
-      if (q.mode == SAMPLE_HF && p.penalty != 1.0f && seen[v]) l = l < 0.f ? l * p.penalty : l / p.penalty;
-      if (q.temperature != 1.0f) l = l / q.temperature;
+      if (mode == SAMPLE_HF && p.penalty != 1.0f && seen[v]) l = l < 0.f ? l * p.penalty : l / p.penalty;
+      if (temperature != 1.0f) l = l / temperature;
     }
     sc[u] = l;
   }
 
   int token;
-  if (q.mode == SAMPLE_ACCEL || (q.top_k == 0 && q.top_p >= 1.0f)) {
+  if (mode == SAMPLE_ACCEL || (top_k == 0 && top_p >= 1.0f)) {
     // softmax over the whole row, divided by the (accel sampler: clamped) noise, argmax
-    const float qmin = q.mode == SAMPLE_ACCEL ? 1e-10f : 0.0f;
+    const float qmin = mode == SAMPLE_ACCEL ? 1e-10f : 0.0f;
     float mx = -INFINITY; int mi = 0;
 #pragma unroll
     for (int u = 0; u < SW_NPT; ++u) if (sc[u] > mx) { mx = sc[u]; mi = tid + 1024 * u; }
@@ -756,10 +758,10 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
     token = bi;
   } else {
     // ---- top-k: the k-th largest value (with multiplicity) by k rounds of block-wide max extraction ----
-    if (q.top_k > 0 && q.top_k < V) {
+    if (top_k > 0 && top_k < V) {
       unsigned taken = 0;
       float kth = -INFINITY;
-      for (int r = 0; r < q.top_k; ++r) {
+      for (int r = 0; r < top_k; ++r) {
         float mx = -INFINITY; int mi = 0x7fffffff;
 #pragma unroll
         for (int u = 0; u < SW_NPT; ++u) {
@@ -798,10 +800,10 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
     if (tid == 0) {
       int keep_from = 0;
       const float mx = sorted_v[n - 1];
-      if (q.top_p < 1.0f) {
+      if (top_p < 1.0f) {
         float tot = 0.f;
         for (int e = 0; e < n; ++e) tot += expf(sorted_v[e] - mx);
-        const float thr = (float)(1.0 - (double)q.top_p);
+        const float thr = (float)(1.0 - (double)top_p);
         float cum = 0.f;
         for (int e = 0; e < n - 1; ++e) {
           cum += expf(sorted_v[e] - mx) / tot;
@@ -825,6 +827,24 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
     block_argmax(best, bi, rv, ri, tid);
     token = bi;
   }
+  return token;
+}
+
+__global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs q) {
+  const SampleArgs& p = q.base;
+  __shared__ float rv[16];
+  __shared__ int ri[16];
+  __shared__ float sval[SW_CAP];
+  __shared__ int sidx[SW_CAP];
+  __shared__ float sorted_v[SW_CAP];
+  __shared__ int sorted_i[SW_CAP];
+  __shared__ int s_count, s_keep_from;
+  __shared__ float s_sum;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int V = p.V;
+  const size_t nbase = ((size_t)p.st->step * p.B + b) * V;
+  const int token = warp_row_token(p, b, q.mode, q.temperature, q.top_k, q.top_p, q.exp_noise, q.seed, nbase, tid, rv, ri, sval, sidx,
+                                   sorted_v, sorted_i, s_count, s_keep_from, s_sum);
   if (tid == 0) {
     const int tok = p.finished[b] ? p.stop_token : token;
     p.codes[(size_t)b * p.codes_ld + p.st->step] = tok;
@@ -843,6 +863,51 @@ int sample_warp_forward(const SampleWarpArgs& a, hipStream_t stream) {
   static const int cat = prof_register("sample_warp_kernel");
   ProfScope prof(cat, stream, 0.0, 8.0 * b.B * (double)b.V);
   hipLaunchKernelGGL(sample_warp_kernel, dim3(b.B), dim3(1024), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// Decode session with per-request sampling: sample_slots_kernel with the sampler of each slot's own SlotSampling row -- greedy_row_argmax
+// (mode 0) or the warped sampler of sample_warp_kernel, whose draws for the slot's step t are the request's noise row t, or the
+// counter-based stream at row 0 of a `p.B`-row generation (independent of the slot id)
+__global__ __launch_bounds__(1024) void sample_slots_warp_kernel(const SampleArgs p, SlotState* slots, const SlotSampling* samp,
+                                                                 const int* slot_ids) {
+  __shared__ float rv[16];
+  __shared__ int ri[16];
+  __shared__ float sval[SW_CAP];
+  __shared__ int sidx[SW_CAP];
+  __shared__ float sorted_v[SW_CAP];
+  __shared__ int sorted_i[SW_CAP];
+  __shared__ int s_count, s_keep_from;
+  __shared__ float s_sum;
+  __shared__ int s_tok, s_mp, s_end;
+  const int b = slot_ids ? slot_ids[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
+  SlotState* const ss = slots + b;
+  if (!ss->live) return;      // free or ended slot (workgroup-uniform)
+  const SlotSampling sp = samp[b];
+  int token;
+  if (sp.mode == 0) {
+    float best;
+    greedy_row_argmax(p, b, tid, rv, ri, best, token);
+  } else {
+    const size_t t = (size_t)ss->step;      // read before any thread can reach slot_tail's update (the warper synchronises first)
+    const size_t nbase = sp.exp_noise ? t * p.V : t * p.B * p.V;
+    token = warp_row_token(p, b, sp.mode, sp.temperature, sp.top_k, sp.top_p, sp.exp_noise, sp.seed, nbase, tid, rv, ri, sval, sidx,
+                           sorted_v, sorted_i, s_count, s_keep_from, s_sum);
+  }
+  slot_tail(p, ss, b, tid, token, s_tok, s_mp, s_end);
+}
+
+int sample_slots_warp_forward(const SampleArgs& a, SlotState* slots, const SlotSampling* samp, const int* slot_ids, int n,
+                              hipStream_t stream) {
+  IDX_CHECK(a.part && a.parts == 1 && a.seen && a.codes && a.cur_tok && slots && samp && (a.embed.x_row || a.embed.x_frag) &&
+            a.embed.mel_emb && a.embed.mel_pos, "null pointer");
+  IDX_CHECK(!a.forced && !a.logits_out, "decode sessions record no logits and take no forced tokens");
+  IDX_CHECK(a.V > 0 && a.V <= 1024 * SW_NPT, "vocabulary size");
+  if (n <= 0) return 0;
+  static const int cat = prof_register("sample_slots_warp_kernel");
+  ProfScope prof(cat, stream, 0.0, 8.0 * n * (double)a.V);
+  hipLaunchKernelGGL(sample_slots_warp_kernel, dim3(n), dim3(1024), 0, stream, a, slots, samp, slot_ids);
   IDX_LAUNCH_CHECK();
   return 0;
 }

@@ -65,6 +65,7 @@ struct GPTModel : ModelBase {
     long long* codes;                         // [B][max_new] generated codes of the call in flight (copied to the caller's tensor at the end)
     size_t bytes;
     SlotState* slots = nullptr;               // decode session only (carve_session): per-row step scalars; the step uses them, not `state`
+    SlotSampling* slot_samp = nullptr;        // sampled decode session only: each slot's sampler (the step samples with it)
   };
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
@@ -111,11 +112,14 @@ struct GPTModel : ModelBase {
              hipStream_t st);
 
   // ---- decode session (continuous batching): `slots` decode rows with one KV region each; requests are admitted into free slots
-  // between steps, every slot advances on its own (SlotState), a slot ends on the stop token or its own cap and is read out.  Greedy
-  // only.  A row's codes equal row 0 of generate() on `slots` copies of it (pad_left 0): every kernel on its path is chosen from the
-  // session's properties (slots, KV format, GEMM mode) alone, never from how many rows are admitted at once.
+  // between steps, every slot advances on its own (SlotState), a slot ends on the stop token or its own cap and is read out.  Greedy,
+  // or (sampled sessions) each request with its own sampler and draws.  A row's codes equal row 0 of generate() on `slots` copies of it
+  // (pad_left 0): every kernel on its path is chosen from the session's properties (slots, KV format, GEMM mode) alone, never from how
+  // many rows are admitted at once.
   struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
     int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv16 = 0, gemm_mode = 0;
+    bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
+    std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
     size_t ws_bytes = 0;
     std::vector<char> busy;           // admitted and not yet read
     bool warm = false;                // one step has run eagerly (first-use function attributes are set outside a capture)
@@ -133,15 +137,18 @@ struct GPTModel : ModelBase {
     Buffers w;                        // decode buffers for `slots` rows (w.slots set) + the admission prefill's activations
     float* x_last;                    // [slots][d] last valid prefill row of each admitted request (first-token head input)
     int *ids, *plen, *klen, *cap;     // admission staging: slot ids, prompt lengths (prefill rows: -1 = padding row), P + 1, caps
+    SlotSampling* samp;               // [slots] per-slot samplers (sampled sessions only, else null)
     size_t bytes;
   };
   size_t session_prefill_rows(int slots, int max_prompt) const { return (size_t)slots * (max_prompt + 1) + 256; }
-  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new) const;
-  size_t session_workspace_bytes(int slots, int max_prompt, int max_new) const;
+  // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before
+  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled) const;
+  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false) const;
   Session* find_session(void* ws);
-  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st);
+  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false);
+  // per_row: null = every row greedy; else one sampler per row (sampled sessions only)
   int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                    const int* max_new, hipStream_t st);
+                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr);
   int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
   int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
   int session_release(void* ws);

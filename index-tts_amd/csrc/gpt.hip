@@ -377,6 +377,7 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
   if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
     if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
     s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d;
+    if (w.slot_samp) return sample_slots_warp_forward(s, w.slots, w.slot_samp, nullptr, B, st);      // sampled session: each slot's own sampler
     return sample_slots_forward(s, w.slots, nullptr, B, st);
   }
   if (fused_tail(B)) {      // the sampler's workgroups also write the next step's input and advance the step scalars
@@ -657,7 +658,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
 // Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
 // the staged last prefill rows and the admission's index arrays.
-GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new) const {
+GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled) const {
   SessionBuffers sb;
   sb.w = carve(ws, slots, max_prompt + 1, max_new, session_prefill_rows(slots, max_prompt));
   Carver c(ws);
@@ -669,12 +670,14 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
   sb.plen = c.take<int>(pre);
   sb.klen = c.take<int>(slots);
   sb.cap = c.take<int>(slots);
+  sb.samp = nullptr;
+  if (sampled) sb.w.slot_samp = sb.samp = c.take<SlotSampling>(slots);
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
 
-size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new) const {
-  return carve_session(nullptr, slots, max_prompt, max_new).bytes;
+size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled) const {
+  return carve_session(nullptr, slots, max_prompt, max_new, sampled).bytes;
 }
 
 GPTModel::Session* GPTModel::find_session(void* ws) {
@@ -683,12 +686,13 @@ GPTModel::Session* GPTModel::find_session(void* ws) {
   return it == sessions.end() ? nullptr : &it->second;
 }
 
-int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st) {
+int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st,
+                           bool sampled) {
   IDX_CHECK(ws, "null workspace");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
-  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new), "workspace too small");
-  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new);
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled);
   const Buffers& w = sb.w;
   const int d = cfg.model_dim;
   IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
@@ -698,6 +702,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   IDX_HIP(hipMemsetAsync(w.slots, 0, slots * sizeof(SlotState), st));                // every slot free
   IDX_HIP(hipMemsetAsync(sb.x_last, 0, (size_t)slots * d * sizeof(float), st));
   IDX_HIP(hipMemsetAsync(w.xrow, 0, (size_t)slots * d * sizeof(float), st));
+  if (sampled) IDX_HIP(hipMemsetAsync(sb.samp, 0, slots * sizeof(SlotSampling), st));      // every slot greedy
   std::lock_guard<std::mutex> l(session_mu);
   Session& s = sessions[ws];
   s.drop_graph();
@@ -705,6 +710,8 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv16 = kv_fmt; s.gemm_mode = get_gemm_mode();
   s.ws_bytes = ws_bytes;
   s.busy.assign(slots, 0);
+  s.sampled = sampled;
+  if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
   return 0;
 }
 
@@ -718,12 +725,23 @@ int GPTModel::session_release(void* ws) {
 }
 
 int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                            const int* caps, hipStream_t st) {
+                            const int* caps, hipStream_t st, const idxtts_sampling* per_row) {
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
   IDX_CHECK(inputs_embeds && prompt_lens && slot_ids && caps, "null pointer");
   IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots rows");
+  IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  if (per_row) {      // every row's sampler is checked before any slot is taken (generate()'s rules)
+    for (int b = 0; b < n; ++b) {
+      const idxtts_sampling& r = per_row[b];
+      IDX_CHECK(r.mode == 0 || r.mode == SAMPLE_HF || r.mode == SAMPLE_ACCEL, "sampling mode (0 greedy, 1 HF, 2 accel)");
+      if (r.mode == 0) continue;
+      IDX_CHECK(r.temperature > 0.0f, "sampling needs a positive temperature");
+      IDX_CHECK(r.top_k >= 0 && r.top_p > 0.0f, "sampling parameters");
+      IDX_CHECK(r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
+    }
+  }
   IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   GenScope gen_scope(this);
   int pmax = 0;
@@ -737,7 +755,7 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
     pmax = std::max(pmax, prompt_lens[b]);
   }
   const int d = cfg.model_dim, V = cfg.number_mel_codes;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
   const Buffers& w = sb.w;
   // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
   // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
@@ -758,6 +776,17 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
+  if (s.sampled) {      // the admitted slots' samplers (greedy when per_row is null); the other rows of the table are rewritten unchanged
+    for (int b = 0; b < n; ++b) {
+      SlotSampling& e = s.samp[slot_ids[b]];
+      e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
+      if (per_row && per_row[b].mode != 0) {
+        const idxtts_sampling& r = per_row[b];
+        e = SlotSampling{r.mode, r.temperature, r.top_k, r.top_p, r.seed, r.exp_noise};
+      }
+    }
+    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
+  }
   IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
 
   if (session_prefill_input(w.x, inputs_embeds, ld_rows, sb.plen, rows, S, d, mel_emb, mel_pos, cfg.start_mel_token, st)) return 1;
@@ -774,7 +803,8 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
   if (use_pl(s.slots)) { sa.embed.x_row = w.xrow; sa.embed.x_stats = w.stats; } else sa.embed.x_frag = w.xd;
   sa.embed.mel_emb = mel_emb; sa.embed.mel_pos = mel_pos; sa.embed.d = d;
-  if (sample_slots_forward(sa, w.slots, sb.ids, n, st)) return 1;
+  if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st))
+    return 1;
   for (int b = 0; b < n; ++b) s.busy[slot_ids[b]] = 1;
   return 0;
 }
@@ -786,7 +816,7 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_CHECK(n_steps >= 0, "n_steps");
   IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   GenScope gen_scope(this);
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
   const Buffers& w = sb.w;
   const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
   if (s.exec && s.geom != geom) s.drop_graph();
@@ -828,7 +858,7 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   Session& s = *sp;
   IDX_CHECK(codes && n_codes, "null pointer");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));

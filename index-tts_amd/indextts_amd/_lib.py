@@ -24,7 +24,8 @@ SYMBOLS = [
     "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
     "idxtts_gpt_beam_workspace_bytes", "idxtts_gpt_generate_beam",
     "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
-    "idxtts_gpt_session_read", "idxtts_gpt_session_release",
+    "idxtts_gpt_session_read", "idxtts_gpt_session_release", "idxtts_gpt_session_workspace_bytes_ex", "idxtts_gpt_session_init_ex",
+    "idxtts_gpt_session_admit_sampled",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_emovec_merge",
@@ -161,6 +162,11 @@ def load() -> ctypes.CDLL:
     lib.idxtts_gpt_session_step.argtypes = [c_void_p, c_int, c_int, c_void_p, POINTER(c_int), c_void_p, c_void_p]
     lib.idxtts_gpt_session_read.argtypes = [c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p, c_void_p]
     lib.idxtts_gpt_session_release.argtypes = [c_void_p, c_void_p]
+    lib.idxtts_gpt_session_workspace_bytes_ex.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
+    lib.idxtts_gpt_session_workspace_bytes_ex.restype = c_size_t
+    lib.idxtts_gpt_session_init_ex.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_gpt_session_admit_sampled.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p]
     lib.idxtts_gpt_latent.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_s2mel_create.argtypes = [POINTER(S2MelConfigC), POINTER(c_void_p)]
     lib.idxtts_s2mel_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
@@ -283,6 +289,7 @@ def profile_read() -> dict:
 
 
 GEMM_F32, GEMM_BF16X3 = 0, 1
+SESSION_SAMPLED = 1      # IDXTTS_SESSION_SAMPLED (include/idxtts.h)
 
 
 class StreamWorkspaces:

@@ -221,14 +221,16 @@ class UnifiedVoice:
         return [emb[i, int(p):] for i, p in enumerate(pads)]
 
     def decode_session(self, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0, do_sample: bool = False,
-                       num_beams: int = 1, use_graph: bool = True) -> "DecodeSession":
-        """Continuous batching: `slots` greedy decode rows, one KV region each, that requests enter and leave between steps
-        (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt."""
+                       num_beams: int = 1, use_graph: bool = True, sampled: bool = False) -> "DecodeSession":
+        """Continuous batching: `slots` decode rows, one KV region each, that requests enter and leave between steps
+        (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt.
+        sampled=True: every request samples with its own parameters and draws (DecodeSession.admit(..., sampling=...))."""
         if do_sample:
-            raise ValueError("decode sessions are greedy only: do_sample=True is not supported (use generate())")
+            raise ValueError("decode sessions sample per request, not session-wide: do_sample=True is not supported; the session is "
+                             "greedy unless created with sampled=True and given per-request parameters (admit(..., sampling=...))")
         if num_beams != 1:
-            raise ValueError("decode sessions are greedy only: beam search is not supported (use generate_beam())")
-        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph)
+            raise ValueError("decode sessions are greedy or sampled per request: beam search is not supported (use generate_beam())")
+        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled)
 
     # ------------------------------------------------------------------------------------------
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 100, temperature: float = 1.0, top_k: int = 50,
@@ -236,7 +238,8 @@ class UnifiedVoice:
                  tts_embeddings: Optional[torch.Tensor] = None, tts_mel_embedding=None, tts_text_pos_embedding=None,
                  repetition_penalty: float = 10.0, return_logits: bool = False, use_graph: bool = True,
                  do_sample: bool = False, sampler: str = "hf", exp_noise: Optional[torch.Tensor] = None,
-                 generator: Optional[torch.Generator] = None, forced_codes: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 generator: Optional[torch.Generator] = None, forced_codes: Optional[torch.Tensor] = None,
+                 seed: Optional[int] = None) -> torch.Tensor:
         """The accel-engine plugin contract (accel_engine.py:378-645): returns LongTensor [B, P+1+generated]
         (prompt ids followed by the generated codes, padded with the stop token).
 
@@ -245,7 +248,8 @@ class UnifiedVoice:
         transformers_generation_utils.py:1036-1044, 3222-3250), sampler="accel" = the accel engine's own Sampler
         (softmax(logits / T) / Exp(1) noise, argmax; accel_engine.py:648-659).  torch.multinomial(probs, 1) is
         argmax(probs / q) with q ~ Exp(1): `exp_noise` [max_new_tokens, B, V] supplies the draws, or `generator` draws them on the
-        CPU with one exponential_() per step, the order HF consumes them; with neither the kernels generate them (see _noise).
+        CPU with one exponential_() per step, the order HF consumes them; with neither the kernels generate them from `seed` (see
+        _noise; None = a seed drawn from torch's global RNG).
         forced_codes [B, max_new_tokens] (greedy only; a parity instrument, `idxtts_gpt_generate_forced`): the sequence is continued with
         these tokens while the returned codes are each step's own argmax -- with return_logits, the logits of a GIVEN token sequence."""
         if tts_embeddings is None:
@@ -270,7 +274,7 @@ class UnifiedVoice:
         if do_sample:
             if sampler not in ("hf", "accel"):
                 raise ValueError("sampler must be 'hf' or 'accel'")
-            noise, seed = self._noise(exp_noise, generator, (max_new_tokens, B, V))
+            noise, seed = self._noise(exp_noise, generator, (max_new_tokens, B, V), seed)
             sc = _lib.SamplingC(mode=1 if sampler == "hf" else 2, temperature=float(temperature),
                                 top_k=int(top_k or 0) if sampler == "hf" else 0,
                                 top_p=float(top_p if top_p is not None else 1.0) if sampler == "hf" else 1.0,
@@ -295,13 +299,13 @@ class UnifiedVoice:
             return out, logits[: n.value].permute(1, 0, 2).contiguous()
         return out
 
-    def _noise(self, exp_noise, generator, shape):
+    def _noise(self, exp_noise, generator, shape, seed: Optional[int] = None):
         """The Exp(1) draws of a sampled generation: (device tensor | None, seed).  An explicit `exp_noise`, or a torch `generator`
         (one exponential_() per step, the order HF consumes them: reproduces the reference's stream under that seed); with neither,
         the kernels draw from a counter-based generator keyed by a 63-bit seed taken from torch's global RNG (so torch.manual_seed
-        still makes a run repeatable) -- no [steps, B, V] tensor is materialised."""
+        still makes a run repeatable), or `seed` itself when given -- no [steps, B, V] tensor is materialised."""
         if exp_noise is None and generator is None:
-            return None, int(torch.randint(0, 2 ** 62, (1,)).item())
+            return None, int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else _seed64(seed)
         if exp_noise is None:
             exp_noise = torch.stack([torch.empty(shape[1:]).exponential_(1, generator=generator) for _ in range(shape[0])])
         if tuple(exp_noise.shape) != tuple(shape):
@@ -458,6 +462,13 @@ class UnifiedVoice:
             pass
 
 
+def _seed64(seed) -> int:
+    s = int(seed)
+    if not 0 <= s < 2 ** 64:
+        raise ValueError("seed must be in 0 .. 2**64 - 1")
+    return s
+
+
 class DecodeSession:
     """A fixed set of greedy decode rows ("slots") with one KV region each, on one HIP stream (the current stream at creation, or a
     stream of its own when that is the legacy default stream, which cannot be captured):
@@ -468,11 +479,18 @@ class DecodeSession:
     Determinism: a request's codes equal, bit for bit, row 0 of UnifiedVoice.generate on `slots` copies of its prompt
     (attention_mask=None) with max_new_tokens = its cap -- whatever else is in flight, when it was admitted and which slot it has.
     With a bf16 KV cache in split-bf16 GEMM mode that reference batch needs slots * (P + 1) >= 256 prefill rows (or the exact
-    GEMM mode).  Results can depend on `slots`: the decode attention's key split and the decode GEMV are chosen from it."""
+    GEMM mode).  Results can depend on `slots`: the decode attention's key split and the decode GEMV are chosen from it.
+
+    sampled=True: admit(rows, caps, sampling=...) gives each request its own sampler -- a dict per row with `sampler` ("greedy" |
+    "hf" | "accel"), `temperature`, `top_k`, `top_p` (HF only), and `seed` or `exp_noise` [cap, V].  A sampled request's codes equal,
+    bit for bit, row 0 of generate(do_sample=True, sampler=..., temperature=..., top_k=..., top_p=..., seed=seed) on `slots` copies of
+    its prompt (with exp_noise: generate's exp_noise whose row 0 is the request's noise); greedy rows equal those of a greedy session.
+    The repetition penalty is the session's (the HF sampler applies it, the accel sampler does not)."""
 
     def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
-                 use_graph: bool = True):
+                 use_graph: bool = True, sampled: bool = False):
         self.gpt = gpt
+        self.sampled = bool(sampled)
         self.slots, self.max_prompt, self.max_new = int(slots), int(max_prompt), int(max_new)
         self.use_graph = bool(use_graph)
         self._lib = _lib.load()
@@ -480,14 +498,16 @@ class DecodeSession:
         if self.stream.cuda_stream == 0:        # the legacy default stream cannot be captured: a stream of the session's own
             self.stream = torch.cuda.Stream(device=gpt.device)
             self.stream.wait_stream(torch.cuda.current_stream(gpt.device))
-        need = int(self._lib.idxtts_gpt_session_workspace_bytes(gpt._h, self.slots, self.max_prompt, self.max_new))
+        flags = _lib.SESSION_SAMPLED if self.sampled else 0
+        need = int(self._lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, self.slots, self.max_prompt, self.max_new, flags))
         if need == 0:
             raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
         with torch.cuda.stream(self.stream):
             self._ws = torch.empty(need, dtype=torch.uint8, device=gpt.device)
-            _lib.check(self._lib.idxtts_gpt_session_init(gpt._h, self.slots, self.max_prompt, self.max_new, float(repetition_penalty),
-                                                         _lib.ptr(self._ws), need, self._sp()))
+            _lib.check(self._lib.idxtts_gpt_session_init_ex(gpt._h, self.slots, self.max_prompt, self.max_new, float(repetition_penalty),
+                                                            flags, _lib.ptr(self._ws), need, self._sp()))
         self._busy = [False] * self.slots
+        self._noise = {}          # slot -> the exp_noise tensor its request reads (kept alive until take())
         self._done = set()
 
     def _sp(self) -> c_void_p:
@@ -501,8 +521,51 @@ class DecodeSession:
     def live_slots(self):
         return [i for i, b in enumerate(self._busy) if b and i not in self._done]
 
-    def admit(self, inputs_embeds_rows, max_new_each) -> list:
-        """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int)."""
+    def _samplers(self, sampling, caps):
+        """sampling (one dict per row, or one dict for every row) -> (SamplingC array, noise tensors); raises ValueError on a bad row."""
+        entries = [sampling] * len(caps) if isinstance(sampling, dict) else list(sampling)
+        if len(entries) != len(caps):
+            raise ValueError("sampling: one entry per row, or one entry for every row")
+        V = self.gpt.cfg.number_mel_codes
+        arr = (_lib.SamplingC * len(caps))()
+        noises = []
+        for i, (e, cap) in enumerate(zip(entries, caps)):
+            unknown = set(e) - {"sampler", "temperature", "top_k", "top_p", "seed", "exp_noise"}
+            if unknown:
+                raise ValueError(f"sampling: unknown keys {sorted(unknown)}")
+            kind = e.get("sampler", "hf")
+            noise = None
+            if kind == "greedy":
+                arr[i] = _lib.SamplingC(mode=0, temperature=1.0, top_k=0, top_p=1.0, exp_noise=None, seed=0)
+            elif kind in ("hf", "accel"):
+                t = float(e.get("temperature", 1.0))
+                k = int(e.get("top_k") or 0) if kind == "hf" else 0
+                p = float(e.get("top_p") if e.get("top_p") is not None else 1.0) if kind == "hf" else 1.0
+                if not t > 0.0:
+                    raise ValueError("sampling needs a positive temperature")
+                if k < 0 or not p > 0.0:
+                    raise ValueError("top_k must be >= 0 and top_p > 0")
+                if p < 1.0 and not 0 < k <= 1024:
+                    raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
+                seed = 0
+                if e.get("exp_noise") is not None:
+                    noise = torch.as_tensor(e["exp_noise"]).to(self.gpt.device, torch.float32).contiguous()
+                    if tuple(noise.shape) != (cap, V):
+                        raise ValueError(f"exp_noise must be [cap, V] = {(cap, V)}")
+                elif e.get("seed") is not None:
+                    seed = _seed64(e["seed"])
+                else:
+                    seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # as generate() draws it
+                arr[i] = _lib.SamplingC(mode=1 if kind == "hf" else 2, temperature=t, top_k=k, top_p=p,
+                                        exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
+            else:
+                raise ValueError("sampler must be 'greedy', 'hf' or 'accel'")
+            noises.append(noise)
+        return arr, noises
+
+    def admit(self, inputs_embeds_rows, max_new_each, sampling=None) -> list:
+        """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int).
+        sampling (sampled sessions): None = every row greedy, else one dict per row or one for every row (see the class)."""
         rows = [r.to(self.gpt.device, torch.float32) for r in inputs_embeds_rows]
         n = len(rows)
         if n == 0:
@@ -520,19 +583,29 @@ class DecodeSession:
                 raise ValueError(f"a prompt row must be [P, {d}] with 1 <= P <= {self.max_prompt}")
             if not 1 <= c <= self.max_new:
                 raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        if sampling is not None and not self.sampled:
+            raise ValueError("sampling= needs a session created with sampled=True")
         ids = free[:n]
         self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
         with torch.cuda.stream(self.stream):
+            samplers, noises = self._samplers(sampling, caps) if sampling is not None else (None, [None] * n)
             pm = max(plen)
             emb = torch.zeros(n, pm, d, device=self.gpt.device, dtype=torch.float32)
             for i, r in enumerate(rows):
                 emb[i, : plen[i]] = r
             h_p, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, ids, caps))
-            _lib.check(self._lib.idxtts_gpt_session_admit(
-                self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
-                h_caps.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
-        for i in ids:
+            if samplers is None:
+                _lib.check(self._lib.idxtts_gpt_session_admit(
+                    self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
+                    h_caps.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
+            else:
+                _lib.check(self._lib.idxtts_gpt_session_admit_sampled(
+                    self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
+                    h_caps.ctypes.data_as(c_void_p), ctypes.cast(samplers, c_void_p), _lib.ptr(self._ws), self._sp()))
+        for i, nz in zip(ids, noises):
             self._busy[i] = True
+            if nz is not None:
+                self._noise[i] = nz
         return ids
 
     def step(self, n: int = 1) -> list:
@@ -556,6 +629,7 @@ class DecodeSession:
                                                          self._sp()))
         self._busy[slot] = False
         self._done.discard(slot)
+        self._noise.pop(slot, None)
         return out[: n.value]
 
     def close(self) -> None:

@@ -276,7 +276,43 @@ class BatchPipeline:
 
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed")
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed", "sampling")
+
+
+_SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
+
+
+def utterance_samplers(sampling: Optional[dict], n: int) -> list:
+    """The per-utterance samplers of a ContinuousPipeline request (DecodeSession.admit's `sampling` entries).  `sampling` is the dict
+    gpt_stage / BatchPipeline take (do_sample, temperature, top_k, top_p, sampler, generator) plus `seed`; missing values take
+    UnifiedVoice.generate's defaults (temperature 1.0, top_k 50, top_p 1.0).  Greedy (no dict, or do_sample false): {"sampler":
+    "greedy"} for every utterance.  Sampled: utterance i gets seed torch.randint(0, 2**62, (1,), generator=g), drawn in utterance
+    order, with g = torch.Generator().manual_seed(seed) when `seed` is given, else the request's `generator`, else torch's global RNG.
+    Raises ValueError on a bad parameter."""
+    s = dict(sampling or {})
+    unknown = set(s) - _SAMPLING_KEYS
+    if unknown:
+        raise ValueError(f"sampling: unknown keys {sorted(unknown)}")
+    if int(s.get("num_beams") or 1) > 1:
+        raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
+    if not s.get("do_sample"):
+        return [{"sampler": "greedy"} for _ in range(n)]
+    kind = s.get("sampler") or "hf"
+    if kind not in ("hf", "accel"):
+        raise ValueError("sampler must be 'hf' or 'accel'")
+    t = float(s["temperature"]) if s.get("temperature") is not None else 1.0
+    k = int(s["top_k"]) if s.get("top_k") is not None else 50
+    p = float(s["top_p"]) if s.get("top_p") is not None else 1.0
+    if not t > 0.0:
+        raise ValueError("sampling needs a positive temperature")
+    if kind == "hf":
+        if k < 0 or not p > 0.0:
+            raise ValueError("top_k must be >= 0 and top_p > 0")
+        if p < 1.0 and not 0 < k <= 1024:
+            raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
+    g = torch.Generator().manual_seed(int(s["seed"])) if s.get("seed") is not None else s.get("generator")
+    seeds = [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
+    return [{"sampler": kind, "temperature": t, "top_k": k, "top_p": p, "seed": sd} for sd in seeds]
 
 
 class ContinuousPipeline:
@@ -287,16 +323,19 @@ class ContinuousPipeline:
     the longest row of a static batch runs on.  Once every row of a request is decoded, the request goes through the existing
     path behind the decode: `gpt_stage(text, cond, codes=...)` (trim + latent pass) and `acoustic_stage` on an acoustic worker.
 
-    Greedy only.  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on `slots` copies of each of its utterances
-    (gpt.DecodeSession), whatever else shares the session; they can differ from `BatchPipeline` / `synthesize_batch` results, whose
-    decode batch is the request itself (the decode attention's key split and the decode GEMV are chosen by row count).  An error
-    (say, a bad token id) fails the offending request's Future only.
+    Greedy, unless allow_sampling: then the sessions are sampled (decode_session(sampled=True)) and submit(sampling=...) takes the
+    dict gpt_stage / BatchPipeline take, plus `seed` (utterance_samplers: the per-utterance seeds are fixed at submit, so a request's
+    audio is reproducible whatever else is in flight).  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on
+    `slots` copies of each of its utterances (gpt.DecodeSession; sampled: with that utterance's sampler and seed), whatever else
+    shares the session; they can differ from `BatchPipeline` / `synthesize_batch` results, whose decode batch is the request itself
+    (the decode attention's key split and the decode GEMV are chosen by row count).  An error (say, a bad token id or a bad sampling
+    parameter) fails the offending request's Future only; num_beams > 1 is refused at submit.
 
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
-                 session_factory=None):
+                 session_factory=None, allow_sampling: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers and poll_steps must be >= 1")
         g = tts.cfg.gpt
@@ -305,7 +344,9 @@ class ContinuousPipeline:
         self.slots, self.poll_steps, self.repetition_penalty = slots, poll_steps, float(repetition_penalty)
         self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
         self.max_new = int(max_new or g.max_mel_tokens)
-        self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty))
+        self.allow_sampling = bool(allow_sampling)
+        self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty,
+                                                                                 sampled=self.allow_sampling))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index) not admitted yet
@@ -331,9 +372,12 @@ class ContinuousPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None) -> concurrent.futures.Future:
-        """BatchPipeline.submit's contract (a Future of the list of waveforms), greedy only; max_mel_tokens caps each row."""
-        if sampling:
-            raise ValueError("ContinuousPipeline decodes greedily; use BatchPipeline for sampling")
+        """BatchPipeline.submit's contract (a Future of the list of waveforms); max_mel_tokens caps each row.  sampling: greedy
+        only, unless the pipeline was built with allow_sampling (see utterance_samplers)."""
+        if sampling and not self.allow_sampling:
+            raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
+        if sampling and int(sampling.get("num_beams") or 1) > 1:
+            raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -343,6 +387,13 @@ class ContinuousPipeline:
         B = int(j.text.shape[0])
         j.codes, j.left, j.failed = [None] * B, B, False
         j.done = concurrent.futures.Future()
+        j.sampling = None
+        if self.allow_sampling:
+            try:
+                j.sampling = utterance_samplers(sampling, B)
+            except ValueError as e:             # a bad parameter fails this request's Future only
+                j.done.set_exception(e)
+                return j.done
         j.caller = torch.cuda.current_stream(self.device) if self._cuda else None
         j.ready = None
         if self._cuda:
@@ -381,7 +432,7 @@ class ContinuousPipeline:
         by_job = collections.OrderedDict()
         for j, i in take:
             by_job.setdefault(id(j), (j, []))[1].append(i)
-        rows, caps, owners = [], [], []
+        rows, caps, owners, samplers = [], [], [], []
         for j, idx in by_job.values():
             try:
                 rs = self._prompt_rows(j, idx)
@@ -393,9 +444,11 @@ class ContinuousPipeline:
             rows.extend(rs)
             caps.extend([j.max_mel_tokens] * len(idx))
             owners.extend((j, i) for i in idx)
+            if self.allow_sampling:
+                samplers.extend(j.sampling[i] for i in idx)
         if rows:
             try:
-                got = sess.admit(rows, caps)
+                got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
             except BaseException as e:       # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
                 for j, _ in owners:
                     self._fail(j, e)

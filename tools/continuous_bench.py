@@ -8,8 +8,10 @@ exactly the caps):
       until its longest row is done).  Throughput counts the audio of the utterances' own caps for both (for BatchPipeline the
       acoustic stage also renders the padding codes: an upper bound of its cost where rows would stop on their own).
 The two pipelines alternate, every shape is warmed up first, and each is repeated so the spread is known.  Prints one JSON line.
+--sampling compares ContinuousPipeline with greedy requests against ContinuousPipeline(allow_sampling=True) with HF-sampled requests
+(temperature 0.8, top_k 30, top_p 0.8: IndexTTS2.infer's defaults; one seed per request) on the same workloads instead.
 
-    python tools/continuous_bench.py [--utterances 64] [--reps 3]
+    python tools/continuous_bench.py [--utterances 64] [--reps 3] [--sampling]
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ def main() -> int:
     ap.add_argument("--slots", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--poll-steps", type=int, default=16)
+    ap.add_argument("--sampling", action="store_true", help="greedy against HF-sampled requests, both on ContinuousPipeline")
     args = ap.parse_args()
     from indextts_amd import synth, weights
     from indextts_amd.config import PipelineConfig
@@ -71,18 +74,30 @@ def main() -> int:
 
     pipes = {"batch": lambda: BatchPipeline(tts, decode_lanes=1),
              "continuous": lambda: ContinuousPipeline(tts, slots=W, decode_lanes=1, poll_steps=args.poll_steps, max_new=800)}
+    sampling = {}
+    if args.sampling:
+        pipes = {"continuous": pipes["continuous"],
+                 "continuous_sampled": lambda: ContinuousPipeline(tts, slots=W, decode_lanes=1, poll_steps=args.poll_steps, max_new=800,
+                                                                  allow_sampling=True)}
+        for wl in jobs:
+            jobs[wl]["continuous_sampled"] = jobs[wl]["continuous"]
+        sampling["continuous_sampled"] = {"do_sample": True, "temperature": 0.8, "top_k": 30, "top_p": 0.8}
 
     def run(kind, wl):
         with pipes[kind]() as pipe:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            futs = [pipe.submit(t, cond, max_mel_tokens=M, noise=z) for t, M, z in jobs[wl][kind]]
+            sp = sampling.get(kind)
+            futs = [pipe.submit(t, cond, max_mel_tokens=M, noise=z, sampling=dict(sp, seed=i) if sp else None)
+                    for i, (t, M, z) in enumerate(jobs[wl][kind])]
             for f in futs:
                 f.result()
             torch.cuda.synchronize()
             return time.perf_counter() - t0
 
-    out = {"utterances": N, "slots": W, "text_tokens": L, "prompt_frames": Tp, "reps": args.reps, "poll_steps": args.poll_steps}
+    out = {"utterances": N, "slots": W, "text_tokens": L, "prompt_frames": Tp, "reps": args.reps, "poll_steps": args.poll_steps,
+           "sampling": bool(args.sampling)}
+    base, other = ("continuous", "continuous_sampled") if args.sampling else ("batch", "continuous")
     for wl in caps:
         for kind in pipes:          # warm-up: every shape (prefill widths, graphs, acoustic lengths) once
             run(kind, wl)
@@ -91,7 +106,7 @@ def main() -> int:
             for kind in pipes:      # alternated
                 rates[kind].append(jobs[wl]["audio_s"] / run(kind, wl))
         out[wl] = {k: {"audio_s_per_s_median": float(np.median(v)), "min": float(min(v)), "max": float(max(v))} for k, v in rates.items()}
-        out[wl]["continuous_over_batch"] = out[wl]["continuous"]["audio_s_per_s_median"] / out[wl]["batch"]["audio_s_per_s_median"]
+        out[wl][f"{other}_over_{base}"] = out[wl][other]["audio_s_per_s_median"] / out[wl][base]["audio_s_per_s_median"]
         out[wl]["audio_s"] = jobs[wl]["audio_s"]
         print(f"[continuous_bench] {wl}: {json.dumps(out[wl])}", file=sys.stderr, flush=True)
     print(json.dumps(out))
