@@ -313,6 +313,30 @@ int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int m
 int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                                      const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_row, void* workspace,
                                      void* stream);
+/* Beam sessions (beam search / beam-sample per request, idxtts_gpt_generate_beam's semantics): the `slots` rows form slots / num_beams
+ * groups of num_beams consecutive slots (2 <= num_beams <= 8, slots % num_beams == 0, slots <= 64); each admitted request takes one
+ * group and runs HF _beam_search + BeamSearchScorer with its own idxtts_beam.  A group retires when its scorer is done
+ * (BeamHypotheses.is_done with the request's early_stopping / length_penalty) or at the request's cap; _step then reports the group's
+ * FIRST slot, and _read on that slot returns the best hypothesis followed by the stop token if it fits under the cap (reading any other
+ * slot of a group is refused) and frees the group.  _admit / _admit_sampled on a beam session are refused, as is _admit_beam on any
+ * other session.  The repetition penalty is the session's.
+ * Determinism: a beam request's codes equal, bit for bit, row 0 of idxtts_gpt_generate_beam (same num_beams, do_sample, temperature,
+ * top_k, top_p, length_penalty, early_stopping, repetition penalty) on slots / num_beams copies of its prompt with no left padding and
+ * max_new_tokens = its cap -- with the same seed, or with exp_noise whose [:, 0, :] is the request's noise -- cut after its first stop
+ * token (or cap codes), whatever else is in flight, whenever it was admitted and whichever group it has, under the greedy rule's
+ * conditions above (bf16 KV in split-bf16 mode: slots * (P + 1) >= 256). */
+size_t idxtts_gpt_session_workspace_bytes_beam(const idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens);
+int idxtts_gpt_session_init_beam(idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens, float repetition_penalty,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* Admits n requests into the free groups group_ids (HOST int32 [n], 0 .. slots / num_beams - 1); inputs_embeds, ld_rows, prompt_lens and
+ * max_new_tokens as in _admit (one prompt row set per request, its prefill runs once).  per_request: HOST [n] idxtts_beam, num_beams equal
+ * to the session's; exp_noise NULL or device fp32 [max_new_tokens[b]][num_beams * V], kept alive by the caller until the group is read
+ * (row t = the draws of the request's step t); with NULL the draws come from `seed`, the stream row 0 of a slots / num_beams-utterance
+ * idxtts_gpt_generate_beam uses.  Every request is checked first (generate_beam's rules, num_beams, the cap): a bad one refuses the
+ * whole call, no group taken.  Runs their prefill and first beam step. */
+int idxtts_gpt_session_admit_beam(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                  const int* group_ids, const int* max_new_tokens, const idxtts_beam* per_request, void* workspace,
+                                  void* stream);
 /* Runs n_steps decode steps for every live slot (a captured hipGraph is replayed when use_graph), then reports the slots that hold a
  * finished request not read yet: finished_slots HOST int32 [slots] (may be NULL), *n_finished. */
 int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* finished_slots, int* n_finished, void* workspace,

@@ -9,6 +9,18 @@ namespace idxtts {
 
 constexpr int BEAM_MAX = 8;     // num_beams <= 8 (the reference default is 3)
 
+// Per-request parameters of a beam decode session (one row per group, in the session workspace; idxtts_beam's values)
+struct SlotBeam {
+  int do_sample;
+  float temperature;
+  int top_k;
+  float top_p;
+  double length_penalty;
+  int early_stopping;
+  unsigned long long seed;       // draws when exp_noise is null: exp1_draw(seed, (t * groups + 0) * nb * V + i) at the group's step t
+  const float* exp_noise;        // the request's draws [max_step][nb * V] (row t at step t), or null
+};
+
 struct BeamState {
   // per decode row r = b * nb + j
   const float* logits = nullptr;      // [R][V] raw lm_head output of this step
@@ -36,6 +48,17 @@ struct BeamState {
   int do_sample = 0, top_k = 0, early_stopping = 0;
   float penalty = 1.0f, temperature = 1.0f, top_p = 1.0f;
   double length_penalty = 0.0;
+  // Beam decode session (slots != null; gpt.hip "decode session"): B groups of nb consecutive slots, each group one request.  Every
+  // per-group value comes from the workspace -- step / pos / mel_pos from the group's SlotState (its first slot; all nb are equal), the
+  // request's parameters from group[g] (the scalar parameters above are unused), the KV range that moves from pos - step + 1 = P_g + 1
+  // -- so a captured step stays valid across admissions.  Groups that are not live do nothing.  The last stage ends a group (done or
+  // cap: live = 0 on its slots, step = steps taken) or writes its rows' next inputs x = mel_emb[tok] + mel_pos[mel_pos + 1] (x_row +
+  // x_stats on the plane GEMV path, else x_frag) and advances its slots: no embed_step / advance_state.
+  SlotState* slots = nullptr;
+  const SlotBeam* group = nullptr;
+  const int* group_ids = nullptr; int n_ids = 0;      // admission: these groups only (every group when null)
+  float* x_row = nullptr; float* x_stats = nullptr; float* x_frag = nullptr;
+  const float* mel_emb = nullptr; const float* mel_pos = nullptr; int d = 0;
 };
 
 // log_softmax -> repetition penalty -> (sampling: temperature, top-k, top-p with min_tokens_to_keep = 2) -> + beam score
@@ -44,6 +67,12 @@ int beam_scores_forward(const BeamState& s, hipStream_t st);
 // BeamSearchScorer.process: finished hypotheses, next beams, done flags
 int beam_select_forward(const BeamState& s, hipStream_t st);
 // re-index token history, seen masks, KV cache rows (generated positions only) by beam_idx; append the chosen tokens
+// (session mode: the KV launch first, then the rows launch with the fused tail; no KV launch for an admission, whose step is 0)
 int beam_reorder_forward(const BeamState& s, hipStream_t st);
+// Beam session admission, per admitted group b (group_ids[b]; s.slots / s.group / s.nb set): reset its nb slots -- seen = {1,
+// start_token}, SlotState {P[b], 1, 0, cap[b], 1}, x_last[slot] = x[b][P[b]] (x [n][S][d]) -- and its scorer: beam scores 0, -1e9, ...,
+// hyp_n 0, hyp_worst 1e9, done 0
+int beam_session_reset(const BeamState& s, int start_token, float* x_last, const float* x, int S, const int* P, const int* cap, int n,
+                       hipStream_t st);
 
 }  // namespace idxtts

@@ -49,6 +49,9 @@ __device__ __forceinline__ float block_sum1024(float v, float* rv, int tid) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
+// SESSION (beam decode session, beam.h): block -> row nb * g + j of group g (group_ids[blockIdx.x / nb] at an admission), the request's
+// parameters from group[g]; a group that is not live returns at once
+template <bool SESSION>
 __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
   __shared__ float rv[16];
   __shared__ int ri[16];
@@ -59,8 +62,18 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
   __shared__ int s_count, s_thr_i, s_digit, s_kk;
   __shared__ int hist[16][256];
   __shared__ float s_thr_v;
-  const int r = blockIdx.x, tid = threadIdx.x, V = p.V;
-  if (p.done[r / p.nb]) return;
+  const int tid = threadIdx.x, V = p.V;
+  int r = blockIdx.x, do_sample = p.do_sample, top_k = p.top_k;
+  float temperature = p.temperature, top_p = p.top_p;
+  if constexpr (SESSION) {
+    const int g = p.group_ids ? p.group_ids[blockIdx.x / p.nb] : blockIdx.x / p.nb;
+    r = g * p.nb + blockIdx.x % p.nb;
+    if (!p.slots[g * p.nb].live) return;
+    const SlotBeam& gb = p.group[g];
+    do_sample = gb.do_sample; top_k = gb.top_k; temperature = gb.temperature; top_p = gb.top_p;
+  } else {
+    if (p.done[r / p.nb]) return;
+  }
   const float* lrow = p.logits + (size_t)r * V;
   const unsigned char* seen = p.seen + (size_t)r * V;
   float sc[NPT];
@@ -83,12 +96,12 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
     if (v < V) {
       float s = (sc[u] - mx) - lse;
       if (p.penalty != 1.0f && seen[v]) s = s < 0.f ? s * p.penalty : s / p.penalty;
-      if (p.do_sample && p.temperature != 1.0f) s = s / p.temperature;
+      if (do_sample && temperature != 1.0f) s = s / temperature;
       sc[u] = s;
     }
   }
-  if (p.do_sample && (p.top_k > 0 || p.top_p < 1.0f)) {
-    const int k = p.top_k > 0 ? max(p.top_k, 2) : 0;         // TopKLogitsWarper: max(top_k, min_tokens_to_keep)
+  if (do_sample && (top_k > 0 || top_p < 1.0f)) {
+    const int k = top_k > 0 ? max(top_k, 2) : 0;         // TopKLogitsWarper: max(top_k, min_tokens_to_keep)
     if (k > 0 && k < V) {
       // the k-th largest score by a radix select over order-preserving 32-bit keys (four 8-bit digits, high to low): per-wave
       // histograms in LDS, one wave walks the 256 bins from the top -- 16 barriers in all instead of 2 k block-wide argmax rounds
@@ -145,7 +158,7 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
 #pragma unroll
       for (int u = 0; u < NPT; ++u) if (sc[u] < kth) sc[u] = -INFINITY;
     }
-    if (p.top_p < 1.0f) {
+    if (top_p < 1.0f) {
       if (tid == 0) s_count = 0;
       __syncthreads();
 #pragma unroll
@@ -170,7 +183,7 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
         const float top = sorted_v[n - 1];
         float tot = 0.f;
         for (int e = 0; e < n; ++e) tot += expf(sorted_v[e] - top);
-        const float thr = (float)(1.0 - (double)p.top_p);
+        const float thr = (float)(1.0 - (double)top_p);
         float cum = 0.f;
         for (int e = 0; e < n - 2; ++e) {
           cum += expf(sorted_v[e] - top) / tot;
@@ -199,27 +212,52 @@ int beam_scores_forward(const BeamState& s, hipStream_t st) {
   IDX_CHECK(s.logits && s.proc && s.seen && s.beam_scores && s.done, "null pointer");
   IDX_CHECK(s.V > 0 && s.V <= 1024 * NPT && s.nb >= 2 && s.nb <= BEAM_MAX, "beam shape");
   static const int cat = prof_register("beam_scores_kernel");
-  ProfScope prof(cat, st, 0.0, 8.0 * s.B * s.nb * (double)s.V);
-  hipLaunchKernelGGL(beam_scores_kernel, dim3(s.B * s.nb), dim3(1024), 0, st, s);
+  const int groups = s.slots && s.group_ids ? s.n_ids : s.B;
+  ProfScope prof(cat, st, 0.0, 8.0 * groups * s.nb * (double)s.V);
+  if (s.slots) {
+    IDX_CHECK(s.group, "null pointer");
+    hipLaunchKernelGGL(beam_scores_kernel<true>, dim3(groups * s.nb), dim3(1024), 0, st, s);
+  } else {
+    hipLaunchKernelGGL(beam_scores_kernel<false>, dim3(s.B * s.nb), dim3(1024), 0, st, s);
+  }
   IDX_LAUNCH_CHECK();
   return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// SESSION: block -> group g (group_ids[blockIdx.x] at an admission); n = the group's step, the request's parameters and draws
+// (its own exp_noise row n, or the seed's stream at row 0 of a B-group generate_beam); a group that is not live returns at once
+template <bool SESSION>
 __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
   __shared__ float rv[16];
   __shared__ int ri[16];
   __shared__ int cand_i[2 * BEAM_MAX];
   __shared__ float cand_s[2 * BEAM_MAX];
   __shared__ int cp_slot[BEAM_MAX], cp_src[BEAM_MAX], n_cp;
-  const int b = blockIdx.x, tid = threadIdx.x, nb = p.nb, V = p.V, N = nb * V;
-  const int n = p.st->step;                   // tokens each live beam holds before this step
-  if (p.done[b]) {                            // BeamSearchScorer.process pads a finished utterance
-    if (tid < nb) { p.next_tok[b * nb + tid] = p.stop_token; p.beam_idx[b * nb + tid] = b * nb + tid; p.beam_scores[b * nb + tid] = 0.f; }
-    return;
+  const int tid = threadIdx.x, nb = p.nb, V = p.V, N = nb * V;
+  int b = blockIdx.x, n, do_sample = p.do_sample, early_stopping = p.early_stopping;
+  const float* exp_noise = p.exp_noise;
+  unsigned long long seed = p.seed;
+  double length_penalty = p.length_penalty;
+  size_t nbase;
+  if constexpr (SESSION) {
+    if (p.group_ids) b = p.group_ids[blockIdx.x];
+    const SlotState& ss = p.slots[b * nb];
+    if (!ss.live) return;
+    n = ss.step;
+    const SlotBeam& gb = p.group[b];
+    do_sample = gb.do_sample; early_stopping = gb.early_stopping; exp_noise = gb.exp_noise; seed = gb.seed;
+    length_penalty = gb.length_penalty;
+    nbase = exp_noise ? (size_t)n * N : (size_t)n * p.B * N;
+  } else {
+    n = p.st->step;                           // tokens each live beam holds before this step
+    if (p.done[b]) {                          // BeamSearchScorer.process pads a finished utterance
+      if (tid < nb) { p.next_tok[b * nb + tid] = p.stop_token; p.beam_idx[b * nb + tid] = b * nb + tid; p.beam_scores[b * nb + tid] = 0.f; }
+      return;
+    }
+    nbase = ((size_t)n * p.B + b) * N;
   }
   const float* base = p.proc + (size_t)b * N;
-  const size_t nbase = ((size_t)n * p.B + b) * N;
   const int n_keep = 2 * nb;
   // multinomial without replacement = the n_keep largest probs / q (ATen: q ~ Exp(1) once per element, then topk); plain
   // top-k of the scores when not sampling.  Ties (only among zero-probability fillers) go to the smaller index.
@@ -235,7 +273,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
       if (i < N && (ks[e] > mx || (ks[e] == mx && i < mi))) { mx = ks[e]; mi = i; }
     }
     block_argmax1024(mx, mi, rv, ri, tid);
-    if (p.do_sample) {
+    if (do_sample) {
       float part = 0.f;
 #pragma unroll
       for (int e = 0; e < SEL_EPT; ++e) if (tid + 1024 * e < N) part += expf(ks[e] - mx);
@@ -243,7 +281,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
 #pragma unroll
       for (int e = 0; e < SEL_EPT; ++e) {
         const int i = tid + 1024 * e;
-        if (i < N) ks[e] = (expf(ks[e] - mx) / tot) / exp1_draw(p.exp_noise, p.seed, nbase + i);
+        if (i < N) ks[e] = (expf(ks[e] - mx) / tot) / exp1_draw(exp_noise, seed, nbase + i);
       }
     }
     unsigned taken = 0;
@@ -264,7 +302,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
     for (int i = tid; i < N; i += 1024) { const float x = base[i]; if (x > mx || (x == mx && i < mi)) { mx = x; mi = i; } }
     block_argmax1024(mx, mi, rv, ri, tid);
     float tot = 1.0f;
-    if (p.do_sample) {
+    if (do_sample) {
       float part = 0.f;
       for (int i = tid; i < N; i += 1024) part += expf(base[i] - mx);
       tot = block_sum1024(part, rv, tid);
@@ -276,7 +314,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
         for (int o = 0; o < c; ++o) taken = taken || cand_i[o] == i;
         if (taken) continue;
         const float x = base[i];
-        const float key = p.do_sample ? (expf(x - mx) / tot) / exp1_draw(p.exp_noise, p.seed, nbase + i) : x;
+        const float key = do_sample ? (expf(x - mx) / tot) / exp1_draw(exp_noise, seed, nbase + i) : x;
         if (key > best || (key == best && i < bi)) { best = key; bi = i; }
       }
       block_argmax1024(best, bi, rv, ri, tid);
@@ -298,7 +336,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
     int hn = p.hyp_n[b];
     double worst = p.hyp_worst[b];
     const int gen_len = n + 1;                                  // cur_len - decoder_prompt_len
-    const double denom = pow((double)gen_len, p.length_penalty);
+    const double denom = pow((double)gen_len, length_penalty);
     int slot = 0, ncp = 0;
     for (int rank = 0; rank < n_keep && slot < nb; ++rank) {
       const int tok = cand_i[rank] % V, src = b * nb + cand_i[rank] / V;
@@ -334,7 +372,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
     n_cp = ncp;
     // BeamHypotheses.is_done with the best candidate of this step
     bool fin = false;
-    if (hn >= nb) fin = p.early_stopping ? true : worst >= (double)cand_s[0] / denom;
+    if (hn >= nb) fin = early_stopping ? true : worst >= (double)cand_s[0] / denom;
     if (fin) p.done[b] = 1;
   }
   __syncthreads();
@@ -346,19 +384,38 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
 }
 
 int beam_select_forward(const BeamState& s, hipStream_t st) {
-  IDX_CHECK(s.proc && s.next_tok && s.beam_idx && s.seq && s.hyp_score && s.hyp_len && s.hyp_slot && s.hyp_seq && s.hyp_n && s.hyp_worst && s.st, "null pointer");
-  hipLaunchKernelGGL(beam_select_kernel, dim3(s.B), dim3(1024), 0, st, s);
+  IDX_CHECK(s.proc && s.next_tok && s.beam_idx && s.seq && s.hyp_score && s.hyp_len && s.hyp_slot && s.hyp_seq && s.hyp_n && s.hyp_worst &&
+            (s.st || s.slots), "null pointer");
+  if (s.slots) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(s.group_ids ? s.n_ids : s.B), dim3(1024), 0, st, s);
+  else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(s.B), dim3(1024), 0, st, s);
   IDX_LAUNCH_CHECK();
   return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// SESSION: block -> group; a group that is not live returns at once, a group the scorer has just finished ends (live = 0 and step = the
+// steps taken, on all its slots).  Otherwise the re-indexing and the new tokens as below, then the fused tail: the group ends at its
+// cap, or each of its rows gets its next input row (slot_tail's write, sample_slots) and its slots advance.
+template <bool SESSION>
 __global__ __launch_bounds__(1024) void beam_reorder_rows_kernel(const BeamState p) {
-  const int b = blockIdx.x, tid = threadIdx.x, nb = p.nb, V = p.V;
-  const int n = p.st->step;
-  if (p.done[b]) {
-    if (tid < nb) { p.cur_tok[b * nb + tid] = p.stop_token; if (n < p.seq_ld) p.seq[(size_t)(b * nb + tid) * p.seq_ld + n] = p.stop_token; }
-    return;
+  const int tid = threadIdx.x, nb = p.nb, V = p.V;
+  int b = blockIdx.x, n, mp = 0, max_step = 0;
+  if constexpr (SESSION) {
+    if (p.group_ids) b = p.group_ids[blockIdx.x];
+    const SlotState ss = p.slots[b * nb];      // read by every thread before the barrier below; written after it
+    if (!ss.live) return;
+    n = ss.step; mp = ss.mel_pos; max_step = ss.max_step;
+    if (p.done[b]) {
+      __syncthreads();
+      if (tid < nb) { p.slots[b * nb + tid].live = 0; p.slots[b * nb + tid].step = n + 1; }
+      return;
+    }
+  } else {
+    n = p.st->step;
+    if (p.done[b]) {
+      if (tid < nb) { p.cur_tok[b * nb + tid] = p.stop_token; if (n < p.seq_ld) p.seq[(size_t)(b * nb + tid) * p.seq_ld + n] = p.stop_token; }
+      return;
+    }
   }
   int src[BEAM_MAX];
   bool identity = true;
@@ -382,19 +439,47 @@ __global__ __launch_bounds__(1024) void beam_reorder_rows_kernel(const BeamState
     p.seen[(size_t)r * V + tok] = 1;
     p.cur_tok[r] = tok;
   }
+  if constexpr (SESSION) {
+    SlotState* const ss = p.slots + b * nb;
+    if (n + 1 >= max_step) {      // the request's cap: the open beams are final (finalize reads them with step = cap)
+      if (tid < nb) { ss[tid].live = 0; ss[tid].step = n + 1; }
+      return;
+    }
+    const int R = p.B * nb;
+    for (int j = 0; j < nb; ++j) {
+      const int r = b * nb + j, tok = p.next_tok[r];
+      if (p.x_frag) {
+        const int d = p.d;
+        for (int e = tid; e < d; e += 1024) p.x_frag[frag_index(r, e, d >> 4)] = p.mel_emb[(size_t)tok * d + e] + p.mel_pos[(size_t)(mp + 1) * d + e];
+      } else {
+        embed_row_pl<1024>(p.x_row, p.x_stats, r, R, p.d, p.mel_emb, p.mel_pos, tok, mp + 1, tid);
+      }
+    }
+    if (tid < nb) { ss[tid].pos += 1; ss[tid].mel_pos += 1; ss[tid].step += 1; }      // the group's own scalars: read by nobody else
+  }
 }
 
 // KV rows of the generated positions [prompt_len, pos]: 16-byte granules (G per key: 16 in a fp32 cache, 8 in a bf16 one), a thread moves
 // one granule of all nb beams
+// SESSION: blockIdx.y -> group; nothing moves for a group that is not live, has just finished or is at its cap.  The range starts at
+// pos - step + 1 = P_g + 1 (admission: pos = P_g, step 0), so npos = step.
+template <bool SESSION>
 __global__ __launch_bounds__(256) void beam_reorder_kv_kernel(const BeamState p) {
-  const int b = blockIdx.y, nb = p.nb;
-  if (p.done[b]) return;
+  const int nb = p.nb;
+  int b = blockIdx.y, pos, prompt_len;
+  if constexpr (SESSION) {
+    const SlotState ss = p.slots[b * nb];
+    if (!ss.live || p.done[b] || ss.step + 1 >= ss.max_step) return;
+    pos = ss.pos; prompt_len = ss.pos - ss.step + 1;
+  } else {
+    if (p.done[b]) return;
+  }
   int src[BEAM_MAX];
   bool identity = true;
   for (int j = 0; j < nb; ++j) { src[j] = p.beam_idx[b * nb + j]; identity = identity && src[j] == b * nb + j; }
   if (identity) return;
-  const int pos = p.st->pos;                       // position written by this step's attention
-  const int npos = pos - p.prompt_len + 1;
+  if constexpr (!SESSION) { pos = p.st->pos; prompt_len = p.prompt_len; }      // position written by this step's attention
+  const int npos = pos - prompt_len + 1;
   if (npos <= 0) return;
   const int R = p.B * nb, H = p.H, Smax = p.Smax, G = p.kv_gran;
   f32x4* const kc = static_cast<f32x4*>(p.kcache);
@@ -404,13 +489,13 @@ __global__ __launch_bounds__(256) void beam_reorder_kv_kernel(const BeamState p)
     const int lh = (int)(it / (G * npos)), rem = (int)(it - (long)lh * G * npos);
     const int l = lh / H, h = lh - l * H;
     {   // K: [L][R][H][G][Smax] granules
-      const int c = rem / npos, s = p.prompt_len + (rem - c * npos);
+      const int c = rem / npos, s = prompt_len + (rem - c * npos);
       f32x4 v[BEAM_MAX];
       for (int j = 0; j < nb; ++j) v[j] = kc[((((size_t)l * R + src[j]) * H + h) * G + c) * Smax + s];
       for (int j = 0; j < nb; ++j) kc[((((size_t)l * R + b * nb + j) * H + h) * G + c) * Smax + s] = v[j];
     }
     {   // V: [L][R][H][Smax][G] granules
-      const int s = p.prompt_len + rem / G, k = rem - (rem / G) * G;
+      const int s = prompt_len + rem / G, k = rem - (rem / G) * G;
       f32x4 v[BEAM_MAX];
       for (int j = 0; j < nb; ++j) v[j] = vc[((((size_t)l * R + src[j]) * H + h) * Smax + s) * G + k];
       for (int j = 0; j < nb; ++j) vc[((((size_t)l * R + b * nb + j) * H + h) * Smax + s) * G + k] = v[j];
@@ -420,11 +505,50 @@ __global__ __launch_bounds__(256) void beam_reorder_kv_kernel(const BeamState p)
 
 int beam_reorder_forward(const BeamState& s, hipStream_t st) {
   IDX_CHECK(s.seq && s.seen && s.cur_tok && s.kcache && s.vcache && s.beam_idx && s.next_tok, "null pointer");
-  hipLaunchKernelGGL(beam_reorder_rows_kernel, dim3(s.B), dim3(1024), 0, st, s);
+  if (s.slots) {      // session: the KV rows move first (the rows launch advances the group's scalars); the rows launch writes the next inputs
+    IDX_CHECK(s.mel_emb && s.mel_pos && (s.x_frag || (s.x_row && s.x_stats)) && s.d % 16 == 0, "null pointer");
+    static const int cat_s = prof_register("beam_select_kernel + beam_reorder_kv_kernel + beam_reorder_rows_kernel (session)");
+    ProfScope prof(cat_s, st, 0.0, 0.0);
+    if (!s.group_ids) {      // (an admission is step 0: no generated position to move)
+      hipLaunchKernelGGL(beam_reorder_kv_kernel<true>, dim3(256, s.B), dim3(256), 0, st, s);
+      IDX_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(beam_reorder_rows_kernel<true>, dim3(s.group_ids ? s.n_ids : s.B), dim3(1024), 0, st, s);
+    IDX_LAUNCH_CHECK();
+    return 0;
+  }
+  hipLaunchKernelGGL(beam_reorder_rows_kernel<false>, dim3(s.B), dim3(1024), 0, st, s);
   IDX_LAUNCH_CHECK();
   static const int cat = prof_register("beam_select_kernel + beam_reorder_rows_kernel + beam_reorder_kv_kernel");
   ProfScope prof(cat, st, 0.0, 0.0);
-  hipLaunchKernelGGL(beam_reorder_kv_kernel, dim3(256, s.B), dim3(256), 0, st, s);
+  hipLaunchKernelGGL(beam_reorder_kv_kernel<false>, dim3(256, s.B), dim3(256), 0, st, s);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void beam_session_reset_kernel(const BeamState p, int start_token, float* x_last, const float* x, int S,
+                                                                 const int* P, const int* cap) {
+  const int b = blockIdx.x, g = p.group_ids[b], Pb = P[b], nb = p.nb, V = p.V, d = p.d;
+  const float* src = x + ((size_t)b * S + Pb) * d;
+  for (int j = 0; j < nb; ++j) {
+    const int r = g * nb + j;
+    unsigned char* sr = p.seen + (size_t)r * V;
+    for (int v = threadIdx.x; v < V; v += 256) sr[v] = (v == 1 || v == start_token) ? 1 : 0;      // input_ids = [1 ... 1, start]
+    for (int e = threadIdx.x; e < d; e += 256) x_last[(size_t)r * d + e] = src[e];
+    if (threadIdx.x == 0) {
+      p.slots[r] = SlotState{Pb, 1, 0, cap[b], 1};
+      p.beam_scores[r] = j == 0 ? 0.0f : -1e9f;      // only the first beam's tokens count in the first step (as generate_beam)
+    }
+  }
+  if (threadIdx.x == 0) { p.hyp_n[g] = 0; p.hyp_worst[g] = 1e9; p.done[g] = 0; }
+}
+
+int beam_session_reset(const BeamState& s, int start_token, float* x_last, const float* x, int S, const int* P, const int* cap, int n,
+                       hipStream_t st) {
+  IDX_CHECK(s.slots && s.group_ids && s.seen && s.beam_scores && s.hyp_n && s.hyp_worst && s.done && x_last && x && P && cap, "null pointer");
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(beam_session_reset_kernel, dim3(n), dim3(256), 0, st, s, start_token, x_last, x, S, P, cap);
   IDX_LAUNCH_CHECK();
   return 0;
 }

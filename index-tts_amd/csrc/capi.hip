@@ -488,6 +488,33 @@ int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs
   API_END
 }
 
+size_t idxtts_gpt_session_workspace_bytes_beam(const idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens) {
+  if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
+  if (num_beams < 2 || num_beams > BEAM_MAX || slots % num_beams) return 0;
+  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
+  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, false, num_beams) : 0;
+}
+
+int idxtts_gpt_session_init_beam(idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens, float repetition_penalty,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(num_beams >= 2 && num_beams <= BEAM_MAX, "2 <= num_beams <= 8");
+  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
+                         false, num_beams);
+  API_END
+}
+
+int idxtts_gpt_session_admit_beam(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                  const int* group_ids, const int* max_new_tokens, const idxtts_beam* per_request, void* workspace,
+                                  void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_admit_beam(workspace, n, inputs_embeds, ld_rows, prompt_lens, group_ids, max_new_tokens, per_request,
+                               static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* finished_slots, int* n_finished, void* workspace,
                             void* stream) {
   API_BEGIN

@@ -124,14 +124,39 @@ struct SlotSampling {
 int sample_slots_warp_forward(const SampleArgs& a, SlotState* slots, const SlotSampling* samp, const int* slot_ids, int n,
                               hipStream_t stream);
 
+// x[b] = mel_emb[tok] + mel_pos[mp] for the plane-GEMV decode step: fp32 row + (mean, M2) per 16 columns (every thread of the
+// workgroup takes part; the session tails of sample_slots_forward and the beam session share it)
+template <int NT>
+__device__ __forceinline__ void embed_row_pl(float* x_row, float* x_stats, const int b, const int B, const int d, const float* mel_emb,
+                                             const float* mel_pos, const int tok, const int mp, const int tid) {
+  const int R = ((B + 15) >> 4) * 16;
+  for (int e0 = 0; e0 < d; e0 += NT) {      // d % 16 == 0: a 16-column tile never straddles the loop's edge or a wave
+    const int e = e0 + tid;
+    const bool on = e < d;
+    const float v = on ? mel_emb[(size_t)tok * d + e] + mel_pos[(size_t)mp * d + e] : 0.f;
+    float s = v;
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m);
+    const float mean = s * 0.0625f;
+    float q = (v - mean) * (v - mean);
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) q += __shfl_xor(q, m);
+    if (on) {
+      x_row[(size_t)b * d + e] = v;
+      if ((e & 15) == 0) *reinterpret_cast<float2*>(&x_stats[((size_t)(e >> 4) * R + b) * 2]) = make_float2(mean, q);
+    }
+  }
+}
+
 int advance_state(DecodeState* st, hipStream_t stream);
 // qkv [B][S][3d] -> caches, positions [0, S).  kv16: the caches hold bf16 and the k / v columns of qkv are rounded IN PLACE, so the
 // prefill attention that follows sees exactly the keys and values later steps read from the cache
 int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, int H, int S, int Smax, int d, hipStream_t stream);
 // Decode-session admission: the same for a right-padded prefill of n rows whose cache rows are the slots slot_ids[b]: positions
-// [0, len[b]) of row b go to slot slot_ids[b] (kcache / vcache laid out for `slots` rows); k / v columns rounded in place for kv16
+// [0, len[b]) of row b go to slot slot_ids[b] (kcache / vcache laid out for `slots` rows); k / v columns rounded in place for kv16.
+// fan > 1 (beam sessions): row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1
 int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
-                   const int* len, hipStream_t stream);
+                   const int* len, hipStream_t stream, int fan = 1);
 // Decode-session admission, input rows of the prefill: x[b][s] = emb[b][s] for s < P[b] (emb [n][ld_rows][d]), mel_emb[start] +
 // mel_pos[0] at s = P[b], 0 after it (right padding); every row S long
 int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P, int n, int S, int d, const float* mel_emb,

@@ -465,29 +465,6 @@ int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// x[b] = mel_emb[tok] + mel_pos[mp] for the plane-GEMV decode step: fp32 row + (mean, M2) per 16 columns
-template <int NT>
-__device__ __forceinline__ void embed_row_pl(float* x_row, float* x_stats, const int b, const int B, const int d, const float* mel_emb,
-                                             const float* mel_pos, const int tok, const int mp, const int tid) {
-  const int R = ((B + 15) >> 4) * 16;
-  for (int e0 = 0; e0 < d; e0 += NT) {      // d % 16 == 0: a 16-column tile never straddles the loop's edge or a wave
-    const int e = e0 + tid;
-    const bool on = e < d;
-    const float v = on ? mel_emb[(size_t)tok * d + e] + mel_pos[(size_t)mp * d + e] : 0.f;
-    float s = v;
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m);
-    const float mean = s * 0.0625f;
-    float q = (v - mean) * (v - mean);
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) q += __shfl_xor(q, m);
-    if (on) {
-      x_row[(size_t)b * d + e] = v;
-      if ((e & 15) == 0) *reinterpret_cast<float2*>(&x_stats[((size_t)(e >> 4) * R + b) * 2]) = make_float2(mean, q);
-    }
-  }
-}
-
 // Row b of the greedy sampler (sample_greedy_kernel's reduction, for the session sampler below): logits (split-K partial sum + bias, optionally recorded) -> repetition penalty -> argmax, the first
 // maximum on ties.  The result is valid in thread 0 only (rv / ri: [16] of shared scratch).
 __device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int b, const int tid, float* rv, int* ri, float& best_out,
@@ -952,12 +929,13 @@ int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, in
   return 0;
 }
 
-// decode-session admission: prefill row b (right-padded, S positions) -> the cache rows of slot slot_ids[b], positions [0, len[b])
-template <bool KV16>
+// decode-session admission: prefill row b (right-padded, S positions) -> the cache rows of slot slot_ids[b], positions [0, len[b]);
+// FAN (beam sessions): to the `fan` consecutive slots slot_ids[b] .. slot_ids[b] + fan - 1 (a group's beams start identical)
+template <bool KV16, bool FAN>
 __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* kcache, void* vcache, int H, int S, int Smax, int d,
-                                                             const int* slot_ids, const int* len) {
+                                                             const int* slot_ids, const int* len, int fan) {
   const int s = blockIdx.x, b = blockIdx.y;
-  const int slot = slot_ids[b];
+  const int slot0 = slot_ids[b];
   const bool keep = s < len[b];
   float* row = qkv + ((size_t)b * S + s) * 3 * d;
   for (int col = threadIdx.x; col < d; col += 256) {
@@ -965,27 +943,41 @@ __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* k
     if (KV16) {      // every row is rounded (as kv_store_prefill does): the prefill attention sees the cached values
       const unsigned kb = bf16_rne_bits(row[d + col]), vb = bf16_rne_bits(row[2 * d + col]);
       if (keep) {
-        static_cast<unsigned short*>(kcache)[(((size_t)(slot * H + h) * 8 + (dd >> 3)) * Smax + s) * 8 + (dd & 7)] = (unsigned short)kb;
-        static_cast<unsigned short*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = (unsigned short)vb;
+        auto put = [&](int slot) {
+          static_cast<unsigned short*>(kcache)[(((size_t)(slot * H + h) * 8 + (dd >> 3)) * Smax + s) * 8 + (dd & 7)] = (unsigned short)kb;
+          static_cast<unsigned short*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = (unsigned short)vb;
+        };
+        if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+        else put(slot0);
       }
       row[d + col] = __uint_as_float(kb << 16);
       row[2 * d + col] = __uint_as_float(vb << 16);
     } else if (keep) {
-      static_cast<float*>(kcache)[(((size_t)(slot * H + h) * 16 + (dd >> 2)) * Smax + s) * 4 + (dd & 3)] = row[d + col];
-      static_cast<float*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = row[2 * d + col];
+      auto put = [&](int slot) {
+        static_cast<float*>(kcache)[(((size_t)(slot * H + h) * 16 + (dd >> 2)) * Smax + s) * 4 + (dd & 3)] = row[d + col];
+        static_cast<float*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = row[2 * d + col];
+      };
+      if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+      else put(slot0);
     }
   }
 }
 
 int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
-                   const int* len, hipStream_t stream) {
+                   const int* len, hipStream_t stream, int fan) {
   IDX_CHECK(S <= Smax, "prefill longer than the cache");
-  IDX_CHECK(slot_ids && len, "null pointer");
+  IDX_CHECK(slot_ids && len && fan >= 1, "null pointer");
   if (n <= 0) return 0;
   static const int cat = prof_register("kv_store_slots_kernel");
   ProfScope prof(cat, stream, 0.0, (kv16 ? 28.0 : 16.0) * n * (double)S * d);
-  if (kv16) hipLaunchKernelGGL(kv_store_slots_kernel<true>, dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len);
-  else hipLaunchKernelGGL(kv_store_slots_kernel<false>, dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len);
+  if (fan > 1) {
+    if (kv16) hipLaunchKernelGGL((kv_store_slots_kernel<true, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
+    else hipLaunchKernelGGL((kv_store_slots_kernel<false, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
+  } else if (kv16) {
+    hipLaunchKernelGGL((kv_store_slots_kernel<true, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1);
+  } else {
+    hipLaunchKernelGGL((kv_store_slots_kernel<false, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1);
+  }
   IDX_LAUNCH_CHECK();
   return 0;
 }

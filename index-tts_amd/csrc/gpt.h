@@ -17,6 +17,15 @@
 
 namespace idxtts {
 
+// beam search buffers after a decode workspace (gpt_beam.hip): B utterances (session: groups) x nb rows
+struct BeamBuffers {
+  float *proc, *beam_scores;
+  int *next_tok, *beam_idx, *seq, *hyp_len, *hyp_slot, *hyp_seq, *hyp_n, *done;
+  double *hyp_score, *hyp_worst;
+  size_t bytes;
+};
+BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new);
+
 struct GPTLayer {
   const float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
   LinearWeights attn_l, proj_l, fc_l, fc2_l;     // MFMA-32x32 packed (prefill / latent pass)
@@ -66,6 +75,8 @@ struct GPTModel : ModelBase {
     size_t bytes;
     SlotState* slots = nullptr;               // decode session only (carve_session): per-row step scalars; the step uses them, not `state`
     SlotSampling* slot_samp = nullptr;        // sampled decode session only: each slot's sampler (the step samples with it)
+    SlotBeam* slot_beam = nullptr;            // beam decode session only: each group's parameters; `beam` then is its step's beam tail
+    BeamState beam;
   };
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
@@ -90,6 +101,7 @@ struct GPTModel : ModelBase {
   size_t workspace_bytes(int B, int S, int max_new) const;
   struct KvScatter {      // decode-session admission: prefill row b's positions [0, len[b]) go to the cache rows of slot slot_ids[b]
     const int* slot_ids = nullptr; const int* len = nullptr; int n = 0; int slots = 0;
+    int fan = 1;          // beam sessions: row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1 (its group)
   };
   int layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter = nullptr);
   int head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st);      // ln_f -> final_norm -> mel_head
@@ -120,6 +132,8 @@ struct GPTModel : ModelBase {
     int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv16 = 0, gemm_mode = 0;
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
     std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
+    int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
+    std::vector<SlotBeam> beam;       // host image of the SlotBeam table (beam sessions), copied whole at each admission
     size_t ws_bytes = 0;
     std::vector<char> busy;           // admitted and not yet read
     bool warm = false;                // one step has run eagerly (first-use function attributes are set outside a capture)
@@ -138,23 +152,39 @@ struct GPTModel : ModelBase {
     float* x_last;                    // [slots][d] last valid prefill row of each admitted request (first-token head input)
     int *ids, *plen, *klen, *cap;     // admission staging: slot ids, prompt lengths (prefill rows: -1 = padding row), P + 1, caps
     SlotSampling* samp;               // [slots] per-slot samplers (sampled sessions only, else null)
+    BeamBuffers bb;                   // beam sessions: proc, beam scores, next_tok, beam_idx, seq [slots][max_new], hypotheses per group
+    SlotBeam* beam;                   // [groups] per-request beam parameters (beam sessions only, else null)
     size_t bytes;
   };
   size_t session_prefill_rows(int slots, int max_prompt) const { return (size_t)slots * (max_prompt + 1) + 256; }
-  // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before
-  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled) const;
-  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false) const;
+  // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before;
+  // num_beams > 0 (beam session): the beam buffers and the SlotBeam table likewise
+  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0) const;
+  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0) const;
   Session* find_session(void* ws);
-  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false);
+  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false,
+                   int num_beams = 0);
   // per_row: null = every row greedy; else one sampler per row (sampled sessions only)
   int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
                     const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr);
+  // beam sessions: n requests into the free groups group_ids, each with its own idxtts_beam (num_beams == the session's); every request
+  // is checked before any group is taken.  One prefill row per request, its KV fanned out to the group's slots; then its first beam step.
+  int session_admit_beam(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* group_ids,
+                         const int* max_new, const idxtts_beam* per_request, hipStream_t st);
+  int session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st);
   int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
   int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
   int session_release(void* ws);
   int embed(float* out, int rows, const int* text_ids, const int* text_pos_idx, const int* mel_ids, const int* mel_pos_idx,
             const float* extra, const int* extra_idx, hipStream_t st);
 };
+
+// BeamSearchScorer.finalize for one utterance (transformers_beam_search.py:320-414) on host copies of its device state: the finished
+// hypotheses (hyp_* rows of the utterance, hyp_seq [BEAM_MAX + 1][seq_ld]) and, unless `done`, its nb open beams (bscore [nb], seq
+// [nb][seq_ld]) scored at steps_done tokens.  Returns the best hypothesis (tokens point into hyp_seq or seq).
+struct BeamHyp { double score; const int* toks; int len; };
+int beam_finalize(int nb, double length_penalty, int hyp_n, const double* hyp_score, const int* hyp_len, const int* hyp_slot,
+                  const int* hyp_seq, int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best);
 
 // beam state of the generation this host thread is running (null = greedy / sampling); read by head_and_sample
 extern thread_local const BeamState* tl_beam;

@@ -307,7 +307,7 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   if (store_kv && scatter) {      // decode-session admission: the rows go to their slots' cache regions
     const size_t per_layer = kv_layer_bytes(scatter->slots, w.Smax);
     if (kv_store_slots(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, scatter->n, cfg.heads, S, w.Smax, d,
-                       scatter->slot_ids, scatter->len, st)) return 1;
+                       scatter->slot_ids, scatter->len, st, scatter->fan)) return 1;
   } else if (store_kv) {
     const size_t per_layer = kv_layer_bytes(B, w.Smax);
     if (kv_store_prefill(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, B, cfg.heads, S, w.Smax, d, st)) return 1;
@@ -368,6 +368,11 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
   const bool pl = use_pl(B);
   if (head_logits(w, B, x, ldx, x_frag, st)) return 1;
+  if (w.slot_beam) {      // beam decode session: the beam stages on every live group, the last one with the fused tail (beam.h)
+    BeamState bs = w.beam;
+    bs.penalty = penalty;
+    return beam_scores_forward(bs, st) || beam_select_forward(bs, st) || beam_reorder_forward(bs, st);
+  }
   if (tl_beam) return beam_scores_forward(*tl_beam, st) || beam_select_forward(*tl_beam, st) || beam_reorder_forward(*tl_beam, st);
   SampleArgs s;
   s.part = w.logits; s.parts = 1; s.part_rows = B; s.bias = nullptr; s.logits_out = logits_out;
@@ -658,7 +663,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
 // Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
 // the staged last prefill rows and the admission's index arrays.
-GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled) const {
+GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams) const {
   SessionBuffers sb;
   sb.w = carve(ws, slots, max_prompt + 1, max_new, session_prefill_rows(slots, max_prompt));
   Carver c(ws);
@@ -672,12 +677,32 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
   sb.cap = c.take<int>(slots);
   sb.samp = nullptr;
   if (sampled) sb.w.slot_samp = sb.samp = c.take<SlotSampling>(slots);
+  sb.bb = BeamBuffers{};
+  sb.beam = nullptr;
+  if (num_beams > 0) {      // beam session: slots / num_beams groups
+    const int G = slots / num_beams, V = cfg.number_mel_codes;
+    c.off = (c.off + 255) & ~(size_t)255;
+    sb.bb = carve_beam(ws ? static_cast<char*>(ws) + c.off : nullptr, G, num_beams, V, max_new);
+    c.off += sb.bb.bytes;
+    sb.w.slot_beam = sb.beam = c.take<SlotBeam>(G);
+    const Buffers& w = sb.w;
+    BeamState& b = sb.w.beam;
+    b.logits = w.logits; b.proc = sb.bb.proc; b.seen = w.seen; b.beam_scores = sb.bb.beam_scores; b.next_tok = sb.bb.next_tok;
+    b.beam_idx = sb.bb.beam_idx; b.seq = sb.bb.seq; b.seq_ld = max_new; b.cur_tok = w.cur_tok;
+    b.hyp_score = sb.bb.hyp_score; b.hyp_len = sb.bb.hyp_len; b.hyp_slot = sb.bb.hyp_slot; b.hyp_seq = sb.bb.hyp_seq; b.hyp_n = sb.bb.hyp_n;
+    b.hyp_worst = sb.bb.hyp_worst; b.done = sb.bb.done;
+    b.kcache = w.kcache; b.vcache = w.vcache; b.kv_gran = kv_fmt ? 8 : 16;
+    b.B = G; b.nb = num_beams; b.V = V; b.stop_token = cfg.stop_mel_token; b.L = cfg.layers; b.H = cfg.heads; b.Smax = w.Smax;
+    b.slots = w.slots; b.group = sb.beam;
+    if (use_pl(slots)) { b.x_row = w.xrow; b.x_stats = w.stats; } else b.x_frag = w.xd;
+    b.mel_emb = mel_emb; b.mel_pos = mel_pos; b.d = cfg.model_dim;
+  }
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
 
-size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled) const {
-  return carve_session(nullptr, slots, max_prompt, max_new, sampled).bytes;
+size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams) const {
+  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams).bytes;
 }
 
 GPTModel::Session* GPTModel::find_session(void* ws) {
@@ -687,12 +712,15 @@ GPTModel::Session* GPTModel::find_session(void* ws) {
 }
 
 int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st,
-                           bool sampled) {
+                           bool sampled, int num_beams) {
   IDX_CHECK(ws, "null workspace");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
+  IDX_CHECK(num_beams == 0 || (num_beams >= 2 && num_beams <= BEAM_MAX), "2 <= num_beams <= 8");
+  IDX_CHECK(num_beams == 0 || slots % num_beams == 0, "slots must be a multiple of num_beams");
+  IDX_CHECK(num_beams == 0 || !sampled, "a beam session has no per-slot samplers");
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
-  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled), "workspace too small");
-  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled);
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams);
   const Buffers& w = sb.w;
   const int d = cfg.model_dim;
   IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
@@ -703,6 +731,14 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   IDX_HIP(hipMemsetAsync(sb.x_last, 0, (size_t)slots * d * sizeof(float), st));
   IDX_HIP(hipMemsetAsync(w.xrow, 0, (size_t)slots * d * sizeof(float), st));
   if (sampled) IDX_HIP(hipMemsetAsync(sb.samp, 0, slots * sizeof(SlotSampling), st));      // every slot greedy
+  if (num_beams) {      // every group free (SlotState zeroed above) and finished: no stale scorer state is ever read
+    const int G = slots / num_beams;
+    IDX_HIP(hipMemsetAsync(sb.beam, 0, G * sizeof(SlotBeam), st));
+    std::vector<int> ones(G, 1);
+    IDX_HIP(hipMemcpyAsync(sb.bb.done, ones.data(), G * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipMemsetAsync(sb.bb.hyp_n, 0, G * sizeof(int), st));
+    IDX_HIP(hipStreamSynchronize(st));      // `ones` goes out of scope below
+  }
   std::lock_guard<std::mutex> l(session_mu);
   Session& s = sessions[ws];
   s.drop_graph();
@@ -712,6 +748,8 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.busy.assign(slots, 0);
   s.sampled = sampled;
   if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
+  s.num_beams = num_beams;
+  if (num_beams) s.beam.assign(slots / num_beams, SlotBeam{0, 1.0f, 0, 1.0f, 0.0, 0, 0, nullptr});
   return 0;
 }
 
@@ -730,6 +768,7 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
   IDX_CHECK(inputs_embeds && prompt_lens && slot_ids && caps, "null pointer");
+  IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
   IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots rows");
   IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
   if (per_row) {      // every row's sampler is checked before any slot is taken (generate()'s rules)
@@ -816,7 +855,7 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_CHECK(n_steps >= 0, "n_steps");
   IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   GenScope gen_scope(this);
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
   const Buffers& w = sb.w;
   const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
   if (s.exec && s.geom != geom) s.drop_graph();
@@ -846,7 +885,8 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_HIP(hipMemcpyAsync(hs.data(), w.slots, s.slots * sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   int nf = 0;
-  for (int i = 0; i < s.slots; ++i)
+  const int stride = s.num_beams ? s.num_beams : 1;      // beam sessions report the first slot of each finished group
+  for (int i = 0; i < s.slots; i += stride)
     if (s.busy[i] && !hs[i].live) { if (finished_slots) finished_slots[nf] = i; ++nf; }
   if (n_finished) *n_finished = nf;
   return 0;
@@ -858,7 +898,8 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   Session& s = *sp;
   IDX_CHECK(codes && n_codes, "null pointer");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  if (s.num_beams) return session_read_beam(s, sb, slot, codes, n_codes, st);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));

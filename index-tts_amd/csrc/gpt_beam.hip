@@ -25,12 +25,7 @@ struct Carver {
   }
 };
 
-struct BeamBuffers {
-  float *proc, *beam_scores;
-  int *next_tok, *beam_idx, *seq, *hyp_len, *hyp_slot, *hyp_seq, *hyp_n, *done;
-  double *hyp_score, *hyp_worst;
-  size_t bytes;
-};
+}  // namespace
 
 BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new) {
   const int R = B * nb;
@@ -52,7 +47,35 @@ BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new) {
   return b;
 }
 
-}  // namespace
+int beam_finalize(int nb, double lp, int hyp_n, const double* hyp_score, const int* hyp_len, const int* hyp_slot, const int* hyp_seq,
+                  int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best) {
+  std::vector<BeamHyp> list;
+  for (int q = 0; q < hyp_n; ++q) list.push_back(BeamHyp{hyp_score[q], &hyp_seq[(size_t)hyp_slot[q] * seq_ld], hyp_len[q]});
+  if (!done) {      // open beams become hypotheses (BeamHypotheses.add with its keep-the-best rule)
+    double worst = 1e9;
+    for (const BeamHyp& h : list) worst = std::min(worst, h.score);
+    for (int j = 0; j < nb; ++j) {
+      const double score = (double)bscore[j] / std::pow((double)steps_done, lp);
+      if ((int)list.size() < nb || score > worst) {
+        list.push_back(BeamHyp{score, &seq[(size_t)j * seq_ld], steps_done});
+        if ((int)list.size() > nb) {
+          size_t wi = 0;
+          for (size_t q = 1; q < list.size(); ++q) if (list[q].score < list[wi].score) wi = q;
+          list.erase(list.begin() + wi);
+          worst = list[0].score;
+          for (const BeamHyp& h : list) worst = std::min(worst, h.score);
+        } else {
+          worst = std::min(worst, score);
+        }
+      }
+    }
+  }
+  IDX_CHECK(!list.empty(), "no hypothesis");
+  size_t bi = 0;       // sorted(..., key=score).pop(): the largest score, the LAST of equals
+  for (size_t q = 1; q < list.size(); ++q) if (list[q].score >= list[bi].score) bi = q;
+  *best = list[bi];
+  return 0;
+}
 
 size_t GPTModel::beam_workspace_bytes(int B, int nb, int S, int max_new) const {
   return workspace_bytes(B * nb, S, max_new) + carve_beam(nullptr, B, nb, cfg.number_mel_codes, max_new).bytes;
@@ -195,40 +218,12 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
   IDX_HIP(hipMemcpyAsync(bscore.data(), bb.beam_scores, R * sizeof(float), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipMemcpyAsync(done.data(), bb.done, B * sizeof(int), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
-  struct Hyp { double score; const int* toks; int len; };
-  std::vector<Hyp> best(B);
+  std::vector<BeamHyp> best(B);
   int longest = 0;
-  const double lp = (double)beam->length_penalty;
   for (int b = 0; b < B; ++b) {
-    std::vector<Hyp> list;
-    for (int q = 0; q < hyp_n[b]; ++q) {
-      const size_t o = (size_t)b * (BEAM_MAX + 1) + q;
-      list.push_back(Hyp{hyp_score[o], &hyp_seq[((size_t)b * (BEAM_MAX + 1) + hyp_slot[o]) * max_new], hyp_len[o]});
-    }
-    if (!done[b]) {      // open beams become hypotheses (BeamHypotheses.add with its keep-the-best rule)
-      double worst = 1e9;
-      for (const Hyp& h : list) worst = std::min(worst, h.score);
-      for (int j = 0; j < nb; ++j) {
-        const int r = b * nb + j;
-        const double score = (double)bscore[r] / std::pow((double)steps_done, lp);
-        if ((int)list.size() < nb || score > worst) {
-          list.push_back(Hyp{score, &seq[(size_t)r * max_new], steps_done});
-          if ((int)list.size() > nb) {
-            size_t wi = 0;
-            for (size_t q = 1; q < list.size(); ++q) if (list[q].score < list[wi].score) wi = q;
-            list.erase(list.begin() + wi);
-            worst = list[0].score;
-            for (const Hyp& h : list) worst = std::min(worst, h.score);
-          } else {
-            worst = std::min(worst, score);
-          }
-        }
-      }
-    }
-    IDX_CHECK(!list.empty(), "no hypothesis");
-    size_t bi = 0;       // sorted(..., key=score).pop(): the largest score, the LAST of equals
-    for (size_t q = 1; q < list.size(); ++q) if (list[q].score >= list[bi].score) bi = q;
-    best[b] = list[bi];
+    const size_t o = (size_t)b * (BEAM_MAX + 1);
+    if (beam_finalize(nb, (double)beam->length_penalty, hyp_n[b], &hyp_score[o], &hyp_len[o], &hyp_slot[o], &hyp_seq[o * max_new], max_new,
+                      done[b] != 0, &bscore[(size_t)b * nb], &seq[(size_t)b * nb * max_new], steps_done, &best[b])) return 1;
     longest = std::max(longest, best[b].len);
   }
   const int n_out = std::min(longest + 1, max_new);          // min(sent_lengths.max() + 1, max_length) - prompt
@@ -238,6 +233,121 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
   IDX_HIP(hipMemcpyAsync(codes, out.data(), out.size() * sizeof(long long), hipMemcpyHostToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));
   *n_steps_out = n_out;
+  return 0;
+}
+
+// ---- beam decode session (gpt.h; the greedy session's machinery in gpt.hip) ----
+int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* group_ids,
+                                 const int* caps, const idxtts_beam* per_request, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams > 0, "_admit_beam needs a session initialised with num_beams (idxtts_gpt_session_init_beam)");
+  IDX_CHECK(inputs_embeds && prompt_lens && group_ids && caps && per_request, "null pointer");
+  const int nb = s.num_beams, G = s.slots / nb;
+  IDX_CHECK(n >= 1 && n <= G, "admit 1 .. slots / num_beams requests");
+  // every request is checked before any group is taken (generate_beam's rules)
+  std::vector<char> taken(G, 0);
+  int pmax = 0;
+  for (int b = 0; b < n; ++b) {
+    const idxtts_beam& r = per_request[b];
+    IDX_CHECK(r.num_beams == nb, "num_beams differs from the session's");
+    IDX_CHECK(!r.do_sample || (r.temperature > 0.0f && r.top_k >= 0 && r.top_k <= 1024 && r.top_p > 0.0f),
+              "beam-sample needs a positive temperature, top_k <= 1024 and top_p > 0");
+    IDX_CHECK(!r.do_sample || r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
+    IDX_CHECK(r.early_stopping == 0 || r.early_stopping == 1, "early_stopping must be 0 (False) or 1 (True)");
+    IDX_CHECK(group_ids[b] >= 0 && group_ids[b] < G, "group id out of range");
+    IDX_CHECK(!s.busy[group_ids[b] * nb] && !taken[group_ids[b]], "group is not free");
+    taken[group_ids[b]] = 1;
+    IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
+    IDX_CHECK(caps[b] >= 1 && caps[b] <= s.max_new, "token cap out of range (1 .. max_new)");
+    pmax = std::max(pmax, prompt_lens[b]);
+  }
+  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  GenScope gen_scope(this);
+  const int d = cfg.model_dim;
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
+  const Buffers& w = sb.w;
+  // one right-padded prefill row per request (session_admit's rules, the 256-row padding of a bf16 cache in split-bf16 mode included);
+  // its keys and values go to every slot of its group
+  const int S = pmax + 1;
+  int rows = n;
+  if (kv_fmt && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
+  IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
+  std::vector<int> stage((size_t)3 * s.slots + rows, 0);      // first slots | group ids (ids) | klen | cap | plen
+  for (int b = 0; b < n; ++b) {
+    stage[b] = group_ids[b] * nb;
+    stage[n + b] = group_ids[b];
+    stage[s.slots + b] = prompt_lens[b] + 1;
+    stage[2 * s.slots + b] = caps[b];
+  }
+  for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
+  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), 2 * n * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots (nb >= 2)
+  IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
+  for (int b = 0; b < n; ++b) {
+    const idxtts_beam& r = per_request[b];
+    s.beam[group_ids[b]] = SlotBeam{r.do_sample ? 1 : 0, r.temperature, r.top_k, r.top_p, (double)r.length_penalty, r.early_stopping,
+                                    r.seed, r.exp_noise};
+  }
+  IDX_HIP(hipMemcpyAsync(sb.beam, s.beam.data(), G * sizeof(SlotBeam), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
+
+  if (session_prefill_input(w.x, inputs_embeds, ld_rows, sb.plen, rows, S, d, mel_emb, mel_pos, cfg.start_mel_token, st)) return 1;
+  KvScatter sc;
+  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = nb;
+  for (int li = 0; li < cfg.layers; ++li)
+    if (layer_full(li, w, rows, S, nullptr, true, st, &sc)) return 1;
+  BeamState bs = w.beam;
+  bs.penalty = s.penalty; bs.group_ids = sb.ids + n; bs.n_ids = n;
+  if (beam_session_reset(bs, cfg.start_mel_token, sb.x_last, w.x, S, sb.plen, sb.cap, n, st)) return 1;
+  // the first beam step of the admitted groups: the head on all `slots` rows (the GEMV generate_beam's R = slots rows selects), the beam
+  // stages on those groups only; the last one writes their first decode inputs
+  if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
+  if (beam_scores_forward(bs, st) || beam_select_forward(bs, st) || beam_reorder_forward(bs, st)) return 1;
+  for (int b = 0; b < n; ++b)
+    for (int j = 0; j < nb; ++j) s.busy[group_ids[b] * nb + j] = 1;
+  return 0;
+}
+
+// BeamSearchScorer.finalize of the group whose first slot is `slot`, with the steps it took: its best hypothesis, then the stop token
+// if it fits under the cap (row 0 of generate_beam's codes, cut after its first stop token)
+int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st) {
+  const int nb = s.num_beams, g = slot / nb, L = s.max_new;
+  IDX_CHECK(slot % nb == 0, "a beam session is read at the first slot of a group");
+  SlotState hs;
+  IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(!hs.live, "slot is still decoding");
+  IDX_CHECK(hs.step >= 1 && hs.step <= hs.max_step && hs.max_step <= L, "slot state corrupt");
+  const BeamBuffers& bb = sb.bb;
+  const size_t H = BEAM_MAX + 1, o = (size_t)g * H;
+  std::vector<int> seq((size_t)nb * L), hyp_len(H), hyp_slot(H), hyp_seq(H * L);
+  std::vector<double> hyp_score(H);
+  std::vector<float> bscore(nb);
+  int hyp_n = 0, done = 0;
+  IDX_HIP(hipMemcpyAsync(seq.data(), bb.seq + (size_t)slot * L, seq.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(hyp_len.data(), bb.hyp_len + o, H * sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(hyp_slot.data(), bb.hyp_slot + o, H * sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(hyp_seq.data(), bb.hyp_seq + o * L, hyp_seq.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(hyp_score.data(), bb.hyp_score + o, H * sizeof(double), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(bscore.data(), bb.beam_scores + slot, nb * sizeof(float), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(&hyp_n, bb.hyp_n + g, sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(&done, bb.done + g, sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(hyp_n >= 0 && hyp_n <= nb, "group state corrupt");
+  BeamHyp best;
+  if (beam_finalize(nb, s.beam[g].length_penalty, hyp_n, hyp_score.data(), hyp_len.data(), hyp_slot.data(), hyp_seq.data(), L, done != 0,
+                    bscore.data(), seq.data(), hs.step, &best)) return 1;
+  IDX_CHECK(best.len >= 0 && best.len <= hs.max_step, "group state corrupt");
+  const int n_out = std::min(best.len + 1, hs.max_step);
+  std::vector<long long> out(n_out, cfg.stop_mel_token);
+  for (int t = 0; t < best.len; ++t) out[t] = best.toks[t];
+  IDX_HIP(hipMemcpyAsync(codes, out.data(), n_out * sizeof(long long), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  *n_codes = n_out;
+  for (int j = 0; j < nb; ++j) s.busy[slot + j] = 0;
   return 0;
 }
 

@@ -229,8 +229,15 @@ class UnifiedVoice:
             raise ValueError("decode sessions sample per request, not session-wide: do_sample=True is not supported; the session is "
                              "greedy unless created with sampled=True and given per-request parameters (admit(..., sampling=...))")
         if num_beams != 1:
-            raise ValueError("decode sessions are greedy or sampled per request: beam search is not supported (use generate_beam())")
+            raise ValueError("decode sessions are greedy or sampled per request: beam search runs in beam_session() (or generate_beam())")
         return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled)
+
+    def beam_session(self, slots: int, num_beams: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
+                     use_graph: bool = True) -> "BeamDecodeSession":
+        """Continuous batching of beam search / beam-sample: `slots` decode rows as slots / num_beams groups of num_beams, one request
+        per group (BeamDecodeSession; `idxtts_gpt_session_*_beam`).  A request's codes equal row 0 of generate_beam() on
+        slots / num_beams copies of its prompt."""
+        return BeamDecodeSession(self, slots, num_beams, max_prompt, max_new, repetition_penalty, use_graph)
 
     # ------------------------------------------------------------------------------------------
     def generate(self, input_ids: torch.Tensor, max_new_tokens: int = 100, temperature: float = 1.0, top_k: int = 50,
@@ -315,12 +322,13 @@ class UnifiedVoice:
     def generate_beam(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: Optional[torch.Tensor], tts_embeddings: torch.Tensor,
                       num_beams: int = 3, do_sample: bool = True, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                       repetition_penalty: float = 1.0, length_penalty: float = 1.0, early_stopping: bool = False,
-                      exp_noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, use_graph: bool = True) -> torch.Tensor:
+                      exp_noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, use_graph: bool = True,
+                      seed: Optional[int] = None) -> torch.Tensor:
         """HF `generate(num_beams > 1)` of the reference (model_v2.py:885-889 -> transformers_generation_utils.py:3325-3516):
         beam search, or beam-sample when do_sample.  Returns LongTensor [B, P+1+n]: the best hypothesis per utterance.
         Sampling draws 2 * num_beams candidates per utterance without replacement: torch.multinomial == top-k of probs / q with
         q ~ Exp(1) from one exponential_() per step on a [B, num_beams * V] tensor -- `exp_noise` [max_new_tokens, B, num_beams*V]
-        supplies them, or `generator` draws them on the CPU in that order; with neither the kernels generate them (see _noise)."""
+        supplies them, or `generator` draws them on the CPU in that order; with neither the kernels generate them from `seed` (see _noise)."""
         emb = tts_embeddings.to(self.device, torch.float32).contiguous()
         B, P, d = emb.shape
         if input_ids.shape != (B, P + 1):
@@ -333,7 +341,7 @@ class UnifiedVoice:
         if attention_mask is not None:
             pad_left = (attention_mask.detach().cpu().numpy()[:, :P] == 0).sum(1).astype(np.int32)
         V, nb = self.cfg.number_mel_codes, int(num_beams)
-        noise, seed = self._noise(exp_noise, generator, (max_new_tokens, B, nb * V)) if do_sample else (None, 0)
+        noise, seed = self._noise(exp_noise, generator, (max_new_tokens, B, nb * V), seed) if do_sample else (None, 0)
         lib = _lib.load()
         need = int(lib.idxtts_gpt_beam_workspace_bytes(self._h, B, nb, P + 1, max_new_tokens))
         if need == 0:
@@ -469,7 +477,100 @@ def _seed64(seed) -> int:
     return s
 
 
-class DecodeSession:
+class _Session:
+    """What DecodeSession and BeamDecodeSession share: the stream, the workspace and its native session, prompt staging, the step loop
+    and the release.  Subclasses set the slot bookkeeping (_busy, _done, _noise) and _unit (slots per request)."""
+    _unit = 1
+
+    def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, use_graph: bool, need: int, init):
+        self.gpt = gpt
+        self.slots, self.max_prompt, self.max_new = int(slots), int(max_prompt), int(max_new)
+        self.use_graph = bool(use_graph)
+        self._lib = _lib.load()
+        self.stream = torch.cuda.current_stream(gpt.device)
+        if self.stream.cuda_stream == 0:        # the legacy default stream cannot be captured: a stream of the session's own
+            self.stream = torch.cuda.Stream(device=gpt.device)
+            self.stream.wait_stream(torch.cuda.current_stream(gpt.device))
+        with torch.cuda.stream(self.stream):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=gpt.device)
+            _lib.check(init(_lib.ptr(self._ws), need, self._sp()))
+        n = self.slots // self._unit
+        self._busy = [False] * n
+        self._noise = {}          # request index (slot or group) -> the exp_noise tensor it reads (kept alive until take())
+        self._done = set()
+
+    def _sp(self) -> c_void_p:
+        return c_void_p(self.stream.cuda_stream)
+
+    def _free(self):
+        return [i for i, b in enumerate(self._busy) if not b]
+
+    def _live(self):
+        return [i for i, b in enumerate(self._busy) if b and i not in self._done]
+
+    def _stage(self, inputs_embeds_rows, max_new_each, free):
+        """Checks and stages the admitted prompts: (rows, plen, caps, emb [n, P_max, d]) -- emb on the session stream."""
+        rows = [r.to(self.gpt.device, torch.float32) for r in inputs_embeds_rows]
+        n = len(rows)
+        caps = [int(max_new_each)] * n if isinstance(max_new_each, int) else [int(c) for c in max_new_each]
+        if len(caps) != n:
+            raise ValueError("one cap per row")
+        if n > len(free):
+            raise RuntimeError(f"{n} rows but {len(free)} free {'slots' if self._unit == 1 else 'groups'}")
+        d = self.gpt.cfg.model_dim
+        plen = [int(r.shape[0]) for r in rows]
+        for r, p, c in zip(rows, plen, caps):
+            if r.dim() != 2 or r.shape[1] != d or not 1 <= p <= self.max_prompt:
+                raise ValueError(f"a prompt row must be [P, {d}] with 1 <= P <= {self.max_prompt}")
+            if not 1 <= c <= self.max_new:
+                raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        return rows, plen, caps
+
+    def _embed_rows(self, rows, plen):
+        pm = max(plen)
+        emb = torch.zeros(len(rows), pm, self.gpt.cfg.model_dim, device=self.gpt.device, dtype=torch.float32)
+        for i, r in enumerate(rows):
+            emb[i, : plen[i]] = r
+        return emb, pm
+
+    def step(self, n: int = 1) -> list:
+        """n decode steps of every live request; returns every request (slot, or group) that has finished and is not taken yet."""
+        fin = np.zeros(self.slots, np.int32)
+        nf = ctypes.c_int(0)
+        steps = int(n) if self._live() else 0
+        _lib.check(self._lib.idxtts_gpt_session_step(self.gpt._h, steps, int(self.use_graph), fin.ctypes.data_as(c_void_p),
+                                                     ctypes.byref(nf), _lib.ptr(self._ws), self._sp()))
+        done = [int(x) // self._unit for x in fin[: nf.value]]
+        self._done.update(done)
+        return done
+
+    def take(self, i: int) -> torch.Tensor:
+        """The codes of the finished request `i` (a slot, or a group) as a LongTensor on the device; `i` is free again."""
+        n = ctypes.c_int(0)
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(self.max_new, dtype=torch.long, device=self.gpt.device)
+            _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(i) * self._unit, _lib.ptr(out), ctypes.byref(n),
+                                                         _lib.ptr(self._ws), self._sp()))
+        self._busy[i] = False
+        self._done.discard(i)
+        self._noise.pop(i, None)
+        return out[: n.value]
+
+    def close(self) -> None:
+        if getattr(self, "_ws", None) is not None:
+            self.stream.synchronize()
+            self._lib.idxtts_gpt_session_release(self.gpt._h, _lib.ptr(self._ws))
+            self._ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DecodeSession(_Session):
     """A fixed set of greedy decode rows ("slots") with one KV region each, on one HIP stream (the current stream at creation, or a
     stream of its own when that is the legacy default stream, which cannot be captured):
       * admit(rows, caps) runs the prefill and first token of new requests in free slots and returns their slot ids;
@@ -489,37 +590,23 @@ class DecodeSession:
 
     def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
                  use_graph: bool = True, sampled: bool = False):
-        self.gpt = gpt
         self.sampled = bool(sampled)
-        self.slots, self.max_prompt, self.max_new = int(slots), int(max_prompt), int(max_new)
-        self.use_graph = bool(use_graph)
-        self._lib = _lib.load()
-        self.stream = torch.cuda.current_stream(gpt.device)
-        if self.stream.cuda_stream == 0:        # the legacy default stream cannot be captured: a stream of the session's own
-            self.stream = torch.cuda.Stream(device=gpt.device)
-            self.stream.wait_stream(torch.cuda.current_stream(gpt.device))
+        lib = _lib.load()
         flags = _lib.SESSION_SAMPLED if self.sampled else 0
-        need = int(self._lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, self.slots, self.max_prompt, self.max_new, flags))
+        need = int(lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, int(slots), int(max_prompt), int(max_new), flags))
         if need == 0:
             raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
-        with torch.cuda.stream(self.stream):
-            self._ws = torch.empty(need, dtype=torch.uint8, device=gpt.device)
-            _lib.check(self._lib.idxtts_gpt_session_init_ex(gpt._h, self.slots, self.max_prompt, self.max_new, float(repetition_penalty),
-                                                            flags, _lib.ptr(self._ws), need, self._sp()))
-        self._busy = [False] * self.slots
-        self._noise = {}          # slot -> the exp_noise tensor its request reads (kept alive until take())
-        self._done = set()
-
-    def _sp(self) -> c_void_p:
-        return c_void_p(self.stream.cuda_stream)
+        super().__init__(gpt, slots, max_prompt, max_new, use_graph, need,
+                         lambda ws, nbytes, sp: lib.idxtts_gpt_session_init_ex(gpt._h, int(slots), int(max_prompt), int(max_new),
+                                                                              float(repetition_penalty), flags, ws, nbytes, sp))
 
     @property
     def free_slots(self):
-        return [i for i, b in enumerate(self._busy) if not b]
+        return self._free()
 
     @property
     def live_slots(self):
-        return [i for i, b in enumerate(self._busy) if b and i not in self._done]
+        return self._live()
 
     def _samplers(self, sampling, caps):
         """sampling (one dict per row, or one dict for every row) -> (SamplingC array, noise tensors); raises ValueError on a bad row."""
@@ -566,33 +653,18 @@ class DecodeSession:
     def admit(self, inputs_embeds_rows, max_new_each, sampling=None) -> list:
         """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int).
         sampling (sampled sessions): None = every row greedy, else one dict per row or one for every row (see the class)."""
-        rows = [r.to(self.gpt.device, torch.float32) for r in inputs_embeds_rows]
-        n = len(rows)
-        if n == 0:
+        if len(inputs_embeds_rows) == 0:
             return []
-        caps = [int(max_new_each)] * n if isinstance(max_new_each, int) else [int(c) for c in max_new_each]
-        if len(caps) != n:
-            raise ValueError("one cap per row")
         free = self.free_slots
-        if n > len(free):
-            raise RuntimeError(f"{n} rows but {len(free)} free slots")
-        d = self.gpt.cfg.model_dim
-        plen = [int(r.shape[0]) for r in rows]
-        for r, p, c in zip(rows, plen, caps):
-            if r.dim() != 2 or r.shape[1] != d or not 1 <= p <= self.max_prompt:
-                raise ValueError(f"a prompt row must be [P, {d}] with 1 <= P <= {self.max_prompt}")
-            if not 1 <= c <= self.max_new:
-                raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        rows, plen, caps = self._stage(inputs_embeds_rows, max_new_each, free)
+        n = len(rows)
         if sampling is not None and not self.sampled:
             raise ValueError("sampling= needs a session created with sampled=True")
         ids = free[:n]
         self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
         with torch.cuda.stream(self.stream):
             samplers, noises = self._samplers(sampling, caps) if sampling is not None else (None, [None] * n)
-            pm = max(plen)
-            emb = torch.zeros(n, pm, d, device=self.gpt.device, dtype=torch.float32)
-            for i, r in enumerate(rows):
-                emb[i, : plen[i]] = r
+            emb, pm = self._embed_rows(rows, plen)
             h_p, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, ids, caps))
             if samplers is None:
                 _lib.check(self._lib.idxtts_gpt_session_admit(
@@ -608,38 +680,108 @@ class DecodeSession:
                 self._noise[i] = nz
         return ids
 
-    def step(self, n: int = 1) -> list:
-        """n decode steps of every live slot; returns every slot whose request has finished and is not taken yet."""
-        fin = np.zeros(self.slots, np.int32)
-        nf = ctypes.c_int(0)
-        steps = int(n) if self.live_slots else 0
-        _lib.check(self._lib.idxtts_gpt_session_step(self.gpt._h, steps, int(self.use_graph), fin.ctypes.data_as(c_void_p),
-                                                     ctypes.byref(nf), _lib.ptr(self._ws), self._sp()))
-        done = [int(x) for x in fin[: nf.value]]
-        self._done.update(done)
-        return done
-
     def take(self, slot: int) -> torch.Tensor:
         """The codes of the finished request in `slot` (LongTensor on the device); the slot is free again."""
-        n = ctypes.c_int(0)
-        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        return super().take(slot)
+
+
+class BeamDecodeSession(_Session):
+    """Beam search / beam-sample with continuous batching: the session's `slots` decode rows form slots / num_beams groups of num_beams
+    consecutive slots, one request per group, each with its own parameters:
+      * admit(rows, caps, beam=...) runs the prefill (once per request) and first beam step of new requests in free groups and returns
+        their group ids;
+      * step(n) runs n decode steps of every live group and returns the groups whose request has finished -- its scorer is done
+        (BeamHypotheses.is_done with the request's early_stopping / length_penalty) or it reached its cap;
+      * take(group) returns that request's codes (the best hypothesis, then the stop token if it fits under the cap) and frees it.
+    `beam`: one dict, or one per request, with keys do_sample, temperature, top_k, top_p, length_penalty, early_stopping (defaults:
+    generate_beam's) and `seed` or `exp_noise` [cap, num_beams * V] (neither: a seed drawn from torch's global RNG).
+    Determinism: a request's codes equal, bit for bit, row 0 of UnifiedVoice.generate_beam with the same parameters and repetition penalty
+    on slots / num_beams copies of its prompt (attention_mask=None, max_new_tokens = its cap; with exp_noise: generate_beam's exp_noise
+    whose [:, 0, :] is the request's noise), cut after its first stop token -- whatever else is in flight, when it was admitted and which
+    group it has (DecodeSession's conditions: a bf16 KV cache in split-bf16 GEMM mode needs slots * (P + 1) >= 256)."""
+
+    _BEAM_KEYS = {"do_sample", "temperature", "top_k", "top_p", "length_penalty", "early_stopping", "seed", "exp_noise"}
+
+    def __init__(self, gpt: UnifiedVoice, slots: int, num_beams: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
+                 use_graph: bool = True):
+        nb = int(num_beams)
+        if not 2 <= nb <= 8:
+            raise ValueError("2 <= num_beams <= 8")
+        if int(slots) % nb:
+            raise ValueError(f"slots ({slots}) must be a multiple of num_beams ({nb})")
+        lib = _lib.load()
+        need = int(lib.idxtts_gpt_session_workspace_bytes_beam(gpt._h, int(slots), nb, int(max_prompt), int(max_new)))
+        if need == 0:
+            raise ValueError(f"beam session shape (slots={slots}, num_beams={nb}, max_prompt={max_prompt}, max_new={max_new}) not supported")
+        self.num_beams = nb
+        self._unit = nb
+        super().__init__(gpt, slots, max_prompt, max_new, use_graph, need,
+                         lambda ws, nbytes, sp: lib.idxtts_gpt_session_init_beam(gpt._h, int(slots), nb, int(max_prompt), int(max_new),
+                                                                                float(repetition_penalty), ws, nbytes, sp))
+        self.groups = self.slots // nb
+
+    @property
+    def free_groups(self):
+        return self._free()
+
+    @property
+    def live_groups(self):
+        return self._live()
+
+    def _beams(self, beam, caps):
+        """beam (one dict, or one per request) -> (BeamC array, noise tensors); parameter values are checked by the library."""
+        entries = [beam or {}] * len(caps) if beam is None or isinstance(beam, dict) else list(beam)
+        if len(entries) != len(caps):
+            raise ValueError("beam: one entry per request, or one entry for every request")
+        V, nb = self.gpt.cfg.number_mel_codes, self.num_beams
+        arr = (_lib.BeamC * len(caps))()
+        noises = []
+        for i, (e, cap) in enumerate(zip(entries, caps)):
+            unknown = set(e) - self._BEAM_KEYS
+            if unknown:
+                raise ValueError(f"beam: unknown keys {sorted(unknown)}")
+            if e.get("early_stopping", False) not in (False, True):
+                raise NotImplementedError('early_stopping="never" is not implemented')
+            noise, seed = None, 0
+            if e.get("exp_noise") is not None:
+                noise = torch.as_tensor(e["exp_noise"]).to(self.gpt.device, torch.float32).contiguous()
+                if tuple(noise.shape) != (cap, nb * V):
+                    raise ValueError(f"exp_noise must be [cap, num_beams * V] = {(cap, nb * V)}")
+            elif e.get("seed") is not None:
+                seed = _seed64(e["seed"])
+            else:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # as generate_beam() draws it
+            tp = e.get("top_p")
+            arr[i] = _lib.BeamC(num_beams=nb, do_sample=int(bool(e.get("do_sample", True))), temperature=float(e.get("temperature", 1.0)),
+                                top_k=int(e.get("top_k", 50) or 0), top_p=float(tp if tp is not None else 1.0),
+                                length_penalty=float(e.get("length_penalty", 1.0)), early_stopping=int(bool(e.get("early_stopping", False))),
+                                exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
+            noises.append(noise)
+        return arr, noises
+
+    def admit(self, inputs_embeds_rows, max_new_each, beam=None) -> list:
+        """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per request (or one int);
+        beam: the requests' parameters (see the class).  Returns their group ids.  A refused call takes no group."""
+        if len(inputs_embeds_rows) == 0:
+            return []
+        free = self.free_groups
+        rows, plen, caps = self._stage(inputs_embeds_rows, max_new_each, free)
+        n = len(rows)
+        ids = free[:n]
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
         with torch.cuda.stream(self.stream):
-            out = torch.empty(self.max_new, dtype=torch.long, device=self.gpt.device)
-            _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(slot), _lib.ptr(out), ctypes.byref(n), _lib.ptr(self._ws),
-                                                         self._sp()))
-        self._busy[slot] = False
-        self._done.discard(slot)
-        self._noise.pop(slot, None)
-        return out[: n.value]
+            beams, noises = self._beams(beam, caps)
+            emb, pm = self._embed_rows(rows, plen)
+            h_p, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, ids, caps))
+            _lib.check(self._lib.idxtts_gpt_session_admit_beam(
+                self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
+                h_caps.ctypes.data_as(c_void_p), ctypes.cast(beams, c_void_p), _lib.ptr(self._ws), self._sp()))
+        for g, nz in zip(ids, noises):
+            self._busy[g] = True
+            if nz is not None:
+                self._noise[g] = nz
+        return ids
 
-    def close(self) -> None:
-        if getattr(self, "_ws", None) is not None:
-            self.stream.synchronize()
-            self._lib.idxtts_gpt_session_release(self.gpt._h, _lib.ptr(self._ws))
-            self._ws = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def take(self, group: int) -> torch.Tensor:
+        """The codes of the finished request in `group` (LongTensor on the device); the group is free again."""
+        return super().take(group)

@@ -315,6 +315,43 @@ def utterance_samplers(sampling: Optional[dict], n: int) -> list:
     return [{"sampler": kind, "temperature": t, "top_k": k, "top_p": p, "seed": sd} for sd in seeds]
 
 
+_BEAM_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "generator", "seed", "length_penalty"}
+
+
+def utterance_beams(sampling: Optional[dict], n: int, num_beams: int) -> list:
+    """The per-utterance beam parameters of a request to a num_beams > 1 ContinuousPipeline (BeamDecodeSession.admit's `beam` entries).
+    `sampling` is the dict IndexTTS2.infer builds for beams (do_sample, num_beams, temperature, top_k, top_p, length_penalty,
+    generator) plus `seed`; num_beams must equal the pipeline's, missing values take UnifiedVoice.generate_beam's defaults (temperature
+    1.0, top_k 50, top_p 1.0, length_penalty 1.0; early_stopping False).  Beam-sample (do_sample): utterance i gets its seed by
+    utterance_samplers' rule -- torch.randint(0, 2**62, (1,), generator=g) in utterance order, g from `seed`, else `generator`, else
+    torch's global RNG.  Raises ValueError on a bad parameter."""
+    s = dict(sampling or {})
+    unknown = set(s) - _BEAM_KEYS
+    if unknown:
+        raise ValueError(f"sampling: unknown keys {sorted(unknown)}")
+    nb = int(s.get("num_beams") or 1)
+    if nb != int(num_beams):
+        raise ValueError(f"this ContinuousPipeline runs num_beams={num_beams}; the request asks for num_beams={nb}")
+    do_sample = bool(s.get("do_sample"))
+    t = float(s["temperature"]) if s.get("temperature") is not None else 1.0
+    k = int(s["top_k"]) if s.get("top_k") is not None else 50
+    p = float(s["top_p"]) if s.get("top_p") is not None else 1.0
+    lp = float(s["length_penalty"]) if s.get("length_penalty") is not None else 1.0
+    if do_sample:
+        if not t > 0.0:
+            raise ValueError("beam-sample needs a positive temperature")
+        if not 0 <= k <= 1024 or not p > 0.0:
+            raise ValueError("top_k must be in 0 .. 1024 and top_p > 0")
+        if p < 1.0 and not 0 < k <= 1024:
+            raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
+        g = torch.Generator().manual_seed(int(s["seed"])) if s.get("seed") is not None else s.get("generator")
+        seeds = [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
+    else:
+        seeds = [0] * n
+    return [{"do_sample": do_sample, "temperature": t, "top_k": k, "top_p": p, "length_penalty": lp, "early_stopping": False, "seed": sd}
+            for sd in seeds]
+
+
 class ContinuousPipeline:
     """Continuous (iteration-level) batching of the GPT decode: each of `decode_lanes` lanes owns one decode session of `slots` rows
     (`UnifiedVoice.decode_session`) on its own stream and host thread.  A lane admits waiting utterances into its free slots --
@@ -331,13 +368,23 @@ class ContinuousPipeline:
     (the decode attention's key split and the decode GEMV are chosen by row count).  An error (say, a bad token id or a bad sampling
     parameter) fails the offending request's Future only; num_beams > 1 is refused at submit.
 
+    num_beams > 1: beam search / beam-sample.  The lanes own beam sessions (`UnifiedVoice.beam_session`): `slots` rows = slots /
+    num_beams groups, one utterance per group, each retiring on its own; submit(sampling=...) takes the dict IndexTTS2.infer builds for
+    beams (its num_beams must equal the pipeline's) plus `seed` (utterance_beams).  An utterance's codes equal row 0 of
+    `UnifiedVoice.generate_beam` on slots / num_beams copies of it (gpt.BeamDecodeSession).
+
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
-                 session_factory=None, allow_sampling: bool = False):
+                 session_factory=None, allow_sampling: bool = False, num_beams: int = 1):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers and poll_steps must be >= 1")
+        self.num_beams = int(num_beams)
+        if not 1 <= self.num_beams <= 8:
+            raise ValueError("num_beams must be in 1 .. 8")
+        if slots % self.num_beams:
+            raise ValueError(f"slots ({slots}) must be a multiple of num_beams ({self.num_beams})")
         g = tts.cfg.gpt
         self.tts = tts
         self.device = torch.device(tts.device)
@@ -345,8 +392,12 @@ class ContinuousPipeline:
         self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
         self.max_new = int(max_new or g.max_mel_tokens)
         self.allow_sampling = bool(allow_sampling)
-        self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty,
-                                                                                 sampled=self.allow_sampling))
+        if self.num_beams > 1:
+            self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
+                                                                                   repetition_penalty=self.repetition_penalty))
+        else:
+            self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty,
+                                                                                     sampled=self.allow_sampling))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index) not admitted yet
@@ -373,11 +424,19 @@ class ContinuousPipeline:
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms); max_mel_tokens caps each row.  sampling: greedy
-        only, unless the pipeline was built with allow_sampling (see utterance_samplers)."""
+        only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
+        (see utterance_beams)."""
+        if self.num_beams > 1:
+            return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
+                                lambda B: utterance_beams(sampling, B, self.num_beams))
         if sampling and not self.allow_sampling:
             raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
         if sampling and int(sampling.get("num_beams") or 1) > 1:
             raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
+        return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None)
+
+    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -388,9 +447,9 @@ class ContinuousPipeline:
         j.codes, j.left, j.failed = [None] * B, B, False
         j.done = concurrent.futures.Future()
         j.sampling = None
-        if self.allow_sampling:
+        if per_utterance is not None:
             try:
-                j.sampling = utterance_samplers(sampling, B)
+                j.sampling = per_utterance(B)
             except ValueError as e:             # a bad parameter fails this request's Future only
                 j.done.set_exception(e)
                 return j.done
@@ -422,10 +481,15 @@ class ContinuousPipeline:
         conds = self.tts.gpt.conds_latent(lat, emo)
         return self.tts.gpt.prompt_rows(conds, j.text[idx])
 
+    def _free(self, sess):
+        """Free places of a lane's session: slots, or groups of a beam session."""
+        return sess.free_groups if self.num_beams > 1 else sess.free_slots
+
     def _admit(self, sess, in_slot) -> None:
         with self._cv:
             take = []
-            while self._waiting and len(take) < len(sess.free_slots):
+            free = len(self._free(sess))
+            while self._waiting and len(take) < free:
                 j, i = self._waiting.popleft()
                 if not j.failed:
                     take.append((j, i))
@@ -444,11 +508,14 @@ class ContinuousPipeline:
             rows.extend(rs)
             caps.extend([j.max_mel_tokens] * len(idx))
             owners.extend((j, i) for i in idx)
-            if self.allow_sampling:
+            if j.sampling is not None:
                 samplers.extend(j.sampling[i] for i in idx)
         if rows:
             try:
-                got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
+                if self.num_beams > 1:
+                    got = sess.admit(rows, caps, beam=samplers)
+                else:
+                    got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
             except BaseException as e:       # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
                 for j, _ in owners:
                     self._fail(j, e)
@@ -481,7 +548,7 @@ class ContinuousPipeline:
                             self._cv.wait()
                         if self._closing and not self._waiting and not in_slot:
                             break
-                    if sess.free_slots:
+                    if self._free(sess):
                         self._admit(sess, in_slot)
                     if in_slot:
                         self._collect(sess, in_slot, sess.step(self.poll_steps))

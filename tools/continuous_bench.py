@@ -10,8 +10,10 @@ exactly the caps):
 The two pipelines alternate, every shape is warmed up first, and each is repeated so the spread is known.  Prints one JSON line.
 --sampling compares ContinuousPipeline with greedy requests against ContinuousPipeline(allow_sampling=True) with HF-sampled requests
 (temperature 0.8, top_k 30, top_p 0.8: IndexTTS2.infer's defaults; one seed per request) on the same workloads instead.
+--beams N compares BatchPipeline and ContinuousPipeline(num_beams=N, slots = 16 N: 16 utterances in flight in both) on beam-sample
+requests with IndexTTS2.infer's defaults (num_beams N, temperature 0.8, top_k 30, top_p 0.8, length_penalty 0; seeded).
 
-    python tools/continuous_bench.py [--utterances 64] [--reps 3] [--sampling]
+    python tools/continuous_bench.py [--utterances 64] [--reps 3] [--sampling | --beams 3]
 """
 from __future__ import annotations
 
@@ -36,7 +38,10 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--poll-steps", type=int, default=16)
     ap.add_argument("--sampling", action="store_true", help="greedy against HF-sampled requests, both on ContinuousPipeline")
+    ap.add_argument("--beams", type=int, default=1, help="N > 1: beam-sample requests, BatchPipeline against ContinuousPipeline(num_beams=N)")
     args = ap.parse_args()
+    if args.beams > 1 and args.sampling:
+        ap.error("--sampling and --beams are separate comparisons")
     from indextts_amd import synth, weights
     from indextts_amd.config import PipelineConfig
     from indextts_amd.infer_v2 import IndexTTS2, PromptConditioning
@@ -82,13 +87,20 @@ def main() -> int:
         for wl in jobs:
             jobs[wl]["continuous_sampled"] = jobs[wl]["continuous"]
         sampling["continuous_sampled"] = {"do_sample": True, "temperature": 0.8, "top_k": 30, "top_p": 0.8}
+    if args.beams > 1:
+        nb = args.beams
+        pipes["continuous"] = lambda: ContinuousPipeline(tts, slots=W * nb, decode_lanes=1, poll_steps=args.poll_steps, max_new=800,
+                                                         num_beams=nb)
+        beam = {"do_sample": True, "num_beams": nb, "temperature": 0.8, "top_k": 30, "top_p": 0.8, "length_penalty": 0.0}
+        sampling["batch"] = sampling["continuous"] = beam
+    seeded = {"continuous", "continuous_sampled"}      # BatchPipeline's gpt_stage draws its seed from torch's global RNG (seeded below)
 
     def run(kind, wl):
         with pipes[kind]() as pipe:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             sp = sampling.get(kind)
-            futs = [pipe.submit(t, cond, max_mel_tokens=M, noise=z, sampling=dict(sp, seed=i) if sp else None)
+            futs = [pipe.submit(t, cond, max_mel_tokens=M, noise=z, sampling=(dict(sp, seed=i) if kind in seeded else dict(sp)) if sp else None)
                     for i, (t, M, z) in enumerate(jobs[wl][kind])]
             for f in futs:
                 f.result()
@@ -96,7 +108,8 @@ def main() -> int:
             return time.perf_counter() - t0
 
     out = {"utterances": N, "slots": W, "text_tokens": L, "prompt_frames": Tp, "reps": args.reps, "poll_steps": args.poll_steps,
-           "sampling": bool(args.sampling)}
+           "sampling": bool(args.sampling), "num_beams": args.beams}
+    torch.manual_seed(0)
     base, other = ("continuous", "continuous_sampled") if args.sampling else ("batch", "continuous")
     for wl in caps:
         for kind in pipes:          # warm-up: every shape (prefill widths, graphs, acoustic lengths) once
