@@ -475,6 +475,22 @@ int idxtts_s2mel_cfm(idxtts_ctx* ctx, const float* mu, const int* x_lens, const 
                      const float* style, const float* z, const float* t_emb, const float* dt, int n_steps, float cfg_rate,
                      float* out, int B, int T, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same solve on a batch whose rows come from DIFFERENT prompts (speakers): cfm.inference (flow_matching.py:31-115) on
+ * mu_b = cat([prompt_condition_b, gen_cond_b]) with prompt ref_mel_b, then vc_target = mel[:, :, Tp_b:] (infer_v2.py:850-856),
+ * for every row b at once.  gen_cond [B][Tg_max][content_dim] (the idxtts_s2mel_prepare_cond output) and target_lens HOST [B];
+ * prompt_conditions / ref_mels: HOST tables of B DEVICE pointers, row b's prompt_condition [Tp_b][content_dim] (16-byte aligned)
+ * and ref_mel [in_channels][Tp_b] -- rows of one speaker point at the same tensors --; prompt_lens HOST [B] = Tp_b;
+ * style [B][style_dim]; z [B][in_channels][T] with T = max_b(Tp_b + Tg_b), row b's noise in its first Tp_b + Tg_b frames;
+ * t_emb, dt, n_steps, cfg_rate as idxtts_s2mel_cfm.  out [B][in_channels][Tg_max]: row b's generated frames left-aligned,
+ * zero from target_lens[b] on (the vocoder's input as it is).  A row's frames do not depend on the other rows' prompts (the
+ * post-transformer part starts at the shortest prompt minus the WaveNet context: more frames, same values on this row's own).
+ * Workspace: idxtts_s2mel_cfm_rows_workspace_bytes(ctx, B, T, max_b Tp_b, n_steps). */
+size_t idxtts_s2mel_cfm_rows_workspace_bytes(const idxtts_ctx* ctx, int B, int T, int Tp_max, int n_steps);
+int idxtts_s2mel_cfm_rows(idxtts_ctx* ctx, const float* gen_cond, const int* target_lens, int Tg_max, const float* const* prompt_conditions,
+                          const float* const* ref_mels, const int* prompt_lens, const float* style, const float* z, const float* t_emb,
+                          const float* dt, int n_steps, float cfg_rate, float* out, int B, int T, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* One evaluation of the CFM estimator = DiT.forward(x, prompt_x, x_lens, t, style, cond) (diffusion_transformer.py:186-257),
  * the function `cfm.inference` calls once per Euler step on the [cond | null] stack (flow_matching.py:96).  x [B][in_channels][T];
  * prompt [B][in_channels][Tp_max] with prompt_lens HOST [B] (prompt_x is zero beyond them); x_lens HOST [B]; t_emb device

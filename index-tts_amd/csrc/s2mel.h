@@ -21,6 +21,7 @@ struct WNLayer {
   bool has_res = true;
 };
 
+struct CfmBuffers;
 struct CondBuffers { float *a, *b, *s, *stats; int *idx_code, *idx_row, *idx_interp, *tlen; size_t bytes; };
 
 struct S2MelModel : ModelBase {
@@ -47,9 +48,17 @@ struct S2MelModel : ModelBase {
   int cfm(const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host, int Tp_max, const float* style,
           const float* z, const float* t_emb, const float* dt_host, int n_steps, float cfg_rate, float* out, int B, int T,
           void* ws, size_t ws_bytes, hipStream_t st);
+  // mixed-prompt batch (idxtts_s2mel_cfm_rows): row b's speaker data through the HOST tables of device pointers; out [B][C][Tg_max]
+  size_t cfm_rows_workspace_bytes(int B, int T, int Tp_max, int n_steps) const;
+  int cfm_rows(const float* gen_cond, const int* target_lens_host, int Tg_max, const float* const* prompt_cond_host,
+               const float* const* ref_mel_host, const int* prompt_lens_host, const float* style, const float* z, const float* t_emb,
+               const float* dt_host, int n_steps, float cfg_rate, float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
   int estimator(const float* x, const float* prompt, const int* prompt_lens_host, int Tp_max, const int* x_lens_host, const float* t_emb,
                 const float* style, const float* mu, float* out_tm, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
   size_t cond_workspace_bytes(int B, int M, int Tg) const;
+  int cfm_solve(CfmBuffers& w, const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host, int Tp_max,
+                const float* style, const float* z, const float* t_emb, const float* dt_host, int n_steps, float cfg_rate, int B, int T,
+                hipStream_t st);
   int regulate_rows(const float* s_rows, const CondBuffers& w, int B, int M, int Tg, float* cond_out, hipStream_t st);
   int regulate(const float* S, const int* in_lens_host, const int* target_lens_host, int B, int M, int Tg, float* cond_out, void* ws,
                size_t ws_bytes, hipStream_t st);

@@ -633,8 +633,17 @@ int S2MelModel::cfm(const float* mu, const int* x_lens_host, const float* prompt
   IDX_CHECK(cfg_rate > 0.0f, "the stacked-CFG path needs inference_cfg_rate > 0 (reference default 0.7)");
   IDX_CHECK(T <= rope_len, "sequence longer than the rope cache");
   IDX_CHECK(ws && ws_bytes >= cfm_workspace_bytes(B, T, n_steps), "workspace too small");
-  const int D = cfg.hidden_dim, C = cfg.in_channels, Wh = cfg.wn_hidden, depth = cfg.depth, L = cfg.wn_layers;
   CfmBuffers w = carve_cfm(*this, ws, B, T, n_steps);
+  if (cfm_solve(w, mu, x_lens_host, prompt, prompt_lens_host, Tp_max, style, z, t_emb, dt_host, n_steps, cfg_rate, B, T, st)) return 1;
+  IDX_HIP(hipMemcpyAsync(out, w.xstate, (size_t)B * cfg.in_channels * T * sizeof(float), hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
+// The Euler solve shared by cfm and cfm_rows: leaves the final state x [B][C][T] in w.xstate.
+int S2MelModel::cfm_solve(CfmBuffers& w, const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host,
+                          int Tp_max, const float* style, const float* z, const float* t_emb, const float* dt_host, int n_steps,
+                          float cfg_rate, int B, int T, hipStream_t st) {
+  const int D = cfg.hidden_dim, C = cfg.in_channels, Wh = cfg.wn_hidden, depth = cfg.depth, L = cfg.wn_layers;
   std::vector<int> lens2(2 * B), plen(B);
   for (int b = 0; b < B; ++b) {
     IDX_CHECK(x_lens_host[b] > 0 && x_lens_host[b] <= T && prompt_lens_host[b] >= 0 && prompt_lens_host[b] <= std::min(Tp_max, x_lens_host[b]), "lengths");
@@ -676,8 +685,68 @@ int S2MelModel::cfm(const float* mu, const int* x_lens_host, const float* prompt
     eu.v_t0 = w.tail_t0; eu.v_T = T - w.tail_t0;
     if (cfm_euler(eu, st)) return 1;
   }
-  IDX_HIP(hipMemcpyAsync(out, w.xstate, (size_t)B * C * T * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+// ---- mixed-prompt batches: every row with its own speaker's prompt_condition / ref_mel (flow_matching.py:31-115, infer_v2.py:850-856) ----
+// The extra workspace behind the solver's: the packed mu rows [B][T][content_dim], the packed prompt mel [B][C][Tp_max], the
+// device copies of the two pointer tables and of the generated lengths.
+struct CfmRowsBuffers { float *mu, *prompt; const float **pcond, **ref_mel; int* gen_len; size_t bytes; };
+
+static CfmRowsBuffers carve_cfm_rows(const S2MelModel& m, void* ws, size_t base, int B, int T, int Tp_max) {
+  const auto& c = m.cfg;
+  CfmRowsBuffers b;
+  Carver2 k(ws ? static_cast<char*>(ws) + base : nullptr);
+  b.mu = k.take<float>((size_t)B * T * c.content_dim);
+  b.prompt = k.take<float>((size_t)B * c.in_channels * Tp_max);
+  b.pcond = k.take<const float*>(B);
+  b.ref_mel = k.take<const float*>(B);
+  b.gen_len = k.take<int>(B);
+  b.bytes = base + ((k.off + 255) & ~(size_t)255);
+  return b;
+}
+
+size_t S2MelModel::cfm_rows_workspace_bytes(int B, int T, int Tp_max, int n_steps) const {
+  return carve_cfm_rows(*this, nullptr, cfm_workspace_bytes(B, T, n_steps), B, T, Tp_max).bytes;
+}
+
+int S2MelModel::cfm_rows(const float* gen_cond, const int* target_lens_host, int Tg_max, const float* const* prompt_cond_host,
+                         const float* const* ref_mel_host, const int* prompt_lens_host, const float* style, const float* z,
+                         const float* t_emb, const float* dt_host, int n_steps, float cfg_rate, float* out, int B, int T, void* ws,
+                         size_t ws_bytes, hipStream_t st) {
+  IDX_CHECK(gen_cond && target_lens_host && prompt_cond_host && ref_mel_host && prompt_lens_host && style && z && t_emb && dt_host && out,
+            "null pointer");
+  IDX_CHECK(B > 0 && T > 0 && Tg_max > 0 && n_steps > 0, "shape");
+  IDX_CHECK(cfg_rate > 0.0f, "the stacked-CFG path needs inference_cfg_rate > 0 (reference default 0.7)");
+  IDX_CHECK(T <= rope_len, "sequence longer than the rope cache");
+  IDX_CHECK(cfg.content_dim % 4 == 0 && ((uintptr_t)gen_cond & 15) == 0, "gen_cond must be 16-byte aligned (content_dim % 4 == 0)");
+  std::vector<int> xl(B), tg(B);
+  int Tp_max = 0, T_need = 0;
+  for (int b = 0; b < B; ++b) {
+    const int Tp = prompt_lens_host[b], Tg = target_lens_host[b];
+    IDX_CHECK(Tp > 0 && Tg > 0 && Tg <= Tg_max, "prompt_lens / target_lens out of range");
+    IDX_CHECK(prompt_cond_host[b] && ref_mel_host[b], "null prompt table entry");
+    IDX_CHECK(((uintptr_t)prompt_cond_host[b] & 15) == 0, "prompt_condition rows must be 16-byte aligned");
+    xl[b] = Tp + Tg;
+    tg[b] = Tg;
+    Tp_max = std::max(Tp_max, Tp);
+    T_need = std::max(T_need, Tp + Tg);
+  }
+  IDX_CHECK(T == T_need, "T must be max_b(prompt_lens[b] + target_lens[b])");
+  IDX_CHECK(ws && ws_bytes >= cfm_rows_workspace_bytes(B, T, Tp_max, n_steps), "workspace too small");
+  CfmBuffers w = carve_cfm(*this, ws, B, T, n_steps);
+  CfmRowsBuffers r = carve_cfm_rows(*this, ws, w.bytes, B, T, Tp_max);
+  IDX_HIP(hipMemcpyAsync(r.pcond, prompt_cond_host, B * sizeof(float*), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(r.ref_mel, ref_mel_host, B * sizeof(float*), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(r.gen_len, tg.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(w.plen, prompt_lens_host, B * sizeof(int), hipMemcpyHostToDevice, st));    // (cfm_solve writes it again)
+  CfmRowsPackArgs pk;
+  pk.mu = r.mu; pk.prompt = r.prompt; pk.pcond = r.pcond; pk.ref_mel = r.ref_mel; pk.gen = gen_cond; pk.prompt_len = w.plen;
+  pk.gen_len = r.gen_len; pk.B = B; pk.T = T; pk.Dc = cfg.content_dim; pk.C = cfg.in_channels; pk.Tp_max = Tp_max; pk.Tg_max = Tg_max;
+  if (cfm_rows_pack(pk, st)) return 1;
+  // (the host tables above are consumed before cfm_solve returns: it synchronises the stream after its own uploads)
+  if (cfm_solve(w, r.mu, xl.data(), r.prompt, prompt_lens_host, Tp_max, style, z, t_emb, dt_host, n_steps, cfg_rate, B, T, st)) return 1;
+  return cfm_rows_emit(out, w.xstate, w.plen, r.gen_len, B, cfg.in_channels, T, Tg_max, st);
 }
 
 // One evaluation of the CFM estimator = DiT.forward(x, prompt_x, x_lens, t, style, cond) (diffusion_transformer.py:186-257)

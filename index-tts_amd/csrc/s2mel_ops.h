@@ -33,6 +33,21 @@ struct CfmEulerArgs {    // x += dt*((1+cfg)*v_cond - cfg*v_null); x[:, :, :Tp] 
 };
 int cfm_euler(const CfmEulerArgs& a, hipStream_t st);
 
+// Mixed-prompt batches (S2MelModel::cfm_rows): every row b brings its own speaker tensors, read through device pointer tables.
+struct CfmRowsPackArgs {
+  float* mu;                     // [B][T][Dc]: [prompt_cond_b (Tp_b rows) | gen_cond_b (Tg_b rows) | 0]   (infer_v2.py:850)
+  float* prompt;                 // [B][C][Tp_max]: ref_mel_b, zero beyond Tp_b
+  const float* const* pcond;     // [B] -> [Tp_b][Dc]
+  const float* const* ref_mel;   // [B] -> [C][Tp_b]
+  const float* gen;              // [B][Tg_max][Dc]
+  const int* prompt_len;         // [B] Tp_b
+  const int* gen_len;            // [B] Tg_b
+  int B, T, Dc, C, Tp_max, Tg_max;
+};
+int cfm_rows_pack(const CfmRowsPackArgs& a, hipStream_t st);
+// out[b][c][j] = j < gen_len[b] ? x[b][c][prompt_len[b] + j] : 0, j < Tg_max: each row's generated frames, left-aligned (infer_v2.py:856)
+int cfm_rows_emit(float* out, const float* x, const int* prompt_len, const int* gen_len, int B, int C, int T, int Tg_max, hipStream_t st);
+
 // GroupNorm(1 group) over the valid (row_len[b] x C) block of each sequence, then Mish; padded rows -> 0
 // (length_regulator.py:51-54 nn.GroupNorm(groups=1) + nn.Mish, per-utterance statistics)
 int groupnorm1_mish(float* y, const float* x, const float* gamma, const float* beta, const int* row_len, int B, int T, int C,

@@ -128,6 +128,61 @@ int cfm_init_state(float* x, const float* z, const int* prompt_len, int B, int C
   return 0;
 }
 
+// block = (t-tile of 64 frames, row b): the tile's mu rows (float4 columns), then the tile's prompt-mel columns t < Tp_max
+__global__ __launch_bounds__(256) void cfm_rows_pack_kernel(const CfmRowsPackArgs p) {
+  const int b = blockIdx.y, t0 = blockIdx.x * 64;
+  const int Tp = p.prompt_len[b], Tg = p.gen_len[b];
+  const int nt = min(64, p.T - t0);
+  const int W = p.Dc / 4;                   // (Dc % 4 == 0: checked by the caller)
+  const f32x4* pc = reinterpret_cast<const f32x4*>(p.pcond[b]);
+  const f32x4* gen = reinterpret_cast<const f32x4*>(p.gen + (size_t)b * p.Tg_max * p.Dc);
+  f32x4* mu = reinterpret_cast<f32x4*>(p.mu + ((size_t)b * p.T + t0) * p.Dc);
+  for (int e = threadIdx.x; e < nt * W; e += 256) {
+    const int tt = e / W, c = e - tt * W, t = t0 + tt;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (t < Tp) v = pc[(size_t)t * W + c];
+    else if (t < Tp + Tg) v = gen[(size_t)(t - Tp) * W + c];
+    mu[(size_t)tt * W + c] = v;
+  }
+  if (t0 >= p.Tp_max) return;
+  const int np = min(64, p.Tp_max - t0);
+  const float* ref = p.ref_mel[b];
+  for (int e = threadIdx.x; e < p.C * np; e += 256) {
+    const int c = e / np, t = t0 + (e - c * np);
+    p.prompt[((size_t)b * p.C + c) * p.Tp_max + t] = t < Tp ? ref[(size_t)c * Tp + t] : 0.0f;
+  }
+}
+
+int cfm_rows_pack(const CfmRowsPackArgs& a, hipStream_t st) {
+  IDX_CHECK(a.mu && a.prompt && a.pcond && a.ref_mel && a.gen && a.prompt_len && a.gen_len, "cfm_rows_pack args");
+  IDX_CHECK(a.B > 0 && a.T > 0 && a.Dc > 0 && a.Dc % 4 == 0 && a.Tp_max > 0 && a.Tp_max <= a.T, "cfm_rows_pack shape");
+  static const int cat = prof_register("cfm_rows_pack_kernel");
+  ProfScope prof(cat, st, 0.0, 8.0 * a.B * ((double)a.T * a.Dc + (double)a.C * a.Tp_max));
+  hipLaunchKernelGGL(cfm_rows_pack_kernel, dim3(cdiv(a.T, 64), a.B), dim3(256), 0, st, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void cfm_rows_emit_kernel(float* out, const float* x, const int* prompt_len, const int* gen_len, int B,
+                                                            int C, int T, int Tg_max) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * C * Tg_max) return;
+  const int j = (int)(idx % Tg_max);
+  const size_t bc = idx / Tg_max;           // = b * C + c
+  const int b = (int)(bc / C);
+  out[idx] = j < gen_len[b] ? x[bc * T + prompt_len[b] + j] : 0.0f;
+}
+
+int cfm_rows_emit(float* out, const float* x, const int* prompt_len, const int* gen_len, int B, int C, int T, int Tg_max, hipStream_t st) {
+  IDX_CHECK(out && x && prompt_len && gen_len && B > 0 && C > 0 && Tg_max > 0 && Tg_max <= T, "cfm_rows_emit args");
+  const size_t total = (size_t)B * C * Tg_max;
+  static const int cat = prof_register("cfm_rows_emit_kernel");
+  ProfScope prof(cat, st, 0.0, 8.0 * total);
+  hipLaunchKernelGGL(cfm_rows_emit_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, out, x, prompt_len, gen_len, B, C, T, Tg_max);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- GroupNorm(1) + Mish over token-major [B][T][C] with per-sequence valid length ----
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll

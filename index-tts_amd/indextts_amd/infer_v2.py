@@ -113,6 +113,26 @@ class PromptConditioning:
         return PromptConditioning(*out)
 
 
+def rows_conditioning(cond, B: int, device):
+    """`cond` as the stages take it: ONE PromptConditioning for all B rows, or a list / tuple of B of them, one per row (rows of one
+    speaker pass the same object).  Returns the single conditioning on `device` when every row shares one prompt (the single-prompt
+    path, unchanged), else a list of B device conditionings in which rows that passed the same object share one converted copy."""
+    if not isinstance(cond, (list, tuple)):
+        return cond.to(device)
+    if len(cond) != B:
+        raise ValueError(f"{len(cond)} prompt conditionings for {B} rows: pass one, or one per row")
+    if any(c is not cond[0] for c in cond):
+        if any(int(c.spk_cond_latent.shape[0]) != 1 or int(c.emo_vec.shape[0]) != 1 for c in cond):
+            raise ValueError("a per-row PromptConditioning holds one prompt (batch dimension 1)")
+    else:
+        return cond[0].to(device)
+    conv = {}
+    for c in cond:
+        if id(c) not in conv:
+            conv[id(c)] = c.to(device)
+    return [conv[id(c)] for c in cond]
+
+
 class IndexTTS2:
     """Drop-in for the hot path of `indextts.infer_v2.IndexTTS2`.
 
@@ -192,8 +212,9 @@ class IndexTTS2:
     def synthesize_batch(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
                          repetition_penalty: float = 10.0, noise: Optional[torch.Tensor] = None, sync_timers: bool = False,
                          return_intermediates: bool = False, sampling: Optional[dict] = None, per_row_noise: bool = False):
-        """One batch of single-segment utterances sharing a prompt: the body of the reference's segment loop
-        (infer_v2.py:732-881) for B rows at once.  text_tokens [B, L] (right-padded with stop_text_token).
+        """One batch of single-segment utterances: the body of the reference's segment loop (infer_v2.py:732-881) for B rows at once.
+        text_tokens [B, L] (right-padded with stop_text_token).  cond: one PromptConditioning shared by every row, or a list of B
+        of them, one per row (several speakers in one batch; see rows_conditioning).
         Returns a list of B waveforms, float32 [1, n_b] in int16 range (infer_v2.py:866).
         sampling: None = greedy; else the num_beams=1 sampling kwargs of UnifiedVoice.inference_speech
         (do_sample, temperature, top_k, top_p, sampler, exp_noise / generator).
@@ -218,12 +239,16 @@ class IndexTTS2:
         acoustic_stage consumes (device tensors + host lengths).  `codes` [B, n] (optional): take these codes instead of decoding --
         the rest of the flow on a given code sequence (parity checks feed the reference's codes through the stages behind the decode)."""
         dev = self.device
-        c = cond.to(dev)
         B = text_tokens.shape[0]
+        c = rows_conditioning(cond, B, dev)
         times = {}
         t0 = self._tick(sync_timers)
-        lat = c.spk_cond_latent.expand(B, -1, -1) if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent
-        emo = c.emo_vec.expand(B, -1) if c.emo_vec.shape[0] == 1 else c.emo_vec
+        if isinstance(c, list):      # one prompt per row: the GPT takes per-row conditioning latents and emotion vectors as they are
+            lat = torch.cat([x.spk_cond_latent for x in c])
+            emo = torch.cat([x.emo_vec for x in c])
+        else:
+            lat = c.spk_cond_latent.expand(B, -1, -1) if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent
+            emo = c.emo_vec.expand(B, -1) if c.emo_vec.shape[0] == 1 else c.emo_vec
         gen = dict(sampling) if sampling else {"do_sample": False}
         gen.setdefault("num_beams", 1)
         if codes is None:
@@ -256,26 +281,42 @@ class IndexTTS2:
 
     def acoustic_stage(self, st: dict, noise: Optional[torch.Tensor] = None, per_row_noise: bool = False, sync_timers: bool = False,
                        return_intermediates: bool = False):
-        """s2mel (length regulator + CFM) and the vocoder (infer_v2.py:835-866) on the current stream."""
+        """s2mel (length regulator + CFM) and the vocoder (infer_v2.py:835-866) on the current stream.  st["cond"]: one
+        PromptConditioning, or a list of one per row (rows_conditioning): then the CFM runs as ONE mixed-prompt batch
+        (S2Mel.cfm_rows) and row b's noise -- given, or drawn -- covers its own Tp_b + Tg_b frames from column 0."""
         dev = self.device
         c, B, codes, code_lens, code_lens_t, latent, times = (st["cond"], st["B"], st["codes"], st["code_lens"], st["code_lens_t"],
                                                               st["latent"], dict(st["times"]))
         t2 = self._tick(sync_timers)
         condv, target_lens = self.s2mel.prepare_condition(latent, codes, code_lens_t)
-        Tp = c.prompt_condition.shape[1]
         Tg = condv.shape[1]
-        cat_condition = torch.cat([c.prompt_condition.expand(B, -1, -1), condv], dim=1)     # infer_v2.py:850
-        x_lens = target_lens.cpu() + Tp
-        if noise is None and per_row_noise and B > 1:
-            noise = torch.zeros([B, self.cfg.s2mel.in_channels, Tp + Tg], device=dev)
-            for b in range(B):
-                nb = int(x_lens[b])
-                noise[b, :, :nb] = torch.randn([1, self.cfg.s2mel.in_channels, nb], device=dev)[0]
-        elif noise is None:
-            noise = torch.randn([B, self.cfg.s2mel.in_channels, Tp + Tg], device=dev)
-        mel = self.s2mel.cfm_inference(cat_condition, x_lens, c.ref_mel.expand(B, -1, -1), c.style.expand(B, -1), None,
-                                       self._diffusion_steps, inference_cfg_rate=self._cfg_rate, z=noise)
-        vc_target = mel[:, :, Tp:]                                                          # infer_v2.py:856
+        C = self.cfg.s2mel.in_channels
+        if isinstance(c, list):
+            x_lens = [int(x.prompt_condition.shape[1]) + int(t) for x, t in zip(c, target_lens.cpu().tolist())]
+            T = max(x_lens)
+            if noise is None and per_row_noise and B > 1:
+                noise = torch.zeros([B, C, T], device=dev)
+                for b in range(B):
+                    noise[b, :, :x_lens[b]] = torch.randn([1, C, x_lens[b]], device=dev)[0]
+            elif noise is None:
+                noise = torch.randn([B, C, T], device=dev)
+            vc_target = self.s2mel.cfm_rows(condv, target_lens, [x.prompt_condition for x in c], [x.ref_mel for x in c],
+                                            torch.cat([x.style for x in c]), self._diffusion_steps, inference_cfg_rate=self._cfg_rate,
+                                            z=noise)                                        # infer_v2.py:850-856, row by row
+        else:
+            Tp = c.prompt_condition.shape[1]
+            cat_condition = torch.cat([c.prompt_condition.expand(B, -1, -1), condv], dim=1)     # infer_v2.py:850
+            x_lens = target_lens.cpu() + Tp
+            if noise is None and per_row_noise and B > 1:
+                noise = torch.zeros([B, C, Tp + Tg], device=dev)
+                for b in range(B):
+                    nb = int(x_lens[b])
+                    noise[b, :, :nb] = torch.randn([1, C, nb], device=dev)[0]
+            elif noise is None:
+                noise = torch.randn([B, C, Tp + Tg], device=dev)
+            mel = self.s2mel.cfm_inference(cat_condition, x_lens, c.ref_mel.expand(B, -1, -1), c.style.expand(B, -1), None,
+                                           self._diffusion_steps, inference_cfg_rate=self._cfg_rate, z=noise)
+            vc_target = mel[:, :, Tp:]                                                      # infer_v2.py:856
         t3 = self._tick(sync_timers)
         times["s2mel_time"] = t3 - t2
         # vocoder: one ragged batch; every layer pads at each row's OWN end (zeros for the convolutions, replicate for the

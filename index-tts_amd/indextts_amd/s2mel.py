@@ -144,6 +144,54 @@ class S2Mel:
                                         float(inference_cfg_rate), _lib.ptr(out), B, T, _lib.ptr(ws), ws.numel(), _lib.current_stream()))
         return out
 
+    def cfm_rows(self, gen_cond: torch.Tensor, target_lens, prompt_conditions, ref_mels, style: torch.Tensor, n_timesteps: int = 20,
+                 inference_cfg_rate: float = 0.7, z: torch.Tensor = None) -> torch.Tensor:
+        """The CFM solve on a batch whose rows have DIFFERENT prompts (idxtts_s2mel_cfm_rows): row b is
+        `cfm_inference(cat([prompt_conditions[b], gen_cond[b, :Tg_b]], 1), Tp_b + Tg_b, ref_mels[b], style[b], z=z[b:b+1, :, :Tp_b + Tg_b])
+        [:, :, Tp_b:]` (infer_v2.py:850-856).  gen_cond [B,Tg_max,512] (prepare_condition's output), target_lens [B];
+        prompt_conditions / ref_mels: B entries, [1,Tp_b,512] / [1,80,Tp_b] (rows of one speaker may pass the same tensor: it is
+        read in place, not copied per row); style [B,192]; z [B,80,T] with T = max_b(Tp_b + Tg_b), row b's noise from column 0.
+        Returns vc_target [B,80,Tg_max]: row b's generated frames, zero from Tg_b on."""
+        lib = _lib.load()
+        gen = gen_cond.to(self.device, torch.float32).contiguous()
+        B, Tg_max, _ = gen.shape
+        tl = np.ascontiguousarray(torch.as_tensor(target_lens).detach().cpu().reshape(-1).numpy(), dtype=np.int32)
+        if len(prompt_conditions) != B or len(ref_mels) != B or len(tl) != B:
+            raise ValueError("cfm_rows needs one prompt_condition, ref_mel and target length per row")
+        kept = {}          # one device-resident, contiguous fp32 copy per distinct tensor (usually the tensor itself)
+
+        def dev(t):
+            k = id(t)
+            if k not in kept:
+                kept[k] = t.to(self.device, torch.float32).contiguous()
+            return kept[k]
+        pcs = [dev(p) for p in prompt_conditions]
+        rms = [dev(r) for r in ref_mels]
+        pl = np.array([int(p.shape[-2]) for p in pcs], dtype=np.int32)
+        for p, r in zip(pcs, rms):
+            if p.shape[-1] != self.cfg.content_dim or r.shape[-2] != self.cfg.in_channels or r.shape[-1] != p.shape[-2]:
+                raise ValueError("prompt_condition [1,Tp,content_dim] and ref_mel [1,in_channels,Tp] of a row must agree")
+        T = int((pl + tl).max())
+        style = style.to(self.device, torch.float32).contiguous()
+        if z is None:
+            z = torch.randn([B, self.cfg.in_channels, T], device=self.device)
+        z = z.to(self.device, torch.float32)
+        if z.shape[-1] < T:
+            raise ValueError(f"z covers {z.shape[-1]} frames; the longest row needs {T}")
+        z = z[:, :, :T].contiguous()
+        pc_tab = (c_void_p * B)(*[p.data_ptr() for p in pcs])
+        rm_tab = (c_void_p * B)(*[r.data_ptr() for r in rms])
+        t_emb, dt = timestep_tables(n_timesteps)
+        t_emb = t_emb.to(self.device)
+        dt_h = np.ascontiguousarray(dt.numpy(), dtype=np.float32)
+        out = torch.empty(B, self.cfg.in_channels, Tg_max, device=self.device, dtype=torch.float32)
+        ws = self._workspace(int(lib.idxtts_s2mel_cfm_rows_workspace_bytes(self._h, B, T, int(pl.max()), n_timesteps)))
+        _lib.check(lib.idxtts_s2mel_cfm_rows(self._h, _lib.ptr(gen), tl.ctypes.data_as(c_void_p), Tg_max, pc_tab, rm_tab,
+                                             pl.ctypes.data_as(c_void_p), _lib.ptr(style), _lib.ptr(z), _lib.ptr(t_emb),
+                                             dt_h.ctypes.data_as(c_void_p), n_timesteps, float(inference_cfg_rate), _lib.ptr(out), B, T,
+                                             _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+        return out
+
     def estimator(self, x: torch.Tensor, prompt_x: torch.Tensor, x_lens, t: torch.Tensor, style: torch.Tensor, cond: torch.Tensor,
                   prompt_lens=None) -> torch.Tensor:
         """`cfm.estimator(x, prompt_x, x_lens, t, style, cond)` = DiT.forward (diffusion_transformer.py:186-257): x, prompt_x

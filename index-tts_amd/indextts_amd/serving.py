@@ -7,8 +7,9 @@ and fill the chip.  `BatchPipeline` keeps `decode_lanes` decode chains running a
 own host thread (the C call releases the GIL), with its own KV-cache workspace -- and runs the acoustic stages on
 `acoustic_workers` further streams.
 
-`acoustic_coalesce` > 1 lets a free acoustic worker take that many decoded requests (same prompt, explicit CFM noise) as ONE s2mel +
-vocoder batch; `coalesce` > 1 is dynamic batching of the decode: a lane that becomes free takes up to `coalesce` waiting requests of the same
+`acoustic_coalesce` > 1 lets a free acoustic worker take that many decoded requests (same prompt, or any prompts with
+`acoustic_mix_prompts=True`; explicit CFM noise) as ONE s2mel + vocoder batch; `coalesce` > 1 is dynamic batching of the decode: a
+lane that becomes free takes up to `coalesce` waiting requests of the same
 prompt and text width and decodes them as ONE batch (a decode step streams the 965 MB of GPT weights once whatever the number of rows, so two
 16-utterance requests decoded together cost little more than one), then hands every request's rows to its own acoustic job.
 
@@ -66,6 +67,33 @@ def merge_keeps_kernels(rows_each, prefix_len: int, split_bf16_gemm: bool, compa
     return True
 
 
+def merge_acoustic_states(items):
+    """Several requests' `gpt_stage` states as ONE acoustic batch.  items: (cond, state, noise) per request, `cond` being what the
+    request was submitted with (one PromptConditioning, or one per row).  Rows are independent in s2mel and the vocoder (ragged
+    lengths: every row is padded at its own end), so stacking them only changes how the launches fill the chip.  Requests of ONE
+    prompt keep the single-prompt path (state["cond"] = that prompt); otherwise state["cond"] is the list of every row's prompt
+    (IndexTTS2.acoustic_stage then runs S2Mel.cfm_rows), rows submitted with the same object sharing one device copy.  Each request's
+    noise keeps its rows' frames from column 0 and is zero-padded on the right.  Returns (state, noise)."""
+    sts = [st for _, st, _ in items]
+    n = max(st["codes"].shape[1] for st in sts)
+    codes = torch.cat([torch.nn.functional.pad(st["codes"], (0, n - st["codes"].shape[1])) for st in sts])
+    latent = torch.cat([torch.nn.functional.pad(st["latent"], (0, 0, 0, n - st["latent"].shape[1])) for st in sts])
+    T = max(z.shape[-1] for _, _, z in items)
+    noise = torch.cat([torch.nn.functional.pad(z, (0, T - z.shape[-1])) for _, _, z in items])
+    keys, first = [], {}
+    for cond, st, _ in items:
+        dc = st["cond"]
+        for b in range(st["B"]):
+            k = id(cond[b]) if isinstance(cond, (list, tuple)) else id(cond)
+            first.setdefault(k, dc[b] if isinstance(dc, list) else dc)
+            keys.append(k)
+    rows = [first[k] for k in keys]
+    cond = sts[0]["cond"] if all(k == keys[0] for k in keys) else rows
+    st = {"cond": cond, "B": sum(st["B"] for st in sts), "codes": codes, "code_lens": [c for st in sts for c in st["code_lens"]],
+          "code_lens_t": torch.cat([st["code_lens_t"] for st in sts]), "latent": latent, "times": dict(sts[0]["times"])}
+    return st, noise
+
+
 class _Request:
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "repetition_penalty", "sampling", "ready", "caller", "done")
 
@@ -78,7 +106,9 @@ class _Request:
 
 class BatchPipeline:
     def __init__(self, tts, decode_lanes: int = 3, acoustic_workers: int = 1, coalesce: int = 1, lane_priority: str = "high",
-                 acoustic_coalesce: int = 1, exclusive: bool = False):
+                 acoustic_coalesce: int = 1, exclusive: bool = False, acoustic_mix_prompts: bool = False):
+        """acoustic_mix_prompts: let `acoustic_coalesce` merge decoded requests of DIFFERENT prompts into one acoustic batch (a
+        mixed-prompt CFM, S2Mel.cfm_rows); default: only requests of one prompt object are merged."""
         if decode_lanes < 1 or acoustic_workers < 1 or coalesce < 1 or acoustic_coalesce < 1:
             raise ValueError("decode_lanes, acoustic_workers, coalesce and acoustic_coalesce must be >= 1")
         self.tts = tts
@@ -87,6 +117,7 @@ class BatchPipeline:
         self.acoustic_workers = acoustic_workers
         self.coalesce = coalesce
         self.acoustic_coalesce = acoustic_coalesce
+        self.acoustic_mix_prompts = bool(acoustic_mix_prompts)
         self._aq = collections.deque()         # decoded requests waiting for an acoustic worker: (request, state)
         lo_pri, hi_pri = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
         self._pri = {"decode": hi_pri if lane_priority == "high" else lo_pri, "acoustic": lo_pri}
@@ -199,31 +230,22 @@ class BatchPipeline:
                     r.done.set_exception(e)
 
     def _take_acoustic(self):
-        """Up to `acoustic_coalesce` decoded requests of one prompt, each with its own CFM noise (a merged draw would consume the
-        generator differently from the separate calls)."""
+        """Up to `acoustic_coalesce` decoded requests of one prompt (of any prompts with acoustic_mix_prompts), each with its own CFM
+        noise (a merged draw would consume the generator differently from the separate calls)."""
         with self._qlock:
             if not self._aq:
                 return []
             group = [self._aq.popleft()]
             while (len(group) < self.acoustic_coalesce and self._aq and group[0][0].noise is not None and self._aq[0][0].noise is not None
-                   and self._aq[0][0].cond is group[0][0].cond):
+                   and (self.acoustic_mix_prompts or self._aq[0][0].cond is group[0][0].cond)):
                 group.append(self._aq.popleft())
             return group
 
     @staticmethod
     def _merge_states(group):
-        """Several decoded batches as ONE acoustic batch: rows are independent in s2mel and the vocoder (ragged lengths: every row is
-        padded at its own end), so stacking them only changes how the launches fill the chip.  (Measured neutral at configs[2]:
-        181.8 vs 182.3 audio-s/s, profiles/README.md "Round 3"; useful where single requests are small.)"""
-        sts = [st for _, st in group]
-        n = max(st["codes"].shape[1] for st in sts)
-        codes = torch.cat([torch.nn.functional.pad(st["codes"], (0, n - st["codes"].shape[1])) for st in sts])
-        latent = torch.cat([torch.nn.functional.pad(st["latent"], (0, 0, 0, n - st["latent"].shape[1])) for st in sts])
-        T = max(r.noise.shape[-1] for r, _ in group)
-        noise = torch.cat([torch.nn.functional.pad(r.noise, (0, T - r.noise.shape[-1])) for r, _ in group])
-        st = {"cond": sts[0]["cond"], "B": sum(st["B"] for st in sts), "codes": codes, "code_lens": [c for st in sts for c in st["code_lens"]],
-              "code_lens_t": torch.cat([st["code_lens_t"] for st in sts]), "latent": latent, "times": dict(sts[0]["times"])}
-        return st, noise
+        """Several decoded batches as ONE acoustic batch (merge_acoustic_states).  (Measured neutral at configs[2]: 181.8 vs 182.3
+        audio-s/s, profiles/README.md "Round 3"; useful where single requests are small.)"""
+        return merge_acoustic_states([(r.cond, st, r.noise) for r, st in group])
 
     def _acoustic_drain(self):
         group = self._take_acoustic()
@@ -276,7 +298,7 @@ class BatchPipeline:
 
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed", "sampling")
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed", "sampling", "seq")
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
@@ -373,13 +395,27 @@ class ContinuousPipeline:
     beams (its num_beams must equal the pipeline's) plus `seed` (utterance_beams).  An utterance's codes equal row 0 of
     `UnifiedVoice.generate_beam` on slots / num_beams copies of it (gpt.BeamDecodeSession).
 
+    acoustic_coalesce > 1: a free acoustic worker takes up to that many decoded requests -- of any prompts -- and runs their s2mel +
+    vocoder as ONE batch of at most `acoustic_max_rows` rows (a request with more rows runs alone), then hands every request its own
+    rows.  Each request's latent pass (`gpt_stage(codes=)`) still runs on its own: it left-pads the text, so merging it would move
+    tile boundaries.  Only requests that carry explicit `noise` are merged (BatchPipeline's rule: a merged draw would consume the
+    generator differently); the rows of requests with different prompts go through the mixed-prompt CFM (S2Mel.cfm_rows).  A failure
+    fails every request of its merged batch and nothing else.  Requests that finish in the same poll are queued together, so a worker
+    that is free then sees all of them.  `trace`: set it to a list to record ("acoustic", start, end, rows, request numbers) for
+    every acoustic job (host perf_counter times; requests numbered from 0 in submission order).
+
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
-                 session_factory=None, allow_sampling: bool = False, num_beams: int = 1):
-        if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1:
-            raise ValueError("slots, decode_lanes, acoustic_workers and poll_steps must be >= 1")
+                 session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
+                 acoustic_max_rows: int = 16):
+        if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
+            raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
+        self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
+        self._aq = collections.deque()          # decoded requests waiting for an acoustic worker
+        self._submitted = 0
+        self.trace = None
         self.num_beams = int(num_beams)
         if not 1 <= self.num_beams <= 8:
             raise ValueError("num_beams must be in 1 .. 8")
@@ -446,7 +482,7 @@ class ContinuousPipeline:
         B = int(j.text.shape[0])
         j.codes, j.left, j.failed = [None] * B, B, False
         j.done = concurrent.futures.Future()
-        j.sampling = None
+        j.sampling, j.seq = None, -1
         if per_utterance is not None:
             try:
                 j.sampling = per_utterance(B)
@@ -461,6 +497,8 @@ class ContinuousPipeline:
         with self._cv:
             if self._closing or self._alive == 0:
                 raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
+            j.seq = self._submitted
+            self._submitted += 1
             self._waiting.extend((j, i) for i in range(B))
             self._cv.notify_all()
         return j.done
@@ -524,6 +562,7 @@ class ContinuousPipeline:
                 in_slot[s] = o
 
     def _collect(self, sess, in_slot, finished) -> None:
+        done = []
         for s in finished:
             j, i = in_slot.pop(s)
             codes = sess.take(s).cpu()
@@ -532,7 +571,12 @@ class ContinuousPipeline:
             j.codes[i] = codes
             j.left -= 1
             if j.left == 0:
-                self._acoustic.submit(self._acoustic_job, j)
+                done.append(j)
+        if done:
+            with self._cv:                  # every request this poll finished is queued before any worker looks
+                self._aq.extend(done)
+            for _ in done:
+                self._acoustic.submit(self._acoustic_drain)      # one drain per request: a drain that finds nothing (merged away) returns
 
     def _lane(self):
         sess, in_slot = None, {}
@@ -568,32 +612,72 @@ class ContinuousPipeline:
         with self._cv:
             self._alive -= 1
 
-    def _acoustic_job(self, j: _Job):
+    def _take_acoustic(self) -> list:
+        """The next acoustic job: the oldest decoded request, plus -- when it carries explicit noise -- the next ones that also do,
+        up to `acoustic_coalesce` requests and `acoustic_max_rows` rows (requests without noise, or too many rows, wait for a job of
+        their own)."""
+        with self._cv:
+            if not self._aq:
+                return []
+            group = [self._aq.popleft()]
+            rows = int(group[0].text.shape[0])
+            if group[0].noise is not None:
+                i = 0
+                while len(group) < self.acoustic_coalesce and i < len(self._aq):
+                    j = self._aq[i]
+                    nb = int(j.text.shape[0])
+                    if j.noise is not None and rows + nb <= self.acoustic_max_rows:
+                        del self._aq[i]
+                        group.append(j)
+                        rows += nb
+                    else:
+                        i += 1
+            return group
+
+    def _acoustic_drain(self):
+        group = self._take_acoustic()
+        if not group:
+            return
         try:
             if self._cuda:
                 torch.cuda.set_device(self.device)
+            t0 = time.perf_counter()
             sa = getattr(self._tls, "stream", None)
             if sa is None:
                 sa = self._tls.stream = self._new_stream()
             stop = self.tts.cfg.gpt.stop_mel_token
-            n = max(int(c.shape[0]) for c in j.codes)
-            codes = torch.full((len(j.codes), n), stop, dtype=torch.long)
-            for i, c in enumerate(j.codes):
-                codes[i, : c.shape[0]] = c
+            states = []
             with self._on(sa):
-                if j.ready is not None:
-                    sa.wait_event(j.ready)
-                st = self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens, repetition_penalty=self.repetition_penalty,
-                                        codes=codes)
-                wavs = self.tts.acoustic_stage(st, noise=j.noise)
+                for j in group:                 # the latent pass per request (merging it would re-pad the text)
+                    n = max(int(c.shape[0]) for c in j.codes)
+                    codes = torch.full((len(j.codes), n), stop, dtype=torch.long)
+                    for i, c in enumerate(j.codes):
+                        codes[i, : c.shape[0]] = c
+                    if j.ready is not None:
+                        sa.wait_event(j.ready)
+                    states.append(self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens,
+                                                     repetition_penalty=self.repetition_penalty, codes=codes))
+                if len(group) == 1:
+                    st, noise = states[0], group[0].noise
+                else:
+                    st, noise = merge_acoustic_states([(j.cond, s, j.noise) for j, s in zip(group, states)])
+                wavs = self.tts.acoustic_stage(st, noise=noise)
                 if sa is not None:
                     sa.synchronize()
-            if j.caller is not None:
-                for w in wavs:                  # allocated on the worker's stream, consumed on the caller's
-                    w.record_stream(j.caller)
-            j.done.set_result(wavs)
-        except BaseException as e:              # noqa: BLE001
-            self._fail(j, e)
+            if self.trace is not None:
+                self.trace.append(("acoustic", t0, time.perf_counter(), sum(int(j.text.shape[0]) for j in group),
+                                   tuple(j.seq for j in group)))
+            a = 0
+            for j in group:
+                mine = wavs[a:a + int(j.text.shape[0])]
+                a += int(j.text.shape[0])
+                if j.caller is not None:
+                    for w in mine:              # allocated on the worker's stream, consumed on the caller's
+                        w.record_stream(j.caller)
+                j.done.set_result(mine)
+        except BaseException as e:              # noqa: BLE001 -- every request of this acoustic batch fails, nothing else
+            for j in group:
+                self._fail(j, e)
 
     def close(self):
         with self._cv:
