@@ -15,8 +15,12 @@ Workloads (BASELINE.json `configs`):
 One process per GPU; utterance batches shard data-parallel (weak scaling: every rank synthesises its own batch, full
 weight replica); exchange steps of the path: conditioning broadcast from rank 0 before, waveform gather to rank 0 after
 (RCCL over xGMI), nothing inside the hot loop.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed on its launch stream) and
-`cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample).
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set up, warm up, time the K steps,
+write --dump-outputs, print; `roofline` and `cpu_baseline` are null there.  With --full the run goes on, after the timed steps
+and the dump, to everything else it measures or checks: every pipelined output against the sequential call
+(`config.outputs_equal_sequential`), the exact mode (`exact_mode`: the same pipelined run on the fp32 KV cache), `roofline`
+(dominant kernel, HIP-event timed on its launch stream) with `stage_seconds` / `roofline_stages` / `decode`, and `cpu_baseline`
+(the CPU oracle timed on the host's cores on a bounded sample, with the decode parity legs).
 """
 from __future__ import annotations
 
@@ -260,7 +264,7 @@ def build_pipeline(args, world, rank, dev):
     log(f"[bench] rank {rank}: synthetic weights in {time.time() - t0:.1f}s")
     compact = args.gpt_weights != "f32"
     tts = IndexTTS2.from_state_dicts(cfg, wg, ws, wv, device=dev, gpt_weight_format=args.gpt_weights, gpt_kv_format=args.gpt_kv,
-                                     keep_effective_gpt=compact and rank == 0 and not args.no_cpu_baseline)
+                                     keep_effective_gpt=compact and rank == 0 and args.full and not args.no_cpu_baseline)
     kv16 = tts.gpt.kv_format == "bf16"
     if tts.gpt.effective_state_dict is not None:      # the CPU leg runs the SAME (rounded) model the kernels run
         wg = tts.gpt.effective_state_dict
@@ -577,9 +581,13 @@ def main() -> int:
     ap.add_argument("--codes", type=int, default=0, help="codes per utterance (default 512; longform 1500)")
     ap.add_argument("--prompt-frames", type=int, default=689)
     ap.add_argument("--cpu-codes", type=int, default=96, help="codes of the bounded CPU-baseline utterance")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-exact-mode", action="store_true", help="pipeline workload: skip the second timed run with the fp32 KV cache")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps and the dump, also run what the headline does not need: the check of every pipelined "
+                         "output against the sequential call, the exact mode (fp32 KV cache), the per-kernel roofline with the stage "
+                         "timers, and the CPU oracle baseline with its parity legs (default: none of them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline and the stage timers")
+    ap.add_argument("--no-exact-mode", action="store_true", help="with --full, pipeline workload: skip the second timed run with the fp32 KV cache")
     ap.add_argument("--decode-lanes", type=int, default=3,
                     help="pipeline workload: decode chains of consecutive batches in flight at once (each on its own stream and host thread)")
     ap.add_argument("--acoustic-workers", type=int, default=1, help="pipeline workload: s2mel + vocoder stages of different batches in flight at once")
@@ -708,7 +716,7 @@ def main() -> int:
             if b >= t_start:
                 log(f"[bench] job {kind:8s} {rows:3d} rows  start {a - t_start:8.3f} s  end {b - t_start:8.3f} s  ({b - a:.3f} s)")
     equal_seq = None
-    if hasattr(step, "reference"):      # every step has the same inputs: each retired batch must equal the sequential call bit for bit
+    if args.full and hasattr(step, "reference"):      # every step has the same inputs: each retired batch must equal the sequential call bit for bit
         ref = step.reference()
         outs = outs + list(getattr(step, "flushed", []))[-args.steps:] + [out]
         equal_seq = bool(all(torch.equal(o, ref) for o in outs))
@@ -719,8 +727,8 @@ def main() -> int:
     # greedy codes are the oracle's up to fp32 summation order) -- reported beside the headline when the headline stores the cache as bf16.
     exact_mode = None
     tts_obj = getattr(step, "tts", None)
-    if (args.workload == "pipeline" and not args.no_exact_mode and tts_obj is not None and tts_obj.gpt.kv_format == "bf16" and not args.no_overlap
-            and not args.longform):
+    if (args.full and args.workload == "pipeline" and not args.no_exact_mode and tts_obj is not None and tts_obj.gpt.kv_format == "bf16"
+            and not args.no_overlap and not args.longform):
         k2 = max(2, min(args.steps, 6))
         tts_obj.gpt.set_kv_format("f32")
         step(last=True); flush(); torch.cuda.synchronize()
@@ -743,7 +751,7 @@ def main() -> int:
         log(f"[bench] exact mode (fp32 KV cache): {k2} steps in {e2:.3f}s = {exact_mode['value']} audio-s/s")
 
     roofline = stages = roofline_stages = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # same work again with per-launch HIP events on the launch stream (graph replay is bypassed while profiling)
         empty_ms = _lib.profile_event_overhead(400)
         _lib.profile_enable(True)
@@ -775,7 +783,7 @@ def main() -> int:
                                               int(desc["codes"] * 1.72), desc["diffusion_steps"], wb, kv_bytes=2 if desc.get("gpt_kv_cache") == "bf16" else 4)
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_leg is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_leg is not None:
         cpu_baseline = cpu_leg()
 
     if rank == 0:

@@ -1,5 +1,6 @@
-"""GPU: bench.py keeps its output contract (one JSON line on stdout with the driver's keys, the `roofline` and `cpu_baseline`
-objects) -- run at a reduced size so it finishes in about two minutes; the weights are the full-size architecture."""
+"""GPU: bench.py keeps its output contract (one JSON line on stdout with the driver's keys; with --full also the `roofline`,
+`cpu_baseline` and `exact_mode` objects) -- run at a reduced size so it finishes in about two minutes; the weights are the full-size
+architecture."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "4",
-           "--codes", "24", "--text-tokens", "40", "--prompt-frames", "120", "--cpu-codes", "64", "--dump-outputs", str(tmp_path / "out")]
+           "--codes", "24", "--text-tokens", "40", "--prompt-frames", "120", "--cpu-codes", "64", "--dump-outputs", str(tmp_path / "out"), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -25,6 +26,7 @@ def test_bench_json_contract(tmp_path):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 0 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["vs_baseline"] is None and d["value"] > 0 and "workload" in d["config"] and "model" not in d["config"]
+    assert d["config"]["outputs_equal_sequential"] is True
     rf = d["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in rf, k
@@ -54,6 +56,32 @@ def test_bench_json_contract(tmp_path):
     em = d["exact_mode"]
     assert em["gpt_kv"] == "f32" and em["value"] > 0 and em["codes_match_rate"] >= 0.97 and em["max_abs_logit_diff"] <= em["logit_bound"]
     # --dump-outputs: the last timed step's waveforms (4 utterances of exactly 24 codes = 41 mel frames x 256 samples)
+    wavs, lens = np.load(tmp_path / "out" / "wavs.npy"), np.load(tmp_path / "out" / "wav_lengths.npy")
+    assert wavs.dtype == np.float32 and wavs.shape == (4, 41 * 256) and np.isfinite(wavs).all() and np.abs(wavs).max() > 0
+    assert lens.dtype == np.float64 and lens.tolist() == [41 * 256] * 4
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the run prints the same headline keys and writes the same outputs, and measures or checks nothing else:
+    no sequential-equality check, no exact mode, no roofline or stage timers, no CPU baseline."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+           "--codes", "24", "--text-tokens", "40", "--prompt-frames", "120", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["unit"] == "audio_s/s" and d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"].startswith("f32")
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for k in ("exact_mode", "stage_seconds", "roofline_stages", "decode"):
+        assert k not in d, k
+    assert "outputs_equal_sequential" not in d["config"]
+    for phrase in ("equal the sequential", "exact mode", "stage seconds", "cpu baseline", "decode parity"):
+        assert phrase not in r.stderr, phrase
     wavs, lens = np.load(tmp_path / "out" / "wavs.npy"), np.load(tmp_path / "out" / "wav_lengths.npy")
     assert wavs.dtype == np.float32 and wavs.shape == (4, 41 * 256) and np.isfinite(wavs).all() and np.abs(wavs).max() > 0
     assert lens.dtype == np.float64 and lens.tolist() == [41 * 256] * 4

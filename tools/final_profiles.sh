@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end evidence on the MI355X box (after tools/profile_round.sh): rocprofv3 kernel stats of the prompt and infer_default workloads,
-# then the default bench line with the fresh traffic file in place.   bash tools/final_profiles.sh r03
+# then the full bench line (roofline, CPU baseline) with the fresh traffic file in place.   bash tools/final_profiles.sh r03
 set -o pipefail
 R=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
@@ -14,5 +14,5 @@ for W in prompt infer_default; do
 done
 rm -rf /tmp/prof_w
 [ -f $OUT/traffic_${R}.json ] && cp $OUT/traffic_${R}.json $ROOT/profiles/traffic_${R}.json
-cd $ROOT && python3 bench.py > $OUT/${R}_pipeline_bench.log 2>&1 || exit 1
+cd $ROOT && python3 bench.py --full > $OUT/${R}_pipeline_bench.log 2>&1 || exit 1
 tail -1 $OUT/${R}_pipeline_bench.log | cut -c1-300
