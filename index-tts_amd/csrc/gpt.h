@@ -1,5 +1,6 @@
 #pragma once
 #include <atomic>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -35,6 +36,16 @@ struct GPTLayer {
   const float *fc_u = nullptr, *fc_c = nullptr;       // folded LayerNorm 2
 };
 
+// a captured decode step and its instance (plain data: whoever holds one drops it)
+struct StepGraph {
+  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+  void drop() {
+    if (exec) (void)hipGraphExecDestroy(exec);
+    if (graph) (void)hipGraphDestroy(graph);
+    exec = nullptr; graph = nullptr;
+  }
+};
+
 struct GPTModel : ModelBase {
   idxtts_gpt_config cfg;
   std::vector<GPTLayer> layers;
@@ -53,8 +64,8 @@ struct GPTModel : ModelBase {
   int* oob_flag = nullptr;        // device ints (one per embed() call in flight): set by the embedding gather when an index exceeds its table
   std::atomic<unsigned> oob_next{0};
   ~GPTModel() override {
-    for (GraphSlot& g : graph_cache) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); }
-    for (auto& kv : sessions) kv.second.drop_graph();
+    for (GraphSlot& g : graph_cache) g.step.drop();
+    for (auto& kv : sessions) kv.second.step.drop();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 
@@ -73,16 +84,19 @@ struct GPTModel : ModelBase {
     DecodeState* state;
     long long* codes;                         // [B][max_new] generated codes of the call in flight (copied to the caller's tensor at the end)
     size_t bytes;
+    // The step's tail (its last launches) is chosen from these fields alone:
     SlotState* slots = nullptr;               // decode session only (carve_session): per-row step scalars; the step uses them, not `state`
     SlotSampling* slot_samp = nullptr;        // sampled decode session only: each slot's sampler (the step samples with it)
-    SlotBeam* slot_beam = nullptr;            // beam decode session only: each group's parameters; `beam` then is its step's beam tail
+    idxtts_sampling samp{0, 1.0f, 0, 1.0f, nullptr, 0};      // generate(): the call's sampler (mode 0 = greedy)
+    const long long* forced = nullptr; int forced_ld = 0;   // generate_forced: [B][forced_ld] tokens fed back instead of the argmax
+    bool beam_tail = false;                   // the beam stages on `beam`: a beam session's (slots set) or generate_beam's
     BeamState beam;
   };
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
   struct GraphSlot {
     void* ws = nullptr; size_t ws_bytes = 0; int B = 0, S = 0, max_new = 0; float penalty = 0.0f; int kv16 = 0, geom = 0;
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; unsigned long stamp = 0; bool in_use = false;
+    StepGraph step; unsigned long stamp = 0; bool in_use = false;
   };
   std::vector<GraphSlot> graph_cache;
   std::mutex graph_mu;
@@ -105,19 +119,27 @@ struct GPTModel : ModelBase {
   };
   int layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter = nullptr);
   int head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st);      // ln_f -> final_norm -> mel_head
-  int head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, long long* codes, int codes_ld,
-                      float* logits_out, hipStream_t st);
-  int decode_step(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base, hipStream_t st);
-  int decode_step_pl(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base, hipStream_t st);
-  bool use_pl(int B) const;        // this many decode rows run on the plane GEMV
-  bool fused_tail(int B) const;    // ... and the generation in flight is greedy: sample + embed + advance are one launch
-  // (the sampling mode of the generation in flight is thread-local state in gpt.hip: generate() is re-entrant across host threads,
-  //  each call with its own workspace and stream)
+  // the step's tail writes w.codes [B][codes_ld]; pos_hint: keys the step reads as the host knows them (profiler accounting; 0 when
+  // the step is captured)
+  int head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, int codes_ld, float* logits_out,
+                      hipStream_t st);
+  int decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
+  int decode_step_pl(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
+  int capture_step(const Buffers& w, int B, float penalty, int codes_ld, hipStream_t st, StepGraph* g);   // one decode step -> *g
+  bool use_pl(int B) const;                   // this many decode rows run on the plane GEMV
+  bool fused_tail(const Buffers& w) const;    // w's step tail also writes the next input and advances: no embed_step / advance_state
+  // generate() and generate_beam() are re-entrant across host threads, each call with its own workspace and stream; both run on
+  // call_stream()'s stream through run_generation() (gpt.hip): R = B * fan rows, row r on prompt r / fan, the step tail w's own
+  int call_stream(hipStream_t user, hipStream_t* st);
+  int run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
+                     float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll, int poll_n,
+                     int poll_every, int* steps_done, hipStream_t st);
   int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_sampling* sampling, long long* codes,
                int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr);
   // Beam search / beam-sample (HF _beam_search; the reference's default decoding mode, infer_v2.py:714-722): B utterances x
   // num_beams rows through the same decode step, selection / hypotheses / re-indexing on the device (beam.hip).
   size_t beam_workspace_bytes(int B, int nb, int S, int max_new) const;
+  BeamState beam_state(const Buffers& w, const BeamBuffers& bb, int B, int nb, int seq_ld) const;   // the fields both beam paths share
   int generate_beam(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_beam* beam,
                     long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st);
   int latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws, size_t ws_bytes,
@@ -138,12 +160,7 @@ struct GPTModel : ModelBase {
     std::vector<char> busy;           // admitted and not yet read
     bool warm = false;                // one step has run eagerly (first-use function attributes are set outside a capture)
     int geom = -1;                    // decode geometry the graph was captured under
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    void drop_graph() {
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
-      exec = nullptr; graph = nullptr;
-    }
+    StepGraph step;
   };
   std::map<void*, Session> sessions;
   std::mutex session_mu;
@@ -164,6 +181,11 @@ struct GPTModel : ModelBase {
   Session* find_session(void* ws);
   int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false,
                    int num_beams = 0);
+  // The admission both session kinds share: n requests into the free units ids[] -- slots, or (fan > 1) groups of fan slots -- each
+  // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's
+  // keys and values going to its unit's slots.  *S: positions per prefill row.
+  int admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                    const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S, hipStream_t st);
   // per_row: null = every row greedy; else one sampler per row (sampled sessions only)
   int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
                     const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr);
@@ -185,11 +207,5 @@ struct GPTModel : ModelBase {
 struct BeamHyp { double score; const int* toks; int len; };
 int beam_finalize(int nb, double length_penalty, int hyp_n, const double* hyp_score, const int* hyp_len, const int* hyp_slot,
                   const int* hyp_seq, int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best);
-
-// beam state of the generation this host thread is running (null = greedy / sampling); read by head_and_sample
-extern thread_local const BeamState* tl_beam;
-// cached positions (incl. the token in flight) of the eager decode step being launched: the profiler's byte accounting of the decode
-// attention (0 while a captured graph replays: the host does not know the position then)
-extern thread_local int tl_prof_pos;
 
 }  // namespace idxtts

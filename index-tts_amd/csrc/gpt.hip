@@ -16,6 +16,7 @@
 // step is captured once into a hipGraph and replayed per token (launch-bound otherwise).
 // The decode weight streams are fp32 by default; quantize_weights() rounds the model once to bf16 / fp8-e4m3 storage
 // (BASELINE configs[4]) -- the arithmetic stays the fp32 MFMA.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -334,13 +335,6 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   return 0;
 }
 
-// sampling mode of the generation this host thread is running (mode 0 = greedy)
-static thread_local idxtts_sampling samp{0, 1.0f, 0, 1.0f, nullptr, 0};
-thread_local const BeamState* tl_beam = nullptr;
-thread_local int tl_prof_pos = 0;
-static thread_local const long long* tl_forced = nullptr;      // teacher-forced generation in flight: [B][max_new] tokens fed back instead of the argmax
-static thread_local int tl_forced_ld = 0;      // keys the eager decode step in flight reads (0 while a captured graph replays)
-
 // head on B rows: ln_f -> final_norm (one rows_norm launch, output as fragment images) -> mel_head -> w.logits
 int GPTModel::head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st) {
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
@@ -362,37 +356,37 @@ int GPTModel::head_logits(const Buffers& w, int B, const float* x, int ldx, bool
   return 0;
 }
 
-// head on B rows -> greedy sampler (or the sampling / beam stages of the generation in flight)
-int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, long long* codes,
-                              int codes_ld, float* logits_out, hipStream_t st) {
+// head on B rows -> the step tail w describes: greedy sampler, sampler, beam stages, or a session's per-slot samplers
+int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, int codes_ld,
+                              float* logits_out, hipStream_t st) {
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
   const bool pl = use_pl(B);
   if (head_logits(w, B, x, ldx, x_frag, st)) return 1;
-  if (w.slot_beam) {      // beam decode session: the beam stages on every live group, the last one with the fused tail (beam.h)
+  if (w.beam_tail) {      // the beam stages (beam.h); a beam session's work on every live group, its last one with the fused tail
     BeamState bs = w.beam;
     bs.penalty = penalty;
     return beam_scores_forward(bs, st) || beam_select_forward(bs, st) || beam_reorder_forward(bs, st);
   }
-  if (tl_beam) return beam_scores_forward(*tl_beam, st) || beam_select_forward(*tl_beam, st) || beam_reorder_forward(*tl_beam, st);
   SampleArgs s;
   s.part = w.logits; s.parts = 1; s.part_rows = B; s.bias = nullptr; s.logits_out = logits_out;
-  s.seen = w.seen; s.finished = w.finished; s.codes = codes; s.codes_ld = codes_ld; s.cur_tok = w.cur_tok;
+  s.seen = w.seen; s.finished = w.finished; s.codes = w.codes; s.codes_ld = codes_ld; s.cur_tok = w.cur_tok;
   s.st = w.state; s.B = B; s.V = V; s.stop_token = cfg.stop_mel_token; s.penalty = penalty;
-  s.forced = tl_forced; s.forced_ld = tl_forced_ld;
+  s.forced = w.forced; s.forced_ld = w.forced_ld;
   if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
     if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
     s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d;
     if (w.slot_samp) return sample_slots_warp_forward(s, w.slots, w.slot_samp, nullptr, B, st);      // sampled session: each slot's own sampler
     return sample_slots_forward(s, w.slots, nullptr, B, st);
   }
-  if (fused_tail(B)) {      // the sampler's workgroups also write the next step's input and advance the step scalars
+  if (fused_tail(w)) {      // the sampler's workgroups also write the next step's input and advance the step scalars
     if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
     s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d; s.embed.st_rw = w.state;
   }
-  if (samp.mode != 0) {
+  if (w.samp.mode != 0) {
+    const idxtts_sampling& r = w.samp;
     SampleWarpArgs sw;
-    sw.base = s; sw.mode = samp.mode; sw.temperature = samp.temperature; sw.top_k = samp.top_k; sw.top_p = samp.top_p;
-    sw.exp_noise = samp.exp_noise; sw.seed = samp.seed;
+    sw.base = s; sw.mode = r.mode; sw.temperature = r.temperature; sw.top_k = r.top_k; sw.top_p = r.top_p;
+    sw.exp_noise = r.exp_noise; sw.seed = r.seed;
     return sample_warp_forward(sw, st);
   }
   return sample_greedy_forward(s, st);
@@ -405,15 +399,16 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
 // requests, 16 utterances x 3 beams).  Measured on the full-size model, 256 tokens, graph replay: 16 rows 0.328 s against 0.303 s on the
 // fp32-MFMA GEMV (its single-round-trip launches win), 32 rows 0.432 / 0.432, 48 rows 0.567 / 0.612 (profiles/README.md "Round 4").
 bool GPTModel::use_pl(int B) const { return weight_fmt != WFMT_F32 && B >= get_decode_plane_rows() && cfg.model_dim % 32 == 0 && head_p.wp; }
-bool GPTModel::fused_tail(int B) const { (void)B; return samp.mode == 0 && !tl_beam; }      // greedy: sample + next embedding + advance are ONE launch
+// sessions, and greedy one-shot generations: sample + next embedding + advance are ONE launch
+bool GPTModel::fused_tail(const Buffers& w) const { return w.slots || (w.samp.mode == 0 && !w.beam_tail); }
 
 // The decode step on the plane GEMV (gemv_pl.hip): the same five launches per layer, every activation a plain fp32 row-major matrix
 // (split into bf16 planes inside the GEMV), the residual stream updated in place, the LayerNorm statistics handed from producer to consumer; greedy generations close the
 // step with ONE launch (sample + next embedding + advance).
-int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base, hipStream_t st) {
+int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st) {
   const int d = cfg.model_dim, T = d / 16;
   const size_t per_layer = kv_layer_bytes(B, w.Smax);
-  const bool fused = w.slots || fused_tail(B);
+  const bool fused = fused_tail(w);
   if (!fused && embed_step_pl(w.xrow, w.stats, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
     const GPTLayer& L = layers[li];
@@ -426,7 +421,7 @@ int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, long long* 
     da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out_row = w.attrow; da.kstart = w.kstart;
     da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
     da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
-    da.pos_hint = tl_prof_pos;
+    da.pos_hint = pos_hint;
     if (decode_attn_forward(da, st)) return 1;
     GemvPLArgs pa;      // x += c_proj(attn) + b (in place: a lane reads and writes only its own elements of x), + the row statistics of the new x
     pa.x = w.attrow; pa.ldx = d; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xrow; pa.y = w.xrow; pa.ldy = d; pa.stats_out = w.stats;
@@ -441,16 +436,15 @@ int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, long long* 
     fb.slab = w.pl_slab; fb.counters = w.pl_cnt;
     if (gemv_pl_forward(L.fc2_p, fb, st)) return 1;
   }
-  if (head_and_sample(w, B, w.xrow, d, false, penalty, codes, codes_ld, logits_base, st)) return 1;
+  if (head_and_sample(w, B, w.xrow, d, false, penalty, codes_ld, logits_base, st)) return 1;
   return fused ? 0 : advance_state(w.state, st);
 }
 
-int GPTModel::decode_step(const Buffers& w, int B, float penalty, long long* codes, int codes_ld, float* logits_base,
-                          hipStream_t st) {
-  if (use_pl(B)) return decode_step_pl(w, B, penalty, codes, codes_ld, logits_base, st);
+int GPTModel::decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st) {
+  if (use_pl(B)) return decode_step_pl(w, B, penalty, codes_ld, logits_base, pos_hint, st);
   const int d = cfg.model_dim;
   const size_t per_layer = kv_layer_bytes(B, w.Smax);
-  const bool fused = w.slots || fused_tail(B);      // greedy: the previous step's sampler has written this step's x and advanced the step scalars
+  const bool fused = fused_tail(w);      // the previous step's tail has written this step's x and advanced the step scalars
   if (!fused && embed_step(w.xd, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
     const GPTLayer& L = layers[li];
@@ -462,7 +456,7 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, long long* cod
     da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out = w.attd; da.kstart = w.kstart;
     da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
     da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
-    da.pos_hint = tl_prof_pos;
+    da.pos_hint = pos_hint;
     if (decode_attn_forward(da, st)) return 1;
     GemvFXArgs pa;      // x += c_proj(attn) + b  (in place: a thread reads and writes only its own element of x)
     pa.xf = w.attd; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xd; pa.y = w.xd; pa.y_frag = 1;
@@ -483,8 +477,119 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, long long* cod
       if (gemv_fx_forward(L.fc2_g, fb, st)) return 1;
     }
   }
-  if (head_and_sample(w, B, w.xd, d, true, penalty, codes, codes_ld, logits_base, st)) return 1;
+  if (head_and_sample(w, B, w.xd, d, true, penalty, codes_ld, logits_base, st)) return 1;
   return fused ? 0 : advance_state(w.state, st);
+}
+
+// one decode step captured into g (every per-step value is device-resident, so the graph replays the step); the caller drops g
+int GPTModel::capture_step(const Buffers& w, int B, float penalty, int codes_ld, hipStream_t st, StepGraph* g) {
+  IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  const int rc = decode_step(w, B, penalty, codes_ld, nullptr, 0, st);
+  const hipError_t e = hipStreamEndCapture(st, &g->graph);
+  if (rc) return 1;
+  IDX_HIP(e);
+  IDX_HIP(hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0));
+  return 0;
+}
+
+// The legacy default stream cannot be captured into a graph: a one-shot generation on it runs on a private stream, ordered after
+// everything already queued by the caller (the call ends with a host sync anyway: n_steps is a host value).
+int GPTModel::call_stream(hipStream_t user, hipStream_t* st) {
+  *st = user;
+  if (user) return 0;
+  if (!own_stream) IDX_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+  IDX_HIP(hipStreamSynchronize(user));
+  *st = own_stream;
+  return 0;
+}
+
+// The one-shot generations' driver (generate, generate_beam) on R = B * fan rows, row r on prompt r / fan with its left pad: resets
+// the per-call state, prefills, runs the first head step, then steps 1 .. max_new - 1 -- eagerly (logits_out [max_new][R][V]), or
+// with `graph` step 1 eagerly and the others replayed from `exec` (a kept graph of this shape) or else from a captured one, handed
+// to *captured when that is not null.  Every poll_every steps it reads the poll_n device flags `poll` and stops when all are set.
+int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
+                             float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll,
+                             int poll_n, int poll_every, int* steps_done, hipStream_t st) {
+  const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1, R = B * fan;
+  // ---- per-call state ----
+  std::vector<int> kstart(R, 0);
+  for (int r = 0; r < R; ++r) {
+    kstart[r] = pad_left_host ? pad_left_host[r / fan] : 0;
+    IDX_CHECK(kstart[r] >= 0 && kstart[r] < P, "pad_left out of range");
+  }
+  IDX_HIP(hipMemcpyAsync(w.kstart, kstart.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemsetAsync(w.finished, 0, R * sizeof(int), st));
+  IDX_HIP(hipMemsetAsync(w.ksb_cnt, 0, (size_t)cdiv(d, 16) * sizeof(unsigned), st));
+  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, (size_t)R * cfg.heads * sizeof(unsigned), st));
+  IDX_HIP(hipMemsetAsync(w.xd, 0, w.frag_bytes, st));      // padding rows of the fragment images (the region starts at xd)
+  // input_ids of the reference = fake prefix of 1s + start_mel_token: both count for the repetition penalty
+  std::vector<unsigned char> seen((size_t)R * V, 0);
+  for (int r = 0; r < R; ++r) { seen[(size_t)r * V + 1] = 1; seen[(size_t)r * V + cfg.start_mel_token] = 1; }
+  IDX_HIP(hipMemcpyAsync(w.seen, seen.data(), seen.size(), hipMemcpyHostToDevice, st));
+  const DecodeState s0{P, 1, 0, 0};
+  IDX_HIP(hipMemcpyAsync(w.state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
+  const std::vector<int> tok(R, cfg.start_mel_token);
+  IDX_HIP(hipMemcpyAsync(w.cur_tok, tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));
+
+  // ---- prefill: x = [inputs_embeds | mel_emb[start] + mel_pos[0]] ----
+  for (int j = 0; j < fan; ++j)      // rows j, fan + j, 2 fan + j, ... from prompts 0, 1, 2, ...
+    IDX_HIP(hipMemcpy2DAsync(w.x + (size_t)j * S * d, (size_t)fan * S * d * sizeof(float), inputs_embeds, (size_t)P * d * sizeof(float),
+                             (size_t)P * d * sizeof(float), B, hipMemcpyDeviceToDevice, st));
+  GatherArgs ga;
+  ga.out = w.x + (size_t)P * d; ga.ld_out = S * d; ga.d = d;
+  ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;           // start_mel_token rows
+  ga.table[1] = mel_pos; ga.idx[1] = w.finished;          // all zeros -> mel position 0
+  if (gather_sum_rows(ga, R, st)) return 1;
+  for (int li = 0; li < cfg.layers; ++li)
+    if (layer_full(li, w, R, S, w.kstart, true, st)) return 1;
+  // the first token: the head on the last position of every row
+  if (head_and_sample(w, R, w.x + (size_t)(S - 1) * d, S * d, false, penalty, max_new, logits_out, st)) return 1;
+  if (!fused_tail(w) && advance_state(w.state, st)) return 1;
+
+  // ---- decode ----
+  struct Guard {      // a captured graph not handed over: released on every return path
+    StepGraph g;
+    ~Guard() { g.drop(); }
+  } cap;
+  int n_first = 1;
+  if (graph && max_new > 2) {
+    // step 1 runs eagerly (first-use function attributes are set outside the capture), steps >= 2 replay
+    if (decode_step(w, R, penalty, max_new, nullptr, S + 1, st)) return 1;
+    n_first = 2;
+    if (!exec) {
+      if (capture_step(w, R, penalty, max_new, st, &cap.g)) return 1;
+      exec = cap.g.exec;
+    }
+  }
+  std::vector<int> flags(poll_n);
+  *steps_done = n_first;
+  for (int n = n_first; n < max_new; ++n) {
+    if (exec) {
+      IDX_HIP(hipGraphLaunch(exec, st));
+    } else {
+      float* lo = logits_out ? logits_out + (size_t)n * R * V : nullptr;
+      if (decode_step(w, R, penalty, max_new, lo, S + n, st)) return 1;      // S + n: keys this step reads
+    }
+    *steps_done = n + 1;
+    if ((n + 1) % poll_every == 0 || n + 1 == max_new) {      // every row finished / every utterance done? (HF stops there)
+      IDX_HIP(hipMemcpyAsync(flags.data(), poll, poll_n * sizeof(int), hipMemcpyDeviceToHost, st));
+      IDX_HIP(hipStreamSynchronize(st));
+      if (std::all_of(flags.begin(), flags.end(), [](int f) { return f != 0; })) break;
+    }
+  }
+  if (captured) std::swap(*captured, cap.g);
+  return 0;
+}
+
+// the rules sample_warp_forward applies, checked before anything runs (generate(), every row of a sampled session admission)
+static int check_sampling(const idxtts_sampling& r) {
+  IDX_CHECK(r.mode == 0 || r.mode == SAMPLE_HF || r.mode == SAMPLE_ACCEL, "sampling mode (0 greedy, 1 HF, 2 accel)");
+  if (r.mode == 0) return 0;
+  IDX_CHECK(r.temperature > 0.0f, "sampling needs a positive temperature");
+  IDX_CHECK(r.top_k >= 0 && r.top_p > 0.0f, "sampling parameters");
+  IDX_CHECK(r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
+  return 0;
 }
 
 int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
@@ -492,157 +597,67 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
                        hipStream_t user_stream, const long long* forced) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out, "null pointer");
   GenScope gen_scope(this);
-  struct ForcedScope {      // the forced tokens apply to this call only, whatever path it returns on
-    ForcedScope(const long long* f, int ld) { tl_forced = f; tl_forced_ld = ld; }
-    ~ForcedScope() { tl_forced = nullptr; tl_forced_ld = 0; }
-  } forced_scope(forced, max_new);
   IDX_CHECK(!forced || !(sampling && sampling->mode != 0), "teacher forcing is a greedy-mode instrument");
-  // The legacy default stream cannot be captured into a graph: run on a private stream, ordered after
-  // everything already queued by the caller (the call ends with a host sync anyway: n_steps is a host value).
-  hipStream_t st = user_stream;
-  if (user_stream == nullptr) {
-    if (!own_stream) IDX_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
-    IDX_HIP(hipStreamSynchronize(user_stream));
-    st = own_stream;
-  }
   IDX_CHECK(B > 0 && B <= 64 && P > 0 && max_new > 0, "shape (1 <= B <= 64)");
-  samp = idxtts_sampling{0, 1.0f, 0, 1.0f, nullptr, 0};
-  if (sampling && sampling->mode != 0) {
-    IDX_CHECK(sampling->mode == SAMPLE_HF || sampling->mode == SAMPLE_ACCEL, "sampling mode");
-    IDX_CHECK(sampling->temperature > 0.0f, "sampling needs a positive temperature");
-    IDX_CHECK(sampling->top_p >= 1.0f || (sampling->top_k > 0 && sampling->top_k <= 1024), "top-p needs 0 < top_k <= 1024");
-    samp = *sampling;
-  }
-  const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1;
+  if (sampling && check_sampling(*sampling)) return 1;
+  const int S = P + 1;
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
   IDX_CHECK(ws && ws_bytes >= workspace_bytes(B, S, max_new), "workspace too small");
+  hipStream_t st = nullptr;
+  if (call_stream(user_stream, &st)) return 1;
   Buffers w = carve(ws, B, S, max_new);
-  long long* const user_codes = codes;
-  codes = w.codes;           // every launch writes here (a stable address: the captured decode step can be kept); copied out at the end
-  IDX_HIP(hipMemcpyAsync(codes, user_codes, (size_t)B * max_new * sizeof(long long), hipMemcpyDeviceToDevice, st));      // the caller's pad fill
+  if (sampling && sampling->mode != 0) w.samp = *sampling;
+  w.forced = forced; w.forced_ld = max_new;
+  // every launch writes w.codes (a stable address: the captured decode step can be kept); the caller's pad fill in, copied out at the end
+  IDX_HIP(hipMemcpyAsync(w.codes, codes, (size_t)B * max_new * sizeof(long long), hipMemcpyDeviceToDevice, st));
 
-  // ---- per-call state ----
-  std::vector<int> kstart(B, 0);
-  if (pad_left_host) for (int b = 0; b < B; ++b) kstart[b] = pad_left_host[b];
-  for (int b = 0; b < B; ++b) IDX_CHECK(kstart[b] >= 0 && kstart[b] < P, "pad_left out of range");
-  IDX_HIP(hipMemcpyAsync(w.kstart, kstart.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemsetAsync(w.finished, 0, B * sizeof(int), st));
-  IDX_HIP(hipMemsetAsync(w.ksb_cnt, 0, (size_t)cdiv(d, 16) * sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, (size_t)B * cfg.heads * sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(static_cast<char*>(ws) + w.frag_off, 0, w.frag_bytes, st));   // padding rows of the fragment images
-  // input_ids of the reference = fake prefix of 1s + start_mel_token: both count for the repetition penalty
-  std::vector<unsigned char> seen((size_t)B * V, 0);
-  for (int b = 0; b < B; ++b) { seen[(size_t)b * V + 1] = 1; seen[(size_t)b * V + cfg.start_mel_token] = 1; }
-  IDX_HIP(hipMemcpyAsync(w.seen, seen.data(), seen.size(), hipMemcpyHostToDevice, st));
-  DecodeState s0{P, 1, 0, 0};
-  IDX_HIP(hipMemcpyAsync(w.state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));   // host staging buffers go out of scope below
-
-  // ---- prefill: x = [inputs_embeds | mel_emb[start] + mel_pos[0]] ----
-  IDX_HIP(hipMemcpy2DAsync(w.x, (size_t)S * d * sizeof(float), inputs_embeds, (size_t)P * d * sizeof(float),
-                           (size_t)P * d * sizeof(float), B, hipMemcpyDeviceToDevice, st));
-  {
-    std::vector<int> tok(B, cfg.start_mel_token);
-    IDX_HIP(hipMemcpyAsync(w.cur_tok, tok.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-    IDX_HIP(hipStreamSynchronize(st));
-    DecodeState zero{0, 0, 0, 0};
-    (void)zero;
-    // reuse embed_step with a temporary state whose mel_pos = 0: state currently has mel_pos = 1, so gather directly
-    GatherArgs ga;
-    ga.out = w.x + (size_t)P * d; ga.ld_out = S * d; ga.d = d;
-    ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;           // start_mel_token rows
-    ga.table[1] = mel_pos; ga.idx[1] = w.finished;          // all zeros -> mel position 0
-    if (gather_sum_rows(ga, B, st)) return 1;
-  }
-  for (int li = 0; li < cfg.layers; ++li)
-    if (layer_full(li, w, B, S, w.kstart, true, st)) return 1;
-  {
-    // last position of every row
-    if (head_and_sample(w, B, w.x + (size_t)(S - 1) * d, S * d, false, penalty, codes, max_new, logits_out, st)) return 1;
-    if (!fused_tail(B) && advance_state(w.state, st)) return 1;      // (the fused sampler of the plane-GEMV path has advanced already)
-  }
-
-  // ---- decode ----
-  struct GraphGuard {      // a graph that is not kept: released on every return path (error paths after the capture included)
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    ~GraphGuard() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
-  } gg;
+  // Instantiated decode-step graphs of greedy generations are kept (graph_cache): nothing call-specific is baked into their launches
+  const bool graph = use_graph && !logits_out && !forced && !prof_enabled();
+  const bool cacheable = graph && w.samp.mode == 0;
+  const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
   struct SlotLease {       // a cached graph in use by this call
     GPTModel* m = nullptr; int idx = -1;
     ~SlotLease() { if (m && idx >= 0) { std::lock_guard<std::mutex> l(m->graph_mu); m->graph_cache[idx].in_use = false; } }
   } lease;
   hipGraphExec_t exec = nullptr;
-  const bool graph_ok = use_graph && !logits_out && !forced && !prof_enabled();
-  const bool cacheable = samp.mode == 0 && !tl_beam;      // greedy: nothing call-specific is baked into the launches
-  int n_first = 1;
-  if (graph_ok && max_new > 2) {
-    // step 1 runs eagerly (first-use function attributes are set outside the capture), steps >= 2 replay
-    if (decode_step(w, B, penalty, codes, max_new, nullptr, st)) return 1;
-    n_first = 2;
-    if (cacheable) {
-      std::lock_guard<std::mutex> l(graph_mu);
-      for (size_t i = 0; i < graph_cache.size(); ++i) {
-        GraphSlot& g = graph_cache[i];
-        if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv16 == kv_fmt && g.geom == (get_decode_geometry() | (get_decode_plane_rows() << 1))) {
-          g.in_use = true; g.stamp = ++graph_stamp; exec = g.exec; lease.m = this; lease.idx = (int)i;
-          break;
-        }
-      }
-    }
-    if (!exec) {
-      IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = decode_step(w, B, penalty, codes, max_new, nullptr, st);
-      hipError_t e = hipStreamEndCapture(st, &gg.graph);
-      if (rc) return 1;
-      IDX_HIP(e);
-      IDX_HIP(hipGraphInstantiate(&gg.exec, gg.graph, nullptr, nullptr, 0));
-      exec = gg.exec;
-      if (cacheable) {      // keep it: hand the objects over to a cache slot (a free one, or the least recently used idle one)
-        std::lock_guard<std::mutex> l(graph_mu);
-        int slot = -1;
-        // an idle entry on the same workspace address describes launches that can no longer be replayed safely: replace it
-        for (size_t i = 0; i < graph_cache.size() && slot < 0; ++i) if (!graph_cache[i].in_use && graph_cache[i].ws == ws) slot = (int)i;
-        if (slot < 0 && graph_cache.size() < GRAPH_CACHE_MAX) { graph_cache.emplace_back(); slot = (int)graph_cache.size() - 1; }
-        if (slot < 0) {
-          for (size_t i = 0; i < graph_cache.size(); ++i)
-            if (!graph_cache[i].in_use && (slot < 0 || graph_cache[i].stamp < graph_cache[slot].stamp)) slot = (int)i;
-        }
-        if (slot >= 0) {
-          GraphSlot& g = graph_cache[slot];
-          if (g.exec) (void)hipGraphExecDestroy(g.exec);
-          if (g.graph) (void)hipGraphDestroy(g.graph);
-          g.ws = ws; g.ws_bytes = ws_bytes; g.B = B; g.S = S; g.max_new = max_new; g.penalty = penalty; g.kv16 = kv_fmt; g.geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
-          g.graph = gg.graph; g.exec = gg.exec; g.stamp = ++graph_stamp; g.in_use = true;
-          gg.graph = nullptr; gg.exec = nullptr;
-          lease.m = this; lease.idx = slot;
-        }
+  if (cacheable) {
+    std::lock_guard<std::mutex> l(graph_mu);
+    for (size_t i = 0; i < graph_cache.size(); ++i) {
+      GraphSlot& g = graph_cache[i];
+      if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv16 == kv_fmt && g.geom == geom) {
+        g.in_use = true; g.stamp = ++graph_stamp; exec = g.step.exec; lease.m = this; lease.idx = (int)i;
+        break;
       }
     }
   }
-  std::vector<int> fin(B);
-  int steps_done = n_first;
-  for (int n = n_first; n < max_new; ++n) {
-    if (exec) {
-      IDX_HIP(hipGraphLaunch(exec, st));
+  StepGraph fresh;
+  int steps_done = 0;
+  if (run_generation(w, inputs_embeds, pad_left_host, B, 1, P, max_new, penalty, logits_out, graph, exec, cacheable ? &fresh : nullptr,
+                     w.finished, B, 16, &steps_done, st)) return 1;
+  if (fresh.exec) {      // keep it: a free cache slot, or the least recently used idle one
+    std::lock_guard<std::mutex> l(graph_mu);
+    int slot = -1;
+    // an idle entry on the same workspace address describes launches that can no longer be replayed safely: replace it
+    for (size_t i = 0; i < graph_cache.size() && slot < 0; ++i) if (!graph_cache[i].in_use && graph_cache[i].ws == ws) slot = (int)i;
+    if (slot < 0 && graph_cache.size() < GRAPH_CACHE_MAX) { graph_cache.emplace_back(); slot = (int)graph_cache.size() - 1; }
+    if (slot < 0) {
+      for (size_t i = 0; i < graph_cache.size(); ++i)
+        if (!graph_cache[i].in_use && (slot < 0 || graph_cache[i].stamp < graph_cache[slot].stamp)) slot = (int)i;
+    }
+    if (slot >= 0) {
+      GraphSlot& g = graph_cache[slot];
+      g.step.drop();
+      g.ws = ws; g.ws_bytes = ws_bytes; g.B = B; g.S = S; g.max_new = max_new; g.penalty = penalty; g.kv16 = kv_fmt; g.geom = geom;
+      g.step = fresh; g.stamp = ++graph_stamp;
     } else {
-      float* lo = logits_out ? logits_out + (size_t)n * B * V : nullptr;
-      tl_prof_pos = S + n;      // keys this step reads (profiler accounting of the decode attention)
-      if (decode_step(w, B, penalty, codes, max_new, lo, st)) return 1;
-      tl_prof_pos = 0;
-    }
-    steps_done = n + 1;
-    if ((n & 15) == 15 || n + 1 == max_new) {     // all rows finished? (HF stops there; later columns would be pad)
-      IDX_HIP(hipMemcpyAsync(fin.data(), w.finished, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      IDX_HIP(hipStreamSynchronize(st));
-      bool all = true;
-      for (int b = 0; b < B; ++b) all = all && fin[b];
-      if (all) break;
+      fresh.drop();
     }
   }
+
   // exact HF length: generation stops at the first step after which every row has emitted the stop token
   std::vector<long long> hc((size_t)B * max_new);
-  IDX_HIP(hipMemcpyAsync(user_codes, codes, hc.size() * sizeof(long long), hipMemcpyDeviceToDevice, st));
-  IDX_HIP(hipMemcpyAsync(hc.data(), codes, hc.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(codes, w.codes, hc.size() * sizeof(long long), hipMemcpyDeviceToDevice, st));
+  IDX_HIP(hipMemcpyAsync(hc.data(), w.codes, hc.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   int n_steps = steps_done;
   int worst = 0;
@@ -684,15 +699,11 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
     c.off = (c.off + 255) & ~(size_t)255;
     sb.bb = carve_beam(ws ? static_cast<char*>(ws) + c.off : nullptr, G, num_beams, V, max_new);
     c.off += sb.bb.bytes;
-    sb.w.slot_beam = sb.beam = c.take<SlotBeam>(G);
+    sb.beam = c.take<SlotBeam>(G);
     const Buffers& w = sb.w;
+    sb.w.beam_tail = true;
     BeamState& b = sb.w.beam;
-    b.logits = w.logits; b.proc = sb.bb.proc; b.seen = w.seen; b.beam_scores = sb.bb.beam_scores; b.next_tok = sb.bb.next_tok;
-    b.beam_idx = sb.bb.beam_idx; b.seq = sb.bb.seq; b.seq_ld = max_new; b.cur_tok = w.cur_tok;
-    b.hyp_score = sb.bb.hyp_score; b.hyp_len = sb.bb.hyp_len; b.hyp_slot = sb.bb.hyp_slot; b.hyp_seq = sb.bb.hyp_seq; b.hyp_n = sb.bb.hyp_n;
-    b.hyp_worst = sb.bb.hyp_worst; b.done = sb.bb.done;
-    b.kcache = w.kcache; b.vcache = w.vcache; b.kv_gran = kv_fmt ? 8 : 16;
-    b.B = G; b.nb = num_beams; b.V = V; b.stop_token = cfg.stop_mel_token; b.L = cfg.layers; b.H = cfg.heads; b.Smax = w.Smax;
+    b = beam_state(w, sb.bb, G, num_beams, max_new);
     b.slots = w.slots; b.group = sb.beam;
     if (use_pl(slots)) { b.x_row = w.xrow; b.x_stats = w.stats; } else b.x_frag = w.xd;
     b.mel_emb = mel_emb; b.mel_pos = mel_pos; b.d = cfg.model_dim;
@@ -741,7 +752,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   }
   std::lock_guard<std::mutex> l(session_mu);
   Session& s = sessions[ws];
-  s.drop_graph();
+  s.step.drop();
   s = Session();
   s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv16 = kv_fmt; s.gemm_mode = get_gemm_mode();
   s.ws_bytes = ws_bytes;
@@ -757,45 +768,27 @@ int GPTModel::session_release(void* ws) {
   std::lock_guard<std::mutex> l(session_mu);
   auto it = sessions.find(ws);
   IDX_CHECK(it != sessions.end(), "no decode session on this workspace");
-  it->second.drop_graph();
+  it->second.step.drop();
   sessions.erase(it);
   return 0;
 }
 
-int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                            const int* caps, hipStream_t st, const idxtts_sampling* per_row) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(inputs_embeds && prompt_lens && slot_ids && caps, "null pointer");
-  IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
-  IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots rows");
-  IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  if (per_row) {      // every row's sampler is checked before any slot is taken (generate()'s rules)
-    for (int b = 0; b < n; ++b) {
-      const idxtts_sampling& r = per_row[b];
-      IDX_CHECK(r.mode == 0 || r.mode == SAMPLE_HF || r.mode == SAMPLE_ACCEL, "sampling mode (0 greedy, 1 HF, 2 accel)");
-      if (r.mode == 0) continue;
-      IDX_CHECK(r.temperature > 0.0f, "sampling needs a positive temperature");
-      IDX_CHECK(r.top_k >= 0 && r.top_p > 0.0f, "sampling parameters");
-      IDX_CHECK(r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
-    }
-  }
+int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                            const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S_out, hipStream_t st) {
+  IDX_CHECK(inputs_embeds && prompt_lens && ids && caps, "null pointer");
+  const int units = s.slots / fan;
+  IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
   IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
-  GenScope gen_scope(this);
   int pmax = 0;
-  std::vector<char> taken(s.slots, 0);
+  std::vector<char> taken(units, 0);
   for (int b = 0; b < n; ++b) {
-    IDX_CHECK(slot_ids[b] >= 0 && slot_ids[b] < s.slots, "slot id out of range");
-    IDX_CHECK(!s.busy[slot_ids[b]] && !taken[slot_ids[b]], "slot is not free");
-    taken[slot_ids[b]] = 1;
+    IDX_CHECK(ids[b] >= 0 && ids[b] < units, "slot or group id out of range");
+    IDX_CHECK(!s.busy[ids[b] * fan] && !taken[ids[b]], "slot or group is not free");
+    taken[ids[b]] = 1;
     IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
     IDX_CHECK(caps[b] >= 1 && caps[b] <= s.max_new, "token cap out of range (1 .. max_new)");
     pmax = std::max(pmax, prompt_lens[b]);
   }
-  const int d = cfg.model_dim, V = cfg.number_mel_codes;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
-  const Buffers& w = sb.w;
   // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
   // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
   // exact kernel; with a bf16 cache in split-bf16 mode gemm_forward takes the split-bf16 kernel from 256 rows on, so the prefill is padded
@@ -804,18 +797,48 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   int rows = n;
   if (kv_fmt && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
   IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
-  std::vector<int> stage((size_t)3 * s.slots + rows, 0);      // ids | klen | cap | plen (one copy)
+  if (params()) return 1;
+  // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen
+  std::vector<int> stage((size_t)3 * s.slots + rows, 0);
   for (int b = 0; b < n; ++b) {
-    stage[b] = slot_ids[b];
+    stage[b] = ids[b] * fan;
+    if (fan > 1) stage[n + b] = ids[b];
     stage[s.slots + b] = prompt_lens[b] + 1;
     stage[2 * s.slots + b] = caps[b];
   }
   for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
-  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), (fan > 1 ? 2 : 1) * n * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots
   IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
-  if (s.sampled) {      // the admitted slots' samplers (greedy when per_row is null); the other rows of the table are rewritten unchanged
+  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
+
+  if (session_prefill_input(sb.w.x, inputs_embeds, ld_rows, sb.plen, rows, S, cfg.model_dim, mel_emb, mel_pos, cfg.start_mel_token, st))
+    return 1;
+  KvScatter sc;
+  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = fan;
+  for (int li = 0; li < cfg.layers; ++li)
+    if (layer_full(li, sb.w, rows, S, nullptr, true, st, &sc)) return 1;
+  *S_out = S;
+  return 0;
+}
+
+int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
+                            const int* caps, hipStream_t st, const idxtts_sampling* per_row) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
+  IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  GenScope gen_scope(this);
+  const int d = cfg.model_dim, V = cfg.number_mel_codes;
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const Buffers& w = sb.w;
+  auto params = [&]() -> int {      // the admitted slots' samplers (greedy when per_row is null); the other rows are rewritten unchanged
+    if (!s.sampled) return 0;
+    if (per_row)
+      for (int b = 0; b < n; ++b)
+        if (check_sampling(per_row[b])) return 1;
     for (int b = 0; b < n; ++b) {
       SlotSampling& e = s.samp[slot_ids[b]];
       e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
@@ -825,14 +848,10 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
       }
     }
     IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
-  }
-  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
-
-  if (session_prefill_input(w.x, inputs_embeds, ld_rows, sb.plen, rows, S, d, mel_emb, mel_pos, cfg.start_mel_token, st)) return 1;
-  KvScatter sc;
-  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots;
-  for (int li = 0; li < cfg.layers; ++li)
-    if (layer_full(li, w, rows, S, nullptr, true, st, &sc)) return 1;
+    return 0;
+  };
+  int S = 0;
+  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st)) return 1;
   if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, n, st)) return 1;
   // first token of each admitted row: the head on all `slots` rows (the GEMV use_pl(slots) selects, as a generate() of `slots` rows),
   // sampled for the admitted slots only; the sampler writes their first decode input
@@ -858,26 +877,19 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
   const Buffers& w = sb.w;
   const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
-  if (s.exec && s.geom != geom) s.drop_graph();
+  if (s.step.exec && s.geom != geom) s.step.drop();
   IDX_CHECK(st != nullptr || !use_graph, "graph replay needs a stream other than the legacy default stream");
   const bool graph_ok = use_graph && !prof_enabled();
   for (int k = 0; k < n_steps; ++k) {
-    if (graph_ok && s.warm && !s.exec) {
+    if (graph_ok && s.warm && !s.step.exec) {
       // every per-step value lives on the device (SlotState, seen, the input rows): admissions between replays keep the graph valid
-      IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = decode_step(w, s.slots, s.penalty, w.codes, s.max_new, nullptr, st);
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(st, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return 1; }
-      IDX_HIP(e);
-      s.graph = g;
-      IDX_HIP(hipGraphInstantiate(&s.exec, s.graph, nullptr, nullptr, 0));
+      if (capture_step(w, s.slots, s.penalty, s.max_new, st, &s.step)) { s.step.drop(); return 1; }
       s.geom = geom;
     }
-    if (graph_ok && s.exec) {
-      IDX_HIP(hipGraphLaunch(s.exec, st));
+    if (graph_ok && s.step.exec) {
+      IDX_HIP(hipGraphLaunch(s.step.exec, st));
     } else {
-      if (decode_step(w, s.slots, s.penalty, w.codes, s.max_new, nullptr, st)) return 1;
+      if (decode_step(w, s.slots, s.penalty, s.max_new, nullptr, 0, st)) return 1;
       s.warm = true;
     }
   }

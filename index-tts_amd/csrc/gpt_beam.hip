@@ -81,49 +81,52 @@ size_t GPTModel::beam_workspace_bytes(int B, int nb, int S, int max_new) const {
   return workspace_bytes(B * nb, S, max_new) + carve_beam(nullptr, B, nb, cfg.number_mel_codes, max_new).bytes;
 }
 
+// the beam stages' buffers of B utterances (session: groups) x nb rows; the caller adds the per-request or per-session fields
+BeamState GPTModel::beam_state(const Buffers& w, const BeamBuffers& bb, int B, int nb, int seq_ld) const {
+  BeamState b;
+  b.logits = w.logits; b.proc = bb.proc; b.seen = w.seen; b.beam_scores = bb.beam_scores; b.next_tok = bb.next_tok;
+  b.beam_idx = bb.beam_idx; b.seq = bb.seq; b.seq_ld = seq_ld; b.cur_tok = w.cur_tok;
+  b.hyp_score = bb.hyp_score; b.hyp_len = bb.hyp_len; b.hyp_slot = bb.hyp_slot; b.hyp_seq = bb.hyp_seq; b.hyp_n = bb.hyp_n;
+  b.hyp_worst = bb.hyp_worst; b.done = bb.done;
+  b.kcache = w.kcache; b.vcache = w.vcache; b.kv_gran = kv_fmt ? 8 : 16;
+  b.B = B; b.nb = nb; b.V = cfg.number_mel_codes; b.stop_token = cfg.stop_mel_token; b.L = cfg.layers; b.H = cfg.heads; b.Smax = w.Smax;
+  return b;
+}
+
+// generate_beam()'s rules for one request's parameters (num_beams is checked by the caller)
+static int check_beam(const idxtts_beam& r) {
+  IDX_CHECK(!r.do_sample || (r.temperature > 0.0f && r.top_k >= 0 && r.top_k <= 1024 && r.top_p > 0.0f),
+            "beam-sample needs a positive temperature, top_k <= 1024 and top_p > 0");
+  // the nucleus is cut inside the top-k survivors (beam_scores_kernel stages at most 2048 of them): without a top-k the whole
+  // vocabulary would survive and the threshold would come from whichever 2048 entries arrived first
+  IDX_CHECK(!r.do_sample || r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
+  IDX_CHECK(r.early_stopping == 0 || r.early_stopping == 1, "early_stopping must be 0 (False) or 1 (True)");
+  return 0;
+}
+
 int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
                             const idxtts_beam* beam, long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph,
                             hipStream_t user_stream) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out && beam, "null pointer");
   GenScope gen_scope(this);
-  hipStream_t st = user_stream;
-  if (user_stream == nullptr) {
-    if (!own_stream) IDX_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
-    IDX_HIP(hipStreamSynchronize(user_stream));
-    st = own_stream;
-  }
   const int nb = beam->num_beams, R = B * nb;
   IDX_CHECK(nb >= 2 && nb <= BEAM_MAX, "2 <= num_beams <= 8");
   IDX_CHECK(B > 0 && R <= 64 && P > 0 && max_new > 0, "shape (B * num_beams <= 64)");
-  IDX_CHECK(!beam->do_sample || (beam->temperature > 0.0f && beam->top_k >= 0 && beam->top_k <= 1024 && beam->top_p > 0.0f),
-            "beam-sample needs a positive temperature, top_k <= 1024 and top_p > 0");
-  // the nucleus is cut inside the top-k survivors (beam_scores_kernel stages at most 2048 of them): without a top-k the whole
-  // vocabulary would survive and the threshold would come from whichever 2048 entries arrived first
-  IDX_CHECK(!beam->do_sample || beam->top_p >= 1.0f || (beam->top_k > 0 && beam->top_k <= 1024), "top-p needs 0 < top_k <= 1024");
-  IDX_CHECK(beam->early_stopping == 0 || beam->early_stopping == 1, "early_stopping must be 0 (False) or 1 (True)");
-  const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1;
+  if (check_beam(*beam)) return 1;
+  const int V = cfg.number_mel_codes, S = P + 1;
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
   IDX_CHECK(ws && ws_bytes >= beam_workspace_bytes(B, nb, S, max_new), "workspace too small");
-  const size_t base_bytes = workspace_bytes(R, S, max_new);
+  hipStream_t st = nullptr;
+  if (call_stream(user_stream, &st)) return 1;
   Buffers w = carve(ws, R, S, max_new);
-  BeamBuffers bb = carve_beam(static_cast<char*>(ws) + base_bytes, B, nb, V, max_new);
+  const BeamBuffers bb = carve_beam(static_cast<char*>(ws) + w.bytes, B, nb, V, max_new);
+  w.beam_tail = true;
+  BeamState& bst = w.beam;
+  bst = beam_state(w, bb, B, nb, max_new);
+  bst.st = w.state; bst.exp_noise = beam->exp_noise; bst.seed = beam->seed; bst.prompt_len = S;
+  bst.do_sample = beam->do_sample ? 1 : 0; bst.top_k = beam->top_k; bst.early_stopping = beam->early_stopping;
+  bst.penalty = penalty; bst.temperature = beam->temperature; bst.top_p = beam->top_p; bst.length_penalty = (double)beam->length_penalty;
 
-  // ---- per-call state ----
-  std::vector<int> kstart(R, 0);
-  for (int r = 0; r < R; ++r) {
-    kstart[r] = pad_left_host ? pad_left_host[r / nb] : 0;
-    IDX_CHECK(kstart[r] >= 0 && kstart[r] < P, "pad_left out of range");
-  }
-  IDX_HIP(hipMemcpyAsync(w.kstart, kstart.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemsetAsync(w.finished, 0, R * sizeof(int), st));
-  IDX_HIP(hipMemsetAsync(w.ksb_cnt, 0, (size_t)cdiv(d, 16) * sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, (size_t)R * cfg.heads * sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(static_cast<char*>(ws) + w.frag_off, 0, w.frag_bytes, st));
-  std::vector<unsigned char> seen((size_t)R * V, 0);
-  for (int r = 0; r < R; ++r) { seen[(size_t)r * V + 1] = 1; seen[(size_t)r * V + cfg.start_mel_token] = 1; }
-  IDX_HIP(hipMemcpyAsync(w.seen, seen.data(), seen.size(), hipMemcpyHostToDevice, st));
-  DecodeState s0{P, 1, 0, 0};
-  IDX_HIP(hipMemcpyAsync(w.state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
   // first beam 0, the others -1e9: only the first beam's tokens count in the first step (transformers_generation_utils.py:3420-3422)
   std::vector<float> bs0(R, -1e9f);
   for (int b = 0; b < B; ++b) bs0[b * nb] = 0.0f;
@@ -132,80 +135,13 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
   IDX_HIP(hipMemcpyAsync(bb.hyp_worst, worst0.data(), B * sizeof(double), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemsetAsync(bb.hyp_n, 0, B * sizeof(int), st));
   IDX_HIP(hipMemsetAsync(bb.done, 0, B * sizeof(int), st));
-  std::vector<int> tok(R, cfg.start_mel_token);
-  IDX_HIP(hipMemcpyAsync(w.cur_tok, tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));   // host staging buffers go out of scope below
-
-  BeamState bst;
-  bst.logits = w.logits; bst.proc = bb.proc; bst.seen = w.seen; bst.beam_scores = bb.beam_scores; bst.next_tok = bb.next_tok;
-  bst.beam_idx = bb.beam_idx; bst.seq = bb.seq; bst.seq_ld = max_new; bst.cur_tok = w.cur_tok;
-  bst.hyp_score = bb.hyp_score; bst.hyp_len = bb.hyp_len; bst.hyp_slot = bb.hyp_slot; bst.hyp_seq = bb.hyp_seq; bst.hyp_n = bb.hyp_n;
-  bst.hyp_worst = bb.hyp_worst; bst.done = bb.done; bst.st = w.state; bst.exp_noise = beam->exp_noise; bst.seed = beam->seed;
-  bst.kcache = w.kcache; bst.vcache = w.vcache; bst.kv_gran = kv_fmt ? 8 : 16;
-  bst.B = B; bst.nb = nb; bst.V = V; bst.stop_token = cfg.stop_mel_token; bst.L = cfg.layers; bst.H = cfg.heads; bst.Smax = w.Smax;
-  bst.prompt_len = S;
-  bst.do_sample = beam->do_sample ? 1 : 0; bst.top_k = beam->top_k; bst.early_stopping = beam->early_stopping;
-  bst.penalty = penalty; bst.temperature = beam->temperature; bst.top_p = beam->top_p; bst.length_penalty = (double)beam->length_penalty;
-  struct Guard {      // the decode step reads the beam state through a thread-local (head_and_sample)
-    Guard(const BeamState* s) { tl_beam = s; }
-    ~Guard() { tl_beam = nullptr; }
-  } guard(&bst);
-
-  // ---- prefill on all R rows (the beams of an utterance start identical): x = [inputs_embeds | mel_emb[start] + mel_pos[0]] ----
-  for (int r = 0; r < R; ++r)
-    IDX_HIP(hipMemcpy2DAsync(w.x + (size_t)r * S * d, (size_t)S * d * sizeof(float), inputs_embeds + (size_t)(r / nb) * P * d,
-                             (size_t)P * d * sizeof(float), (size_t)P * d * sizeof(float), 1, hipMemcpyDeviceToDevice, st));
-  {
-    GatherArgs ga;
-    ga.out = w.x + (size_t)P * d; ga.ld_out = S * d; ga.d = d;
-    ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;
-    ga.table[1] = mel_pos; ga.idx[1] = w.finished;          // zeros -> mel position 0
-    if (gather_sum_rows(ga, R, st)) return 1;
-  }
-  for (int li = 0; li < cfg.layers; ++li)
-    if (layer_full(li, w, R, S, w.kstart, true, st)) return 1;
-  if (head_and_sample(w, R, w.x + (size_t)(S - 1) * d, S * d, false, penalty, nullptr, max_new, nullptr, st)) return 1;
-  if (advance_state(w.state, st)) return 1;
-
-  // ---- decode ----
-  struct GraphGuard {
-    hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-    ~GraphGuard() { if (exec) (void)hipGraphExecDestroy(exec); if (graph) (void)hipGraphDestroy(graph); }
-  } gg;
-  const bool graph_ok = use_graph && !prof_enabled();
-  int n_first = 1;
-  if (graph_ok && max_new > 2) {
-    if (decode_step(w, R, penalty, nullptr, max_new, nullptr, st)) return 1;
-    n_first = 2;
-    IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    const int rc = decode_step(w, R, penalty, nullptr, max_new, nullptr, st);
-    const hipError_t e = hipStreamEndCapture(st, &gg.graph);
-    if (rc) return 1;
-    IDX_HIP(e);
-    IDX_HIP(hipGraphInstantiate(&gg.exec, gg.graph, nullptr, nullptr, 0));
-  }
-  std::vector<int> done(B, 0);
-  int steps_done = std::min(n_first, max_new);
-  for (int n = n_first; n < max_new; ++n) {
-    if (gg.exec) IDX_HIP(hipGraphLaunch(gg.exec, st));
-    else {
-      tl_prof_pos = S + n;      // keys this step reads (profiler accounting of the decode attention)
-      const int rc = decode_step(w, R, penalty, nullptr, max_new, nullptr, st);
-      tl_prof_pos = 0;
-      if (rc) return 1;
-    }
-    steps_done = n + 1;
-    if ((n & 7) == 7 || n + 1 == max_new) {     // beam_scorer.is_done (every utterance finished)?
-      IDX_HIP(hipMemcpyAsync(done.data(), bb.done, B * sizeof(int), hipMemcpyDeviceToHost, st));
-      IDX_HIP(hipStreamSynchronize(st));
-      bool all = true;
-      for (int b = 0; b < B; ++b) all = all && done[b];
-      if (all) break;
-    }
-  }
+  // the beams of an utterance start identical: its prompt on all nb rows; beam_scorer.is_done (every utterance finished) polled
+  int steps_done = 0;
+  if (run_generation(w, inputs_embeds, pad_left_host, B, nb, P, max_new, penalty, nullptr, use_graph && !prof_enabled(), nullptr, nullptr,
+                     bb.done, B, 8, &steps_done, st)) return 1;
 
   // ---- BeamSearchScorer.finalize on the host (transformers_beam_search.py:320-414) ----
-  std::vector<int> seq((size_t)R * max_new), hyp_len((size_t)B * (BEAM_MAX + 1)), hyp_slot(hyp_len.size()), hyp_n(B);
+  std::vector<int> seq((size_t)R * max_new), hyp_len((size_t)B * (BEAM_MAX + 1)), hyp_slot(hyp_len.size()), hyp_n(B), done(B);
   std::vector<int> hyp_seq((size_t)B * (BEAM_MAX + 1) * max_new);
   std::vector<double> hyp_score(hyp_len.size());
   std::vector<float> bscore(R);
@@ -243,62 +179,27 @@ int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, in
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
   IDX_CHECK(s.num_beams > 0, "_admit_beam needs a session initialised with num_beams (idxtts_gpt_session_init_beam)");
-  IDX_CHECK(inputs_embeds && prompt_lens && group_ids && caps && per_request, "null pointer");
-  const int nb = s.num_beams, G = s.slots / nb;
-  IDX_CHECK(n >= 1 && n <= G, "admit 1 .. slots / num_beams requests");
-  // every request is checked before any group is taken (generate_beam's rules)
-  std::vector<char> taken(G, 0);
-  int pmax = 0;
-  for (int b = 0; b < n; ++b) {
-    const idxtts_beam& r = per_request[b];
-    IDX_CHECK(r.num_beams == nb, "num_beams differs from the session's");
-    IDX_CHECK(!r.do_sample || (r.temperature > 0.0f && r.top_k >= 0 && r.top_k <= 1024 && r.top_p > 0.0f),
-              "beam-sample needs a positive temperature, top_k <= 1024 and top_p > 0");
-    IDX_CHECK(!r.do_sample || r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
-    IDX_CHECK(r.early_stopping == 0 || r.early_stopping == 1, "early_stopping must be 0 (False) or 1 (True)");
-    IDX_CHECK(group_ids[b] >= 0 && group_ids[b] < G, "group id out of range");
-    IDX_CHECK(!s.busy[group_ids[b] * nb] && !taken[group_ids[b]], "group is not free");
-    taken[group_ids[b]] = 1;
-    IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
-    IDX_CHECK(caps[b] >= 1 && caps[b] <= s.max_new, "token cap out of range (1 .. max_new)");
-    pmax = std::max(pmax, prompt_lens[b]);
-  }
-  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(per_request, "null pointer");
   GenScope gen_scope(this);
-  const int d = cfg.model_dim;
+  const int nb = s.num_beams, G = s.slots / nb, d = cfg.model_dim;
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
   const Buffers& w = sb.w;
-  // one right-padded prefill row per request (session_admit's rules, the 256-row padding of a bf16 cache in split-bf16 mode included);
-  // its keys and values go to every slot of its group
-  const int S = pmax + 1;
-  int rows = n;
-  if (kv_fmt && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
-  IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
-  std::vector<int> stage((size_t)3 * s.slots + rows, 0);      // first slots | group ids (ids) | klen | cap | plen
-  for (int b = 0; b < n; ++b) {
-    stage[b] = group_ids[b] * nb;
-    stage[n + b] = group_ids[b];
-    stage[s.slots + b] = prompt_lens[b] + 1;
-    stage[2 * s.slots + b] = caps[b];
-  }
-  for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
-  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), 2 * n * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots (nb >= 2)
-  IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
-  for (int b = 0; b < n; ++b) {
-    const idxtts_beam& r = per_request[b];
-    s.beam[group_ids[b]] = SlotBeam{r.do_sample ? 1 : 0, r.temperature, r.top_k, r.top_p, (double)r.length_penalty, r.early_stopping,
-                                    r.seed, r.exp_noise};
-  }
-  IDX_HIP(hipMemcpyAsync(sb.beam, s.beam.data(), G * sizeof(SlotBeam), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
-
-  if (session_prefill_input(w.x, inputs_embeds, ld_rows, sb.plen, rows, S, d, mel_emb, mel_pos, cfg.start_mel_token, st)) return 1;
-  KvScatter sc;
-  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = nb;
-  for (int li = 0; li < cfg.layers; ++li)
-    if (layer_full(li, w, rows, S, nullptr, true, st, &sc)) return 1;
+  auto params = [&]() -> int {      // every request is checked before any group is taken (generate_beam's rules)
+    for (int b = 0; b < n; ++b) {
+      IDX_CHECK(per_request[b].num_beams == nb, "num_beams differs from the session's");
+      if (check_beam(per_request[b])) return 1;
+    }
+    for (int b = 0; b < n; ++b) {
+      const idxtts_beam& r = per_request[b];
+      s.beam[group_ids[b]] = SlotBeam{r.do_sample ? 1 : 0, r.temperature, r.top_k, r.top_p, (double)r.length_penalty, r.early_stopping,
+                                      r.seed, r.exp_noise};
+    }
+    IDX_HIP(hipMemcpyAsync(sb.beam, s.beam.data(), G * sizeof(SlotBeam), hipMemcpyHostToDevice, st));
+    return 0;
+  };
+  // one prefill row per request, its keys and values going to every slot of its group
+  int S = 0;
+  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, group_ids, caps, nb, params, &S, st)) return 1;
   BeamState bs = w.beam;
   bs.penalty = s.penalty; bs.group_ids = sb.ids + n; bs.n_ids = n;
   if (beam_session_reset(bs, cfg.start_mel_token, sb.x_last, w.x, S, sb.plen, sb.cap, n, st)) return 1;
