@@ -811,12 +811,8 @@ int flash_attn_forward(const AttnArgs& a, hipStream_t stream) {
               "relative_key: non-causal self-attention, at most 96 distances");
     IDX_CHECK((reinterpret_cast<uintptr_t>(a.rel_key) & 15) == 0, "rel_key must be 16-byte aligned");
     dyn = REL_LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-      IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, REL_LDS));
-      IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(flash_attn_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, REL_LDS));
-      attr_set = true;
-    }
+    static DynLdsLimit lds_limit;
+    IDX_HIP(lds_limit.set(REL_LDS, flash_attn_bf16x3_kernel, flash_attn_f32_kernel));
   }
   if (a.split_bf16) hipLaunchKernelGGL(flash_attn_bf16x3_kernel, grid, dim3(256), dyn, stream, a);
   else hipLaunchKernelGGL(flash_attn_f32_kernel, grid, dim3(256), dyn, stream, a);

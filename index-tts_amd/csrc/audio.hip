@@ -32,8 +32,8 @@ int MelSpecModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& ar
       m[(size_t)n * nf + k] = (float)(wfull[k] * std::cos(ang));
       m[(size_t)(nbins + n) * nf + k] = (float)(-wfull[k] * std::sin(ang));
     }
-  if (make_linear(arena, m.data(), nullptr, 2 * nbins, nf, nf, &dft)) return 1;
-  return make_linear(arena, mb->data.data(), nullptr, cfg.num_mels, nbins, nbins4, &mel);
+  if (make_linear(arena, m.data(), nullptr, 2 * nbins, nf, {WP16_DMA_SHAPES}, &dft)) return 1;
+  return make_linear(arena, mb->data.data(), nullptr, cfg.num_mels, nbins, {WP16_DMA_SHAPES, W_NK, nbins4}, &mel);
 }
 
 int MelSpecModel::frames(int N) const {

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "bigvgan.h"
+#include "model_util.h"
 
 namespace idxtts {
 
@@ -54,20 +55,6 @@ bool BigVGANModel::accepts(const std::string& name) const {
   if (name.rfind("conv_pre.", 0) == 0 || name.rfind("conv_post.", 0) == 0) return true;
   if (name.rfind("ups.", 0) == 0 || name.rfind("resblocks.", 0) == 0 || name.rfind("activation_post.", 0) == 0) return true;
   return false;
-}
-
-static int need(std::map<std::string, HostTensor>& t, const std::string& key, std::vector<int64_t> shape, HostTensor** out) {
-  auto it = t.find(key);
-  if (it == t.end()) IDX_FAIL("missing tensor '" + key + "'");
-  if (it->second.shape != shape) {
-    std::string s = "tensor '" + key + "' has shape [";
-    for (auto d : it->second.shape) s += std::to_string(d) + ",";
-    s += "] expected [";
-    for (auto d : shape) s += std::to_string(d) + ",";
-    IDX_FAIL(s + "]");
-  }
-  *out = &it->second;
-  return 0;
 }
 
 static int make_conv(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int Cout,
@@ -112,15 +99,6 @@ static int make_conv(std::map<std::string, HostTensor>& t, DeviceArena& arena, c
   return 0;
 }
 
-static int make_vec(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, int n, const float** out) {
-  HostTensor* v = nullptr;
-  if (need(t, key, {n}, &v)) return 1;
-  float* d = nullptr;
-  if (arena.upload(v->data.data(), v->data.size(), &d)) return 1;
-  *out = d;
-  return 0;
-}
-
 int BigVGANModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena) {
   IDX_CHECK(cfg.num_upsamples > 0 && cfg.num_upsamples <= 8 && cfg.num_kernels > 0 && cfg.num_kernels <= 4, "config");
   IDX_CHECK((cfg.upsample_initial_channel >> cfg.num_upsamples) >= 1, "upsample_initial_channel too small");
@@ -141,14 +119,14 @@ int BigVGANModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& ar
         if (make_conv(t, arena, pre + ".convs2." + std::to_string(l), cout, cout, blk.kernel, true, 1, &blk.convs2[l])) return 1;
       }
       for (int a = 0; a < 6; ++a) {
-        if (make_vec(t, arena, pre + ".activations." + std::to_string(a) + ".act.alpha", cout, &blk.alpha[a])) return 1;
-        if (make_vec(t, arena, pre + ".activations." + std::to_string(a) + ".act.beta", cout, &blk.beta[a])) return 1;
+        if (vec_from(t, arena, pre + ".activations." + std::to_string(a) + ".act.alpha", cout, &blk.alpha[a])) return 1;
+        if (vec_from(t, arena, pre + ".activations." + std::to_string(a) + ".act.beta", cout, &blk.beta[a])) return 1;
       }
     }
   }
   const int cl = stage_channels(cfg.num_upsamples);
-  if (make_vec(t, arena, "activation_post.act.alpha", cl, &post_alpha)) return 1;
-  if (make_vec(t, arena, "activation_post.act.beta", cl, &post_beta)) return 1;
+  if (vec_from(t, arena, "activation_post.act.alpha", cl, &post_alpha)) return 1;
+  if (vec_from(t, arena, "activation_post.act.beta", cl, &post_beta)) return 1;
   HostTensor* wpost = nullptr;
   if (need(t, "conv_post.weight", {1, cl, 7}, &wpost)) return 1;
   float* d = nullptr;

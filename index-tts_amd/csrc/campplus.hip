@@ -59,7 +59,7 @@ int conv1d_linear(DeviceArena& arena, const HostTensor& w, int N, int Cin, int k
       for (int kk = 0; kk < k; ++kk) r[((size_t)n * k + kk) * Cin + ci] = w.data[((size_t)n * Cin + ci) * k + kk] * s;
     b[n] = (bias ? bias[n] * s : 0.0f) + (bn ? bn->t[n] : 0.0f);
   }
-  return make_linear(arena, r.data(), (bn || bias) ? b.data() : nullptr, N, k * Cin, k * Cin, out);
+  return make_linear(arena, r.data(), (bn || bias) ? b.data() : nullptr, N, k * Cin, {WP16_DMA_SHAPES}, out);
 }
 
 }  // namespace

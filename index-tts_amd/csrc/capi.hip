@@ -12,6 +12,7 @@
 #include "conv1d.h"
 #include "ctx.h"
 #include "gpt.h"
+#include "model_util.h"
 #include "s2mel.h"
 
 namespace idxtts {
@@ -232,28 +233,9 @@ int idxtts_linear_create(const float* weight, const float* bias, int N, int K, i
   std::unique_ptr<idxtts_linear> l(new idxtts_linear());
   std::vector<float> hw, hb;
   if (fetch(weight, (size_t)N * K, &hw)) return 1;
-  std::vector<float> packed(linear_packed_floats(N, K));
-  if (weight_is_kn) pack_linear_kn(packed.data(), hw.data(), K, N);
-  else pack_linear(packed.data(), hw.data(), N, K);
-  float* d = nullptr;
-  if (l->arena.upload(packed.data(), packed.size(), &d)) return 1;
-  l->w.wp = d; l->w.N = N; l->w.K = K;
-  {
-    std::vector<float> wnk(hw);
-    if (weight_is_kn)
-      for (int k = 0; k < K; ++k)
-        for (int n = 0; n < N; ++n) wnk[(size_t)n * K + k] = hw[(size_t)k * N + n];
-    std::vector<float> p16((linear_bf16x3_packed_bytes(N, K) + 3) / 4);
-    pack_linear_bf16x3(p16.data(), wnk.data(), N, K);
-    float* d16 = nullptr;
-    if (l->arena.upload(p16.data(), p16.size(), &d16)) return 1;
-    l->w.wp16 = d16;
-  }
-  if (bias) {
-    if (fetch(bias, N, &hb)) return 1;
-    if (l->arena.upload(hb.data(), hb.size(), &d)) return 1;
-    l->w.bias = d;
-  }
+  if (bias && fetch(bias, N, &hb)) return 1;
+  // always with the split-bf16 pack: idxtts_linear_fwd(bf16x3 = 1) takes any shape and any M
+  if (make_linear(l->arena, hw.data(), bias ? hb.data() : nullptr, N, K, {WP16_ALWAYS, weight_is_kn ? W_KN : W_NK}, &l->w)) return 1;
   *out = l.release();
   return 0;
   API_END
@@ -793,7 +775,7 @@ int idxtts_get_decode_geometry(void) { return get_decode_geometry(); }
 int idxtts_release_stream(void* stream) {
   API_BEGIN
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return gemm_release_stream_scratch(st) || gemm_tn_release_stream_scratch(st) || s2mel_release_stream(st);
+  return gemm_release_stream_scratch(st) || s2mel_release_stream(st);
   API_END
 }
 

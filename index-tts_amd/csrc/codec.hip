@@ -32,7 +32,7 @@ int RepCodecModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& a
     for (int n = 0; n < D; ++n)
       for (int ci = 0; ci < Hs; ++ci)
         for (int k = 0; k < 7; ++k) r[((size_t)n * 7 + k) * Hs + ci] = w->data[((size_t)n * Hs + ci) * 7 + k];
-    if (make_linear(arena, r.data(), b->data.data(), D, 7 * Hs, 7 * Hs, &embed)) return 1;
+    if (make_linear(arena, r.data(), b->data.data(), D, 7 * Hs, {WP16_DMA_SHAPES}, &embed)) return 1;
   }
   if (ln_from(t, arena, "encoder.0.norm", D, &norm_g, &norm_b) || ln_from(t, arena, "encoder.0.final_layer_norm", D, &fin_g, &fin_b)) return 1;
   layers.resize(cfg.vocos_num_layers);
@@ -42,19 +42,19 @@ int RepCodecModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& a
     HostTensor *dw = nullptr, *g = nullptr, *w2 = nullptr, *b2 = nullptr;
     if (need(t, e + ".dwconv.weight", {D, 1, 7}, &dw) || up(arena, dw->data, &L.dw_w) || vec_from(t, arena, e + ".dwconv.bias", D, &L.dw_b)) return 1;
     if (ln_from(t, arena, e + ".norm", D, &L.ln_g, &L.ln_b)) return 1;
-    if (linear_from(t, arena, e + ".pwconv1", F, D, true, &L.pw1)) return 1;
+    if (linear_from(t, arena, e + ".pwconv1", F, D, true, WP16_DMA_SHAPES, &L.pw1)) return 1;
     if (need(t, e + ".gamma", {D}, &g) || need(t, e + ".pwconv2.weight", {D, F}, &w2) || need(t, e + ".pwconv2.bias", {D}, &b2)) return 1;
     std::vector<float> ws((size_t)D * F), bs(D);      // x = residual + gamma * pwconv2(.)  ->  layer scale folded into pwconv2
     for (int n = 0; n < D; ++n) {
       for (int k = 0; k < F; ++k) ws[(size_t)n * F + k] = g->data[n] * w2->data[(size_t)n * F + k];
       bs[n] = g->data[n] * b2->data[n];
     }
-    if (make_linear(arena, ws.data(), bs.data(), D, F, F, &L.pw2)) return 1;
+    if (make_linear(arena, ws.data(), bs.data(), D, F, {WP16_DMA_SHAPES}, &L.pw2)) return 1;
   }
-  if (linear_from(t, arena, "encoder.1", Hs, D, true, &enc_out)) return 1;
+  if (linear_from(t, arena, "encoder.1", Hs, D, true, WP16_DMA_SHAPES, &enc_out)) return 1;
   const std::string q = "quantizer.quantizers.0";
-  if (linear_from(t, arena, q + ".in_project", cd, Hs, true, &in_proj, {cd, Hs, 1})) return 1;
-  if (linear_from(t, arena, q + ".out_project", Hs, cd, true, &out_proj, {Hs, cd, 1})) return 1;
+  if (linear_from(t, arena, q + ".in_project", cd, Hs, true, WP16_DMA_SHAPES, &in_proj, {cd, Hs, 1})) return 1;
+  if (linear_from(t, arena, q + ".out_project", Hs, cd, true, WP16_DMA_SHAPES, &out_proj, {Hs, cd, 1})) return 1;
   HostTensor* cb = nullptr;
   if (need(t, q + ".codebook.weight", {cs, cd}, &cb) || up(arena, cb->data, &codebook)) return 1;
   std::vector<float> cn(cb->data.size());

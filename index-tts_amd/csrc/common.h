@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 #include <string>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -19,6 +20,23 @@ int fail(const char* file, int line, const std::string& msg);
 #define IDX_HIP(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) \
     IDX_FAIL(std::string(#expr " -> ") + hipGetErrorString(e__)); } while (0)
 #define IDX_LAUNCH_CHECK() IDX_HIP(hipGetLastError())
+
+// Raises the dynamic-LDS limit of the given kernels to `bytes`, once per process: a launcher keeps one `static DynLdsLimit` and calls
+// set() in front of every launch.  Host threads that launch at the same time (the decode lanes and acoustic workers of serving.py)
+// wait for the first one; every call returns the result recorded then.
+struct DynLdsLimit {
+  std::once_flag once;
+  hipError_t err = hipSuccess;
+  template <class... Kernels> hipError_t set(int bytes, Kernels... kernels) {
+    std::call_once(once, [&] {
+      for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (r != hipSuccess) err = r;
+      }
+    });
+    return err;
+  }
+};
 
 // Decode-step activations are kept as MFMA A-fragment images (v_mfma_f32_16x16x4_f32): [rows/16][K/16][64 lanes][4],
 // lane = (k % 16) / 4 * 16 + row % 16, component = k % 4 -- the fragment of a 16-k chunk is one contiguous KiB.

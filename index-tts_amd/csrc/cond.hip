@@ -57,7 +57,7 @@ int CondModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena
     std::vector<float> ws(ow->data.size()), bs(D);
     for (size_t i = 0; i < ws.size(); ++i) ws[i] = ow->data[i] * s;
     for (int i = 0; i < D; ++i) bs[i] = ob->data[i] * s;
-    if (make_linear(arena, ws.data(), nullptr, D, D * F2, D * F2, &embed)) return 1;
+    if (make_linear(arena, ws.data(), nullptr, D, D * F2, {WP16_DMA_SHAPES}, &embed)) return 1;
     if (up(arena, bs, &embed_bias)) return 1;
   }
   {
@@ -84,25 +84,25 @@ int CondModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena
         std::memcpy(&w[(size_t)s * D * D], lw->data.data(), (size_t)D * D * sizeof(float));
         std::memcpy(&b[(size_t)s * D], lb->data.data(), D * sizeof(float));
       }
-      if (make_linear(arena, w.data(), b.data(), 3 * D, D, D, &L.qkv)) return 1;
+      if (make_linear(arena, w.data(), b.data(), 3 * D, D, {WP16_DMA_SHAPES}, &L.qkv)) return 1;
     }
-    if (linear_from(t, arena, e + ".self_attn.linear_out", D, D, true, &L.out)) return 1;
-    if (linear_from(t, arena, e + ".self_attn.linear_pos", D, D, false, &L.pos)) return 1;
+    if (linear_from(t, arena, e + ".self_attn.linear_out", D, D, true, WP16_DMA_SHAPES, &L.out)) return 1;
+    if (linear_from(t, arena, e + ".self_attn.linear_pos", D, D, false, WP16_DMA_SHAPES, &L.pos)) return 1;
     HostTensor *bu = nullptr, *bv = nullptr;
     if (need(t, e + ".self_attn.pos_bias_u", {H, dk}, &bu) || need(t, e + ".self_attn.pos_bias_v", {H, dk}, &bv)) return 1;
     if (up(arena, bu->data, &L.bias_u) || up(arena, bv->data, &L.bias_v)) return 1;
-    if (linear_from(t, arena, e + ".conv_module.pointwise_conv1", 2 * D, D, true, &L.pw1, {2 * D, D, 1})) return 1;
-    if (linear_from(t, arena, e + ".conv_module.pointwise_conv2", D, D, true, &L.pw2, {D, D, 1})) return 1;
+    if (linear_from(t, arena, e + ".conv_module.pointwise_conv1", 2 * D, D, true, WP16_DMA_SHAPES, &L.pw1, {2 * D, D, 1})) return 1;
+    if (linear_from(t, arena, e + ".conv_module.pointwise_conv2", D, D, true, WP16_DMA_SHAPES, &L.pw2, {D, D, 1})) return 1;
     HostTensor* dw = nullptr;
     if (need(t, e + ".conv_module.depthwise_conv.weight", {D, 1, kc}, &dw) || up(arena, dw->data, &L.dw_w)) return 1;
     if (vec_from(t, arena, e + ".conv_module.depthwise_conv.bias", D, &L.dw_b)) return 1;
     if (ln_from(t, arena, e + ".conv_module.norm", D, &L.dwn_g, &L.dwn_b)) return 1;
-    if (linear_from(t, arena, e + ".feed_forward.w_1", LU, D, true, &L.ff1)) return 1;
-    if (linear_from(t, arena, e + ".feed_forward.w_2", D, LU, true, &L.ff2)) return 1;
+    if (linear_from(t, arena, e + ".feed_forward.w_1", LU, D, true, WP16_DMA_SHAPES, &L.ff1)) return 1;
+    if (linear_from(t, arena, e + ".feed_forward.w_2", D, LU, true, WP16_DMA_SHAPES, &L.ff2)) return 1;
   }
   // ---- PerceiverResampler ----
   if (dim != D) {
-    if (linear_from(t, arena, p + ".proj_context", dim, D, true, &proj_ctx)) return 1;
+    if (linear_from(t, arena, p + ".proj_context", dim, D, true, WP16_DMA_SHAPES, &proj_ctx)) return 1;
   } else {
     IDX_CHECK(t.find(p + ".proj_context.weight") == t.end(), "proj_context is nn.Identity when dim_context == dim");
   }
@@ -112,15 +112,15 @@ int CondModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena
   for (int l = 0; l < cfg.perceiver_depth; ++l) {
     PerceiverLayer& P = player[l];
     const std::string a = p + ".layers." + std::to_string(l);
-    if (linear_from(t, arena, a + ".0.to_q", inner, dim, false, &P.to_q) || linear_from(t, arena, a + ".0.to_kv", 2 * inner, dim, false, &P.to_kv) ||
-        linear_from(t, arena, a + ".0.to_out", dim, inner, false, &P.to_out)) return 1;
-    if (linear_from(t, arena, a + ".1.0", 2 * ffi, dim, true, &P.ff1) || linear_from(t, arena, a + ".1.2", dim, ffi, true, &P.ff2)) return 1;
+    if (linear_from(t, arena, a + ".0.to_q", inner, dim, false, WP16_DMA_SHAPES, &P.to_q) || linear_from(t, arena, a + ".0.to_kv", 2 * inner, dim, false, WP16_DMA_SHAPES, &P.to_kv) ||
+        linear_from(t, arena, a + ".0.to_out", dim, inner, false, WP16_DMA_SHAPES, &P.to_out)) return 1;
+    if (linear_from(t, arena, a + ".1.0", 2 * ffi, dim, true, WP16_DMA_SHAPES, &P.ff1) || linear_from(t, arena, a + ".1.2", dim, ffi, true, WP16_DMA_SHAPES, &P.ff2)) return 1;
   }
   if (vec_from(t, arena, p + ".norm.gamma", dim, &pnorm_g)) return 1;
   if (cfg.emotion) {
     IDX_CHECK(cfg.model_dim > 0 && (cfg.model_dim & 3) == 0, "model_dim");
-    if (linear_from(t, arena, "emovec_layer", cfg.model_dim, dim, true, &emovec)) return 1;
-    if (linear_from(t, arena, "emo_layer", cfg.model_dim, cfg.model_dim, true, &emo)) return 1;
+    if (linear_from(t, arena, "emovec_layer", cfg.model_dim, dim, true, WP16_DMA_SHAPES, &emovec)) return 1;
+    if (linear_from(t, arena, "emo_layer", cfg.model_dim, cfg.model_dim, true, WP16_DMA_SHAPES, &emo)) return 1;
   }
   return 0;
 }

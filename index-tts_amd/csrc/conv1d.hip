@@ -258,11 +258,8 @@ static int launch_conv(const ConvWeights& w, const ConvArgs& a, hipStream_t stre
   const int64_t grid = (int64_t)8 * mblocks * p.nt8;
   IDX_CHECK(grid > 0 && grid < (1ll << 31), "grid size");
   auto kern = conv1d_mfma_kernel<TM, TN, WGM, WGN>;
-  static bool attr_set = false;   // one per template instance
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;   // one per template instance
+  IDX_HIP(lds_limit.set(160 * 1024, kern));
   {
     // algorithmic work: 2*Cout*Cin*taps per output sample (a transposed conv has Kt/u = 2 live taps
     // per output, not the 3 the packed form multiplies); bytes = x + y (+ residual / accumulate) + weights once

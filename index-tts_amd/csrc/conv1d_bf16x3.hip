@@ -16,6 +16,7 @@
 
 #include "conv1d.h"
 #include "conv_epilogue.h"
+#include "gemm_common.h"
 #include <string>
 
 #include "prof.h"
@@ -24,20 +25,6 @@ namespace idxtts {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-static inline uint16_t f2bf_c(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float bf2f_c(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
 
 // fp32 pack [.. sub-tile ..][g2][h2][i32][4] (ci = 8g + 4h + e)  ->  [.. sub-tile ..][hl][g2][i32][8] bf16 (k-slot 4h + e)
 void pack_conv_bf16x3(void* dst, const float* packed_f32, size_t n_subtiles) {
@@ -51,10 +38,10 @@ void pack_conv_bf16x3(void* dst, const float* packed_f32, size_t n_subtiles) {
         for (int i = 0; i < 32; ++i)
           for (int e = 0; e < 4; ++e) {
             const float x = src[((g * 2 + h) * 32 + i) * 4 + e];
-            const uint16_t xh = f2bf_c(x);
+            const uint16_t xh = f2bf(x);
             const int d = (g * 32 + i) * 8 + 4 * h + e;
             hi[d] = xh;
-            lo[d] = f2bf_c(x - bf2f_c(xh));
+            lo[d] = f2bf(x - bf2f(xh));
           }
   }
 }
@@ -321,11 +308,8 @@ static int launch_conv16(const ConvWeights& w, const ConvArgs& a, hipStream_t st
   const int64_t grid = (int64_t)8 * mblocks * p.nt8;
   IDX_CHECK(grid > 0 && grid < (1ll << 31), "grid size");
   auto kern = conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set(160 * 1024, kern));
   const double cout = (double)(w.M / w.ups), tout = (double)a.T * w.ups * a.B;
   const double taps = w.ups > 1 ? 2.0 : (double)w.K;
   const double flops = 2.0 * cout * w.Cin * taps * tout;

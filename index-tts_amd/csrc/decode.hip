@@ -440,14 +440,8 @@ int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
   constexpr int nt = 512;      // 512 threads measured 4 % faster than 256 (profiles/README.md)
   const size_t lds = (size_t)(256 + (nt / (a.kv16 ? 8 : 16)) * 64 + a.Smax) * sizeof(float);
   IDX_CHECK(lds <= 128 * 1024, "Smax too large for the LDS score buffer");
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_kernel<512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn16_kernel<512, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn_kernel<512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_attn16_kernel<512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set(128 * 1024, decode_attn_kernel<512, false>, decode_attn16_kernel<512, false>, decode_attn_kernel<512, true>, decode_attn16_kernel<512, true>));
   IDX_CHECK(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.cnt)), "key split: 1..16 pieces, partial buffer and counters");
   // algorithmic bytes: K and V of every cached position, all heads: B * S * 2 * d * (4 | 2) (S as the host knows it: pos_hint)
   static const int cat = prof_register("decode_attn_kernel"), cat16 = prof_register("decode_attn16_kernel");

@@ -18,8 +18,6 @@ static inline size_t linear_packed_floats(int N, int K) { return (size_t)cdiv(N,
 
 // w: [N][K] row-major (torch nn.Linear layout).  Same sub-tile format as the conv weights with one tap.
 void pack_linear(float* dst, const float* w, int N, int K);
-// HF Conv1D layout [K][N] (y = x @ W + b).
-void pack_linear_kn(float* dst, const float* w_kn, int K, int N);
 
 struct GemmArgs {
   const float* x = nullptr; int ldx = 0;      // [M][K], row stride ldx floats
@@ -64,7 +62,7 @@ int gemm_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream);
 // true when gemm_forward would run this shape on the LDS-DMA split-bf16 kernel (the only consumer / producer of planes)
 bool gemm_uses_planes(const LinearWeights& w, const GemmArgs& a);
 
-int gemm_release_stream_scratch(hipStream_t stream);      // idxtts_release_stream: the split-plane scratch kept per stream
-int gemm_tn_release_stream_scratch(hipStream_t stream);   // ... and the exact kernel's K-group combine scratch
+// idxtts_release_stream: the scratch kept per stream (the split-bf16 activation planes, the exact kernel's K-group combine)
+int gemm_release_stream_scratch(hipStream_t stream);
 
 }  // namespace idxtts

@@ -18,8 +18,6 @@
 // an XCD share one weight slice in their L2 while streaming different activation rows.
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <mutex>
 
 #include "gemm_common.h"
 #include "prof.h"
@@ -41,41 +39,47 @@ void pack_linear(float* dst, const float* w, int N, int K) {
     }
 }
 
-void pack_linear_kn(float* dst, const float* w_kn, int K, int N) {
-  const int NT = cdiv(N, 32), KC = cdiv(K, 16);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c) {
-      float* sub = dst + ((size_t)nt * KC + c) * 512;
-      for (int g = 0; g < 2; ++g)
-        for (int h = 0; h < 2; ++h)
-          for (int j = 0; j < 32; ++j)
-            for (int e = 0; e < 4; ++e) {
-              const int n = nt * 32 + j, k = c * 16 + 8 * g + 4 * h + e;
-              sub[((g * 2 + h) * 32 + j) * 4 + e] = (n < N && k < K) ? w_kn[(size_t)k * N + n] : 0.0f;
-            }
-    }
-}
-
 constexpr int XBLK = 132;   // floats per padded [32 rows][4] sub-block (528 B)
 
-// per-(device, stream) scratch of the few-tile launches' K-group combine: [4 KiB arrival counters][partial tiles]
-struct SplitKScratch { void* ptr = nullptr; size_t bytes = 0; };
-static std::map<std::pair<int, hipStream_t>, SplitKScratch> g_sk;
-static std::mutex g_sk_mu;
-int gemm_tn_release_stream_scratch(hipStream_t stream) {
+int StreamScratch::acquire(hipStream_t stream, size_t bytes, void** out, bool* grew) {
   int dev_id = 0;
   IDX_HIP(hipGetDevice(&dev_id));
-  SplitKScratch sc;
+  Block* b = nullptr;
   {
-    std::lock_guard<std::mutex> lock(g_sk_mu);
-    auto it = g_sk.find(std::make_pair(dev_id, stream));
-    if (it == g_sk.end()) return 0;
-    sc = it->second;
-    g_sk.erase(it);
+    std::lock_guard<std::mutex> lock(mu_);
+    b = &blocks_[std::make_pair(dev_id, stream)];
   }
-  if (sc.ptr) IDX_HIP(hipFreeAsync(sc.ptr, stream));
+  const bool grow = b->bytes < bytes;
+  if (grew) *grew = grow;
+  if (grow) {      // the old block is released behind the launches that still read it
+    if (b->ptr) IDX_HIP(hipFreeAsync(b->ptr, stream));
+    b->ptr = nullptr; b->bytes = 0;
+    const size_t nb = bytes + (headroom_div_ ? bytes / headroom_div_ : 0);
+    IDX_HIP(hipMallocAsync(&b->ptr, nb, stream));
+    b->bytes = nb;
+  }
+  *out = b->ptr;
   return 0;
 }
+
+int StreamScratch::release(hipStream_t stream) {
+  int dev_id = 0;
+  IDX_HIP(hipGetDevice(&dev_id));
+  Block b;
+  {
+    std::lock_guard<std::mutex> lock(mu_);
+    auto it = blocks_.find(std::make_pair(dev_id, stream));
+    if (it == blocks_.end()) return 0;
+    b = it->second;
+    blocks_.erase(it);
+  }
+  if (b.ptr) IDX_HIP(hipFreeAsync(b.ptr, stream));
+  return 0;
+}
+
+// scratch of the few-tile launches' K-group combine: [4 KiB arrival counters][partial tiles]
+static StreamScratch g_sk_scratch;
+int gemm_release_stream_scratch(hipStream_t stream) { return g_plane_scratch.release(stream) || g_sk_scratch.release(stream); }
 
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -258,9 +262,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
   gemm_epilogue(p, tot, bm, bn, wm, wn, h, j);
 }
 
-int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream) {
-  IDX_CHECK(w.wp && a.x && a.y, "null pointer");
-  if (a.M == 0) return 0;
+int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* out, double* flops, double* bytes) {
   IDX_CHECK(a.M > 0 && w.N > 0 && w.K > 0, "bad shape");
   IDX_CHECK((w.K & 3) == 0 && (a.ldx & 3) == 0, "K and ldx must be multiples of 4 (16-byte row segments)");
   IDX_CHECK((reinterpret_cast<uintptr_t>(a.x) & 15) == 0, "x must be 16-byte aligned");
@@ -271,68 +273,65 @@ int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t strea
   }
   if (a.row_len) IDX_CHECK(a.seq_len > 0, "row_len needs seq_len");
   GemmKP p;
-  IDX_CHECK(a.x && a.y && !a.y_planes && !a.rope, "the fp32 GEMM takes and produces fp32 rows only (no fused rotary)");
   p.x = a.x; p.wp = w.wp; p.bias = w.bias; p.res = a.res; p.y = a.y; p.y_hi = p.y_lo = nullptr; p.rope = nullptr; p.rope_T = 1; p.rope_cols = 0;
   p.M = a.M; p.N = w.N; p.K = w.K; p.ldx = a.ldx; p.ldy = a.ldy; p.ldr = a.ldr;
   p.kc16 = cdiv(w.K, 16);
   p.mtiles = cdiv(a.M, 128);
   p.mt8 = cdiv(p.mtiles, 8);
+  p.nblocks = cdiv(w.N, 128);
+  p.n_fast = ((double)w.N * w.K * 4.0 <= 8.0 * 1024 * 1024) && a.M > w.N ? 1 : 0;
   p.act = a.act; p.out_scale = a.out_scale;
   p.taps = a.taps; p.kc = w.K / std::max(1, a.taps); p.seq_len = a.seq_len > 0 ? a.seq_len : 1; p.dil = a.dil; p.pad_left = a.pad_left;
   p.pad_mode = a.pad_mode; p.row_len = a.row_len;
+  p.ksplit = 1; p.ksteps_per_split = 0;
+  p.kg = 0; p.direct_map = 0; p.sk_slab = nullptr; p.sk_cnt = nullptr; p.sk_slab_bytes = 0;
+  IDX_CHECK((int64_t)8 * p.nblocks * p.mt8 < (1ll << 31), "grid size");
+  *out = p;
+  *flops = 2.0 * a.M * (double)w.N * w.K;
+  *bytes = 4.0 * ((double)a.M * w.K + (double)w.N * w.K + (double)a.M * w.N * (a.res ? 2.0 : 1.0));
+  return 0;
+}
+
+int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream) {
+  IDX_CHECK(w.wp && a.x && a.y, "null pointer");
+  if (a.M == 0) return 0;
+  IDX_CHECK(!a.y_planes && !a.rope, "the fp32 GEMM takes and produces fp32 rows only (no fused rotary)");
+  GemmKP p;
+  double flops, bytes;
+  if (gemm_prepare(w, a, &p, &flops, &bytes)) return 1;
   p.ksplit = std::max(1, a.ksplit);
   p.ksteps_per_split = cdiv(cdiv(p.kc16, 2), p.ksplit);
   if (p.ksplit > 1) {
     IDX_CHECK(a.taps <= 1 && a.act == ACT_NONE && !a.res && !a.row_len, "split-K launches produce raw partial slabs");
     IDX_CHECK((p.ksplit - 1) * p.ksteps_per_split < cdiv(p.kc16, 2), "ksplit leaves an empty K range");
   }
-  const int nblocks = cdiv(w.N, 128);
-  p.nblocks = nblocks;
-  p.n_fast = ((double)w.N * w.K * 4.0 <= 8.0 * 1024 * 1024) && ((double)a.M * w.K > (double)w.N * w.K) ? 1 : 0;
   // K groups (GemmKP::kg): a function of K alone, so a row's result never depends on how many rows are computed beside it
   const int ksteps_all = cdiv(p.kc16, 2);
   p.kg = std::max(5, cdiv(ksteps_all, 8));
   const int ngroups = cdiv(ksteps_all, p.kg);
-  p.direct_map = 0; p.sk_slab = nullptr; p.sk_cnt = nullptr; p.sk_slab_bytes = 0;
-  const int tiles = nblocks * p.mtiles;
+  const int tiles = p.nblocks * p.mtiles;
   // Few output tiles (a B = 1 prefill, the prompt encoders' projections): one workgroup per tile would leave most CUs idle behind
   // a K loop of dependent global-load -> LDS -> MFMA steps.  One K group per workgroup instead (up to 8 x the workgroups), combined in
   // the kernel by the last arriver.
   if (p.ksplit == 1 && tiles <= 96 && ngroups >= 2) {
     const size_t slab_bytes = (size_t)ngroups * tiles * 65536, cnt_bytes = 4096;
     static_assert(96 * 4 <= 4096, "arrival counters");
-    int dev_id = 0;
-    IDX_HIP(hipGetDevice(&dev_id));
-    SplitKScratch* scp = nullptr;
-    {
-      std::lock_guard<std::mutex> lock(g_sk_mu);
-      scp = &g_sk[std::make_pair(dev_id, stream)];
-    }
-    if (scp->bytes < cnt_bytes + slab_bytes) {      // stream-ordered (no device-wide synchronisation), grow-only
-      if (scp->ptr) IDX_HIP(hipFreeAsync(scp->ptr, stream));
-      scp->ptr = nullptr; scp->bytes = 0;
-      IDX_HIP(hipMallocAsync(&scp->ptr, cnt_bytes + slab_bytes, stream));
-      IDX_HIP(hipMemsetAsync(scp->ptr, 0, cnt_bytes, stream));      // counters start at 0 and every launch leaves them at 0
-      scp->bytes = cnt_bytes + slab_bytes;
-    }
-    p.sk_cnt = static_cast<unsigned*>(scp->ptr);
-    p.sk_slab = reinterpret_cast<float*>(static_cast<char*>(scp->ptr) + cnt_bytes);
+    void* sc = nullptr;
+    bool grew = false;
+    if (g_sk_scratch.acquire(stream, cnt_bytes + slab_bytes, &sc, &grew)) return 1;
+    if (grew) IDX_HIP(hipMemsetAsync(sc, 0, cnt_bytes, stream));      // counters start at 0 and every launch leaves them at 0
+    p.sk_cnt = static_cast<unsigned*>(sc);
+    p.sk_slab = reinterpret_cast<float*>(static_cast<char*>(sc) + cnt_bytes);
     p.sk_slab_bytes = (int)slab_bytes;
     p.ksplit = ngroups; p.ksteps_per_split = p.kg;
   }
   if (tiles <= 96) p.direct_map = 1;
-  const int64_t grid = p.direct_map ? (int64_t)tiles : (int64_t)8 * nblocks * p.mt8;
-  IDX_CHECK(grid < (1ll << 31), "grid size");
-  const double flops = 2.0 * a.M * (double)w.N * w.K;
-  const double bytes = 4.0 * ((double)a.M * w.K + (double)w.N * w.K + (double)a.M * w.N * (a.res ? 2.0 : 1.0));
+  const int64_t grid = p.direct_map ? (int64_t)tiles : (int64_t)8 * p.nblocks * p.mt8;
   static const int cat = prof_register("gemm_tn_kernel");
   ProfScope prof(cat, stream, flops, bytes);
   constexpr size_t lds = (size_t)(2 * 4 * 2 * 4 * XBLK + 2 * 4 * 2 * 512) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set((int)lds, gemm_tn_kernel));
   hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)grid, (unsigned)p.ksplit), dim3(256), lds, stream, p);
   IDX_LAUNCH_CHECK();
   return 0;

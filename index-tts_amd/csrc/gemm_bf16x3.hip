@@ -35,20 +35,6 @@ constexpr int BROW = 40;                       // bf16 elements per LDS row (32 
 constexpr int TILE_HALF = 128 * BROW;          // elements of one [128][40] image (hi or lo)
 constexpr int WTILE_BYTES = 2 * TILE_HALF * 2; // 20480 bytes per packed (n-block, k-step) weight tile
 
-static inline uint16_t f2bf(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 // the pack holds two images: the padded LDS-image tiles of the register-staged kernels below, then the
 // [hl][K/16][Npad][16] planes of the LDS-DMA kernel (gemm_bf16x3_v2.hip)
 size_t linear_planes_bytes(int N, int K);
@@ -351,11 +337,8 @@ static int launch_big(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipSt
   const int64_t grid = (int64_t)8 * p.nblocks * p.mt8;
   IDX_CHECK(grid < (1ll << 31), "grid size");
   constexpr size_t lds = (size_t)(2 * 2 * 256 * BROW + 2 * NB128 * 2 * TILE_HALF) * sizeof(__bf16);
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_big_kernel<TN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set((int)lds, gemm_bf16x3_big_kernel<TN>));
   static const int cat = prof_register(TN == 2 ? "gemm_bf16x3_big_kernel<2>" : "gemm_bf16x3_big_kernel<4>");
   ProfScope prof(cat, stream, flops, bytes);
   hipLaunchKernelGGL(gemm_bf16x3_big_kernel<TN>, dim3((unsigned)grid), dim3(512), lds, stream, p);
@@ -366,34 +349,12 @@ static int launch_big(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipSt
 int gemm_bf16x3_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream) {
   IDX_CHECK(w.wp16 && (a.x || a.x_planes) && (a.y || a.y_planes), "null pointer (split-bf16 weights not packed?)");
   if (a.M == 0) return 0;
-  IDX_CHECK(a.M > 0 && w.N > 0 && w.K > 0, "bad shape");
-  IDX_CHECK((w.K & 3) == 0 && (a.ldx & 3) == 0, "K and ldx must be multiples of 4");
-  IDX_CHECK((reinterpret_cast<uintptr_t>(a.x) & 15) == 0, "x must be 16-byte aligned");
   if (a.x_planes || a.y_planes || !a.x || !a.y || a.rope) IDX_CHECK(gemm_bf16x3_uses_v2(w, a), "operand planes are only understood by the LDS-DMA kernel (shape not eligible)");
-  if (a.act == ACT_SWIGLU || a.act == ACT_GATE) IDX_CHECK((w.N & 63) == 0, "paired activations need N % 64 == 0");
-  if (a.taps > 1) {
-    IDX_CHECK(a.seq_len > 0 && a.M % a.seq_len == 0 && w.K % a.taps == 0 && ((w.K / a.taps) & 31) == 0, "conv mode shape");
-    if (a.pad_mode == 1) IDX_CHECK(a.seq_len > (a.taps - 1) * a.dil, "reflect pad needs seq_len > halo");
-  }
-  if (a.row_len) IDX_CHECK(a.seq_len > 0, "row_len needs seq_len");
-  GemmKP p;
-  p.x = a.x; p.wp = reinterpret_cast<const float*>(w.wp16); p.bias = w.bias; p.res = a.res; p.y = a.y; p.y_hi = p.y_lo = nullptr; p.rope = nullptr; p.rope_T = 1; p.rope_cols = 0;
-  p.M = a.M; p.N = w.N; p.K = w.K; p.ldx = a.ldx; p.ldy = a.ldy; p.ldr = a.ldr;
-  p.kc16 = cdiv(w.K, 16);
-  p.mtiles = cdiv(a.M, 128);
-  p.mt8 = cdiv(p.mtiles, 8);
-  p.act = a.act; p.out_scale = a.out_scale;
-  p.taps = a.taps; p.kc = w.K / std::max(1, a.taps); p.seq_len = a.seq_len > 0 ? a.seq_len : 1; p.dil = a.dil; p.pad_left = a.pad_left;
-  p.pad_mode = a.pad_mode; p.row_len = a.row_len;
-  p.ksplit = 1; p.ksteps_per_split = 0;
   IDX_CHECK(a.ksplit <= 1, "split-K is a feature of the exact-fp32 kernel");
-  const int nblocks = cdiv(w.N, 128);
-  p.nblocks = nblocks;
-  p.n_fast = ((double)w.N * w.K * 4.0 <= 8.0 * 1024 * 1024) && (a.M > w.N) ? 1 : 0;
-  const int64_t grid = (int64_t)8 * nblocks * p.mt8;
-  IDX_CHECK(grid < (1ll << 31), "grid size");
-  const double flops = 2.0 * a.M * (double)w.N * w.K;
-  const double bytes = 4.0 * ((double)a.M * w.K + (double)w.N * w.K + (double)a.M * w.N * (a.res ? 2.0 : 1.0));
+  GemmKP p;
+  double flops, bytes;
+  if (gemm_prepare(w, a, &p, &flops, &bytes)) return 1;
+  p.wp = reinterpret_cast<const float*>(w.wp16);
   if (gemm_bf16x3_uses_v2(w, a))
     return gemm_bf16x3_v2_forward(p, static_cast<const char*>(w.wp16) + tiles_bytes(w.N, w.K), w, a, stream, flops, bytes);
   if (a.M >= 4096) {      // shapes the LDS-DMA kernel does not take (N < 192, K % 16 != 0): the register-staged 256-row tiles
@@ -402,14 +363,11 @@ int gemm_bf16x3_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t s
     return launch_big<2>(p, w, a, stream, flops, bytes);
   }
   constexpr size_t lds = (size_t)(2 * 2 * 2 * TILE_HALF) * sizeof(__bf16);
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set((int)lds, gemm_bf16x3_kernel));
   static const int cat = prof_register("gemm_bf16x3_kernel");
   ProfScope prof(cat, stream, flops, bytes);
-  hipLaunchKernelGGL(gemm_bf16x3_kernel, dim3((unsigned)grid), dim3(256), lds, stream, p);
+  hipLaunchKernelGGL(gemm_bf16x3_kernel, dim3((unsigned)(8 * p.nblocks * p.mt8)), dim3(256), lds, stream, p);
   IDX_LAUNCH_CHECK();
   return 0;
 }

@@ -19,9 +19,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <utility>
 
 #include "gemm_common.h"
 #include "prof.h"
@@ -30,20 +27,6 @@ namespace idxtts {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-static inline uint16_t f2bf_v2(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float bf2f_v2(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
 
 // ---- weight planes: [hl][K/16][Npad][16] bf16, Npad = N rounded up to 256 (zero rows), K rounded up to 16 ----
 size_t linear_planes_bytes(int N, int K) { return (size_t)2 * cdiv(K, 16) * (cdiv(N, 256) * 256) * 16 * sizeof(uint16_t); }
@@ -56,10 +39,10 @@ void pack_linear_planes(void* dst, const float* w, int N, int K) {
   for (int n = 0; n < N; ++n)
     for (int k = 0; k < K; ++k) {
       const float x = w[(size_t)n * K + k];
-      const uint16_t hi = f2bf_v2(x);
+      const uint16_t hi = f2bf(x);
       const size_t idx = ((size_t)(k >> 4) * NP + n) * 16 + (k & 15);
       o[idx] = hi;
-      lo[idx] = f2bf_v2(x - bf2f_v2(hi));
+      lo[idx] = f2bf(x - bf2f(hi));
     }
 }
 
@@ -347,29 +330,8 @@ __global__ __launch_bounds__(CFG ? 256 : 512, CFG ? 3 : 2) void gemm_bf16x3_v2_k
   gemm_v2_tile<TAPS, EPI, CFG>(q, bm, bn, threadIdx.x);
 }
 
-// ---- per-stream scratch for the activation planes (grow-only) ----
-struct PlaneScratch { void* ptr = nullptr; size_t bytes = 0; };
-// keyed by (device, stream): the null stream exists on every device.  Guarded by g_scratch_mu (stages of different batches run on
-// different streams from different host threads).
-static std::map<std::pair<int, hipStream_t>, PlaneScratch> g_scratch;
-static std::mutex g_scratch_mu;
-
-
-// idxtts_release_stream: drop what the library keeps for a stream that is going away
-int gemm_release_stream_scratch(hipStream_t stream) {
-  int dev_id = 0;
-  IDX_HIP(hipGetDevice(&dev_id));
-  PlaneScratch sc;
-  {
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    auto it = g_scratch.find(std::make_pair(dev_id, stream));
-    if (it == g_scratch.end()) return 0;
-    sc = it->second;
-    g_scratch.erase(it);
-  }
-  if (sc.ptr) IDX_HIP(hipFreeAsync(sc.ptr, stream));
-  return 0;
-}
+// per-stream scratch for the activation planes: room for a quarter more rows than the launch that grows it
+StreamScratch g_plane_scratch(8);
 
 // p: fully prepared by gemm_bf16x3_forward (shapes, epilogue, conv parameters); planes: w.wp16 + offset
 int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w, const GemmArgs& a, hipStream_t stream, double flops,
@@ -377,24 +339,9 @@ int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w
   IDX_CHECK(w.K % 16 == 0 && (a.taps <= 1 || (w.K / a.taps) % 16 == 0), "v2 needs K % 16 == 0");
   const int xk = a.taps > 1 ? w.K / a.taps : w.K;       // channels of the activation rows
   const size_t plane = (size_t)(xk / 16) * a.M * 16 * sizeof(__bf16);
-  int dev_id = 0;
-  IDX_HIP(hipGetDevice(&dev_id));
-  PlaneScratch* scp = nullptr;
-  {      // the lock covers the map only (nodes are stable and a stream has one user): growing one stream's scratch stalls nobody else
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    scp = &g_scratch[std::make_pair(dev_id, stream)];
-  }
-  PlaneScratch& sc = *scp;
-  if (!a.x_planes && sc.bytes < 2 * plane) {
-    // stream-ordered: the old block is released behind the launches that still read it, without the device-wide synchronisation of
-    // hipFree (which would stall every decode lane and acoustic worker of a serving loop)
-    if (sc.ptr) IDX_HIP(hipFreeAsync(sc.ptr, stream));
-    sc.ptr = nullptr; sc.bytes = 0;
-    const size_t nb = 2 * plane + (plane >> 2);
-    IDX_HIP(hipMallocAsync(&sc.ptr, nb, stream));
-    sc.bytes = nb;
-  }
-  const __bf16* hi = a.x_planes ? static_cast<const __bf16*>(a.x_planes) : static_cast<const __bf16*>(sc.ptr);
+  void* scratch = nullptr;
+  if (!a.x_planes && g_plane_scratch.acquire(stream, 2 * plane, &scratch)) return 1;
+  const __bf16* hi = static_cast<const __bf16*>(a.x_planes ? a.x_planes : scratch);
   const __bf16* lo = hi + plane / sizeof(__bf16);
   if (!a.x_planes) {
     static const int cat_split = prof_register("split_planes_kernel");
@@ -458,21 +405,12 @@ int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w
   IDX_CHECK(!a.row_len || a.seq_len >= 16, "row masks need seq_len >= 16");
   const int epi = a.rope ? EPI_ROPE : paired ? EPI_PAIRED : a.act != ACT_NONE ? EPI_ACT : EPI_PLAIN;
   typedef void (*KernelFn)(const GemmV2P);
-#define V2_ROW(T, C) {gemm_bf16x3_v2_kernel<T, EPI_PLAIN, C>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, C>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, C>, gemm_bf16x3_v2_kernel<T, EPI_ACT, C>}
-  static const KernelFn kernels[2][2][4] = {{V2_ROW(false, 0), V2_ROW(true, 0)}, {V2_ROW(false, 1), V2_ROW(true, 1)}};
+#define V2_ROW(T, C) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, C>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, C>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, C>, gemm_bf16x3_v2_kernel<T, EPI_ACT, C>
+  static const KernelFn kernels[2][2][4] = {{{V2_ROW(false, 0)}, {V2_ROW(true, 0)}}, {{V2_ROW(false, 1)}, {V2_ROW(true, 1)}}};
+  static DynLdsLimit lds_limit[2];
+  IDX_HIP(lds_limit[0].set(4 * (4 * 256 * 32), V2_ROW(false, 0), V2_ROW(true, 0)));
+  IDX_HIP(lds_limit[1].set(3 * (4 * 128 * 32), V2_ROW(false, 1), V2_ROW(true, 1)));
 #undef V2_ROW
-  static std::once_flag attr_once;
-  static hipError_t attr_err = hipSuccess;
-  std::call_once(attr_once, [&] {
-    for (int c = 0; c < 2; ++c)
-      for (int t = 0; t < 2; ++t)
-        for (int e = 0; e < 4; ++e) {
-          const hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[c][t][e]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   c ? 3 * (4 * 128 * 32) : 4 * (4 * 256 * 32));
-          if (r != hipSuccess) attr_err = r;
-        }
-  });
-  IDX_HIP(attr_err);
   hipLaunchKernelGGL(kernels[cfg][a.taps > 1 ? 1 : 0][epi], dim3((unsigned)grid), dim3(cfg ? 256 : 512), lds, stream, q);
   IDX_LAUNCH_CHECK();
   return 0;

@@ -1,10 +1,48 @@
 // Shared by the fp32 and the split-bf16 GEMM kernels: kernel parameter block, activation functions and the
 // accumulator epilogue (bias, activation / paired gate, residual, row mask, store) for a 2x2-wave, 2x2-tile
-// 128x128 workgroup tile in the 32x32 MFMA C/D layout.
+// 128x128 workgroup tile in the 32x32 MFMA C/D layout.  And by their host code: the launch set-up (gemm_prepare), host bf16
+// rounding for the weight packs, the per-stream scratch.
 #pragma once
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "gemm.h"
 
 namespace idxtts {
+
+// host bf16: round to nearest even, NaN stays NaN (the split-bf16 weight packs: hi = f2bf(x), lo = f2bf(x - bf2f(hi)))
+inline uint16_t f2bf(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+inline float bf2f(uint16_t b) {
+  uint32_t u = (uint32_t)b << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+// Grow-only device scratch per (device, stream): the null stream exists on every device, and a stream has one user at a time.  Blocks
+// are allocated and freed in stream order, so growing one stream's block stalls nobody else (hipFree would synchronise the device
+// under every decode lane and acoustic worker of a serving loop).  The lock covers the map only; its nodes are stable.
+class StreamScratch {
+ public:
+  explicit StreamScratch(int headroom_div = 0) : headroom_div_(headroom_div) {}      // a new block is bytes + bytes / headroom_div
+  // *out: the stream's block, at least `bytes`; *grew (optional): it is a new block, its contents undefined
+  int acquire(hipStream_t stream, size_t bytes, void** out, bool* grew = nullptr);
+  int release(hipStream_t stream);      // the stream is going away
+ private:
+  struct Block { void* ptr = nullptr; size_t bytes = 0; };
+  std::map<std::pair<int, hipStream_t>, Block> blocks_;
+  std::mutex mu_;
+  const int headroom_div_;
+};
+extern StreamScratch g_plane_scratch;      // the split-bf16 activation planes (gemm_bf16x3_v2.hip)
 
 struct GemmKP {
   const float* x; const float* wp; const float* bias; const float* res; float* y;
@@ -29,6 +67,10 @@ struct GemmKP {
   float* sk_slab; unsigned* sk_cnt; int sk_slab_bytes;
 };
 
+
+// What every GEMM launch shares: the argument checks, the parameter block (fp32 weights, 128 x 128 tiles, XCD walk, no K split) and
+// the algorithmic flops / bytes of the launch.  gemm_tn_forward and gemm_bf16x3_forward add what is their own.
+int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* p, double* flops, double* bytes);
 
 // Hardware-rate forms for the split-bf16 GEMM's fused gates (v_exp_f32 + v_rcp_f32, ~1 ulp each: absolute error < 2e-7, far below
 // the 2^-16 of the products they follow).  The exact-fp32 kernels keep libm (gemm_epilogue_t, act_apply).

@@ -566,22 +566,14 @@ int gemv_fx_forward(const Gemv16Weights& w, const GemvFXArgs& a, hipStream_t str
   ProfScope prof(cat, stream, flops, bytes);
 #define LAUNCH_R(MTV, NTWV, SG, WTV, R4V)                                                                                 \
   {                                                                                                                       \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_fx_kernel<MTV, NTWV, SG, WTV, R4V>),                 \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));                               \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
+    static DynLdsLimit lds_limit;                                                                                         \
+    IDX_HIP(lds_limit.set(128 * 1024, gemv_fx_kernel<MTV, NTWV, SG, WTV, R4V>));                                          \
     hipLaunchKernelGGL((gemv_fx_kernel<MTV, NTWV, SG, WTV, R4V>), grid, dim3(threads), lds, stream, p);                   \
   }
 #define LAUNCH_N(WTV)                                                                                                     \
   {                                                                                                                       \
-    static bool attr_set = false;                                                                                         \
-    if (!attr_set) {                                                                                                      \
-      IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_fx_kernel<1, 1, true, WTV, false, 10>),              \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));                               \
-      attr_set = true;                                                                                                    \
-    }                                                                                                                     \
+    static DynLdsLimit lds_limit;                                                                                         \
+    IDX_HIP(lds_limit.set(128 * 1024, gemv_fx_kernel<1, 1, true, WTV, false, 10>));                                       \
     hipLaunchKernelGGL((gemv_fx_kernel<1, 1, true, WTV, false, 10>), grid, dim3(threads), lds, stream, p);                \
   }
 #define LAUNCH_W(MTV, NTWV, SG, WTV)                                                                                      \

@@ -477,11 +477,8 @@ size_t gemv_pl_slab_floats(int N, int K, int rows) {
 template <int MT, int CT, int WT>
 static int pl_launch(const GemvPLP& p, dim3 grid, hipStream_t stream) {
   const int lds = pl_lds_bytes(MT, CT, 8 / CT > 1 || p.kparts == 1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    IDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemv_pl_kernel<MT, CT, WT>), hipFuncAttributeMaxDynamicSharedMemorySize, pl_lds_bytes(MT, CT, true)));
-    attr_set = true;
-  }
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set(pl_lds_bytes(MT, CT, true), gemv_pl_kernel<MT, CT, WT>));
   hipLaunchKernelGGL((gemv_pl_kernel<MT, CT, WT>), grid, dim3(512), lds, stream, p);
   return 0;
 }

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "gpt.h"
+#include "model_util.h"
 
 namespace idxtts {
 
@@ -32,24 +33,6 @@ bool GPTModel::accepts(const std::string& name) const {
   for (const char* p : prefixes)
     if (name.rfind(p, 0) == 0) return true;
   return false;
-}
-
-static int need(std::map<std::string, HostTensor>& t, const std::string& key, std::vector<int64_t> shape, HostTensor** out) {
-  auto it = t.find(key);
-  if (it == t.end()) IDX_FAIL("missing tensor '" + key + "'");
-  if (it->second.shape != shape) IDX_FAIL("tensor '" + key + "' has the wrong shape");
-  *out = &it->second;
-  return 0;
-}
-
-static int upload(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, std::vector<int64_t> shape,
-                  const float** out) {
-  HostTensor* v = nullptr;
-  if (need(t, key, shape, &v)) return 1;
-  float* d = nullptr;
-  if (arena.upload(v->data.data(), v->data.size(), &d)) return 1;
-  *out = d;
-  return 0;
 }
 
 // HF Conv1D weight [K][N] -> both packed forms
@@ -99,28 +82,12 @@ static int upload_stream32(DeviceArena& arena, const float* w, int N, int K, boo
 static int make_proj(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int K, int N, int fmt,
                      LinearWeights* lw, Gemv16Weights* gw, Gemv32Weights* gp, const HostTensor* ln_g = nullptr, const HostTensor* ln_b = nullptr,
                      const float** u_out = nullptr, const float** c_out = nullptr) {
-  HostTensor* w = nullptr;
-  if (need(t, prefix + ".weight", {K, N}, &w)) return 1;
-  std::vector<float> buf(linear_packed_floats(N, K));
-  pack_linear_kn(buf.data(), w->data.data(), K, N);
-  float* d = nullptr;
-  if (arena.upload(buf.data(), buf.size(), &d)) return 1;
-  lw->wp = d; lw->N = N; lw->K = K;
-  if (upload(t, arena, prefix + ".bias", {N}, &lw->bias)) return 1;
-  {   // split-bf16 copy, used by the latent pass only (the KV-cache-building prefill stays exact fp32)
-    std::vector<float> wt((size_t)N * K);
-    for (int k = 0; k < K; ++k)
-      for (int n = 0; n < N; ++n) wt[(size_t)n * K + k] = w->data[(size_t)k * N + n];
-    std::vector<float> p16((linear_bf16x3_packed_bytes(N, K) + 3) / 4);
-    pack_linear_bf16x3(p16.data(), wt.data(), N, K);
-    float* d16 = nullptr;
-    if (arena.upload(p16.data(), p16.size(), &d16)) return 1;
-    lw->wp16 = d16;
-  }
-  buf.assign(gemv16_packed_floats(N, K), 0.0f);
+  HostTensor *w = nullptr, *bias = nullptr;
+  if (need(t, prefix + ".weight", {K, N}, &w) || need(t, prefix + ".bias", {N}, &bias)) return 1;
+  // the split-bf16 copy is used by the latent pass only (the KV-cache-building prefill stays exact fp32)
+  if (make_linear(arena, w->data.data(), bias->data.data(), N, K, {WP16_ALWAYS, W_KN}, lw)) return 1;
+  std::vector<float> buf(gemv16_packed_floats(N, K), 0.0f);
   if (ln_g) {
-    HostTensor* bias = nullptr;
-    if (need(t, prefix + ".bias", {N}, &bias)) return 1;
     std::vector<float> wf((size_t)K * N), u(N), c(N);
     std::vector<double> ud(N, 0.0), cd(N, 0.0);
     for (int k = 0; k < K; ++k) {
@@ -202,8 +169,8 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
   for (int i = 0; i < cfg.layers; ++i) {
     GPTLayer& L = layers[i];
     const std::string p = "gpt.h." + std::to_string(i);
-    if (upload(t, arena, p + ".ln_1.weight", {d}, &L.ln1_g) || upload(t, arena, p + ".ln_1.bias", {d}, &L.ln1_b)) return 1;
-    if (upload(t, arena, p + ".ln_2.weight", {d}, &L.ln2_g) || upload(t, arena, p + ".ln_2.bias", {d}, &L.ln2_b)) return 1;
+    if (tensor_from(t, arena, p + ".ln_1.weight", {d}, &L.ln1_g) || tensor_from(t, arena, p + ".ln_1.bias", {d}, &L.ln1_b)) return 1;
+    if (tensor_from(t, arena, p + ".ln_2.weight", {d}, &L.ln2_g) || tensor_from(t, arena, p + ".ln_2.bias", {d}, &L.ln2_b)) return 1;
     HostTensor *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
     if (need(t, p + ".ln_1.weight", {d}, &g1) || need(t, p + ".ln_1.bias", {d}, &b1)) return 1;
     if (need(t, p + ".ln_2.weight", {d}, &g2) || need(t, p + ".ln_2.bias", {d}, &b2)) return 1;
@@ -214,8 +181,8 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
     if (make_proj(t, arena, p + ".mlp.c_fc", d, f, weight_fmt, &L.fc_l, &L.fc_g, p32 ? &L.fc_p : no32, g2, b2, &L.fc_u, &L.fc_c)) return 1;
     if (make_proj(t, arena, p + ".mlp.c_proj", f, d, weight_fmt, &L.fc2_l, &L.fc2_g, p32 ? &L.fc2_p : no32)) return 1;
   }
-  if (upload(t, arena, "gpt.ln_f.weight", {d}, &lnf_g) || upload(t, arena, "gpt.ln_f.bias", {d}, &lnf_b)) return 1;
-  if (upload(t, arena, "final_norm.weight", {d}, &fn_g) || upload(t, arena, "final_norm.bias", {d}, &fn_b)) return 1;
+  if (tensor_from(t, arena, "gpt.ln_f.weight", {d}, &lnf_g) || tensor_from(t, arena, "gpt.ln_f.bias", {d}, &lnf_b)) return 1;
+  if (tensor_from(t, arena, "final_norm.weight", {d}, &fn_g) || tensor_from(t, arena, "final_norm.bias", {d}, &fn_b)) return 1;
   const int V = cfg.number_mel_codes;
   HostTensor* hw = nullptr;
   if (need(t, "mel_head.weight", {V, d}, &hw)) return 1;
@@ -223,26 +190,15 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
   pack_gemv16_nk(buf.data(), hw->data.data(), V, d);
   if (upload_stream(arena, buf, V, d, weight_fmt, &head_g)) return 1;
   if (weight_fmt != WFMT_F32 && d % 32 == 0 && upload_stream32(arena, hw->data.data(), V, d, false, weight_fmt, &head_p)) return 1;
-  if (upload(t, arena, "mel_head.bias", {V}, &head_b)) return 1;
-  if (upload(t, arena, "mel_embedding.weight", {V, d}, &mel_emb)) return 1;
-  if (upload(t, arena, "text_embedding.weight", {cfg.number_text_tokens + 1, d}, &text_emb)) return 1;
-  if (upload(t, arena, "mel_pos_embedding.emb.weight", {cfg.mel_pos_len, d}, &mel_pos)) return 1;
-  if (upload(t, arena, "text_pos_embedding.emb.weight", {cfg.text_pos_len, d}, &text_pos)) return 1;
+  if (tensor_from(t, arena, "mel_head.bias", {V}, &head_b)) return 1;
+  if (tensor_from(t, arena, "mel_embedding.weight", {V, d}, &mel_emb)) return 1;
+  if (tensor_from(t, arena, "text_embedding.weight", {cfg.number_text_tokens + 1, d}, &text_emb)) return 1;
+  if (tensor_from(t, arena, "mel_pos_embedding.emb.weight", {cfg.mel_pos_len, d}, &mel_pos)) return 1;
+  if (tensor_from(t, arena, "text_pos_embedding.emb.weight", {cfg.text_pos_len, d}, &text_pos)) return 1;
   return 0;
 }
 
 // ---- workspace carving ----
-struct Carver {
-  char* base; size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  template <typename T> T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new, size_t prefill_rows) const {
   const int d = cfg.model_dim, V = cfg.number_mel_codes, L = cfg.layers;
   Buffers b;

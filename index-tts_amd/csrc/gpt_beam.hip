@@ -9,23 +9,9 @@
 #include <cstring>
 
 #include "gpt.h"
+#include "model_util.h"
 
 namespace idxtts {
-
-namespace {
-
-struct Carver {
-  char* base; size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  template <typename T> T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
-}  // namespace
 
 BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new) {
   const int R = B * nb;

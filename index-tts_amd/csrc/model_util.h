@@ -1,77 +1,40 @@
-// Helpers shared by the small once-per-prompt models (cond.hip, semantic.hip): staged host tensors -> device weights in the
-// exact-fp32 MFMA GEMM pack (+ the split-bf16 pack), workspace carving, and the two launches every layer repeats.
+// Shared by every model's finalize(): staged host tensors -> device weights (the exact-fp32 MFMA GEMM pack, the split-bf16 pack),
+// workspace carving, and the two launches every layer of the small once-per-prompt models repeats.  Definitions: model_util.hip.
 #pragma once
-#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "ctx.h"
 #include "gemm.h"
-#include "norm.h"
 
 namespace idxtts {
-namespace {
 
-int need(std::map<std::string, HostTensor>& t, const std::string& key, std::vector<int64_t> shape, HostTensor** out) {
-  auto it = t.find(key);
-  if (it == t.end()) IDX_FAIL("missing tensor '" + key + "'");
-  if (it->second.shape != shape) IDX_FAIL("tensor '" + key + "' has the wrong shape");
-  *out = &it->second;
-  return 0;
-}
+// the staged tensor `key`, which must have `shape`
+int need(std::map<std::string, HostTensor>& t, const std::string& key, std::vector<int64_t> shape, HostTensor** out);
+int up(DeviceArena& arena, const std::vector<float>& v, const float** out);
+// need + up: a tensor that goes to the device as it is (vec_from: a vector of n)
+int tensor_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, std::vector<int64_t> shape, const float** out);
+int vec_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, int n, const float** out);
+int ln_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int n, const float** g, const float** b);
 
-int up(DeviceArena& arena, const std::vector<float>& v, const float** out) {
-  float* d = nullptr;
-  if (arena.upload(v.data(), v.size(), &d)) return 1;
-  *out = d;
-  return 0;
-}
-
-int vec_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, int n, const float** out) {
-  HostTensor* h = nullptr;
-  if (need(t, key, {n}, &h)) return 1;
-  return up(arena, h->data, out);
-}
-
-// [N][K] host rows (+ bias) -> exact-fp32 MFMA pack; K is padded with zero columns to Kpad (a multiple of 4)
-int make_linear(DeviceArena& arena, const float* w, const float* bias, int N, int K, int Kpad, LinearWeights* out) {
-  std::vector<float> padded;
-  if (Kpad != K) {
-    padded.assign((size_t)N * Kpad, 0.0f);
-    for (int n = 0; n < N; ++n) std::memcpy(&padded[(size_t)n * Kpad], w + (size_t)n * K, K * sizeof(float));
-    w = padded.data();
-  }
-  std::vector<float> packed(linear_packed_floats(N, Kpad));
-  pack_linear(packed.data(), w, N, Kpad);
-  if (up(arena, packed, &out->wp)) return 1;
-  out->N = N; out->K = Kpad;
-  if (N >= 96 && Kpad % 16 == 0) {      // split-bf16 copy: launches of >= 256 rows run on the LDS-DMA kernel in GEMM_BF16X3 mode (gemm_forward)
-    std::vector<float> p16((linear_bf16x3_packed_bytes(N, Kpad) + 3) / 4);
-    pack_linear_bf16x3(p16.data(), w, N, Kpad);
-    const float* d16 = nullptr;
-    if (up(arena, p16, &d16)) return 1;
-    out->wp16 = d16;
-  }
-  if (bias) {
-    std::vector<float> b(bias, bias + N);
-    if (up(arena, b, &out->bias)) return 1;
-  }
-  return 0;
-}
-
-int linear_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int N, int K, bool bias,
-                LinearWeights* out, std::vector<int64_t> wshape = {}) {
-  HostTensor *w = nullptr, *b = nullptr;
-  if (wshape.empty()) wshape = {N, K};
-  if (need(t, prefix + ".weight", wshape, &w)) return 1;
-  if (bias && need(t, prefix + ".bias", {N}, &b)) return 1;
-  return make_linear(arena, w->data.data(), b ? b->data.data() : nullptr, N, K, (K + 3) & ~3, out);
-}
-
-int ln_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int n, const float** g, const float** b) {
-  return vec_from(t, arena, prefix + ".weight", n, g) || vec_from(t, arena, prefix + ".bias", n, b);
-}
+// Which linears get a split-bf16 pack (LinearWeights::wp16) beside the fp32 one.  gemm_forward runs a launch of >= 256 rows on the
+// split-bf16 kernels when the weights carry the pack, and on the exact fp32 kernel when they do not.
+enum Wp16Policy {
+  WP16_ALWAYS,      // every shape: s2mel, the GPT projections, idxtts_linear_create (N < 96 or K % 16 != 0 run on the tile kernels)
+  WP16_DMA_SHAPES,  // only shapes the LDS-DMA kernel takes (N >= 96, K % 16 == 0), the rest stays exact fp32: the small models
+};
+enum WeightLayout { W_NK /* torch nn.Linear [N][K] */, W_KN /* HF Conv1D [K][N] (y = x @ W + b) */ };
+struct LinearOpts {
+  Wp16Policy wp16;
+  WeightLayout layout = W_NK;
+  int Kpad = 0;      // K of the packed weights, >= K: zero columns are added (0: K as it is)
+};
+// host weights (+ bias [N] or null) -> both packs on the device
+int make_linear(DeviceArena& arena, const float* w, const float* bias, int N, int K, const LinearOpts& o, LinearWeights* out);
+// the nn.Linear `prefix`.weight [N][K] (or `wshape`, a 1-tap Conv1d's [N][K][1]) + `prefix`.bias; K is padded to a multiple of 4
+int linear_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int N, int K, bool bias, Wp16Policy wp16,
+                LinearWeights* out, std::vector<int64_t> wshape = {});
 
 struct Carver {
   char* base; size_t off = 0;
@@ -84,29 +47,12 @@ struct Carver {
   }
 };
 
+// exact fp32 MFMA in GEMM_F32 mode; split-bf16 (3 bf16 MFMAs per product, ~2^-16 per product) for M >= 256 in the default mode
 int lin(const LinearWeights& w, const float* x, int ldx, float* y, int ldy, int M, hipStream_t st, int act = ACT_NONE,
-        const float* res = nullptr, int ldr = 0) {
-  GemmArgs g;
-  g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.M = M; g.act = act; g.res = res; g.ldr = ldr;
-  // exact fp32 MFMA in GEMM_F32 mode; split-bf16 (3 bf16 MFMAs per product, ~2^-16 per product) for M >= 256 in the default mode
-  if ((act == ACT_GELU_ERF || act == ACT_RELU)) return gemm_tn_forward(w, g, st);      // (activations only the exact kernel's epilogue has)
-  return gemm_forward(w, g, st);
-}
-
+        const float* res = nullptr, int ldr = 0);
 // exact fp32 whatever the mode: where an integer result follows (the semantic codec's nearest-code search)
 int lin_exact(const LinearWeights& w, const float* x, int ldx, float* y, int ldy, int M, hipStream_t st, int act = ACT_NONE,
-              const float* res = nullptr, int ldr = 0) {
-  GemmArgs g;
-  g.x = x; g.ldx = ldx; g.y = y; g.ldy = ldy; g.M = M; g.act = act; g.res = res; g.ldr = ldr;
-  return gemm_tn_forward(w, g, st);
-}
+              const float* res = nullptr, int ldr = 0);
+int layer_norm(const float* x, float* y, const float* g, const float* b, int M, int d, hipStream_t st);
 
-int layer_norm(const float* x, float* y, const float* g, const float* b, int M, int d, hipStream_t st) {
-  RowsNormArgs n;
-  n.x_in = x; n.ld_in = d; n.y = y; n.ld_y = d; n.M = M; n.d = d; n.mode = NORM_LN; n.eps = 1e-5f; n.g1 = g; n.b1 = b;
-  return rows_norm_forward(n, st);
-}
-
-
-}  // namespace
 }  // namespace idxtts

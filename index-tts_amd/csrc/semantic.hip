@@ -14,6 +14,7 @@
 // reference masks them; the values the reference computes AT padded frames are not reproduced (they never reach a valid
 // frame: the depthwise conv is causal and the padding sits on the right).
 #include <cmath>
+#include <cstring>
 
 #include "model_util.h"
 #include "semantic.h"
@@ -32,7 +33,7 @@ int W2VBertModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& ar
   dk = D / H;
   IDX_CHECK((dk & 3) == 0 && dk <= 128, "head_dim must be a multiple of 4, at most 128");
   if (ln_from(t, arena, "feature_projection.layer_norm", In, &fp_g, &fp_b)) return 1;
-  if (linear_from(t, arena, "feature_projection.projection", D, In, true, &proj)) return 1;
+  if (linear_from(t, arena, "feature_projection.projection", D, In, true, WP16_DMA_SHAPES, &proj)) return 1;
   layers.resize(cfg.num_layers);
   const int nd = cfg.left_max + cfg.right_max + 1;
   for (int i = 0; i < cfg.num_layers; ++i) {
@@ -42,8 +43,8 @@ int W2VBertModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& ar
         ln_from(t, arena, e + ".conv_module.layer_norm", D, &L.conv_g, &L.conv_b) ||
         ln_from(t, arena, e + ".conv_module.depthwise_layer_norm", D, &L.dwn_g, &L.dwn_b) ||
         ln_from(t, arena, e + ".ffn2_layer_norm", D, &L.ffn2_g, &L.ffn2_b) || ln_from(t, arena, e + ".final_layer_norm", D, &L.fin_g, &L.fin_b)) return 1;
-    if (linear_from(t, arena, e + ".ffn1.intermediate_dense", F, D, true, &L.ffn1_in) || linear_from(t, arena, e + ".ffn1.output_dense", D, F, true, &L.ffn1_out) ||
-        linear_from(t, arena, e + ".ffn2.intermediate_dense", F, D, true, &L.ffn2_in) || linear_from(t, arena, e + ".ffn2.output_dense", D, F, true, &L.ffn2_out)) return 1;
+    if (linear_from(t, arena, e + ".ffn1.intermediate_dense", F, D, true, WP16_DMA_SHAPES, &L.ffn1_in) || linear_from(t, arena, e + ".ffn1.output_dense", D, F, true, WP16_DMA_SHAPES, &L.ffn1_out) ||
+        linear_from(t, arena, e + ".ffn2.intermediate_dense", F, D, true, WP16_DMA_SHAPES, &L.ffn2_in) || linear_from(t, arena, e + ".ffn2.output_dense", D, F, true, WP16_DMA_SHAPES, &L.ffn2_out)) return 1;
     {   // q, k, v projections stacked into one [3D][D] GEMM
       std::vector<float> w((size_t)3 * D * D), b((size_t)3 * D);
       const char* names[3] = {"linear_q", "linear_k", "linear_v"};
@@ -53,13 +54,13 @@ int W2VBertModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& ar
         std::memcpy(&w[(size_t)s * D * D], lw->data.data(), (size_t)D * D * sizeof(float));
         std::memcpy(&b[(size_t)s * D], lb->data.data(), D * sizeof(float));
       }
-      if (make_linear(arena, w.data(), b.data(), 3 * D, D, D, &L.qkv)) return 1;
+      if (make_linear(arena, w.data(), b.data(), 3 * D, D, {WP16_DMA_SHAPES}, &L.qkv)) return 1;
     }
-    if (linear_from(t, arena, e + ".self_attn.linear_out", D, D, true, &L.out)) return 1;
+    if (linear_from(t, arena, e + ".self_attn.linear_out", D, D, true, WP16_DMA_SHAPES, &L.out)) return 1;
     HostTensor *de = nullptr, *dw = nullptr;
     if (need(t, e + ".self_attn.distance_embedding.weight", {nd, dk}, &de) || up(arena, de->data, &L.dist)) return 1;
-    if (linear_from(t, arena, e + ".conv_module.pointwise_conv1", 2 * D, D, false, &L.pw1, {2 * D, D, 1})) return 1;
-    if (linear_from(t, arena, e + ".conv_module.pointwise_conv2", D, D, false, &L.pw2, {D, D, 1})) return 1;
+    if (linear_from(t, arena, e + ".conv_module.pointwise_conv1", 2 * D, D, false, WP16_DMA_SHAPES, &L.pw1, {2 * D, D, 1})) return 1;
+    if (linear_from(t, arena, e + ".conv_module.pointwise_conv2", D, D, false, WP16_DMA_SHAPES, &L.pw2, {D, D, 1})) return 1;
     if (need(t, e + ".conv_module.depthwise_conv.weight", {D, 1, kc}, &dw) || up(arena, dw->data, &L.dw_w)) return 1;
   }
   if (t.count("semantic_mean") || t.count("semantic_std")) {
