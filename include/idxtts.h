@@ -500,6 +500,48 @@ int idxtts_s2mel_estimator(idxtts_ctx* ctx, const float* x, const float* prompt,
                            const float* t_emb, const float* style, const float* mu, float* out, int B, int T, void* workspace,
                            size_t workspace_bytes, void* stream);
 
+/* ---- emotion-from-text classifier: Qwen3 causal LM, B = 1 greedy generation (reference: QwenEmotion.inference, infer_v2.py:948-1063:
+ * AutoModelForCausalLM.from_pretrained(qwen_emo_path) + model.generate(max_new_tokens=32768) on a two-message chat prompt; third-party
+ * model: transformers' Qwen3ForCausalLM) --------------------------------------------------------------------------------------
+ * State-dict keys: the HF checkpoint's own -- "model.embed_tokens.weight", "model.layers.{i}.self_attn.{q,k,v,o}_proj.weight",
+ * "model.layers.{i}.self_attn.{q,k}_norm.weight", "model.layers.{i}.mlp.{gate,up,down}_proj.weight",
+ * "model.layers.{i}.{input,post_attention}_layernorm.weight", "model.norm.weight", "lm_head.weight" (required unless
+ * tie_word_embeddings) -- plus the optional buffer "model.rotary_emb.inv_freq" [head_dim / 2] (absent: theta^(-2i/d) in fp32).
+ * Arithmetic is fp32 throughout (the reference loads the model without a dtype). */
+typedef struct idxtts_qwen_config {
+  int vocab_size;                /* 151936 */
+  int hidden_size;               /* 1024 */
+  int intermediate_size;         /* 3072 */
+  int num_hidden_layers;         /* 28 */
+  int num_attention_heads;       /* 16 */
+  int num_key_value_heads;       /* 8 */
+  int head_dim;                  /* 128: the only value the kernels are built for, any other is refused */
+  float rms_norm_eps;            /* 1e-6 */
+  float rope_theta;              /* 1e6 */
+  int tie_word_embeddings;       /* 1: the head reads model.embed_tokens.weight */
+  int max_context;               /* prompt + generated tokens a call may reach (the rotary table's rows), e.g. 4096 */
+} idxtts_qwen_config;
+int idxtts_qwen_create(const idxtts_qwen_config* cfg, idxtts_ctx** out);
+/* Storage of the linear weights and the embedding / head table (before idxtts_ctx_finalize): 0 = fp32 (default), 1 = bf16.  bf16 holds
+ * a bf16 checkpoint widened to fp32 exactly and halves the bytes a token streams; finalize then FAILS, naming the first tensor, if a
+ * weight is not on the bf16 grid (nothing is rounded).  Norm gains and the KV cache stay fp32.  Both formats give the same bits. */
+int idxtts_qwen_set_weight_format(idxtts_ctx* ctx, int format);
+size_t idxtts_qwen_workspace_bytes(const idxtts_ctx* ctx, int n_prompt, int max_new_tokens, int n_eos, int n_logit_cols /* 0 without out_logits; vocab_size for all columns */);
+/* Prefill of prompt_ids (HOST int32 [n_prompt]) + greedy loop: out_ids (HOST int32 [max_new_tokens]) receives every step's argmax
+ * (ties: the lowest id, as torch.argmax), *n_out the steps run; the loop ends after the step whose fed token is one of eos_ids (HOST
+ * int32 [n_eos]; that token is the last entry) or at max_new_tokens.  forced_ids (HOST int32 [max_new_tokens], or NULL): the
+ * teacher-forced parity instrument -- forced_ids[s] continues the sequence after step s (and is what ends it) while out_ids still
+ * records the model's own choice.  out_logits (DEVICE fp32 [max_new_tokens][n], or NULL): the logits of every step that ran at the
+ * columns logit_cols (HOST int32 [n_logit_cols], n = n_logit_cols), or at every column (logit_cols NULL, n = vocab_size).
+ * use_graph: steps 2.. replay one captured hipGraph (kept for the next call with the same shapes on the same workspace); eager
+ * launches and replay give the same bits.  The call returns after the stream has finished. */
+int idxtts_qwen_generate(idxtts_ctx* ctx, const int* prompt_ids, int n_prompt, int max_new_tokens, const int* eos_ids, int n_eos,
+                         const int* forced_ids /* may be NULL */, int* out_ids, int* n_out, float* out_logits /* may be NULL */,
+                         const int* logit_cols /* may be NULL */, int n_logit_cols, void* workspace, size_t bytes, int use_graph,
+                         void* stream);
+/* Kernel launches in the kept decode-step graph (5 per layer + 2, + 1 with out_logits); -1 when no graph is held. */
+int idxtts_qwen_step_graph_launches(const idxtts_ctx* ctx);
+
 /* ---- per-kernel timing for the benchmark's roofline report ------------------------------------------
  * When enabled, every kernel launch is bracketed by HIP events on its own stream and the library
  * accumulates, per kernel family, the launch count, elapsed milliseconds and the ALGORITHMIC flops /

@@ -34,6 +34,8 @@ SYMBOLS = [
     "idxtts_repcodec_create", "idxtts_repcodec_workspace_bytes", "idxtts_repcodec_quantize",
     "idxtts_melspec_create", "idxtts_melspec_frames", "idxtts_melspec_workspace_bytes", "idxtts_melspec_forward",
     "idxtts_campplus_create", "idxtts_campplus_workspace_bytes", "idxtts_campplus_forward",
+    "idxtts_qwen_create", "idxtts_qwen_set_weight_format", "idxtts_qwen_workspace_bytes", "idxtts_qwen_generate",
+    "idxtts_qwen_step_graph_launches",
 ]
 
 
@@ -78,6 +80,12 @@ class MelSpecConfigC(ctypes.Structure):      # idxtts_melspec_config (include/id
 class CamPPlusConfigC(ctypes.Structure):     # idxtts_campplus_config (include/idxtts.h)
     _fields_ = [(n, c_int) for n in ("feat_dim", "embedding_size", "m_channels", "growth_rate", "bn_size", "init_channels", "num_blocks")] + [
         ("block_layers", c_int * 4), ("block_dilation", c_int * 4)]
+
+
+class QwenConfigC(ctypes.Structure):         # idxtts_qwen_config (include/idxtts.h)
+    _fields_ = ([(n, c_int) for n in ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads",
+                                      "num_key_value_heads", "head_dim")]
+                + [("rms_norm_eps", c_float), ("rope_theta", c_float), ("tie_word_embeddings", c_int), ("max_context", c_int)])
 
 
 class BeamC(ctypes.Structure):               # idxtts_beam (include/idxtts.h)
@@ -213,6 +221,13 @@ def load() -> ctypes.CDLL:
     lib.idxtts_w2vbert_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
     lib.idxtts_w2vbert_workspace_bytes.restype = c_size_t
     lib.idxtts_w2vbert_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_qwen_create.argtypes = [POINTER(QwenConfigC), POINTER(c_void_p)]
+    lib.idxtts_qwen_set_weight_format.argtypes = [c_void_p, c_int]
+    lib.idxtts_qwen_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
+    lib.idxtts_qwen_workspace_bytes.restype = c_size_t
+    lib.idxtts_qwen_generate.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p,
+                                         c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_qwen_step_graph_launches.argtypes = [c_void_p]
     lib.idxtts_profile_enable.argtypes = [c_int]
     lib.idxtts_profile_kernel_name.argtypes = [c_int]
     lib.idxtts_profile_kernel_name.restype = c_char_p

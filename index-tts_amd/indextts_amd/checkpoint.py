@@ -186,3 +186,53 @@ def reference_text_normalizer():
         return TextNormalizer()
     except Exception:                                         # noqa: BLE001
         return None
+
+
+def read_safetensors(path: str) -> Dict[str, torch.Tensor]:
+    """A .safetensors file as {name: float32 tensor}, read directly: 8 bytes little-endian header length, a JSON header
+    {name: {"dtype", "shape", "data_offsets": [begin, end]}} and the raw little-endian tensors after it.  F32 as it is; BF16 / F16
+    widened on the host (exact)."""
+    import json
+    import numpy as np
+    with open(path, "rb") as f:
+        n = int.from_bytes(f.read(8), "little")
+        header = json.loads(f.read(n).decode("utf-8"))
+        blob = np.frombuffer(f.read(), dtype=np.uint8)
+    out = {}
+    for name, meta in header.items():
+        if name == "__metadata__":
+            continue
+        b, e = meta["data_offsets"]
+        raw, shape = blob[b:e], tuple(meta["shape"])
+        if meta["dtype"] == "F32":
+            a = raw.view("<f4").astype(np.float32)
+        elif meta["dtype"] == "BF16":
+            a = (raw.view("<u2").astype(np.uint32) << np.uint32(16)).view(np.float32)
+        elif meta["dtype"] == "F16":
+            a = raw.view("<f2").astype(np.float32)
+        else:
+            raise ValueError(f"{path}: tensor '{name}' has dtype {meta['dtype']}; F32, BF16 and F16 are read")
+        out[name] = torch.from_numpy(np.ascontiguousarray(a).reshape(shape))
+    return out
+
+
+def qwen_emotion_from_pretrained(model_dir: str, device="cuda:0", weight_format: str = "bf16", max_new_tokens: int = 512, tokenizer=None):
+    """QwenEmotion from the reference's `qwen_emo_path` directory (infer_v2.py:949-960): config.json -> QwenConfig, model.safetensors ->
+    the state dict, generation_config.json -> the end ids, and the tokenizer from transformers' AutoTokenizer (local files only)
+    unless one is given."""
+    import json
+    from .qwen_emo import QwenConfig, QwenEmotion
+    with open(os.path.join(model_dir, "config.json")) as f:
+        cfg = QwenConfig.from_hf(json.load(f))
+    sd = read_safetensors(os.path.join(model_dir, "model.safetensors"))
+    eos_ids = None
+    gen = os.path.join(model_dir, "generation_config.json")
+    if os.path.exists(gen):
+        with open(gen) as f:
+            e = json.load(f).get("eos_token_id")
+        if e is not None:
+            eos_ids = [int(i) for i in e] if isinstance(e, (list, tuple)) else [int(e)]
+    if tokenizer is None:
+        from transformers import AutoTokenizer      # noqa: PLC0415 -- only this loader needs transformers
+        tokenizer = AutoTokenizer.from_pretrained(model_dir, local_files_only=True, trust_remote_code=True)
+    return QwenEmotion(sd, cfg, tokenizer, weight_format=weight_format, device=device, max_new_tokens=max_new_tokens, eos_ids=eos_ids)

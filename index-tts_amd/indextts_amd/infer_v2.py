@@ -163,6 +163,8 @@ class IndexTTS2:
         from .checkpoint import load_prompt_checkpoints, reference_text_normalizer
         self.model_dir = model_dir
         self.attach_prompt_models(load_prompt_checkpoints(model_dir, raw), normalizer=reference_text_normalizer())
+        if raw and raw.get("qwen_emo_path"):      # loaded on first use, as the reference does (infer_v2.py:118-128, 322-328)
+            self._qwen_emo_path = os.path.join(model_dir, str(raw["qwen_emo_path"]))
 
     def attach_prompt_models(self, ck: dict, normalizer=None) -> None:
         """ck: checkpoint.load_prompt_checkpoints()'s dict (state dicts in the reference modules' own key layouts, statistics,
@@ -207,6 +209,28 @@ class IndexTTS2:
         self._cfg_rate = float(os.environ.get("TARS_CFG_RATE", cfg.cfg_rate))                      # infer_v2.py:126
         self.last_stage_times = {}
         self.segment_batch = int(segment_batch)      # segments of one infer() call synthesised together
+
+    @property
+    def qwen_emo(self):
+        """The emotion-from-text classifier (qwen_emo.QwenEmotion, or anything with `inference(text) -> dict` of the eight scores in
+        order): set it, or -- built from a checkpoint directory whose config names `qwen_emo_path` -- it loads on first use."""
+        if getattr(self, "_qwen_emo", None) is None:
+            path = getattr(self, "_qwen_emo_path", None)
+            if path is None:
+                raise NotImplementedError("emo_text routing (the Qwen emotion classifier, infer_v2.py:590-598) needs a classifier: set "
+                                          "tts.qwen_emo = QwenEmotion(...), or pass its result as emo_vector")
+            from .checkpoint import qwen_emotion_from_pretrained
+            self._qwen_emo = qwen_emotion_from_pretrained(path, device=self.device)
+        return self._qwen_emo
+
+    @qwen_emo.setter
+    def qwen_emo(self, value):
+        self._qwen_emo = value
+
+    def normalize_emo_vec(self, emo_vector, apply_bias=True):
+        """infer_v2.py:524-538: de-emphasise the emotions that tend to sound odd, then cap the sum at 0.8."""
+        from .qwen_emo import normalize_emo_vec
+        return normalize_emo_vec(emo_vector, apply_bias)
 
     # ------------------------------------------------------------------------------------------
     def synthesize_batch(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
@@ -393,6 +417,7 @@ class IndexTTS2:
         CPU, already scaled and clamped to +-32767) and then the inter-segment silence, and nothing else (874-879, 885-886)."""
         if stream_return and return_audio:
             raise ValueError("stream_return and return_audio are mutually exclusive")                # infer_v2.py:575-576
+        text_str = text if isinstance(text, str) else None      # use_emo_text without emo_text classifies the text itself
         if isinstance(text, str):
             # text front-end (infer_v2.py:697-704): tokenize, split into segments, ids.  The tokenizer (indextts_amd/tokenizer.py) needs
             # the checkpoint's bpe.model and, for real text, the reference's normaliser (WeTextProcessing): both absent offline.
@@ -403,9 +428,13 @@ class IndexTTS2:
             tokens = tok.tokenize(text)
             text = [tok.convert_tokens_to_ids(seg) for seg in tok.split_segments(tokens, max_text_tokens_per_segment,
                                                                                  quick_streaming_tokens=quick_streaming_tokens)]
-        if use_emo_text:
-            raise NotImplementedError("emo_text routing (the Qwen emotion classifier, infer_v2.py:590-598) happens upstream of this path: "
-                                      "pass its result as emo_vector")
+        if use_emo_text:                                                                             # infer_v2.py:591-598
+            classifier = self.qwen_emo      # NotImplementedError when none is attached
+            if emo_text is None:
+                emo_text = text_str
+            if emo_text is None:
+                raise ValueError("use_emo_text with token-id text needs emo_text: there is no string to classify")
+            emo_vector = list(classifier.inference(emo_text).values())      # the dict's order is the vector's
         if emo_vector is not None:
             emo_audio_prompt = None                                                                  # infer_v2.py:586-589
             scale = max(0.0, min(1.0, emo_alpha))                                                    # 600-608
