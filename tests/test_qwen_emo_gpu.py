@@ -14,6 +14,7 @@ import torch
 from indextts_amd import synth, weights
 from indextts_amd.config import PipelineConfig
 from indextts_amd.qwen_emo import QwenConfig, QwenEmotion, QwenLM, synth_qwen_weights
+import qwen_shapes as qs
 from qwen_ckpt_dir import EOS_ID, StubTokenizer, write_qwen_dir
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +82,24 @@ def test_graph_replay_equals_eager_bit_for_bit(name, fmt, golden, device):
     assert 0 < n <= 5 * CONFIGS[name].num_hidden_layers + 3, n
     lm.generate(prompt, len(ids), use_graph=True)
     assert 0 < lm.step_graph_launches() <= 5 * CONFIGS[name].num_hidden_layers + 2
+
+
+@pytest.fixture(scope="module")
+def shapes(golden_dir):
+    return dict(np.load(os.path.join(golden_dir, "qwen_lm_shapes.npz")))
+
+
+# "full_long" (tests/qwen_shapes.py): the "full" weights at prompt 150 + 100 steps -- four key pieces, as every real call has
+@pytest.mark.parametrize("fmt", ["f32", "bf16"])
+def test_full_width_key_split_matches_the_reference(fmt, golden, shapes, device):
+    assert int(shapes["full_long_wseed"]) == int(golden["full_seed"]) and qs.BY_NAME["full_long"].nsplit == 4
+    qs.check_against_reference(_lm("full", fmt, golden, device), "full_long", fmt, shapes)
+
+
+def test_full_width_key_split_formats_and_graph_agree_bit_for_bit(golden, shapes, device):
+    assert int(shapes["full_long_wseed"]) == int(golden["full_seed"])
+    qs.check_formats_agree(_lm("full", "f32", golden, device), _lm("full", "bf16", golden, device), "full_long", shapes)
+    qs.check_graph_equals_eager(_lm("full", "bf16", golden, device), "full_long", shapes)
 
 
 def test_stops_at_an_end_id_and_at_the_cap(golden, device):
