@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "beam.h"
+#include "device_util.h"
 #include "prof.h"
 
 namespace idxtts {
@@ -19,32 +20,6 @@ namespace {
 constexpr int NPT = 16;          // vocabulary entries per thread of a 1024-thread block: V <= 16384
 constexpr int CAP = 2048;        // survivors of the top-k filter handled by the top-p stage
 constexpr int SEL_EPT = 32;      // beam_select: candidates per thread kept in registers (nb * V <= 32768), else the re-reading loop
-
-__device__ __forceinline__ void block_argmax1024(float& v, int& i, float* rv, int* ri, int tid) {   // max value, smallest index on ties
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off);
-    const int oi = __shfl_xor(i, off);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) { rv[tid >> 6] = v; ri[tid >> 6] = i; }
-  __syncthreads();
-  v = rv[0]; i = ri[0];
-  for (int w = 1; w < 16; ++w)
-    if (rv[w] > v || (rv[w] == v && ri[w] < i)) { v = rv[w]; i = ri[w]; }
-}
-
-__device__ __forceinline__ float block_sum1024(float v, float* rv, int tid) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((tid & 63) == 0) rv[tid >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int w = 0; w < 16; ++w) t += rv[w];
-  return t;
-}
 
 }  // namespace
 
@@ -84,11 +59,11 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
     sc[u] = v < V ? lrow[v] : -INFINITY;
     if (sc[u] > mx) { mx = sc[u]; mi = v; }
   }
-  block_argmax1024(mx, mi, rv, ri, tid);
+  block_argmax<16>(mx, mi, rv, ri, tid);
   float part = 0.f;
 #pragma unroll
   for (int u = 0; u < NPT; ++u) if (tid + 1024 * u < V) part += expf(sc[u] - mx);
-  const float lse = logf(block_sum1024(part, rv, tid));
+  const float lse = logf(block_sum<16>(part, rv));
   // log_softmax (fp32, before the processors: transformers_generation_utils.py:3473-3477), repetition penalty, temperature
 #pragma unroll
   for (int u = 0; u < NPT; ++u) {
@@ -272,12 +247,12 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
       ks[e] = i < N ? base[i] : -INFINITY;
       if (i < N && (ks[e] > mx || (ks[e] == mx && i < mi))) { mx = ks[e]; mi = i; }
     }
-    block_argmax1024(mx, mi, rv, ri, tid);
+    block_argmax<16>(mx, mi, rv, ri, tid);
     if (do_sample) {
       float part = 0.f;
 #pragma unroll
       for (int e = 0; e < SEL_EPT; ++e) if (tid + 1024 * e < N) part += expf(ks[e] - mx);
-      const float tot = block_sum1024(part, rv, tid);
+      const float tot = block_sum<16>(part, rv);
 #pragma unroll
       for (int e = 0; e < SEL_EPT; ++e) {
         const int i = tid + 1024 * e;
@@ -292,7 +267,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
         const int i = tid + 1024 * e;
         if (i < N && !((taken >> e) & 1u) && (ks[e] > best || (ks[e] == best && i < bi))) { best = ks[e]; bi = i; }
       }
-      block_argmax1024(best, bi, rv, ri, tid);
+      block_argmax<16>(best, bi, rv, ri, tid);
       if (bi < N && (bi & 1023) == tid) taken |= 1u << (bi >> 10);
       if (tid == 0) { cand_i[c] = bi; cand_s[c] = base[bi]; }
     }
@@ -300,12 +275,12 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
   } else {
     float mx = -INFINITY; int mi = 0x7fffffff;
     for (int i = tid; i < N; i += 1024) { const float x = base[i]; if (x > mx || (x == mx && i < mi)) { mx = x; mi = i; } }
-    block_argmax1024(mx, mi, rv, ri, tid);
+    block_argmax<16>(mx, mi, rv, ri, tid);
     float tot = 1.0f;
     if (do_sample) {
       float part = 0.f;
       for (int i = tid; i < N; i += 1024) part += expf(base[i] - mx);
-      tot = block_sum1024(part, rv, tid);
+      tot = block_sum<16>(part, rv);
     }
     for (int c = 0; c < n_keep; ++c) {
       float best = -INFINITY; int bi = 0x7fffffff;
@@ -317,7 +292,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
         const float key = do_sample ? (expf(x - mx) / tot) / exp1_draw(exp_noise, seed, nbase + i) : x;
         if (key > best || (key == best && i < bi)) { best = key; bi = i; }
       }
-      block_argmax1024(best, bi, rv, ri, tid);
+      block_argmax<16>(best, bi, rv, ri, tid);
       if (tid == 0) { cand_i[c] = bi; cand_s[c] = base[bi]; }
       __syncthreads();
     }

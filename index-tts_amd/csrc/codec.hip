@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "codec.h"
+#include "device_util.h"
 #include "model_util.h"
 
 namespace idxtts {
@@ -119,17 +120,11 @@ __global__ __launch_bounds__(256) void nearest_code_kernel(const float* ze, cons
     const float nd = -((s_e2 - 2.0f * dot) + c2);
     if (nd > best) { best = nd; bidx = v; }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off);
-    const int oi = __shfl_xor(bidx, off);
-    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
-  }
+  wave_argmax(best, bidx);
   if ((tid & 63) == 0) { rv[tid >> 6] = best; ri[tid >> 6] = bidx; }
   __syncthreads();
   if (tid == 0) {
-    for (int w = 1; w < 4; ++w)
-      if (rv[w] > best || (rv[w] == best && ri[w] < bidx)) { best = rv[w]; bidx = ri[w]; }
+    argmax_take_waves<4>(best, bidx, rv, ri);
     indices[m] = bidx;
     ri[0] = bidx;
   }

@@ -8,6 +8,7 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace idxtts {
 
@@ -60,6 +61,17 @@ __device__ __forceinline__ void split_bf16_x4(const f32x4 v, idx_bf16x4& hi, idx
   hi = __builtin_bit_cast(idx_bf16x4, u2{h0, h1});
   lo = __builtin_bit_cast(idx_bf16x4, u2{l0, l1});
 }
+
+// One value as bf16: rounded to nearest even when it is produced (no NaN case: the KV cache holds finite values), widened exactly
+// (<< 16) when it is used.  load_w: a weight stored as fp32 or as bf16 bits.
+__device__ __forceinline__ unsigned bf16_rne_bits(float f) {
+  unsigned u = __float_as_uint(f);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+__device__ __forceinline__ float bf16_widen(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
+__device__ __forceinline__ float load_w(const float* p) { return *p; }
+__device__ __forceinline__ float load_w(const unsigned short* p) { return bf16_widen(*p); }
 
 // Split-bf16 GEMM operands (gemm_bf16x3_v2.hip): activation x[rows][K] fp32 as two bf16 planes (hi, lo = x - hi), each
 // [K/16][rows][16]: a 16-k chunk of all rows is one contiguous run.  Producers may write them directly.

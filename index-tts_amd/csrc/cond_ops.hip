@@ -6,31 +6,10 @@
 #include <cmath>
 
 #include "cond_ops.h"
+#include "device_util.h"
 #include "prof.h"
 
 namespace idxtts {
-
-namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float bsum256(float v, float* red) {   // 256 threads; red: 4 floats of LDS
-  v = wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
 // One workgroup per output frame (b, t2): the three input rows and all C filters sit in LDS; a thread owns output
@@ -130,14 +109,14 @@ __global__ __launch_bounds__(256) void seq_attn_kernel(const SeqAttnArgs p) {
     sc[j] = s;
     mx = fmaxf(mx, s);
   }
-  mx = wmax(mx);
+  mx = wave_max(mx);
   float sum = 0.0f;
   for (int j = lane; j < kend; j += 64) {
     const float e = expf(sc[j] - mx);
     sc[j] = e;
     sum += e;
   }
-  sum = wsum(sum);
+  sum = wave_sum(sum);
   __builtin_amdgcn_wave_barrier();
   const float inv = kend > 0 ? 1.0f / sum : 0.0f;
   float* o = p.o + (size_t)b * p.o_bs + (size_t)qi * p.ldo + h * dk;
@@ -222,11 +201,11 @@ __global__ __launch_bounds__(256) void dwconv_ln_kernel(float* y, const float* p
     }
     v[i] = acc;
   }
-  const float mean = bsum256(s, red) / D;
+  const float mean = block_sum<4>(s, red) / D;
   float ss = 0.0f;
 #pragma unroll
   for (int i = 0; i < DW_MAX_PER_THREAD; ++i) { const int c = tid + 256 * i; if (c < D) { const float dlt = v[i] - mean; ss += dlt * dlt; } }
-  const float rstd = rsqrtf(bsum256(ss, red) / D + eps);
+  const float rstd = rsqrtf(block_sum<4>(ss, red) / D + eps);
 #pragma unroll
   for (int i = 0; i < DW_MAX_PER_THREAD; ++i) {
     const int c = tid + 256 * i;
@@ -304,7 +283,7 @@ __global__ __launch_bounds__(256) void l2norm_scale_kernel(float* y, const float
   const int m = blockIdx.x;
   float ss = 0.0f;
   for (int e = threadIdx.x; e < d; e += 256) { const float v = x[(size_t)m * d + e]; ss = fmaf(v, v, ss); }
-  const float nrm = fmaxf(sqrtf(bsum256(ss, red)), 1e-12f);
+  const float nrm = fmaxf(sqrtf(block_sum<4>(ss, red)), 1e-12f);
   for (int e = threadIdx.x; e < d; e += 256) y[(size_t)m * d + e] = x[(size_t)m * d + e] / nrm * scale * gamma[e];
 }
 

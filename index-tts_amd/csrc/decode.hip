@@ -18,20 +18,10 @@
 #include <cstdlib>
 
 #include "decode.h"
+#include "device_util.h"
 #include "prof.h"
 
 namespace idxtts {
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float wave_add(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // Output of one (utterance, head) workgroup: o = this thread's unnormalised output element (threads 0..63), mx / l = the piece's
 // score maximum and exp-sum.  NS == 1: normalise and write the A-fragment image for the c_proj GEMV.  Key split: leave (o, max, sum)
@@ -48,20 +38,11 @@ __device__ __forceinline__ void decode_attn_finish(const DecodeAttnArgs& p, cons
     return;
   }
   // ---- key split: leave (o, max, sum) of this piece; the last piece to arrive merges all of them in piece order ----
-  __shared__ int s_last;
   float* mine = p.part + ((size_t)(b * p.H + h) * NS + z) * 66;
   if (tid < 64) __hip_atomic_store(&mine[tid], o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (tid == 64) __hip_atomic_store(&mine[64], mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (tid == 65) __hip_atomic_store(&mine[65], l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // device-scope stores acknowledged before the arrival (see gemv_fx.hip)
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = __hip_atomic_fetch_add(&p.cnt[b * p.H + h], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == (unsigned)NS - 1u;
-    if (s_last) __hip_atomic_store(&p.cnt[b * p.H + h], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last || tid >= 64) return;
+  if (!wg_arrive_last(&p.cnt[b * p.H + h], (unsigned)NS) || tid >= 64) return;
   const float* all = p.part + (size_t)(b * p.H + h) * NS * 66;
   float mi[16], li[16], oi[16];       // every piece's (max, sum, this lane's output) in ONE round trip
 #pragma unroll
@@ -84,8 +65,6 @@ __device__ __forceinline__ void decode_attn_finish(const DecodeAttnArgs& p, cons
   put(L > 0.f ? O / L : 0.f);
 }
 
-// NT threads per workgroup: NT / 16 key groups in the P.V phase, NT keys per pass of the score phase.  512 threads at <= 128
-// VGPRs (two workgroups per CU) halve the number of dependent load -> use passes of the 256-thread form.
 // Output of a row whose session slot is not live: zeros, written once per (row, head)
 __device__ __forceinline__ void decode_attn_dead(const DecodeAttnArgs& p, const int b, const int h, const int z, const int tid) {
   if (z != 0 || tid >= 64) return;
@@ -93,13 +72,102 @@ __device__ __forceinline__ void decode_attn_dead(const DecodeAttnArgs& p, const 
   else p.out[frag_index(b, h * 64 + tid, p.d >> 4)] = 0.f;
 }
 
-// SLOTS: decode session (DecodeAttnArgs::slot) -- the row's own position, dead rows return at once
-template <int NT, bool SLOTS>
-__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(const DecodeAttnArgs p) {
-  constexpr int NW = NT / 64, NG = NT / 16;
+// ---- the two cache formats: how a 16-byte key / value granule is laid out, widened, multiplied and stored.  Both keep a key as
+//      64 / EPG granules [granule][Smax] and a value row as 64 / EPG granules, one per lane; every product and sum is fp32. ----
+// fp32 cache: K [B][H][16][Smax][4], V [B][H][Smax][64] (256-byte rows)
+struct KvF32 {
+  typedef float E;                        // cache element
+  typedef f32x4 G;                        // granule
+  typedef f32x4 Acc;                      // a lane's P.V accumulator: the head dims of its granule
+  typedef f32x4 VNew;                     // the new token's value, this lane's granule
+  static constexpr int EPG = 4;           // elements per granule
+  static constexpr int NACC = 4;          // independent accumulators
+  static constexpr int OUT_UNROLL = 32;   // the group reduction, fully unrolled
+  __device__ static __forceinline__ G zero() { return G{0.f, 0.f, 0.f, 0.f}; }
+  // the new token's k / v element: the cache gets it (piece 0), this step uses what a later step will read back
+  __device__ static __forceinline__ float put(E* dst, const bool write, const float x) {
+    if (write) *dst = x;
+    return x;
+  }
+  __device__ static __forceinline__ float dot_new(const float (&qv)[64], const float* knew) {
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dot += qv[4 * i] * knew[4 * i] + qv[4 * i + 1] * knew[4 * i + 1] + qv[4 * i + 2] * knew[4 * i + 2] + qv[4 * i + 3] * knew[4 * i + 3];
+    return dot;
+  }
+  __device__ static __forceinline__ float dot_key(const float (&qv)[64], const G (&kk)[16]) {
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dot += qv[4 * i] * kk[i][0] + qv[4 * i + 1] * kk[i][1] + qv[4 * i + 2] * kk[i][2] + qv[4 * i + 3] * kk[i][3];
+    return dot;
+  }
+  __device__ static __forceinline__ VNew vnew_of(const float* vnew, const int l) { return *reinterpret_cast<const f32x4*>(&vnew[4 * l]); }
+  __device__ static __forceinline__ void fma(Acc& acc, const float pw, const G v) { acc += pw * v; }
+  __device__ static __forceinline__ void fma_new(Acc& acc, const float pw, const VNew vn) { acc += pw * vn; }
+  __device__ static __forceinline__ void store(float* dst, const Acc (&a)[4]) { *reinterpret_cast<f32x4*>(dst) = (a[0] + a[1]) + (a[2] + a[3]); }
+};
+// bf16 cache (DecodeAttnArgs::kv16), half the bytes: K [B][H][8][Smax][8], V [B][H][Smax][64] (128-byte rows).  A key / value is
+// rounded to bf16 (nearest even) when it is produced -- the new token's own k / v too, so a position reads the same whether it is
+// the newest or an old one -- and widened exactly (<< 16) when used.
+struct KvBf16 {
+  typedef unsigned short E;
+  typedef u32x4 G;
+  struct Acc { float e[8]; };
+  typedef const float* VNew;
+  static constexpr int EPG = 8;
+  static constexpr int NACC = 2;
+  static constexpr int OUT_UNROLL = 16;
+  __device__ static __forceinline__ G zero() { return G{0u, 0u, 0u, 0u}; }
+  __device__ static __forceinline__ float put(E* dst, const bool write, const float x) {
+    const unsigned bits = bf16_rne_bits(x);
+    if (write) *dst = (unsigned short)bits;
+    return __uint_as_float(bits << 16);
+  }
+  __device__ static __forceinline__ float dot_new(const float (&qv)[64], const float* knew) {
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) dot += qv[i] * knew[i];
+    return dot;
+  }
+  __device__ static __forceinline__ float dot_key(const float (&qv)[64], const G (&kk)[8]) {
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        dot += qv[8 * i + 2 * j] * __uint_as_float(kk[i][j] << 16) + qv[8 * i + 2 * j + 1] * __uint_as_float(kk[i][j] & 0xffff0000u);
+    return dot;
+  }
+  __device__ static __forceinline__ VNew vnew_of(const float* vnew, const int l) { return vnew + 8 * l; }
+  __device__ static __forceinline__ void fma(Acc& acc, const float pw, const G v) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc.e[2 * j] += pw * __uint_as_float(v[j] << 16);
+      acc.e[2 * j + 1] += pw * __uint_as_float(v[j] & 0xffff0000u);
+    }
+  }
+  __device__ static __forceinline__ void fma_new(Acc& acc, const float pw, const VNew vn) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc.e[e] += pw * vn[e];
+  }
+  __device__ static __forceinline__ void store(float* dst, const Acc (&a)[2]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dst[e] = a[0].e[e] + a[1].e[e];
+  }
+};
+
+// One query token per (utterance, head) workgroup against its cached keys, or against one of gridDim.z pieces of them.
+// NT threads per workgroup: NT keys per pass of the score phase, NG = NT / (lanes of a value row) key groups in the P.V phase.  512
+// threads at <= 128 VGPRs (two workgroups per CU) halve the number of dependent load -> use passes of the 256-thread form.
+// SLOTS: decode session (DecodeAttnArgs::slot) -- the row's own position, dead rows return at once.  KV: the cache format.
+template <int NT, bool SLOTS, class KV>
+__device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
+  typedef typename KV::G G;
+  typedef typename KV::E E;
+  constexpr int NW = NT / 64, EPG = KV::EPG, KG = 64 / EPG, LPR = 64 / EPG, NG = NT / LPR, NACC = KV::NACC;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* qs = sm;            // [64] scaled query
-  float* knew = sm + 64;     // [64]
+  float* knew = sm + 64;     // [64] the new token's key and value, as the cache holds them
   float* vnew = sm + 128;    // [64]
   float* red = sm + 192;     // [2 * NW]
   float* outp = sm + 256;    // [NG][64] per-key-group partial outputs
@@ -114,11 +182,11 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(co
     pos = p.st->pos;
   }
   const int d = p.d, Smax = p.Smax;
-  float* kc = static_cast<float*>(p.kcache) + (size_t)(b * p.H + h) * 16 * Smax * 4;
-  float* vc = static_cast<float*>(p.vcache) + (size_t)(b * p.H + h) * Smax * 64;
+  G* const kc = static_cast<G*>(p.kcache) + (size_t)(b * p.H + h) * KG * Smax;       // granule (c, s) at c * Smax + s
+  G* const vc = static_cast<G*>(p.vcache) + (size_t)(b * p.H + h) * Smax * LPR;      // granule (s, c) at s * LPR + c
 
-  // Everything that does not depend on the new token's q is put in flight first: this thread's first key (16 x 16 B,
-  // coalesced across threads) and its first 8 value rows of the P.V phase; the kernel is a chain of dependent
+  // Everything that does not depend on the new token's q is put in flight first: this thread's first key (KG x 16 B,
+  // coalesced across threads) and its first value rows of the P.V phase; the kernel is a chain of dependent
   // HBM / L2 round trips, so the cache streams have to overlap the qkv fetch and the softmax barriers.
   // key range of this workgroup: all of [kstart, pos] (pos = the new token), or one of gridDim.z contiguous pieces of it
   const int ks0 = p.kstart ? p.kstart[b] : 0;
@@ -126,21 +194,20 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(co
   const int chunk = NS > 1 ? (((pos - ks0 + NS) / NS + 15) & ~15) : pos - ks0 + 1;
   const int ks = ks0 + z * chunk;
   const int ke = min(pos, ks + chunk - 1);          // inclusive; ks > ke: an empty piece
-  const int grp = tid >> 4, l16 = tid & 15;
+  const int grp = tid / LPR, lpr = tid % LPR;
   const int s_first = ks + tid;
-  f32x4 kk0[16];
+  G kk0[KG];
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
-    kk0[i] = (s_first < pos && s_first <= ke) ? *reinterpret_cast<const f32x4*>(kc + ((size_t)i * Smax + s_first) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int VP = NT == 512 ? 4 : 8;      // value rows prefetched per lane before the scores (NG * VP = 128 keys either way)
-  f32x4 vpre[VP];
+  for (int i = 0; i < KG; ++i) kk0[i] = (s_first < pos && s_first <= ke) ? kc[(size_t)i * Smax + s_first] : KV::zero();
+  constexpr int VP = 128 / NG;      // value rows prefetched per lane before the scores (NG * VP = 128 keys)
+  G vpre[VP];
 #pragma unroll
   for (int j = 0; j < VP; ++j) {
     const int sj = ks + grp + NG * j;
-    vpre[j] = (sj < pos && sj <= ke) ? *reinterpret_cast<const f32x4*>(vc + (size_t)sj * 64 + 4 * l16) : f32x4{0.f, 0.f, 0.f, 0.f};
+    vpre[j] = (sj < pos && sj <= ke) ? vc[(size_t)sj * LPR + lpr] : KV::zero();
   }
 
-  // ---- q, k, v of the new token (waves 0,1,2 take q,k,v) ----
+  // ---- q, k, v of the new token (waves 0,1,2 take q,k,v): the c_attn split-K partial sum + bias, k / v to the cache ----
   if (tid < 192) {
     const int which = tid >> 6, dd = tid & 63;
     const int col = which * d + h * 64 + dd;
@@ -149,8 +216,8 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(co
     float acc = p.qkv_bias ? p.qkv_bias[col] : 0.0f;
     for (int s = 0; s < p.parts; ++s) acc += row[(size_t)s * sst];
     if (which == 0) qs[dd] = acc * p.scale;
-    else if (which == 1) { knew[dd] = acc; if (z == 0) kc[((size_t)(dd >> 2) * Smax + pos) * 4 + (dd & 3)] = acc; }
-    else { vnew[dd] = acc; if (z == 0) vc[(size_t)pos * 64 + dd] = acc; }
+    else if (which == 1) knew[dd] = KV::put(reinterpret_cast<E*>(kc + (size_t)(dd / EPG) * Smax + pos) + dd % EPG, z == 0, acc);
+    else vnew[dd] = KV::put(reinterpret_cast<E*>(vc + (size_t)pos * LPR) + dd, z == 0, acc);
   }
   __syncthreads();
 
@@ -163,202 +230,23 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(co
   // ---- scores: one key per thread and pass; the first pass consumes the prefetched key ----
   float mx = -1e30f;
   if (s_first <= ke) {
-    float dot = 0.f;
-    if (s_first == pos) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dot += qv[4 * i] * knew[4 * i] + qv[4 * i + 1] * knew[4 * i + 1] + qv[4 * i + 2] * knew[4 * i + 2] + qv[4 * i + 3] * knew[4 * i + 3];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dot += qv[4 * i] * kk0[i][0] + qv[4 * i + 1] * kk0[i][1] + qv[4 * i + 2] * kk0[i][2] + qv[4 * i + 3] * kk0[i][3];
-    }
-    pr[s_first] = dot;
-    mx = dot;
-  }
-  for (int s = s_first + NT; s <= ke; s += NT) {
-    float dot = 0.f;
-    if (s == pos) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dot += qv[4 * i] * knew[4 * i] + qv[4 * i + 1] * knew[4 * i + 1] + qv[4 * i + 2] * knew[4 * i + 2] + qv[4 * i + 3] * knew[4 * i + 3];
-    } else {
-      f32x4 kk[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) kk[i] = *reinterpret_cast<const f32x4*>(kc + ((size_t)i * Smax + s) * 4);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dot += qv[4 * i] * kk[i][0] + qv[4 * i + 1] * kk[i][1] + qv[4 * i + 2] * kk[i][2] + qv[4 * i + 3] * kk[i][3];
-    }
-    pr[s] = dot;
-    mx = fmaxf(mx, dot);
-  }
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = red[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) mx = fmaxf(mx, red[w]);
-  float sum = 0.f;
-  for (int s = s_first; s <= ke; s += NT) {
-    const float e = expf(pr[s] - mx);
-    pr[s] = e;
-    sum += e;
-  }
-  sum = wave_add(sum);
-  if (lane == 0) red[NW + wave] = sum;
-  __syncthreads();
-  float l = 0.f;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) l += red[NW + w];
-
-  // ---- P.V : 16 key groups x 16 lanes; a lane owns 4 head dims (one 16-byte load per key, 256-byte rows coalesced),
-  //      8 keys in flight per lane; group g takes keys ks+g, ks+g+16, ... ----
-  const f32x4 vn4 = *reinterpret_cast<const f32x4*>(&vnew[4 * l16]);
-  f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-#pragma unroll
-  for (int j = 0; j < VP; ++j) {
-    const int sj = ks + grp + NG * j;
-    if (sj <= ke) {
-      const f32x4 t = pr[sj] * (sj == pos ? vn4 : vpre[j]);
-      if ((j & 3) == 0) a0 += t; else if ((j & 3) == 1) a1 += t; else if ((j & 3) == 2) a2 += t; else a3 += t;
-    }
-  }
-  for (int sb = ks + grp + VP * NG; sb <= ke; sb += 8 * NG) {
-    f32x4 v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int sj = sb + NG * j;
-      v[j] = sj < pos ? *reinterpret_cast<const f32x4*>(vc + (size_t)sj * 64 + 4 * l16) : vn4;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int sj = sb + NG * j;
-      if (sj <= ke) {
-        const f32x4 t = pr[sj] * v[j];
-        if ((j & 3) == 0) a0 += t; else if ((j & 3) == 1) a1 += t; else if ((j & 3) == 2) a2 += t; else a3 += t;
-      }
-    }
-  }
-  *reinterpret_cast<f32x4*>(&outp[grp * 64 + 4 * l16]) = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  float o = 0.f;
-  if (tid < 64) {
-#pragma unroll
-    for (int g = 0; g < NG; ++g) o += outp[g * 64 + tid];
-  }
-  decode_attn_finish(p, b, h, z, NS, tid, o, mx, l);
-}
-
-// ---- bf16 cache form (DecodeAttnArgs::kv16) ----
-// Same structure, half the bytes: K [B][H][8][Smax][8] bf16 (a key's 16-byte granule per 8-dim chunk: 8 coalesced 16-byte loads per
-// key instead of 16), V [B][H][Smax][64] bf16 (128-byte rows: 8 lanes x 16 bytes per key, 64 key groups per workgroup).  A key /
-// value is rounded to bf16 (nearest even) when it is produced -- the new token's own k / v too, so a position reads the same
-// whether it is the newest or an old one -- and widened exactly (<< 16) when used; every product and sum is fp32.
-__device__ __forceinline__ unsigned bf16_rne_bits(float f) {
-  unsigned u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-__device__ __forceinline__ float bf16_round_f32(float f) { return __uint_as_float(bf16_rne_bits(f) << 16); }
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <int NT, bool SLOTS>
-__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(const DecodeAttnArgs p) {
-  constexpr int NW = NT / 64, NG = NT / 8;
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* qs = sm;            // [64] scaled query
-  float* knew = sm + 64;     // [64] (rounded)
-  float* vnew = sm + 128;    // [64] (rounded)
-  float* red = sm + 192;     // [2 * NW]
-  float* outp = sm + 256;    // [NG][64] per-key-group partial outputs
-  float* pr = sm + 256 + NG * 64;   // [Smax] scores / probabilities
-
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  int pos;
-  if constexpr (SLOTS) {
-    if (!p.slot[b].live) { decode_attn_dead(p, b, h, blockIdx.z, tid); return; }
-    pos = p.slot[b].pos;
-  } else {
-    pos = p.st->pos;
-  }
-  const int d = p.d, Smax = p.Smax;
-  u32x4* const kc = static_cast<u32x4*>(p.kcache) + (size_t)(b * p.H + h) * 8 * Smax;      // granule (c, s) at c * Smax + s
-  u32x4* const vc = static_cast<u32x4*>(p.vcache) + (size_t)(b * p.H + h) * Smax * 8;      // granule (s, c) at s * 8 + c
-
-  const int ks0 = p.kstart ? p.kstart[b] : 0;
-  const int NS = gridDim.z, z = blockIdx.z;
-  const int chunk = NS > 1 ? (((pos - ks0 + NS) / NS + 15) & ~15) : pos - ks0 + 1;
-  const int ks = ks0 + z * chunk;
-  const int ke = min(pos, ks + chunk - 1);          // inclusive; ks > ke: an empty piece
-  const int grp = tid >> 3, l8 = tid & 7;
-  const int s_first = ks + tid;
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
-  u32x4 kk0[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) kk0[i] = (s_first < pos && s_first <= ke) ? kc[(size_t)i * Smax + s_first] : zero4;
-  constexpr int VP = 2;      // value rows prefetched per lane before the scores (NG * VP = 128 keys, as in the fp32 form)
-  u32x4 vpre[VP];
-#pragma unroll
-  for (int j = 0; j < VP; ++j) {
-    const int sj = ks + grp + NG * j;
-    vpre[j] = (sj < pos && sj <= ke) ? vc[(size_t)sj * 8 + l8] : zero4;
-  }
-
-  // ---- q, k, v of the new token (waves 0,1,2 take q,k,v) ----
-  if (tid < 192) {
-    const int which = tid >> 6, dd = tid & 63;
-    const int col = which * d + h * 64 + dd;
-    const float* row = p.qkv_part + (size_t)b * 3 * d + col;
-    const size_t sst = (size_t)p.part_rows * 3 * d;
-    float acc = p.qkv_bias ? p.qkv_bias[col] : 0.0f;
-    for (int s = 0; s < p.parts; ++s) acc += row[(size_t)s * sst];
-    if (which == 0) qs[dd] = acc * p.scale;
-    else {
-      const unsigned bits = bf16_rne_bits(acc);
-      unsigned short* dst = which == 1 ? reinterpret_cast<unsigned short*>(kc + (size_t)(dd >> 3) * Smax + pos) + (dd & 7)
-                                       : reinterpret_cast<unsigned short*>(vc + (size_t)pos * 8) + dd;
-      (which == 1 ? knew : vnew)[dd] = __uint_as_float(bits << 16);
-      if (z == 0) *dst = (unsigned short)bits;
-    }
-  }
-  __syncthreads();
-
-  const float qlane = qs[lane];
-  float qv[64];
-#pragma unroll
-  for (int i = 0; i < 64; ++i) qv[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qlane), i));
-
-  auto dot_new = [&]() {
-    float dot = 0.f;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) dot += qv[i] * knew[i];
-    return dot;
-  };
-  auto dot_key = [&](const u32x4 (&kk)[8]) {
-    float dot = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        dot += qv[8 * i + 2 * j] * __uint_as_float(kk[i][j] << 16) + qv[8 * i + 2 * j + 1] * __uint_as_float(kk[i][j] & 0xffff0000u);
-    return dot;
-  };
-  // ---- scores: one key per thread and pass; the first pass consumes the prefetched key ----
-  float mx = -1e30f;
-  if (s_first <= ke) {
-    const float dot = s_first == pos ? dot_new() : dot_key(kk0);
+    const float dot = s_first == pos ? KV::dot_new(qv, knew) : KV::dot_key(qv, kk0);
     pr[s_first] = dot;
     mx = dot;
   }
   for (int s = s_first + NT; s <= ke; s += NT) {
     float dot;
-    if (s == pos) dot = dot_new();
+    if (s == pos) dot = KV::dot_new(qv, knew);
     else {
-      u32x4 kk[8];
+      G kk[KG];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) kk[i] = kc[(size_t)i * Smax + s];
-      dot = dot_key(kk);
+      for (int i = 0; i < KG; ++i) kk[i] = kc[(size_t)i * Smax + s];
+      dot = KV::dot_key(qv, kk);
     }
     pr[s] = dot;
     mx = fmaxf(mx, dot);
   }
+  // (the two softmax reductions: disjoint halves of `red`, one barrier each)
   mx = wave_max(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
@@ -371,61 +259,58 @@ __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(
     pr[s] = e;
     sum += e;
   }
-  sum = wave_add(sum);
+  sum = wave_sum(sum);
   if (lane == 0) red[NW + wave] = sum;
   __syncthreads();
   float l = 0.f;
 #pragma unroll
   for (int w = 0; w < NW; ++w) l += red[NW + w];
 
-  // ---- P.V : NG key groups x 8 lanes; a lane owns 8 head dims (one 16-byte load per key), 8 keys in flight per lane ----
-  float a0[8], a1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
-  auto fma8 = [&](float (&acc)[8], const float pw, const u32x4 v) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      acc[2 * j] += pw * __uint_as_float(v[j] << 16);
-      acc[2 * j + 1] += pw * __uint_as_float(v[j] & 0xffff0000u);
-    }
-  };
-  auto fma8_new = [&](float (&acc)[8], const float pw) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] += pw * vnew[8 * l8 + e];
-  };
+  // ---- P.V : NG key groups x LPR lanes; a lane owns the head dims of one granule (one 16-byte load per key, whole rows
+  //      coalesced), 8 keys in flight per lane; group g takes keys ks+g, ks+g+NG, ... ----
+  const typename KV::VNew vn = KV::vnew_of(vnew, lpr);
+  typename KV::Acc acc[NACC] = {};
 #pragma unroll
   for (int j = 0; j < VP; ++j) {
     const int sj = ks + grp + NG * j;
     if (sj <= ke) {
-      if (sj == pos) fma8_new((j & 1) ? a1 : a0, pr[sj]);
-      else fma8((j & 1) ? a1 : a0, pr[sj], vpre[j]);
+      if (sj == pos) KV::fma_new(acc[j % NACC], pr[sj], vn);
+      else KV::fma(acc[j % NACC], pr[sj], vpre[j]);
     }
   }
   for (int sb = ks + grp + VP * NG; sb <= ke; sb += 8 * NG) {
-    u32x4 v[8];
+    G v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int sj = sb + NG * j;
-      v[j] = (sj < pos && sj <= ke) ? vc[(size_t)sj * 8 + l8] : zero4;
+      v[j] = (sj < pos && sj <= ke) ? vc[(size_t)sj * LPR + lpr] : KV::zero();
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int sj = sb + NG * j;
       if (sj <= ke) {
-        if (sj == pos) fma8_new((j & 1) ? a1 : a0, pr[sj]);
-        else fma8((j & 1) ? a1 : a0, pr[sj], v[j]);
+        if (sj == pos) KV::fma_new(acc[j % NACC], pr[sj], vn);
+        else KV::fma(acc[j % NACC], pr[sj], v[j]);
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) outp[grp * 64 + 8 * l8 + e] = a0[e] + a1[e];
+  KV::store(&outp[grp * 64 + EPG * lpr], acc);
   __syncthreads();
   float o = 0.f;
   if (tid < 64) {
-#pragma unroll 16
+#pragma unroll KV::OUT_UNROLL
     for (int g = 0; g < NG; ++g) o += outp[g * 64 + tid];
   }
   decode_attn_finish(p, b, h, z, NS, tid, o, mx, l);
+}
+
+template <int NT, bool SLOTS>
+__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_kernel(const DecodeAttnArgs p) {
+  decode_attn_body<NT, SLOTS, KvF32>(p);
+}
+template <int NT, bool SLOTS>
+__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(const DecodeAttnArgs p) {
+  decode_attn_body<NT, SLOTS, KvBf16>(p);
 }
 
 int decode_attn_nsplit(int B, int H) {
@@ -459,7 +344,7 @@ int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// Row b of the greedy sampler (sample_greedy_kernel's reduction, for the session sampler below): logits (split-K partial sum + bias, optionally recorded) -> repetition penalty -> argmax, the first
+// Row b of the greedy samplers: logits (split-K partial sum + bias, optionally recorded) -> repetition penalty -> argmax, the first
 // maximum on ties.  The result is valid in thread 0 only (rv / ri: [16] of shared scratch).
 __device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int b, const int tid, float* rv, int* ri, float& best_out,
                                                   int& bidx_out) {
@@ -494,20 +379,23 @@ __device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int
       if (l > best) { best = l; bidx = v; }      // ascending v per thread: strict > keeps the first maximum
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off);
-    const int oi = __shfl_xor(bidx, off);
-    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
-  }
+  wave_argmax(best, bidx);
   if (lane == 0) { rv[wave] = best; ri[wave] = bidx; }
   __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 16; ++w)
-      if (rv[w] > best || (rv[w] == best && ri[w] < bidx)) { best = rv[w]; bidx = ri[w]; }
-  }
+  if (tid == 0) argmax_take_waves<16>(best, bidx, rv, ri);
   best_out = best;
   bidx_out = bidx;
+}
+
+// Row b's next input x = mel_emb[tok] + mel_pos[mel_pos], by all 1024 threads of a sampler's workgroup: A-fragment images for the
+// fp32-MFMA GEMV step (the folded LayerNorm's statistics are computed by the consumer), or a row + its statistics for the plane GEMV
+__device__ __forceinline__ void write_next_input(const SampleArgs& p, const int b, const int tok, const int mel_pos, const int tid) {
+  if (p.embed.x_frag) {
+    const int d = p.embed.d;
+    for (int e = tid; e < d; e += 1024) p.embed.x_frag[frag_index(b, e, d >> 4)] = p.embed.mel_emb[(size_t)tok * d + e] + p.embed.mel_pos[(size_t)mel_pos * d + e];
+  } else {
+    embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, tok, mel_pos, tid);
+  }
 }
 
 __global__ __launch_bounds__(1024) void sample_greedy_kernel(const SampleArgs p) {
@@ -516,66 +404,25 @@ __global__ __launch_bounds__(1024) void sample_greedy_kernel(const SampleArgs p)
   __shared__ int s_tok;
   const bool fused = p.embed.x_row || p.embed.x_frag;
   const int mp_next = fused ? p.st->mel_pos + 1 : 0;      // read before anybody can advance the state
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int V = p.V;
-  float best = -INFINITY;
-  int bidx = 0x7fffffff;
-  const unsigned char* seen = p.seen + (size_t)b * V;
-  const size_t sst = (size_t)p.part_rows * V;
-  const float* prow = p.part + (size_t)b * V;
-  for (int v0 = tid; v0 < V; v0 += 4096) {       // 4 vocabulary entries per trip, all their slab loads in flight together
-    float l4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = v0 + 1024 * u;
-      l4[u] = (v < V && p.bias) ? p.bias[v] : 0.0f;
-    }
-    for (int s = 0; s < p.parts; ++s) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int v = v0 + 1024 * u;
-        if (v < V) l4[u] += prow[(size_t)s * sst + v];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int v = v0 + 1024 * u;
-      if (v >= V) continue;
-      float l = l4[u];
-      if (p.logits_out) p.logits_out[(size_t)b * V + v] = l;
-      if (seen[v]) l = l < 0.f ? l * p.penalty : l / p.penalty;
-      if (l > best) { best = l; bidx = v; }      // ascending v per thread: strict > keeps the first maximum
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(best, off);
-    const int oi = __shfl_xor(bidx, off);
-    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
-  }
-  if (lane == 0) { rv[wave] = best; ri[wave] = bidx; }
-  __syncthreads();
+  const int b = blockIdx.x, tid = threadIdx.x;
+  float best;
+  int bidx;
+  greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
   if (tid == 0) {
-    for (int w = 1; w < 16; ++w)
-      if (rv[w] > best || (rv[w] == best && ri[w] < bidx)) { best = rv[w]; bidx = ri[w]; }
     int tok = p.finished[b] ? p.stop_token : bidx;      // finished rows emit pad (= eos = stop token)
     const int step = p.st->step;
     p.codes[(size_t)b * p.codes_ld + step] = tok;
     if (p.forced) tok = (int)p.forced[(size_t)b * p.forced_ld + step];      // teacher forcing: the given token continues the sequence
-    p.seen[(size_t)b * V + tok] = 1;
+    p.seen[(size_t)b * p.V + tok] = 1;
     if (tok == p.stop_token) p.finished[b] = 1;
     p.cur_tok[b] = tok;
     s_tok = tok;
   }
   if (!fused) return;
   __syncthreads();
-  if (p.embed.x_frag) {      // fp32-MFMA GEMV step: x as A-fragment images (the folded LayerNorm's statistics are computed by the consumer)
-    const int d = p.embed.d, tok = s_tok;
-    for (int e = tid; e < d; e += 1024) p.embed.x_frag[frag_index(b, e, d >> 4)] = p.embed.mel_emb[(size_t)tok * d + e] + p.embed.mel_pos[(size_t)mp_next * d + e];
-  } else {
-    embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, s_tok, mp_next, tid);
-  }
+  write_next_input(p, b, s_tok, mp_next, tid);
   __syncthreads();      // every read of the step scalars by this workgroup is behind us
+  // (not wg_arrive_last: this workgroup hands over no stores, so there is no wait in front and nothing to return behind)
   if (tid == 0) {
     DecodeState* st = p.embed.st_rw;
     const unsigned old = __hip_atomic_fetch_add(&st->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -616,12 +463,7 @@ __device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const 
     if (tid == 0) { ss->step += 1; ss->live = 0; }
     return;
   }
-  if (p.embed.x_frag) {
-    const int d = p.embed.d, tok = s_tok;
-    for (int e = tid; e < d; e += 1024) p.embed.x_frag[frag_index(b, e, d >> 4)] = p.embed.mel_emb[(size_t)tok * d + e] + p.embed.mel_pos[(size_t)s_mp * d + e];
-  } else {
-    embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, s_tok, s_mp, tid);
-  }
+  write_next_input(p, b, s_tok, s_mp, tid);
   if (tid == 0) { ss->pos += 1; ss->mel_pos += 1; ss->step += 1; }      // this slot's scalars: nobody else reads them in this launch
 }
 
@@ -651,26 +493,9 @@ int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_
 }
 
 // -------------------------------------------------------------------------------------------------
-// -------------------------------------------------------------------------------------------------
 // multinomial sampling with the HF warpers / the accel-engine sampler (SampleWarpArgs, decode.h)
 constexpr int SW_NPT = 16;          // vocabulary entries per thread: V <= 16384
 constexpr int SW_CAP = 2048;        // survivors of the top-k filter handled by the top-p stage (more only on massive ties)
-
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* rv, int* ri, int tid) {
-  // max value, smallest index on ties; result broadcast to every thread
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off);
-    const int oi = __shfl_xor(i, off);
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-  }
-  __syncthreads();
-  if ((tid & 63) == 0) { rv[tid >> 6] = v; ri[tid >> 6] = i; }
-  __syncthreads();
-  v = rv[0]; i = ri[0];
-  for (int w = 1; w < 16; ++w)
-    if (rv[w] > v || (rv[w] == v && ri[w] < i)) { v = rv[w]; i = ri[w]; }
-}
 
 // Row b of the warped sampler (parts = 1; the penalty in HF mode only): the token, valid in every thread.  The draw for id v is
 // exp1_draw(noise, seed, nbase + v).  rv / ri: [16], sval / sidx / sorted_v / sorted_i: [SW_CAP] of shared scratch.
@@ -705,17 +530,11 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
     float mx = -INFINITY; int mi = 0;
 #pragma unroll
     for (int u = 0; u < SW_NPT; ++u) if (sc[u] > mx) { mx = sc[u]; mi = tid + 1024 * u; }
-    block_argmax(mx, mi, rv, ri, tid);
+    block_argmax<16>(mx, mi, rv, ri, tid);
     float part = 0.f;
 #pragma unroll
     for (int u = 0; u < SW_NPT; ++u) if (tid + 1024 * u < V) part += expf(sc[u] - mx);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    __syncthreads();
-    if ((tid & 63) == 0) rv[tid >> 6] = part;
-    __syncthreads();
-    float tot = 0.f;
-    for (int w = 0; w < 16; ++w) tot += rv[w];
+    const float tot = block_sum<16>(part, rv);
     float best = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
     for (int u = 0; u < SW_NPT; ++u) {
@@ -725,7 +544,7 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
         if (r > best) { best = r; bi = v; }
       }
     }
-    block_argmax(best, bi, rv, ri, tid);
+    block_argmax<16>(best, bi, rv, ri, tid);
     token = bi;
   } else {
     // ---- top-k: the k-th largest value (with multiplicity) by k rounds of block-wide max extraction ----
@@ -739,7 +558,7 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
           const int v = tid + 1024 * u;
           if (v < V && !((taken >> u) & 1u) && (sc[u] > mx || (sc[u] == mx && v < mi))) { mx = sc[u]; mi = v; }
         }
-        block_argmax(mx, mi, rv, ri, tid);
+        block_argmax<16>(mx, mi, rv, ri, tid);
         kth = mx;
         if ((mi & 1023) == tid && mi < V) taken |= 1u << (mi >> 10);
       }
@@ -795,7 +614,7 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
       const float r = (expf(sorted_v[e] - mx) / s_sum) / draw(v);
       if (r > best || (r == best && v < bi)) { best = r; bi = v; }
     }
-    block_argmax(best, bi, rv, ri, tid);
+    block_argmax<16>(best, bi, rv, ri, tid);
     token = bi;
   }
   return token;

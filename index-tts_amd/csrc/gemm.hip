@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "device_util.h"
 #include "gemm_common.h"
 #include "prof.h"
 
@@ -208,8 +209,6 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
   if (p.sk_cnt) {
     // one K group per workgroup: the partial tile goes to the slab in register order (write-through 16-byte stores: [group][tile][16][256
     // threads]), the last workgroup of the tile to arrive adds the groups in order
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ int s_last;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.sk_slab, 0, p.sk_slab_bytes, 0x00020000);
     const int tile = bm * p.nblocks + bn, ntiles = p.mtiles * p.nblocks;
     const int part_stride = ntiles * 16 * 256 * 16;      // bytes between two groups
@@ -223,15 +222,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
           const f32x4 v = {tot[mt][nt][4 * r4], tot[mt][nt][4 * r4 + 1], tot[mt][nt][4 * r4 + 2], tot[mt][nt][4 * r4 + 3]};
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, mine + ((mt * 2 + nt) * 4 + r4) * 4096, (int)blockIdx.y * part_stride, 17);
         }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // acknowledged at the device coherence point before the arrival
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&p.sk_cnt[tile], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)p.ksplit - 1u;
-      if (s_last) __hip_atomic_store(&p.sk_cnt[tile], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!wg_arrive_last(&p.sk_cnt[tile], (unsigned)p.ksplit)) return;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll

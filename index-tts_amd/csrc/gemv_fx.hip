@@ -27,6 +27,7 @@
 
 #include <atomic>
 
+#include "device_util.h"
 #include "gemv16.h"
 #include "prof.h"
 
@@ -429,25 +430,13 @@ __global__ __launch_bounds__(UNS == 10 ? 512 : 1024) void gemv_fx_kernel(const G
     // K split across workgroups, finished by whichever of them arrives last (wait-free: nobody spins).  Partial sums travel
     // through agent-scope atomics (coherent across the XCDs' L2s); the sum runs in slab order, so the result does not depend
     // on who is last.
-    __shared__ int s_last;
     if (e_ok) {
       float v = 0.f;
       for (int w = 0; w < p.kw; ++w) v += redbuf[(w * NACC + e_t) * 256 + (tid & 255)];
       if (WT == WFMT_FP8) v *= e_s;
       __hip_atomic_store(&p.slab[((size_t)blockIdx.y * p.rows + e_row) * p.N + e_col], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // EVERY wave waits for the acknowledgement of its device-scope (sc1) stores before the workgroup barrier, so the arrival
-    // below is issued after all partial sums of this workgroup are at the device coherence point.  (An acq_rel arrival would
-    // say the same in the memory model, but costs an L2 write-back + invalidate per launch: measured +10 us.)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned old = __hip_atomic_fetch_add(&p.cnt[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = old == (unsigned)p.ksb - 1u;
-      if (s_last) __hip_atomic_store(&p.cnt[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!s_last || !e_ok) return;
+    if (!wg_arrive_last(&p.cnt[blockIdx.x], (unsigned)p.ksb) || !e_ok) return;
     float t[8];      // all partial sums in ONE round trip (a loop of atomic loads is issued one after the other)
 #pragma unroll
     for (int s = 0; s < 8; ++s)

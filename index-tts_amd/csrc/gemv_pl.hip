@@ -27,7 +27,6 @@
 namespace idxtts {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 int pack_gemv32(void* dst, const float* w, int N, int K, bool kn, int fmt, float* scale_out) {
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(512) void gemv_pl_kernel(const GemvPLP p) {
       for (int mt = 0; mt < MT; ++mt)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[mt]), rs, (tile * MT + mt) * 1024 + lane * 16, kp * part_stride, 17);      // sc0 sc1
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // acknowledged at the device coherence point before the arrival
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // wg_arrive_last (device_util.h) written out: a stamp sits in its middle, its flag in the dynamic LDS image
     PLS(7);
     __syncthreads();
     if (tid == 0) {

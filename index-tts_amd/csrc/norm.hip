@@ -13,24 +13,10 @@
 // bitwise reproducible: their K-slices are combined here, in the next kernel's prologue, in a fixed order.
 // Reductions: per-thread partial -> wave64 shuffle tree -> one LDS exchange between the 4 waves.
 #include "norm.h"
+#include "device_util.h"
 #include "prof.h"
 
 namespace idxtts {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threads
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();                 // protect `red` from the previous use
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 constexpr int NORM_MAX_PER_THREAD = 32;   // d <= 8192
 
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(256) void rows_norm_kernel(const RowsNormArgs p) {
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) ss += v[i] * v[i]; }
-    const float r = rsqrtf(block_sum(ss, red) * inv_d + p.eps);
+    const float r = rsqrtf(block_sum<4>(ss, red) * inv_d + p.eps);
     const float* wm = p.mod_a ? p.mod_a + (size_t)b * p.ld_mod : nullptr;
     const float* bm = p.mod_b ? p.mod_b + (size_t)b * p.ld_mod : nullptr;
 #pragma unroll
@@ -129,11 +115,11 @@ __global__ __launch_bounds__(256) void rows_norm_kernel(const RowsNormArgs p) {
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) s += v[i]; }
-  const float mean = block_sum(s, red) * inv_d;
+  const float mean = block_sum<4>(s, red) * inv_d;
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) { const float c = v[i] - mean; ss += c * c; } }
-  const float rstd = rsqrtf(block_sum(ss, red) * inv_d + p.eps);
+  const float rstd = rsqrtf(block_sum<4>(ss, red) * inv_d + p.eps);
   if (p.mode == NORM_MOD_LN) {
     const float* sh = p.mod_a + (size_t)b * p.ld_mod;   // shift
     const float* sc = p.mod_b + (size_t)b * p.ld_mod;   // scale
@@ -150,11 +136,11 @@ __global__ __launch_bounds__(256) void rows_norm_kernel(const RowsNormArgs p) {
     s = 0.f;
 #pragma unroll
     for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) s += v[i]; }
-    const float mean2 = block_sum(s, red) * inv_d;
+    const float mean2 = block_sum<4>(s, red) * inv_d;
     ss = 0.f;
 #pragma unroll
     for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) { const float c = v[i] - mean2; ss += c * c; } }
-    const float rstd2 = rsqrtf(block_sum(ss, red) * inv_d + p.eps2);
+    const float rstd2 = rsqrtf(block_sum<4>(ss, red) * inv_d + p.eps2);
 #pragma unroll
     for (int i = 0; i < nper; ++i) { const int e = tid + (i << 8); if (e < d) v[i] = (v[i] - mean2) * rstd2 * p.g2[e] + p.b2[e]; }
   }
@@ -188,8 +174,7 @@ __global__ __launch_bounds__(256) void ada_rms_planes512_kernel(const RowsNormAr
     const int r = wave * 4 + i, m = min(m0 + r, p.M - 1);
     const f32x4 a = xa[i], c = xb[i];
     float ss = a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3] + c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + c[3] * c[3];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
+    ss = wave_sum(ss);
     const float rs = rsqrtf(ss * (1.0f / 512.0f) + p.eps);
     f32x4 oa = {a[0] * rs * ga[0], a[1] * rs * ga[1], a[2] * rs * ga[2], a[3] * rs * ga[3]};
     f32x4 ob = {c[0] * rs * gb[0], c[1] * rs * gb[1], c[2] * rs * gb[2], c[3] * rs * gb[3]};

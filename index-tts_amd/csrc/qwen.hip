@@ -20,6 +20,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "device_util.h"
 #include "model_util.h"
 
 namespace idxtts {
@@ -29,35 +30,6 @@ namespace {
 constexpr int HD = 128;            // head_dim (the one instantiation)
 constexpr int GMAX = 4;            // q heads per kv head, at most
 constexpr int QWEN_HEAD_UPW = 8;   // row pairs per wave of the head GEMV (64 rows per workgroup)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// sum / max over the 256 threads of a workgroup in a fixed order; every thread gets the result.  red: 4 floats of LDS
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-__device__ __forceinline__ float bf16_widen(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
-__device__ __forceinline__ float load_w(const float* p) { return *p; }
-__device__ __forceinline__ float load_w(const unsigned short* p) { return bf16_widen(*p); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 enum { EPI_STORE = 0, EPI_RES = 1, EPI_SWIGLU = 2, EPI_HEAD = 3 };
@@ -85,7 +57,6 @@ template <int NCH> struct RowRaw<NCH, float> {
   }
   __device__ __forceinline__ float get(int j, int e) const { return v[j][e >> 2][e & 3]; }
 };
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <int NCH> struct RowRaw<NCH, unsigned short> {
   u32x4 v[NCH];
   __device__ __forceinline__ void load(const unsigned short* row, const int (&koff)[NCH]) {
@@ -124,7 +95,7 @@ __global__ __launch_bounds__(256) void qwen_gemv_kernel(const QwenGemvArgs p) {
     ss = fmaf(v, v, ss);
   }
   if (p.g) {
-    const float tot = block_sum(ss, red);
+    const float tot = block_sum<4>(ss, red);
     const float rs = 1.0f / sqrtf(tot / (float)K + p.eps);
     for (int k = tid; k < K; k += 256) xs[k] = (xs[k] * rs) * p.g[k];
   }
@@ -178,11 +149,11 @@ __global__ __launch_bounds__(256) void qwen_gemv_kernel(const QwenGemvArgs p) {
   __syncthreads();
   if (tid == 0) {
     float bv = s_val[0]; int bi = s_idx[0];
-    for (int w = 1; w < 4; ++w)
-      if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+    argmax_take_waves<4>(bv, bi, s_val, s_idx);
     __hip_atomic_store(&p.part_val[blockIdx.x], bv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&p.part_idx[blockIdx.x], bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // device-scope stores acknowledged before the arrival
+    // wg_arrive_last (device_util.h) by thread 0 alone, the only one that stored: one barrier behind it, none in front
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned old = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_last = old == gridDim.x - 1u;
     if (s_last) __hip_atomic_store(p.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -193,23 +164,10 @@ __global__ __launch_bounds__(256) void qwen_gemv_kernel(const QwenGemvArgs p) {
   for (int b = tid; b < (int)gridDim.x; b += 256) {
     const float v = __hip_atomic_load(&p.part_val[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int ix = __hip_atomic_load(&p.part_idx[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
+    argmax_take(bv, bi, v, ix);
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  __syncthreads();
-  if (lane == 0) { s_val[wave] = bv; s_idx[wave] = bi; }
-  __syncthreads();
-  if (tid == 0) {
-    bv = s_val[0]; bi = s_idx[0];
-    for (int w = 1; w < 4; ++w)
-      if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
-    p.st->argmax = bi;
-  }
+  block_argmax<4>(bv, bi, s_val, s_idx, tid);
+  if (tid == 0) p.st->argmax = bi;
 }
 
 template <int EPI, typename WT>
@@ -273,7 +231,6 @@ __global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
   __shared__ float vn[HD];
   __shared__ float acc2[GMAX][HD];
   __shared__ float red[4];
-  __shared__ int s_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int kvh = blockIdx.x, z = blockIdx.y, r = blockIdx.z, G = p.G;
   const int pos = p.st ? p.st->pos : p.pos0 + r;
@@ -349,7 +306,7 @@ __global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
     }
 #pragma unroll
     for (int g = 0; g < GMAX; ++g)
-      if (g < G) mx[g] = block_max(mx[g], red);
+      if (g < G) mx[g] = block_max<4>(mx[g], red);
     for (int j = j0 + tid; j < j1; j += 256) {
 #pragma unroll
       for (int g = 0; g < GMAX; ++g)
@@ -361,7 +318,7 @@ __global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
     }
 #pragma unroll
     for (int g = 0; g < GMAX; ++g)
-      if (g < G) l[g] = block_sum(l[g], red);      // (its barriers also publish the probabilities)
+      if (g < G) l[g] = block_sum<4>(l[g], red);      // (its barriers also publish the probabilities)
     // ---- pass 2: probabilities x values, threads = (feature, key parity) ----
     const int d = tid & 127, half = tid >> 7;
     for (int j = j0 + half; j < j1; j += 2) {
@@ -404,15 +361,7 @@ __global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
         }
       }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = __hip_atomic_fetch_add(&p.cnt[kvh], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == (unsigned)NS - 1u;
-    if (s_last) __hip_atomic_store(&p.cnt[kvh], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last || tid >= 128) return;
+  if (!wg_arrive_last(&p.cnt[kvh], (unsigned)NS) || tid >= 128) return;
   for (int g = 0; g < G; ++g) {
     const float* all = p.part + (size_t)(kvh * G + g) * NS * 130;
     float M = -INFINITY;
@@ -493,7 +442,7 @@ __global__ __launch_bounds__(256) void qwen_rmsnorm_rows_kernel(const float* x, 
   const float* xr = x + (size_t)blockIdx.x * H;
   float ss = 0.0f;
   for (int k = threadIdx.x; k < H; k += 256) ss = fmaf(xr[k], xr[k], ss);
-  const float rs = 1.0f / sqrtf(block_sum(ss, red) / (float)H + eps);
+  const float rs = 1.0f / sqrtf(block_sum<4>(ss, red) / (float)H + eps);
   for (int k = threadIdx.x; k < H; k += 256) y[(size_t)blockIdx.x * H + k] = (xr[k] * rs) * g[k];
 }
 

@@ -1,4 +1,5 @@
 // Small HBM-bound element-wise kernels of the s2mel stage (everything GEMM-shaped is in gemm.hip).
+#include "device_util.h"
 #include "prof.h"
 #include "s2mel_ops.h"
 
@@ -184,12 +185,6 @@ int cfm_rows_emit(float* out, const float* x, const int* prompt_len, const int* 
 }
 
 // ---- GroupNorm(1) + Mish over token-major [B][T][C] with per-sequence valid length ----
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 __global__ __launch_bounds__(1024) void gn_stats_kernel(const float* x, const int* row_len, int T, int C, float* stats) {
   // one 1024-thread workgroup per sequence: mean, then centred variance (two passes, as torch)
   __shared__ float red[16];
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(1024) void gn_stats_kernel(const float* x, const in
   const float* xb = x + (size_t)b * T * C;
   float s = 0.f;
   for (size_t i = tid; i < n; i += 1024) s += xb[i];
-  s = wsum(s);
+  s = wave_sum(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) { float a = 0.f; for (int i = 0; i < 16; ++i) a += red[i]; bc = n ? a / (float)n : 0.f; }
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(1024) void gn_stats_kernel(const float* x, const in
   const float mean = bc;
   float ss = 0.f;
   for (size_t i = tid; i < n; i += 1024) { const float c = xb[i] - mean; ss += c * c; }
-  ss = wsum(ss);
+  ss = wave_sum(ss);
   __syncthreads();
   if ((tid & 63) == 0) red[tid >> 6] = ss;
   __syncthreads();

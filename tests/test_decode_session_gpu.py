@@ -180,6 +180,23 @@ def test_full_width_bf16_session(device):
         assert np.array_equal(out[i][0], ref), i
 
 
+@pytest.mark.parametrize("kv", ["f32", "bf16"])
+def test_unsplit_attention_session(device, kv):
+    """33 slots x 4 heads = 132 attention workgroups, past the 128 up to which the decode attention splits a row's keys over several
+    workgroups: every key range here is ONE piece, in both cache formats (the sessions above, 4 or 20 slots x 2 heads, split theirs).
+    Prompts of about 40 rows run to caps of up to 24 codes, so a key range crosses a 16-key boundary; most slots stay dead."""
+    import dataclasses
+    cfg = dataclasses.replace(GPTConfig.tiny(), model_dim=256, heads=4)
+    uv, _ = _model(device, cfg, "t/sess/unsplit", kv_format=kv, stop_bias=-1e4)      # no stop token: every row runs to its cap
+    slots = 33
+    reqs = _requests(uv, cfg, "t/sess/unsplit", 3, [33, 30, 35], [24, 17, 24])
+    sess = uv.decode_session(slots, max_prompt=max(r["row"].shape[0] for r in reqs), max_new=24)
+    out = _run(sess, reqs, seed=5, max_admit=2)
+    sess.close()
+    assert sorted(out) == [0, 1, 2]
+    _check(uv, reqs, out, slots, cfg.stop_mel_token)
+
+
 def test_session_refuses_sampling_and_beams(device):
     cfg = GPTConfig.tiny()
     uv, _ = _model(device, cfg, "t/sess/refuse")
