@@ -500,7 +500,7 @@ int idxtts_s2mel_estimator(idxtts_ctx* ctx, const float* x, const float* prompt,
                            const float* t_emb, const float* style, const float* mu, float* out, int B, int T, void* workspace,
                            size_t workspace_bytes, void* stream);
 
-/* ---- emotion-from-text classifier: Qwen3 causal LM, B = 1 greedy generation (reference: QwenEmotion.inference, infer_v2.py:948-1063:
+/* ---- emotion-from-text classifier: Qwen3 causal LM, greedy generation for one prompt or a batch (reference: QwenEmotion.inference, infer_v2.py:948-1063:
  * AutoModelForCausalLM.from_pretrained(qwen_emo_path) + model.generate(max_new_tokens=32768) on a two-message chat prompt; third-party
  * model: transformers' Qwen3ForCausalLM) --------------------------------------------------------------------------------------
  * State-dict keys: the HF checkpoint's own -- "model.embed_tokens.weight", "model.layers.{i}.self_attn.{q,k,v,o}_proj.weight",
@@ -541,6 +541,29 @@ int idxtts_qwen_generate(idxtts_ctx* ctx, const int* prompt_ids, int n_prompt, i
                          void* stream);
 /* Kernel launches in the kept decode-step graph (5 per layer + 2, + 1 with out_logits); -1 when no graph is held. */
 int idxtts_qwen_step_graph_launches(const idxtts_ctx* ctx);
+/* ---- batched generation: several prompts share every weight pass of a decode step (replaces B calls of idxtts_qwen_generate in series;
+ * reference: QwenEmotion.inference once per text, infer_v2.py:1013-1063).  Row b of a batched call equals
+ * idxtts_qwen_generate(prompt b, max_new_tokens[b], ...) bit for bit: ids, stop step and every logit, in both storage formats, eager or
+ * replayed.  Rows the library passes through the weights together (replaces the fixed B = 1): a call with more rows is served in
+ * consecutive tiles of this many inside the library. */
+int idxtts_qwen_max_batch(const idxtts_ctx* ctx);
+/* Workspace for a batched call (replaces idxtts_qwen_workspace_bytes; n_prompt, max_new_tokens: HOST int32 [B]); 0 on a bad shape
+ * (B < 1, a null array, a length < 1). */
+size_t idxtts_qwen_batch_workspace_bytes(const idxtts_ctx* ctx, int B, const int* n_prompt, const int* max_new_tokens, int n_eos,
+                                         int n_logit_cols /* 0 without out_logits; vocab_size for all columns */);
+/* idxtts_qwen_generate for B prompts (replaces B calls in series): prompt_ids HOST int32, the rows concatenated (n_prompt[b] each);
+ * forced_ids / out_ids HOST int32, the rows concatenated by max_new_tokens[b]; n_out HOST int32 [B].  Every row stops at its own end id
+ * (one of eos_ids, shared by the rows) or its own max_new_tokens[b].  out_logits (DEVICE fp32, or NULL): row b's steps start at row
+ * (sum of max_new_tokens[0..b-1]) of a [sum max_new_tokens][n] matrix; rows of steps a row did not run are left untouched.
+ * logit_cols / n_logit_cols / use_graph / stream: as idxtts_qwen_generate; the kept batched step graph is separate from the single one
+ * and is reused by the next call with the same lengths on the same workspace.  Nothing runs when a row fails a check. */
+int idxtts_qwen_generate_batch(idxtts_ctx* ctx, int B, const int* prompt_ids, const int* n_prompt, const int* max_new_tokens,
+                               const int* eos_ids, int n_eos, const int* forced_ids /* may be NULL */, int* out_ids, int* n_out,
+                               float* out_logits /* may be NULL */, const int* logit_cols /* may be NULL */, int n_logit_cols,
+                               void* workspace, size_t bytes, int use_graph, void* stream);
+/* Kernel launches in the kept batched decode-step graph (replaces idxtts_qwen_step_graph_launches: the same 5 per layer + 2, + 1 with
+ * out_logits, whatever the rows); -1 when no graph is held.  A tile of one row runs idxtts_qwen_generate's path and its graph, not this one. */
+int idxtts_qwen_batch_step_graph_launches(const idxtts_ctx* ctx);
 
 /* ---- per-kernel timing for the benchmark's roofline report ------------------------------------------
  * When enabled, every kernel launch is bracketed by HIP events on its own stream and the library

@@ -27,147 +27,13 @@ namespace idxtts {
 
 namespace {
 
-constexpr int HD = 128;            // head_dim (the one instantiation)
-constexpr int GMAX = 4;            // q heads per kv head, at most
-constexpr int QWEN_HEAD_UPW = 8;   // row pairs per wave of the head GEMV (64 rows per workgroup)
+constexpr int HD = QWEN_HD, GMAX = QWEN_GMAX;      // the shared device code and its argument structs: qwen.h
 
 // ---------------------------------------------------------------------------------------------------------------------------
-enum { EPI_STORE = 0, EPI_RES = 1, EPI_SWIGLU = 2, EPI_HEAD = 3 };
-
-struct QwenGemvArgs {
-  const void* wa = nullptr;      // [N][K]; EPI_SWIGLU: gate_proj
-  const void* wb = nullptr;      // EPI_SWIGLU: up_proj
-  int K = 0, units = 0, upw = 1; // units: rows (EPI_RES), row pairs (EPI_STORE / EPI_HEAD), (gate, up) pairs (EPI_SWIGLU); per wave
-  const float* x = nullptr;      // [K]
-  const float* g = nullptr;      // RMSNorm gain [K], or null: x as it is
-  float eps = 0.0f;
-  float* y = nullptr;            // [N] (EPI_RES: y[n] += ...; EPI_SWIGLU: [units]; EPI_HEAD: the logits)
-  float* part_val = nullptr; int* part_idx = nullptr; unsigned* cnt = nullptr; QwenState* st = nullptr;   // EPI_HEAD
-};
-
-template <int NCH, typename WT> struct RowRaw;
-template <int NCH> struct RowRaw<NCH, float> {
-  f32x4 v[NCH][2];
-  __device__ __forceinline__ void load(const float* row, const int (&koff)[NCH]) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      v[j][0] = *reinterpret_cast<const f32x4*>(row + koff[j]);
-      v[j][1] = *reinterpret_cast<const f32x4*>(row + koff[j] + 4);
-    }
-  }
-  __device__ __forceinline__ float get(int j, int e) const { return v[j][e >> 2][e & 3]; }
-};
-template <int NCH> struct RowRaw<NCH, unsigned short> {
-  u32x4 v[NCH];
-  __device__ __forceinline__ void load(const unsigned short* row, const int (&koff)[NCH]) {
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) v[j] = *reinterpret_cast<const u32x4*>(row + koff[j]);
-  }
-  __device__ __forceinline__ float get(int j, int e) const {
-    const unsigned w = v[j][e >> 1];
-    return __builtin_bit_cast(float, (e & 1) ? (w & 0xffff0000u) : (w << 16));
-  }
-};
-template <int NCH, typename WT>
-__device__ __forceinline__ float row_dot(const RowRaw<NCH, WT>& r, const float (&xr)[NCH][8]) {
-  float acc = 0.0f;
-#pragma unroll
-  for (int j = 0; j < NCH; ++j)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc = fmaf(r.get(j, e), xr[j][e], acc);
-  return wave_sum(acc);
-}
-
 template <int NCH, int EPI, typename WT>
 __global__ __launch_bounds__(256) void qwen_gemv_kernel(const QwenGemvArgs p) {
   __shared__ float xs[NCH * 512];
-  __shared__ float red[4];
-  __shared__ float s_val[4];
-  __shared__ int s_idx[4];
-  __shared__ int s_last;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int K = p.K;
-  // ---- prologue: the activation vector, RMS-normed when a gain is given ----
-  float ss = 0.0f;
-  for (int k = tid; k < NCH * 512; k += 256) {
-    const float v = k < K ? p.x[k] : 0.0f;
-    xs[k] = v;
-    ss = fmaf(v, v, ss);
-  }
-  if (p.g) {
-    const float tot = block_sum<4>(ss, red);
-    const float rs = 1.0f / sqrtf(tot / (float)K + p.eps);
-    for (int k = tid; k < K; k += 256) xs[k] = (xs[k] * rs) * p.g[k];
-  }
-  __syncthreads();
-  float xr[NCH][8];
-  int koff[NCH];
-#pragma unroll
-  for (int j = 0; j < NCH; ++j) {
-    const int k0 = j * 512 + 8 * lane;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) xr[j][e] = xs[k0 + e];
-    koff[j] = min(k0, K - 8);      // past K: a valid address whose weights meet zeros of x
-  }
-  const WT* wa = static_cast<const WT*>(p.wa);
-  const WT* wb = static_cast<const WT*>(p.wb);
-  float best = -INFINITY;
-  int best_i = 0x7fffffff;
-  const int u0 = (blockIdx.x * 4 + wave) * p.upw;
-  for (int i = 0; i < p.upw; ++i) {
-    const int u = u0 + i;
-    if (u >= p.units) break;      // the whole wave
-    if (EPI == EPI_RES) {
-      RowRaw<NCH, WT> a;
-      a.load(wa + (size_t)u * K, koff);
-      const float s = row_dot(a, xr);
-      if (lane == 0) p.y[u] += s;
-    } else {
-      RowRaw<NCH, WT> a, b;
-      if (EPI == EPI_SWIGLU) {
-        a.load(wa + (size_t)u * K, koff);
-        b.load(wb + (size_t)u * K, koff);
-      } else {
-        a.load(wa + (size_t)(2 * u) * K, koff);
-        b.load(wa + (size_t)(2 * u + 1) * K, koff);
-      }
-      const float s0 = row_dot(a, xr), s1 = row_dot(b, xr);
-      if (EPI == EPI_SWIGLU) {
-        if (lane == 0) p.y[u] = (s0 / (1.0f + expf(-s0))) * s1;
-      } else {
-        if (lane == 0) { p.y[2 * u] = s0; p.y[2 * u + 1] = s1; }
-        if (EPI == EPI_HEAD) {      // rows ascend within a wave: a strict > keeps the lowest index among equals
-          if (s0 > best) { best = s0; best_i = 2 * u; }
-          if (s1 > best) { best = s1; best_i = 2 * u + 1; }
-        }
-      }
-    }
-  }
-  if (EPI != EPI_HEAD) return;
-  // ---- argmax, stage 1: this workgroup's best; stage 2: the last workgroup to arrive reduces every workgroup's ----
-  if (lane == 0) { s_val[wave] = best; s_idx[wave] = best_i; }
-  __syncthreads();
-  if (tid == 0) {
-    float bv = s_val[0]; int bi = s_idx[0];
-    argmax_take_waves<4>(bv, bi, s_val, s_idx);
-    __hip_atomic_store(&p.part_val[blockIdx.x], bv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&p.part_idx[blockIdx.x], bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // wg_arrive_last (device_util.h) by thread 0 alone, the only one that stored: one barrier behind it, none in front
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned old = __hip_atomic_fetch_add(p.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == gridDim.x - 1u;
-    if (s_last) __hip_atomic_store(p.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  float bv = -INFINITY; int bi = 0x7fffffff;
-  for (int b = tid; b < (int)gridDim.x; b += 256) {
-    const float v = __hip_atomic_load(&p.part_val[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int ix = __hip_atomic_load(&p.part_idx[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    argmax_take(bv, bi, v, ix);
-  }
-  block_argmax<4>(bv, bi, s_val, s_idx, tid);
-  if (tid == 0) p.st->argmax = bi;
+  qwen_gemv_body<NCH, EPI, WT, 1>(p, xs, 1, 0, 0);
 }
 
 template <int EPI, typename WT>
@@ -194,189 +60,11 @@ int qwen_gemv(const QwenGemvArgs& a, int fmt, int rows, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// One workgroup per (kv head, key piece, query): the G q heads of the group against the piece's keys.  q (and, when APPEND, the new
-// k) get their per-head RMSNorm and rotary here; APPEND also writes the new k / v to the cache (piece 0) and every piece takes them
-// from LDS, so no workgroup waits for another's store.  Pass 1: threads = keys; pass 2: threads = (output feature, key parity).
-struct QwenAttnArgs {
-  const float* qkv = nullptr; int ld_qkv = 0;      // per query row [q: Hq*128 | k: Hkv*128 | v: Hkv*128]
-  const float *qn_g = nullptr, *kn_g = nullptr; float eps = 0.0f;
-  const float* rope = nullptr;                     // [pos][64][2]
-  float *kc = nullptr, *vc = nullptr; int Smax = 0; // this layer's [Hkv][Smax][128]
-  int Hq = 0, Hkv = 0, G = 0;
-  float* out = nullptr; int ld_out = 0;            // per query row [Hq*128]
-  const QwenState* st = nullptr; int pos0 = 0;     // query row r sits at position (st ? st->pos : pos0 + r)
-  int nsplit = 1, slice_cap = 0;
-  float* part = nullptr; unsigned* cnt = nullptr;  // [Hq][nsplit][130], [Hkv]
-  float scale = 0.0f;
-};
-
-// RMSNorm over the head + rotary of one 128-vector by one wave: the lane holds elements lane and lane + 64, a rotary pair
-// (rotate_half: out[i] = x[i] cos - x[i + 64] sin, out[i + 64] = x[i + 64] cos + x[i] sin, products rounded before the sum as the
-// reference's element-wise ops are)
-__device__ __forceinline__ void head_norm_rope(const float* v, const float* g, float eps, const float* rope_pos, int lane, float* o0, float* o1) {
-  const float a = v[lane], b = v[lane + 64];
-  const float ss = wave_sum(fmaf(a, a, b * b));
-  const float rs = 1.0f / sqrtf(ss / (float)HD + eps);
-  const float na = (a * rs) * g[lane], nb = (b * rs) * g[lane + 64];
-  const float c = rope_pos[2 * lane], s = rope_pos[2 * lane + 1];
-  *o0 = __fadd_rn(__fmul_rn(na, c), __fmul_rn(-nb, s));
-  *o1 = __fadd_rn(__fmul_rn(nb, c), __fmul_rn(na, s));
-}
-
+// One workgroup per (kv head, key piece, query): qwen_attn_body (qwen.h)
 template <bool APPEND>
 __global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
-  extern __shared__ float sc[];      // [G][slice_cap]
-  __shared__ __attribute__((aligned(16))) float qs[GMAX][HD];
-  __shared__ __attribute__((aligned(16))) float kn[HD];
-  __shared__ float vn[HD];
-  __shared__ float acc2[GMAX][HD];
-  __shared__ float red[4];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int kvh = blockIdx.x, z = blockIdx.y, r = blockIdx.z, G = p.G;
-  const int pos = p.st ? p.st->pos : p.pos0 + r;
-  const float* row = p.qkv + (size_t)r * p.ld_qkv;
-  const float* rope_pos = p.rope + (size_t)pos * HD;
-  const int qdim = p.Hq * HD, kvdim = p.Hkv * HD;
-  for (int item = wave; item < G + (APPEND ? 2 : 0); item += 4) {
-    if (item < G) {
-      float o0, o1;
-      head_norm_rope(row + (kvh * G + item) * HD, p.qn_g, p.eps, rope_pos, lane, &o0, &o1);
-      qs[item][lane] = o0; qs[item][lane + 64] = o1;
-    } else if (item == G) {
-      float o0, o1;
-      head_norm_rope(row + qdim + kvh * HD, p.kn_g, p.eps, rope_pos, lane, &o0, &o1);
-      kn[lane] = o0; kn[lane + 64] = o1;
-      if (z == 0) {
-        float* kd = p.kc + ((size_t)kvh * p.Smax + pos) * HD;
-        kd[lane] = o0; kd[lane + 64] = o1;
-      }
-    } else {
-      const float* vs = row + qdim + kvdim + kvh * HD;
-      const float a = vs[lane], b = vs[lane + 64];
-      vn[lane] = a; vn[lane + 64] = b;
-      if (z == 0) {
-        float* vd = p.vc + ((size_t)kvh * p.Smax + pos) * HD;
-        vd[lane] = a; vd[lane + 64] = b;
-      }
-    }
-  }
-  __syncthreads();
-  const int n_keys = pos + 1;
-  const int slice = (n_keys + p.nsplit - 1) / p.nsplit;
-  const int j0 = z * slice, j1 = min(n_keys, j0 + slice);
-  const int cap = p.slice_cap;
-  float mx[GMAX], l[GMAX], o[GMAX];
-#pragma unroll
-  for (int g = 0; g < GMAX; ++g) { mx[g] = -INFINITY; l[g] = 0.0f; o[g] = 0.0f; }
-  if (j0 < j1) {
-    // ---- pass 1: scores, threads = keys ----
-    for (int j = j0 + tid; j < j1; j += 256) {
-      float s[GMAX];
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g) s[g] = 0.0f;
-      if (APPEND && j == pos) {
-        for (int e = 0; e < HD; e += 4) {
-          const f32x4 kv = *reinterpret_cast<const f32x4*>(kn + e);
-#pragma unroll
-          for (int g = 0; g < GMAX; ++g)
-            if (g < G) {
-              const f32x4 qq = *reinterpret_cast<const f32x4*>(&qs[g][e]);
-              s[g] = fmaf(qq[0], kv[0], s[g]); s[g] = fmaf(qq[1], kv[1], s[g]); s[g] = fmaf(qq[2], kv[2], s[g]); s[g] = fmaf(qq[3], kv[3], s[g]);
-            }
-        }
-      } else {
-        const f32x4* kr = reinterpret_cast<const f32x4*>(p.kc + ((size_t)kvh * p.Smax + j) * HD);
-        for (int e = 0; e < HD / 4; ++e) {
-          const f32x4 kv = kr[e];
-#pragma unroll
-          for (int g = 0; g < GMAX; ++g)
-            if (g < G) {
-              const f32x4 qq = *reinterpret_cast<const f32x4*>(&qs[g][4 * e]);
-              s[g] = fmaf(qq[0], kv[0], s[g]); s[g] = fmaf(qq[1], kv[1], s[g]); s[g] = fmaf(qq[2], kv[2], s[g]); s[g] = fmaf(qq[3], kv[3], s[g]);
-            }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) {
-          const float v = s[g] * p.scale;
-          sc[g * cap + (j - j0)] = v;
-          mx[g] = fmaxf(mx[g], v);
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g)
-      if (g < G) mx[g] = block_max<4>(mx[g], red);
-    for (int j = j0 + tid; j < j1; j += 256) {
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) {
-          const float e = expf(sc[g * cap + (j - j0)] - mx[g]);
-          sc[g * cap + (j - j0)] = e;
-          l[g] += e;
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g)
-      if (g < G) l[g] = block_sum<4>(l[g], red);      // (its barriers also publish the probabilities)
-    // ---- pass 2: probabilities x values, threads = (feature, key parity) ----
-    const int d = tid & 127, half = tid >> 7;
-    for (int j = j0 + half; j < j1; j += 2) {
-      const float v = (APPEND && j == pos) ? vn[d] : p.vc[((size_t)kvh * p.Smax + j) * HD + d];
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) o[g] = fmaf(sc[g * cap + (j - j0)], v, o[g]);
-    }
-    if (half == 1) {
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) acc2[g][d] = o[g];
-    }
-    __syncthreads();
-    if (half == 0) {
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) o[g] += acc2[g][d];
-    }
-  }
-  float* out = p.out + (size_t)r * p.ld_out;
-  if (p.nsplit == 1) {
-    if (tid < 128)
-#pragma unroll
-      for (int g = 0; g < GMAX; ++g)
-        if (g < G) out[(kvh * G + g) * HD + tid] = o[g] / l[g];
-    return;
-  }
-  // ---- key split: leave (o, max, sum) of this piece; the last piece of the kv head to arrive merges them in piece order ----
-  const int NS = p.nsplit;
-  if (tid < 128) {
-#pragma unroll
-    for (int g = 0; g < GMAX; ++g)
-      if (g < G) {
-        float* mine = p.part + ((size_t)(kvh * G + g) * NS + z) * 130;
-        __hip_atomic_store(&mine[tid], o[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid == 0) {
-          __hip_atomic_store(&mine[128], mx[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(&mine[129], l[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-  }
-  if (!wg_arrive_last(&p.cnt[kvh], (unsigned)NS) || tid >= 128) return;
-  for (int g = 0; g < G; ++g) {
-    const float* all = p.part + (size_t)(kvh * G + g) * NS * 130;
-    float M = -INFINITY;
-    for (int i = 0; i < NS; ++i) M = fmaxf(M, __hip_atomic_load(&all[i * 130 + 128], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    float L = 0.0f, O = 0.0f;
-    for (int i = 0; i < NS; ++i) {
-      const float mi = __hip_atomic_load(&all[i * 130 + 128], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float li = __hip_atomic_load(&all[i * 130 + 129], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float oi = __hip_atomic_load(&all[i * 130 + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float w = li > 0.0f ? expf(mi - M) : 0.0f;      // an empty piece (more pieces than keys) carries nothing
-      L = fmaf(li, w, L);
-      O = fmaf(oi, w, O);
-    }
-    out[(kvh * G + g) * HD + tid] = O / L;
-  }
+  const int r = blockIdx.z;
+  qwen_attn_body<APPEND>(p, blockIdx.x, blockIdx.y, r, p.st ? p.st->pos : p.pos0 + r);
 }
 
 int qwen_attn(const QwenAttnArgs& a, int rows, bool append, int keys_hint, hipStream_t st) {
@@ -394,39 +82,13 @@ int qwen_attn(const QwenAttnArgs& a, int rows, bool append, int keys_hint, hipSt
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// The step's last launch (one workgroup): record the head's choice, pick what continues the sequence (the forced id, or the choice),
-// stop on an end id or at the cap, write the next input's embedding row and advance the step scalars.
-struct QwenTailArgs {
-  QwenState* st; int* out_ids; const int* forced; const int* eos; int n_eos, max_new;
-  const void* emb; int H, V; float* xd;
-};
+// The step's last launch (one workgroup): qwen_tail_row (qwen.h)
 template <typename WT>
-__global__ __launch_bounds__(256) void qwen_tail_kernel(const QwenTailArgs p) {
-  const QwenState s = *p.st;
-  const bool live = !s.done && s.step < p.max_new;
-  int next = s.argmax;
-  if (live && p.forced) next = p.forced[s.step];
-  next = min(max(next, 0), p.V - 1);
-  bool stop = false;
-  for (int i = 0; i < p.n_eos; ++i) stop |= next == p.eos[i];
-  const WT* er = static_cast<const WT*>(p.emb) + (size_t)next * p.H;
-  for (int k = threadIdx.x; k < p.H; k += 256) p.xd[k] = load_w(er + k);
-  __syncthreads();      // every thread has read the step scalars
-  if (threadIdx.x == 0 && live) {
-    p.out_ids[s.step] = s.argmax;
-    p.st->n_out = s.step + 1;
-    p.st->step = s.step + 1;
-    if (stop || s.step + 1 >= p.max_new) p.st->done = 1;
-    else p.st->pos = s.pos + 1;
-  }
-}
+__global__ __launch_bounds__(256) void qwen_tail_kernel(const QwenTailArgs p) { qwen_tail_row<WT>(p); }
 
 // out_logits[step][c] = logits[cols[c]] (cols null: column c) of a live step
 __global__ __launch_bounds__(256) void qwen_logits_kernel(const QwenState* st, const float* logits, const int* cols, int n_cols, int max_new, float* out) {
-  const QwenState s = *st;
-  if (s.done || s.step >= max_new) return;
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c < n_cols) out[(size_t)s.step * n_cols + c] = logits[cols ? cols[c] : c];
+  qwen_logits_row(st, logits, cols, n_cols, max_new, out, blockIdx.x * 256 + threadIdx.x);
 }
 
 // ---- prefill helpers (once per call, not tuned) ----
@@ -468,7 +130,7 @@ __global__ __launch_bounds__(256) void qwen_silu_mul_kernel(const float* gu, flo
   }
 }
 
-int nsplit_for(int Smax) { return std::min(16, std::max(1, cdiv(Smax, 64))); }
+int nsplit_for(int Smax) { return qwen_nsplit_for(Smax); }
 
 const char* const LAYER_KEYS[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                                   "self_attn.q_norm.weight", "self_attn.k_norm.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
@@ -480,6 +142,7 @@ const char* const INV_FREQ_KEY = "model.rotary_emb.inv_freq";
 // ---------------------------------------------------------------------------------------------------------------------------
 QwenModel::~QwenModel() {
   drop_graph();
+  drop_batch_graph();
   if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
@@ -616,7 +279,8 @@ int QwenModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena
       tab[((size_t)pos * (HD / 2) + i) * 2] = (float)std::cos((double)ang);
       tab[((size_t)pos * (HD / 2) + i) * 2 + 1] = (float)std::sin((double)ang);
     }
-  return up(arena, tab, &rope);
+  if (up(arena, tab, &rope)) return 1;
+  return batch_prepare();
 }
 
 QwenModel::Buffers QwenModel::carve(void* ws, int P, int max_new, int n_eos, int n_cols) const {

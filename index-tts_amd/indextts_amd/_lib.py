@@ -35,7 +35,8 @@ SYMBOLS = [
     "idxtts_melspec_create", "idxtts_melspec_frames", "idxtts_melspec_workspace_bytes", "idxtts_melspec_forward",
     "idxtts_campplus_create", "idxtts_campplus_workspace_bytes", "idxtts_campplus_forward",
     "idxtts_qwen_create", "idxtts_qwen_set_weight_format", "idxtts_qwen_workspace_bytes", "idxtts_qwen_generate",
-    "idxtts_qwen_step_graph_launches",
+    "idxtts_qwen_step_graph_launches", "idxtts_qwen_max_batch", "idxtts_qwen_batch_workspace_bytes", "idxtts_qwen_generate_batch",
+    "idxtts_qwen_batch_step_graph_launches",
 ]
 
 
@@ -228,6 +229,12 @@ def load() -> ctypes.CDLL:
     lib.idxtts_qwen_generate.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p,
                                          c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]
     lib.idxtts_qwen_step_graph_launches.argtypes = [c_void_p]
+    lib.idxtts_qwen_max_batch.argtypes = [c_void_p]
+    lib.idxtts_qwen_batch_workspace_bytes.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]
+    lib.idxtts_qwen_batch_workspace_bytes.restype = c_size_t
+    lib.idxtts_qwen_generate_batch.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_qwen_batch_step_graph_launches.argtypes = [c_void_p]
     lib.idxtts_profile_enable.argtypes = [c_int]
     lib.idxtts_profile_kernel_name.argtypes = [c_int]
     lib.idxtts_profile_kernel_name.restype = c_char_p

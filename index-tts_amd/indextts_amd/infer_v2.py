@@ -87,11 +87,17 @@ class PromptConditioning:
         emo = spk if feats.emo_cond_emb is None else feats.emo_cond_emb.to(dev, torch.float32)
         ln_s, ln_e = torch.tensor([spk.shape[-1]]), torch.tensor([emo.shape[-1]])
         emovec = gpt.merge_emovec(spk, emo, ln_s, ln_e, alpha=emo_alpha)
-        if emo_mix is not None:                     # (emovec_mat [1,d], weight_vector): infer_v2.py:756-757
-            emovec_mat, weight_vector = emo_mix
-            emovec = emovec_mat.to(dev, torch.float32) + (1 - torch.sum(weight_vector.to(dev, torch.float32))) * emovec
+        if emo_mix is not None:
+            emovec = PromptConditioning.mix_emovec(emovec, emo_mix)
         latent = gpt.get_conditioning(spk.transpose(1, 2), ln_s)
         return PromptConditioning(latent, emovec, feats.style, feats.prompt_condition, feats.ref_mel)
+
+    @staticmethod
+    def mix_emovec(emovec: torch.Tensor, emo_mix) -> torch.Tensor:
+        """The prompt's emotion vector with an `emo_vector` mix laid over it; emo_mix = (emovec_mat [1,d], weight_vector): infer_v2.py:756-757."""
+        emovec_mat, weight_vector = emo_mix
+        dev = emovec.device
+        return emovec_mat.to(dev, torch.float32) + (1 - torch.sum(weight_vector.to(dev, torch.float32))) * emovec
 
     def to(self, device) -> "PromptConditioning":
         return PromptConditioning(*[getattr(self, f).to(device, torch.float32).contiguous() for f in self.FIELDS])
@@ -408,6 +414,27 @@ class IndexTTS2:
             index = [int(torch.argmax(torch.nn.functional.cosine_similarity(style, tmp, dim=1))) for tmp in self.spk_matrix]     # find_most_similar_cosine
         emo_matrix = torch.cat([tmp[i].unsqueeze(0) for i, tmp in zip(index, self.emo_matrix)], 0)
         return torch.sum(weight_vector.unsqueeze(1) * emo_matrix, 0).unsqueeze(0), weight_vector
+
+    def conditionings_from_emo_texts(self, feats: "PromptFeatures", emo_texts, emo_alpha=1.0, use_random=False) -> List["PromptConditioning"]:
+        """One PromptConditioning per emotion text for the same speaker prompt, for the per-row `cond` of BatchPipeline.submit /
+        ContinuousPipeline.submit: ONE batched classification (`qwen_emo.inference_batch`), the speaker-side encoders once, then per
+        text the scaling, `emotion_vector_mix` and merge of `infer_generator`.  Element i is what
+        `infer(feats, ..., use_emo_text=True, emo_text=emo_texts[i], emo_alpha=emo_alpha)` conditions on."""
+        if not isinstance(feats, PromptFeatures):
+            raise NotImplementedError("conditionings_from_emo_texts takes the speaker prompt as PromptFeatures")
+        emo_texts = list(emo_texts)
+        classifier = self.qwen_emo      # NotImplementedError when none is attached
+        scores = classifier.inference_batch(emo_texts) if emo_texts else []
+        scale = max(0.0, min(1.0, emo_alpha))                                                        # infer_v2.py:600-608
+        base = PromptConditioning.from_features(self.gpt, feats, emo_alpha=1.0)                      # 610-615: the speaker prompt serves
+        out = []
+        for d in scores:
+            emo_vector = list(d.values())      # the dict's order is the vector's
+            if scale != 1.0:
+                emo_vector = [int(x * scale * 10000) / 10000 for x in emo_vector]
+            emovec = PromptConditioning.mix_emovec(base.emo_vec, self.emotion_vector_mix(feats.style, emo_vector, use_random=use_random))
+            out.append(PromptConditioning(base.spk_cond_latent, emovec, base.style, base.prompt_condition, base.ref_mel))
+        return out
 
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,

@@ -1,7 +1,7 @@
 """Emotion from text: the reference's `QwenEmotion` (indextts/infer_v2.py:948-1063) on the HIP Qwen3 decoder.
 
-`QwenLM` is the language model (include/idxtts.h "emotion-from-text classifier"): a Qwen3 causal LM at B = 1, prefill + greedy
-decode on the GPU.  `QwenEmotion` wraps it the way the reference wraps transformers: a two-message chat prompt, greedy generation up
+`QwenLM` is the language model (include/idxtts.h "emotion-from-text classifier"): a Qwen3 causal LM, prefill + greedy decode on the
+GPU for one prompt (`generate`) or for several that share every weight pass (`generate_batch`, each row bit-equal to its own `generate`).  `QwenEmotion` wraps it the way the reference wraps transformers: a two-message chat prompt, greedy generation up
 to the end token, the answer parsed as JSON into eight scores in a fixed order.  The tokenizer is whatever the caller hands in (the
 reference's is transformers' AutoTokenizer; checkpoint.qwen_emotion_from_pretrained binds it) -- this module imports no transformers.
 """
@@ -138,6 +138,61 @@ class QwenLM:
         n = n_out.value
         return out_ids[:n].tolist(), (lg[:n] if logits else None)
 
+    def max_batch(self) -> int:
+        """Rows the library passes through the weights together; `generate_batch` takes any number and serves them in such tiles."""
+        return int(self._lib.idxtts_qwen_max_batch(self._h))
+
+    def generate_batch(self, prompts, max_new_tokens, eos_ids=(), forced_ids=None, logits: bool = False, logit_cols=None,
+                       use_graph: bool = True):
+        """`generate` for several prompts at once: row b equals generate(prompts[b], max_new_tokens[b], ...) bit for bit.
+        max_new_tokens: an int or one per row; forced_ids: one array per row (max_new_tokens[b] entries).  Returns (list of id lists,
+        list of [n_b, n_cols] float32 tensors or None)."""
+        rows = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1) for p in prompts]
+        B = len(rows)
+        if B < 1:
+            raise ValueError("generate_batch needs at least one prompt")
+        caps = [int(max_new_tokens)] * B if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
+        if len(caps) != B:
+            raise ValueError("max_new_tokens: an int, or one per prompt")
+        eos = np.ascontiguousarray(list(eos_ids), dtype=np.int32).reshape(-1)
+        forced = None
+        if forced_ids is not None:
+            fr = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for f in forced_ids]
+            if len(fr) != B or any(f.size != m for f, m in zip(fr, caps)):
+                raise ValueError("forced_ids needs one array per prompt with that row's max_new_tokens entries")
+            forced = np.ascontiguousarray(np.concatenate(fr)) if fr else None
+        cols = None if logit_cols is None else np.ascontiguousarray(logit_cols, dtype=np.int32).reshape(-1)
+        n_cols = 0 if not logits else (self.cfg.vocab_size if cols is None else int(cols.size))
+        n_prompt = np.ascontiguousarray([r.size for r in rows], dtype=np.int32)
+        max_new = np.ascontiguousarray(caps, dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(rows)) if all(r.size for r in rows) else np.zeros(0, dtype=np.int32)
+        total = int(sum(max(0, m) for m in caps))
+        out_ids = np.zeros(max(1, total), dtype=np.int32)
+        n_out = np.zeros(B, dtype=np.int32)
+        hp = lambda a: c_void_p(a.ctypes.data) if a is not None and a.size else c_void_p(0)
+        with torch.cuda.device(self.device):
+            need = self._lib.idxtts_qwen_batch_workspace_bytes(self._h, B, hp(n_prompt), hp(max_new), int(eos.size), n_cols)
+            if need == 0:
+                raise ValueError("empty prompt or max_new_tokens < 1")
+            ws = self._ws.get(need, self.device)
+            lg = torch.zeros(total, n_cols, dtype=torch.float32, device=self.device) if logits else None
+            _lib.check(self._lib.idxtts_qwen_generate_batch(self._h, B, hp(flat), hp(n_prompt), hp(max_new), hp(eos), int(eos.size), hp(forced),
+                                                            hp(out_ids), hp(n_out), _lib.ptr(lg), hp(cols) if logits else c_void_p(0),
+                                                            0 if cols is None else int(cols.size), _lib.ptr(ws), ws.numel(), int(use_graph),
+                                                            _lib.current_stream()))
+        ids, lgs, off = [], [], 0
+        for b in range(B):
+            n = int(n_out[b])
+            ids.append(out_ids[off:off + n].tolist())
+            if logits:
+                lgs.append(lg[off:off + n])
+            off += caps[b]
+        return ids, (lgs if logits else None)
+
+    def batch_step_graph_launches(self) -> int:
+        """Kernel launches of the kept batched decode-step graph (-1: none held)."""
+        return int(self._lib.idxtts_qwen_batch_step_graph_launches(self._h))
+
     def step_graph_launches(self) -> int:
         """Kernel launches of the kept decode-step graph (-1: none held)."""
         return int(self._lib.idxtts_qwen_step_graph_launches(self._h))
@@ -211,14 +266,24 @@ class QwenEmotion:
             return []
         return [int(i) for i in ids] if isinstance(ids, (list, tuple)) else [int(ids)]
 
+    def _warn_if_cut(self, ids):
+        if len(ids) >= self.max_new_tokens and (not ids or ids[-1] not in self._end_ids()):
+            warnings.warn(f"QwenEmotion: no end token within max_new_tokens={self.max_new_tokens}; the answer is cut there")
+
     def generate(self, input_ids):
         """The answer's token ids (the end token included when it came): what the reference slices off model.generate's output."""
         ids, _ = self.model.generate(input_ids, self.max_new_tokens, eos_ids=self._end_ids())
-        if len(ids) >= self.max_new_tokens and (not ids or ids[-1] not in self._end_ids()):
-            warnings.warn(f"QwenEmotion: no end token within max_new_tokens={self.max_new_tokens}; the answer is cut there")
+        self._warn_if_cut(ids)
         return ids
 
-    def inference(self, text_input):
+    def generate_batch(self, input_ids_rows):
+        """`generate` for several prompts in one batched call of the language model; the cap warning fires per row."""
+        rows, _ = self.model.generate_batch(input_ids_rows, self.max_new_tokens, eos_ids=self._end_ids())
+        for ids in rows:
+            self._warn_if_cut(ids)
+        return rows
+
+    def _prompt_ids(self, text_input):
         messages = [{"role": "system", "content": f"{self.prompt}"}, {"role": "user", "content": f"{text_input}"}]
         text = self.tokenizer.apply_chat_template(messages, tokenize=False, add_generation_prompt=True, enable_thinking=False)
         enc = self.tokenizer([text])
@@ -226,7 +291,11 @@ class QwenEmotion:
         input_ids = input_ids[0]
         if hasattr(input_ids, "tolist"):
             input_ids = input_ids.tolist()
-        output_ids = list(self.generate(list(input_ids)))
+        return list(input_ids)
+
+    def _scores(self, text_input, output_ids):
+        """The answer's ids -> the eight scores: parsing, the melancholic swap, clamping (one copy for `inference` and `inference_batch`)."""
+        output_ids = list(output_ids)
         # what follows the last "</think>"
         start = 0
         for i in range(len(output_ids) - 1, -1, -1):
@@ -242,3 +311,14 @@ class QwenEmotion:
         if any(word in lowered for word in self.melancholic_words):
             content["悲伤"], content["低落"] = content.get("低落", 0.0), content.get("悲伤", 0.0)
         return self.convert(content)
+
+    def inference(self, text_input):
+        return self._scores(text_input, self.generate(self._prompt_ids(text_input)))
+
+    def inference_batch(self, texts):
+        """`inference` for several texts with one batched generation: element i equals inference(texts[i])."""
+        texts = list(texts)
+        if not texts:
+            return []
+        answers = self.generate_batch([self._prompt_ids(t) for t in texts])
+        return [self._scores(t, ids) for t, ids in zip(texts, answers)]
