@@ -136,9 +136,13 @@ int idxtts_get_decode_geometry(void);
 int idxtts_set_decode_plane_rows(int min_rows);
 int idxtts_get_decode_plane_rows(void);
 /* The CFM solver (idxtts_s2mel_cfm) can evaluate the conditional and the null half of its stacked batch (flow_matching.py:91-103,
- * one DiT.forward on 2B rows there) as two chains of launches on two streams, the null half a few kernels behind: same kernels
- * on the same rows, bit-identical results, 9 % less time for a solver that has the device to itself (one half's HBM-bound
- * epilogues beside the other's MFMA-bound loops).  on = 0 (default): one stacked 2B batch on the caller's stream, as the
+ * one DiT.forward on 2B rows there) as two chains of launches on two streams, the null half a few kernels behind: 9 % less time
+ * for a solver that has the device to itself (one half's HBM-bound epilogues beside the other's MFMA-bound loops).  Each half is
+ * an evaluation of its own on B sequences, and the split-bf16 mode picks its kernels by row count (256 rows, see
+ * idxtts_set_gemm_mode): the results are bit-identical to the stacked form -- same kernels on the same rows -- when B*T and 2B*T
+ * are on the same side of 256 rows, and likewise B*Tt and 2B*Tt for the Tt = T - (shortest prompt - WaveNet context) frames the
+ * solver evaluates behind the transformer when that prompt is long enough; otherwise they differ as the two GEMM modes do.  The
+ * exact fp32 mode picks its kernels regardless of the row count and is bit-identical always.  on = 0 (default): one stacked 2B batch on the caller's stream, as the
  * reference evaluates it -- serving loops with several decode chains in flight should leave it off (profiles/README.md "Round 3"). */
 int idxtts_s2mel_set_overlap(int on);
 int idxtts_s2mel_get_overlap(void);

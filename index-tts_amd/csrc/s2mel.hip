@@ -499,7 +499,10 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
 // all workgroups of one launch are in the same phase.  Two launches of DIFFERENT kernels side by side are not: with the null
 // half of the batch a couple of kernels behind the conditional half, one half's epilogues drain while the other half multiplies
 // (tools/two_stream_gemm.py: the four GEMMs of a DiT layer 1290 -> 1098 us).  The halves share nothing between cfm_pack and the
-// Euler update; results are bit-identical to the single-stream order (same kernels on the same rows).
+// Euler update.  Each half is a dit_eval of its own with N2 = B, so chain / chain_t are taken at B*T and B*Tt rows instead of 2B*T
+// and 2B*Tt: results are bit-identical to the single-stream order (same kernels on the same rows) when both pairs are on the
+// same side of the 256-row switch (and always in GEMM_F32 mode); otherwise a half runs the fp32-row kernels where the stacked
+// batch runs planes, within the split-bf16 bounds (tests/test_s2mel_dispatch_gpu.py::test_solver_halves_on_two_streams).
 struct HalfStreams { hipStream_t side = nullptr; hipEvent_t fork = nullptr, lag = nullptr, join = nullptr; };
 static std::map<std::pair<int, hipStream_t>, HalfStreams> g_half_streams;   // per (device, caller stream)
 static std::mutex g_half_mu;

@@ -388,7 +388,8 @@ def get_decode_plane_rows() -> int:
 
 def set_s2mel_overlap(on: bool) -> None:
     """The CFM solver's two CFG halves on two streams (on) or as one stacked 2B batch on the caller's stream (off, the default: faster
-    beside concurrent decode chains, profiles/README.md "Round 3").  Same result bit for bit."""
+    beside concurrent decode chains, profiles/README.md "Round 3").  Same result bit for bit when both forms land on the same
+    side of the 256-row kernel switch (include/idxtts.h)."""
     check(load().idxtts_s2mel_set_overlap(int(bool(on))))
 
 

@@ -1,4 +1,5 @@
-"""ORACLE (test infrastructure, not product): CPU fp32 restatement of the IndexTTS-2 semantic-to-mel stage.
+"""ORACLE (test infrastructure, not product): CPU restatement of the IndexTTS-2 semantic-to-mel stage.  fp32 as the reference
+runs it; with float64 weights AND inputs every tensor created here (time-step features, t_span, rope table) is float64 too.
 
 Only `tests/`, `__graft_entry__.smoke()` and `bench.py`'s `cpu_baseline` leg may import this.
 
@@ -70,31 +71,31 @@ def length_regulator(w, cfg, x: torch.Tensor, ylens: torch.Tensor) -> torch.Tens
 
 
 # ------------------------------------------------------------------------------------------------
-def timestep_embedding(t: torch.Tensor, dim: int = 256) -> torch.Tensor:
+def timestep_embedding(t: torch.Tensor, dim: int = 256, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """TimestepEmbedder.timestep_embedding (diffusion_transformer.py:41-55): scale 1000, max_period 10000."""
     half = dim // 2
-    freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half)
-    args = 1000 * t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=dtype) / half)
+    args = 1000 * t[:, None].to(dtype) * freqs[None]
     return torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
 
 
 def t_embed(w, name: str, t: torch.Tensor) -> torch.Tensor:
-    h = _lin(w, f"{name}.mlp.0", timestep_embedding(t))
+    h = _lin(w, f"{name}.mlp.0", timestep_embedding(t, dtype=_t(w, f"{name}.mlp.0.weight").dtype))
     return _lin(w, f"{name}.mlp.2", F.silu(h))
 
 
-def rope_cache(seq_len: int, n_elem: int, base: float = 10000.0) -> torch.Tensor:
-    """precompute_freqs_cis (gpt_fast/model.py:336-345) in the weight dtype (fp32) -> [T, n_elem/2, 2]."""
-    freqs = 1.0 / (base ** (torch.arange(0, n_elem, 2)[: (n_elem // 2)].float() / n_elem))
+def rope_cache(seq_len: int, n_elem: int, base: float = 10000.0, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """precompute_freqs_cis (gpt_fast/model.py:336-345) in the weight dtype (fp32 in the reference) -> [T, n_elem/2, 2]."""
+    freqs = 1.0 / (base ** (torch.arange(0, n_elem, 2)[: (n_elem // 2)].to(dtype) / n_elem))
     t = torch.arange(seq_len)
     freqs = torch.outer(t, freqs)
     fc = torch.polar(torch.ones_like(freqs), freqs)
-    return torch.stack([fc.real, fc.imag], dim=-1).to(torch.float32)
+    return torch.stack([fc.real, fc.imag], dim=-1).to(dtype)
 
 
 def apply_rotary(x: torch.Tensor, fc: torch.Tensor) -> torch.Tensor:
     """apply_rotary_emb (model.py:348-360): interleaved pairs.  x [B,T,H,hd], fc [T,hd/2,2]."""
-    xs = x.float().reshape(*x.shape[:-1], -1, 2)
+    xs = x.to(fc.dtype).reshape(*x.shape[:-1], -1, 2)
     fc = fc.view(1, xs.size(1), 1, xs.size(3), 2)
     out = torch.stack([xs[..., 0] * fc[..., 0] - xs[..., 1] * fc[..., 1],
                        xs[..., 1] * fc[..., 0] + xs[..., 0] * fc[..., 1]], -1)
@@ -117,7 +118,7 @@ def dit_transformer(w, cfg, x: torch.Tensor, c: torch.Tensor, key_mask: torch.Te
     """Transformer.forward (model.py:160-191).  x [N,T,D], c [N,1,D], key_mask [N,T] bool."""
     N, T, D = x.shape
     H, hd = cfg.num_heads, cfg.head_dim
-    fc = rope_cache(cfg.block_size, hd, cfg.rope_base)[:T]
+    fc = rope_cache(cfg.block_size, hd, cfg.rope_base, x.dtype)[:T]
     attn_mask = key_mask[:, None, None, :].expand(N, 1, T, T)
     half = cfg.depth // 2
     skips = []
@@ -193,7 +194,7 @@ def cfm_inference(w, cfg, mu, x_lens, prompt, style, z, n_timesteps: int, cfg_ra
     (the reference draws it from the global RNG at line 52; temperature 1.0)."""
     B, T = mu.shape[0], mu.shape[1]
     x = z.clone()
-    t_span = torch.linspace(0, 1, n_timesteps + 1)
+    t_span = torch.linspace(0, 1, n_timesteps + 1, dtype=z.dtype)
     Tp = prompt.shape[-1]
     prompt_x = torch.zeros_like(x)
     prompt_x[..., :Tp] = prompt[..., :Tp]

@@ -201,7 +201,7 @@ def test_cfm_split_bf16_mode_vs_oracle(device, golden_dir):
 
 
 def test_cfm_long_batch_dma_gemm_chain_vs_oracle(device):
-    """2B*T >= 4096 rows and every projection >= 192 columns: the DiT / WaveNet GEMMs run on the LDS-DMA split-bf16 kernel,
+    """2B*T >= 256 rows and every projection >= 96 columns: the DiT / WaveNet GEMMs run on the LDS-DMA split-bf16 kernel,
     producers hand their outputs over as bf16 hi/lo planes (adaLN norm, attention, SwiGLU and gate epilogues), the rotary
     embedding rides in the qkv epilogue and attention runs in its split-bf16 form -- against the fp32 CPU oracle, ragged."""
     import dataclasses
@@ -233,8 +233,9 @@ def test_cfm_long_batch_dma_gemm_chain_vs_oracle(device):
 def test_cfm_long_prompts_tail_only_wavenet_vs_oracle(device, lens, plens):
     """Prompts longer than 64 frames + the WaveNet's context: the solver evaluates the post-transformer part (long skip, WaveNet,
     final layer) only from frame min(prompt_len) - halo on, on compacted rows -- the Euler step discards the prompt frames anyway
-    (flow_matching.py:113).  Ragged batch vs the per-utterance CPU oracle; the second case keeps the compacted rows on the LDS-DMA
-    GEMM chain (>= 4096 rows), the first drops to the fp32-row kernels for the tail."""
+    (flow_matching.py:113).  Ragged batch vs the per-utterance CPU oracle; both cases keep the compacted rows on the LDS-DMA
+    GEMM chain (>= 256 rows: 2784 and 2816 here).  The hand-over from planes to the fp32-row kernels inside the last block, and
+    every other switch point of the solver, is tests/test_s2mel_dispatch_gpu.py's."""
     import dataclasses
     from indextts_amd.s2mel import S2Mel
     from oracle import s2mel as osm
