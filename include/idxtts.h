@@ -111,7 +111,7 @@ typedef struct idxtts_linear idxtts_linear;
 int idxtts_linear_create(const float* weight, const float* bias /* may be NULL */, int N, int K, int weight_is_kn,
                          idxtts_linear** out);
 int idxtts_linear_fwd(const idxtts_linear* lin, const float* x, int ldx, float* y, int ldy, const float* residual /* may be NULL */,
-                      int ldr, int M, int act, int bf16x3 /* 0: exact fp32 MFMA, 1: split-bf16 (3 bf16 MFMAs per product) */,
+                      int ldr, int M, int act, int bf16x3 /* 0: exact fp32 MFMA, 1: split-bf16 (3 bf16 MFMAs per product), 2: split-bf16 with the LDS-DMA kernel's 32x32x16 main loop */,
                       void* stream);
 /* Arithmetic of the compute-bound passes of the model contexts (s2mel GEMMs and DiT attention, GPT latent pass, vocoder
  * convolutions): 0 = exact fp32 MFMA, 1 (default) = split-bf16: x*w ~= hi*hi' + hi*lo' + lo*hi' on

@@ -235,7 +235,7 @@ int idxtts_linear_create(const float* weight, const float* bias, int N, int K, i
   if (fetch(weight, (size_t)N * K, &hw)) return 1;
   if (bias && fetch(bias, N, &hb)) return 1;
   // always with the split-bf16 pack: idxtts_linear_fwd(bf16x3 = 1) takes any shape and any M
-  if (make_linear(l->arena, hw.data(), bias ? hb.data() : nullptr, N, K, {WP16_ALWAYS, weight_is_kn ? W_KN : W_NK}, &l->w)) return 1;
+  if (make_linear(l->arena, hw.data(), bias ? hb.data() : nullptr, N, K, {WP16_ALWAYS_MF16, weight_is_kn ? W_KN : W_NK}, &l->w)) return 1;
   *out = l.release();
   return 0;
   API_END
@@ -247,7 +247,10 @@ int idxtts_linear_fwd(const idxtts_linear* lin, const float* x, int ldx, float* 
   IDX_CHECK(lin, "null handle");
   GemmArgs a;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.res = residual; a.ldr = ldr; a.M = M; a.act = act;
-  return bf16x3 ? gemm_bf16x3_forward(lin->w, a, static_cast<hipStream_t>(stream)) : gemm_tn_forward(lin->w, a, static_cast<hipStream_t>(stream));
+  if (!bf16x3) return gemm_tn_forward(lin->w, a, static_cast<hipStream_t>(stream));
+  LinearWeights w = lin->w;
+  if (bf16x3 == 2) w.mf16 = false;      // the LDS-DMA kernel's 32x32x16 loop: what the GPT, conditioning and semantic weights run
+  return gemm_bf16x3_forward(w, a, static_cast<hipStream_t>(stream));
   API_END
 }
 

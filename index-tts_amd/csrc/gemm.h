@@ -12,6 +12,7 @@ struct LinearWeights {      // device-resident, packed for the MFMA B operand
   const float* bias = nullptr; // [N] (for SWIGLU: [N] in packed row order) or null
   int N = 0, K = 0;
   const void* wp16 = nullptr;  // optional split-bf16 pack [N/128][K/32][hl][128][40] bf16 (gemm_bf16x3.hip)
+  bool mf16 = false;           // the LDS-DMA kernel multiplies on v_mfma_f32_16x16x32_bf16 (model_util.h: WP16_ALWAYS_MF16)
 };
 
 static inline size_t linear_packed_floats(int N, int K) { return (size_t)cdiv(N, 32) * cdiv(K, 16) * 512; }

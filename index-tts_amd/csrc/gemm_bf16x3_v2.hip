@@ -1,5 +1,5 @@
-// Split-bf16 token-major GEMM, LDS-DMA pipeline (256 x 256 tile): same contract and arithmetic as gemm_bf16x3.hip
-// (Y = epi(X W^T + b), x*w ~= hi*hi' + hi*lo' + lo*hi' on v_mfma_f32_32x32x16_bf16, fp32 accumulation), different
+// Split-bf16 token-major GEMM, LDS-DMA pipeline (128 x 128 tile): same contract and arithmetic as gemm_bf16x3.hip
+// (Y = epi(X W^T + b), x*w ~= hi*hi' + hi*lo' + lo*hi' on v_mfma_f32_16x16x32_bf16 or 32x32x16, fp32 accumulation), different
 // data movement.
 //
 // Why (profiles/r01 PMC, gemm_bf16x3_big_kernel<4> at M=50208 N=1024 K=2560): MFMA busy 30 %, waves parked 39 % of their
@@ -10,10 +10,9 @@
 //   * both operands live in HBM already split, as planes [hl][K/16][rows][16] bf16 (a 16-k chunk of all rows is one
 //     contiguous run): the weights are laid out like that at load, the activations by one streaming pre-pass
 //     (split_planes_kernel; 8 B/element moved once per GEMM instead of a conversion in every column-block);
-//   * tiles go HBM/L2 -> LDS by global_load_lds_dwordx4 (1 KiB per wave-instruction) into a 4-deep ring of 16-k stages
-//     (32 KiB each); three stages are always in flight, retired with counted s_waitcnt vmcnt(8/4/0) and ONE raw
-//     s_barrier per stage (RAW: wait, then barrier, then read; WAR: the stage overwritten after barrier i was last read
-//     before it);
+//   * tiles go HBM/L2 -> LDS by global_load_lds_dwordx4 (1 KiB per wave-instruction) into a 3-deep ring of 16-k stages
+//     (16 KiB each), retired with counted s_waitcnt vmcnt and raw s_barriers (RAW: wait, then barrier, then read; WAR: a
+//     stage is overwritten only after a barrier behind its last read);
 //   * LDS rows are 32 B (2 x 16-B units); unit' = unit ^ (row >> 3 & 1), applied on the DMA's SOURCE address and on the
 //     ds_read_b128 address, makes every fragment read conflict-free without padding (the DMA destination is lane-linear).
 #include <algorithm>
@@ -92,15 +91,14 @@ struct GemmV2P {
 #endif
 };
 
-// Two geometries of the same loop (CFG):
-//   1 (the one in use): workgroup = 2 x 2 waves, each 64 x 64 (2 x 2 MFMA tiles): 128 x 128 per workgroup, 256 threads, 16 KiB
-//      stages, 3-deep ring (48 KiB), <= 168 registers: THREE workgroups per CU, whose phases (main loop / store-bound epilogue)
-//      interleave on a CU; 4x the tiles of the large form, so launches of a few hundred rows still spread over the chip;
-//   0: workgroup = 4 x 2 waves, each a 64 x 128 output tile (2 x 4 MFMA tiles): 256 x 256 per workgroup, 512 threads, 32 KiB
-//      stages, 4-deep ring, one workgroup per CU (round 2's geometry; measured slower on every shape, see the dispatch).
-//   Same stage = 16 k, same four DMA pieces per wave and stage in both.
+// Geometry: workgroup = 2 x 2 waves, each 64 x 64: 128 x 128 per workgroup, 256 threads, 16 KiB stages, 3-deep ring (48 KiB),
+// <= 168 registers: THREE workgroups per CU, whose phases (main loop / store-bound epilogue) interleave on a CU; launches of a
+// few hundred rows still spread over the chip.  (Round 2's 256 x 256 tiles at one workgroup per CU were slower on every shape,
+// see the dispatch, and are gone.)  Two main loops (MF) over the same ring, DMA pieces and epilogue:
+//   32  v_mfma_f32_32x32x16_bf16, one 16-k stage per step, two fragment register sets, one barrier per stage;
+//   16  v_mfma_f32_16x16x32_bf16, a pair of stages per step (below).
 //
-// Round 3: what a stage's instruction stream holds besides its 24 MFMAs decides the kernel (profiles/README.md "Round 3"):
+// Round 3: what a stage's instruction stream holds besides its MFMAs (24 per stage) decides the kernel (profiles/README.md "Round 3"):
 //   * every LDS-DMA is ONE buffer_load_dwordx4 ... lds: the lane's byte offset inside the operand planes is a VGPR computed
 //     once per tile (once per tap for the convolution form), the stage offset an SGPR that advances by a constant, the
 //     ring slot goes to M0 -- no vector arithmetic per piece (the per-piece 64-bit address arithmetic of the first form was
@@ -114,12 +112,13 @@ struct V2Rsrc { __amdgpu_buffer_rsrc_t a, b; };
 
 #define V2_WAITCNT(vm) __builtin_amdgcn_s_waitcnt(((vm) & 15) | (((vm) >> 4) << 14) | 0x70)   /* vmcnt(vm) lgkmcnt(0) */
 
-template <bool TAPS, int EPI, int CFG>
+template <bool TAPS, int EPI, int MF>      // MF: the MFMA shape of the main loop, 32 = 32x32x16, 16 = 16x16x32
 __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, const int bn, const int tid) {
-  constexpr int NSTAGE = CFG ? 3 : 4;      // ring depth (16-k stages): CFG 2 = the 128 x 128 geometry at three workgroups per CU
-  constexpr int WMW = CFG ? 2 : 4, WNW = 2, TN = CFG ? 2 : 4;      // waves along M / N, 32-column MFMA tiles per wave
-  constexpr int BM = 64 * WMW, BN = 32 * TN * WNW;                 // 256 x 256 or 128 x 128
+  constexpr int NSTAGE = 3;                // ring depth (16-k stages)
+  constexpr int WMW = 2, WNW = 2, TN = 2;      // waves along M / N, 32-column MFMA tiles per wave
+  constexpr int BM = 64 * WMW, BN = 32 * TN * WNW;                 // 128 x 128
   static_assert(BM / 32 == WMW * WNW && BN / 32 == WMW * WNW, "one 32-row block of A and of B per wave and plane");
+  static_assert(MF == 32 || MF == 16, "MFMA shape");
   constexpr int PLANE = BM * 32;               // bytes of one operand plane of a stage (BM = BN rows x 32 B)
   constexpr int STAGE_BYTES = 4 * PLANE;       // [A hi][A lo][B hi][B lo]
   constexpr int PPW = 4;                       // DMA instructions per wave and stage
@@ -178,131 +177,247 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
     }
   };
 
-  // fragment read offsets (bytes inside a plane image): row * 32 + (h ^ (row >> 3 & 1)) * 16, row = tile row of lane j
-  const int sw = (h ^ ((j >> 3) & 1)) * 16;
-  const int a_off = (wm * 64 + j) * 32 + sw;          // + t * 1024 for the second 32-row tile
-  const int b_offr = (wn * TN * 32 + j) * 32 + sw;    // + t * 1024 per 32-column tile
+  if constexpr (MF == 16) {
+    // ---- v_mfma_f32_16x16x32_bf16: a step multiplies a PAIR of stages (32 k).  Lane (g = lane >> 4, r = lane & 15) holds row r of a
+    // 16-row tile and k = 8 g .. 8 g + 7 of the pair: 16-B unit g & 1 of stage (pair's first) + (g >> 1), same swizzle.  A step reads
+    // each of its 4 + 4 A and 4 + 4 B fragments once (16 ds_read_b128 per 32 k, as the 32x32 loop) and issues 48 MFMAs:
+    //   wait (the pair has landed) | barrier | 16 fragment reads | 12 MFMAs (column tile 0, each row tile as its fragments arrive) |
+    //   lgkmcnt(0), barrier: every wave has the pair in registers, its two ring slots are free | 36 MFMAs with the DMA of the two
+    //   stages that take those slots between them.
+    // The ring holds three stages, so the fragments of pair p + 1 cannot be read beside the MFMAs of pair p (their second stage
+    // needs a slot of pair p); what hides the reads and the barriers is the other two workgroups of the CU.  One stage stays in
+    // flight across the step's first barrier, two across the next step's wait.  Against the 32x32x16 loop (stamps, profiles/README.md
+    // "MFMA shape"): + 14-20 % cycles per stage, + 12-19 % clock held -- 0.6-7 % less wall per launch.
+    // An odd stage count ends in a step whose upper 32 lanes hold zero fragments (k order of a row's sum: pairs in order, then the
+    // tail; independent of M and of the tile).
+    const int g = lane >> 4, r16 = lane & 15;
+    const int sw = ((g & 1) ^ ((r16 >> 3) & 1)) * 16;
+    const int a_off = (wm * 64 + r16) * 32 + sw;                       // + t * 512 per 16-row tile
+    const int b_off = 2 * PLANE + (wn * 64 + r16) * 32 + sw;
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
+    for (int s = 0; s < NSTAGE; ++s)
+      if (s < ns) {
+#pragma unroll
+        for (int pi = 0; pi < PPW; ++pi) issue_piece(pi);
+        advance();
+      }
 
-  f32x16 acc[2][TN];
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    // one step: stages (done, done + 1), or the last stage alone (tail); nreq = stages to request in it (0 .. 2)
+    auto pair_step = [&](const bool tail, const bool vm_one_behind, const int nreq) {
+      if (vm_one_behind) V2_WAITCNT(PPW); else V2_WAITCNT(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      const int second = rslot + 1 == NSTAGE ? 0 : rslot + 1;
+      const char* st = smv2 + ((g >> 1) && !tail ? second : rslot) * STAGE_BYTES;
+      rslot = second + 1 == NSTAGE ? 0 : second + 1;       // (a tail is the last step)
+      bf16x8 ah[4], al[4], bh[4], bl[4];
+      auto rd_a = [&](int t) {
+        ah[t] = *reinterpret_cast<const bf16x8*>(st + a_off + t * 512);
+        al[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + a_off + t * 512);
+      };
+      auto rd_b = [&](int t) {
+        bh[t] = *reinterpret_cast<const bf16x8*>(st + b_off + t * 512);
+        bl[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + b_off + t * 512);
+      };
+      // row tile 0 and column tile 0 first: the first MFMAs wait for three reads, not for all of A
+      rd_a(0); rd_b(0);
+      __builtin_amdgcn_sched_barrier(0);
+      rd_a(1);
+      __builtin_amdgcn_sched_barrier(0);
+      rd_a(2);
+      __builtin_amdgcn_sched_barrier(0);
+      rd_a(3);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+      for (int t = 1; t < 4; ++t) rd_b(t);
+      if (tail) {
+        const unsigned keep = (g >> 1) ? 0u : 0xffffffffu;
 #pragma unroll
-    for (int b = 0; b < TN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+        for (int t = 0; t < 4; ++t) {
+          ah[t] = (bf16x8)((u32x4)ah[t] & keep); al[t] = (bf16x8)((u32x4)al[t] & keep);
+          bh[t] = (bf16x8)((u32x4)bh[t] & keep); bl[t] = (bf16x8)((u32x4)bl[t] & keep);
+        }
+      }
+#define V2_MFMA3(nt)                                                                                               \
+      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                            \
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);                \
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);                \
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);                \
+      }
+#define V2_MFMA1(mt, nt)                                                                                           \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);                  \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);                  \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);                  \
+      __builtin_amdgcn_sched_barrier(0);
 
-  for (int s = 0; s < NSTAGE; ++s)
-    if (s < ns) {
-#pragma unroll
-      for (int pi = 0; pi < PPW; ++pi) issue_piece(pi);
-      advance();
-    }
-
-  struct Frag { bf16x8 ah[2], al[2], bh[TN], bl[TN]; };
-  // stage s has landed for the whole workgroup: this wave's pieces by the counted wait (younger stages may stay in
-  // flight), everyone's by the barrier; the lgkmcnt(0) retires this wave's fragment reads of stage s - 1, so after the
-  // barrier that ring slot may be overwritten.  Stages in flight behind s: min(2, ns - 1 - s) (3 behind stage 0).
-  auto wait_stage = [&](int s) {
-    const int rem = ns - 1 - s;           // stages behind s; at most NSTAGE - 2 of them have been requested
-    if (NSTAGE >= 4 && rem >= 2) V2_WAITCNT(2 * PPW);
-    else if (NSTAGE >= 3 && rem >= 1) V2_WAITCNT(PPW);
-    else V2_WAITCNT(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto load_frags = [&](Frag& f) {           // the next stage in order
-    const char* st = smv2 + rslot * STAGE_BYTES;
-    rslot = rslot + 1 == NSTAGE ? 0 : rslot + 1;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      f.ah[t] = *reinterpret_cast<const bf16x8*>(st + a_off + t * 1024);
-      f.al[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + a_off + t * 1024);
-    }
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-      f.bh[t] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE + b_offr + t * 1024);
-      f.bl[t] = *reinterpret_cast<const bf16x8*>(st + 3 * PLANE + b_offr + t * 1024);
-    }
-  };
-  // 24 MFMAs of stage i; the DMA of stage i + NSTAGE (ring slot of stage i, free since the last barrier) is issued
-  // piecewise between the four MFMA groups
-  auto compute = [&](const Frag& f, const bool more) {
-#define V2_MFMA3(mt, nt)                                                                                         \
-    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[mt], f.bh[nt], acc[mt][nt], 0, 0, 0);             \
-    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], f.bl[nt], acc[mt][nt], 0, 0, 0);             \
-    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], f.bh[nt], acc[mt][nt], 0, 0, 0);
-    // four MFMA groups (half a row of tiles each) with one DMA piece behind each
-    if constexpr (TN == 4) { V2_MFMA3(0, 0) V2_MFMA3(0, 1) } else { V2_MFMA3(0, 0) }
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) issue_piece(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TN == 4) { V2_MFMA3(0, 2) V2_MFMA3(0, 3) } else { V2_MFMA3(0, 1) }
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) issue_piece(1);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TN == 4) { V2_MFMA3(1, 0) V2_MFMA3(1, 1) } else { V2_MFMA3(1, 0) }
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) issue_piece(2);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TN == 4) { V2_MFMA3(1, 2) V2_MFMA3(1, 3) } else { V2_MFMA3(1, 1) }
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) { issue_piece(3); advance(); }
-    __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA1(0, 0) V2_MFMA1(1, 0) V2_MFMA1(2, 0) V2_MFMA1(3, 0)      // (in the order their A fragments arrive)
+      V2_WAITCNT(63);                           // lgkmcnt(0): every fragment of the pair is in registers
+      __builtin_amdgcn_s_barrier();             // ... in every wave: the pair's ring slots are free
+      __builtin_amdgcn_sched_barrier(0);
+      if (nreq >= 1) { issue_piece(0); issue_piece(1); }
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(1)
+      __builtin_amdgcn_sched_barrier(0);
+      if (nreq >= 1) { issue_piece(2); issue_piece(3); advance(); }
+      if (nreq >= 2) { issue_piece(0); issue_piece(1); }
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(2)
+      __builtin_amdgcn_sched_barrier(0);
+      if (nreq >= 2) { issue_piece(2); issue_piece(3); advance(); }
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(3)
+      __builtin_amdgcn_sched_barrier(0);
+#undef V2_MFMA1
 #undef V2_MFMA3
-  };
+    };
+    V2_STAMP(1);
+    int done = 0;                               // stages multiplied
+    // steady state, straight-line: the stage behind the pair is in flight at the wait, two stages to request in the step
+    for (; ist + 2 <= ns && ist > done + 2; done += 2) pair_step(false, true, 2);
+    for (; done + 2 <= ns; done += 2) pair_step(false, ist > done + 2, min(ns - ist, 2));
+    if (done < ns) pair_step(true, false, 0);
+    V2_STAMP(2);
+    // 16 x 16 C/D layout: register e of tile (mt, nt) is row mt * 16 + 4 g + e, column nt * 16 + r16
+    auto write_pass = [&](int ps, float* lds, int RS) {
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lds[(4 * g + e) * RS + nt * 16 + r16] = acc[ps][nt][e];
+    };
+    gemm_epilogue_wave<EPI, TN, 3>(p, write_pass, reinterpret_cast<float*>(smv2), bm * BM + wm * 64, bn * BN + wn * TN * 32, wave, lane);
+  } else {
+    // fragment read offsets (bytes inside a plane image): row * 32 + (h ^ (row >> 3 & 1)) * 16, row = tile row of lane j
+    const int sw = (h ^ ((j >> 3) & 1)) * 16;
+    const int a_off = (wm * 64 + j) * 32 + sw;          // + t * 1024 for the second 32-row tile
+    const int b_offr = (wn * TN * 32 + j) * 32 + sw;    // + t * 1024 per 32-column tile
 
-  // two fragment register sets: the reads of stage i + 1 are in flight while stage i is multiplied
-  Frag f0, f1;
-  {   // stage 0: up to three younger stages in flight
-    const int rem = ns - 1;
-    if (NSTAGE >= 4 && rem >= 3) V2_WAITCNT(3 * PPW);
-    else if (NSTAGE >= 3 && rem >= 2) V2_WAITCNT(2 * PPW);
-    else if (rem >= 1) V2_WAITCNT(PPW);
-    else V2_WAITCNT(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  V2_STAMP(1);
-  load_frags(f0);
-  int i = 0;
-  // steady state, straight-line: two younger stages in flight behind every wait, a stage to request beside every compute
-  // (a branch-free body also keeps the compiler's counter model exact: at a join of paths with different numbers of LDS reads
-  // pending it falls back to s_waitcnt lgkmcnt(0) in front of the first MFMA, i.e. behind the next stage's fragment reads)
-  for (; i + NSTAGE + 1 < ns; i += 2) {
-    V2_WAITCNT((NSTAGE - 2) * PPW);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(f1);
-    compute(f0, true);
-    V2_WAITCNT((NSTAGE - 2) * PPW);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(f0);
-    compute(f1, true);
-  }
-  for (; i < ns; i += 2) {     // the last stages: the ring drains
-    if (i + 1 < ns) { wait_stage(i + 1); load_frags(f1); }
-    else V2_WAITCNT(0);
-    compute(f0, ist < ns);
-    if (i + 1 < ns) {
-      if (i + 2 < ns) { wait_stage(i + 2); load_frags(f0); }
+    f32x16 acc[2][TN];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < TN; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+
+    for (int s = 0; s < NSTAGE; ++s)
+      if (s < ns) {
+#pragma unroll
+        for (int pi = 0; pi < PPW; ++pi) issue_piece(pi);
+        advance();
+      }
+
+    struct Frag { bf16x8 ah[2], al[2], bh[TN], bl[TN]; };
+    // stage s has landed for the whole workgroup: this wave's pieces by the counted wait (younger stages may stay in
+    // flight), everyone's by the barrier; the lgkmcnt(0) retires this wave's fragment reads of stage s - 1, so after the
+    // barrier that ring slot may be overwritten.  Stages in flight behind s: min(2, ns - 1 - s) (3 behind stage 0).
+    auto wait_stage = [&](int s) {
+      const int rem = ns - 1 - s;           // stages behind s; at most NSTAGE - 2 of them have been requested
+      if (rem >= 1) V2_WAITCNT(PPW);
       else V2_WAITCNT(0);
-      compute(f1, ist < ns);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto load_frags = [&](Frag& f) {           // the next stage in order
+      const char* st = smv2 + rslot * STAGE_BYTES;
+      rslot = rslot + 1 == NSTAGE ? 0 : rslot + 1;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        f.ah[t] = *reinterpret_cast<const bf16x8*>(st + a_off + t * 1024);
+        f.al[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + a_off + t * 1024);
+      }
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        f.bh[t] = *reinterpret_cast<const bf16x8*>(st + 2 * PLANE + b_offr + t * 1024);
+        f.bl[t] = *reinterpret_cast<const bf16x8*>(st + 3 * PLANE + b_offr + t * 1024);
+      }
+    };
+    // 24 MFMAs of stage i; the DMA of stage i + NSTAGE (ring slot of stage i, free since the last barrier) is issued
+    // piecewise between the four MFMA groups
+    auto compute = [&](const Frag& f, const bool more) {
+#define V2_MFMA3(mt, nt)                                                                                         \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.al[mt], f.bh[nt], acc[mt][nt], 0, 0, 0);             \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], f.bl[nt], acc[mt][nt], 0, 0, 0);             \
+      acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.ah[mt], f.bh[nt], acc[mt][nt], 0, 0, 0);
+      // four MFMA groups (half a row of tiles each) with one DMA piece behind each
+      V2_MFMA3(0, 0)
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) issue_piece(0);
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(0, 1)
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) issue_piece(1);
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(1, 0)
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) issue_piece(2);
+      __builtin_amdgcn_sched_barrier(0);
+      V2_MFMA3(1, 1)
+      __builtin_amdgcn_sched_barrier(0);
+      if (more) { issue_piece(3); advance(); }
+      __builtin_amdgcn_sched_barrier(0);
+#undef V2_MFMA3
+    };
+
+    // two fragment register sets: the reads of stage i + 1 are in flight while stage i is multiplied
+    Frag f0, f1;
+    {   // stage 0: up to three younger stages in flight
+      const int rem = ns - 1;
+      if (rem >= 2) V2_WAITCNT(2 * PPW);
+      else if (rem >= 1) V2_WAITCNT(PPW);
+      else V2_WAITCNT(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
     }
+    V2_STAMP(1);
+    load_frags(f0);
+    int i = 0;
+    // steady state, straight-line: two younger stages in flight behind every wait, a stage to request beside every compute
+    // (a branch-free body also keeps the compiler's counter model exact: at a join of paths with different numbers of LDS reads
+    // pending it falls back to s_waitcnt lgkmcnt(0) in front of the first MFMA, i.e. behind the next stage's fragment reads)
+    for (; i + NSTAGE + 1 < ns; i += 2) {
+      V2_WAITCNT((NSTAGE - 2) * PPW);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      load_frags(f1);
+      compute(f0, true);
+      V2_WAITCNT((NSTAGE - 2) * PPW);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      load_frags(f0);
+      compute(f1, true);
+    }
+    for (; i < ns; i += 2) {     // the last stages: the ring drains
+      if (i + 1 < ns) { wait_stage(i + 1); load_frags(f1); }
+      else V2_WAITCNT(0);
+      compute(f0, ist < ns);
+      if (i + 1 < ns) {
+        if (i + 2 < ns) { wait_stage(i + 2); load_frags(f0); }
+        else V2_WAITCNT(0);
+        compute(f1, ist < ns);
+      }
+    }
+    // (the last wait_stage left no DMA in flight; the epilogue synchronises the workgroup itself before it reuses the ring)
+    V2_STAMP(2);
+    // 32 x 32 C/D layout: register r = (2 hh + qq) * 4 + e of tile (mt, nt) is row mt * 32 + 16 hh + 8 qq + 4 h + e, column nt * 32 + j
+    auto write_pass = [&](int ps, float* lds, int RS) {
+      const int mt = ps >> 1, hh = ps & 1;
+#pragma unroll
+      for (int nt = 0; nt < TN; ++nt)
+#pragma unroll
+        for (int qq = 0; qq < 2; ++qq)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) lds[(8 * qq + 4 * h + e) * RS + nt * 32 + j] = acc[mt][nt][(2 * hh + qq) * 4 + e];
+    };
+    gemm_epilogue_wave<EPI, TN, 3>(p, write_pass, reinterpret_cast<float*>(smv2), bm * BM + wm * 64, bn * BN + wn * TN * 32, wave, lane);
   }
-  // (the last wait_stage left no DMA in flight; the epilogue synchronises the workgroup itself before it reuses the ring)
-  V2_STAMP(2);
-  // 32 x 32 C/D layout: register r = (2 hh + qq) * 4 + e of tile (mt, nt) is row mt * 32 + 16 hh + 8 qq + 4 h + e, column nt * 32 + j
-  auto write_pass = [&](int ps, float* lds, int RS) {
-    const int mt = ps >> 1, hh = ps & 1;
-#pragma unroll
-    for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) lds[(8 * qq + 4 * h + e) * RS + nt * 32 + j] = acc[mt][nt][(2 * hh + qq) * 4 + e];
-  };
-  gemm_epilogue_wave<EPI, TN, 3>(p, write_pass, reinterpret_cast<float*>(smv2), bm * BM + wm * 64, bn * BN + wn * TN * 32, wave, lane);
   V2_STAMP(6);
 #ifdef V2_TIMING
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -311,8 +426,8 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
 }
 
 // one output tile per workgroup; XCD x owns the row tiles == x (mod 8) (gemm.hip explains the two walk orders)
-template <bool TAPS, int EPI, int CFG>
-__global__ __launch_bounds__(CFG ? 256 : 512, CFG ? 3 : 2) void gemm_bf16x3_v2_kernel(const GemmV2P q) {
+template <bool TAPS, int EPI, int MF>
+__global__ __launch_bounds__(256, 3) void gemm_bf16x3_v2_kernel(const GemmV2P q) {
   const GemmKP& p = q.g;
   const int L = blockIdx.x, xcd = L & 7, qq = L >> 3;
   int bn, bm;
@@ -327,7 +442,7 @@ __global__ __launch_bounds__(CFG ? 256 : 512, CFG ? 3 : 2) void gemm_bf16x3_v2_k
     if (bn >= p.nblocks) return;
   } else { bn = qq / p.mt8; bm = (qq - bn * p.mt8) * 8 + xcd; }
   if (bm >= p.mtiles) return;
-  gemm_v2_tile<TAPS, EPI, CFG>(q, bm, bn, threadIdx.x);
+  gemm_v2_tile<TAPS, EPI, MF>(q, bm, bn, threadIdx.x);
 }
 
 // per-stream scratch for the activation planes: room for a quarter more rows than the launch that grows it
@@ -365,9 +480,8 @@ int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w
   // beat the 256 x 256 form on every shape measured -- M = 50 208: N = 512, K = 512 99 vs 117 us, N = 1536 224 vs 252, N = 3072 (SwiGLU)
   // 410 vs 456; M = 10 848, N = 5120, K = 1280 364 vs 435; 8192^2 x 1024 334 vs 347; under-filled grids (M = 750 .. 2066) 1.8-2.5x --
   // three co-resident workgroups overlap one tile's store-bound epilogue with the others' main loops, and four times as many tiles
-  // quantise better over 256 CUs.  The 256 x 256 form stays in the source (CFG 0) as the measured alternative; nothing selects it.
-  const int cfg = 1;
-  const int BMh = cfg ? 128 : 256, BNh = cfg ? 128 : 256;
+  // quantise better over 256 CUs.
+  const int BMh = 128, BNh = 128;
   q.g.mtiles = cdiv(a.M, BMh);
   q.g.mt8 = cdiv(q.g.mtiles, 8);
   q.g.nblocks = cdiv(w.N, BNh);
@@ -399,19 +513,26 @@ int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w
   IDX_CHECK(grid < (1ll << 31), "grid size");
   static const int cat = prof_register("gemm_bf16x3_v2_kernel");
   ProfScope prof(cat, stream, flops, bytes);
-  const int lds = cfg ? 3 * (4 * 128 * 32) : 4 * (4 * 256 * 32);
+  const int lds = 3 * (4 * 128 * 32);
   const bool paired = a.act == ACT_SWIGLU || a.act == ACT_GATE;
   IDX_CHECK(!(a.rope && (a.res || paired)), "the rotary epilogue takes no residual and no paired activation");
   IDX_CHECK(!a.row_len || a.seq_len >= 16, "row masks need seq_len >= 16");
   const int epi = a.rope ? EPI_ROPE : paired ? EPI_PAIRED : a.act != ACT_NONE ? EPI_ACT : EPI_PLAIN;
   typedef void (*KernelFn)(const GemmV2P);
-#define V2_ROW(T, C) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, C>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, C>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, C>, gemm_bf16x3_v2_kernel<T, EPI_ACT, C>
-  static const KernelFn kernels[2][2][4] = {{{V2_ROW(false, 0)}, {V2_ROW(true, 0)}}, {{V2_ROW(false, 1)}, {V2_ROW(true, 1)}}};
-  static DynLdsLimit lds_limit[2];
-  IDX_HIP(lds_limit[0].set(4 * (4 * 256 * 32), V2_ROW(false, 0), V2_ROW(true, 0)));
-  IDX_HIP(lds_limit[1].set(3 * (4 * 128 * 32), V2_ROW(false, 1), V2_ROW(true, 1)));
+#define V2_ROW(T, F) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, F>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, F>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, F>, gemm_bf16x3_v2_kernel<T, EPI_ACT, F>
+  // the main loop's MFMA shape comes with the weights (model_util.h: WP16_ALWAYS_MF16): 16x16x32 is 1.5-7 % faster on six of eight
+  // shapes and equal on two (tools/gemm_ab.py, profiles/README.md "MFMA shape"), but its sums differ in the last bits from the
+  // 32x32x16 loop's, which the models that feed a choice of discrete codes keep
+  static const KernelFn kernels[2][2][4] = {{{V2_ROW(false, 32)}, {V2_ROW(true, 32)}}, {{V2_ROW(false, 16)}, {V2_ROW(true, 16)}}};
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set(lds, V2_ROW(false, 32), V2_ROW(true, 32), V2_ROW(false, 16), V2_ROW(true, 16)));
+  int mf16 = w.mf16 ? 1 : 0;
+#ifdef V2_EXP_SHAPE
+  if (const char* e = getenv("IDXTTS_EXP_V2_SHAPE")) mf16 = atoi(e) == 16;      // tools/gemm_ab.py's scratch build only
+#endif
+  const KernelFn kernel = kernels[mf16][a.taps > 1 ? 1 : 0][epi];
 #undef V2_ROW
-  hipLaunchKernelGGL(kernels[cfg][a.taps > 1 ? 1 : 0][epi], dim3((unsigned)grid), dim3(cfg ? 256 : 512), lds, stream, q);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, stream, q);
   IDX_LAUNCH_CHECK();
   return 0;
 }

@@ -21,8 +21,13 @@ int ln_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std:
 // Which linears get a split-bf16 pack (LinearWeights::wp16) beside the fp32 one.  gemm_forward runs a launch of >= 256 rows on the
 // split-bf16 kernels when the weights carry the pack, and on the exact fp32 kernel when they do not.
 enum Wp16Policy {
-  WP16_ALWAYS,      // every shape: s2mel, the GPT projections, idxtts_linear_create (N < 96 or K % 16 != 0 run on the tile kernels)
+  WP16_ALWAYS,      // every shape: the GPT projections (N < 96 or K % 16 != 0 run on the tile kernels)
   WP16_DMA_SHAPES,  // only shapes the LDS-DMA kernel takes (N >= 96, K % 16 == 0), the rest stays exact fp32: the small models
+  // every shape, and the LDS-DMA kernel's v_mfma_f32_16x16x32_bf16 loop (LinearWeights::mf16): s2mel and idxtts_linear_create.  That
+  // loop adds a row's k in another order than the 32x32x16 loop, so results move in the last bits.  Where they only become a waveform
+  // that is rounding; a GPT prefill into a bf16 cache, the conditioning and the semantic models feed a choice of discrete codes, where
+  // a last bit can flip a near-tie and change the whole utterance: those keep the sums they have always had.
+  WP16_ALWAYS_MF16,
 };
 enum WeightLayout { W_NK /* torch nn.Linear [N][K] */, W_KN /* HF Conv1D [K][N] (y = x @ W + b) */ };
 struct LinearOpts {

@@ -88,12 +88,12 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
   for (int i = 0; i < depth; ++i) {
     DiTBlock& B = blocks[i];
     const std::string p = e + ".transformer.layers." + std::to_string(i);
-    if (linear_from(t, arena, p + ".attention.wqkv", 3 * D, D, false, WP16_ALWAYS, &B.wqkv)) return 1;
-    if (linear_from(t, arena, p + ".attention.wo", D, D, false, WP16_ALWAYS, &B.wo)) return 1;
+    if (linear_from(t, arena, p + ".attention.wqkv", 3 * D, D, false, WP16_ALWAYS_MF16, &B.wqkv)) return 1;
+    if (linear_from(t, arena, p + ".attention.wo", D, D, false, WP16_ALWAYS_MF16, &B.wo)) return 1;
     HostTensor *w1 = nullptr, *w3 = nullptr;
     if (need(t, p + ".feed_forward.w1.weight", {ffn, D}, &w1) || need(t, p + ".feed_forward.w3.weight", {ffn, D}, &w3)) return 1;
-    if (make_linear(arena, pair_pack(w1->data.data(), w3->data.data(), ffn, D).data(), nullptr, 2 * ffn, D, {WP16_ALWAYS}, &B.w13)) return 1;
-    if (linear_from(t, arena, p + ".feed_forward.w2", D, ffn, false, WP16_ALWAYS, &B.w2)) return 1;
+    if (make_linear(arena, pair_pack(w1->data.data(), w3->data.data(), ffn, D).data(), nullptr, 2 * ffn, D, {WP16_ALWAYS_MF16}, &B.w13)) return 1;
+    if (linear_from(t, arena, p + ".feed_forward.w2", D, ffn, false, WP16_ALWAYS_MF16, &B.w2)) return 1;
     HostTensor *g = nullptr;
     if (need(t, p + ".attention_norm.norm.weight", {D}, &g) || up(arena, g->data, &B.attn_g)) return 1;
     if (need(t, p + ".ffn_norm.norm.weight", {D}, &g) || up(arena, g->data, &B.ffn_g)) return 1;
@@ -101,35 +101,35 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     if (i > depth / 2) {
       HostTensor *sw = nullptr, *sb = nullptr;
       if (need(t, p + ".skip_in_linear.weight", {D, 2 * D}, &sw) || need(t, p + ".skip_in_linear.bias", {D}, &sb)) return 1;
-      if (make_linear(arena, col_slice(sw->data, D, 2 * D, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS}, &B.skip_a)) return 1;
-      if (make_linear(arena, col_slice(sw->data, D, 2 * D, D, 2 * D).data(), nullptr, D, D, {WP16_ALWAYS}, &B.skip_b)) return 1;
+      if (make_linear(arena, col_slice(sw->data, D, 2 * D, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS_MF16}, &B.skip_a)) return 1;
+      if (make_linear(arena, col_slice(sw->data, D, 2 * D, D, 2 * D).data(), nullptr, D, D, {WP16_ALWAYS_MF16}, &B.skip_b)) return 1;
     }
   }
   {
     HostTensor* g = nullptr;
     if (need(t, e + ".transformer.norm.norm.weight", {D}, &g) || up(arena, g->data, &final_g)) return 1;
     if (append_mod(e + ".transformer.norm")) return 1;
-    if (make_linear(arena, mod_w.data(), mod_b.data(), (2 * depth + 1) * 2 * D, D, {WP16_ALWAYS}, &mod_all)) return 1;
+    if (make_linear(arena, mod_w.data(), mod_b.data(), (2 * depth + 1) * 2 * D, D, {WP16_ALWAYS_MF16}, &mod_all)) return 1;
   }
   const int Win = 2 * C + D + cfg.style_dim;
-  if (linear_from(t, arena, e + ".cond_projection", D, cfg.content_dim, true, WP16_ALWAYS, &cond_proj)) return 1;
-  if (linear_from(t, arena, e + ".cond_x_merge_linear", D, Win, true, WP16_ALWAYS, &merge)) return 1;
-  if (linear_from(t, arena, e + ".t_embedder.mlp.0", D, 256, true, WP16_ALWAYS, &temb0) || linear_from(t, arena, e + ".t_embedder.mlp.2", D, D, true, WP16_ALWAYS, &temb2)) return 1;
-  if (linear_from(t, arena, e + ".t_embedder2.mlp.0", Wh, 256, true, WP16_ALWAYS, &t2emb0) || linear_from(t, arena, e + ".t_embedder2.mlp.2", Wh, Wh, true, WP16_ALWAYS, &t2emb2)) return 1;
+  if (linear_from(t, arena, e + ".cond_projection", D, cfg.content_dim, true, WP16_ALWAYS_MF16, &cond_proj)) return 1;
+  if (linear_from(t, arena, e + ".cond_x_merge_linear", D, Win, true, WP16_ALWAYS_MF16, &merge)) return 1;
+  if (linear_from(t, arena, e + ".t_embedder.mlp.0", D, 256, true, WP16_ALWAYS_MF16, &temb0) || linear_from(t, arena, e + ".t_embedder.mlp.2", D, D, true, WP16_ALWAYS_MF16, &temb2)) return 1;
+  if (linear_from(t, arena, e + ".t_embedder2.mlp.0", Wh, 256, true, WP16_ALWAYS_MF16, &t2emb0) || linear_from(t, arena, e + ".t_embedder2.mlp.2", Wh, Wh, true, WP16_ALWAYS_MF16, &t2emb2)) return 1;
   {
     HostTensor *sw = nullptr, *sb = nullptr;
     if (need(t, e + ".skip_linear.weight", {D, D + C}, &sw) || need(t, e + ".skip_linear.bias", {D}, &sb)) return 1;
-    if (make_linear(arena, col_slice(sw->data, D, D + C, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS}, &skiplin_a)) return 1;
-    if (make_linear(arena, col_slice(sw->data, D, D + C, D, D + C).data(), nullptr, D, C, {WP16_ALWAYS}, &skiplin_b)) return 1;
+    if (make_linear(arena, col_slice(sw->data, D, D + C, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS_MF16}, &skiplin_a)) return 1;
+    if (make_linear(arena, col_slice(sw->data, D, D + C, D, D + C).data(), nullptr, D, C, {WP16_ALWAYS_MF16}, &skiplin_b)) return 1;
   }
-  if (linear_from(t, arena, e + ".conv1", Wh, D, true, WP16_ALWAYS, &conv1)) return 1;
-  if (linear_from(t, arena, e + ".res_projection", Wh, D, true, WP16_ALWAYS, &res_proj)) return 1;
-  if (linear_from(t, arena, e + ".final_layer.linear", Wh, Wh, true, WP16_ALWAYS, &final_lin)) return 1;
-  if (linear_from(t, arena, e + ".final_layer.adaLN_modulation.1", 2 * Wh, Wh, true, WP16_ALWAYS, &final_mod)) return 1;
+  if (linear_from(t, arena, e + ".conv1", Wh, D, true, WP16_ALWAYS_MF16, &conv1)) return 1;
+  if (linear_from(t, arena, e + ".res_projection", Wh, D, true, WP16_ALWAYS_MF16, &res_proj)) return 1;
+  if (linear_from(t, arena, e + ".final_layer.linear", Wh, Wh, true, WP16_ALWAYS_MF16, &final_lin)) return 1;
+  if (linear_from(t, arena, e + ".final_layer.adaLN_modulation.1", 2 * Wh, Wh, true, WP16_ALWAYS_MF16, &final_mod)) return 1;
   {
     HostTensor *w = nullptr, *b = nullptr;
     if (need(t, e + ".conv2.weight", {C, Wh, 1}, &w) || need(t, e + ".conv2.bias", {C}, &b)) return 1;
-    if (make_linear(arena, w->data.data(), b->data.data(), C, Wh, {WP16_ALWAYS}, &conv2)) return 1;      // (N = 80: the split-bf16 tile kernels)
+    if (make_linear(arena, w->data.data(), b->data.data(), C, Wh, {WP16_ALWAYS_MF16}, &conv2)) return 1;      // (N = 80: the split-bf16 tile kernels)
   }
   // ---- WaveNet ----
   const int L = cfg.wn_layers, k = cfg.wn_kernel;
@@ -145,7 +145,7 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
       HostTensor *iw = nullptr, *ib = nullptr;
       if (need(t, p + ".weight", {2 * Wh, Wh, k}, &iw) || need(t, p + ".bias", {2 * Wh}, &ib)) return 1;
       const std::vector<float> rows = conv_to_rows(iw->data, 2 * Wh, Wh, k);
-      if (make_linear(arena, pair_pack(rows.data(), rows.data() + (size_t)Wh * k * Wh, Wh, k * Wh).data(), nullptr, 2 * Wh, k * Wh, {WP16_ALWAYS}, &W.in_gate)) return 1;
+      if (make_linear(arena, pair_pack(rows.data(), rows.data() + (size_t)Wh * k * Wh, Wh, k * Wh).data(), nullptr, 2 * Wh, k * Wh, {WP16_ALWAYS_MF16}, &W.in_gate)) return 1;
       // cond_layer slice of this layer, same gate packing; its bias absorbs the in_layer bias
       const float* cwl = cw->data.data() + (size_t)l * 2 * Wh * Wh;
       const std::vector<float> cwp = pair_pack(cwl, cwl + (size_t)Wh * Wh, Wh, Wh);
@@ -161,17 +161,17 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
       if (l < L - 1) {
         std::vector<float> w_res(rw->data.begin(), rw->data.begin() + (size_t)Wh * Wh), b_res(rb->data.begin(), rb->data.begin() + Wh);
         std::vector<float> w_skip(rw->data.begin() + (size_t)Wh * Wh, rw->data.end()), b_skip(rb->data.begin() + Wh, rb->data.end());
-        if (make_linear(arena, w_res.data(), b_res.data(), Wh, Wh, {WP16_ALWAYS}, &W.res) || make_linear(arena, w_skip.data(), b_skip.data(), Wh, Wh, {WP16_ALWAYS}, &W.skip)) return 1;
+        if (make_linear(arena, w_res.data(), b_res.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.res) || make_linear(arena, w_skip.data(), b_skip.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.skip)) return 1;
       } else {
         W.has_res = false;
-        if (make_linear(arena, rw->data.data(), rb->data.data(), Wh, Wh, {WP16_ALWAYS}, &W.skip)) return 1;
+        if (make_linear(arena, rw->data.data(), rb->data.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.skip)) return 1;
       }
     }
-    if (make_linear(arena, cw_perm.data(), cb_perm.data(), 2 * Wh * L, Wh, {WP16_ALWAYS}, &wn_cond)) return 1;
+    if (make_linear(arena, cw_perm.data(), cb_perm.data(), 2 * Wh * L, Wh, {WP16_ALWAYS_MF16}, &wn_cond)) return 1;
   }
   // ---- length regulator, gpt_layer, codec table ----
   const int LC = cfg.lr_channels;
-  if (linear_from(t, arena, "length_regulator.content_in_proj", LC, cfg.lr_in_channels, true, WP16_ALWAYS, &lr_in)) return 1;
+  if (linear_from(t, arena, "length_regulator.content_in_proj", LC, cfg.lr_in_channels, true, WP16_ALWAYS_MF16, &lr_in)) return 1;
   lr_conv.resize(cfg.lr_num_convs);
   lr_gn_g.resize(cfg.lr_num_convs);
   lr_gn_b.resize(cfg.lr_num_convs);
@@ -179,7 +179,7 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     HostTensor *w = nullptr, *b = nullptr, *g = nullptr, *bb = nullptr;
     const std::string p = "length_regulator.model." + std::to_string(3 * n);
     if (need(t, p + ".weight", {LC, LC, 3}, &w) || need(t, p + ".bias", {LC}, &b)) return 1;
-    if (make_linear(arena, conv_to_rows(w->data, LC, LC, 3).data(), b->data.data(), LC, 3 * LC, {WP16_ALWAYS}, &lr_conv[n])) return 1;
+    if (make_linear(arena, conv_to_rows(w->data, LC, LC, 3).data(), b->data.data(), LC, 3 * LC, {WP16_ALWAYS_MF16}, &lr_conv[n])) return 1;
     const std::string q = "length_regulator.model." + std::to_string(3 * n + 1);
     if (need(t, q + ".weight", {LC}, &g) || need(t, q + ".bias", {LC}, &bb)) return 1;
     if (up(arena, g->data, &lr_gn_g[n]) || up(arena, bb->data, &lr_gn_b[n])) return 1;
@@ -188,12 +188,12 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     HostTensor *w = nullptr, *b = nullptr;
     const std::string p = "length_regulator.model." + std::to_string(3 * cfg.lr_num_convs);
     if (need(t, p + ".weight", {LC, LC, 1}, &w) || need(t, p + ".bias", {LC}, &b)) return 1;
-    if (make_linear(arena, w->data.data(), b->data.data(), LC, LC, {WP16_ALWAYS}, &lr_out)) return 1;
+    if (make_linear(arena, w->data.data(), b->data.data(), LC, LC, {WP16_ALWAYS_MF16}, &lr_out)) return 1;
   }
   {
     const int dims[4] = {cfg.gpt_dim, cfg.gpt_layer_dims[0], cfg.gpt_layer_dims[1], cfg.gpt_layer_dims[2]};
     for (int n = 0; n < 3; ++n)
-      if (linear_from(t, arena, "gpt_layer." + std::to_string(n), dims[n + 1], dims[n], true, WP16_ALWAYS, &gl[n])) return 1;
+      if (linear_from(t, arena, "gpt_layer." + std::to_string(n), dims[n + 1], dims[n], true, WP16_ALWAYS_MF16, &gl[n])) return 1;
     IDX_CHECK(dims[3] == cfg.codec_hidden && cfg.codec_hidden == cfg.lr_in_channels, "gpt_layer / codec / length-regulator widths");
   }
   {

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """In-kernel s_memtime stamps of the LDS-DMA GEMM (diagnostic build of the library: tools/build_timing_lib.sh ->
 tools/libidxtts_timing.so, gemm_bf16x3_v2.hip compiled with -DV2_TIMING).  Per workgroup (wave 1): cycles from start to the
-first stage landed, main loop, epilogue (incl. store drain), and the in-kernel clock (s_memtime / s_memrealtime)."""
+first stage landed, main loop, epilogue (incl. store drain), and the in-kernel clock (s_memtime / s_memrealtime) of a launch that
+follows 2 s of back-to-back launches.  A library built with DEFS="-DV2_TIMING -DV2_EXP_SHAPE" stamps the loop that
+IDXTTS_EXP_V2_SHAPE (32 or 16) names."""
 import ctypes
 import os
 import sys
+import time
 from ctypes import c_void_p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,8 +37,11 @@ def run(M, N, K, act, with_res):
         _lib.check(lib.idxtts_linear_fwd(h, _lib.ptr(x), K, _lib.ptr(y), n_out, _lib.ptr(res) if with_res else None, n_out if with_res else 0, M, act, 1, st))
 
     lib.idxtts_dbg_v2_stamps(None)
-    for _ in range(20):
-        call()
+    t_end = time.time() + 2.0
+    while time.time() < t_end:
+        for _ in range(20):
+            call()
+        torch.cuda.synchronize()
     lib.idxtts_dbg_v2_stamps(c_void_p(stamps.data_ptr()))
     call()
     torch.cuda.synchronize()
