@@ -14,9 +14,11 @@ pytestmark = pytest.mark.gpu
 # fp32 kernels vs fp32 reference: differences are summation order + sin implementation only.
 ACT_ATOL = 1e-5
 CONV_RTOL = 2e-5
-# Every test runs in both arithmetic modes: "f32" = exact-fp32 MFMA everywhere (tolerances above); "bf16x3" = the wide
-# convolutions (> 96 output rows) on bf16 MFMAs with split operands (3 MFMAs per product, ~2^-16 relative per product):
-# tolerances x TOL["m"].
+# Every test runs in both arithmetic modes: "f32" = exact-fp32 MFMA everywhere (tolerances above); "bf16x3" = EVERY
+# convolution (conv1d_forward sends all four tile configurations to conv1d_bf16x3.hip in that mode) on bf16 MFMAs with split
+# operands (3 MFMAs per product, ~2^-16 relative per product): tolerances x TOL["m"].
+# The tile edges, M thresholds, epilogue forms, K1 instances and tile walks of these kernels are pinned one by one in
+# tests/test_vocoder_dispatch_gpu.py.
 TOL = {"m": 1.0}
 
 
@@ -83,7 +85,9 @@ def test_aa_act_half_precision_io(device, dtype):
 @pytest.mark.parametrize("shape", [(1, 1, 1), (1, 3, 2), (2, 5, 3), (1, 2, 5), (1, 4, 1023), (1, 3, 1024), (2, 3, 1025),
                                    (1, 2, 1030), (1, 24, 2048 + 7), (3, 7, 4096), (1, 1, 5000)])
 def test_aa_act_vs_oracle_ragged(device, shape):
-    """tile edges (1024-sample tiles), lengths not multiple of 4, and tiny T where pads dominate."""
+    """Multi-tile lengths (tiles are AA_TILE = 1016 samples, four to a workgroup; these lengths date from 1024-sample tiles and
+    sit next to no tile edge -- the edges themselves are in tests/test_vocoder_dispatch_gpu.py), lengths not multiple of 4, and
+    tiny T where pads dominate."""
     from indextts_amd.vocoder import anti_alias_activation_forward
     from oracle import vocoder as ov
     B, C, T = shape
@@ -209,7 +213,8 @@ def test_bigvgan_matches_reference_golden(device, golden_dir):
 
 
 def test_bigvgan_vs_oracle_mid_width(device):
-    """Width 256 (channels 128..4): exercises every conv tile configuration; oracle on CPU in ~seconds."""
+    """Width 256 (channels 256, 128, 64, 32, ... 4): the 128-, 64- and 32-row conv tile configurations, not the 96-row one (65..96
+    rows; tests/test_vocoder_dispatch_gpu.py runs it, at width 192); oracle on CPU in ~seconds."""
     from indextts_amd.vocoder import BigVGAN
     from oracle import vocoder as ov
     cfg = BigVGANConfig.tiny(256)
