@@ -377,6 +377,12 @@ size_t idxtts_cond_workspace_bytes(const idxtts_ctx* ctx, int B, int T);
  * clamped: the reference passes the feature width 1024 as "length", infer_v2.py:751-752, i.e. no padding). */
 int idxtts_cond_forward(idxtts_ctx* ctx, const float* feats, const int* lengths, int B, int T, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* The same for several prompts of different lengths, right-padded into one batch, each row computing what its OWN unpadded call of
+ * idxtts_cond_forward computes (the reference runs these encoders on one prompt at a time, infer_v2.py:748-754, model_v2.py:819; its
+ * masks alone do not give that: a padded frame's pointwise-conv bias reaches the last valid frames through the depthwise taps).
+ * extents: HOST int32 [B], the frames row b really holds (3 .. T); lengths: as above, what the row's own call would be given, or NULL. */
+int idxtts_cond_forward_rows(idxtts_ctx* ctx, const float* feats, const int* lengths, const int* extents, int B, int T, float* out,
+                             void* workspace, size_t workspace_bytes, void* stream);
 /* out = base + alpha * (emo - base) over n floats (merge_emovec, model_v2.py:904-910). */
 int idxtts_emovec_merge(float* out, const float* base, const float* emo, float alpha, size_t n, void* stream);
 
@@ -428,6 +434,41 @@ size_t idxtts_melspec_workspace_bytes(const idxtts_ctx* ctx, int B, int n_sample
 /* audio: device [B][n_samples] in [-1, 1]; mel: device [B][num_mels][frames] = log(clamp(mel_basis @ |STFT|, 1e-5)). */
 int idxtts_melspec_forward(idxtts_ctx* ctx, const float* audio, int B, int n_samples, float* mel, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/* ---- Kaldi filter bank of the 16 kHz prompt audio, for a ragged batch of prompts (replaces the host numpy of
+ * indextts_amd/features.py: `SeamlessM4TFeatureExtractor(audio_16k)`, infer_v2.py:633, 680, and `torchaudio.compliance.kaldi.fbank(
+ * audio_16k, num_mel_bins=80, dither=0, sample_frequency=16000)` minus its mean over time, infer_v2.py:641-646) -------------
+ * snip_edges framing, per frame: mean removal, pre-emphasis, window, power spectrum, mel filters, log(max(., 2^-23)).
+ * Tensors of the context: "window" [frame_length] (povey) and "mel_filters" [num_mel_bins][fft_length/2+1] (Kaldi's get_mel_banks). */
+typedef struct idxtts_fbank_config {
+  int frame_length, hop_length, fft_length, num_mel_bins;      /* 400, 160, 512, 80 */
+  float preemphasis;                                           /* 0.97 */
+} idxtts_fbank_config;
+#define IDXTTS_FBANK_RAW 0        /* the log-mel energies themselves (kaldi.fbank) */
+#define IDXTTS_FBANK_CAMPPLUS 1   /* minus every bin's mean over the row's own frames (infer_v2.py:646) */
+#define IDXTTS_FBANK_W2VBERT 2    /* every bin normalised over the row's own frames (mean, variance with ddof = 1, + 1e-7), frames stacked in pairs */
+int idxtts_fbank_create(const idxtts_fbank_config* cfg, idxtts_ctx** out);
+int idxtts_fbank_frames(const idxtts_ctx* ctx, int n_samples);       /* n_samples < frame_length ? 0 : 1 + (n_samples - frame_length) / hop_length */
+/* n_samples: HOST int32 [B] */
+size_t idxtts_fbank_workspace_bytes(const idxtts_ctx* ctx, const int* n_samples, int B);
+/* audio: device [B][ld_audio], row b holds n_samples[b] (HOST int32 [B], each >= frame_length) samples, multiplied by `scale` before
+ * anything else (2^15 for w2v-BERT, 1 for CAMPPlus).  out: device, zero at every padded position;
+ *   RAW / CAMPPLUS: [B][T_out][num_mel_bins], T_out >= the longest row's frames;
+ *   W2VBERT:        [B][T_out][2 * num_mel_bins], T_out >= ceil(longest row's frames / 2); every row needs two frames; an odd frame
+ *                   count leaves a last row (frame | zeros), which the extractor's attention mask does not count (valid = frames / 2).
+ * Both GEMMs are exact fp32 whatever the GEMM mode: a row's result does not depend on the rows beside it. */
+int idxtts_fbank_forward(idxtts_ctx* ctx, const float* audio, int ld_audio, const int* n_samples, int B, float scale, int mode, float* out,
+                         int T_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- polyphase windowed-sinc resampler for a ragged batch of one rate pair (replaces the host `audioio.sinc_resample`, i.e.
+ * `torchaudio.transforms.Resample(orig, new)`, infer_v2.py:629-630; torchaudio/functional/functional.py::_apply_sinc_resample_kernel) ----
+ * orig / new: the two rates divided by their gcd.  kernel_t: device [2 * width + orig][new], the TRANSPOSE of torchaudio's
+ * `_get_sinc_resample_kernel` table (float32).  x: device [B][ldx], row b holds lengths[b] (HOST int32 [B], >= 0) samples.
+ * out: device [B][ldo], ldo >= ceil(new * max length / orig): out[b][f * new + p] = sum_t padded_b[f * orig + t] * kernel[p][t] for the
+ * first ceil(new * lengths[b] / orig) positions (padded_b = `width` zeros, the row, zeros), 0 behind them.  Products are summed in
+ * float64 and rounded once.  No context: the table belongs to the caller. */
+int idxtts_resample_forward(const float* kernel_t, int orig, int new_rate, int width, const float* x, int ldx, const int* lengths, int B,
+                            float* out, int ldo, void* stream);
 
 /* ---- CAMPPlus speaker encoder: the global style vector of the prompt (reference: `style = self.campplus_model(feat.unsqueeze(0))`,
  * infer_v2.py:251-257, 641-647; CAMPPlus, s2mel/modules/campplus/DTDNN.py:62-140, layers.py) ------------------------------

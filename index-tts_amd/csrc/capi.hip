@@ -11,6 +11,7 @@
 #include "campplus.h"
 #include "conv1d.h"
 #include "ctx.h"
+#include "fbank.h"
 #include "gpt.h"
 #include "model_util.h"
 #include "s2mel.h"
@@ -558,6 +559,18 @@ int idxtts_cond_forward(idxtts_ctx* ctx, const float* feats, const int* lengths,
   API_END
 }
 
+int idxtts_cond_forward_rows(idxtts_ctx* ctx, const float* feats, const int* lengths, const int* extents, int B, int T, float* out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  IDX_CHECK(ctx, "null ctx");
+  IDX_CHECK(ctx->finalized, "context not finalized");
+  auto* m = dynamic_cast<CondModel*>(ctx->model.get());
+  IDX_CHECK(m, "not a conditioning-encoder context");
+  IDX_CHECK(extents, "null extents");
+  return m->forward(feats, lengths, B, T, out, workspace, workspace_bytes, static_cast<hipStream_t>(stream), extents);
+  API_END
+}
+
 int idxtts_w2vbert_create(const idxtts_w2vbert_config* cfg, idxtts_ctx** out) {
   API_BEGIN
   IDX_CHECK(cfg && out, "null pointer");
@@ -642,6 +655,46 @@ int idxtts_melspec_forward(idxtts_ctx* ctx, const float* audio, int B, int n_sam
   auto* m = dynamic_cast<MelSpecModel*>(ctx->model.get());
   IDX_CHECK(m, "not a mel-spectrogram context");
   return m->forward(audio, B, n_samples, mel, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_fbank_create(const idxtts_fbank_config* cfg, idxtts_ctx** out) {
+  API_BEGIN
+  IDX_CHECK(cfg && out, "null pointer");
+  std::unique_ptr<idxtts_ctx> ctx(new idxtts_ctx());
+  ctx->model.reset(new FbankModel(*cfg));
+  *out = ctx.release();
+  return 0;
+  API_END
+}
+
+int idxtts_fbank_frames(const idxtts_ctx* ctx, int n_samples) {
+  if (!ctx || n_samples <= 0) return 0;
+  auto* m = dynamic_cast<const FbankModel*>(ctx->model.get());
+  return m && m->cfg.frame_length > 0 && m->cfg.hop_length > 0 ? m->frames(n_samples) : 0;
+}
+
+size_t idxtts_fbank_workspace_bytes(const idxtts_ctx* ctx, const int* n_samples, int B) {
+  if (!ctx || !ctx->finalized || !n_samples || B <= 0) return 0;
+  auto* m = dynamic_cast<const FbankModel*>(ctx->model.get());
+  return m ? m->workspace_bytes(n_samples, B) : 0;
+}
+
+int idxtts_fbank_forward(idxtts_ctx* ctx, const float* audio, int ld_audio, const int* n_samples, int B, float scale, int mode, float* out,
+                         int T_out, void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  IDX_CHECK(ctx, "null ctx");
+  IDX_CHECK(ctx->finalized, "context not finalized");
+  auto* m = dynamic_cast<FbankModel*>(ctx->model.get());
+  IDX_CHECK(m, "not a filter-bank context");
+  return m->forward(audio, ld_audio, n_samples, B, scale, mode, out, T_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_resample_forward(const float* kernel_t, int orig, int new_rate, int width, const float* x, int ldx, const int* lengths, int B,
+                            float* out, int ldo, void* stream) {
+  API_BEGIN
+  return resample_forward(kernel_t, orig, new_rate, width, x, ldx, lengths, B, out, ldo, static_cast<hipStream_t>(stream));
   API_END
 }
 

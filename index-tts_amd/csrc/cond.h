@@ -41,7 +41,8 @@ struct CondModel : ModelBase {
   bool accepts(const std::string& name) const override;
   int finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena) override;
   size_t workspace_bytes(int B, int T) const;
-  int forward(const float* feats, const int* lens_host, int B, int T, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+  int forward(const float* feats, const int* lens_host, int B, int T, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+              const int* extents_host = nullptr);      // extents: idxtts_cond_forward_rows
 };
 
 }  // namespace idxtts

@@ -131,7 +131,7 @@ namespace {
 struct CondBuf {
   float *a, *slab, *xa, *xb, *h, *h2, *qkv, *att, *pw, *ff, *posp;
   float *ctxp, *lat, *lat2, *cat, *kv, *q, *o, *ffh, *ffg, *ev;
-  int *len2, *kend;
+  int *len2, *kend, *ext2;
   int T2, ksplit;
   size_t bytes;
 };
@@ -179,6 +179,7 @@ CondBuf carve(const CondModel& m, void* ws, int B, int T) {
   b.ev = k.take<float>((size_t)B * std::max(c.model_dim, dim));
   b.len2 = k.take<int>(B);
   b.kend = k.take<int>(B);
+  b.ext2 = k.take<int>(B);
   b.bytes = (k.off + 255) & ~(size_t)255;
   return b;
 }
@@ -187,7 +188,8 @@ CondBuf carve(const CondModel& m, void* ws, int B, int T) {
 
 size_t CondModel::workspace_bytes(int B, int T) const { return carve(*this, nullptr, B, T).bytes; }
 
-int CondModel::forward(const float* feats, const int* lens_host, int B, int T, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+int CondModel::forward(const float* feats, const int* lens_host, int B, int T, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                       const int* extents_host) {
   IDX_CHECK(feats && out, "null pointer");
   IDX_CHECK(B > 0 && T >= 3, "Conv2dSubsampling2 needs at least 3 frames");
   IDX_CHECK(ws && ws_bytes >= workspace_bytes(B, T), "workspace too small");
@@ -197,18 +199,29 @@ int CondModel::forward(const float* feats, const int* lens_host, int B, int T, f
   IDX_CHECK(T2 <= pe_len, "prompt longer than the positional-encoding table");
   // subsampled valid lengths: mask[:, :, 2::2] of (t < len)  (subsampling.py:181); len > T means "no padding" (the reference
   // passes shape[-1] = 1024 here, infer_v2.py:751-752)
-  std::vector<int> len2(B, T2), kend(B);
-  bool ragged = false;
+  // extents (idxtts_cond_forward_rows): the frames a row really holds.  The reference masks a padded frame at the convolution module's
+  // input only, so its pointwise bias still reaches the last valid frames through the depthwise taps: a right-padded row is not its own
+  // unpadded call (conformer_encoder.py:114-164).  Behind a row's extent the gated rows are zeroed as well, which is what the depthwise
+  // convolution's own zero padding gives the row alone.
+  std::vector<int> len2(B, T2), kend(B), ext2(B, T2);
+  bool ragged = false, padded = false;
   for (int b = 0; b < B; ++b) {
+    if (extents_host) {
+      IDX_CHECK(extents_host[b] >= 3 && extents_host[b] <= T, "a row's extent is 3 .. T frames");
+      ext2[b] = (extents_host[b] - 3) / 2 + 1;
+      len2[b] = ext2[b];
+    }
     if (lens_host) {
       IDX_CHECK(lens_host[b] >= 3, "a prompt needs at least 3 valid frames");
       const int l = std::min(lens_host[b], T);
-      len2[b] = std::min(T2, (l - 3) / 2 + 1);
+      len2[b] = std::min(len2[b], (l - 3) / 2 + 1);
     }
     ragged = ragged || len2[b] != T2;
+    padded = padded || ext2[b] != T2;
     kend[b] = n + len2[b];
   }
   IDX_HIP(hipMemcpyAsync(w.len2, len2.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  if (padded) IDX_HIP(hipMemcpyAsync(w.ext2, ext2.data(), B * sizeof(int), hipMemcpyHostToDevice, st));      // idxtts_cond_forward: never
   IDX_HIP(hipMemcpyAsync(w.kend, kend.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));      // the host vectors go out of scope
   // ---- Conv2dSubsampling2: conv + ReLU -> [M][D*F2]; Linear (split-K) ; x * sqrt(D) folded in ----
@@ -241,6 +254,7 @@ int CondModel::forward(const float* feats, const int* lens_host, int B, int T, f
     if (layer_norm(x, w.h, L.conv_g, L.conv_b, M, D, st)) return 1;
     if (ragged && mask_rows(w.h, M, D, T2, w.len2, st)) return 1;
     if (lin(L.pw1, w.h, D, w.pw, 2 * D, M, st)) return 1;
+    if (padded && mask_rows(w.pw, M, 2 * D, T2, w.ext2, st)) return 1;      // a zero row stays zero through the GLU
     if (glu_dwconv_ln_silu(w.h2, w.pw, L.dw_w, L.dw_b, L.dwn_g, L.dwn_b, B, T2, D, cfg.cnn_kernel, st)) return 1;
     if (lin(L.pw2, w.h2, D, y, D, M, st, ACT_NONE, x, D)) return 1;
     std::swap(x, y);

@@ -28,6 +28,7 @@ enum Wp16Policy {
   // that is rounding; a GPT prefill into a bf16 cache, the conditioning and the semantic models feed a choice of discrete codes, where
   // a last bit can flip a near-tie and change the whole utterance: those keep the sums they have always had.
   WP16_ALWAYS_MF16,
+  WP16_NONE,        // no split-bf16 pack: weights only lin_exact ever reads (the filter bank's DFT and mel matrices)
 };
 enum WeightLayout { W_NK /* torch nn.Linear [N][K] */, W_KN /* HF Conv1D [K][N] (y = x @ W + b) */ };
 struct LinearOpts {

@@ -57,7 +57,7 @@ int make_linear(DeviceArena& arena, const float* w, const float* bias, int N, in
   if (up(arena, packed, &out->wp)) return 1;
   out->N = N; out->K = Kpad;
   out->mf16 = o.wp16 == WP16_ALWAYS_MF16;
-  if (o.wp16 != WP16_DMA_SHAPES || (N >= 96 && Kpad % 16 == 0)) {
+  if (o.wp16 != WP16_NONE && (o.wp16 != WP16_DMA_SHAPES || (N >= 96 && Kpad % 16 == 0))) {
     std::vector<float> p16((linear_bf16x3_packed_bytes(N, Kpad) + 3) / 4);
     pack_linear_bf16x3(p16.data(), w, N, Kpad);
     const float* d16 = nullptr;

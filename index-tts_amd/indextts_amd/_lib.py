@@ -29,10 +29,11 @@ SYMBOLS = [
     "idxtts_gpt_session_admit_beam",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
-    "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_emovec_merge",
+    "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
     "idxtts_gpt_graph_cache_entries", "idxtts_w2vbert_create", "idxtts_w2vbert_workspace_bytes", "idxtts_w2vbert_forward",
     "idxtts_repcodec_create", "idxtts_repcodec_workspace_bytes", "idxtts_repcodec_quantize",
     "idxtts_melspec_create", "idxtts_melspec_frames", "idxtts_melspec_workspace_bytes", "idxtts_melspec_forward",
+    "idxtts_fbank_create", "idxtts_fbank_frames", "idxtts_fbank_workspace_bytes", "idxtts_fbank_forward", "idxtts_resample_forward",
     "idxtts_campplus_create", "idxtts_campplus_workspace_bytes", "idxtts_campplus_forward",
     "idxtts_qwen_create", "idxtts_qwen_set_weight_format", "idxtts_qwen_workspace_bytes", "idxtts_qwen_generate",
     "idxtts_qwen_step_graph_launches", "idxtts_qwen_max_batch", "idxtts_qwen_batch_workspace_bytes", "idxtts_qwen_generate_batch",
@@ -76,6 +77,10 @@ class RepCodecConfigC(ctypes.Structure):     # idxtts_repcodec_config (include/i
 
 class MelSpecConfigC(ctypes.Structure):      # idxtts_melspec_config (include/idxtts.h)
     _fields_ = [(n, c_int) for n in ("n_fft", "hop_size", "win_size", "num_mels")]
+
+
+class FbankConfigC(ctypes.Structure):       # idxtts_fbank_config (include/idxtts.h)
+    _fields_ = [(n, c_int) for n in ("frame_length", "hop_length", "fft_length", "num_mel_bins")] + [("preemphasis", c_float)]
 
 
 class CamPPlusConfigC(ctypes.Structure):     # idxtts_campplus_config (include/idxtts.h)
@@ -203,6 +208,7 @@ def load() -> ctypes.CDLL:
     lib.idxtts_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
     lib.idxtts_cond_workspace_bytes.restype = c_size_t
     lib.idxtts_cond_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_cond_forward_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_emovec_merge.argtypes = [c_void_p, c_void_p, c_void_p, c_float, c_size_t, c_void_p]
     lib.idxtts_campplus_create.argtypes = [POINTER(CamPPlusConfigC), POINTER(c_void_p)]
     lib.idxtts_campplus_workspace_bytes.argtypes = [c_void_p, c_int]
@@ -213,6 +219,12 @@ def load() -> ctypes.CDLL:
     lib.idxtts_melspec_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
     lib.idxtts_melspec_workspace_bytes.restype = c_size_t
     lib.idxtts_melspec_forward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_fbank_create.argtypes = [POINTER(FbankConfigC), POINTER(c_void_p)]
+    lib.idxtts_fbank_frames.argtypes = [c_void_p, c_int]
+    lib.idxtts_fbank_workspace_bytes.argtypes = [c_void_p, c_void_p, c_int]
+    lib.idxtts_fbank_workspace_bytes.restype = c_size_t
+    lib.idxtts_fbank_forward.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+    lib.idxtts_resample_forward.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]
     lib.idxtts_repcodec_create.argtypes = [POINTER(RepCodecConfigC), POINTER(c_void_p)]
     lib.idxtts_repcodec_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
     lib.idxtts_repcodec_workspace_bytes.restype = c_size_t
@@ -321,6 +333,7 @@ def profile_read() -> dict:
 
 
 GEMM_F32, GEMM_BF16X3 = 0, 1
+FBANK_RAW, FBANK_CAMPPLUS, FBANK_W2VBERT = 0, 1, 2      # IDXTTS_FBANK_* (include/idxtts.h)
 SESSION_SAMPLED = 1      # IDXTTS_SESSION_SAMPLED (include/idxtts.h)
 
 

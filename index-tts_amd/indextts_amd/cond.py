@@ -38,8 +38,9 @@ class _Encoder:
             _lib.load_state_dict(h, sd)
         self._ws = None
 
-    def __call__(self, feats: torch.Tensor, lengths) -> torch.Tensor:
-        """feats [B,T,input_size] -> [B,latents,dim] (speaker) or the emotion vector [B,model_dim]."""
+    def __call__(self, feats: torch.Tensor, lengths, extents=None) -> torch.Tensor:
+        """feats [B,T,input_size] -> [B,latents,dim] (speaker) or the emotion vector [B,model_dim].  `extents` [B]: the frames each
+        right-padded row really holds; every row then computes what its own unpadded call computes (idxtts_cond_forward_rows)."""
         lib = _lib.load()
         x = feats.to(self.device, torch.float32).contiguous()
         B, T, _ = x.shape
@@ -52,6 +53,14 @@ class _Encoder:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         out = torch.empty((B,) + self.out_shape, device=self.device, dtype=torch.float32)
+        if extents is not None:
+            ex = np.ascontiguousarray(np.asarray(torch.as_tensor(extents).detach().cpu()).reshape(-1), dtype=np.int32)
+            if ex.shape != (B,):
+                raise ValueError("extents: one frame count per row")
+            _lib.check(lib.idxtts_cond_forward_rows(self._h, _lib.ptr(x), c_void_p(ln.ctypes.data) if ln is not None else c_void_p(0),
+                                                    c_void_p(ex.ctypes.data), B, T, _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(),
+                                                    _lib.current_stream()))
+            return out
         _lib.check(lib.idxtts_cond_forward(self._h, _lib.ptr(x), c_void_p(ln.ctypes.data) if ln is not None else c_void_p(0), B, T,
                                            _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()))
         return out
@@ -80,16 +89,16 @@ class ConditioningEncoders:
     def has_weights(state_dict) -> bool:
         return any(k.startswith("conditioning_encoder.") for k in state_dict)
 
-    def get_conditioning(self, speech_conditioning_input: torch.Tensor, cond_mel_lengths=None) -> torch.Tensor:
-        return self.spk(speech_conditioning_input.transpose(1, 2), cond_mel_lengths)
+    def get_conditioning(self, speech_conditioning_input: torch.Tensor, cond_mel_lengths=None, extents=None) -> torch.Tensor:
+        return self.spk(speech_conditioning_input.transpose(1, 2), cond_mel_lengths, extents)
 
-    def get_emovec(self, emo_speech_conditioning_latent: torch.Tensor, emo_cond_lengths=None) -> torch.Tensor:
-        return self.emo(emo_speech_conditioning_latent, emo_cond_lengths)
+    def get_emovec(self, emo_speech_conditioning_latent: torch.Tensor, emo_cond_lengths=None, extents=None) -> torch.Tensor:
+        return self.emo(emo_speech_conditioning_latent, emo_cond_lengths, extents)
 
     def merge_emovec(self, speech_conditioning_latent, emo_speech_conditioning_latent, cond_lengths=None, emo_cond_lengths=None,
-                     alpha: float = 1.0) -> torch.Tensor:
-        emo_vec = self.get_emovec(emo_speech_conditioning_latent, emo_cond_lengths)
-        base_vec = self.get_emovec(speech_conditioning_latent, cond_lengths)
+                     alpha: float = 1.0, extents=None, emo_extents=None) -> torch.Tensor:
+        emo_vec = self.get_emovec(emo_speech_conditioning_latent, emo_cond_lengths, emo_extents)
+        base_vec = self.get_emovec(speech_conditioning_latent, cond_lengths, extents)
         out = torch.empty_like(base_vec)
         _lib.check(_lib.load().idxtts_emovec_merge(_lib.ptr(out), _lib.ptr(base_vec), _lib.ptr(emo_vec), float(alpha), out.numel(),
                                                    _lib.current_stream()))

@@ -146,15 +146,18 @@ class UnifiedVoice:
             raise RuntimeError("this UnifiedVoice was built without conditioning_encoder / perceiver_encoder weights")
         return self.cond
 
-    def get_conditioning(self, speech_conditioning_input: torch.Tensor, cond_mel_lengths=None) -> torch.Tensor:
-        """[B,1024,T] (transposed features, as model_v2.py:819 passes them) -> [B,32,d]."""
-        return self._need_cond().get_conditioning(speech_conditioning_input, cond_mel_lengths)
+    def get_conditioning(self, speech_conditioning_input: torch.Tensor, cond_mel_lengths=None, extents=None) -> torch.Tensor:
+        """[B,1024,T] (transposed features, as model_v2.py:819 passes them) -> [B,32,d].  `extents` [B] (here and below): the frames each
+        right-padded row holds, for a batch of several prompts in which every row computes what its own call computes (cond.py)."""
+        return self._need_cond().get_conditioning(speech_conditioning_input, cond_mel_lengths, extents)
 
-    def get_emovec(self, emo_speech_conditioning_latent: torch.Tensor, emo_cond_lengths=None) -> torch.Tensor:
-        return self._need_cond().get_emovec(emo_speech_conditioning_latent, emo_cond_lengths)
+    def get_emovec(self, emo_speech_conditioning_latent: torch.Tensor, emo_cond_lengths=None, extents=None) -> torch.Tensor:
+        return self._need_cond().get_emovec(emo_speech_conditioning_latent, emo_cond_lengths, extents)
 
-    def merge_emovec(self, speech_conditioning_latent, emo_speech_conditioning_latent, cond_lengths=None, emo_cond_lengths=None, alpha=1.0):
-        return self._need_cond().merge_emovec(speech_conditioning_latent, emo_speech_conditioning_latent, cond_lengths, emo_cond_lengths, alpha)
+    def merge_emovec(self, speech_conditioning_latent, emo_speech_conditioning_latent, cond_lengths=None, emo_cond_lengths=None, alpha=1.0,
+                     extents=None, emo_extents=None):
+        return self._need_cond().merge_emovec(speech_conditioning_latent, emo_speech_conditioning_latent, cond_lengths, emo_cond_lengths, alpha,
+                                              extents, emo_extents)
 
     def conds_latent(self, speech_conditioning_latent: torch.Tensor, emo_vec: torch.Tensor) -> torch.Tensor:
         """cat(latent + emo_vec, speed_emb(1), speed_emb(0)) -> [B, 34, d]   (model_v2.py:830-834)."""

@@ -93,6 +93,34 @@ class PromptConditioning:
         return PromptConditioning(latent, emovec, feats.style, feats.prompt_condition, feats.ref_mel)
 
     @staticmethod
+    def from_features_batch(gpt: UnifiedVoice, feats_list, emo_alpha: float = 1.0) -> list:
+        """`from_features` of several prompts (PromptEncoders.encode_batch) with `get_conditioning` and `merge_emovec` run ONCE over the
+        ragged batch: the features are right-padded and the conditioning encoders take each row's own frame count as its extent
+        (idxtts_cond_forward_rows: every row computes what its own unpadded call computes; the reference's masks alone do not give
+        that) beside the "length" `from_features` passes, the reference's `shape[-1]`.
+        -> one PromptConditioning per prompt, as `cond=` of synthesize_batch / BatchPipeline / ContinuousPipeline takes them."""
+        feats_list = list(feats_list)
+        if not feats_list:
+            raise ValueError("from_features_batch needs at least one PromptFeatures")
+        for f in feats_list:
+            if f.spk_cond_emb.dim() != 3 or int(f.spk_cond_emb.shape[0]) != 1:
+                raise ValueError("every PromptFeatures holds one prompt: spk_cond_emb [1, T, features]")
+        dev = gpt.device
+
+        def pad(rows):
+            ln = [int(r.shape[1]) for r in rows]
+            x = torch.zeros(len(rows), max(ln), rows[0].shape[2], device=dev, dtype=torch.float32)
+            for i, r in enumerate(rows):
+                x[i, : ln[i]] = r[0].to(dev, torch.float32)
+            return x, torch.tensor([int(rows[0].shape[2])] * len(rows)), torch.tensor(ln)
+
+        spk, ln_s, ex_s = pad([f.spk_cond_emb for f in feats_list])
+        emo, ln_e, ex_e = pad([f.spk_cond_emb if f.emo_cond_emb is None else f.emo_cond_emb for f in feats_list])
+        emovec = gpt.merge_emovec(spk, emo, ln_s, ln_e, alpha=emo_alpha, extents=ex_s, emo_extents=ex_e)
+        latent = gpt.get_conditioning(spk.transpose(1, 2), ln_s, extents=ex_s)
+        return [PromptConditioning(latent[i:i + 1], emovec[i:i + 1], f.style, f.prompt_condition, f.ref_mel) for i, f in enumerate(feats_list)]
+
+    @staticmethod
     def mix_emovec(emovec: torch.Tensor, emo_mix) -> torch.Tensor:
         """The prompt's emotion vector with an `emo_vector` mix laid over it; emo_mix = (emovec_mat [1,d], weight_vector): infer_v2.py:756-757."""
         emovec_mat, weight_vector = emo_mix
