@@ -235,8 +235,8 @@ int idxtts_linear_create(const float* weight, const float* bias, int N, int K, i
   std::vector<float> hw, hb;
   if (fetch(weight, (size_t)N * K, &hw)) return 1;
   if (bias && fetch(bias, N, &hb)) return 1;
-  // always with the split-bf16 pack: idxtts_linear_fwd(bf16x3 = 1) takes any shape and any M
-  if (make_linear(l->arena, hw.data(), bias ? hb.data() : nullptr, N, K, {WP16_ALWAYS_MF16, weight_is_kn ? W_KN : W_NK}, &l->w)) return 1;
+  // idxtts_linear_fwd(bf16x3 = 1) takes any shape and any M: the tile pack always, the planes where the LDS-DMA kernel takes the shape
+  if (make_linear(l->arena, hw.data(), bias ? hb.data() : nullptr, N, K, {WP16_ALWAYS_MF16, weight_is_kn ? W_KN : W_NK, 0, true}, &l->w)) return 1;
   *out = l.release();
   return 0;
   API_END

@@ -78,7 +78,7 @@ __device__ __forceinline__ float load_w(const unsigned short* p) { return bf16_w
 __host__ __device__ static inline size_t plane_index(int row, int k, int rows) { return ((size_t)(k >> 4) * rows + row) * 16 + (k & 15); }
 __host__ __device__ static inline size_t plane_elems(int rows, int K) { return (size_t)((K + 15) / 16) * rows * 16; }    // per plane; lo plane follows hi
 static inline size_t frag_image_floats(int rows, int K) { return (size_t)((rows + 15) / 16) * ((K + 15) / 16) * 256; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+__host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace idxtts

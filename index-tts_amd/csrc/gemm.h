@@ -11,7 +11,9 @@ struct LinearWeights {      // device-resident, packed for the MFMA B operand
   const float* wp = nullptr;   // [ceil(N/32)][ceil(K/16)][g2][h2][j32][4]
   const float* bias = nullptr; // [N] (for SWIGLU: [N] in packed row order) or null
   int N = 0, K = 0;
-  const void* wp16 = nullptr;  // optional split-bf16 pack [N/128][K/32][hl][128][40] bf16 (gemm_bf16x3.hip)
+  // optional split-bf16 packs (hi = bf16(w), lo = bf16(w - hi)), each present only where a kernel reads it (model_util.h: make_linear)
+  const void* tiles16 = nullptr;   // [N/128][K/32][hl][128][40] bf16: LDS images of the register-staged tile kernel (gemm_bf16x3.hip)
+  const void* planes16 = nullptr;  // [hl][K/16][Npad][16] bf16: the LDS-DMA kernel (gemm_bf16x3_v2.hip)
   bool mf16 = false;           // the LDS-DMA kernel multiplies on v_mfma_f32_16x16x32_bf16 (model_util.h: WP16_ALWAYS_MF16)
 };
 
@@ -50,11 +52,17 @@ struct GemmArgs {
 
 int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream);      // exact fp32 MFMA
 int gemm_bf16x3_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream);  // split-bf16 (3 bf16 MFMAs / product)
-size_t linear_bf16x3_packed_bytes(int N, int K);
-void pack_linear_bf16x3(void* dst, const float* w, int N, int K);
+// The split-bf16 kernel a weight shape runs on from 256 rows up: the LDS-DMA kernel reads planes16, every other shape (and every
+// launch below 256 rows) runs on the tile kernel and reads tiles16.
+static inline bool linear_takes_planes(int N, int K) { return N >= 96 && K % 16 == 0; }
+// w: [N][K] fp32 -> one of the two packs
+size_t linear_tiles_bytes(int N, int K);
+void pack_linear_tiles(void* dst, const float* w, int N, int K);
+size_t linear_planes_bytes(int N, int K);
+void pack_linear_planes(void* dst, const float* w, int N, int K);
 
 // Arithmetic of the GEMM-shaped (compute-bound) passes: GEMM_F32 = exact fp32 MFMA everywhere; GEMM_BF16X3 = split-bf16
-// for launches with M >= 256 whose weights carry a bf16 pack (s2mel, GPT latent pass).  Decode GEMVs are always fp32.
+// for launches with M >= 256 whose weights carry the pack their shape runs on (s2mel, GPT latent pass).  Decode GEMVs are always fp32.
 enum GemmMode { GEMM_F32 = 0, GEMM_BF16X3 = 1 };
 void set_gemm_mode(int mode);
 int get_gemm_mode();

@@ -14,7 +14,7 @@
 // ds_read_b128 of 64 x 16 contiguous bytes (conflict-free).  The activation tile gets there through a
 // transposing register->LDS write; its 512-byte sub-blocks are padded to 528 B so the 8 lanes that hold
 // one 128-byte row segment hit 8 different bank groups.  W is packed once at context creation.
-// XCD-aware tile map: XCD x owns the m-tiles == x (mod 8) and walks them n-block-major, so the 32 CUs of
+// XCD-aware tile map (gemm_common.h: gemm_tile_walk): XCD x owns the m-tiles == x (mod 8), so the 32 CUs of
 // an XCD share one weight slice in their L2 while streaming different activation rows.
 #include <algorithm>
 #include <cmath>
@@ -87,53 +87,24 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
   float (*Xs)[4 * 2 * 4 * XBLK] = reinterpret_cast<float (*)[4 * 2 * 4 * XBLK]>(smem);
   float (*Ws)[4 * 2 * 512] = reinterpret_cast<float (*)[4 * 2 * 512]>(smem + 2 * 4 * 2 * 4 * XBLK);
 
-  // XCD x owns the m-tiles == x (mod 8).  Walk order inside an XCD:
-  //   n_fast = 1 (weights fit the 4 MiB L2): all n-blocks of one m-tile back to back -> the activation tile is fetched
-  //              from HBM once and W stays L2-resident (DiT / WaveNet shapes: W <= 6 MB, X = 100+ MB)
-  //   n_fast = 0 (big W, few rows: GPT prefill): all m-tiles of one n-block back to back -> W streams once per XCD
-  const int L = blockIdx.x, xcd = L & 7, q = L >> 3;
   int bn, bm;
-  if (p.direct_map) { bn = L / p.mtiles; bm = L - bn * p.mtiles; }      // few tiles: one per workgroup id, spread over all XCDs
-  else if (p.n_fast) { const int bml = q / p.nblocks; bn = q - bml * p.nblocks; bm = bml * 8 + xcd; }
-  else { bn = q / p.mt8; bm = (q - bn * p.mt8) * 8 + xcd; }
-  if (bm >= p.mtiles) return;
+  if (!gemm_tile_walk(p, blockIdx.x, bm, bn)) return;
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int h = lane >> 5, j = lane & 31;
   const int wm = wave >> 1, wn = wave & 1;
 
   f32x4 xr[4], wr[4];
-  // conv mode: (sequence base row, position in sequence) of the 4 activation rows this thread stages
-  int seq_base[4], seq_t[4], seq_n[4];     // seq_n: true length of that sequence (reflect pad bounces at ITS end)
-  if (p.taps > 1) {
+  ConvRow xrow[4];      // conv form: the 4 activation rows this thread stages
 #pragma unroll
-    for (int l = 0; l < 4; ++l) {
-      const int m = bm * 128 + ((tid + 256 * l) >> 3);
-      const int sb = m / p.seq_len;
-      seq_base[l] = sb * p.seq_len;
-      seq_t[l] = m - sb * p.seq_len;
-      seq_n[l] = (p.row_len && m < p.M) ? min(p.row_len[sb], p.seq_len) : p.seq_len;
-    }
-  }
+  for (int l = 0; l < 4; ++l) xrow[l] = conv_row(p, bm * 128 + ((tid + 256 * l) >> 3));
   auto load_tiles = [&](int kstep) {
-    int tap = 0, kk0 = kstep * 32;
-    if (p.taps > 1) { tap = kk0 / p.kc; kk0 -= tap * p.kc; }
+    const KStep ks = gemm_kstep(p, kstep);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const int idx = tid + 256 * l;
       // activations: 8 lanes per 128-byte row segment
-      const int row = idx >> 3, q8 = idx & 7;
-      const int m = bm * 128 + row, k = kstep * 32 + q8 * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (p.taps > 1) {
-        int t = seq_t[l] + tap * p.dil - p.pad_left;
-        if (p.pad_mode == 1) { t = t < 0 ? -t : t; t = t >= seq_n[l] ? 2 * (seq_n[l] - 1) - t : t; }
-        if (m < p.M && k < p.K && t >= 0 && t < seq_n[l])
-          v = *reinterpret_cast<const f32x4*>(p.x + (size_t)(seq_base[l] + t) * p.ldx + kk0 + q8 * 4);
-      } else if (m < p.M && k < p.K) {
-        v = *reinterpret_cast<const f32x4*>(p.x + (size_t)m * p.ldx + k);
-      }
-      xr[l] = v;
+      xr[l] = gemm_load_x(p, xrow[l], bm * 128 + (idx >> 3), ks, idx & 7);
       // weights: 4 KiB contiguous per 32-column tile (two 16-wide chunks)
       const int nt = idx >> 8, off = idx & 255;
       const int ntg = bn * 4 + nt, c16 = kstep * 2 + (off >> 7);
@@ -206,6 +177,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
     __syncthreads();
   }
 
+  const int row0 = bm * 128 + wm * 64, col0 = bn * 128 + wn * 64;      // the wave's 64 x 64 tile
   if (p.sk_cnt) {
     // one K group per workgroup: the partial tile goes to the slab in register order (write-through 16-byte stores: [group][tile][16][256
     // threads]), the last workgroup of the tile to arrive adds the groups in order
@@ -240,17 +212,17 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
         for (int e = 0; e < 4; ++e) tot[u >> 3][(u >> 2) & 1][4 * (u & 3) + e] += v[e];
       }
     }
-    gemm_epilogue(p, tot, bm, bn, wm, wn, h, j);
+    gemm_epilogue_t<2, 2>(p, tot, row0, col0, h, j);
     return;
   }
   if (p.ksplit > 1) {      // raw partial slab of this K range
     GemmKP q = p;
     q.y = p.y + (size_t)blockIdx.y * p.M * p.ldy;
     q.bias = nullptr; q.res = nullptr; q.row_len = nullptr; q.act = ACT_NONE; q.out_scale = 1.0f;
-    gemm_epilogue(q, tot, bm, bn, wm, wn, h, j);
+    gemm_epilogue_t<2, 2>(q, tot, row0, col0, h, j);
     return;
   }
-  gemm_epilogue(p, tot, bm, bn, wm, wn, h, j);
+  gemm_epilogue_t<2, 2>(p, tot, row0, col0, h, j);
 }
 
 int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* out, double* flops, double* bytes) {
@@ -332,12 +304,12 @@ static int g_gemm_mode = GEMM_BF16X3;
 void set_gemm_mode(int mode) { g_gemm_mode = mode == GEMM_F32 ? GEMM_F32 : GEMM_BF16X3; }
 int get_gemm_mode() { return g_gemm_mode; }
 
-bool gemm_bf16x3_uses_v2(const LinearWeights& w, const GemmArgs& a);
 bool gemm_uses_planes(const LinearWeights& w, const GemmArgs& a) {
-  return g_gemm_mode == GEMM_BF16X3 && w.wp16 && a.M >= 256 && gemm_bf16x3_uses_v2(w, a);
+  return g_gemm_mode == GEMM_BF16X3 && w.planes16 && gemm_bf16x3_uses_v2(w, a);
 }
 int gemm_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream) {
-  if (g_gemm_mode == GEMM_BF16X3 && w.wp16 && a.M >= 256) return gemm_bf16x3_forward(w, a, stream);
+  // split-bf16 from 256 rows up, where the weights carry the pack of the kernel their shape runs on
+  if (g_gemm_mode == GEMM_BF16X3 && a.M >= 256 && (linear_takes_planes(w.N, w.K) ? w.planes16 : w.tiles16)) return gemm_bf16x3_forward(w, a, stream);
   return gemm_tn_forward(w, a, stream);
 }
 

@@ -137,20 +137,12 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(q.b_hi), 0, q.b_bytes, 0x00020000);
   const int voffB = (bn * BN + 32 * wave + lrow) * 32 + dunit * 16;
   int voffA = min(a_m, q.a_rows - 1) * 32 + dunit * 16;
-  int seq_base = 0, seq_t = 0, seq_n = 0;
-  if (TAPS) {
-    const int sb = a_m / p.seq_len;
-    seq_base = sb * p.seq_len;
-    seq_t = a_m - seq_base;
-    seq_n = (p.row_len && a_m < p.M) ? min(p.row_len[sb], p.seq_len) : p.seq_len;
-  }
-  // the lane's A offset for tap `tap` (convolution form): row t = seq_t + tap * dil - pad_left of its own sequence, reflected
-  // or zero outside [0, seq_n)
+  const ConvRow arow = conv_row(p, a_m);
+  // the lane's A offset for tap `tap` (convolution form): row t = arow.t + tap * dil - pad_left of its own sequence, reflected
+  // or zero outside [0, arow.n)
   auto tap_voff = [&](int tap) -> int {
-    int t = seq_t + tap * p.dil - p.pad_left;
-    if (p.pad_mode == 1) { t = t < 0 ? -t : t; t = t >= seq_n ? 2 * (seq_n - 1) - t : t; }
-    const bool ok = a_m < p.M && t >= 0 && t < seq_n;
-    return ok ? (seq_base + t) * 32 + dunit * 16 : (int)0x80000000;
+    const int t = conv_src_row(arow.t + tap * p.dil - p.pad_left, arow.n, p.pad_mode);
+    return a_m < p.M && t >= 0 ? (arow.base + t) * 32 + dunit * 16 : (int)0x80000000;
   };
   V2_STAMP(0); V2_RSTAMP(4);
   const int ns = q.nstages;
@@ -425,32 +417,18 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
   V2_STAMP(3); V2_RSTAMP(5);
 }
 
-// one output tile per workgroup; XCD x owns the row tiles == x (mod 8) (gemm.hip explains the two walk orders)
+// one output tile per workgroup, walked in column groups (gemm_common.h: gemm_tile_walk)
 template <bool TAPS, int EPI, int MF>
 __global__ __launch_bounds__(256, 3) void gemm_bf16x3_v2_kernel(const GemmV2P q) {
-  const GemmKP& p = q.g;
-  const int L = blockIdx.x, xcd = L & 7, qq = L >> 3;
   int bn, bm;
-  if (p.n_fast) {
-    // XCD x = (row class x / cs, column group x % cs): it owns the row tiles == its class (mod 8 / cs) and a contiguous 1 / cs of the
-    // column blocks, and walks its columns fastest.  cs = 1: every XCD sweeps all columns of its rows (A read once, the whole B through
-    // its L2); cs > 1 where B would not stay in a 4 MiB L2 next to the streaming A: the XCD's B slice stays resident, A is read cs times.
-    const int cs = q.cs, cg = xcd % cs, rc = xcd / cs;
-    const int bml = qq / q.nbg, bnl = qq - bml * q.nbg;
-    bm = bml * (8 / cs) + rc;
-    bn = cg * q.nbg + bnl;
-    if (bn >= p.nblocks) return;
-  } else { bn = qq / p.mt8; bm = (qq - bn * p.mt8) * 8 + xcd; }
-  if (bm >= p.mtiles) return;
+  if (!gemm_tile_walk(q.g, blockIdx.x, bm, bn, q.cs, q.nbg)) return;
   gemm_v2_tile<TAPS, EPI, MF>(q, bm, bn, threadIdx.x);
 }
 
 // per-stream scratch for the activation planes: room for a quarter more rows than the launch that grows it
 StreamScratch g_plane_scratch(8);
 
-// p: fully prepared by gemm_bf16x3_forward (shapes, epilogue, conv parameters); planes: w.wp16 + offset
-int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w, const GemmArgs& a, hipStream_t stream, double flops,
-                           double bytes) {
+int gemm_bf16x3_v2_forward(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipStream_t stream, double flops, double bytes) {
   IDX_CHECK(w.K % 16 == 0 && (a.taps <= 1 || (w.K / a.taps) % 16 == 0), "v2 needs K % 16 == 0");
   const int xk = a.taps > 1 ? w.K / a.taps : w.K;       // channels of the activation rows
   const size_t plane = (size_t)(xk / 16) * a.M * 16 * sizeof(__bf16);
@@ -487,7 +465,7 @@ int gemm_bf16x3_v2_forward(GemmKP p, const void* wplanes, const LinearWeights& w
   q.g.nblocks = cdiv(w.N, BNh);
   q.a_hi = hi; q.a_lo = lo; q.a_rows = a.M;
   q.npad = cdiv(w.N, 256) * 256;
-  q.b_hi = static_cast<const __bf16*>(wplanes);
+  q.b_hi = static_cast<const __bf16*>(w.planes16);
   q.b_lo = q.b_hi + (size_t)(w.K / 16) * q.npad * 16;
   q.nstages = w.K / 16;
 #ifdef V2_TIMING

@@ -1,6 +1,6 @@
-// Shared by the fp32 and the split-bf16 GEMM kernels: kernel parameter block, activation functions and the
-// accumulator epilogue (bias, activation / paired gate, residual, row mask, store) for a 2x2-wave, 2x2-tile
-// 128x128 workgroup tile in the 32x32 MFMA C/D layout.  And by their host code: the launch set-up (gemm_prepare), host bf16
+// Shared by the fp32 and the split-bf16 GEMM kernels: kernel parameter block, the workgroup-id -> tile walk, the activation-row
+// loader (plain and convolution form), activation functions and the accumulator epilogue (bias, activation / paired gate, residual,
+// row mask, store) of a wave tile in the 32x32 MFMA C/D layout.  And by their host code: the launch set-up (gemm_prepare), host bf16
 // rounding for the weight packs, the per-stream scratch.
 #pragma once
 #include <cstring>
@@ -48,7 +48,7 @@ struct GemmKP {
   const float* x; const float* wp; const float* bias; const float* res; float* y;
   int M, N, K, ldx, ldy, ldr;
   int kc16;        // 16-wide K chunks in the packed weights
-  int mtiles, mt8; // 128-row tiles, ceil(mtiles/8)
+  int mtiles, mt8; // row tiles, ceil(mtiles/8)
   int nblocks, n_fast;
   int act;
   float out_scale;
@@ -71,6 +71,63 @@ struct GemmKP {
 // What every GEMM launch shares: the argument checks, the parameter block (fp32 weights, 128 x 128 tiles, XCD walk, no K split) and
 // the algorithmic flops / bytes of the launch.  gemm_tn_forward and gemm_bf16x3_forward add what is their own.
 int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* p, double* flops, double* bytes);
+// gemm_bf16x3_forward's two kernel families: from 256 rows up a shape with weight planes runs on the LDS-DMA kernel
+// (gemm_bf16x3_v2.hip; p: fully prepared -- shapes, epilogue, conv parameters), everything else on the register-staged tile kernel
+inline bool gemm_bf16x3_uses_v2(const LinearWeights& w, const GemmArgs& a) { return a.M >= 256 && linear_takes_planes(w.N, w.K); }
+int gemm_bf16x3_v2_forward(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipStream_t stream, double flops, double bytes);
+
+// Which output tile workgroup L computes (false: none).  XCD x = L % 8 owns the m-tiles == x (mod 8).  Walk order inside an XCD:
+//   n_fast = 1 (weights fit the 4 MiB L2): all n-blocks of one m-tile back to back -> the activation tile is fetched
+//              from HBM once and W stays L2-resident (DiT / WaveNet shapes: W <= 6 MB, X = 100+ MB)
+//   n_fast = 0 (big W, few rows: GPT prefill): all m-tiles of one n-block back to back -> W streams once per XCD
+// cs > 1 (n_fast only; the LDS-DMA kernel, where B would not stay in an L2 next to the streaming A): XCD x = (row class x / cs, column
+// group x % cs) owns the m-tiles == its class (mod 8 / cs) and `nbg` contiguous n-blocks: its B slice stays resident, A is read cs times.
+// direct_map (the exact kernel's few-tile launches): one tile per workgroup id, spread over all XCDs.
+__device__ __forceinline__ bool gemm_tile_walk(const GemmKP& p, int L, int& bm, int& bn, int cs = 1, int nbg = 0) {
+  const int xcd = L & 7, q = L >> 3;
+  if (p.direct_map) { bn = L / p.mtiles; bm = L - bn * p.mtiles; }
+  else if (p.n_fast) {
+    if (cs == 1) nbg = p.nblocks;
+    const int bml = q / nbg;
+    bn = (xcd % cs) * nbg + q - bml * nbg;
+    bm = bml * (8 / cs) + xcd / cs;
+  } else { bn = q / p.mt8; bm = (q - bn * p.mt8) * 8 + xcd; }
+  return bm < p.mtiles && bn < p.nblocks;
+}
+
+// Convolution form (taps > 1): conv_src_row is the position of its sequence (true length n: a reflect pad bounces at ITS end) that
+// tap offset t reads -- reflected for pad_mode 1 -- or -1 where the tap reads zero.
+__device__ __forceinline__ int conv_src_row(int t, int n, int pad_mode) {
+  if (pad_mode == 1) { t = t < 0 ? -t : t; t = t >= n ? 2 * (n - 1) - t : t; }
+  return t >= 0 && t < n ? t : -1;
+}
+// A staged activation row m as position t of the sequence that starts at row `base` and has the true length n (conv form only)
+struct ConvRow { int base, t, n; };
+__device__ __forceinline__ ConvRow conv_row(const GemmKP& p, int m) {
+  if (p.taps <= 1) return {0, 0, 0};
+  const int sb = m / p.seq_len;
+  return {sb * p.seq_len, m - sb * p.seq_len, (p.row_len && m < p.M) ? min(p.row_len[sb], p.seq_len) : p.seq_len};
+}
+
+// A 32-k step: its first k; conv form: its tap and its first channel inside the tap (a step never straddles taps: K / taps % 32 == 0)
+struct KStep { int k0, tap, c0; };
+__device__ __forceinline__ KStep gemm_kstep(const GemmKP& p, int kstep) {
+  KStep s = {kstep * 32, 0, kstep * 32};
+  if (p.taps > 1) { s.tap = s.k0 / p.kc; s.c0 -= s.tap * p.kc; }
+  return s;
+}
+// Activation row m (r = conv_row(p, m)), columns 4 q8 .. 4 q8 + 3 of k-step s: zero outside M, outside K and outside the sequence
+__device__ __forceinline__ f32x4 gemm_load_x(const GemmKP& p, const ConvRow& r, int m, const KStep& s, int q8) {
+  const int k = s.k0 + q8 * 4;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (p.taps > 1) {
+    const int t = conv_src_row(r.t + s.tap * p.dil - p.pad_left, r.n, p.pad_mode);
+    if (m < p.M && k < p.K && t >= 0) v = *reinterpret_cast<const f32x4*>(p.x + (size_t)(r.base + t) * p.ldx + s.c0 + q8 * 4);
+  } else if (m < p.M && k < p.K) {
+    v = *reinterpret_cast<const f32x4*>(p.x + (size_t)m * p.ldx + k);
+  }
+  return v;
+}
 
 // Hardware-rate forms for the split-bf16 GEMM's fused gates (v_exp_f32 + v_rcp_f32, ~1 ulp each: absolute error < 2e-7, far below
 // the 2^-16 of the products they follow).  The exact-fp32 kernels keep libm (gemm_epilogue_t, act_apply).
@@ -319,11 +376,6 @@ __device__ __forceinline__ void gemm_epilogue_wave(const GemmKP& p, WritePass&& 
     }
     if (PREF && ps + PF < 4) prefetch(ps + PF);
   }
-}
-
-// 128x128 workgroup tile, 2x2 waves of 64x64
-__device__ __forceinline__ void gemm_epilogue(const GemmKP& p, f32x16 (&acc)[2][2], int bm, int bn, int wm, int wn, int h, int j) {
-  gemm_epilogue_t<2, 2>(p, acc, bm * 128 + wm * 64, bn * 128 + wn * 64, h, j);
 }
 
 }  // namespace idxtts

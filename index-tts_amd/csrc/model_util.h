@@ -1,4 +1,4 @@
-// Shared by every model's finalize(): staged host tensors -> device weights (the exact-fp32 MFMA GEMM pack, the split-bf16 pack),
+// Shared by every model's finalize(): staged host tensors -> device weights (the exact-fp32 MFMA GEMM pack, the split-bf16 packs),
 // workspace carving, and the two launches every layer of the small once-per-prompt models repeats.  Definitions: model_util.hip.
 #pragma once
 #include <map>
@@ -18,10 +18,11 @@ int tensor_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const 
 int vec_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& key, int n, const float** out);
 int ln_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int n, const float** g, const float** b);
 
-// Which linears get a split-bf16 pack (LinearWeights::wp16) beside the fp32 one.  gemm_forward runs a launch of >= 256 rows on the
-// split-bf16 kernels when the weights carry the pack, and on the exact fp32 kernel when they do not.
+// Which linears get a split-bf16 pack beside the fp32 one.  gemm_forward runs a launch of >= 256 rows on the split-bf16 kernel of its
+// shape (linear_takes_planes, gemm.h) when the weights carry that kernel's pack, and on the exact fp32 kernel when they do not.  A
+// pack is made only where that dispatch can read it: planes for the shapes the LDS-DMA kernel takes, tiles for the others.
 enum Wp16Policy {
-  WP16_ALWAYS,      // every shape: the GPT projections (N < 96 or K % 16 != 0 run on the tile kernels)
+  WP16_ALWAYS,      // every shape: the GPT projections (N < 96 or K % 16 != 0 get tiles and run on the tile kernel)
   WP16_DMA_SHAPES,  // only shapes the LDS-DMA kernel takes (N >= 96, K % 16 == 0), the rest stays exact fp32: the small models
   // every shape, and the LDS-DMA kernel's v_mfma_f32_16x16x32_bf16 loop (LinearWeights::mf16): s2mel and idxtts_linear_create.  That
   // loop adds a row's k in another order than the 32x32x16 loop, so results move in the last bits.  Where they only become a waveform
@@ -35,8 +36,10 @@ struct LinearOpts {
   Wp16Policy wp16;
   WeightLayout layout = W_NK;
   int Kpad = 0;      // K of the packed weights, >= K: zero columns are added (0: K as it is)
+  // launches below 256 rows also run split-bf16 (idxtts_linear_fwd calls gemm_bf16x3_forward at any M): tiles for every shape
+  bool split_bf16_below_256_rows = false;
 };
-// host weights (+ bias [N] or null) -> both packs on the device
+// host weights (+ bias [N] or null) -> the fp32 pack and the split-bf16 packs of the policy, on the device
 int make_linear(DeviceArena& arena, const float* w, const float* bias, int N, int K, const LinearOpts& o, LinearWeights* out);
 // the nn.Linear `prefix`.weight [N][K] (or `wshape`, a 1-tap Conv1d's [N][K][1]) + `prefix`.bias; K is padded to a multiple of 4
 int linear_from(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int N, int K, bool bias, Wp16Policy wp16,

@@ -57,13 +57,18 @@ int make_linear(DeviceArena& arena, const float* w, const float* bias, int N, in
   if (up(arena, packed, &out->wp)) return 1;
   out->N = N; out->K = Kpad;
   out->mf16 = o.wp16 == WP16_ALWAYS_MF16;
-  if (o.wp16 != WP16_NONE && (o.wp16 != WP16_DMA_SHAPES || (N >= 96 && Kpad % 16 == 0))) {
-    std::vector<float> p16((linear_bf16x3_packed_bytes(N, Kpad) + 3) / 4);
-    pack_linear_bf16x3(p16.data(), w, N, Kpad);
+  auto pack16 = [&](size_t bytes, void (*pack)(void*, const float*, int, int), const void** dst) {
+    std::vector<float> p16((bytes + 3) / 4);
+    pack(p16.data(), w, N, Kpad);
     const float* d16 = nullptr;
     if (up(arena, p16, &d16)) return 1;
-    out->wp16 = d16;
-  }
+    *dst = d16;
+    return 0;
+  };
+  const bool planes = o.wp16 != WP16_NONE && linear_takes_planes(N, Kpad);
+  const bool tiles = o.wp16 != WP16_NONE && (o.split_bf16_below_256_rows || (o.wp16 != WP16_DMA_SHAPES && !planes));
+  if (planes && pack16(linear_planes_bytes(N, Kpad), pack_linear_planes, &out->planes16)) return 1;
+  if (tiles && pack16(linear_tiles_bytes(N, Kpad), pack_linear_tiles, &out->tiles16)) return 1;
   if (bias && up(arena, std::vector<float>(bias, bias + N), &out->bias)) return 1;
   return 0;
 }
