@@ -536,6 +536,20 @@ int idxtts_s2mel_cfm_rows(idxtts_ctx* ctx, const float* gen_cond, const int* tar
                           const float* dt, int n_steps, float cfg_rate, float* out, int B, int T, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* The noise `z` of either solve from a counter-based generator, one seed per utterance: row b's element (c, t) is a pure function of
+ * (seeds[b], c, t) -- t counted from the row's column 0, prompt frames included -- whatever batch, padding, row position or stream it is
+ * produced in, so a request's audio is reproducible alone and merged.  With idx = (c << 32) | t, in arithmetic mod 2^64:
+ *   z = (seed ^ 0xD1B54A32D192ED03) + 0x9E3779B97F4A7C15 * (idx + 1);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;
+ *   u1 = ((z >> 41) + 0.5) * 2^-23;  u2 = (((z >> 18) & 0x7FFFFF) + 0.5) * 2^-23;  n = sqrt(-2 ln u1) * cos(2 pi u2)
+ * (23-bit uniforms: exact in fp32, never 0 or 1; the tail is cut at 5.77 sigma = 8e-9 of the mass per draw; the xor constant keeps
+ * the stream apart from a sampler given the same seed).
+ * z[b][c][t] = that draw for t < x_lens[b], 0.0f for x_lens[b] <= t < T.  seeds, x_lens: HOST [B].
+ * z: device [B][C][T] fp32, any T >= max x_lens (rows need not be 16-byte aligned).  No workspace, no allocation,
+ * no host-device copy, no synchronisation; seeds / x_lens may be reused as soon as the call returns.
+ * Errors: a null pointer, B < 1, C < 1, T < 1 (or C * T beyond an int), an x_lens[b] outside 0..T. */
+int idxtts_cfm_noise(const unsigned long long* seeds, const int* x_lens, int B, int C, int T, float* z, void* stream);
+
 /* One evaluation of the CFM estimator = DiT.forward(x, prompt_x, x_lens, t, style, cond) (diffusion_transformer.py:186-257),
  * the function `cfm.inference` calls once per Euler step on the [cond | null] stack (flow_matching.py:96).  x [B][in_channels][T];
  * prompt [B][in_channels][Tp_max] with prompt_lens HOST [B] (prompt_x is zero beyond them); x_lens HOST [B]; t_emb device

@@ -269,7 +269,8 @@ class IndexTTS2:
     # ------------------------------------------------------------------------------------------
     def synthesize_batch(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
                          repetition_penalty: float = 10.0, noise: Optional[torch.Tensor] = None, sync_timers: bool = False,
-                         return_intermediates: bool = False, sampling: Optional[dict] = None, per_row_noise: bool = False):
+                         return_intermediates: bool = False, sampling: Optional[dict] = None, per_row_noise: bool = False,
+                         noise_seeds=None):
         """One batch of single-segment utterances: the body of the reference's segment loop (infer_v2.py:732-881) for B rows at once.
         text_tokens [B, L] (right-padded with stop_text_token).  cond: one PromptConditioning shared by every row, or a list of B
         of them, one per row (several speakers in one batch; see rows_conditioning).
@@ -278,12 +279,13 @@ class IndexTTS2:
         (do_sample, temperature, top_k, top_p, sampler, exp_noise / generator).
         per_row_noise: draw the CFM noise row by row, `randn([1, 80, Tp + Tg_b])` in row order -- the draws the reference's
         sequential segment loop makes (flow_matching.py:62 once per segment) -- instead of one [B, 80, T] draw.
+        noise_seeds: one int per row instead of `noise` (see acoustic_stage).
         = acoustic_stage(gpt_stage(...)): the two halves are separate entry points so that a serving loop can overlap the
         (latency-bound) decode of one batch with the (MFMA-bound) s2mel + vocoder of the previous one on another stream."""
         st = self.gpt_stage(text_tokens, cond, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
                             sampling=sampling, sync_timers=sync_timers)
         return self.acoustic_stage(st, noise=noise, per_row_noise=per_row_noise, sync_timers=sync_timers,
-                                   return_intermediates=return_intermediates)
+                                   return_intermediates=return_intermediates, noise_seeds=noise_seeds)
 
     def _tick(self, sync: bool) -> float:
         if sync:
@@ -338,10 +340,21 @@ class IndexTTS2:
         return {"cond": c, "B": B, "codes": codes, "code_lens": code_lens, "code_lens_t": code_lens_t, "latent": latent, "times": times}
 
     def acoustic_stage(self, st: dict, noise: Optional[torch.Tensor] = None, per_row_noise: bool = False, sync_timers: bool = False,
-                       return_intermediates: bool = False):
+                       return_intermediates: bool = False, noise_seeds=None):
         """s2mel (length regulator + CFM) and the vocoder (infer_v2.py:835-866) on the current stream.  st["cond"]: one
         PromptConditioning, or a list of one per row (rows_conditioning): then the CFM runs as ONE mixed-prompt batch
-        (S2Mel.cfm_rows) and row b's noise -- given, or drawn -- covers its own Tp_b + Tg_b frames from column 0."""
+        (S2Mel.cfm_rows) and row b's noise -- given, or drawn -- covers its own Tp_b + Tg_b frames from column 0.
+        noise_seeds: one int per row instead of `noise` (both: ValueError).  Row b's noise is then S2Mel.noise's function of
+        (noise_seeds[b], channel, frame) alone -- the same in any batch, on any stream -- and torch's generators are not touched;
+        per_row_noise is ignored."""
+        if noise is not None and noise_seeds is not None:
+            raise ValueError("pass `noise` or `noise_seeds`, not both")
+        if noise_seeds is not None:
+            noise_seeds = [int(s) for s in noise_seeds]
+            if len(noise_seeds) != st["B"]:
+                raise ValueError(f"{len(noise_seeds)} noise seeds for {st['B']} rows")
+            per_row_noise = False
+        seeded = noise_seeds is not None
         dev = self.device
         c, B, codes, code_lens, code_lens_t, latent, times = (st["cond"], st["B"], st["codes"], st["code_lens"], st["code_lens_t"],
                                                               st["latent"], dict(st["times"]))
@@ -356,11 +369,11 @@ class IndexTTS2:
                 noise = torch.zeros([B, C, T], device=dev)
                 for b in range(B):
                     noise[b, :, :x_lens[b]] = torch.randn([1, C, x_lens[b]], device=dev)[0]
-            elif noise is None:
+            elif noise is None and not seeded:
                 noise = torch.randn([B, C, T], device=dev)
             vc_target = self.s2mel.cfm_rows(condv, target_lens, [x.prompt_condition for x in c], [x.ref_mel for x in c],
                                             torch.cat([x.style for x in c]), self._diffusion_steps, inference_cfg_rate=self._cfg_rate,
-                                            z=noise)                                        # infer_v2.py:850-856, row by row
+                                            z=noise, noise_seeds=noise_seeds)              # infer_v2.py:850-856, row by row
         else:
             Tp = c.prompt_condition.shape[1]
             cat_condition = torch.cat([c.prompt_condition.expand(B, -1, -1), condv], dim=1)     # infer_v2.py:850
@@ -370,10 +383,10 @@ class IndexTTS2:
                 for b in range(B):
                     nb = int(x_lens[b])
                     noise[b, :, :nb] = torch.randn([1, C, nb], device=dev)[0]
-            elif noise is None:
+            elif noise is None and not seeded:
                 noise = torch.randn([B, C, Tp + Tg], device=dev)
             mel = self.s2mel.cfm_inference(cat_condition, x_lens, c.ref_mel.expand(B, -1, -1), c.style.expand(B, -1), None,
-                                           self._diffusion_steps, inference_cfg_rate=self._cfg_rate, z=noise)
+                                           self._diffusion_steps, inference_cfg_rate=self._cfg_rate, z=noise, noise_seeds=noise_seeds)
             vc_target = mel[:, :, Tp:]                                                      # infer_v2.py:856
         t3 = self._tick(sync_timers)
         times["s2mel_time"] = t3 - t2
@@ -569,6 +582,10 @@ class IndexTTS2:
         num_beams = generation_kwargs.pop("num_beams", 3)
         repetition_penalty = generation_kwargs.pop("repetition_penalty", 10.0)
         max_mel_tokens = generation_kwargs.pop("max_mel_tokens", 1500)
+        # noise_seed: the CFM noise of segment i comes from seed i of utterance_noise_seeds(noise_seed, n_segments) instead of
+        # torch's generator -- the same audio streaming or not, at any segment_batch, whatever else draws from torch
+        from .serving import utterance_noise_seeds
+        nseeds = utterance_noise_seeds(generation_kwargs.pop("noise_seed", None), len(segs))
         sampling = {"do_sample": bool(do_sample), "num_beams": int(num_beams), "generator": generation_kwargs.pop("generator", None)}
         if do_sample:
             sampling.update(top_p=top_p, top_k=top_k, temperature=temperature)
@@ -582,9 +599,9 @@ class IndexTTS2:
         wavs = []
         sil = self.interval_silence(interval_silence=interval_silence)
         if stream_return:
-            for s in segs:                                                                           # segment loop, infer_v2.py:732
+            for i, s in enumerate(segs):                                                             # segment loop, infer_v2.py:732
                 w = self.synthesize_batch(s, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
-                                          sampling=sampling)[0]
+                                          sampling=sampling, noise_seeds=None if nseeds is None else nseeds[i:i + 1])[0]
                 yield w.cpu()                                                                        # infer_v2.py:874-879
                 yield sil.cpu()
             return                                                                                   # infer_v2.py:885-886
@@ -601,7 +618,8 @@ class IndexTTS2:
             for r, s in enumerate(grp):
                 toks[r, : s.shape[1]] = s[0]
             wavs.extend(self.synthesize_batch(toks, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
-                                              sampling=sampling, per_row_noise=True))
+                                              sampling=sampling, per_row_noise=True,
+                                              noise_seeds=None if nseeds is None else nseeds[i:i + nb]))
         out = []
         for i, w in enumerate(wavs):                                                                 # insert_interval_silence 499-522
             out.append(w)

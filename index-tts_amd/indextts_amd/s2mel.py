@@ -114,23 +114,51 @@ class S2Mel:
                                              _lib.ptr(cond), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
         return cond, tl.to(self.device)
 
+    def noise(self, seeds, x_lens, T: int = None) -> torch.Tensor:
+        """The CFM noise of a batch from one seed per row (idxtts_cfm_noise), on the current stream: [B, in_channels, T], row b's
+        element (c, t) a function of (seeds[b], c, t) alone for t < x_lens[b] and 0 from there on.  seeds: B ints in 0 .. 2**64 - 1;
+        T defaults to max(x_lens).  torch's generators are not touched."""
+        sd = [int(s) for s in seeds]
+        if any(not 0 <= s < 2 ** 64 for s in sd):
+            raise ValueError("noise seeds must be in 0 <= seed < 2**64")
+        xl = np.ascontiguousarray(torch.as_tensor(x_lens).detach().cpu().reshape(-1).numpy(), dtype=np.int32)
+        if len(sd) != len(xl):
+            raise ValueError(f"{len(sd)} noise seeds for {len(xl)} rows")
+        B = len(sd)
+        T = int(xl.max()) if T is None and B else int(T or 0)
+        sa = np.array(sd, dtype=np.uint64)
+        with torch.cuda.device(self.device):
+            z = torch.empty(B, self.cfg.in_channels, max(T, 0), device=self.device, dtype=torch.float32)
+            _lib.check(_lib.load().idxtts_cfm_noise(sa.ctypes.data_as(c_void_p), xl.ctypes.data_as(c_void_p), B, self.cfg.in_channels, T,
+                                                    _lib.ptr(z), _lib.current_stream()))
+        return z
+
     def cfm_inference(self, mu: torch.Tensor, x_lens, prompt: torch.Tensor, style: torch.Tensor, f0=None, n_timesteps: int = 20,
-                      temperature: float = 1.0, inference_cfg_rate: float = 0.7, z: torch.Tensor = None, prompt_lens=None):
+                      temperature: float = 1.0, inference_cfg_rate: float = 0.7, z: torch.Tensor = None, prompt_lens=None,
+                      noise_seeds=None):
         """mu [B,T,512], x_lens [B], prompt [B,80,Tp], style [B,192] -> mel [B,80,T] (flow_matching.py:31-55).
-        `z` is the N(0,1) noise the reference draws at line 52; when omitted it is drawn here on the device."""
+        `z` is the N(0,1) noise the reference draws at line 52; when omitted it is drawn here on the device: from torch's generator,
+        or -- noise_seeds, one int per row -- as `self.noise(noise_seeds, x_lens)` (times `temperature`), which depends on nothing
+        but a row's own seed."""
         if f0 is not None:
             raise NotImplementedError("f0 conditioning is disabled in IndexTTS-2 (config.yaml:76)")
+        if z is not None and noise_seeds is not None:
+            raise ValueError("pass the noise `z` or `noise_seeds`, not both")
         lib = _lib.load()
         mu = mu.to(self.device, torch.float32).contiguous()
         B, T, _ = mu.shape
         prompt = prompt.to(self.device, torch.float32).contiguous()
         style = style.to(self.device, torch.float32).contiguous()
-        if z is None:
-            z = torch.randn([B, self.cfg.in_channels, T], device=self.device) * temperature
-        z = z.to(self.device, torch.float32).contiguous()
         xl = np.ascontiguousarray(torch.as_tensor(x_lens).detach().cpu().reshape(-1).numpy(), dtype=np.int32)
         if len(xl) == 1 and B > 1:
             xl = np.repeat(xl, B)
+        if noise_seeds is not None:
+            z = self.noise(noise_seeds, xl, T)
+            if temperature != 1.0:
+                z = z * temperature
+        elif z is None:
+            z = torch.randn([B, self.cfg.in_channels, T], device=self.device) * temperature
+        z = z.to(self.device, torch.float32).contiguous()
         Tp = prompt.shape[-1]
         pl = np.full(B, Tp, np.int32) if prompt_lens is None else np.ascontiguousarray(
             torch.as_tensor(prompt_lens).detach().cpu().reshape(-1).numpy(), dtype=np.int32)
@@ -145,13 +173,16 @@ class S2Mel:
         return out
 
     def cfm_rows(self, gen_cond: torch.Tensor, target_lens, prompt_conditions, ref_mels, style: torch.Tensor, n_timesteps: int = 20,
-                 inference_cfg_rate: float = 0.7, z: torch.Tensor = None) -> torch.Tensor:
+                 inference_cfg_rate: float = 0.7, z: torch.Tensor = None, noise_seeds=None) -> torch.Tensor:
         """The CFM solve on a batch whose rows have DIFFERENT prompts (idxtts_s2mel_cfm_rows): row b is
         `cfm_inference(cat([prompt_conditions[b], gen_cond[b, :Tg_b]], 1), Tp_b + Tg_b, ref_mels[b], style[b], z=z[b:b+1, :, :Tp_b + Tg_b])
         [:, :, Tp_b:]` (infer_v2.py:850-856).  gen_cond [B,Tg_max,512] (prepare_condition's output), target_lens [B];
         prompt_conditions / ref_mels: B entries, [1,Tp_b,512] / [1,80,Tp_b] (rows of one speaker may pass the same tensor: it is
         read in place, not copied per row); style [B,192]; z [B,80,T] with T = max_b(Tp_b + Tg_b), row b's noise from column 0.
+        noise_seeds (one int per row) instead of z: z = self.noise(noise_seeds, Tp_b + Tg_b).
         Returns vc_target [B,80,Tg_max]: row b's generated frames, zero from Tg_b on."""
+        if z is not None and noise_seeds is not None:
+            raise ValueError("pass the noise `z` or `noise_seeds`, not both")
         lib = _lib.load()
         gen = gen_cond.to(self.device, torch.float32).contiguous()
         B, Tg_max, _ = gen.shape
@@ -173,7 +204,9 @@ class S2Mel:
                 raise ValueError("prompt_condition [1,Tp,content_dim] and ref_mel [1,in_channels,Tp] of a row must agree")
         T = int((pl + tl).max())
         style = style.to(self.device, torch.float32).contiguous()
-        if z is None:
+        if noise_seeds is not None:
+            z = self.noise(noise_seeds, pl + tl, T)
+        elif z is None:
             z = torch.randn([B, self.cfg.in_channels, T], device=self.device)
         z = z.to(self.device, torch.float32)
         if z.shape[-1] < T:

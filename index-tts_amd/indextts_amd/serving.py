@@ -8,7 +8,7 @@ own host thread (the C call releases the GIL), with its own KV-cache workspace -
 `acoustic_workers` further streams.
 
 `acoustic_coalesce` > 1 lets a free acoustic worker take that many decoded requests (same prompt, or any prompts with
-`acoustic_mix_prompts=True`; explicit CFM noise) as ONE s2mel + vocoder batch; `coalesce` > 1 is dynamic batching of the decode: a
+`acoustic_mix_prompts=True`; explicit CFM noise, or a `noise_seed`) as ONE s2mel + vocoder batch; `coalesce` > 1 is dynamic batching of the decode: a
 lane that becomes free takes up to `coalesce` waiting requests of the same
 prompt and text width and decodes them as ONE batch (a decode step streams the 965 MB of GPT weights once whatever the number of rows, so two
 16-utterance requests decoded together cost little more than one), then hands every request's rows to its own acoustic job.
@@ -31,7 +31,7 @@ a CU's whole register file) -- so there is one schedule: sharing.
     _lib.set_decode_geometry(True)           # once per process, before generating: decode GEMVs as 512-thread workgroups, which find room
                                              # beside the acoustic stage's kernels (+1.5 % here, 7 % slower for a decode alone)
     pipe = BatchPipeline(tts, decode_lanes=3)
-    futs = [pipe.submit(text_k, cond, max_mel_tokens=..., noise=noise_k) for text_k in batches]
+    futs = [pipe.submit(text_k, cond, max_mel_tokens=..., noise_seed=seed_k) for text_k in batches]      # or noise=noise_k
     wavs = [f.result() for f in futs]        # lists of [1, n] waveforms, as synthesize_batch returns them
     pipe.close()
 """
@@ -40,6 +40,7 @@ from __future__ import annotations
 import collections
 import concurrent.futures
 import contextlib
+import operator
 import threading
 import time
 from typing import Optional
@@ -67,19 +68,71 @@ def merge_keeps_kernels(rows_each, prefix_len: int, split_bf16_gemm: bool, compa
     return True
 
 
+def utterance_noise_seeds(noise_seed, n: int):
+    """The per-utterance CFM noise seeds of a request of `n` utterances (IndexTTS2.acoustic_stage's `noise_seeds`).  None: None (the
+    noise is given, or drawn from torch's generator).  An int: n seeds drawn as utterance_samplers draws its seeds,
+    torch.randint(0, 2**62, (1,), generator=torch.Generator().manual_seed(noise_seed)) in utterance order.  A sequence of n ints
+    (0 <= s < 2**64): taken as given.  Raises ValueError on anything else."""
+    if noise_seed is None:
+        return None
+    if isinstance(noise_seed, int) and not isinstance(noise_seed, bool):
+        if not 0 <= noise_seed < 2 ** 64:
+            raise ValueError("noise_seed must be in 0 <= seed < 2**64")
+        g = torch.Generator().manual_seed(noise_seed)
+        return [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
+    try:
+        seeds = [operator.index(v) for v in noise_seed]
+    except TypeError:
+        raise ValueError("noise_seed must be None, an int or a sequence of one int per utterance") from None
+    if len(seeds) != n:
+        raise ValueError(f"{len(seeds)} noise seeds for {n} utterances")
+    if any(not 0 <= v < 2 ** 64 for v in seeds):
+        raise ValueError("noise seeds must be in 0 <= seed < 2**64")
+    return seeds
+
+
+def _request_noise(noise, noise_seed, n: int):
+    """(noise, per-utterance seeds) of a request as submitted: at most one of the two."""
+    if noise is not None and noise_seed is not None:
+        raise ValueError("pass `noise` or `noise_seed`, not both")
+    return noise, utterance_noise_seeds(noise_seed, n)
+
+
+def _noise_kind(r) -> int:
+    """How a request's CFM noise is fixed: 1 = explicit tensor, 2 = seeds, 0 = neither (drawn when its acoustic stage runs, so it is
+    never merged).  Only requests of one non-zero kind share an acoustic batch."""
+    return 1 if r.noise is not None else 2 if r.noise_seeds is not None else 0
+
+
+def _noise_of(r):
+    return r.noise if r.noise is not None else r.noise_seeds
+
+
+def _acoustic_call(tts, st, noise):
+    """acoustic_stage on a (merged) state with what merge_acoustic_states returned for its noise: a tensor, None or a seed list."""
+    if isinstance(noise, list):
+        return tts.acoustic_stage(st, noise_seeds=noise)
+    return tts.acoustic_stage(st, noise=noise)
+
+
 def merge_acoustic_states(items):
     """Several requests' `gpt_stage` states as ONE acoustic batch.  items: (cond, state, noise) per request, `cond` being what the
     request was submitted with (one PromptConditioning, or one per row).  Rows are independent in s2mel and the vocoder (ragged
     lengths: every row is padded at its own end), so stacking them only changes how the launches fill the chip.  Requests of ONE
     prompt keep the single-prompt path (state["cond"] = that prompt); otherwise state["cond"] is the list of every row's prompt
     (IndexTTS2.acoustic_stage then runs S2Mel.cfm_rows), rows submitted with the same object sharing one device copy.  Each request's
-    noise keeps its rows' frames from column 0 and is zero-padded on the right.  Returns (state, noise)."""
+    noise keeps its rows' frames from column 0 and is zero-padded on the right.  Returns (state, noise).  Seeded requests pass
+    their list of per-row seeds in place of the noise tensor (every item, or none): the second value is then the concatenated
+    list, in row order."""
     sts = [st for _, st, _ in items]
     n = max(st["codes"].shape[1] for st in sts)
     codes = torch.cat([torch.nn.functional.pad(st["codes"], (0, n - st["codes"].shape[1])) for st in sts])
     latent = torch.cat([torch.nn.functional.pad(st["latent"], (0, 0, 0, n - st["latent"].shape[1])) for st in sts])
-    T = max(z.shape[-1] for _, _, z in items)
-    noise = torch.cat([torch.nn.functional.pad(z, (0, T - z.shape[-1])) for _, _, z in items])
+    if all(isinstance(z, (list, tuple)) for _, _, z in items):
+        noise = [int(s) for _, _, z in items for s in z]
+    else:
+        T = max(z.shape[-1] for _, _, z in items)
+        noise = torch.cat([torch.nn.functional.pad(z, (0, T - z.shape[-1])) for _, _, z in items])
     keys, first = [], {}
     for cond, st, _ in items:
         dc = st["cond"]
@@ -95,7 +148,7 @@ def merge_acoustic_states(items):
 
 
 class _Request:
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "repetition_penalty", "sampling", "ready", "caller", "done")
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done")
 
     def compatible(self, other: "_Request") -> bool:
         # same prompt and settings, greedy (sampling draws are per call) and the SAME text width: a wider neighbour would left-pad this
@@ -144,17 +197,24 @@ class BatchPipeline:
         return s
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
-               repetition_penalty: float = 10.0, sampling: Optional[dict] = None) -> concurrent.futures.Future:
+               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None) -> concurrent.futures.Future:
         """Queue one batch; returns a Future of the list of waveforms `synthesize_batch` would return.  Inputs produced on the
         caller's current stream are safe to use (an event recorded here is waited for on the lane's stream), and the waveforms
-        are safe to read on that stream (they are tied to it with record_stream before the Future resolves)."""
+        are safe to read on that stream (they are tied to it with record_stream before the Future resolves).
+        noise_seed (instead of `noise`): an int, or one int per row (utterance_noise_seeds) -- the rows' CFM noise seeds are fixed
+        here, so the request's noise is the same whatever it is merged with.  A bad value, or both, fails this Future only."""
         r = _Request()
-        r.text, r.cond, r.max_mel_tokens, r.noise = text_tokens, cond, max_mel_tokens, noise
+        r.done = concurrent.futures.Future()
+        try:
+            r.noise, r.noise_seeds = _request_noise(noise, noise_seed, int(text_tokens.shape[0]))
+        except ValueError as e:
+            r.done.set_exception(e)
+            return r.done
+        r.text, r.cond, r.max_mel_tokens = text_tokens, cond, max_mel_tokens
         r.repetition_penalty, r.sampling = repetition_penalty, sampling
         r.caller = torch.cuda.current_stream(self.device)
         r.ready = torch.cuda.Event()
         r.ready.record(r.caller)
-        r.done = concurrent.futures.Future()
         with self._qlock:
             self._queue.append(r)
         self._lanes.submit(self._lane_job)      # one drain per request: a drain that finds the queue empty (its request was merged) returns
@@ -231,12 +291,13 @@ class BatchPipeline:
 
     def _take_acoustic(self):
         """Up to `acoustic_coalesce` decoded requests of one prompt (of any prompts with acoustic_mix_prompts), each with its own CFM
-        noise (a merged draw would consume the generator differently from the separate calls)."""
+        noise or all with noise seeds (a merged draw from torch's generator would consume it differently from the separate calls)."""
         with self._qlock:
             if not self._aq:
                 return []
             group = [self._aq.popleft()]
-            while (len(group) < self.acoustic_coalesce and self._aq and group[0][0].noise is not None and self._aq[0][0].noise is not None
+            kind = _noise_kind(group[0][0])
+            while (len(group) < self.acoustic_coalesce and self._aq and kind and _noise_kind(self._aq[0][0]) == kind
                    and (self.acoustic_mix_prompts or self._aq[0][0].cond is group[0][0].cond)):
                 group.append(self._aq.popleft())
             return group
@@ -245,7 +306,7 @@ class BatchPipeline:
     def _merge_states(group):
         """Several decoded batches as ONE acoustic batch (merge_acoustic_states).  (Measured neutral at configs[2]: 181.8 vs 182.3
         audio-s/s, profiles/README.md "Round 3"; useful where single requests are small.)"""
-        return merge_acoustic_states([(r.cond, st, r.noise) for r, st in group])
+        return merge_acoustic_states([(r.cond, st, _noise_of(r)) for r, st in group])
 
     def _acoustic_drain(self):
         group = self._take_acoustic()
@@ -257,10 +318,10 @@ class BatchPipeline:
             sa = self._stream("acoustic")
             with self._turn, torch.cuda.stream(sa):
                 if len(group) == 1:
-                    st, noise = group[0][1], group[0][0].noise
+                    st, noise = group[0][1], _noise_of(group[0][0])
                 else:
                     st, noise = self._merge_states(group)
-                wavs = self.tts.acoustic_stage(st, noise=noise)
+                wavs = _acoustic_call(self.tts, st, noise)
                 sa.synchronize()                 # the states' tensors may be released once this returns
             if self.trace is not None:
                 self.trace.append(("acoustic", t0, time.perf_counter(), st["B"]))
@@ -298,7 +359,8 @@ class BatchPipeline:
 
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "caller", "ready", "done", "codes", "left", "failed", "sampling", "seq")
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
+                 "seq")
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
@@ -384,7 +446,8 @@ class ContinuousPipeline:
 
     Greedy, unless allow_sampling: then the sessions are sampled (decode_session(sampled=True)) and submit(sampling=...) takes the
     dict gpt_stage / BatchPipeline take, plus `seed` (utterance_samplers: the per-utterance seeds are fixed at submit, so a request's
-    audio is reproducible whatever else is in flight).  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on
+    codes are reproducible whatever else is in flight; with submit(noise_seed=...) -- utterance_noise_seeds, fixed at submit too -- so
+    is its CFM noise, and with both its audio).  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on
     `slots` copies of each of its utterances (gpt.DecodeSession; sampled: with that utterance's sampler and seed), whatever else
     shares the session; they can differ from `BatchPipeline` / `synthesize_batch` results, whose decode batch is the request itself
     (the decode attention's key split and the decode GEMV are chosen by row count).  An error (say, a bad token id or a bad sampling
@@ -398,8 +461,9 @@ class ContinuousPipeline:
     acoustic_coalesce > 1: a free acoustic worker takes up to that many decoded requests -- of any prompts -- and runs their s2mel +
     vocoder as ONE batch of at most `acoustic_max_rows` rows (a request with more rows runs alone), then hands every request its own
     rows.  Each request's latent pass (`gpt_stage(codes=)`) still runs on its own: it left-pads the text, so merging it would move
-    tile boundaries.  Only requests that carry explicit `noise` are merged (BatchPipeline's rule: a merged draw would consume the
-    generator differently); the rows of requests with different prompts go through the mixed-prompt CFM (S2Mel.cfm_rows).  A failure
+    tile boundaries.  Only requests that carry explicit `noise`, or only requests with a `noise_seed`, are merged -- the two kinds not
+    with each other, and a request with neither runs alone (BatchPipeline's rule: a merged draw would consume torch's generator
+    differently); the rows of requests with different prompts go through the mixed-prompt CFM (S2Mel.cfm_rows).  A failure
     fails every request of its merged batch and nothing else.  Requests that finish in the same poll are queued together, so a worker
     that is free then sees all of them.  `trace`: set it to a list to record ("acoustic", start, end, rows, request numbers) for
     every acoustic job (host perf_counter times; requests numbered from 0 in submission order).
@@ -458,21 +522,21 @@ class ContinuousPipeline:
         return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
-               repetition_penalty: float = 10.0, sampling: Optional[dict] = None) -> concurrent.futures.Future:
-        """BatchPipeline.submit's contract (a Future of the list of waveforms); max_mel_tokens caps each row.  sampling: greedy
+               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None) -> concurrent.futures.Future:
+        """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams)."""
         if self.num_beams > 1:
             return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                                lambda B: utterance_beams(sampling, B, self.num_beams))
+                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed)
         if sampling and not self.allow_sampling:
             raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
         if sampling and int(sampling.get("num_beams") or 1) > 1:
             raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None)
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed)
 
-    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance):
+    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -482,13 +546,14 @@ class ContinuousPipeline:
         B = int(j.text.shape[0])
         j.codes, j.left, j.failed = [None] * B, B, False
         j.done = concurrent.futures.Future()
-        j.sampling, j.seq = None, -1
-        if per_utterance is not None:
-            try:
+        j.sampling, j.seq, j.noise_seeds = None, -1, None
+        try:                                    # a bad parameter fails this request's Future only
+            j.noise, j.noise_seeds = _request_noise(noise, noise_seed, B)
+            if per_utterance is not None:
                 j.sampling = per_utterance(B)
-            except ValueError as e:             # a bad parameter fails this request's Future only
-                j.done.set_exception(e)
-                return j.done
+        except ValueError as e:
+            j.done.set_exception(e)
+            return j.done
         j.caller = torch.cuda.current_stream(self.device) if self._cuda else None
         j.ready = None
         if self._cuda:
@@ -613,20 +678,21 @@ class ContinuousPipeline:
             self._alive -= 1
 
     def _take_acoustic(self) -> list:
-        """The next acoustic job: the oldest decoded request, plus -- when it carries explicit noise -- the next ones that also do,
-        up to `acoustic_coalesce` requests and `acoustic_max_rows` rows (requests without noise, or too many rows, wait for a job of
-        their own)."""
+        """The next acoustic job: the oldest decoded request, plus -- when it carries explicit noise, or noise seeds -- the next ones of
+        the same kind, up to `acoustic_coalesce` requests and `acoustic_max_rows` rows (requests with neither, of the other kind, or with
+        too many rows, wait for a job of their own)."""
         with self._cv:
             if not self._aq:
                 return []
             group = [self._aq.popleft()]
             rows = int(group[0].text.shape[0])
-            if group[0].noise is not None:
+            kind = _noise_kind(group[0])
+            if kind:
                 i = 0
                 while len(group) < self.acoustic_coalesce and i < len(self._aq):
                     j = self._aq[i]
                     nb = int(j.text.shape[0])
-                    if j.noise is not None and rows + nb <= self.acoustic_max_rows:
+                    if _noise_kind(j) == kind and rows + nb <= self.acoustic_max_rows:
                         del self._aq[i]
                         group.append(j)
                         rows += nb
@@ -658,10 +724,10 @@ class ContinuousPipeline:
                     states.append(self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens,
                                                      repetition_penalty=self.repetition_penalty, codes=codes))
                 if len(group) == 1:
-                    st, noise = states[0], group[0].noise
+                    st, noise = states[0], _noise_of(group[0])
                 else:
-                    st, noise = merge_acoustic_states([(j.cond, s, j.noise) for j, s in zip(group, states)])
-                wavs = self.tts.acoustic_stage(st, noise=noise)
+                    st, noise = merge_acoustic_states([(j.cond, s, _noise_of(j)) for j, s in zip(group, states)])
+                wavs = _acoustic_call(self.tts, st, noise)
                 if sa is not None:
                     sa.synchronize()
             if self.trace is not None:

@@ -17,9 +17,10 @@ prompts) as one s2mel + vocoder batch.  --speakers K: K synthetic prompts of dif
 frames) assigned to the utterances round-robin; a static batch then holds rows of several speakers (one PromptConditioning per
 row), and each request's noise covers its own prompt.  The JSON line also reports, per pipeline, the padding fraction of the
 acoustic batches ContinuousPipeline ran: the share of the s2mel frames B * T_max that lie beyond each row's own Tp_b + Tg_b.
+--noise-seed: requests carry submit(noise_seed=...) instead of an explicit noise tensor (the only other form that is merged).
 
     python tools/continuous_bench.py [--utterances 64] [--reps 3] [--sampling | --beams 3] [--acoustic-coalesce 4] [--speakers 3]
-                                     [--workloads ragged]
+                                     [--workloads ragged] [--noise-seed]
 """
 from __future__ import annotations
 
@@ -48,6 +49,7 @@ def main() -> int:
     ap.add_argument("--acoustic-coalesce", type=int, default=1, help="ContinuousPipeline(acoustic_coalesce=N)")
     ap.add_argument("--speakers", type=int, default=1, help="K prompts of different lengths, round-robin over the utterances")
     ap.add_argument("--workloads", default="fixed,ragged", help="comma-separated subset of fixed,ragged")
+    ap.add_argument("--noise-seed", action="store_true", help="submit(noise_seed=request number) instead of explicit noise tensors")
     args = ap.parse_args()
     if args.beams > 1 and args.sampling:
         ap.error("--sampling and --beams are separate comparisons")
@@ -76,6 +78,8 @@ def main() -> int:
     frame_s = cfg.bigvgan.total_upsample / cfg.bigvgan.sampling_rate
 
     def noise(k, rows, Tp, M):
+        if args.noise_seed:
+            return None
         return torch.from_numpy(synth.uniform(f"cbench/noise/{k}", (rows, cfg.s2mel.in_channels, Tp + int(M * cfg.code_to_frame)), 1.7)).to(dev)
 
     def cond_of(idx):        # one prompt for the request, or one per row when its utterances have different speakers
@@ -127,7 +131,7 @@ def main() -> int:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             sp = sampling.get(kind)
-            futs = [pipe.submit(t, c, max_mel_tokens=M, noise=z, sampling=(dict(sp, seed=i) if kind in seeded else dict(sp)) if sp else None)
+            futs = [pipe.submit(t, c, max_mel_tokens=M, noise=z, noise_seed=i if args.noise_seed else None, sampling=(dict(sp, seed=i) if kind in seeded else dict(sp)) if sp else None)
                     for i, (t, M, z, c) in enumerate(jobs[wl][kind])]
             for f in futs:
                 f.result()
@@ -135,7 +139,8 @@ def main() -> int:
             return time.perf_counter() - t0
 
     out = {"utterances": N, "slots": W, "text_tokens": L, "prompt_frames": plens, "reps": args.reps, "poll_steps": args.poll_steps,
-           "sampling": bool(args.sampling), "num_beams": args.beams, "acoustic_coalesce": args.acoustic_coalesce, "speakers": K}
+           "sampling": bool(args.sampling), "num_beams": args.beams, "acoustic_coalesce": args.acoustic_coalesce, "speakers": K,
+           "noise_seed": bool(args.noise_seed)}
     torch.manual_seed(0)
     base, other = ("continuous", "continuous_sampled") if args.sampling else ("batch", "continuous")
     for wl in caps:
