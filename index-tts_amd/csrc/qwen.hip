@@ -1,136 +1,26 @@
-// Qwen3 causal LM at B = 1 (qwen.h): prefill on the exact-fp32 GEMM, then a greedy decode step of five launches per layer --
-//   qkv GEMV (input RMSNorm in its prologue) | q/k RMSNorm + rotary + KV append + grouped-query attention (keys split over
-//   workgroups, merged by the last to arrive) | o_proj GEMV + residual | gate/up GEMV (post-attention RMSNorm in its prologue,
-//   silu(g) * u in its epilogue) | down_proj GEMV + residual
-// -- and a tail of final norm + head GEMV with a two-stage argmax, the optional logits hand-over, and the next token's embedding row.
-// Every per-step value lives in QwenState on the device, so one captured step replays for the whole generation.
+// Qwen3 causal LM (qwen.h), host side: loading, the workspace of a tile, the decode step's launch sequence, generation, the C API.
+// A call of B prompts is served in consecutive tiles of R <= QWEN_BATCH_ROWS rows that share every weight pass of a step; a single-prompt
+// call is a tile of one row.  Per tile: prefill on the exact-fp32 GEMM, row by row into the row's cache (not batched: a packed prefill
+// would change the GEMM's M and is not claimed to keep a row equal to its own single call), then greedy decode steps of five launches
+// per layer and a tail of three (qwen_kernels.hip).  Every per-step value lives in QwenState on the device, so one captured step
+// replays for the whole generation.
 //
-// The RMSNorm gain is applied to the activation vector in the GEMV's prologue ((x * rsqrt(mean x^2 + eps)) * g, the reference's order of
-// operations), not folded into the weights: W diag(g) would leave the bf16 grid, and bf16 storage here holds the checkpoint's weights
-// exactly.  Each workgroup redoes the norm of the <= 3072-element vector it multiplies with (L2-resident, a few hundred FMAs a thread).
-//
-// The GEMVs are plain weight streams: a wave owns whole rows, a lane the same 8 consecutive k of every 512-k chunk (two 16-byte loads
-// of fp32, one of bf16), all loads of a row pair issued before the first FMA, no branch among them (addresses past K are clamped and
-// meet zeros of x), then a shuffle butterfly.  The k -> lane map and the order of the FMAs do not depend on the storage format or on how the step is
-// launched: bf16 and fp32 storage of the same values, and eager launches and graph replay, agree bit for bit.
+// Step graphs (QwenStepGraphs): a captured step bakes in the tile's workspace layout, i.e. every row's prompt length and cap.  Tiles of
+// real texts differ in these, so up to MAX_BATCH_GRAPHS steps are kept for tiles of several rows, one per key, and the one unused
+// longest leaves; a tile whose lengths have not been seen pays one capture and instantiation.  One-row tiles keep one step of their own.
 #include "qwen.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 
-#include "device_util.h"
 #include "model_util.h"
 
 namespace idxtts {
 
 namespace {
 
-constexpr int HD = QWEN_HD, GMAX = QWEN_GMAX;      // the shared device code and its argument structs: qwen.h
-
-// ---------------------------------------------------------------------------------------------------------------------------
-template <int NCH, int EPI, typename WT>
-__global__ __launch_bounds__(256) void qwen_gemv_kernel(const QwenGemvArgs p) {
-  __shared__ float xs[NCH * 512];
-  qwen_gemv_body<NCH, EPI, WT, 1>(p, xs, 1, 0, 0);
-}
-
-template <int EPI, typename WT>
-int gemv_launch_fmt(const QwenGemvArgs& a, int blocks, hipStream_t st) {
-  const int nch = cdiv(a.K, 512);
-  if (nch <= 1) hipLaunchKernelGGL((qwen_gemv_kernel<1, EPI, WT>), dim3(blocks), dim3(256), 0, st, a);
-  else if (nch <= 2) hipLaunchKernelGGL((qwen_gemv_kernel<2, EPI, WT>), dim3(blocks), dim3(256), 0, st, a);
-  else if (nch <= 4) hipLaunchKernelGGL((qwen_gemv_kernel<4, EPI, WT>), dim3(blocks), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((qwen_gemv_kernel<6, EPI, WT>), dim3(blocks), dim3(256), 0, st, a);
-  IDX_LAUNCH_CHECK();
-  return 0;
-}
-
-int gemv_blocks(const QwenGemvArgs& a) { return cdiv(a.units, 4 * a.upw); }
-
-template <int EPI>
-int qwen_gemv(const QwenGemvArgs& a, int fmt, int rows, hipStream_t st) {
-  IDX_CHECK(a.K >= 8 && a.K % 8 == 0 && a.K <= 3072, "GEMV K must be a multiple of 8, at most 3072");
-  IDX_CHECK(a.units > 0 && a.upw > 0, "GEMV shape");
-  static const int cat = prof_register("qwen_gemv_kernel");
-  ProfScope prof(cat, st, 2.0 * rows * a.K, (double)rows * a.K * (fmt == QWEN_W_BF16 ? 2 : 4));
-  const int blocks = gemv_blocks(a);
-  return fmt == QWEN_W_BF16 ? gemv_launch_fmt<EPI, unsigned short>(a, blocks, st) : gemv_launch_fmt<EPI, float>(a, blocks, st);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// One workgroup per (kv head, key piece, query): qwen_attn_body (qwen.h)
-template <bool APPEND>
-__global__ __launch_bounds__(256) void qwen_attn_kernel(const QwenAttnArgs p) {
-  const int r = blockIdx.z;
-  qwen_attn_body<APPEND>(p, blockIdx.x, blockIdx.y, r, p.st ? p.st->pos : p.pos0 + r);
-}
-
-int qwen_attn(const QwenAttnArgs& a, int rows, bool append, int keys_hint, hipStream_t st) {
-  IDX_CHECK(a.G >= 1 && a.G <= GMAX && a.Hq == a.Hkv * a.G, "query heads per kv head: 1..4");
-  IDX_CHECK(a.nsplit >= 1 && a.slice_cap >= 1 && (a.nsplit == 1 || (a.part && a.cnt && rows == 1)), "key split");
-  const size_t lds = (size_t)a.G * a.slice_cap * sizeof(float);
-  IDX_CHECK(lds <= 40 * 1024, "context too long for the attention kernel's score buffer");
-  static const int cat = prof_register("qwen_attn_kernel");
-  ProfScope prof(cat, st, 4.0 * rows * a.Hq * (double)keys_hint * HD, 8.0 * a.Hkv * (double)keys_hint * HD);
-  const dim3 grid(a.Hkv, a.nsplit, rows);
-  if (append) hipLaunchKernelGGL(qwen_attn_kernel<true>, grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL(qwen_attn_kernel<false>, grid, dim3(256), lds, st, a);
-  IDX_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The step's last launch (one workgroup): qwen_tail_row (qwen.h)
-template <typename WT>
-__global__ __launch_bounds__(256) void qwen_tail_kernel(const QwenTailArgs p) { qwen_tail_row<WT>(p); }
-
-// out_logits[step][c] = logits[cols[c]] (cols null: column c) of a live step
-__global__ __launch_bounds__(256) void qwen_logits_kernel(const QwenState* st, const float* logits, const int* cols, int n_cols, int max_new, float* out) {
-  qwen_logits_row(st, logits, cols, n_cols, max_new, out, blockIdx.x * 256 + threadIdx.x);
-}
-
-// ---- prefill helpers (once per call, not tuned) ----
-template <typename WT>
-__global__ __launch_bounds__(256) void qwen_embed_rows_kernel(float* x, const int* ids, const void* emb, int H, int V) {
-  const int id = min(max(ids[blockIdx.x], 0), V - 1);
-  const WT* er = static_cast<const WT*>(emb) + (size_t)id * H;
-  for (int k = threadIdx.x; k < H; k += 256) x[(size_t)blockIdx.x * H + k] = load_w(er + k);
-}
-
-__global__ __launch_bounds__(256) void qwen_rmsnorm_rows_kernel(const float* x, float* y, const float* g, int H, float eps) {
-  __shared__ float red[4];
-  const float* xr = x + (size_t)blockIdx.x * H;
-  float ss = 0.0f;
-  for (int k = threadIdx.x; k < H; k += 256) ss = fmaf(xr[k], xr[k], ss);
-  const float rs = 1.0f / sqrtf(block_sum<4>(ss, red) / (float)H + eps);
-  for (int k = threadIdx.x; k < H; k += 256) y[(size_t)blockIdx.x * H + k] = (xr[k] * rs) * g[k];
-}
-
-// keys (RMSNorm + rotary) and values of every prompt position into the cache: grid (P, Hkv), one wave
-__global__ __launch_bounds__(64) void qwen_kv_store_kernel(const float* qkv, int ld_qkv, const float* kn_g, float eps, const float* rope, float* kc,
-                                                           float* vc, int Smax, int qdim, int kvdim) {
-  const int pos = blockIdx.x, kvh = blockIdx.y, lane = threadIdx.x;
-  const float* row = qkv + (size_t)pos * ld_qkv;
-  float o0, o1;
-  head_norm_rope(row + qdim + kvh * HD, kn_g, eps, rope + (size_t)pos * HD, lane, &o0, &o1);
-  float* kd = kc + ((size_t)kvh * Smax + pos) * HD;
-  kd[lane] = o0; kd[lane + 64] = o1;
-  const float* vs = row + qdim + kvdim + kvh * HD;
-  float* vd = vc + ((size_t)kvh * Smax + pos) * HD;
-  vd[lane] = vs[lane]; vd[lane + 64] = vs[lane + 64];
-}
-
-__global__ __launch_bounds__(256) void qwen_silu_mul_kernel(const float* gu, float* h, int I) {      // gu row: [gate I | up I]
-  const float* r = gu + (size_t)blockIdx.x * 2 * I;
-  for (int k = threadIdx.x; k < I; k += 256) {
-    const float g = r[k];
-    h[(size_t)blockIdx.x * I + k] = (g / (1.0f + expf(-g))) * r[I + k];
-  }
-}
-
-int nsplit_for(int Smax) { return qwen_nsplit_for(Smax); }
+constexpr int HD = QWEN_HD, GMAX = QWEN_GMAX;
 
 const char* const LAYER_KEYS[] = {"self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "self_attn.o_proj.weight",
                                   "self_attn.q_norm.weight", "self_attn.k_norm.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
@@ -141,16 +31,7 @@ const char* const INV_FREQ_KEY = "model.rotary_emb.inv_freq";
 
 // ---------------------------------------------------------------------------------------------------------------------------
 QwenModel::~QwenModel() {
-  drop_graph();
-  drop_batch_graph();
   if (own_stream) (void)hipStreamDestroy(own_stream);
-}
-
-void QwenModel::drop_graph() {
-  if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-  if (graph) (void)hipGraphDestroy(graph);
-  graph_exec = nullptr; graph = nullptr;
-  graph_key = GraphKey();
 }
 
 bool QwenModel::accepts(const std::string& name) const {
@@ -280,231 +161,307 @@ int QwenModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena
       tab[((size_t)pos * (HD / 2) + i) * 2 + 1] = (float)std::sin((double)ang);
     }
   if (up(arena, tab, &rope)) return 1;
-  return batch_prepare();
+  return qwen_kernels_prepare();
 }
 
-QwenModel::Buffers QwenModel::carve(void* ws, int P, int max_new, int n_eos, int n_cols) const {
+// Every take starts 256-aligned, so the total does not depend on the order of the takes.  The time of a step does, a little: a row's
+// id arrays sit behind its cache in a tile of several rows, and behind the step state in a tile of one row, where the other order
+// measured 0.2 - 0.3 % more per token (profiles/README.md, "One host path").
+QwenModel::Tile QwenModel::carve(void* ws, int R, const int* P, const int* max_new, int n_eos, int n_cols) const {
   const int H = cfg.hidden_size, I = cfg.intermediate_size, L = cfg.num_hidden_layers, V = cfg.vocab_size;
-  Buffers b;
+  Tile b;
+  memset(&b, 0, sizeof(b));
   Carver c(ws);
-  b.Smax = (P + max_new + 3) & ~3;
-  b.x = c.take<float>((size_t)P * H);
-  b.x2 = c.take<float>((size_t)P * H);
-  b.xn = c.take<float>((size_t)P * H);
-  b.qkv = c.take<float>((size_t)P * qkvdim());
-  b.att = c.take<float>((size_t)P * qdim());
-  b.gu = c.take<float>((size_t)P * 2 * I);
-  b.hmid = c.take<float>((size_t)P * I);
-  const size_t kv = (size_t)L * cfg.num_key_value_heads * b.Smax * HD;
-  b.kc = c.take<float>(kv);
-  b.vc = c.take<float>(kv);
-  b.xd = c.take<float>(H);
-  b.qkvd = c.take<float>(qkvdim());
-  b.attd = c.take<float>(qdim());
-  b.hd = c.take<float>(I);
-  b.logits = c.take<float>(V);
+  b.R = R;
+  const int Pmax = *std::max_element(P, P + R);
+  b.x = c.take<float>((size_t)Pmax * H);
+  b.x2 = c.take<float>((size_t)Pmax * H);
+  b.xn = c.take<float>((size_t)Pmax * H);
+  b.qkv = c.take<float>((size_t)Pmax * qkvdim());
+  b.att = c.take<float>((size_t)Pmax * qdim());
+  b.gu = c.take<float>((size_t)Pmax * 2 * I);
+  b.hmid = c.take<float>((size_t)Pmax * I);
+  for (int r = 0; r < R; ++r) {
+    b.max_new[r] = max_new[r];
+    b.Smax[r] = (P[r] + max_new[r] + 3) & ~3;
+    b.nsplit[r] = qwen_nsplit_for(b.Smax[r]);
+    b.max_nsplit = std::max(b.max_nsplit, b.nsplit[r]);
+    b.max_cap = std::max(b.max_cap, cdiv(b.Smax[r], b.nsplit[r]));
+    b.keys += b.Smax[r];
+    const size_t kv = (size_t)L * cfg.num_key_value_heads * b.Smax[r] * HD;
+    b.kc[r] = c.take<float>(kv);
+    b.vc[r] = c.take<float>(kv);
+    if (R > 1) {
+      b.prompt[r] = c.take<int>(P[r]);
+      b.forced[r] = c.take<int>(max_new[r]);
+      b.out_ids[r] = c.take<int>(max_new[r]);
+    }
+  }
+  b.xd = c.take<float>((size_t)R * H);
+  b.qkvd = c.take<float>((size_t)R * qkvdim());
+  b.attd = c.take<float>((size_t)R * qdim());
+  b.hd = c.take<float>((size_t)R * I);
+  b.logits = c.take<float>((size_t)R * V);
   b.head_blocks = cdiv(V / 2, 4 * QWEN_HEAD_UPW);
-  b.head_val = c.take<float>(b.head_blocks);
-  b.head_idx = c.take<int>(b.head_blocks);
+  b.head_val = c.take<float>((size_t)R * b.head_blocks);
+  b.head_idx = c.take<int>((size_t)R * b.head_blocks);
   b.head_cnt = c.take<unsigned>(1);
-  b.nsplit = nsplit_for(b.Smax);
-  b.attn_part = c.take<float>((size_t)cfg.num_attention_heads * b.nsplit * 130);
-  b.attn_cnt = c.take<unsigned>(cfg.num_key_value_heads);
-  b.st = c.take<QwenState>(1);
-  b.prompt = c.take<int>(P);
+  b.part_stride = cfg.num_attention_heads * b.max_nsplit * 130;
+  b.attn_part = c.take<float>((size_t)R * b.part_stride);
+  b.attn_cnt = c.take<unsigned>((size_t)R * cfg.num_key_value_heads);
+  b.st = c.take<QwenState>(R);
+  if (R > 1) b.rows = c.take<QwenBatchRow>(R);      // one row: its geometry goes into the launch arguments
+  if (R == 1) b.prompt[0] = c.take<int>(P[0]);
   b.eos = c.take<int>(std::max(1, n_eos));
-  b.forced = c.take<int>(max_new);
+  if (R == 1) b.forced[0] = c.take<int>(max_new[0]);
   b.cols = c.take<int>(std::max(1, n_cols));
-  b.out_ids = c.take<int>(max_new);
+  if (R == 1) b.out_ids[0] = c.take<int>(max_new[0]);
   b.bytes = (c.off + 255) & ~(size_t)255;
   return b;
 }
 
-int QwenModel::prefill(const Buffers& w, int P, hipStream_t st) {
-  const int H = cfg.hidden_size, I = cfg.intermediate_size, V = cfg.vocab_size, QD = qdim(), KD = kvdim(), QKV = qkvdim();
+size_t QwenModel::workspace_bytes(int B, const int* P, const int* max_new, int n_eos, int n_cols) const {
+  size_t need = 0;
+  for (int t0 = 0; t0 < B; t0 += QWEN_BATCH_ROWS)
+    need = std::max(need, carve(nullptr, std::min(QWEN_BATCH_ROWS, B - t0), P + t0, max_new + t0, n_eos, n_cols).bytes);
+  return need;
+}
+
+int QwenModel::prefill(const Tile& w, int r, int P, hipStream_t st) {
+  const int H = cfg.hidden_size, I = cfg.intermediate_size, V = cfg.vocab_size, QD = qdim(), QKV = qkvdim();
   const int Hq = cfg.num_attention_heads, Hkv = cfg.num_key_value_heads;
-  static const int cat = prof_register("qwen_prefill_rows");
-  if (fmt == QWEN_W_BF16) hipLaunchKernelGGL(qwen_embed_rows_kernel<unsigned short>, dim3(P), dim3(256), 0, st, w.x, w.prompt, embed_s.w, H, V);
-  else hipLaunchKernelGGL(qwen_embed_rows_kernel<float>, dim3(P), dim3(256), 0, st, w.x, w.prompt, embed_s.w, H, V);
-  IDX_LAUNCH_CHECK();
-  const size_t per_layer = (size_t)Hkv * w.Smax * HD;
+  if (qwen_embed_rows(w.x, w.prompt[r], embed_s.w, P, H, V, fmt, st)) return 1;
+  const size_t per_layer = (size_t)Hkv * w.Smax[r] * HD;
   for (int li = 0; li < cfg.num_hidden_layers; ++li) {
     const QwenLayer& Y = layers[li];
-    float* kc = w.kc + li * per_layer;
-    float* vc = w.vc + li * per_layer;
-    {
-      ProfScope prof(cat, st, 0.0, 8.0 * P * H);
-      hipLaunchKernelGGL(qwen_rmsnorm_rows_kernel, dim3(P), dim3(256), 0, st, w.x, w.xn, Y.in_g, H, cfg.rms_norm_eps);
-      IDX_LAUNCH_CHECK();
-    }
+    if (qwen_rmsnorm_rows(w.x, w.xn, Y.in_g, P, H, cfg.rms_norm_eps, st)) return 1;
     if (lin_exact(Y.qkv_l, w.xn, H, w.qkv, QKV, P, st)) return 1;
-    {
-      ProfScope prof(cat, st, 0.0, 16.0 * P * KD);
-      hipLaunchKernelGGL(qwen_kv_store_kernel, dim3(P, Hkv), dim3(64), 0, st, w.qkv, QKV, Y.kn_g, cfg.rms_norm_eps, rope, kc, vc, w.Smax, QD, KD);
-      IDX_LAUNCH_CHECK();
-    }
     QwenAttnArgs a;
     a.qkv = w.qkv; a.ld_qkv = QKV; a.qn_g = Y.qn_g; a.kn_g = Y.kn_g; a.eps = cfg.rms_norm_eps; a.rope = rope;
-    a.kc = kc; a.vc = vc; a.Smax = w.Smax; a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv; a.out = w.att; a.ld_out = QD;
-    a.st = nullptr; a.pos0 = 0; a.nsplit = 1; a.slice_cap = P; a.scale = 1.0f / sqrtf((float)HD);
-    if (qwen_attn(a, P, false, P, st)) return 1;
+    a.kc = w.kc[r] + li * per_layer; a.vc = w.vc[r] + li * per_layer; a.Smax = w.Smax[r]; a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv;
+    a.out = w.att; a.ld_out = QD; a.st = nullptr; a.pos0 = 0; a.nsplit = 1; a.slice_cap = P; a.scale = 1.0f / sqrtf((float)HD);
+    if (qwen_kv_store(a, P, st)) return 1;
+    if (qwen_attn(a, P, false, (double)P * P, P, st)) return 1;
     if (lin_exact(Y.o_l, w.att, QD, w.x2, H, P, st, ACT_NONE, w.x, H)) return 1;
-    {
-      ProfScope prof(cat, st, 0.0, 8.0 * P * H);
-      hipLaunchKernelGGL(qwen_rmsnorm_rows_kernel, dim3(P), dim3(256), 0, st, w.x2, w.xn, Y.post_g, H, cfg.rms_norm_eps);
-      IDX_LAUNCH_CHECK();
-    }
+    if (qwen_rmsnorm_rows(w.x2, w.xn, Y.post_g, P, H, cfg.rms_norm_eps, st)) return 1;
     if (lin_exact(Y.gu_l, w.xn, H, w.gu, 2 * I, P, st)) return 1;
-    {
-      ProfScope prof(cat, st, 0.0, 12.0 * P * I);
-      hipLaunchKernelGGL(qwen_silu_mul_kernel, dim3(P), dim3(256), 0, st, w.gu, w.hmid, I);
-      IDX_LAUNCH_CHECK();
-    }
+    if (qwen_silu_mul(w.gu, w.hmid, P, I, st)) return 1;
     if (lin_exact(Y.down_l, w.hmid, I, w.x, H, P, st, ACT_NONE, w.x2, H)) return 1;
   }
+  IDX_HIP(hipMemcpyAsync(w.xd + (size_t)r * H, w.x + (size_t)(P - 1) * H, H * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
-int QwenModel::head_tail(const Buffers& w, int max_new, int n_eos, bool forced, float* out_logits, int n_cols, bool all_cols, hipStream_t st) {
-  const int H = cfg.hidden_size, V = cfg.vocab_size;
+int QwenModel::head_tail(const Tile& w, int n_eos, bool forced, float* const* out_logits, int n_cols, bool all_cols, hipStream_t st) {
+  const int H = cfg.hidden_size, V = cfg.vocab_size, R = w.R;
   QwenGemvArgs a;
   a.wa = head_s.w; a.K = H; a.units = V / 2; a.upw = QWEN_HEAD_UPW; a.x = w.xd; a.g = norm_g; a.eps = cfg.rms_norm_eps; a.y = w.logits;
   a.part_val = w.head_val; a.part_idx = w.head_idx; a.cnt = w.head_cnt; a.st = w.st;
-  IDX_CHECK(gemv_blocks(a) == w.head_blocks, "head partial buffers");
-  if (qwen_gemv<EPI_HEAD>(a, fmt, V, st)) return 1;
-  if (out_logits) {
-    static const int cat = prof_register("qwen_logits_kernel");
-    ProfScope prof(cat, st, 0.0, 8.0 * n_cols);
-    hipLaunchKernelGGL(qwen_logits_kernel, dim3(cdiv(n_cols, 256)), dim3(256), 0, st, w.st, w.logits, all_cols ? nullptr : w.cols, n_cols, max_new, out_logits);
-    IDX_LAUNCH_CHECK();
-  }
+  a.R = R; a.ldy = V; a.part_stride = w.head_blocks;
+  IDX_CHECK(qwen_gemv_blocks(a) == w.head_blocks, "head partial buffers");
+  if (qwen_gemv(EPI_HEAD, a, fmt, V, st)) return 1;
+  if (out_logits && qwen_logits(w.st, w.logits, V, all_cols ? nullptr : w.cols, n_cols, R, w.max_new[0], out_logits[0], w.rows, st)) return 1;
   QwenTailArgs t;
-  t.st = w.st; t.out_ids = w.out_ids; t.forced = forced ? w.forced : nullptr; t.eos = w.eos; t.n_eos = n_eos; t.max_new = max_new;
-  t.emb = embed_s.w; t.H = H; t.V = V; t.xd = w.xd;
-  static const int cat = prof_register("qwen_tail_kernel");
-  ProfScope prof(cat, st, 0.0, 8.0 * H);
-  if (fmt == QWEN_W_BF16) hipLaunchKernelGGL(qwen_tail_kernel<unsigned short>, dim3(1), dim3(256), 0, st, t);
-  else hipLaunchKernelGGL(qwen_tail_kernel<float>, dim3(1), dim3(256), 0, st, t);
-  IDX_LAUNCH_CHECK();
-  return 0;
+  memset(&t, 0, sizeof(t));
+  t.st = w.st; t.eos = w.eos; t.n_eos = n_eos; t.emb = embed_s.w; t.H = H; t.V = V; t.xd = w.xd;
+  t.rows = w.rows; t.use_forced = forced ? 1 : 0;
+  if (!w.rows) { t.out_ids = w.out_ids[0]; t.forced = forced ? w.forced[0] : nullptr; t.max_new = w.max_new[0]; }
+  return qwen_tail(t, R, fmt, st);
 }
 
-int QwenModel::decode_step(const Buffers& w, int max_new, int n_eos, bool forced, float* out_logits, int n_cols, bool all_cols, hipStream_t st) {
-  const int H = cfg.hidden_size, I = cfg.intermediate_size, QD = qdim(), QKV = qkvdim();
+int QwenModel::decode_step(const Tile& w, int n_eos, bool forced, float* const* out_logits, int n_cols, bool all_cols, hipStream_t st) {
+  const int H = cfg.hidden_size, I = cfg.intermediate_size, QD = qdim(), QKV = qkvdim(), R = w.R;
   const int Hq = cfg.num_attention_heads, Hkv = cfg.num_key_value_heads;
-  const size_t per_layer = (size_t)Hkv * w.Smax * HD;
   for (int li = 0; li < cfg.num_hidden_layers; ++li) {
     const QwenLayer& Y = layers[li];
     QwenGemvArgs q;      // qkv = [q_proj; k_proj; v_proj] RMSNorm(x)
-    q.wa = Y.qkv_s.w; q.K = H; q.units = QKV / 2; q.x = w.xd; q.g = Y.in_g; q.eps = cfg.rms_norm_eps; q.y = w.qkvd;
-    if (qwen_gemv<EPI_STORE>(q, fmt, QKV, st)) return 1;
-    QwenAttnArgs a;
+    q.wa = Y.qkv_s.w; q.K = H; q.units = QKV / 2; q.x = w.xd; q.g = Y.in_g; q.eps = cfg.rms_norm_eps; q.y = w.qkvd; q.R = R; q.ldy = QKV;
+    if (qwen_gemv(EPI_STORE, q, fmt, QKV, st)) return 1;
+    QwenAttnArgs a;      // the grid and the score buffer cover the largest row; one row: that row's geometry, baked in
     a.qkv = w.qkvd; a.ld_qkv = QKV; a.qn_g = Y.qn_g; a.kn_g = Y.kn_g; a.eps = cfg.rms_norm_eps; a.rope = rope;
-    a.kc = w.kc + li * per_layer; a.vc = w.vc + li * per_layer; a.Smax = w.Smax; a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv;
-    a.out = w.attd; a.ld_out = QD; a.st = w.st; a.nsplit = w.nsplit; a.slice_cap = cdiv(w.Smax, w.nsplit);
+    a.Hq = Hq; a.Hkv = Hkv; a.G = Hq / Hkv; a.out = w.attd; a.ld_out = QD; a.st = w.st; a.nsplit = w.max_nsplit; a.slice_cap = w.max_cap;
     a.part = w.attn_part; a.cnt = w.attn_cnt; a.scale = 1.0f / sqrtf((float)HD);
-    if (qwen_attn(a, 1, true, w.Smax, st)) return 1;
+    a.rows = w.rows; a.layer = li; a.part_stride = w.part_stride;
+    if (!w.rows) {
+      const size_t off = (size_t)li * Hkv * w.Smax[0] * HD;
+      a.kc = w.kc[0] + off; a.vc = w.vc[0] + off; a.Smax = w.Smax[0];
+    }
+    if (qwen_attn(a, R, true, w.keys, w.keys, st)) return 1;
     QwenGemvArgs o;      // x += o_proj(att)
-    o.wa = Y.o_s.w; o.K = QD; o.units = H; o.x = w.attd; o.y = w.xd;
-    if (qwen_gemv<EPI_RES>(o, fmt, H, st)) return 1;
+    o.wa = Y.o_s.w; o.K = QD; o.units = H; o.x = w.attd; o.y = w.xd; o.R = R; o.ldy = H;
+    if (qwen_gemv(EPI_RES, o, fmt, H, st)) return 1;
     QwenGemvArgs g;      // h = silu(gate_proj(n)) * up_proj(n), n = RMSNorm(x)
-    g.wa = Y.gate_s.w; g.wb = Y.up_s.w; g.K = H; g.units = I; g.x = w.xd; g.g = Y.post_g; g.eps = cfg.rms_norm_eps; g.y = w.hd;
-    if (qwen_gemv<EPI_SWIGLU>(g, fmt, 2 * I, st)) return 1;
+    g.wa = Y.gate_s.w; g.wb = Y.up_s.w; g.K = H; g.units = I; g.x = w.xd; g.g = Y.post_g; g.eps = cfg.rms_norm_eps; g.y = w.hd; g.R = R; g.ldy = I;
+    if (qwen_gemv(EPI_SWIGLU, g, fmt, 2 * I, st)) return 1;
     QwenGemvArgs d;      // x += down_proj(h)
-    d.wa = Y.down_s.w; d.K = I; d.units = H; d.x = w.hd; d.y = w.xd;
-    if (qwen_gemv<EPI_RES>(d, fmt, H, st)) return 1;
+    d.wa = Y.down_s.w; d.K = I; d.units = H; d.x = w.hd; d.y = w.xd; d.R = R; d.ldy = H;
+    if (qwen_gemv(EPI_RES, d, fmt, H, st)) return 1;
   }
-  return head_tail(w, max_new, n_eos, forced, out_logits, n_cols, all_cols, st);
+  return head_tail(w, n_eos, forced, out_logits, n_cols, all_cols, st);
 }
 
-int QwenModel::generate(const int* prompt_ids, int P, int max_new, const int* eos_ids, int n_eos, const int* forced_ids, int* out_ids, int* n_out,
-                        float* out_logits, const int* logit_cols, int n_logit_cols, void* ws, size_t ws_bytes, int use_graph, hipStream_t user) {
-  IDX_CHECK(prompt_ids && out_ids && n_out, "null pointer");
-  IDX_CHECK(P > 0 && max_new > 0 && n_eos >= 0 && (n_eos == 0 || eos_ids), "shape");
+// ---------------------------------------------------------------------------------------------------------------------------
+void QwenStepGraphs::destroy(Entry& e) {
+  if (e.exec) (void)hipGraphExecDestroy(e.exec);
+  if (e.graph) (void)hipGraphDestroy(e.graph);
+  e.exec = nullptr; e.graph = nullptr;
+}
+
+void QwenStepGraphs::clear() {
+  for (Entry& e : kept_) destroy(e);
+  kept_.clear();
+}
+
+int QwenStepGraphs::get(const Key& key, hipStream_t st, const std::function<int()>& step, hipGraphExec_t* exec, bool* captured) {
+  *captured = false;
+  const auto hit = std::find_if(kept_.begin(), kept_.end(), [&](const Entry& e) { return e.key == key; });
+  if (hit != kept_.end()) {
+    std::rotate(hit, hit + 1, kept_.end());      // the latest used last
+    *exec = kept_.back().exec;
+    return 0;
+  }
+  if ((int)kept_.size() >= cap_) {
+    destroy(kept_.front());
+    kept_.erase(kept_.begin());
+  }
+  // one step runs eagerly (a first launch may load code objects, which a capture refuses), then one step is captured
+  if (step()) return 1;
+  *captured = true;
+  Entry g;
+  g.key = key;
+  IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  const int rc = step();
+  const hipError_t e = hipStreamEndCapture(st, &g.graph);
+  if (rc || e != hipSuccess) destroy(g);
+  if (rc) return 1;
+  IDX_HIP(e);
+  size_t n_nodes = 0;
+  hipError_t en = hipGraphGetNodes(g.graph, nullptr, &n_nodes);
+  std::vector<hipGraphNode_t> nodes(n_nodes);
+  if (en == hipSuccess && n_nodes) en = hipGraphGetNodes(g.graph, nodes.data(), &n_nodes);
+  bool kernels_only = true;
+  for (size_t i = 0; en == hipSuccess && i < n_nodes; ++i) {
+    hipGraphNodeType ty;
+    en = hipGraphNodeGetType(nodes[i], &ty);
+    kernels_only = kernels_only && ty == hipGraphNodeTypeKernel;
+  }
+  if (en == hipSuccess) en = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
+  if (en != hipSuccess || !kernels_only) destroy(g);
+  IDX_HIP(en);
+  IDX_CHECK(kernels_only, "the captured decode step holds a node that is not a kernel launch");
+  kernel_nodes_ = (int)n_nodes;
+  kept_.push_back(g);
+  *exec = g.exec;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+int QwenModel::generate_tile(int R, const int* const* prompts, const int* P, const int* max_new, const int* eos_ids, int n_eos,
+                             const int* const* forced_ids, int* const* out_ids, int* n_out, float* const* out_logits, const int* logit_cols,
+                             int n_cols, bool all_cols, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  const bool forced = forced_ids != nullptr;
+  const Tile w = carve(ws, R, P, max_new, n_eos, n_cols);
+  IDX_CHECK(ws && ws_bytes >= w.bytes, "workspace too small");
+  QwenBatchRow rows[QWEN_BATCH_ROWS];
+  QwenState s0[QWEN_BATCH_ROWS];
+  memset(rows, 0, sizeof(rows));
+  memset(s0, 0, sizeof(s0));
+  int Nmax = 0;
+  for (int r = 0; r < R; ++r) {
+    rows[r].kc = w.kc[r]; rows[r].vc = w.vc[r]; rows[r].Smax = w.Smax[r]; rows[r].nsplit = w.nsplit[r]; rows[r].max_new = max_new[r];
+    rows[r].out_ids = w.out_ids[r]; rows[r].forced = w.forced[r]; rows[r].out_logits = out_logits ? out_logits[r] : nullptr;
+    s0[r].pos = P[r] - 1;      // the tail of the prefill's head step moves it to P, the first generated token's position
+    Nmax = std::max(Nmax, max_new[r]);
+    IDX_HIP(hipMemcpyAsync(w.prompt[r], prompts[r], P[r] * sizeof(int), hipMemcpyHostToDevice, st));
+    if (forced) IDX_HIP(hipMemcpyAsync(w.forced[r], forced_ids[r], max_new[r] * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipMemsetAsync(w.out_ids[r], 0, max_new[r] * sizeof(int), st));
+  }
+  if (w.rows) IDX_HIP(hipMemcpyAsync(w.rows, rows, R * sizeof(QwenBatchRow), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(w.st, s0, R * sizeof(QwenState), hipMemcpyHostToDevice, st));
+  if (n_eos) IDX_HIP(hipMemcpyAsync(w.eos, eos_ids, n_eos * sizeof(int), hipMemcpyHostToDevice, st));
+  if (n_cols && !all_cols) IDX_HIP(hipMemcpyAsync(w.cols, logit_cols, n_cols * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemsetAsync(w.head_cnt, 0, sizeof(unsigned), st));
+  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, (size_t)R * cfg.num_key_value_heads * sizeof(unsigned), st));
+  IDX_HIP(hipStreamSynchronize(st));      // the host arrays above are the caller's, or this frame's
+
+  for (int r = 0; r < R; ++r)      // row by row, into the row's cache
+    if (prefill(w, r, P[r], st)) return 1;
+  const auto step = [&]() { return decode_step(w, n_eos, forced, out_logits, n_cols, all_cols, st); };
+  if (head_tail(w, n_eos, forced, out_logits, n_cols, all_cols, st)) return 1;
+
+  hipGraphExec_t exec = nullptr;
+  int n_first = 1;
+  if (use_graph && !prof_enabled() && Nmax > 2) {
+    QwenStepGraphs::Key key;
+    key.ws = ws; key.ws_bytes = ws_bytes; key.R = R; std::copy(P, P + R, key.P.begin()); std::copy(max_new, max_new + R, key.max_new.begin());
+    key.n_eos = n_eos; key.n_cols = n_cols; key.forced = forced; key.all_cols = all_cols;
+    key.out_logits = out_logits && R == 1 ? out_logits[0] : nullptr;
+    bool captured = false;
+    const int rc = (R == 1 ? graphs1 : graphs).get(key, st, std::cref(step), &exec, &captured);
+    if (captured) n_first = 2;
+    if (rc) return 1;
+  }
+  QwenState hs[QWEN_BATCH_ROWS];
+  for (int n = n_first; n < Nmax; ++n) {
+    if (exec) IDX_HIP(hipGraphLaunch(exec, st));
+    else if (step()) return 1;
+    if ((n + 1) % 8 == 0 && n + 1 < Nmax) {      // look every 8 steps: when every row is done, later launches change nothing
+      IDX_HIP(hipMemcpyAsync(hs, w.st, R * sizeof(QwenState), hipMemcpyDeviceToHost, st));
+      IDX_HIP(hipStreamSynchronize(st));
+      if (std::all_of(hs, hs + R, [](const QwenState& s) { return s.done != 0; })) break;
+    }
+  }
+  IDX_HIP(hipMemcpyAsync(hs, w.st, R * sizeof(QwenState), hipMemcpyDeviceToHost, st));
+  for (int r = 0; r < R; ++r) IDX_HIP(hipMemcpyAsync(out_ids[r], w.out_ids[r], max_new[r] * sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  for (int r = 0; r < R; ++r) {
+    IDX_CHECK(hs[r].n_out >= 1 && hs[r].n_out <= max_new[r], "generation state");
+    n_out[r] = hs[r].n_out;
+  }
+  return 0;
+}
+
+int QwenModel::generate_batch(int B, const int* prompt_ids, const int* n_prompt, const int* max_new, const int* eos_ids, int n_eos,
+                              const int* forced_ids, int* out_ids, int* n_out, float* out_logits, const int* logit_cols, int n_logit_cols, void* ws,
+                              size_t ws_bytes, int use_graph, hipStream_t user) {
+  IDX_CHECK(prompt_ids && n_prompt && max_new && out_ids && n_out, "null pointer");
+  IDX_CHECK(B > 0 && n_eos >= 0 && (n_eos == 0 || eos_ids), "shape");
   const int V = cfg.vocab_size;
   const bool all_cols = out_logits && !logit_cols;
   const int n_cols = out_logits ? (all_cols ? V : n_logit_cols) : 0;
   IDX_CHECK(!out_logits || n_cols > 0, "n_logit_cols");
-  for (int i = 0; i < P; ++i) IDX_CHECK(prompt_ids[i] >= 0 && prompt_ids[i] < V, "prompt id outside the vocabulary");
-  for (int i = 0; forced_ids && i < max_new; ++i) IDX_CHECK(forced_ids[i] >= 0 && forced_ids[i] < V, "forced id outside the vocabulary");
+  // every row is checked before anything runs
+  std::vector<size_t> p_off(B + 1, 0), m_off(B + 1, 0);
+  for (int b = 0; b < B; ++b) {
+    IDX_CHECK(n_prompt[b] > 0 && max_new[b] > 0, "shape");
+    p_off[b + 1] = p_off[b] + n_prompt[b];
+    m_off[b + 1] = m_off[b] + max_new[b];
+  }
+  for (size_t i = 0; i < p_off[B]; ++i) IDX_CHECK(prompt_ids[i] >= 0 && prompt_ids[i] < V, "prompt id outside the vocabulary");
+  for (size_t i = 0; forced_ids && i < m_off[B]; ++i) IDX_CHECK(forced_ids[i] >= 0 && forced_ids[i] < V, "forced id outside the vocabulary");
   for (int i = 0; i < n_cols && !all_cols; ++i) IDX_CHECK(logit_cols[i] >= 0 && logit_cols[i] < V, "logit column outside the vocabulary");
-  IDX_CHECK(((P + max_new + 3) & ~3) <= cfg.max_context, "prompt + max_new_tokens exceeds the context the model was created for");
-  IDX_CHECK(ws && ws_bytes >= workspace_bytes(P, max_new, n_eos, n_cols), "workspace too small");
+  for (int b = 0; b < B; ++b)
+    IDX_CHECK(((n_prompt[b] + max_new[b] + 3) & ~3) <= cfg.max_context, "prompt + max_new_tokens exceeds the context the model was created for");
+  IDX_CHECK(ws && ws_bytes >= workspace_bytes(B, n_prompt, max_new, n_eos, n_cols), "workspace too small");
   hipStream_t st = user;
   if (!user) {      // the legacy default stream cannot be captured: run on a private stream, after what the caller has queued
     if (!own_stream) IDX_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
     IDX_HIP(hipStreamSynchronize(user));
     st = own_stream;
   }
-  const Buffers w = carve(ws, P, max_new, n_eos, n_cols);
-  IDX_HIP(hipMemcpyAsync(w.prompt, prompt_ids, P * sizeof(int), hipMemcpyHostToDevice, st));
-  if (n_eos) IDX_HIP(hipMemcpyAsync(w.eos, eos_ids, n_eos * sizeof(int), hipMemcpyHostToDevice, st));
-  if (forced_ids) IDX_HIP(hipMemcpyAsync(w.forced, forced_ids, max_new * sizeof(int), hipMemcpyHostToDevice, st));
-  if (n_cols && !all_cols) IDX_HIP(hipMemcpyAsync(w.cols, logit_cols, n_cols * sizeof(int), hipMemcpyHostToDevice, st));
-  QwenState s0;
-  memset(&s0, 0, sizeof(s0));
-  s0.pos = P - 1;      // the tail of the prefill's head step moves it to P, the first generated token's position
-  IDX_HIP(hipMemcpyAsync(w.st, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemsetAsync(w.head_cnt, 0, sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(w.attn_cnt, 0, cfg.num_key_value_heads * sizeof(unsigned), st));
-  IDX_HIP(hipMemsetAsync(w.out_ids, 0, max_new * sizeof(int), st));
-  IDX_HIP(hipStreamSynchronize(st));      // the host arrays above are the caller's
-
-  if (prefill(w, P, st)) return 1;
-  IDX_HIP(hipMemcpyAsync(w.xd, w.x + (size_t)(P - 1) * cfg.hidden_size, cfg.hidden_size * sizeof(float), hipMemcpyDeviceToDevice, st));
-  const bool forced = forced_ids != nullptr;
-  if (head_tail(w, max_new, n_eos, forced, out_logits, n_cols, all_cols, st)) return 1;
-
-  const bool graph_ok = use_graph && !prof_enabled() && max_new > 2;
-  hipGraphExec_t exec = nullptr;
-  int n_first = 1;
-  if (graph_ok) {
-    GraphKey key;
-    key.ws = ws; key.ws_bytes = ws_bytes; key.P = P; key.max_new = max_new; key.n_eos = n_eos; key.n_cols = n_cols; key.forced = forced;
-    key.all_cols = all_cols; key.out_logits = out_logits;
-    if (graph_exec && graph_key == key) {
-      exec = graph_exec;
-    } else {
-      drop_graph();
-      // step 1 runs eagerly (a first launch may load code objects, which a capture refuses), then one step is captured
-      if (decode_step(w, max_new, n_eos, forced, out_logits, n_cols, all_cols, st)) return 1;
-      n_first = 2;
-      IDX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      const int rc = decode_step(w, max_new, n_eos, forced, out_logits, n_cols, all_cols, st);
-      const hipError_t e = hipStreamEndCapture(st, &graph);
-      if (rc) { drop_graph(); return 1; }
-      IDX_HIP(e);
-      IDX_HIP(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
-      size_t n_nodes = 0;
-      IDX_HIP(hipGraphGetNodes(graph, nullptr, &n_nodes));
-      std::vector<hipGraphNode_t> nodes(n_nodes);
-      if (n_nodes) IDX_HIP(hipGraphGetNodes(graph, nodes.data(), &n_nodes));
-      graph_kernel_nodes = 0;
-      for (hipGraphNode_t n : nodes) {
-        hipGraphNodeType ty;
-        IDX_HIP(hipGraphNodeGetType(n, &ty));
-        IDX_CHECK(ty == hipGraphNodeTypeKernel, "the captured decode step holds a node that is not a kernel launch");
-        ++graph_kernel_nodes;
-      }
-      graph_key = key;
-      exec = graph_exec;
+  for (int t0 = 0; t0 < B; t0 += QWEN_BATCH_ROWS) {      // consecutive tiles on the one workspace; each ends with the stream finished
+    const int R = std::min(QWEN_BATCH_ROWS, B - t0);
+    const int* prompts[QWEN_BATCH_ROWS]; const int* forced[QWEN_BATCH_ROWS]; int* outs[QWEN_BATCH_ROWS]; float* lg[QWEN_BATCH_ROWS];
+    for (int r = 0; r < R; ++r) {
+      prompts[r] = prompt_ids + p_off[t0 + r];
+      forced[r] = forced_ids ? forced_ids + m_off[t0 + r] : nullptr;
+      outs[r] = out_ids + m_off[t0 + r];
+      lg[r] = out_logits ? out_logits + m_off[t0 + r] * (size_t)n_cols : nullptr;
     }
+    if (generate_tile(R, prompts, n_prompt + t0, max_new + t0, eos_ids, n_eos, forced_ids ? forced : nullptr, outs, n_out + t0,
+                      out_logits ? lg : nullptr, logit_cols, n_cols, all_cols, ws, ws_bytes, use_graph, st))
+      return 1;
   }
-  QwenState hs;
-  for (int n = n_first; n < max_new; ++n) {
-    if (exec) IDX_HIP(hipGraphLaunch(exec, st));
-    else if (decode_step(w, max_new, n_eos, forced, out_logits, n_cols, all_cols, st)) return 1;
-    if ((n + 1) % 8 == 0 && n + 1 < max_new) {      // an end id ends the generation: look every 8 steps (later launches change nothing)
-      IDX_HIP(hipMemcpyAsync(&hs, w.st, sizeof(hs), hipMemcpyDeviceToHost, st));
-      IDX_HIP(hipStreamSynchronize(st));
-      if (hs.done) break;
-    }
-  }
-  IDX_HIP(hipMemcpyAsync(&hs, w.st, sizeof(hs), hipMemcpyDeviceToHost, st));
-  IDX_HIP(hipMemcpyAsync(out_ids, w.out_ids, max_new * sizeof(int), hipMemcpyDeviceToHost, st));
-  IDX_HIP(hipStreamSynchronize(st));
-  IDX_CHECK(hs.n_out >= 1 && hs.n_out <= max_new, "generation state");
-  *n_out = hs.n_out;
   return 0;
 }
 
@@ -544,28 +501,48 @@ int idxtts_qwen_set_weight_format(idxtts_ctx* ctx, int format) {
   return 0;
 }
 
-size_t idxtts_qwen_workspace_bytes(const idxtts_ctx* ctx, int n_prompt, int max_new_tokens, int n_eos, int n_logit_cols) {
-  if (!ctx || n_prompt <= 0 || max_new_tokens <= 0 || n_eos < 0 || n_logit_cols < 0) return 0;
+size_t idxtts_qwen_batch_workspace_bytes(const idxtts_ctx* ctx, int B, const int* n_prompt, const int* max_new_tokens, int n_eos, int n_logit_cols) {
+  if (!ctx || B < 1 || !n_prompt || !max_new_tokens || n_eos < 0 || n_logit_cols < 0) return 0;
+  for (int b = 0; b < B; ++b)
+    if (n_prompt[b] <= 0 || max_new_tokens[b] <= 0) return 0;
   auto* m = dynamic_cast<const QwenModel*>(ctx->model.get());
-  return m ? m->workspace_bytes(n_prompt, max_new_tokens, n_eos, n_logit_cols) : 0;
+  return m ? m->workspace_bytes(B, n_prompt, max_new_tokens, n_eos, n_logit_cols) : 0;
 }
 
-int idxtts_qwen_generate(idxtts_ctx* ctx, const int* prompt_ids, int n_prompt, int max_new_tokens, const int* eos_ids, int n_eos,
-                         const int* forced_ids, int* out_ids, int* n_out, float* out_logits, const int* logit_cols, int n_logit_cols,
-                         void* workspace, size_t bytes, int use_graph, void* stream) {
+size_t idxtts_qwen_workspace_bytes(const idxtts_ctx* ctx, int n_prompt, int max_new_tokens, int n_eos, int n_logit_cols) {
+  return idxtts_qwen_batch_workspace_bytes(ctx, 1, &n_prompt, &max_new_tokens, n_eos, n_logit_cols);
+}
+
+int idxtts_qwen_max_batch(const idxtts_ctx* ctx) {
+  if (!ctx) return -1;
+  return dynamic_cast<const QwenModel*>(ctx->model.get()) ? QWEN_BATCH_ROWS : -1;
+}
+
+int idxtts_qwen_generate_batch(idxtts_ctx* ctx, int B, const int* prompt_ids, const int* n_prompt, const int* max_new_tokens, const int* eos_ids,
+                               int n_eos, const int* forced_ids, int* out_ids, int* n_out, float* out_logits, const int* logit_cols,
+                               int n_logit_cols, void* workspace, size_t bytes, int use_graph, void* stream) {
   try {
     IDX_CHECK(ctx && ctx->finalized, "context not finalized");
     auto* m = dynamic_cast<QwenModel*>(ctx->model.get());
     IDX_CHECK(m, "not a Qwen context");
-    return m->generate(prompt_ids, n_prompt, max_new_tokens, eos_ids, n_eos, forced_ids, out_ids, n_out, out_logits, logit_cols, n_logit_cols,
-                       workspace, bytes, use_graph, static_cast<hipStream_t>(stream));
+    return m->generate_batch(B, prompt_ids, n_prompt, max_new_tokens, eos_ids, n_eos, forced_ids, out_ids, n_out, out_logits, logit_cols,
+                             n_logit_cols, workspace, bytes, use_graph, static_cast<hipStream_t>(stream));
   } catch (const std::exception& e) { return fail(__FILE__, __LINE__, std::string("exception: ") + e.what()); }
 }
 
-int idxtts_qwen_step_graph_launches(const idxtts_ctx* ctx) {
-  if (!ctx) return -1;
-  auto* m = dynamic_cast<const QwenModel*>(ctx->model.get());
-  return m && m->graph_exec ? m->graph_kernel_nodes : -1;
+// a single-prompt call is a batch of one row
+int idxtts_qwen_generate(idxtts_ctx* ctx, const int* prompt_ids, int n_prompt, int max_new_tokens, const int* eos_ids, int n_eos,
+                         const int* forced_ids, int* out_ids, int* n_out, float* out_logits, const int* logit_cols, int n_logit_cols,
+                         void* workspace, size_t bytes, int use_graph, void* stream) {
+  return idxtts_qwen_generate_batch(ctx, 1, prompt_ids, &n_prompt, &max_new_tokens, eos_ids, n_eos, forced_ids, out_ids, n_out, out_logits,
+                                    logit_cols, n_logit_cols, workspace, bytes, use_graph, stream);
 }
+
+static int kept_launches(const idxtts_ctx* ctx, QwenStepGraphs QwenModel::*which) {
+  auto* m = ctx ? dynamic_cast<const QwenModel*>(ctx->model.get()) : nullptr;
+  return m ? (m->*which).launches() : -1;
+}
+int idxtts_qwen_step_graph_launches(const idxtts_ctx* ctx) { return kept_launches(ctx, &QwenModel::graphs1); }
+int idxtts_qwen_batch_step_graph_launches(const idxtts_ctx* ctx) { return kept_launches(ctx, &QwenModel::graphs); }
 
 }  // extern "C"

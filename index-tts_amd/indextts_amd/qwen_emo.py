@@ -84,8 +84,13 @@ def rotary_inv_freq(cfg: QwenConfig) -> torch.Tensor:
     return 1.0 / (cfg.rope_theta ** (torch.arange(0, cfg.head_dim, 2, dtype=torch.int64).float() / cfg.head_dim))
 
 
+def _hp(a):
+    """Host pointer of a numpy array (null for None or an empty one)."""
+    return c_void_p(a.ctypes.data) if a is not None and a.size else c_void_p(0)
+
+
 class QwenLM:
-    """Qwen3 causal LM on the HIP library: `generate(prompt_ids, ...)` = prefill + greedy decode, B = 1."""
+    """Qwen3 causal LM on the HIP library: `generate(prompt_ids, ...)` = prefill + greedy decode; `generate_batch` for several prompts."""
 
     def __init__(self, state_dict, cfg: QwenConfig = QwenConfig(), device="cuda:0", weight_format: str = "bf16"):
         if weight_format not in WEIGHT_FORMATS:
@@ -107,33 +112,36 @@ class QwenLM:
                 lib.idxtts_qwen_set_weight_format(ctx, WEIGHT_FORMATS[weight_format])))
         self._ws = _lib.StreamWorkspaces(2)
 
+    def _call_args(self, eos_ids, logits: bool, logit_cols):
+        """What `generate` and `generate_batch` hand over alike: (eos, cols, n_cols), then the C arguments that follow out_logits."""
+        eos = np.ascontiguousarray(list(eos_ids), dtype=np.int32).reshape(-1)
+        cols = None if logit_cols is None else np.ascontiguousarray(logit_cols, dtype=np.int32).reshape(-1)
+        n_cols = 0 if not logits else (self.cfg.vocab_size if cols is None else int(cols.size))
+        return eos, cols, n_cols, (_hp(cols) if logits else c_void_p(0), 0 if cols is None else int(cols.size))
+
     def generate(self, prompt_ids, max_new_tokens: int, eos_ids=(), forced_ids=None, logits: bool = False, logit_cols=None,
                  use_graph: bool = True):
         """Greedy continuation of `prompt_ids`: returns (ids, logits).  ids: each step's argmax up to and including the first one in
         `eos_ids` (or `max_new_tokens` of them); logits: None, or a [len(ids), n] float32 tensor of every step's logits at
         `logit_cols` (all columns when None).  forced_ids: teacher forcing -- they continue the sequence, ids stay the model's own."""
         prompt = np.ascontiguousarray(prompt_ids, dtype=np.int32).reshape(-1)
-        eos = np.ascontiguousarray(list(eos_ids), dtype=np.int32).reshape(-1)
+        eos, cols, n_cols, col_args = self._call_args(eos_ids, logits, logit_cols)
         P, M = int(prompt.size), int(max_new_tokens)
         forced = None
         if forced_ids is not None:
             forced = np.ascontiguousarray(forced_ids, dtype=np.int32).reshape(-1)
             if forced.size != M:
                 raise ValueError("forced_ids needs max_new_tokens entries")
-        cols = None if logit_cols is None else np.ascontiguousarray(logit_cols, dtype=np.int32).reshape(-1)
-        n_cols = 0 if not logits else (self.cfg.vocab_size if cols is None else int(cols.size))
         out_ids = np.zeros(M, dtype=np.int32)
         n_out = c_int(0)
-        hp = lambda a: c_void_p(a.ctypes.data) if a is not None and a.size else c_void_p(0)
         with torch.cuda.device(self.device):
             need = self._lib.idxtts_qwen_workspace_bytes(self._h, P, M, int(eos.size), n_cols)
             if need == 0:
                 raise ValueError("empty prompt or max_new_tokens < 1")
             ws = self._ws.get(need, self.device)
             lg = torch.zeros(M, n_cols, dtype=torch.float32, device=self.device) if logits else None
-            _lib.check(self._lib.idxtts_qwen_generate(self._h, hp(prompt), P, M, hp(eos), int(eos.size), hp(forced), hp(out_ids),
-                                                      ctypes.byref(n_out), _lib.ptr(lg), hp(cols) if logits else c_void_p(0),
-                                                      0 if cols is None else int(cols.size), _lib.ptr(ws), ws.numel(), int(use_graph),
+            _lib.check(self._lib.idxtts_qwen_generate(self._h, _hp(prompt), P, M, _hp(eos), int(eos.size), _hp(forced), _hp(out_ids),
+                                                      ctypes.byref(n_out), _lib.ptr(lg), *col_args, _lib.ptr(ws), ws.numel(), int(use_graph),
                                                       _lib.current_stream()))
         n = n_out.value
         return out_ids[:n].tolist(), (lg[:n] if logits else None)
@@ -154,32 +162,28 @@ class QwenLM:
         caps = [int(max_new_tokens)] * B if np.isscalar(max_new_tokens) else [int(m) for m in max_new_tokens]
         if len(caps) != B:
             raise ValueError("max_new_tokens: an int, or one per prompt")
-        eos = np.ascontiguousarray(list(eos_ids), dtype=np.int32).reshape(-1)
+        eos, cols, n_cols, col_args = self._call_args(eos_ids, logits, logit_cols)
         forced = None
         if forced_ids is not None:
             fr = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for f in forced_ids]
             if len(fr) != B or any(f.size != m for f, m in zip(fr, caps)):
                 raise ValueError("forced_ids needs one array per prompt with that row's max_new_tokens entries")
             forced = np.ascontiguousarray(np.concatenate(fr)) if fr else None
-        cols = None if logit_cols is None else np.ascontiguousarray(logit_cols, dtype=np.int32).reshape(-1)
-        n_cols = 0 if not logits else (self.cfg.vocab_size if cols is None else int(cols.size))
         n_prompt = np.ascontiguousarray([r.size for r in rows], dtype=np.int32)
         max_new = np.ascontiguousarray(caps, dtype=np.int32)
         flat = np.ascontiguousarray(np.concatenate(rows)) if all(r.size for r in rows) else np.zeros(0, dtype=np.int32)
         total = int(sum(max(0, m) for m in caps))
         out_ids = np.zeros(max(1, total), dtype=np.int32)
         n_out = np.zeros(B, dtype=np.int32)
-        hp = lambda a: c_void_p(a.ctypes.data) if a is not None and a.size else c_void_p(0)
         with torch.cuda.device(self.device):
-            need = self._lib.idxtts_qwen_batch_workspace_bytes(self._h, B, hp(n_prompt), hp(max_new), int(eos.size), n_cols)
+            need = self._lib.idxtts_qwen_batch_workspace_bytes(self._h, B, _hp(n_prompt), _hp(max_new), int(eos.size), n_cols)
             if need == 0:
                 raise ValueError("empty prompt or max_new_tokens < 1")
             ws = self._ws.get(need, self.device)
             lg = torch.zeros(total, n_cols, dtype=torch.float32, device=self.device) if logits else None
-            _lib.check(self._lib.idxtts_qwen_generate_batch(self._h, B, hp(flat), hp(n_prompt), hp(max_new), hp(eos), int(eos.size), hp(forced),
-                                                            hp(out_ids), hp(n_out), _lib.ptr(lg), hp(cols) if logits else c_void_p(0),
-                                                            0 if cols is None else int(cols.size), _lib.ptr(ws), ws.numel(), int(use_graph),
-                                                            _lib.current_stream()))
+            _lib.check(self._lib.idxtts_qwen_generate_batch(self._h, B, _hp(flat), _hp(n_prompt), _hp(max_new), _hp(eos), int(eos.size), _hp(forced),
+                                                            _hp(out_ids), _hp(n_out), _lib.ptr(lg), *col_args, _lib.ptr(ws), ws.numel(),
+                                                            int(use_graph), _lib.current_stream()))
         ids, lgs, off = [], [], 0
         for b in range(B):
             n = int(n_out[b])

@@ -2,8 +2,8 @@
 claims to reach.  Shared by the generator (tests/golden/make_qwen_golden.py shapes), tests/test_qwen_emo_cpu.py and the GPU tests; it
 imports no transformers.
 
-The geometry is restated here from the library's workspace layout (csrc/qwen.hip: QwenModel::carve, nsplit_for, decode_step, the GEMV
-launcher), in plain Python, so a case that stops reaching its path fails a CPU test instead of passing quietly:
+The geometry is restated here from the library's workspace layout (csrc/qwen.hip: QwenModel::carve, decode_step; csrc/qwen.h: qwen_nsplit_for;
+csrc/qwen_kernels.hip: the GEMV launcher), in plain Python, so a case that stops reaching its path fails a CPU test instead of passing quietly:
     Smax      = (P + max_new + 3) & ~3           rows of the KV cache
     nsplit    = min(16, max(1, cdiv(Smax, 64)))  key pieces of a decode step (1: the unsplit return)
     slice_cap = cdiv(Smax, nsplit)               score slots of a piece; > 256 makes the 256-thread score pass loop twice

@@ -98,6 +98,26 @@ def test_batch_workspace_refusals_and_growth():
         lib.idxtts_ctx_destroy(h)
 
 
+def test_a_batch_of_one_needs_the_single_call_workspace():
+    """Both size functions go through the one carve: a one-row tile takes no row table."""
+    from indextts_amd import _lib
+    lib = _lib.load()
+    cfg = qs.CONFIGS["tiny"]
+    c = _lib.QwenConfigC(cfg.vocab_size, cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers, cfg.num_attention_heads,
+                         cfg.num_key_value_heads, cfg.head_dim, cfg.rms_norm_eps, cfg.rope_theta, int(cfg.tie_word_embeddings), cfg.max_context)
+    h = ctypes.c_void_p()
+    _lib.check(lib.idxtts_qwen_create(ctypes.byref(c), ctypes.byref(h)))
+    try:
+        for P, M in ((1, 3), (40, 25), (63, 8), (65, 8), (980, 40)):
+            for n_eos, n_cols in ((0, 0), (1, 64), (2, 512)):
+                Pa, Ma = np.ascontiguousarray([P], dtype=np.int32), np.ascontiguousarray([M], dtype=np.int32)
+                one = lib.idxtts_qwen_workspace_bytes(h, P, M, n_eos, n_cols)
+                batch = lib.idxtts_qwen_batch_workspace_bytes(h, 1, ctypes.c_void_p(Pa.ctypes.data), ctypes.c_void_p(Ma.ctypes.data), n_eos, n_cols)
+                assert batch == one > 0, (P, M, n_eos, n_cols)
+    finally:
+        lib.idxtts_ctx_destroy(h)
+
+
 @pytest.fixture(scope="module")
 def lm_golden(golden_dir):
     return {f: dict(np.load(os.path.join(golden_dir, f))) for f in ("qwen_lm.npz", "qwen_lm_shapes.npz")}

@@ -1,4 +1,4 @@
-"""GPU: batched generation of the Qwen3 decoder (csrc/qwen_batch.hip through QwenLM.generate_batch, QwenEmotion.inference_batch and
+"""GPU: batched generation of the Qwen3 decoder (csrc/qwen.hip, csrc/qwen_kernels.hip through QwenLM.generate_batch, QwenEmotion.inference_batch and
 IndexTTS2.conditionings_from_emo_texts).  Rows of a batch are independent, so every expectation is the single-prompt one: the
 fixtures tests/golden/qwen_lm.npz and qwen_lm_shapes.npz (third-party transformers on the same synthetic weights; case list:
 tests/qwen_shapes.py) give each row's ids and logits within that case's own logit_tol, and `generate` on the same model gives them
@@ -206,7 +206,53 @@ def test_launch_count(shapes, device):
     assert 0 < lm.batch_step_graph_launches() <= 5 * layers + 2
 
 
-# ---- 8. the classifier and the conditioning helper ----
+# ---- 8. the kept step graphs: one more key than the tiles' cache holds, and the two caches side by side ----
+MAX_BATCH_GRAPHS = 8      # QwenModel::MAX_BATCH_GRAPHS (csrc/qwen.h)
+
+
+def test_step_graph_eviction_and_recapture(shapes, device):
+    lm = _lm("tiny_p40_n25", "bf16", shapes, device)
+    (pa, ia, _), (pb, ib, _) = qs.stored("tiny_p40_n25", shapes), qs.stored("tiny_p40_n25_b", shapes)
+    layers = qs.CONFIGS["tiny"].num_hidden_layers
+
+    def call(i):
+        caps = [3 + i, 4]
+        ids, lg = lm.generate_batch([pa, pb], caps, logits=True)
+        assert ids == [ia.tolist()[:caps[0]], ib.tolist()[:caps[1]]], i
+        assert 0 < lm.batch_step_graph_launches() <= 5 * layers + 3, i
+        return ids, lg
+
+    first = call(0)
+    for i in range(1, MAX_BATCH_GRAPHS + 1):      # nine distinct keys: the first one leaves
+        call(i)
+    again = call(0)                               # captured anew
+    assert again[0] == first[0]
+    assert all(torch.equal(a, b) for a, b in zip(again[1], first[1]))
+
+
+def test_the_two_step_graph_caches_do_not_disturb_each_other(shapes, device):
+    lm = _lm("tiny_p40_n25", "bf16", shapes, device)
+    (pa, ia, _), (pb, ib, _) = qs.stored("tiny_p40_n25", shapes), qs.stored("tiny_p40_n25_b", shapes)
+    assert len(ia) == len(ib) == 25
+    single = lambda: lm.generate(pa, 25, logits=True)
+    batch = lambda: lm.generate_batch([pa, pb], [25, 25], logits=True)
+    one = single()
+    kept = lm.step_graph_launches()
+    assert kept > 0
+    batch()
+    two = single()
+    assert two[0] == one[0] == ia.tolist() and torch.equal(two[1], one[1])
+    assert lm.step_graph_launches() == kept
+    b1 = batch()
+    kept_b = lm.batch_step_graph_launches()
+    assert kept_b > 0
+    single()
+    b2 = batch()
+    assert b2[0] == b1[0] == [ia.tolist(), ib.tolist()] and all(torch.equal(x, y) for x, y in zip(b2[1], b1[1]))
+    assert lm.batch_step_graph_launches() == kept_b and lm.step_graph_launches() == kept
+
+
+# ---- 9. the classifier and the conditioning helper ----
 class ScoringTokenizer(StubTokenizer):
     """decode: a JSON answer whose scores come from the generated ids, so the emotion vector depends on what the GPU decoded."""
 
