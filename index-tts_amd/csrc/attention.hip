@@ -17,6 +17,9 @@
 // accumulator registers and feed the second product directly as its B operand
 //   O^T += V^T . P^T   (2 tiles of 32 d x 32 queries, k-order = accumulator row order)
 // so P never touches LDS.  Q fragments live in registers for the whole kernel (pre-scaled by 1/8).
+//
+// Three kernels share this design and the helpers below: flash_attn_f32_kernel (exact fp32 MFMAs), flash_attn_bf16x3_kernel
+// (split-bf16 MFMAs on the same fp32 inputs) and flash_attn_planes_kernel (split-bf16 planes in, LDS-DMA ring).
 #include <algorithm>
 
 #include "attention.h"
@@ -39,41 +42,146 @@ constexpr float NEG_BIG = -1e30f;
 constexpr int REL_MAX = 96;  // rows of a relative_key table (three 32-row tiles)
 constexpr int REL_ROW = 97;  // floats per query in the LDS table of q . rel_key products (odd: lanes = queries hit distinct banks)
 constexpr int REL_LDS = 4 * 32 * REL_ROW * (int)sizeof(float);      // dynamic LDS of a relative_key launch: one table per wave
+constexpr int STAGE_FLOATS = 4 * 32 * 65;      // output transpose buffer: per wave 32 queries x (64 + 1 pad) dims
 
-// scores of one 32 x 32 tile (register r of lane half h = key key0 + (r & 3) + 8 (r >> 2) + 4 h, lane j = query qi) += the relative_key
-// term from the wave's table
-__device__ __forceinline__ void add_rel_term(f32x16& s, const float* tbl_row, int key0, int q0, int qi, int h, int L, int R) {
-  const int dmin = key0 - (q0 + 31), dmax = key0 + 31 - q0;      // range of key - query over the tile (wave-uniform)
+// Accumulator layout of a 32 x 32 MFMA: register r of lane half h holds row (r & 3) + 8 (r >> 2) + 4 h -- a key of S^T, a dim of
+// O^T -- of column lane & 31 (a query)
+__device__ __forceinline__ int acc_key(int r, int h, int key0 = 0) { return key0 + (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+struct WaveLane {
+  int tid, wave, lane;
+  int h, j;        // lane half, column of the accumulator tile
+  int q0, qi;      // this wave's first query, this lane's query
+};
+__device__ __forceinline__ WaveLane wave_lane(int qblk) {
+  WaveLane w;
+  w.tid = threadIdx.x; w.wave = w.tid >> 6; w.lane = w.tid & 63;
+  w.h = w.lane >> 5; w.j = w.lane & 31;
+  w.q0 = qblk * 128 + w.wave * 32;
+  w.qi = w.q0 + w.j;
+  return w;
+}
+
+// keys of batch row b that query block qblk can see at all: valid keys [kstart, kend), walked as ntiles 32-key tiles from k_lo
+struct KeyRange {
+  int kstart, kend, k_lo, ntiles;
+  __device__ __forceinline__ bool sees(int key, int qi, int causal) const { return key >= kstart && key < kend && (!causal || key <= qi); }
+};
+__device__ __forceinline__ KeyRange visible_keys(const AttnArgs& p, int b, int qblk) {
+  KeyRange k;
+  k.kstart = p.kstart ? p.kstart[b] : 0;
+  k.kend = p.kend ? min(p.kend[b], p.Sk) : p.Sk;
+  int k_hi = k.kend;
+  if (p.causal) k_hi = min(k_hi, qblk * 128 + 128);
+  k.k_lo = k.kstart & ~31;
+  k.ntiles = k_hi > k.k_lo ? (k_hi - k.k_lo + 31) >> 5 : 0;
+  return k;
+}
+
+// A 32 x 64 fp32 tile is 512 float4: thread tid moves float4 tid and tid + 256, i.e. (row, c4) = (idx >> 4, idx & 15).
+// K and V rows key0 .. key0 + 31 into registers (rows past Sk as zeros); the kernel's store_kv puts them into LDS a tile later.
+__device__ __forceinline__ void load_kv(const AttnArgs& p, const float* kb, const float* vb, int key0, int tid, f32x4 (&kr)[2], f32x4 (&vr)[2]) {
+#pragma unroll
+  for (int l = 0; l < 2; ++l) {
+    const int idx = tid + 256 * l;
+    const int row = idx >> 4, c4 = idx & 15;
+    const int key = key0 + row;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
+    if (key < p.Sk) {
+      a = *reinterpret_cast<const f32x4*>(kb + (size_t)key * p.k_ts + c4 * 4);
+      c = *reinterpret_cast<const f32x4*>(vb + (size_t)key * p.v_ts + c4 * 4);
+    }
+    kr[l] = a;
+    vr[l] = c;
+  }
+}
+
+// relative_key: tbl_row[r] = q . rel_key[r] for this lane's query, once per workgroup.  The table's rows go through the kernel's K
+// tile and its QK product: store_k(row, c4, float4) writes a piece of K tile 0, qk() multiplies that tile by the wave's queries.
+template <class StoreK, class QK>
+__device__ __forceinline__ void build_rel_table(const AttnArgs& p, const WaveLane& w, float* tbl_row, StoreK store_k, QK qk) {
+  const int nrel = p.rel_left + p.rel_right + 1;
+  for (int rt = 0; rt * 32 < nrel; ++rt) {
+#pragma unroll
+    for (int l = 0; l < 2; ++l) {
+      const int idx = w.tid + 256 * l, row = idx >> 4, c4 = idx & 15, rr = rt * 32 + row;
+      f32x4 a = {0.f, 0.f, 0.f, 0.f};
+      if (rr < nrel) a = *reinterpret_cast<const f32x4*>(p.rel_key + (size_t)rr * 64 + c4 * 4);
+      store_k(row, c4, a);
+    }
+    __syncthreads();
+    const f32x16 s = qk();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tbl_row[rt * 32 + acc_key(r, w.h)] = s[r];
+    __syncthreads();
+  }
+}
+
+// scores of one 32 x 32 tile (keys key0 + acc_key, lane j = query qi) += the relative_key term from the wave's table
+__device__ __forceinline__ void add_rel_term(f32x16& s, const float* tbl_row, int key0, const WaveLane& w, int L, int R) {
+  const int dmin = key0 - (w.q0 + 31), dmax = key0 + 31 - w.q0;      // range of key - query over the tile (wave-uniform)
   if (dmax <= -L || dmin >= R) {
     const float c = tbl_row[dmax <= -L ? 0 : L + R];
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] += c;
   } else {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      s[r] += tbl_row[min(max(key - qi, -L), R) + L];
+    for (int r = 0; r < 16; ++r) s[r] += tbl_row[min(max(acc_key(r, w.h, key0) - w.qi, -L), R) + L];
+  }
+}
+
+// Normalise and store: O^T tiles (rows = d, cols = query) -> O[b][q][head*64 + d] through LDS.  `stage` is the kernel's K/V LDS, which
+// every wave must be done with.  PLANES: p.o may be null, and p.o_planes (if set) also takes the output as split-bf16 planes.
+template <bool PLANES, class Args>
+__device__ __forceinline__ void write_output(const Args& p, const f32x16 (&o)[2], float l_run, float* stage, const WaveLane& w, int b, int hd) {
+  const float l_tot = xor32_sum(l_run);
+  const float inv_l = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+  stage += w.wave * (32 * 65);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) stage[w.j * 65 + t * 32 + acc_key(r, w.h)] = o[t][r] * inv_l;
+  __syncthreads();
+  float* ob = (!PLANES || p.o) ? p.o + (size_t)b * p.o_bs + hd * 64 : nullptr;
+  __bf16* const o_hi = PLANES ? static_cast<__bf16*>(p.o_planes) : nullptr;
+  __bf16* const o_lo = o_hi ? o_hi + plane_elems(p.B * p.Sq, p.H * 64) : nullptr;
+#pragma unroll
+  for (int it = 0; it < 32; ++it) {                  // one 256-byte output row per wave-instruction
+    const int qq = w.q0 + it;
+    if (qq < p.Sq) {
+      const float val = stage[it * 65 + w.lane];
+      if (!PLANES || ob) ob[(size_t)qq * p.o_ts + w.lane] = val;
+      if (o_hi) {
+        const __bf16 hi = (__bf16)val;
+        const size_t at = plane_index(b * p.Sq + qq, hd * 64 + w.lane, p.B * p.Sq);
+        o_hi[at] = hi;
+        o_lo[at] = (__bf16)(val - (float)hi);
+      }
     }
   }
 }
 
+// S^T = K . Q^T of the f32 kernel: K rows are ds_read_b128 A operands, lane (j, h) holds Q[qi][8g + 4h + e] in qf[g][e]
+__device__ __forceinline__ f32x16 qk_f32(const float* kt, const f32x4 (&qf)[8], const WaveLane& w) {
+  f32x16 s = {};
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    const f32x4 kf = *reinterpret_cast<const f32x4*>(kt + w.j * KROW + 8 * g + 4 * w.h);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[g][e], s, 0, 0, 0);
+  }
+  return s;
+}
+
 __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) float smem[2 * 32 * KROW + 2 * 32 * 64];
+  static_assert(STAGE_FLOATS <= 2 * 32 * KROW + 2 * 32 * 64, "output staging must fit in the K/V tiles");
   float (*Ks)[32 * KROW] = reinterpret_cast<float (*)[32 * KROW]>(smem);
   float (*Vs)[32 * 64] = reinterpret_cast<float (*)[32 * 64]>(smem + 2 * 32 * KROW);
 
   const int qblk = blockIdx.x, hd = blockIdx.y, b = blockIdx.z;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int h = lane >> 5, j = lane & 31;
-  const int q0 = qblk * 128 + wave * 32;            // this wave's first query
-  const int qi = q0 + j;                            // this lane's query
-  const int kstart = p.kstart ? p.kstart[b] : 0;
-  const int kend = p.kend ? min(p.kend[b], p.Sk) : p.Sk;
-  // keys this block can see at all
-  int k_hi = kend;
-  if (p.causal) k_hi = min(k_hi, qblk * 128 + 128);
-  const int k_lo = kstart & ~31;
-  const int ntiles = k_hi > k_lo ? (k_hi - k_lo + 31) >> 5 : 0;
+  const WaveLane w = wave_lane(qblk);
+  const KeyRange keys = visible_keys(p, b, qblk);
 
   const float* qb = p.q + (size_t)b * p.q_bs + hd * 64;
   const float* kb = p.k + (size_t)b * p.k_bs + hd * 64;
@@ -82,109 +190,56 @@ __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const AttnArgs p) {
   // Q fragments: B operand of K.Q^T -> lane (j,h) holds Q[qi][8g + 4h + s], g = 0..7
   f32x4 qf[8];
   {
-    const bool ok = qi < p.Sq;
-    const float* qrow = qb + (size_t)(ok ? qi : 0) * p.q_ts;
+    const bool ok = w.qi < p.Sq;
+    const float* qrow = qb + (size_t)(ok ? w.qi : 0) * p.q_ts;
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (ok) v = *reinterpret_cast<const f32x4*>(qrow + 8 * g + 4 * h);
+      if (ok) v = *reinterpret_cast<const f32x4*>(qrow + 8 * g + 4 * w.h);
       qf[g] = v * p.scale;
     }
   }
 
   f32x4 kr[2], vr[2];
-  auto load_kv = [&](int tile) {
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int idx = tid + 256 * l;            // 512 float4 per 32x64 tile
-      const int row = idx >> 4, c4 = idx & 15;
-      const int key = k_lo + tile * 32 + row;
-      f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
-      if (key < p.Sk) {
-        a = *reinterpret_cast<const f32x4*>(kb + (size_t)key * p.k_ts + c4 * 4);
-        c = *reinterpret_cast<const f32x4*>(vb + (size_t)key * p.v_ts + c4 * 4);
-      }
-      kr[l] = a;
-      vr[l] = c;
-    }
-  };
+  auto store_k = [&](int buf, int row, int c4, f32x4 a) { *reinterpret_cast<f32x4*>(&Ks[buf][row * KROW + c4 * 4]) = a; };
   auto store_kv = [&](int buf) {
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
-      const int idx = tid + 256 * l;
+      const int idx = w.tid + 256 * l;
       const int row = idx >> 4, c4 = idx & 15;
-      *reinterpret_cast<f32x4*>(&Ks[buf][row * KROW + c4 * 4]) = kr[l];
+      store_k(buf, row, c4, kr[l]);
       *reinterpret_cast<f32x4*>(&Vs[buf][row * 64 + c4 * 4]) = vr[l];
     }
   };
 
-  f32x16 o[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.0f;
+  f32x16 o[2] = {};
   float m_run = NEG_BIG, l_run = 0.0f;
 
   extern __shared__ float rel_dyn[];
-  float* const tbl_row = rel_dyn + (wave * 32 + j) * REL_ROW;      // this lane's query
-  if (p.rel_key) {      // q . rel_key[r] for this workgroup's queries: the table's rows go through the K tile and the QK MFMAs
-    const int nrel = p.rel_left + p.rel_right + 1;
-    for (int rt = 0; rt * 32 < nrel; ++rt) {
-#pragma unroll
-      for (int l = 0; l < 2; ++l) {
-        const int idx = tid + 256 * l, row = idx >> 4, c4 = idx & 15, rr = rt * 32 + row;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (rr < nrel) a = *reinterpret_cast<const f32x4*>(p.rel_key + (size_t)rr * 64 + c4 * 4);
-        *reinterpret_cast<f32x4*>(&Ks[0][row * KROW + c4 * 4]) = a;
-      }
-      __syncthreads();
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks[0] + j * KROW + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[g][e], s, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tbl_row[rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = s[r];
-      __syncthreads();
-    }
-  }
+  float* const tbl_row = rel_dyn + (w.wave * 32 + w.j) * REL_ROW;      // this lane's query
+  if (p.rel_key)
+    build_rel_table(p, w, tbl_row, [&](int row, int c4, f32x4 a) { store_k(0, row, c4, a); }, [&] { return qk_f32(Ks[0], qf, w); });
 
-  if (ntiles > 0) {
-    load_kv(0);
+  if (keys.ntiles > 0) {
+    load_kv(p, kb, vb, keys.k_lo, w.tid, kr, vr);
     store_kv(0);
   }
   __syncthreads();
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const bool has_next = tile + 1 < ntiles;
-    if (has_next) load_kv(tile + 1);
-    const float* kt = Ks[tile & 1];
+  for (int tile = 0; tile < keys.ntiles; ++tile) {
+    const bool has_next = tile + 1 < keys.ntiles;
+    const int key0 = keys.k_lo + tile * 32;
+    if (has_next) load_kv(p, kb, vb, key0 + 32, w.tid, kr, vr);
     const float* vt = Vs[tile & 1];
-    const int key0 = k_lo + tile * 32;
     // wave-uniform skip: under the causal mask a tile entirely in this wave's future contributes nothing
-    const bool wave_active = !(p.causal && key0 > q0 + 31) && q0 < p.Sq;
+    const bool wave_active = !(p.causal && key0 > w.q0 + 31) && w.q0 < p.Sq;
     if (wave_active) {
-      // ---- S^T = K . Q^T ----
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-      for (int g = 0; g < 8; ++g) {
-        const f32x4 kf = *reinterpret_cast<const f32x4*>(kt + j * KROW + 8 * g + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[g][e], s, 0, 0, 0);
-      }
-      if (p.rel_key) add_rel_term(s, tbl_row, key0, q0, qi, h, p.rel_left, p.rel_right);
+      f32x16 s = qk_f32(Ks[tile & 1], qf, w);
+      if (p.rel_key) add_rel_term(s, tbl_row, key0, w, p.rel_left, p.rel_right);
       // ---- mask + online softmax (query = lane, keys = registers of both lane halves) ----
       float mx = NEG_BIG;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        const bool ok = key >= kstart && key < kend && (!p.causal || key <= qi);
-        s[r] = ok ? s[r] : NEG_BIG;
+        s[r] = keys.sees(acc_key(r, w.h, key0), w.qi, p.causal) ? s[r] : NEG_BIG;
         mx = fmaxf(mx, s[r]);
       }
       mx = xor32_max(mx);
@@ -203,11 +258,11 @@ __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const AttnArgs p) {
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-      // ---- O^T += V^T . P^T : k-step r uses key (r&3)+8(r>>2)+4h, exactly the row that register r of s holds ----
+      // ---- O^T += V^T . P^T : k-step r uses exactly the key row that register r of s holds ----
+      const float* vlane = vt + acc_key(0, w.h) * 64 + w.j;      // per-lane part apart: the rows of r stay immediate offsets of the reads
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int krow = (r & 3) + 8 * (r >> 2) + 4 * h;
-        const float* vrow = vt + krow * 64 + j;
+        const float* vrow = vlane + acc_key(r, 0) * 64;
 #pragma unroll
         for (int t = 0; t < 2; ++t) o[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vrow[t * 32], s[r], o[t], 0, 0, 0);
       }
@@ -215,26 +270,7 @@ __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const AttnArgs p) {
     if (has_next) store_kv((tile + 1) & 1);
     __syncthreads();
   }
-
-  // ---- normalise and store: O^T tiles (rows = d, cols = query) -> O[b][q][head*64 + d] through LDS ----
-  const float l_tot = xor32_sum(l_run);
-  const float inv_l = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
-  float* stage = smem + wave * (32 * 65);            // reuse the (now idle) K/V tiles as the transpose buffer
-  static_assert(4 * 32 * 65 <= 2 * 32 * KROW + 2 * 32 * 64, "output staging must fit in the K/V tiles");
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dd = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      stage[j * 65 + dd] = o[t][r] * inv_l;
-    }
-  __syncthreads();
-  float* ob = p.o + (size_t)b * p.o_bs + hd * 64;
-#pragma unroll
-  for (int it = 0; it < 32; ++it) {                  // one 256-byte output row per wave-instruction
-    const int qq = q0 + it;
-    if (qq < p.Sq) ob[(size_t)qq * p.o_ts + lane] = stage[it * 65 + lane];
-  }
+  write_output<false>(p, o, l_run, smem, w, b, hd);      // the (now idle) K/V tiles are the transpose buffer
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -257,20 +293,79 @@ constexpr int ABUF = 2 * 32 * KB16 + 2 * 32 * VB16;     // hi/lo K, hi/lo V of o
 
 __device__ __forceinline__ void split4(const f32x4 v, bf16x4& hi, bf16x4& lo) { split_bf16_x4(v, hi, lo); }
 
+// acc += (ah + al) . (bh + bl) without the lo * lo term, smallest products first
+__device__ __forceinline__ f32x16 mfma_x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 acc) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// S^T = K . Q^T from split-bf16 operands: 12 MFMAs over the four 16-d chunks.  k_hi(c) is the LDS address of this lane's ds_read_b128
+// fragment of chunk c in the K hi plane; the lo plane's fragment lies lo_off bytes behind it.
+template <class KHi>
+__device__ __forceinline__ f32x16 qk_bf16x3(const bf16x8 (&qh)[4], const bf16x8 (&ql)[4], int lo_off, KHi k_hi) {
+  f32x16 s = {};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const bf16x8 kh = *reinterpret_cast<const bf16x8*>(k_hi(c));
+    const bf16x8 kl = *reinterpret_cast<const bf16x8*>(k_hi(c) + lo_off);
+    s = mfma_x3(kh, kl, qh[c], ql[c], s);
+  }
+  return s;
+}
+
+// Online softmax of one tile in the log2 domain (query = lane): s becomes P, the running maximum / sum and the accumulators follow.
+// SCALE_IN_EXP: the scores are unscaled and sc = scale * log2 e rides in the exponent's fma; otherwise Q was pre-scaled by it.
+// zero_masked: the tile was masked with NEG_BIG and a query may have no visible key yet (exp2(NEG_BIG - NEG_BIG) = 1 must read 0).
+template <bool SCALE_IN_EXP>
+__device__ __forceinline__ void online_softmax_log2(f32x16& s, f32x16 (&o)[2], float& m_run, float& l_run, float sc, bool zero_masked) {
+  float mx = NEG_BIG;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
+  mx = xor32_max(mx);
+  const float m_new = fmaxf(m_run, SCALE_IN_EXP ? mx * sc : mx);
+  const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+  float psum = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    float pv = __builtin_amdgcn_exp2f(SCALE_IN_EXP ? fmaf(s[r], sc, -m_new) : s[r] - m_new);
+    if (zero_masked) pv = s[r] <= -1e29f ? 0.0f : pv;
+    s[r] = pv;
+    psum += pv;
+  }
+  l_run = l_run * alpha + psum;
+  // the running maximum moves in the first few tiles and then rarely: when no lane's maximum moved (alpha == 1 everywhere,
+  // wave-uniform test) the 32 accumulator rescales are skipped -- same bits, a ninth of the loop's VALU work less
+  if (__builtin_amdgcn_ballot_w64(m_new != m_run) != 0) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+  }
+  m_run = m_new;
+}
+
+// P^T operands of the PV product: registers 8 t2 .. 8 t2 + 7 of s are the k-slots of MFMA t2
+__device__ __forceinline__ void split_p(const f32x16& s, bf16x8 (&ph)[2], bf16x8 (&pl)[2]) {
+#pragma unroll
+  for (int t2 = 0; t2 < 2; ++t2) {
+    const f32x4 a = {s[8 * t2 + 0], s[8 * t2 + 1], s[8 * t2 + 2], s[8 * t2 + 3]};
+    const f32x4 c = {s[8 * t2 + 4], s[8 * t2 + 5], s[8 * t2 + 6], s[8 * t2 + 7]};
+    bf16x4 ah, al, ch, cl;
+    split4(a, ah, al);
+    split4(c, ch, cl);
+    ph[t2] = __builtin_shufflevector(ah, ch, 0, 1, 2, 3, 4, 5, 6, 7);
+    pl[t2] = __builtin_shufflevector(al, cl, 0, 1, 2, 3, 4, 5, 6, 7);
+  }
+}
+
 __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * ABUF];
+  static_assert(STAGE_FLOATS * 4 <= 2 * ABUF, "output staging must fit in the K/V tiles");
 
   const int qblk = blockIdx.x, hd = blockIdx.y, b = blockIdx.z;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int h = lane >> 5, j = lane & 31;
-  const int q0 = qblk * 128 + wave * 32;
-  const int qi = q0 + j;
-  const int kstart = p.kstart ? p.kstart[b] : 0;
-  const int kend = p.kend ? min(p.kend[b], p.Sk) : p.Sk;
-  int k_hi = kend;
-  if (p.causal) k_hi = min(k_hi, qblk * 128 + 128);
-  const int k_lo = kstart & ~31;
-  const int ntiles = k_hi > k_lo ? (k_hi - k_lo + 31) >> 5 : 0;
+  const WaveLane w = wave_lane(qblk);
+  const KeyRange keys = visible_keys(p, b, qblk);
 
   const float* qb = p.q + (size_t)b * p.q_bs + hd * 64;
   const float* kb = p.k + (size_t)b * p.k_bs + hd * 64;
@@ -279,15 +374,15 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
   // Q^T fragments (B operand): lane (query j, half h) holds Q[qi][16c + 8h + e], e = 0..7, for the four 16-d chunks c
   bf16x8 qh[4], ql[4];
   {
-    const bool ok = qi < p.Sq;
-    const float* qrow = qb + (size_t)(ok ? qi : 0) * p.q_ts;
+    const bool ok = w.qi < p.Sq;
+    const float* qrow = qb + (size_t)(ok ? w.qi : 0) * p.q_ts;
     const float sc = p.scale * 1.4426950408889634f;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f}, bq = a;
       if (ok) {
-        a = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * h);
-        bq = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * h + 4);
+        a = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * w.h);
+        bq = *reinterpret_cast<const f32x4*>(qrow + 16 * c + 8 * w.h + 4);
       }
       bf16x4 ah, al, bh, bl;
       split4(a * sc, ah, al);
@@ -298,153 +393,62 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
   }
 
   f32x4 kr[2], vr[2];
-  auto load_kv = [&](int tile) {
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-      const int idx = tid + 256 * l;
-      const int row = idx >> 4, c4 = idx & 15;
-      const int key = k_lo + tile * 32 + row;
-      f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = {0.f, 0.f, 0.f, 0.f};
-      if (key < p.Sk) {
-        a = *reinterpret_cast<const f32x4*>(kb + (size_t)key * p.k_ts + c4 * 4);
-        c = *reinterpret_cast<const f32x4*>(vb + (size_t)key * p.v_ts + c4 * 4);
-      }
-      kr[l] = a;
-      vr[l] = c;
-    }
+  auto store_k = [&](char* base, int row, int c4, f32x4 a) {
+    bf16x4 hi, lo;
+    split4(a, hi, lo);
+    *reinterpret_cast<bf16x4*>(base + row * KB16 + c4 * 8) = hi;
+    *reinterpret_cast<bf16x4*>(base + 32 * KB16 + row * KB16 + c4 * 8) = lo;
   };
   auto store_kv = [&](int buf) {
     char* base = smem + buf * ABUF;
 #pragma unroll
     for (int l = 0; l < 2; ++l) {
-      const int idx = tid + 256 * l;
+      const int idx = w.tid + 256 * l;
       const int row = idx >> 4, c4 = idx & 15;
+      store_k(base, row, c4, kr[l]);
       bf16x4 hi, lo;
-      split4(kr[l], hi, lo);
-      *reinterpret_cast<bf16x4*>(base + row * KB16 + c4 * 8) = hi;
-      *reinterpret_cast<bf16x4*>(base + 32 * KB16 + row * KB16 + c4 * 8) = lo;
       split4(vr[l], hi, lo);
       *reinterpret_cast<bf16x4*>(base + 64 * KB16 + row * VB16 + c4 * 8) = hi;
       *reinterpret_cast<bf16x4*>(base + 64 * KB16 + 32 * VB16 + row * VB16 + c4 * 8) = lo;
     }
   };
 
-  f32x16 o[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.0f;
+  f32x16 o[2] = {};
   float m_run = NEG_BIG, l_run = 0.0f;
 
   // byte offsets of this lane's operand reads inside a tile buffer
-  const int k_off = j * KB16 + 16 * h;                                  // + 32 * c per 16-d chunk (+ 32*KB16 for lo)
+  const int k_off = w.j * KB16 + 16 * w.h;                                  // + 32 * c per 16-d chunk (+ 32*KB16 for lo)
   // transposing V read: lane 4q+p of a 16-lane group addresses row (key) q, columns 4p..4p+3 of the group's 16 columns
-  const int v_off = 64 * KB16 + (4 * h + ((lane & 15) >> 2)) * VB16 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+  const int v_off = 64 * KB16 + (4 * w.h + ((w.lane & 15) >> 2)) * VB16 + (16 * ((w.lane >> 4) & 1) + 4 * (w.lane & 3)) * 2;
+  auto qk = [&](const char* tb) { return qk_bf16x3(qh, ql, 32 * KB16, [&](int c) { return tb + k_off + 32 * c; }); };
 
   extern __shared__ float rel_dyn[];
-  float* const tbl_row = rel_dyn + (wave * 32 + j) * REL_ROW;      // this lane's query
-  if (p.rel_key) {      // q . rel_key[r] for this workgroup's queries: the table's rows go through the K planes and the QK MFMAs
-    const int nrel = p.rel_left + p.rel_right + 1;
-    for (int rt = 0; rt * 32 < nrel; ++rt) {
-#pragma unroll
-      for (int l = 0; l < 2; ++l) {
-        const int idx = tid + 256 * l, row = idx >> 4, c4 = idx & 15, rr = rt * 32 + row;
-        f32x4 a = {0.f, 0.f, 0.f, 0.f};
-        if (rr < nrel) a = *reinterpret_cast<const f32x4*>(p.rel_key + (size_t)rr * 64 + c4 * 4);
-        bf16x4 hi, lo;
-        split4(a, hi, lo);
-        *reinterpret_cast<bf16x4*>(smem + row * KB16 + c4 * 8) = hi;
-        *reinterpret_cast<bf16x4*>(smem + 32 * KB16 + row * KB16 + c4 * 8) = lo;
-      }
-      __syncthreads();
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(smem + k_off + 32 * c);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(smem + 32 * KB16 + k_off + 32 * c);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[c], s, 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tbl_row[rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h] = s[r];
-      __syncthreads();
-    }
-  }
+  float* const tbl_row = rel_dyn + (w.wave * 32 + w.j) * REL_ROW;      // this lane's query
+  if (p.rel_key) build_rel_table(p, w, tbl_row, [&](int row, int c4, f32x4 a) { store_k(smem, row, c4, a); }, [&] { return qk(smem); });
 
-  if (ntiles > 0) {
-    load_kv(0);
+  if (keys.ntiles > 0) {
+    load_kv(p, kb, vb, keys.k_lo, w.tid, kr, vr);
     store_kv(0);
   }
   __syncthreads();
-  for (int tile = 0; tile < ntiles; ++tile) {
-    const bool has_next = tile + 1 < ntiles;
-    if (has_next) load_kv(tile + 1);
+  for (int tile = 0; tile < keys.ntiles; ++tile) {
+    const bool has_next = tile + 1 < keys.ntiles;
+    const int key0 = keys.k_lo + tile * 32;
+    if (has_next) load_kv(p, kb, vb, key0 + 32, w.tid, kr, vr);
     const char* tb = smem + (tile & 1) * ABUF;
-    const int key0 = k_lo + tile * 32;
-    const bool wave_active = !(p.causal && key0 > q0 + 31) && q0 < p.Sq;      // wave-uniform
+    const bool wave_active = !(p.causal && key0 > w.q0 + 31) && w.q0 < p.Sq;      // wave-uniform
     if (wave_active) {
-      // ---- S^T = K . Q^T ----
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(tb + k_off + 32 * c);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(tb + 32 * KB16 + k_off + 32 * c);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[c], s, 0, 0, 0);
-      }
-      if (p.rel_key) add_rel_term(s, tbl_row, key0, q0, qi, h, p.rel_left, p.rel_right);
-      // ---- mask (boundary tiles only: wave-uniform test) + online softmax in the log2 domain ----
-      const bool need_mask = key0 < kstart || key0 + 32 > kend || (p.causal && key0 + 31 > q0);
-      float mx = NEG_BIG;
+      f32x16 s = qk(tb);
+      if (p.rel_key) add_rel_term(s, tbl_row, key0, w, p.rel_left, p.rel_right);
+      // ---- mask (boundary tiles only: wave-uniform test) + online softmax ----
+      const bool need_mask = key0 < keys.kstart || key0 + 32 > keys.kend || (p.causal && key0 + 31 > w.q0);
       if (need_mask) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const bool ok = key >= kstart && key < kend && (!p.causal || key <= qi);
-          s[r] = ok ? s[r] : NEG_BIG;
-        }
+        for (int r = 0; r < 16; ++r) s[r] = keys.sees(acc_key(r, w.h, key0), w.qi, p.causal) ? s[r] : NEG_BIG;
       }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
-      mx = xor32_max(mx);
-      const float m_new = fmaxf(m_run, mx);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      float psum = 0.0f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        float pv = __builtin_amdgcn_exp2f(s[r] - m_new);
-        if (need_mask) pv = s[r] <= -1e29f ? 0.0f : pv;
-        s[r] = pv;
-        psum += pv;
-      }
-      l_run = l_run * alpha + psum;
-      // the running maximum moves in the first few tiles and then rarely: when no lane's maximum moved (alpha == 1 everywhere,
-      // wave-uniform test) the 32 accumulator rescales are skipped -- same bits, a ninth of the loop's VALU work less
-      if (__builtin_amdgcn_ballot_w64(m_new != m_run) != 0) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-      }
-      m_run = m_new;
-      // ---- P^T operands: registers 8 t2 .. 8 t2 + 7 are the k-slots of MFMA t2 ----
+      online_softmax_log2<false>(s, o, m_run, l_run, 0.0f, need_mask);
       bf16x8 ph[2], pl[2];
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        const f32x4 a = {s[8 * t2 + 0], s[8 * t2 + 1], s[8 * t2 + 2], s[8 * t2 + 3]};
-        const f32x4 c = {s[8 * t2 + 4], s[8 * t2 + 5], s[8 * t2 + 6], s[8 * t2 + 7]};
-        bf16x4 ah, al, ch, cl;
-        split4(a, ah, al);
-        split4(c, ch, cl);
-        ph[t2] = __builtin_shufflevector(ah, ch, 0, 1, 2, 3, 4, 5, 6, 7);
-        pl[t2] = __builtin_shufflevector(al, cl, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
+      split_p(s, ph, pl);
       // ---- O^T += V^T . P^T ----
 #pragma unroll
       for (int t2 = 0; t2 < 2; ++t2)
@@ -458,44 +462,13 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
           const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 40 * VB16));
           const bf16x8 vh = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
           const bf16x8 vl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph[t2], o[t], 0, 0, 0);
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl[t2], o[t], 0, 0, 0);
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph[t2], o[t], 0, 0, 0);
+          o[t] = mfma_x3(vh, vl, ph[t2], pl[t2], o[t]);
         }
     }
     if (has_next) store_kv((tile + 1) & 1);
     __syncthreads();
   }
-
-  const float l_tot = xor32_sum(l_run);
-  const float inv_l = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
-  float* stage = reinterpret_cast<float*>(smem) + wave * (32 * 65);
-  static_assert(4 * 32 * 65 * 4 <= 2 * ABUF, "output staging must fit in the K/V tiles");
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dd = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      stage[j * 65 + dd] = o[t][r] * inv_l;
-    }
-  __syncthreads();
-  float* ob = p.o ? p.o + (size_t)b * p.o_bs + hd * 64 : nullptr;
-  __bf16* const o_hi = static_cast<__bf16*>(p.o_planes);
-  __bf16* const o_lo = o_hi ? o_hi + plane_elems(p.B * p.Sq, p.H * 64) : nullptr;
-#pragma unroll
-  for (int it = 0; it < 32; ++it) {
-    const int qq = q0 + it;
-    if (qq < p.Sq) {
-      const float val = stage[it * 65 + lane];
-      if (ob) ob[(size_t)qq * p.o_ts + lane] = val;
-      if (o_hi) {
-        const __bf16 hi = (__bf16)val;
-        const size_t o = plane_index(b * p.Sq + qq, hd * 64 + lane, p.B * p.Sq);
-        o_hi[o] = hi;
-        o_lo[o] = (__bf16)(val - (float)hi);
-      }
-    }
-  }
+  write_output<true>(p, o, l_run, reinterpret_cast<float*>(smem), w, b, hd);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -511,23 +484,12 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
 #define ATT_GLDS16(gptr, lptr) \
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr), (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
-// Diagnostic build only (-DATT_TIMING; never in the product library, tests/test_abi.py checks the exported symbols): per-tile
-// s_memtime stamps and a per-workgroup (start, end, XCC | HW_ID, loop cycles) record read back by tools/attn_trace.py.
-// -DDBG_PAD=bytes pads the LDS allocation to lower the occupancy (2 workgroups per CU at 16 KiB, 1 at 40 KiB) for the same study.
-#ifdef ATT_TIMING
-__device__ long long att_trace[4 * 4096];
-extern "C" int idxtts_debug_att_trace(long long* out, int n) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(att_trace), sizeof(long long) * n);
-}
-#endif
 constexpr int ATT_SLOT = 16 * 1024;       // 16 pieces of 1 KiB: [K hi, K lo, V hi, V lo] x 4 chunks
 constexpr int ATT_NSLOT = 3;
-#ifndef DBG_PAD
-#define DBG_PAD 0
-#endif
 
 __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanesArgs p) {
-  __shared__ __attribute__((aligned(1024))) char smem[ATT_NSLOT * ATT_SLOT + DBG_PAD];
+  __shared__ __attribute__((aligned(1024))) char smem[ATT_NSLOT * ATT_SLOT];
+  static_assert(STAGE_FLOATS * 4 <= ATT_NSLOT * ATT_SLOT, "output staging must fit in the ring");
 
   // XCD-aware walk: consecutive workgroup ids go to the 8 XCDs round-robin, each with its own L2.  All query blocks of one
   // (batch row, head) pair read the same K / V planes, so they are given to ONE XCD: pair = 8 * (id / 8 / nq) + id % 8.
@@ -535,15 +497,10 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
   const int qx = L >> 3, pair = (qx / nq) * 8 + (L & 7), qblk = qx % nq;
   if (pair >= p.B * p.H) return;      // whole workgroup (uniform)
   const int b = pair / p.H, hd = pair - b * p.H;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int h = lane >> 5, j = lane & 31;
-  const int q0 = qblk * 128 + wave * 32;
-  const int qi = q0 + j;
+  const WaveLane w = wave_lane(qblk);
+  const int lane = w.lane, h = w.h, j = w.j;
   const int kend = p.kend ? min(p.kend[b], p.T) : p.T;
   const int ntiles = (kend + 31) >> 5;
-#ifdef ATT_TIMING
-  const long long r_kernel = __builtin_amdgcn_s_memrealtime();
-#endif
   const __bf16* const hi = static_cast<const __bf16*>(p.planes);
   const __bf16* const lo = hi + plane_elems(p.Mrows, p.ncols);
   const size_t rows16 = (size_t)p.Mrows * 16;
@@ -551,7 +508,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
   // Q^T fragments (B operand): lane (query j, half h) holds Q[qi][16c + 8h + e], e = 0..7
   bf16x8 qh[4], ql[4];
   {
-    const size_t qrow = (size_t)b * p.T + p.q_row0 + min(qi, p.Sq - 1);
+    const size_t qrow = (size_t)b * p.T + p.q_row0 + min(w.qi, p.Sq - 1);
     const size_t base = (size_t)((p.q_col >> 4) + hd * 4) * rows16 + qrow * 16 + 8 * h;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -570,7 +527,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
   // and odd chunks differ in the row permutation only) -- the per-tile address arithmetic is six vector instructions.
   const int lrow = lane >> 1;
   const unsigned half_b = (unsigned)(((lane & 1) ^ ((lrow >> 3) & 1)) * 16);
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+  const int wave_s = __builtin_amdgcn_readfirstlane(w.wave);
   const char* const src0 = reinterpret_cast<const char*>(((wave_s & 1) ? lo : hi) + (size_t)(((wave_s < 2 ? p.k_col : p.v_col) >> 4) + hd * 4) * rows16);
   const size_t chunk_bytes = rows16 * sizeof(__bf16);
   const unsigned row_e = (unsigned)(b * p.T + lrow), row_o = (unsigned)(b * p.T + (lrow ^ 4));
@@ -584,11 +541,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
     for (int c = 0; c < 4; ++c) ATT_GLDS16(src0 + c * chunk_bytes + ((c & 1) ? off_o : off_e), dst + c * 1024);
   };
 
-  f32x16 o[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[t][r] = 0.0f;
+  f32x16 o[2] = {};
   float m_run = NEG_BIG, l_run = 0.0f;
   const float sc = p.scale * 1.4426950408889634f;
 
@@ -602,14 +555,6 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
   const int v_off_a = 2 * 4096 + g1 * 1024 + vL * 32 + ((vp >> 1) << 4) + ((vp & 1) << 3);            // keys 16 t2 + [0, 8): L & 8 == 0
   const int v_off_b = 2 * 4096 + g1 * 1024 + (vL + 8) * 32 + (((vp >> 1) ^ 1) << 4) + ((vp & 1) << 3);   // keys 16 t2 + [8, 16)
 
-#ifdef ATT_TIMING
-  long long tacc[5] = {0, 0, 0, 0, 0};
-#define ATT_T(i) { const long long tn = __builtin_readcyclecounter(); tacc[i] += tn - tprev; tprev = tn; }
-  long long tprev = __builtin_readcyclecounter();
-  const long long t_begin = tprev, r_begin = __builtin_amdgcn_s_memrealtime();
-#else
-#define ATT_T(i)
-#endif
   const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   if (ntiles > 0) issue_tile(0);
   if (ntiles > 1) issue_tile(1);
@@ -620,80 +565,33 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    ATT_T(0)
     if (tile + 2 < ntiles) issue_tile(tile + 2);
-    ATT_T(1)
     const char* tb = smem + (tile % ATT_NSLOT) * ATT_SLOT;
     const unsigned slot_lds = smem_lds + (tile % ATT_NSLOT) * ATT_SLOT;
     const int key0 = tile * 32;
-    if (q0 < p.Sq) {      // wave-uniform
-      // ---- S^T = K . Q^T ----
-      f32x16 s;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[r] = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int ko = (c & 1) ? k_off1 : k_off0;
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(tb + c * 1024 + ko);
-        const bf16x8 kl = *reinterpret_cast<const bf16x8*>(tb + 4096 + c * 1024 + ko);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kl, qh[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, ql[c], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kh, qh[c], s, 0, 0, 0);
-      }
-      ATT_T(2)
+    if (w.q0 < p.Sq) {      // wave-uniform
+      // K chunk c: pieces c (hi) and 4 + c (lo) of the slot
+      f32x16 s = qk_bf16x3(qh, ql, 4096, [&](int c) { return tb + c * 1024 + ((c & 1) ? k_off1 : k_off0); });
       // V fragments: requested now, behind the QK MFMAs, so that they have landed by the time the softmax is through.
-        const unsigned va = slot_lds + v_off_a, vb = slot_lds + v_off_b;
-        bf16x4 vf[2][2][4];      // [t2][t][hi a, hi b, lo a, lo b]
+      const unsigned va = slot_lds + v_off_a, vb = slot_lds + v_off_b;
+      bf16x4 vf[2][2][4];      // [t2][t][hi a, hi b, lo a, lo b]
 #define ATT_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define ATT_TR4(t2, t)                                       \
-        ATT_TR(vf[t2][t][0], va, 512 * t2 + 2048 * t);        \
-        ATT_TR(vf[t2][t][1], vb, 512 * t2 + 2048 * t);        \
-        ATT_TR(vf[t2][t][2], va, 512 * t2 + 2048 * t + 4096); \
-        ATT_TR(vf[t2][t][3], vb, 512 * t2 + 2048 * t + 4096);
-        ATT_TR4(0, 0) ATT_TR4(0, 1) ATT_TR4(1, 0) ATT_TR4(1, 1)
+#define ATT_TR4(t2, t)                                     \
+      ATT_TR(vf[t2][t][0], va, 512 * t2 + 2048 * t);        \
+      ATT_TR(vf[t2][t][1], vb, 512 * t2 + 2048 * t);        \
+      ATT_TR(vf[t2][t][2], va, 512 * t2 + 2048 * t + 4096); \
+      ATT_TR(vf[t2][t][3], vb, 512 * t2 + 2048 * t + 4096);
+      ATT_TR4(0, 0) ATT_TR4(0, 1) ATT_TR4(1, 0) ATT_TR4(1, 1)
 #undef ATT_TR4
 #undef ATT_TR
-      // ---- mask (last tile only) + online softmax in the log2 domain, scale folded into the exponent ----
+      // ---- mask (last tile only) + online softmax, scale folded into the exponent (masked: s = -1e30 -> p = 0) ----
       if (key0 + 32 > kend) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          s[r] = key < kend ? s[r] : NEG_BIG;
-        }
+        for (int r = 0; r < 16; ++r) s[r] = acc_key(r, h, key0) < kend ? s[r] : NEG_BIG;
       }
-      float mx = NEG_BIG;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[r]);
-      mx = xor32_max(mx);
-      const float m_new = fmaxf(m_run, mx * sc);
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-      float psum = 0.0f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float pv = __builtin_amdgcn_exp2f(fmaf(s[r], sc, -m_new));      // masked: s = -1e30 -> 0
-        s[r] = pv;
-        psum += pv;
-      }
-      l_run = l_run * alpha + psum;
-      if (__builtin_amdgcn_ballot_w64(m_new != m_run) != 0) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
-      }
-      m_run = m_new;
+      online_softmax_log2<true>(s, o, m_run, l_run, sc, false);
       bf16x8 ph[2], pl[2];
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-        const f32x4 a = {s[8 * t2 + 0], s[8 * t2 + 1], s[8 * t2 + 2], s[8 * t2 + 3]};
-        const f32x4 c = {s[8 * t2 + 4], s[8 * t2 + 5], s[8 * t2 + 6], s[8 * t2 + 7]};
-        bf16x4 ah, al, ch, cl;
-        split4(a, ah, al);
-        split4(c, ch, cl);
-        ph[t2] = __builtin_shufflevector(ah, ch, 0, 1, 2, 3, 4, 5, 6, 7);
-        pl[t2] = __builtin_shufflevector(al, cl, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
-      ATT_T(3)
+      split_p(s, ph, pl);
       // ---- O^T += V^T . P^T ----
       // The transposing reads are issued by hand: the compiler models the ds_read_tr intrinsic as an LDS access that may collide with
       // the LDS-DMA writes in flight and drains vmcnt(0) before it -- the tile just requested would be waited for in every iteration.
@@ -703,9 +601,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
         {                                                                                          \
           const bf16x8 vh = __builtin_shufflevector(vf[t2][t][0], vf[t2][t][1], 0, 1, 2, 3, 4, 5, 6, 7); \
           const bf16x8 vl = __builtin_shufflevector(vf[t2][t][2], vf[t2][t][3], 0, 1, 2, 3, 4, 5, 6, 7); \
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vl, ph[t2], o[t], 0, 0, 0);                \
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, pl[t2], o[t], 0, 0, 0);                \
-          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vh, ph[t2], o[t], 0, 0, 0);                \
+          o[t] = mfma_x3(vh, vl, ph[t2], pl[t2], o[t]);                                             \
         }
 #define ATT_WAIT4(n, t2, t) \
         asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(vf[t2][t][0]), "+v"(vf[t2][t][1]), "+v"(vf[t2][t][2]), "+v"(vf[t2][t][3])::"memory")
@@ -716,60 +612,12 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
 #undef ATT_WAIT4
 #undef ATT_PV
       }
-      ATT_T(4)
     }
   }
-#ifdef ATT_TIMING
-  const long long r_loop_end = __builtin_amdgcn_s_memrealtime();
-  long long tsave[5] = {tacc[0], tacc[1], tacc[2], tacc[3], tacc[4]};
-  const long long t_loop = (long long)__builtin_readcyclecounter() - t_begin;
-#endif
 
-  const float l_tot = xor32_sum(l_run);
-  const float inv_l = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();                                            // every wave is done with the ring: reuse it as the transpose buffer
-  float* stage = reinterpret_cast<float*>(smem) + wave * (32 * 65);
-  static_assert(4 * 32 * 65 * 4 <= ATT_NSLOT * ATT_SLOT, "output staging must fit in the ring");
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int dd = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-      stage[j * 65 + dd] = o[t][r] * inv_l;
-    }
-  __syncthreads();
-  float* ob = p.o ? p.o + (size_t)b * p.o_bs + hd * 64 : nullptr;
-  __bf16* const o_hi = static_cast<__bf16*>(p.o_planes);
-  __bf16* const o_lo = o_hi ? o_hi + plane_elems(p.B * p.Sq, p.H * 64) : nullptr;
-#pragma unroll
-  for (int it = 0; it < 32; ++it) {
-    const int qq = q0 + it;
-    if (qq < p.Sq) {
-      const float val = stage[it * 65 + lane];
-      if (ob) ob[(size_t)qq * p.o_ts + lane] = val;
-      if (o_hi) {
-        const __bf16 vhi = (__bf16)val;
-        const size_t oo = plane_index(b * p.Sq + qq, hd * 64 + lane, p.B * p.Sq);
-        o_hi[oo] = vhi;
-        o_lo[oo] = (__bf16)(val - (float)vhi);
-      }
-    }
-  }
-#ifdef ATT_TIMING
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const long long r_end = __builtin_amdgcn_s_memrealtime();
-  if (tid == 0) {
-    const int wg = blockIdx.x;
-    unsigned hwid, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    if (wg < 4096) {
-      att_trace[4 * wg] = r_kernel; att_trace[4 * wg + 1] = r_end; att_trace[4 * wg + 2] = ((long long)xcc << 32) | hwid;
-      att_trace[4 * wg + 3] = t_loop + tsave[0] * 0;
-    }
-  }
-#endif
+  write_output<true>(p, o, l_run, reinterpret_cast<float*>(smem), w, b, hd);
 }
 
 int flash_attn_planes_forward(const AttnPlanesArgs& a, hipStream_t stream) {

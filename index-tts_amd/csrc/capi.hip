@@ -260,15 +260,24 @@ int idxtts_linear_destroy(idxtts_linear* lin) {
   return 0;
 }
 
-int idxtts_attention_fwd(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
-                         long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
-                         int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream) {
-  API_BEGIN
+// what the attention entry points share: pointers, strides, shape and mask of one call (each adds its own mode)
+static AttnArgs attn_args(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
+                          long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
+                          int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale) {
   AttnArgs a;
   a.q = q; a.k = k; a.v = v; a.o = o;
   a.q_bs = q_batch_stride; a.k_bs = a.v_bs = kv_batch_stride; a.o_bs = o_batch_stride;
   a.q_ts = q_token_stride; a.k_ts = a.v_ts = kv_token_stride; a.o_ts = o_token_stride;
   a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.causal = causal; a.kstart = kstart; a.kend = kend; a.scale = scale;
+  return a;
+}
+
+int idxtts_attention_fwd(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
+                         long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
+                         int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream) {
+  API_BEGIN
+  const AttnArgs a = attn_args(q, k, v, o, q_batch_stride, q_token_stride, kv_batch_stride, kv_token_stride, o_batch_stride,
+                               o_token_stride, B, H, Sq, Sk, causal, kstart, kend, scale);
   return flash_attn_forward(a, static_cast<hipStream_t>(stream));
   API_END
 }
@@ -278,11 +287,8 @@ int idxtts_attention_relkey_fwd(const float* q, const float* k, const float* v, 
                                 const float* rel_key, int rel_left, int rel_right, int split_bf16, void* stream) {
   API_BEGIN
   IDX_CHECK(rel_key, "rel_key is null");
-  AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.o = o;
-  a.q_bs = a.k_bs = a.v_bs = batch_stride; a.o_bs = o_batch_stride;
-  a.q_ts = a.k_ts = a.v_ts = token_stride; a.o_ts = o_token_stride;
-  a.B = B; a.H = H; a.Sq = S; a.Sk = S; a.causal = 0; a.kend = kend; a.scale = scale;
+  AttnArgs a = attn_args(q, k, v, o, batch_stride, token_stride, batch_stride, token_stride, o_batch_stride, o_token_stride, B, H, S, S,
+                         0, nullptr, kend, scale);
   a.rel_key = rel_key; a.rel_left = rel_left; a.rel_right = rel_right; a.split_bf16 = split_bf16 ? 1 : 0;
   return flash_attn_forward(a, static_cast<hipStream_t>(stream));
   API_END
@@ -292,11 +298,9 @@ int idxtts_attention_bf16x3_fwd(const float* q, const float* k, const float* v, 
                          long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
                          int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream) {
   API_BEGIN
-  AttnArgs a;
-  a.q = q; a.k = k; a.v = v; a.o = o;
-  a.q_bs = q_batch_stride; a.k_bs = a.v_bs = kv_batch_stride; a.o_bs = o_batch_stride;
-  a.q_ts = q_token_stride; a.k_ts = a.v_ts = kv_token_stride; a.o_ts = o_token_stride;
-  a.B = B; a.H = H; a.Sq = Sq; a.Sk = Sk; a.causal = causal; a.kstart = kstart; a.kend = kend; a.scale = scale; a.split_bf16 = 1;
+  AttnArgs a = attn_args(q, k, v, o, q_batch_stride, q_token_stride, kv_batch_stride, kv_token_stride, o_batch_stride, o_token_stride,
+                         B, H, Sq, Sk, causal, kstart, kend, scale);
+  a.split_bf16 = 1;
   return flash_attn_forward(a, static_cast<hipStream_t>(stream));
   API_END
 }

@@ -102,7 +102,9 @@ def test_gemm_swiglu_and_silu(device):
 
 
 @pytest.mark.parametrize("cfg", [(2, 2, 37, True, True), (1, 4, 165, True, False), (3, 2, 300, False, True), (2, 8, 129, False, False),
-                                 (1, 2, 1, True, False), (1, 1, 700, True, True)])
+                                 (1, 2, 1, True, False), (1, 1, 700, True, True),
+                                 (1, 2, 128, False, False),      # one full query block, no tile masked: the split-bf16 unmasked path on every tile
+                                 (1, 2, 256, True, False)])      # causal, exactly two full query blocks
 def test_attention_vs_torch(device, cfg):
     B, H, S, causal, ragged = cfg
     d = H * 64
