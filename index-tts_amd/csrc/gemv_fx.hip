@@ -19,12 +19,6 @@
 //   * the K-slices of the 16 waves of a workgroup are reduced through LDS in a fixed order; bias / colsum / residual
 //     operands of the epilogue are fetched at kernel entry.
 #include <algorithm>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include <atomic>
 
 #include "device_util.h"
@@ -32,145 +26,6 @@
 #include "prof.h"
 
 namespace idxtts {
-
-// ---- host-side packing: B-fragment order of v_mfma_f32_16x16x4_f32, [N/16][K/16][lane][4], k = 4*(lane>>4)+s, n = lane&15 ----
-void pack_gemv16_kn(float* dst, const float* w_kn, int K, int N) {
-  const int NT = cdiv(N, 16), KC = cdiv(K, 16);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c) {
-      float* sub = dst + ((size_t)nt * KC + c) * 256;
-      for (int lane = 0; lane < 64; ++lane)
-        for (int s = 0; s < 4; ++s) {
-          const int k = c * 16 + 4 * (lane >> 4) + s, n = nt * 16 + (lane & 15);
-          sub[lane * 4 + s] = (k < K && n < N) ? w_kn[(size_t)k * N + n] : 0.0f;
-        }
-    }
-}
-
-void pack_gemv16_nk(float* dst, const float* w_nk, int N, int K) {
-  const int NT = cdiv(N, 16), KC = cdiv(K, 16);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c) {
-      float* sub = dst + ((size_t)nt * KC + c) * 256;
-      for (int lane = 0; lane < 64; ++lane)
-        for (int s = 0; s < 4; ++s) {
-          const int k = c * 16 + 4 * (lane >> 4) + s, n = nt * 16 + (lane & 15);
-          sub[lane * 4 + s] = (k < K && n < N) ? w_nk[(size_t)n * K + k] : 0.0f;
-        }
-    }
-}
-
-// ---- compact weight formats (gemv16.h) ----
-float fp8_e4m3_decode(unsigned char code) {
-  const int e = (code >> 3) & 15, m = code & 7;
-  float v;
-  if (e == 15 && m == 7) v = NAN;
-  else if (e == 0) v = ldexpf((float)m, -9);                 // m/8 * 2^-6
-  else v = ldexpf(8.0f + (float)m, e - 10);                  // (1 + m/8) * 2^(e-7)
-  return (code & 0x80) ? -v : v;
-}
-
-unsigned char fp8_e4m3_encode(float v) {
-  const unsigned char sign = std::signbit(v) ? 0x80 : 0;
-  const float a = std::fabs(v);
-  if (!(a < 448.0f)) return sign | 126;                      // saturate (NaN too: quantize_matrix never feeds one)
-  if (a < 0.015625f) return sign | (unsigned char)nearbyintf(a * 512.0f);   // subnormal grid 2^-9 (8 -> the smallest normal)
-  uint32_t u; memcpy(&u, &a, 4);
-  u += 0x7ffffu + ((u >> 20) & 1u);                          // nearest-even on the 3 kept mantissa bits
-  const int c = (int)(u >> 20) - ((127 - 7) << 3);
-  return sign | (unsigned char)std::min(c, 126);
-}
-
-float bf16_round(float v) {
-  uint32_t u; memcpy(&u, &v, 4);
-  if ((u & 0x7f800000u) == 0x7f800000u) return v;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  u &= 0xffff0000u;
-  float r; memcpy(&r, &u, 4);
-  return r;
-}
-
-float fp8_column_scale(float maxabs) {
-  if (!(maxabs > 0.0f)) return 1.0f;
-  int e; const float f = frexpf(maxabs / 448.0f, &e);        // maxabs/448 = f * 2^e, f in [0.5, 1)
-  if (f == 0.5f) e -= 1;
-  return ldexpf(1.0f, std::max(-100, std::min(100, e)));
-}
-
-void quantize_matrix(float* w, int K, int N, bool kn, int fmt) {
-  if (fmt == WFMT_F32) return;
-  auto at = [&](int k, int n) -> float& { return kn ? w[(size_t)k * N + n] : w[(size_t)n * K + k]; };
-  if (fmt == WFMT_BF16) {
-    for (size_t i = 0; i < (size_t)K * N; ++i) w[i] = bf16_round(w[i]);
-    return;
-  }
-  std::vector<float> mx(N, 0.0f);
-  for (int k = 0; k < K; ++k)
-    for (int n = 0; n < N; ++n) mx[n] = std::max(mx[n], std::fabs(at(k, n)));
-  for (int n = 0; n < N; ++n) mx[n] = fp8_column_scale(mx[n]);
-  for (int k = 0; k < K; ++k)
-    for (int n = 0; n < N; ++n) { float& v = at(k, n); v = mx[n] * fp8_e4m3_decode(fp8_e4m3_encode(v / mx[n])); }
-}
-
-int compact_gemv16(void* dst, const float* pk, int N, int K, int fmt, float* scale_out) {
-  const int NT = cdiv(N, 16), KC = cdiv(K, 16);
-  const size_t total = (size_t)NT * KC * 256;
-  if (fmt == WFMT_BF16) {
-    uint16_t* o = static_cast<uint16_t*>(dst);
-    for (size_t i = 0; i < total; ++i) {
-      uint32_t u; memcpy(&u, &pk[i], 4);
-      if (u & 0xffffu) return 1;
-      o[i] = (uint16_t)(u >> 16);
-    }
-    return 0;
-  }
-  if (fmt != WFMT_FP8) return 1;
-  std::vector<float> mx(NT * 16, 0.0f);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c) {
-      const float* sub = pk + ((size_t)nt * KC + c) * 256;
-      for (int i = 0; i < 256; ++i) { float& m = mx[nt * 16 + ((i >> 2) & 15)]; m = std::max(m, std::fabs(sub[i])); }
-    }
-  for (int n = 0; n < NT * 16; ++n) { mx[n] = fp8_column_scale(mx[n]); if (n < N) scale_out[n] = mx[n]; }
-  unsigned char* o = static_cast<unsigned char*>(dst);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c) {
-      const size_t base = ((size_t)nt * KC + c) * 256;
-      for (int i = 0; i < 256; ++i) {
-        const float s = mx[nt * 16 + ((i >> 2) & 15)], v = pk[base + i];
-        const unsigned char q = fp8_e4m3_encode(v / s);
-        if (s * fp8_e4m3_decode(q) != v) return 1;
-        o[base + i] = q;
-      }
-    }
-  return 0;
-}
-
-__global__ void fp8_decode_table_kernel(float* out) {
-  const int c = threadIdx.x;      // 256 codes
-  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(c, false);
-  out[c] = lo[0];
-}
-
-int fp8_check_device_decode(hipStream_t stream) {
-  static bool ok = false;
-  if (ok) return 0;
-  float* d = nullptr;
-  IDX_HIP(hipMalloc(&d, 256 * sizeof(float)));
-  hipLaunchKernelGGL(fp8_decode_table_kernel, dim3(1), dim3(256), 0, stream, d);
-  float h[256];
-  hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void)hipFree(d);
-  IDX_HIP(e);
-  for (int c = 0; c < 256; ++c) {
-    const float want = fp8_e4m3_decode((unsigned char)c);
-    if (std::isnan(want)) continue;
-    if (!(h[c] == want)) IDX_FAIL("this device's fp8 conversion is not OCP e4m3fn (code " + std::to_string(c) + ")");
-  }
-  ok = true;
-  return 0;
-}
 
 // Ablation masks of tools/gemv_probe.hip (built with -DGEMV_PROBE); the product build compiles every probe branch out.
 #ifdef GEMV_PROBE
@@ -189,9 +44,9 @@ struct GemvFXP {
   const float* res;         // residual, same layout as y, may alias y
   float* y; int y_frag; int ldy;   // y_frag: fragment images with kc16 = N/16 (N % 16 == 0), else row-major [rows][ldy]
   int rows, N, K, kc16, ntiles, kw, cps, act;
-  int ksb;                  // > 1: K also split across gridDim.y workgroups; y = raw partial sums [ksb][rows][N] (row-major)
-  float* slab;              // fused K-split: partial sums [ksb][rows][N]; the last workgroup of a column tile finishes the job
-  unsigned* cnt;            // [gridDim.x] arrival counters (0 on entry and on exit); null = unfused
+  int ksb;                  // > 1: K also split across gridDim.y workgroups
+  float* slab;              // K-split: partial sums [ksb][rows][N]; the last workgroup of a column tile finishes the job
+  unsigned* cnt;            // K-split: [gridDim.x] arrival counters (0 on entry and on exit); null with ksb == 1
   int dbg;
 };
 
@@ -268,6 +123,8 @@ __global__ __launch_bounds__(UNS == 10 ? 512 : 1024) void gemv_fx_kernel(const G
   if (e_ok) {
     if (WT == WFMT_FP8) e_s = p.wscale[e_col];
     e_addr = p.y_frag ? frag_index(e_row, e_col, p.N >> 4) : (size_t)e_row * p.ldy + e_col;
+    // (never taken: the launcher sets cnt whenever ksb > 1.  The select stays because register allocation and instruction order of
+    // every instantiation change without it, which this kernel's measured figures do not cover.)
     if (p.ksb > 1 && !p.cnt) e_addr = ((size_t)blockIdx.y * p.rows + e_row) * p.N + e_col;
     if (p.bias) e_bias = p.bias[e_col];
     if (ln) e_u = p.colsum[e_col];
@@ -462,139 +319,110 @@ __global__ __launch_bounds__(UNS == 10 ? 512 : 1024) void gemv_fx_kernel(const G
   }
 }
 
+
+// ---- host side ----
 // Narrow layers (N = d: 80 column tiles) with a long K (mlp.c_proj: 26 MB) cannot reach HBM speed from 80 workgroups:
 // a CU sustains ~11 B/clk from HBM (tools/l2_probe.hip), so all 256 have to stream.  Their K is split across `ksb`
-// workgroups per column tile; the partial sums go to a [ksb][rows][N] slab and gemv_fx_combine adds them in a fixed order
-// (bitwise reproducible) together with bias and residual.
+// workgroups per column tile; the partial sums go to a [ksb][rows][N] slab and the last workgroup of a column tile to arrive
+// adds them in a fixed order (bitwise reproducible) together with bias and residual.
 int gemv_fx_ksb(int N, int K) {
   const int ntiles = cdiv(N, 16), kc16 = cdiv(K, 16);
   return (ntiles <= 128 && kc16 >= 64) ? 4 : 1;
-}
-
-__global__ __launch_bounds__(256) void gemv_fx_combine_kernel(const float* __restrict__ slab, int ksb, int rows, int N, const float* __restrict__ bias,
-                                                              const float* res, float* y) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows * N) return;
-  const int row = idx / N, col = idx - row * N;
-  float t[8];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) t[s] = s < ksb ? slab[((size_t)s * rows + row) * N + col] : 0.f;
-  const size_t o = frag_index(row, col, N >> 4);
-  float v = res ? res[o] : 0.f;
-  if (bias) v += bias[col];
-#pragma unroll
-  for (int s = 0; s < 8; ++s) v += t[s];
-  y[o] = v;
-}
-
-// y (fragment images over N) = res + bias + sum_s slab[s]
-int gemv_fx_combine(const float* slab, int ksb, int rows, int N, const float* bias, const float* res, float* y, hipStream_t stream) {
-  IDX_CHECK(slab && y && ksb >= 1 && ksb <= 8 && N % 16 == 0, "combine arguments");
-  static const int cat = prof_register("gemv_fx_combine_kernel");
-  ProfScope prof(cat, stream, 0.0, 4.0 * rows * (double)N * (ksb + 2));
-  hipLaunchKernelGGL(gemv_fx_combine_kernel, dim3(cdiv(rows * N, 256)), dim3(256), 0, stream, slab, ksb, rows, N, bias, res, y);
-  IDX_LAUNCH_CHECK();
-  return 0;
 }
 
 // Process-wide geometry of the 5..16-row decode GEMVs on compact weight streams (include/idxtts.h::idxtts_set_decode_geometry).
 static std::atomic<int> g_decode_narrow{0};
 void set_decode_geometry(int narrow) { g_decode_narrow.store(narrow ? 1 : 0); }
 int get_decode_geometry() { return g_decode_narrow.load(); }
-static bool gemv_fx_narrow() { return g_decode_narrow.load() != 0; }
 
-static void gemv_fx_plan_geom(int N, int K, int rows, bool narrow_geom, int* ntw, int* kw) {
-  const int kc16 = cdiv(K, 16), ntiles = cdiv(N, 16), MT = cdiv(rows, 16);
-  int k = 16;
-  while (k > 1 && kc16 < k) k >>= 1;
-  *kw = k;
-  if (narrow_geom && MT == 1 && rows > 4 && kc16 % 80 == 0) { *kw = 8; *ntw = 1; return; }
-  // Two column tiles per wave (one activation fragment feeds both) exactly when that turns a two-round launch into one
-  // round of <= 256 workgroups (c_fc: 320 tiles); measured per shape in profiles/r01_gemv_probe.txt
-  *ntw = (MT <= 2 && ntiles > 256 && cdiv(ntiles, 2) <= 256) ? 2 : 1;
+FxPlan gemv_fx_make_plan(int N, int K, int rows, int fmt, int ksb, bool narrow_geom) {
+  const int kc16 = cdiv(K, 16), ntiles = cdiv(N, 16);
+  FxPlan pl;
+  pl.MT = cdiv(rows, 16);
+  pl.r4 = rows <= 4;
+  // The narrow geometry: 5..16 rows on a compact stream whose K gives each of 8 waves exactly 10 chunks (d = 1280, and 4 d split
+  // over 4 workgroups); fp32 streams and every other shape keep the 16-wave form.
+  pl.narrow = narrow_geom && pl.MT == 1 && rows > 4 && fmt != WFMT_F32 && kc16 % 80 == 0 && cdiv(kc16, 8 * ksb) == 10;
+  if (pl.narrow) {
+    pl.kw = 8; pl.ntw = 1;
+  } else {
+    pl.kw = 16;
+    while (pl.kw > 1 && kc16 < pl.kw) pl.kw >>= 1;
+    // Two column tiles per wave (one activation fragment feeds both) exactly when that turns a two-round launch into one
+    // round of <= 256 workgroups (c_fc: 320 tiles); measured per shape in profiles/r01_gemv_probe.txt
+    pl.ntw = (pl.MT <= 2 && ntiles > 256 && cdiv(ntiles, 2) <= 256) ? 2 : 1;
+  }
+  pl.cps = cdiv(kc16, pl.kw * ksb);
+  // 17..48 rows (coalesced decodes, 16 utterances x 3 beams): the one-batch form as well -- all five chunks of a wave's K-slice in
+  // flight at once (10 + 20 MT VGPRs of operands: one workgroup per CU); the two-buffer form with 1-2 chunks per batch measured
+  // 14.6 / 16.5 us per launch at 32 / 48 rows against 7.8 at 16 (profiles/README.md "Round 3").  49..64 rows have the two-buffer form only.
+  pl.single = pl.narrow || (pl.cps <= 5 && pl.MT <= 3);
+  if (pl.MT == 2 && !pl.single) pl.ntw = 1;      // two column tiles per wave at 17..32 rows exist in the one-batch form only
+  const int nacc = pl.MT * pl.ntw;
+  pl.threads = std::max(64 * pl.kw, 256 * nacc);      // one epilogue thread per output element of the workgroup
+  pl.lds = (size_t)(pl.kw * nacc * 256 + pl.kw * pl.MT * 32 + pl.MT * 32) * sizeof(float);
+  pl.grid_x = cdiv(ntiles, pl.ntw); pl.grid_y = ksb;
+  return pl;
 }
 
-void gemv_fx_plan(int N, int K, int rows, int* ntw, int* kw) { gemv_fx_plan_geom(N, K, rows, gemv_fx_narrow(), ntw, kw); }
+template <int MT, int NTW, bool SINGLE, int WT, bool R4, int UNS = 5>
+static int fx_launch(const GemvFXP& p, const FxPlan& pl, hipStream_t stream) {
+  static DynLdsLimit lds_limit;
+  IDX_HIP(lds_limit.set(128 * 1024, gemv_fx_kernel<MT, NTW, SINGLE, WT, R4, UNS>));
+  hipLaunchKernelGGL((gemv_fx_kernel<MT, NTW, SINGLE, WT, R4, UNS>), dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), pl.lds, stream, p);
+  return 0;
+}
 
-int gemv_fx_forward(const Gemv16Weights& w, const GemvFXArgs& a, hipStream_t stream) {
-  const bool narrow_geom = gemv_fx_narrow();      // the process-wide switch, read ONCE per launch (a setter racing with a launch cannot tear the plan)
+template <int WT, bool R4>
+static int fx_launch_mt1(const GemvFXP& p, const FxPlan& pl, hipStream_t stream) {
+  if (pl.ntw == 2) return pl.single ? fx_launch<1, 2, true, WT, R4>(p, pl, stream) : fx_launch<1, 2, false, WT, R4>(p, pl, stream);
+  return pl.single ? fx_launch<1, 1, true, WT, R4>(p, pl, stream) : fx_launch<1, 1, false, WT, R4>(p, pl, stream);
+}
+
+template <int WT>
+static int fx_launch_wt(const GemvFXP& p, const FxPlan& pl, hipStream_t stream) {
+  if (pl.narrow) {
+    if constexpr (WT == WFMT_F32) IDX_FAIL("gemv_fx: the narrow form reads compact streams");
+    else return fx_launch<1, 1, true, WT, false, 10>(p, pl, stream);
+  }
+  switch (pl.MT) {
+    case 1: return pl.r4 ? fx_launch_mt1<WT, true>(p, pl, stream) : fx_launch_mt1<WT, false>(p, pl, stream);
+    case 2:
+      if (pl.ntw == 2) return fx_launch<2, 2, true, WT, false>(p, pl, stream);
+      return pl.single ? fx_launch<2, 1, true, WT, false>(p, pl, stream) : fx_launch<2, 1, false, WT, false>(p, pl, stream);
+    case 3: return pl.single ? fx_launch<3, 1, true, WT, false>(p, pl, stream) : fx_launch<3, 1, false, WT, false>(p, pl, stream);
+    case 4: return fx_launch<4, 1, false, WT, false>(p, pl, stream);
+  }
+  IDX_FAIL("gemv_fx: no kernel for this plan");
+}
+
+int gemv_fx_forward(const WeightStream& w, const GemvFXArgs& a, hipStream_t stream) {
+  const bool narrow_geom = g_decode_narrow.load() != 0;      // the process-wide switch, read ONCE per launch (a setter racing with a launch cannot tear the plan)
   IDX_CHECK(w.wp && a.xf && a.y, "null pointer");
+  IDX_CHECK(w.kdepth == 16, "weight stream of 16 k per chunk");
   IDX_CHECK(a.rows > 0 && a.rows <= 64, "1..64 rows");
   IDX_CHECK((reinterpret_cast<uintptr_t>(a.xf) & 15) == 0, "x alignment");
   if (a.colsum) IDX_CHECK(w.K % 16 == 0, "folded LayerNorm needs K % 16 == 0");
   if (a.y_frag) IDX_CHECK(w.N % 16 == 0, "fragment-image output needs N % 16 == 0");
-  GemvFXP p;
   IDX_CHECK(w.fmt == WFMT_F32 || w.fmt == WFMT_BF16 || (w.fmt == WFMT_FP8 && w.wscale), "weight format");
+  const int ksb = (a.slab && a.ksb_counters) ? gemv_fx_ksb(w.N, w.K) : 1;
+  if (ksb > 1) IDX_CHECK(!a.colsum && a.act == 0 && ksb <= 8, "K split across workgroups: no folded LayerNorm, no activation, <= 8 pieces");
+  const FxPlan pl = gemv_fx_make_plan(w.N, w.K, a.rows, w.fmt, ksb, narrow_geom);
+  IDX_CHECK(pl.threads <= 1024, "workgroup size");
+  GemvFXP p;
   p.xf = a.xf; p.wp = w.wp; p.wscale = w.wscale; p.bias = a.bias; p.colsum = a.colsum; p.ln_eps = a.ln_eps;
   p.res = a.res; p.y = a.y; p.y_frag = a.y_frag; p.ldy = a.ldy;
   p.rows = a.rows; p.N = w.N; p.K = w.K; p.kc16 = cdiv(w.K, 16); p.ntiles = cdiv(w.N, 16);
-  int ntw = 1;
-  gemv_fx_plan_geom(w.N, w.K, a.rows, narrow_geom, &ntw, &p.kw);
-  p.ksb = a.ksb > 1 ? a.ksb : 1;
-  p.slab = a.slab; p.cnt = p.ksb > 1 ? a.ksb_counters : nullptr;
-  if (p.ksb > 1 && !p.cnt) IDX_CHECK(!a.colsum && !a.bias && !a.res && a.act == 0 && !a.y_frag, "a K-split launch writes raw partial sums");
-  if (p.cnt) IDX_CHECK(a.slab && !a.colsum && a.act == 0 && p.ksb <= 8, "fused K-split: slab, no folded LayerNorm, no activation, <= 8 pieces");
-  p.cps = cdiv(p.kc16, p.kw * p.ksb);
-  p.act = a.act; p.dbg = a.dbg;
-  const int MT = cdiv(a.rows, 16);
-  const bool narrow = p.kw == 8 && p.cps == 10 && MT == 1 && a.rows > 4 && w.fmt != WFMT_F32 && narrow_geom;
-  if (p.kw == 8 && !narrow && narrow_geom && MT == 1 && a.rows > 4 && cdiv(w.K, 16) % 80 == 0) {      // fp32 streams: the 16-wave form
-    p.kw = 16; p.cps = cdiv(p.kc16, p.kw * p.ksb);
-    ntw = (p.ntiles > 256 && cdiv(p.ntiles, 2) <= 256) ? 2 : 1;
-  }
-  const bool single = p.cps <= 5;
-  if (MT == 2 && !single) ntw = 1;      // two column tiles per wave at 17..32 rows exist in the one-batch form only
-  const int nacc = MT * ntw;
-  const int threads = std::max(64 * p.kw, 256 * nacc);      // one epilogue thread per output element of the workgroup
-  IDX_CHECK(threads <= 1024, "workgroup size");
-  const size_t lds = (size_t)(p.kw * nacc * 256 + p.kw * MT * 32 + MT * 32) * sizeof(float);
-  dim3 grid(cdiv(p.ntiles, ntw), p.ksb);
+  p.kw = pl.kw; p.cps = pl.cps; p.act = a.act;
+  p.ksb = ksb; p.slab = a.slab; p.cnt = ksb > 1 ? a.ksb_counters : nullptr;
+  p.dbg = a.dbg;
   const double flops = 2.0 * a.rows * (double)w.N * w.K;
   const double bytes = (double)wfmt_bytes(w.fmt) * w.N * w.K + 4.0 * ((double)a.rows * w.N * (a.res ? 2.0 : 1.0) + (double)a.rows * w.K);
   static const int cat = prof_register("gemv_fx_kernel");
   ProfScope prof(cat, stream, flops, bytes);
-#define LAUNCH_R(MTV, NTWV, SG, WTV, R4V)                                                                                 \
-  {                                                                                                                       \
-    static DynLdsLimit lds_limit;                                                                                         \
-    IDX_HIP(lds_limit.set(128 * 1024, gemv_fx_kernel<MTV, NTWV, SG, WTV, R4V>));                                          \
-    hipLaunchKernelGGL((gemv_fx_kernel<MTV, NTWV, SG, WTV, R4V>), grid, dim3(threads), lds, stream, p);                   \
-  }
-#define LAUNCH_N(WTV)                                                                                                     \
-  {                                                                                                                       \
-    static DynLdsLimit lds_limit;                                                                                         \
-    IDX_HIP(lds_limit.set(128 * 1024, gemv_fx_kernel<1, 1, true, WTV, false, 10>));                                       \
-    hipLaunchKernelGGL((gemv_fx_kernel<1, 1, true, WTV, false, 10>), grid, dim3(threads), lds, stream, p);                \
-  }
-#define LAUNCH_W(MTV, NTWV, SG, WTV)                                                                                      \
-  {                                                                                                                       \
-    if (MTV == 1 && r4) LAUNCH_R(1, NTWV, SG, WTV, true)                                                                  \
-    else LAUNCH_R(MTV, NTWV, SG, WTV, false)                                                                              \
-  }
-#define LAUNCH(MTV, NTWV, SG)                                                                                             \
-  {                                                                                                                       \
-    if (w.fmt == WFMT_FP8) LAUNCH_W(MTV, NTWV, SG, WFMT_FP8)                                                              \
-    else if (w.fmt == WFMT_BF16) LAUNCH_W(MTV, NTWV, SG, WFMT_BF16)                                                       \
-    else LAUNCH_W(MTV, NTWV, SG, WFMT_F32)                                                                                \
-  }
-  const bool r4 = a.rows <= 4;
-  if (narrow) {
-    if (w.fmt == WFMT_FP8) { LAUNCH_N(WFMT_FP8) } else { LAUNCH_N(WFMT_BF16) }
-  } else
-  if (MT == 1 && ntw == 2 && single) LAUNCH(1, 2, true)
-  else if (MT == 1 && ntw == 2) LAUNCH(1, 2, false)
-  else if (MT == 1 && single) LAUNCH(1, 1, true)
-  else if (MT == 1) LAUNCH(1, 1, false)
-  // 17..48 rows (coalesced decodes, 16 utterances x 3 beams): the one-batch form as well -- all five chunks of a wave's K-slice in
-  // flight at once (10 + 20 MT VGPRs of operands: one workgroup per CU); the two-buffer form with 1-2 chunks per batch measured
-  // 14.6 / 16.5 us per launch at 32 / 48 rows against 7.8 at 16 (profiles/README.md "Round 3")
-  else if (MT == 2 && ntw == 2 && single) LAUNCH(2, 2, true)
-  else if (MT == 2 && single) LAUNCH(2, 1, true)
-  else if (MT == 3 && single) LAUNCH(3, 1, true)
-  else if (MT == 2) LAUNCH(2, 1, false) else if (MT == 3) LAUNCH(3, 1, false) else LAUNCH(4, 1, false)
-#undef LAUNCH_N
-#undef LAUNCH_R
-#undef LAUNCH_W
-#undef LAUNCH
+  const int rc = w.fmt == WFMT_FP8 ? fx_launch_wt<WFMT_FP8>(p, pl, stream)
+               : w.fmt == WFMT_BF16 ? fx_launch_wt<WFMT_BF16>(p, pl, stream) : fx_launch_wt<WFMT_F32>(p, pl, stream);
+  if (rc) return rc;
   IDX_LAUNCH_CHECK();
   return 0;
 }

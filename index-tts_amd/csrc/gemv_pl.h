@@ -1,5 +1,5 @@
 #pragma once
-#include "gemv16.h"
+#include "wstream.h"
 
 namespace idxtts {
 
@@ -12,21 +12,10 @@ namespace idxtts {
 // for the cost of one 16-row launch: the weight stream is read once for all of them.
 //
 // Layouts:
-//   weights      [N/16][K/32][64 lanes][8] bf16: B fragments of v_mfma_f32_16x16x32_bf16, lane l holds k = 32 c + 8 (l >> 4) + j, n = 16 t + (l & 15)
-//                (fp8: the same order, one byte per weight + [N] power-of-two column scales)
+//   weights      a bf16 or fp8 stream of kdepth 32 (wstream.h): [N/16][K/32][64 lanes][8], B fragments of v_mfma_f32_16x16x32_bf16, lane l
+//                holds k = 32 c + 8 (l >> 4) + j, n = 16 t + (l & 15) (fp8: one byte per weight + [N] power-of-two column scales)
 //   activations  fp32 rows [rows][ldx] in HBM (4 bytes per element past the L2, not 6): a workgroup splits the K part it needs into the
 //                three planes ONCE, on the way into LDS (A-fragment order: lane l holds row 16 mt + (l & 15), k = 32 c + 8 (l >> 4) + j)
-struct Gemv32Weights {
-  const void* wp = nullptr;
-  const float* wscale = nullptr;    // WFMT_FP8: [N] power-of-two column scales
-  int fmt = WFMT_BF16;
-  int N = 0, K = 0;
-};
-static inline size_t gemv32_packed_elems(int N, int K) { return (size_t)cdiv(N, 16) * cdiv(K, 32) * 512; }
-// Pack an already-quantised matrix (every value representable in `fmt`) given as [K][N] (kn) or [N][K]; fp8 also returns the per-column
-// scales.  Returns 1 if a value is not representable.
-int pack_gemv32(void* dst, const float* w, int N, int K, bool kn, int fmt, float* scale_out);
-
 struct GemvPLArgs {
   const float* x = nullptr; int ldx = 0; int rows = 0;  // activations, fp32 rows (16-byte aligned, ldx % 4 == 0)
   const float* bias = nullptr;                          // [N]; folded layers: c = ln_b . W + bias
@@ -47,6 +36,6 @@ size_t gemv_pl_slab_floats(int N, int K, int rows);
 void set_decode_plane_rows(int min_rows);       // include/idxtts.h::idxtts_set_decode_plane_rows
 int get_decode_plane_rows();
 void gemv_pl_set_ct_override(int ct);      // measurement hook (tools/gemv_pl_probe.hip): 0 = the plan
-int gemv_pl_forward(const Gemv32Weights& w, const GemvPLArgs& a, hipStream_t stream);
+int gemv_pl_forward(const WeightStream& w, const GemvPLArgs& a, hipStream_t stream);
 
 }  // namespace idxtts

@@ -18,8 +18,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "gemv_pl.h"
 #include "prof.h"
@@ -28,44 +26,6 @@ namespace idxtts {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-int pack_gemv32(void* dst, const float* w, int N, int K, bool kn, int fmt, float* scale_out) {
-  const int NT = cdiv(N, 16), KC = cdiv(K, 32);
-  auto at = [&](int k, int n) -> float { return (k < K && n < N) ? (kn ? w[(size_t)k * N + n] : w[(size_t)n * K + k]) : 0.0f; };
-  if (fmt == WFMT_BF16) {
-    uint16_t* o = static_cast<uint16_t*>(dst);
-    for (int nt = 0; nt < NT; ++nt)
-      for (int c = 0; c < KC; ++c)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const float v = at(c * 32 + 8 * (lane >> 4) + j, nt * 16 + (lane & 15));
-            uint32_t u; memcpy(&u, &v, 4);
-            if (u & 0xffffu) return 1;
-            o[(((size_t)nt * KC + c) * 64 + lane) * 8 + j] = (uint16_t)(u >> 16);
-          }
-    return 0;
-  }
-  if (fmt != WFMT_FP8) return 1;
-  std::vector<float> sc(NT * 16, 1.0f);
-  for (int n = 0; n < N; ++n) {
-    float mx = 0.0f;
-    for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(at(k, n)));
-    sc[n] = fp8_column_scale(mx);
-    if (scale_out) scale_out[n] = sc[n];
-  }
-  unsigned char* o = static_cast<unsigned char*>(dst);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int c = 0; c < KC; ++c)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j) {
-          const int n = nt * 16 + (lane & 15);
-          const float v = at(c * 32 + 8 * (lane >> 4) + j, n);
-          const unsigned char q = fp8_e4m3_encode(v / sc[n]);
-          if (sc[n] * fp8_e4m3_decode(q) != v) return 1;
-          o[(((size_t)nt * KC + c) * 64 + lane) * 8 + j] = q;
-        }
-  return 0;
-}
 
 struct GemvPLP {
   const float* x; int ldx;       // [rows][ldx] fp32
@@ -493,8 +453,9 @@ static int pl_launch_ct(int ct, const GemvPLP& p, dim3 grid, hipStream_t stream)
   IDX_FAIL("gemv_pl: no kernel for this geometry");
 }
 
-int gemv_pl_forward(const Gemv32Weights& w, const GemvPLArgs& a, hipStream_t stream) {
+int gemv_pl_forward(const WeightStream& w, const GemvPLArgs& a, hipStream_t stream) {
   IDX_CHECK(w.wp && a.x && a.y, "null pointer");
+  IDX_CHECK(w.kdepth == 32, "weight stream of 32 k per chunk");
   IDX_CHECK(a.rows > 0 && a.rows <= 64, "1..64 rows");
   IDX_CHECK(w.fmt == WFMT_BF16 || (w.fmt == WFMT_FP8 && w.wscale), "weight format (bf16 / fp8 streams)");
   IDX_CHECK((reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (a.ldx & 3) == 0 && (w.K & 3) == 0 && a.ldx >= w.K && (reinterpret_cast<uintptr_t>(w.wp) & 15) == 0,

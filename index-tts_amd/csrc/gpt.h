@@ -30,8 +30,8 @@ BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new);
 struct GPTLayer {
   const float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
   LinearWeights attn_l, proj_l, fc_l, fc2_l;     // MFMA-32x32 packed (prefill / latent pass)
-  Gemv16Weights attn_g, proj_g, fc_g, fc2_g;     // stream-order packed (decode); attn_g / fc_g carry diag(ln_g) folded in
-  Gemv32Weights attn_p, proj_p, fc_p, fc2_p;     // compact formats only: the bf16-MFMA order of the plane GEMV (gemv_pl.h), 5..64 rows
+  WeightStream attn_g, proj_g, fc_g, fc2_g;      // stream-order packed (decode, kdepth 16); attn_g / fc_g carry diag(ln_g) folded in
+  WeightStream attn_p, proj_p, fc_p, fc2_p;      // compact formats only: kdepth 32, the bf16-MFMA order of the plane GEMV (gemv_pl.h), 5..64 rows
   const float *attn_u = nullptr, *attn_c = nullptr;   // folded LayerNorm 1: colsum(diag(g) W), b . W + bias
   const float *fc_u = nullptr, *fc_c = nullptr;       // folded LayerNorm 2
 };
@@ -50,8 +50,7 @@ struct GPTModel : ModelBase {
   idxtts_gpt_config cfg;
   std::vector<GPTLayer> layers;
   const float *lnf_g = nullptr, *lnf_b = nullptr, *fn_g = nullptr, *fn_b = nullptr;
-  Gemv16Weights head_g;
-  Gemv32Weights head_p;
+  WeightStream head_g, head_p;
   const float* head_b = nullptr;
   const float *mel_emb = nullptr, *text_emb = nullptr, *mel_pos = nullptr, *text_pos = nullptr;
   int weight_fmt = WFMT_F32;      // storage format of the decode weight streams (quantize_weights)
@@ -123,6 +122,8 @@ struct GPTModel : ModelBase {
   // the step is captured)
   int head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, int codes_ld, float* logits_out,
                       hipStream_t st);
+  DecodeAttnArgs attn_args(int li, const Buffers& w, int B, int pos_hint) const;      // layer li's decode attention; the caller sets out / out_row
+  SampleArgs::Embed tail_embed(const Buffers& w, bool pl) const;                      // the fused tail's next-input block (st_rw left to the caller)
   int decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
   int decode_step_pl(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
   int capture_step(const Buffers& w, int B, float penalty, int codes_ld, hipStream_t st, StepGraph* g);   // one decode step -> *g

@@ -35,60 +35,39 @@ bool GPTModel::accepts(const std::string& name) const {
   return false;
 }
 
-// HF Conv1D weight [K][N] -> both packed forms
-// ln_g / ln_b (host, [K]) non-null: the decode copy gets the LayerNorm in front of it folded in (gemv_fx.hip):
+// One decode weight stream: the matrix ([K][N] if kn, else [N][K]) packed at `kdepth` in the model's storage format (wstream.h) and
+// uploaded; the matrix holds values the format represents exactly
+static int upload_stream(DeviceArena& arena, const float* w, int N, int K, bool kn, int fmt, int kdepth, WeightStream* ws) {
+  ws->N = N; ws->K = K; ws->fmt = fmt; ws->kdepth = kdepth;
+  std::vector<unsigned char> buf(wstream_elems(N, K, kdepth) * wfmt_bytes(fmt));
+  std::vector<float> scale(N, 1.0f);
+  if (pack_wstream(buf.data(), w, N, K, kn, fmt, kdepth, scale.data())) IDX_FAIL("decode weights are not representable in the compact format (quantize_weights not applied?)");
+  void* d = nullptr;
+  if (arena.upload_bytes(buf.data(), buf.size(), &d)) return 1;
+  ws->wp = d;
+  if (fmt == WFMT_FP8) {
+    float* ds = nullptr;
+    if (arena.upload(scale.data(), scale.size(), &ds)) return 1;
+    ws->wscale = ds;
+  }
+  return 0;
+}
+
+// HF Conv1D weight [K][N] -> every packed form: the GEMM's, the decode stream (gw) and, where gp is given, the plane GEMV's stream
+// ln_g / ln_b (host, [K]) non-null: the decode copies get the LayerNorm in front of them folded in (gemv_fx.hip):
 //   W' = diag(g) W (packed), u = colsum(W'), c = b . W + bias
-// decode stream in the model's storage format (the fp32 pack `buf` holds values the format represents exactly)
-static int upload_stream(DeviceArena& arena, const std::vector<float>& buf, int N, int K, int fmt, Gemv16Weights* gw) {
-  gw->N = N; gw->K = K; gw->fmt = fmt;
-  if (fmt == WFMT_F32) {
-    float* d = nullptr;
-    if (arena.upload(buf.data(), buf.size(), &d)) return 1;
-    gw->wp = d;
-    return 0;
-  }
-  std::vector<unsigned char> cbuf(buf.size() * wfmt_bytes(fmt));
-  std::vector<float> scale(N, 1.0f);
-  if (compact_gemv16(cbuf.data(), buf.data(), N, K, fmt, scale.data())) IDX_FAIL("decode weights are not representable in the compact format (quantize_weights not applied?)");
-  void* d = nullptr;
-  if (arena.upload_bytes(cbuf.data(), cbuf.size(), &d)) return 1;
-  gw->wp = d;
-  if (fmt == WFMT_FP8) {
-    float* ds = nullptr;
-    if (arena.upload(scale.data(), scale.size(), &ds)) return 1;
-    gw->wscale = ds;
-  }
-  return 0;
-}
-
-// the same matrix in the plane GEMV's order (compact formats only; gemv_pl.h)
-static int upload_stream32(DeviceArena& arena, const float* w, int N, int K, bool kn, int fmt, Gemv32Weights* gp) {
-  gp->N = N; gp->K = K; gp->fmt = fmt;
-  if (fmt == WFMT_F32) return 0;
-  std::vector<unsigned char> cbuf(gemv32_packed_elems(N, K) * wfmt_bytes(fmt));
-  std::vector<float> scale(N, 1.0f);
-  if (pack_gemv32(cbuf.data(), w, N, K, kn, fmt, scale.data())) IDX_FAIL("decode weights are not representable in the compact format (quantize_weights not applied?)");
-  void* d = nullptr;
-  if (arena.upload_bytes(cbuf.data(), cbuf.size(), &d)) return 1;
-  gp->wp = d;
-  if (fmt == WFMT_FP8) {
-    float* ds = nullptr;
-    if (arena.upload(scale.data(), scale.size(), &ds)) return 1;
-    gp->wscale = ds;
-  }
-  return 0;
-}
-
 static int make_proj(std::map<std::string, HostTensor>& t, DeviceArena& arena, const std::string& prefix, int K, int N, int fmt,
-                     LinearWeights* lw, Gemv16Weights* gw, Gemv32Weights* gp, const HostTensor* ln_g = nullptr, const HostTensor* ln_b = nullptr,
+                     LinearWeights* lw, WeightStream* gw, WeightStream* gp, const HostTensor* ln_g = nullptr, const HostTensor* ln_b = nullptr,
                      const float** u_out = nullptr, const float** c_out = nullptr) {
   HostTensor *w = nullptr, *bias = nullptr;
   if (need(t, prefix + ".weight", {K, N}, &w) || need(t, prefix + ".bias", {N}, &bias)) return 1;
   // the split-bf16 copy is used by the latent pass only (the KV-cache-building prefill stays exact fp32)
   if (make_linear(arena, w->data.data(), bias->data.data(), N, K, {WP16_ALWAYS, W_KN}, lw)) return 1;
-  std::vector<float> buf(gemv16_packed_floats(N, K), 0.0f);
+  const float* wm = w->data.data();
+  std::vector<float> wf;
   if (ln_g) {
-    std::vector<float> wf((size_t)K * N), u(N), c(N);
+    wf.resize((size_t)K * N);
+    std::vector<float> u(N), c(N);
     std::vector<double> ud(N, 0.0), cd(N, 0.0);
     for (int k = 0; k < K; ++k) {
       const float g = ln_g->data[k];
@@ -102,16 +81,13 @@ static int make_proj(std::map<std::string, HostTensor>& t, DeviceArena& arena, c
       }
     }
     for (int n = 0; n < N; ++n) { u[n] = (float)ud[n]; c[n] = (float)(cd[n] + (double)bias->data[n]); }
-    pack_gemv16_kn(buf.data(), wf.data(), K, N);
     float *du = nullptr, *dc = nullptr;
     if (arena.upload(u.data(), u.size(), &du) || arena.upload(c.data(), c.size(), &dc)) return 1;
     *u_out = du; *c_out = dc;
-    if (gp && upload_stream32(arena, wf.data(), N, K, true, fmt, gp)) return 1;
-  } else {
-    pack_gemv16_kn(buf.data(), w->data.data(), K, N);
-    if (gp && upload_stream32(arena, w->data.data(), N, K, true, fmt, gp)) return 1;
+    wm = wf.data();
   }
-  return upload_stream(arena, buf, N, K, fmt, gw);
+  if (gp && upload_stream(arena, wm, N, K, true, fmt, 32, gp)) return 1;
+  return upload_stream(arena, wm, N, K, true, fmt, 16, gw);
 }
 
 int GPTModel::quantize_weights(std::map<std::string, HostTensor>& t, int fmt) {
@@ -174,7 +150,7 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
     HostTensor *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
     if (need(t, p + ".ln_1.weight", {d}, &g1) || need(t, p + ".ln_1.bias", {d}, &b1)) return 1;
     if (need(t, p + ".ln_2.weight", {d}, &g2) || need(t, p + ".ln_2.bias", {d}, &b2)) return 1;
-    Gemv32Weights* const no32 = nullptr;
+    WeightStream* const no32 = nullptr;
     const bool p32 = weight_fmt != WFMT_F32 && d % 32 == 0;
     if (make_proj(t, arena, p + ".attn.c_attn", d, 3 * d, weight_fmt, &L.attn_l, &L.attn_g, p32 ? &L.attn_p : no32, g1, b1, &L.attn_u, &L.attn_c)) return 1;
     if (make_proj(t, arena, p + ".attn.c_proj", d, d, weight_fmt, &L.proj_l, &L.proj_g, p32 ? &L.proj_p : no32)) return 1;
@@ -186,10 +162,8 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
   const int V = cfg.number_mel_codes;
   HostTensor* hw = nullptr;
   if (need(t, "mel_head.weight", {V, d}, &hw)) return 1;
-  std::vector<float> buf(gemv16_packed_floats(V, d));
-  pack_gemv16_nk(buf.data(), hw->data.data(), V, d);
-  if (upload_stream(arena, buf, V, d, weight_fmt, &head_g)) return 1;
-  if (weight_fmt != WFMT_F32 && d % 32 == 0 && upload_stream32(arena, hw->data.data(), V, d, false, weight_fmt, &head_p)) return 1;
+  if (upload_stream(arena, hw->data.data(), V, d, false, weight_fmt, 16, &head_g)) return 1;
+  if (weight_fmt != WFMT_F32 && d % 32 == 0 && upload_stream(arena, hw->data.data(), V, d, false, weight_fmt, 32, &head_p)) return 1;
   if (tensor_from(t, arena, "mel_head.bias", {V}, &head_b)) return 1;
   if (tensor_from(t, arena, "mel_embedding.weight", {V, d}, &mel_emb)) return 1;
   if (tensor_from(t, arena, "text_embedding.weight", {cfg.number_text_tokens + 1, d}, &text_emb)) return 1;
@@ -312,10 +286,18 @@ int GPTModel::head_logits(const Buffers& w, int B, const float* x, int ldx, bool
   return 0;
 }
 
+// where the fused tail writes the next step's input: the plane-GEMV step's fp32 row + statistics, or the fragment image
+SampleArgs::Embed GPTModel::tail_embed(const Buffers& w, bool pl) const {
+  SampleArgs::Embed e;
+  if (pl) { e.x_row = w.xrow; e.x_stats = w.stats; } else e.x_frag = w.xd;
+  e.mel_emb = mel_emb; e.mel_pos = mel_pos; e.d = cfg.model_dim;
+  return e;
+}
+
 // head on B rows -> the step tail w describes: greedy sampler, sampler, beam stages, or a session's per-slot samplers
 int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, int codes_ld,
                               float* logits_out, hipStream_t st) {
-  const int V = cfg.number_mel_codes, d = cfg.model_dim;
+  const int V = cfg.number_mel_codes;
   const bool pl = use_pl(B);
   if (head_logits(w, B, x, ldx, x_frag, st)) return 1;
   if (w.beam_tail) {      // the beam stages (beam.h); a beam session's work on every live group, its last one with the fused tail
@@ -329,14 +311,13 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
   s.st = w.state; s.B = B; s.V = V; s.stop_token = cfg.stop_mel_token; s.penalty = penalty;
   s.forced = w.forced; s.forced_ld = w.forced_ld;
   if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
-    if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
-    s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d;
+    s.embed = tail_embed(w, pl);
     if (w.slot_samp) return sample_slots_warp_forward(s, w.slots, w.slot_samp, nullptr, B, st);      // sampled session: each slot's own sampler
     return sample_slots_forward(s, w.slots, nullptr, B, st);
   }
   if (fused_tail(w)) {      // the sampler's workgroups also write the next step's input and advance the step scalars
-    if (pl) { s.embed.x_row = w.xrow; s.embed.x_stats = w.stats; } else s.embed.x_frag = w.xd;
-    s.embed.mel_emb = mel_emb; s.embed.mel_pos = mel_pos; s.embed.d = d; s.embed.st_rw = w.state;
+    s.embed = tail_embed(w, pl);
+    s.embed.st_rw = w.state;
   }
   if (w.samp.mode != 0) {
     const idxtts_sampling& r = w.samp;
@@ -361,9 +342,19 @@ bool GPTModel::fused_tail(const Buffers& w) const { return w.slots || (w.samp.mo
 // The decode step on the plane GEMV (gemv_pl.hip): the same five launches per layer, every activation a plain fp32 row-major matrix
 // (split into bf16 planes inside the GEMV), the residual stream updated in place, the LayerNorm statistics handed from producer to consumer; greedy generations close the
 // step with ONE launch (sample + next embedding + advance).
+DecodeAttnArgs GPTModel::attn_args(int li, const Buffers& w, int B, int pos_hint) const {
+  const size_t per_layer = kv_layer_bytes(B, w.Smax);
+  DecodeAttnArgs da;
+  da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
+  da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.kstart = w.kstart;
+  da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = cfg.model_dim; da.scale = 0.125f;
+  da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
+  da.pos_hint = pos_hint;
+  return da;
+}
+
 int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st) {
   const int d = cfg.model_dim, T = d / 16;
-  const size_t per_layer = kv_layer_bytes(B, w.Smax);
   const bool fused = fused_tail(w);
   if (!fused && embed_step_pl(w.xrow, w.stats, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
@@ -372,12 +363,8 @@ int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, int codes_l
     qa.x = w.xrow; qa.ldx = d; qa.rows = B; qa.colsum = L.attn_u; qa.bias = L.attn_c; qa.stats_in = w.stats; qa.stats_tiles = T;
     qa.y = w.qkvd; qa.ldy = 3 * d; qa.slab = w.pl_slab; qa.counters = w.pl_cnt;
     if (gemv_pl_forward(L.attn_p, qa, st)) return 1;
-    DecodeAttnArgs da;
-    da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
-    da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out_row = w.attrow; da.kstart = w.kstart;
-    da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
-    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
-    da.pos_hint = pos_hint;
+    DecodeAttnArgs da = attn_args(li, w, B, pos_hint);
+    da.out_row = w.attrow;
     if (decode_attn_forward(da, st)) return 1;
     GemvPLArgs pa;      // x += c_proj(attn) + b (in place: a lane reads and writes only its own elements of x), + the row statistics of the new x
     pa.x = w.attrow; pa.ldx = d; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xrow; pa.y = w.xrow; pa.ldy = d; pa.stats_out = w.stats;
@@ -399,7 +386,6 @@ int GPTModel::decode_step_pl(const Buffers& w, int B, float penalty, int codes_l
 int GPTModel::decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st) {
   if (use_pl(B)) return decode_step_pl(w, B, penalty, codes_ld, logits_base, pos_hint, st);
   const int d = cfg.model_dim;
-  const size_t per_layer = kv_layer_bytes(B, w.Smax);
   const bool fused = fused_tail(w);      // the previous step's tail has written this step's x and advanced the step scalars
   if (!fused && embed_step(w.xd, B, d, mel_emb, mel_pos, w.cur_tok, w.state, st)) return 1;
   for (int li = 0; li < cfg.layers; ++li) {
@@ -407,12 +393,8 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, int codes_ld, 
     GemvFXArgs qa;      // qkv = c_attn(LN1(x)) + b, row-major for the attention kernel
     qa.xf = w.xd; qa.rows = B; qa.colsum = L.attn_u; qa.bias = L.attn_c; qa.y = w.qkvd; qa.ldy = 3 * d;
     if (gemv_fx_forward(L.attn_g, qa, st)) return 1;
-    DecodeAttnArgs da;
-    da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
-    da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.out = w.attd; da.kstart = w.kstart;
-    da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = d; da.scale = 0.125f;
-    da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
-    da.pos_hint = pos_hint;
+    DecodeAttnArgs da = attn_args(li, w, B, pos_hint);
+    da.out = w.attd;
     if (decode_attn_forward(da, st)) return 1;
     GemvFXArgs pa;      // x += c_proj(attn) + b  (in place: a thread reads and writes only its own element of x)
     pa.xf = w.attd; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xd; pa.y = w.xd; pa.y_frag = 1;
@@ -420,18 +402,11 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, int codes_ld, 
     GemvFXArgs fa;      // ff = gelu_new(c_fc(LN2(x)) + b)
     fa.xf = w.xd; fa.rows = B; fa.colsum = L.fc_u; fa.bias = L.fc_c; fa.act = 1; fa.y = w.ffd; fa.y_frag = 1;
     if (gemv_fx_forward(L.fc_g, fa, st)) return 1;
-    GemvFXArgs fb;      // x += mlp.c_proj(ff) + b
-    fb.xf = w.ffd; fb.rows = B;
-    const int ksb = gemv_fx_ksb(L.fc2_g.N, L.fc2_g.K);
-    if (ksb > 1) {          // K split across workgroups (all 256 CUs stream); the partial sums are combined in a fixed order by the
-                            // last workgroup of each column tile to arrive (no combine launch)
-      fb.ksb = ksb; fb.slab = w.slab; fb.ksb_counters = w.ksb_cnt;
-      fb.bias = L.fc2_l.bias; fb.res = w.xd; fb.y = w.xd; fb.y_frag = 1;
-      if (gemv_fx_forward(L.fc2_g, fb, st)) return 1;
-    } else {
-      fb.bias = L.fc2_l.bias; fb.res = w.xd; fb.y = w.xd; fb.y_frag = 1;
-      if (gemv_fx_forward(L.fc2_g, fb, st)) return 1;
-    }
+    GemvFXArgs fb;      // x += mlp.c_proj(ff) + b; at full size K is also split across workgroups (gemv_fx_ksb: all 256 CUs stream), the
+                        // partial sums combined in a fixed order by the last workgroup of each column tile to arrive (no combine launch)
+    fb.xf = w.ffd; fb.rows = B; fb.bias = L.fc2_l.bias; fb.res = w.xd; fb.y = w.xd; fb.y_frag = 1;
+    fb.slab = w.slab; fb.ksb_counters = w.ksb_cnt;
+    if (gemv_fx_forward(L.fc2_g, fb, st)) return 1;
   }
   if (head_and_sample(w, B, w.xd, d, true, penalty, codes_ld, logits_base, st)) return 1;
   return fused ? 0 : advance_state(w.state, st);

@@ -1,7 +1,7 @@
 // Cold-weight timing of the plane GEMV (csrc/gemv_pl.hip) on the GPT's decode shapes, by row count and workgroup geometry.
 // Build on the GPU box:
-//   hipcc -O3 --offload-arch=gfx950 -DPL_STAMPS -Iindex-tts_amd/csrc tools/gemv_pl_probe.hip index-tts_amd/csrc/gemv_pl.hip index-tts_amd/csrc/gemv_fx.hip \
-//         index-tts_amd/csrc/prof.hip -o /tmp/gemv_pl_probe
+//   hipcc -O3 --offload-arch=gfx950 -DPL_STAMPS -Iindex-tts_amd/csrc tools/gemv_pl_probe.hip index-tts_amd/csrc/gemv_pl.hip index-tts_amd/csrc/prof.hip \
+//         -o /tmp/gemv_pl_probe
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -38,11 +38,11 @@ int main(int argc, char** argv) {
         int ctp, kp;
         gemv_pl_plan(sh.N, sh.K, rows, &ctp, &kp);
         if (ctp != ct) continue;      // not a valid geometry for this shape
-        const size_t wbytes = gemv32_packed_elems(sh.N, sh.K) * 2;
+        const size_t wbytes = wstream_elems(sh.N, sh.K, 32) * 2;
         size_t off = 0; const int reps = 40;
         for (int it = -3; it < reps; ++it) {
           if (it == 0) CK(hipEventRecord(e0, 0));
-          Gemv32Weights w; w.wp = pool + off; w.N = sh.N; w.K = sh.K; w.fmt = WFMT_BF16;
+          WeightStream w; w.wp = pool + off; w.N = sh.N; w.K = sh.K; w.fmt = WFMT_BF16; w.kdepth = 32;
           off += (wbytes + 255) & ~(size_t)255; if (off + wbytes > pool_bytes) off = 0;
           GemvPLArgs a; a.x = reinterpret_cast<float*>(xp); a.ldx = sh.K; a.rows = rows; a.bias = g; a.slab = slab; a.counters = cnt;
           if (sh.ln) { a.colsum = g; a.stats_in = stats; a.stats_tiles = sh.K / 16; }
@@ -63,7 +63,7 @@ int main(int argc, char** argv) {
           // [9] realtime at the arrival decision, [10] s_memtime / [11] realtime at the very end (last arrivers only)
           CK(hipMemset(stamps, 0, 4096 * 16 * 8));
           gemv_pl_set_stamps(stamps);
-          Gemv32Weights w; w.wp = pool + off; w.N = sh.N; w.K = sh.K; w.fmt = WFMT_BF16;
+          WeightStream w; w.wp = pool + off; w.N = sh.N; w.K = sh.K; w.fmt = WFMT_BF16; w.kdepth = 32;
           GemvPLArgs a; a.x = reinterpret_cast<float*>(xp); a.ldx = sh.K; a.rows = rows; a.bias = g; a.slab = slab; a.counters = cnt; a.y = y; a.ldy = sh.N;
           if (sh.ln) { a.colsum = g; a.stats_in = stats; a.stats_tiles = sh.K / 16; }
           if (sh.res) a.res = y;

@@ -10,12 +10,12 @@ namespace idxtts { int fail(const char* file, int line, const std::string& msg) 
 static int g_fmt = WFMT_F32;
 static int time_it(const char* tag, int N, int K, int rows, bool ln, bool res, int dbg, float* pool, size_t pool_floats,
                    float* x, float* y, float* g) {
-  const size_t wfl = gemv16_packed_floats(N, K);
+  const size_t wfl = wstream_elems(N, K, 16);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   size_t off = 0; const int reps = 48;
   for (int it = -3; it < reps; ++it) {
     if (it == 0) CK(hipEventRecord(e0, 0));
-    Gemv16Weights w; w.wp = pool + off; w.N = N; w.K = K; w.fmt = g_fmt; w.wscale = g;
+    WeightStream w; w.wp = pool + off; w.N = N; w.K = K; w.fmt = g_fmt; w.wscale = g; w.kdepth = 16;
     off += wfl; if (off + wfl > pool_floats) off = 0;
     GemvFXArgs a; a.xf = x; a.rows = rows; a.y = y; a.ldy = N; a.dbg = dbg; a.bias = g;
     if (ln) a.colsum = g;

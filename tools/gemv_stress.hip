@@ -18,7 +18,7 @@ int main(int argc, char** argv) {
   const int N = 3840, K = 1280, rows = 16;
   const int ln = argc > 1 ? atoi(argv[1]) : 1, C = argc > 2 ? atoi(argv[2]) : 768, T = argc > 3 ? atoi(argv[3]) : 3520, taps = argc > 4 ? atoi(argv[4]) : 3;
   const int gemv_dbg = argc > 5 ? atoi(argv[5]) : 0;
-  const size_t wfl = gemv16_packed_floats(N, K);
+  const size_t wfl = wstream_elems(N, K, 16);
   std::vector<float> hw(wfl), hx((size_t)64 * K), hg(N), hb(N);
   srand(1);
   for (auto& v : hw) v = (rand() / (float)RAND_MAX - 0.5f) * 0.1f;
@@ -42,7 +42,7 @@ int main(int argc, char** argv) {
   CK(hipMemset(cx, 0, (size_t)Bc * C * T * 4));
   ConvArgs ca; ca.x = cx; ca.y = cy; ca.B = Bc; ca.T = T; ca.dil = 1; ca.pad_left = (taps - 1) / 2;
   hipStream_t sa, sb; CK(hipStreamCreate(&sa)); CK(hipStreamCreate(&sb));
-  Gemv16Weights W; W.wp = w; W.N = N; W.K = K; W.fmt = WFMT_F32; W.wscale = nullptr;
+  WeightStream W; W.wp = w; W.N = N; W.K = K; W.fmt = WFMT_F32; W.kdepth = 16;
   GemvFXArgs a; a.xf = x; a.rows = rows; a.y = y; a.ldy = N; a.dbg = gemv_dbg; a.bias = b;
   if (ln) a.colsum = g;
   if (gemv_fx_forward(W, a, sa)) return 1;
