@@ -21,7 +21,7 @@ struct WNLayer {
   bool has_res = true;
 };
 
-struct CfmBuffers;
+struct CfmBuffers;      // the solver's workspace: s2mel_buffers.h (one table: carve_cfm lays it out, half_view splits it per CFG half)
 struct CondBuffers { float *a, *b, *s, *stats; int *idx_code, *idx_row, *idx_interp, *tlen; size_t bytes; };
 
 struct S2MelModel : ModelBase {
@@ -56,6 +56,9 @@ struct S2MelModel : ModelBase {
   int estimator(const float* x, const float* prompt, const int* prompt_lens_host, int Tp_max, const int* x_lens_host, const float* t_emb,
                 const float* style, const float* mu, float* out_tm, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
   size_t cond_workspace_bytes(int B, int M, int Tg) const;
+  // The Euler loop of cfm / cfm_rows.  One estimator evaluation (s2mel.hip: dit_eval) runs on at most two row sets (RowSet: all
+  // frames, and the tail behind tail_t0), each DiT block through one routine (dit_block); its set-up (upload_lens, step_constants,
+  // pack_args) is shared with estimator().
   int cfm_solve(CfmBuffers& w, const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host, int Tp_max,
                 const float* style, const float* z, const float* t_emb, const float* dt_host, int n_steps, float cfg_rate, int B, int T,
                 hipStream_t st);

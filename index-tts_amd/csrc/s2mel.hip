@@ -24,6 +24,7 @@
 
 #include "model_util.h"
 #include "s2mel.h"
+#include "s2mel_buffers.h"
 
 namespace idxtts {
 
@@ -76,6 +77,9 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     ffn = (nh % 256 == 0) ? nh : nh + 256 - (nh % 256);
   }
   const std::string e = "cfm.estimator";
+  // every linear of this stage: a split-bf16 pack for every shape, the LDS-DMA kernel on its 16x16x32 loop (model_util.h)
+  auto lin_from = [&](const std::string& key, int N, int K, bool bias, LinearWeights* out) { return linear_from(t, arena, key, N, K, bias, WP16_ALWAYS_MF16, out); };
+  auto mk_lin = [&](const float* w, const float* bias, int N, int K, LinearWeights* out) { return make_linear(arena, w, bias, N, K, {WP16_ALWAYS_MF16}, out); };
   blocks.resize(depth);
   std::vector<float> mod_w, mod_b;
   auto append_mod = [&](const std::string& name) -> int {
@@ -88,12 +92,12 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
   for (int i = 0; i < depth; ++i) {
     DiTBlock& B = blocks[i];
     const std::string p = e + ".transformer.layers." + std::to_string(i);
-    if (linear_from(t, arena, p + ".attention.wqkv", 3 * D, D, false, WP16_ALWAYS_MF16, &B.wqkv)) return 1;
-    if (linear_from(t, arena, p + ".attention.wo", D, D, false, WP16_ALWAYS_MF16, &B.wo)) return 1;
+    if (lin_from(p + ".attention.wqkv", 3 * D, D, false, &B.wqkv)) return 1;
+    if (lin_from(p + ".attention.wo", D, D, false, &B.wo)) return 1;
     HostTensor *w1 = nullptr, *w3 = nullptr;
     if (need(t, p + ".feed_forward.w1.weight", {ffn, D}, &w1) || need(t, p + ".feed_forward.w3.weight", {ffn, D}, &w3)) return 1;
-    if (make_linear(arena, pair_pack(w1->data.data(), w3->data.data(), ffn, D).data(), nullptr, 2 * ffn, D, {WP16_ALWAYS_MF16}, &B.w13)) return 1;
-    if (linear_from(t, arena, p + ".feed_forward.w2", D, ffn, false, WP16_ALWAYS_MF16, &B.w2)) return 1;
+    if (mk_lin(pair_pack(w1->data.data(), w3->data.data(), ffn, D).data(), nullptr, 2 * ffn, D, &B.w13)) return 1;
+    if (lin_from(p + ".feed_forward.w2", D, ffn, false, &B.w2)) return 1;
     HostTensor *g = nullptr;
     if (need(t, p + ".attention_norm.norm.weight", {D}, &g) || up(arena, g->data, &B.attn_g)) return 1;
     if (need(t, p + ".ffn_norm.norm.weight", {D}, &g) || up(arena, g->data, &B.ffn_g)) return 1;
@@ -101,35 +105,35 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     if (i > depth / 2) {
       HostTensor *sw = nullptr, *sb = nullptr;
       if (need(t, p + ".skip_in_linear.weight", {D, 2 * D}, &sw) || need(t, p + ".skip_in_linear.bias", {D}, &sb)) return 1;
-      if (make_linear(arena, col_slice(sw->data, D, 2 * D, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS_MF16}, &B.skip_a)) return 1;
-      if (make_linear(arena, col_slice(sw->data, D, 2 * D, D, 2 * D).data(), nullptr, D, D, {WP16_ALWAYS_MF16}, &B.skip_b)) return 1;
+      if (mk_lin(col_slice(sw->data, D, 2 * D, 0, D).data(), sb->data.data(), D, D, &B.skip_a)) return 1;
+      if (mk_lin(col_slice(sw->data, D, 2 * D, D, 2 * D).data(), nullptr, D, D, &B.skip_b)) return 1;
     }
   }
   {
     HostTensor* g = nullptr;
     if (need(t, e + ".transformer.norm.norm.weight", {D}, &g) || up(arena, g->data, &final_g)) return 1;
     if (append_mod(e + ".transformer.norm")) return 1;
-    if (make_linear(arena, mod_w.data(), mod_b.data(), (2 * depth + 1) * 2 * D, D, {WP16_ALWAYS_MF16}, &mod_all)) return 1;
+    if (mk_lin(mod_w.data(), mod_b.data(), (2 * depth + 1) * 2 * D, D, &mod_all)) return 1;
   }
   const int Win = 2 * C + D + cfg.style_dim;
-  if (linear_from(t, arena, e + ".cond_projection", D, cfg.content_dim, true, WP16_ALWAYS_MF16, &cond_proj)) return 1;
-  if (linear_from(t, arena, e + ".cond_x_merge_linear", D, Win, true, WP16_ALWAYS_MF16, &merge)) return 1;
-  if (linear_from(t, arena, e + ".t_embedder.mlp.0", D, 256, true, WP16_ALWAYS_MF16, &temb0) || linear_from(t, arena, e + ".t_embedder.mlp.2", D, D, true, WP16_ALWAYS_MF16, &temb2)) return 1;
-  if (linear_from(t, arena, e + ".t_embedder2.mlp.0", Wh, 256, true, WP16_ALWAYS_MF16, &t2emb0) || linear_from(t, arena, e + ".t_embedder2.mlp.2", Wh, Wh, true, WP16_ALWAYS_MF16, &t2emb2)) return 1;
+  if (lin_from(e + ".cond_projection", D, cfg.content_dim, true, &cond_proj)) return 1;
+  if (lin_from(e + ".cond_x_merge_linear", D, Win, true, &merge)) return 1;
+  if (lin_from(e + ".t_embedder.mlp.0", D, 256, true, &temb0) || lin_from(e + ".t_embedder.mlp.2", D, D, true, &temb2)) return 1;
+  if (lin_from(e + ".t_embedder2.mlp.0", Wh, 256, true, &t2emb0) || lin_from(e + ".t_embedder2.mlp.2", Wh, Wh, true, &t2emb2)) return 1;
   {
     HostTensor *sw = nullptr, *sb = nullptr;
     if (need(t, e + ".skip_linear.weight", {D, D + C}, &sw) || need(t, e + ".skip_linear.bias", {D}, &sb)) return 1;
-    if (make_linear(arena, col_slice(sw->data, D, D + C, 0, D).data(), sb->data.data(), D, D, {WP16_ALWAYS_MF16}, &skiplin_a)) return 1;
-    if (make_linear(arena, col_slice(sw->data, D, D + C, D, D + C).data(), nullptr, D, C, {WP16_ALWAYS_MF16}, &skiplin_b)) return 1;
+    if (mk_lin(col_slice(sw->data, D, D + C, 0, D).data(), sb->data.data(), D, D, &skiplin_a)) return 1;
+    if (mk_lin(col_slice(sw->data, D, D + C, D, D + C).data(), nullptr, D, C, &skiplin_b)) return 1;
   }
-  if (linear_from(t, arena, e + ".conv1", Wh, D, true, WP16_ALWAYS_MF16, &conv1)) return 1;
-  if (linear_from(t, arena, e + ".res_projection", Wh, D, true, WP16_ALWAYS_MF16, &res_proj)) return 1;
-  if (linear_from(t, arena, e + ".final_layer.linear", Wh, Wh, true, WP16_ALWAYS_MF16, &final_lin)) return 1;
-  if (linear_from(t, arena, e + ".final_layer.adaLN_modulation.1", 2 * Wh, Wh, true, WP16_ALWAYS_MF16, &final_mod)) return 1;
+  if (lin_from(e + ".conv1", Wh, D, true, &conv1)) return 1;
+  if (lin_from(e + ".res_projection", Wh, D, true, &res_proj)) return 1;
+  if (lin_from(e + ".final_layer.linear", Wh, Wh, true, &final_lin)) return 1;
+  if (lin_from(e + ".final_layer.adaLN_modulation.1", 2 * Wh, Wh, true, &final_mod)) return 1;
   {
     HostTensor *w = nullptr, *b = nullptr;
     if (need(t, e + ".conv2.weight", {C, Wh, 1}, &w) || need(t, e + ".conv2.bias", {C}, &b)) return 1;
-    if (make_linear(arena, w->data.data(), b->data.data(), C, Wh, {WP16_ALWAYS_MF16}, &conv2)) return 1;      // (N = 80: the split-bf16 tile kernels)
+    if (mk_lin(w->data.data(), b->data.data(), C, Wh, &conv2)) return 1;      // (N = 80: the split-bf16 tile kernels)
   }
   // ---- WaveNet ----
   const int L = cfg.wn_layers, k = cfg.wn_kernel;
@@ -145,7 +149,7 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
       HostTensor *iw = nullptr, *ib = nullptr;
       if (need(t, p + ".weight", {2 * Wh, Wh, k}, &iw) || need(t, p + ".bias", {2 * Wh}, &ib)) return 1;
       const std::vector<float> rows = conv_to_rows(iw->data, 2 * Wh, Wh, k);
-      if (make_linear(arena, pair_pack(rows.data(), rows.data() + (size_t)Wh * k * Wh, Wh, k * Wh).data(), nullptr, 2 * Wh, k * Wh, {WP16_ALWAYS_MF16}, &W.in_gate)) return 1;
+      if (mk_lin(pair_pack(rows.data(), rows.data() + (size_t)Wh * k * Wh, Wh, k * Wh).data(), nullptr, 2 * Wh, k * Wh, &W.in_gate)) return 1;
       // cond_layer slice of this layer, same gate packing; its bias absorbs the in_layer bias
       const float* cwl = cw->data.data() + (size_t)l * 2 * Wh * Wh;
       const std::vector<float> cwp = pair_pack(cwl, cwl + (size_t)Wh * Wh, Wh, Wh);
@@ -161,17 +165,17 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
       if (l < L - 1) {
         std::vector<float> w_res(rw->data.begin(), rw->data.begin() + (size_t)Wh * Wh), b_res(rb->data.begin(), rb->data.begin() + Wh);
         std::vector<float> w_skip(rw->data.begin() + (size_t)Wh * Wh, rw->data.end()), b_skip(rb->data.begin() + Wh, rb->data.end());
-        if (make_linear(arena, w_res.data(), b_res.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.res) || make_linear(arena, w_skip.data(), b_skip.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.skip)) return 1;
+        if (mk_lin(w_res.data(), b_res.data(), Wh, Wh, &W.res) || mk_lin(w_skip.data(), b_skip.data(), Wh, Wh, &W.skip)) return 1;
       } else {
         W.has_res = false;
-        if (make_linear(arena, rw->data.data(), rb->data.data(), Wh, Wh, {WP16_ALWAYS_MF16}, &W.skip)) return 1;
+        if (mk_lin(rw->data.data(), rb->data.data(), Wh, Wh, &W.skip)) return 1;
       }
     }
-    if (make_linear(arena, cw_perm.data(), cb_perm.data(), 2 * Wh * L, Wh, {WP16_ALWAYS_MF16}, &wn_cond)) return 1;
+    if (mk_lin(cw_perm.data(), cb_perm.data(), 2 * Wh * L, Wh, &wn_cond)) return 1;
   }
   // ---- length regulator, gpt_layer, codec table ----
   const int LC = cfg.lr_channels;
-  if (linear_from(t, arena, "length_regulator.content_in_proj", LC, cfg.lr_in_channels, true, WP16_ALWAYS_MF16, &lr_in)) return 1;
+  if (lin_from("length_regulator.content_in_proj", LC, cfg.lr_in_channels, true, &lr_in)) return 1;
   lr_conv.resize(cfg.lr_num_convs);
   lr_gn_g.resize(cfg.lr_num_convs);
   lr_gn_b.resize(cfg.lr_num_convs);
@@ -179,7 +183,7 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     HostTensor *w = nullptr, *b = nullptr, *g = nullptr, *bb = nullptr;
     const std::string p = "length_regulator.model." + std::to_string(3 * n);
     if (need(t, p + ".weight", {LC, LC, 3}, &w) || need(t, p + ".bias", {LC}, &b)) return 1;
-    if (make_linear(arena, conv_to_rows(w->data, LC, LC, 3).data(), b->data.data(), LC, 3 * LC, {WP16_ALWAYS_MF16}, &lr_conv[n])) return 1;
+    if (mk_lin(conv_to_rows(w->data, LC, LC, 3).data(), b->data.data(), LC, 3 * LC, &lr_conv[n])) return 1;
     const std::string q = "length_regulator.model." + std::to_string(3 * n + 1);
     if (need(t, q + ".weight", {LC}, &g) || need(t, q + ".bias", {LC}, &bb)) return 1;
     if (up(arena, g->data, &lr_gn_g[n]) || up(arena, bb->data, &lr_gn_b[n])) return 1;
@@ -188,12 +192,12 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
     HostTensor *w = nullptr, *b = nullptr;
     const std::string p = "length_regulator.model." + std::to_string(3 * cfg.lr_num_convs);
     if (need(t, p + ".weight", {LC, LC, 1}, &w) || need(t, p + ".bias", {LC}, &b)) return 1;
-    if (make_linear(arena, w->data.data(), b->data.data(), LC, LC, {WP16_ALWAYS_MF16}, &lr_out)) return 1;
+    if (mk_lin(w->data.data(), b->data.data(), LC, LC, &lr_out)) return 1;
   }
   {
     const int dims[4] = {cfg.gpt_dim, cfg.gpt_layer_dims[0], cfg.gpt_layer_dims[1], cfg.gpt_layer_dims[2]};
     for (int n = 0; n < 3; ++n)
-      if (linear_from(t, arena, "gpt_layer." + std::to_string(n), dims[n + 1], dims[n], true, WP16_ALWAYS_MF16, &gl[n])) return 1;
+      if (lin_from("gpt_layer." + std::to_string(n), dims[n + 1], dims[n], true, &gl[n])) return 1;
     IDX_CHECK(dims[3] == cfg.codec_hidden && cfg.codec_hidden == cfg.lr_in_channels, "gpt_layer / codec / length-regulator widths");
   }
   {
@@ -223,242 +227,187 @@ int S2MelModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& aren
 }
 
 // ---------------------------------------------------------------------------------------------------------
-struct CfmBuffers {
-  float *x_in, *ha, *hb, *hmid, *hn, *qkv, *att, *ff, *xres, *wn_x, *wn_acts, *wn_out, *vout, *condp, *xstate;
-  void *hn_p, *att_p, *ff_p, *acts_p;     // split-bf16 planes of hn / att / ff / wn_acts (producers write them for the next GEMM)
-  void *h_p, *wnx_p, *xres_p;             // planes of the residual stream entering a skip-receive layer, of wn_x, of xres
-  std::vector<void*> skips_p;             // planes of the U-ViT skip tensors
-  std::vector<float*> skips;
-  float *t1, *t1s, *mods, *fmod, *t2, *wnb, *tmp_steps;
-  int *lens2, *plen, *lens2t;      // lens2t: lens2 - tail_t0
-  int tail_t0 = 0;                 // first frame the post-transformer part is evaluated on (0 = every frame)
-  size_t bytes;
+size_t S2MelModel::cfm_workspace_bytes(int B, int T, int n_steps) const { return carve_cfm(cfg, ffn, nullptr, B, T, n_steps).bytes; }
+
+// An operand of a launch: fp32 rows, split-bf16 planes of them (GemmArgs::x_planes / y_planes), or -- an output -- both.
+// A launch given planes to read does not read the rows; one given only planes to write writes no fp32 output.
+struct Src { const float* f; const void* p; Src(const float* rows, const void* planes = nullptr) : f(planes ? nullptr : rows), p(planes) {} };
+struct Dst { float* f; void* p; Dst(float* rows, void* planes = nullptr) : f(rows), p(planes) {} };
+
+static GemmArgs gemm_args(Src x, int ldx, Dst y, int ldy, int M, int act = ACT_NONE, const float* res = nullptr, int ldr = 0) {
+  GemmArgs a;
+  a.x = x.f; a.x_planes = x.p; a.ldx = ldx; a.y = y.f; a.y_planes = y.p; a.ldy = ldy; a.M = M; a.act = act; a.res = res; a.ldr = ldr;
+  return a;
+}
+static int gemm(const LinearWeights& w, Src x, int ldx, Dst y, int ldy, int M, hipStream_t st, int act = ACT_NONE,
+                const float* res = nullptr, int ldr = 0) {
+  return gemm_forward(w, gemm_args(x, ldx, y, ldy, M, act, res, ldr), st);
+}
+
+// The rows a part of one evaluation runs on, and how its operands travel from launch to launch.  An evaluation has at most two
+// row sets: ALL frames (nseq * T rows) and the TAIL, the frames t >= tail_t0 of every sequence compacted to nseq * (T - tail_t0)
+// rows (tail_t0 == 0: the tail IS the set of all frames).
+// Producer -> GEMM chaining: when the consumers run on the LDS-DMA split-bf16 kernel, hn / att / ff / wn_acts are written by
+// their producers directly as bf16 hi/lo planes (same bytes as the fp32 row) and never exist in fp32; the operands that are also
+// read as rows (h, the skips, xres, wn_x) get planes beside their rows.  A call site takes its operands from the accessors and
+// never looks at the flags: planes of one row set handed to a launch on the other are wrong data with no error.
+struct RowSet {
+  const CfmBuffers* w = nullptr;
+  int nseq = 0, seq = 0, rows = 0;      // rows = nseq * seq
+  const int* lens = nullptr;            // [nseq] valid frames
+  bool planes = false;                  // hn / att / ff / wn_acts / skips / h travel as planes
+  bool planes_wn = false;               // and so do the long skip's and the WaveNet's operands (xres, wn_x)
+
+  Src hn_in() const { return in(w->hn, w->hn_p, planes); }                  Dst hn_out() const { return instead(w->hn, w->hn_p, planes); }
+  Src att_in() const { return in(w->att, w->att_p, planes); }               Dst att_out() const { return instead(w->att, w->att_p, planes); }
+  Src ff_in() const { return in(w->ff, w->ff_p, planes); }                  Dst ff_out() const { return instead(w->ff, w->ff_p, planes); }
+  Src acts_in() const { return in(w->wn_acts, w->acts_p, planes); }         Dst acts_out() const { return instead(w->wn_acts, w->acts_p, planes); }
+  Src skip_in(int i) const { return in(w->skips[i], w->skips_p[i], planes); }   Dst skip_out(int i) const { return beside(w->skips[i], w->skips_p[i], planes); }
+  Src xres_in() const { return in(w->xres, w->xres_p, planes_wn); }         Dst xres_out() const { return beside(w->xres, w->xres_p, planes_wn); }
+  Src wnx_in() const { return in(w->wn_x, w->wnx_p, planes_wn); }           Dst wnx_out() const { return beside(w->wn_x, w->wnx_p, planes_wn); }
+  // the residual stream (in ha or hb): its planes exist only where a skip-receive layer reads it next (reread)
+  Src h_in(const float* h) const { return in(h, w->h_p, planes); }          Dst h_out(float* h, bool reread) const { return beside(h, w->h_p, planes && reread); }
+
+ private:
+  static Src in(const float* f, const void* p, bool on) { return on ? Src(f, p) : Src(f); }
+  static Dst instead(float* f, void* p, bool on) { return on ? Dst(nullptr, p) : Dst(f); }      // planes INSTEAD of the rows
+  static Dst beside(float* f, void* p, bool on) { return on ? Dst(f, p) : Dst(f); }             // planes BESIDE the rows
 };
 
-static CfmBuffers carve_cfm(const S2MelModel& m, void* ws, int B, int T, int n_steps) {
-  const auto& c = m.cfg;
-  const int D = c.hidden_dim, C = c.in_channels, Wh = c.wn_hidden;
-  const size_t M2 = (size_t)2 * B * T;
-  const int Win = 2 * C + D + c.style_dim;
-  CfmBuffers b;
-  Carver k(ws);
-  b.x_in = k.take<float>(M2 * Win);
-  b.ha = k.take<float>(M2 * D);
-  b.hb = k.take<float>(M2 * D);
-  b.hmid = k.take<float>(M2 * D);
-  b.hn = k.take<float>(M2 * D);
-  b.qkv = k.take<float>(M2 * 3 * D);
-  b.att = k.take<float>(M2 * D);
-  b.ff = k.take<float>(M2 * m.ffn);
-  b.xres = k.take<float>(M2 * D);
-  b.hn_p = k.take<float>(M2 * std::max(D, Wh));      // 2 bf16 planes = 4 bytes per element
-  b.att_p = k.take<float>(M2 * D);
-  b.ff_p = k.take<float>(M2 * m.ffn);
-  b.acts_p = k.take<float>(M2 * Wh);
-  b.h_p = k.take<float>(M2 * D);
-  b.wnx_p = k.take<float>(M2 * Wh);
-  b.xres_p = k.take<float>(M2 * D);
-  b.wn_x = k.take<float>(M2 * Wh);
-  b.wn_acts = k.take<float>(M2 * Wh);
-  b.wn_out = k.take<float>(M2 * Wh);
-  b.vout = k.take<float>(M2 * C);
-  b.condp = k.take<float>((size_t)B * T * D);
-  b.xstate = k.take<float>((size_t)B * C * T);
-  for (int i = 0; i < c.depth / 2; ++i) b.skips.push_back(k.take<float>(M2 * D));
-  for (int i = 0; i < c.depth / 2; ++i) b.skips_p.push_back(k.take<float>(M2 * D));
-  b.t1 = k.take<float>((size_t)n_steps * D);
-  b.t1s = k.take<float>((size_t)n_steps * D);
-  b.tmp_steps = k.take<float>((size_t)n_steps * std::max(D, Wh));
-  b.mods = k.take<float>((size_t)n_steps * (2 * c.depth + 1) * 2 * D);
-  b.fmod = k.take<float>((size_t)n_steps * 2 * Wh);
-  b.t2 = k.take<float>((size_t)n_steps * Wh);
-  b.wnb = k.take<float>((size_t)n_steps * c.wn_layers * 2 * Wh);
-  b.lens2 = k.take<int>(2 * B);
-  b.plen = k.take<int>(B);
-  b.lens2t = k.take<int>(2 * B);
-  b.bytes = (k.off + 255) & ~(size_t)255;
-  return b;
+// The only place that asks gemm_uses_planes (and with it the 256-row rule) on behalf of the hand-offs: a row set is on planes when
+// EVERY GEMM that reads or writes a chained operand on its rows runs on the LDS-DMA kernel.  within: the set of all frames when
+// this one is its tail -- a tail is on planes only if all frames are (the last block hands planes from one to the other), and the
+// K/V projection never runs on a tail.
+static RowSet row_set(const S2MelModel& m, const CfmBuffers& w, int nseq, int seq, const int* lens, const RowSet* within) {
+  RowSet r;
+  r.w = &w; r.nseq = nseq; r.seq = seq; r.rows = nseq * seq; r.lens = lens;
+  const DiTBlock& b0 = m.blocks[0];
+  const WNLayer& wn0 = m.wn[0];
+  GemmArgs pr;
+  pr.M = r.rows;
+  r.planes = within ? within->planes : gemm_uses_planes(b0.wqkv, pr);
+  for (const LinearWeights* lw : {&b0.wo, &b0.w13, &b0.w2, &m.skiplin_a, &m.final_lin, &wn0.skip}) r.planes = r.planes && gemm_uses_planes(*lw, pr);
+  r.planes_wn = r.planes && (!within || within->planes_wn);
+  for (const LinearWeights* lw : {&m.skiplin_b, &m.conv1, &m.res_proj, &wn0.res}) r.planes_wn = r.planes_wn && gemm_uses_planes(*lw, pr);
+  pr.taps = m.cfg.wn_kernel; pr.seq_len = seq;
+  r.planes_wn = r.planes_wn && gemm_uses_planes(wn0.in_gate, pr);
+  return r;
 }
 
-size_t S2MelModel::cfm_workspace_bytes(int B, int T, int n_steps) const { return carve_cfm(*this, nullptr, B, T, n_steps).bytes; }
-
-// The buffers of ONE half of the stacked [conditional | null] batch: every activation buffer is [2B*T rows][cols] (or planes
-// of that many rows), so half h is the block of B*T rows at h * B*T*cols elements -- for planes too: a half's hi + lo planes
-// [cols/16][B*T][16] are B*T*cols*4 bytes, laid out with rows = B*T.  The two halves never read each other's rows between
-// cfm_pack and the Euler update, which is what lets them run on two streams (dit_eval_halves).
-static CfmBuffers half_view(const S2MelModel& m, const CfmBuffers& w, int h, int B, int T) {
-  const auto& c = m.cfg;
-  const int D = c.hidden_dim, C = c.in_channels, Wh = c.wn_hidden, Win = 2 * C + D + c.style_dim;
-  const size_t R = (size_t)h * B * T;
-  CfmBuffers v = w;
-  auto sh = [&](float* p, int cols) { return p + R * cols; };
-  auto shp = [&](void* p, int cols) -> void* { return static_cast<float*>(p) + R * cols; };
-  v.x_in = sh(w.x_in, Win); v.ha = sh(w.ha, D); v.hb = sh(w.hb, D); v.hmid = sh(w.hmid, D); v.hn = sh(w.hn, D); v.qkv = sh(w.qkv, 3 * D);
-  v.att = sh(w.att, D); v.ff = sh(w.ff, m.ffn); v.xres = sh(w.xres, D); v.wn_x = sh(w.wn_x, Wh); v.wn_acts = sh(w.wn_acts, Wh);
-  v.wn_out = sh(w.wn_out, Wh); v.vout = sh(w.vout, C);
-  v.hn_p = shp(w.hn_p, std::max(D, Wh)); v.att_p = shp(w.att_p, D); v.ff_p = shp(w.ff_p, m.ffn); v.acts_p = shp(w.acts_p, Wh);
-  v.h_p = shp(w.h_p, D); v.wnx_p = shp(w.wnx_p, Wh); v.xres_p = shp(w.xres_p, D);
-  for (size_t i = 0; i < w.skips.size(); ++i) { v.skips[i] = sh(w.skips[i], D); v.skips_p[i] = shp(w.skips_p[i], D); }
-  v.lens2 = w.lens2 + h * B; v.lens2t = w.lens2t + h * B;
-  return v;
+// adaLN-RMSNorm of x into the set's hn; mod: the (weight, bias) pair of this norm and step
+static int ada_norm(const S2MelModel& m, const float* x, const float* g, const float* mod, const RowSet& r, hipStream_t st) {
+  const int D = m.cfg.hidden_dim;
+  const Dst hn = r.hn_out();
+  RowsNormArgs n;
+  n.x_in = x; n.ld_in = D; n.y = hn.f; n.y_planes = hn.p; n.ld_y = D; n.M = r.rows; n.d = D;
+  n.mode = NORM_ADA_RMS; n.eps = m.cfg.norm_eps; n.g1 = g;
+  n.mod_a = mod; n.mod_b = mod + D; n.ld_mod = 0; n.rows_per_batch = 0;
+  return rows_norm_forward(n, st);
 }
 
-// xp / yp: split-bf16 planes of the input / output (GemmArgs::x_planes / y_planes); with xp the fp32 x is not read,
-// with yp and y == nullptr no fp32 output is written
-static int gemm(const LinearWeights& w, const float* x, int ldx, float* y, int ldy, int M, hipStream_t st, int act = ACT_NONE,
-                const float* res = nullptr, int ldr = 0, const void* xp = nullptr, void* yp = nullptr) {
-  GemmArgs a;
-  a.x = xp ? nullptr : x; a.ldx = ldx; a.y = y; a.ldy = ldy; a.M = M; a.act = act; a.res = res; a.ldr = ldr;
-  a.x_planes = xp; a.y_planes = yp;
-  return gemm_forward(w, a, st);
+// Attention of the queries [q0, q0 + Sq) of every sequence over the keys / values of all its frames.  w.qkv: the projection of
+// all frames as fp32 rows, or (qkv_planes) as the split-bf16 planes the planes kernel reads.
+static int attention(const S2MelModel& m, const RowSet& all, bool qkv_planes, int q0, int Sq, Dst o, hipStream_t st) {
+  const int D = m.cfg.hidden_dim, T = all.seq;
+  const float* qkv = all.w->qkv;
+  if (qkv_planes) {
+    AttnPlanesArgs ap;
+    ap.planes = qkv; ap.Mrows = all.rows; ap.ncols = 3 * D; ap.q_col = 0; ap.k_col = D; ap.v_col = 2 * D; ap.T = T; ap.q_row0 = q0; ap.Sq = Sq;
+    ap.B = all.nseq; ap.H = m.cfg.num_heads; ap.kend = all.lens; ap.scale = 0.125f;
+    ap.o = o.f; ap.o_planes = o.p; ap.o_bs = (long)Sq * D; ap.o_ts = D;
+    return flash_attn_planes_forward(ap, st);
+  }
+  AttnArgs a;
+  a.q = qkv + (size_t)q0 * 3 * D; a.k = qkv + D; a.v = qkv + 2 * D; a.o = o.f; a.o_planes = o.p;
+  a.q_bs = a.k_bs = a.v_bs = (long)T * 3 * D; a.o_bs = (long)Sq * D; a.q_ts = a.k_ts = a.v_ts = 3 * D; a.o_ts = D;
+  a.B = all.nseq; a.H = m.cfg.num_heads; a.Sq = Sq; a.Sk = T; a.causal = 0; a.kend = all.lens; a.scale = 0.125f;
+  a.split_bf16 = get_gemm_mode() == GEMM_BF16X3;
+  return flash_attn_forward(a, st);
+}
+
+// One DiT block: h (on the rows of `all`) -> out.  Norm and K/V projection run on all frames; everything behind them -- queries,
+// attention output, wo, norm, w13, w2 -- on `post`: all frames again, or, in the last block of a compacted tail, whose keys and
+// values cover every frame but whose output nothing attends to, the tail rows alone.  res: h on post's rows: h itself, or the
+// buffer the block gathers h's tail rows into.  lag_event (optional) is recorded behind the attention.
+static int dit_block(S2MelModel& m, int i, const float* mods, const float* h, const RowSet& all, const RowSet& post, float* res, Dst out,
+                     hipEvent_t lag_event, hipStream_t st) {
+  const auto& c = m.cfg;
+  const CfmBuffers& w = *all.w;
+  const DiTBlock& B = m.blocks[i];
+  const int D = c.hidden_dim, T = all.seq, q0 = T - post.seq;
+  if (ada_norm(m, h, B.attn_g, mods + (size_t)(2 * i) * 2 * D, all, st)) return 1;
+  bool qkv_planes = false;
+  {     // qkv projection; the rotary embedding of q and k rides in its epilogue when the LDS-DMA kernel runs it
+    GemmArgs g = gemm_args(all.hn_in(), D, w.qkv, 3 * D, all.rows);
+    const bool fuse_rope = gemm_uses_planes(B.wqkv, g);
+    // LDS-DMA GEMM: rotary embedding in its epilogue, and q / k / v leave it as split-bf16 planes (the same bytes as the fp32
+    // rows they replace) for the planes attention kernel
+    qkv_planes = fuse_rope && D == 64 * c.num_heads;
+    if (fuse_rope) { g.rope = m.rope; g.rope_T = T; g.rope_cols = 2 * D; }
+    if (qkv_planes) { g.y = nullptr; g.y_planes = w.qkv; }
+    if (gemm_forward(B.wqkv, g, st)) return 1;
+    if (!fuse_rope && rotary_qk(w.qkv, all.rows, c.num_heads, T, m.rope, st)) return 1;
+  }
+  if (attention(m, all, qkv_planes, q0, post.seq, post.att_out(), st)) return 1;
+  if (lag_event) IDX_HIP(hipEventRecord(lag_event, st));
+  if (res != h && gather_tail_rows(res, D, h, D, D, all.nseq, T, q0, st)) return 1;
+  if (gemm(B.wo, post.att_in(), D, w.hmid, D, post.rows, st, ACT_NONE, res, D)) return 1;           // h + attention(...)
+  if (ada_norm(m, w.hmid, B.ffn_g, mods + (size_t)(2 * i + 1) * 2 * D, post, st)) return 1;
+  if (gemm(B.w13, post.hn_in(), D, post.ff_out(), m.ffn, post.rows, st, ACT_SWIGLU)) return 1;
+  return gemm(B.w2, post.ff_in(), m.ffn, out, D, post.rows, st, ACT_NONE, w.hmid, D);               // out = h + ffn
 }
 
 // N2 sequences of T frames (one CFG half, or the stacked batch); lag_event (optional) is recorded behind the first attention
 static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipStream_t st, hipEvent_t lag_event) {
   const auto& c = m.cfg;
   const int D = c.hidden_dim, C = c.in_channels, Wh = c.wn_hidden, depth = c.depth, half = depth / 2;
-  const int M = N2 * T, Win = 2 * C + D + c.style_dim;
+  const int Win = 2 * C + D + c.style_dim;
   const float* mods = w.mods + (size_t)step * (2 * depth + 1) * 2 * D;
-  // Producer -> GEMM chaining: when the consumers run on the LDS-DMA split-bf16 kernel, hn / att / ff / wn_acts are
-  // written by their producers directly as bf16 hi/lo planes (same bytes as the fp32 row) and never exist in fp32.
-  bool chain = true;
-  {
-    GemmArgs pr;
-    pr.M = M;
-    const LinearWeights* used[] = {&m.blocks[0].wqkv, &m.blocks[0].wo, &m.blocks[0].w13, &m.blocks[0].w2, &m.skiplin_a, &m.final_lin,
-                                   &m.wn[0].skip};
-    for (const LinearWeights* lw : used) chain = chain && gemm_uses_planes(*lw, pr);
-  }
-  bool chain_wn = chain;      // the same for the long skip and the WaveNet operands (xres, wn_x)
-  {
-    GemmArgs pr;
-    pr.M = M;
-    const LinearWeights* used[] = {&m.skiplin_b, &m.conv1, &m.res_proj, &m.wn[0].res};
-    for (const LinearWeights* lw : used) chain_wn = chain_wn && gemm_uses_planes(*lw, pr);
-    pr.taps = c.wn_kernel; pr.seq_len = T;
-    chain_wn = chain_wn && gemm_uses_planes(m.wn[0].in_gate, pr);
-  }
-  void* const hn_p = chain ? w.hn_p : nullptr;
   // The solver needs the estimate only on the frames t >= tail_t0 (see below): the post-transformer part and, in the LAST block,
-  // everything after the K/V projection run on those frames alone, compacted to [N2][Tt] rows.
-  const int t0 = w.tail_t0, Tt = T - t0, Mt = N2 * Tt;
-  bool chain_t = chain, chain_wn_t = chain_wn;
-  if (t0 > 0) {
-    GemmArgs pr;
-    pr.M = Mt;
-    const LinearWeights* used[] = {&m.blocks[0].wo, &m.blocks[0].w13, &m.blocks[0].w2, &m.skiplin_a, &m.final_lin, &m.wn[0].skip};
-    for (const LinearWeights* lw : used) chain_t = chain_t && gemm_uses_planes(*lw, pr);
-    chain_wn_t = chain_t && chain_wn && gemm_uses_planes(m.skiplin_b, pr) && gemm_uses_planes(m.conv1, pr) && gemm_uses_planes(m.res_proj, pr) &&
-                 gemm_uses_planes(m.wn[0].res, pr);
-    pr.taps = c.wn_kernel; pr.seq_len = Tt;
-    chain_wn_t = chain_wn_t && gemm_uses_planes(m.wn[0].in_gate, pr);
-  }
-  float* const hnt_f = chain_t ? nullptr : w.hn;
-  void* const hnt_p = chain_t ? w.hn_p : nullptr;
-  auto ada_rows = [&](const float* x, const float* g, int mod_idx, int rows, bool planes) {
-    RowsNormArgs n;
-    n.x_in = x; n.ld_in = D; n.y = planes ? nullptr : w.hn; n.y_planes = planes ? w.hn_p : nullptr; n.ld_y = D; n.M = rows; n.d = D;
-    n.mode = NORM_ADA_RMS; n.eps = c.norm_eps; n.g1 = g;
-    n.mod_a = mods + (size_t)mod_idx * 2 * D; n.mod_b = n.mod_a + D; n.ld_mod = 0; n.rows_per_batch = 0;
-    return rows_norm_forward(n, st);
-  };
-  auto ada = [&](const float* x, const float* g, int mod_idx) { return ada_rows(x, g, mod_idx, M, chain); };
+  // everything after the K/V projection run on those frames alone, compacted to [N2][T - tail_t0] rows.
+  const int t0 = w.tail_t0;
+  const RowSet all = row_set(m, w, N2, T, w.lens2, nullptr);
+  const RowSet tail = t0 > 0 ? row_set(m, w, N2, T - t0, w.lens2t, &all) : all;
   if (lag_event && depth < 2) IDX_HIP(hipEventRecord(lag_event, st));      // (a one-block model has no "behind the first attention")
-  bool h_compact = false;      // h already holds only the tail rows (the last block produced it that way)
-  if (gemm(m.merge, w.x_in, Win, w.ha, D, M, st)) return 1;
+  if (gemm(m.merge, w.x_in, Win, w.ha, D, all.rows, st)) return 1;
   float* h = w.ha;
   int pushed = 0;
   for (int i = 0; i < depth; ++i) {
-    DiTBlock& B = m.blocks[i];
     if (i > half) {     // U-ViT receive: skip_in_linear(cat[x, skip]) as two GEMMs (model.py:233-234)
-      float* skip = w.skips[--pushed];
-      void* skip_p = chain ? w.skips_p[pushed] : nullptr;
-      if (gemm(B.skip_a, h, D, w.hmid, D, M, st, ACT_NONE, nullptr, 0, chain ? w.h_p : nullptr)) return 1;
+      DiTBlock& B = m.blocks[i];
+      --pushed;
+      if (gemm(B.skip_a, all.h_in(h), D, w.hmid, D, all.rows, st)) return 1;
       float* dst = (h == w.ha) ? w.hb : w.ha;
-      if (gemm(B.skip_b, skip, D, dst, D, M, st, ACT_NONE, w.hmid, D, skip_p)) return 1;
+      if (gemm(B.skip_b, all.skip_in(pushed), D, dst, D, all.rows, st, ACT_NONE, w.hmid, D)) return 1;
       h = dst;
     }
-    if (ada(h, B.attn_g, 2 * i)) return 1;
-    bool qkv_planes = false;
-    {     // qkv projection; the rotary embedding of q and k rides in its epilogue when the LDS-DMA kernel runs it
-      GemmArgs g;
-      g.x = chain ? nullptr : w.hn; g.x_planes = hn_p; g.ldx = D; g.y = w.qkv; g.ldy = 3 * D; g.M = M;
-      const bool fuse_rope = gemm_uses_planes(B.wqkv, g);
-      // LDS-DMA GEMM: rotary embedding in its epilogue, and q / k / v leave it as split-bf16 planes (the same bytes as the fp32
-      // rows they replace) for the planes attention kernel
-      qkv_planes = fuse_rope && D == 64 * c.num_heads;
-      if (fuse_rope) { g.rope = m.rope; g.rope_T = T; g.rope_cols = 2 * D; }
-      if (qkv_planes) { g.y = nullptr; g.y_planes = w.qkv; }
-      if (gemm_forward(B.wqkv, g, st)) return 1;
-      if (!fuse_rope && rotary_qk(w.qkv, M, c.num_heads, T, m.rope, st)) return 1;
-    }
-    AttnPlanesArgs ap;
-    ap.planes = w.qkv; ap.Mrows = M; ap.ncols = 3 * D; ap.q_col = 0; ap.k_col = D; ap.v_col = 2 * D; ap.T = T; ap.q_row0 = 0; ap.Sq = T;
-    ap.B = N2; ap.H = c.num_heads; ap.kend = w.lens2; ap.scale = 0.125f; ap.o = w.att; ap.o_bs = (long)T * D; ap.o_ts = D;
-    AttnArgs a;
-    a.q = w.qkv; a.k = w.qkv + D; a.v = w.qkv + 2 * D; a.o = w.att;
-    a.q_bs = a.k_bs = a.v_bs = (long)T * 3 * D; a.o_bs = (long)T * D;
-    a.q_ts = a.k_ts = a.v_ts = 3 * D; a.o_ts = D;
-    a.B = N2; a.H = c.num_heads; a.Sq = T; a.Sk = T; a.causal = 0; a.kend = w.lens2; a.scale = 0.125f;
-    a.split_bf16 = get_gemm_mode() == GEMM_BF16X3;
-    if (i == depth - 1 && t0 > 0 && i >= half) {
-      // last block: its keys / values cover every frame, but only the tail frames' queries, attention output, projection and
-      // feed-forward are ever used (nothing attends to this block's output): Mt rows instead of M from here on
-      a.q = w.qkv + (size_t)t0 * 3 * D; a.Sq = Tt; a.o_bs = (long)Tt * D;
-      ap.q_row0 = t0; ap.Sq = Tt; ap.o_bs = (long)Tt * D;
-      if (chain_t) { a.o = nullptr; a.o_planes = w.att_p; ap.o = nullptr; ap.o_planes = w.att_p; }
-      if (qkv_planes ? flash_attn_planes_forward(ap, st) : flash_attn_forward(a, st)) return 1;
-      if (gather_tail_rows(w.xres, D, h, D, D, N2, T, t0, st)) return 1;                       // residual rows (xres is free here)
-      if (gemm(B.wo, w.att, D, w.hmid, D, Mt, st, ACT_NONE, w.xres, D, chain_t ? w.att_p : nullptr)) return 1;
-      if (ada_rows(w.hmid, B.ffn_g, 2 * i + 1, Mt, chain_t)) return 1;
-      if (gemm(B.w13, w.hn, D, chain_t ? nullptr : w.ff, m.ffn, Mt, st, ACT_SWIGLU, nullptr, 0, hnt_p, chain_t ? w.ff_p : nullptr)) return 1;
-      float* dst = (h == w.ha) ? w.hb : w.ha;
-      if (gemm(B.w2, w.ff, m.ffn, dst, D, Mt, st, ACT_NONE, w.hmid, D, chain_t ? w.ff_p : nullptr, nullptr)) return 1;
-      h = dst;
-      h_compact = true;
-      break;
-    }
-    if (chain) { a.o = nullptr; a.o_planes = w.att_p; ap.o = nullptr; ap.o_planes = w.att_p; }
-    if (qkv_planes ? flash_attn_planes_forward(ap, st) : flash_attn_forward(a, st)) return 1;
-    if (i == 0 && lag_event) IDX_HIP(hipEventRecord(lag_event, st));
-    if (gemm(B.wo, w.att, D, w.hmid, D, M, st, ACT_NONE, h, D, chain ? w.att_p : nullptr)) return 1;           // h + attention(...)
-    if (ada(w.hmid, B.ffn_g, 2 * i + 1)) return 1;
-    if (gemm(B.w13, w.hn, D, chain ? nullptr : w.ff, m.ffn, M, st, ACT_SWIGLU, nullptr, 0, hn_p, chain ? w.ff_p : nullptr)) return 1;
-    float* dst = (i < half) ? w.skips[pushed] : ((h == w.ha) ? w.hb : w.ha);
-    // its output is read again as a GEMM operand when it is a skip tensor (skip_b later) or enters a skip-receive layer (skip_a)
-    void* dst_p = !chain ? nullptr : (i < half ? w.skips_p[pushed] : (i + 1 < depth && i + 1 > half ? w.h_p : nullptr));
-    if (gemm(B.w2, w.ff, m.ffn, dst, D, M, st, ACT_NONE, w.hmid, D, chain ? w.ff_p : nullptr, dst_p)) return 1;      // out = h + ffn
+    // the first half's outputs are the skip tensors; a block's output is read again as a GEMM operand when it is a skip tensor
+    // (skip_b later) or enters a skip-receive layer (skip_a)
+    const Dst out = i < half ? all.skip_out(pushed) : all.h_out((h == w.ha) ? w.hb : w.ha, i + 1 < depth && i + 1 > half);
+    // the last block of a compacted tail gathers its residual rows into xres (free here) and leaves h on the tail rows; it is
+    // never a skip push (depth - 1 >= depth / 2), so with t0 > 0 h always leaves the loop compacted
+    const bool cut = i == depth - 1 && t0 > 0;
+    if (dit_block(m, i, mods, h, all, cut ? tail : all, cut ? w.xres : h, out, i == 0 && !cut ? lag_event : nullptr, st)) return 1;
     if (i < half) ++pushed;
-    h = dst;
+    h = out.f;
   }
   // ---- everything after the transformer is row-local or a short convolution (WaveNet: k = 5, 8 layers -> 16 frames of context),
   // and the Euler step discards the estimate on the prompt frames (x[..., :prompt_len] = 0, flow_matching.py:113): in the solver
   // only the frames t >= tail_t0 = prompt_len - halo are evaluated -- the prompt is 44 % of the frames at configs[2] -- on rows
   // compacted to [N2][T - tail_t0].  The frames t >= prompt_len come out bit-identical: the reflect padding at the cut only reaches
   // the halo.  tail_t0 = 0 (the stand-alone estimator entry point): every frame.
-  const float* ht = h;
+  const int Mt = tail.rows, Tt = tail.seq;
   const float* xin_t = w.x_in;
   int ld_xin = Win;
-  const int* lens_t = w.lens2;
   if (t0 > 0) {
-    if (!h_compact) {
-      float* hc = (h == w.ha) ? w.hb : w.ha;
-      if (gather_tail_rows(hc, D, h, D, D, N2, T, t0, st)) return 1;
-      ht = hc;
-    }
     if (gather_tail_rows(w.qkv, C, w.x_in, Win, C, N2, T, t0, st)) return 1;      // the x columns of x_in (qkv is free here)
-    xin_t = w.qkv; ld_xin = C; lens_t = w.lens2t;
+    xin_t = w.qkv; ld_xin = C;
   }
-  {
-    RowsNormArgs n;
-    n.x_in = ht; n.ld_in = D; n.y = hnt_f; n.y_planes = hnt_p; n.ld_y = D; n.M = Mt; n.d = D; n.mode = NORM_ADA_RMS; n.eps = c.norm_eps; n.g1 = m.final_g;
-    n.mod_a = mods + (size_t)(2 * depth) * 2 * D; n.mod_b = n.mod_a + D; n.ld_mod = 0; n.rows_per_batch = 0;
-    if (rows_norm_forward(n, st)) return 1;
-  }
+  if (ada_norm(m, h, m.final_g, mods + (size_t)(2 * depth) * 2 * D, tail, st)) return 1;
   // long skip: skip_linear(cat[x_res, x]) (diffusion_transformer.py:243-244); x rows live in x_in[:, :C]
-  if (gemm(m.skiplin_a, w.hn, D, w.hmid, D, Mt, st, ACT_NONE, nullptr, 0, hnt_p)) return 1;
-  if (gemm(m.skiplin_b, xin_t, ld_xin, w.xres, D, Mt, st, ACT_NONE, w.hmid, D, nullptr, chain_wn_t ? w.xres_p : nullptr)) return 1;
-  if (gemm(m.conv1, w.xres, D, w.wn_x, Wh, Mt, st, ACT_NONE, nullptr, 0, chain_wn_t ? w.xres_p : nullptr, chain_wn_t ? w.wnx_p : nullptr)) return 1;
+  if (gemm(m.skiplin_a, tail.hn_in(), D, w.hmid, D, Mt, st)) return 1;
+  if (gemm(m.skiplin_b, xin_t, ld_xin, tail.xres_out(), D, Mt, st, ACT_NONE, w.hmid, D)) return 1;
+  if (gemm(m.conv1, tail.xres_in(), D, tail.wnx_out(), Wh, Mt, st)) return 1;
   // WaveNet (wavenet.py:138-166)
   const int L = c.wn_layers, k = c.wn_kernel;
   for (int l = 0; l < L; ++l) {
@@ -467,29 +416,28 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
     for (int q = 0; q < l; ++q) dil *= c.wn_dilation_rate;
     LinearWeights in = W.in_gate;
     in.bias = w.wnb + ((size_t)step * L + l) * 2 * Wh;     // in_layer bias + g_l of this step, gate-packed
-    GemmArgs g;
-    g.x = chain_wn_t ? nullptr : w.wn_x; g.x_planes = chain_wn_t ? w.wnx_p : nullptr; g.ldx = Wh; g.y = chain_t ? nullptr : w.wn_acts; g.y_planes = chain_t ? w.acts_p : nullptr; g.ldy = Wh; g.M = Mt; g.act = ACT_GATE;
-    g.taps = k; g.seq_len = Tt; g.dil = dil; g.pad_left = (k - 1) / 2 * dil; g.pad_mode = 1; g.row_len = lens_t;
+    GemmArgs g = gemm_args(tail.wnx_in(), Wh, tail.acts_out(), Wh, Mt, ACT_GATE);
+    g.taps = k; g.seq_len = Tt; g.dil = dil; g.pad_left = (k - 1) / 2 * dil; g.pad_mode = 1; g.row_len = tail.lens;
     if (gemm_forward(in, g, st)) return 1;
     if (W.has_res) {   // x = (x + res) * mask
-      GemmArgs r;
-      r.x = chain_t ? nullptr : w.wn_acts; r.x_planes = chain_t ? w.acts_p : nullptr; r.ldx = Wh; r.y = w.wn_x; r.y_planes = chain_wn_t ? w.wnx_p : nullptr; r.ldy = Wh; r.res = w.wn_x; r.ldr = Wh; r.M = Mt; r.seq_len = Tt; r.row_len = lens_t;
+      GemmArgs r = gemm_args(tail.acts_in(), Wh, tail.wnx_out(), Wh, Mt, ACT_NONE, w.wn_x, Wh);
+      r.seq_len = Tt; r.row_len = tail.lens;
       if (gemm_forward(W.res, r, st)) return 1;
     }
-    GemmArgs sk;       // output += skip ; the last layer's epilogue applies "* x_mask" to the finished sum
-    sk.x = chain_t ? nullptr : w.wn_acts; sk.x_planes = chain_t ? w.acts_p : nullptr; sk.ldx = Wh; sk.y = w.wn_out; sk.ldy = Wh; sk.M = Mt;
+    GemmArgs sk = gemm_args(tail.acts_in(), Wh, w.wn_out, Wh, Mt);     // output += skip ; the last layer's epilogue applies "* x_mask" to the finished sum
     if (l > 0) { sk.res = w.wn_out; sk.ldr = Wh; }
-    if (l == L - 1) { sk.seq_len = Tt; sk.row_len = lens_t; }
+    if (l == L - 1) { sk.seq_len = Tt; sk.row_len = tail.lens; }
     if (gemm_forward(W.skip, sk, st)) return 1;
   }
-  if (gemm(m.res_proj, w.xres, D, w.hmid, Wh, Mt, st, ACT_NONE, w.wn_out, Wh, chain_wn_t ? w.xres_p : nullptr)) return 1;
+  if (gemm(m.res_proj, tail.xres_in(), D, w.hmid, Wh, Mt, st, ACT_NONE, w.wn_out, Wh)) return 1;
   {
+    const Dst hn = tail.hn_out();
     RowsNormArgs n;     // FinalLayer (diffusion_transformer.py:96-101)
-    n.x_in = w.hmid; n.ld_in = Wh; n.y = hnt_f; n.y_planes = hnt_p; n.ld_y = Wh; n.M = Mt; n.d = Wh; n.mode = NORM_MOD_LN; n.eps = 1e-6f;
+    n.x_in = w.hmid; n.ld_in = Wh; n.y = hn.f; n.y_planes = hn.p; n.ld_y = Wh; n.M = Mt; n.d = Wh; n.mode = NORM_MOD_LN; n.eps = 1e-6f;
     n.mod_a = w.fmod + (size_t)step * 2 * Wh; n.mod_b = n.mod_a + Wh; n.ld_mod = 0; n.rows_per_batch = 0;
     if (rows_norm_forward(n, st)) return 1;
   }
-  if (gemm(m.final_lin, w.hn, Wh, w.att, Wh, Mt, st, ACT_NONE, nullptr, 0, hnt_p)) return 1;
+  if (gemm(m.final_lin, tail.hn_in(), Wh, w.att, Wh, Mt, st)) return 1;
   return gemm(m.conv2, w.att, Wh, w.vout, C, Mt, st);
 }
 
@@ -499,7 +447,7 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
 // all workgroups of one launch are in the same phase.  Two launches of DIFFERENT kernels side by side are not: with the null
 // half of the batch a couple of kernels behind the conditional half, one half's epilogues drain while the other half multiplies
 // (tools/two_stream_gemm.py: the four GEMMs of a DiT layer 1290 -> 1098 us).  The halves share nothing between cfm_pack and the
-// Euler update.  Each half is a dit_eval of its own with N2 = B, so chain / chain_t are taken at B*T and B*Tt rows instead of 2B*T
+// Euler update.  Each half is a dit_eval of its own with N2 = B, so its row sets (row_set) are taken at B*T and B*Tt rows instead of 2B*T
 // and 2B*Tt: results are bit-identical to the single-stream order (same kernels on the same rows) when both pairs are on the
 // same side of the 256-row switch (and always in GEMM_F32 mode); otherwise a half runs the fp32-row kernels where the stacked
 // batch runs planes, within the split-bf16 bounds (tests/test_s2mel_dispatch_gpu.py::test_solver_halves_on_two_streams).
@@ -562,8 +510,8 @@ static bool halves_on_two_streams(hipStream_t st) {
 // one estimator evaluation of the solver: both CFG halves, on two streams (two_streams) or stacked
 static int dit_eval_halves(S2MelModel& m, CfmBuffers& w, int B, int T, int step, bool two_streams, hipStream_t st) {
   if (!two_streams) return dit_eval(m, w, 2 * B, T, step, st, nullptr);
-  CfmBuffers v0 = half_view(m, w, 0, B, T);
-  CfmBuffers v1 = half_view(m, w, 1, B, T);
+  CfmBuffers v0 = half_view(m.cfg, m.ffn, w, 0, B, T);
+  CfmBuffers v1 = half_view(m.cfg, m.ffn, w, 1, B, T);
   HalfStreams hs;
   if (half_streams_for(st, &hs)) return 1;
   IDX_HIP(hipEventRecord(hs.fork, st));
@@ -586,50 +534,73 @@ int S2MelModel::cfm(const float* mu, const int* x_lens_host, const float* prompt
   IDX_CHECK(cfg_rate > 0.0f, "the stacked-CFG path needs inference_cfg_rate > 0 (reference default 0.7)");
   IDX_CHECK(T <= rope_len, "sequence longer than the rope cache");
   IDX_CHECK(ws && ws_bytes >= cfm_workspace_bytes(B, T, n_steps), "workspace too small");
-  CfmBuffers w = carve_cfm(*this, ws, B, T, n_steps);
+  CfmBuffers w = carve_cfm(cfg, ffn, ws, B, T, n_steps);
   if (cfm_solve(w, mu, x_lens_host, prompt, prompt_lens_host, Tp_max, style, z, t_emb, dt_host, n_steps, cfg_rate, B, T, st)) return 1;
   IDX_HIP(hipMemcpyAsync(out, w.xstate, (size_t)B * cfg.in_channels * T * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
+}
+
+// ---- the per-call set-up the solver and the stand-alone estimator share -----------------------------------
+// Lengths, checked and on the device when it returns: lens2 (both halves) and plen.  solver: a prompt lies inside its own row, and
+// the tail cut is taken from the shortest prompt (w.tail_t0, lens2t = lens2 - tail_t0); the stand-alone estimator (prompt within T)
+// evaluates every frame.
+static int upload_lens(const S2MelModel& m, CfmBuffers& w, const int* x_lens_host, const int* prompt_lens_host, int Tp_max, int B, int T,
+                       bool solver, hipStream_t st) {
+  const auto& c = m.cfg;
+  std::vector<int> lens2(2 * B), plen(B), lens2t(2 * B);
+  for (int b = 0; b < B; ++b) {
+    const int pmax = std::min(Tp_max, solver ? x_lens_host[b] : T);
+    IDX_CHECK(x_lens_host[b] > 0 && x_lens_host[b] <= T && prompt_lens_host[b] >= 0 && prompt_lens_host[b] <= pmax, "lengths");
+    lens2[b] = lens2[B + b] = x_lens_host[b];
+    plen[b] = prompt_lens_host[b];
+  }
+  IDX_HIP(hipMemcpyAsync(w.lens2, lens2.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
+  if (solver) {
+    // the post-transformer part runs on the frames from tail_t0 on: the shortest prompt minus the WaveNet's one-sided context
+    int halo = 0, dil = 1, pmin = plen[0];
+    for (int l = 0; l < c.wn_layers; ++l) { halo += (c.wn_kernel - 1) / 2 * dil; dil *= c.wn_dilation_rate; }
+    for (int b = 0; b < B; ++b) pmin = std::min(pmin, plen[b]);
+    w.tail_t0 = pmin - halo >= 64 ? pmin - halo : 0;
+    for (int i = 0; i < 2 * B; ++i) lens2t[i] = lens2[i] - w.tail_t0;
+    IDX_HIP(hipMemcpyAsync(w.lens2t, lens2t.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  IDX_HIP(hipMemcpyAsync(w.plen, plen.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+// per-call constants: every t-dependent vector for all steps at once (M = n_steps GEMMs)
+static int step_constants(const S2MelModel& m, const CfmBuffers& w, const float* t_emb, int n_steps, hipStream_t st) {
+  const int D = m.cfg.hidden_dim, Wh = m.cfg.wn_hidden;
+  if (gemm(m.temb0, t_emb, 256, w.tmp_steps, D, n_steps, st, ACT_SILU) || gemm(m.temb2, w.tmp_steps, D, w.t1, D, n_steps, st)) return 1;
+  if (gemm(m.mod_all, w.t1, D, w.mods, (2 * m.cfg.depth + 1) * 2 * D, n_steps, st)) return 1;
+  if (silu_rows(w.t1s, w.t1, (size_t)n_steps * D, st) || gemm(m.final_mod, w.t1s, Wh, w.fmod, 2 * Wh, n_steps, st)) return 1;
+  if (gemm(m.t2emb0, t_emb, 256, w.tmp_steps, Wh, n_steps, st, ACT_SILU) || gemm(m.t2emb2, w.tmp_steps, Wh, w.t2, Wh, n_steps, st)) return 1;
+  return gemm(m.wn_cond, w.t2, Wh, w.wnb, m.cfg.wn_layers * 2 * Wh, n_steps, st);
+}
+
+// the stacked [cond | null] input rows from the state w.xstate (x_only: see CfmPackArgs)
+static CfmPackArgs pack_args(const S2MelModel& m, const CfmBuffers& w, const float* prompt, const float* style, int B, int T, int Tp_max) {
+  const auto& c = m.cfg;
+  CfmPackArgs pk;
+  pk.x_in = w.x_in; pk.ld = 2 * c.in_channels + c.hidden_dim + c.style_dim; pk.x = w.xstate; pk.prompt = prompt; pk.prompt_len = w.plen;
+  pk.cond = w.condp; pk.cond_null = m.cond_proj.bias; pk.style = style;
+  pk.B = B; pk.T = T; pk.C = c.in_channels; pk.D = c.hidden_dim; pk.S = c.style_dim; pk.Tp_max = Tp_max;
+  return pk;
 }
 
 // The Euler solve shared by cfm and cfm_rows: leaves the final state x [B][C][T] in w.xstate.
 int S2MelModel::cfm_solve(CfmBuffers& w, const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host,
                           int Tp_max, const float* style, const float* z, const float* t_emb, const float* dt_host, int n_steps,
                           float cfg_rate, int B, int T, hipStream_t st) {
-  const int D = cfg.hidden_dim, C = cfg.in_channels, Wh = cfg.wn_hidden, depth = cfg.depth, L = cfg.wn_layers;
-  std::vector<int> lens2(2 * B), plen(B);
-  for (int b = 0; b < B; ++b) {
-    IDX_CHECK(x_lens_host[b] > 0 && x_lens_host[b] <= T && prompt_lens_host[b] >= 0 && prompt_lens_host[b] <= std::min(Tp_max, x_lens_host[b]), "lengths");
-    lens2[b] = lens2[B + b] = x_lens_host[b];
-    plen[b] = prompt_lens_host[b];
-  }
-  {
-    // the post-transformer part runs on the frames from tail_t0 on: the shortest prompt minus the WaveNet's one-sided context
-    int halo = 0, dil = 1, pmin = plen[0];
-    for (int l = 0; l < L; ++l) { halo += (cfg.wn_kernel - 1) / 2 * dil; dil *= cfg.wn_dilation_rate; }
-    for (int b = 0; b < B; ++b) pmin = std::min(pmin, plen[b]);
-    w.tail_t0 = pmin - halo >= 64 ? pmin - halo : 0;
-  }
-  std::vector<int> lens2t(2 * B);
-  for (int i = 0; i < 2 * B; ++i) lens2t[i] = lens2[i] - w.tail_t0;
-  IDX_HIP(hipMemcpyAsync(w.lens2, lens2.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(w.lens2t, lens2t.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(w.plen, plen.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));
-  // ---- per-call constants: every t-dependent vector for all steps at once (M = n_steps GEMMs) ----
-  if (gemm(temb0, t_emb, 256, w.tmp_steps, D, n_steps, st, ACT_SILU) || gemm(temb2, w.tmp_steps, D, w.t1, D, n_steps, st)) return 1;
-  if (gemm(mod_all, w.t1, D, w.mods, (2 * depth + 1) * 2 * D, n_steps, st)) return 1;
-  if (silu_rows(w.t1s, w.t1, (size_t)n_steps * D, st) || gemm(final_mod, w.t1s, Wh, w.fmod, 2 * Wh, n_steps, st)) return 1;
-  if (gemm(t2emb0, t_emb, 256, w.tmp_steps, Wh, n_steps, st, ACT_SILU) || gemm(t2emb2, w.tmp_steps, Wh, w.t2, Wh, n_steps, st)) return 1;
-  if (gemm(wn_cond, w.t2, Wh, w.wnb, L * 2 * Wh, n_steps, st)) return 1;
+  const int D = cfg.hidden_dim, C = cfg.in_channels;
+  if (upload_lens(*this, w, x_lens_host, prompt_lens_host, Tp_max, B, T, true, st)) return 1;
+  if (step_constants(*this, w, t_emb, n_steps, st)) return 1;
   if (gemm(cond_proj, mu, cfg.content_dim, w.condp, D, B * T, st)) return 1;
   if (cfm_init_state(w.xstate, z, w.plen, B, C, T, st)) return 1;       // x[..., :prompt_len] = 0 (flow_matching.py:82)
   const bool two_streams = halves_on_two_streams(st);
   for (int s = 0; s < n_steps; ++s) {
-    CfmPackArgs pk;
-    pk.x_in = w.x_in; pk.ld = 2 * C + D + cfg.style_dim; pk.x = w.xstate; pk.prompt = prompt; pk.prompt_len = w.plen;
-    pk.cond = w.condp; pk.cond_null = cond_proj.bias; pk.style = style;
-    pk.B = B; pk.T = T; pk.C = C; pk.D = D; pk.S = cfg.style_dim; pk.Tp_max = Tp_max;
+    CfmPackArgs pk = pack_args(*this, w, prompt, style, B, T, Tp_max);
     pk.x_only = s > 0;      // x_in is read by the merge GEMM and the long skip only: its other 784 columns are packed once
     if (cfm_pack(pk, st)) return 1;
     if (dit_eval_halves(*this, w, B, T, s, two_streams, st)) return 1;
@@ -687,7 +658,7 @@ int S2MelModel::cfm_rows(const float* gen_cond, const int* target_lens_host, int
   }
   IDX_CHECK(T == T_need, "T must be max_b(prompt_lens[b] + target_lens[b])");
   IDX_CHECK(ws && ws_bytes >= cfm_rows_workspace_bytes(B, T, Tp_max, n_steps), "workspace too small");
-  CfmBuffers w = carve_cfm(*this, ws, B, T, n_steps);
+  CfmBuffers w = carve_cfm(cfg, ffn, ws, B, T, n_steps);
   CfmRowsBuffers r = carve_cfm_rows(*this, ws, w.bytes, B, T, Tp_max);
   IDX_HIP(hipMemcpyAsync(r.pcond, prompt_cond_host, B * sizeof(float*), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(r.ref_mel, ref_mel_host, B * sizeof(float*), hipMemcpyHostToDevice, st));
@@ -710,31 +681,15 @@ int S2MelModel::estimator(const float* x, const float* prompt, const int* prompt
   IDX_CHECK(x && prompt && prompt_lens_host && x_lens_host && t_emb && style && mu && out_tm, "null pointer");
   IDX_CHECK(B > 0 && T > 0 && Tp_max > 0 && T <= rope_len, "shape");
   IDX_CHECK(ws && ws_bytes >= cfm_workspace_bytes(B, T, 1), "workspace too small");
-  const int D = cfg.hidden_dim, C = cfg.in_channels, Wh = cfg.wn_hidden, depth = cfg.depth, L = cfg.wn_layers;
-  CfmBuffers w = carve_cfm(*this, ws, B, T, 1);
-  std::vector<int> lens2(2 * B), plen(B);
-  for (int b = 0; b < B; ++b) {
-    IDX_CHECK(x_lens_host[b] > 0 && x_lens_host[b] <= T && prompt_lens_host[b] >= 0 && prompt_lens_host[b] <= std::min(Tp_max, T), "lengths");
-    lens2[b] = lens2[B + b] = x_lens_host[b];
-    plen[b] = prompt_lens_host[b];
-  }
-  IDX_HIP(hipMemcpyAsync(w.lens2, lens2.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(w.plen, plen.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));
-  if (gemm(temb0, t_emb, 256, w.tmp_steps, D, 1, st, ACT_SILU) || gemm(temb2, w.tmp_steps, D, w.t1, D, 1, st)) return 1;
-  if (gemm(mod_all, w.t1, D, w.mods, (2 * depth + 1) * 2 * D, 1, st)) return 1;
-  if (silu_rows(w.t1s, w.t1, (size_t)D, st) || gemm(final_mod, w.t1s, Wh, w.fmod, 2 * Wh, 1, st)) return 1;
-  if (gemm(t2emb0, t_emb, 256, w.tmp_steps, Wh, 1, st, ACT_SILU) || gemm(t2emb2, w.tmp_steps, Wh, w.t2, Wh, 1, st)) return 1;
-  if (gemm(wn_cond, w.t2, Wh, w.wnb, L * 2 * Wh, 1, st)) return 1;
-  if (gemm(cond_proj, mu, cfg.content_dim, w.condp, D, B * T, st)) return 1;
+  const int C = cfg.in_channels;
+  CfmBuffers w = carve_cfm(cfg, ffn, ws, B, T, 1);
+  if (upload_lens(*this, w, x_lens_host, prompt_lens_host, Tp_max, B, T, false, st)) return 1;
+  if (step_constants(*this, w, t_emb, 1, st)) return 1;
+  if (gemm(cond_proj, mu, cfg.content_dim, w.condp, cfg.hidden_dim, B * T, st)) return 1;
   IDX_HIP(hipMemcpyAsync(w.xstate, x, (size_t)B * C * T * sizeof(float), hipMemcpyDeviceToDevice, st));
-  CfmPackArgs pk;
-  pk.x_in = w.x_in; pk.ld = 2 * C + D + cfg.style_dim; pk.x = w.xstate; pk.prompt = prompt; pk.prompt_len = w.plen;
-  pk.cond = w.condp; pk.cond_null = cond_proj.bias; pk.style = style;
-  pk.B = B; pk.T = T; pk.C = C; pk.D = D; pk.S = cfg.style_dim; pk.Tp_max = Tp_max;
-  if (cfm_pack(pk, st)) return 1;
+  if (cfm_pack(pack_args(*this, w, prompt, style, B, T, Tp_max), st)) return 1;
   {
-    CfmBuffers v0 = half_view(*this, w, 0, B, T);      // the conditional half alone
+    CfmBuffers v0 = half_view(cfg, ffn, w, 0, B, T);      // the conditional half alone
     if (dit_eval(*this, v0, B, T, 0, st, nullptr)) return 1;
   }
   IDX_HIP(hipMemcpyAsync(out_tm, w.vout, (size_t)B * T * C * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -763,6 +718,13 @@ static CondBuffers carve_cond(const S2MelModel& m, void* ws, int B, int M, int T
 
 size_t S2MelModel::cond_workspace_bytes(int B, int M, int Tg) const { return carve_cond(*this, nullptr, B, M, Tg).bytes; }
 
+// torch's 'nearest' source row for the tb target frames of one sequence of mb rows that start at row0:
+// F.interpolate(mode='nearest'): src = min(floor(dst * (float)in / out), in - 1), float32 arithmetic
+static void nearest_rows(int* idx, int row0, int mb, int tb) {
+  const float scale = (float)mb / (float)tb;
+  for (int j = 0; j < tb; ++j) idx[j] = row0 + std::min((int)std::floor((float)j * scale), mb - 1);
+}
+
 int S2MelModel::prepare_cond(const float* latent, const long long* codes, const int* code_lens_host, const int* target_lens_host,
                              int B, int M, int Tg, float* cond_out, void* ws, size_t ws_bytes, hipStream_t st) {
   IDX_CHECK(latent && codes && code_lens_host && target_lens_host && cond_out, "null pointer");
@@ -785,9 +747,7 @@ int S2MelModel::prepare_cond(const float* latent, const long long* codes, const 
       ic[(size_t)b * M + i] = i < mb ? (int)cde : -1;
       ir[(size_t)b * M + i] = i < mb ? b * M + i : -1;
     }
-    // F.interpolate(mode='nearest'): src = min(floor(dst * (float)in / out), in - 1), float32 arithmetic
-    const float scale = (float)mb / (float)tb;
-    for (int j = 0; j < tb; ++j) ii[(size_t)b * Tg + j] = b * M + std::min((int)std::floor((float)j * scale), mb - 1);
+    nearest_rows(&ii[(size_t)b * Tg], b * M, mb, tb);
   }
   IDX_HIP(hipMemcpyAsync(w.idx_code, ic.data(), ic.size() * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(w.idx_row, ir.data(), ir.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -842,8 +802,7 @@ int S2MelModel::regulate(const float* S, const int* in_lens_host, const int* tar
     const int mb = in_lens_host[b], tb = target_lens_host[b];
     IDX_CHECK(mb > 0 && mb <= M && tb > 0 && tb <= Tg, "in_lens / target_lens out of range");
     tl[b] = tb;
-    const float scale = (float)mb / (float)tb;      // F.interpolate(mode='nearest'), float32 arithmetic
-    for (int j = 0; j < tb; ++j) ii[(size_t)b * Tg + j] = b * M + std::min((int)std::floor((float)j * scale), mb - 1);
+    nearest_rows(&ii[(size_t)b * Tg], b * M, mb, tb);
   }
   IDX_HIP(hipMemcpyAsync(w.idx_interp, ii.data(), ii.size() * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(w.tlen, tl.data(), B * sizeof(int), hipMemcpyHostToDevice, st));

@@ -1,10 +1,14 @@
 """Cases of tests/test_s2mel_dispatch_gpu.py and tests/test_s2mel_dispatch_cpu.py: shapes at which the CFM solver
 (index-tts_amd/csrc/s2mel.hip::dit_eval) switches kernel families, their synthetic inputs and the oracle calls both files share.
 
-dit_eval picks its kernels from three numbers (N2 = 2B rows stacked, B per half with idxtts_s2mel_set_overlap(1)):
-  M  = N2 * T            split-bf16 mode and M >= 256: producers hand bf16 hi/lo planes on, attention is flash_attn_planes_kernel
-  t0 = pmin - halo       when >= 64 (else 0): last block after K/V, long skip, WaveNet and final layer on rows [N2][T - t0]
-  Mt = N2 * (T - t0)     the 256-row test again on the compacted rows; M >= 256 > Mt hands planes over to fp32 rows in the last block
+dit_eval runs on two row sets (s2mel.hip: RowSet, built by row_set; N2 = 2B sequences stacked, B per half with
+idxtts_s2mel_set_overlap(1)) and picks its kernels from three numbers:
+  M  = N2 * T            all frames.  Split-bf16 mode and M >= 256: RowSet::planes, producers hand bf16 hi/lo planes on, attention
+                         is flash_attn_planes_kernel
+  t0 = pmin - halo       when >= 64 (else 0, and the tail is the set of all frames): the last block (dit_block) behind K/V, long
+                         skip, WaveNet and final layer run on the tail rows [N2][T - t0]
+  Mt = N2 * (T - t0)     the tail.  The 256-row test again on the compacted rows; M >= 256 > Mt hands planes over to fp32 rows in
+                         the last block
 S2MelConfig.tiny(): 3 WaveNet layers of kernel 5, dilation rate 1 -> halo = 6, tail compaction from a 70-frame prompt on."""
 import numpy as np
 import torch
@@ -55,6 +59,36 @@ ESTIMATOR_PROMPT = 20
 ESTIMATOR_TIME = 0.35
 
 
+# Launches per call of the families a path shows in (the launch profile of every case, as the library's event profile counts
+# them; tests/test_s2mel_dispatch_gpu.py asserts them exactly).  Columns: LAUNCH_FAMILIES.  tn = the exact fp32 GEMM, v2 = the
+# LDS-DMA split-bf16 GEMM, x3 = the split-bf16 tile GEMM (shapes v2 does not take: the merge GEMM's K = 184, conv2's 16 columns).
+LAUNCH_FAMILIES = ("gemm_tn_kernel", "gemm_bf16x3_v2_kernel", "gemm_bf16x3_kernel", "flash_attn_planes_kernel", "flash_attn_bf16x3_kernel",
+                   "flash_attn_f32_kernel", "gather_tail_rows_kernel", "rows_norm_kernel", "rotary_qk_kernel")
+_F32_SOLVE, _F32_SOLVE_TAIL, _F32_EST = (125, 0, 0, 0, 0, 15, 0, 36, 15), (125, 0, 0, 0, 0, 15, 6, 36, 15), (47, 0, 0, 0, 0, 5, 0, 12, 5)
+LAUNCHES = {
+    "f32": {**{("solver", n): _F32_SOLVE for n in (1, 2, 3, 4)}, **{("solver", n): _F32_SOLVE_TAIL for n in range(5, 13)},
+            ("rows", 1): _F32_SOLVE_TAIL, ("rows", 2): _F32_SOLVE_TAIL, ("estimator", 127): _F32_EST, ("estimator", 128): _F32_EST},
+    "bf16x3": {                       #  tn   v2  x3  planes  bf16x3  f32  gather  norm  rotary
+        ("solver", 1):                 (125,   0,  0,      0,     15,   0,      0,   36,     15),      # rows, no tail
+        ("solver", 2):                 (  8, 111,  6,     15,      0,   0,      0,   36,      0),      # planes, two full 128-row tiles
+        ("solver", 3):                 (  8, 111,  6,     15,      0,   0,      0,   36,      0),      # planes, 2-row last tile
+        ("solver", 4):                 (  8, 111,  6,     15,      0,   0,      0,   36,      0),      # pmin - halo = 63: no tail
+        ("solver", 5):                 (  8, 111,  6,     15,      0,   0,      6,   36,      0),      # planes tail
+        ("solver", 6):                 (  8, 111,  6,     15,      0,   0,      6,   36,      0),      # planes tail, odd offset
+        ("solver", 7):                 ( 59,  63,  3,     15,      0,   0,      6,   36,      0),      # planes, then rows
+        ("solver", 8):                 (  7, 112,  6,     15,      0,   0,      6,   36,      0),      # planes tail at its floor
+        ("solver", 9):                 ( 58,  64,  3,     15,      0,   0,      6,   36,      0),      # planes, then rows
+        ("solver", 10):                (125,   0,  0,      0,     15,   0,      6,   36,     15),      # rows, rows tail
+        ("solver", 11):                (  7, 112,  6,     15,      0,   0,      6,   36,      0),      # ragged, planes tail
+        ("solver", 12):                ( 58,  64,  3,     15,      0,   0,      6,   36,      0),      # ragged, planes, then rows
+        ("rows", 1):                   (  7, 112,  6,     15,      0,   0,      6,   36,      0),      # planes tail
+        ("rows", 2):                   ( 58,  64,  3,     15,      0,   0,      6,   36,      0),      # planes, then rows
+        ("estimator", 127):            ( 47,   0,  0,      0,      5,   0,      0,   12,      5),      # one evaluation of B = 2 sequences
+        ("estimator", 128):            (  7,  38,  2,      5,      0,   0,      0,   12,      0),
+    },
+}
+
+
 def config():
     return S2MelConfig.tiny()
 
@@ -68,7 +102,7 @@ def halo(cfg) -> int:
 
 
 def tail_t0(cfg, plens) -> int:
-    """S2MelModel::cfm_solve's rule."""
+    """The solver's rule (s2mel.hip: upload_lens, called by S2MelModel::cfm_solve)."""
     cut = min(plens) - halo(cfg)
     return cut if cut >= 64 else 0
 

@@ -12,8 +12,12 @@ gemm_bf16x3_v2_kernel, the LDS-DMA GEMM; x3 = gemm_bf16x3_kernel, split-bf16 for
 conv2's 16 columns).  Attention is ONE family per call, 15 launches (5 blocks x 3 steps): the qkv planes decide it from M, also
 in the last block of a compacted tail.  rows_norm_kernel is the only norm family at D = 128 (36 launches everywhere), so the
 mixed cases show in the GEMM counts: the 17 GEMMs per evaluation that run on Mt rows (wo, w13, w2 of the last block; skip_linear
-x 2, conv1; 8 in the WaveNet; res_projection, final linear, conv2) move to tn, 51 over 3 steps.  In GEMM_F32 mode every case is
-125 tn, 15 flash_attn_f32_kernel, 15 rotary_qk_kernel, no other GEMM or attention family.
+x 2, conv1; 8 in the WaveNet; res_projection, final linear, conv2) move to tn, 51 over 3 steps.  In GEMM_F32 mode every solver
+and cfm_rows case is 125 tn, 15 flash_attn_f32_kernel, 15 rotary_qk_kernel, 36 rows_norm_kernel (one estimator evaluation: 47 /
+5 / 5 / 12), no other GEMM or attention family.  rotary_qk_kernel runs wherever the qkv projection is not on the LDS-DMA GEMM
+(15 launches in cases 1 and 10, 5 at estimator 127), nowhere else in GEMM_BF16X3 mode.  The table below is
+s2mel_dispatch_cases.LAUNCHES as text; _check_signature asserts the counts of both modes exactly.  In the library's terms
+(s2mel.hip): M and Mt are the rows of dit_eval's two RowSets, all frames and the tail; "planes" is RowSet::planes.
 
   case            M    t0   Mt  attention        tn   v2  x3  gather_tail_rows  path
   solver 1      254     0  254  bf16x3 (rows)   125    -   -   -                rows, no tail
@@ -61,7 +65,7 @@ beside what the library measured against the float64 oracle on an MI355X (max |d
 The reference's noise is at most 6 % of the fp32 max bound (14 % of the mean bound), nowhere near a quarter of it.
 
 What the bounds catch (tests/test_s2mel_dispatch_cpu.py): a tail cut one frame late misses the oracle by 1.1e-3 .. 3.9e-3 in these
-cases -- 3.7 .. 12.9 x the fp32 max bound, mostly INSIDE the split-bf16 one.  With cfm_solve's tail_t0 moved one frame on purpose,
+cases -- 3.7 .. 12.9 x the fp32 max bound, mostly INSIDE the split-bf16 one.  With the solver's tail_t0 moved one frame on purpose,
 every tail case here failed its GEMM_F32 leg and only cases 5, 8 and 9 their GEMM_BF16X3 leg.
 """
 import types
@@ -149,10 +153,12 @@ def _check_solver_rows(what, out, ref, valid, mode):
         assert emax <= max_bound and emean <= mean_bound, (what, mode, b, emax, emean)
 
 
-def _check_signature(what, prof, mode, geo, evals, depth):
-    """The launch families of one call against the path (M, t0, Mt) names: a later change of a threshold turns the case red."""
+def _check_signature(what, prof, mode, geo, evals, depth, case):
+    """The launch families of one call against the path (M, t0, Mt) names, and their launch counts against dc.LAUNCHES[mode][case]
+    exactly: a later change of a threshold, or a launch that moves from one row set to the other, turns the case red."""
     M, t0, Mt = geo
     print(f"{what} {mode}: M = {M}, t0 = {t0}, Mt = {Mt}:", dict(sorted(prof.items())))
+    assert tuple(prof.get(k, 0) for k in dc.LAUNCH_FAMILIES) == dc.LAUNCHES[mode][case], (what, mode, prof)
     planes = mode == "bf16x3" and M >= 256
     assert ("gather_tail_rows_kernel" in prof) == (t0 > 0), (what, mode, prof)
     assert ("flash_attn_planes_kernel" in prof) == planes and ("gemm_bf16x3_v2_kernel" in prof) == planes, (what, mode, prof)
@@ -191,7 +197,7 @@ def test_solver_switch_points_vs_float64_oracle(model, num, mode):
     assert geo == dc.SOLVER_GEOMETRY[num]
     out, prof = _run_solver(m, num, mode)
     assert out.shape == (len(lens), m.cfg.in_channels, max(lens)) and torch.isfinite(out).all()
-    _check_signature(f"solver {num}", prof, mode, geo, dc.STEPS, m.cfg.depth)
+    _check_signature(f"solver {num}", prof, mode, geo, dc.STEPS, m.cfg.depth, ("solver", num))
     if mode == "bf16x3" and num in dc.MIXED_NEIGHBOUR:
         nb = dc.MIXED_NEIGHBOUR[num]
         _check_mixed(f"solver {num}", prof, _run_solver(m, nb, mode)[1], dc.STEPS, _tail_gemms(m.cfg))
@@ -236,7 +242,7 @@ def test_cfm_rows_switch_points_vs_float64_oracle(model, num, mode):
     assert geo == dc.ROWS_GEOMETRY[num]
     out, prof = _run_rows(m, num, mode)
     assert out.shape == (len(plens), m.cfg.in_channels, max(glens)) and torch.isfinite(out).all()
-    _check_signature(f"cfm_rows {num}", prof, mode, geo, dc.STEPS, m.cfg.depth)
+    _check_signature(f"cfm_rows {num}", prof, mode, geo, dc.STEPS, m.cfg.depth, ("rows", num))
     assert prof.get("cfm_rows_pack_kernel") == 1 and prof.get("cfm_rows_emit_kernel") == 1
     if mode == "bf16x3" and num == 2:
         _check_mixed("cfm_rows 2", prof, _run_rows(m, 1, mode)[1], dc.STEPS, _tail_gemms(m.cfg))
@@ -258,7 +264,7 @@ def test_estimator_switch_point_vs_float64_oracle(model, T, mode):
     out, prof = _call(mode, lambda: m.sm.estimator(x, px, lens, torch.full((2,), dc.ESTIMATOR_TIME), style, mu,
                                                    prompt_lens=[dc.ESTIMATOR_PROMPT] * 2))
     assert out.shape == x.shape
-    _check_signature(f"estimator T = {T}", prof, mode, (2 * T, 0, 2 * T), 1, m.cfg.depth)
+    _check_signature(f"estimator T = {T}", prof, mode, (2 * T, 0, 2 * T), 1, m.cfg.depth, ("estimator", T))
     if ("est", T) not in m.refs:
         m.refs["est", T] = dc.estimator_oracle_rows(m.tw64, m.cfg, inputs, torch.float64)
     ref = m.refs["est", T]
