@@ -87,8 +87,10 @@ int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_
 // clamp_min(q, 1e-10), argmax; no penalty, no top-k / top-p.
 enum SampleMode { SAMPLE_HF = 1, SAMPLE_ACCEL = 2 };
 // The Exp(1) draw of element `idx` of a generation: the caller's tensor when it supplied one (reproduces torch's stream), else a
-// counter-based generator -- splitmix64 of (seed, idx) -> u in (0, 1), 24 bits, never 0 or 1 -> -log(u) -- so that default calls need no
-// [steps][B][V] noise tensor (0.8 GB for 16 utterances x 1500 steps; 2.4 GB with 3 beams).
+// counter-based generator -- splitmix64 of (seed, idx + 1) -> its top 24 bits h -> u = (h + 0.5) / 2^24 in fp32, at most 1 - 2^-24 ->
+// -log(u) -- so that default calls need no [steps][B][V] noise tensor (0.8 GB for 16 utterances x 1500 steps; 2.4 GB with 3 beams).
+// From h = 2^23 on, h + 0.5 is no fp32 number and rounds to the even neighbour, which for h = 2^24 - 1 is 2^24: u = 1, a draw of
+// 0 and that id taken whatever its probability, hence the upper bound (tests/sampler_cases.py restates all of this).
 __host__ __device__ static inline float exp1_draw(const float* noise, unsigned long long seed, size_t idx) {
   if (noise) return noise[idx];
   unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(idx + 1);
@@ -97,7 +99,7 @@ __host__ __device__ static inline float exp1_draw(const float* noise, unsigned l
   z = z ^ (z >> 31);
   // the open interval: u = 1 would make the draw 0 and probs / q infinite (or 0 / 0 for a filtered token) -- torch's exponential_
   // never returns 0 either
-  const float u = ((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);
+  const float u = fminf(((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   return -logf(u);
 }
 struct SampleWarpArgs {

@@ -495,7 +495,11 @@ int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_
 // -------------------------------------------------------------------------------------------------
 // multinomial sampling with the HF warpers / the accel-engine sampler (SampleWarpArgs, decode.h)
 constexpr int SW_NPT = 16;          // vocabulary entries per thread: V <= 16384
-constexpr int SW_CAP = 2048;        // survivors of the top-k filter handled by the top-p stage (more only on massive ties)
+// Survivors of the top-k filter that the top-p stage (top_p < 1 only) can sort.  Its callers require 0 < top_k <= 1024 there, so the
+// survivors are top_k plus the other entries equal to the k-th largest score: more than SW_CAP only when over SW_CAP - top_k + 1
+// scores tie exactly at the threshold, and then the ones that arrive after the first SW_CAP are dropped (HF's own sort leaves the
+// order inside such a group unspecified too).  Without top-p nothing is staged and nothing is capped.
+constexpr int SW_CAP = 2048;
 
 // Row b of the warped sampler (parts = 1; the penalty in HF mode only): the token, valid in every thread.  The draw for id v is
 // exp1_draw(noise, seed, nbase + v).  rv / ri: [16], sval / sidx / sorted_v / sorted_i: [SW_CAP] of shared scratch.
@@ -523,9 +527,30 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
     sc[u] = l;
   }
 
+  // ---- top-k (HF): the k-th largest value (with multiplicity) by k rounds of block-wide max extraction; everything strictly below
+  //      it becomes -inf, ties at the threshold stay ----
+  if (mode == SAMPLE_HF && top_k > 0 && top_k < V) {
+    unsigned taken = 0;
+    float kth = -INFINITY;
+    for (int r = 0; r < top_k; ++r) {
+      float mx = -INFINITY; int mi = 0x7fffffff;
+#pragma unroll
+      for (int u = 0; u < SW_NPT; ++u) {
+        const int v = tid + 1024 * u;
+        if (v < V && !((taken >> u) & 1u) && (sc[u] > mx || (sc[u] == mx && v < mi))) { mx = sc[u]; mi = v; }
+      }
+      block_argmax<16>(mx, mi, rv, ri, tid);
+      kth = mx;
+      if ((mi & 1023) == tid && mi < V) taken |= 1u << (mi >> 10);
+    }
+#pragma unroll
+    for (int u = 0; u < SW_NPT; ++u) if (sc[u] < kth) sc[u] = -INFINITY;
+  }
+
   int token;
-  if (mode == SAMPLE_ACCEL || (top_k == 0 && top_p >= 1.0f)) {
-    // softmax over the whole row, divided by the (accel sampler: clamped) noise, argmax
+  if (mode == SAMPLE_ACCEL || top_p >= 1.0f) {
+    // no top-p, so nothing needs sorting: softmax over the row as it stands in the registers (a filtered entry is -inf and weighs 0,
+    // whatever top_k is and however many entries tie at its threshold), divided by the (accel sampler: clamped) noise, argmax
     const float qmin = mode == SAMPLE_ACCEL ? 1e-10f : 0.0f;
     float mx = -INFINITY; int mi = 0;
 #pragma unroll
@@ -547,25 +572,9 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
     block_argmax<16>(best, bi, rv, ri, tid);
     token = bi;
   } else {
-    // ---- top-k: the k-th largest value (with multiplicity) by k rounds of block-wide max extraction ----
-    if (top_k > 0 && top_k < V) {
-      unsigned taken = 0;
-      float kth = -INFINITY;
-      for (int r = 0; r < top_k; ++r) {
-        float mx = -INFINITY; int mi = 0x7fffffff;
-#pragma unroll
-        for (int u = 0; u < SW_NPT; ++u) {
-          const int v = tid + 1024 * u;
-          if (v < V && !((taken >> u) & 1u) && (sc[u] > mx || (sc[u] == mx && v < mi))) { mx = sc[u]; mi = v; }
-        }
-        block_argmax<16>(mx, mi, rv, ri, tid);
-        kth = mx;
-        if ((mi & 1023) == tid && mi < V) taken |= 1u << (mi >> 10);
-      }
-#pragma unroll
-      for (int u = 0; u < SW_NPT; ++u) if (sc[u] < kth) sc[u] = -INFINITY;
-    }
-    // ---- survivors -> LDS (finite scores only: -inf has probability 0 and sorts first) ----
+    // ---- top-p: survivors of the top-k filter -> LDS (finite scores only: -inf has probability 0 and sorts first).  Survivor
+    //      number SW_CAP and later (in arrival order) is dropped; the host rule for top_p < 1, 0 < top_k <= 1024 (check_sampling),
+    //      leaves that to a tie group of more than SW_CAP - top_k + 1 entries at the top-k threshold ----
     if (tid == 0) s_count = 0;
     __syncthreads();
 #pragma unroll
