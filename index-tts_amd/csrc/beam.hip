@@ -18,7 +18,10 @@ namespace idxtts {
 namespace {
 
 constexpr int NPT = 16;          // vocabulary entries per thread of a 1024-thread block: V <= 16384
-constexpr int CAP = 2048;        // survivors of the top-k filter handled by the top-p stage
+// Survivors of the top-k filter that the top-p stage can sort.  check_beam requires 0 < top_k <= 1024 with top_p < 1, so more survive
+// only when more than CAP - top_k + 1 scores tie exactly at the top-k threshold; that group is one value in index order and needs no
+// sorting: it is then walked by count, and only the (fewer than top_k) scores above the threshold are staged.
+constexpr int CAP = 2048;
 constexpr int SEL_EPT = 32;      // beam_select: candidates per thread kept in registers (nb * V <= 32768), else the re-reading loop
 
 }  // namespace
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
   __shared__ int sidx[CAP];
   __shared__ float sorted_v[CAP];
   __shared__ int sorted_i[CAP];
-  __shared__ int s_count, s_thr_i, s_digit, s_kk;
+  __shared__ int s_count, s_thr_i, s_digit, s_kk, s_tie_skip;
   __shared__ int hist[16][256];
   __shared__ float s_thr_v;
   const int tid = threadIdx.x, V = p.V;
@@ -77,6 +80,7 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
   }
   if (do_sample && (top_k > 0 || top_p < 1.0f)) {
     const int k = top_k > 0 ? max(top_k, 2) : 0;         // TopKLogitsWarper: max(top_k, min_tokens_to_keep)
+    float kth = -INFINITY;
     if (k > 0 && k < V) {
       // the k-th largest score by a radix select over order-preserving 32-bit keys (four 8-bit digits, high to low): per-wave
       // histograms in LDS, one wave walks the 256 bins from the top -- 16 barriers in all instead of 2 k block-wide argmax rounds
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
         kk = s_kk;
       }
       const unsigned kb = (prefix & 0x80000000u) ? (prefix & 0x7fffffffu) : ~prefix;
-      const float kth = __uint_as_float(kb);
+      kth = __uint_as_float(kb);
 #pragma unroll
       for (int u = 0; u < NPT; ++u) if (sc[u] < kth) sc[u] = -INFINITY;
     }
@@ -145,7 +149,23 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
         }
       }
       __syncthreads();
-      const int n = min(s_count, CAP);
+      const int total = s_count;
+      int n = total, m = 0;      // n staged entries; m entries of the tie group at the threshold, counted instead
+      if (total > CAP) {         // (block-uniform) only the scores above the threshold are staged: fewer than k <= 1024
+        __syncthreads();
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) {
+          const int v = tid + 1024 * u;
+          if (v < V && sc[u] > kth) {
+            const int slot = atomicAdd(&s_count, 1);
+            if (slot < CAP) { sval[slot] = sc[u]; sidx[slot] = v; }
+          }
+        }
+        __syncthreads();
+        n = min(s_count, CAP); m = total - s_count;
+      }
       for (int e = tid; e < n; e += 1024) {        // rank sort, ascending by (value, index)
         const float ve = sval[e]; const int ie = sidx[e];
         int rank = 0;
@@ -154,19 +174,46 @@ __global__ __launch_bounds__(1024) void beam_scores_kernel(const BeamState p) {
       }
       __syncthreads();
       if (tid == 0) {      // TopPLogitsWarper, min_tokens_to_keep = 2: remove while cum <= 1 - top_p, never the last two
+        // ascending order: the m tied entries by index, then the n staged ones
+        const int N = n + m;
         int keep_from = 0;
-        const float top = sorted_v[n - 1];
-        float tot = 0.f;
+        const float top = n > 0 ? sorted_v[n - 1] : kth;
+        const float pt = m > 0 ? expf(kth - top) : 0.f;
+        float tot = (float)m * pt;
         for (int e = 0; e < n; ++e) tot += expf(sorted_v[e] - top);
         const float thr = (float)(1.0 - (double)top_p);
         float cum = 0.f;
-        for (int e = 0; e < n - 2; ++e) {
-          cum += expf(sorted_v[e] - top) / tot;
-          if (cum <= thr) keep_from = e + 1; else break;
+        if (m > 0) {       // j tied entries sum to j * pt / tot: the largest j with that at or below thr
+          const float each = pt / tot;
+          int j = min((int)fminf(thr / each, (float)m), min(m, N - 2));
+          while (j < min(m, N - 2) && (float)(j + 1) * each <= thr) ++j;
+          while (j > 0 && (float)j * each > thr) --j;
+          keep_from = j; cum = (float)j * each;
         }
-        s_thr_v = sorted_v[keep_from]; s_thr_i = sorted_i[keep_from];
+        if (keep_from == m) {
+          for (int e = m; e < N - 2; ++e) {
+            cum += expf(sorted_v[e - m] - top) / tot;
+            if (cum <= thr) keep_from = e + 1; else break;
+          }
+        }
+        if (keep_from < m) { s_thr_v = kth; s_thr_i = 0; s_tie_skip = keep_from; }
+        else { s_thr_v = sorted_v[keep_from - m]; s_thr_i = sorted_i[keep_from - m]; s_tie_skip = -1; }
       }
       __syncthreads();
+      if (s_tie_skip > 0) {      // (block-uniform) the index below which exactly s_tie_skip tied entries lie: bisection on the count
+        const int want = s_tie_skip;
+        int lo = 0, hi = V;        // the count below lo is < want, the count below hi is >= want
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          float c = 0.f;
+#pragma unroll
+          for (int u = 0; u < NPT; ++u) c += (sc[u] == kth && tid + 1024 * u < mid) ? 1.f : 0.f;
+          if (block_sum<16>(c, rv) >= (float)want) hi = mid; else lo = mid;
+        }
+        __syncthreads();
+        if (tid == 0) s_thr_i = hi;
+        __syncthreads();
+      }
 #pragma unroll
       for (int u = 0; u < NPT; ++u) {
         const int v = tid + 1024 * u;
@@ -235,7 +282,9 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
   const float* base = p.proc + (size_t)b * N;
   const int n_keep = 2 * nb;
   // multinomial without replacement = the n_keep largest probs / q (ATen: q ~ Exp(1) once per element, then topk); plain
-  // top-k of the scores when not sampling.  Ties (only among zero-probability fillers) go to the smaller index.
+  // top-k of the scores when not sampling.  Equal keys go to the smaller flat index: the zero-probability fillers of a step with fewer
+  // than n_keep survivors, and in beam search the bit-equal scores of beams that hold the same tokens in another order ([a, b] and
+  // [b, a] at step 2) -- that rule and the stable sort below decide which of them becomes which beam.
   if (N <= 1024 * SEL_EPT) {
     // every element's key is computed ONCE and stays in registers (the exponential, the division and the draw are the cost of a
     // round); a round is then a masked scan of SEL_EPT registers and one block-wide argmax

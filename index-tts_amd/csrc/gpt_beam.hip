@@ -83,8 +83,9 @@ BeamState GPTModel::beam_state(const Buffers& w, const BeamBuffers& bb, int B, i
 static int check_beam(const idxtts_beam& r) {
   IDX_CHECK(!r.do_sample || (r.temperature > 0.0f && r.top_k >= 0 && r.top_k <= 1024 && r.top_p > 0.0f),
             "beam-sample needs a positive temperature, top_k <= 1024 and top_p > 0");
-  // the nucleus is cut inside the top-k survivors (beam_scores_kernel stages at most 2048 of them): without a top-k the whole
-  // vocabulary would survive and the threshold would come from whichever 2048 entries arrived first
+  // the nucleus is cut inside the top-k survivors: beam_scores_kernel sorts at most 2048 of them, and with 0 < top_k <= 1024 more
+  // survive only as one group of equal scores at the top-k threshold, which it walks by count.  Without a top-k the whole vocabulary
+  // would survive unsorted, so that combination is refused; top_p >= 1 needs no sorting and takes any top_k <= 1024, 0 included.
   IDX_CHECK(!r.do_sample || r.top_p >= 1.0f || (r.top_k > 0 && r.top_k <= 1024), "top-p needs 0 < top_k <= 1024");
   IDX_CHECK(r.early_stopping == 0 || r.early_stopping == 1, "early_stopping must be 0 (False) or 1 (True)");
   return 0;

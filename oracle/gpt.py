@@ -183,7 +183,7 @@ def warp_scores(scores: torch.Tensor, temperature: float, top_k: int, top_p: flo
         kth = torch.topk(scores, k)[0][..., -1, None]
         scores = scores.masked_fill(scores < kth, float("-inf"))
     if top_p is not None and top_p < 1.0:
-        sorted_logits, sorted_indices = torch.sort(scores, descending=False)
+        sorted_logits, sorted_indices = torch.sort(scores, descending=False, stable=True)      # equal scores: ascending by index
         cumulative = sorted_logits.softmax(dim=-1).cumsum(dim=-1)
         remove = cumulative <= (1 - top_p)
         remove[..., -min_tokens_to_keep:] = False
@@ -271,7 +271,8 @@ def generate_beam(w, cfg, conds: torch.Tensor, text_inputs: torch.Tensor, max_ne
       warpers with min_tokens_to_keep = 2 (1022-1029); + running beam scores (first beam 0, the others -1e9: 3420-3422);
       2 * num_beams candidates over the num_beams * V flattened scores -- `torch.multinomial` without replacement
       (3509-3510: ATen draws q ~ Exp(1) ONCE for the [B, num_beams * V] tensor and takes topk(probs / q), so the draw is the
-      explicit input exp_noise[step]) re-sorted by score (3511-3513), or plain top-k when do_sample=False (3517-3519);
+      explicit input exp_noise[step]) re-sorted by score (3511-3513), or plain top-k when do_sample=False (3517-3519); equal keys
+      and equal scores, whose order torch leaves open, go to the lower flat index (the library's rule);
       BeamSearchScorer.process / finalize (transformers_beam_search.py:215-318, 320-414) with BeamHypotheses above; the KV
       cache re-indexed by beam_idx every step (`_reorder_cache`, model_v2.py:227-240).
     Returns codes [B, n] (best hypothesis per utterance, eos appended when it fits, stop-token padded)."""
@@ -310,13 +311,16 @@ def generate_beam(w, cfg, conds: torch.Tensor, text_inputs: torch.Tensor, max_ne
         if do_sample:
             probs = F.softmax(scores, dim=-1)
             key = probs / exp_noise[step].float()
-            cand = torch.topk(key, n_keep, dim=-1)[1]       # == torch.multinomial(probs, n_keep)
+            # == torch.multinomial(probs, n_keep), whose topk leaves the order of equal keys open; pinned here: the lower flat index
+            # first (stable sorts) -- the zero keys that fill up a step with fewer than n_keep survivors, and equal scores below
+            cand = torch.sort(key, dim=-1, descending=True, stable=True)[1][:, :n_keep]
             cand_scores = torch.gather(scores, -1, cand)
-            cand_scores, order = torch.sort(cand_scores, descending=True, dim=1)
+            cand_scores, order = torch.sort(cand_scores, descending=True, dim=1, stable=True)
             cand = torch.gather(cand, -1, order)
         else:
             key = scores
-            cand_scores, cand = torch.topk(scores, n_keep, dim=1, largest=True, sorted=True)
+            cand_scores, cand = torch.sort(scores, dim=1, descending=True, stable=True)
+            cand_scores, cand = cand_scores[:, :n_keep], cand[:, :n_keep]
         if return_trace:
             # how close this step's decisions are: the smallest gap between neighbours among the best n_keep + 1 selection keys (who is
             # drawn), relative for the sampling key probs / q, and among the drawn candidates' scores (their order = the beams' order)
