@@ -131,10 +131,24 @@ int idxtts_get_decode_geometry(void);
  * for up to 64 rows -- the accel engine's one-graph-for-all-rows batching, accel/accel_engine.py:221-310) instead of the fp32-MFMA
  * GEMV.  Default 17: two or more 16-row tiles (merged requests, 16 utterances x 3 beams: 7 % faster at 48 rows); at <= 16 rows the
  * fp32-MFMA GEMV's single-round-trip launches win by 8 %.  5..64 selects a threshold, 65 turns the plane path off, 0 restores the
- * default.  Rows of 17..64-row decodes do not depend on the batch they are in; the two kernel families differ in summation order
+ * default.  A shape the plane GEMV has no kernel for (49..64 rows of a compact model wider than d = 1280, idxtts_gemv_pl_plan_query)
+ * stays on the fp32-MFMA GEMV.  Rows of 17..64-row decodes do not depend on the batch they are in; the two kernel families differ in summation order
  * (last bits), so choose once per process, before generating (cached decode graphs carry the choice). */
 int idxtts_set_decode_plane_rows(int min_rows);
 int idxtts_get_decode_plane_rows(void);
+/* What the library itself would launch for one decode GEMV (host only, no GPU work: the answers of the launchers' own plan
+ * functions, for tests and diagnostics).
+ *   fx: the fp32-MFMA GEMV (csrc/gemv_fx.hip) on an [K][N] weight stream of `format` (0 fp32, 1 bf16, 2 fp8) and `rows` rows;
+ *       with_slab = the caller hands the K-split slab (mlp.c_proj in the decode step), narrow = idxtts_set_decode_geometry(1).
+ *       (mt, ntw, single, r4, narrow) and the format name the kernel instantiation; kw, cps, ksb the split of K over waves,
+ *       16-k chunks per wave and workgroups.
+ *   pl: the plane GEMV (csrc/gemv_pl.hip): column tiles per workgroup, K parts across workgroups, and whether a kernel exists
+ *       for that pair (where none does, the decode step stays on the fp32-MFMA GEMV). */
+typedef struct idxtts_gemv_fx_plan {
+  int mt, ntw, single, r4, narrow, kw, cps, ksb;
+} idxtts_gemv_fx_plan;
+int idxtts_gemv_fx_plan_query(int N, int K, int rows, int format, int with_slab, int narrow, idxtts_gemv_fx_plan* out);
+int idxtts_gemv_pl_plan_query(int N, int K, int rows, int* ct, int* kparts, int* has_kernel);
 /* The CFM solver (idxtts_s2mel_cfm) can evaluate the conditional and the null half of its stacked batch (flow_matching.py:91-103,
  * one DiT.forward on 2B rows there) as two chains of launches on two streams, the null half a few kernels behind: 9 % less time
  * for a solver that has the device to itself (one half's HBM-bound epilogues beside the other's MFMA-bound loops).  Each half is

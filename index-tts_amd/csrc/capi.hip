@@ -849,6 +849,27 @@ int idxtts_set_decode_plane_rows(int min_rows) {
 
 int idxtts_get_decode_plane_rows(void) { return get_decode_plane_rows(); }
 
+int idxtts_gemv_fx_plan_query(int N, int K, int rows, int format, int with_slab, int narrow, idxtts_gemv_fx_plan* out) {
+  API_BEGIN
+  IDX_CHECK(out && N > 0 && K > 0 && rows > 0 && rows <= 64, "N, K > 0, 1..64 rows");
+  IDX_CHECK(format == WFMT_F32 || format == WFMT_BF16 || format == WFMT_FP8, "weight format 0..2");
+  const int ksb = with_slab ? gemv_fx_ksb(N, K) : 1;
+  const FxPlan pl = gemv_fx_make_plan(N, K, rows, format, ksb, narrow != 0);
+  out->mt = pl.MT; out->ntw = pl.ntw; out->single = pl.single; out->r4 = pl.r4; out->narrow = pl.narrow;
+  out->kw = pl.kw; out->cps = pl.cps; out->ksb = ksb;
+  return 0;
+  API_END
+}
+
+int idxtts_gemv_pl_plan_query(int N, int K, int rows, int* ct, int* kparts, int* has_kernel) {
+  API_BEGIN
+  IDX_CHECK(ct && kparts && has_kernel && N > 0 && K > 0 && rows > 0 && rows <= 64, "N, K > 0, 1..64 rows");
+  gemv_pl_plan(N, K, rows, ct, kparts);
+  *has_kernel = gemv_pl_can_run(N, K, rows) ? 1 : 0;
+  return 0;
+  API_END
+}
+
 int idxtts_s2mel_set_overlap(int on) {
   set_s2mel_overlap(on);
   return 0;

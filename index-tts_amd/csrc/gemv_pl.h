@@ -33,6 +33,9 @@ struct GemvPLArgs {
 // geometry of a launch (column tiles per workgroup; K parts across workgroups) for the given shape
 void gemv_pl_plan(int N, int K, int rows, int* ct, int* kparts);
 size_t gemv_pl_slab_floats(int N, int K, int rows);
+// whether the plan of this shape names a kernel that exists: CT = 4 does not fit the LDS at 49..64 rows, and where CT = 8 would need more
+// than 32 K parts (K in 5121..10240) the plan has nothing left to launch -- the caller keeps such a decode on gemv_fx (GPTModel::use_pl)
+bool gemv_pl_can_run(int N, int K, int rows);
 void set_decode_plane_rows(int min_rows);       // include/idxtts.h::idxtts_set_decode_plane_rows
 int get_decode_plane_rows();
 void gemv_pl_set_ct_override(int ct);      // measurement hook (tools/gemv_pl_probe.hip): 0 = the plan

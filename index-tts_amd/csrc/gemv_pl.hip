@@ -442,12 +442,24 @@ static int pl_launch(const GemvPLP& p, dim3 grid, hipStream_t stream) {
   return 0;
 }
 
+// The (row tiles, column tiles per workgroup) pairs that have a kernel: every one whose LDS footprint fits a CU
+static constexpr bool pl_has_kernel(int MT, int CT) {
+  return MT >= 1 && MT <= 4 && (CT == 1 || CT == 2 || CT == 4 || CT == 8) && (CT == 8 || pl_lds_bytes(MT, CT, true) <= 159 * 1024);
+}
+
+bool gemv_pl_can_run(int N, int K, int rows) {
+  if (rows < 1 || rows > 64) return false;
+  int ct, kp;
+  gemv_pl_plan(N, K, rows, &ct, &kp);
+  return pl_has_kernel(cdiv(rows, 16), ct);
+}
+
 template <int MT, int WT>
 static int pl_launch_ct(int ct, const GemvPLP& p, dim3 grid, hipStream_t stream) {
   switch (ct) {
-    case 1: if constexpr (pl_lds_bytes(MT, 1, true) <= 159 * 1024) return pl_launch<MT, 1, WT>(p, grid, stream); break;
-    case 2: if constexpr (pl_lds_bytes(MT, 2, true) <= 159 * 1024) return pl_launch<MT, 2, WT>(p, grid, stream); break;
-    case 4: if constexpr (pl_lds_bytes(MT, 4, true) <= 159 * 1024) return pl_launch<MT, 4, WT>(p, grid, stream); break;
+    case 1: if constexpr (pl_has_kernel(MT, 1)) return pl_launch<MT, 1, WT>(p, grid, stream); break;
+    case 2: if constexpr (pl_has_kernel(MT, 2)) return pl_launch<MT, 2, WT>(p, grid, stream); break;
+    case 4: if constexpr (pl_has_kernel(MT, 4)) return pl_launch<MT, 4, WT>(p, grid, stream); break;
     case 8: return pl_launch<MT, 8, WT>(p, grid, stream);
   }
   IDX_FAIL("gemv_pl: no kernel for this geometry");

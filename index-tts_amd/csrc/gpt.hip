@@ -335,7 +335,14 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
 // The decode step runs on the plane GEMV from idxtts_set_decode_plane_rows() rows on (default 17: two or more MFMA row tiles -- merged
 // requests, 16 utterances x 3 beams).  Measured on the full-size model, 256 tokens, graph replay: 16 rows 0.328 s against 0.303 s on the
 // fp32-MFMA GEMV (its single-round-trip launches win), 32 rows 0.432 / 0.432, 48 rows 0.567 / 0.612 (profiles/README.md "Round 4").
-bool GPTModel::use_pl(int B) const { return weight_fmt != WFMT_F32 && B >= get_decode_plane_rows() && cfg.model_dim % 32 == 0 && head_p.wp; }
+// A shape whose plane plan names no kernel (49..64 rows with K in 5121..10240, a compact model wider than d = 1280: gemv_pl_can_run)
+// keeps the whole step on the fp32-MFMA GEMV, which serves every row count.
+bool GPTModel::use_pl(int B) const {
+  if (weight_fmt == WFMT_F32 || B < get_decode_plane_rows() || cfg.model_dim % 32 != 0 || !head_p.wp) return false;
+  const int d = cfg.model_dim;
+  return gemv_pl_can_run(3 * d, d, B) && gemv_pl_can_run(d, d, B) && gemv_pl_can_run(4 * d, d, B) && gemv_pl_can_run(d, 4 * d, B) &&
+         gemv_pl_can_run(cfg.number_mel_codes, d, B);
+}
 // sessions, and greedy one-shot generations: sample + next embedding + advance are ONE launch
 bool GPTModel::fused_tail(const Buffers& w) const { return w.slots || (w.samp.mode == 0 && !w.beam_tail); }
 

@@ -28,7 +28,7 @@ SYMBOLS = [
     "idxtts_gpt_session_admit_sampled", "idxtts_gpt_session_workspace_bytes_beam", "idxtts_gpt_session_init_beam",
     "idxtts_gpt_session_admit_beam",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
-    "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
+    "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
     "idxtts_gpt_graph_cache_entries", "idxtts_w2vbert_create", "idxtts_w2vbert_workspace_bytes", "idxtts_w2vbert_forward",
     "idxtts_repcodec_create", "idxtts_repcodec_workspace_bytes", "idxtts_repcodec_quantize",
@@ -398,6 +398,24 @@ def set_decode_plane_rows(min_rows: int) -> None:
 
 def get_decode_plane_rows() -> int:
     return int(load().idxtts_get_decode_plane_rows())
+
+
+class GemvFxPlanC(ctypes.Structure):          # idxtts_gemv_fx_plan (include/idxtts.h)
+    _fields_ = [(n, c_int) for n in ("mt", "ntw", "single", "r4", "narrow", "kw", "cps", "ksb")]
+
+
+def gemv_fx_plan(N: int, K: int, rows: int, fmt: int, with_slab: bool = False, narrow: bool = False) -> dict:
+    """The launch plan of the fp32-MFMA decode GEMV for this shape (host only): mt, ntw, single, r4, narrow, kw, cps, ksb."""
+    out = GemvFxPlanC()
+    check(load().idxtts_gemv_fx_plan_query(int(N), int(K), int(rows), int(fmt), int(bool(with_slab)), int(bool(narrow)), ctypes.byref(out)))
+    return {n: int(getattr(out, n)) for n, _ in GemvFxPlanC._fields_}
+
+
+def gemv_pl_plan(N: int, K: int, rows: int) -> dict:
+    """The launch plan of the plane decode GEMV for this shape (host only): ct, kparts, has_kernel."""
+    ct, kp, ok = c_int(), c_int(), c_int()
+    check(load().idxtts_gemv_pl_plan_query(int(N), int(K), int(rows), ctypes.byref(ct), ctypes.byref(kp), ctypes.byref(ok)))
+    return {"ct": ct.value, "kparts": kp.value, "has_kernel": bool(ok.value)}
 
 
 def set_s2mel_overlap(on: bool) -> None:

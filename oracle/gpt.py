@@ -117,7 +117,7 @@ def prepare_gpt_inputs(w, cfg, conds: torch.Tensor, text_inputs: torch.Tensor):
         mask = torch.ones(target_len + 1, dtype=torch.long)
         padding = L + 2 - ti.shape[0]
         if padding > 0:
-            parts.insert(0, torch.zeros(padding, conds.shape[-1]))
+            parts.insert(0, torch.zeros(padding, conds.shape[-1], dtype=conds.dtype))
             mask[:padding] = 0
         embs.append(torch.cat(parts))
         masks.append(mask)
@@ -136,9 +136,16 @@ def repetition_penalty(input_ids: torch.Tensor, scores: torch.Tensor, penalty: f
 
 
 def generate_greedy(w, cfg, conds: torch.Tensor, text_inputs: torch.Tensor, max_new_tokens: int,
-                    repetition_penalty_value: float = 10.0, return_logits: bool = False, kv_round: bool = False):
+                    repetition_penalty_value: float = 10.0, return_logits: bool = False, kv_round: bool = False,
+                    dtype: Optional[torch.dtype] = None):
     """inference_speech (model_v2.py:835-892) with do_sample=False, num_beams=1.
-    Returns codes [B, n_steps] (eos and post-eos pad = stop_mel_token included, as HF returns them)."""
+    Returns codes [B, n_steps] (eos and post-eos pad = stop_mel_token included, as HF returns them).
+    dtype: None = the fp32 restatement; torch.float64 evaluates the same fp32 model (weights and inputs widened exactly) with
+    every operation and the returned logits in double precision -- the reference of a kernel's fp32 rounding."""
+    out_dtype = torch.float32
+    if dtype is not None:
+        w = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(dtype) for k, v in w.items()}
+        conds, out_dtype = conds.to(dtype), dtype
     fake, inputs_embeds, attention_mask = prepare_gpt_inputs(w, cfg, conds, text_inputs)
     B, P, d = inputs_embeds.shape
     me, mp = _t(w, "mel_embedding.weight"), _t(w, "mel_pos_embedding.emb.weight")
@@ -154,7 +161,7 @@ def generate_greedy(w, cfg, conds: torch.Tensor, text_inputs: torch.Tensor, max_
             pos = attention_mask.shape[1] - P
             emb = (me[input_ids[:, -1]] + mp[pos])[:, None, :]
         hidden, past = gpt2_stack(w, cfg, emb, attention_mask, past, kv_round)
-        logits = lm_head(w, cfg, hidden[:, -1]).float()
+        logits = lm_head(w, cfg, hidden[:, -1]).to(out_dtype)
         if return_logits:
             all_logits.append(logits.clone())
         scores = repetition_penalty(input_ids, logits, repetition_penalty_value) if repetition_penalty_value != 1.0 else logits
