@@ -54,7 +54,9 @@ int idxtts_conv1d_create(const float* weight, const float* bias /* may be NULL *
                          int transposed_stride /* 1 = Conv1d, u>1 = ConvTranspose1d(k=2u, stride u, pad u/2) */,
                          idxtts_conv1d** out);
 /* y[b][co][t] = scale*(bias + sum x[..t + k*dil - pad_left..] + residual) (+ y if accumulate).
- * pad_mode: 0 zero, 1 reflect.  x: [B][Cin][T]; y/residual: [B][Cout][T*transposed_stride]. */
+ * pad_mode: 0 zero, 1 reflect.  x: [B][Cin][T]; y/residual: [B][Cout][T*transposed_stride].
+ * Follows idxtts_set_gemm_mode (split-bf16 for layers that carry the bf16 pack) and, in that mode, idxtts_set_acoustic_bf16 (one
+ * bf16 MFMA per product on w and x rounded to nearest-even bf16; bias, residual, scale and the fp32 output unchanged). */
 int idxtts_conv1d_fwd(const idxtts_conv1d* conv, const float* x, float* y, const float* residual /* may be NULL */,
                       int B, int T, int dilation, int pad_left, int pad_mode, float scale, int accumulate,
                       void* stream);
@@ -111,7 +113,10 @@ typedef struct idxtts_linear idxtts_linear;
 int idxtts_linear_create(const float* weight, const float* bias /* may be NULL */, int N, int K, int weight_is_kn,
                          idxtts_linear** out);
 int idxtts_linear_fwd(const idxtts_linear* lin, const float* x, int ldx, float* y, int ldy, const float* residual /* may be NULL */,
-                      int ldr, int M, int act, int bf16x3 /* 0: exact fp32 MFMA, 1: split-bf16 (3 bf16 MFMAs per product), 2: split-bf16 with the LDS-DMA kernel's 32x32x16 main loop */,
+                      int ldr, int M, int act, int bf16x3 /* 0: exact fp32 MFMA, 1: split-bf16 (3 bf16 MFMAs per product), 2: split-bf16 with the LDS-DMA kernel's 32x32x16 main loop,
+                                    3: bf16 -- x and w rounded to nearest-even bf16, ONE MFMA per product, fp32 accumulation in the k order of
+                                    form 1, epilogue and fp32 output unchanged: the LDS-DMA kernel's 16x16x32 loop, whatever
+                                    idxtts_set_acoustic_bf16 says; needs M >= 256, N >= 96, K % 16 == 0.  Forms 0..2 never read that switch. */,
                       void* stream);
 /* Arithmetic of the compute-bound passes of the model contexts (s2mel GEMMs and DiT attention, GPT latent pass, vocoder
  * convolutions): 0 = exact fp32 MFMA, 1 (default) = split-bf16: x*w ~= hi*hi' + hi*lo' + lo*hi' on
@@ -119,6 +124,19 @@ int idxtts_linear_fwd(const idxtts_linear* lin, const float* x, int ldx, float* 
  * reference).  The KV-cached greedy decode and its prefill are always exact fp32 (token indices are bit-exact in both modes). */
 int idxtts_set_gemm_mode(int mode);
 int idxtts_get_gemm_mode(void);
+/* Opt-in bf16 arithmetic of the acoustic stage (s2mel and BigVGAN): process-wide, default 0, effective only while the GEMM mode is 1
+ * (mode 0 stays exact).  With it on, the compute-bound kernels of those two models multiply the hi values of the split form alone --
+ * every fp32 operand rounded once to nearest-even bf16, ONE bf16 MFMA per product, fp32 accumulation in the k order of the split
+ * kernel replaced (rows stay independent of row count and tile place), epilogues and fp32 outputs unchanged:
+ *   - GEMMs of 256 rows and more on the LDS-DMA kernel whose weights run its 16x16x32 loop (s2mel, idxtts_linear_create).  Launches
+ *     below 256 rows, shapes without weight planes (N < 96 or K % 16 != 0) and the exact kernel keep their arithmetic, so results below
+ *     and above 256 rows differ by bf16 rounding (~2^-9 relative per operand), not by ~1e-5;
+ *   - the DiT attention: QK^T on bf16 q and k, P rounded once to bf16, PV on bf16 v;
+ *   - the vocoder convolutions that carry the bf16 pack (and idxtts_conv1d_fwd).
+ * The GPT (prefill, latent pass, decode), conditioning, semantic, CAMPPlus and Qwen3 contexts never read the switch: everything that
+ * feeds a choice of discrete codes is bit-identical with it on.  Measured cost and gain: profiles/README.md "Acoustic bf16". */
+int idxtts_set_acoustic_bf16(int on);
+int idxtts_get_acoustic_bf16(void);
 /* Geometry of the decode step's GEMVs (5..16 rows, bf16 / fp8 weight streams): 0 (default) = 1024-thread workgroups, the fastest form
  * for a decode that has the GPU to itself; 1 = 512-thread workgroups at <= 88 VGPRs, which fit into what ONE retiring workgroup of
  * an s2mel / vocoder kernel frees on a CU: 7 % slower alone, but a serving loop that decodes beside the acoustic stages of other
@@ -177,6 +195,13 @@ int idxtts_attention_fwd(const float* q, const float* k, const float* v, float* 
  * accumulation; relative error ~2^-16).  Used by the s2mel DiT and the GPT latent pass when the GEMM mode is
  * IDXTTS_GEMM_BF16X3; the KV-cache-building prefill always runs the exact-fp32 form above. */
 int idxtts_attention_bf16x3_fwd(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
+                         long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
+                         int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream);
+/* Same contract in bf16 (what the DiT attention runs under idxtts_set_acoustic_bf16): q, k and v rounded once to nearest-even bf16
+ * (q unscaled; the softmax scale is applied in fp32), QK^T with one bf16 MFMA per product and fp32 accumulation, fp32 softmax, P
+ * rounded once to bf16 (the denominator sums the unrounded P), PV with one MFMA per product; fp32 output.  Against float64 attention
+ * on the rounded inputs the error stays below 2^-8 max|v| + 1e-5. */
+int idxtts_attention_bf16_fwd(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
                          long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
                          int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream);
 /* Non-causal self-attention (head_dim 64) with the "relative_key" distance embedding of the w2v-bert-2.0 encoder the reference's prompt block

@@ -15,6 +15,7 @@ struct AttnArgs {
   float scale = 0.125f;
   void* o_planes = nullptr;       // split_bf16 only: write the output as split-bf16 planes over rows b*Sq + q, columns head*64 + d (o may be null)
   int split_bf16 = 0;             // 1: split-bf16 products (3 bf16 MFMAs each, ~2^-16 relative) instead of exact-fp32 MFMAs
+                                  // 2: bf16 products (q, k, v and P rounded once to nearest-even bf16, one MFMA each; no rel_key)
   // "relative_key" distance embedding (HF Wav2Vec2BertSelfAttention): scores[i][j] += scale * q_i . rel_key[clamp(j - i, -rel_left,
   // rel_right) + rel_left]; rel_key [rel_left + rel_right + 1][64] fp32, one table for every head (<= 96 rows); non-causal self-attention
   // only.  The kernel multiplies the table by its queries once per workgroup (three more 32-row "key" tiles through the same MFMAs) and
@@ -38,6 +39,7 @@ struct AttnPlanesArgs {
   float scale = 0.125f;
   float* o = nullptr; long o_bs = 0; int o_ts = 0;      // fp32 output rows (batch stride, token stride), or null
   void* o_planes = nullptr;       // and / or planes over rows b * Sq + q, columns head * 64 + d
+  int split_bf16 = 1;             // 1: three MFMAs per product; 2: the hi planes alone, P rounded once, one MFMA per product
   int nqblk = 0;                  // (set by the launcher) query blocks of 128 per (batch row, head) pair
 };
 int flash_attn_planes_forward(const AttnPlanesArgs& a, hipStream_t stream);

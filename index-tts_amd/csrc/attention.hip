@@ -19,7 +19,9 @@
 // so P never touches LDS.  Q fragments live in registers for the whole kernel (pre-scaled by 1/8).
 //
 // Three kernels share this design and the helpers below: flash_attn_f32_kernel (exact fp32 MFMAs), flash_attn_bf16x3_kernel
-// (split-bf16 MFMAs on the same fp32 inputs) and flash_attn_planes_kernel (split-bf16 planes in, LDS-DMA ring).
+// (split-bf16 MFMAs on the same fp32 inputs) and flash_attn_planes_kernel (split-bf16 planes in, LDS-DMA ring).  The two split-bf16
+// kernels also exist with one MFMA per product (split_bf16 = 2: q, k, v and P rounded once to bf16; the DiT attention under
+// idxtts_set_acoustic_bf16, idxtts_attention_bf16_fwd).  The relative_key form and the GPT's calls never take that form.
 #include <algorithm>
 
 #include "attention.h"
@@ -300,16 +302,24 @@ __device__ __forceinline__ f32x16 mfma_x3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
 }
 
-// S^T = K . Q^T from split-bf16 operands: 12 MFMAs over the four 16-d chunks.  k_hi(c) is the LDS address of this lane's ds_read_b128
-// fragment of chunk c in the K hi plane; the lo plane's fragment lies lo_off bytes behind it.
-template <class KHi>
+// NP = 1 (split_bf16 = 2, the opt-in acoustic bf16 arithmetic): the hi * hi' product alone; the lo operands are never loaded
+template <int NP>
+__device__ __forceinline__ f32x16 mfma_np(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 acc) {
+  if constexpr (NP == 3) return mfma_x3(ah, al, bh, bl, acc);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// S^T = K . Q^T from split-bf16 operands: 12 MFMAs (NP = 1: 4) over the four 16-d chunks.  k_hi(c) is the LDS address of this lane's
+// ds_read_b128 fragment of chunk c in the K hi plane; the lo plane's fragment lies lo_off bytes behind it.
+template <int NP = 3, class KHi>
 __device__ __forceinline__ f32x16 qk_bf16x3(const bf16x8 (&qh)[4], const bf16x8 (&ql)[4], int lo_off, KHi k_hi) {
   f32x16 s = {};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const bf16x8 kh = *reinterpret_cast<const bf16x8*>(k_hi(c));
-    const bf16x8 kl = *reinterpret_cast<const bf16x8*>(k_hi(c) + lo_off);
-    s = mfma_x3(kh, kl, qh[c], ql[c], s);
+    bf16x8 kl = kh;
+    if constexpr (NP == 3) kl = *reinterpret_cast<const bf16x8*>(k_hi(c) + lo_off);
+    s = mfma_np<NP>(kh, kl, qh[c], ql[c], s);
   }
   return s;
 }
@@ -359,6 +369,9 @@ __device__ __forceinline__ void split_p(const f32x16& s, bf16x8 (&ph)[2], bf16x8
   }
 }
 
+// NP = 1: q, k, v rounded once to bf16 (q unscaled: the softmax scale rides in the exponent, as in the planes kernel), P rounded once,
+// one MFMA per product; no relative_key form.
+template <int NP>
 __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * ABUF];
   static_assert(STAGE_FLOATS * 4 <= 2 * ABUF, "output staging must fit in the K/V tiles");
@@ -376,7 +389,7 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
   {
     const bool ok = w.qi < p.Sq;
     const float* qrow = qb + (size_t)(ok ? w.qi : 0) * p.q_ts;
-    const float sc = p.scale * 1.4426950408889634f;
+    const float sc = NP == 3 ? p.scale * 1.4426950408889634f : 1.0f;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f}, bq = a;
@@ -397,7 +410,7 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
     bf16x4 hi, lo;
     split4(a, hi, lo);
     *reinterpret_cast<bf16x4*>(base + row * KB16 + c4 * 8) = hi;
-    *reinterpret_cast<bf16x4*>(base + 32 * KB16 + row * KB16 + c4 * 8) = lo;
+    if (NP == 3) *reinterpret_cast<bf16x4*>(base + 32 * KB16 + row * KB16 + c4 * 8) = lo;
   };
   auto store_kv = [&](int buf) {
     char* base = smem + buf * ABUF;
@@ -409,7 +422,7 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
       bf16x4 hi, lo;
       split4(vr[l], hi, lo);
       *reinterpret_cast<bf16x4*>(base + 64 * KB16 + row * VB16 + c4 * 8) = hi;
-      *reinterpret_cast<bf16x4*>(base + 64 * KB16 + 32 * VB16 + row * VB16 + c4 * 8) = lo;
+      if (NP == 3) *reinterpret_cast<bf16x4*>(base + 64 * KB16 + 32 * VB16 + row * VB16 + c4 * 8) = lo;
     }
   };
 
@@ -420,7 +433,7 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
   const int k_off = w.j * KB16 + 16 * w.h;                                  // + 32 * c per 16-d chunk (+ 32*KB16 for lo)
   // transposing V read: lane 4q+p of a 16-lane group addresses row (key) q, columns 4p..4p+3 of the group's 16 columns
   const int v_off = 64 * KB16 + (4 * w.h + ((w.lane & 15) >> 2)) * VB16 + (16 * ((w.lane >> 4) & 1) + 4 * (w.lane & 3)) * 2;
-  auto qk = [&](const char* tb) { return qk_bf16x3(qh, ql, 32 * KB16, [&](int c) { return tb + k_off + 32 * c; }); };
+  auto qk = [&](const char* tb) { return qk_bf16x3<NP>(qh, ql, 32 * KB16, [&](int c) { return tb + k_off + 32 * c; }); };
 
   extern __shared__ float rel_dyn[];
   float* const tbl_row = rel_dyn + (w.wave * 32 + w.j) * REL_ROW;      // this lane's query
@@ -446,7 +459,7 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = keys.sees(acc_key(r, w.h, key0), w.qi, p.causal) ? s[r] : NEG_BIG;
       }
-      online_softmax_log2<false>(s, o, m_run, l_run, 0.0f, need_mask);
+      online_softmax_log2<NP == 1>(s, o, m_run, l_run, p.scale * 1.4426950408889634f, need_mask);
       bf16x8 ph[2], pl[2];
       split_p(s, ph, pl);
       // ---- O^T += V^T . P^T ----
@@ -458,11 +471,14 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
           typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
           const bf16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va));
           const bf16x4 h1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 8 * VB16));
-          const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 32 * VB16));
-          const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 40 * VB16));
           const bf16x8 vh = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
-          const bf16x8 vl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[t] = mfma_x3(vh, vl, ph[t2], pl[t2], o[t]);
+          bf16x8 vl = vh;
+          if constexpr (NP == 3) {
+            const bf16x4 l0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 32 * VB16));
+            const bf16x4 l1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(va + 40 * VB16));
+            vl = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+          }
+          o[t] = mfma_np<NP>(vh, vl, ph[t2], pl[t2], o[t]);
         }
     }
     if (has_next) store_kv((tile + 1) & 1);
@@ -487,6 +503,9 @@ __global__ __launch_bounds__(256) void flash_attn_bf16x3_kernel(const AttnArgs p
 constexpr int ATT_SLOT = 16 * 1024;       // 16 pieces of 1 KiB: [K hi, K lo, V hi, V lo] x 4 chunks
 constexpr int ATT_NSLOT = 3;
 
+// NP = 1 (AttnPlanesArgs::split_bf16 = 2): the hi planes alone -- the lo waves request nothing, the lo halves of a slot stay unwritten,
+// a tile is 8 fragment reads and 8 MFMAs.
+template <int NP>
 __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanesArgs p) {
   __shared__ __attribute__((aligned(1024))) char smem[ATT_NSLOT * ATT_SLOT];
   static_assert(STAGE_FLOATS * 4 <= ATT_NSLOT * ATT_SLOT, "output staging must fit in the ring");
@@ -513,14 +532,17 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       qh[c] = *reinterpret_cast<const bf16x8*>(hi + base + c * rows16);
-      ql[c] = *reinterpret_cast<const bf16x8*>(lo + base + c * rows16);
+      ql[c] = NP == 3 ? *reinterpret_cast<const bf16x8*>(lo + base + c * rows16) : qh[c];
     }
   }
   // The fragments are consumed here, before the first tile DMA is issued: the compiler places its own wait for the loads now and
   // knows them complete inside the loop.  (With only a hand-written s_waitcnt it kept them "pending" in its counter model and,
   // since DMAs are issued after them, drained vmcnt(0) before the first MFMA of EVERY tile -- the prefetch ring was worth nothing.)
 #pragma unroll
-  for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(qh[c]), "+v"(ql[c]));
+  for (int c = 0; c < 4; ++c) {
+    if constexpr (NP == 3) asm volatile("" : "+v"(qh[c]), "+v"(ql[c]));
+    else asm volatile("" : "+v"(qh[c]));
+  }
 
   // DMA role: wave 0 K hi, 1 K lo, 2 V hi, 3 V lo; lane = (LDS row lrow, LDS half unit) of each of the wave's four chunk pieces.
   // Addresses: a wave-uniform 64-bit base per chunk (scalar registers) + a 32-bit per-lane byte offset, two offsets per tile (even
@@ -537,6 +559,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
     // keys past the row's end: finite rows of a neighbour, masked below
     const unsigned off_e = min(row_e + (unsigned)tile * 32u, last_row) * 32u + half_b;
     const unsigned off_o = min(row_o + (unsigned)tile * 32u, last_row) * 32u + half_b;
+    if (NP == 1 && (wave_s & 1)) return;      // (the lo waves: their counted waits find nothing in flight)
 #pragma unroll
     for (int c = 0; c < 4; ++c) ATT_GLDS16(src0 + c * chunk_bytes + ((c & 1) ? off_o : off_e), dst + c * 1024);
   };
@@ -571,7 +594,7 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
     const int key0 = tile * 32;
     if (w.q0 < p.Sq) {      // wave-uniform
       // K chunk c: pieces c (hi) and 4 + c (lo) of the slot
-      f32x16 s = qk_bf16x3(qh, ql, 4096, [&](int c) { return tb + c * 1024 + ((c & 1) ? k_off1 : k_off0); });
+      f32x16 s = qk_bf16x3<NP>(qh, ql, 4096, [&](int c) { return tb + c * 1024 + ((c & 1) ? k_off1 : k_off0); });
       // V fragments: requested now, behind the QK MFMAs, so that they have landed by the time the softmax is through.
       const unsigned va = slot_lds + v_off_a, vb = slot_lds + v_off_b;
       bf16x4 vf[2][2][4];      // [t2][t][hi a, hi b, lo a, lo b]
@@ -579,8 +602,10 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
 #define ATT_TR4(t2, t)                                     \
       ATT_TR(vf[t2][t][0], va, 512 * t2 + 2048 * t);        \
       ATT_TR(vf[t2][t][1], vb, 512 * t2 + 2048 * t);        \
-      ATT_TR(vf[t2][t][2], va, 512 * t2 + 2048 * t + 4096); \
-      ATT_TR(vf[t2][t][3], vb, 512 * t2 + 2048 * t + 4096);
+      if constexpr (NP == 3) {                                \
+        ATT_TR(vf[t2][t][2], va, 512 * t2 + 2048 * t + 4096); \
+        ATT_TR(vf[t2][t][3], vb, 512 * t2 + 2048 * t + 4096); \
+      }
       ATT_TR4(0, 0) ATT_TR4(0, 1) ATT_TR4(1, 0) ATT_TR4(1, 1)
 #undef ATT_TR4
 #undef ATT_TR
@@ -600,15 +625,20 @@ __global__ __launch_bounds__(256) void flash_attn_planes_kernel(const AttnPlanes
 #define ATT_PV(t2, t)                                                                              \
         {                                                                                          \
           const bf16x8 vh = __builtin_shufflevector(vf[t2][t][0], vf[t2][t][1], 0, 1, 2, 3, 4, 5, 6, 7); \
-          const bf16x8 vl = __builtin_shufflevector(vf[t2][t][2], vf[t2][t][3], 0, 1, 2, 3, 4, 5, 6, 7); \
-          o[t] = mfma_x3(vh, vl, ph[t2], pl[t2], o[t]);                                             \
+          bf16x8 vl = vh;                                                                          \
+          if constexpr (NP == 3) vl = __builtin_shufflevector(vf[t2][t][2], vf[t2][t][3], 0, 1, 2, 3, 4, 5, 6, 7); \
+          o[t] = mfma_np<NP>(vh, vl, ph[t2], pl[t2], o[t]);                                         \
         }
-#define ATT_WAIT4(n, t2, t) \
-        asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(vf[t2][t][0]), "+v"(vf[t2][t][1]), "+v"(vf[t2][t][2]), "+v"(vf[t2][t][3])::"memory")
-        ATT_WAIT4(12, 0, 0); ATT_PV(0, 0)
-        ATT_WAIT4(8, 0, 1);  ATT_PV(0, 1)
-        ATT_WAIT4(4, 1, 0);  ATT_PV(1, 0)
-        ATT_WAIT4(0, 1, 1);  ATT_PV(1, 1)
+        // (n3 / n1: transposing reads still in flight behind this fragment's, with four / two reads per fragment)
+#define ATT_WAIT4(n3, n1, t2, t)                                                                                                          \
+        if constexpr (NP == 3)                                                                                                            \
+          asm volatile("s_waitcnt lgkmcnt(" #n3 ")" : "+v"(vf[t2][t][0]), "+v"(vf[t2][t][1]), "+v"(vf[t2][t][2]), "+v"(vf[t2][t][3])::"memory"); \
+        else                                                                                                                              \
+          asm volatile("s_waitcnt lgkmcnt(" #n1 ")" : "+v"(vf[t2][t][0]), "+v"(vf[t2][t][1])::"memory")
+        ATT_WAIT4(12, 6, 0, 0); ATT_PV(0, 0)
+        ATT_WAIT4(8, 4, 0, 1);  ATT_PV(0, 1)
+        ATT_WAIT4(4, 2, 1, 0);  ATT_PV(1, 0)
+        ATT_WAIT4(0, 0, 1, 1);  ATT_PV(1, 1)
 #undef ATT_WAIT4
 #undef ATT_PV
       }
@@ -637,7 +667,9 @@ int flash_attn_planes_forward(const AttnPlanesArgs& a, hipStream_t stream) {
   const double bytes = 4.0 * a.B * a.H * 64.0 * (2.0 * a.Sq + 2.0 * a.T);
   static const int cat = prof_register("flash_attn_planes_kernel");
   ProfScope prof(cat, stream, flops, bytes);
-  hipLaunchKernelGGL(flash_attn_planes_kernel, grid, dim3(256), 0, stream, k);
+  IDX_CHECK(a.split_bf16 == 1 || a.split_bf16 == 2, "split_bf16: 1 (three MFMAs per product) or 2 (one)");
+  if (a.split_bf16 == 2) hipLaunchKernelGGL(flash_attn_planes_kernel<1>, grid, dim3(256), 0, stream, k);
+  else hipLaunchKernelGGL(flash_attn_planes_kernel<3>, grid, dim3(256), 0, stream, k);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -660,9 +692,12 @@ int flash_attn_forward(const AttnArgs& a, hipStream_t stream) {
     IDX_CHECK((reinterpret_cast<uintptr_t>(a.rel_key) & 15) == 0, "rel_key must be 16-byte aligned");
     dyn = REL_LDS;
     static DynLdsLimit lds_limit;
-    IDX_HIP(lds_limit.set(REL_LDS, flash_attn_bf16x3_kernel, flash_attn_f32_kernel));
+    IDX_CHECK(a.split_bf16 != 2, "relative_key has no single-product form");
+    IDX_HIP(lds_limit.set(REL_LDS, flash_attn_bf16x3_kernel<3>, flash_attn_f32_kernel));
   }
-  if (a.split_bf16) hipLaunchKernelGGL(flash_attn_bf16x3_kernel, grid, dim3(256), dyn, stream, a);
+  IDX_CHECK(a.split_bf16 >= 0 && a.split_bf16 <= 2, "split_bf16: 0, 1 or 2");
+  if (a.split_bf16 == 2) hipLaunchKernelGGL(flash_attn_bf16x3_kernel<1>, grid, dim3(256), dyn, stream, a);
+  else if (a.split_bf16) hipLaunchKernelGGL(flash_attn_bf16x3_kernel<3>, grid, dim3(256), dyn, stream, a);
   else hipLaunchKernelGGL(flash_attn_f32_kernel, grid, dim3(256), dyn, stream, a);
   IDX_LAUNCH_CHECK();
   return 0;

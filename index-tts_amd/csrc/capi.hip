@@ -251,6 +251,12 @@ int idxtts_linear_fwd(const idxtts_linear* lin, const float* x, int ldx, float* 
   if (!bf16x3) return gemm_tn_forward(lin->w, a, static_cast<hipStream_t>(stream));
   LinearWeights w = lin->w;
   if (bf16x3 == 2) w.mf16 = false;      // the LDS-DMA kernel's 32x32x16 loop: what the GPT, conditioning and semantic weights run
+  if (bf16x3 == 3) {                    // one bf16 MFMA per product: the LDS-DMA kernel's 16x16x32 loop only, whatever the switch says
+    IDX_CHECK(w.planes16 && w.mf16 && M >= 256 && linear_takes_planes(w.N, w.K), "bf16x3 = 3 needs M >= 256 and a shape the LDS-DMA kernel takes (N >= 96, K % 16 == 0)");
+    a.bf16_products = 1;
+  } else {
+    IDX_CHECK(bf16x3 == 1 || bf16x3 == 2, "bf16x3: 0 .. 3");
+  }
   return gemm_bf16x3_forward(w, a, static_cast<hipStream_t>(stream));
   API_END
 }
@@ -301,6 +307,17 @@ int idxtts_attention_bf16x3_fwd(const float* q, const float* k, const float* v, 
   AttnArgs a = attn_args(q, k, v, o, q_batch_stride, q_token_stride, kv_batch_stride, kv_token_stride, o_batch_stride, o_token_stride,
                          B, H, Sq, Sk, causal, kstart, kend, scale);
   a.split_bf16 = 1;
+  return flash_attn_forward(a, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_attention_bf16_fwd(const float* q, const float* k, const float* v, float* o, long q_batch_stride, int q_token_stride,
+                         long kv_batch_stride, int kv_token_stride, long o_batch_stride, int o_token_stride, int B, int H,
+                         int Sq, int Sk, int causal, const int* kstart, const int* kend, float scale, void* stream) {
+  API_BEGIN
+  AttnArgs a = attn_args(q, k, v, o, q_batch_stride, q_token_stride, kv_batch_stride, kv_token_stride, o_batch_stride, o_token_stride,
+                         B, H, Sq, Sk, causal, kstart, kend, scale);
+  a.split_bf16 = 2;
   return flash_attn_forward(a, static_cast<hipStream_t>(stream));
   API_END
 }
@@ -824,6 +841,13 @@ int idxtts_set_gemm_mode(int mode) {
 }
 
 int idxtts_get_gemm_mode(void) { return get_gemm_mode(); }
+
+int idxtts_set_acoustic_bf16(int on) {
+  set_acoustic_bf16(on);
+  return 0;
+}
+
+int idxtts_get_acoustic_bf16(void) { return get_acoustic_bf16(); }
 
 int idxtts_set_decode_geometry(int narrow) {
   set_decode_geometry(narrow);

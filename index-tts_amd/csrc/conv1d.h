@@ -50,8 +50,10 @@ struct ConvArgs {
 };
 
 int conv1d_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream);
-// split-bf16 path (taken by conv1d_forward when the GEMM mode is GEMM_BF16X3 and w.wp16 is set)
+// split-bf16 path (taken by conv1d_forward when the GEMM mode is GEMM_BF16X3 and w.wp16 is set).  products: bf16 MFMAs per product, 3, or
+// 1 = hi * hi' alone (conv1d_forward passes 1 while the acoustic-bf16 switch is on, gemm.h: its only callers are BigVGAN and
+// idxtts_conv1d_fwd)
 void pack_conv_bf16x3(void* dst, const float* packed_f32, size_t n_subtiles);
-int conv1d_bf16x3_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream);
+int conv1d_bf16x3_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream, int products = 3);
 
 }  // namespace idxtts

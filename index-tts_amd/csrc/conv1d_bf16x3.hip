@@ -73,12 +73,18 @@ constexpr int XROW_B = 32;            // bytes per LDS x row (16 ci bf16)
 // differs: with K > 1 the next chunk's x rows are requested BEHIND the step's weight tile and stored at least one step later, so the
 // counted wait in front of their store (vmcnt = the weight requests issued since) never drains the weight tiles in flight, and the x
 // rows get a whole step to arrive; with K = 1 they are stored in the step that requested them.
-template <int TM, int TN, int WGM, int WGN, bool K1>
+// NP: bf16 MFMAs per product.  3 = split-bf16.  1 (the opt-in acoustic bf16 arithmetic, gemm.h: set_acoustic_bf16) = hi * hi' alone:
+// the loader stores the hi plane of the x tile only, a step's weight tile is the hi halves of its sub-tile images (1 KiB each: half the
+// DMA instructions, the counted waits follow), a step is 4 MFMAs per wave tile pair instead of 12; the k order of an output's sum
+// (chunks, then taps) is unchanged.
+template <int TM, int TN, int WGM, int WGN, bool K1, int NP>
 __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
   constexpr int NSUB = TM * WGM;
   constexpr int NXJ = (BN + CONV_MAX_HALO + 63) / 64;    // time steps per lane in the x loader
-  constexpr int NW4 = NSUB * 128;                        // 16-byte units per weight tile (2 KiB per sub-tile)
+  static_assert(NP == 3 || NP == 1, "MFMAs per product");
+  constexpr int SUB4 = NP == 1 ? 64 : 128;               // 16-byte units of a sub-tile image that a step moves (hi + lo: 2 KiB, hi: 1 KiB)
+  constexpr int NW4 = NSUB * SUB4;                       // 16-byte units per weight tile
   constexpr int NWL = (NW4 + 255) / 256;
   constexpr int XT_MAX = BN + CONV_MAX_HALO;
   constexpr int XPLANE = XT_MAX * XROW_B;                // bytes of one x plane
@@ -153,7 +159,7 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
         split_bf16_x4(v, hi, lo);
         const int off = c * XROW_B + (((cg >> 1) ^ ((c >> 3) & 1)) << 4) + ((cg & 1) << 3);
         *reinterpret_cast<bf16x4*>(dst + off) = hi;
-        *reinterpret_cast<bf16x4*>(dst + XPLANE + off) = lo;
+        if (NP == 3) *reinterpret_cast<bf16x4*>(dst + XPLANE + off) = lo;
       }
     }
   };
@@ -165,12 +171,12 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
 #pragma unroll
   for (int l = 0; l < NWL; ++l) {
     const int idx = min(tid + l * 256, NW4 - 1);
-    wvoff[l] = min(m_blk * NSUB + (idx >> 7), p.mt32 - 1) * p.w_mt_stride + (idx & 127) * 16;
+    wvoff[l] = min(m_blk * NSUB + idx / SUB4, p.mt32 - 1) * p.w_mt_stride + (idx % SUB4) * 16;
   }
   char* const lds_w = Ws + wave * 1024;
   auto request_w = [&](int slot, int chunk, int tap) {
     const int so = (chunk * p.K + tap) * 2048;
-    if (NSUB == 1 && wave >= 2) return;      // (wave-uniform; waves 2 and 3 hold no weight request: their counted waits only see x loads)
+    if (NSUB == 1 && wave >= SUB4 / 64) return;      // (wave-uniform; waves 2 and 3 hold no weight request: their counted waits only see x loads)
 #pragma unroll
     for (int l = 0; l < NWL; ++l)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (__attribute__((address_space(3))) void*)(lds_w + slot * WSLOT + l * 4096), 16, wvoff[l], so, 0, 0);
@@ -226,23 +232,25 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
       bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt) {
-        const char* wsub = wb + (wm * TM + mt) * 2048 + (h * 32 + j) * 16;
+        const char* wsub = wb + (wm * TM + mt) * (SUB4 * 16) + (h * 32 + j) * 16;
         ah[mt] = *reinterpret_cast<const bf16x8*>(wsub);
-        al[mt] = *reinterpret_cast<const bf16x8*>(wsub + 1024);
+        if (NP == 3) al[mt] = *reinterpret_cast<const bf16x8*>(wsub + 1024);
       }
 #pragma unroll
       for (int nt = 0; nt < TN; ++nt) {
         const int row = (wn * TN + nt) * 32 + j + tap * p.dil;
         const int off = row * XROW_B + ((h ^ ((row >> 3) & 1)) << 4);
         bh[nt] = *reinterpret_cast<const bf16x8*>(xb + off);
-        bl[nt] = *reinterpret_cast<const bf16x8*>(xb + XPLANE + off);
+        if (NP == 3) bl[nt] = *reinterpret_cast<const bf16x8*>(xb + XPLANE + off);
       }
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
+          if (NP == 3) {
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
+            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
+          }
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
         }
     }
@@ -265,13 +273,13 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
 }
 
 // (the body lives in a __device__ function: the host pass cannot instantiate a __global__ template whose body names device builtins)
-template <int TM, int TN, int WGM, int WGN, bool K1>
+template <int TM, int TN, int WGM, int WGN, bool K1, int NP>
 __global__ __launch_bounds__(256, (TM == 3 ? 2 : 3)) void conv1d_bf16x3_kernel(const ConvKP16 p) {
-  conv1d_bf16x3_body<TM, TN, WGM, WGN, K1>(p);
+  conv1d_bf16x3_body<TM, TN, WGM, WGN, K1, NP>(p);
 }
 
 template <int TM, int TN, int WGM, int WGN, bool K1>
-static int launch_conv16(const ConvWeights& w, const ConvArgs& a, hipStream_t stream) {
+static int launch_conv16(const ConvWeights& w, const ConvArgs& a, hipStream_t stream, int products) {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN, NSUB = TM * WGM;
   constexpr int XT_MAX = BN + CONV_MAX_HALO;
   IDX_CHECK(w.wp16 && a.x && a.y, "null pointer");
@@ -300,40 +308,41 @@ static int launch_conv16(const ConvWeights& w, const ConvArgs& a, hipStream_t st
   const double weight_bytes = 4.0 * w.M * (double)w.Cin * w.K;
   p.mblocks = mblocks;
   p.walk = mblocks > 1 && (walk_env >= 0 ? walk_env == 1 : weight_bytes <= 20e6) ? 1 : 0;
-  constexpr int NWL = (NSUB * 128 + 255) / 256;
+  constexpr int NWL = (NSUB * 128 + 255) / 256;      // (the ring keeps the split form's slots under NP = 1)
   const size_t lds = (size_t)3 * (NSUB == 1 ? 2048 : NWL * 4096) + (size_t)2 * 2 * XT_MAX * XROW_B;
   const size_t w_bytes = (size_t)cdiv(w.M, CONV_MT) * w.nchunk * w.K * 2048;
   IDX_CHECK(w_bytes < (1ull << 31), "weight pack beyond the 2 GiB a buffer offset addresses");
   p.w_bytes = (int)w_bytes; p.w_mt_stride = w.nchunk * w.K * 2048;
   const int64_t grid = (int64_t)8 * mblocks * p.nt8;
   IDX_CHECK(grid > 0 && grid < (1ll << 31), "grid size");
-  auto kern = conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1>;
+  auto kern = products == 1 ? conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 1> : conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 3>;
   static DynLdsLimit lds_limit;
-  IDX_HIP(lds_limit.set(160 * 1024, kern));
+  IDX_HIP(lds_limit.set(160 * 1024, conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 3>, conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 1>));
   const double cout = (double)(w.M / w.ups), tout = (double)a.T * w.ups * a.B;
   const double taps = w.ups > 1 ? 2.0 : (double)w.K;
   const double flops = 2.0 * cout * w.Cin * taps * tout;
   const double bytes = 4.0 * ((double)a.B * w.Cin * a.T + cout * tout * (1.0 + (a.res ? 1.0 : 0.0) + (a.accum ? 1.0 : 0.0)) +
                               cout * w.Cin * (w.ups > 1 ? 2.0 * w.ups : (double)w.K));
-  static const int cat = prof_register(("conv1d_bf16x3_kernel<" + std::to_string(TM) + ", " + std::to_string(TN) + ", " + std::to_string(WGM) + ", " + std::to_string(WGN) + (K1 ? ", true>" : ", false>")).c_str());
-  ProfScope prof(cat, stream, flops, bytes);
+  const std::string kname = "conv1d_bf16x3_kernel<" + std::to_string(TM) + ", " + std::to_string(TN) + ", " + std::to_string(WGM) + ", " + std::to_string(WGN) + (K1 ? ", true" : ", false");
+  static const int cat = prof_register((kname + ">").c_str()), cat1 = prof_register((kname + ", 1>").c_str());
+  ProfScope prof(products == 1 ? cat1 : cat, stream, flops, bytes);
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
   IDX_LAUNCH_CHECK();
   return 0;
 }
 
-// same tile configurations as conv1d_forward
-int conv1d_bf16x3_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream) {
+// same tile configurations as conv1d_forward; products (3 or 1) selects the instance of the configuration
+int conv1d_bf16x3_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream, int products) {
   if (w.K == 1) {
-    if (w.M > 96) return launch_conv16<2, 2, 2, 2, true>(w, a, stream);
-    if (w.M > 64) return launch_conv16<3, 2, 1, 4, true>(w, a, stream);
-    if (w.M > 32) return launch_conv16<2, 2, 1, 4, true>(w, a, stream);
-    return launch_conv16<1, 4, 1, 4, true>(w, a, stream);
+    if (w.M > 96) return launch_conv16<2, 2, 2, 2, true>(w, a, stream, products);
+    if (w.M > 64) return launch_conv16<3, 2, 1, 4, true>(w, a, stream, products);
+    if (w.M > 32) return launch_conv16<2, 2, 1, 4, true>(w, a, stream, products);
+    return launch_conv16<1, 4, 1, 4, true>(w, a, stream, products);
   }
-  if (w.M > 96) return launch_conv16<2, 2, 2, 2, false>(w, a, stream);   // 128 x 128
-  if (w.M > 64) return launch_conv16<3, 2, 1, 4, false>(w, a, stream);   //  96 x 256
-  if (w.M > 32) return launch_conv16<2, 2, 1, 4, false>(w, a, stream);   //  64 x 256
-  return launch_conv16<1, 4, 1, 4, false>(w, a, stream);                 //  32 x 512
+  if (w.M > 96) return launch_conv16<2, 2, 2, 2, false>(w, a, stream, products);   // 128 x 128
+  if (w.M > 64) return launch_conv16<3, 2, 1, 4, false>(w, a, stream, products);   //  96 x 256
+  if (w.M > 32) return launch_conv16<2, 2, 1, 4, false>(w, a, stream, products);   //  64 x 256
+  return launch_conv16<1, 4, 1, 4, false>(w, a, stream, products);                 //  32 x 512
 }
 
 }  // namespace idxtts

@@ -48,6 +48,9 @@ struct GemmArgs {
   // activation or residual -- which the caller sums in a fixed order (rows_norm_forward partials), so results stay
   // bitwise reproducible.
   int ksplit = 1;
+  // bf16 MFMAs per product of the LDS-DMA kernel's 16x16x32 loop: 3 = split-bf16, 1 = hi * hi' alone.  gemm_forward sets it from the
+  // acoustic-bf16 switch (below); every other kernel ignores it.
+  int bf16_products = 3;
 };
 
 int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream);      // exact fp32 MFMA
@@ -66,6 +69,14 @@ void pack_linear_planes(void* dst, const float* w, int N, int K);
 enum GemmMode { GEMM_F32 = 0, GEMM_BF16X3 = 1 };
 void set_gemm_mode(int mode);
 int get_gemm_mode();
+// Opt-in bf16 arithmetic of the acoustic stage (s2mel, BigVGAN), process-wide, default off, effective only in GEMM_BF16X3: operands are
+// the hi values of the split form (fp32 rounded to nearest-even bf16), one bf16 MFMA per product, fp32 accumulation.  Here it reaches
+// the launches that would run the LDS-DMA kernel (M >= 256, planes16) with weights of the 16x16x32 loop (LinearWeights::mf16: s2mel and
+// idxtts_linear_create, the set that feeds no choice of discrete codes).  The 32x32x16 loop, the tile kernel and the exact kernel keep
+// their arithmetic.  Also read by s2mel.hip (DiT attention) and conv1d.hip (vocoder convolutions).
+void set_acoustic_bf16(int on);
+int get_acoustic_bf16();
+bool acoustic_bf16_active();      // the switch is on and the mode is GEMM_BF16X3
 // dispatches on the mode above
 int gemm_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream);
 // true when gemm_forward would run this shape on the LDS-DMA split-bf16 kernel (the only consumer / producer of planes)

@@ -304,12 +304,24 @@ static int g_gemm_mode = GEMM_BF16X3;
 void set_gemm_mode(int mode) { g_gemm_mode = mode == GEMM_F32 ? GEMM_F32 : GEMM_BF16X3; }
 int get_gemm_mode() { return g_gemm_mode; }
 
+static int g_acoustic_bf16 = 0;
+void set_acoustic_bf16(int on) { g_acoustic_bf16 = on ? 1 : 0; }
+int get_acoustic_bf16() { return g_acoustic_bf16; }
+bool acoustic_bf16_active() { return g_acoustic_bf16 && g_gemm_mode == GEMM_BF16X3; }
+
 bool gemm_uses_planes(const LinearWeights& w, const GemmArgs& a) {
   return g_gemm_mode == GEMM_BF16X3 && w.planes16 && gemm_bf16x3_uses_v2(w, a);
 }
 int gemm_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t stream) {
   // split-bf16 from 256 rows up, where the weights carry the pack of the kernel their shape runs on
-  if (g_gemm_mode == GEMM_BF16X3 && a.M >= 256 && (linear_takes_planes(w.N, w.K) ? w.planes16 : w.tiles16)) return gemm_bf16x3_forward(w, a, stream);
+  if (g_gemm_mode == GEMM_BF16X3 && a.M >= 256 && (linear_takes_planes(w.N, w.K) ? w.planes16 : w.tiles16)) {
+    if (acoustic_bf16_active() && w.mf16 && linear_takes_planes(w.N, w.K)) {      // the LDS-DMA kernel's 16x16x32 loop: one MFMA per product
+      GemmArgs b = a;
+      b.bf16_products = 1;
+      return gemm_bf16x3_forward(w, b, stream);
+    }
+    return gemm_bf16x3_forward(w, a, stream);
+  }
   return gemm_tn_forward(w, a, stream);
 }
 

@@ -15,6 +15,12 @@
 //     stage is overwritten only after a barrier behind its last read);
 //   * LDS rows are 32 B (2 x 16-B units); unit' = unit ^ (row >> 3 & 1), applied on the DMA's SOURCE address and on the
 //     ds_read_b128 address, makes every fragment read conflict-free without padding (the DMA destination is lane-linear).
+//
+// Opt-in bf16 arithmetic (gemm.h: set_acoustic_bf16; GemmArgs::bf16_products = 1): the 16x16x32 loop also exists with ONE MFMA per
+// product, hi * hi' alone (template parameter NP of gemm_v2_tile).  gemm_forward selects it when the switch is on, the launch runs this
+// kernel and the weights carry mf16.  The 32x32x16 loop here, the register-staged tile kernel (gemm_bf16x3.hip: fewer than 256 rows, or
+// shapes without planes) and the exact kernel (gemm.hip) keep their arithmetic under the switch.  Both output planes (y_planes) and both
+// planes of split_planes_kernel are written in either form: launches below 256 rows read the lo plane.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -112,16 +118,20 @@ struct V2Rsrc { __amdgpu_buffer_rsrc_t a, b; };
 
 #define V2_WAITCNT(vm) __builtin_amdgcn_s_waitcnt(((vm) & 15) | (((vm) >> 4) << 14) | 0x70)   /* vmcnt(vm) lgkmcnt(0) */
 
-template <bool TAPS, int EPI, int MF>      // MF: the MFMA shape of the main loop, 32 = 32x32x16, 16 = 16x16x32
+// NP: bf16 MFMAs per product.  3 = split-bf16 (above).  1 (MF == 16 only; the opt-in acoustic bf16 arithmetic, gemm.h:
+// set_acoustic_bf16) = hi * hi' alone, fp32 accumulation: a stage requests and reads its two hi pieces only (the lo halves of the ring
+// slots stay unwritten), a step issues 16 MFMAs for 8 fragment reads, the k order of a row's sum is that of the split loop.
+template <bool TAPS, int EPI, int MF, int NP = 3>      // MF: the MFMA shape of the main loop, 32 = 32x32x16, 16 = 16x16x32
 __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, const int bn, const int tid) {
   constexpr int NSTAGE = 3;                // ring depth (16-k stages)
   constexpr int WMW = 2, WNW = 2, TN = 2;      // waves along M / N, 32-column MFMA tiles per wave
   constexpr int BM = 64 * WMW, BN = 32 * TN * WNW;                 // 128 x 128
   static_assert(BM / 32 == WMW * WNW && BN / 32 == WMW * WNW, "one 32-row block of A and of B per wave and plane");
   static_assert(MF == 32 || MF == 16, "MFMA shape");
+  static_assert(NP == 3 || (NP == 1 && MF == 16), "one MFMA per product exists in the 16x16x32 loop only");
   constexpr int PLANE = BM * 32;               // bytes of one operand plane of a stage (BM = BN rows x 32 B)
   constexpr int STAGE_BYTES = 4 * PLANE;       // [A hi][A lo][B hi][B lo]
-  constexpr int PPW = 4;                       // DMA instructions per wave and stage
+  constexpr int PPW = NP == 1 ? 2 : 4;         // DMA instructions per wave and stage (the counted waits follow it)
   const GemmKP& p = q.g;
   extern __shared__ __attribute__((aligned(1024))) char smv2[];
 
@@ -159,6 +169,8 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
     else if (pi == 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, dst, 16, voffB, soB, 0, 0);
     else __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, dst, 16, voffB, soB + q.b_plane, 0, 0);
   };
+  auto issue_a = [&]() { issue_piece(0); if (NP == 3) issue_piece(1); };      // the A pieces of stage ist / its B pieces
+  auto issue_b = [&]() { issue_piece(2); if (NP == 3) issue_piece(3); };
   auto advance = [&]() {
     ++ist;
     wslot = wslot + 1 == NSTAGE ? 0 : wslot + 1;
@@ -195,8 +207,7 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
         for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0f;
     for (int s = 0; s < NSTAGE; ++s)
       if (s < ns) {
-#pragma unroll
-        for (int pi = 0; pi < PPW; ++pi) issue_piece(pi);
+        issue_a(); issue_b();
         advance();
       }
 
@@ -212,11 +223,11 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
       bf16x8 ah[4], al[4], bh[4], bl[4];
       auto rd_a = [&](int t) {
         ah[t] = *reinterpret_cast<const bf16x8*>(st + a_off + t * 512);
-        al[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + a_off + t * 512);
+        if (NP == 3) al[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + a_off + t * 512);
       };
       auto rd_b = [&](int t) {
         bh[t] = *reinterpret_cast<const bf16x8*>(st + b_off + t * 512);
-        bl[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + b_off + t * 512);
+        if (NP == 3) bl[t] = *reinterpret_cast<const bf16x8*>(st + PLANE + b_off + t * 512);
       };
       // row tile 0 and column tile 0 first: the first MFMAs wait for three reads, not for all of A
       rd_a(0); rd_b(0);
@@ -233,37 +244,36 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
         const unsigned keep = (g >> 1) ? 0u : 0xffffffffu;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          ah[t] = (bf16x8)((u32x4)ah[t] & keep); al[t] = (bf16x8)((u32x4)al[t] & keep);
-          bh[t] = (bf16x8)((u32x4)bh[t] & keep); bl[t] = (bf16x8)((u32x4)bl[t] & keep);
+          ah[t] = (bf16x8)((u32x4)ah[t] & keep); if (NP == 3) al[t] = (bf16x8)((u32x4)al[t] & keep);
+          bh[t] = (bf16x8)((u32x4)bh[t] & keep); if (NP == 3) bl[t] = (bf16x8)((u32x4)bl[t] & keep);
         }
       }
-#define V2_MFMA3(nt)                                                                                               \
-      _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) {                                                            \
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);                \
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);                \
-        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);                \
-      }
-#define V2_MFMA1(mt, nt)                                                                                           \
-      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);                  \
-      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);                  \
-      acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);                  \
-      __builtin_amdgcn_sched_barrier(0);
+      // one product of tile (mt, nt): lo * hi' + hi * lo' + hi * hi', or hi * hi' alone
+      auto prod = [&](int mt, int nt) {
+        if (NP == 3) {
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
+        }
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
+      };
+#define V2_MFMA3(nt) _Pragma("unroll") for (int mt = 0; mt < 4; ++mt) prod(mt, nt);
+#define V2_MFMA1(mt, nt) prod(mt, nt); __builtin_amdgcn_sched_barrier(0);
 
       __builtin_amdgcn_sched_barrier(0);
       V2_MFMA1(0, 0) V2_MFMA1(1, 0) V2_MFMA1(2, 0) V2_MFMA1(3, 0)      // (in the order their A fragments arrive)
       V2_WAITCNT(63);                           // lgkmcnt(0): every fragment of the pair is in registers
       __builtin_amdgcn_s_barrier();             // ... in every wave: the pair's ring slots are free
       __builtin_amdgcn_sched_barrier(0);
-      if (nreq >= 1) { issue_piece(0); issue_piece(1); }
+      if (nreq >= 1) issue_a();
       __builtin_amdgcn_sched_barrier(0);
       V2_MFMA3(1)
       __builtin_amdgcn_sched_barrier(0);
-      if (nreq >= 1) { issue_piece(2); issue_piece(3); advance(); }
-      if (nreq >= 2) { issue_piece(0); issue_piece(1); }
+      if (nreq >= 1) { issue_b(); advance(); }
+      if (nreq >= 2) issue_a();
       __builtin_amdgcn_sched_barrier(0);
       V2_MFMA3(2)
       __builtin_amdgcn_sched_barrier(0);
-      if (nreq >= 2) { issue_piece(2); issue_piece(3); advance(); }
+      if (nreq >= 2) { issue_b(); advance(); }
       __builtin_amdgcn_sched_barrier(0);
       V2_MFMA3(3)
       __builtin_amdgcn_sched_barrier(0);
@@ -418,11 +428,11 @@ __device__ __forceinline__ void gemm_v2_tile(const GemmV2P& q, const int bm, con
 }
 
 // one output tile per workgroup, walked in column groups (gemm_common.h: gemm_tile_walk)
-template <bool TAPS, int EPI, int MF>
+template <bool TAPS, int EPI, int MF, int NP = 3>
 __global__ __launch_bounds__(256, 3) void gemm_bf16x3_v2_kernel(const GemmV2P q) {
   int bn, bm;
   if (!gemm_tile_walk(q.g, blockIdx.x, bm, bn, q.cs, q.nbg)) return;
-  gemm_v2_tile<TAPS, EPI, MF>(q, bm, bn, threadIdx.x);
+  gemm_v2_tile<TAPS, EPI, MF, NP>(q, bm, bn, threadIdx.x);
 }
 
 // per-stream scratch for the activation planes: room for a quarter more rows than the launch that grows it
@@ -497,18 +507,21 @@ int gemm_bf16x3_v2_forward(GemmKP p, const LinearWeights& w, const GemmArgs& a, 
   IDX_CHECK(!a.row_len || a.seq_len >= 16, "row masks need seq_len >= 16");
   const int epi = a.rope ? EPI_ROPE : paired ? EPI_PAIRED : a.act != ACT_NONE ? EPI_ACT : EPI_PLAIN;
   typedef void (*KernelFn)(const GemmV2P);
-#define V2_ROW(T, F) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, F>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, F>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, F>, gemm_bf16x3_v2_kernel<T, EPI_ACT, F>
+#define V2_ROW(T, F, P) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, F, P>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, F, P>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, F, P>, gemm_bf16x3_v2_kernel<T, EPI_ACT, F, P>
   // the main loop's MFMA shape comes with the weights (model_util.h: WP16_ALWAYS_MF16): 16x16x32 is 1.5-7 % faster on six of eight
   // shapes and equal on two (tools/gemm_ab.py, profiles/README.md "MFMA shape"), but its sums differ in the last bits from the
   // 32x32x16 loop's, which the models that feed a choice of discrete codes keep
-  static const KernelFn kernels[2][2][4] = {{{V2_ROW(false, 32)}, {V2_ROW(true, 32)}}, {{V2_ROW(false, 16)}, {V2_ROW(true, 16)}}};
+  // (row 2: one MFMA per product, GemmArgs::bf16_products == 1 -- the 16x16x32 loop only)
+  static const KernelFn kernels[3][2][4] = {{{V2_ROW(false, 32, 3)}, {V2_ROW(true, 32, 3)}}, {{V2_ROW(false, 16, 3)}, {V2_ROW(true, 16, 3)}},
+                                            {{V2_ROW(false, 16, 1)}, {V2_ROW(true, 16, 1)}}};
   static DynLdsLimit lds_limit;
-  IDX_HIP(lds_limit.set(lds, V2_ROW(false, 32), V2_ROW(true, 32), V2_ROW(false, 16), V2_ROW(true, 16)));
+  IDX_HIP(lds_limit.set(lds, V2_ROW(false, 32, 3), V2_ROW(true, 32, 3), V2_ROW(false, 16, 3), V2_ROW(true, 16, 3), V2_ROW(false, 16, 1), V2_ROW(true, 16, 1)));
+  IDX_CHECK(a.bf16_products == 3 || (a.bf16_products == 1 && w.mf16), "one MFMA per product needs weights of the 16x16x32 loop");
   int mf16 = w.mf16 ? 1 : 0;
 #ifdef V2_EXP_SHAPE
   if (const char* e = getenv("IDXTTS_EXP_V2_SHAPE")) mf16 = atoi(e) == 16;      // tools/gemm_ab.py's scratch build only
 #endif
-  const KernelFn kernel = kernels[mf16][a.taps > 1 ? 1 : 0][epi];
+  const KernelFn kernel = kernels[a.bf16_products == 1 ? 2 : mf16][a.taps > 1 ? 1 : 0][epi];
 #undef V2_ROW
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, stream, q);
   IDX_LAUNCH_CHECK();

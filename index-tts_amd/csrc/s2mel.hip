@@ -315,13 +315,14 @@ static int attention(const S2MelModel& m, const RowSet& all, bool qkv_planes, in
     ap.planes = qkv; ap.Mrows = all.rows; ap.ncols = 3 * D; ap.q_col = 0; ap.k_col = D; ap.v_col = 2 * D; ap.T = T; ap.q_row0 = q0; ap.Sq = Sq;
     ap.B = all.nseq; ap.H = m.cfg.num_heads; ap.kend = all.lens; ap.scale = 0.125f;
     ap.o = o.f; ap.o_planes = o.p; ap.o_bs = (long)Sq * D; ap.o_ts = D;
+    ap.split_bf16 = acoustic_bf16_active() ? 2 : 1;
     return flash_attn_planes_forward(ap, st);
   }
   AttnArgs a;
   a.q = qkv + (size_t)q0 * 3 * D; a.k = qkv + D; a.v = qkv + 2 * D; a.o = o.f; a.o_planes = o.p;
   a.q_bs = a.k_bs = a.v_bs = (long)T * 3 * D; a.o_bs = (long)Sq * D; a.q_ts = a.k_ts = a.v_ts = 3 * D; a.o_ts = D;
   a.B = all.nseq; a.H = m.cfg.num_heads; a.Sq = Sq; a.Sk = T; a.causal = 0; a.kend = all.lens; a.scale = 0.125f;
-  a.split_bf16 = get_gemm_mode() == GEMM_BF16X3;
+  a.split_bf16 = get_gemm_mode() == GEMM_BF16X3 ? (acoustic_bf16_active() ? 2 : 1) : 0;
   return flash_attn_forward(a, st);
 }
 

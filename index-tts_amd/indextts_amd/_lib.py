@@ -20,7 +20,7 @@ SYMBOLS = [
     "idxtts_fp8_e4m3_decode", "idxtts_fp8_e4m3_encode",
     "idxtts_bigvgan_create", "idxtts_bigvgan_workspace_bytes", "idxtts_bigvgan_fwd", "idxtts_bigvgan_fwd_ragged",
     "idxtts_profile_enable", "idxtts_profile_num_kernels", "idxtts_profile_kernel_name", "idxtts_profile_read", "idxtts_profile_event_overhead",
-    "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
+    "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_bf16_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
     "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
     "idxtts_gpt_beam_workspace_bytes", "idxtts_gpt_generate_beam",
     "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
@@ -28,7 +28,7 @@ SYMBOLS = [
     "idxtts_gpt_session_admit_sampled", "idxtts_gpt_session_workspace_bytes_beam", "idxtts_gpt_session_init_beam",
     "idxtts_gpt_session_admit_beam",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
-    "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
+    "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
     "idxtts_gpt_graph_cache_entries", "idxtts_w2vbert_create", "idxtts_w2vbert_workspace_bytes", "idxtts_w2vbert_forward",
     "idxtts_repcodec_create", "idxtts_repcodec_workspace_bytes", "idxtts_repcodec_quantize",
@@ -149,10 +149,12 @@ def load() -> ctypes.CDLL:
     lib.idxtts_linear_create.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_void_p)]
     lib.idxtts_linear_fwd.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.idxtts_set_gemm_mode.argtypes = [c_int]
+    lib.idxtts_set_acoustic_bf16.argtypes = [c_int]
     lib.idxtts_linear_destroy.argtypes = [c_void_p]
     lib.idxtts_attention_fwd.argtypes = [c_void_p] * 4 + [c_long, c_int, c_long, c_int, c_long, c_int, c_int, c_int, c_int, c_int,
                                                           c_int, c_void_p, c_void_p, c_float, c_void_p]
     lib.idxtts_attention_bf16x3_fwd.argtypes = lib.idxtts_attention_fwd.argtypes
+    lib.idxtts_attention_bf16_fwd.argtypes = lib.idxtts_attention_fwd.argtypes
     lib.idxtts_attention_relkey_fwd.argtypes = [c_void_p] * 4 + [c_long, c_int, c_long, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_int,
                                                                  c_int, c_void_p]
     lib.idxtts_layernorm_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]
@@ -373,6 +375,17 @@ def set_gemm_mode(mode: int) -> None:
 
 def get_gemm_mode() -> int:
     return int(load().idxtts_get_gemm_mode())
+
+
+def set_acoustic_bf16(on: bool) -> None:
+    """Opt-in bf16 arithmetic of the acoustic stage (s2mel GEMMs of 256 rows and more, DiT attention, vocoder convolutions): one bf16
+    MFMA per product on operands rounded to bf16 instead of the split form's three.  Process-wide, default off, effective only in the
+    split-bf16 GEMM mode; the GPT and every context that feeds discrete codes never read it (include/idxtts.h)."""
+    check(load().idxtts_set_acoustic_bf16(int(bool(on))))
+
+
+def get_acoustic_bf16() -> bool:
+    return bool(load().idxtts_get_acoustic_bf16())
 
 
 def set_decode_geometry(narrow: bool) -> None:

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import synth
+from . import _lib, synth
 from .config import PipelineConfig
 from .gpt import UnifiedVoice
 from .s2mel import S2Mel
@@ -179,7 +179,8 @@ class IndexTTS2:
 
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", use_fp16=False, device=None,
                  use_cuda_kernel=None, use_deepspeed=False, use_accel=False, use_torch_compile=False, gpt_weight_format=None,
-                 segment_batch: int = 16, gpt_kv_format=None):
+                 segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None):
+        # acoustic_bf16: see from_state_dicts (process-wide).
         # use_fp16 (reference: gpt.half() + fp16 autocast, infer_v2.py:109, 145-146) maps to bf16 STORAGE of the GPT weights:
         # the arithmetic of the HIP path stays fp32.  gpt_weight_format ("f32" | "bf16" | "fp8") overrides it.
         if gpt_weight_format is None:
@@ -191,7 +192,8 @@ class IndexTTS2:
         from .checkpoint import config_from_yaml, load_reference_checkpoints
         cfg, raw = config_from_yaml(cfg_path, model_dir) if os.path.exists(cfg_path) else (PipelineConfig(), None)
         gpt_sd, s2mel_sd, voc_sd = load_reference_checkpoints(model_dir, raw)
-        self._init(cfg, gpt_sd, s2mel_sd, voc_sd, device, gpt_weight_format, segment_batch=segment_batch, gpt_kv_format=gpt_kv_format)
+        self._init(cfg, gpt_sd, s2mel_sd, voc_sd, device, gpt_weight_format, segment_batch=segment_batch, gpt_kv_format=gpt_kv_format,
+                   acoustic_bf16=acoustic_bf16)
         # the rest of the reference's constructor (infer_v2.py:187-289): semantic model + statistics, semantic codec, CAMPPlus,
         # emotion banks, tokenizer
         from .checkpoint import load_prompt_checkpoints, reference_text_normalizer
@@ -215,17 +217,22 @@ class IndexTTS2:
 
     @classmethod
     def from_state_dicts(cls, cfg: PipelineConfig, gpt_sd, s2mel_sd, bigvgan_sd, device=None, gpt_weight_format="f32",
-                         keep_effective_gpt=False, segment_batch: int = 16, gpt_kv_format=None) -> "IndexTTS2":
+                         keep_effective_gpt=False, segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None) -> "IndexTTS2":
         """gpt_weight_format: "f32" | "bf16" | "fp8" storage of the GPT linear weights, gpt_kv_format: "f32" | "bf16" storage of its KV
         cache (default: fp32 with fp32 weights, bf16 with compact weights) (UnifiedVoice); keep_effective_gpt keeps
         `self.gpt.effective_state_dict` (the rounded model, reference keys) for parity checks; segment_batch: segments of one
-        infer() call synthesised together (1 = the reference's loop as written)."""
+        infer() call synthesised together (1 = the reference's loop as written); acoustic_bf16: None leaves the library's switch as
+        it is, True / False sets it (_lib.set_acoustic_bf16): s2mel and the vocoder on one bf16 MFMA per product instead of the split
+        form's three -- about 1.45 x faster, mel L1 7.7e-3 instead of 1.3e-5 from the exact mode (profiles/README.md "Acoustic bf16"), the GPT and the codes it
+        chooses untouched.  The switch is PROCESS-WIDE: it holds for every IndexTTS2 of the process, not for this object."""
         self = cls.__new__(cls)
-        self._init(cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format, keep_effective_gpt, segment_batch, gpt_kv_format)
+        self._init(cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format, keep_effective_gpt, segment_batch, gpt_kv_format, acoustic_bf16)
         return self
 
     def _init(self, cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format="f32", keep_effective_gpt=False, segment_batch=16,
-              gpt_kv_format=None):
+              gpt_kv_format=None, acoustic_bf16=None):
+        if acoustic_bf16 is not None:
+            _lib.set_acoustic_bf16(bool(acoustic_bf16))
         if device is None:
             device = f"cuda:{torch.cuda.current_device()}" if torch.cuda.is_available() else "cpu"
         self.device = torch.device(device)
