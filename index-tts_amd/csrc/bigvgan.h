@@ -4,6 +4,13 @@
 
 namespace idxtts {
 
+// Activation1d (2x up-sample, SnakeBeta, 2x down-sample) as one kernel (aa_act.hip); dtype of x and y: 0 float32, 1 float16,
+// 2 bfloat16; lens: ragged float32 batches, row b is valid up to lens[b] * len_mul samples
+int aa_act_forward(void* y, const void* x, const float* up_f, const float* down_f, const float* log_alpha,
+                   const float* log_beta, int B, int C, int T, hipStream_t stream, const int* lens = nullptr, int len_mul = 1, int dtype = 0);
+// conv_post (C -> 1, 7 taps, no bias) with the optional clamp to [-1, 1] (conv_post.hip)
+int conv_post_forward(float* y, const float* x, const float* w, int B, int C, int T, int clamp, hipStream_t stream);
+
 struct AmpBlock {          // AMPBlock1 (bigvgan.py:31-141)
   int kernel = 3;
   int dil[3] = {1, 3, 5};

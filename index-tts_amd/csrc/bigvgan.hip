@@ -17,10 +17,6 @@
 
 namespace idxtts {
 
-int aa_act_forward(void* y, const void* x, const float* up_f, const float* down_f, const float* log_alpha,
-                   const float* log_beta, int B, int C, int T, hipStream_t stream, const int* lens = nullptr, int len_mul = 1, int dtype = 0);
-int conv_post_forward(float* y, const float* x, const float* w, int B, int C, int T, int clamp, hipStream_t stream);
-
 // kaiser-sinc low-pass, cutoff 0.25, half-width 0.3, 12 taps (filter.py:30-62), in double.
 static void kaiser_sinc12(float* out) {
   const int K = 12, half = 6;
@@ -67,36 +63,7 @@ static int make_conv(std::map<std::string, HostTensor>& t, DeviceArena& arena, c
     if (need(t, prefix + ".weight", {Cout, Cin, K}, &w)) return 1;
   }
   if (bias && need(t, prefix + ".bias", {Cout}, &b)) return 1;
-  ConvWeights cw;
-  cw.Cin = Cin;
-  cw.nchunk = cdiv(Cin, CONV_KC);
-  cw.ups = ups;
-  if (ups > 1) {
-    IDX_CHECK(K == 2 * ups, "ConvTranspose1d kernel must be 2*stride");
-    cw.M = Cout * ups;
-    cw.K = 3;
-  } else {
-    cw.M = Cout;
-    cw.K = K;
-  }
-  std::vector<float> packed(conv_packed_floats(cw.M, Cin, cw.K));
-  if (ups > 1) pack_conv_transpose1d(packed.data(), w->data.data(), Cin, Cout, K, ups);
-  else pack_conv1d(packed.data(), w->data.data(), Cout, Cin, K);
-  float* d = nullptr;
-  if (arena.upload(packed.data(), packed.size(), &d)) return 1;
-  cw.wp = d;
-  {                     // split-bf16 images (conv1d_bf16x3.hip); same size as the fp32 pack
-    std::vector<float> p16(packed.size());      // hi + lo bf16 = 4 bytes per weight, as the fp32 pack
-    pack_conv_bf16x3(p16.data(), packed.data(), packed.size() / CONV_SUB);
-    if (arena.upload(p16.data(), p16.size(), &d)) return 1;
-    cw.wp16 = d;
-  }
-  if (b) {
-    if (arena.upload(b->data.data(), b->data.size(), &d)) return 1;
-    cw.bias = d;
-  }
-  *out = cw;
-  return 0;
+  return make_conv_weights(arena, w->data.data(), b ? b->data.data() : nullptr, Cout, Cin, K, ups, out);
 }
 
 int BigVGANModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena) {

@@ -27,9 +27,6 @@ int fail(const char* file, int line, const std::string& msg) {
   return 1;
 }
 
-int aa_act_forward(void* y, const void* x, const float* up_f, const float* down_f, const float* log_alpha,
-                   const float* log_beta, int B, int C, int T, hipStream_t stream, const int* lens = nullptr, int len_mul = 1, int dtype = 0);
-
 }  // namespace idxtts
 
 using namespace idxtts;
@@ -88,35 +85,9 @@ int idxtts_conv1d_create(const float* weight, const float* bias, int Cout, int C
   std::unique_ptr<idxtts_conv1d> c(new idxtts_conv1d());
   std::vector<float> hw, hb;
   if (fetch(weight, (size_t)Cout * Cin * K, &hw)) return 1;
+  if (bias && fetch(bias, Cout, &hb)) return 1;
   c->Cout = Cout;
-  c->w.Cin = Cin;
-  c->w.nchunk = cdiv(Cin, CONV_KC);
-  c->w.ups = transposed_stride;
-  if (transposed_stride > 1) {
-    IDX_CHECK(K == 2 * transposed_stride, "ConvTranspose1d kernel must be 2*stride");
-    c->w.M = Cout * transposed_stride;
-    c->w.K = 3;
-  } else {
-    c->w.M = Cout;
-    c->w.K = K;
-  }
-  std::vector<float> packed(conv_packed_floats(c->w.M, Cin, c->w.K));
-  if (transposed_stride > 1) pack_conv_transpose1d(packed.data(), hw.data(), Cin, Cout, K, transposed_stride);
-  else pack_conv1d(packed.data(), hw.data(), Cout, Cin, K);
-  float* d = nullptr;
-  if (c->arena.upload(packed.data(), packed.size(), &d)) return 1;
-  c->w.wp = d;
-  {
-    std::vector<float> p16(packed.size());      // hi + lo bf16 = 4 bytes per weight, as the fp32 pack
-    pack_conv_bf16x3(p16.data(), packed.data(), packed.size() / CONV_SUB);
-    if (c->arena.upload(p16.data(), p16.size(), &d)) return 1;
-    c->w.wp16 = d;
-  }
-  if (bias) {
-    if (fetch(bias, Cout, &hb)) return 1;
-    if (c->arena.upload(hb.data(), hb.size(), &d)) return 1;
-    c->w.bias = d;
-  }
+  if (make_conv_weights(c->arena, hw.data(), bias ? hb.data() : nullptr, Cout, Cin, K, transposed_stride, &c->w)) return 1;
   *out = c.release();
   return 0;
   API_END

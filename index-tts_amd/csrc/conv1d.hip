@@ -1,8 +1,8 @@
-// Implicit-GEMM Conv1d for channels-first activations on the gfx950 fp32 matrix core.
+// Implicit-GEMM Conv1d for channels-first activations on the gfx950 fp32 matrix core: the exact-fp32 arithmetic of the family
+// (conv1d.h), and its host side: the weight packers, the weight builder and conv1d_forward, which BigVGAN (bigvgan.hip) and
+// idxtts_conv1d_fwd (capi.hip) call and which hands the launch to conv1d_bf16x3.hip in the split-bf16 GEMM mode.
 //
-// Replaces (for the vocoder and the s2mel convolutions) what the reference leaves to
-// torch.nn.Conv1d / ConvTranspose1d: bigvgan.py:362,367,136-139,379; wavenet.py:149,161;
-// length_regulator.py:51,61.
+// Replaces what the reference's vocoder leaves to torch.nn.Conv1d / ConvTranspose1d: bigvgan.py:362,367,136-139,379.
 //
 //   y[b][m][t] = bias[m] + sum_{ci,k} W[m][ci][k] * x[b][ci][t + k*dil - pad_left]
 //
@@ -18,11 +18,12 @@
 // Workgroup -> tile map is XCD-aware: blockIdx round-robins over the 8 XCDs, so XCD x takes
 // the n-tiles n = x (mod 8) and walks them m-tile-major; the 32 CUs of an XCD then stream
 // the SAME weight slice through their shared 4 MiB L2 while their x tiles differ.
-#include "conv1d.h"
-#include "conv_epilogue.h"
-#include "gemm.h"
-#include <string>
+#include <vector>
 
+#include "conv_epilogue.h"
+#include "conv_launch.h"
+#include "ctx.h"
+#include "gemm.h"
 #include "prof.h"
 
 namespace idxtts {
@@ -73,10 +74,33 @@ void pack_conv_transpose1d(float* dst, const float* w, int Cin, int Cout, int Kt
       }
 }
 
+int make_conv_weights(DeviceArena& arena, const float* w, const float* bias, int Cout, int Cin, int K, int ups, ConvWeights* out) {
+  if (ups > 1) IDX_CHECK(K == 2 * ups, "ConvTranspose1d kernel must be 2*stride");
+  ConvWeights cw;
+  cw.Cin = Cin; cw.nchunk = cdiv(Cin, CONV_KC); cw.ups = ups;
+  cw.M = ups > 1 ? Cout * ups : Cout;      // a transposed conv: a row per output phase, 3 taps over x[s-1], x[s], x[s+1]
+  cw.K = ups > 1 ? 3 : K;
+  std::vector<float> packed(conv_packed_floats(cw.M, Cin, cw.K));
+  if (ups > 1) pack_conv_transpose1d(packed.data(), w, Cin, Cout, K, ups);
+  else pack_conv1d(packed.data(), w, Cout, Cin, K);
+  float* d = nullptr;
+  void* d16 = nullptr;
+  if (arena.upload(packed.data(), packed.size(), &d)) return 1;
+  cw.wp = d;
+  std::vector<char> p16(conv_packed16_bytes(cw.M, Cin, cw.K));
+  pack_conv_bf16x3(p16.data(), packed.data(), packed.size() / CONV_SUB);
+  if (arena.upload_bytes(p16.data(), p16.size(), &d16)) return 1;
+  cw.wp16 = d16;
+  if (bias && arena.upload(bias, Cout, &d)) return 1;
+  if (bias) cw.bias = d;
+  *out = cw;
+  return 0;
+}
+
 // ----------------------------------------------------------------------------------------
 // kernel
 // ----------------------------------------------------------------------------------------
-struct ConvKP {
+struct ConvKP {           // (all but wp and xs: conv_launch_setup)
   const float* x;
   const float* wp;
   const float* bias;
@@ -233,44 +257,22 @@ __global__ __launch_bounds__(256, (TM == 3 ? 2 : 3)) void conv1d_mfma_kernel(con
   conv_epilogue<TM, TN>(p, acc, m_blk * BM + wm * TM * 32, t0 + wn * TN * 32, b, T, h, j);
 }
 
-template <int TM, int TN, int WGM, int WGN>
+template <class Tile>
 static int launch_conv(const ConvWeights& w, const ConvArgs& a, hipStream_t stream) {
-  constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN, NSUB = TM * WGM;
   ConvKP p;
-  p.x = a.x; p.wp = w.wp; p.bias = w.bias; p.res = a.res; p.y = a.y;
-  p.Cin = w.Cin; p.M = w.M; p.T = a.T;
-  p.K = w.K; p.dil = a.dil; p.pad_left = a.pad_left; p.pad_mode = a.pad_mode;
-  p.nchunk = w.nchunk; p.mt32 = cdiv(w.M, CONV_MT);
-  int ul = 0;
-  while ((1 << ul) < w.ups) ++ul;
-  IDX_CHECK((1 << ul) == w.ups, "transposed-conv stride must be a power of two");
-  p.ups_log2 = ul;
-  const int halo = (w.K - 1) * a.dil;
-  IDX_CHECK(halo <= CONV_MAX_HALO, "(K-1)*dil exceeds CONV_MAX_HALO");
-  p.xt = BN + halo;
-  p.xs = (p.xt + 3) & ~3;
-  p.ntiles_row = cdiv(a.T, BN);
-  p.ntiles = p.ntiles_row * a.B;
-  p.nt8 = cdiv(p.ntiles, 8);
-  p.scale = a.scale; p.accum = a.accum; p.lens = a.lens; p.len_mul_out = a.len_mul_out;
-  const int mblocks = cdiv(w.M, BM);
-  const size_t lds = (size_t)(2 * NSUB * CONV_SUB + 2 * 16 * p.xs) * sizeof(float);
-  const int64_t grid = (int64_t)8 * mblocks * p.nt8;
-  IDX_CHECK(grid > 0 && grid < (1ll << 31), "grid size");
-  auto kern = conv1d_mfma_kernel<TM, TN, WGM, WGN>;
+  ConvGrid grid;
+  if (conv_launch_setup(w, a, Tile::BM, Tile::BN, &p, &grid)) return 1;
+  p.wp = w.wp; p.xs = (p.xt + 3) & ~3;
+  const size_t lds = (size_t)(2 * Tile::NSUB * CONV_SUB + 2 * 16 * p.xs) * sizeof(float);
+  auto kern = conv1d_mfma_kernel<Tile::TM, Tile::TN, Tile::WGM, Tile::WGN>;
   static DynLdsLimit lds_limit;   // one per template instance
   IDX_HIP(lds_limit.set(160 * 1024, kern));
   {
-    // algorithmic work: 2*Cout*Cin*taps per output sample (a transposed conv has Kt/u = 2 live taps
-    // per output, not the 3 the packed form multiplies); bytes = x + y (+ residual / accumulate) + weights once
-    const double cout = (double)(w.M / w.ups), tout = (double)a.T * w.ups * a.B;
-    const double taps = w.ups > 1 ? 2.0 : (double)w.K;
-    const double flops = 2.0 * cout * w.Cin * taps * tout;
-    const double bytes = 4.0 * ((double)a.B * w.Cin * a.T + cout * tout * (1.0 + (a.res ? 1.0 : 0.0) + (a.accum ? 1.0 : 0.0)) +
-                                cout * w.Cin * (w.ups > 1 ? 2.0 * w.ups : (double)w.K));
-    static const int cat = prof_register(("conv1d_mfma_kernel<" + std::to_string(TM) + ", " + std::to_string(TN) + ", " + std::to_string(WGM) + ", " + std::to_string(WGN) + ">").c_str());
+    double flops, bytes;
+    conv_work(w, a, &flops, &bytes);
+    static const int cat = prof_register(conv_category<Tile>("conv1d_mfma_kernel").c_str());
     ProfScope prof(cat, stream, flops, bytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(kern, dim3(grid.blocks), dim3(256), lds, stream, p);
   }
   IDX_LAUNCH_CHECK();
   return 0;
@@ -281,10 +283,7 @@ int conv1d_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream) 
   IDX_CHECK(a.B > 0 && a.T > 0, "empty shape");
   if (a.pad_mode == PAD_REFLECT) IDX_CHECK(a.T > (w.K - 1) * a.dil, "reflect pad needs T > halo");
   if (w.wp16 && get_gemm_mode() == GEMM_BF16X3) return conv1d_bf16x3_forward(w, a, stream, acoustic_bf16_active() ? 1 : 3);
-  if (w.M > 96) return launch_conv<2, 2, 2, 2>(w, a, stream);   // 128 x 128
-  if (w.M > 64) return launch_conv<3, 2, 1, 4>(w, a, stream);   //  96 x 256
-  if (w.M > 32) return launch_conv<2, 2, 1, 4>(w, a, stream);   //  64 x 256
-  return launch_conv<1, 4, 1, 4>(w, a, stream);                 //  32 x 512
+  return conv_tile_dispatch(w.M, [&](auto tile) { return launch_conv<decltype(tile)>(w, a, stream); });
 }
 
 }  // namespace idxtts

@@ -1,8 +1,10 @@
-// Split-bf16 variant of the channels-first implicit-GEMM Conv1d (conv1d.hip) for the wide vocoder layers (M > 96 rows:
-// conv_pre, the first four upsamplers and AMP-block stages of BigVGAN, bigvgan.py:362-379): same tiling, same epilogue,
+// The bf16 arithmetics of the channels-first implicit-GEMM Conv1d (conv1d.h): conv1d_forward (conv1d.hip) sends every layer of
+// BigVGAN and every idxtts_conv1d_fwd call here, in all four tile configurations, while the GEMM mode is GEMM_BF16X3;
+// tools/gemv_stress.hip calls conv1d_bf16x3_forward directly.  Same tiling, same epilogue as the fp32 kernel,
 // but the contraction runs on v_mfma_f32_32x32x16_bf16 with every fp32 operand written as hi + lo (bf16 each) and three
 // MFMAs per product (hi*hi + hi*lo + lo*hi, fp32 accumulation; relative product error ~2^-16).  12 bf16 MFMAs (384
-// cycles) per (16-channel chunk, tap) and 64 x 64 wave tile instead of 32 f32 MFMAs (2048 cycles).
+// cycles) per (16-channel chunk, tap) and 64 x 64 wave tile instead of 32 f32 MFMAs of 64 cycles each.  The opt-in acoustic bf16
+// arithmetic (NP = 1 below) keeps hi*hi alone.
 //
 // What changes against the fp32 kernel is the x tile: the bf16 MFMA wants the 8 input channels of a k-slot group packed
 // in ONE lane, so the tile is stored time-major in LDS, [t][16 ci] bf16 (32-byte rows, hi and lo planes).  The loader
@@ -12,13 +14,10 @@
 // conflict-free).  Weights are permuted once at load from the fp32 pack into per-sub-tile [hl][g2][i32][8] bf16 images
 // (same 2 KiB per sub-tile and tap).
 #include <cstdlib>
-#include <cstring>
 
-#include "conv1d.h"
 #include "conv_epilogue.h"
+#include "conv_launch.h"
 #include "gemm_common.h"
-#include <string>
-
 #include "prof.h"
 
 namespace idxtts {
@@ -31,8 +30,8 @@ void pack_conv_bf16x3(void* dst, const float* packed_f32, size_t n_subtiles) {
   uint16_t* o = static_cast<uint16_t*>(dst);
   for (size_t s = 0; s < n_subtiles; ++s) {
     const float* src = packed_f32 + s * CONV_SUB;
-    uint16_t* hi = o + s * 1024;      // 2 planes x 512 bf16
-    uint16_t* lo = hi + 512;
+    uint16_t* hi = o + s * (CONV_SUB16_BYTES / 2);      // 2 planes x CONV_SUB bf16
+    uint16_t* lo = hi + CONV_SUB;
     for (int g = 0; g < 2; ++g)
       for (int h = 0; h < 2; ++h)
         for (int i = 0; i < 32; ++i)
@@ -46,7 +45,7 @@ void pack_conv_bf16x3(void* dst, const float* packed_f32, size_t n_subtiles) {
   }
 }
 
-struct ConvKP16 {
+struct ConvKP16 {         // (all but wp16, mblocks, walk and the w_ fields: conv_launch_setup)
   const float* x;
   const void* wp16;
   const float* bias;
@@ -64,7 +63,7 @@ struct ConvKP16 {
   int accum;
   const int* lens; int len_mul_out;
   int w_bytes;            // size of the weight pack (buffer resource bound)
-  int w_mt_stride;        // bytes between two 32-row sub-tiles of the pack: nchunk * K * 2048
+  int w_mt_stride;        // bytes between two 32-row sub-tiles of the pack: nchunk * K * CONV_SUB16_BYTES
 };
 
 constexpr int XROW_B = 32;            // bytes per LDS x row (16 ci bf16)
@@ -93,7 +92,7 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
   extern __shared__ __attribute__((aligned(16))) char smem16[];
   // bytes of a weight ring slot: what NWL DMA instructions of 256 lanes x 16 B write; the one-sub-tile configuration (2 KiB per step)
   // lets only waves 0 and 1 request, so that its 74 KiB of x planes + ring stay under half a CU's LDS (two workgroups per CU)
-  constexpr int WSLOT = NSUB == 1 ? 2048 : NWL * 4096;
+  constexpr int WSLOT = NSUB == 1 ? CONV_SUB16_BYTES : NWL * 4096;
   // a tile is requested DIST steps ahead of its use.  (3 steps ahead for the narrow tiles was measured: the fourth ring slot took the
   // 64 x 256 configuration from three workgroups per CU to two: 188 -> 158 TF-eq.)
   constexpr int DIST = 2;
@@ -175,7 +174,7 @@ __device__ __forceinline__ void conv1d_bf16x3_body(const ConvKP16& p) {
   }
   char* const lds_w = Ws + wave * 1024;
   auto request_w = [&](int slot, int chunk, int tap) {
-    const int so = (chunk * p.K + tap) * 2048;
+    const int so = (chunk * p.K + tap) * CONV_SUB16_BYTES;
     if (NSUB == 1 && wave >= SUB4 / 64) return;      // (wave-uniform; waves 2 and 3 hold no weight request: their counted waits only see x loads)
 #pragma unroll
     for (int l = 0; l < NWL; ++l)
@@ -278,71 +277,45 @@ __global__ __launch_bounds__(256, (TM == 3 ? 2 : 3)) void conv1d_bf16x3_kernel(c
   conv1d_bf16x3_body<TM, TN, WGM, WGN, K1, NP>(p);
 }
 
-template <int TM, int TN, int WGM, int WGN, bool K1>
+template <class Tile, bool K1>
 static int launch_conv16(const ConvWeights& w, const ConvArgs& a, hipStream_t stream, int products) {
-  constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN, NSUB = TM * WGM;
-  constexpr int XT_MAX = BN + CONV_MAX_HALO;
-  IDX_CHECK(w.wp16 && a.x && a.y, "null pointer");
+  constexpr int TM = Tile::TM, TN = Tile::TN, WGM = Tile::WGM, WGN = Tile::WGN, NSUB = Tile::NSUB;
+  constexpr int XT_MAX = Tile::BN + CONV_MAX_HALO;
+  IDX_CHECK(w.wp16, "null pointer");
   ConvKP16 p;
-  p.x = a.x; p.wp16 = w.wp16; p.bias = w.bias; p.res = a.res; p.y = a.y;
-  p.Cin = w.Cin; p.M = w.M; p.T = a.T;
-  p.K = w.K; p.dil = a.dil; p.pad_left = a.pad_left; p.pad_mode = a.pad_mode;
-  p.nchunk = w.nchunk; p.mt32 = cdiv(w.M, CONV_MT);
-  int ul = 0;
-  while ((1 << ul) < w.ups) ++ul;
-  IDX_CHECK((1 << ul) == w.ups, "transposed-conv stride must be a power of two");
-  p.ups_log2 = ul;
-  const int halo = (w.K - 1) * a.dil;
-  IDX_CHECK(halo <= CONV_MAX_HALO, "(K-1)*dil exceeds CONV_MAX_HALO");
-  p.xt = BN + halo;
-  p.ntiles_row = cdiv(a.T, BN);
-  p.ntiles = p.ntiles_row * a.B;
-  p.nt8 = cdiv(p.ntiles, 8);
-  p.scale = a.scale; p.accum = a.accum; p.lens = a.lens; p.len_mul_out = a.len_mul_out;
-  const int mblocks = cdiv(w.M, BM);
+  ConvGrid grid;
+  if (conv_launch_setup(w, a, Tile::BM, Tile::BN, &p, &grid)) return 1;
+  p.wp16 = w.wp16; p.mblocks = grid.mblocks;
   // Tile walk, per shape (FETCH_SIZE per launch under both walks: profiles/r04_conv_walk_pmc.txt): row blocks fastest -- x leaves HBM once,
   // the row blocks' weight slices stream through the XCD's L2 once per round of resident workgroups -- unless the layer's weights are so
   // large (> 20 MB: the first upsampler, the 768-channel k = 11 convolutions) that this stream outweighs the x re-reads it saves.
   // IDXTTS_CONV_WALK = 0 / 1 forces one walk for that comparison.
   static const int walk_env = [] { const char* e = getenv("IDXTTS_CONV_WALK"); return e ? atoi(e) : -1; }();
   const double weight_bytes = 4.0 * w.M * (double)w.Cin * w.K;
-  p.mblocks = mblocks;
-  p.walk = mblocks > 1 && (walk_env >= 0 ? walk_env == 1 : weight_bytes <= 20e6) ? 1 : 0;
+  p.walk = p.mblocks > 1 && (walk_env >= 0 ? walk_env == 1 : weight_bytes <= 20e6) ? 1 : 0;
   constexpr int NWL = (NSUB * 128 + 255) / 256;      // (the ring keeps the split form's slots under NP = 1)
-  const size_t lds = (size_t)3 * (NSUB == 1 ? 2048 : NWL * 4096) + (size_t)2 * 2 * XT_MAX * XROW_B;
-  const size_t w_bytes = (size_t)cdiv(w.M, CONV_MT) * w.nchunk * w.K * 2048;
+  const size_t lds = (size_t)3 * (NSUB == 1 ? CONV_SUB16_BYTES : NWL * 4096) + (size_t)2 * 2 * XT_MAX * XROW_B;
+  const size_t w_bytes = conv_packed16_bytes(w.M, w.Cin, w.K);
   IDX_CHECK(w_bytes < (1ull << 31), "weight pack beyond the 2 GiB a buffer offset addresses");
-  p.w_bytes = (int)w_bytes; p.w_mt_stride = w.nchunk * w.K * 2048;
-  const int64_t grid = (int64_t)8 * mblocks * p.nt8;
-  IDX_CHECK(grid > 0 && grid < (1ll << 31), "grid size");
+  p.w_bytes = (int)w_bytes; p.w_mt_stride = w.nchunk * w.K * CONV_SUB16_BYTES;
   auto kern = products == 1 ? conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 1> : conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 3>;
   static DynLdsLimit lds_limit;
   IDX_HIP(lds_limit.set(160 * 1024, conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 3>, conv1d_bf16x3_kernel<TM, TN, WGM, WGN, K1, 1>));
-  const double cout = (double)(w.M / w.ups), tout = (double)a.T * w.ups * a.B;
-  const double taps = w.ups > 1 ? 2.0 : (double)w.K;
-  const double flops = 2.0 * cout * w.Cin * taps * tout;
-  const double bytes = 4.0 * ((double)a.B * w.Cin * a.T + cout * tout * (1.0 + (a.res ? 1.0 : 0.0) + (a.accum ? 1.0 : 0.0)) +
-                              cout * w.Cin * (w.ups > 1 ? 2.0 * w.ups : (double)w.K));
-  const std::string kname = "conv1d_bf16x3_kernel<" + std::to_string(TM) + ", " + std::to_string(TN) + ", " + std::to_string(WGM) + ", " + std::to_string(WGN) + (K1 ? ", true" : ", false");
-  static const int cat = prof_register((kname + ">").c_str()), cat1 = prof_register((kname + ", 1>").c_str());
+  double flops, bytes;
+  conv_work(w, a, &flops, &bytes);
+  static const int cat = prof_register(conv_category<Tile>("conv1d_bf16x3_kernel", K1 ? ", true" : ", false").c_str()),
+                   cat1 = prof_register(conv_category<Tile>("conv1d_bf16x3_kernel", K1 ? ", true, 1" : ", false, 1").c_str());
   ProfScope prof(products == 1 ? cat1 : cat, stream, flops, bytes);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, stream, p);
+  hipLaunchKernelGGL(kern, dim3(grid.blocks), dim3(256), lds, stream, p);
   IDX_LAUNCH_CHECK();
   return 0;
 }
 
-// same tile configurations as conv1d_forward; products (3 or 1) selects the instance of the configuration
+// products (3 or 1) selects the instance of the tile configuration; a 1-tap convolution has an instance of its own (K1 above)
 int conv1d_bf16x3_forward(const ConvWeights& w, const ConvArgs& a, hipStream_t stream, int products) {
-  if (w.K == 1) {
-    if (w.M > 96) return launch_conv16<2, 2, 2, 2, true>(w, a, stream, products);
-    if (w.M > 64) return launch_conv16<3, 2, 1, 4, true>(w, a, stream, products);
-    if (w.M > 32) return launch_conv16<2, 2, 1, 4, true>(w, a, stream, products);
-    return launch_conv16<1, 4, 1, 4, true>(w, a, stream, products);
-  }
-  if (w.M > 96) return launch_conv16<2, 2, 2, 2, false>(w, a, stream, products);   // 128 x 128
-  if (w.M > 64) return launch_conv16<3, 2, 1, 4, false>(w, a, stream, products);   //  96 x 256
-  if (w.M > 32) return launch_conv16<2, 2, 1, 4, false>(w, a, stream, products);   //  64 x 256
-  return launch_conv16<1, 4, 1, 4, false>(w, a, stream, products);                 //  32 x 512
+  return conv_tile_dispatch(w.M, [&](auto tile) {
+    return w.K == 1 ? launch_conv16<decltype(tile), true>(w, a, stream, products) : launch_conv16<decltype(tile), false>(w, a, stream, products);
+  });
 }
 
 }  // namespace idxtts

@@ -41,20 +41,27 @@ def test_constants_match_the_sources():
     for name in ("AA_TILE", "AA_TPW", "AA_XH", "AA_VH"):
         assert _const(aa, name) == getattr(dc, name), f"{name}: {REDERIVE}"
     assert _const(_src("conv1d.h"), "CONV_MAX_HALO") == dc.CONV_MAX_HALO, f"CONV_MAX_HALO: {REDERIVE}"
-    launch = re.compile(r"if \(w\.M > (\d+)\) return launch_conv(?:16)?<(\d), (\d), (\d), (\d)(?:, (?:true|false))?>")
-    last = re.compile(r"\n\s+return launch_conv(?:16)?<(\d), (\d), (\d), (\d)(?:, (?:true|false))?>")
-    bodies = [_forward_body(_src("conv1d.hip"), "conv1d_forward")]
-    b16 = _forward_body(_src("conv1d_bf16x3.hip"), "conv1d_bf16x3_forward")
-    k1_part, rest = b16.split("}\n", 1)                      # the `if (w.K == 1) { ... }` block, then the K > 1 table
-    assert "w.K == 1" in k1_part and "true>" in k1_part and "true>" not in rest, f"K1 dispatch: {REDERIVE}"
-    bodies += [k1_part, rest]
-    for body in bodies:
-        rows = launch.findall(body)
-        assert tuple(int(r[0]) for r in rows) == dc.CONV_M_THRESHOLDS, f"M thresholds: {REDERIVE}"
-        tiles = [(32 * int(tm) * int(wgm), 32 * int(tn) * int(wgn)) for _, tm, tn, wgm, wgn in rows]
-        tm, tn, wgm, wgn = (int(v) for v in last.findall(body)[-1])
-        tiles.append((32 * tm * wgm, 32 * tn * wgn))
-        assert tuple(tiles) == dc.CONV_CONFIGS, f"tile configurations: {REDERIVE}"
+    # the one tile table (conv1d.h: conv_tile_dispatch) ...
+    header = _src("conv1d.h")
+    m = re.search(r"\nstatic inline int conv_tile_dispatch\(int M, F&& f\) \{\n(.*?)\n\}\n", header, re.S)
+    assert m, "conv_tile_dispatch not found"
+    table = m.group(1)
+    rows = re.findall(r"if \(M > (\d+)\) return f\(ConvTile<(\d), (\d), (\d), (\d)>\{\}\);", table)
+    last = re.findall(r"\n\s+return f\(ConvTile<(\d), (\d), (\d), (\d)>\{\}\);", table)
+    assert len(rows) + len(last) == len(re.findall(r"ConvTile<\d", header)) == 4, "one table of four configurations"
+    assert tuple(int(r[0]) for r in rows) == dc.CONV_M_THRESHOLDS, f"M thresholds: {REDERIVE}"
+    tiles = [(int(tm), int(tn), int(wgm), int(wgn)) for _, tm, tn, wgm, wgn in rows] + [tuple(int(v) for v in last[-1])]
+    assert tuple((32 * tm * wgm, 32 * tn * wgn) for tm, tn, wgm, wgn in tiles) == dc.CONV_CONFIGS, f"tile configurations: {REDERIVE}"
+    assert "BM = 32 * TM_ * WGM_, BN = 32 * TN_ * WGN_" in header, f"tile size of a configuration: {REDERIVE}"
+    # ... which both forward functions go through, the bf16 one with a separate K == 1 instance; no second table in either file
+    f32, b16 = _src("conv1d.hip"), _src("conv1d_bf16x3.hip")
+    assert "return conv_tile_dispatch(w.M, " in _forward_body(f32, "conv1d_forward")
+    body16 = _forward_body(b16, "conv1d_bf16x3_forward")
+    assert "return conv_tile_dispatch(w.M, " in body16
+    assert re.search(r"w\.K == 1 \? launch_conv16<decltype\(tile\), true>\(.*?\) : launch_conv16<decltype\(tile\), false>\(", body16), \
+        f"K1 dispatch: {REDERIVE}"
+    for text in (f32, b16):
+        assert not re.search(r"launch_conv(?:16)?<\d, \d, \d, \d", text) and "ConvTile<" not in text, "a second tile table"
     m = re.search(r"weight_bytes <= ([0-9.e]+)", _src("conv1d_bf16x3.hip"))
     assert m and float(m.group(1)) == dc.CONV_WALK_BYTES, f"walk limit: {REDERIVE}"
     assert "4.0 * w.M * (double)w.Cin * w.K" in _src("conv1d_bf16x3.hip"), f"walk's weight bytes: {REDERIVE}"

@@ -30,7 +30,7 @@ CONV_WALK_BYTES = 20e6
 
 
 def conv_config(M: int):
-    """(BM, BN) of conv1d_forward / conv1d_bf16x3_forward for M GEMM rows."""
+    """(BM, BN) of conv_tile_dispatch (conv1d.h: the one table of conv1d_forward and conv1d_bf16x3_forward) for M GEMM rows."""
     for thr, cfg in zip(CONV_M_THRESHOLDS, CONV_CONFIGS):
         if M > thr:
             return cfg
@@ -47,7 +47,7 @@ def row_blocks(M: int) -> int:
 
 
 def walk(M: int, Cin: int, K: int) -> int:
-    """launch_conv16's tile walk (M, K as the GEMM sees them: a transposed conv has M = Cout * u rows and 3 taps)."""
+    """The bf16 kernels' tile walk, chosen in launch_conv16 of conv1d_bf16x3.hip (M, K as the GEMM sees them: a transposed conv has M = Cout * u rows and 3 taps)."""
     return 1 if row_blocks(M) > 1 and 4.0 * M * Cin * K <= CONV_WALK_BYTES else 0
 
 

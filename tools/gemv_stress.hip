@@ -35,7 +35,7 @@ int main(int argc, char** argv) {
   // the hog: Conv1d(C -> C, taps) over [16][C][T]
   const int Bc = 16;
   ConvWeights cw; cw.M = C; cw.Cin = C; cw.K = taps; cw.nchunk = (C + 15) / 16; cw.ups = 1;
-  const size_t wbytes = (size_t)((C + 31) / 32) * cw.nchunk * taps * 2048;
+  const size_t wbytes = conv_packed16_bytes(cw.M, cw.Cin, cw.K);
   void* cwp; CK(hipMalloc(&cwp, wbytes)); CK(hipMemset(cwp, 0x3c, wbytes));      // bf16 0x3c3c = 0.0115
   cw.wp16 = cwp;
   float *cx, *cy; CK(hipMalloc(&cx, (size_t)Bc * C * T * 4)); CK(hipMalloc(&cy, (size_t)Bc * C * T * 4));
