@@ -76,6 +76,10 @@ int idxtts_ctx_destroy(idxtts_ctx* ctx);
 /* OCP fp8 e4m3fn value of a code / nearest-even saturating code of a value (host helpers of the fp8 weight format). */
 float idxtts_fp8_e4m3_decode(unsigned char code);
 unsigned char idxtts_fp8_e4m3_encode(float v);
+/* Instrument: the quantiser of the scaled-fp8 KV cache (IDXTTS_KV_FP8 below) on n_vectors device vectors x [n_vectors][64] ->
+ * codes [n_vectors][64], scales [n_vectors] (device pointers).  The very device routine the cache's producers call; it plays for the
+ * cache the role idxtts_fp8_e4m3_encode plays for the weights. */
+int idxtts_kv_fp8_quantize(const float* x, int n_vectors, unsigned char* codes, float* scales, void* stream);
 
 /* ---- BigVGAN-v2 vocoder (reference: BigVGAN.forward, bigvgan.py:360-386) ------------------------- */
 typedef struct idxtts_bigvgan_config {
@@ -245,7 +249,29 @@ int idxtts_gpt_quantize_weights(idxtts_ctx* ctx, int format);
  * is produced -- in the prefill (whose own attention then reads the rounded values) and in every decode step (the new token's own
  * k / v included) -- and every product and sum stays fp32; the decode attention streams half the bytes (the KV read is the largest
  * HBM stream of a batched decode step: 1.7 GB against 1.0 GB of bf16 weights at 16 utterances).  The latent pass has no cache and
- * is unchanged.  Call any time between generations on the context; idxtts_gpt_workspace_bytes follows the format. */
+ * is unchanged.  Call any time between generations on the context; idxtts_gpt_workspace_bytes follows the format.
+ *
+ * 2 = IDXTTS_KV_FP8, scaled fp8: opt-in, never selected implicitly (not with fp8 weights either).  The contract:
+ *   unit    one vector: the 64 head dims of one (layer, row, head, position); a key vector and a value vector separately, same rule
+ *   scale   amax = max |x_i| over the fp32 values; s = 2^ceil(log2(amax / 448)), exponent clamped to [-100, 100] (the weight columns'
+ *           rule), s = 1 when amax == 0.  Computed exactly from amax's exponent and mantissa (448 = 1.75 * 2^8)
+ *   code    the OCP e4m3fn encoding of x_i / s, nearest with ties to the even code; |x_i / s| <= 448, so nothing ever saturates
+ *   value   decode(code_i) * s, an exact fp32 product; every product and sum of the attention stays fp32
+ *   when    once, when the key / value is produced: in the prefill (the k / v columns are replaced by the cached values, so the
+ *           prefill attention reads them) and in every decode step, the new token's own k / v included
+ *   Non-finite inputs, and amax above 448 * 2^100, are outside the contract.
+ * Storage: one byte per element in the bf16 cache's arrangement, plus one fp32 scale per cached vector ([layer][row][head][position],
+ * for K and for V) in the same caller-owned workspace: 68 bytes per vector against 128 for bf16; every *_workspace_bytes entry counts
+ * them.  (fp32 scales, not one-byte exponents: the reader multiplies a score or a probability by the scale as loaded.)  The call fails
+ * on a device whose f32 <-> fp8 conversions are not OCP e4m3fn (checked against the host codec on every code and every midpoint).
+ * The prefill of an fp8 cache runs on the exact fp32 GEMMs in every arithmetic mode, like that of an fp32 cache: the split-bf16 GEMM's
+ * 2^-16 moves a key / value across an e4m3 rounding boundary 250 x as often as an fp32 summation order does (measured: max |dlogit|
+ * against the oracle 5.5e-2 with the split prefill, 1.8e-2 with the exact one).  Everywhere else the format follows the bf16 cache's
+ * rules.  Measured on MI355X (profiles/README.md "fp8 KV cache"): half the cache memory; the decode attention's time per step and
+ * the logit noise are tabulated there. */
+#define IDXTTS_KV_F32 0
+#define IDXTTS_KV_BF16 1
+#define IDXTTS_KV_FP8 2
 int idxtts_gpt_set_kv_format(idxtts_ctx* ctx, int format);
 int idxtts_gpt_get_kv_format(const idxtts_ctx* ctx);
 /* Greedy generations keep their instantiated decode-step hipGraph per (workspace address and size, B, prompt length, max_new_tokens,

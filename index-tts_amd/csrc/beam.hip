@@ -483,11 +483,12 @@ __global__ __launch_bounds__(1024) void beam_reorder_rows_kernel(const BeamState
   }
 }
 
-// KV rows of the generated positions [prompt_len, pos]: 16-byte granules (G per key: 16 in a fp32 cache, 8 in a bf16 one), a thread moves
-// one granule of all nb beams
+// KV rows of the generated positions [prompt_len, pos]: granules of type GT (G per key: 16 x 16 bytes in a fp32 cache, 8 x 16 in a bf16
+// one, 8 x 8 in an fp8 one), a thread moves one granule of all nb beams; an fp8 cache's scales of the same positions move with the
+// same ancestry
 // SESSION: blockIdx.y -> group; nothing moves for a group that is not live, has just finished or is at its cap.  The range starts at
 // pos - step + 1 = P_g + 1 (admission: pos = P_g, step 0), so npos = step.
-template <bool SESSION>
+template <bool SESSION, class GT>
 __global__ __launch_bounds__(256) void beam_reorder_kv_kernel(const BeamState p) {
   const int nb = p.nb;
   int b = blockIdx.y, pos, prompt_len;
@@ -506,25 +507,48 @@ __global__ __launch_bounds__(256) void beam_reorder_kv_kernel(const BeamState p)
   const int npos = pos - prompt_len + 1;
   if (npos <= 0) return;
   const int R = p.B * nb, H = p.H, Smax = p.Smax, G = p.kv_gran;
-  f32x4* const kc = static_cast<f32x4*>(p.kcache);
-  f32x4* const vc = static_cast<f32x4*>(p.vcache);
+  GT* const kc = static_cast<GT*>(p.kcache);
+  GT* const vc = static_cast<GT*>(p.vcache);
   const long items = (long)p.L * H * G * npos;
   for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
     const int lh = (int)(it / (G * npos)), rem = (int)(it - (long)lh * G * npos);
     const int l = lh / H, h = lh - l * H;
     {   // K: [L][R][H][G][Smax] granules
       const int c = rem / npos, s = prompt_len + (rem - c * npos);
-      f32x4 v[BEAM_MAX];
+      GT v[BEAM_MAX];
       for (int j = 0; j < nb; ++j) v[j] = kc[((((size_t)l * R + src[j]) * H + h) * G + c) * Smax + s];
       for (int j = 0; j < nb; ++j) kc[((((size_t)l * R + b * nb + j) * H + h) * G + c) * Smax + s] = v[j];
     }
     {   // V: [L][R][H][Smax][G] granules
       const int s = prompt_len + rem / G, k = rem - (rem / G) * G;
-      f32x4 v[BEAM_MAX];
+      GT v[BEAM_MAX];
       for (int j = 0; j < nb; ++j) v[j] = vc[((((size_t)l * R + src[j]) * H + h) * Smax + s) * G + k];
       for (int j = 0; j < nb; ++j) vc[((((size_t)l * R + b * nb + j) * H + h) * Smax + s) * G + k] = v[j];
     }
   }
+  if constexpr (sizeof(GT) == 8) {      // the fp8 cache (8-byte granules): its scales [L][R][H][Smax], K and V
+    const long sitems = (long)p.L * H * npos;
+    for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < sitems; it += (long)gridDim.x * 256) {
+      const int lh = (int)(it / npos), s = prompt_len + (int)(it - (long)lh * npos);
+      const int l = lh / H, h = lh - l * H;
+      float kv[BEAM_MAX], vv[BEAM_MAX];
+      for (int j = 0; j < nb; ++j) {
+        const size_t at = (((size_t)l * R + src[j]) * H + h) * Smax + s;
+        kv[j] = p.kscale[at]; vv[j] = p.vscale[at];
+      }
+      for (int j = 0; j < nb; ++j) {
+        const size_t at = (((size_t)l * R + b * nb + j) * H + h) * Smax + s;
+        p.kscale[at] = kv[j]; p.vscale[at] = vv[j];
+      }
+    }
+  }
+}
+
+// the launch for the cache's granule width
+template <bool SESSION>
+static void launch_beam_reorder_kv(const BeamState& s, hipStream_t st) {
+  if (s.kscale) hipLaunchKernelGGL((beam_reorder_kv_kernel<SESSION, u32x2>), dim3(256, s.B), dim3(256), 0, st, s);
+  else hipLaunchKernelGGL((beam_reorder_kv_kernel<SESSION, f32x4>), dim3(256, s.B), dim3(256), 0, st, s);
 }
 
 int beam_reorder_forward(const BeamState& s, hipStream_t st) {
@@ -534,7 +558,7 @@ int beam_reorder_forward(const BeamState& s, hipStream_t st) {
     static const int cat_s = prof_register("beam_select_kernel + beam_reorder_kv_kernel + beam_reorder_rows_kernel (session)");
     ProfScope prof(cat_s, st, 0.0, 0.0);
     if (!s.group_ids) {      // (an admission is step 0: no generated position to move)
-      hipLaunchKernelGGL(beam_reorder_kv_kernel<true>, dim3(256, s.B), dim3(256), 0, st, s);
+      launch_beam_reorder_kv<true>(s, st);
       IDX_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(beam_reorder_rows_kernel<true>, dim3(s.group_ids ? s.n_ids : s.B), dim3(1024), 0, st, s);
@@ -545,7 +569,7 @@ int beam_reorder_forward(const BeamState& s, hipStream_t st) {
   IDX_LAUNCH_CHECK();
   static const int cat = prof_register("beam_select_kernel + beam_reorder_rows_kernel + beam_reorder_kv_kernel");
   ProfScope prof(cat, st, 0.0, 0.0);
-  hipLaunchKernelGGL(beam_reorder_kv_kernel<false>, dim3(256, s.B), dim3(256), 0, st, s);
+  launch_beam_reorder_kv<false>(s, st);
   IDX_LAUNCH_CHECK();
   return 0;
 }

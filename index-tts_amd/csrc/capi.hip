@@ -159,6 +159,13 @@ int idxtts_ctx_destroy(idxtts_ctx* ctx) {
 float idxtts_fp8_e4m3_decode(unsigned char code) { return fp8_e4m3_decode(code); }
 unsigned char idxtts_fp8_e4m3_encode(float v) { return fp8_e4m3_encode(v); }
 
+int idxtts_kv_fp8_quantize(const float* x, int n_vectors, unsigned char* codes, float* scales, void* stream) {
+  API_BEGIN
+  if (fp8_check_device_decode(nullptr) || fp8_check_device_encode(nullptr)) return 1;
+  return kv_fp8_quantize(x, n_vectors, codes, scales, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_bigvgan_create(const idxtts_bigvgan_config* cfg, idxtts_ctx** out) {
   API_BEGIN
   IDX_CHECK(cfg && out, "null pointer");
@@ -324,9 +331,11 @@ int idxtts_gpt_quantize_weights(idxtts_ctx* ctx, int format) {
 int idxtts_gpt_set_kv_format(idxtts_ctx* ctx, int format) {
   API_BEGIN
   IDX_CHECK(ctx, "null ctx");
-  IDX_CHECK(format == 0 || format == 1, "KV cache format: 0 (fp32) or 1 (bf16)");
+  IDX_CHECK(format == 0 || format == 1 || format == 2, "KV cache format: 0 (fp32), 1 (bf16) or 2 (scaled fp8)");
   auto* m = dynamic_cast<GPTModel*>(ctx->model.get());
   IDX_CHECK(m, "not a GPT context");
+  // scaled fp8 needs a device whose conversions are OCP e4m3fn, both ways (as idxtts_gpt_quantize_weights(ctx, 2) does for decoding)
+  if (format == 2 && (fp8_check_device_decode(nullptr) || fp8_check_device_encode(nullptr))) return 1;
   // a generation in flight has carved its workspace for the current format: switching under it would overrun the cache
   IDX_CHECK(m->kv_fmt == format || m->generating.load() == 0, "a generation is in flight on this context: switch the KV format between generations");
   m->kv_fmt = format;      // cached decode graphs carry the format in their key; workspace sizes follow idxtts_gpt_workspace_bytes

@@ -23,9 +23,12 @@ struct SlotState {
 struct DecodeAttnArgs {
   const float* qkv_part = nullptr; int parts = 0; int part_rows = 0;   // [parts][part_rows][3d] c_attn split-K slab
   const float* qkv_bias = nullptr;                                      // [3d]
-  // this layer's cache.  kv16 = 0: fp32, K [B][H][16][Smax][4], V [B][H][Smax][64].  kv16 = 1: bf16 (rounded to nearest even when a
-  // key / value is produced, the new token's own included), K [B][H][8][Smax][8], V [B][H][Smax][64]: 16-byte granules either way
-  void* kcache = nullptr; void* vcache = nullptr; int kv16 = 0;
+  // this layer's cache.  kv_fmt = 0: fp32, K [B][H][16][Smax][4], V [B][H][Smax][64].  kv_fmt = 1: bf16 (rounded to nearest even when a
+  // key / value is produced, the new token's own included), K [B][H][8][Smax][8], V [B][H][Smax][64]: 16-byte granules either way.
+  // kv_fmt = 2: scaled fp8 (kv_fp8.h), the bf16 geometry with one-byte codes -- K [B][H][8][Smax][8], V [B][H][Smax][64], 8-byte
+  // granules -- and one fp32 scale per cached vector, kscale / vscale [B][H][Smax]
+  void* kcache = nullptr; void* vcache = nullptr; int kv_fmt = 0;
+  float* kscale = nullptr; float* vscale = nullptr;
   float* out = nullptr;                                                 // [B][d] as A-fragment images (frag_index), or
   float* out_row = nullptr;                                             // as fp32 rows [B][d] (the plane GEMV's input, gemv_pl.h)
   const int* kstart = nullptr;                                          // [B] first valid key (left pad), or null
@@ -151,14 +154,24 @@ __device__ __forceinline__ void embed_row_pl(float* x_row, float* x_stats, const
 }
 
 int advance_state(DecodeState* st, hipStream_t stream);
-// qkv [B][S][3d] -> caches, positions [0, S).  kv16: the caches hold bf16 and the k / v columns of qkv are rounded IN PLACE, so the
-// prefill attention that follows sees exactly the keys and values later steps read from the cache
-int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, int H, int S, int Smax, int d, hipStream_t stream);
+// The cache one layer's producers write: kcache / vcache in format fmt (DecodeAttnArgs::kv_fmt); kscale / vscale: the fp8 format's
+// scales [rows][H][Smax], else null
+struct KvDst {
+  void* kcache = nullptr; void* vcache = nullptr; int fmt = 0;
+  float* kscale = nullptr; float* vscale = nullptr;
+};
+// qkv [B][S][3d] -> caches, positions [0, S).  bf16 / fp8: the k / v columns of qkv are rounded IN PLACE to what the cache holds, so
+// the prefill attention that follows sees exactly the keys and values later steps read from the cache
+int kv_store_prefill(float* qkv, const KvDst& kv, int B, int H, int S, int Smax, int d, hipStream_t stream);
 // Decode-session admission: the same for a right-padded prefill of n rows whose cache rows are the slots slot_ids[b]: positions
-// [0, len[b]) of row b go to slot slot_ids[b] (kcache / vcache laid out for `slots` rows); k / v columns rounded in place for kv16.
+// [0, len[b]) of row b go to slot slot_ids[b] (the caches laid out for `slots` rows); k / v columns rounded in place as above.
 // fan > 1 (beam sessions): row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1
-int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
-                   const int* len, hipStream_t stream, int fan = 1);
+int kv_store_slots(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len,
+                   hipStream_t stream, int fan = 1);
+// Instrument (idxtts_kv_fp8_quantize): the fp8 cache's quantiser on n vectors x [n][64] -> codes [n][64], scales [n]
+int kv_fp8_quantize(const float* x, int n, unsigned char* codes, float* scales, hipStream_t stream);
+// the device's f32 -> fp8 conversion equals wstream.h::fp8_e4m3_encode on every code value and every midpoint between neighbours
+int fp8_check_device_encode(hipStream_t stream);
 // Decode-session admission, input rows of the prefill: x[b][s] = emb[b][s] for s < P[b] (emb [n][ld_rows][d]), mel_emb[start] +
 // mel_pos[0] at s = P[b], 0 after it (right padding); every row S long
 int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P, int n, int S, int d, const float* mel_emb,

@@ -13,13 +13,18 @@
 // KV cache layout (chosen for the decode read pattern, the only hot reader):
 //   K: [B][H][16][Smax][4]   dot products walk the keys with lanes = keys -> 16-byte, fully coalesced
 //   V: [B][H][Smax][64]      P.V walks the keys with lanes = head dim    -> 256-byte coalesced rows
-// or, with DecodeAttnArgs::kv16 (decode_attn16_kernel), the same in bf16: K [B][H][8][Smax][8], V [B][H][Smax][64].
+// or, with DecodeAttnArgs::kv_fmt 1 (decode_attn16_kernel), the same in bf16: K [B][H][8][Smax][8], V [B][H][Smax][64];
+// or, with kv_fmt 2 (decode_attn8_kernel), that geometry in scaled fp8 codes plus one fp32 scale per key and per value (kv_fp8.h).
 #include <algorithm>
 #include <cstdlib>
+#include <string>
+#include <vector>
 
 #include "decode.h"
 #include "device_util.h"
+#include "kv_fp8.h"
 #include "prof.h"
+#include "wstream.h"
 
 namespace idxtts {
 
@@ -72,10 +77,11 @@ __device__ __forceinline__ void decode_attn_dead(const DecodeAttnArgs& p, const 
   else p.out[frag_index(b, h * 64 + tid, p.d >> 4)] = 0.f;
 }
 
-// ---- the two cache formats: how a 16-byte key / value granule is laid out, widened, multiplied and stored.  Both keep a key as
-//      64 / EPG granules [granule][Smax] and a value row as 64 / EPG granules, one per lane; every product and sum is fp32. ----
+// ---- the cache formats: how a key / value granule (16 bytes; fp8: 8) is laid out, widened, multiplied and stored.  All keep a key
+//      as 64 / EPG granules [granule][Smax] and a value row as 64 / EPG granules, one per lane; every product and sum is fp32. ----
 // fp32 cache: K [B][H][16][Smax][4], V [B][H][Smax][64] (256-byte rows)
 struct KvF32 {
+  static constexpr bool SCALED = false;   // no per-vector scales
   typedef float E;                        // cache element
   typedef f32x4 G;                        // granule
   typedef f32x4 Acc;                      // a lane's P.V accumulator: the head dims of its granule
@@ -110,6 +116,7 @@ struct KvF32 {
 // rounded to bf16 (nearest even) when it is produced -- the new token's own k / v too, so a position reads the same whether it is
 // the newest or an old one -- and widened exactly (<< 16) when used.
 struct KvBf16 {
+  static constexpr bool SCALED = false;
   typedef unsigned short E;
   typedef u32x4 G;
   struct Acc { float e[8]; };
@@ -156,6 +163,55 @@ struct KvBf16 {
   }
 };
 
+// scaled fp8 cache (DecodeAttnArgs::kv_fmt 2; the format: kv_fp8.h), half the bf16 bytes in its geometry: K [B][H][8][Smax][8],
+// V [B][H][Smax][64] (64-byte rows), 8-byte granules, LPR = 8 lanes per value row and NG = 64 key groups as KvBf16 -- 16-byte granules
+// (LPR = 4, NG = 128: 32 KB of outp, a 128-term group reduction) were not tried.  The body multiplies a key's score by its scale and
+// folds a value's scale into its probability; both are powers of two, so a position reads the same whether it is the newest (knew /
+// vnew hold decode(code) * scale) or an old one.
+struct KvFp8 {
+  static constexpr bool SCALED = true;
+  typedef unsigned char E;
+  typedef u32x2 G;
+  struct Acc { float e[8]; };
+  typedef const float* VNew;
+  static constexpr int EPG = 8;
+  static constexpr int NACC = 2;
+  static constexpr int OUT_UNROLL = 16;
+  __device__ static __forceinline__ G zero() { return G{0u, 0u}; }
+  __device__ static __forceinline__ float dot_new(const float (&qv)[64], const float* knew) { return KvBf16::dot_new(qv, knew); }
+  __device__ static __forceinline__ float dot_key(const float (&qv)[64], const G (&kk)[8]) {
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)kk[i][j], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)kk[i][j], true);
+        dot += qv[8 * i + 4 * j] * lo[0] + qv[8 * i + 4 * j + 1] * lo[1];
+        dot += qv[8 * i + 4 * j + 2] * hi[0] + qv[8 * i + 4 * j + 3] * hi[1];
+      }
+    return dot;
+  }
+  __device__ static __forceinline__ VNew vnew_of(const float* vnew, const int l) { return vnew + 8 * l; }
+  __device__ static __forceinline__ void fma(Acc& acc, const float pw, const G v) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[j], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)v[j], true);
+      acc.e[4 * j] += pw * lo[0];
+      acc.e[4 * j + 1] += pw * lo[1];
+      acc.e[4 * j + 2] += pw * hi[0];
+      acc.e[4 * j + 3] += pw * hi[1];
+    }
+  }
+  __device__ static __forceinline__ void fma_new(Acc& acc, const float pw, const VNew vn) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc.e[e] += pw * vn[e];
+  }
+  __device__ static __forceinline__ void store(float* dst, const Acc (&a)[2]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dst[e] = a[0].e[e] + a[1].e[e];
+  }
+};
+
 // One query token per (utterance, head) workgroup against its cached keys, or against one of gridDim.z pieces of them.
 // NT threads per workgroup: NT keys per pass of the score phase, NG = NT / (lanes of a value row) key groups in the P.V phase.  512
 // threads at <= 128 VGPRs (two workgroups per CU) halve the number of dependent load -> use passes of the 256-thread form.
@@ -184,6 +240,8 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   const int d = p.d, Smax = p.Smax;
   G* const kc = static_cast<G*>(p.kcache) + (size_t)(b * p.H + h) * KG * Smax;       // granule (c, s) at c * Smax + s
   G* const vc = static_cast<G*>(p.vcache) + (size_t)(b * p.H + h) * Smax * LPR;      // granule (s, c) at s * LPR + c
+  float* const ksc = KV::SCALED ? p.kscale + (size_t)(b * p.H + h) * Smax : nullptr;   // scaled formats: one scale per key / value
+  float* const vsc = KV::SCALED ? p.vscale + (size_t)(b * p.H + h) * Smax : nullptr;
 
   // Everything that does not depend on the new token's q is put in flight first: this thread's first key (KG x 16 B,
   // coalesced across threads) and its first value rows of the P.V phase; the kernel is a chain of dependent
@@ -199,6 +257,10 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   G kk0[KG];
 #pragma unroll
   for (int i = 0; i < KG; ++i) kk0[i] = (s_first < pos && s_first <= ke) ? kc[(size_t)i * Smax + s_first] : KV::zero();
+  float ks_first = 1.f, vs_first = 1.f;      // scaled formats: the first key's scales travel with it (the new token's own: 1)
+  if constexpr (KV::SCALED) {
+    if (s_first < pos && s_first <= ke) { ks_first = ksc[s_first]; vs_first = vsc[s_first]; }
+  }
   constexpr int VP = 128 / NG;      // value rows prefetched per lane before the scores (NG * VP = 128 keys)
   G vpre[VP];
 #pragma unroll
@@ -216,7 +278,17 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
     float acc = p.qkv_bias ? p.qkv_bias[col] : 0.0f;
     for (int s = 0; s < p.parts; ++s) acc += row[(size_t)s * sst];
     if (which == 0) qs[dd] = acc * p.scale;
-    else if (which == 1) knew[dd] = KV::put(reinterpret_cast<E*>(kc + (size_t)(dd / EPG) * Smax + pos) + dd % EPG, z == 0, acc);
+    else if constexpr (KV::SCALED) {      // waves 1 and 2 whole, one vector each: its scale needs the maximum over the 64 lanes
+      unsigned code;
+      float sc;
+      const float val = kv_fp8_quantize_lane(acc, code, sc);
+      (which == 1 ? knew : vnew)[dd] = val;
+      if (z == 0) {
+        if (which == 1) reinterpret_cast<E*>(kc + (size_t)(dd / EPG) * Smax + pos)[dd % EPG] = (E)code;
+        else reinterpret_cast<E*>(vc + (size_t)pos * LPR)[dd] = (E)code;
+        if (dd == 0) (which == 1 ? ksc : vsc)[pos] = sc;
+      }
+    } else if (which == 1) knew[dd] = KV::put(reinterpret_cast<E*>(kc + (size_t)(dd / EPG) * Smax + pos) + dd % EPG, z == 0, acc);
     else vnew[dd] = KV::put(reinterpret_cast<E*>(vc + (size_t)pos * LPR) + dd, z == 0, acc);
   }
   __syncthreads();
@@ -230,7 +302,8 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   // ---- scores: one key per thread and pass; the first pass consumes the prefetched key ----
   float mx = -1e30f;
   if (s_first <= ke) {
-    const float dot = s_first == pos ? KV::dot_new(qv, knew) : KV::dot_key(qv, kk0);
+    float dot = s_first == pos ? KV::dot_new(qv, knew) : KV::dot_key(qv, kk0);
+    if constexpr (KV::SCALED) dot *= ks_first;
     pr[s_first] = dot;
     mx = dot;
   }
@@ -242,6 +315,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
 #pragma unroll
       for (int i = 0; i < KG; ++i) kk[i] = kc[(size_t)i * Smax + s];
       dot = KV::dot_key(qv, kk);
+      if constexpr (KV::SCALED) dot *= ksc[s];
     }
     pr[s] = dot;
     mx = fmaxf(mx, dot);
@@ -256,7 +330,11 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   float sum = 0.f;
   for (int s = s_first; s <= ke; s += NT) {
     const float e = expf(pr[s] - mx);
-    pr[s] = e;
+    if constexpr (KV::SCALED) {      // the P.V weight of a cached value carries its scale; the sum does not
+      pr[s] = e * (s == s_first ? vs_first : s == pos ? 1.f : vsc[s]);
+    } else {
+      pr[s] = e;
+    }
     sum += e;
   }
   sum = wave_sum(sum);
@@ -312,6 +390,10 @@ template <int NT, bool SLOTS>
 __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn16_kernel(const DecodeAttnArgs p) {
   decode_attn_body<NT, SLOTS, KvBf16>(p);
 }
+template <int NT, bool SLOTS>
+__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn8_kernel(const DecodeAttnArgs p) {
+  decode_attn_body<NT, SLOTS, KvFp8>(p);
+}
 
 int decode_attn_nsplit(int B, int H) {
   const int wgs = B * H;
@@ -322,21 +404,32 @@ int decode_attn_nsplit(int B, int H) {
 int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
   IDX_CHECK(a.qkv_part && a.kcache && a.vcache && (a.out || a.out_row) && (a.st || a.slot), "null pointer");
   IDX_CHECK(a.d == a.H * 64, "head_dim must be 64");
+  IDX_CHECK(a.kv_fmt >= 0 && a.kv_fmt <= 2 && (a.kv_fmt != 2 || (a.kscale && a.vscale)), "KV format 0 / 1 / 2 (2: with the scale arrays)");
   constexpr int nt = 512;      // 512 threads measured 4 % faster than 256 (profiles/README.md)
-  const size_t lds = (size_t)(256 + (nt / (a.kv16 ? 8 : 16)) * 64 + a.Smax) * sizeof(float);
+  const size_t lds = (size_t)(256 + (nt / (a.kv_fmt ? 8 : 16)) * 64 + a.Smax) * sizeof(float);
   IDX_CHECK(lds <= 128 * 1024, "Smax too large for the LDS score buffer");
   static DynLdsLimit lds_limit;
-  IDX_HIP(lds_limit.set(128 * 1024, decode_attn_kernel<512, false>, decode_attn16_kernel<512, false>, decode_attn_kernel<512, true>, decode_attn16_kernel<512, true>));
+  IDX_HIP(lds_limit.set(128 * 1024, decode_attn_kernel<512, false>, decode_attn16_kernel<512, false>, decode_attn8_kernel<512, false>,
+                        decode_attn_kernel<512, true>, decode_attn16_kernel<512, true>, decode_attn8_kernel<512, true>));
   IDX_CHECK(a.nsplit >= 1 && a.nsplit <= 16 && (a.nsplit == 1 || (a.part && a.cnt)), "key split: 1..16 pieces, partial buffer and counters");
-  // algorithmic bytes: K and V of every cached position, all heads: B * S * 2 * d * (4 | 2) (S as the host knows it: pos_hint)
+  // algorithmic bytes: K and V of every cached position, all heads: B * S * 2 * d * (4 | 2 | 1), fp8: + two fp32 scales per 64 (S as
+  // the host knows it: pos_hint)
   static const int cat = prof_register("decode_attn_kernel"), cat16 = prof_register("decode_attn16_kernel");
-  ProfScope prof(a.kv16 ? cat16 : cat, stream, 0.0, (a.kv16 ? 4.0 : 8.0) * a.B * (double)a.pos_hint * a.d);
+  int cat_of = a.kv_fmt ? cat16 : cat;
+  if (a.kv_fmt == 2) {      // (registered at its first use: a profile of the other formats lists what it always listed)
+    static const int cat8 = prof_register("decode_attn8_kernel");
+    cat_of = cat8;
+  }
+  const double bytes_per = a.kv_fmt == 2 ? 2.0 + 8.0 / 64.0 : a.kv_fmt ? 4.0 : 8.0;
+  ProfScope prof(cat_of, stream, 0.0, bytes_per * a.B * (double)a.pos_hint * a.d);
   const dim3 grid(a.H, a.B, a.nsplit);
   if (a.slot) {
-    if (a.kv16) hipLaunchKernelGGL((decode_attn16_kernel<512, true>), grid, dim3(512), lds, stream, a);
+    if (a.kv_fmt == 2) hipLaunchKernelGGL((decode_attn8_kernel<512, true>), grid, dim3(512), lds, stream, a);
+    else if (a.kv_fmt) hipLaunchKernelGGL((decode_attn16_kernel<512, true>), grid, dim3(512), lds, stream, a);
     else hipLaunchKernelGGL((decode_attn_kernel<512, true>), grid, dim3(512), lds, stream, a);
   } else {
-    if (a.kv16) hipLaunchKernelGGL((decode_attn16_kernel<512, false>), grid, dim3(512), lds, stream, a);
+    if (a.kv_fmt == 2) hipLaunchKernelGGL((decode_attn8_kernel<512, false>), grid, dim3(512), lds, stream, a);
+    else if (a.kv_fmt) hipLaunchKernelGGL((decode_attn16_kernel<512, false>), grid, dim3(512), lds, stream, a);
     else hipLaunchKernelGGL((decode_attn_kernel<512, false>), grid, dim3(512), lds, stream, a);
   }
   IDX_LAUNCH_CHECK();
@@ -741,12 +834,56 @@ __global__ __launch_bounds__(256) void kv_store_prefill_kernel(float* qkv, void*
   }
 }
 
-int kv_store_prefill(float* qkv, void* kcache, void* vcache, int kv16, int B, int H, int S, int Smax, int d, hipStream_t stream) {
+// scaled fp8 cache (kv_fp8.h): one wave owns one head -- a vector's scale needs the maximum over its 64 lanes -- and takes the heads
+// wave, wave + 4, ...; k / v columns of qkv become the cached values in place.  slot_ids / len null: the prefill (row b -> cache row b,
+// every position); else the admission rule of kv_store_slots_kernel (positions [0, len[b]) -> slot slot_ids[b], FAN: and the next
+// fan - 1 slots, codes and scales alike)
+template <bool FAN>
+__global__ __launch_bounds__(256) void kv_store_fp8_kernel(float* qkv, unsigned char* kcache, unsigned char* vcache, float* kscale,
+                                                           float* vscale, int H, int S, int Smax, int d, const int* slot_ids,
+                                                           const int* len, int fan) {
+  const int s = blockIdx.x, b = blockIdx.y, wave = threadIdx.x >> 6, dd = threadIdx.x & 63;
+  const int slot0 = slot_ids ? slot_ids[b] : b;
+  const bool keep = !len || s < len[b];
+  float* row = qkv + ((size_t)b * S + s) * 3 * d;
+  for (int h = wave; h < H; h += 4) {      // (wave-uniform: every lane of a wave reaches the quantiser's reduction)
+    const int col = h * 64 + dd;
+    unsigned kcode, vcode;
+    float ks, vs;
+    const float kq = kv_fp8_quantize_lane(row[d + col], kcode, ks), vq = kv_fp8_quantize_lane(row[2 * d + col], vcode, vs);
+    if (keep) {
+      auto put = [&](int slot) {
+        const size_t vec = (size_t)slot * H + h;
+        kcache[((vec * 8 + (dd >> 3)) * Smax + s) * 8 + (dd & 7)] = (unsigned char)kcode;
+        vcache[(vec * Smax + s) * 64 + dd] = (unsigned char)vcode;
+        if (dd == 0) { kscale[vec * Smax + s] = ks; vscale[vec * Smax + s] = vs; }
+      };
+      if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+      else put(slot0);
+    }
+    row[d + col] = kq;
+    row[2 * d + col] = vq;
+  }
+}
+
+static int kv_store_fp8(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len, int fan,
+                        hipStream_t stream) {
+  IDX_CHECK(kv.kscale && kv.vscale, "the fp8 cache needs its scale arrays");
+  unsigned char* const kc = static_cast<unsigned char*>(kv.kcache);
+  unsigned char* const vc = static_cast<unsigned char*>(kv.vcache);
+  if (fan > 1) hipLaunchKernelGGL(kv_store_fp8_kernel<true>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, fan);
+  else hipLaunchKernelGGL(kv_store_fp8_kernel<false>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, 1);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+int kv_store_prefill(float* qkv, const KvDst& kv, int B, int H, int S, int Smax, int d, hipStream_t stream) {
   IDX_CHECK(S <= Smax, "prefill longer than the cache");
   static const int cat = prof_register("kv_store_prefill_kernel");
-  ProfScope prof(cat, stream, 0.0, (kv16 ? 28.0 : 16.0) * B * (double)S * d);
-  if (kv16) hipLaunchKernelGGL(kv_store_prefill_kernel<true>, dim3(S, B), dim3(256), 0, stream, qkv, kcache, vcache, B, H, S, Smax, d);
-  else hipLaunchKernelGGL(kv_store_prefill_kernel<false>, dim3(S, B), dim3(256), 0, stream, qkv, kcache, vcache, B, H, S, Smax, d);
+  ProfScope prof(cat, stream, 0.0, (kv.fmt == 2 ? 26.0 : kv.fmt ? 28.0 : 16.0) * B * (double)S * d);
+  if (kv.fmt == 2) return kv_store_fp8(qkv, kv, B, H, S, Smax, d, nullptr, nullptr, 1, stream);
+  if (kv.fmt) hipLaunchKernelGGL(kv_store_prefill_kernel<true>, dim3(S, B), dim3(256), 0, stream, qkv, kv.kcache, kv.vcache, B, H, S, Smax, d);
+  else hipLaunchKernelGGL(kv_store_prefill_kernel<false>, dim3(S, B), dim3(256), 0, stream, qkv, kv.kcache, kv.vcache, B, H, S, Smax, d);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -785,13 +922,17 @@ __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* k
   }
 }
 
-int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int H, int S, int Smax, int d, const int* slot_ids,
-                   const int* len, hipStream_t stream, int fan) {
+int kv_store_slots(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len,
+                   hipStream_t stream, int fan) {
   IDX_CHECK(S <= Smax, "prefill longer than the cache");
   IDX_CHECK(slot_ids && len && fan >= 1, "null pointer");
   if (n <= 0) return 0;
   static const int cat = prof_register("kv_store_slots_kernel");
-  ProfScope prof(cat, stream, 0.0, (kv16 ? 28.0 : 16.0) * n * (double)S * d);
+  ProfScope prof(cat, stream, 0.0, (kv.fmt == 2 ? 26.0 : kv.fmt ? 28.0 : 16.0) * n * (double)S * d);
+  if (kv.fmt == 2) return kv_store_fp8(qkv, kv, n, H, S, Smax, d, slot_ids, len, fan, stream);
+  void* const kcache = kv.kcache;
+  void* const vcache = kv.vcache;
+  const int kv16 = kv.fmt;
   if (fan > 1) {
     if (kv16) hipLaunchKernelGGL((kv_store_slots_kernel<true, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
     else hipLaunchKernelGGL((kv_store_slots_kernel<false, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
@@ -801,6 +942,65 @@ int kv_store_slots(float* qkv, void* kcache, void* vcache, int kv16, int n, int 
     hipLaunchKernelGGL((kv_store_slots_kernel<false, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1);
   }
   IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- the fp8 cache's instruments: its quantiser on plain vectors, and the check of the device's f32 -> fp8 conversion ----
+__global__ __launch_bounds__(256) void kv_fp8_quantize_kernel(const float* x, int n, unsigned char* codes, float* scales) {
+  const int v = blockIdx.x * 4 + (threadIdx.x >> 6), dd = threadIdx.x & 63;
+  if (v >= n) return;      // (wave-uniform)
+  unsigned code;
+  float sc;
+  kv_fp8_quantize_lane(x[(size_t)v * 64 + dd], code, sc);
+  codes[(size_t)v * 64 + dd] = (unsigned char)code;
+  if (dd == 0) scales[v] = sc;
+}
+
+int kv_fp8_quantize(const float* x, int n, unsigned char* codes, float* scales, hipStream_t stream) {
+  IDX_CHECK(x && codes && scales && n >= 0, "null pointer");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(kv_fp8_quantize_kernel, dim3(cdiv(n, 4)), dim3(256), 0, stream, x, n, codes, scales);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ void fp8_encode_table_kernel(const float* in, unsigned char* out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (unsigned char)kv_fp8_encode(in[i]);
+}
+
+int fp8_check_device_encode(hipStream_t stream) {
+  static bool ok = false;
+  if (ok) return 0;
+  std::vector<float> tab;      // every code value and every midpoint between neighbouring codes, both signs
+  for (int c = 0; c <= 126; ++c) {
+    const float v = fp8_e4m3_decode((unsigned char)c);
+    tab.push_back(v);
+    tab.push_back(-v);
+    if (c < 126) {
+      const float mid = 0.5f * (v + fp8_e4m3_decode((unsigned char)(c + 1)));      // exact: neighbours share all but 4 mantissa bits
+      tab.push_back(mid);
+      tab.push_back(-mid);
+    }
+  }
+  const int n = (int)tab.size();
+  float* din = nullptr;
+  unsigned char* dout = nullptr;
+  IDX_HIP(hipMalloc(&din, n * sizeof(float)));
+  hipError_t e = hipMalloc(&dout, n);
+  std::vector<unsigned char> got(n);
+  if (e == hipSuccess) e = hipMemcpyAsync(din, tab.data(), n * sizeof(float), hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(fp8_encode_table_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, din, dout, n);
+    e = hipMemcpyAsync(got.data(), dout, n, hipMemcpyDeviceToHost, stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  IDX_HIP(e);
+  for (int i = 0; i < n; ++i)
+    if (got[i] != fp8_e4m3_encode(tab[i])) IDX_FAIL("this device's f32 -> fp8 conversion is not OCP e4m3fn, nearest even (input " + std::to_string(tab[i]) + ")");
+  ok = true;
   return 0;
 }
 

@@ -54,10 +54,11 @@ struct GPTModel : ModelBase {
   const float* head_b = nullptr;
   const float *mel_emb = nullptr, *text_emb = nullptr, *mel_pos = nullptr, *text_pos = nullptr;
   int weight_fmt = WFMT_F32;      // storage format of the decode weight streams (quantize_weights)
-  int kv_fmt = 0;                 // KV cache of the cached generation: 0 = fp32, 1 = bf16 (keys / values rounded when produced; decode.h)
+  int kv_fmt = 0;                 // KV cache of the cached generation: 0 = fp32, 1 = bf16, 2 = scaled fp8 (keys / values rounded when produced; decode.h)
   std::atomic<int> generating{0}; // generate() / generate_beam() calls in flight: idxtts_gpt_set_kv_format refuses to switch under them
   struct GenScope { GPTModel* m; explicit GenScope(GPTModel* mm) : m(mm) { m->generating.fetch_add(1); } ~GenScope() { m->generating.fetch_sub(1); } };
-  size_t kv_layer_bytes(int B, int Smax) const { return (size_t)B * cfg.heads * Smax * 64 * (kv_fmt ? 2 : 4); }
+  size_t kv_layer_bytes(int B, int Smax) const { return (size_t)B * cfg.heads * Smax * 64 * (kv_fmt == 2 ? 1 : kv_fmt ? 2 : 4); }
+  size_t kv_layer_scales(int B, int Smax) const { return kv_fmt == 2 ? (size_t)B * cfg.heads * Smax : 0; }      // fp8: one per cached vector
   hipStream_t own_stream = nullptr;
   static constexpr int OOB_SLOTS = 64;
   int* oob_flag = nullptr;        // device ints (one per embed() call in flight): set by the embedding gather when an index exceeds its table
@@ -70,7 +71,8 @@ struct GPTModel : ModelBase {
 
   struct Buffers {
     float *x, *h, *qkv, *att, *ff;            // [B*S][..] prefill / latent activations
-    char *kcache, *vcache; int Smax;          // [L][B][H] x (Smax x 64 elements) each; fp32 or bf16 elements (kv_fmt, decode.h)
+    char *kcache, *vcache; int Smax;          // [L][B][H] x (Smax x 64 elements) each; fp32, bf16 or fp8 elements (kv_fmt, decode.h)
+    float *kscale = nullptr, *vscale = nullptr;   // fp8 cache only: [L][B][H][Smax] scales, carved right after the codes
     float *xd, *hd, *attd, *ffd;              // decode residual / final-normed / attention output / mlp hidden: A-fragment images
     // plane-GEMV decode step (gemv_pl.h; compact weight streams, more than 4 rows): every activation a plain fp32 row-major matrix,
     // per-16-column row statistics for the folded LayerNorms, K-part partial sums and arrival counters
@@ -94,7 +96,7 @@ struct GPTModel : ModelBase {
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
   struct GraphSlot {
-    void* ws = nullptr; size_t ws_bytes = 0; int B = 0, S = 0, max_new = 0; float penalty = 0.0f; int kv16 = 0, geom = 0;
+    void* ws = nullptr; size_t ws_bytes = 0; int B = 0, S = 0, max_new = 0; float penalty = 0.0f; int kv_fmt = 0, geom = 0;
     StepGraph step; unsigned long stamp = 0; bool in_use = false;
   };
   std::vector<GraphSlot> graph_cache;
@@ -122,6 +124,7 @@ struct GPTModel : ModelBase {
   // the step is captured)
   int head_and_sample(const Buffers& w, int B, const float* x, int ldx, bool x_frag, float penalty, int codes_ld, float* logits_out,
                       hipStream_t st);
+  KvDst kv_dst(int li, const Buffers& w, int rows) const;      // layer li of a cache laid out for `rows` rows, as its producers write it
   DecodeAttnArgs attn_args(int li, const Buffers& w, int B, int pos_hint) const;      // layer li's decode attention; the caller sets out / out_row
   SampleArgs::Embed tail_embed(const Buffers& w, bool pl) const;                      // the fused tail's next-input block (st_rw left to the caller)
   int decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
@@ -152,7 +155,7 @@ struct GPTModel : ModelBase {
   // (pad_left 0): every kernel on its path is chosen from the session's properties (slots, KV format, GEMM mode) alone, never from how
   // many rows are admitted at once.
   struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
-    int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv16 = 0, gemm_mode = 0;
+    int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
     std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
     int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each

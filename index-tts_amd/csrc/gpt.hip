@@ -187,6 +187,10 @@ GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new, size_t pr
   const size_t cache = (size_t)L * kv_layer_bytes(B, b.Smax);
   b.kcache = c.take<char>(cache);
   b.vcache = c.take<char>(cache);
+  if (kv_fmt == 2) {      // (the other formats' carve is what it always was)
+    b.kscale = c.take<float>((size_t)L * kv_layer_scales(B, b.Smax));
+    b.vscale = c.take<float>((size_t)L * kv_layer_scales(B, b.Smax));
+  }
   // decode activations as A-fragment images (frag_index, common.h); one contiguous region so it can be zeroed in one go
   b.xd = c.take<float>(frag_image_floats(B, d));
   b.frag_off = c.off - frag_image_floats(B, d) * sizeof(float);
@@ -224,8 +228,11 @@ size_t GPTModel::workspace_bytes(int B, int S, int max_new) const { return carve
 int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter) {
   // The prefill (store_kv) that fills an fp32 KV cache feeds an exact greedy decode: exact fp32 MFMA.  With a bf16 cache its keys and
   // values are rounded to 8 bits on the way in (relative 2^-9), which buries the split-bf16 GEMM's 2^-16 product error: that prefill
-  // runs like the latent pass, mode-dependent (split-bf16 by default, 3-4 x the exact kernel's rate).
-  const bool exact = store_kv && kv_fmt == 0;
+  // runs like the latent pass, mode-dependent (split-bf16 by default, 3-4 x the exact kernel's rate).  An fp8 cache keeps the exact
+  // prefill: a key / value moved by the split GEMM's 2^-16 lands on the other e4m3 neighbour 250 x as often as one moved by an fp32
+  // summation order, and each such flip is 2^-4 of the element -- measured against the oracle, max |dlogit| 5.5e-2 with the split
+  // prefill and 1.8e-2 with the exact one (profiles/README.md "fp8 KV cache").
+  const bool exact = store_kv && kv_fmt != 1;
   auto mm = [&](const LinearWeights& lw, const GemmArgs& ga) { return exact ? gemm_tn_forward(lw, ga, st) : gemm_forward(lw, ga, st); };
   const GPTLayer& L = layers[li];
   const int d = cfg.model_dim, M = B * S;
@@ -236,12 +243,10 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   g.x = w.h; g.ldx = d; g.y = w.qkv; g.ldy = 3 * d; g.M = M;
   if (mm(L.attn_l, g)) return 1;
   if (store_kv && scatter) {      // decode-session admission: the rows go to their slots' cache regions
-    const size_t per_layer = kv_layer_bytes(scatter->slots, w.Smax);
-    if (kv_store_slots(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, scatter->n, cfg.heads, S, w.Smax, d,
-                       scatter->slot_ids, scatter->len, st, scatter->fan)) return 1;
+    if (kv_store_slots(w.qkv, kv_dst(li, w, scatter->slots), scatter->n, cfg.heads, S, w.Smax, d, scatter->slot_ids, scatter->len, st,
+                       scatter->fan)) return 1;
   } else if (store_kv) {
-    const size_t per_layer = kv_layer_bytes(B, w.Smax);
-    if (kv_store_prefill(w.qkv, w.kcache + li * per_layer, w.vcache + li * per_layer, kv_fmt, B, cfg.heads, S, w.Smax, d, st)) return 1;
+    if (kv_store_prefill(w.qkv, kv_dst(li, w, B), B, cfg.heads, S, w.Smax, d, st)) return 1;
   }
   AttnArgs a;
   a.q = w.qkv; a.k = w.qkv + d; a.v = w.qkv + 2 * d; a.o = w.att;
@@ -349,11 +354,19 @@ bool GPTModel::fused_tail(const Buffers& w) const { return w.slots || (w.samp.mo
 // The decode step on the plane GEMV (gemv_pl.hip): the same five launches per layer, every activation a plain fp32 row-major matrix
 // (split into bf16 planes inside the GEMV), the residual stream updated in place, the LayerNorm statistics handed from producer to consumer; greedy generations close the
 // step with ONE launch (sample + next embedding + advance).
+KvDst GPTModel::kv_dst(int li, const Buffers& w, int rows) const {
+  const size_t per_layer = kv_layer_bytes(rows, w.Smax), scales = kv_layer_scales(rows, w.Smax);
+  KvDst kv;
+  kv.kcache = w.kcache + li * per_layer; kv.vcache = w.vcache + li * per_layer; kv.fmt = kv_fmt;
+  if (kv_fmt == 2) { kv.kscale = w.kscale + li * scales; kv.vscale = w.vscale + li * scales; }
+  return kv;
+}
+
 DecodeAttnArgs GPTModel::attn_args(int li, const Buffers& w, int B, int pos_hint) const {
-  const size_t per_layer = kv_layer_bytes(B, w.Smax);
+  const KvDst kv = kv_dst(li, w, B);
   DecodeAttnArgs da;
   da.qkv_part = w.qkvd; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
-  da.kcache = w.kcache + li * per_layer; da.vcache = w.vcache + li * per_layer; da.kv16 = kv_fmt; da.kstart = w.kstart;
+  da.kcache = kv.kcache; da.vcache = kv.vcache; da.kv_fmt = kv.fmt; da.kscale = kv.kscale; da.vscale = kv.vscale; da.kstart = w.kstart;
   da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = cfg.model_dim; da.scale = 0.125f;
   da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
   da.pos_hint = pos_hint;
@@ -562,7 +575,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
     std::lock_guard<std::mutex> l(graph_mu);
     for (size_t i = 0; i < graph_cache.size(); ++i) {
       GraphSlot& g = graph_cache[i];
-      if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv16 == kv_fmt && g.geom == geom) {
+      if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv_fmt == kv_fmt && g.geom == geom) {
         g.in_use = true; g.stamp = ++graph_stamp; exec = g.step.exec; lease.m = this; lease.idx = (int)i;
         break;
       }
@@ -585,7 +598,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
     if (slot >= 0) {
       GraphSlot& g = graph_cache[slot];
       g.step.drop();
-      g.ws = ws; g.ws_bytes = ws_bytes; g.B = B; g.S = S; g.max_new = max_new; g.penalty = penalty; g.kv16 = kv_fmt; g.geom = geom;
+      g.ws = ws; g.ws_bytes = ws_bytes; g.B = B; g.S = S; g.max_new = max_new; g.penalty = penalty; g.kv_fmt = kv_fmt; g.geom = geom;
       g.step = fresh; g.stamp = ++graph_stamp;
     } else {
       fresh.drop();
@@ -692,7 +705,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   Session& s = sessions[ws];
   s.step.drop();
   s = Session();
-  s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv16 = kv_fmt; s.gemm_mode = get_gemm_mode();
+  s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv_fmt = kv_fmt; s.gemm_mode = get_gemm_mode();
   s.ws_bytes = ws_bytes;
   s.busy.assign(slots, 0);
   s.sampled = sampled;
@@ -716,7 +729,7 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   IDX_CHECK(inputs_embeds && prompt_lens && ids && caps, "null pointer");
   const int units = s.slots / fan;
   IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
-  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   int pmax = 0;
   std::vector<char> taken(units, 0);
   for (int b = 0; b < n; ++b) {
@@ -729,11 +742,11 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   }
   // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
   // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
-  // exact kernel; with a bf16 cache in split-bf16 mode gemm_forward takes the split-bf16 kernel from 256 rows on, so the prefill is padded
+  // exact kernel, and so it does with an fp8 cache; with a bf16 cache in split-bf16 mode gemm_forward takes the split-bf16 kernel from 256 rows on, so the prefill is padded
   // with zero rows (b >= n) to at least 256 rows -- every admission then runs the kernel a generate() batch of >= 256 prefill rows runs.
   const int S = pmax + 1;
   int rows = n;
-  if (kv_fmt && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
+  if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
   IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
   if (params()) return 1;
   // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen
@@ -810,7 +823,7 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
   IDX_CHECK(n_steps >= 0, "n_steps");
-  IDX_CHECK(kv_fmt == s.kv16 && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   GenScope gen_scope(this);
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
   const Buffers& w = sb.w;

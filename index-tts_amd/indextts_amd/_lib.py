@@ -17,7 +17,7 @@ SYMBOLS = [
     "idxtts_version", "idxtts_last_error", "idxtts_aa_act_fwd",
     "idxtts_conv1d_create", "idxtts_conv1d_fwd", "idxtts_conv1d_destroy",
     "idxtts_ctx_load_tensor", "idxtts_ctx_finalize", "idxtts_ctx_get_tensor", "idxtts_ctx_destroy",
-    "idxtts_fp8_e4m3_decode", "idxtts_fp8_e4m3_encode",
+    "idxtts_fp8_e4m3_decode", "idxtts_fp8_e4m3_encode", "idxtts_kv_fp8_quantize",
     "idxtts_bigvgan_create", "idxtts_bigvgan_workspace_bytes", "idxtts_bigvgan_fwd", "idxtts_bigvgan_fwd_ragged",
     "idxtts_profile_enable", "idxtts_profile_num_kernels", "idxtts_profile_kernel_name", "idxtts_profile_read", "idxtts_profile_event_overhead",
     "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_bf16_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
@@ -136,6 +136,7 @@ def load() -> ctypes.CDLL:
     lib.idxtts_fp8_e4m3_encode.argtypes = [ctypes.c_float]
     lib.idxtts_fp8_e4m3_encode.restype = ctypes.c_ubyte
     lib.idxtts_gpt_quantize_weights.argtypes = [c_void_p, c_int]
+    lib.idxtts_kv_fp8_quantize.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_set_kv_format.argtypes = [c_void_p, c_int]
     lib.idxtts_gpt_get_kv_format.argtypes = [c_void_p]
     lib.idxtts_ctx_destroy.argtypes = [c_void_p]

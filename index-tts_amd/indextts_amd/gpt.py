@@ -31,7 +31,7 @@ def _i32(dev, arr) -> torch.Tensor:
 
 
 WEIGHT_FORMATS = {"f32": 0, "bf16": 1, "fp8": 2}
-KV_FORMATS = {"f32": 0, "bf16": 1}
+KV_FORMATS = {"f32": 0, "bf16": 1, "fp8": 2}
 
 
 class UnifiedVoice:
@@ -43,9 +43,10 @@ class UnifiedVoice:
         per output channel): the reference's `use_fp16` switch (infer_v2.py:145-146) / BASELINE configs[4].  The weights are
         rounded ONCE at load (`idxtts_gpt_quantize_weights`); the arithmetic stays fp32, and every pass runs that one rounded
         model.  keep_effective: keep `self.effective_state_dict` (numpy, reference keys) = exactly that model, for parity checks.
-        kv_format: storage of the KV cache of the cached generation, "f32" or "bf16" (`idxtts_gpt_set_kv_format`: keys / values
-        rounded to bf16 once, when produced; fp32 arithmetic).  Default: "f32" with fp32 weights, "bf16" with compact weights --
-        the reference's `use_fp16` halves weights and cache together."""
+        kv_format: storage of the KV cache of the cached generation, "f32", "bf16" or "fp8" (`idxtts_gpt_set_kv_format`: keys /
+        values rounded once, when produced -- to bf16, or to e4m3 codes with one power-of-two scale per 64-dim vector; fp32
+        arithmetic).  Default: "f32" with fp32 weights, "bf16" with compact weights -- the reference's `use_fp16` halves weights
+        and cache together; "fp8" is opt-in only, fp8 weights do not select it."""
         lib = _lib.load()
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {sorted(WEIGHT_FORMATS)}")
@@ -89,7 +90,7 @@ class UnifiedVoice:
         self.accel_engine = self       # the reference selects `self.accel_engine.generate` (model_v2.py:871)
 
     def set_kv_format(self, kv_format: str) -> None:
-        """Switch the KV-cache storage between generations ("f32" | "bf16")."""
+        """Switch the KV-cache storage between generations ("f32" | "bf16" | "fp8")."""
         if kv_format not in KV_FORMATS:
             raise ValueError(f"kv_format must be one of {sorted(KV_FORMATS)}")
         _lib.check(_lib.load().idxtts_gpt_set_kv_format(self._h, KV_FORMATS[kv_format]))

@@ -218,8 +218,8 @@ class IndexTTS2:
     @classmethod
     def from_state_dicts(cls, cfg: PipelineConfig, gpt_sd, s2mel_sd, bigvgan_sd, device=None, gpt_weight_format="f32",
                          keep_effective_gpt=False, segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None) -> "IndexTTS2":
-        """gpt_weight_format: "f32" | "bf16" | "fp8" storage of the GPT linear weights, gpt_kv_format: "f32" | "bf16" storage of its KV
-        cache (default: fp32 with fp32 weights, bf16 with compact weights) (UnifiedVoice); keep_effective_gpt keeps
+        """gpt_weight_format: "f32" | "bf16" | "fp8" storage of the GPT linear weights, gpt_kv_format: "f32" | "bf16" | "fp8" storage of its KV
+        cache (default: fp32 with fp32 weights, bf16 with compact weights; fp8 only when asked for) (UnifiedVoice); keep_effective_gpt keeps
         `self.gpt.effective_state_dict` (the rounded model, reference keys) for parity checks; segment_batch: segments of one
         infer() call synthesised together (1 = the reference's loop as written); acoustic_bf16: None leaves the library's switch as
         it is, True / False sets it (_lib.set_acoustic_bf16): s2mel and the vocoder on one bf16 MFMA per product instead of the split
