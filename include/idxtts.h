@@ -413,6 +413,23 @@ int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* fi
 /* Copies a finished slot's codes (up to and including the stop token) to codes (device int64, >= *n_codes entries: at most
  * max_new_tokens), sets *n_codes (host) and frees the slot. */
 int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_codes, void* workspace, void* stream);
+/* Ending requests from outside (a client that went away, a failed job): what KVCacheManager.remove_seq is to the accel engine
+ * (kv_manager.py:130-202) -- a sequence's KV allocation given back before it finished.  slots: HOST int32 [n], every kind of session; a
+ * beam session addresses a group by its FIRST slot, as _read does.  Every id is checked before anything changes -- in range, holding a
+ * request (admitted and not read), a group's first slot: one bad id refuses the whole call and changes nothing.  Both are one small
+ * launch on `stream`, the session's stream, between steps (the ids travel in its arguments): no copy, no synchronisation, the captured
+ * step and the workspace layout are untouched.
+ * _evict: the requests end and are free at once: admissible in the next _admit, never reported by a later _step, _read refused.
+ *   Allowed on a request that is decoding and on one that has ended and was not read.  A sampled request's exp_noise may be freed
+ *   once the call has returned and the work queued on `stream` before it has run (stream order).
+ * _stop: the requests that are decoding end and are kept: the next _step reports them (n_steps = 0 included) and _read returns the k
+ *   codes produced so far (a beam group: its best hypothesis at k steps).  A request that has already ended is left alone.
+ * Determinism: with any sequence of _evict and _stop calls between steps every other request's codes stay those of the rules above; a
+ * request admitted into an evicted slot or group meets them as in any other; a stopped request returns, bit for bit, what the same
+ * request with max_new_tokens = k returns (greedy, sampled: the first k codes of its uninterrupted run; beam: row 0 of
+ * idxtts_gpt_generate_beam with max_new_tokens = k and the same seed, or the first k rows of its exp_noise). */
+int idxtts_gpt_session_evict(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream);
+int idxtts_gpt_session_stop(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream);
 /* Forgets the session on this workspace (and its captured step); the caller may then free or reuse the workspace. */
 int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace);
 /* Latent pass: full causal forward over emb [B][S][d]; latent[b][i] = final_norm(ln_f(h[b][mel_start + i])), i < M.

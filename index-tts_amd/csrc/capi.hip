@@ -517,6 +517,20 @@ int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_
   API_END
 }
 
+int idxtts_gpt_session_evict(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_end(workspace, n, slots, true, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_stop(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_end(workspace, n, slots, false, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace) {
   API_BEGIN
   GPT_MODEL(ctx);

@@ -180,6 +180,10 @@ int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P,
 // step = 0, max_step = cap[b], live = 1} -- and copy the prefill's last valid row x[b][P[b]] (x [n][S][d]) to x_last[slot]
 int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
                         const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream);
+// Ends slots of a decode session between steps (eviction, stop): slot i of the n_slots <= 64 slots for every set bit i of `mask`, passed
+// by value -- live = 0, step kept (the codes produced so far).  cap_at_step: a slot that was live also gets max_step = step (a cap set
+// late: what reads the slot afterwards sees a request that ended at that cap); a slot that had ended is left as it was.
+int session_end_slots(SlotState* slots, int n_slots, unsigned long long mask, bool cap_at_step, hipStream_t stream);
 constexpr int GATHER_MAX_TABLES = 5;
 struct GatherArgs {
   float* out = nullptr; int ld_out = 0; int d = 0;

@@ -1048,6 +1048,25 @@ int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_
   return 0;
 }
 
+// ends the slots of `mask` (bit i = slot i) from outside the step: live = 0, step left as it is (the codes produced so far), as the
+// sampler leaves a slot that ended by itself.  cap_at_step (stop): a slot that was live also gets max_step = step, the cap it would
+// have ended at by itself; one that had ended keeps its state.
+__global__ __launch_bounds__(64) void session_end_slots_kernel(SlotState* slots, int n_slots, unsigned long long mask, int cap_at_step) {
+  const int i = threadIdx.x;
+  if (i >= n_slots || !((mask >> i) & 1ull)) return;
+  if (cap_at_step && slots[i].live) slots[i].max_step = slots[i].step;
+  slots[i].live = 0;
+}
+
+int session_end_slots(SlotState* slots, int n_slots, unsigned long long mask, bool cap_at_step, hipStream_t stream) {
+  IDX_CHECK(slots, "null pointer");
+  IDX_CHECK(n_slots >= 1 && n_slots <= 64, "1 <= slots <= 64");
+  if (!mask) return 0;
+  hipLaunchKernelGGL(session_end_slots_kernel, dim3(1), dim3(64), 0, stream, slots, n_slots, mask, cap_at_step ? 1 : 0);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
 // out[r][:] = sum over the tables t with idx[t][r] >= 0 of table[t][idx[t][r]][:]
 __global__ __launch_bounds__(256) void gather_sum_rows_kernel(const GatherArgs p) {
   const int r = blockIdx.x;

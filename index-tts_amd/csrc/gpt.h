@@ -200,6 +200,11 @@ struct GPTModel : ModelBase {
   int session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st);
   int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
   int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
+  // Ends the requests in slot_ids (HOST; beam sessions: the first slot of each group) from outside the step.  evict: they are free at
+  // once -- admissible in the next admit, never reported by a later step; allowed on a live request and on one that ended and was not
+  // read.  Otherwise stop: a live request ends as if its cap were the codes it has (the next step reports it, read returns them); one
+  // that has ended is left alone.  One id that is out of range, holds no request or is no group's first slot refuses the whole call.
+  int session_end(void* ws, int n, const int* slot_ids, bool evict, hipStream_t st);
   int session_release(void* ws);
   int embed(float* out, int rows, const int* text_ids, const int* text_pos_idx, const int* mel_ids, const int* mel_pos_idx,
             const float* extra, const int* extra_idx, hipStream_t st);

@@ -875,6 +875,31 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   return 0;
 }
 
+// evict and stop: every id is checked before anything changes; then one launch on the session's stream (ordered between step replays;
+// the ids travel in the launch arguments) ends the requests' slots -- a beam group's num_beams slots, which is all the beam stages read
+// to find a group dead (the state they leave a group in at its cap) -- and evict gives the units back
+int GPTModel::session_end(void* ws, int n, const int* slot_ids, bool evict, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(n >= 0 && (slot_ids || n == 0), "null pointer");
+  const int fan = s.num_beams ? s.num_beams : 1;
+  unsigned long long mask = 0;
+  for (int b = 0; b < n; ++b) {
+    const int slot = slot_ids[b];
+    IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+    IDX_CHECK(slot % fan == 0, "a beam session's group is addressed by its first slot");
+    IDX_CHECK(s.busy[slot], "slot holds no request");
+    for (int j = 0; j < fan; ++j) mask |= 1ull << (slot + j);
+  }
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  if (session_end_slots(sb.w.slots, s.slots, mask, !evict, st)) return 1;
+  if (evict)
+    for (int i = 0; i < s.slots; ++i)
+      if ((mask >> i) & 1ull) s.busy[i] = 0;
+  return 0;
+}
+
 int GPTModel::latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws,
                      size_t ws_bytes, hipStream_t st) {
   IDX_CHECK(emb && latent_out, "null pointer");

@@ -26,7 +26,7 @@ SYMBOLS = [
     "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
     "idxtts_gpt_session_read", "idxtts_gpt_session_release", "idxtts_gpt_session_workspace_bytes_ex", "idxtts_gpt_session_init_ex",
     "idxtts_gpt_session_admit_sampled", "idxtts_gpt_session_workspace_bytes_beam", "idxtts_gpt_session_init_beam",
-    "idxtts_gpt_session_admit_beam",
+    "idxtts_gpt_session_admit_beam", "idxtts_gpt_session_evict", "idxtts_gpt_session_stop",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
@@ -190,6 +190,8 @@ def load() -> ctypes.CDLL:
     lib.idxtts_gpt_session_init_beam.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]
     lib.idxtts_gpt_session_admit_beam.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p]
+    lib.idxtts_gpt_session_evict.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_stop.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_latent.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_s2mel_create.argtypes = [POINTER(S2MelConfigC), POINTER(c_void_p)]
     lib.idxtts_s2mel_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]

@@ -561,6 +561,43 @@ class _Session:
         self._noise.pop(i, None)
         return out[: n.value]
 
+    def _ids(self, ids) -> list:
+        """One id or a list of them -> a list of requests this session holds (admitted and not taken); ValueError otherwise."""
+        ids = [ids] if isinstance(ids, (int, np.integer)) else list(ids)
+        out = []
+        for i in ids:
+            if not isinstance(i, (int, np.integer)) or not 0 <= int(i) < len(self._busy) or not self._busy[int(i)]:
+                raise ValueError(f"{i!r} holds no request ({'slot' if self._unit == 1 else 'group'} ids 0 .. {len(self._busy) - 1})")
+            out.append(int(i))
+        return out
+
+    def _end(self, fn, ids: list) -> None:
+        h = np.ascontiguousarray([i * self._unit for i in ids], dtype=np.int32)
+        _lib.check(fn(self.gpt._h, len(ids), h.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
+
+    def evict(self, ids) -> None:
+        """Ends the requests `ids` (one id or a list: slots, or groups) and frees them now: live ones and ones that have finished and
+        were not taken.  Their places are admissible at once, step() never reports them and take() on them raises.  One launch on the
+        session's stream, no synchronisation; every other request's codes are untouched.  A bad id raises ValueError, nothing changes."""
+        ids = self._ids(ids)
+        if not ids:
+            return
+        self._end(self._lib.idxtts_gpt_session_evict, ids)
+        for i in ids:       # as take(); a request's draws are let go only now, with the launch that ends its reads on the stream
+            self._busy[i] = False
+            self._done.discard(i)
+            nz = self._noise.pop(i, None)
+            if nz is not None:
+                nz.record_stream(self.stream)
+
+    def stop(self, ids) -> None:
+        """Ends the live requests among `ids` and keeps them: the next step() (step(0) too) reports them and take() returns the k
+        codes produced so far -- bit for bit what the same request with cap k returns (a beam group: generate_beam with
+        max_new_tokens = k).  A request that has already finished is left alone.  A bad id raises ValueError, nothing changes."""
+        ids = self._ids(ids)
+        if ids:
+            self._end(self._lib.idxtts_gpt_session_stop, ids)
+
     def close(self) -> None:
         if getattr(self, "_ws", None) is not None:
             self.stream.synchronize()

@@ -147,8 +147,48 @@ def merge_acoustic_states(items):
     return st, noise
 
 
+def _set_exception(fut, e: BaseException) -> None:
+    """A failure handed to a request that has no outcome yet.  A cancelled request has one: it is left alone, also when the caller's
+    cancel() lands between the check and the call."""
+    try:
+        if not fut.done():
+            fut.set_exception(e)
+    except concurrent.futures.InvalidStateError:
+        pass
+
+
+_NOTIFY = threading.Lock()
+
+
+def _cancelled(owner) -> bool:
+    """Has the request's Future (owner.done) been cancelled?  Whoever sees it first tells the Future's waiters: concurrent.futures.wait
+    and as_completed count a cancelled Future only once set_running_or_notify_cancel has been called on it, and a second call is an
+    error, hence the flag."""
+    if not owner.done.cancelled():
+        return False
+    with _NOTIFY:
+        if not owner.notified:
+            owner.notified = True
+            owner.done.set_running_or_notify_cancel()
+    return True
+
+
+def _start(owner) -> bool:
+    """The point of no return: marks the request running, after which cancel() on its Future returns False.  False: the request was
+    cancelled first (its waiters are told), or it already has an outcome."""
+    fut = owner.done
+    with _NOTIFY:
+        if owner.notified or (fut.done() and not fut.cancelled()):
+            return False
+        if fut.set_running_or_notify_cancel():
+            return True
+        owner.notified = True
+        return False
+
+
 class _Request:
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done")
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done",
+                 "notified")
 
     def compatible(self, other: "_Request") -> bool:
         # same prompt and settings, greedy (sampling draws are per call) and the SAME text width: a wider neighbour would left-pad this
@@ -204,7 +244,7 @@ class BatchPipeline:
         noise_seed (instead of `noise`): an int, or one int per row (utterance_noise_seeds) -- the rows' CFM noise seeds are fixed
         here, so the request's noise is the same whatever it is merged with.  A bad value, or both, fails this Future only."""
         r = _Request()
-        r.done = concurrent.futures.Future()
+        r.done, r.notified = concurrent.futures.Future(), False
         try:
             r.noise, r.noise_seeds = _request_noise(noise, noise_seed, int(text_tokens.shape[0]))
         except ValueError as e:
@@ -230,12 +270,35 @@ class BatchPipeline:
             if self._running == 0:
                 self._groups_taken = 0
             limit = min(self.coalesce, 1 + self._groups_taken // self.decode_lanes)
+            self._drop_cancelled_head()
+            if not self._queue:
+                return []
             group = [self._queue.popleft()]
-            while len(group) < limit and self._queue and group[0].compatible(self._queue[0]) and self._keeps_kernels(group + [self._queue[0]]):
+            while len(group) < limit and self._drop_cancelled_head() and group[0].compatible(self._queue[0]) and \
+                    self._keeps_kernels(group + [self._queue[0]]):
                 group.append(self._queue.popleft())
             self._groups_taken += 1
             self._running += len(group)
             return group
+
+    def _drop_cancelled_head(self) -> bool:
+        """Drops the cancelled requests at the head of the queue (under _qlock); is a request left?"""
+        while self._queue and _cancelled(self._queue[0]):
+            self._queue.popleft()
+        return bool(self._queue)
+
+    def cancel(self, fut: concurrent.futures.Future) -> bool:
+        """fut.cancel(), and the request leaves the queues now.  True: the request is cancelled -- it is never merged into a decode
+        group or an acoustic batch from here on (a static decode that has started runs to its end: there is no slot to free, its rows
+        are dropped behind it).  False: its acoustic job has started (or it is done) and it completes as usual.  Calling fut.cancel()
+        alone has the same outcome; the request is then dropped where the pipeline next touches it."""
+        ok = fut.cancel()
+        with self._qlock:
+            self._queue = collections.deque(r for r in self._queue if not _cancelled(r))
+            kept = collections.deque(item for item in self._aq if not _cancelled(item[0]))
+            self._running -= len(self._aq) - len(kept)
+            self._aq = kept
+        return ok
 
     def _keeps_kernels(self, group) -> bool:
         from . import _lib
@@ -277,30 +340,39 @@ class BatchPipeline:
                 sg.synchronize()
             if self.trace is not None:
                 self.trace.append(("decode", t0, time.perf_counter(), int(text.shape[0])))
-            for r, sub in zip(group, subs):      # every request's rows go to its own acoustic job
+            for r, sub in zip(group, subs):      # every request's rows go to its own acoustic job; a cancelled one is retired here
                 with self._qlock:
-                    self._aq.append((r, sub))
+                    keep = not _cancelled(r)
+                    if keep:
+                        self._aq.append((r, sub))
+                    else:
+                        self._running -= 1
                 handed += 1
-                self._acoustic.submit(self._acoustic_drain)      # one drain per request: a drain that finds nothing (merged away) returns
+                if keep:
+                    self._acoustic.submit(self._acoustic_drain)      # one drain per request: a drain that finds nothing (merged away) returns
         except BaseException as e:                  # noqa: BLE001 -- handed to the callers through their futures
             with self._qlock:
-                self._running -= len(group) - handed      # (requests already handed to an acoustic job are retired there)
+                self._running -= len(group) - handed      # (requests already handed on or dropped are retired there)
             for r in group:
-                if not r.done.done():
-                    r.done.set_exception(e)
+                _set_exception(r.done, e)
 
     def _take_acoustic(self):
         """Up to `acoustic_coalesce` decoded requests of one prompt (of any prompts with acoustic_mix_prompts), each with its own CFM
-        noise or all with noise seeds (a merged draw from torch's generator would consume it differently from the separate calls)."""
+        noise or all with noise seeds (a merged draw from torch's generator would consume it differently from the separate calls).
+        The point of no return: every request taken is marked running (_start), so cancel() on it fails from here on; the cancelled
+        ones are dropped and retired."""
         with self._qlock:
-            if not self._aq:
-                return []
-            group = [self._aq.popleft()]
-            kind = _noise_kind(group[0][0])
-            while (len(group) < self.acoustic_coalesce and self._aq and kind and _noise_kind(self._aq[0][0]) == kind
-                   and (self.acoustic_mix_prompts or self._aq[0][0].cond is group[0][0].cond)):
-                group.append(self._aq.popleft())
-            return group
+            while self._aq:
+                group = [self._aq.popleft()]
+                kind = _noise_kind(group[0][0])
+                while (len(group) < self.acoustic_coalesce and self._aq and kind and _noise_kind(self._aq[0][0]) == kind
+                       and (self.acoustic_mix_prompts or self._aq[0][0].cond is group[0][0].cond)):
+                    group.append(self._aq.popleft())
+                kept = [item for item in group if _start(item[0])]
+                self._running -= len(group) - len(kept)
+                if kept:
+                    return kept
+            return []
 
     @staticmethod
     def _merge_states(group):
@@ -334,8 +406,7 @@ class BatchPipeline:
                 r.done.set_result(mine)
         except BaseException as e:                  # noqa: BLE001
             for r, _ in group:
-                if not r.done.done():
-                    r.done.set_exception(e)
+                _set_exception(r.done, e)
         finally:
             with self._qlock:
                 self._running -= len(group)
@@ -360,7 +431,7 @@ class BatchPipeline:
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq")
+                 "seq", "deadline", "notified")
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
@@ -468,6 +539,14 @@ class ContinuousPipeline:
     that is free then sees all of them.  `trace`: set it to a list to record ("acoustic", start, end, rows, request numbers) for
     every acoustic job (host perf_counter times; requests numbered from 0 in submission order).
 
+    Cancellation: the Future is the interface.  fut.cancel() (or pipe.cancel(fut), which also wakes the lanes) succeeds until the
+    request's acoustic job starts; from then on it returns False and the request completes.  A cancelled request is dropped wherever
+    the pipeline next touches it: its waiting utterances are never admitted, its decoding rows are evicted at the next poll
+    (session.evict: their slots or groups are admissible in that same poll), its finished rows are not kept, and it never reaches an
+    acoustic job -- the other requests of a merged acoustic batch get their own results.  The rows of a request that failed are
+    evicted the same way.  submit(deadline_s=...) cancels a request that many seconds after submit unless its acoustic job has
+    started.  Nobody else's codes move (the session contract holds across evictions).
+
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
@@ -480,6 +559,7 @@ class ContinuousPipeline:
         self._aq = collections.deque()          # decoded requests waiting for an acoustic worker
         self._submitted = 0
         self.trace = None
+        self._clock = time.monotonic            # deadlines are read off this clock
         self.num_beams = int(num_beams)
         if not 1 <= self.num_beams <= 8:
             raise ValueError("num_beams must be in 1 .. 8")
@@ -522,21 +602,25 @@ class ContinuousPipeline:
         return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
-               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None) -> concurrent.futures.Future:
+               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
+               deadline_s: Optional[float] = None) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
-        (see utterance_beams)."""
+        (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
+        has started by then (checked wherever cancellation is: each poll, each acoustic hand-over); None: no deadline."""
+        if deadline_s is not None:
+            deadline_s = float(deadline_s)
         if self.num_beams > 1:
             return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed)
+                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed, deadline_s)
         if sampling and not self.allow_sampling:
             raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
         if sampling and int(sampling.get("num_beams") or 1) > 1:
             raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed)
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s)
 
-    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None):
+    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -545,8 +629,9 @@ class ContinuousPipeline:
         j.text, j.cond, j.max_mel_tokens, j.noise = torch.as_tensor(text_tokens), cond, int(max_mel_tokens), noise
         B = int(j.text.shape[0])
         j.codes, j.left, j.failed = [None] * B, B, False
-        j.done = concurrent.futures.Future()
+        j.done, j.notified = concurrent.futures.Future(), False
         j.sampling, j.seq, j.noise_seeds = None, -1, None
+        j.deadline = None if deadline_s is None else self._clock() + deadline_s
         try:                                    # a bad parameter fails this request's Future only
             j.noise, j.noise_seeds = _request_noise(noise, noise_seed, B)
             if per_utterance is not None:
@@ -571,8 +656,30 @@ class ContinuousPipeline:
     @staticmethod
     def _fail(j: _Job, e: BaseException) -> None:
         j.failed = True
-        if not j.done.done():
-            j.done.set_exception(e)
+        _set_exception(j.done, e)
+
+    def cancel(self, fut: concurrent.futures.Future) -> bool:
+        """fut.cancel(), and the lanes are woken so that the request is dropped at once.  True: the request is cancelled (see the
+        class); False: its acoustic job has started (or it is done) and it completes as usual."""
+        ok = fut.cancel()
+        with self._cv:
+            self._cv.notify_all()
+        return ok
+
+    def _gone(self, j: _Job) -> bool:
+        """Is there nobody left to decode `j` for -- cancelled (by its caller, or here: past its deadline) or failed?"""
+        if j.deadline is not None and not j.done.done() and self._clock() >= j.deadline:
+            j.done.cancel()                     # refused once the acoustic job has started: the request then completes
+        return j.failed or _cancelled(j)
+
+    def _evict_gone(self, sess, in_slot) -> None:
+        """Frees the slots (groups) whose request is gone, in one evict call; sessions without evict are never asked while there is
+        nothing to evict."""
+        gone = [s for s, (j, _) in in_slot.items() if self._gone(j)]
+        if gone:
+            sess.evict(gone)
+            for s in gone:
+                del in_slot[s]
 
     def _prompt_rows(self, j: _Job, idx):
         """The [P, d] prompts of utterances `idx` of a job (prepare_gpt_inputs, unpadded), on the current stream."""
@@ -594,7 +701,7 @@ class ContinuousPipeline:
             free = len(self._free(sess))
             while self._waiting and len(take) < free:
                 j, i = self._waiting.popleft()
-                if not j.failed:
+                if not self._gone(j):           # a cancelled or failed request's waiting utterances are dropped
                     take.append((j, i))
         by_job = collections.OrderedDict()
         for j, i in take:
@@ -631,7 +738,7 @@ class ContinuousPipeline:
         for s in finished:
             j, i = in_slot.pop(s)
             codes = sess.take(s).cpu()
-            if j.failed:
+            if self._gone(j):
                 continue
             j.codes[i] = codes
             j.left -= 1
@@ -657,6 +764,7 @@ class ContinuousPipeline:
                             self._cv.wait()
                         if self._closing and not self._waiting and not in_slot:
                             break
+                    self._evict_gone(sess, in_slot)      # before admitting: the freed places are admissible in this poll
                     if self._free(sess):
                         self._admit(sess, in_slot)
                     if in_slot:
@@ -680,25 +788,30 @@ class ContinuousPipeline:
     def _take_acoustic(self) -> list:
         """The next acoustic job: the oldest decoded request, plus -- when it carries explicit noise, or noise seeds -- the next ones of
         the same kind, up to `acoustic_coalesce` requests and `acoustic_max_rows` rows (requests with neither, of the other kind, or with
-        too many rows, wait for a job of their own)."""
+        too many rows, wait for a job of their own).  Requests that are gone are dropped from the queue first.  The point of no return:
+        every request taken is marked running (_start), so cancel() on it fails from here on."""
         with self._cv:
-            if not self._aq:
-                return []
-            group = [self._aq.popleft()]
-            rows = int(group[0].text.shape[0])
-            kind = _noise_kind(group[0])
-            if kind:
-                i = 0
-                while len(group) < self.acoustic_coalesce and i < len(self._aq):
-                    j = self._aq[i]
-                    nb = int(j.text.shape[0])
-                    if _noise_kind(j) == kind and rows + nb <= self.acoustic_max_rows:
-                        del self._aq[i]
-                        group.append(j)
-                        rows += nb
-                    else:
-                        i += 1
-            return group
+            while True:
+                self._aq = collections.deque(j for j in self._aq if not self._gone(j))
+                if not self._aq:
+                    return []
+                group = [self._aq.popleft()]
+                rows = int(group[0].text.shape[0])
+                kind = _noise_kind(group[0])
+                if kind:
+                    i = 0
+                    while len(group) < self.acoustic_coalesce and i < len(self._aq):
+                        j = self._aq[i]
+                        nb = int(j.text.shape[0])
+                        if _noise_kind(j) == kind and rows + nb <= self.acoustic_max_rows:
+                            del self._aq[i]
+                            group.append(j)
+                            rows += nb
+                        else:
+                            i += 1
+                group = [j for j in group if _start(j)]      # (but for a cancel that landed since the check above)
+                if group:
+                    return group
 
     def _acoustic_drain(self):
         group = self._take_acoustic()
