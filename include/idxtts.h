@@ -430,6 +430,50 @@ int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_
  * idxtts_gpt_generate_beam with max_new_tokens = k and the same seed, or the first k rows of its exp_noise). */
 int idxtts_gpt_session_evict(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream);
 int idxtts_gpt_session_stop(idxtts_ctx* ctx, int n, const int* slots, void* workspace, void* stream);
+/* Preempt and resume: a decoding request steps aside and keeps what it has computed.  _park gathers everything the request's slot
+ * owns -- step scalars, sampler, the ids it has seen, its codes and positions [0, pos) of its keys and values in every layer -- into
+ * one contiguous DEVICE buffer, the parked row, and frees the slot as _evict does; _resume scatters a parked row into any free slot of
+ * any session that fits it, at any later time.  Both are one launch on `stream`, the session's stream, between steps: bytes moved are
+ * proportional to pos, the captured step and the workspace layout are untouched.  The row's next decode input is not saved: _resume
+ * rebuilds it from the last code and the mel position, so a parked row does not depend on which GEMV the step runs.
+ * Determinism: a request parked and resumed any number of times, into any slots, returns bit for bit the codes of its uninterrupted
+ * run; every other request's codes are untouched.  Greedy and sampled sessions; a beam session's group (its scorer state) cannot be
+ * parked, both calls fail on one.
+ * The parked row: idxtts_park_header, then segments that each start 16-byte aligned, padding written as zero (a parked row is a
+ * function of the request's state alone, byte for byte).  With pad16(n) = (n + 15) & ~15, V = number_mel_codes, C = 16 key chunks
+ * (fp32 cache) or 8 (bf16, fp8), g = 16 bytes of one key chunk per position (fp32, bf16) or 8 (fp8), e = 4 / 2 / 1 bytes per element:
+ *   [header 128] [seen: pad16(V)] [codes int64: pad16(8 * step)]
+ *   then for every layer, for every head:  C key runs of pad16(pos * g) | values pos * 64 * e | fp8 only: key scales pad16(4 * pos) |
+ *   value scales pad16(4 * pos)
+ *   bytes = 128 + pad16(V) + pad16(8 * step) + layers * heads * (C * pad16(pos * g) + pos * 64 * e + (fp8 ? 2 * pad16(4 * pos) : 0))
+ * exp_noise travels as the caller's pointer: the tensor must stay alive while the row is parked and until the resumed request ends. */
+#define IDXTTS_PARK_MAGIC 0x4b525049u      /* "IPRK" */
+#define IDXTTS_PARK_VERSION 1
+typedef struct idxtts_park_header {      /* 128 bytes */
+  unsigned magic, version;
+  int layers, heads, model_dim, number_mel_codes;      /* the model the row belongs to */
+  int slots, kv_format, gemm_mode, sampled;            /* of the session it left (sampled: IDXTTS_SESSION_SAMPLED) */
+  int pos, mel_pos, step, max_step;                    /* keys cached, mel position, codes produced, the request's cap */
+  int mode; float temperature; int top_k; float top_p; /* the request's sampler (idxtts_sampling; mode 0 = greedy) */
+  unsigned long long seed;
+  unsigned long long exp_noise;                        /* device pointer, or 0 */
+  unsigned long long bytes;                            /* the whole parked row, header included */
+  int reserved[8];                                /* zero */
+} idxtts_park_header;
+/* Exact size of slot's parked row now (one small device-to-host read of its state); 0 with idxtts_last_error set when the slot cannot
+ * be parked (see _park). */
+size_t idxtts_gpt_session_park_bytes(idxtts_ctx* ctx, int slot, void* workspace, void* stream);
+/* slot must hold a request that is still decoding: one that has ended is to be read (_read), not parked.  dst: device, 16-byte aligned,
+ * dst_bytes >= _park_bytes.  Sets *written (host, may be NULL) and frees the slot: admissible in the next call, never reported by a
+ * later _step.  Every refusal happens before anything changes. */
+int idxtts_gpt_session_park(idxtts_ctx* ctx, int slot, void* dst, size_t dst_bytes, size_t* written, void* workspace, void* stream);
+/* src: a parked row in device memory (16-byte aligned), src_bytes of it.  Refused, before anything changes: a bad magic or version,
+ * another model's dimensions, a session with other slots, KV format or GEMM mode (they select the key split and the GEMV: the
+ * remaining codes would belong to another reference), a sampled request offered to a greedy session, a cap above the session's
+ * max_new_tokens, pos + (max_step - step) + 1 beyond the session's cache length, a slot that is busy or out of range, src_bytes
+ * shorter than the header says.  On success the slot decodes on from the next _step; src may be freed once the work queued on `stream`
+ * has run (stream order). */
+int idxtts_gpt_session_resume(idxtts_ctx* ctx, int slot, const void* src, size_t src_bytes, void* workspace, void* stream);
 /* Forgets the session on this workspace (and its captured step); the caller may then free or reuse the workspace. */
 int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace);
 /* Latent pass: full causal forward over emb [B][S][d]; latent[b][i] = final_norm(ln_f(h[b][mel_start + i])), i < M.

@@ -1,4 +1,5 @@
 #pragma once
+#include "../../include/idxtts.h"
 #include "common.h"
 
 namespace idxtts {
@@ -184,6 +185,39 @@ int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_
 // by value -- live = 0, step kept (the codes produced so far).  cap_at_step: a slot that was live also gets max_step = step (a cap set
 // late: what reads the slot afterwards sees a request that ended at that cap); a slot that had ended is left as it was.
 int session_end_slots(SlotState* slots, int n_slots, unsigned long long mask, bool cap_at_step, hipStream_t stream);
+// Preempt and resume (idxtts.h "Preempt and resume"): the byte layout of a parked row, from the header's fields alone
+struct ParkLayout {
+  int chunks = 0, gran = 0, elem = 0;      // key chunks per head, bytes of one chunk per position, bytes per element
+  size_t krun = 0, vrun = 0, srun = 0;     // padded bytes of one key run, the value run, one scale run (fp8 only, else 0)
+  size_t off_seen = 0, off_codes = 0, off_kv = 0, per_head = 0, bytes = 0;
+};
+__host__ __device__ static inline size_t park_pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+__host__ __device__ static inline ParkLayout park_layout(int kv_fmt, int layers, int heads, int V, int pos, int step) {
+  ParkLayout l;
+  l.chunks = kv_fmt == 0 ? 16 : 8; l.gran = kv_fmt == 2 ? 8 : 16; l.elem = kv_fmt == 2 ? 1 : kv_fmt ? 2 : 4;
+  l.krun = park_pad16((size_t)pos * l.gran); l.vrun = (size_t)pos * 64 * l.elem; l.srun = kv_fmt == 2 ? park_pad16((size_t)pos * 4) : 0;
+  l.off_seen = sizeof(idxtts_park_header);
+  l.off_codes = l.off_seen + park_pad16((size_t)V);
+  l.off_kv = l.off_codes + park_pad16((size_t)step * 8);
+  l.per_head = l.chunks * l.krun + l.vrun + 2 * l.srun;
+  l.bytes = l.off_kv + (size_t)layers * heads * l.per_head;
+  return l;
+}
+static_assert(sizeof(idxtts_park_header) == 128, "parked-row header");
+struct ParkArgs {
+  idxtts_park_header hdr;        // by value: _park writes it in front of the row, _resume restores the slot from it (checked on the host)
+  char* blob = nullptr;          // the parked row (16-byte aligned): written by park, read by resume
+  char* kcache = nullptr; char* vcache = nullptr; float* kscale = nullptr; float* vscale = nullptr;   // layer 0 of the session's cache
+  size_t layer_bytes = 0, layer_scales = 0;      // one layer of kcache / vcache in bytes, of kscale / vscale in floats
+  int slot = 0, Smax = 0;
+  SlotState* slots = nullptr; SlotSampling* samp = nullptr;      // samp: sampled sessions only (resume rewrites the slot's row)
+  unsigned char* seen = nullptr; long long* codes = nullptr; int codes_ld = 0; int* cur_tok = nullptr;
+  SampleArgs::Embed embed; int B = 0;      // resume: where the slot's next input goes (the session tails' block), B = the session's slots
+};
+// One launch each, between steps on the session's stream.  park: slot -> blob, then live = 0.  resume: blob -> slot, live = 1 with the
+// header's scalars, and the slot's next input mel_emb[last code] + mel_pos[mel_pos] written as the sampler tails write it.
+int session_park_slot(const ParkArgs& a, hipStream_t stream);
+int session_resume_slot(const ParkArgs& a, hipStream_t stream);
 constexpr int GATHER_MAX_TABLES = 5;
 struct GatherArgs {
   float* out = nullptr; int ld_out = 0; int d = 0;

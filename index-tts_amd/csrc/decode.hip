@@ -482,12 +482,15 @@ __device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int
 
 // Row b's next input x = mel_emb[tok] + mel_pos[mel_pos], by all 1024 threads of a sampler's workgroup: A-fragment images for the
 // fp32-MFMA GEMV step (the folded LayerNorm's statistics are computed by the consumer), or a row + its statistics for the plane GEMV
-__device__ __forceinline__ void write_next_input(const SampleArgs& p, const int b, const int tok, const int mel_pos, const int tid) {
-  if (p.embed.x_frag) {
-    const int d = p.embed.d;
-    for (int e = tid; e < d; e += 1024) p.embed.x_frag[frag_index(b, e, d >> 4)] = p.embed.mel_emb[(size_t)tok * d + e] + p.embed.mel_pos[(size_t)mel_pos * d + e];
+// (NT threads; session_resume_slot rebuilds a resumed row's input with it)
+template <int NT>
+__device__ __forceinline__ void write_next_input(const SampleArgs::Embed& em, const int B, const int b, const int tok, const int mel_pos,
+                                                 const int tid) {
+  if (em.x_frag) {
+    const int d = em.d;
+    for (int e = tid; e < d; e += NT) em.x_frag[frag_index(b, e, d >> 4)] = em.mel_emb[(size_t)tok * d + e] + em.mel_pos[(size_t)mel_pos * d + e];
   } else {
-    embed_row_pl<1024>(p.embed.x_row, p.embed.x_stats, b, p.B, p.embed.d, p.embed.mel_emb, p.embed.mel_pos, tok, mel_pos, tid);
+    embed_row_pl<NT>(em.x_row, em.x_stats, b, B, em.d, em.mel_emb, em.mel_pos, tok, mel_pos, tid);
   }
 }
 
@@ -513,7 +516,7 @@ __global__ __launch_bounds__(1024) void sample_greedy_kernel(const SampleArgs p)
   }
   if (!fused) return;
   __syncthreads();
-  write_next_input(p, b, s_tok, mp_next, tid);
+  write_next_input<1024>(p.embed, p.B, b, s_tok, mp_next, tid);
   __syncthreads();      // every read of the step scalars by this workgroup is behind us
   // (not wg_arrive_last: this workgroup hands over no stores, so there is no wait in front and nothing to return behind)
   if (tid == 0) {
@@ -556,7 +559,7 @@ __device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const 
     if (tid == 0) { ss->step += 1; ss->live = 0; }
     return;
   }
-  write_next_input(p, b, s_tok, s_mp, tid);
+  write_next_input<1024>(p.embed, p.B, b, s_tok, s_mp, tid);
   if (tid == 0) { ss->pos += 1; ss->mel_pos += 1; ss->step += 1; }      // this slot's scalars: nobody else reads them in this launch
 }
 
@@ -1066,6 +1069,129 @@ int session_end_slots(SlotState* slots, int n_slots, unsigned long long mask, bo
   IDX_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- preempt and resume (decode.h ParkArgs, idxtts.h "Preempt and resume") ----
+// n bytes (a multiple of 4) from src to dst, both 16-byte aligned, by the PARK_NT threads of a workgroup: 16-byte vectors, consecutive
+// lanes on consecutive vectors, four in flight per thread; the last n % 16 bytes go dword by dword.  PAD: dst is a segment of the
+// parked row, whose last vector is written whole with zeros behind the data; else exactly n bytes are written (a cache run: what lies
+// behind position pos belongs to later steps).
+constexpr int PARK_NT = 256;
+template <bool PAD>
+__device__ __forceinline__ void park_copy_run(char* dst, const char* src, const size_t n, const int tid) {
+  const size_t nv = n >> 4;
+  const uint4* s4 = reinterpret_cast<const uint4*>(src);
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  size_t i = tid;
+  for (; i + 3 * PARK_NT < nv; i += 4 * PARK_NT) {
+    const uint4 a = s4[i], b = s4[i + PARK_NT], c = s4[i + 2 * PARK_NT], e = s4[i + 3 * PARK_NT];
+    d4[i] = a; d4[i + PARK_NT] = b; d4[i + 2 * PARK_NT] = c; d4[i + 3 * PARK_NT] = e;
+  }
+  for (; i < nv; i += PARK_NT) d4[i] = s4[i];
+  const int tail = (int)(n & 15) >> 2;      // dwords behind the last whole vector
+  if (tail && tid == 0) {
+    const unsigned* sw = reinterpret_cast<const unsigned*>(src) + nv * 4;
+    unsigned* dw = reinterpret_cast<unsigned*>(dst) + nv * 4;
+    if (PAD) {
+      d4[nv] = make_uint4(sw[0], tail > 1 ? sw[1] : 0u, tail > 2 ? sw[2] : 0u, 0u);
+    } else {
+      dw[0] = sw[0];
+      if (tail > 1) dw[1] = sw[1];
+      if (tail > 2) dw[2] = sw[2];
+    }
+  }
+}
+
+// Grid (runs + 1, heads, layers), runs = 2 * chunks (+ 2: fp8 scales).  Workgroup (r, h, l): r < chunks: key chunk r of (l, h), one
+// straight run of pos granules; r < 2 * chunks: piece r - chunks of the value run (pos * 64 elements, cut into `chunks` pieces at
+// vector boundaries so that every workgroup moves about as much as a key run); then the two scale runs.  Workgroup (runs, 0, 0) moves
+// the small state -- header, seen row, codes, step scalars, sampler -- and on resume writes the slot's next input.
+template <bool RESUME>
+__global__ __launch_bounds__(PARK_NT) void session_park_kernel(const ParkArgs p) {
+  const int tid = threadIdx.x, r = blockIdx.x, h = blockIdx.y, l = blockIdx.z, H = gridDim.y;
+  const idxtts_park_header& hd = p.hdr;
+  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step);
+  const int C = lay.chunks, runs = 2 * C + (hd.kv_format == 2 ? 2 : 0);
+  auto move = [&](char* cache, char* seg, size_t n) {      // one run between the cache and its segment of the parked row
+    if (RESUME) park_copy_run<false>(cache, seg, n, tid);
+    else park_copy_run<true>(seg, cache, n, tid);
+  };
+  if (r < runs) {
+    char* const seg = p.blob + lay.off_kv + ((size_t)l * H + h) * lay.per_head;
+    const size_t sh = (size_t)p.slot * H + h;
+    if (r < C) {
+      move(p.kcache + l * p.layer_bytes + (sh * C + r) * p.Smax * lay.gran, seg + r * lay.krun, (size_t)hd.pos * lay.gran);
+    } else if (r < 2 * C) {
+      const size_t nv = lay.vrun >> 4, v0 = nv * (r - C) / C, v1 = nv * (r - C + 1) / C;
+      move(p.vcache + l * p.layer_bytes + sh * p.Smax * 64 * lay.elem + (v0 << 4), seg + C * lay.krun + (v0 << 4), (v1 - v0) << 4);
+    } else {
+      float* const sc = (r == 2 * C ? p.kscale : p.vscale) + l * p.layer_scales + sh * p.Smax;
+      move(reinterpret_cast<char*>(sc), seg + C * lay.krun + lay.vrun + (r - 2 * C) * lay.srun, (size_t)hd.pos * 4);
+    }
+    return;
+  }
+  if (h || l) return;
+  const int V = hd.number_mel_codes, step = hd.step;
+  unsigned char* const seen = p.seen + (size_t)p.slot * V;      // (a row of seen is only byte aligned)
+  long long* const codes = p.codes + (size_t)p.slot * p.codes_ld;
+  unsigned* const bseen = reinterpret_cast<unsigned*>(p.blob + lay.off_seen);
+  long long* const bcodes = reinterpret_cast<long long*>(p.blob + lay.off_codes);
+  const int nd = (int)(park_pad16((size_t)V) >> 2), nc = (int)(park_pad16((size_t)step * 8) >> 3);
+  SlotState* const ss = p.slots + p.slot;
+  if (!RESUME) {
+    for (int i = tid; i < nd; i += PARK_NT) {
+      unsigned w = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * i + j < V) w |= (unsigned)seen[4 * i + j] << (8 * j);
+      bseen[i] = w;
+    }
+    for (int i = tid; i < nc; i += PARK_NT) bcodes[i] = i < step ? codes[i] : 0ll;
+    if (tid == 0) {
+      *reinterpret_cast<idxtts_park_header*>(p.blob) = hd;
+      ss->live = 0;      // the slot is free, as session_end_slots leaves an evicted one
+    }
+  } else {
+    for (int i = tid; i < nd; i += PARK_NT) {
+      const unsigned w = bseen[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (4 * i + j < V) seen[4 * i + j] = (unsigned char)(w >> (8 * j));
+    }
+    for (int i = tid; i < step; i += PARK_NT) codes[i] = bcodes[i];
+    // the row's last code, kept inside the embedding table whatever the bytes say (the header is checked on the host, the body is not)
+    const int tok = min(max((int)bcodes[step - 1], 0), V - 1);
+    write_next_input<PARK_NT>(p.embed, p.B, p.slot, tok, hd.mel_pos, tid);
+    if (tid == 0) {
+      p.cur_tok[p.slot] = tok;
+      if (p.samp) p.samp[p.slot] = SlotSampling{hd.mode, hd.temperature, hd.top_k, hd.top_p, hd.seed, reinterpret_cast<const float*>(hd.exp_noise)};
+      *ss = SlotState{hd.pos, hd.mel_pos, hd.step, hd.max_step, 1};
+    }
+  }
+}
+
+static int park_launch(const ParkArgs& a, bool resume, hipStream_t stream) {
+  const idxtts_park_header& hd = a.hdr;
+  IDX_CHECK(a.blob && a.kcache && a.vcache && a.slots && a.seen && a.codes && a.cur_tok, "null pointer");
+  IDX_CHECK(hd.kv_format >= 0 && hd.kv_format <= 2 && (hd.kv_format != 2 || (a.kscale && a.vscale)), "KV format");
+  IDX_CHECK(hd.layers >= 1 && hd.layers <= 65535 && hd.heads >= 1 && hd.heads <= 65535, "shape");
+  IDX_CHECK(a.slot >= 0 && a.slot < a.B && hd.step >= 1 && hd.step <= a.codes_ld && hd.pos >= 1 && hd.pos <= a.Smax, "slot state out of range");
+  IDX_CHECK(a.Smax % 4 == 0 && a.layer_bytes % 16 == 0 && a.layer_scales % 4 == 0, "cache runs must start 16-byte aligned");
+  IDX_CHECK(((uintptr_t)a.blob | (uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.kscale | (uintptr_t)a.vscale) % 16 == 0,
+            "the parked row and the caches must be 16-byte aligned");
+  IDX_CHECK(!resume || ((a.embed.x_row && a.embed.x_stats) || a.embed.x_frag), "resume needs the step's input buffers");
+  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step);
+  const int runs = 2 * lay.chunks + (hd.kv_format == 2 ? 2 : 0);
+  static const int cat_p = prof_register("session_park_kernel"), cat_r = prof_register("session_resume_kernel");
+  ProfScope prof(resume ? cat_r : cat_p, stream, 0.0, 2.0 * (double)lay.bytes);
+  const dim3 grid(runs + 1, hd.heads, hd.layers);
+  if (resume) hipLaunchKernelGGL(session_park_kernel<true>, grid, dim3(PARK_NT), 0, stream, a);
+  else hipLaunchKernelGGL(session_park_kernel<false>, grid, dim3(PARK_NT), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+int session_park_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, false, stream); }
+int session_resume_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, true, stream); }
 
 // out[r][:] = sum over the tables t with idx[t][r] >= 0 of table[t][idx[t][r]][:]
 __global__ __launch_bounds__(256) void gather_sum_rows_kernel(const GatherArgs p) {

@@ -205,6 +205,13 @@ struct GPTModel : ModelBase {
   // read.  Otherwise stop: a live request ends as if its cap were the codes it has (the next step reports it, read returns them); one
   // that has ended is left alone.  One id that is out of range, holds no request or is no group's first slot refuses the whole call.
   int session_end(void* ws, int n, const int* slot_ids, bool evict, hipStream_t st);
+  // Preempt and resume (idxtts.h): park gathers a live slot's state into the parked row dst and frees the slot; resume scatters a parked
+  // row into a free slot and marks it busy.  Greedy and sampled sessions; every refusal happens before anything changes.
+  ParkArgs park_args(const Session& s, const SessionBuffers& sb, int slot) const;      // everything but hdr and blob
+  int session_park_header(void* ws, int slot, idxtts_park_header* hdr, hipStream_t st);   // the checks of park + the slot's header now
+  size_t session_park_bytes(void* ws, int slot, hipStream_t st);
+  int session_park(void* ws, int slot, void* dst, size_t dst_bytes, size_t* written, hipStream_t st);
+  int session_resume(void* ws, int slot, const void* src, size_t src_bytes, hipStream_t st);
   int session_release(void* ws);
   int embed(float* out, int rows, const int* text_ids, const int* text_pos_idx, const int* mel_ids, const int* mel_pos_idx,
             const float* extra, const int* extra_idx, hipStream_t st);

@@ -900,6 +900,107 @@ int GPTModel::session_end(void* ws, int n, const int* slot_ids, bool evict, hipS
   return 0;
 }
 
+// ---- preempt and resume ----
+ParkArgs GPTModel::park_args(const Session& s, const SessionBuffers& sb, int slot) const {
+  const Buffers& w = sb.w;
+  ParkArgs a;
+  a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
+  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
+  a.slot = slot; a.Smax = w.Smax; a.slots = w.slots; a.samp = sb.samp; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new;
+  a.cur_tok = w.cur_tok; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots;
+  return a;
+}
+
+int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams == 0, "a beam session's groups cannot be parked (the scorer state of a group is not saved)");
+  IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+  IDX_CHECK(s.busy[slot], "slot holds no request");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  SlotState hs;
+  IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(hs.live, "slot has ended: read it, a request that is over cannot be parked");
+  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.max_new && hs.pos >= 1 && hs.pos < sb.w.Smax, "slot state corrupt");
+  idxtts_park_header h{};
+  h.magic = IDXTTS_PARK_MAGIC; h.version = IDXTTS_PARK_VERSION;
+  h.layers = cfg.layers; h.heads = cfg.heads; h.model_dim = cfg.model_dim; h.number_mel_codes = cfg.number_mel_codes;
+  h.slots = s.slots; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode; h.sampled = s.sampled ? IDXTTS_SESSION_SAMPLED : 0;
+  h.pos = hs.pos; h.mel_pos = hs.mel_pos; h.step = hs.step; h.max_step = hs.max_step;
+  h.mode = 0; h.temperature = 1.0f; h.top_k = 0; h.top_p = 1.0f;
+  if (s.sampled) {
+    const SlotSampling& e = s.samp[slot];
+    h.mode = e.mode; h.temperature = e.temperature; h.top_k = e.top_k; h.top_p = e.top_p; h.seed = e.seed;
+    h.exp_noise = (unsigned long long)(uintptr_t)e.exp_noise;
+  }
+  h.bytes = park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step).bytes;
+  *hdr = h;
+  return 0;
+}
+
+size_t GPTModel::session_park_bytes(void* ws, int slot, hipStream_t st) {
+  idxtts_park_header h;
+  return session_park_header(ws, slot, &h, st) ? 0 : (size_t)h.bytes;
+}
+
+int GPTModel::session_park(void* ws, int slot, void* dst, size_t dst_bytes, size_t* written, hipStream_t st) {
+  IDX_CHECK(dst, "null pointer");
+  IDX_CHECK((uintptr_t)dst % 16 == 0, "the parked row must be 16-byte aligned");
+  idxtts_park_header h;
+  if (session_park_header(ws, slot, &h, st)) return 1;
+  IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked row (idxtts_gpt_session_park_bytes)");
+  Session& s = *find_session(ws);
+  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled), slot);
+  a.hdr = h; a.blob = static_cast<char*>(dst);
+  if (session_park_slot(a, st)) return 1;
+  s.busy[slot] = 0;
+  if (written) *written = (size_t)h.bytes;
+  return 0;
+}
+
+int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_bytes, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams == 0, "a beam session's groups cannot be parked or resumed (the scorer state of a group is not saved)");
+  IDX_CHECK(src, "null pointer");
+  IDX_CHECK((uintptr_t)src % 16 == 0, "the parked row must be 16-byte aligned");
+  IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+  IDX_CHECK(!s.busy[slot], "slot is not free");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(src_bytes >= sizeof(idxtts_park_header), "parked row shorter than its header");
+  idxtts_park_header h;
+  IDX_HIP(hipMemcpyAsync(&h, src, sizeof(h), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(h.magic == IDXTTS_PARK_MAGIC, "not a parked row (magic)");
+  IDX_CHECK(h.version == IDXTTS_PARK_VERSION, "parked row of another format version");
+  IDX_CHECK(h.layers == cfg.layers && h.heads == cfg.heads && h.model_dim == cfg.model_dim && h.number_mel_codes == cfg.number_mel_codes,
+            "parked row of another model (dimensions)");
+  IDX_CHECK(h.slots == s.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
+  IDX_CHECK(h.kv_format == s.kv_fmt, "parked row of another KV format");
+  IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked row of another GEMM mode");
+  IDX_CHECK(h.mode == 0 || s.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
+  IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= 1, "parked row's step scalars are corrupt");
+  IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
+  if (h.mode != 0) {
+    idxtts_sampling r{h.mode, h.temperature, h.top_k, h.top_p, reinterpret_cast<const float*>((uintptr_t)h.exp_noise), h.seed};
+    if (check_sampling(r)) return 1;
+  }
+  IDX_CHECK(h.bytes == park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step).bytes, "parked row's size field is corrupt");
+  IDX_CHECK(src_bytes >= h.bytes, "parked row is truncated");
+  ParkArgs a = park_args(s, sb, slot);
+  a.hdr = h; a.blob = const_cast<char*>(static_cast<const char*>(src));
+  if (session_resume_slot(a, st)) return 1;
+  if (s.sampled) s.samp[slot] = SlotSampling{h.mode, h.temperature, h.top_k, h.top_p, h.seed, reinterpret_cast<const float*>((uintptr_t)h.exp_noise)};
+  s.busy[slot] = 1;
+  return 0;
+}
+
 int GPTModel::latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws,
                      size_t ws_bytes, hipStream_t st) {
   IDX_CHECK(emb && latent_out, "null pointer");

@@ -27,6 +27,7 @@ SYMBOLS = [
     "idxtts_gpt_session_read", "idxtts_gpt_session_release", "idxtts_gpt_session_workspace_bytes_ex", "idxtts_gpt_session_init_ex",
     "idxtts_gpt_session_admit_sampled", "idxtts_gpt_session_workspace_bytes_beam", "idxtts_gpt_session_init_beam",
     "idxtts_gpt_session_admit_beam", "idxtts_gpt_session_evict", "idxtts_gpt_session_stop",
+    "idxtts_gpt_session_park_bytes", "idxtts_gpt_session_park", "idxtts_gpt_session_resume",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
@@ -58,6 +59,14 @@ class GPTConfigC(ctypes.Structure):
 class SamplingC(ctypes.Structure):          # idxtts_sampling (include/idxtts.h)
     _fields_ = [("mode", c_int), ("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("exp_noise", c_void_p),
                 ("seed", ctypes.c_ulonglong)]
+
+
+class ParkHeaderC(ctypes.Structure):         # idxtts_park_header (include/idxtts.h): the first 128 bytes of a parked row
+    _fields_ = ([("magic", ctypes.c_uint), ("version", ctypes.c_uint)]
+                + [(n, c_int) for n in ("layers", "heads", "model_dim", "number_mel_codes", "slots", "kv_format", "gemm_mode", "sampled",
+                                        "pos", "mel_pos", "step", "max_step", "mode")]
+                + [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("seed", ctypes.c_ulonglong),
+                   ("exp_noise", ctypes.c_ulonglong), ("bytes", ctypes.c_ulonglong), ("reserved", c_int * 8)])
 
 
 class CondConfigC(ctypes.Structure):         # idxtts_cond_config (include/idxtts.h)
@@ -192,6 +201,10 @@ def load() -> ctypes.CDLL:
                                                   c_void_p]
     lib.idxtts_gpt_session_evict.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_session_stop.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_park_bytes.restype = c_size_t
+    lib.idxtts_gpt_session_park_bytes.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_park.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t), c_void_p, c_void_p]
+    lib.idxtts_gpt_session_resume.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.idxtts_gpt_latent.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_s2mel_create.argtypes = [POINTER(S2MelConfigC), POINTER(c_void_p)]
     lib.idxtts_s2mel_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]

@@ -481,6 +481,58 @@ def _seed64(seed) -> int:
     return s
 
 
+class ParkedRow:
+    """A decode row that stepped aside (DecodeSession.park): the parked row's bytes (include/idxtts.h "Preempt and resume") on the
+    device or, after to("cpu"), in pinned host memory; `n_codes` codes produced so far, the request's `cap`, and the request's
+    exp_noise tensor if it has one (kept alive here while the row is parked).  DecodeSession.resume takes it once."""
+
+    def __init__(self, blob: torch.Tensor, n_codes: int, cap: int, noise, stream):
+        self._blob, self.n_codes, self.cap, self._noise, self._stream = blob, int(n_codes), int(cap), noise, stream
+
+    @property
+    def device(self) -> torch.device:
+        self._check()
+        return self._blob.device
+
+    @property
+    def nbytes(self) -> int:
+        self._check()
+        return int(self._blob.numel())
+
+    @property
+    def resumed(self) -> bool:
+        return self._blob is None
+
+    def _check(self) -> None:
+        if self._blob is None:
+            raise RuntimeError("this ParkedRow has been resumed: a parked row is resumed once")
+
+    def to(self, device) -> "ParkedRow":
+        """Moves the bytes IN PLACE (through pinned host memory) and returns self: to("cpu") gives the device memory back, to(a GPU)
+        stages it again.  The copy runs on the stream the row was written on and is complete on return."""
+        self._check()
+        device = torch.device(device)
+        if device.type == self._blob.device.type and (device.index is None or device == self._blob.device):
+            return self
+        if device.type == "cpu":
+            host = torch.empty(self._blob.numel(), dtype=torch.uint8, pin_memory=True)
+            with torch.cuda.stream(self._stream):
+                host.copy_(self._blob, non_blocking=True)
+            self._stream.synchronize()
+            self._blob = host
+        elif device.type == "cuda":
+            host = self._blob if self._blob.is_pinned() else self._blob.pin_memory()
+            stream = torch.cuda.current_stream(device)
+            with torch.cuda.stream(stream):
+                dev = torch.empty(host.numel(), dtype=torch.uint8, device=device)
+                dev.copy_(host, non_blocking=True)
+            stream.synchronize()      # the pinned buffer is let go below
+            self._blob, self._stream = dev, stream
+        else:
+            raise ValueError(f"a ParkedRow lives on the GPU or in host memory, not on {device}")
+        return self
+
+
 class _Session:
     """What DecodeSession and BeamDecodeSession share: the stream, the workspace and its native session, prompt staging, the step loop
     and the release.  Subclasses set the slot bookkeeping (_busy, _done, _noise) and _unit (slots per request)."""
@@ -725,6 +777,65 @@ class DecodeSession(_Session):
         """The codes of the finished request in `slot` (LongTensor on the device); the slot is free again."""
         return super().take(slot)
 
+    def park(self, slot: int) -> ParkedRow:
+        """Takes the decoding request in `slot` out of the session with everything it has computed -- its step state, sampler, codes
+        and the keys and values of its pos cached positions -- and frees the slot: admissible at once, never reported by step().  One
+        gather launch on the session's stream; bytes moved are proportional to the row's length.  resume() puts the row back, into any
+        free slot of this session or of another one of the same shape, and it goes on to produce, bit for bit, the codes of its
+        uninterrupted run.  A slot that is free, has finished (take() it) or is out of range raises, nothing changes."""
+        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots or not self._busy[int(slot)]:
+            raise ValueError(f"{slot!r} holds no request (slot ids 0 .. {self.slots - 1})")
+        slot = int(slot)
+        with torch.cuda.stream(self.stream):
+            need = int(self._lib.idxtts_gpt_session_park_bytes(self.gpt._h, slot, _lib.ptr(self._ws), self._sp()))
+            if need == 0:
+                _lib.check(1)
+            blob = torch.empty(need, dtype=torch.uint8, device=self.gpt.device)
+            written = ctypes.c_size_t(0)
+            _lib.check(self._lib.idxtts_gpt_session_park(self.gpt._h, slot, _lib.ptr(blob), need, ctypes.byref(written), _lib.ptr(self._ws),
+                                                         self._sp()))
+            hdr = _lib.ParkHeaderC.from_buffer_copy(blob[: ctypes.sizeof(_lib.ParkHeaderC)].cpu().numpy().tobytes())
+        assert written.value == need == hdr.bytes
+        self._busy[slot] = False
+        self._done.discard(slot)
+        nz = self._noise.pop(slot, None)      # the draws move with the row: alive while it is parked
+        if nz is not None:
+            nz.record_stream(self.stream)
+        return ParkedRow(blob, hdr.step, hdr.max_step, nz, self.stream)
+
+    def resume(self, parked: ParkedRow, slot=None) -> int:
+        """Puts a parked row into `slot` (default: the first free slot) and returns the slot; the row decodes on from the next step().
+        `parked` may live on the device or in host memory (it is staged here) and may come from another session of the same model,
+        slots, KV format and GEMM mode whose max_new and cache length hold the rest of the request.  A refusal raises and changes
+        nothing; a ParkedRow is resumed once."""
+        if not isinstance(parked, ParkedRow):
+            raise TypeError("resume() takes a ParkedRow")
+        parked._check()
+        if slot is None:
+            free = self.free_slots
+            if not free:
+                raise RuntimeError("no free slot")
+            slot = free[0]
+        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots:
+            raise ValueError(f"slot {slot!r} out of range (0 .. {self.slots - 1})")
+        slot = int(slot)
+        if self._busy[slot]:
+            raise ValueError(f"slot {slot} is not free")
+        if parked._blob.device != self.gpt.device:
+            with torch.cuda.stream(self.stream):
+                parked.to(self.gpt.device)
+        blob = parked._blob
+        self.stream.wait_stream(parked._stream)      # the row may have been written on another session's stream
+        with torch.cuda.stream(self.stream):
+            _lib.check(self._lib.idxtts_gpt_session_resume(self.gpt._h, slot, _lib.ptr(blob), blob.numel(), _lib.ptr(self._ws), self._sp()))
+        blob.record_stream(self.stream)
+        self._busy[slot] = True
+        if parked._noise is not None:
+            parked._noise.record_stream(self.stream)
+            self._noise[slot] = parked._noise
+        parked._blob = parked._noise = None
+        return slot
+
 
 class BeamDecodeSession(_Session):
     """Beam search / beam-sample with continuous batching: the session's `slots` decode rows form slots / num_beams groups of num_beams
@@ -826,3 +937,9 @@ class BeamDecodeSession(_Session):
     def take(self, group: int) -> torch.Tensor:
         """The codes of the finished request in `group` (LongTensor on the device); the group is free again."""
         return super().take(group)
+
+    def park(self, group: int):
+        raise NotImplementedError("a beam session's groups cannot be parked: a group's scorer state (hypotheses, beam scores) is not saved")
+
+    def resume(self, parked, group=None):
+        raise NotImplementedError("a beam session's groups cannot be parked or resumed: a group's scorer state is not saved")

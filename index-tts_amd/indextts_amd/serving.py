@@ -431,7 +431,7 @@ class BatchPipeline:
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq", "deadline", "notified")
+                 "seq", "deadline", "notified", "priority", "stamp")
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
@@ -547,12 +547,28 @@ class ContinuousPipeline:
     evicted the same way.  submit(deadline_s=...) cancels a request that many seconds after submit unless its acoustic job has
     started.  Nobody else's codes move (the session contract holds across evictions).
 
-    session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close) replaces the HIP session (tests)."""
+    Priorities: submit(priority=n), larger is more urgent.  The waiting utterances are admitted by (higher priority first, then
+    submission order, then utterance index): with every priority equal, in arrival order.  preempt=True lets an urgent request take a
+    slot that is in use.  In each poll, after evicting gone requests and before admitting, a lane whose slots are all taken looks at
+    the waiting utterances in order: for each one that is strictly more urgent than the least urgent row still decoding here, it parks
+    that row (session.park: the row's KV and state gathered into a ParkedRow, bytes proportional to its length, its slot free at once)
+    and admits the utterance in its place in the same poll -- the row of lowest priority first, among equals the one admitted last,
+    and never more rows than there are more-urgent utterances waiting.  A parked row waits ahead of the never-admitted utterances of
+    its own priority; when its turn comes, whichever lane has a free slot resumes it (session.resume: no prefill), and it goes on to
+    the codes of its uninterrupted run, bit for bit.  Equal priority never preempts, so nothing ping-pongs.  park_to="host" moves
+    every parked row to pinned host memory until it resumes.  A lane does not look at the other lanes' free slots before it parks.  A
+    parked request that is cancelled, past its deadline or failed is dropped when next touched; a resume that fails fails that
+    request only; close() drains parked rows like any other waiting work.  Strict priorities can starve: a steady stream of urgent
+    requests keeps less urgent ones waiting (or parked) for as long as it lasts -- there is no aging.  Beam pipelines do not preempt
+    (a group's scorer state is not saved).  `trace` also records ("park", t, request, utterance) and ("resume", t, request, utterance).
+
+    session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close; evict to cancel; park / resume to
+    preempt) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
                  session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
-                 acoustic_max_rows: int = 16):
+                 acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device"):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
@@ -572,6 +588,13 @@ class ContinuousPipeline:
         self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
         self.max_new = int(max_new or g.max_mel_tokens)
         self.allow_sampling = bool(allow_sampling)
+        self.preempt = bool(preempt)
+        if park_to not in ("device", "host"):
+            raise ValueError('park_to must be "device" or "host"')
+        self.park_to = park_to
+        if self.preempt and self.num_beams > 1:
+            raise ValueError("preempt=True needs num_beams == 1: a beam session's groups cannot be parked")
+        self._admitted = 0                      # admission stamps (which row of a priority was admitted last)
         if self.num_beams > 1:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
                                                                                    repetition_penalty=self.repetition_penalty))
@@ -580,7 +603,7 @@ class ContinuousPipeline:
                                                                                      sampled=self.allow_sampling))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
-        self._waiting = collections.deque()     # (job, utterance index) not admitted yet
+        self._waiting = collections.deque()     # (job, utterance index, ParkedRow or None) waiting for a slot, most urgent first
         self._closing = False
         self._streams = []
         self._tls = threading.local()
@@ -603,24 +626,28 @@ class ContinuousPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               deadline_s: Optional[float] = None) -> concurrent.futures.Future:
+               deadline_s: Optional[float] = None, priority: int = 0) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
-        has started by then (checked wherever cancellation is: each poll, each acoustic hand-over); None: no deadline."""
+        has started by then (checked wherever cancellation is: each poll, each acoustic hand-over); None: no deadline.
+        priority: larger is more urgent (see the class); it orders the waiting utterances and, with preempt=True, lets this request
+        park rows of lower priority."""
         if deadline_s is not None:
             deadline_s = float(deadline_s)
+        priority = int(priority)
         if self.num_beams > 1:
             return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed, deadline_s)
+                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed, deadline_s, priority)
         if sampling and not self.allow_sampling:
             raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
         if sampling and int(sampling.get("num_beams") or 1) > 1:
             raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s)
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority)
 
-    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None):
+    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None,
+                priority=0):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -631,6 +658,7 @@ class ContinuousPipeline:
         j.codes, j.left, j.failed = [None] * B, B, False
         j.done, j.notified = concurrent.futures.Future(), False
         j.sampling, j.seq, j.noise_seeds = None, -1, None
+        j.priority, j.stamp = priority, [0] * B
         j.deadline = None if deadline_s is None else self._clock() + deadline_s
         try:                                    # a bad parameter fails this request's Future only
             j.noise, j.noise_seeds = _request_noise(noise, noise_seed, B)
@@ -649,9 +677,23 @@ class ContinuousPipeline:
                 raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
             j.seq = self._submitted
             self._submitted += 1
-            self._waiting.extend((j, i) for i in range(B))
+            for i in range(B):
+                self._enqueue(j, i, None)
             self._cv.notify_all()
         return j.done
+
+    @staticmethod
+    def _order(j: _Job, i: int, parked) -> tuple:
+        """Where a waiting entry stands: higher priority first, parked rows ahead of never-admitted utterances of their priority, then
+        submission order, then utterance index."""
+        return (-j.priority, parked is None, j.seq, i)
+
+    def _enqueue(self, j: _Job, i: int, parked) -> None:
+        """Puts an entry into the waiting queue at its place (self._cv held); with every priority equal that is the end."""
+        key, at = self._order(j, i, parked), len(self._waiting)
+        while at > 0 and self._order(*self._waiting[at - 1]) > key:
+            at -= 1
+        self._waiting.insert(at, (j, i, parked))
 
     @staticmethod
     def _fail(j: _Job, e: BaseException) -> None:
@@ -697,15 +739,30 @@ class ContinuousPipeline:
 
     def _admit(self, sess, in_slot) -> None:
         with self._cv:
-            take = []
+            take, victims = [], []
             free = len(self._free(sess))
-            while self._waiting and len(take) < free:
-                j, i = self._waiting.popleft()
-                if not self._gone(j):           # a cancelled or failed request's waiting utterances are dropped
-                    take.append((j, i))
+            # the rows a more urgent utterance may displace, first choice first: lowest priority, among equals admitted last
+            rows = sorted(in_slot, key=lambda s: (in_slot[s][0].priority, -in_slot[s][0].stamp[in_slot[s][1]])) if self.preempt else []
+            while self._waiting:
+                j = self._waiting[0][0]
+                room = len(take) < free
+                if not room and not (len(victims) < len(rows) and in_slot[rows[len(victims)]][0].priority < j.priority):
+                    break
+                j, i, parked = self._waiting.popleft()
+                if self._gone(j):               # a cancelled or failed request's waiting utterances (and parked rows) are dropped
+                    continue
+                if not room:
+                    victims.append(rows[len(victims)])
+                take.append((j, i, parked))
+        for s in victims:                       # their slots are free for `take` in this poll
+            self._park(sess, in_slot, s)
+        for j, i, parked in take:
+            if parked is not None:
+                self._resume(sess, in_slot, j, i, parked)
         by_job = collections.OrderedDict()
-        for j, i in take:
-            by_job.setdefault(id(j), (j, []))[1].append(i)
+        for j, i, parked in take:
+            if parked is None:
+                by_job.setdefault(id(j), (j, []))[1].append(i)
         rows, caps, owners, samplers = [], [], [], []
         for j, idx in by_job.values():
             try:
@@ -730,8 +787,39 @@ class ContinuousPipeline:
                 for j, _ in owners:
                     self._fail(j, e)
                 return
-            for s, o in zip(got, owners):
-                in_slot[s] = o
+            with self._cv:
+                for s, (j, i) in zip(got, owners):
+                    in_slot[s] = (j, i)
+                    self._admitted += 1
+                    j.stamp[i] = self._admitted
+
+    def _park(self, sess, in_slot, s) -> None:
+        """Parks the row in slot s and queues it for whichever lane next has room; a park that fails fails its request (and frees the
+        slot by eviction)."""
+        j, i = in_slot.pop(s)
+        try:
+            parked = sess.park(s)
+            if self.park_to == "host":
+                parked = parked.to("cpu")
+        except BaseException as e:           # noqa: BLE001
+            self._fail(j, e)
+            sess.evict([s])
+            return
+        if self.trace is not None:
+            self.trace.append(("park", time.perf_counter(), j.seq, i))
+        with self._cv:
+            self._enqueue(j, i, parked)
+            self._cv.notify_all()
+
+    def _resume(self, sess, in_slot, j: _Job, i: int, parked) -> None:
+        try:
+            s = sess.resume(parked)
+        except BaseException as e:           # noqa: BLE001 -- this request's own failure: nothing was changed, the lane goes on
+            self._fail(j, e)
+            return
+        in_slot[s] = (j, i)
+        if self.trace is not None:
+            self.trace.append(("resume", time.perf_counter(), j.seq, i))
 
     def _collect(self, sess, in_slot, finished) -> None:
         done = []
@@ -765,7 +853,7 @@ class ContinuousPipeline:
                         if self._closing and not self._waiting and not in_slot:
                             break
                     self._evict_gone(sess, in_slot)      # before admitting: the freed places are admissible in this poll
-                    if self._free(sess):
+                    if self._free(sess) or (self.preempt and in_slot):
                         self._admit(sess, in_slot)
                     if in_slot:
                         self._collect(sess, in_slot, sess.step(self.poll_steps))
@@ -776,7 +864,7 @@ class ContinuousPipeline:
                 if self._alive == 0:
                     pending += list(self._waiting)
                     self._waiting.clear()
-            for j, _ in pending:
+            for j, *_ in pending:
                 self._fail(j, e)
             return
         finally:
