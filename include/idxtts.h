@@ -274,6 +274,45 @@ int idxtts_gpt_quantize_weights(idxtts_ctx* ctx, int format);
 #define IDXTTS_KV_FP8 2
 int idxtts_gpt_set_kv_format(idxtts_ctx* ctx, int format);
 int idxtts_gpt_get_kv_format(const idxtts_ctx* ctx);
+/* Batch-invariant mode: opt-in, per context, default 0 (off: every path is bit for bit what it is without the call).  With the mode on,
+ * everything that feeds the choice of a code is a function of the request alone.
+ * Contract: a request's codes -- and with logits_out its logits -- equal BIT FOR BIT those of the B = 1 call (idxtts_gpt_generate,
+ * _generate_forced, _generate_sampled or _generate_beam) on its own unpadded prompt, for the same weight format, KV format and GEMM
+ * mode, wherever the request runs: any row of a one-shot call of any B <= 64 with any pad_left; any slot or group of a greedy, sampled
+ * or beam session of any `slots`; any lane; after any _park and _resume, into a session of any slot count.  It holds whatever
+ * idxtts_set_decode_geometry and idxtts_set_decode_plane_rows say: the mode reads neither switch.
+ * Seeded draws (exp_noise NULL) carry no term in B or in the group count: row b of a one-shot call at step t draws id v (beam: flat
+ * index v of num_beams * V) from exp1_draw(seed + b * 0xD6E8FEB86659FD93, t * V + v) (beam: t * num_beams * V + v).  Row 0's stream is
+ * the B = 1 stream, and that is the stream a session request (slot, group) draws from.  exp_noise supplied by the caller is read as
+ * without the mode.
+ * What the mode launches (csrc/gpt.hip; idxtts_batch_invariant_plan_query answers for one shape):
+ *   decode GEMVs    the fp32-MFMA GEMV at every row count, in its 16-row-tile forms only: K slices, chunks per slice and K pieces
+ *                   follow (N, K) alone, and a row's products are added in one order at every number of row tiles.  The 4-row form,
+ *                   the narrow geometry and the plane GEMV (other summation orders) are never taken.
+ *   decode attention  a row with n keys is cut into ceil(n / 512) pieces (at most 16; ceil(n / pieces) keys each, rounded up to 16) and
+ *                   the pieces are merged in piece order.  The batch size only decides how many workgroups share a row's pieces out
+ *                   (one workgroup walks all of them from 7 rows x 20 heads on), never what is added to what.
+ *   prefill         the exact fp32 GEMMs and fp32 attention for every KV format (a bf16 cache's prefill too, which otherwise follows
+ *                   the GEMM mode from 256 rows), and the attention's 32-key tiles counted from each row's first real key, so a
+ *                   left-padded row equals the unpadded one.
+ * Rules: those of idxtts_gpt_set_kv_format -- callable between generations (refused while one is in flight); cached decode graphs
+ * carry the mode in their key; a session keeps the mode it had at _init (every later call on it is refused while the context's mode
+ * differs).  Cost: profiles/README.md "Batch-invariant decode".  The latent pass and the acoustic stage are outside the contract. */
+int idxtts_gpt_set_batch_invariant(idxtts_ctx* ctx, int on);
+int idxtts_gpt_get_batch_invariant(const idxtts_ctx* ctx);
+/* What the batch-invariant mode would launch (host only, no GPU work; the launchers' own plan functions):
+ *   one decode GEMV of an [K][N] weight stream in `format` on `rows` rows (with_slab as idxtts_gemv_fx_plan_query): family (0 = the
+ *   fp32-MFMA GEMV), r4, narrow, kw, cps, ksb -- the summation order, a function of (N, K) alone -- and mt, ntw, single, which name
+ *   the instantiation for that many rows (how many row / column tiles a wave carries; no part in the order);
+ *   the decode attention of a row with n_keys keys in a B-row step of `heads` heads on a cache of smax positions: attn_pieces and
+ *   attn_piece_keys -- functions of n_keys alone -- and attn_workgroups, how many workgroups share the pieces out at that B. */
+typedef struct idxtts_batch_invariant_plan {
+  int family, r4, narrow, kw, cps, ksb;
+  int mt, ntw, single;
+  int attn_pieces, attn_piece_keys, attn_workgroups;
+} idxtts_batch_invariant_plan;
+int idxtts_batch_invariant_plan_query(int N, int K, int rows, int format, int with_slab, int B, int heads, int smax, int n_keys,
+                                      idxtts_batch_invariant_plan* out);
 /* Greedy generations keep their instantiated decode-step hipGraph per (workspace address and size, B, prompt length, max_new_tokens,
  * penalty): the same shapes on the same workspace replay it without re-capturing (at most 8 are kept, least recently used first
  * out).  Returns how many are held (diagnostics / tests), -1 for a non-GPT context. */
@@ -354,7 +393,10 @@ int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const 
  * padding (for a bf16 KV cache in split-bf16 GEMM mode: a reference batch of slots * (P + 1) >= 256 prefill rows), whatever else is in
  * flight, whenever it was admitted and whichever slot it has.  Results can depend on `slots` (decode attention key split, decode GEMV).
  * The caller owns the workspace (idxtts_gpt_session_workspace_bytes); the session lives in it until _release or the next _init on
- * it.  The KV format and the GEMM mode must stay as they were at _init. */
+ * it.  The KV format and the GEMM mode must stay as they were at _init.
+ * In the batch-invariant mode (idxtts_gpt_set_batch_invariant; the session keeps the mode of its _init) the rule is simpler: a
+ * request's codes equal those of the B = 1 call on its own prompt, for every `slots`, and so do the sampled and beam rules below
+ * (seeded draws: the B = 1 stream). */
 size_t idxtts_gpt_session_workspace_bytes(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens);
 /* Prepares the workspace: every slot free.  max_prompt: longest prompt (P, the `tts_embeddings` rows) a request may have;
  * max_new_tokens: largest per-request cap. */
@@ -458,7 +500,7 @@ typedef struct idxtts_park_header {      /* 128 bytes */
   unsigned long long seed;
   unsigned long long exp_noise;                        /* device pointer, or 0 */
   unsigned long long bytes;                            /* the whole parked row, header included */
-  int reserved[8];                                /* zero */
+  int reserved[8];                                /* [0]: 1 = parked in the batch-invariant mode; everything else zero */
 } idxtts_park_header;
 /* Exact size of slot's parked row now (one small device-to-host read of its state); 0 with idxtts_last_error set when the slot cannot
  * be parked (see _park). */
@@ -471,7 +513,9 @@ int idxtts_gpt_session_park(idxtts_ctx* ctx, int slot, void* dst, size_t dst_byt
  * another model's dimensions, a session with other slots, KV format or GEMM mode (they select the key split and the GEMV: the
  * remaining codes would belong to another reference), a sampled request offered to a greedy session, a cap above the session's
  * max_new_tokens, pos + (max_step - step) + 1 beyond the session's cache length, a slot that is busy or out of range, src_bytes
- * shorter than the header says.  On success the slot decodes on from the next _step; src may be freed once the work queued on `stream`
+ * shorter than the header says, a row whose batch-invariant flag (reserved[0]) differs from the session's.  When both are in the
+ * batch-invariant mode the slot counts need not match: nothing on the row's path depends on them, and the row's codes stay those of
+ * its uninterrupted B = 1 run.  On success the slot decodes on from the next _step; src may be freed once the work queued on `stream`
  * has run (stream order). */
 int idxtts_gpt_session_resume(idxtts_ctx* ctx, int slot, const void* src, size_t src_bytes, void* workspace, void* stream);
 /* Forgets the session on this workspace (and its captured step); the caller may then free or reuse the workspace. */

@@ -11,6 +11,8 @@ struct AttnArgs {
   int B = 0, H = 0, Sq = 0, Sk = 0, head_dim = 64;
   int causal = 0;                 // key <= query (Sq == Sk, aligned at 0)
   const int* kstart = nullptr;    // [B] first valid key (left padding), or null
+  int tiles_from_kstart = 0;      // fp32 kernel: the 32-key tiles start AT kstart[b], not at the 32-aligned key below it -- a row's own
+                                  // keys then fall into the same tiles, and are summed in the same order, whatever its left padding
   const int* kend = nullptr;      // [B] one past the last valid key (right padding / x_lens), or null
   float scale = 0.125f;
   void* o_planes = nullptr;       // split_bf16 only: write the output as split-bf16 planes over rows b*Sq + q, columns head*64 + d (o may be null)

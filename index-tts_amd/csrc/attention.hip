@@ -75,7 +75,7 @@ __device__ __forceinline__ KeyRange visible_keys(const AttnArgs& p, int b, int q
   k.kend = p.kend ? min(p.kend[b], p.Sk) : p.Sk;
   int k_hi = k.kend;
   if (p.causal) k_hi = min(k_hi, qblk * 128 + 128);
-  k.k_lo = k.kstart & ~31;
+  k.k_lo = p.tiles_from_kstart ? k.kstart : k.kstart & ~31;
   k.ntiles = k_hi > k.k_lo ? (k_hi - k.k_lo + 31) >> 5 : 0;
   return k;
 }
@@ -696,6 +696,7 @@ int flash_attn_forward(const AttnArgs& a, hipStream_t stream) {
     IDX_HIP(lds_limit.set(REL_LDS, flash_attn_bf16x3_kernel<3>, flash_attn_f32_kernel));
   }
   IDX_CHECK(a.split_bf16 >= 0 && a.split_bf16 <= 2, "split_bf16: 0, 1 or 2");
+  IDX_CHECK(!a.tiles_from_kstart || (a.split_bf16 == 0 && !a.rel_key), "key tiles from kstart: the fp32 kernel only");
   if (a.split_bf16 == 2) hipLaunchKernelGGL(flash_attn_bf16x3_kernel<1>, grid, dim3(256), dyn, stream, a);
   else if (a.split_bf16) hipLaunchKernelGGL(flash_attn_bf16x3_kernel<3>, grid, dim3(256), dyn, stream, a);
   else hipLaunchKernelGGL(flash_attn_f32_kernel, grid, dim3(256), dyn, stream, a);

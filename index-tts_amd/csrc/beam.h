@@ -42,6 +42,8 @@ struct BeamState {
   const DecodeState* st = nullptr;
   const float* exp_noise = nullptr;   // [steps][B][nb * V] Exp(1) draws (do_sample), or null: exp1_draw(seed, ...)
   unsigned long long seed = 0;
+  int invariant = 0;                  // batch-invariant mode: seeded draws without a term in B (utterance b: seed + b * DRAW_ROW_STRIDE,
+                                      // index n * nb * V + i; a session group draws utterance 0's stream)
   void* kcache = nullptr; void* vcache = nullptr;     // [L][R][H][G][Smax] / [L][R][H][Smax][G] granules of 16 bytes (fp8 cache: 8)
   int kv_gran = 16;                                   // G: granules per key (16 = fp32 cache, 8 = bf16 or fp8 cache; decode.h)
   float* kscale = nullptr; float* vscale = nullptr;   // fp8 cache: [L][R][H][Smax] scales, which follow their rows; else null

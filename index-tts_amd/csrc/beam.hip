@@ -270,7 +270,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
     const SlotBeam& gb = p.group[b];
     do_sample = gb.do_sample; early_stopping = gb.early_stopping; exp_noise = gb.exp_noise; seed = gb.seed;
     length_penalty = gb.length_penalty;
-    nbase = exp_noise ? (size_t)n * N : (size_t)n * p.B * N;
+    nbase = (exp_noise || p.invariant) ? (size_t)n * N : (size_t)n * p.B * N;
   } else {
     n = p.st->step;                           // tokens each live beam holds before this step
     if (p.done[b]) {                          // BeamSearchScorer.process pads a finished utterance
@@ -278,6 +278,7 @@ __global__ __launch_bounds__(1024) void beam_select_kernel(const BeamState p) {
       return;
     }
     nbase = ((size_t)n * p.B + b) * N;
+    if (p.invariant && !exp_noise) { nbase = (size_t)n * N; seed += DRAW_ROW_STRIDE * (unsigned long long)b; }
   }
   const float* base = p.proc + (size_t)b * N;
   const int n_keep = 2 * nb;

@@ -349,6 +349,25 @@ int idxtts_gpt_get_kv_format(const idxtts_ctx* ctx) {
   return m ? m->kv_fmt : -1;
 }
 
+int idxtts_gpt_set_batch_invariant(idxtts_ctx* ctx, int on) {
+  API_BEGIN
+  IDX_CHECK(ctx, "null ctx");
+  IDX_CHECK(on == 0 || on == 1, "batch-invariant mode: 0 (off) or 1 (on)");
+  auto* m = dynamic_cast<GPTModel*>(ctx->model.get());
+  IDX_CHECK(m, "not a GPT context");
+  // a generation in flight has chosen its kernels (and captured its step) for the current mode
+  IDX_CHECK(m->batch_invariant == on || m->generating.load() == 0, "a generation is in flight on this context: switch the mode between generations");
+  m->batch_invariant = on;      // cached decode graphs carry the mode in their key; a session keeps the mode it was initialised in
+  return 0;
+  API_END
+}
+
+int idxtts_gpt_get_batch_invariant(const idxtts_ctx* ctx) {
+  if (!ctx) return -1;
+  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
+  return m ? m->batch_invariant : -1;
+}
+
 int idxtts_gpt_graph_cache_entries(idxtts_ctx* ctx) {
   if (!ctx || !ctx->finalized) return -1;
   auto* m = dynamic_cast<GPTModel*>(ctx->model.get());
@@ -897,6 +916,25 @@ int idxtts_gemv_fx_plan_query(int N, int K, int rows, int format, int with_slab,
   const FxPlan pl = gemv_fx_make_plan(N, K, rows, format, ksb, narrow != 0);
   out->mt = pl.MT; out->ntw = pl.ntw; out->single = pl.single; out->r4 = pl.r4; out->narrow = pl.narrow;
   out->kw = pl.kw; out->cps = pl.cps; out->ksb = ksb;
+  return 0;
+  API_END
+}
+
+int idxtts_batch_invariant_plan_query(int N, int K, int rows, int format, int with_slab, int B, int heads, int smax, int n_keys,
+                                      idxtts_batch_invariant_plan* out) {
+  API_BEGIN
+  IDX_CHECK(out && N > 0 && K > 0 && rows > 0 && rows <= 64, "N, K > 0, 1..64 rows");
+  IDX_CHECK(format == WFMT_F32 || format == WFMT_BF16 || format == WFMT_FP8, "weight format 0..2");
+  IDX_CHECK(B > 0 && B <= 64 && heads > 0 && n_keys > 0 && smax >= n_keys, "1..64 attention rows, 1 <= n_keys <= smax");
+  const int ksb = with_slab ? gemv_fx_ksb(N, K) : 1;
+  // the switches as they stand: the plan must not read them
+  const FxPlan pl = gemv_fx_make_plan(N, K, rows, format, ksb, get_decode_geometry() != 0, true);
+  out->family = 0; out->r4 = pl.r4; out->narrow = pl.narrow; out->kw = pl.kw; out->cps = pl.cps; out->ksb = ksb;
+  out->mt = pl.MT; out->ntw = pl.ntw; out->single = pl.single;
+  const int np = decode_attn_pieces(n_keys);
+  out->attn_pieces = np;
+  out->attn_piece_keys = np > 1 ? ((n_keys + np - 1) / np + 15) & ~15 : n_keys;
+  out->attn_workgroups = std::min(decode_attn_inv_wgs(B, heads, smax), np);
   return 0;
   API_END
 }

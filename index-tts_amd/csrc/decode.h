@@ -46,8 +46,25 @@ struct DecodeAttnArgs {
   // Decode session: per-row positions slot[b].pos instead of st->pos; a row whose slot is not live returns at once (zero output,
   // no KV traffic).  The key split keeps its rule: pieces start at the row's first key, nsplit = decode_attn_nsplit(B, H).
   const SlotState* slot = nullptr;
+  // Batch-invariant mode (idxtts_gpt_set_batch_invariant): the row's n = pos - kstart + 1 keys are cut into decode_attn_pieces(n)
+  // pieces whatever B is, and nsplit only says how many workgroups share a (row, head)'s pieces out (decode_attn_inv_wgs); part is
+  // [B][H][DECODE_ATTN_MAX_PIECES][66].  The merged result is a function of the row's own keys alone.
+  int invariant = 0;
 };
 int decode_attn_nsplit(int B, int H);
+// The invariant mode's rule: pieces of at most DECODE_ATTN_PIECE_KEYS keys (one key per thread of a 512-thread workgroup: each piece
+// is exactly one pass of the score phase), at most DECODE_ATTN_MAX_PIECES of them (longer pieces from 8192 keys on), cut as the key
+// split cuts: ceil(n / pieces) keys each, rounded up to 16
+#ifndef IDXTTS_DECODE_ATTN_PIECE_KEYS
+#define IDXTTS_DECODE_ATTN_PIECE_KEYS 512      // (a build-time constant so that another piece length can be measured: profiles/README.md)
+#endif
+constexpr int DECODE_ATTN_PIECE_KEYS = IDXTTS_DECODE_ATTN_PIECE_KEYS;
+constexpr int DECODE_ATTN_MAX_PIECES = 16;
+__host__ __device__ static inline int decode_attn_pieces(int n) {
+  const int np = (n + DECODE_ATTN_PIECE_KEYS - 1) / DECODE_ATTN_PIECE_KEYS;
+  return np < 1 ? 1 : np > DECODE_ATTN_MAX_PIECES ? DECODE_ATTN_MAX_PIECES : np;
+}
+int decode_attn_inv_wgs(int B, int H, int Smax);      // workgroups per (row, head): min(decode_attn_nsplit, pieces of a full cache)
 int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream);
 
 struct SampleArgs {
@@ -64,6 +81,9 @@ struct SampleArgs {
   // teacher forcing (idxtts_gpt_generate_forced): `codes` still records the row's own argmax, but the token fed back (cur_tok, the
   // repetition-penalty set, the finished flag) is forced[b][step]
   const long long* forced = nullptr; int forced_ld = 0;
+  // Batch-invariant mode: the counter-based draws (no exp_noise) are keyed without the batch size -- row b of a one-shot generation
+  // draws exp1_draw(seed + b * DRAW_ROW_STRIDE, step * V + v), so row 0 is the B = 1 stream, and a session slot draws that B = 1 stream
+  int invariant = 0;
   // Fused tail of a greedy step (embed.x_row or embed.x_frag != null): the workgroup that picked row b's token also writes the NEXT
   // step's input x[b] = mel_emb[token] + mel_pos[st->mel_pos + 1] (model_v2.py:173-177) -- as the fp32 residual row
   // and the per-16-column row statistics of the first folded LayerNorm -- and the last workgroup to arrive advances the
@@ -106,6 +126,7 @@ __host__ __device__ static inline float exp1_draw(const float* noise, unsigned l
   const float u = fminf(((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   return -logf(u);
 }
+constexpr unsigned long long DRAW_ROW_STRIDE = 0xD6E8FEB86659FD93ull;      // odd: rows of one seed are distinct seeds
 struct SampleWarpArgs {
   SampleArgs base;                   // logits source, bookkeeping buffers, penalty (parts must be 1)
   int mode = SAMPLE_HF;

@@ -77,6 +77,44 @@ __device__ __forceinline__ void decode_attn_dead(const DecodeAttnArgs& p, const 
   else p.out[frag_index(b, h * 64 + tid, p.d >> 4)] = 0.f;
 }
 
+// Batch-invariant mode (DecodeAttnArgs::invariant): piece z of the row's NP = decode_attn_pieces(n) pieces leaves (o, max, sum) at a
+// fixed stride of 16 pieces per (row, head), whichever workgroup computed it
+__device__ __forceinline__ void decode_attn_piece_store(const DecodeAttnArgs& p, const int b, const int h, const int z, const int tid,
+                                                        const float o, const float mx, const float l) {
+  float* mine = p.part + ((size_t)(b * p.H + h) * DECODE_ATTN_MAX_PIECES + z) * 66;
+  if (tid < 64) __hip_atomic_store(&mine[tid], o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 64) __hip_atomic_store(&mine[64], mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 65) __hip_atomic_store(&mine[65], l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ... and the last of the row's `wgs` workgroups to arrive merges the NP pieces in piece order: the same sums whether one workgroup
+// walked all the pieces or each piece had its own
+__device__ __forceinline__ void decode_attn_piece_merge(const DecodeAttnArgs& p, const int b, const int h, const int NP, const int wgs,
+                                                        const int tid) {
+  if (!wg_arrive_last(&p.cnt[b * p.H + h], (unsigned)wgs) || tid >= 64) return;
+  const float* all = p.part + (size_t)(b * p.H + h) * DECODE_ATTN_MAX_PIECES * 66;
+  float mi[DECODE_ATTN_MAX_PIECES], li[DECODE_ATTN_MAX_PIECES], oi[DECODE_ATTN_MAX_PIECES];
+#pragma unroll
+  for (int i = 0; i < DECODE_ATTN_MAX_PIECES; ++i) {
+    const bool on = i < NP;
+    mi[i] = on ? __hip_atomic_load(&all[i * 66 + 64], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1e30f;
+    li[i] = on ? __hip_atomic_load(&all[i * 66 + 65], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+    oi[i] = on ? __hip_atomic_load(&all[i * 66 + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+  }
+  float M = -1e30f;
+#pragma unroll
+  for (int i = 0; i < DECODE_ATTN_MAX_PIECES; ++i) M = fmaxf(M, mi[i]);
+  float O = 0.f, L = 0.f;
+#pragma unroll
+  for (int i = 0; i < DECODE_ATTN_MAX_PIECES; ++i) {
+    const float wgt = li[i] > 0.f ? expf(mi[i] - M) : 0.f;
+    O += wgt * oi[i];
+    L += wgt * li[i];
+  }
+  const float val = L > 0.f ? O / L : 0.f;
+  if (p.out_row) p.out_row[(size_t)b * p.d + h * 64 + tid] = val;
+  else p.out[frag_index(b, h * 64 + tid, p.d >> 4)] = val;
+}
+
 // ---- the cache formats: how a key / value granule (16 bytes; fp8: 8) is laid out, widened, multiplied and stored.  All keep a key
 //      as 64 / EPG granules [granule][Smax] and a value row as 64 / EPG granules, one per lane; every product and sum is fp32. ----
 // fp32 cache: K [B][H][16][Smax][4], V [B][H][Smax][64] (256-byte rows)
@@ -216,7 +254,11 @@ struct KvFp8 {
 // NT threads per workgroup: NT keys per pass of the score phase, NG = NT / (lanes of a value row) key groups in the P.V phase.  512
 // threads at <= 128 VGPRs (two workgroups per CU) halve the number of dependent load -> use passes of the 256-thread form.
 // SLOTS: decode session (DecodeAttnArgs::slot) -- the row's own position, dead rows return at once.  KV: the cache format.
-template <int NT, bool SLOTS, class KV>
+// BI: the batch-invariant mode (DecodeAttnArgs::invariant).  The row's n keys are cut into NP = decode_attn_pieces(n) pieces, a rule of
+// n alone, and the gridDim.z workgroups of the (row, head) share them out: workgroup z walks pieces z, z + gridDim.z, ... one after
+// the other, each through the same score / softmax / P.V passes a piece of the key split takes.  gridDim.z decides how many workgroups
+// work on the row, never what is summed with what.
+template <int NT, bool SLOTS, class KV, bool BI = false>
 __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   typedef typename KV::G G;
   typedef typename KV::E E;
@@ -248,11 +290,14 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   // HBM / L2 round trips, so the cache streams have to overlap the qkv fetch and the softmax barriers.
   // key range of this workgroup: all of [kstart, pos] (pos = the new token), or one of gridDim.z contiguous pieces of it
   const int ks0 = p.kstart ? p.kstart[b] : 0;
-  const int NS = gridDim.z, z = blockIdx.z;
-  const int chunk = NS > 1 ? (((pos - ks0 + NS) / NS + 15) & ~15) : pos - ks0 + 1;
+  const int NS = gridDim.z, z0 = blockIdx.z;
+  const int NP = BI ? decode_attn_pieces(pos - ks0 + 1) : NS;      // pieces of this row's keys
+  if (BI && z0 >= NP) return;                                       // (workgroup-uniform) more workgroups than pieces
+  const int chunk = NP > 1 ? (((pos - ks0 + NP) / NP + 15) & ~15) : pos - ks0 + 1;
+  const int grp = tid / LPR, lpr = tid % LPR;
+  for (int z = z0;; z += NS) {      // one pass unless BI (the body below keeps the one-pass kernels' indentation)
   const int ks = ks0 + z * chunk;
   const int ke = min(pos, ks + chunk - 1);          // inclusive; ks > ke: an empty piece
-  const int grp = tid / LPR, lpr = tid % LPR;
   const int s_first = ks + tid;
   G kk0[KG];
 #pragma unroll
@@ -270,7 +315,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   }
 
   // ---- q, k, v of the new token (waves 0,1,2 take q,k,v): the c_attn split-K partial sum + bias, k / v to the cache ----
-  if (tid < 192) {
+  if ((!BI || z == z0) && tid < 192) {
     const int which = tid >> 6, dd = tid & 63;
     const int col = which * d + h * 64 + dd;
     const float* row = p.qkv_part + (size_t)b * 3 * d + col;
@@ -294,6 +339,7 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
   __syncthreads();
 
   // the query is wave-uniform: 64 SGPRs (v_readlane of one LDS read per lane) instead of 64 VGPRs
+  // (BI: read again in every pass -- 64 scalar moves -- rather than carried round the loop)
   const float qlane = qs[lane];
   float qv[64];
 #pragma unroll
@@ -379,7 +425,22 @@ __device__ __forceinline__ void decode_attn_body(const DecodeAttnArgs& p) {
 #pragma unroll KV::OUT_UNROLL
     for (int g = 0; g < NG; ++g) o += outp[g * 64 + tid];
   }
-  decode_attn_finish(p, b, h, z, NS, tid, o, mx, l);
+  if constexpr (!BI) {
+    decode_attn_finish(p, b, h, z, NS, tid, o, mx, l);
+    break;
+  } else {
+    if (NP == 1) {      // n <= DECODE_ATTN_PIECE_KEYS: the row's only piece, normalised in place
+      decode_attn_finish(p, b, h, 0, 1, tid, o, mx, l);
+      break;
+    }
+    decode_attn_piece_store(p, b, h, z, tid, o, mx, l);
+    if (z + NS >= NP) {
+      decode_attn_piece_merge(p, b, h, NP, min(NS, NP), tid);
+      break;
+    }
+    // (pr / red / outp are reused by the next piece: the barrier behind its prefetch orders that)
+  }
+  }
 }
 
 template <int NT, bool SLOTS>
@@ -394,12 +455,23 @@ template <int NT, bool SLOTS>
 __global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn8_kernel(const DecodeAttnArgs p) {
   decode_attn_body<NT, SLOTS, KvFp8>(p);
 }
+// the batch-invariant mode's form of the three (KVF: DecodeAttnArgs::kv_fmt)
+template <int NT, bool SLOTS, int KVF>
+__global__ __launch_bounds__(NT, (NT == 512 ? 4 : 1)) void decode_attn_inv_kernel(const DecodeAttnArgs p) {
+  if constexpr (KVF == 2) decode_attn_body<NT, SLOTS, KvFp8, true>(p);
+  else if constexpr (KVF == 1) decode_attn_body<NT, SLOTS, KvBf16, true>(p);
+  else decode_attn_body<NT, SLOTS, KvF32, true>(p);
+}
 
 int decode_attn_nsplit(int B, int H) {
   const int wgs = B * H;
   // (bf16 cache, 320 workgroups: two / three key pieces per (utterance, head) measured 185 / 215 ms per step against 156 unsplit)
   return wgs <= 128 ? std::max(1, std::min(16, 256 / wgs)) : 1;
 }
+
+// Workgroups per (row, head) in the batch-invariant mode: as many as the key split would use at this batch size, and no more than the
+// longest row the cache can hold has pieces.  Only the parallelism follows B; the pieces follow the row (decode_attn_pieces).
+int decode_attn_inv_wgs(int B, int H, int Smax) { return std::min(decode_attn_nsplit(B, H), decode_attn_pieces(std::max(Smax, 1))); }
 
 int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
   IDX_CHECK(a.qkv_part && a.kcache && a.vcache && (a.out || a.out_row) && (a.st || a.slot), "null pointer");
@@ -423,6 +495,24 @@ int decode_attn_forward(const DecodeAttnArgs& a, hipStream_t stream) {
   const double bytes_per = a.kv_fmt == 2 ? 2.0 + 8.0 / 64.0 : a.kv_fmt ? 4.0 : 8.0;
   ProfScope prof(cat_of, stream, 0.0, bytes_per * a.B * (double)a.pos_hint * a.d);
   const dim3 grid(a.H, a.B, a.nsplit);
+  if (a.invariant) {
+    IDX_CHECK(a.part && a.cnt, "batch-invariant attention: partial buffer and counters");
+    static DynLdsLimit inv_limit;
+    IDX_HIP(inv_limit.set(128 * 1024, decode_attn_inv_kernel<512, false, 0>, decode_attn_inv_kernel<512, false, 1>,
+                          decode_attn_inv_kernel<512, false, 2>, decode_attn_inv_kernel<512, true, 0>,
+                          decode_attn_inv_kernel<512, true, 1>, decode_attn_inv_kernel<512, true, 2>));
+    if (a.slot) {
+      if (a.kv_fmt == 2) hipLaunchKernelGGL((decode_attn_inv_kernel<512, true, 2>), grid, dim3(512), lds, stream, a);
+      else if (a.kv_fmt) hipLaunchKernelGGL((decode_attn_inv_kernel<512, true, 1>), grid, dim3(512), lds, stream, a);
+      else hipLaunchKernelGGL((decode_attn_inv_kernel<512, true, 0>), grid, dim3(512), lds, stream, a);
+    } else {
+      if (a.kv_fmt == 2) hipLaunchKernelGGL((decode_attn_inv_kernel<512, false, 2>), grid, dim3(512), lds, stream, a);
+      else if (a.kv_fmt) hipLaunchKernelGGL((decode_attn_inv_kernel<512, false, 1>), grid, dim3(512), lds, stream, a);
+      else hipLaunchKernelGGL((decode_attn_inv_kernel<512, false, 0>), grid, dim3(512), lds, stream, a);
+    }
+    IDX_LAUNCH_CHECK();
+    return 0;
+  }
   if (a.slot) {
     if (a.kv_fmt == 2) hipLaunchKernelGGL((decode_attn8_kernel<512, true>), grid, dim3(512), lds, stream, a);
     else if (a.kv_fmt) hipLaunchKernelGGL((decode_attn16_kernel<512, true>), grid, dim3(512), lds, stream, a);
@@ -737,8 +827,10 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
   __shared__ float s_sum;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int V = p.V;
-  const size_t nbase = ((size_t)p.st->step * p.B + b) * V;
-  const int token = warp_row_token(p, b, q.mode, q.temperature, q.top_k, q.top_p, q.exp_noise, q.seed, nbase, tid, rv, ri, sval, sidx,
+  const bool own = p.invariant && !q.exp_noise;      // the row's own stream (SampleArgs::invariant)
+  const size_t nbase = own ? (size_t)p.st->step * V : ((size_t)p.st->step * p.B + b) * V;
+  const unsigned long long seed = own ? q.seed + DRAW_ROW_STRIDE * (unsigned long long)b : q.seed;
+  const int token = warp_row_token(p, b, q.mode, q.temperature, q.top_k, q.top_p, q.exp_noise, seed, nbase, tid, rv, ri, sval, sidx,
                                    sorted_v, sorted_i, s_count, s_keep_from, s_sum);
   if (tid == 0) {
     const int tok = p.finished[b] ? p.stop_token : token;
@@ -786,7 +878,7 @@ __global__ __launch_bounds__(1024) void sample_slots_warp_kernel(const SampleArg
     greedy_row_argmax(p, b, tid, rv, ri, best, token);
   } else {
     const size_t t = (size_t)ss->step;      // read before any thread can reach slot_tail's update (the warper synchronises first)
-    const size_t nbase = sp.exp_noise ? t * p.V : t * p.B * p.V;
+    const size_t nbase = (sp.exp_noise || p.invariant) ? t * p.V : t * p.B * p.V;
     token = warp_row_token(p, b, sp.mode, sp.temperature, sp.top_k, sp.top_p, sp.exp_noise, sp.seed, nbase, tid, rv, ri, sval, sidx,
                            sorted_v, sorted_i, s_count, s_keep_from, s_sum);
   }

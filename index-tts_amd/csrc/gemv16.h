@@ -17,6 +17,7 @@ struct GemvFXArgs {
   unsigned* ksb_counters = nullptr;               // workgroups per column tile (slab [ksb][rows][N]); the LAST of them to arrive adds
                                                   // the partial sums in slab order (fixed, whoever is last) and runs the normal
                                                   // epilogue into y; counters [ceil(N/16)] start at 0 and are left at 0
+  int invariant = 0;                              // batch-invariant mode: one summation order per (N, K, format) for 1..64 rows (below)
   int dbg = 0;                                    // ablation mask for tools/gemv_probe.hip only
 };
 int gemv_fx_ksb(int N, int K);
@@ -37,7 +38,11 @@ struct FxPlan {
   size_t lds;
   int grid_x, grid_y; // column-tile groups; K pieces across workgroups (ksb)
 };
-FxPlan gemv_fx_make_plan(int N, int K, int rows, int fmt, int ksb, bool narrow_geom);
+// invariant: only the forms that sum a row's products in ONE order -- the 16x16x4 MFMA over the wave's chunks in turn, the K-slices
+// in wave order, the K pieces in slab order: the one-batch and two-buffer kernels at every MT and ntw.  The 4-row form (its 4x4x1
+// MFMA adds four k-groups by shuffles) and the narrow geometry (8 slices instead of 16) sum otherwise and are left out; kw, cps and
+// ksb follow (N, K) alone, so a row's bits do not depend on how many rows the launch has.
+FxPlan gemv_fx_make_plan(int N, int K, int rows, int fmt, int ksb, bool narrow_geom, bool invariant = false);
 int gemv_fx_forward(const WeightStream& w, const GemvFXArgs& a, hipStream_t stream);
 
 }  // namespace idxtts

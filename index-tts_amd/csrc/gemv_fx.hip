@@ -335,11 +335,12 @@ static std::atomic<int> g_decode_narrow{0};
 void set_decode_geometry(int narrow) { g_decode_narrow.store(narrow ? 1 : 0); }
 int get_decode_geometry() { return g_decode_narrow.load(); }
 
-FxPlan gemv_fx_make_plan(int N, int K, int rows, int fmt, int ksb, bool narrow_geom) {
+FxPlan gemv_fx_make_plan(int N, int K, int rows, int fmt, int ksb, bool narrow_geom, bool invariant) {
+  if (invariant) narrow_geom = false;
   const int kc16 = cdiv(K, 16), ntiles = cdiv(N, 16);
   FxPlan pl;
   pl.MT = cdiv(rows, 16);
-  pl.r4 = rows <= 4;
+  pl.r4 = rows <= 4 && !invariant;
   // The narrow geometry: 5..16 rows on a compact stream whose K gives each of 8 waves exactly 10 chunks (d = 1280, and 4 d split
   // over 4 workgroups); fp32 streams and every other shape keep the 16-wave form.
   pl.narrow = narrow_geom && pl.MT == 1 && rows > 4 && fmt != WFMT_F32 && kc16 % 80 == 0 && cdiv(kc16, 8 * ksb) == 10;
@@ -407,7 +408,7 @@ int gemv_fx_forward(const WeightStream& w, const GemvFXArgs& a, hipStream_t stre
   IDX_CHECK(w.fmt == WFMT_F32 || w.fmt == WFMT_BF16 || (w.fmt == WFMT_FP8 && w.wscale), "weight format");
   const int ksb = (a.slab && a.ksb_counters) ? gemv_fx_ksb(w.N, w.K) : 1;
   if (ksb > 1) IDX_CHECK(!a.colsum && a.act == 0 && ksb <= 8, "K split across workgroups: no folded LayerNorm, no activation, <= 8 pieces");
-  const FxPlan pl = gemv_fx_make_plan(w.N, w.K, a.rows, w.fmt, ksb, narrow_geom);
+  const FxPlan pl = gemv_fx_make_plan(w.N, w.K, a.rows, w.fmt, ksb, narrow_geom, a.invariant != 0);
   IDX_CHECK(pl.threads <= 1024, "workgroup size");
   GemvFXP p;
   p.xf = a.xf; p.wp = w.wp; p.wscale = w.wscale; p.bias = a.bias; p.colsum = a.colsum; p.ln_eps = a.ln_eps;

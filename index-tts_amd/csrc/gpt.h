@@ -55,6 +55,10 @@ struct GPTModel : ModelBase {
   const float *mel_emb = nullptr, *text_emb = nullptr, *mel_pos = nullptr, *text_pos = nullptr;
   int weight_fmt = WFMT_F32;      // storage format of the decode weight streams (quantize_weights)
   int kv_fmt = 0;                 // KV cache of the cached generation: 0 = fp32, 1 = bf16, 2 = scaled fp8 (keys / values rounded when produced; decode.h)
+  // idxtts_gpt_set_batch_invariant: every launch that feeds the choice of a code is chosen from the request alone (idxtts.h
+  // "Batch-invariant mode") -- fp32-MFMA GEMV in its 16-row-tile forms at every row count, decode attention in pieces that follow the
+  // row's own key count, exact prefill GEMMs with key tiles counted from the row's first key, seeded draws without a term in B
+  int batch_invariant = 0;
   std::atomic<int> generating{0}; // generate() / generate_beam() calls in flight: idxtts_gpt_set_kv_format refuses to switch under them
   struct GenScope { GPTModel* m; explicit GenScope(GPTModel* mm) : m(mm) { m->generating.fetch_add(1); } ~GenScope() { m->generating.fetch_sub(1); } };
   size_t kv_layer_bytes(int B, int Smax) const { return (size_t)B * cfg.heads * Smax * 64 * (kv_fmt == 2 ? 1 : kv_fmt ? 2 : 4); }
@@ -90,6 +94,7 @@ struct GPTModel : ModelBase {
     SlotSampling* slot_samp = nullptr;        // sampled decode session only: each slot's sampler (the step samples with it)
     idxtts_sampling samp{0, 1.0f, 0, 1.0f, nullptr, 0};      // generate(): the call's sampler (mode 0 = greedy)
     const long long* forced = nullptr; int forced_ld = 0;   // generate_forced: [B][forced_ld] tokens fed back instead of the argmax
+    int invariant = 0;                        // the context's batch_invariant when the buffers were carved
     bool beam_tail = false;                   // the beam stages on `beam`: a beam session's (slots set) or generate_beam's
     BeamState beam;
   };
@@ -130,7 +135,9 @@ struct GPTModel : ModelBase {
   int decode_step(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
   int decode_step_pl(const Buffers& w, int B, float penalty, int codes_ld, float* logits_base, int pos_hint, hipStream_t st);
   int capture_step(const Buffers& w, int B, float penalty, int codes_ld, hipStream_t st, StepGraph* g);   // one decode step -> *g
-  bool use_pl(int B) const;                   // this many decode rows run on the plane GEMV
+  bool use_pl(int B) const;                   // this many decode rows run on the plane GEMV (never in the batch-invariant mode)
+  int step_key() const;                       // what a captured step's kernels were chosen by besides shape and KV format: the two
+                                              // process-wide decode switches, or the batch-invariant mode, which ignores both
   bool fused_tail(const Buffers& w) const;    // w's step tail also writes the next input and advances: no embed_step / advance_state
   // generate() and generate_beam() are re-entrant across host threads, each call with its own workspace and stream; both run on
   // call_stream()'s stream through run_generation() (gpt.hip): R = B * fan rows, row r on prompt r / fan, the step tail w's own
@@ -156,6 +163,7 @@ struct GPTModel : ModelBase {
   // many rows are admitted at once.
   struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
     int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
+    int invariant = 0;                // the context's batch-invariant mode at _init: the session keeps it (changed since: every call refuses)
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
     std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
     int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each

@@ -176,6 +176,7 @@ int GPTModel::finalize(std::map<std::string, HostTensor>& t, DeviceArena& arena)
 GPTModel::Buffers GPTModel::carve(void* ws, int B, int S, int max_new, size_t prefill_rows) const {
   const int d = cfg.model_dim, V = cfg.number_mel_codes, L = cfg.layers;
   Buffers b;
+  b.invariant = batch_invariant;
   Carver c(ws);
   const size_t rows = prefill_rows ? prefill_rows : (size_t)B * S;
   b.x = c.take<float>(rows * d);
@@ -232,7 +233,9 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   // prefill: a key / value moved by the split GEMM's 2^-16 lands on the other e4m3 neighbour 250 x as often as one moved by an fp32
   // summation order, and each such flip is 2^-4 of the element -- measured against the oracle, max |dlogit| 5.5e-2 with the split
   // prefill and 1.8e-2 with the exact one (profiles/README.md "fp8 KV cache").
-  const bool exact = store_kv && kv_fmt != 1;
+  // Batch-invariant mode: the exact kernel for every cache format -- one GEMM family whatever M is (its K groups follow K alone) -- and
+  // the prefill attention's key tiles counted from each row's first real key, so a left-padded row is summed as the unpadded one.
+  const bool exact = store_kv && (kv_fmt != 1 || batch_invariant);
   auto mm = [&](const LinearWeights& lw, const GemmArgs& ga) { return exact ? gemm_tn_forward(lw, ga, st) : gemm_forward(lw, ga, st); };
   const GPTLayer& L = layers[li];
   const int d = cfg.model_dim, M = B * S;
@@ -254,6 +257,7 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   a.q_ts = a.k_ts = a.v_ts = 3 * d; a.o_ts = d;
   a.B = B; a.H = cfg.heads; a.Sq = S; a.Sk = S; a.causal = 1; a.kstart = kstart; a.scale = 0.125f;
   a.split_bf16 = !exact && get_gemm_mode() == GEMM_BF16X3;      // the prefill of an fp32 cache stays exact fp32
+  a.tiles_from_kstart = store_kv && batch_invariant;
   if (flash_attn_forward(a, st)) return 1;
   GemmArgs p;
   p.x = w.att; p.ldx = d; p.y = w.x; p.ldy = d; p.res = w.x; p.ldr = d; p.M = M;
@@ -285,7 +289,7 @@ int GPTModel::head_logits(const Buffers& w, int B, const float* x, int ldx, bool
     if (gemv_pl_forward(head_p, hv, st)) return 1;
   } else {
     GemvFXArgs hv;
-    hv.xf = w.hd; hv.rows = B; hv.bias = head_b; hv.y = w.logits; hv.ldy = V;
+    hv.xf = w.hd; hv.rows = B; hv.bias = head_b; hv.y = w.logits; hv.ldy = V; hv.invariant = w.invariant;
     if (gemv_fx_forward(head_g, hv, st)) return 1;
   }
   return 0;
@@ -314,7 +318,7 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
   s.part = w.logits; s.parts = 1; s.part_rows = B; s.bias = nullptr; s.logits_out = logits_out;
   s.seen = w.seen; s.finished = w.finished; s.codes = w.codes; s.codes_ld = codes_ld; s.cur_tok = w.cur_tok;
   s.st = w.state; s.B = B; s.V = V; s.stop_token = cfg.stop_mel_token; s.penalty = penalty;
-  s.forced = w.forced; s.forced_ld = w.forced_ld;
+  s.forced = w.forced; s.forced_ld = w.forced_ld; s.invariant = w.invariant;
   if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
     s.embed = tail_embed(w, pl);
     if (w.slot_samp) return sample_slots_warp_forward(s, w.slots, w.slot_samp, nullptr, B, st);      // sampled session: each slot's own sampler
@@ -343,6 +347,9 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
 // A shape whose plane plan names no kernel (49..64 rows with K in 5121..10240, a compact model wider than d = 1280: gemv_pl_can_run)
 // keeps the whole step on the fp32-MFMA GEMV, which serves every row count.
 bool GPTModel::use_pl(int B) const {
+  // batch-invariant mode: one GEMV family for 1..64 rows.  The plane GEMV's three bf16 planes are other arithmetic than the fp32 MFMA,
+  // and it has no form below 5 rows, so the mode stays on the fp32-MFMA GEMV (48 rows: 0.612 s against 0.567 s per 256 tokens)
+  if (batch_invariant) return false;
   if (weight_fmt == WFMT_F32 || B < get_decode_plane_rows() || cfg.model_dim % 32 != 0 || !head_p.wp) return false;
   const int d = cfg.model_dim;
   return gemv_pl_can_run(3 * d, d, B) && gemv_pl_can_run(d, d, B) && gemv_pl_can_run(4 * d, d, B) && gemv_pl_can_run(d, 4 * d, B) &&
@@ -369,6 +376,7 @@ DecodeAttnArgs GPTModel::attn_args(int li, const Buffers& w, int B, int pos_hint
   da.kcache = kv.kcache; da.vcache = kv.vcache; da.kv_fmt = kv.fmt; da.kscale = kv.kscale; da.vscale = kv.vscale; da.kstart = w.kstart;
   da.st = w.state; da.B = B; da.H = cfg.heads; da.Smax = w.Smax; da.d = cfg.model_dim; da.scale = 0.125f;
   da.nsplit = decode_attn_nsplit(B, cfg.heads); da.part = w.attn_part; da.cnt = w.attn_cnt; da.slot = w.slots;
+  if (w.invariant) { da.invariant = 1; da.nsplit = decode_attn_inv_wgs(B, cfg.heads, w.Smax); }
   da.pos_hint = pos_hint;
   return da;
 }
@@ -411,26 +419,28 @@ int GPTModel::decode_step(const Buffers& w, int B, float penalty, int codes_ld, 
   for (int li = 0; li < cfg.layers; ++li) {
     const GPTLayer& L = layers[li];
     GemvFXArgs qa;      // qkv = c_attn(LN1(x)) + b, row-major for the attention kernel
-    qa.xf = w.xd; qa.rows = B; qa.colsum = L.attn_u; qa.bias = L.attn_c; qa.y = w.qkvd; qa.ldy = 3 * d;
+    qa.xf = w.xd; qa.rows = B; qa.colsum = L.attn_u; qa.bias = L.attn_c; qa.y = w.qkvd; qa.ldy = 3 * d; qa.invariant = w.invariant;
     if (gemv_fx_forward(L.attn_g, qa, st)) return 1;
     DecodeAttnArgs da = attn_args(li, w, B, pos_hint);
     da.out = w.attd;
     if (decode_attn_forward(da, st)) return 1;
     GemvFXArgs pa;      // x += c_proj(attn) + b  (in place: a thread reads and writes only its own element of x)
-    pa.xf = w.attd; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xd; pa.y = w.xd; pa.y_frag = 1;
+    pa.xf = w.attd; pa.rows = B; pa.bias = L.proj_l.bias; pa.res = w.xd; pa.y = w.xd; pa.y_frag = 1; pa.invariant = w.invariant;
     if (gemv_fx_forward(L.proj_g, pa, st)) return 1;
     GemvFXArgs fa;      // ff = gelu_new(c_fc(LN2(x)) + b)
-    fa.xf = w.xd; fa.rows = B; fa.colsum = L.fc_u; fa.bias = L.fc_c; fa.act = 1; fa.y = w.ffd; fa.y_frag = 1;
+    fa.xf = w.xd; fa.rows = B; fa.colsum = L.fc_u; fa.bias = L.fc_c; fa.act = 1; fa.y = w.ffd; fa.y_frag = 1; fa.invariant = w.invariant;
     if (gemv_fx_forward(L.fc_g, fa, st)) return 1;
     GemvFXArgs fb;      // x += mlp.c_proj(ff) + b; at full size K is also split across workgroups (gemv_fx_ksb: all 256 CUs stream), the
                         // partial sums combined in a fixed order by the last workgroup of each column tile to arrive (no combine launch)
     fb.xf = w.ffd; fb.rows = B; fb.bias = L.fc2_l.bias; fb.res = w.xd; fb.y = w.xd; fb.y_frag = 1;
-    fb.slab = w.slab; fb.ksb_counters = w.ksb_cnt;
+    fb.slab = w.slab; fb.ksb_counters = w.ksb_cnt; fb.invariant = w.invariant;
     if (gemv_fx_forward(L.fc2_g, fb, st)) return 1;
   }
   if (head_and_sample(w, B, w.xd, d, true, penalty, codes_ld, logits_base, st)) return 1;
   return fused ? 0 : advance_state(w.state, st);
 }
+
+int GPTModel::step_key() const { return batch_invariant ? 1 << 16 : get_decode_geometry() | (get_decode_plane_rows() << 1); }
 
 // one decode step captured into g (every per-step value is device-resident, so the graph replays the step); the caller drops g
 int GPTModel::capture_step(const Buffers& w, int B, float penalty, int codes_ld, hipStream_t st, StepGraph* g) {
@@ -565,7 +575,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   // Instantiated decode-step graphs of greedy generations are kept (graph_cache): nothing call-specific is baked into their launches
   const bool graph = use_graph && !logits_out && !forced && !prof_enabled();
   const bool cacheable = graph && w.samp.mode == 0;
-  const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
+  const int geom = step_key();
   struct SlotLease {       // a cached graph in use by this call
     GPTModel* m = nullptr; int idx = -1;
     ~SlotLease() { if (m && idx >= 0) { std::lock_guard<std::mutex> l(m->graph_mu); m->graph_cache[idx].in_use = false; } }
@@ -706,6 +716,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.step.drop();
   s = Session();
   s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv_fmt = kv_fmt; s.gemm_mode = get_gemm_mode();
+  s.invariant = batch_invariant;
   s.ws_bytes = ws_bytes;
   s.busy.assign(slots, 0);
   s.sampled = sampled;
@@ -730,6 +741,7 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   const int units = s.slots / fan;
   IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   int pmax = 0;
   std::vector<char> taken(units, 0);
   for (int b = 0; b < n; ++b) {
@@ -746,7 +758,7 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   // with zero rows (b >= n) to at least 256 rows -- every admission then runs the kernel a generate() batch of >= 256 prefill rows runs.
   const int S = pmax + 1;
   int rows = n;
-  if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3) rows = std::max(n, cdiv(256, S));
+  if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3 && !s.invariant) rows = std::max(n, cdiv(256, S));      // (the mode's prefill is exact)
   IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
   if (params()) return 1;
   // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen
@@ -824,10 +836,11 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   Session& s = *sp;
   IDX_CHECK(n_steps >= 0, "n_steps");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   GenScope gen_scope(this);
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
   const Buffers& w = sb.w;
-  const int geom = get_decode_geometry() | (get_decode_plane_rows() << 1);
+  const int geom = step_key();
   if (s.step.exec && s.geom != geom) s.step.drop();
   IDX_CHECK(st != nullptr || !use_graph, "graph replay needs a stream other than the legacy default stream");
   const bool graph_ok = use_graph && !prof_enabled();
@@ -919,6 +932,7 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
   IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
   IDX_CHECK(s.busy[slot], "slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
@@ -936,6 +950,7 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
     h.mode = e.mode; h.temperature = e.temperature; h.top_k = e.top_k; h.top_p = e.top_p; h.seed = e.seed;
     h.exp_noise = (unsigned long long)(uintptr_t)e.exp_noise;
   }
+  h.reserved[0] = s.invariant;      // a row parked in the batch-invariant mode says so; every other row carries zeros
   h.bytes = park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step).bytes;
   *hdr = h;
   return 0;
@@ -971,6 +986,7 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
   IDX_CHECK(!s.busy[slot], "slot is not free");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   IDX_CHECK(src_bytes >= sizeof(idxtts_park_header), "parked row shorter than its header");
   idxtts_park_header h;
   IDX_HIP(hipMemcpyAsync(&h, src, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -979,7 +995,10 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   IDX_CHECK(h.version == IDXTTS_PARK_VERSION, "parked row of another format version");
   IDX_CHECK(h.layers == cfg.layers && h.heads == cfg.heads && h.model_dim == cfg.model_dim && h.number_mel_codes == cfg.number_mel_codes,
             "parked row of another model (dimensions)");
-  IDX_CHECK(h.slots == s.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
+  IDX_CHECK(h.reserved[0] == 0 || h.reserved[0] == 1, "parked row's mode field is corrupt");
+  IDX_CHECK(h.reserved[0] == s.invariant, "parked row and session differ in the batch-invariant mode");
+  // in the mode nothing on a row's path depends on the slot count: a row moves between sessions of any size
+  IDX_CHECK(s.invariant || h.slots == s.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
   IDX_CHECK(h.kv_format == s.kv_fmt, "parked row of another KV format");
   IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked row of another GEMM mode");
   IDX_CHECK(h.mode == 0 || s.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");

@@ -75,6 +75,7 @@ BeamState GPTModel::beam_state(const Buffers& w, const BeamBuffers& bb, int B, i
   b.hyp_score = bb.hyp_score; b.hyp_len = bb.hyp_len; b.hyp_slot = bb.hyp_slot; b.hyp_seq = bb.hyp_seq; b.hyp_n = bb.hyp_n;
   b.hyp_worst = bb.hyp_worst; b.done = bb.done;
   b.kcache = w.kcache; b.vcache = w.vcache; b.kv_gran = kv_fmt ? 8 : 16; b.kscale = w.kscale; b.vscale = w.vscale;
+  b.invariant = w.invariant;
   b.B = B; b.nb = nb; b.V = cfg.number_mel_codes; b.stop_token = cfg.stop_mel_token; b.L = cfg.layers; b.H = cfg.heads; b.Smax = w.Smax;
   return b;
 }

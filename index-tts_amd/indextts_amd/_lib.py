@@ -21,7 +21,7 @@ SYMBOLS = [
     "idxtts_bigvgan_create", "idxtts_bigvgan_workspace_bytes", "idxtts_bigvgan_fwd", "idxtts_bigvgan_fwd_ragged",
     "idxtts_profile_enable", "idxtts_profile_num_kernels", "idxtts_profile_kernel_name", "idxtts_profile_read", "idxtts_profile_event_overhead",
     "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_bf16_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
-    "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
+    "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_set_batch_invariant", "idxtts_gpt_get_batch_invariant", "idxtts_batch_invariant_plan_query", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
     "idxtts_gpt_beam_workspace_bytes", "idxtts_gpt_generate_beam",
     "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
     "idxtts_gpt_session_read", "idxtts_gpt_session_release", "idxtts_gpt_session_workspace_bytes_ex", "idxtts_gpt_session_init_ex",
@@ -148,6 +148,8 @@ def load() -> ctypes.CDLL:
     lib.idxtts_kv_fp8_quantize.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_set_kv_format.argtypes = [c_void_p, c_int]
     lib.idxtts_gpt_get_kv_format.argtypes = [c_void_p]
+    lib.idxtts_gpt_set_batch_invariant.argtypes = [c_void_p, c_int]
+    lib.idxtts_gpt_get_batch_invariant.argtypes = [c_void_p]
     lib.idxtts_ctx_destroy.argtypes = [c_void_p]
     lib.idxtts_bigvgan_create.argtypes = [POINTER(BigVGANConfigC), POINTER(c_void_p)]
     lib.idxtts_bigvgan_workspace_bytes.argtypes = [c_void_p, c_int, c_int]
@@ -438,6 +440,25 @@ def gemv_fx_plan(N: int, K: int, rows: int, fmt: int, with_slab: bool = False, n
     out = GemvFxPlanC()
     check(load().idxtts_gemv_fx_plan_query(int(N), int(K), int(rows), int(fmt), int(bool(with_slab)), int(bool(narrow)), ctypes.byref(out)))
     return {n: int(getattr(out, n)) for n, _ in GemvFxPlanC._fields_}
+
+
+class BatchInvariantPlanC(ctypes.Structure):          # idxtts_batch_invariant_plan (include/idxtts.h)
+    _fields_ = [(n, c_int) for n in ("family", "r4", "narrow", "kw", "cps", "ksb", "mt", "ntw", "single", "attn_pieces", "attn_piece_keys",
+                                     "attn_workgroups")]
+
+
+# the fields of batch_invariant_plan() that say what is added to what; the others (mt, ntw, single, attn_workgroups) say how many
+# tiles and workgroups the launch has for its row count
+BATCH_INVARIANT_ORDER_FIELDS = ("family", "r4", "narrow", "kw", "cps", "ksb", "attn_pieces", "attn_piece_keys")
+
+
+def batch_invariant_plan(N: int, K: int, rows: int, fmt: int, with_slab: bool = False, B: int = 1, heads: int = 20, smax: int = 2048,
+                         n_keys: int = 1) -> dict:
+    """What the batch-invariant mode launches for one decode GEMV and for the decode attention of a row with n_keys keys (host only)."""
+    out = BatchInvariantPlanC()
+    check(load().idxtts_batch_invariant_plan_query(int(N), int(K), int(rows), int(fmt), int(bool(with_slab)), int(B), int(heads), int(smax),
+                                                   int(n_keys), ctypes.byref(out)))
+    return {n: int(getattr(out, n)) for n, _ in BatchInvariantPlanC._fields_}
 
 
 def gemv_pl_plan(N: int, K: int, rows: int) -> dict:

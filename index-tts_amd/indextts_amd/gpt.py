@@ -38,7 +38,7 @@ class UnifiedVoice:
     MAX_WORKSPACES = 4
 
     def __init__(self, state_dict, cfg: GPTConfig = GPTConfig(), device="cuda:0", weight_format: str = "f32", keep_effective: bool = False,
-                 kv_format: str = None):
+                 kv_format: str = None, batch_invariant: bool = False):
         """weight_format: storage of the GPT's linear weights -- "f32" (default), "bf16", or "fp8" (e4m3 + power-of-two scale
         per output channel): the reference's `use_fp16` switch (infer_v2.py:145-146) / BASELINE configs[4].  The weights are
         rounded ONCE at load (`idxtts_gpt_quantize_weights`); the arithmetic stays fp32, and every pass runs that one rounded
@@ -46,7 +46,8 @@ class UnifiedVoice:
         kv_format: storage of the KV cache of the cached generation, "f32", "bf16" or "fp8" (`idxtts_gpt_set_kv_format`: keys /
         values rounded once, when produced -- to bf16, or to e4m3 codes with one power-of-two scale per 64-dim vector; fp32
         arithmetic).  Default: "f32" with fp32 weights, "bf16" with compact weights -- the reference's `use_fp16` halves weights
-        and cache together; "fp8" is opt-in only, fp8 weights do not select it."""
+        and cache together; "fp8" is opt-in only, fp8 weights do not select it.
+        batch_invariant: the opt-in batch-invariant mode (`set_batch_invariant`)."""
         lib = _lib.load()
         if weight_format not in WEIGHT_FORMATS:
             raise ValueError(f"weight_format must be one of {sorted(WEIGHT_FORMATS)}")
@@ -76,6 +77,8 @@ class UnifiedVoice:
                     self.effective_state_dict = {k: _lib.get_tensor(ctx, k, tuple(v.shape)) for k, v in sd.items()}
             _lib.load_state_dict(h, sd, before_finalize=hook)
             _lib.check(lib.idxtts_gpt_set_kv_format(h, KV_FORMATS[kv_format]))
+            _lib.check(lib.idxtts_gpt_set_batch_invariant(h, int(bool(batch_invariant))))
+        self.batch_invariant = bool(batch_invariant)
         from .cond import ConditioningEncoders
         self.cond = ConditioningEncoders(state_dict, cfg, device=self.device) if ConditioningEncoders.has_weights(state_dict) else None
         se = state_dict["speed_emb.weight"]
@@ -95,6 +98,14 @@ class UnifiedVoice:
             raise ValueError(f"kv_format must be one of {sorted(KV_FORMATS)}")
         _lib.check(_lib.load().idxtts_gpt_set_kv_format(self._h, KV_FORMATS[kv_format]))
         self.kv_format = kv_format
+
+    def set_batch_invariant(self, on: bool = True) -> None:
+        """Switch the batch-invariant mode between generations (`idxtts_gpt_set_batch_invariant`, per context, default off).  With it
+        on, a request's codes (and recorded logits) equal bit for bit those of the B = 1 call on its own unpadded prompt, whichever
+        batch, session size, slot, lane or park / resume history it runs with, and seeded draws carry no term in the batch size.  A
+        decode session keeps the mode it was opened in."""
+        _lib.check(_lib.load().idxtts_gpt_set_batch_invariant(self._h, int(bool(on))))
+        self.batch_invariant = bool(on)
 
     @staticmethod
     def _on_path(key: str) -> bool:
@@ -674,6 +685,9 @@ class DecodeSession(_Session):
     (attention_mask=None) with max_new_tokens = its cap -- whatever else is in flight, when it was admitted and which slot it has.
     With a bf16 KV cache in split-bf16 GEMM mode that reference batch needs slots * (P + 1) >= 256 prefill rows (or the exact
     GEMM mode).  Results can depend on `slots`: the decode attention's key split and the decode GEMV are chosen from it.
+    With the batch-invariant mode on (UnifiedVoice.set_batch_invariant, before the session is created; it keeps the mode) the rule is
+    simply: a request's codes equal, bit for bit, those of generate on its own prompt alone (B = 1), for every `slots` -- greedy and
+    sampled (a seeded request draws the B = 1 stream) -- and a parked row resumes into a session of any slot count.
 
     sampled=True: admit(rows, caps, sampling=...) gives each request its own sampler -- a dict per row with `sampler` ("greedy" |
     "hf" | "accel"), `temperature`, `top_k`, `top_p` (HF only), and `seed` or `exp_noise` [cap, V].  A sampled request's codes equal,
@@ -806,8 +820,9 @@ class DecodeSession(_Session):
     def resume(self, parked: ParkedRow, slot=None) -> int:
         """Puts a parked row into `slot` (default: the first free slot) and returns the slot; the row decodes on from the next step().
         `parked` may live on the device or in host memory (it is staged here) and may come from another session of the same model,
-        slots, KV format and GEMM mode whose max_new and cache length hold the rest of the request.  A refusal raises and changes
-        nothing; a ParkedRow is resumed once."""
+        slots, KV format and GEMM mode whose max_new and cache length hold the rest of the request.  In the batch-invariant mode the
+        slot counts need not match (both sessions must be in the mode; a row parked with the mode off is refused there, and the
+        reverse).  A refusal raises and changes nothing; a ParkedRow is resumed once."""
         if not isinstance(parked, ParkedRow):
             raise TypeError("resume() takes a ParkedRow")
         parked._check()
@@ -850,7 +865,9 @@ class BeamDecodeSession(_Session):
     Determinism: a request's codes equal, bit for bit, row 0 of UnifiedVoice.generate_beam with the same parameters and repetition penalty
     on slots / num_beams copies of its prompt (attention_mask=None, max_new_tokens = its cap; with exp_noise: generate_beam's exp_noise
     whose [:, 0, :] is the request's noise), cut after its first stop token -- whatever else is in flight, when it was admitted and which
-    group it has (DecodeSession's conditions: a bf16 KV cache in split-bf16 GEMM mode needs slots * (P + 1) >= 256)."""
+    group it has (DecodeSession's conditions: a bf16 KV cache in split-bf16 GEMM mode needs slots * (P + 1) >= 256).
+    With the batch-invariant mode on (UnifiedVoice.set_batch_invariant) a request's codes equal those of generate(num_beams=...) on
+    its own prompt alone, for every `slots` and group; a seeded request draws the B = 1 stream."""
 
     _BEAM_KEYS = {"do_sample", "temperature", "top_k", "top_p", "length_penalty", "early_stopping", "seed", "exp_noise"}
 

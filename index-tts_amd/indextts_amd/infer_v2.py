@@ -179,8 +179,8 @@ class IndexTTS2:
 
     def __init__(self, cfg_path="checkpoints/config.yaml", model_dir="checkpoints", use_fp16=False, device=None,
                  use_cuda_kernel=None, use_deepspeed=False, use_accel=False, use_torch_compile=False, gpt_weight_format=None,
-                 segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None):
-        # acoustic_bf16: see from_state_dicts (process-wide).
+                 segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None, batch_invariant: bool = False):
+        # acoustic_bf16: see from_state_dicts (process-wide).  batch_invariant: see from_state_dicts (this object's GPT only).
         # use_fp16 (reference: gpt.half() + fp16 autocast, infer_v2.py:109, 145-146) maps to bf16 STORAGE of the GPT weights:
         # the arithmetic of the HIP path stays fp32.  gpt_weight_format ("f32" | "bf16" | "fp8") overrides it.
         if gpt_weight_format is None:
@@ -193,7 +193,7 @@ class IndexTTS2:
         cfg, raw = config_from_yaml(cfg_path, model_dir) if os.path.exists(cfg_path) else (PipelineConfig(), None)
         gpt_sd, s2mel_sd, voc_sd = load_reference_checkpoints(model_dir, raw)
         self._init(cfg, gpt_sd, s2mel_sd, voc_sd, device, gpt_weight_format, segment_batch=segment_batch, gpt_kv_format=gpt_kv_format,
-                   acoustic_bf16=acoustic_bf16)
+                   acoustic_bf16=acoustic_bf16, batch_invariant=batch_invariant)
         # the rest of the reference's constructor (infer_v2.py:187-289): semantic model + statistics, semantic codec, CAMPPlus,
         # emotion banks, tokenizer
         from .checkpoint import load_prompt_checkpoints, reference_text_normalizer
@@ -217,20 +217,24 @@ class IndexTTS2:
 
     @classmethod
     def from_state_dicts(cls, cfg: PipelineConfig, gpt_sd, s2mel_sd, bigvgan_sd, device=None, gpt_weight_format="f32",
-                         keep_effective_gpt=False, segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None) -> "IndexTTS2":
+                         keep_effective_gpt=False, segment_batch: int = 16, gpt_kv_format=None, acoustic_bf16=None,
+                         batch_invariant: bool = False) -> "IndexTTS2":
         """gpt_weight_format: "f32" | "bf16" | "fp8" storage of the GPT linear weights, gpt_kv_format: "f32" | "bf16" | "fp8" storage of its KV
         cache (default: fp32 with fp32 weights, bf16 with compact weights; fp8 only when asked for) (UnifiedVoice); keep_effective_gpt keeps
         `self.gpt.effective_state_dict` (the rounded model, reference keys) for parity checks; segment_batch: segments of one
         infer() call synthesised together (1 = the reference's loop as written); acoustic_bf16: None leaves the library's switch as
         it is, True / False sets it (_lib.set_acoustic_bf16): s2mel and the vocoder on one bf16 MFMA per product instead of the split
         form's three -- about 1.45 x faster, mel L1 7.7e-3 instead of 1.3e-5 from the exact mode (profiles/README.md "Acoustic bf16"), the GPT and the codes it
-        chooses untouched.  The switch is PROCESS-WIDE: it holds for every IndexTTS2 of the process, not for this object."""
+        chooses untouched.  The switch is PROCESS-WIDE: it holds for every IndexTTS2 of the process, not for this object.
+        batch_invariant: this object's GPT in the batch-invariant mode (UnifiedVoice.set_batch_invariant): an utterance's codes do not
+        depend on the batch, session size, lane or pipeline it is decoded in (the acoustic stage is outside that contract)."""
         self = cls.__new__(cls)
-        self._init(cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format, keep_effective_gpt, segment_batch, gpt_kv_format, acoustic_bf16)
+        self._init(cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format, keep_effective_gpt, segment_batch, gpt_kv_format, acoustic_bf16,
+                   batch_invariant)
         return self
 
     def _init(self, cfg, gpt_sd, s2mel_sd, bigvgan_sd, device, gpt_weight_format="f32", keep_effective_gpt=False, segment_batch=16,
-              gpt_kv_format=None, acoustic_bf16=None):
+              gpt_kv_format=None, acoustic_bf16=None, batch_invariant=False):
         if acoustic_bf16 is not None:
             _lib.set_acoustic_bf16(bool(acoustic_bf16))
         if device is None:
@@ -240,7 +244,7 @@ class IndexTTS2:
             raise RuntimeError("IndexTTS2 (HIP path) needs an MI355X device; there is no CPU fallback")
         self.cfg = cfg
         self.gpt = UnifiedVoice(gpt_sd, cfg.gpt, device=self.device, weight_format=gpt_weight_format, keep_effective=keep_effective_gpt,
-                                kv_format=gpt_kv_format)
+                                kv_format=gpt_kv_format, batch_invariant=batch_invariant)
         self.s2mel = S2Mel(s2mel_sd, cfg.s2mel, device=self.device)
         self.bigvgan = BigVGAN(bigvgan_sd, cfg.bigvgan)
         self.stop_mel_token = cfg.gpt.stop_mel_token

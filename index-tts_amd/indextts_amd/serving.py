@@ -48,16 +48,19 @@ from typing import Optional
 import torch
 
 
-def merge_keeps_kernels(rows_each, prefix_len: int, split_bf16_gemm: bool, compact_weights: bool, plane_rows: int) -> bool:
+def merge_keeps_kernels(rows_each, prefix_len: int, split_bf16_gemm: bool, compact_weights: bool, plane_rows: int,
+                        batch_invariant: bool = False) -> bool:
     """May requests of `rows_each` utterances (same text width; `prefix_len` = conditioning + text rows of one utterance's prompt) be
     decoded as ONE batch and still equal their own sequential calls bit for bit?  Rows are independent inside every kernel; what a merge
     can change is WHICH kernel runs:
       * GEMM-shaped passes (prefill, latent pass): exact fp32 below 256 rows, split-bf16 from 256 rows on (csrc/gemm.hip dispatch) --
         every request must be on the split-bf16 side by itself (its prefill alone has >= 256 rows), unless the exact mode is selected;
       * the decode step with compact weight streams: fp32-MFMA GEMV below `plane_rows` rows, plane GEMV from there on
-        (idxtts_set_decode_plane_rows) -- all requests and the merged batch must fall on the same side."""
+        (idxtts_set_decode_plane_rows) -- all requests and the merged batch must fall on the same side.
+    batch_invariant (UnifiedVoice.set_batch_invariant): every launch that feeds the choice of a code follows the request alone, so
+    any merge keeps every request's codes."""
     rows_each = [int(r) for r in rows_each]
-    if len(rows_each) <= 1:
+    if len(rows_each) <= 1 or batch_invariant:
         return True
     if split_bf16_gemm and any(r * prefix_len < 256 for r in rows_each):
         return False
@@ -305,7 +308,8 @@ class BatchPipeline:
         g = self.tts.cfg.gpt
         prefix = g.cond_latents + 2 + int(group[0].text.shape[1]) + 2 + 1      # [cond | start, text, stop] + start_mel (gpt.py::prepare_gpt_inputs)
         return merge_keeps_kernels([r.text.shape[0] for r in group], prefix, _lib.get_gemm_mode() == _lib.GEMM_BF16X3,
-                                   self.tts.gpt.weight_format != "f32", _lib.get_decode_plane_rows())
+                                   self.tts.gpt.weight_format != "f32", _lib.get_decode_plane_rows(),
+                                   batch_invariant=bool(getattr(self.tts.gpt, "batch_invariant", False)))
 
     def _lane_job(self):
         group = self._take()
@@ -521,7 +525,10 @@ class ContinuousPipeline:
     is its CFM noise, and with both its audio).  A request's codes equal, bit for bit, row 0 of `UnifiedVoice.generate` on
     `slots` copies of each of its utterances (gpt.DecodeSession; sampled: with that utterance's sampler and seed), whatever else
     shares the session; they can differ from `BatchPipeline` / `synthesize_batch` results, whose decode batch is the request itself
-    (the decode attention's key split and the decode GEMV are chosen by row count).  An error (say, a bad token id or a bad sampling
+    (the decode attention's key split and the decode GEMV are chosen by row count).  With the GPT in the batch-invariant mode
+    (IndexTTS2(batch_invariant=True) / UnifiedVoice.set_batch_invariant, before the pipeline is built) the contract is simply: an
+    utterance's codes equal those of `UnifiedVoice.generate` on that utterance alone -- for every `slots`, every lane, and the same
+    as `BatchPipeline` and `synthesize_batch` give it under the same seed.  An error (say, a bad token id or a bad sampling
     parameter) fails the offending request's Future only; num_beams > 1 is refused at submit.
 
     num_beams > 1: beam search / beam-sample.  The lanes own beam sessions (`UnifiedVoice.beam_session`): `slots` rows = slots /
