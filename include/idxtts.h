@@ -479,8 +479,8 @@ int idxtts_gpt_session_stop(idxtts_ctx* ctx, int n, const int* slots, void* work
  * proportional to pos, the captured step and the workspace layout are untouched.  The row's next decode input is not saved: _resume
  * rebuilds it from the last code and the mel position, so a parked row does not depend on which GEMV the step runs.
  * Determinism: a request parked and resumed any number of times, into any slots, returns bit for bit the codes of its uninterrupted
- * run; every other request's codes are untouched.  Greedy and sampled sessions; a beam session's group (its scorer state) cannot be
- * parked, both calls fail on one.
+ * run; every other request's codes are untouched.  Greedy and sampled sessions; both calls fail on a beam session, where one row of
+ * a group cannot leave it: a whole group is parked with _park_group / _resume_group below.
  * The parked row: idxtts_park_header, then segments that each start 16-byte aligned, padding written as zero (a parked row is a
  * function of the request's state alone, byte for byte).  With pad16(n) = (n + 15) & ~15, V = number_mel_codes, C = 16 key chunks
  * (fp32 cache) or 8 (bf16, fp8), g = 16 bytes of one key chunk per position (fp32, bf16) or 8 (fp8), e = 4 / 2 / 1 bytes per element:
@@ -518,6 +518,65 @@ int idxtts_gpt_session_park(idxtts_ctx* ctx, int slot, void* dst, size_t dst_byt
  * its uninterrupted B = 1 run.  On success the slot decodes on from the next _step; src may be freed once the work queued on `stream`
  * has run (stream order). */
 int idxtts_gpt_session_resume(idxtts_ctx* ctx, int slot, const void* src, size_t src_bytes, void* workspace, void* stream);
+/* Preempt and resume, beam sessions: a GROUP steps aside (one row of a group cannot leave it, so the slot-addressed calls above keep
+ * refusing a beam session; these calls refuse every other session).  _park_group gathers everything a decoding group owns -- the step
+ * scalars of its num_beams slots (all equal), the request's idxtts_beam values, per beam the ids it has seen, its tokens and its beam
+ * score, the scorer's finished hypotheses, and the keys and values of its cached positions in every layer -- into one contiguous
+ * DEVICE buffer, the parked group, and frees the group as _evict does; _resume_group scatters it into any free group of any beam
+ * session that fits it.  One launch each on `stream`, the session's stream, between steps; the captured step and the workspace layout
+ * are untouched.  The prompt positions [0, Ps), Ps = pos - step + 1, hold the same keys and values in every row of a group (the
+ * admission writes them to all of its slots and the beam re-indexing never moves them): they are read from the group's first slot and
+ * stored ONCE, and _resume_group writes them to all num_beams rows; only the T = step - 1 generated positions [Ps, pos) are stored
+ * per beam.  Bytes moved are proportional to Ps + num_beams * T.  The rows' next decode inputs are rebuilt from each beam's last token
+ * and the mel position, as _resume does.
+ * Determinism: a group parked and resumed any number of times, into any groups, returns bit for bit the codes of its uninterrupted
+ * run; every other request's codes are untouched.
+ * The parked group: idxtts_park_group_header, then segments that each start 16-byte aligned, padding written as zero, and so are the
+ * tails of each token row behind its length and the hypothesis rows behind hyp_n: a parked group is a function of the request's state
+ * alone, byte for byte.  With pad16, V, C, g, e as for a parked row, nb = num_beams, and
+ *   kv(n) = C * pad16(n * g) + n * 64 * e + (fp8 ? 2 * pad16(4 * n) : 0)
+ * the bytes of n positions of one (layer, head) -- C key runs, the value run, fp8 only: key scales, value scales:
+ *   [header 128] [seen: nb x pad16(V)] [tokens int32: nb x pad16(4 * step)] [beam scores fp32: pad16(4 * nb)]
+ *   [hyp_worst fp64: 16] [hypothesis scores fp64: pad16(8 * nb)] [hypothesis lengths int32: pad16(4 * nb)]
+ *   [hypothesis tokens int32: nb x pad16(4 * step), the scorer's list in its own order]
+ *   then for every layer, for every head:  kv(Ps) of the shared positions | for every beam: kv(T) of its generated positions
+ *   bytes = 128 + nb * pad16(V) + 2 * nb * pad16(4 * step) + 16 + pad16(8 * nb) + 2 * pad16(4 * nb)
+ *           + layers * heads * (kv(Ps) + nb * kv(T))
+ * exp_noise travels as the caller's pointer, under the same lifetime rule as a parked row's. */
+#define IDXTTS_PARK_GROUP_MAGIC 0x4b524742u      /* "BGRK" */
+#define IDXTTS_PARK_GROUP_VERSION 1
+typedef struct idxtts_park_group_header {      /* 128 bytes */
+  unsigned magic, version;
+  int layers, heads, model_dim, number_mel_codes;      /* the model the group belongs to */
+  int slots, num_beams, kv_format, gemm_mode;          /* of the session it left */
+  int pos, mel_pos, step, max_step;                    /* keys cached, mel position, tokens per beam, the request's cap */
+  int do_sample; float temperature; int top_k; float top_p;      /* the request's idxtts_beam values */
+  double length_penalty;
+  int early_stopping;
+  int batch_invariant;                                 /* 1 = parked in the batch-invariant mode */
+  unsigned long long seed;
+  unsigned long long exp_noise;                        /* device pointer, or 0 */
+  int hyp_n, done;                                     /* finished hypotheses the scorer holds (0 .. num_beams); its done flag */
+  unsigned long long bytes;                            /* the whole parked group, header included */
+  int reserved[2];                                     /* zero */
+} idxtts_park_group_header;
+/* Exact size of the parked group now (one small device-to-host read of its state); 0 with idxtts_last_error set when the group cannot
+ * be parked (see _park_group).  group: 0 .. slots / num_beams - 1, as in _admit_beam. */
+size_t idxtts_gpt_session_park_group_bytes(idxtts_ctx* ctx, int group, void* workspace, void* stream);
+/* group must hold a request that is still decoding: one that has ended is to be read (_read).  dst: device, 16-byte aligned, dst_bytes
+ * >= _park_group_bytes.  Sets *written (host, may be NULL) and frees the group: admissible in the next call, never reported by a later
+ * _step.  Refused, before anything changes: a greedy or sampled session, a group that is free, out of range or has ended, dst_bytes
+ * too small. */
+int idxtts_gpt_session_park_group(idxtts_ctx* ctx, int group, void* dst, size_t dst_bytes, size_t* written, void* workspace,
+                                  void* stream);
+/* src: a parked group in device memory (16-byte aligned), src_bytes of it.  Refused, before anything changes: a greedy or sampled
+ * session, a bad magic (a parked row's included) or version, another model's dimensions, a session with another num_beams, KV format
+ * or GEMM mode, or other slots (seeded draws index with slots / num_beams, the key split and the GEMV follow the row count) unless
+ * both sides are in the batch-invariant mode, a batch-invariant flag that differs from the session's, a cap above the session's
+ * max_new_tokens, pos + (max_step - step) + 1 beyond the session's cache length, a group that is busy or out of range, src_bytes
+ * shorter than the header says.  On success the group decodes on from the next _step; src may be freed once the work queued on
+ * `stream` has run (stream order). */
+int idxtts_gpt_session_resume_group(idxtts_ctx* ctx, int group, const void* src, size_t src_bytes, void* workspace, void* stream);
 /* Forgets the session on this workspace (and its captured step); the caller may then free or reuse the workspace. */
 int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace);
 /* Latent pass: full causal forward over emb [B][S][d]; latent[b][i] = final_norm(ln_f(h[b][mel_start + i])), i < M.

@@ -78,4 +78,48 @@ int beam_reorder_forward(const BeamState& s, hipStream_t st);
 int beam_session_reset(const BeamState& s, int start_token, float* x_last, const float* x, int S, const int* P, const int* cap, int n,
                        hipStream_t st);
 
+// Preempt and resume of a beam group (idxtts.h "Preempt and resume, beam sessions"): the byte layout of a parked group, from the
+// header's fields alone.  The KV part of a (layer, head) is a parked row's for the Ps = pos - step + 1 shared positions (ParkLayout of
+// Ps: sh), then one for the T = step - 1 generated positions of every beam (ParkLayout of T: pb).
+struct ParkGroupLayout {
+  ParkLayout sh, pb;
+  int Ps = 0, T = 0;
+  size_t seen_row = 0, tok_row = 0;      // padded bytes of one seen row, of one token row (seq and hypotheses alike)
+  size_t off_seen = 0, off_seq = 0, off_scores = 0, off_worst = 0, off_hscore = 0, off_hlen = 0, off_hseq = 0, off_kv = 0;
+  size_t per_head = 0, bytes = 0;
+};
+__host__ __device__ static inline ParkGroupLayout park_group_layout(int kv_fmt, int layers, int heads, int V, int nb, int pos, int step) {
+  ParkGroupLayout l;
+  l.Ps = pos - step + 1; l.T = step - 1;
+  l.sh = park_layout(kv_fmt, 1, 1, V, l.Ps, step);
+  l.pb = park_layout(kv_fmt, 1, 1, V, l.T, step);
+  l.seen_row = park_pad16((size_t)V); l.tok_row = park_pad16((size_t)step * 4);
+  l.off_seen = sizeof(idxtts_park_group_header);
+  l.off_seq = l.off_seen + nb * l.seen_row;
+  l.off_scores = l.off_seq + nb * l.tok_row;
+  l.off_worst = l.off_scores + park_pad16((size_t)nb * 4);
+  l.off_hscore = l.off_worst + 16;
+  l.off_hlen = l.off_hscore + park_pad16((size_t)nb * 8);
+  l.off_hseq = l.off_hlen + park_pad16((size_t)nb * 4);
+  l.off_kv = l.off_hseq + nb * l.tok_row;
+  l.per_head = l.sh.per_head + nb * l.pb.per_head;
+  l.bytes = l.off_kv + (size_t)layers * heads * l.per_head;
+  return l;
+}
+static_assert(sizeof(idxtts_park_group_header) == 128, "parked-group header");
+struct ParkGroupArgs {
+  idxtts_park_group_header hdr;  // by value: park writes it in front of the group, resume restores the group from it (checked on the host)
+  char* blob = nullptr;          // the parked group (16-byte aligned): written by park, read by resume
+  char* kcache = nullptr; char* vcache = nullptr; float* kscale = nullptr; float* vscale = nullptr;   // layer 0 of the session's cache
+  size_t layer_bytes = 0, layer_scales = 0;      // one layer of kcache / vcache in bytes, of kscale / vscale in floats
+  int group = 0, Smax = 0, B = 0;                // B: the session's slots
+  BeamState bs;                  // the session's beam buffers (slots, seen, seq, cur_tok, beam scores, hypotheses)
+  SlotBeam* group_tab = nullptr; // the session's SlotBeam table (resume rewrites the group's entry)
+  SampleArgs::Embed embed;       // resume: where the rows' next inputs go (the session tails' block)
+};
+// One launch each, between steps on the session's stream.  park: group -> blob, then live = 0 on its slots.  resume: blob -> group,
+// live = 1 with the header's scalars, the device SlotBeam entry, and every row's next input as the tails write it.
+int session_park_group(const ParkGroupArgs& a, hipStream_t stream);
+int session_resume_group(const ParkGroupArgs& a, hipStream_t stream);
+
 }  // namespace idxtts

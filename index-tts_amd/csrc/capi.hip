@@ -572,6 +572,29 @@ int idxtts_gpt_session_resume(idxtts_ctx* ctx, int slot, const void* src, size_t
   API_END
 }
 
+size_t idxtts_gpt_session_park_group_bytes(idxtts_ctx* ctx, int group, void* workspace, void* stream) {
+  auto* m = ctx && ctx->finalized ? dynamic_cast<GPTModel*>(ctx->model.get()) : nullptr;
+  if (!m) { set_error("not a finalized GPT context"); return 0; }
+  try {
+    return m->session_park_group_bytes(workspace, group, static_cast<hipStream_t>(stream));
+  } catch (const std::exception& e) { set_error(std::string("exception: ") + e.what()); return 0; }
+}
+
+int idxtts_gpt_session_park_group(idxtts_ctx* ctx, int group, void* dst, size_t dst_bytes, size_t* written, void* workspace,
+                                  void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_park_group(workspace, group, dst, dst_bytes, written, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_resume_group(idxtts_ctx* ctx, int group, const void* src, size_t src_bytes, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_resume_group(workspace, group, src, src_bytes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_gpt_session_release(idxtts_ctx* ctx, void* workspace) {
   API_BEGIN
   GPT_MODEL(ctx);

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "beam.h"
 #include "decode.h"
 #include "device_util.h"
 #include "kv_fp8.h"
@@ -1284,6 +1285,174 @@ static int park_launch(const ParkArgs& a, bool resume, hipStream_t stream) {
 
 int session_park_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, false, stream); }
 int session_resume_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, true, stream); }
+
+// ---- preempt and resume of a beam group (beam.h ParkGroupArgs, idxtts.h "Preempt and resume, beam sessions") ----
+// n bytes (a multiple of sizeof(U)) in units of U, for a run whose cache side starts in the middle of a cache row and is only
+// sizeof(U)-aligned: consecutive lanes on consecutive units.  PAD as in park_copy_run: dst is a 16-byte aligned segment of the parked
+// group and is written up to pad16(n) with zeros behind the data; else exactly n bytes are written.
+template <class U, bool PAD>
+__device__ __forceinline__ void park_copy_units(char* dst, const char* src, const size_t n, const int tid) {
+  const size_t nu = n / sizeof(U), nt = PAD ? park_pad16(n) / sizeof(U) : nu;
+  const U* s = reinterpret_cast<const U*>(src);
+  U* d = reinterpret_cast<U*>(dst);
+  for (size_t i = tid; i < nt; i += PARK_NT) d[i] = i < nu ? s[i] : U{};
+}
+
+// Grid (runs + 1, heads, layers), runs as in session_park_kernel: workgroup (r, h, l) moves run r -- a key chunk, a piece of the value
+// run or a scale run, split as the row kernel splits them -- of every part of (l, h) in turn: part 0 is the shared run, positions
+// [0, Ps), read from the group's first slot and on resume written to all nb rows, and part 1 + j the positions [Ps, pos) of beam j.
+// So every workgroup of one kind moves the same Ps + nb * T positions' worth, and there are no more workgroups than a row's launch
+// has (one per part would be nb + 1 times as many of a few KB each, and the launch would be bound by the workgroup dispatch rate,
+// not by bytes: measured, profiles/README.md "Preemption").  The per-beam runs start at position Ps inside a cache row: values and
+// 16-byte key granules stay 16-byte aligned, fp8 key granules are 8-byte aligned when Ps is odd and scales 4-byte aligned unless
+// Ps % 4 == 0, so the copy is chosen from the cache address.  Workgroup (runs, 0, 0) moves the small state and on resume writes the
+// rows' next inputs.
+template <bool RESUME>
+__global__ __launch_bounds__(PARK_NT) void session_park_group_kernel(const ParkGroupArgs p) {
+  const int tid = threadIdx.x, r = blockIdx.x, h = blockIdx.y, H = gridDim.y;
+  const idxtts_park_group_header& hd = p.hdr;
+  const int nb = hd.num_beams, l = blockIdx.z, slot0 = p.group * nb;
+  const ParkGroupLayout lay = park_group_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, nb, hd.pos, hd.step);
+  const int C = lay.sh.chunks, runs = 2 * C + (hd.kv_format == 2 ? 2 : 0);
+  auto move = [&](char* cache, char* seg, size_t n) {      // one run between the cache and its segment of the parked group
+    const unsigned mis = (unsigned)((uintptr_t)cache & 15);
+    if (mis == 0) {
+      if (RESUME) park_copy_run<false>(cache, seg, n, tid);
+      else park_copy_run<true>(seg, cache, n, tid);
+    } else if ((mis & 7) == 0 && (n & 7) == 0) {
+      if (RESUME) park_copy_units<uint2, false>(cache, seg, n, tid);
+      else park_copy_units<uint2, true>(seg, cache, n, tid);
+    } else {
+      if (RESUME) park_copy_units<unsigned, false>(cache, seg, n, tid);
+      else park_copy_units<unsigned, true>(seg, cache, n, tid);
+    }
+  };
+  if (r < runs) {
+    for (int part = 0; part <= nb; ++part) {
+      const ParkLayout& pl = part ? lay.pb : lay.sh;
+      const int first = part ? lay.Ps : 0, npos = part ? lay.T : lay.Ps;
+      if (npos <= 0) continue;
+      char* const seg = p.blob + lay.off_kv + ((size_t)l * H + h) * lay.per_head + (part ? lay.sh.per_head + (size_t)(part - 1) * lay.pb.per_head : 0);
+      const int j0 = part ? part - 1 : 0, j1 = part ? part : (RESUME ? nb : 1);      // the cache rows this segment belongs to
+      for (int j = j0; j < j1; ++j) {
+        const size_t sh = (size_t)(slot0 + j) * H + h;
+        if (r < C) {
+          move(p.kcache + l * p.layer_bytes + ((sh * C + r) * p.Smax + first) * pl.gran, seg + r * pl.krun, (size_t)npos * pl.gran);
+        } else if (r < 2 * C) {
+          const size_t nv = pl.vrun >> 4, v0 = nv * (r - C) / C, v1 = nv * (r - C + 1) / C;
+          move(p.vcache + l * p.layer_bytes + (sh * p.Smax + first) * 64 * pl.elem + (v0 << 4), seg + C * pl.krun + (v0 << 4), (v1 - v0) << 4);
+        } else {
+          float* const sc = (r == 2 * C ? p.kscale : p.vscale) + l * p.layer_scales + sh * p.Smax + first;
+          move(reinterpret_cast<char*>(sc), seg + C * pl.krun + pl.vrun + (r - 2 * C) * pl.srun, (size_t)npos * 4);
+        }
+      }
+    }
+    return;
+  }
+  if (h || l) return;
+  const BeamState& b = p.bs;
+  const int V = hd.number_mel_codes, step = hd.step, g = p.group, ld = b.seq_ld, hn = hd.hyp_n;
+  const size_t o = (size_t)g * (BEAM_MAX + 1);
+  const int nd = (int)(lay.seen_row >> 2), nt = (int)(lay.tok_row >> 2);
+  const int nsc = (int)(park_pad16((size_t)nb * 4) >> 2), nhs = (int)(park_pad16((size_t)nb * 8) >> 3);
+  float* const bscore = reinterpret_cast<float*>(p.blob + lay.off_scores);
+  double* const bworst = reinterpret_cast<double*>(p.blob + lay.off_worst);
+  double* const bhscore = reinterpret_cast<double*>(p.blob + lay.off_hscore);
+  int* const bhlen = reinterpret_cast<int*>(p.blob + lay.off_hlen);
+  for (int j = 0; j < nb; ++j) {
+    unsigned char* const seen = b.seen + (size_t)(slot0 + j) * V;      // (a row of seen is only byte aligned)
+    int* const seq = b.seq + (size_t)(slot0 + j) * ld;
+    unsigned* const bseen = reinterpret_cast<unsigned*>(p.blob + lay.off_seen + j * lay.seen_row);
+    int* const bseq = reinterpret_cast<int*>(p.blob + lay.off_seq + j * lay.tok_row);
+    if (!RESUME) {
+      for (int i = tid; i < nd; i += PARK_NT) {
+        unsigned w = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * i + k < V) w |= (unsigned)seen[4 * i + k] << (8 * k);
+        bseen[i] = w;
+      }
+      for (int i = tid; i < nt; i += PARK_NT) bseq[i] = i < step ? seq[i] : 0;
+    } else {
+      for (int i = tid; i < nd; i += PARK_NT) {
+        const unsigned w = bseen[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * i + k < V) seen[4 * i + k] = (unsigned char)(w >> (8 * k));
+      }
+      for (int i = tid; i < step; i += PARK_NT) seq[i] = bseq[i];
+      // the beam's last token, kept inside the embedding table whatever the bytes say (the header is checked on the host, the body is not)
+      const int tok = min(max(bseq[step - 1], 0), V - 1);
+      write_next_input<PARK_NT>(p.embed, p.B, slot0 + j, tok, hd.mel_pos, tid);
+      if (tid == 0) {
+        b.cur_tok[slot0 + j] = tok;
+        b.slots[slot0 + j] = SlotState{hd.pos, hd.mel_pos, hd.step, hd.max_step, 1};
+      }
+    }
+  }
+  // the scorer's list in its own order: hypothesis q of the parked group is row q, whatever physical row of hyp_seq held it
+  for (int q = 0; q < nb; ++q) {
+    int* const bh = reinterpret_cast<int*>(p.blob + lay.off_hseq + q * lay.tok_row);
+    if (!RESUME) {
+      const int len = q < hn ? min(max(b.hyp_len[o + q], 0), step) : 0;
+      const int* const src = b.hyp_seq + (o + (q < hn ? min(max(b.hyp_slot[o + q], 0), BEAM_MAX) : 0)) * ld;
+      for (int i = tid; i < nt; i += PARK_NT) bh[i] = i < len ? src[i] : 0;
+    } else if (q < hn) {
+      int* const dst = b.hyp_seq + (o + q) * ld;
+      for (int i = tid; i < step; i += PARK_NT) dst[i] = bh[i];
+    }
+  }
+  if (!RESUME) {
+    for (int i = tid; i < nsc; i += PARK_NT) bscore[i] = i < nb ? b.beam_scores[slot0 + i] : 0.f;
+    for (int i = tid; i < nhs; i += PARK_NT) bhscore[i] = i < hn ? b.hyp_score[o + i] : 0.0;
+    for (int i = tid; i < nsc; i += PARK_NT) bhlen[i] = i < hn ? min(max(b.hyp_len[o + i], 0), step) : 0;
+    if (tid == 0) {
+      bworst[0] = b.hyp_worst[g]; bworst[1] = 0.0;
+      *reinterpret_cast<idxtts_park_group_header*>(p.blob) = hd;
+    }
+    if (tid < nb) b.slots[slot0 + tid].live = 0;      // the group is free, as session_end_slots leaves an evicted one
+  } else {
+    if (tid < nb) {
+      b.beam_scores[slot0 + tid] = bscore[tid];
+      b.hyp_score[o + tid] = bhscore[tid];
+      b.hyp_len[o + tid] = min(max(bhlen[tid], 0), step);
+      b.hyp_slot[o + tid] = tid;
+    }
+    if (tid == 0) {
+      b.hyp_n[g] = hn; b.hyp_worst[g] = bworst[0]; b.done[g] = hd.done;
+      p.group_tab[g] = SlotBeam{hd.do_sample, hd.temperature, hd.top_k, hd.top_p, hd.length_penalty, hd.early_stopping, hd.seed,
+                                reinterpret_cast<const float*>(hd.exp_noise)};
+    }
+  }
+}
+
+static int park_group_launch(const ParkGroupArgs& a, bool resume, hipStream_t stream) {
+  const idxtts_park_group_header& hd = a.hdr;
+  const BeamState& b = a.bs;
+  IDX_CHECK(a.blob && a.kcache && a.vcache && a.group_tab && b.slots && b.seen && b.seq && b.cur_tok && b.beam_scores && b.hyp_score &&
+            b.hyp_len && b.hyp_slot && b.hyp_seq && b.hyp_n && b.hyp_worst && b.done, "null pointer");
+  IDX_CHECK(hd.kv_format >= 0 && hd.kv_format <= 2 && (hd.kv_format != 2 || (a.kscale && a.vscale)), "KV format");
+  IDX_CHECK(hd.num_beams >= 2 && hd.num_beams <= BEAM_MAX && hd.num_beams == b.nb, "num_beams");
+  IDX_CHECK(hd.layers >= 1 && hd.layers <= 65535 && hd.heads >= 1 && hd.heads <= 65535, "shape");
+  IDX_CHECK(a.group >= 0 && (a.group + 1) * hd.num_beams <= a.B && hd.step >= 1 && hd.step <= b.seq_ld && hd.pos >= hd.step &&
+            hd.pos <= a.Smax && hd.hyp_n >= 0 && hd.hyp_n <= hd.num_beams, "group state out of range");
+  IDX_CHECK(a.Smax % 4 == 0 && a.layer_bytes % 16 == 0 && a.layer_scales % 4 == 0, "cache rows must start 16-byte aligned");
+  IDX_CHECK(((uintptr_t)a.blob | (uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.kscale | (uintptr_t)a.vscale) % 16 == 0,
+            "the parked group and the caches must be 16-byte aligned");
+  IDX_CHECK(!resume || ((a.embed.x_row && a.embed.x_stats) || a.embed.x_frag), "resume needs the step's input buffers");
+  const ParkGroupLayout lay = park_group_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.num_beams, hd.pos, hd.step);
+  const int runs = 2 * lay.sh.chunks + (hd.kv_format == 2 ? 2 : 0);
+  static const int cat_p = prof_register("session_park_group_kernel"), cat_r = prof_register("session_resume_group_kernel");
+  ProfScope prof(resume ? cat_r : cat_p, stream, 0.0, 2.0 * (double)lay.bytes);
+  const dim3 grid(runs + 1, hd.heads, hd.layers);
+  if (resume) hipLaunchKernelGGL(session_park_group_kernel<true>, grid, dim3(PARK_NT), 0, stream, a);
+  else hipLaunchKernelGGL(session_park_group_kernel<false>, grid, dim3(PARK_NT), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+int session_park_group(const ParkGroupArgs& a, hipStream_t stream) { return park_group_launch(a, false, stream); }
+int session_resume_group(const ParkGroupArgs& a, hipStream_t stream) { return park_group_launch(a, true, stream); }
 
 // out[r][:] = sum over the tables t with idx[t][r] >= 0 of table[t][idx[t][r]][:]
 __global__ __launch_bounds__(256) void gather_sum_rows_kernel(const GatherArgs p) {

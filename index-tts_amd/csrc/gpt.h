@@ -220,6 +220,13 @@ struct GPTModel : ModelBase {
   size_t session_park_bytes(void* ws, int slot, hipStream_t st);
   int session_park(void* ws, int slot, void* dst, size_t dst_bytes, size_t* written, hipStream_t st);
   int session_resume(void* ws, int slot, const void* src, size_t src_bytes, hipStream_t st);
+  // The same for a beam session's group (idxtts.h "Preempt and resume, beam sessions"; gpt_beam.hip): park also clears the group's
+  // busy flags, resume restores them and the host image of the group's SlotBeam entry, which every admission uploads whole.
+  ParkGroupArgs park_group_args(const Session& s, const SessionBuffers& sb, int group) const;      // everything but hdr and blob
+  int session_park_group_header(void* ws, int group, idxtts_park_group_header* hdr, hipStream_t st);
+  size_t session_park_group_bytes(void* ws, int group, hipStream_t st);
+  int session_park_group(void* ws, int group, void* dst, size_t dst_bytes, size_t* written, hipStream_t st);
+  int session_resume_group(void* ws, int group, const void* src, size_t src_bytes, hipStream_t st);
   int session_release(void* ws);
   int embed(float* out, int rows, const int* text_ids, const int* text_pos_idx, const int* mel_ids, const int* mel_pos_idx,
             const float* extra, const int* extra_idx, hipStream_t st);

@@ -928,7 +928,7 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0, "a beam session's groups cannot be parked (the scorer state of a group is not saved)");
+  IDX_CHECK(s.num_beams == 0, "one row of a beam group cannot be parked: park the group (idxtts_gpt_session_park_group)");
   IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
   IDX_CHECK(s.busy[slot], "slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
@@ -980,7 +980,7 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0, "a beam session's groups cannot be parked or resumed (the scorer state of a group is not saved)");
+  IDX_CHECK(s.num_beams == 0, "a beam session resumes whole groups (idxtts_gpt_session_resume_group), not rows");
   IDX_CHECK(src, "null pointer");
   IDX_CHECK((uintptr_t)src % 16 == 0, "the parked row must be 16-byte aligned");
   IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");

@@ -240,4 +240,122 @@ int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, 
   return 0;
 }
 
+// ---- preempt and resume of a group (idxtts.h "Preempt and resume, beam sessions"; kernel in decode.hip) ----
+ParkGroupArgs GPTModel::park_group_args(const Session& s, const SessionBuffers& sb, int group) const {
+  const Buffers& w = sb.w;
+  ParkGroupArgs a;
+  a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
+  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
+  a.group = group; a.Smax = w.Smax; a.B = s.slots; a.bs = w.beam; a.group_tab = sb.beam;
+  a.embed = tail_embed(w, use_pl(s.slots));
+  return a;
+}
+
+int GPTModel::session_park_group_header(void* ws, int group, idxtts_park_group_header* hdr, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams > 0, "_park_group needs a beam session: a greedy or sampled session parks rows (idxtts_gpt_session_park)");
+  const int nb = s.num_beams, G = s.slots / nb;
+  IDX_CHECK(group >= 0 && group < G, "group out of range");
+  IDX_CHECK(s.busy[group * nb], "group holds no request");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
+  SlotState hs;
+  int hyp_n = 0, done = 0;
+  IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + group * nb, sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(&hyp_n, sb.bb.hyp_n + group, sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipMemcpyAsync(&done, sb.bb.done + group, sizeof(int), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(hs.live, "group has ended: read it, a request that is over cannot be parked");
+  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.max_new && hs.pos >= hs.step && hs.pos < sb.w.Smax &&
+            hs.mel_pos == hs.step + 1, "group state corrupt");
+  IDX_CHECK(hyp_n >= 0 && hyp_n <= nb && (done == 0 || done == 1), "group state corrupt");
+  const SlotBeam& e = s.beam[group];
+  idxtts_park_group_header h{};
+  h.magic = IDXTTS_PARK_GROUP_MAGIC; h.version = IDXTTS_PARK_GROUP_VERSION;
+  h.layers = cfg.layers; h.heads = cfg.heads; h.model_dim = cfg.model_dim; h.number_mel_codes = cfg.number_mel_codes;
+  h.slots = s.slots; h.num_beams = nb; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode;
+  h.pos = hs.pos; h.mel_pos = hs.mel_pos; h.step = hs.step; h.max_step = hs.max_step;
+  h.do_sample = e.do_sample; h.temperature = e.temperature; h.top_k = e.top_k; h.top_p = e.top_p;
+  h.length_penalty = e.length_penalty; h.early_stopping = e.early_stopping; h.batch_invariant = s.invariant;
+  h.seed = e.seed; h.exp_noise = (unsigned long long)(uintptr_t)e.exp_noise;
+  h.hyp_n = hyp_n; h.done = done;
+  h.bytes = park_group_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, nb, h.pos, h.step).bytes;
+  *hdr = h;
+  return 0;
+}
+
+size_t GPTModel::session_park_group_bytes(void* ws, int group, hipStream_t st) {
+  idxtts_park_group_header h;
+  return session_park_group_header(ws, group, &h, st) ? 0 : (size_t)h.bytes;
+}
+
+int GPTModel::session_park_group(void* ws, int group, void* dst, size_t dst_bytes, size_t* written, hipStream_t st) {
+  IDX_CHECK(dst, "null pointer");
+  IDX_CHECK((uintptr_t)dst % 16 == 0, "the parked group must be 16-byte aligned");
+  idxtts_park_group_header h;
+  if (session_park_group_header(ws, group, &h, st)) return 1;
+  IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked group (idxtts_gpt_session_park_group_bytes)");
+  Session& s = *find_session(ws);
+  const int nb = s.num_beams;
+  ParkGroupArgs a = park_group_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb), group);
+  a.hdr = h; a.blob = static_cast<char*>(dst);
+  if (idxtts::session_park_group(a, st)) return 1;
+  // the host image too: the next admission uploads the whole SlotBeam table, and a free group carries no request's parameters
+  s.beam[group] = SlotBeam{0, 1.0f, 0, 1.0f, 0.0, 0, 0, nullptr};
+  for (int j = 0; j < nb; ++j) s.busy[group * nb + j] = 0;
+  if (written) *written = (size_t)h.bytes;
+  return 0;
+}
+
+int GPTModel::session_resume_group(void* ws, int group, const void* src, size_t src_bytes, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams > 0, "_resume_group needs a beam session: a greedy or sampled session resumes rows (idxtts_gpt_session_resume)");
+  const int nb = s.num_beams, G = s.slots / nb;
+  IDX_CHECK(src, "null pointer");
+  IDX_CHECK((uintptr_t)src % 16 == 0, "the parked group must be 16-byte aligned");
+  IDX_CHECK(group >= 0 && group < G, "group out of range");
+  IDX_CHECK(!s.busy[group * nb], "group is not free");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
+  IDX_CHECK(src_bytes >= sizeof(idxtts_park_group_header), "parked group shorter than its header");
+  idxtts_park_group_header h;
+  IDX_HIP(hipMemcpyAsync(&h, src, sizeof(h), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(h.magic == IDXTTS_PARK_GROUP_MAGIC, "not a parked group (magic; a parked row goes to idxtts_gpt_session_resume)");
+  IDX_CHECK(h.version == IDXTTS_PARK_GROUP_VERSION, "parked group of another format version");
+  IDX_CHECK(h.layers == cfg.layers && h.heads == cfg.heads && h.model_dim == cfg.model_dim && h.number_mel_codes == cfg.number_mel_codes,
+            "parked group of another model (dimensions)");
+  IDX_CHECK(h.num_beams == nb, "parked group of another num_beams");
+  IDX_CHECK(h.batch_invariant == 0 || h.batch_invariant == 1, "parked group's mode field is corrupt");
+  IDX_CHECK(h.batch_invariant == s.invariant, "parked group and session differ in the batch-invariant mode");
+  // seeded draws index with slots / num_beams, the key split and the GEMV follow the row count; in the mode none of them does
+  IDX_CHECK(s.invariant || h.slots == s.slots, "parked group of a session with a different number of slots");
+  IDX_CHECK(h.kv_format == s.kv_fmt, "parked group of another KV format");
+  IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked group of another GEMM mode");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
+  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
+  IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= h.step, "parked group's step scalars are corrupt");
+  IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
+  IDX_CHECK(h.hyp_n >= 0 && h.hyp_n <= nb && (h.done == 0 || h.done == 1), "parked group's scorer fields are corrupt");
+  idxtts_beam r{nb, h.do_sample, h.temperature, h.top_k, h.top_p, (float)h.length_penalty, h.early_stopping,
+                reinterpret_cast<const float*>((uintptr_t)h.exp_noise), h.seed};
+  IDX_CHECK(h.do_sample == 0 || h.do_sample == 1, "parked group's beam parameters are corrupt");
+  if (check_beam(r)) return 1;
+  IDX_CHECK(h.bytes == park_group_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, nb, h.pos, h.step).bytes,
+            "parked group's size field is corrupt");
+  IDX_CHECK(src_bytes >= h.bytes, "parked group is truncated");
+  ParkGroupArgs a = park_group_args(s, sb, group);
+  a.hdr = h; a.blob = const_cast<char*>(static_cast<const char*>(src));
+  if (idxtts::session_resume_group(a, st)) return 1;
+  s.beam[group] = SlotBeam{h.do_sample, h.temperature, h.top_k, h.top_p, h.length_penalty, h.early_stopping, h.seed,
+                           reinterpret_cast<const float*>((uintptr_t)h.exp_noise)};
+  for (int j = 0; j < nb; ++j) s.busy[group * nb + j] = 1;
+  return 0;
+}
+
 }  // namespace idxtts

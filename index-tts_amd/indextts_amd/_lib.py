@@ -28,6 +28,7 @@ SYMBOLS = [
     "idxtts_gpt_session_admit_sampled", "idxtts_gpt_session_workspace_bytes_beam", "idxtts_gpt_session_init_beam",
     "idxtts_gpt_session_admit_beam", "idxtts_gpt_session_evict", "idxtts_gpt_session_stop",
     "idxtts_gpt_session_park_bytes", "idxtts_gpt_session_park", "idxtts_gpt_session_resume",
+    "idxtts_gpt_session_park_group_bytes", "idxtts_gpt_session_park_group", "idxtts_gpt_session_resume_group",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
@@ -69,7 +70,19 @@ class ParkHeaderC(ctypes.Structure):         # idxtts_park_header (include/idxtt
                    ("exp_noise", ctypes.c_ulonglong), ("bytes", ctypes.c_ulonglong), ("reserved", c_int * 8)])
 
 
-class CondConfigC(ctypes.Structure):         # idxtts_cond_config (include/idxtts.h)
+class ParkGroupHeaderC(ctypes.Structure):    # idxtts_park_group_header (include/idxtts.h): the first 128 bytes of a parked beam group
+    _fields_ = ([("magic", ctypes.c_uint), ("version", ctypes.c_uint)]
+                + [(n, c_int) for n in ("layers", "heads", "model_dim", "number_mel_codes", "slots", "num_beams", "kv_format", "gemm_mode",
+                                        "pos", "mel_pos", "step", "max_step", "do_sample")]
+                + [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("length_penalty", ctypes.c_double),
+                   ("early_stopping", c_int), ("batch_invariant", c_int), ("seed", ctypes.c_ulonglong), ("exp_noise", ctypes.c_ulonglong),
+                   ("hyp_n", c_int), ("done", c_int), ("bytes", ctypes.c_ulonglong), ("reserved", c_int * 2)])
+
+
+PARK_MAGIC, PARK_GROUP_MAGIC = 0x4B525049, 0x4B524742      # IDXTTS_PARK_MAGIC, IDXTTS_PARK_GROUP_MAGIC
+
+
+class CondConfigC(ctypes.Structure):       # idxtts_cond_config (include/idxtts.h)
     _fields_ = [(n, c_int) for n in ("input_size", "output_size", "linear_units", "attention_heads", "num_blocks", "cnn_kernel",
                                      "perceiver_dim", "num_latents", "perceiver_depth", "perceiver_dim_head", "perceiver_mult",
                                      "emotion", "model_dim")]
@@ -207,6 +220,10 @@ def load() -> ctypes.CDLL:
     lib.idxtts_gpt_session_park_bytes.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
     lib.idxtts_gpt_session_park.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t), c_void_p, c_void_p]
     lib.idxtts_gpt_session_resume.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_park_group_bytes.restype = c_size_t
+    lib.idxtts_gpt_session_park_group_bytes.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_park_group.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_size_t), c_void_p, c_void_p]
+    lib.idxtts_gpt_session_resume_group.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
     lib.idxtts_gpt_latent.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_s2mel_create.argtypes = [POINTER(S2MelConfigC), POINTER(c_void_p)]
     lib.idxtts_s2mel_cond_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]

@@ -544,6 +544,17 @@ class ParkedRow:
         return self
 
 
+class ParkedGroup(ParkedRow):
+    """A beam group that stepped aside (BeamDecodeSession.park_group): a ParkedRow whose bytes are a parked group (include/idxtts.h
+    "Preempt and resume, beam sessions").  `n_codes` is the tokens each beam holds, `hyp_n` the finished hypotheses the scorer carried,
+    `header` a copy of the blob's idxtts_park_group_header.  BeamDecodeSession.resume_group takes it once; DecodeSession.resume
+    refuses it, as resume_group refuses a ParkedRow."""
+
+    def __init__(self, blob: torch.Tensor, header, noise, stream):
+        super().__init__(blob, header.step, header.max_step, noise, stream)
+        self.header, self.num_beams, self.hyp_n = header, int(header.num_beams), int(header.hyp_n)
+
+
 class _Session:
     """What DecodeSession and BeamDecodeSession share: the stream, the workspace and its native session, prompt staging, the step loop
     and the release.  Subclasses set the slot bookkeeping (_busy, _done, _noise) and _unit (slots per request)."""
@@ -823,8 +834,8 @@ class DecodeSession(_Session):
         slots, KV format and GEMM mode whose max_new and cache length hold the rest of the request.  In the batch-invariant mode the
         slot counts need not match (both sessions must be in the mode; a row parked with the mode off is refused there, and the
         reverse).  A refusal raises and changes nothing; a ParkedRow is resumed once."""
-        if not isinstance(parked, ParkedRow):
-            raise TypeError("resume() takes a ParkedRow")
+        if not isinstance(parked, ParkedRow) or isinstance(parked, ParkedGroup):
+            raise TypeError("resume() takes a ParkedRow (a ParkedGroup goes to BeamDecodeSession.resume_group)")
         parked._check()
         if slot is None:
             free = self.free_slots
@@ -859,7 +870,9 @@ class BeamDecodeSession(_Session):
         their group ids;
       * step(n) runs n decode steps of every live group and returns the groups whose request has finished -- its scorer is done
         (BeamHypotheses.is_done with the request's early_stopping / length_penalty) or it reached its cap;
-      * take(group) returns that request's codes (the best hypothesis, then the stop token if it fits under the cap) and frees it.
+      * take(group) returns that request's codes (the best hypothesis, then the stop token if it fits under the cap) and frees it;
+      * park_group(group) takes a decoding request out with everything it has computed and frees its group, resume_group(parked)
+        puts it into a free group of this or another session of the same shape: it goes on to bit-identical codes.
     `beam`: one dict, or one per request, with keys do_sample, temperature, top_k, top_p, length_penalty, early_stopping (defaults:
     generate_beam's) and `seed` or `exp_noise` [cap, num_beams * V] (neither: a seed drawn from torch's global RNG).
     Determinism: a request's codes equal, bit for bit, row 0 of UnifiedVoice.generate_beam with the same parameters and repetition penalty
@@ -956,7 +969,69 @@ class BeamDecodeSession(_Session):
         return super().take(group)
 
     def park(self, group: int):
-        raise NotImplementedError("a beam session's groups cannot be parked: a group's scorer state (hypotheses, beam scores) is not saved")
+        raise NotImplementedError("one row of a beam group cannot leave it: park the whole group with park_group()")
 
     def resume(self, parked, group=None):
-        raise NotImplementedError("a beam session's groups cannot be parked or resumed: a group's scorer state is not saved")
+        raise NotImplementedError("a beam session resumes whole groups: resume_group() takes what park_group() returned")
+
+    def park_group(self, group: int) -> ParkedGroup:
+        """Takes the decoding request in `group` out of the session with everything it has computed -- the step state, the request's
+        beam parameters, every beam's tokens, seen ids and score, the scorer's finished hypotheses, and the cached keys and values: the
+        prompt positions once, the generated positions per beam -- and frees the group: admissible at once, never reported by step().
+        One gather launch on the session's stream.  resume_group() puts it back, into any free group of this session or of another
+        beam session of the same shape, and it goes on to produce, bit for bit, the codes of its uninterrupted run.  A group that is
+        free, has finished (take() it) or is out of range raises, nothing changes."""
+        if not isinstance(group, (int, np.integer)) or not 0 <= int(group) < self.groups or not self._busy[int(group)]:
+            raise ValueError(f"{group!r} holds no request (group ids 0 .. {self.groups - 1})")
+        group = int(group)
+        with torch.cuda.stream(self.stream):
+            need = int(self._lib.idxtts_gpt_session_park_group_bytes(self.gpt._h, group, _lib.ptr(self._ws), self._sp()))
+            if need == 0:
+                _lib.check(1)
+            blob = torch.empty(need, dtype=torch.uint8, device=self.gpt.device)
+            written = ctypes.c_size_t(0)
+            _lib.check(self._lib.idxtts_gpt_session_park_group(self.gpt._h, group, _lib.ptr(blob), need, ctypes.byref(written),
+                                                               _lib.ptr(self._ws), self._sp()))
+            hdr = _lib.ParkGroupHeaderC.from_buffer_copy(blob[: ctypes.sizeof(_lib.ParkGroupHeaderC)].cpu().numpy().tobytes())
+        assert written.value == need == hdr.bytes
+        self._busy[group] = False
+        self._done.discard(group)
+        nz = self._noise.pop(group, None)      # the draws move with the group: alive while it is parked
+        if nz is not None:
+            nz.record_stream(self.stream)
+        return ParkedGroup(blob, hdr, nz, self.stream)
+
+    def resume_group(self, parked: ParkedGroup, group=None) -> int:
+        """Puts a parked group into `group` (default: the first free group) and returns the group id; it decodes on from the next
+        step().  `parked` may live on the device or in host memory (it is staged here) and may come from another beam session of the
+        same model, slots, num_beams, KV format and GEMM mode whose max_new and cache length hold the rest of the request.  In the
+        batch-invariant mode the slot counts need not match (both sessions must be in the mode).  A refusal raises and changes nothing;
+        a ParkedGroup is resumed once."""
+        if not isinstance(parked, ParkedGroup):
+            raise TypeError("resume_group() takes a ParkedGroup (a ParkedRow goes to DecodeSession.resume)")
+        parked._check()
+        if group is None:
+            free = self.free_groups
+            if not free:
+                raise RuntimeError("no free group")
+            group = free[0]
+        if not isinstance(group, (int, np.integer)) or not 0 <= int(group) < self.groups:
+            raise ValueError(f"group {group!r} out of range (0 .. {self.groups - 1})")
+        group = int(group)
+        if self._busy[group]:
+            raise ValueError(f"group {group} is not free")
+        if parked._blob.device != self.gpt.device:
+            with torch.cuda.stream(self.stream):
+                parked.to(self.gpt.device)
+        blob = parked._blob
+        self.stream.wait_stream(parked._stream)      # the group may have been written on another session's stream
+        with torch.cuda.stream(self.stream):
+            _lib.check(self._lib.idxtts_gpt_session_resume_group(self.gpt._h, group, _lib.ptr(blob), blob.numel(), _lib.ptr(self._ws),
+                                                                 self._sp()))
+        blob.record_stream(self.stream)
+        self._busy[group] = True
+        if parked._noise is not None:
+            parked._noise.record_stream(self.stream)
+            self._noise[group] = parked._noise
+        parked._blob = parked._noise = None
+        return group

@@ -566,16 +566,22 @@ class ContinuousPipeline:
     every parked row to pinned host memory until it resumes.  A lane does not look at the other lanes' free slots before it parks.  A
     parked request that is cancelled, past its deadline or failed is dropped when next touched; a resume that fails fails that
     request only; close() drains parked rows like any other waiting work.  Strict priorities can starve: a steady stream of urgent
-    requests keeps less urgent ones waiting (or parked) for as long as it lasts -- there is no aging.  Beam pipelines do not preempt
-    (a group's scorer state is not saved).  `trace` also records ("park", t, request, utterance) and ("resume", t, request, utterance).
+    requests keeps less urgent ones waiting (or parked) for as long as it lasts -- there is no aging.  `trace` also records
+    ("park", t, request, utterance) and ("resume", t, request, utterance).
+
+    preempt_groups=True is the same for a beam pipeline (num_beams > 1; preempt=True keeps refusing one, and preempt_groups refuses
+    num_beams == 1): the unit that steps aside is a whole group (session.park_group: the request's beams, scorer state and KV -- the
+    prompt positions once, the generated ones per beam -- in a ParkedGroup; session.resume_group puts it into a free group of any
+    lane), under the same rules: strictly more urgent only, the least urgent and last admitted group first, parked groups ahead of
+    never-admitted utterances of their priority, park_to, the trace entries, cancellation, deadlines, failures and close().
 
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close; evict to cancel; park / resume to
-    preempt) replaces the HIP session (tests)."""
+    preempt; a beam pipeline's: free_groups, park_group / resume_group) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
                  session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
-                 acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device"):
+                 acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device", preempt_groups: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
@@ -600,7 +606,11 @@ class ContinuousPipeline:
             raise ValueError('park_to must be "device" or "host"')
         self.park_to = park_to
         if self.preempt and self.num_beams > 1:
-            raise ValueError("preempt=True needs num_beams == 1: a beam session's groups cannot be parked")
+            raise ValueError("preempt=True needs num_beams == 1: a beam pipeline parks whole groups (preempt_groups=True)")
+        self.preempt_groups = bool(preempt_groups)
+        if self.preempt_groups and self.num_beams == 1:
+            raise ValueError("preempt_groups=True needs num_beams > 1: a greedy or sampled pipeline parks rows (preempt=True)")
+        self._preempts = self.preempt or self.preempt_groups      # rows or groups: the scheduling is the same
         self._admitted = 0                      # admission stamps (which row of a priority was admitted last)
         if self.num_beams > 1:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
@@ -749,7 +759,7 @@ class ContinuousPipeline:
             take, victims = [], []
             free = len(self._free(sess))
             # the rows a more urgent utterance may displace, first choice first: lowest priority, among equals admitted last
-            rows = sorted(in_slot, key=lambda s: (in_slot[s][0].priority, -in_slot[s][0].stamp[in_slot[s][1]])) if self.preempt else []
+            rows = sorted(in_slot, key=lambda s: (in_slot[s][0].priority, -in_slot[s][0].stamp[in_slot[s][1]])) if self._preempts else []
             while self._waiting:
                 j = self._waiting[0][0]
                 room = len(take) < free
@@ -801,11 +811,11 @@ class ContinuousPipeline:
                     j.stamp[i] = self._admitted
 
     def _park(self, sess, in_slot, s) -> None:
-        """Parks the row in slot s and queues it for whichever lane next has room; a park that fails fails its request (and frees the
-        slot by eviction)."""
+        """Parks the row in slot s (a beam pipeline: the group s) and queues it for whichever lane next has room; a park that fails
+        fails its request (and frees the slot by eviction)."""
         j, i = in_slot.pop(s)
         try:
-            parked = sess.park(s)
+            parked = sess.park_group(s) if self.num_beams > 1 else sess.park(s)
             if self.park_to == "host":
                 parked = parked.to("cpu")
         except BaseException as e:           # noqa: BLE001
@@ -820,7 +830,7 @@ class ContinuousPipeline:
 
     def _resume(self, sess, in_slot, j: _Job, i: int, parked) -> None:
         try:
-            s = sess.resume(parked)
+            s = sess.resume_group(parked) if self.num_beams > 1 else sess.resume(parked)
         except BaseException as e:           # noqa: BLE001 -- this request's own failure: nothing was changed, the lane goes on
             self._fail(j, e)
             return
@@ -860,7 +870,7 @@ class ContinuousPipeline:
                         if self._closing and not self._waiting and not in_slot:
                             break
                     self._evict_gone(sess, in_slot)      # before admitting: the freed places are admissible in this poll
-                    if self._free(sess) or (self.preempt and in_slot):
+                    if self._free(sess) or (self._preempts and in_slot):
                         self._admit(sess, in_slot)
                     if in_slot:
                         self._collect(sess, in_slot, sess.step(self.poll_steps))
