@@ -359,6 +359,18 @@ typedef struct idxtts_sampling {
 int idxtts_gpt_generate_sampled(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
                                 float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps,
                                 float* logits_out, void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* Several takes of every prompt in one call (HF's num_return_sequences, _expand_inputs_for_generation): idxtts_gpt_generate (sampling
+ * NULL or mode 0) or idxtts_gpt_generate_sampled on B * takes decode rows, row b * takes + j being take j of prompt b -- codes
+ * [B * takes][max_new_tokens], logits_out [max_new_tokens][B * takes][V], exp_noise [steps][B * takes][V], a seeded row draws the
+ * stream of row b * takes + j, the workspace is idxtts_gpt_workspace_bytes(B * takes, P + 1, max_new_tokens), B * takes <= 64 -- while
+ * inputs_embeds [B][P][d] and pad_left [B] hold one entry per prompt and the prefill runs on those B rows: each row's keys and values
+ * are written to its takes' cache rows and its last position feeds all of their first tokens.  The result equals the plain call on
+ * the caller-expanded batch wherever the two prefills (B * (P + 1) and B * takes * (P + 1) rows) choose the same kernels: always
+ * with an fp32 or fp8 KV cache or in the batch-invariant mode; with a bf16 cache in split-bf16 GEMM mode when both row counts lie on
+ * the same side of 256.  takes = 1 is the plain call. */
+int idxtts_gpt_generate_takes(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                              float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps, float* logits_out,
+                              void* workspace, size_t workspace_bytes, int use_graph, void* stream);
 /* Beam search / beam-sample = what `IndexTTS2.infer` runs by default (infer_v2.py:714-722, 767: do_sample=True, num_beams=3,
  * top_p .8, top_k 30, temperature .8, repetition_penalty 10, length_penalty 0) through HF `_beam_search`
  * (transformers_generation_utils.py:3325-3516) + BeamSearchScorer (transformers_beam_search.py:123-420): log_softmax before
@@ -382,6 +394,24 @@ size_t idxtts_gpt_beam_workspace_bytes(const idxtts_ctx* ctx, int B, int num_bea
 int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
                              float repetition_penalty, const idxtts_beam* beam, long long* codes, int* n_steps, void* workspace,
                              size_t workspace_bytes, int use_graph, void* stream);
+/* idxtts_gpt_generate_beam returning the scorer's n_best best hypotheses of every utterance (BeamSearchScorer with
+ * num_beam_hyps_to_keep = n_best = HF's num_return_sequences), 1 <= n_best <= num_beams: codes device int64 [B][n_best][max_new_tokens],
+ * lens HOST int32 [B][n_best], scores HOST fp32 [B][n_best] (sequences_scores).  Order: finalize's (transformers_beam_search.py:355-380)
+ * -- the ascending stable sort of the utterance's list, popped from the end: best first, among equal scores the one added later
+ * first.  Each row is the hypothesis, then the stop token where it fits under the cap (lens counts it), then stop-padded.  Fewer than
+ * n_best hypotheses cannot occur: finalize tops the list up from the open beams to num_beams entries.  *n_steps: min(longest
+ * hypothesis + 1, max_new_tokens).  n_best = 1 returns exactly what idxtts_gpt_generate_beam returns. */
+int idxtts_gpt_generate_beam_nbest(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
+                                   float repetition_penalty, const idxtts_beam* beam, int n_best, long long* codes, int* lens, float* scores,
+                                   int* n_steps, void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* Instrument: the host routine behind every beam read -- BeamSearchScorer.finalize for one utterance on HOST copies of its state, then
+ * the rows of an n-best read.  hyp_score / hyp_len / hyp_slot [hyp_n]: the finished hypotheses in the order they were added, hypothesis q's
+ * tokens in row hyp_slot[q] (0 .. 8) of hyp_seq [9][seq_ld]; unless `done`, the num_beams open beams (beam_scores
+ * [num_beams], seq [num_beams][seq_ld]) join at steps_done tokens under BeamHypotheses.add's rule.  Out: codes [n_best][seq_ld]
+ * stop-padded, lens [n_best] = min(length + 1, cap), scores [n_best]. */
+int idxtts_beam_finalize_host(int num_beams, double length_penalty, int hyp_n, const double* hyp_score, const int* hyp_len,
+                              const int* hyp_slot, const int* hyp_seq, int seq_ld, int done, const float* beam_scores, const int* seq,
+                              int steps_done, int cap, int stop_token, int n_best, long long* codes, int* lens, float* scores);
 /* ---- GPT decode session (continuous batching) ----
  * Stands in for the accel engine's per-sequence bookkeeping -- `context_lens` per sequence in the decode step and a KV allocation per
  * sequence that is taken when a sequence is admitted and given back when it finishes (accel_engine.py:154-212,
@@ -424,6 +454,43 @@ int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int m
 int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                                      const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_row, void* workspace,
                                      void* stream);
+/* ---- Several takes of one request ----
+ * What HF's num_return_sequences is to generate (_expand_inputs_for_generation, model_v2.py:796, infer_v2.py:718, 771): several
+ * continuations of one prompt, each an ordinary row of the session -- its own slot, cache rows, sampler, cap; stepped, read, evicted,
+ * stopped, parked and resumed like any other -- whose prompt was prefilled once.  Greedy and sampled sessions; a beam session returns its
+ * scorer's list instead (_read_nbest below).
+ * _admit_takes: _admit_sampled with takes[b] >= 1 slots for request b (HOST int32 [n]).  slot_ids, max_new_tokens and per_take then hold
+ * one entry per take, request after request -- T = sum(takes) <= slots entries; the slots free, distinct, in any order and not necessarily
+ * adjacent.  per_take: HOST [T] idxtts_sampling, or NULL = every take greedy (the only choice on a greedy session).  Each request's
+ * prefill runs once; its keys and values for positions [0, P + 1) go to all of its takes' slots, and each take's first token is drawn
+ * with its own sampler in the admission's one head-and-sample pass.  Every check happens before anything changes.
+ * Determinism: take j's codes equal, bit for bit, those of the same prompt admitted alone with sampler j -- the session rules above
+ * hold per take.  The zero-row padding of the bf16 cache's prefill in split-bf16 mode counts prefill rows: a request counts once. */
+int idxtts_gpt_session_admit_takes(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* takes,
+                                   const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take, void* workspace,
+                                   void* stream);
+/* _fork: n further takes of the request in src_slot, branching where it stood after `at` codes, in the free slots dst_slots (HOST int32
+ * [n]; at = -1: after all the codes it has, the stop token left out).  The source may be decoding, or ended and not read yet; it is only read.  One launch on `stream`, the session's stream, between
+ * steps, that loads every 16-byte vector of the source's rows once and stores it to all n destinations (no intermediate buffer): bytes
+ * read are proportional to P + at, bytes written n times that; the captured step and the workspace layout are untouched.
+ * Each destination receives the source's step scalars cut back to step = at (pos = P + at, mel_pos = at + 1), codes [0, at), the set
+ * of seen ids rebuilt from the start token and those codes, the cached keys, values and fp8 scales of every layer for the positions a
+ * row with `at` codes holds -- [0, P + max(at, 1)): the prefill's P + 1 and one per code fed back -- its own sampler samplers[j] (HOST
+ * [n]; NULL = greedy takes; exp_noise device fp32 [cap][V], row t = the draws of step t, rows below `at` never read), its own cap
+ * max_new_tokens[j] (HOST [n]; NULL = the source's cap), live = 1, and its next decode input rebuilt from codes[at - 1] as _resume
+ * rebuilds it.  at = 0: the take starts in front of its first token, which is drawn at once with its sampler (the admission's
+ * head-and-sample pass on the destinations, after the copy).
+ * Refused, before anything changes: a beam session; a source that is free or out of range; at < 0 or at > the source's codes (a source
+ * that ended on the stop token: > the codes in front of it, for nothing follows a stop token); at = 0 on a source that came in through
+ * _resume (or a take of one): its prefill output is gone; a destination that is busy, repeated, out of range or the source; a sampled
+ * take on a greedy session or a bad sampler; a cap above the session's max_new_tokens, one that is not above `at`, or P + 1 + cap
+ * beyond the cache length.
+ * Determinism: a take forked at `at` = k with explicit draws E', E'[t] equal to the source's draws for t < k, returns bit for bit the
+ * codes of a fresh admission of the same prompt with E' into a session of the same configuration; its first k codes are the source's.
+ * With a seed the take draws from its own seed from step k on (a slot's stream is keyed by seed and step).  Every other row's codes,
+ * the source's included, are untouched. */
+int idxtts_gpt_session_fork(idxtts_ctx* ctx, int src_slot, int at, int n, const int* dst_slots, const idxtts_sampling* samplers,
+                            const int* max_new_tokens, void* workspace, void* stream);
 /* Beam sessions (beam search / beam-sample per request, idxtts_gpt_generate_beam's semantics): the `slots` rows form slots / num_beams
  * groups of num_beams consecutive slots (2 <= num_beams <= 8, slots % num_beams == 0, slots <= 64); each admitted request takes one
  * group and runs HF _beam_search + BeamSearchScorer with its own idxtts_beam.  A group retires when its scorer is done
@@ -455,6 +522,12 @@ int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* fi
 /* Copies a finished slot's codes (up to and including the stop token) to codes (device int64, >= *n_codes entries: at most
  * max_new_tokens), sets *n_codes (host) and frees the slot. */
 int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_codes, void* workspace, void* stream);
+/* _read on a beam session's group for the scorer's n_best best hypotheses, 1 <= n_best <= num_beams: codes device int64, lens and scores
+ * HOST [n_best], in idxtts_gpt_generate_beam_nbest's order and padding.  n_best = 1: codes receives lens[0] entries, exactly what _read
+ * returns; else codes is [n_best][max_new_tokens of _init_beam], every row stop-padded to the end.  Frees the group.  Refused on every
+ * other kind of session. */
+int idxtts_gpt_session_read_nbest(idxtts_ctx* ctx, int slot, int n_best, long long* codes, int* lens, float* scores, void* workspace,
+                                  void* stream);
 /* Ending requests from outside (a client that went away, a failed job): what KVCacheManager.remove_seq is to the accel engine
  * (kv_manager.py:130-202) -- a sequence's KV allocation given back before it finished.  slots: HOST int32 [n], every kind of session; a
  * beam session addresses a group by its FIRST slot, as _read does.  Every id is checked before anything changes -- in range, holding a

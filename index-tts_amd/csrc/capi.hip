@@ -428,6 +428,16 @@ int idxtts_gpt_generate_sampled(idxtts_ctx* ctx, const float* inputs_embeds, con
   API_END
 }
 
+int idxtts_gpt_generate_takes(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                              float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps, float* logits_out,
+                              void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes);
+  API_END
+}
+
 size_t idxtts_gpt_beam_workspace_bytes(const idxtts_ctx* ctx, int B, int num_beams, int S, int max_new_tokens) {
   if (!ctx || !ctx->finalized || B <= 0 || num_beams < 2 || S <= 0 || max_new_tokens <= 0) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
@@ -441,6 +451,35 @@ int idxtts_gpt_generate_beam(idxtts_ctx* ctx, const float* inputs_embeds, const 
   GPT_MODEL(ctx);
   return m->generate_beam(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, beam, codes, n_steps, workspace,
                           workspace_bytes, use_graph, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_generate_beam_nbest(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
+                                   float repetition_penalty, const idxtts_beam* beam, int n_best, long long* codes, int* lens, float* scores,
+                                   int* n_steps, void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(lens && scores, "null pointer");
+  return m->generate_beam(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, beam, codes, n_steps, workspace,
+                          workspace_bytes, use_graph, static_cast<hipStream_t>(stream), n_best, lens, scores);
+  API_END
+}
+
+int idxtts_beam_finalize_host(int num_beams, double length_penalty, int hyp_n, const double* hyp_score, const int* hyp_len,
+                              const int* hyp_slot, const int* hyp_seq, int seq_ld, int done, const float* beam_scores, const int* seq,
+                              int steps_done, int cap, int stop_token, int n_best, long long* codes, int* lens, float* scores) {
+  API_BEGIN
+  IDX_CHECK(hyp_score && hyp_len && hyp_slot && hyp_seq && beam_scores && seq && codes && lens && scores, "null pointer");
+  IDX_CHECK(num_beams >= 2 && num_beams <= BEAM_MAX && hyp_n >= 0 && hyp_n <= num_beams && seq_ld >= 1, "shape");
+  IDX_CHECK(steps_done >= 1 && steps_done <= seq_ld && cap >= steps_done && cap <= seq_ld, "steps_done <= cap <= seq_ld");
+  IDX_CHECK(n_best >= 1 && n_best <= num_beams, "1 <= n_best <= num_beams");
+  for (int q = 0; q < hyp_n; ++q)
+    IDX_CHECK(hyp_slot[q] >= 0 && hyp_slot[q] <= BEAM_MAX && hyp_len[q] >= 0 && hyp_len[q] <= seq_ld, "hypothesis out of range");
+  std::vector<BeamHyp> best(n_best);
+  if (beam_finalize(num_beams, length_penalty, hyp_n, hyp_score, hyp_len, hyp_slot, hyp_seq, seq_ld, done != 0, beam_scores, seq, steps_done,
+                    best.data(), n_best)) return 1;
+  beam_fill_rows(best.data(), n_best, seq_ld, cap, stop_token, codes, lens, scores);
+  return 0;
   API_END
 }
 
@@ -494,6 +533,25 @@ int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs
   API_END
 }
 
+int idxtts_gpt_session_admit_takes(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* takes,
+                                   const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take, void* workspace,
+                                   void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(takes, "null pointer");
+  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
+                          per_take, takes);
+  API_END
+}
+
+int idxtts_gpt_session_fork(idxtts_ctx* ctx, int src_slot, int at, int n, const int* dst_slots, const idxtts_sampling* samplers,
+                            const int* max_new_tokens, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_fork(workspace, src_slot, at, n, dst_slots, samplers, max_new_tokens, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 size_t idxtts_gpt_session_workspace_bytes_beam(const idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens) {
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
   if (num_beams < 2 || num_beams > BEAM_MAX || slots % num_beams) return 0;
@@ -533,6 +591,14 @@ int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_
   API_BEGIN
   GPT_MODEL(ctx);
   return m->session_read(workspace, slot, codes, n_codes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_read_nbest(idxtts_ctx* ctx, int slot, int n_best, long long* codes, int* lens, float* scores, void* workspace,
+                                  void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_read_nbest(workspace, slot, n_best, codes, lens, scores, static_cast<hipStream_t>(stream));
   API_END
 }
 

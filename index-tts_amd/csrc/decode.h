@@ -187,9 +187,10 @@ struct KvDst {
 int kv_store_prefill(float* qkv, const KvDst& kv, int B, int H, int S, int Smax, int d, hipStream_t stream);
 // Decode-session admission: the same for a right-padded prefill of n rows whose cache rows are the slots slot_ids[b]: positions
 // [0, len[b]) of row b go to slot slot_ids[b] (the caches laid out for `slots` rows); k / v columns rounded in place as above.
-// fan > 1 (beam sessions): row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1
+// fan > 1 (beam sessions): row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1.  first (device [n + 1], fan = 1; admission
+// with takes): row b goes to the slots slot_ids[first[b]] .. slot_ids[first[b + 1] - 1] instead, any slots in any order
 int kv_store_slots(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len,
-                   hipStream_t stream, int fan = 1);
+                   hipStream_t stream, int fan = 1, const int* first = nullptr);
 // Instrument (idxtts_kv_fp8_quantize): the fp8 cache's quantiser on n vectors x [n][64] -> codes [n][64], scales [n]
 int kv_fp8_quantize(const float* x, int n, unsigned char* codes, float* scales, hipStream_t stream);
 // the device's f32 -> fp8 conversion equals wstream.h::fp8_e4m3_encode on every code value and every midpoint between neighbours
@@ -199,9 +200,10 @@ int fp8_check_device_encode(hipStream_t stream);
 int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P, int n, int S, int d, const float* mel_emb,
                           const float* mel_pos, int start_token, hipStream_t stream);
 // Decode-session admission, per admitted row b: reset slot slot_ids[b] -- seen row = {1, start_token}, state {pos = P[b], mel_pos = 1,
-// step = 0, max_step = cap[b], live = 1} -- and copy the prefill's last valid row x[b][P[b]] (x [n][S][d]) to x_last[slot]
+// step = 0, max_step = cap[b], live = 1} -- and copy the prefill's last valid row x[b][P[b]] (x [n][S][d]) to x_last[slot].  row
+// (admission with takes): entry t of slot_ids / cap is a take of prefill row row[t], whose P and x row it gets
 int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
-                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream);
+                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream, const int* row = nullptr);
 // Ends slots of a decode session between steps (eviction, stop): slot i of the n_slots <= 64 slots for every set bit i of `mask`, passed
 // by value -- live = 0, step kept (the codes produced so far).  cap_at_step: a slot that was live also gets max_step = step (a cap set
 // late: what reads the slot afterwards sees a request that ended at that cap); a slot that had ended is left as it was.
@@ -239,6 +241,25 @@ struct ParkArgs {
 // header's scalars, and the slot's next input mel_emb[last code] + mel_pos[mel_pos] written as the sampler tails write it.
 int session_park_slot(const ParkArgs& a, hipStream_t stream);
 int session_resume_slot(const ParkArgs& a, hipStream_t stream);
+// Fork (idxtts.h "Several takes of one request"): the row in slot `src`, cut back to `at` codes, copied to the n free slots dst[] in one
+// launch that reads every 16-byte vector of the source once and stores it n times -- positions [0, P + max(at, 1)) of the keys, values and
+// fp8 scales of every layer (what a row holding `at` codes has cached), codes[0, at), a seen row rebuilt from the start token and those
+// codes, SlotState {P + at, at + 1, at, cap[j], 1} and the next input mel_emb[codes[at - 1]] + mel_pos[at + 1] as the sampler tails write
+// it.  at = 0: the state session_reset_slots leaves (SlotState {P, 1, 0, cap[j], 1}, x_last[src] copied), and the caller runs the
+// admission's head-and-sample pass on the destinations.  The source is only read.
+constexpr int FORK_MAX = 64;
+struct ForkArgs {
+  int kv_fmt = 0, layers = 0, heads = 0, V = 0, start_token = 0;
+  int src = 0, P = 0, at = 0, n = 0;
+  unsigned char dst[FORK_MAX] = {}; int cap[FORK_MAX] = {};      // by value: no staging copy, no synchronisation
+  char* kcache = nullptr; char* vcache = nullptr; float* kscale = nullptr; float* vscale = nullptr;   // layer 0 of the session's cache
+  size_t layer_bytes = 0, layer_scales = 0;
+  int Smax = 0;
+  SlotState* slots = nullptr; unsigned char* seen = nullptr; long long* codes = nullptr; int codes_ld = 0; int* cur_tok = nullptr;
+  float* x_last = nullptr;
+  SampleArgs::Embed embed; int B = 0;
+};
+int session_fork_slots(const ForkArgs& a, hipStream_t stream);
 constexpr int GATHER_MAX_TABLES = 5;
 struct GatherArgs {
   float* out = nullptr; int ld_out = 0; int d = 0;

@@ -937,9 +937,11 @@ __global__ __launch_bounds__(256) void kv_store_prefill_kernel(float* qkv, void*
 template <bool FAN>
 __global__ __launch_bounds__(256) void kv_store_fp8_kernel(float* qkv, unsigned char* kcache, unsigned char* vcache, float* kscale,
                                                            float* vscale, int H, int S, int Smax, int d, const int* slot_ids,
-                                                           const int* len, int fan) {
+                                                           const int* len, int fan, const int* first) {
   const int s = blockIdx.x, b = blockIdx.y, wave = threadIdx.x >> 6, dd = threadIdx.x & 63;
-  const int slot0 = slot_ids ? slot_ids[b] : b;
+  const int slot0 = slot_ids ? slot_ids[FAN && first ? first[b] : b] : b;
+  const int* const list = FAN && first ? slot_ids + first[b] : nullptr;      // takes: the row's own slot list
+  if (list) fan = first[b + 1] - first[b];
   const bool keep = !len || s < len[b];
   float* row = qkv + ((size_t)b * S + s) * 3 * d;
   for (int h = wave; h < H; h += 4) {      // (wave-uniform: every lane of a wave reaches the quantiser's reduction)
@@ -954,7 +956,7 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(float* qkv, unsigned 
         vcache[(vec * Smax + s) * 64 + dd] = (unsigned char)vcode;
         if (dd == 0) { kscale[vec * Smax + s] = ks; vscale[vec * Smax + s] = vs; }
       };
-      if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+      if (FAN) for (int j = 0; j < fan; ++j) put(list ? list[j] : slot0 + j);
       else put(slot0);
     }
     row[d + col] = kq;
@@ -963,12 +965,12 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(float* qkv, unsigned 
 }
 
 static int kv_store_fp8(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len, int fan,
-                        hipStream_t stream) {
+                        hipStream_t stream, const int* first = nullptr) {
   IDX_CHECK(kv.kscale && kv.vscale, "the fp8 cache needs its scale arrays");
   unsigned char* const kc = static_cast<unsigned char*>(kv.kcache);
   unsigned char* const vc = static_cast<unsigned char*>(kv.vcache);
-  if (fan > 1) hipLaunchKernelGGL(kv_store_fp8_kernel<true>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, fan);
-  else hipLaunchKernelGGL(kv_store_fp8_kernel<false>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, 1);
+  if (fan > 1 || first) hipLaunchKernelGGL(kv_store_fp8_kernel<true>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, fan, first);
+  else hipLaunchKernelGGL(kv_store_fp8_kernel<false>, dim3(S, n), dim3(256), 0, stream, qkv, kc, vc, kv.kscale, kv.vscale, H, S, Smax, d, slot_ids, len, 1, nullptr);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -985,12 +987,15 @@ int kv_store_prefill(float* qkv, const KvDst& kv, int B, int H, int S, int Smax,
 }
 
 // decode-session admission: prefill row b (right-padded, S positions) -> the cache rows of slot slot_ids[b], positions [0, len[b]);
-// FAN (beam sessions): to the `fan` consecutive slots slot_ids[b] .. slot_ids[b] + fan - 1 (a group's beams start identical)
+// FAN: to several slots -- first null (beam sessions): the `fan` consecutive slots slot_ids[b] .. slot_ids[b] + fan - 1 (a group's beams
+// start identical); else (takes) the row's own list slot_ids[first[b]] .. slot_ids[first[b + 1] - 1], in any order
 template <bool KV16, bool FAN>
 __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* kcache, void* vcache, int H, int S, int Smax, int d,
-                                                             const int* slot_ids, const int* len, int fan) {
+                                                             const int* slot_ids, const int* len, int fan, const int* first) {
   const int s = blockIdx.x, b = blockIdx.y;
-  const int slot0 = slot_ids[b];
+  const int* const list = FAN && first ? slot_ids + first[b] : nullptr;
+  const int slot0 = list ? list[0] : slot_ids[b];
+  if (list) fan = first[b + 1] - first[b];
   const bool keep = s < len[b];
   float* row = qkv + ((size_t)b * S + s) * 3 * d;
   for (int col = threadIdx.x; col < d; col += 256) {
@@ -1002,7 +1007,7 @@ __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* k
           static_cast<unsigned short*>(kcache)[(((size_t)(slot * H + h) * 8 + (dd >> 3)) * Smax + s) * 8 + (dd & 7)] = (unsigned short)kb;
           static_cast<unsigned short*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = (unsigned short)vb;
         };
-        if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+        if (FAN) for (int j = 0; j < fan; ++j) put(list ? list[j] : slot0 + j);
         else put(slot0);
       }
       row[d + col] = __uint_as_float(kb << 16);
@@ -1012,30 +1017,30 @@ __global__ __launch_bounds__(256) void kv_store_slots_kernel(float* qkv, void* k
         static_cast<float*>(kcache)[(((size_t)(slot * H + h) * 16 + (dd >> 2)) * Smax + s) * 4 + (dd & 3)] = row[d + col];
         static_cast<float*>(vcache)[((size_t)(slot * H + h) * Smax + s) * 64 + dd] = row[2 * d + col];
       };
-      if (FAN) for (int j = 0; j < fan; ++j) put(slot0 + j);
+      if (FAN) for (int j = 0; j < fan; ++j) put(list ? list[j] : slot0 + j);
       else put(slot0);
     }
   }
 }
 
 int kv_store_slots(float* qkv, const KvDst& kv, int n, int H, int S, int Smax, int d, const int* slot_ids, const int* len,
-                   hipStream_t stream, int fan) {
+                   hipStream_t stream, int fan, const int* first) {
   IDX_CHECK(S <= Smax, "prefill longer than the cache");
-  IDX_CHECK(slot_ids && len && fan >= 1, "null pointer");
+  IDX_CHECK(slot_ids && len && fan >= 1 && (!first || fan == 1), "null pointer");
   if (n <= 0) return 0;
   static const int cat = prof_register("kv_store_slots_kernel");
   ProfScope prof(cat, stream, 0.0, (kv.fmt == 2 ? 26.0 : kv.fmt ? 28.0 : 16.0) * n * (double)S * d);
-  if (kv.fmt == 2) return kv_store_fp8(qkv, kv, n, H, S, Smax, d, slot_ids, len, fan, stream);
+  if (kv.fmt == 2) return kv_store_fp8(qkv, kv, n, H, S, Smax, d, slot_ids, len, fan, stream, first);
   void* const kcache = kv.kcache;
   void* const vcache = kv.vcache;
   const int kv16 = kv.fmt;
-  if (fan > 1) {
-    if (kv16) hipLaunchKernelGGL((kv_store_slots_kernel<true, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
-    else hipLaunchKernelGGL((kv_store_slots_kernel<false, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan);
+  if (fan > 1 || first) {
+    if (kv16) hipLaunchKernelGGL((kv_store_slots_kernel<true, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan, first);
+    else hipLaunchKernelGGL((kv_store_slots_kernel<false, true>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, fan, first);
   } else if (kv16) {
-    hipLaunchKernelGGL((kv_store_slots_kernel<true, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1);
+    hipLaunchKernelGGL((kv_store_slots_kernel<true, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1, nullptr);
   } else {
-    hipLaunchKernelGGL((kv_store_slots_kernel<false, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1);
+    hipLaunchKernelGGL((kv_store_slots_kernel<false, false>), dim3(S, n), dim3(256), 0, stream, qkv, kcache, vcache, H, S, Smax, d, slot_ids, len, 1, nullptr);
   }
   IDX_LAUNCH_CHECK();
   return 0;
@@ -1126,20 +1131,21 @@ int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P,
 
 // decode-session admission: reset the admitted slots, stage the prefill's last valid row of each for the first-token head
 __global__ __launch_bounds__(256) void session_reset_slots_kernel(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last,
-                                                                  const float* x, int S, int d, const int* slot_ids, const int* P, const int* cap) {
-  const int b = blockIdx.x, slot = slot_ids[b], Pb = P[b];
+                                                                  const float* x, int S, int d, const int* slot_ids, const int* P, const int* cap,
+                                                                  const int* row) {
+  const int t = blockIdx.x, slot = slot_ids[t], b = row ? row[t] : t, Pb = P[b];      // (takes: slot t holds a take of prefill row row[t])
   unsigned char* sr = seen + (size_t)slot * V;
   for (int v = threadIdx.x; v < V; v += 256) sr[v] = (v == 1 || v == start_token) ? 1 : 0;      // input_ids = [1 ... 1, start]
   const float* src = x + ((size_t)b * S + Pb) * d;
   for (int e = threadIdx.x; e < d; e += 256) x_last[(size_t)slot * d + e] = src[e];
-  if (threadIdx.x == 0) slots[slot] = SlotState{Pb, 1, 0, cap[b], 1};
+  if (threadIdx.x == 0) slots[slot] = SlotState{Pb, 1, 0, cap[t], 1};
 }
 
 int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
-                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream) {
+                        const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream, const int* row) {
   IDX_CHECK(slots && seen && x_last && x && slot_ids && P && cap, "null pointer");
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(session_reset_slots_kernel, dim3(n), dim3(256), 0, stream, slots, seen, V, start_token, x_last, x, S, d, slot_ids, P, cap);
+  hipLaunchKernelGGL(session_reset_slots_kernel, dim3(n), dim3(256), 0, stream, slots, seen, V, start_token, x_last, x, S, d, slot_ids, P, cap, row);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -1285,6 +1291,102 @@ static int park_launch(const ParkArgs& a, bool resume, hipStream_t stream) {
 
 int session_park_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, false, stream); }
 int session_resume_slot(const ParkArgs& a, hipStream_t stream) { return park_launch(a, true, stream); }
+
+// ---- fork (decode.h ForkArgs, idxtts.h "Several takes of one request") ----
+// n bytes (a multiple of 4) of the source slot's run to the same run of every destination slot: run0 is the run in slot 0, a slot's run
+// lies slot * stride bytes behind it, and every run starts 16-byte aligned.  park_copy_run's access pattern -- 16-byte vectors,
+// consecutive lanes on consecutive vectors, four loads in flight per thread -- with each vector loaded once and stored p.n times; the
+// n % 16 bytes behind the last whole vector (fp8 scale runs and odd fp8 key runs end off a vector) go as dwords, one lane each.
+__device__ __forceinline__ void fork_copy_run(char* const run0, const size_t stride, const ForkArgs& p, const size_t n, const int tid) {
+  const uint4* const s4 = reinterpret_cast<const uint4*>(run0 + p.src * stride);
+  const size_t nv = n >> 4;
+  size_t i = tid;
+  for (; i + 3 * PARK_NT < nv; i += 4 * PARK_NT) {
+    const uint4 a = s4[i], b = s4[i + PARK_NT], c = s4[i + 2 * PARK_NT], e = s4[i + 3 * PARK_NT];
+    for (int j = 0; j < p.n; ++j) {
+      uint4* const d4 = reinterpret_cast<uint4*>(run0 + p.dst[j] * stride);
+      d4[i] = a; d4[i + PARK_NT] = b; d4[i + 2 * PARK_NT] = c; d4[i + 3 * PARK_NT] = e;
+    }
+  }
+  for (; i < nv; i += PARK_NT) {
+    const uint4 a = s4[i];
+    for (int j = 0; j < p.n; ++j) reinterpret_cast<uint4*>(run0 + p.dst[j] * stride)[i] = a;
+  }
+  const int tail = (int)(n & 15) >> 2;      // dwords behind the last whole vector: exactly n bytes are written
+  if (tid < tail) {
+    const unsigned w = reinterpret_cast<const unsigned*>(s4)[nv * 4 + tid];
+    for (int j = 0; j < p.n; ++j) reinterpret_cast<unsigned*>(run0 + p.dst[j] * stride)[nv * 4 + tid] = w;
+  }
+}
+
+// The grid of session_park_kernel: (runs + 1, heads, layers), workgroup (r, h, l) on run r of (l, h) -- a key chunk, a piece of the value
+// run, a scale run -- and workgroup (runs, 0, 0) on the small state of every destination.
+__global__ __launch_bounds__(PARK_NT) void session_fork_kernel(const ForkArgs p) {
+  const int tid = threadIdx.x, r = blockIdx.x, h = blockIdx.y, l = blockIdx.z, H = gridDim.y;
+  const int pos = p.P + (p.at > 1 ? p.at : 1);      // cached positions of a row that holds `at` codes (the prefill alone: P + 1)
+  const ParkLayout lay = park_layout(p.kv_fmt, p.layers, H, p.V, pos, p.at);
+  const int C = lay.chunks, runs = 2 * C + (p.kv_fmt == 2 ? 2 : 0);
+  if (r < runs) {
+    if (r < C) {
+      const size_t run = (size_t)p.Smax * lay.gran;
+      fork_copy_run(p.kcache + l * p.layer_bytes + ((size_t)h * C + r) * run, (size_t)H * C * run, p, (size_t)pos * lay.gran, tid);
+    } else if (r < 2 * C) {
+      const size_t run = (size_t)p.Smax * 64 * lay.elem, nv = lay.vrun >> 4, v0 = nv * (r - C) / C, v1 = nv * (r - C + 1) / C;
+      fork_copy_run(p.vcache + l * p.layer_bytes + h * run + (v0 << 4), H * run, p, (v1 - v0) << 4, tid);
+    } else {
+      float* const sc = (r == 2 * C ? p.kscale : p.vscale) + l * p.layer_scales + (size_t)h * p.Smax;
+      fork_copy_run(reinterpret_cast<char*>(sc), (size_t)H * p.Smax * 4, p, (size_t)pos * 4, tid);
+    }
+    return;
+  }
+  if (h || l) return;
+  const int V = p.V, at = p.at;
+  const long long* const scodes = p.codes + (size_t)p.src * p.codes_ld;
+  for (int j = 0; j < p.n; ++j) {      // input_ids = [1 ... 1, start] and nothing else yet
+    unsigned char* const sr = p.seen + (size_t)p.dst[j] * V;
+    for (int v = tid; v < V; v += PARK_NT) sr[v] = (v == 1 || v == p.start_token) ? 1 : 0;
+  }
+  __syncthreads();
+  for (int i = tid; i < at; i += PARK_NT) {
+    const long long c = scodes[i];
+    const int tok = min(max((int)c, 0), V - 1);      // (inside the row whatever the source holds)
+    for (int j = 0; j < p.n; ++j) {
+      p.codes[(size_t)p.dst[j] * p.codes_ld + i] = c;
+      p.seen[(size_t)p.dst[j] * V + tok] = 1;
+    }
+  }
+  for (int j = 0; j < p.n; ++j)      // the prefill's last row travels with every take: a take can be forked at 0 like its source
+    for (int e = tid; e < p.embed.d; e += PARK_NT) p.x_last[(size_t)p.dst[j] * p.embed.d + e] = p.x_last[(size_t)p.src * p.embed.d + e];
+  if (at == 0) {      // the admission's state before the first token: the head reads x_last
+    if (tid < p.n) p.slots[p.dst[tid]] = SlotState{p.P, 1, 0, p.cap[tid], 1};
+    return;
+  }
+  const int tok = min(max((int)scodes[at - 1], 0), V - 1);
+  for (int j = 0; j < p.n; ++j) write_next_input<PARK_NT>(p.embed, p.B, p.dst[j], tok, at + 1, tid);
+  if (tid < p.n) {
+    p.cur_tok[p.dst[tid]] = tok;
+    p.slots[p.dst[tid]] = SlotState{p.P + at, at + 1, at, p.cap[tid], 1};
+  }
+}
+
+int session_fork_slots(const ForkArgs& a, hipStream_t stream) {
+  IDX_CHECK(a.kcache && a.vcache && a.slots && a.seen && a.codes && a.cur_tok && a.x_last, "null pointer");
+  IDX_CHECK(a.kv_fmt >= 0 && a.kv_fmt <= 2 && (a.kv_fmt != 2 || (a.kscale && a.vscale)), "KV format");
+  IDX_CHECK(a.layers >= 1 && a.layers <= 65535 && a.heads >= 1 && a.heads <= 65535 && a.V >= 2, "shape");
+  IDX_CHECK(a.B >= 1 && a.B <= FORK_MAX && a.n >= 1 && a.n < a.B && a.n <= PARK_NT && a.src >= 0 && a.src < a.B, "slots out of range");
+  for (int j = 0; j < a.n; ++j) IDX_CHECK(a.dst[j] < a.B && a.dst[j] != a.src, "destination slot out of range");
+  IDX_CHECK(a.P >= 1 && a.at >= 0 && a.at <= a.codes_ld && a.P + std::max(a.at, 1) <= a.Smax, "slot state out of range");
+  IDX_CHECK(a.Smax % 4 == 0 && a.layer_bytes % 16 == 0 && a.layer_scales % 4 == 0, "cache runs must start 16-byte aligned");
+  IDX_CHECK(((uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.kscale | (uintptr_t)a.vscale) % 16 == 0, "the caches must be 16-byte aligned");
+  IDX_CHECK((a.embed.x_row && a.embed.x_stats) || a.embed.x_frag, "fork needs the step's input buffers");
+  const ParkLayout lay = park_layout(a.kv_fmt, a.layers, a.heads, a.V, a.P + std::max(a.at, 1), a.at);
+  const int runs = 2 * lay.chunks + (a.kv_fmt == 2 ? 2 : 0);
+  static const int cat = prof_register("session_fork_kernel");
+  ProfScope prof(cat, stream, 0.0, (1.0 + a.n) * (double)lay.bytes);
+  hipLaunchKernelGGL(session_fork_kernel, dim3(runs + 1, a.heads, a.layers), dim3(PARK_NT), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
 
 // ---- preempt and resume of a beam group (beam.h ParkGroupArgs, idxtts.h "Preempt and resume, beam sessions") ----
 // n bytes (a multiple of sizeof(U)) in units of U, for a run whose cache side starts in the middle of a cache row and is only

@@ -122,6 +122,7 @@ struct GPTModel : ModelBase {
   struct KvScatter {      // decode-session admission: prefill row b's positions [0, len[b]) go to the cache rows of slot slot_ids[b]
     const int* slot_ids = nullptr; const int* len = nullptr; int n = 0; int slots = 0;
     int fan = 1;          // beam sessions: row b goes to the fan slots slot_ids[b] .. slot_ids[b] + fan - 1 (its group)
+    const int* first = nullptr;      // takes (fan = 1): row b goes to the slots slot_ids[first[b]] .. slot_ids[first[b + 1] - 1]
   };
   int layer_full(int li, const Buffers& w, int B, int S, const int* kstart, bool store_kv, hipStream_t st, const KvScatter* scatter = nullptr);
   int head_logits(const Buffers& w, int B, const float* x, int ldx, bool x_frag, hipStream_t st);      // ln_f -> final_norm -> mel_head
@@ -144,15 +145,18 @@ struct GPTModel : ModelBase {
   int call_stream(hipStream_t user, hipStream_t* st);
   int run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                      float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll, int poll_n,
-                     int poll_every, int* steps_done, hipStream_t st);
+                     int poll_every, int* steps_done, hipStream_t st, bool share_prefill = false);      // share_prefill: B prefill rows,
+                     // each row's KV and last position fanned out to its fan decode rows (takes); else R prefill rows (beams)
   int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_sampling* sampling, long long* codes,
-               int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr);
+               int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr,
+               int takes = 1);      // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per prompt
   // Beam search / beam-sample (HF _beam_search; the reference's default decoding mode, infer_v2.py:714-722): B utterances x
   // num_beams rows through the same decode step, selection / hypotheses / re-indexing on the device (beam.hip).
   size_t beam_workspace_bytes(int B, int nb, int S, int max_new) const;
   BeamState beam_state(const Buffers& w, const BeamBuffers& bb, int B, int nb, int seq_ld) const;   // the fields both beam paths share
   int generate_beam(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_beam* beam,
-                    long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st);
+                    long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, int n_best = 1,
+                    int* lens = nullptr, float* scores = nullptr);      // codes [B][n_best][max_new]; lens / scores: HOST [B][n_best]
   int latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws, size_t ws_bytes,
              hipStream_t st);
 
@@ -170,6 +174,8 @@ struct GPTModel : ModelBase {
     std::vector<SlotBeam> beam;       // host image of the SlotBeam table (beam sessions), copied whole at each admission
     size_t ws_bytes = 0;
     std::vector<char> busy;           // admitted and not yet read
+    std::vector<int> prompt;          // greedy / sampled sessions: prompt length P of the request in each busy slot (fork needs it)
+    std::vector<char> first_in;       // ... and whether x_last[slot] still is that request's last prefill row (not after a resume)
     bool warm = false;                // one step has run eagerly (first-use function attributes are set outside a capture)
     int geom = -1;                    // decode geometry the graph was captured under
     StepGraph step;
@@ -197,15 +203,24 @@ struct GPTModel : ModelBase {
   // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's
   // keys and values going to its unit's slots.  *S: positions per prefill row.
   int admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
-                    const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S, hipStream_t st);
-  // per_row: null = every row greedy; else one sampler per row (sampled sessions only)
+                    const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S, hipStream_t st,
+                    const int* takes = nullptr, const int** take_row = nullptr);
+  // takes (fan = 1): request b gets takes[b] slots -- ids and caps then hold one entry per take, request after request -- and its one
+  // prefill row's keys and values go to all of them; *take_row: device array, the prefill row of each take
+  // per_row: null = every row greedy; else one sampler per row (sampled sessions only).  takes: null, or takes[b] >= 1 slots per
+  // request (slot_ids, max_new and per_row then have one entry per take)
   int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr);
+                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr, const int* takes = nullptr);
+  // n further takes of the request in slot src, cut back to `at` codes, in the free slots dst_slots (idxtts.h); samplers: null = greedy
+  // takes; caps: null = the source's cap.  Every refusal happens before anything changes.
+  int session_fork(void* ws, int src, int at, int n, const int* dst_slots, const idxtts_sampling* samplers, const int* caps, hipStream_t st);
   // beam sessions: n requests into the free groups group_ids, each with its own idxtts_beam (num_beams == the session's); every request
   // is checked before any group is taken.  One prefill row per request, its KV fanned out to the group's slots; then its first beam step.
   int session_admit_beam(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* group_ids,
                          const int* max_new, const idxtts_beam* per_request, hipStream_t st);
-  int session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st);
+  int session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st, int n_best = 1,
+                        float* scores = nullptr);
+  int session_read_nbest(void* ws, int slot, int n_best, long long* codes, int* lens, float* scores, hipStream_t st);
   int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
   int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
   // Ends the requests in slot_ids (HOST; beam sessions: the first slot of each group) from outside the step.  evict: they are free at
@@ -237,6 +252,11 @@ struct GPTModel : ModelBase {
 // [nb][seq_ld]) scored at steps_done tokens.  Returns the best hypothesis (tokens point into hyp_seq or seq).
 struct BeamHyp { double score; const int* toks; int len; };
 int beam_finalize(int nb, double length_penalty, int hyp_n, const double* hyp_score, const int* hyp_len, const int* hyp_slot,
-                  const int* hyp_seq, int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best);
+                  const int* hyp_seq, int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best,
+                  int n_best = 1);      // n_best > 1: best [n_best], finalize's order -- best first, of equal scores the one added later first
+
+// The rows an n-best read returns: row q of out [n][ld] = hypothesis q, then the stop token to the end of the row; lens[q] = the
+// hypothesis and the stop token behind it where that fits under `cap`; scores[q] = its score (lens / scores may be null)
+void beam_fill_rows(const BeamHyp* hyps, int n, int ld, int cap, int stop_token, long long* out, int* lens, float* scores);
 
 }  // namespace idxtts

@@ -247,7 +247,7 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   if (mm(L.attn_l, g)) return 1;
   if (store_kv && scatter) {      // decode-session admission: the rows go to their slots' cache regions
     if (kv_store_slots(w.qkv, kv_dst(li, w, scatter->slots), scatter->n, cfg.heads, S, w.Smax, d, scatter->slot_ids, scatter->len, st,
-                       scatter->fan)) return 1;
+                       scatter->fan, scatter->first)) return 1;
   } else if (store_kv) {
     if (kv_store_prefill(w.qkv, kv_dst(li, w, B), B, cfg.heads, S, w.Smax, d, st)) return 1;
   }
@@ -470,8 +470,9 @@ int GPTModel::call_stream(hipStream_t user, hipStream_t* st) {
 // to *captured when that is not null.  Every poll_every steps it reads the poll_n device flags `poll` and stops when all are set.
 int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                              float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll,
-                             int poll_n, int poll_every, int* steps_done, hipStream_t st) {
+                             int poll_n, int poll_every, int* steps_done, hipStream_t st, bool share_prefill) {
   const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1, R = B * fan;
+  if (fan == 1) share_prefill = false;
   // ---- per-call state ----
   std::vector<int> kstart(R, 0);
   for (int r = 0; r < R; ++r) {
@@ -494,18 +495,41 @@ int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const
   IDX_HIP(hipStreamSynchronize(st));
 
   // ---- prefill: x = [inputs_embeds | mel_emb[start] + mel_pos[0]] ----
-  for (int j = 0; j < fan; ++j)      // rows j, fan + j, 2 fan + j, ... from prompts 0, 1, 2, ...
-    IDX_HIP(hipMemcpy2DAsync(w.x + (size_t)j * S * d, (size_t)fan * S * d * sizeof(float), inputs_embeds, (size_t)P * d * sizeof(float),
+  // share_prefill (takes of one prompt: generate(takes > 1)): B prefill rows, one per prompt; each row's keys and values go to its fan
+  // decode rows (the beam admission's fan-out), and so does its last position, the head's input
+  const int Rp = share_prefill ? B : R, pfan = share_prefill ? 1 : fan;
+  for (int j = 0; j < pfan; ++j)      // rows j, fan + j, 2 fan + j, ... from prompts 0, 1, 2, ...
+    IDX_HIP(hipMemcpy2DAsync(w.x + (size_t)j * S * d, (size_t)pfan * S * d * sizeof(float), inputs_embeds, (size_t)P * d * sizeof(float),
                              (size_t)P * d * sizeof(float), B, hipMemcpyDeviceToDevice, st));
   GatherArgs ga;
   ga.out = w.x + (size_t)P * d; ga.ld_out = S * d; ga.d = d;
   ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;           // start_mel_token rows
   ga.table[1] = mel_pos; ga.idx[1] = w.finished;          // all zeros -> mel position 0
-  if (gather_sum_rows(ga, R, st)) return 1;
-  for (int li = 0; li < cfg.layers; ++li)
-    if (layer_full(li, w, R, S, w.kstart, true, st)) return 1;
-  // the first token: the head on the last position of every row
-  if (head_and_sample(w, R, w.x + (size_t)(S - 1) * d, S * d, false, penalty, max_new, logits_out, st)) return 1;
+  if (gather_sum_rows(ga, Rp, st)) return 1;
+  if (share_prefill) {
+    // the prefill rows' own left pads in w.kstart while they run (the decode rows' afterwards); the fan-out's first rows and lengths in
+    // w.cur_tok, which nobody reads between the gather above and the sampler that rewrites it (2 B <= R entries)
+    std::vector<int> pk(B), sc(2 * (size_t)B);
+    for (int b = 0; b < B; ++b) { pk[b] = kstart[(size_t)b * fan]; sc[b] = b * fan; sc[B + b] = S; }
+    IDX_HIP(hipMemcpyAsync(w.kstart, pk.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipMemcpyAsync(w.cur_tok, sc.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipStreamSynchronize(st));      // the staging vectors go out of scope below
+    KvScatter fo;
+    fo.slot_ids = w.cur_tok; fo.len = w.cur_tok + B; fo.n = B; fo.slots = R; fo.fan = fan;
+    for (int li = 0; li < cfg.layers; ++li)
+      if (layer_full(li, w, B, S, w.kstart, true, st, &fo)) return 1;
+    IDX_HIP(hipMemcpyAsync(w.kstart, kstart.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
+    float* const last = w.x + (size_t)B * S * d;      // [R][d] behind the B prefill rows (x holds R * S rows; fan <= (fan - 1) S)
+    for (int j = 0; j < fan; ++j)
+      IDX_HIP(hipMemcpy2DAsync(last + (size_t)j * d, (size_t)fan * d * sizeof(float), w.x + (size_t)(S - 1) * d, (size_t)S * d * sizeof(float),
+                               d * sizeof(float), B, hipMemcpyDeviceToDevice, st));
+    if (head_and_sample(w, R, last, d, false, penalty, max_new, logits_out, st)) return 1;
+  } else {
+    for (int li = 0; li < cfg.layers; ++li)
+      if (layer_full(li, w, R, S, w.kstart, true, st)) return 1;
+    // the first token: the head on the last position of every row
+    if (head_and_sample(w, R, w.x + (size_t)(S - 1) * d, S * d, false, penalty, max_new, logits_out, st)) return 1;
+  }
   if (!fused_tail(w) && advance_state(w.state, st)) return 1;
 
   // ---- decode ----
@@ -555,11 +579,14 @@ static int check_sampling(const idxtts_sampling& r) {
 
 int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
                        const idxtts_sampling* sampling, long long* codes, int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph,
-                       hipStream_t user_stream, const long long* forced) {
+                       hipStream_t user_stream, const long long* forced, int takes) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out, "null pointer");
   GenScope gen_scope(this);
   IDX_CHECK(!forced || !(sampling && sampling->mode != 0), "teacher forcing is a greedy-mode instrument");
-  IDX_CHECK(B > 0 && B <= 64 && P > 0 && max_new > 0, "shape (1 <= B <= 64)");
+  IDX_CHECK(takes >= 1 && (takes == 1 || !forced), "takes >= 1 (teacher forcing: 1)");
+  IDX_CHECK(B > 0 && B * takes <= 64 && P > 0 && max_new > 0, "shape (1 <= B * takes <= 64)");
+  const int prompts = B;      // the prefill's rows; from here on B counts decode rows, row b * takes + j being take j of prompt b
+  B *= takes;
   if (sampling && check_sampling(*sampling)) return 1;
   const int S = P + 1;
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
@@ -593,8 +620,8 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   }
   StepGraph fresh;
   int steps_done = 0;
-  if (run_generation(w, inputs_embeds, pad_left_host, B, 1, P, max_new, penalty, logits_out, graph, exec, cacheable ? &fresh : nullptr,
-                     w.finished, B, 16, &steps_done, st)) return 1;
+  if (run_generation(w, inputs_embeds, pad_left_host, prompts, takes, P, max_new, penalty, logits_out, graph, exec, cacheable ? &fresh : nullptr,
+                     w.finished, B, 16, &steps_done, st, true)) return 1;
   if (fresh.exec) {      // keep it: a free cache slot, or the least recently used idle one
     std::lock_guard<std::mutex> l(graph_mu);
     int slot = -1;
@@ -719,6 +746,8 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.invariant = batch_invariant;
   s.ws_bytes = ws_bytes;
   s.busy.assign(slots, 0);
+  s.prompt.assign(slots, 0);
+  s.first_in.assign(slots, 0);
   s.sampled = sampled;
   if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
   s.num_beams = num_beams;
@@ -736,50 +765,69 @@ int GPTModel::session_release(void* ws) {
 }
 
 int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
-                            const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S_out, hipStream_t st) {
+                            const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S_out, hipStream_t st,
+                            const int* takes, const int** take_row) {
   IDX_CHECK(inputs_embeds && prompt_lens && ids && caps, "null pointer");
+  IDX_CHECK(!takes || (fan == 1 && take_row), "takes belong to sessions of single rows");
   const int units = s.slots / fan;
   IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  int pmax = 0;
+  int pmax = 0, T = 0;      // T: units taken (with takes: ids and caps have one entry per take, request after request)
   std::vector<char> taken(units, 0);
   for (int b = 0; b < n; ++b) {
-    IDX_CHECK(ids[b] >= 0 && ids[b] < units, "slot or group id out of range");
-    IDX_CHECK(!s.busy[ids[b] * fan] && !taken[ids[b]], "slot or group is not free");
-    taken[ids[b]] = 1;
+    const int tb = takes ? takes[b] : 1;
+    IDX_CHECK(tb >= 1 && T + tb <= units, "takes: at least 1 per request, at most the session's slots in all");
+    for (int t = T; t < T + tb; ++t) {
+      IDX_CHECK(ids[t] >= 0 && ids[t] < units, "slot or group id out of range");
+      IDX_CHECK(!s.busy[ids[t] * fan] && !taken[ids[t]], "slot or group is not free");
+      taken[ids[t]] = 1;
+    }
     IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
-    IDX_CHECK(caps[b] >= 1 && caps[b] <= s.max_new, "token cap out of range (1 .. max_new)");
+    for (int t = T; t < T + tb; ++t) IDX_CHECK(caps[t] >= 1 && caps[t] <= s.max_new, "token cap out of range (1 .. max_new)");
+    T += tb;
     pmax = std::max(pmax, prompt_lens[b]);
   }
   // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
   // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
   // exact kernel, and so it does with an fp8 cache; with a bf16 cache in split-bf16 mode gemm_forward takes the split-bf16 kernel from 256 rows on, so the prefill is padded
   // with zero rows (b >= n) to at least 256 rows -- every admission then runs the kernel a generate() batch of >= 256 prefill rows runs.
+  // (A request with takes is one prefill row: it counts once.)
   const int S = pmax + 1;
   int rows = n;
   if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3 && !s.invariant) rows = std::max(n, cdiv(256, S));      // (the mode's prefill is exact)
-  IDX_CHECK((size_t)rows * S <= session_prefill_rows(s.slots, s.max_prompt), "admission prefill exceeds the workspace");
+  const size_t pre = session_prefill_rows(s.slots, s.max_prompt);
+  IDX_CHECK((size_t)rows * S <= pre, "admission prefill exceeds the workspace");
+  // takes: the index arrays of the fan-out live behind the prefill rows' lengths in sb.plen (rows <= pre / 2, n + 1 + T <= 2 slots + 1)
+  IDX_CHECK(!takes || (size_t)rows + n + 1 + T <= pre, "admission index arrays exceed the workspace");
   if (params()) return 1;
-  // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen
-  std::vector<int> stage((size_t)3 * s.slots + rows, 0);
-  for (int b = 0; b < n; ++b) {
-    stage[b] = ids[b] * fan;
-    if (fan > 1) stage[n + b] = ids[b];
-    stage[s.slots + b] = prompt_lens[b] + 1;
-    stage[2 * s.slots + b] = caps[b];
+  // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen | (takes: first [n + 1], row [T])
+  std::vector<int> stage((size_t)3 * s.slots + rows + (takes ? n + 1 + T : 0), 0);
+  for (int t = 0; t < T; ++t) {
+    stage[t] = ids[t] * fan;
+    if (fan > 1) stage[n + t] = ids[t];
+    stage[2 * s.slots + t] = caps[t];
   }
+  for (int b = 0; b < n; ++b) stage[s.slots + b] = prompt_lens[b] + 1;
   for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
-  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), (fan > 1 ? 2 : 1) * n * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots
+  if (takes) {
+    int* const first = stage.data() + 3 * s.slots + rows;
+    for (int b = 0, t = 0; b < n; t += takes[b], ++b) {
+      first[b] = t; first[b + 1] = t + takes[b];
+      for (int j = 0; j < takes[b]; ++j) first[n + 1 + t + j] = b;
+    }
+  }
+  IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), (fan > 1 ? 2 : 1) * T * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots
   IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, rows * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, T * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, (rows + (takes ? n + 1 + T : 0)) * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
 
   if (session_prefill_input(sb.w.x, inputs_embeds, ld_rows, sb.plen, rows, S, cfg.model_dim, mel_emb, mel_pos, cfg.start_mel_token, st))
     return 1;
   KvScatter sc;
   sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = fan;
+  if (takes) { sc.first = sb.plen + rows; *take_row = sb.plen + rows + n + 1; }
   for (int li = 0; li < cfg.layers; ++li)
     if (layer_full(li, sb.w, rows, S, nullptr, true, st, &sc)) return 1;
   *S_out = S;
@@ -787,12 +835,22 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
 }
 
 int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                            const int* caps, hipStream_t st, const idxtts_sampling* per_row) {
+                            const int* caps, hipStream_t st, const idxtts_sampling* per_row, const int* takes) {
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
   IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
   IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots requests");
+  // takes: slot_ids, caps and per_row have one entry per take, request after request (T of them); else one per request
+  int T = n;
+  if (takes) {
+    T = 0;
+    for (int b = 0; b < n; ++b) {
+      IDX_CHECK(takes[b] >= 1 && T + takes[b] <= s.slots, "takes: at least 1 per request, at most the session's slots in all");
+      T += takes[b];
+    }
+  }
   GenScope gen_scope(this);
   const int d = cfg.model_dim, V = cfg.number_mel_codes;
   const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
@@ -800,9 +858,9 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   auto params = [&]() -> int {      // the admitted slots' samplers (greedy when per_row is null); the other rows are rewritten unchanged
     if (!s.sampled) return 0;
     if (per_row)
-      for (int b = 0; b < n; ++b)
+      for (int b = 0; b < T; ++b)
         if (check_sampling(per_row[b])) return 1;
-    for (int b = 0; b < n; ++b) {
+    for (int b = 0; b < T; ++b) {
       SlotSampling& e = s.samp[slot_ids[b]];
       e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
       if (per_row && per_row[b].mode != 0) {
@@ -814,8 +872,9 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
     return 0;
   };
   int S = 0;
-  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st)) return 1;
-  if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, n, st)) return 1;
+  const int* take_row = nullptr;      // takes: the prefill row of each take (device)
+  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st, takes, &take_row)) return 1;
+  if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, T, st, take_row)) return 1;
   // first token of each admitted row: the head on all `slots` rows (the GEMV use_pl(slots) selects, as a generate() of `slots` rows),
   // sampled for the admitted slots only; the sampler writes their first decode input
   if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
@@ -824,9 +883,10 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
   if (use_pl(s.slots)) { sa.embed.x_row = w.xrow; sa.embed.x_stats = w.stats; } else sa.embed.x_frag = w.xd;
   sa.embed.mel_emb = mel_emb; sa.embed.mel_pos = mel_pos; sa.embed.d = d;
-  if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st))
+  if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, T, st) : sample_slots_forward(sa, w.slots, sb.ids, T, st))
     return 1;
-  for (int b = 0; b < n; ++b) s.busy[slot_ids[b]] = 1;
+  for (int b = 0, t = 0; b < n; ++b)
+    for (int j = 0; j < (takes ? takes[b] : 1); ++j, ++t) { s.busy[slot_ids[t]] = 1; s.prompt[slot_ids[t]] = prompt_lens[b]; s.first_in[slot_ids[t]] = 1; }
   return 0;
 }
 
@@ -886,6 +946,17 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   *n_codes = hs.step;
   s.busy[slot] = 0;
   return 0;
+}
+
+int GPTModel::session_read_nbest(void* ws, int slot, int n_best, long long* codes, int* lens, float* scores, hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams > 0, "_read_nbest needs a beam session: every other session holds one sequence per slot (_read)");
+  IDX_CHECK(codes && lens && scores, "null pointer");
+  IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  return session_read_beam(s, sb, slot, codes, lens, st, n_best, scores);
 }
 
 // evict and stop: every id is checked before anything changes; then one launch on the session's stream (ordered between step replays;
@@ -1016,7 +1087,93 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   a.hdr = h; a.blob = const_cast<char*>(static_cast<const char*>(src));
   if (session_resume_slot(a, st)) return 1;
   if (s.sampled) s.samp[slot] = SlotSampling{h.mode, h.temperature, h.top_k, h.top_p, h.seed, reinterpret_cast<const float*>((uintptr_t)h.exp_noise)};
-  s.busy[slot] = 1;
+  s.busy[slot] = 1; s.prompt[slot] = h.pos - h.step; s.first_in[slot] = 0;
+  return 0;
+}
+
+// ---- fork: further takes of a row that is already in the session (idxtts.h "Several takes of one request") ----
+int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slots, const idxtts_sampling* samplers, const int* caps,
+                           hipStream_t st) {
+  Session* sp = find_session(ws);
+  IDX_CHECK(sp, "no decode session on this workspace");
+  Session& s = *sp;
+  IDX_CHECK(s.num_beams == 0, "a beam session's rows cannot be forked: beams of a group are not independent requests");
+  IDX_CHECK(dst_slots && n >= 1 && n < s.slots, "fork to 1 .. slots - 1 destinations");
+  IDX_CHECK(!samplers || s.sampled, "a sampled take needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  IDX_CHECK(src >= 0 && src < s.slots, "source slot out of range");
+  IDX_CHECK(s.busy[src], "source slot holds no request");
+  IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
+  IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
+  std::vector<char> taken(s.slots, 0);
+  for (int j = 0; j < n; ++j) {
+    IDX_CHECK(dst_slots[j] >= 0 && dst_slots[j] < s.slots, "destination slot out of range");
+    IDX_CHECK(dst_slots[j] != src, "a destination is the source slot");
+    IDX_CHECK(!s.busy[dst_slots[j]] && !taken[dst_slots[j]], "destination slot is not free");
+    taken[dst_slots[j]] = 1;
+  }
+  if (samplers)
+    for (int j = 0; j < n; ++j)
+      if (check_sampling(samplers[j])) return 1;
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const Buffers& w = sb.w;
+  const int V = cfg.number_mel_codes, d = cfg.model_dim;
+  SlotState hs;
+  IDX_HIP(hipMemcpyAsync(&hs, w.slots + src, sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  IDX_CHECK(hs.step >= 1 && hs.step <= hs.max_step && hs.max_step <= s.max_new && hs.pos >= 1 && hs.pos <= w.Smax, "slot state corrupt");
+  // a row that ended on the stop token has nothing behind it: a take may keep at most the codes in front of the stop token
+  int most = hs.step;
+  if (!hs.live) {
+    long long last = 0;
+    IDX_HIP(hipMemcpyAsync(&last, w.codes + (size_t)src * s.max_new + hs.step - 1, sizeof(last), hipMemcpyDeviceToHost, st));
+    IDX_HIP(hipStreamSynchronize(st));
+    if (last == cfg.stop_mel_token) most = hs.step - 1;
+  }
+  if (at == -1) at = most;      // where the source stands now
+  IDX_CHECK(at >= 0 && at <= most, "at out of range (0 .. the source's codes, the stop token not among them)");
+  const int P = s.prompt[src];      // (an ended row's pos does not say: it stays behind when the row ends by itself, not when it is stopped)
+  IDX_CHECK(P >= 1 && P <= s.max_prompt && P + hs.step - 1 <= hs.pos && hs.pos <= P + hs.step, "slot state corrupt");
+  IDX_CHECK(at > 0 || s.first_in[src], "at = 0 needs a source that still has its prefill output: a resumed row (and a take of one) does not");
+  ForkArgs a;
+  for (int j = 0; j < n; ++j) {
+    const int cap = caps ? caps[j] : hs.max_step;
+    IDX_CHECK(cap >= 1 && cap <= s.max_new, "token cap out of range (1 .. max_new)");
+    IDX_CHECK(cap > at, "a take's cap must leave it a code to produce (cap > at)");
+    IDX_CHECK((long long)P + 1 + cap <= w.Smax, "the take does not fit the session's cache");
+    a.dst[j] = (unsigned char)dst_slots[j]; a.cap[j] = cap;
+  }
+  GenScope gen_scope(this);
+  a.kv_fmt = s.kv_fmt; a.layers = cfg.layers; a.heads = cfg.heads; a.V = V; a.start_token = cfg.start_mel_token;
+  a.src = src; a.P = P; a.at = at; a.n = n;
+  a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
+  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
+  a.Smax = w.Smax; a.slots = w.slots; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new; a.cur_tok = w.cur_tok;
+  a.x_last = sb.x_last; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots;
+  if (session_fork_slots(a, st)) return 1;      // (its own checks come before its launch: from here on nothing refuses)
+  if (s.sampled) {      // the takes' samplers (greedy when samplers is null); the other rows are rewritten unchanged
+    for (int j = 0; j < n; ++j) {
+      SlotSampling& e = s.samp[dst_slots[j]];
+      e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
+      if (samplers && samplers[j].mode != 0) {
+        const idxtts_sampling& r = samplers[j];
+        e = SlotSampling{r.mode, r.temperature, r.top_k, r.top_p, r.seed, r.exp_noise};
+      }
+    }
+    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
+  }
+  if (at == 0) {      // the takes' first token: the admission's head-and-sample pass on the destinations
+    std::vector<int> ids(dst_slots, dst_slots + n);
+    IDX_HIP(hipMemcpyAsync(sb.ids, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
+    if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
+    SampleArgs sa;
+    sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
+    sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
+    sa.embed = tail_embed(w, use_pl(s.slots));
+    if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st))
+      return 1;
+  }
+  for (int j = 0; j < n; ++j) { s.busy[dst_slots[j]] = 1; s.prompt[dst_slots[j]] = P; s.first_in[dst_slots[j]] = s.first_in[src]; }
   return 0;
 }
 

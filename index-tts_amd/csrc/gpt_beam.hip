@@ -34,7 +34,7 @@ BeamBuffers carve_beam(void* ws, int B, int nb, int V, int max_new) {
 }
 
 int beam_finalize(int nb, double lp, int hyp_n, const double* hyp_score, const int* hyp_len, const int* hyp_slot, const int* hyp_seq,
-                  int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best) {
+                  int seq_ld, bool done, const float* bscore, const int* seq, int steps_done, BeamHyp* best, int n_best) {
   std::vector<BeamHyp> list;
   for (int q = 0; q < hyp_n; ++q) list.push_back(BeamHyp{hyp_score[q], &hyp_seq[(size_t)hyp_slot[q] * seq_ld], hyp_len[q]});
   if (!done) {      // open beams become hypotheses (BeamHypotheses.add with its keep-the-best rule)
@@ -57,10 +57,19 @@ int beam_finalize(int nb, double lp, int hyp_n, const double* hyp_score, const i
     }
   }
   IDX_CHECK(!list.empty(), "no hypothesis");
-  size_t bi = 0;       // sorted(..., key=score).pop(): the largest score, the LAST of equals
-  for (size_t q = 1; q < list.size(); ++q) if (list[q].score >= list[bi].score) bi = q;
-  *best = list[bi];
+  // sorted(..., key=score), popped from the end n_best times: best first, among equal scores the one added LATER first
+  IDX_CHECK(n_best >= 1 && (size_t)n_best <= list.size(), "fewer hypotheses than n_best");
+  std::stable_sort(list.begin(), list.end(), [](const BeamHyp& a, const BeamHyp& b) { return a.score < b.score; });
+  for (int q = 0; q < n_best; ++q) best[q] = list[list.size() - 1 - q];
   return 0;
+}
+
+void beam_fill_rows(const BeamHyp* hyps, int n, int ld, int cap, int stop_token, long long* out, int* lens, float* scores) {
+  for (int q = 0; q < n; ++q) {
+    for (int t = 0; t < ld; ++t) out[(size_t)q * ld + t] = t < hyps[q].len ? hyps[q].toks[t] : stop_token;
+    if (lens) lens[q] = std::min(hyps[q].len + 1, cap);
+    if (scores) scores[q] = (float)hyps[q].score;
+  }
 }
 
 size_t GPTModel::beam_workspace_bytes(int B, int nb, int S, int max_new) const {
@@ -94,8 +103,9 @@ static int check_beam(const idxtts_beam& r) {
 
 int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
                             const idxtts_beam* beam, long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph,
-                            hipStream_t user_stream) {
+                            hipStream_t user_stream, int n_best, int* lens, float* scores) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out && beam, "null pointer");
+  IDX_CHECK(n_best >= 1 && n_best <= beam->num_beams, "1 <= n_best <= num_beams");
   GenScope gen_scope(this);
   const int nb = beam->num_beams, R = B * nb;
   IDX_CHECK(nb >= 2 && nb <= BEAM_MAX, "2 <= num_beams <= 8");
@@ -142,18 +152,19 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
   IDX_HIP(hipMemcpyAsync(bscore.data(), bb.beam_scores, R * sizeof(float), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipMemcpyAsync(done.data(), bb.done, B * sizeof(int), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
-  std::vector<BeamHyp> best(B);
+  // codes [B][n_best][max_new]: each hypothesis, then eos if it fits (already the fill value), stop-padded
+  std::vector<BeamHyp> best((size_t)B * n_best);
   int longest = 0;
   for (int b = 0; b < B; ++b) {
     const size_t o = (size_t)b * (BEAM_MAX + 1);
     if (beam_finalize(nb, (double)beam->length_penalty, hyp_n[b], &hyp_score[o], &hyp_len[o], &hyp_slot[o], &hyp_seq[o * max_new], max_new,
-                      done[b] != 0, &bscore[(size_t)b * nb], &seq[(size_t)b * nb * max_new], steps_done, &best[b])) return 1;
-    longest = std::max(longest, best[b].len);
+                      done[b] != 0, &bscore[(size_t)b * nb], &seq[(size_t)b * nb * max_new], steps_done, &best[(size_t)b * n_best], n_best))
+      return 1;
+    for (int q = 0; q < n_best; ++q) longest = std::max(longest, best[(size_t)b * n_best + q].len);
   }
   const int n_out = std::min(longest + 1, max_new);          // min(sent_lengths.max() + 1, max_length) - prompt
-  std::vector<long long> out((size_t)B * max_new, cfg.stop_mel_token);
-  for (int b = 0; b < B; ++b)
-    for (int t = 0; t < best[b].len; ++t) out[(size_t)b * max_new + t] = best[b].toks[t];      // then eos if it fits: already the fill value
+  std::vector<long long> out((size_t)B * n_best * max_new);
+  beam_fill_rows(best.data(), B * n_best, max_new, max_new, cfg.stop_mel_token, out.data(), lens, scores);
   IDX_HIP(hipMemcpyAsync(codes, out.data(), out.size() * sizeof(long long), hipMemcpyHostToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));
   *n_steps_out = n_out;
@@ -202,8 +213,10 @@ int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, in
 
 // BeamSearchScorer.finalize of the group whose first slot is `slot`, with the steps it took: its best hypothesis, then the stop token
 // if it fits under the cap (row 0 of generate_beam's codes, cut after its first stop token)
-int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st) {
+int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st, int n_best,
+                                float* scores) {
   const int nb = s.num_beams, g = slot / nb, L = s.max_new;
+  IDX_CHECK(n_best >= 1 && n_best <= nb, "1 <= n_best <= num_beams");
   IDX_CHECK(slot % nb == 0, "a beam session is read at the first slot of a group");
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
@@ -226,16 +239,15 @@ int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, 
   IDX_HIP(hipMemcpyAsync(&done, bb.done + g, sizeof(int), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   IDX_CHECK(hyp_n >= 0 && hyp_n <= nb, "group state corrupt");
-  BeamHyp best;
+  // n_best = 1: codes holds the hypothesis alone (n_codes[0] entries); else codes [n_best][L], every row stop-padded to L
+  std::vector<BeamHyp> best(n_best);
   if (beam_finalize(nb, s.beam[g].length_penalty, hyp_n, hyp_score.data(), hyp_len.data(), hyp_slot.data(), hyp_seq.data(), L, done != 0,
-                    bscore.data(), seq.data(), hs.step, &best)) return 1;
-  IDX_CHECK(best.len >= 0 && best.len <= hs.max_step, "group state corrupt");
-  const int n_out = std::min(best.len + 1, hs.max_step);
-  std::vector<long long> out(n_out, cfg.stop_mel_token);
-  for (int t = 0; t < best.len; ++t) out[t] = best.toks[t];
-  IDX_HIP(hipMemcpyAsync(codes, out.data(), n_out * sizeof(long long), hipMemcpyHostToDevice, st));
+                    bscore.data(), seq.data(), hs.step, best.data(), n_best)) return 1;
+  for (const BeamHyp& h : best) IDX_CHECK(h.len >= 0 && h.len <= hs.max_step, "group state corrupt");
+  std::vector<long long> out((size_t)n_best * L);
+  beam_fill_rows(best.data(), n_best, L, hs.max_step, cfg.stop_mel_token, out.data(), n_codes, scores);
+  IDX_HIP(hipMemcpyAsync(codes, out.data(), (n_best == 1 ? (size_t)n_codes[0] : out.size()) * sizeof(long long), hipMemcpyHostToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));
-  *n_codes = n_out;
   for (int j = 0; j < nb; ++j) s.busy[slot + j] = 0;
   return 0;
 }

@@ -29,6 +29,8 @@ SYMBOLS = [
     "idxtts_gpt_session_admit_beam", "idxtts_gpt_session_evict", "idxtts_gpt_session_stop",
     "idxtts_gpt_session_park_bytes", "idxtts_gpt_session_park", "idxtts_gpt_session_resume",
     "idxtts_gpt_session_park_group_bytes", "idxtts_gpt_session_park_group", "idxtts_gpt_session_resume_group",
+    "idxtts_gpt_session_admit_takes", "idxtts_gpt_session_fork", "idxtts_gpt_generate_beam_nbest", "idxtts_gpt_session_read_nbest",
+    "idxtts_beam_finalize_host", "idxtts_gpt_generate_takes",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
@@ -209,6 +211,16 @@ def load() -> ctypes.CDLL:
     lib.idxtts_gpt_session_init_ex.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p]
     lib.idxtts_gpt_session_admit_sampled.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_void_p]
+    lib.idxtts_gpt_session_admit_takes.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p]
+    lib.idxtts_gpt_session_fork.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_generate_beam_nbest.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, POINTER(BeamC), c_int, c_void_p,
+                                                   c_void_p, c_void_p, POINTER(c_int), c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_gpt_generate_takes.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
+                                              POINTER(c_int), c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_beam_finalize_host.argtypes = [c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                              c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_read_nbest.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_session_workspace_bytes_beam.argtypes = [c_void_p, c_int, c_int, c_int, c_int]
     lib.idxtts_gpt_session_workspace_bytes_beam.restype = c_size_t
     lib.idxtts_gpt_session_init_beam.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]

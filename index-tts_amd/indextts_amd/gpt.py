@@ -261,9 +261,17 @@ class UnifiedVoice:
                  repetition_penalty: float = 10.0, return_logits: bool = False, use_graph: bool = True,
                  do_sample: bool = False, sampler: str = "hf", exp_noise: Optional[torch.Tensor] = None,
                  generator: Optional[torch.Generator] = None, forced_codes: Optional[torch.Tensor] = None,
-                 seed: Optional[int] = None) -> torch.Tensor:
+                 seed: Optional[int] = None, num_return_sequences: int = 1) -> torch.Tensor:
         """The accel-engine plugin contract (accel_engine.py:378-645): returns LongTensor [B, P+1+generated]
         (prompt ids followed by the generated codes, padded with the stop token).
+
+        num_return_sequences=n > 1: n takes of every prompt, rows expanded as HF's _expand_inputs_for_generation does
+        (repeat_interleave: row b * n + j is take j of prompt b); returns [B * n, P+1+generated].  exp_noise is then
+        [max_new_tokens, B * n, V] and a seeded call draws the stream of row b * n + j of a B * n-row call, so the result equals generate
+        on the caller-expanded batch wherever the two prefills choose the same kernels -- the prefill runs once per prompt, on B rows,
+        and each row's keys and values are written to its n takes' cache rows (`idxtts_gpt_generate_takes`).  That holds always with
+        an fp32 (or fp8) KV cache or in the batch-invariant mode; with a bf16 cache in split-bf16 GEMM mode when B * (P + 1) and
+        B * n * (P + 1) lie on the same side of 256 prefill rows.
 
         do_sample=False: greedy (temperature / top_k / top_p ignored).  do_sample=True: multinomial sampling,
         sampler="hf" = HF `_sample` with its warpers (repetition penalty -> temperature -> top-k -> top-p -> multinomial,
@@ -279,13 +287,22 @@ class UnifiedVoice:
         if stop_tokens is not None and list(stop_tokens) != [self.cfg.stop_mel_token]:
             raise ValueError("stop_tokens must be [stop_mel_token]")
         emb = tts_embeddings.to(self.device, torch.float32).contiguous()
+        nrs = int(num_return_sequences)
+        if nrs < 1:
+            raise ValueError("num_return_sequences must be >= 1")
+        if nrs > 1:
+            if forced_codes is not None:
+                raise ValueError("forced_codes is a single-sequence instrument (num_return_sequences must be 1)")
         B, P, d = emb.shape
         if input_ids.shape != (B, P + 1):
             raise ValueError("input_ids must be [B, P+1] (fake prefix + start_mel_token)")
-        pad_left = np.zeros(B, np.int32)
+        pad_left = np.zeros(B, np.int32)      # one entry per prompt: the prefill runs on the B prompts, the takes share it
         if attention_mask is not None:
             am = attention_mask.detach().cpu().numpy()
             pad_left = (am[:, :P] == 0).sum(1).astype(np.int32)
+        prompts, B = B, B * nrs               # from here on B counts decode rows (row b * n + j: take j of prompt b)
+        if nrs > 1:
+            input_ids = input_ids.repeat_interleave(nrs, dim=0)
         codes = torch.full((B, max_new_tokens), self.cfg.stop_mel_token, dtype=torch.long, device=self.device)
         V = self.cfg.number_mel_codes
         logits = torch.zeros(max_new_tokens, B, V, device=self.device) if return_logits else None
@@ -301,6 +318,12 @@ class UnifiedVoice:
                                 top_k=int(top_k or 0) if sampler == "hf" else 0,
                                 top_p=float(top_p if top_p is not None else 1.0) if sampler == "hf" else 1.0,
                                 exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
+        if nrs > 1:
+            _lib.check(_lib.load().idxtts_gpt_generate_takes(
+                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
+                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits),
+                _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
+        elif do_sample:
             _lib.check(_lib.load().idxtts_gpt_generate_sampled(
                 self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty),
                 ctypes.byref(sc), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph),
@@ -338,9 +361,12 @@ class UnifiedVoice:
                       num_beams: int = 3, do_sample: bool = True, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
                       repetition_penalty: float = 1.0, length_penalty: float = 1.0, early_stopping: bool = False,
                       exp_noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, use_graph: bool = True,
-                      seed: Optional[int] = None) -> torch.Tensor:
+                      seed: Optional[int] = None, num_return_sequences: int = 1, return_scores: bool = False):
         """HF `generate(num_beams > 1)` of the reference (model_v2.py:885-889 -> transformers_generation_utils.py:3325-3516):
         beam search, or beam-sample when do_sample.  Returns LongTensor [B, P+1+n]: the best hypothesis per utterance.
+        num_return_sequences=n (1 <= n <= num_beams): the scorer's n best hypotheses of every utterance, best first (row b * n + j;
+        BeamSearchScorer.finalize's order: of equal scores the one added later first) -- for n > 1, or with return_scores, the result is
+        (sequences [B * n, P+1+L], sequences_scores fp32 [B * n]); row b * n of it is bit for bit row b of the n = 1 call.
         Sampling draws 2 * num_beams candidates per utterance without replacement: torch.multinomial == top-k of probs / q with
         q ~ Exp(1) from one exponential_() per step on a [B, num_beams * V] tensor -- `exp_noise` [max_new_tokens, B, num_beams*V]
         supplies them, or `generator` draws them on the CPU in that order; with neither the kernels generate them from `seed` (see _noise)."""
@@ -362,15 +388,26 @@ class UnifiedVoice:
         if need == 0:
             raise RuntimeError("idxtts_gpt_beam_workspace_bytes returned 0")
         ws = self._workspace_bytes(need)
-        codes = torch.full((B, max_new_tokens), self.cfg.stop_mel_token, dtype=torch.long, device=self.device)
+        nrs = int(num_return_sequences)
+        if not 1 <= nrs <= nb:
+            raise ValueError("1 <= num_return_sequences <= num_beams")
+        codes = torch.full((B * nrs, max_new_tokens), self.cfg.stop_mel_token, dtype=torch.long, device=self.device)
         bc = _lib.BeamC(num_beams=nb, do_sample=int(bool(do_sample)), temperature=float(temperature), top_k=int(top_k or 0),
                         top_p=float(top_p if top_p is not None else 1.0), length_penalty=float(length_penalty),
                         early_stopping=int(bool(early_stopping)), exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
         n = ctypes.c_int(0)
-        _lib.check(lib.idxtts_gpt_generate_beam(self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens,
-                                                float(repetition_penalty), ctypes.byref(bc), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(ws),
-                                                ws.numel(), int(use_graph), _lib.current_stream()))
-        return torch.cat([input_ids.to(self.device), codes[:, : n.value]], dim=1)
+        if nrs == 1 and not return_scores:
+            _lib.check(lib.idxtts_gpt_generate_beam(self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens,
+                                                    float(repetition_penalty), ctypes.byref(bc), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(ws),
+                                                    ws.numel(), int(use_graph), _lib.current_stream()))
+            return torch.cat([input_ids.to(self.device), codes[:, : n.value]], dim=1)
+        lens, scores = np.zeros(B * nrs, np.int32), np.zeros(B * nrs, np.float32)
+        _lib.check(lib.idxtts_gpt_generate_beam_nbest(
+            self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), ctypes.byref(bc), nrs,
+            _lib.ptr(codes), lens.ctypes.data_as(c_void_p), scores.ctypes.data_as(c_void_p), ctypes.byref(n), _lib.ptr(ws), ws.numel(),
+            int(use_graph), _lib.current_stream()))
+        seqs = torch.cat([input_ids.to(self.device).repeat_interleave(nrs, dim=0), codes[:, : n.value]], dim=1)
+        return seqs, torch.from_numpy(scores).to(self.device)
 
     def inference_speech(self, speech_condition, text_inputs, emo_speech_condition=None, cond_lengths=None, emo_cond_lengths=None,
                          emo_vec=None, use_speed=False, input_tokens=None, num_return_sequences=1, max_generate_length=None,
@@ -380,11 +417,13 @@ class UnifiedVoice:
         819-828) or -- hoisted out of the caller's segment loop -- the ready conditioning latent [B, 32, d] together with `emo_vec`.
         Decoding modes = HF generate's: greedy (do_sample=False, num_beams=1), multinomial sampling with the warpers
         (do_sample=True, num_beams=1; extra kwargs `exp_noise` / `generator` / `sampler`, see generate()), beam search and
-        beam-sample (num_beams > 1: generate_beam())."""
+        beam-sample (num_beams > 1: generate_beam()).  num_return_sequences=n: codes [B * n, L], row b * n + j take j of utterance b --
+        n sampled takes (generate()), or the n best beam hypotheses (n <= num_beams), as HF's generate returns them."""
         if input_tokens is not None or typical_sampling or use_speed:
             raise NotImplementedError("input_tokens / typical_sampling / use_speed are not used by IndexTTS2.infer and not implemented")
-        if num_return_sequences != 1:
-            raise NotImplementedError("num_return_sequences must be 1")
+        nrs = int(num_return_sequences)
+        if nrs < 1:
+            raise ValueError("num_return_sequences must be >= 1")
         sc = speech_condition if speech_condition.ndim == 3 else speech_condition.unsqueeze(0)
         if sc.shape[-1] == self.cfg.cond_module.input_size and sc.shape[-1] != self.cfg.model_dim:      # raw features
             if emo_speech_condition is None:
@@ -420,11 +459,16 @@ class UnifiedVoice:
             if return_logits:
                 raise NotImplementedError("return_logits is a num_beams=1 feature")
             out = self.generate_beam(input_ids, max_new, attention_mask, inputs_embeds, num_beams=num_beams, repetition_penalty=penalty,
-                                     length_penalty=length_penalty, early_stopping=early_stopping, use_graph=use_graph, **samp)
+                                     length_penalty=length_penalty, early_stopping=early_stopping, use_graph=use_graph,
+                                     num_return_sequences=nrs, **samp)
+            out = out[0] if nrs > 1 else out
             return out[:, trunc_index:], speech_conditioning_latent
+        if nrs > 1 and return_logits:
+            raise NotImplementedError("return_logits is a num_return_sequences=1 feature")
         out = self.generate(input_ids, max_new_tokens=max_new, stop_tokens=[self.cfg.stop_mel_token],
                             attention_mask=attention_mask, tts_embeddings=inputs_embeds, repetition_penalty=penalty,
-                            return_logits=return_logits, sampler=sampler, use_graph=use_graph, forced_codes=forced_codes, **samp)
+                            return_logits=return_logits, sampler=sampler, use_graph=use_graph, forced_codes=forced_codes,
+                            num_return_sequences=nrs, **samp)
         if return_logits:
             return out[0][:, trunc_index:], speech_conditioning_latent, out[1]
         return out[:, trunc_index:], speech_conditioning_latent
@@ -728,6 +772,7 @@ class DecodeSession(_Session):
 
     def _samplers(self, sampling, caps):
         """sampling (one dict per row, or one dict for every row) -> (SamplingC array, noise tensors); raises ValueError on a bad row."""
+        caps = [None] * len(sampling) if caps is None else caps
         entries = [sampling] * len(caps) if isinstance(sampling, dict) else list(sampling)
         if len(entries) != len(caps):
             raise ValueError("sampling: one entry per row, or one entry for every row")
@@ -768,17 +813,24 @@ class DecodeSession(_Session):
             noises.append(noise)
         return arr, noises
 
-    def admit(self, inputs_embeds_rows, max_new_each, sampling=None) -> list:
+    def admit(self, inputs_embeds_rows, max_new_each, sampling=None, takes=None, slots=None):
         """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int).
-        sampling (sampled sessions): None = every row greedy, else one dict per row or one for every row (see the class)."""
+        sampling (sampled sessions): None = every row greedy, else one dict per row or one for every row (see the class).
+        takes (an int for every row, or one per row): that many takes of each request -- its prefill runs once, its keys and values go
+        to all of its takes' slots, and every take is an ordinary row from then on.  The result is then a list of slot lists, one per
+        request; max_new_each and sampling may be given per request (each take of it gets them; a seeded entry would make the takes
+        equal, so give seeds per take) or per take, as a list of lists.  Take j's codes equal those of the same prompt admitted alone
+        with its sampler.  slots: the free slots to use, in order (default: the first free ones)."""
         if len(inputs_embeds_rows) == 0:
             return []
+        if takes is not None:
+            return self._admit_takes(inputs_embeds_rows, max_new_each, sampling, takes, slots)
         free = self.free_slots
         rows, plen, caps = self._stage(inputs_embeds_rows, max_new_each, free)
         n = len(rows)
         if sampling is not None and not self.sampled:
             raise ValueError("sampling= needs a session created with sampled=True")
-        ids = free[:n]
+        ids = self._pick(slots, n, free)
         self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
         with torch.cuda.stream(self.stream):
             samplers, noises = self._samplers(sampling, caps) if sampling is not None else (None, [None] * n)
@@ -792,6 +844,118 @@ class DecodeSession(_Session):
                 _lib.check(self._lib.idxtts_gpt_session_admit_sampled(
                     self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
                     h_caps.ctypes.data_as(c_void_p), ctypes.cast(samplers, c_void_p), _lib.ptr(self._ws), self._sp()))
+        for i, nz in zip(ids, noises):
+            self._busy[i] = True
+            if nz is not None:
+                self._noise[i] = nz
+        return ids
+
+    def _pick(self, slots, n: int, free: list) -> list:
+        """The n slots an admission takes: the first free ones, or the caller's choice (free, distinct)."""
+        if slots is None:
+            if n > len(free):
+                raise RuntimeError(f"{n} rows but {len(free)} free slots")
+            return free[:n]
+        ids = [int(i) for i in slots]
+        if len(ids) != n or len(set(ids)) != n or any(i not in free for i in ids):
+            raise ValueError(f"slots= must name {n} distinct free slots")
+        return ids
+
+    @staticmethod
+    def _per_take(value, tk: list, what: str) -> list:
+        """One value for all, one per request, or a list per request with one per take -> a flat list, one per take."""
+        if isinstance(value, (int, dict)) or value is None:
+            return [value] * sum(tk)
+        value = list(value)
+        if len(value) != len(tk):
+            raise ValueError(f"{what}: one entry per request (or a list per request with one entry per take)")
+        flat = []
+        for v, t in zip(value, tk):
+            if isinstance(v, (list, tuple)):
+                if len(v) != t:
+                    raise ValueError(f"{what}: a request's list must have one entry per take")
+                flat.extend(v)
+            else:
+                flat.extend([v] * t)
+        return flat
+
+    def _admit_takes(self, inputs_embeds_rows, max_new_each, sampling, takes, slots) -> list:
+        n = len(inputs_embeds_rows)
+        tk = [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
+        if len(tk) != n or any(t < 1 for t in tk):
+            raise ValueError("takes: one count >= 1 per row (or one int for every row)")
+        if sampling is not None and not self.sampled:
+            raise ValueError("sampling= needs a session created with sampled=True")
+        T = sum(tk)
+        free = self.free_slots
+        if T > len(free) and slots is None:
+            raise RuntimeError(f"{T} takes but {len(free)} free slots")
+        ids = self._pick(slots, T, free)
+        caps_t = [int(c) for c in self._per_take(max_new_each, tk, "max_new_each")]
+        rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
+        if any(not 1 <= c <= self.max_new for c in caps_t):
+            raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        with torch.cuda.stream(self.stream):
+            samplers, noises = (self._samplers(self._per_take(sampling, tk, "sampling"), caps_t) if sampling is not None
+                                else (None, [None] * T))
+            emb, pm = self._embed_rows(rows, plen)
+            h_p, h_t, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, tk, ids, caps_t))
+            _lib.check(self._lib.idxtts_gpt_session_admit_takes(
+                self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_t.ctypes.data_as(c_void_p),
+                h_ids.ctypes.data_as(c_void_p), h_caps.ctypes.data_as(c_void_p),
+                ctypes.cast(samplers, c_void_p) if samplers is not None else c_void_p(0), _lib.ptr(self._ws), self._sp()))
+        for i, nz in zip(ids, noises):
+            self._busy[i] = True
+            if nz is not None:
+                self._noise[i] = nz
+        out, o = [], 0
+        for t in tk:
+            out.append(ids[o:o + t])
+            o += t
+        return out
+
+    def fork(self, slot: int, samplers=None, at=None, caps=None, n=None, slots=None) -> list:
+        """Further takes of the request in `slot`, branching where it stood after `at` codes (default: where it stands now): one per
+        entry of `samplers` (dicts as in admit(sampling=...); exp_noise [cap, V], rows below `at` are never read), or `n` greedy takes
+        when samplers is None.  The source may be decoding, or finished and not taken; it is only read.  One launch on the session's
+        stream copies what the source holds for its first `at` codes -- keys and values read once, written to every take -- into free
+        slots (`slots`, or the first free ones), which are returned; each take decodes on from the next step() with its own sampler
+        and cap (caps: one per take or one int; default the source's, or the row count of a take's exp_noise).  A take forked at k with explicit draws that equal the source's
+        below k returns, bit for bit, the codes of a fresh admission with those draws; a seeded take draws from its own seed from step
+        k on.  at = 0 redraws the first token too (not on a row that came in through resume()).  A refusal raises, nothing changes."""
+        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots or not self._busy[int(slot)]:
+            raise ValueError(f"{slot!r} holds no request (slot ids 0 .. {self.slots - 1})")
+        slot = int(slot)
+        if samplers is not None and not self.sampled:
+            raise ValueError("samplers= needs a session created with sampled=True")
+        if samplers is None:
+            k = 1 if n is None else int(n)
+        else:
+            samplers = [samplers] if isinstance(samplers, dict) else list(samplers)
+            k = len(samplers)
+            if n is not None and int(n) != k:
+                raise ValueError("n differs from the number of samplers")
+        if k < 1:
+            raise ValueError("fork to at least one take")
+        ids = self._pick(slots, k, self.free_slots)
+        caps_t = None if caps is None else [int(caps)] * k if isinstance(caps, (int, np.integer)) else [int(c) for c in caps]
+        if caps_t is None and samplers is not None and any(e.get("exp_noise") is not None for e in samplers):
+            # explicit draws are [cap, V]: a take that brings them says its cap with their row count (the source's cap: NULL below)
+            if any(e.get("exp_noise") is None for e in samplers):
+                raise ValueError("caps=: needed when only some takes carry exp_noise")
+            caps_t = [int(torch.as_tensor(e["exp_noise"]).shape[0]) for e in samplers]
+        if caps_t is not None and (len(caps_t) != k or any(not 1 <= c <= self.max_new for c in caps_t)):
+            raise ValueError(f"caps: one per take, in 1 .. {self.max_new}")
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the draws may come from another stream
+        with torch.cuda.stream(self.stream):
+            arr, noises = self._samplers(samplers, caps_t) if samplers is not None else (None, [None] * k)
+            h_ids = np.ascontiguousarray(ids, dtype=np.int32)
+            h_caps = np.ascontiguousarray(caps_t, dtype=np.int32) if caps_t is not None else None
+            _lib.check(self._lib.idxtts_gpt_session_fork(
+                self.gpt._h, slot, -1 if at is None else int(at), k, h_ids.ctypes.data_as(c_void_p),
+                ctypes.cast(arr, c_void_p) if arr is not None else c_void_p(0),
+                h_caps.ctypes.data_as(c_void_p) if h_caps is not None else c_void_p(0), _lib.ptr(self._ws), self._sp()))
         for i, nz in zip(ids, noises):
             self._busy[i] = True
             if nz is not None:
@@ -964,9 +1128,27 @@ class BeamDecodeSession(_Session):
                 self._noise[g] = nz
         return ids
 
-    def take(self, group: int) -> torch.Tensor:
-        """The codes of the finished request in `group` (LongTensor on the device); the group is free again."""
-        return super().take(group)
+    def take(self, group: int, n_best=None):
+        """The codes of the finished request in `group` (LongTensor on the device); the group is free again.
+        n_best (1 .. num_beams): the scorer's n_best best hypotheses instead, best first -- a list of (codes, score), each codes as the
+        plain take() cuts it (the hypothesis, then the stop token where it fits under the cap), in generate_beam(num_return_sequences=)'s
+        order; entry 0's codes are bit for bit what take(group) returns."""
+        if n_best is None:
+            return super().take(group)
+        n_best = int(n_best)
+        if not 1 <= n_best <= self.num_beams:
+            raise ValueError("1 <= n_best <= num_beams")
+        lens, scores = np.zeros(n_best, np.int32), np.zeros(n_best, np.float32)
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(n_best, self.max_new, dtype=torch.long, device=self.gpt.device)
+            _lib.check(self._lib.idxtts_gpt_session_read_nbest(self.gpt._h, int(group) * self._unit, n_best, _lib.ptr(out),
+                                                               lens.ctypes.data_as(c_void_p), scores.ctypes.data_as(c_void_p),
+                                                               _lib.ptr(self._ws), self._sp()))
+        self._busy[group] = False
+        self._done.discard(group)
+        self._noise.pop(group, None)
+        return [(out[q, : int(lens[q])], float(scores[q])) for q in range(n_best)]
 
     def park(self, group: int):
         raise NotImplementedError("one row of a beam group cannot leave it: park the whole group with park_group()")

@@ -427,12 +427,23 @@ class IndexTTS2:
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, return_audio=False,
-              return_numpy=False, **generation_kwargs):
+              return_numpy=False, takes=1, **generation_kwargs):
         """Reference signature and return contract (infer_v2.py:541-567): the generator itself when `stream_return`, else its
         first (only) item -- the output path, an InferenceResult, or (sampling_rate, int16 [n, 1]) -- or None for empty input.
+        takes=n > 1: n takes of the whole text, one after the other, each drawing on from where the last one left the generators --
+        a list of n results; with an output path the files are `stem.takeK.ext`, K = 0 .. n - 1.  Refused with `stream_return`.
         `spk_audio_prompt` (and `emo_audio_prompt`): a WAV file path as in the reference, or a PromptAudio / PromptFeatures /
         PromptConditioning; `text`: a string (needs self.tokenizer), a list of token-id segments (List[List[int]]) or one segment
         (List[int] / 1-D tensor)."""
+        takes = int(takes)
+        if takes < 1 or (takes > 1 and stream_return):
+            raise ValueError("takes must be >= 1, and takes > 1 does not stream (stream_return)")
+        if takes > 1:
+            stem, ext = os.path.splitext(output_path) if output_path else (None, "")
+            return [self.infer(spk_audio_prompt, text, f"{stem}.take{k}{ext}" if stem else output_path, emo_audio_prompt, emo_alpha,
+                               emo_vector, use_emo_text, emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment,
+                               False, more_segment_before, return_audio=return_audio, return_numpy=return_numpy, **generation_kwargs)
+                    for k in range(takes)]
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, return_audio=return_audio, return_numpy=return_numpy, **generation_kwargs)

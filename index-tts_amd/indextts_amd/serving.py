@@ -191,7 +191,7 @@ def _start(owner) -> bool:
 
 class _Request:
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done",
-                 "notified")
+                 "notified", "takes")
 
     def compatible(self, other: "_Request") -> bool:
         # same prompt and settings, greedy (sampling draws are per call) and the SAME text width: a wider neighbour would left-pad this
@@ -240,15 +240,25 @@ class BatchPipeline:
         return s
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
-               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None) -> concurrent.futures.Future:
+               repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
+               takes: int = 1) -> concurrent.futures.Future:
         """Queue one batch; returns a Future of the list of waveforms `synthesize_batch` would return.  Inputs produced on the
         caller's current stream are safe to use (an event recorded here is waited for on the lane's stream), and the waveforms
         are safe to read on that stream (they are tied to it with record_stream before the Future resolves).
         noise_seed (instead of `noise`): an int, or one int per row (utterance_noise_seeds) -- the rows' CFM noise seeds are fixed
-        here, so the request's noise is the same whatever it is merged with.  A bad value, or both, fails this Future only."""
+        here, so the request's noise is the same whatever it is merged with.  A bad value, or both, fails this Future only.
+        takes=n > 1 (sampled or beam-sample requests; a greedy one is refused, every take would be the same): the batch is decoded
+        with every utterance repeated n times, row i * n + j take j of utterance i, each row drawing its own stream of the request's
+        sampler; `noise` and the noise seeds (utterance_noise_seeds(noise_seed, B * n)) have B * n rows, and the Future resolves to
+        result[i][j]."""
+        takes = int(takes)
+        if takes < 1 or (takes > 1 and not (sampling and sampling.get("do_sample"))):
+            raise ValueError("takes must be >= 1, and takes > 1 needs a sampled request: every take of a greedy one would be the same")
         r = _Request()
-        r.done, r.notified = concurrent.futures.Future(), False
+        r.done, r.notified, r.takes = concurrent.futures.Future(), False, takes
         try:
+            if takes > 1:
+                text_tokens, cond = torch.as_tensor(text_tokens).repeat_interleave(takes, 0), _expand_cond(cond, takes)
             r.noise, r.noise_seeds = _request_noise(noise, noise_seed, int(text_tokens.shape[0]))
         except ValueError as e:
             r.done.set_exception(e)
@@ -407,7 +417,7 @@ class BatchPipeline:
                 a += sub["B"]
                 for w in mine:                    # allocated on the worker's stream, consumed on the caller's
                     w.record_stream(r.caller)
-                r.done.set_result(mine)
+                r.done.set_result(mine if r.takes == 1 else [mine[i:i + r.takes] for i in range(0, len(mine), r.takes)])
         except BaseException as e:                  # noqa: BLE001
             for r, _ in group:
                 _set_exception(r.done, e)
@@ -435,7 +445,17 @@ class BatchPipeline:
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq", "deadline", "notified", "priority", "stamp")
+                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest")
+
+
+def _expand_cond(cond, n: int):
+    """The conditioning of a request with n takes per utterance, one entry per take (row i * n + j: utterance i): a list of prompts is
+    repeated entry by entry; one prompt for every row (leading dimension 1) serves as it is."""
+    if isinstance(cond, (list, tuple)):
+        return [c for c in cond for _ in range(n)]
+    if int(cond.spk_cond_latent.shape[0]) == 1 and int(cond.emo_vec.shape[0]) == 1:
+        return cond
+    raise ValueError("takes > 1 needs one prompt for the whole request, or a list of one prompt per utterance")
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
@@ -643,36 +663,57 @@ class ContinuousPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               deadline_s: Optional[float] = None, priority: int = 0) -> concurrent.futures.Future:
+               deadline_s: Optional[float] = None, priority: int = 0, takes: int = 1) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
         has started by then (checked wherever cancellation is: each poll, each acoustic hand-over); None: no deadline.
         priority: larger is more urgent (see the class); it orders the waiting utterances and, with preempt=True, lets this request
-        park rows of lower priority."""
+        park rows of lower priority.
+        takes=n > 1: n takes of every utterance; the Future resolves to result[i][j], take j of utterance i (takes=1: the flat list).
+        Sampled pipelines: utterance i, take j gets entry i * n + j of utterance_samplers(sampling, B * n) and of
+        utterance_noise_seeds(noise_seed, B * n) (`noise`: B * n rows); the takes are ordinary rows for admission order, cancellation,
+        deadlines, priorities, park and resume, and the takes of an utterance that are admitted in one poll share one prefill
+        (DecodeSession.admit(takes=)) -- a request whose takes do not all fit is admitted in parts.  Greedy requests are refused
+        (every take would be the same).  Beam pipelines: the n best hypotheses of each utterance's group
+        (BeamDecodeSession.take(n_best=)), n <= num_beams, else the request's Future fails; the noise seeds are again B * n."""
         if deadline_s is not None:
             deadline_s = float(deadline_s)
-        priority = int(priority)
+        priority, takes = int(priority), int(takes)
+        if takes < 1:
+            raise ValueError("takes must be >= 1")
         if self.num_beams > 1:
-            return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                                lambda B: utterance_beams(sampling, B, self.num_beams), noise_seed, deadline_s, priority)
+            def beams(B):
+                if takes > self.num_beams:
+                    raise ValueError(f"takes ({takes}) exceeds the pipeline's num_beams ({self.num_beams})")
+                return utterance_beams(sampling, B, self.num_beams)
+            return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty, beams, noise_seed, deadline_s, priority, takes)
         if sampling and not self.allow_sampling:
             raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
         if sampling and int(sampling.get("num_beams") or 1) > 1:
             raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
+        if takes > 1 and not (self.allow_sampling and sampling and sampling.get("do_sample")):
+            raise ValueError("takes > 1 needs a sampled request: every take of a greedy one would be the same")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority)
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority, takes)
 
     def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None,
-                priority=0):
+                priority=0, takes=1):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
             raise ValueError(f"max_mel_tokens must be in 1 .. {self.max_new}")
         j = _Job()
         j.text, j.cond, j.max_mel_tokens, j.noise = torch.as_tensor(text_tokens), cond, int(max_mel_tokens), noise
-        B = int(j.text.shape[0])
-        j.codes, j.left, j.failed = [None] * B, B, False
+        # takes: the job holds one row per take, row i * takes + j (text and conditioning repeated).  A sampled pipeline decodes every
+        # row; a beam pipeline decodes one group per utterance, queued as the utterance's first row, and reads its `takes` best
+        units = int(j.text.shape[0])
+        beam = self.num_beams > 1
+        j.takes, j.nbest = takes, takes if beam else 1
+        if takes > 1:
+            j.text = j.text.repeat_interleave(takes, 0)
+        B = units * takes
+        j.codes, j.left, j.failed = [None] * B, (units if beam else B), False
         j.done, j.notified = concurrent.futures.Future(), False
         j.sampling, j.seq, j.noise_seeds = None, -1, None
         j.priority, j.stamp = priority, [0] * B
@@ -680,7 +721,11 @@ class ContinuousPipeline:
         try:                                    # a bad parameter fails this request's Future only
             j.noise, j.noise_seeds = _request_noise(noise, noise_seed, B)
             if per_utterance is not None:
-                j.sampling = per_utterance(B)
+                j.sampling = per_utterance(units if beam else B)
+                if beam and takes > 1:
+                    j.sampling = [j.sampling[r // takes] for r in range(B)]
+            if takes > 1:
+                j.cond = _expand_cond(cond, takes)
         except ValueError as e:
             j.done.set_exception(e)
             return j.done
@@ -694,7 +739,7 @@ class ContinuousPipeline:
                 raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
             j.seq = self._submitted
             self._submitted += 1
-            for i in range(B):
+            for i in range(0, B, j.nbest):
                 self._enqueue(j, i, None)
             self._cv.notify_all()
         return j.done
@@ -780,26 +825,37 @@ class ContinuousPipeline:
         for j, i, parked in take:
             if parked is None:
                 by_job.setdefault(id(j), (j, []))[1].append(i)
-        rows, caps, owners, samplers = [], [], [], []
+        rows, caps, owners, samplers, counts = [], [], [], [], []
         for j, idx in by_job.values():
+            # the takes of one utterance taken in this poll are one request with that many takes: one prompt, one prefill
+            share = j.takes if self.num_beams == 1 else 1
+            parts = collections.OrderedDict()
+            for i in idx:
+                parts.setdefault(i // share, []).append(i)
             try:
-                rs = self._prompt_rows(j, idx)
+                rs = self._prompt_rows(j, [p[0] for p in parts.values()])
                 if any(int(r.shape[0]) > self.max_prompt for r in rs):
                     raise ValueError(f"prompt longer than the pipeline's max_prompt ({self.max_prompt})")
             except BaseException as e:       # noqa: BLE001 -- the request's own error (bad token id, too long)
                 self._fail(j, e)
                 continue
             rows.extend(rs)
-            caps.extend([j.max_mel_tokens] * len(idx))
-            owners.extend((j, i) for i in idx)
-            if j.sampling is not None:
-                samplers.extend(j.sampling[i] for i in idx)
+            for p in parts.values():
+                counts.append(len(p))
+                caps.append([j.max_mel_tokens] * len(p))
+                owners.extend((j, i) for i in p)
+                if j.sampling is not None:
+                    samplers.append([j.sampling[i] for i in p])
         if rows:
             try:
-                if self.num_beams > 1:
-                    got = sess.admit(rows, caps, beam=samplers)
+                if max(counts) > 1:             # (sampled pipelines only)
+                    got = [s for g in sess.admit(rows, caps, sampling=samplers, takes=counts) for s in g]
                 else:
-                    got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
+                    caps, samplers = [c[0] for c in caps], [e[0] for e in samplers]
+                    if self.num_beams > 1:
+                        got = sess.admit(rows, caps, beam=samplers)
+                    else:
+                        got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
             except BaseException as e:       # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
                 for j, _ in owners:
                     self._fail(j, e)
@@ -842,10 +898,13 @@ class ContinuousPipeline:
         done = []
         for s in finished:
             j, i = in_slot.pop(s)
-            codes = sess.take(s).cpu()
+            if j.nbest > 1:                     # a beam group's n best: the rows i .. i + n - 1 of the job
+                best = [c.cpu() for c, _ in sess.take(s, n_best=j.nbest)]
+            else:
+                best = [sess.take(s).cpu()]
             if self._gone(j):
                 continue
-            j.codes[i] = codes
+            j.codes[i:i + len(best)] = best
             j.left -= 1
             if j.left == 0:
                 done.append(j)
@@ -958,7 +1017,7 @@ class ContinuousPipeline:
                 if j.caller is not None:
                     for w in mine:              # allocated on the worker's stream, consumed on the caller's
                         w.record_stream(j.caller)
-                j.done.set_result(mine)
+                j.done.set_result(mine if j.takes == 1 else [mine[i:i + j.takes] for i in range(0, len(mine), j.takes)])
         except BaseException as e:              # noqa: BLE001 -- every request of this acoustic batch fails, nothing else
             for j in group:
                 self._fail(j, e)
