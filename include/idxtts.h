@@ -371,6 +371,28 @@ int idxtts_gpt_generate_sampled(idxtts_ctx* ctx, const float* inputs_embeds, con
 int idxtts_gpt_generate_takes(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
                               float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps, float* logits_out,
                               void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* ---- Scores: the log-probability of every code ----
+ * For decode row b at the step t that writes token tok to codes[b][t]:
+ *   lp[b][t] = (l[tok] - m) - logf(S),  m = max_v l[v],  S = sum_v expf(l[v] - m)
+ * where l is the row's raw fp32 logits, exactly the values logits_out records: before the repetition penalty, temperature, top-k and
+ * top-p, in every mode (greedy, HF, accel).  It is what HF's generate(output_logits=True) + compute_transition_scores(
+ * normalize_logits=True) give -- not output_scores: with repetition penalty 10 and top-k 30 the processed scores of two takes are not
+ * comparable.  S is summed in an order that depends on V alone (each of 1024 threads its own ids ascending, the wave butterfly, the
+ * waves ascending): never on B, the slot, the sampler mode.  lp is finite for every finite logit row.  Steps after a one-shot row has
+ * finished (pad steps) record 0.  A teacher-forced call records the log-probability of the code it writes to `codes`.
+ * Sequence score (host, HF's sum_logprobs / len ** length_penalty): (sum_{t<n} lp[t]) / n ** length_penalty over the n codes produced,
+ * the stop token included.
+ * idxtts_gpt_generate_scored: idxtts_gpt_generate_takes (same workspace size, same codes, bit for bit) that also writes logprobs,
+ * device fp32 [B * takes][max_new_tokens] (columns from *n_steps on are not defined).  sampling NULL = greedy.  A kept decode-step graph
+ * is keyed by the logprobs address as well: a call with another buffer captures anew, a stale address is never replayed.
+ * Determinism: wherever this header says "codes equal, bit for bit", the log-probabilities do too. */
+int idxtts_gpt_generate_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                               float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps, float* logprobs,
+                               float* logits_out, void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* idxtts_gpt_generate_forced with the log-probabilities of the codes it writes (the rows' own argmax, not the forced tokens). */
+int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
+                                      float repetition_penalty, const long long* forced_codes, long long* codes, int* n_steps,
+                                      float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Beam search / beam-sample = what `IndexTTS2.infer` runs by default (infer_v2.py:714-722, 767: do_sample=True, num_beams=3,
  * top_p .8, top_k 30, temperature .8, repetition_penalty 10, length_penalty 0) through HF `_beam_search`
  * (transformers_generation_utils.py:3325-3516) + BeamSearchScorer (transformers_beam_search.py:123-420): log_softmax before
@@ -440,6 +462,13 @@ int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds,
 /* Sampled sessions: _workspace_bytes_ex / _init_ex with flags = IDXTTS_SESSION_SAMPLED add a per-slot sampler table; flags = 0 is
  * exactly _workspace_bytes / _init.  A sampled session's step samples every slot with its own request's idxtts_sampling. */
 #define IDXTTS_SESSION_SAMPLED 1
+/* Scored sessions ("Scores" above): flags |= IDXTTS_SESSION_SCORES, alone or with IDXTTS_SESSION_SAMPLED, adds [slots][max_new_tokens]
+ * fp32 behind everything else in the workspace (flags 0 and 1: exactly the sizes and layout of before); every sampler launch of the
+ * session -- the step's, the admissions' and _fork's first-token pass -- then records the log-probability of the code it writes, and
+ * _read_scored returns them.  _admit, _admit_sampled, _admit_takes (each take's first code with its own lp[0]), _fork (a destination
+ * receives lp[0, at) of the source), _evict, _stop, _park, _park_bytes and _resume work as on any session.  Beam sessions have no such
+ * flag: their hypotheses carry the scorer's scores. */
+#define IDXTTS_SESSION_SCORES 2
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags);
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
                                void* workspace, size_t workspace_bytes, void* stream);
@@ -522,6 +551,10 @@ int idxtts_gpt_session_step(idxtts_ctx* ctx, int n_steps, int use_graph, int* fi
 /* Copies a finished slot's codes (up to and including the stop token) to codes (device int64, >= *n_codes entries: at most
  * max_new_tokens), sets *n_codes (host) and frees the slot. */
 int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_codes, void* workspace, void* stream);
+/* _read on a scored session (IDXTTS_SESSION_SCORES), which also copies the slot's *n_codes log-probabilities to logprobs (device fp32,
+ * >= *n_codes entries).  Frees the slot as _read does.  Refused on a session without the flag, before anything changes. */
+int idxtts_gpt_session_read_scored(idxtts_ctx* ctx, int slot, long long* codes, float* logprobs, int* n_codes, void* workspace,
+                                   void* stream);
 /* _read on a beam session's group for the scorer's n_best best hypotheses, 1 <= n_best <= num_beams: codes device int64, lens and scores
  * HOST [n_best], in idxtts_gpt_generate_beam_nbest's order and padding.  n_best = 1: codes receives lens[0] entries, exactly what _read
  * returns; else codes is [n_best][max_new_tokens of _init_beam], every row stop-padded to the end.  Frees the group.  Refused on every
@@ -561,6 +594,9 @@ int idxtts_gpt_session_stop(idxtts_ctx* ctx, int n, const int* slots, void* work
  *   then for every layer, for every head:  C key runs of pad16(pos * g) | values pos * 64 * e | fp8 only: key scales pad16(4 * pos) |
  *   value scales pad16(4 * pos)
  *   bytes = 128 + pad16(V) + pad16(8 * step) + layers * heads * (C * pad16(pos * g) + pos * 64 * e + (fp8 ? 2 * pad16(4 * pos) : 0))
+ * A row parked from a scored session (IDXTTS_SESSION_SCORES) carries one more segment behind the codes, announced by reserved[1] = 1:
+ *   [header 128] [seen: pad16(V)] [codes int64: pad16(8 * step)] [logprobs fp32: pad16(4 * step)]  then the layers as above
+ * and bytes grows by pad16(4 * step); a row from any other session is byte for byte what it always was.
  * exp_noise travels as the caller's pointer: the tensor must stay alive while the row is parked and until the resumed request ends. */
 #define IDXTTS_PARK_MAGIC 0x4b525049u      /* "IPRK" */
 #define IDXTTS_PARK_VERSION 1
@@ -573,7 +609,8 @@ typedef struct idxtts_park_header {      /* 128 bytes */
   unsigned long long seed;
   unsigned long long exp_noise;                        /* device pointer, or 0 */
   unsigned long long bytes;                            /* the whole parked row, header included */
-  int reserved[8];                                /* [0]: 1 = parked in the batch-invariant mode; everything else zero */
+  int reserved[8];                                /* [0]: 1 = parked in the batch-invariant mode; [1]: 1 = parked from a scored
+                                                     session (the logprobs segment follows the codes); everything else zero */
 } idxtts_park_header;
 /* Exact size of slot's parked row now (one small device-to-host read of its state); 0 with idxtts_last_error set when the slot cannot
  * be parked (see _park). */
@@ -586,7 +623,8 @@ int idxtts_gpt_session_park(idxtts_ctx* ctx, int slot, void* dst, size_t dst_byt
  * another model's dimensions, a session with other slots, KV format or GEMM mode (they select the key split and the GEMV: the
  * remaining codes would belong to another reference), a sampled request offered to a greedy session, a cap above the session's
  * max_new_tokens, pos + (max_step - step) + 1 beyond the session's cache length, a slot that is busy or out of range, src_bytes
- * shorter than the header says, a row whose batch-invariant flag (reserved[0]) differs from the session's.  When both are in the
+ * shorter than the header says, a row whose batch-invariant flag (reserved[0]) or scores flag (reserved[1]) differs from the
+ * session's.  When both are in the
  * batch-invariant mode the slot counts need not match: nothing on the row's path depends on them, and the row's codes stay those of
  * its uninterrupted B = 1 run.  On success the slot decodes on from the next _step; src may be freed once the work queued on `stream`
  * has run (stream order). */

@@ -438,6 +438,28 @@ int idxtts_gpt_generate_takes(idxtts_ctx* ctx, const float* inputs_embeds, const
   API_END
 }
 
+int idxtts_gpt_generate_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                               float repetition_penalty, const idxtts_sampling* sampling, long long* codes, int* n_steps, float* logprobs,
+                               float* logits_out, void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(logprobs, "null logprobs");
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes, logprobs);
+  API_END
+}
+
+int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
+                                      float repetition_penalty, const long long* forced_codes, long long* codes, int* n_steps,
+                                      float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(forced_codes && logprobs, "null forced_codes or logprobs");
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, nullptr, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, 0, static_cast<hipStream_t>(stream), forced_codes, 1, logprobs);
+  API_END
+}
+
 size_t idxtts_gpt_beam_workspace_bytes(const idxtts_ctx* ctx, int B, int num_beams, int S, int max_new_tokens) {
   if (!ctx || !ctx->finalized || B <= 0 || num_beams < 2 || S <= 0 || max_new_tokens <= 0) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
@@ -499,18 +521,19 @@ int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_
 
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags) {
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
-  if (flags & ~IDXTTS_SESSION_SAMPLED) return 0;
+  if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES)) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
-  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, (flags & IDXTTS_SESSION_SAMPLED) != 0) : 0;
+  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, (flags & IDXTTS_SESSION_SAMPLED) != 0, 0,
+                                        (flags & IDXTTS_SESSION_SCORES) != 0) : 0;
 }
 
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
                                void* workspace, size_t workspace_bytes, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  IDX_CHECK(!(flags & ~IDXTTS_SESSION_SAMPLED), "unknown session flags");
+  IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES)), "unknown session flags");
   return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
-                         (flags & IDXTTS_SESSION_SAMPLED) != 0);
+                         (flags & IDXTTS_SESSION_SAMPLED) != 0, 0, (flags & IDXTTS_SESSION_SCORES) != 0);
   API_END
 }
 
@@ -591,6 +614,14 @@ int idxtts_gpt_session_read(idxtts_ctx* ctx, int slot, long long* codes, int* n_
   API_BEGIN
   GPT_MODEL(ctx);
   return m->session_read(workspace, slot, codes, n_codes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_read_scored(idxtts_ctx* ctx, int slot, long long* codes, float* logprobs, int* n_codes, void* workspace,
+                                   void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->session_read(workspace, slot, codes, n_codes, static_cast<hipStream_t>(stream), logprobs, true);
   API_END
 }
 

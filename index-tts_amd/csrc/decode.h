@@ -74,6 +74,10 @@ struct SampleArgs {
   unsigned char* seen = nullptr;                                   // [B][V] ids present in input_ids
   int* finished = nullptr;                                         // [B]
   long long* codes = nullptr; int codes_ld = 0;                    // [B][codes_ld]
+  // optional [B][logprob_ld]: the log-probability of the token written to codes[b][step] under the row's raw logits (the values
+  // logits_out records: before penalty, temperature, top-k and top-p, in every mode); a pad step of a finished row records 0
+  // (idxtts.h "Scores").  Null = off: the samplers then run as they always did
+  float* logprob_out = nullptr; int logprob_ld = 0;
   int* cur_tok = nullptr;                                          // [B]
   const DecodeState* st = nullptr;
   int B = 0, V = 0, stop_token = 0;
@@ -212,16 +216,18 @@ int session_end_slots(SlotState* slots, int n_slots, unsigned long long mask, bo
 struct ParkLayout {
   int chunks = 0, gran = 0, elem = 0;      // key chunks per head, bytes of one chunk per position, bytes per element
   size_t krun = 0, vrun = 0, srun = 0;     // padded bytes of one key run, the value run, one scale run (fp8 only, else 0)
-  size_t off_seen = 0, off_codes = 0, off_kv = 0, per_head = 0, bytes = 0;
+  size_t off_seen = 0, off_codes = 0, off_lp = 0, off_kv = 0, per_head = 0, bytes = 0;      // off_lp: scored rows only, else = off_kv
 };
 __host__ __device__ static inline size_t park_pad16(size_t n) { return (n + 15) & ~(size_t)15; }
-__host__ __device__ static inline ParkLayout park_layout(int kv_fmt, int layers, int heads, int V, int pos, int step) {
+__host__ __device__ static inline ParkLayout park_layout(int kv_fmt, int layers, int heads, int V, int pos, int step,
+                                                                int scores = 0) {      // scores: idxtts_park_header::reserved[1]
   ParkLayout l;
   l.chunks = kv_fmt == 0 ? 16 : 8; l.gran = kv_fmt == 2 ? 8 : 16; l.elem = kv_fmt == 2 ? 1 : kv_fmt ? 2 : 4;
   l.krun = park_pad16((size_t)pos * l.gran); l.vrun = (size_t)pos * 64 * l.elem; l.srun = kv_fmt == 2 ? park_pad16((size_t)pos * 4) : 0;
   l.off_seen = sizeof(idxtts_park_header);
   l.off_codes = l.off_seen + park_pad16((size_t)V);
-  l.off_kv = l.off_codes + park_pad16((size_t)step * 8);
+  l.off_lp = l.off_codes + park_pad16((size_t)step * 8);
+  l.off_kv = l.off_lp + (scores ? park_pad16((size_t)step * 4) : 0);
   l.per_head = l.chunks * l.krun + l.vrun + 2 * l.srun;
   l.bytes = l.off_kv + (size_t)layers * heads * l.per_head;
   return l;
@@ -235,6 +241,7 @@ struct ParkArgs {
   int slot = 0, Smax = 0;
   SlotState* slots = nullptr; SlotSampling* samp = nullptr;      // samp: sampled sessions only (resume rewrites the slot's row)
   unsigned char* seen = nullptr; long long* codes = nullptr; int codes_ld = 0; int* cur_tok = nullptr;
+  float* logprobs = nullptr;               // scored sessions (hdr.reserved[1] = 1): [B][codes_ld], the row's segment behind the codes
   SampleArgs::Embed embed; int B = 0;      // resume: where the slot's next input goes (the session tails' block), B = the session's slots
 };
 // One launch each, between steps on the session's stream.  park: slot -> blob, then live = 0.  resume: blob -> slot, live = 1 with the
@@ -243,7 +250,7 @@ int session_park_slot(const ParkArgs& a, hipStream_t stream);
 int session_resume_slot(const ParkArgs& a, hipStream_t stream);
 // Fork (idxtts.h "Several takes of one request"): the row in slot `src`, cut back to `at` codes, copied to the n free slots dst[] in one
 // launch that reads every 16-byte vector of the source once and stores it n times -- positions [0, P + max(at, 1)) of the keys, values and
-// fp8 scales of every layer (what a row holding `at` codes has cached), codes[0, at), a seen row rebuilt from the start token and those
+// fp8 scales of every layer (what a row holding `at` codes has cached), codes[0, at) (scored sessions: and their log-probabilities), a seen row rebuilt from the start token and those
 // codes, SlotState {P + at, at + 1, at, cap[j], 1} and the next input mel_emb[codes[at - 1]] + mel_pos[at + 1] as the sampler tails write
 // it.  at = 0: the state session_reset_slots leaves (SlotState {P, 1, 0, cap[j], 1}, x_last[src] copied), and the caller runs the
 // admission's head-and-sample pass on the destinations.  The source is only read.
@@ -257,6 +264,7 @@ struct ForkArgs {
   int Smax = 0;
   SlotState* slots = nullptr; unsigned char* seen = nullptr; long long* codes = nullptr; int codes_ld = 0; int* cur_tok = nullptr;
   float* x_last = nullptr;
+  float* logprobs = nullptr;      // scored sessions: [B][codes_ld], else null
   SampleArgs::Embed embed; int B = 0;
 };
 int session_fork_slots(const ForkArgs& a, hipStream_t stream);

@@ -571,6 +571,35 @@ __device__ __forceinline__ void greedy_row_argmax(const SampleArgs& p, const int
   bidx_out = bidx;
 }
 
+// Scores (SampleArgs::logprob_out, idxtts.h "Scores"): the log-probability of token `tok` (workgroup-uniform) under row b's raw logits,
+// lp = (l[tok] - m) - logf(S) with m = max_v l[v] and S = sum_v expf(l[v] - m); valid in every thread of the 1024.  A pass of its own
+// behind the sampler, in the kernels' LP = true instantiations only: with scores off the kernels of before run, instruction for instruction.  It RE-SUMS the slab
+// (no row values are kept in registers: greedy_row_argmax holds four per trip and has no bound on V): l[v] is rebuilt as the samplers
+// build it -- the bias (or 0), then the split-K parts in ascending order -- so it is bit for bit the value logits_out records, and the
+// row's 4 V bytes per part come from L2 the second and third time.  m first; then S in an order that depends on V and the workgroup
+// size alone: every thread its own ids tid, tid + 1024, ... ascending, the wave butterfly, the waves in ascending order (block_sum).
+// Neither B, the slot, nor the sampler mode enters; parts only through l[v] itself.  red: [16] of shared scratch.
+// Registers and occupancy (hipcc --offload-arch=gfx950 -save-temps; 1024-thread workgroups, so at most 2 per CU either way):
+//   LP = false as before (22, 22, 66, 67 VGPRs); LP = true: sample_greedy_kernel and sample_slots_kernel 32 VGPRs, occupancy 8 as
+//   before; sample_warp_kernel 68, sample_slots_warp_kernel 67, occupancy 7 as before; no scratch in any of them.
+__device__ __forceinline__ float row_logit(const SampleArgs& p, const int b, const int v) {
+  float l = p.bias ? p.bias[v] : 0.0f;
+  const float* prow = p.part + (size_t)b * p.V + v;
+  const size_t sst = (size_t)p.part_rows * p.V;
+  for (int s = 0; s < p.parts; ++s) l += prow[(size_t)s * sst];
+  return l;
+}
+__device__ __forceinline__ float row_logprob(const SampleArgs& p, const int b, const int tok, const int tid, float* red) {
+  const int V = p.V;
+  float m = -INFINITY;
+  for (int v = tid; v < V; v += 1024) m = fmaxf(m, row_logit(p, b, v));
+  m = block_max<16>(m, red);
+  float part = 0.f;
+  for (int v = tid; v < V; v += 1024) part += expf(row_logit(p, b, v) - m);
+  const float S = block_sum<16>(part, red);
+  return (row_logit(p, b, tok) - m) - logf(S);
+}
+
 // Row b's next input x = mel_emb[tok] + mel_pos[mel_pos], by all 1024 threads of a sampler's workgroup: A-fragment images for the
 // fp32-MFMA GEMV step (the folded LayerNorm's statistics are computed by the consumer), or a row + its statistics for the plane GEMV
 // (NT threads; session_resume_slot rebuilds a resumed row's input with it)
@@ -585,25 +614,36 @@ __device__ __forceinline__ void write_next_input(const SampleArgs::Embed& em, co
   }
 }
 
+// LP (every sampler kernel): scores are recorded (p.logprob_out set).  The LP = false instantiations are the kernels of before.
+template <bool LP>
 __global__ __launch_bounds__(1024) void sample_greedy_kernel(const SampleArgs p) {
   __shared__ float rv[16];
   __shared__ int ri[16];
-  __shared__ int s_tok;
+  __shared__ int s_tok, s_code;
   const bool fused = p.embed.x_row || p.embed.x_frag;
   const int mp_next = fused ? p.st->mel_pos + 1 : 0;      // read before anybody can advance the state
   const int b = blockIdx.x, tid = threadIdx.x;
   float best;
   int bidx;
   greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
+  int step = 0;      // (thread 0's)
   if (tid == 0) {
-    int tok = p.finished[b] ? p.stop_token : bidx;      // finished rows emit pad (= eos = stop token)
-    const int step = p.st->step;
+    const bool pad = p.finished[b] != 0;
+    int tok = pad ? p.stop_token : bidx;      // finished rows emit pad (= eos = stop token)
+    step = p.st->step;
     p.codes[(size_t)b * p.codes_ld + step] = tok;
+    if (LP) s_code = pad ? -1 : tok;      // what the scores describe: the code just written, not a forced token
     if (p.forced) tok = (int)p.forced[(size_t)b * p.forced_ld + step];      // teacher forcing: the given token continues the sequence
     p.seen[(size_t)b * p.V + tok] = 1;
     if (tok == p.stop_token) p.finished[b] = 1;
     p.cur_tok[b] = tok;
     s_tok = tok;
+  }
+  if (LP) {      // (before this workgroup's arrival below, so `step` is still this launch's)
+    __syncthreads();
+    const int code = s_code;
+    const float lp = code < 0 ? 0.0f : row_logprob(p, b, code, tid, rv);
+    if (tid == 0) p.logprob_out[(size_t)b * p.logprob_ld + step] = lp;
   }
   if (!fused) return;
   __syncthreads();
@@ -624,7 +664,8 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream) {
   IDX_CHECK(a.part && a.seen && a.finished && a.codes && a.cur_tok && a.st, "null pointer");
   static const int cat = prof_register("sample_greedy_kernel");
   ProfScope prof(cat, stream, 0.0, 4.0 * a.B * (double)a.V * (a.parts + 1));
-  hipLaunchKernelGGL(sample_greedy_kernel, dim3(a.B), dim3(1024), 0, stream, a);
+  if (a.logprob_out) hipLaunchKernelGGL(sample_greedy_kernel<true>, dim3(a.B), dim3(1024), 0, stream, a);
+  else hipLaunchKernelGGL(sample_greedy_kernel<false>, dim3(a.B), dim3(1024), 0, stream, a);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -633,11 +674,14 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream) {
 // Decode session (continuous batching): the greedy tail with per-slot state (SlotState, decode.h)
 
 // The tail of a session sampler, once thread 0 holds the slot's token: record it, then end the slot (stop token or cap) or write its
-// next input row and advance its own scalars.  s_tok / s_mp / s_end: shared scratch.
+// next input row and advance its own scalars.  s_tok / s_mp / s_end: shared scratch; red: [16] floats of it (scores only).
+template <bool LP>
 __device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const ss, const int b, const int tid, const int token, int& s_tok,
-                                          int& s_mp, int& s_end) {
+                                          int& s_mp, int& s_end, float* red) {
+  int step = 0;      // (thread 0's)
   if (tid == 0) {
-    const int tok = token, step = ss->step;
+    const int tok = token;
+    step = ss->step;
     p.codes[(size_t)b * p.codes_ld + step] = tok;
     p.seen[(size_t)b * p.V + tok] = 1;
     p.cur_tok[b] = tok;
@@ -646,6 +690,10 @@ __device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const 
     s_end = tok == p.stop_token || step + 1 >= ss->max_step;
   }
   __syncthreads();
+  if (LP) {
+    const float lp = row_logprob(p, b, s_tok, tid, red);
+    if (tid == 0) p.logprob_out[(size_t)b * p.logprob_ld + step] = lp;
+  }
   if (s_end) {      // the stop token (recorded) or the slot's cap: the slot retires; step = codes produced
     if (tid == 0) { ss->step += 1; ss->live = 0; }
     return;
@@ -654,6 +702,7 @@ __device__ __forceinline__ void slot_tail(const SampleArgs& p, SlotState* const 
   if (tid == 0) { ss->pos += 1; ss->mel_pos += 1; ss->step += 1; }      // this slot's scalars: nobody else reads them in this launch
 }
 
+template <bool LP>
 __global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, SlotState* slots, const int* slot_ids) {
   __shared__ float rv[16];
   __shared__ int ri[16];
@@ -664,7 +713,7 @@ __global__ __launch_bounds__(1024) void sample_slots_kernel(const SampleArgs p, 
   float best;
   int bidx;
   greedy_row_argmax(p, b, tid, rv, ri, best, bidx);
-  slot_tail(p, ss, b, tid, bidx, s_tok, s_mp, s_end);
+  slot_tail<LP>(p, ss, b, tid, bidx, s_tok, s_mp, s_end, rv);
 }
 
 int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_ids, int n, hipStream_t stream) {
@@ -674,7 +723,8 @@ int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_
   if (n <= 0) return 0;
   static const int cat = prof_register("sample_slots_kernel");
   ProfScope prof(cat, stream, 0.0, 4.0 * n * (double)a.V * (a.parts + 1));
-  hipLaunchKernelGGL(sample_slots_kernel, dim3(n), dim3(1024), 0, stream, a, slots, slot_ids);
+  if (a.logprob_out) hipLaunchKernelGGL(sample_slots_kernel<true>, dim3(n), dim3(1024), 0, stream, a, slots, slot_ids);
+  else hipLaunchKernelGGL(sample_slots_kernel<false>, dim3(n), dim3(1024), 0, stream, a, slots, slot_ids);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -816,6 +866,7 @@ __device__ __forceinline__ int warp_row_token(const SampleArgs& p, const int b, 
   return token;
 }
 
+template <bool LP>
 __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs q) {
   const SampleArgs& p = q.base;
   __shared__ float rv[16];
@@ -833,6 +884,10 @@ __global__ __launch_bounds__(1024) void sample_warp_kernel(const SampleWarpArgs 
   const unsigned long long seed = own ? q.seed + DRAW_ROW_STRIDE * (unsigned long long)b : q.seed;
   const int token = warp_row_token(p, b, q.mode, q.temperature, q.top_k, q.top_p, q.exp_noise, seed, nbase, tid, rv, ri, sval, sidx,
                                    sorted_v, sorted_i, s_count, s_keep_from, s_sum);
+  if (LP) {      // (every thread reads finished[b] before the barriers inside, thread 0 sets it after them)
+    const float lp = p.finished[b] ? 0.0f : row_logprob(p, b, token, tid, rv);
+    if (tid == 0) p.logprob_out[(size_t)b * p.logprob_ld + p.st->step] = lp;
+  }
   if (tid == 0) {
     const int tok = p.finished[b] ? p.stop_token : token;
     p.codes[(size_t)b * p.codes_ld + p.st->step] = tok;
@@ -850,7 +905,8 @@ int sample_warp_forward(const SampleWarpArgs& a, hipStream_t stream) {
   IDX_CHECK(a.mode == SAMPLE_HF || a.mode == SAMPLE_ACCEL, "sampling mode");
   static const int cat = prof_register("sample_warp_kernel");
   ProfScope prof(cat, stream, 0.0, 8.0 * b.B * (double)b.V);
-  hipLaunchKernelGGL(sample_warp_kernel, dim3(b.B), dim3(1024), 0, stream, a);
+  if (b.logprob_out) hipLaunchKernelGGL(sample_warp_kernel<true>, dim3(b.B), dim3(1024), 0, stream, a);
+  else hipLaunchKernelGGL(sample_warp_kernel<false>, dim3(b.B), dim3(1024), 0, stream, a);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -858,6 +914,7 @@ int sample_warp_forward(const SampleWarpArgs& a, hipStream_t stream) {
 // Decode session with per-request sampling: sample_slots_kernel with the sampler of each slot's own SlotSampling row -- greedy_row_argmax
 // (mode 0) or the warped sampler of sample_warp_kernel, whose draws for the slot's step t are the request's noise row t, or the
 // counter-based stream at row 0 of a `p.B`-row generation (independent of the slot id)
+template <bool LP>
 __global__ __launch_bounds__(1024) void sample_slots_warp_kernel(const SampleArgs p, SlotState* slots, const SlotSampling* samp,
                                                                  const int* slot_ids) {
   __shared__ float rv[16];
@@ -883,7 +940,7 @@ __global__ __launch_bounds__(1024) void sample_slots_warp_kernel(const SampleArg
     token = warp_row_token(p, b, sp.mode, sp.temperature, sp.top_k, sp.top_p, sp.exp_noise, sp.seed, nbase, tid, rv, ri, sval, sidx,
                            sorted_v, sorted_i, s_count, s_keep_from, s_sum);
   }
-  slot_tail(p, ss, b, tid, token, s_tok, s_mp, s_end);
+  slot_tail<LP>(p, ss, b, tid, token, s_tok, s_mp, s_end, rv);
 }
 
 int sample_slots_warp_forward(const SampleArgs& a, SlotState* slots, const SlotSampling* samp, const int* slot_ids, int n,
@@ -895,7 +952,8 @@ int sample_slots_warp_forward(const SampleArgs& a, SlotState* slots, const SlotS
   if (n <= 0) return 0;
   static const int cat = prof_register("sample_slots_warp_kernel");
   ProfScope prof(cat, stream, 0.0, 8.0 * n * (double)a.V);
-  hipLaunchKernelGGL(sample_slots_warp_kernel, dim3(n), dim3(1024), 0, stream, a, slots, samp, slot_ids);
+  if (a.logprob_out) hipLaunchKernelGGL(sample_slots_warp_kernel<true>, dim3(n), dim3(1024), 0, stream, a, slots, samp, slot_ids);
+  else hipLaunchKernelGGL(sample_slots_warp_kernel<false>, dim3(n), dim3(1024), 0, stream, a, slots, samp, slot_ids);
   IDX_LAUNCH_CHECK();
   return 0;
 }
@@ -1208,7 +1266,7 @@ template <bool RESUME>
 __global__ __launch_bounds__(PARK_NT) void session_park_kernel(const ParkArgs p) {
   const int tid = threadIdx.x, r = blockIdx.x, h = blockIdx.y, l = blockIdx.z, H = gridDim.y;
   const idxtts_park_header& hd = p.hdr;
-  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step);
+  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step, hd.reserved[1]);
   const int C = lay.chunks, runs = 2 * C + (hd.kv_format == 2 ? 2 : 0);
   auto move = [&](char* cache, char* seg, size_t n) {      // one run between the cache and its segment of the parked row
     if (RESUME) park_copy_run<false>(cache, seg, n, tid);
@@ -1245,6 +1303,12 @@ __global__ __launch_bounds__(PARK_NT) void session_park_kernel(const ParkArgs p)
       bseen[i] = w;
     }
     for (int i = tid; i < nc; i += PARK_NT) bcodes[i] = i < step ? codes[i] : 0ll;
+    if (hd.reserved[1]) {      // scored row: the log-probabilities of its codes, zeros to the end of the last vector
+      const float* const lp = p.logprobs + (size_t)p.slot * p.codes_ld;
+      float* const blp = reinterpret_cast<float*>(p.blob + lay.off_lp);
+      const int nl = (int)(park_pad16((size_t)step * 4) >> 2);
+      for (int i = tid; i < nl; i += PARK_NT) blp[i] = i < step ? lp[i] : 0.0f;
+    }
     if (tid == 0) {
       *reinterpret_cast<idxtts_park_header*>(p.blob) = hd;
       ss->live = 0;      // the slot is free, as session_end_slots leaves an evicted one
@@ -1257,6 +1321,11 @@ __global__ __launch_bounds__(PARK_NT) void session_park_kernel(const ParkArgs p)
         if (4 * i + j < V) seen[4 * i + j] = (unsigned char)(w >> (8 * j));
     }
     for (int i = tid; i < step; i += PARK_NT) codes[i] = bcodes[i];
+    if (hd.reserved[1]) {
+      float* const lp = p.logprobs + (size_t)p.slot * p.codes_ld;
+      const float* const blp = reinterpret_cast<const float*>(p.blob + lay.off_lp);
+      for (int i = tid; i < step; i += PARK_NT) lp[i] = blp[i];
+    }
     // the row's last code, kept inside the embedding table whatever the bytes say (the header is checked on the host, the body is not)
     const int tok = min(max((int)bcodes[step - 1], 0), V - 1);
     write_next_input<PARK_NT>(p.embed, p.B, p.slot, tok, hd.mel_pos, tid);
@@ -1278,7 +1347,8 @@ static int park_launch(const ParkArgs& a, bool resume, hipStream_t stream) {
   IDX_CHECK(((uintptr_t)a.blob | (uintptr_t)a.kcache | (uintptr_t)a.vcache | (uintptr_t)a.kscale | (uintptr_t)a.vscale) % 16 == 0,
             "the parked row and the caches must be 16-byte aligned");
   IDX_CHECK(!resume || ((a.embed.x_row && a.embed.x_stats) || a.embed.x_frag), "resume needs the step's input buffers");
-  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step);
+  IDX_CHECK((hd.reserved[1] == 0 && !a.logprobs) || (hd.reserved[1] == 1 && a.logprobs), "a scored row needs a scored session, and the reverse");
+  const ParkLayout lay = park_layout(hd.kv_format, hd.layers, hd.heads, hd.number_mel_codes, hd.pos, hd.step, hd.reserved[1]);
   const int runs = 2 * lay.chunks + (hd.kv_format == 2 ? 2 : 0);
   static const int cat_p = prof_register("session_park_kernel"), cat_r = prof_register("session_resume_kernel");
   ProfScope prof(resume ? cat_r : cat_p, stream, 0.0, 2.0 * (double)lay.bytes);
@@ -1353,6 +1423,10 @@ __global__ __launch_bounds__(PARK_NT) void session_fork_kernel(const ForkArgs p)
     for (int j = 0; j < p.n; ++j) {
       p.codes[(size_t)p.dst[j] * p.codes_ld + i] = c;
       p.seen[(size_t)p.dst[j] * V + tok] = 1;
+    }
+    if (p.logprobs) {      // scored session: lp[0, at) of the source
+      const float lp = p.logprobs[(size_t)p.src * p.codes_ld + i];
+      for (int j = 0; j < p.n; ++j) p.logprobs[(size_t)p.dst[j] * p.codes_ld + i] = lp;
     }
   }
   for (int j = 0; j < p.n; ++j)      // the prefill's last row travels with every take: a take can be forked at 0 like its source

@@ -95,6 +95,8 @@ struct GPTModel : ModelBase {
     idxtts_sampling samp{0, 1.0f, 0, 1.0f, nullptr, 0};      // generate(): the call's sampler (mode 0 = greedy)
     const long long* forced = nullptr; int forced_ld = 0;   // generate_forced: [B][forced_ld] tokens fed back instead of the argmax
     int invariant = 0;                        // the context's batch_invariant when the buffers were carved
+    float* logprobs = nullptr;                // scores (idxtts.h "Scores"): [B][codes_ld] beside `codes` -- a scored session's table in
+                                              // its workspace, generate()'s caller's buffer -- or null: the samplers record none
     bool beam_tail = false;                   // the beam stages on `beam`: a beam session's (slots set) or generate_beam's
     BeamState beam;
   };
@@ -102,6 +104,7 @@ struct GPTModel : ModelBase {
   // address and carve, batch, penalty): a server replaying the same shapes on the same stream re-captures nothing.
   struct GraphSlot {
     void* ws = nullptr; size_t ws_bytes = 0; int B = 0, S = 0, max_new = 0; float penalty = 0.0f; int kv_fmt = 0, geom = 0;
+    float* logprobs = nullptr;      // the caller's scores buffer the captured samplers write (null: none); the one address outside ws
     StepGraph step; unsigned long stamp = 0; bool in_use = false;
   };
   std::vector<GraphSlot> graph_cache;
@@ -149,7 +152,8 @@ struct GPTModel : ModelBase {
                      // each row's KV and last position fanned out to its fan decode rows (takes); else R prefill rows (beams)
   int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_sampling* sampling, long long* codes,
                int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr,
-               int takes = 1);      // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per prompt
+               int takes = 1,       // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per prompt
+               float* logprobs = nullptr);      // device [B * takes][max_new]: every code's log-probability (idxtts.h "Scores")
   // Beam search / beam-sample (HF _beam_search; the reference's default decoding mode, infer_v2.py:714-722): B utterances x
   // num_beams rows through the same decode step, selection / hypotheses / re-indexing on the device (beam.hip).
   size_t beam_workspace_bytes(int B, int nb, int S, int max_new) const;
@@ -169,6 +173,7 @@ struct GPTModel : ModelBase {
     int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
     int invariant = 0;                // the context's batch-invariant mode at _init: the session keeps it (changed since: every call refuses)
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
+    bool scores = false;              // IDXTTS_SESSION_SCORES: [slots][max_new] log-probabilities behind everything else (w.logprobs)
     std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
     int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
     std::vector<SlotBeam> beam;       // host image of the SlotBeam table (beam sessions), copied whole at each admission
@@ -194,11 +199,11 @@ struct GPTModel : ModelBase {
   size_t session_prefill_rows(int slots, int max_prompt) const { return (size_t)slots * (max_prompt + 1) + 256; }
   // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before;
   // num_beams > 0 (beam session): the beam buffers and the SlotBeam table likewise
-  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0) const;
-  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0) const;
+  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0, bool scores = false) const;
+  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0, bool scores = false) const;
   Session* find_session(void* ws);
   int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false,
-                   int num_beams = 0);
+                   int num_beams = 0, bool scores = false);
   // The admission both session kinds share: n requests into the free units ids[] -- slots, or (fan > 1) groups of fan slots -- each
   // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's
   // keys and values going to its unit's slots.  *S: positions per prefill row.
@@ -222,7 +227,8 @@ struct GPTModel : ModelBase {
                         float* scores = nullptr);
   int session_read_nbest(void* ws, int slot, int n_best, long long* codes, int* lens, float* scores, hipStream_t st);
   int session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st);
-  int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st);
+  // logprobs: null = _read; else _read_scored (device fp32, the slot's log-probabilities; a scored session only)
+  int session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st, float* logprobs = nullptr, bool scored = false);
   // Ends the requests in slot_ids (HOST; beam sessions: the first slot of each group) from outside the step.  evict: they are free at
   // once -- admissible in the next admit, never reported by a later step; allowed on a live request and on one that ended and was not
   // read.  Otherwise stop: a live request ends as if its cap were the codes it has (the next step reports it, read returns them); one

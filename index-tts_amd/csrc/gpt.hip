@@ -319,6 +319,7 @@ int GPTModel::head_and_sample(const Buffers& w, int B, const float* x, int ldx, 
   s.seen = w.seen; s.finished = w.finished; s.codes = w.codes; s.codes_ld = codes_ld; s.cur_tok = w.cur_tok;
   s.st = w.state; s.B = B; s.V = V; s.stop_token = cfg.stop_mel_token; s.penalty = penalty;
   s.forced = w.forced; s.forced_ld = w.forced_ld; s.invariant = w.invariant;
+  s.logprob_out = w.logprobs; s.logprob_ld = codes_ld;
   if (w.slots) {      // decode session: the per-slot greedy tail (sample + next input row + the slot's own advance)
     s.embed = tail_embed(w, pl);
     if (w.slot_samp) return sample_slots_warp_forward(s, w.slots, w.slot_samp, nullptr, B, st);      // sampled session: each slot's own sampler
@@ -579,7 +580,7 @@ static int check_sampling(const idxtts_sampling& r) {
 
 int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
                        const idxtts_sampling* sampling, long long* codes, int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph,
-                       hipStream_t user_stream, const long long* forced, int takes) {
+                       hipStream_t user_stream, const long long* forced, int takes, float* logprobs) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out, "null pointer");
   GenScope gen_scope(this);
   IDX_CHECK(!forced || !(sampling && sampling->mode != 0), "teacher forcing is a greedy-mode instrument");
@@ -596,6 +597,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   Buffers w = carve(ws, B, S, max_new);
   if (sampling && sampling->mode != 0) w.samp = *sampling;
   w.forced = forced; w.forced_ld = max_new;
+  w.logprobs = logprobs;      // the samplers write the caller's buffer; a kept graph is keyed by it (GraphSlot::logprobs)
   // every launch writes w.codes (a stable address: the captured decode step can be kept); the caller's pad fill in, copied out at the end
   IDX_HIP(hipMemcpyAsync(w.codes, codes, (size_t)B * max_new * sizeof(long long), hipMemcpyDeviceToDevice, st));
 
@@ -612,7 +614,8 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
     std::lock_guard<std::mutex> l(graph_mu);
     for (size_t i = 0; i < graph_cache.size(); ++i) {
       GraphSlot& g = graph_cache[i];
-      if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv_fmt == kv_fmt && g.geom == geom) {
+      if (!g.in_use && g.ws == ws && g.ws_bytes == ws_bytes && g.B == B && g.S == S && g.max_new == max_new && g.penalty == penalty && g.kv_fmt == kv_fmt && g.geom == geom &&
+          g.logprobs == logprobs) {
         g.in_use = true; g.stamp = ++graph_stamp; exec = g.step.exec; lease.m = this; lease.idx = (int)i;
         break;
       }
@@ -636,6 +639,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
       GraphSlot& g = graph_cache[slot];
       g.step.drop();
       g.ws = ws; g.ws_bytes = ws_bytes; g.B = B; g.S = S; g.max_new = max_new; g.penalty = penalty; g.kv_fmt = kv_fmt; g.geom = geom;
+      g.logprobs = logprobs;
       g.step = fresh; g.stamp = ++graph_stamp;
     } else {
       fresh.drop();
@@ -666,7 +670,8 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
 // Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
 // the staged last prefill rows and the admission's index arrays.
-GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams) const {
+GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams,
+                                                 bool scores) const {
   SessionBuffers sb;
   sb.w = carve(ws, slots, max_prompt + 1, max_new, session_prefill_rows(slots, max_prompt));
   Carver c(ws);
@@ -696,12 +701,13 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
     if (use_pl(slots)) { b.x_row = w.xrow; b.x_stats = w.stats; } else b.x_frag = w.xd;
     b.mel_emb = mel_emb; b.mel_pos = mel_pos; b.d = cfg.model_dim;
   }
+  if (scores) sb.w.logprobs = c.take<float>((size_t)slots * max_new);      // (after everything else: flags 0 and 1 keep their layout)
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
 
-size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams) const {
-  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams).bytes;
+size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams, bool scores) const {
+  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams, scores).bytes;
 }
 
 GPTModel::Session* GPTModel::find_session(void* ws) {
@@ -711,15 +717,16 @@ GPTModel::Session* GPTModel::find_session(void* ws) {
 }
 
 int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st,
-                           bool sampled, int num_beams) {
+                           bool sampled, int num_beams, bool scores) {
   IDX_CHECK(ws, "null workspace");
+  IDX_CHECK(num_beams == 0 || !scores, "a beam session records no per-code scores: its hypotheses carry the scorer's");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
   IDX_CHECK(num_beams == 0 || (num_beams >= 2 && num_beams <= BEAM_MAX), "2 <= num_beams <= 8");
   IDX_CHECK(num_beams == 0 || slots % num_beams == 0, "slots must be a multiple of num_beams");
   IDX_CHECK(num_beams == 0 || !sampled, "a beam session has no per-slot samplers");
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
-  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams), "workspace too small");
-  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams);
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams, scores), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams, scores);
   const Buffers& w = sb.w;
   const int d = cfg.model_dim;
   IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
@@ -749,6 +756,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.prompt.assign(slots, 0);
   s.first_in.assign(slots, 0);
   s.sampled = sampled;
+  s.scores = scores;
   if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
   s.num_beams = num_beams;
   if (num_beams) s.beam.assign(slots / num_beams, SlotBeam{0, 1.0f, 0, 1.0f, 0.0, 0, 0, nullptr});
@@ -853,7 +861,7 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   }
   GenScope gen_scope(this);
   const int d = cfg.model_dim, V = cfg.number_mel_codes;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
   const Buffers& w = sb.w;
   auto params = [&]() -> int {      // the admitted slots' samplers (greedy when per_row is null); the other rows are rewritten unchanged
     if (!s.sampled) return 0;
@@ -881,6 +889,7 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   SampleArgs sa;
   sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
   sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
+  sa.logprob_out = w.logprobs; sa.logprob_ld = s.max_new;
   if (use_pl(s.slots)) { sa.embed.x_row = w.xrow; sa.embed.x_stats = w.stats; } else sa.embed.x_frag = w.xd;
   sa.embed.mel_emb = mel_emb; sa.embed.mel_pos = mel_pos; sa.embed.d = d;
   if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, T, st) : sample_slots_forward(sa, w.slots, sb.ids, T, st))
@@ -898,7 +907,7 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   GenScope gen_scope(this);
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
   const Buffers& w = sb.w;
   const int geom = step_key();
   if (s.step.exec && s.geom != geom) s.step.drop();
@@ -928,13 +937,14 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   return 0;
 }
 
-int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st) {
+int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st, float* logprobs, bool scored) {
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
-  IDX_CHECK(codes && n_codes, "null pointer");
+  IDX_CHECK(codes && n_codes && (logprobs || !scored), "null pointer");
+  IDX_CHECK(!scored || s.scores, "_read_scored needs a session initialised with IDXTTS_SESSION_SCORES");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
   if (s.num_beams) return session_read_beam(s, sb, slot, codes, n_codes, st);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
@@ -942,6 +952,8 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   IDX_CHECK(!hs.live, "slot is still decoding");
   IDX_CHECK(hs.step >= 1 && hs.step <= s.max_new, "slot state corrupt");
   IDX_HIP(hipMemcpyAsync(codes, sb.w.codes + (size_t)slot * s.max_new, (size_t)hs.step * sizeof(long long), hipMemcpyDeviceToDevice, st));
+  if (scored)
+    IDX_HIP(hipMemcpyAsync(logprobs, sb.w.logprobs + (size_t)slot * s.max_new, (size_t)hs.step * sizeof(float), hipMemcpyDeviceToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));
   *n_codes = hs.step;
   s.busy[slot] = 0;
@@ -955,7 +967,7 @@ int GPTModel::session_read_nbest(void* ws, int slot, int n_best, long long* code
   IDX_CHECK(s.num_beams > 0, "_read_nbest needs a beam session: every other session holds one sequence per slot (_read)");
   IDX_CHECK(codes && lens && scores, "null pointer");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
   return session_read_beam(s, sb, slot, codes, lens, st, n_best, scores);
 }
 
@@ -976,7 +988,7 @@ int GPTModel::session_end(void* ws, int n, const int* slot_ids, bool evict, hipS
     IDX_CHECK(s.busy[slot], "slot holds no request");
     for (int j = 0; j < fan; ++j) mask |= 1ull << (slot + j);
   }
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
   if (session_end_slots(sb.w.slots, s.slots, mask, !evict, st)) return 1;
   if (evict)
     for (int i = 0; i < s.slots; ++i)
@@ -992,6 +1004,7 @@ ParkArgs GPTModel::park_args(const Session& s, const SessionBuffers& sb, int slo
   a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
   a.slot = slot; a.Smax = w.Smax; a.slots = w.slots; a.samp = sb.samp; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new;
   a.cur_tok = w.cur_tok; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots;
+  a.logprobs = w.logprobs;
   return a;
 }
 
@@ -1004,7 +1017,7 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
   IDX_CHECK(s.busy[slot], "slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
@@ -1022,7 +1035,8 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
     h.exp_noise = (unsigned long long)(uintptr_t)e.exp_noise;
   }
   h.reserved[0] = s.invariant;      // a row parked in the batch-invariant mode says so; every other row carries zeros
-  h.bytes = park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step).bytes;
+  h.reserved[1] = s.scores ? 1 : 0; // a scored session's row carries its log-probabilities behind the codes
+  h.bytes = park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step, h.reserved[1]).bytes;
   *hdr = h;
   return 0;
 }
@@ -1039,7 +1053,7 @@ int GPTModel::session_park(void* ws, int slot, void* dst, size_t dst_bytes, size
   if (session_park_header(ws, slot, &h, st)) return 1;
   IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked row (idxtts_gpt_session_park_bytes)");
   Session& s = *find_session(ws);
-  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled), slot);
+  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores), slot);
   a.hdr = h; a.blob = static_cast<char*>(dst);
   if (session_park_slot(a, st)) return 1;
   s.busy[slot] = 0;
@@ -1068,12 +1082,14 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
             "parked row of another model (dimensions)");
   IDX_CHECK(h.reserved[0] == 0 || h.reserved[0] == 1, "parked row's mode field is corrupt");
   IDX_CHECK(h.reserved[0] == s.invariant, "parked row and session differ in the batch-invariant mode");
+  IDX_CHECK(h.reserved[1] == 0 || h.reserved[1] == 1, "parked row's scores field is corrupt");
+  IDX_CHECK(h.reserved[1] == (s.scores ? 1 : 0), "parked row and session differ in IDXTTS_SESSION_SCORES (a scored row carries a segment more)");
   // in the mode nothing on a row's path depends on the slot count: a row moves between sessions of any size
   IDX_CHECK(s.invariant || h.slots == s.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
   IDX_CHECK(h.kv_format == s.kv_fmt, "parked row of another KV format");
   IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked row of another GEMM mode");
   IDX_CHECK(h.mode == 0 || s.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
   IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
   IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= 1, "parked row's step scalars are corrupt");
   IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
@@ -1081,7 +1097,8 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
     idxtts_sampling r{h.mode, h.temperature, h.top_k, h.top_p, reinterpret_cast<const float*>((uintptr_t)h.exp_noise), h.seed};
     if (check_sampling(r)) return 1;
   }
-  IDX_CHECK(h.bytes == park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step).bytes, "parked row's size field is corrupt");
+  IDX_CHECK(h.bytes == park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step, h.reserved[1]).bytes,
+            "parked row's size field is corrupt");
   IDX_CHECK(src_bytes >= h.bytes, "parked row is truncated");
   ParkArgs a = park_args(s, sb, slot);
   a.hdr = h; a.blob = const_cast<char*>(static_cast<const char*>(src));
@@ -1114,7 +1131,7 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
   if (samplers)
     for (int j = 0; j < n; ++j)
       if (check_sampling(samplers[j])) return 1;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
   const Buffers& w = sb.w;
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
   SlotState hs;
@@ -1148,7 +1165,7 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
   a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
   a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
   a.Smax = w.Smax; a.slots = w.slots; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new; a.cur_tok = w.cur_tok;
-  a.x_last = sb.x_last; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots;
+  a.x_last = sb.x_last; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots; a.logprobs = w.logprobs;
   if (session_fork_slots(a, st)) return 1;      // (its own checks come before its launch: from here on nothing refuses)
   if (s.sampled) {      // the takes' samplers (greedy when samplers is null); the other rows are rewritten unchanged
     for (int j = 0; j < n; ++j) {
@@ -1169,6 +1186,7 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
     SampleArgs sa;
     sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
     sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
+    sa.logprob_out = w.logprobs; sa.logprob_ld = s.max_new;
     sa.embed = tail_embed(w, use_pl(s.slots));
     if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st))
       return 1;

@@ -236,22 +236,26 @@ class UnifiedVoice:
         return [emb[i, int(p):] for i, p in enumerate(pads)]
 
     def decode_session(self, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0, do_sample: bool = False,
-                       num_beams: int = 1, use_graph: bool = True, sampled: bool = False) -> "DecodeSession":
+                       num_beams: int = 1, use_graph: bool = True, sampled: bool = False, scores: bool = False) -> "DecodeSession":
         """Continuous batching: `slots` decode rows, one KV region each, that requests enter and leave between steps
         (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt.
-        sampled=True: every request samples with its own parameters and draws (DecodeSession.admit(..., sampling=...))."""
+        sampled=True: every request samples with its own parameters and draws (DecodeSession.admit(..., sampling=...)).
+        scores=True: every code's log-probability is recorded (take(slot, scores=True); include/idxtts.h "Scores")."""
         if do_sample:
             raise ValueError("decode sessions sample per request, not session-wide: do_sample=True is not supported; the session is "
                              "greedy unless created with sampled=True and given per-request parameters (admit(..., sampling=...))")
         if num_beams != 1:
             raise ValueError("decode sessions are greedy or sampled per request: beam search runs in beam_session() (or generate_beam())")
-        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled)
+        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled, scores=scores)
 
     def beam_session(self, slots: int, num_beams: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
-                     use_graph: bool = True) -> "BeamDecodeSession":
+                     use_graph: bool = True, scores: bool = False) -> "BeamDecodeSession":
         """Continuous batching of beam search / beam-sample: `slots` decode rows as slots / num_beams groups of num_beams, one request
         per group (BeamDecodeSession; `idxtts_gpt_session_*_beam`).  A request's codes equal row 0 of generate_beam() on
-        slots / num_beams copies of its prompt."""
+        slots / num_beams copies of its prompt.  scores=True raises: a beam session's hypotheses carry the scorer's scores
+        (take(group, n_best=))."""
+        if scores:
+            raise ValueError("a beam session records no per-code scores: take(group, n_best=) returns the scorer's sequences_scores")
         return BeamDecodeSession(self, slots, num_beams, max_prompt, max_new, repetition_penalty, use_graph)
 
     # ------------------------------------------------------------------------------------------
@@ -261,7 +265,7 @@ class UnifiedVoice:
                  repetition_penalty: float = 10.0, return_logits: bool = False, use_graph: bool = True,
                  do_sample: bool = False, sampler: str = "hf", exp_noise: Optional[torch.Tensor] = None,
                  generator: Optional[torch.Generator] = None, forced_codes: Optional[torch.Tensor] = None,
-                 seed: Optional[int] = None, num_return_sequences: int = 1) -> torch.Tensor:
+                 seed: Optional[int] = None, num_return_sequences: int = 1, return_logprobs: bool = False) -> torch.Tensor:
         """The accel-engine plugin contract (accel_engine.py:378-645): returns LongTensor [B, P+1+generated]
         (prompt ids followed by the generated codes, padded with the stop token).
 
@@ -281,7 +285,12 @@ class UnifiedVoice:
         CPU with one exponential_() per step, the order HF consumes them; with neither the kernels generate them from `seed` (see
         _noise; None = a seed drawn from torch's global RNG).
         forced_codes [B, max_new_tokens] (greedy only; a parity instrument, `idxtts_gpt_generate_forced`): the sequence is continued with
-        these tokens while the returned codes are each step's own argmax -- with return_logits, the logits of a GIVEN token sequence."""
+        these tokens while the returned codes are each step's own argmax -- with return_logits, the logits of a GIVEN token sequence.
+        return_logprobs=True: also returns logprobs [rows, generated] fp32, the model's log-probability of every generated code under
+        the raw logits (what return_logits records, log-softmaxed: HF's output_logits + compute_transition_scores(normalize_logits=True),
+        not the processed output_scores; include/idxtts.h "Scores"); 0 on the pad steps of a row that has stopped.  The return value is
+        (sequences, logprobs), with return_logits (sequences, logits, logprobs).  Every mode: greedy, forced, both samplers, takes.
+        The codes are bit for bit those of the call without it."""
         if tts_embeddings is None:
             raise ValueError("tts_embeddings ([pad][cond][text] prompt embeddings) is required")
         if stop_tokens is not None and list(stop_tokens) != [self.cfg.stop_mel_token]:
@@ -306,6 +315,7 @@ class UnifiedVoice:
         codes = torch.full((B, max_new_tokens), self.cfg.stop_mel_token, dtype=torch.long, device=self.device)
         V = self.cfg.number_mel_codes
         logits = torch.zeros(max_new_tokens, B, V, device=self.device) if return_logits else None
+        logprobs = torch.zeros(B, max_new_tokens, device=self.device) if return_logprobs else None
         ws = self._workspace(B, P + 1, max_new_tokens)
         n = ctypes.c_int(0)
         if do_sample and forced_codes is not None:
@@ -318,7 +328,20 @@ class UnifiedVoice:
                                 top_k=int(top_k or 0) if sampler == "hf" else 0,
                                 top_p=float(top_p if top_p is not None else 1.0) if sampler == "hf" else 1.0,
                                 exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
-        if nrs > 1:
+        if forced_codes is not None:
+            fc = forced_codes.to(self.device, torch.long).contiguous()
+            if tuple(fc.shape) != (B, max_new_tokens):
+                raise ValueError(f"forced_codes must be {(B, max_new_tokens)}")
+        if return_logprobs and forced_codes is not None:
+            _lib.check(_lib.load().idxtts_gpt_generate_forced_scored(
+                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc),
+                _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+        elif return_logprobs:
+            _lib.check(_lib.load().idxtts_gpt_generate_scored(
+                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
+                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs),
+                _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
+        elif nrs > 1:
             _lib.check(_lib.load().idxtts_gpt_generate_takes(
                 self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
                 ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits),
@@ -329,9 +352,6 @@ class UnifiedVoice:
                 ctypes.byref(sc), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph),
                 _lib.current_stream()))
         elif forced_codes is not None:
-            fc = forced_codes.to(self.device, torch.long).contiguous()
-            if tuple(fc.shape) != (B, max_new_tokens):
-                raise ValueError(f"forced_codes must be {(B, max_new_tokens)}")
             _lib.check(_lib.load().idxtts_gpt_generate_forced(
                 self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc),
                 _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
@@ -340,9 +360,12 @@ class UnifiedVoice:
                 self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty),
                 _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
         out = torch.cat([input_ids.to(self.device), codes[:, : n.value]], dim=1)
+        res = (out,)
         if return_logits:
-            return out, logits[: n.value].permute(1, 0, 2).contiguous()
-        return out
+            res += (logits[: n.value].permute(1, 0, 2).contiguous(),)
+        if return_logprobs:
+            res += (logprobs[:, : n.value].contiguous(),)
+        return res if len(res) > 1 else out
 
     def _noise(self, exp_noise, generator, shape, seed: Optional[int] = None):
         """The Exp(1) draws of a sampled generation: (device tensor | None, seed).  An explicit `exp_noise`, or a torch `generator`
@@ -411,14 +434,16 @@ class UnifiedVoice:
 
     def inference_speech(self, speech_condition, text_inputs, emo_speech_condition=None, cond_lengths=None, emo_cond_lengths=None,
                          emo_vec=None, use_speed=False, input_tokens=None, num_return_sequences=1, max_generate_length=None,
-                         typical_sampling=False, typical_mass=.9, return_logits=False, **hf_generate_kwargs):
+                         typical_sampling=False, typical_mass=.9, return_logits=False, return_logprobs=False, **hf_generate_kwargs):
         """`inference_speech` (model_v2.py:796-895): returns (codes [B, n], speech_conditioning_latent).
         speech_condition: the prompt features [B, T, 1024] as the reference takes them (conditioning encoders run here, model_v2.py:
         819-828) or -- hoisted out of the caller's segment loop -- the ready conditioning latent [B, 32, d] together with `emo_vec`.
         Decoding modes = HF generate's: greedy (do_sample=False, num_beams=1), multinomial sampling with the warpers
         (do_sample=True, num_beams=1; extra kwargs `exp_noise` / `generator` / `sampler`, see generate()), beam search and
         beam-sample (num_beams > 1: generate_beam()).  num_return_sequences=n: codes [B * n, L], row b * n + j take j of utterance b --
-        n sampled takes (generate()), or the n best beam hypotheses (n <= num_beams), as HF's generate returns them."""
+        n sampled takes (generate()), or the n best beam hypotheses (n <= num_beams), as HF's generate returns them.
+        return_logprobs (num_beams = 1): the log-probability of every code, [rows, n] fp32 (generate(return_logprobs=True)), as one more
+        value at the end of the returned tuple."""
         if input_tokens is not None or typical_sampling or use_speed:
             raise NotImplementedError("input_tokens / typical_sampling / use_speed are not used by IndexTTS2.infer and not implemented")
         nrs = int(num_return_sequences)
@@ -456,8 +481,9 @@ class UnifiedVoice:
         trunc_index = input_ids.shape[1]
         max_new = (self.cfg.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
         if num_beams > 1:
-            if return_logits:
-                raise NotImplementedError("return_logits is a num_beams=1 feature")
+            if return_logits or return_logprobs:
+                raise NotImplementedError("return_logits / return_logprobs are num_beams=1 features (generate_beam(return_scores=True) "
+                                          "returns the scorer's sequence scores)")
             out = self.generate_beam(input_ids, max_new, attention_mask, inputs_embeds, num_beams=num_beams, repetition_penalty=penalty,
                                      length_penalty=length_penalty, early_stopping=early_stopping, use_graph=use_graph,
                                      num_return_sequences=nrs, **samp)
@@ -468,9 +494,9 @@ class UnifiedVoice:
         out = self.generate(input_ids, max_new_tokens=max_new, stop_tokens=[self.cfg.stop_mel_token],
                             attention_mask=attention_mask, tts_embeddings=inputs_embeds, repetition_penalty=penalty,
                             return_logits=return_logits, sampler=sampler, use_graph=use_graph, forced_codes=forced_codes,
-                            num_return_sequences=nrs, **samp)
-        if return_logits:
-            return out[0][:, trunc_index:], speech_conditioning_latent, out[1]
+                            num_return_sequences=nrs, return_logprobs=return_logprobs, **samp)
+        if return_logits or return_logprobs:
+            return (out[0][:, trunc_index:], speech_conditioning_latent) + tuple(out[1:])
         return out[:, trunc_index:], speech_conditioning_latent
 
     # ------------------------------------------------------------------------------------------
@@ -527,6 +553,36 @@ class UnifiedVoice:
                 _lib.load().idxtts_ctx_destroy(self._h)
         except Exception:
             pass
+
+
+def sequence_scores(logprobs, lengths, length_penalty: float = 1.0) -> np.ndarray:
+    """Sequence score of every row: (sum_{t < n} lp[t]) / n ** length_penalty with n = lengths[row], the codes the row produced (the
+    stop token included) -- HF's sum_logprobs / len ** length_penalty.  logprobs: [rows, steps] (tensor or array; or a list of 1-D rows),
+    the fp32 values generate(return_logprobs=True) / take(scores=True) return; summed on the host in float64, in index order.
+    Returns float64 [rows]."""
+    rows = [np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, dtype=np.float32) for r in logprobs]
+    lengths = [int(n) for n in lengths]
+    if len(rows) != len(lengths):
+        raise ValueError("one length per row")
+    out = np.zeros(len(rows), np.float64)
+    for i, (r, n) in enumerate(zip(rows, lengths)):
+        if r.ndim != 1 or not 1 <= n <= r.shape[0]:
+            raise ValueError(f"row {i}: length {n} outside 1 .. {r.shape[0] if r.ndim == 1 else '?'}")
+        tot = 0.0
+        for t in range(n):      # index order, float64
+            tot += float(r[t])
+        out[i] = tot / float(n) ** float(length_penalty)
+    return out
+
+
+def rank_takes(scores, stopped) -> list:
+    """The takes of one utterance, best first: a take that stopped (its last code is the stop token) before every take that ran into its
+    cap, then the higher score, then the lower take index.  Returns the take indices in that order."""
+    scores = [float(x) for x in scores]
+    stopped = [bool(x) for x in stopped]
+    if len(scores) != len(stopped):
+        raise ValueError("one stopped flag per score")
+    return sorted(range(len(scores)), key=lambda j: (not stopped[j], -scores[j], j))
 
 
 def _seed64(seed) -> int:
@@ -666,18 +722,24 @@ class _Session:
         self._done.update(done)
         return done
 
-    def take(self, i: int) -> torch.Tensor:
-        """The codes of the finished request `i` (a slot, or a group) as a LongTensor on the device; `i` is free again."""
+    def take(self, i: int, scores: bool = False):
+        """The codes of the finished request `i` (a slot, or a group) as a LongTensor on the device; `i` is free again.
+        scores=True (a session created with scores=True): (codes, logprobs fp32 of the same length)."""
         n = ctypes.c_int(0)
         self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
         with torch.cuda.stream(self.stream):
             out = torch.empty(self.max_new, dtype=torch.long, device=self.gpt.device)
-            _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(i) * self._unit, _lib.ptr(out), ctypes.byref(n),
-                                                         _lib.ptr(self._ws), self._sp()))
+            if scores:
+                lp = torch.empty(self.max_new, dtype=torch.float32, device=self.gpt.device)
+                _lib.check(self._lib.idxtts_gpt_session_read_scored(self.gpt._h, int(i) * self._unit, _lib.ptr(out), _lib.ptr(lp),
+                                                                    ctypes.byref(n), _lib.ptr(self._ws), self._sp()))
+            else:
+                _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(i) * self._unit, _lib.ptr(out), ctypes.byref(n),
+                                                             _lib.ptr(self._ws), self._sp()))
         self._busy[i] = False
         self._done.discard(i)
         self._noise.pop(i, None)
-        return out[: n.value]
+        return (out[: n.value], lp[: n.value]) if scores else out[: n.value]
 
     def _ids(self, ids) -> list:
         """One id or a list of them -> a list of requests this session holds (admitted and not taken); ValueError otherwise."""
@@ -748,13 +810,18 @@ class DecodeSession(_Session):
     "hf" | "accel"), `temperature`, `top_k`, `top_p` (HF only), and `seed` or `exp_noise` [cap, V].  A sampled request's codes equal,
     bit for bit, row 0 of generate(do_sample=True, sampler=..., temperature=..., top_k=..., top_p=..., seed=seed) on `slots` copies of
     its prompt (with exp_noise: generate's exp_noise whose row 0 is the request's noise); greedy rows equal those of a greedy session.
-    The repetition penalty is the session's (the HF sampler applies it, the accel sampler does not)."""
+    The repetition penalty is the session's (the HF sampler applies it, the accel sampler does not).
+
+    scores=True: the samplers also record every code's log-probability under the raw logits; take(slot, scores=True) returns them
+    with the codes.  They follow a row through admit(takes=), fork (a take gets the source's first `at` values), park (the ParkedRow
+    carries them, to("cpu") included) and resume (into a session that was also created with scores=True; the reverse is refused too),
+    and obey every determinism rule above, bit for bit.  The codes are those of a session without scores."""
 
     def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
-                 use_graph: bool = True, sampled: bool = False):
-        self.sampled = bool(sampled)
+                 use_graph: bool = True, sampled: bool = False, scores: bool = False):
+        self.sampled, self.scores = bool(sampled), bool(scores)
         lib = _lib.load()
-        flags = _lib.SESSION_SAMPLED if self.sampled else 0
+        flags = (_lib.SESSION_SAMPLED if self.sampled else 0) | (_lib.SESSION_SCORES if self.scores else 0)
         need = int(lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, int(slots), int(max_prompt), int(max_new), flags))
         if need == 0:
             raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
@@ -962,9 +1029,12 @@ class DecodeSession(_Session):
                 self._noise[i] = nz
         return ids
 
-    def take(self, slot: int) -> torch.Tensor:
-        """The codes of the finished request in `slot` (LongTensor on the device); the slot is free again."""
-        return super().take(slot)
+    def take(self, slot: int, scores: bool = False):
+        """The codes of the finished request in `slot` (LongTensor on the device); the slot is free again.  scores=True, on a session
+        created with scores=True: (codes, logprobs) -- one fp32 log-probability per code (include/idxtts.h "Scores")."""
+        if scores and not self.scores:
+            raise ValueError("take(scores=True) needs a session created with scores=True")
+        return super().take(slot, scores=scores)
 
     def park(self, slot: int) -> ParkedRow:
         """Takes the decoding request in `slot` out of the session with everything it has computed -- its step state, sampler, codes

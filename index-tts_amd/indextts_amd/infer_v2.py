@@ -10,6 +10,7 @@ forms (`PromptAudio`, `PromptFeatures`, `PromptConditioning`; token-id segments)
 """
 from __future__ import annotations
 
+import functools
 import os
 import time
 import warnings
@@ -303,6 +304,55 @@ class IndexTTS2:
             torch.cuda.synchronize(self.device)
         return time.perf_counter()
 
+    @staticmethod
+    def _row_latents(c, B: int):
+        """The GPT's per-row conditioning latents and emotion vectors of rows_conditioning's result."""
+        if isinstance(c, list):      # one prompt per row: the GPT takes per-row conditioning latents and emotion vectors as they are
+            return torch.cat([x.spk_cond_latent for x in c]), torch.cat([x.emo_vec for x in c])
+        lat = c.spk_cond_latent.expand(B, -1, -1) if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent
+        emo = c.emo_vec.expand(B, -1) if c.emo_vec.shape[0] == 1 else c.emo_vec
+        return lat, emo
+
+    def ranked_takes(self, text_tokens: torch.Tensor, cond, takes: int, max_mel_tokens: int = 1500, repetition_penalty: float = 10.0,
+                     sampling: Optional[dict] = None, length_penalty: float = 1.0):
+        """`takes` sampled takes of every row, decoded with one prefill per row (generate(num_return_sequences=takes,
+        return_logprobs=True)), and their ranking.  Returns (codes [B * takes, n] on the device, row i * takes + j take j of row i,
+        stop-padded; ranking): ranking[i] lists all the takes of row i best first as (take_index, score, stopped, n_codes) --
+        serving.rank_request: a take whose last code is the stop token ranks above every take that ran into max_mel_tokens, then the
+        higher score (gpt.sequence_scores of the codes' log-probabilities), then the lower index.  sampling: gpt_stage's dict, with
+        do_sample true and num_beams 1 (ValueError otherwise)."""
+        from .serving import rank_request
+        gen = dict(sampling or {})
+        if not gen.get("do_sample") or int(gen.pop("num_beams", None) or 1) != 1:
+            raise ValueError("ranked takes need do_sample=True and num_beams=1: greedy takes are all the same, and a beam search returns "
+                             "its scorer's n best")
+        gen.pop("length_penalty", None)
+        B = text_tokens.shape[0]
+        lat, emo = self._row_latents(rows_conditioning(cond, B, self.device), B)
+        codes, _, lp = self.gpt.inference_speech(lat, text_tokens, emo_vec=emo, max_generate_length=max_mel_tokens,
+                                                 repetition_penalty=repetition_penalty, num_return_sequences=int(takes),
+                                                 return_logprobs=True, num_beams=1, **gen)
+        hc, hl = codes.cpu(), lp.cpu()
+        rows, lps = [], []
+        for r in range(hc.shape[0]):
+            hits = (hc[r] == self.stop_mel_token).nonzero()
+            n = int(hits[0]) + 1 if len(hits) else int(hc.shape[1])
+            rows.append(hc[r, :n])
+            lps.append(hl[r, :n])
+        return codes, rank_request(rows, lps, int(takes), self.stop_mel_token, length_penalty)
+
+    def synthesize_best_of(self, text_tokens: torch.Tensor, cond, best_of: int, max_mel_tokens: int = 1500,
+                           repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise: Optional[torch.Tensor] = None,
+                           per_row_noise: bool = False, noise_seeds=None):
+        """synthesize_batch on the best of `best_of` sampled takes of every row: ranked_takes, then only each row's winner goes through
+        the latent pass, s2mel and the vocoder.  Returns the B waveforms; self.last_ranking keeps ranked_takes' ranking."""
+        codes, ranking = self.ranked_takes(text_tokens, cond, best_of, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
+                                           sampling=sampling)
+        self.last_ranking = ranking
+        win = [i * int(best_of) + rk[0][0] for i, rk in enumerate(ranking)]
+        st = self.gpt_stage(text_tokens, cond, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty, codes=codes[win])
+        return self.acoustic_stage(st, noise=noise, per_row_noise=per_row_noise, noise_seeds=noise_seeds)
+
     def gpt_stage(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
                   repetition_penalty: float = 10.0, sampling: Optional[dict] = None, sync_timers: bool = False,
                   codes: Optional[torch.Tensor] = None) -> dict:
@@ -314,12 +364,7 @@ class IndexTTS2:
         c = rows_conditioning(cond, B, dev)
         times = {}
         t0 = self._tick(sync_timers)
-        if isinstance(c, list):      # one prompt per row: the GPT takes per-row conditioning latents and emotion vectors as they are
-            lat = torch.cat([x.spk_cond_latent for x in c])
-            emo = torch.cat([x.emo_vec for x in c])
-        else:
-            lat = c.spk_cond_latent.expand(B, -1, -1) if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent
-            emo = c.emo_vec.expand(B, -1) if c.emo_vec.shape[0] == 1 else c.emo_vec
+        lat, emo = self._row_latents(c, B)
         gen = dict(sampling) if sampling else {"do_sample": False}
         gen.setdefault("num_beams", 1)
         if codes is None:
@@ -427,17 +472,24 @@ class IndexTTS2:
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, return_audio=False,
-              return_numpy=False, takes=1, **generation_kwargs):
+              return_numpy=False, takes=1, best_of=1, **generation_kwargs):
         """Reference signature and return contract (infer_v2.py:541-567): the generator itself when `stream_return`, else its
         first (only) item -- the output path, an InferenceResult, or (sampling_rate, int16 [n, 1]) -- or None for empty input.
         takes=n > 1: n takes of the whole text, one after the other, each drawing on from where the last one left the generators --
         a list of n results; with an output path the files are `stem.takeK.ext`, K = 0 .. n - 1.  Refused with `stream_return`.
+        best_of=n > 1: every segment is decoded as n sampled takes that share one prefill, the takes are ranked by the model's own
+        log-probabilities (ranked_takes: a take that ran into max_mel_tokens ranks last) and only the best one is synthesised; the
+        return contract is that of a plain call, streaming included.  Needs do_sample=True, num_beams=1 (ValueError otherwise) and is
+        refused together with takes > 1.
         `spk_audio_prompt` (and `emo_audio_prompt`): a WAV file path as in the reference, or a PromptAudio / PromptFeatures /
         PromptConditioning; `text`: a string (needs self.tokenizer), a list of token-id segments (List[List[int]]) or one segment
         (List[int] / 1-D tensor)."""
         takes = int(takes)
         if takes < 1 or (takes > 1 and stream_return):
             raise ValueError("takes must be >= 1, and takes > 1 does not stream (stream_return)")
+        best_of = self._check_best_of(best_of, generation_kwargs)
+        if best_of > 1 and takes > 1:
+            raise ValueError("best_of returns the one best take, takes every take: pass one of them")
         if takes > 1:
             stem, ext = os.path.splitext(output_path) if output_path else (None, "")
             return [self.infer(spk_audio_prompt, text, f"{stem}.take{k}{ext}" if stem else output_path, emo_audio_prompt, emo_alpha,
@@ -446,13 +498,24 @@ class IndexTTS2:
                     for k in range(takes)]
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
-                                   more_segment_before, return_audio=return_audio, return_numpy=return_numpy, **generation_kwargs)
+                                   more_segment_before, return_audio=return_audio, return_numpy=return_numpy, best_of=best_of,
+                                   **generation_kwargs)
         if stream_return:
             return gen
         try:
             return list(gen)[0]
         except IndexError:
             return None
+
+    @staticmethod
+    def _check_best_of(best_of, generation_kwargs) -> int:
+        best_of = int(best_of)
+        if best_of < 1:
+            raise ValueError("best_of must be >= 1")
+        if best_of > 1 and not (generation_kwargs.get("do_sample", True) and int(generation_kwargs.get("num_beams", 3)) == 1):
+            raise ValueError("best_of needs do_sample=True and num_beams=1: greedy takes are all the same, and a beam search already "
+                             "returns its best hypothesis")
+        return best_of
 
     def set_emotion_matrices(self, emo_matrix: torch.Tensor, spk_matrix: torch.Tensor, emo_num):
         """feat2.pt / feat1.pt and cfg.emo_num (infer_v2.py:281-289): the per-emotion banks the emo_vector mode mixes from."""
@@ -502,11 +565,12 @@ class IndexTTS2:
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, return_audio=False,
-                        return_numpy=False, **generation_kwargs):
+                        return_numpy=False, best_of=1, **generation_kwargs):
         """infer_v2.py:569-937.  Streaming (`stream_return`): after every segment yields its waveform (`[1, n]` float32 on the
         CPU, already scaled and clamped to +-32767) and then the inter-segment silence, and nothing else (874-879, 885-886)."""
         if stream_return and return_audio:
             raise ValueError("stream_return and return_audio are mutually exclusive")                # infer_v2.py:575-576
+        best_of = self._check_best_of(best_of, generation_kwargs)
         text_str = text if isinstance(text, str) else None      # use_emo_text without emo_text classifies the text itself
         if isinstance(text, str):
             # text front-end (infer_v2.py:697-704): tokenize, split into segments, ids.  The tokenizer (indextts_amd/tokenizer.py) needs
@@ -620,10 +684,12 @@ class IndexTTS2:
         start = time.perf_counter()
         wavs = []
         sil = self.interval_silence(interval_silence=interval_silence)
+        # best_of: the same call on each row's best take (synthesize_best_of)
+        synthesize = self.synthesize_batch if best_of == 1 else functools.partial(self.synthesize_best_of, best_of=best_of)
         if stream_return:
             for i, s in enumerate(segs):                                                             # segment loop, infer_v2.py:732
-                w = self.synthesize_batch(s, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
-                                          sampling=sampling, noise_seeds=None if nseeds is None else nseeds[i:i + 1])[0]
+                w = synthesize(s, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
+                               sampling=sampling, noise_seeds=None if nseeds is None else nseeds[i:i + 1])[0]
                 yield w.cpu()                                                                        # infer_v2.py:874-879
                 yield sil.cpu()
             return                                                                                   # infer_v2.py:885-886
@@ -639,9 +705,8 @@ class IndexTTS2:
             toks = torch.full((len(grp), L), stop_text, dtype=torch.long)
             for r, s in enumerate(grp):
                 toks[r, : s.shape[1]] = s[0]
-            wavs.extend(self.synthesize_batch(toks, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
-                                              sampling=sampling, per_row_noise=True,
-                                              noise_seeds=None if nseeds is None else nseeds[i:i + nb]))
+            wavs.extend(synthesize(toks, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
+                                   sampling=sampling, per_row_noise=True, noise_seeds=None if nseeds is None else nseeds[i:i + nb]))
         out = []
         for i, w in enumerate(wavs):                                                                 # insert_interval_silence 499-522
             out.append(w)

@@ -150,6 +150,56 @@ def merge_acoustic_states(items):
     return st, noise
 
 
+def rank_request(codes, logprobs, takes: int, stop_token: int, length_penalty: float = 1.0) -> list:
+    """The takes of every utterance of a request, ranked.  codes / logprobs: one 1-D row per take (row i * takes + j: take j of
+    utterance i), each as long as the take (the stop token included).  Returns ranking[i]: all `takes` takes of utterance i, best first,
+    as (take_index, score, stopped, n_codes) -- score = gpt.sequence_scores (the sum of the codes' log-probabilities over
+    n_codes ** length_penalty, float64), stopped = the last code is the stop token, order = gpt.rank_takes (stopped first, higher score,
+    lower index): a take that ran into its cap ranks below every take that stopped."""
+    from .gpt import rank_takes, sequence_scores
+    takes = int(takes)
+    lens = [int(c.shape[0]) for c in codes]
+    if len(codes) != len(logprobs) or len(codes) % takes or any(int(lp.shape[0]) != n for lp, n in zip(logprobs, lens)):
+        raise ValueError("one row of log-probabilities per row of codes, of the same length, `takes` rows per utterance")
+    scores = sequence_scores(logprobs, lens, length_penalty)
+    stopped = [int(c[-1]) == int(stop_token) for c in codes]
+    out = []
+    for a in range(0, len(codes), takes):
+        order = rank_takes(scores[a:a + takes], stopped[a:a + takes])
+        out.append([(t, float(scores[a + t]), stopped[a + t], lens[a + t]) for t in order])
+    return out
+
+
+def _keep_best(r, ranking, keep: int) -> list:
+    """Cuts a request (a _Request or a _Job) with r.takes takes per utterance down to the best `keep` of each, best first: its text,
+    per-row prompts, CFM noise rows and noise seeds follow the kept takes (take j of utterance i keeps entry i * takes + j), and r.takes
+    becomes `keep`.  Returns the kept rows' indices."""
+    rows = [i * r.takes + rk[q][0] for i, rk in enumerate(ranking) for q in range(keep)]
+    r.text = r.text[rows]
+    if isinstance(r.cond, (list, tuple)):
+        r.cond = [r.cond[q] for q in rows]
+    if r.noise is not None:
+        r.noise = r.noise[rows]
+    if r.noise_seeds is not None:
+        r.noise_seeds = [r.noise_seeds[q] for q in rows]
+    r.takes = keep
+    return rows
+
+
+def _check_keep(keep, takes: int, scored: bool, beam: bool):
+    """submit(keep=): None, or 1 <= keep <= takes on a pipeline that scores sampled takes."""
+    if keep is None:
+        return None
+    if beam:
+        raise ValueError("keep on a beam pipeline: `takes` already returns the scorer's n best hypotheses, best first")
+    if not scored:
+        raise ValueError("keep needs the takes' scores: build the pipeline with scores=True")
+    keep = int(keep)
+    if not 1 <= keep <= takes:
+        raise ValueError("keep must be in 1 .. takes")
+    return keep
+
+
 def _set_exception(fut, e: BaseException) -> None:
     """A failure handed to a request that has no outcome yet.  A cancelled request has one: it is left alone, also when the caller's
     cancel() lands between the check and the call."""
@@ -191,7 +241,7 @@ def _start(owner) -> bool:
 
 class _Request:
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done",
-                 "notified", "takes")
+                 "notified", "takes", "keep", "base")
 
     def compatible(self, other: "_Request") -> bool:
         # same prompt and settings, greedy (sampling draws are per call) and the SAME text width: a wider neighbour would left-pad this
@@ -241,7 +291,7 @@ class BatchPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               takes: int = 1) -> concurrent.futures.Future:
+               takes: int = 1, keep: Optional[int] = None) -> concurrent.futures.Future:
         """Queue one batch; returns a Future of the list of waveforms `synthesize_batch` would return.  Inputs produced on the
         caller's current stream are safe to use (an event recorded here is waited for on the lane's stream), and the waveforms
         are safe to read on that stream (they are tied to it with record_stream before the Future resolves).
@@ -250,12 +300,21 @@ class BatchPipeline:
         takes=n > 1 (sampled or beam-sample requests; a greedy one is refused, every take would be the same): the batch is decoded
         with every utterance repeated n times, row i * n + j take j of utterance i, each row drawing its own stream of the request's
         sampler; `noise` and the noise seeds (utterance_noise_seeds(noise_seed, B * n)) have B * n rows, and the Future resolves to
-        result[i][j]."""
+        result[i][j].
+        keep=k (1 <= k <= n; sampled, num_beams = 1): the takes are decoded with one prefill per utterance and scored
+        (IndexTTS2.ranked_takes: generate(num_return_sequences=n, return_logprobs=True)), and only the best k of every utterance go
+        through the latent pass, s2mel and the vocoder: result[i][j], j < k, best first, with their own noise rows / seeds (entry
+        i * n + take).  fut.ranking[i] -- every take of utterance i as (take_index, score, stopped, n_codes), best first
+        (rank_request) -- is set before the Future resolves.  A request with keep is never merged into another's decode."""
         takes = int(takes)
         if takes < 1 or (takes > 1 and not (sampling and sampling.get("do_sample"))):
             raise ValueError("takes must be >= 1, and takes > 1 needs a sampled request: every take of a greedy one would be the same")
+        if keep is not None and not (sampling and sampling.get("do_sample")):
+            raise ValueError("keep ranks sampled takes: the request must sample (do_sample)")
+        keep = _check_keep(keep, takes, True, bool(sampling and int(sampling.get("num_beams") or 1) > 1))
         r = _Request()
-        r.done, r.notified, r.takes = concurrent.futures.Future(), False, takes
+        r.done, r.notified, r.takes, r.keep = concurrent.futures.Future(), False, takes, keep
+        r.base = (torch.as_tensor(text_tokens), cond)      # one row per utterance: what a request with keep decodes from
         try:
             if takes > 1:
                 text_tokens, cond = torch.as_tensor(text_tokens).repeat_interleave(takes, 0), _expand_cond(cond, takes)
@@ -335,8 +394,18 @@ class BatchPipeline:
             text = group[0].text if len(group) == 1 else torch.cat([torch.as_tensor(r.text).cpu() for r in group])      # equal widths
             subs = []
             with self._turn, torch.cuda.stream(sg):
-                st = self.tts.gpt_stage(text, group[0].cond, max_mel_tokens=group[0].max_mel_tokens,
-                                        repetition_penalty=group[0].repetition_penalty, sampling=group[0].sampling)
+                if group[0].keep is not None:      # (a sampled request: alone in its group) every take decoded and ranked, the best kept
+                    r = group[0]
+                    codes, ranking = self.tts.ranked_takes(r.base[0], r.base[1], r.takes, max_mel_tokens=r.max_mel_tokens,
+                                                           repetition_penalty=r.repetition_penalty, sampling=r.sampling)
+                    rows = _keep_best(r, ranking, r.keep)
+                    r.done.ranking = ranking
+                    text = r.text
+                    st = self.tts.gpt_stage(text, r.cond, max_mel_tokens=r.max_mel_tokens, repetition_penalty=r.repetition_penalty,
+                                            codes=codes[rows])
+                else:
+                    st = self.tts.gpt_stage(text, group[0].cond, max_mel_tokens=group[0].max_mel_tokens,
+                                            repetition_penalty=group[0].repetition_penalty, sampling=group[0].sampling)
                 # every request's rows as its own state, cut on the LANE's stream: the slicing copies below are launches like any
                 # other, and the acoustic worker reads their results on a stream of its own -- they must be inside what the
                 # host-side wait below covers (and allocated from this stream's pool)
@@ -417,7 +486,7 @@ class BatchPipeline:
                 a += sub["B"]
                 for w in mine:                    # allocated on the worker's stream, consumed on the caller's
                     w.record_stream(r.caller)
-                r.done.set_result(mine if r.takes == 1 else [mine[i:i + r.takes] for i in range(0, len(mine), r.takes)])
+                r.done.set_result(mine if r.takes == 1 and r.keep is None else [mine[i:i + r.takes] for i in range(0, len(mine), r.takes)])
         except BaseException as e:                  # noqa: BLE001
             for r, _ in group:
                 _set_exception(r.done, e)
@@ -445,7 +514,7 @@ class BatchPipeline:
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest")
+                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest", "keep", "lps")
 
 
 def _expand_cond(cond, n: int):
@@ -595,13 +664,19 @@ class ContinuousPipeline:
     lane), under the same rules: strictly more urgent only, the least urgent and last admitted group first, parked groups ahead of
     never-admitted utterances of their priority, park_to, the trace entries, cancellation, deadlines, failures and close().
 
-    session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close; evict to cancel; park / resume to
+    scores=True (num_beams == 1): the sessions record every code's log-probability (decode_session(scores=True)) and
+    submit(takes=n, keep=k) ranks each utterance's takes once all of them are decoded; only the best k go on to the latent pass and the
+    acoustic job (see submit).  The codes are those of a pipeline without scores.
+
+    session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close; scores=True: take(slot, scores=True)
+    -> (codes, logprobs); evict to cancel; park / resume to
     preempt; a beam pipeline's: free_groups, park_group / resume_group) replaces the HIP session (tests)."""
 
     def __init__(self, tts, slots: int = 16, decode_lanes: int = 1, acoustic_workers: int = 1, poll_steps: int = 16,
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
                  session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
-                 acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device", preempt_groups: bool = False):
+                 acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device", preempt_groups: bool = False,
+                 scores: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
@@ -621,6 +696,9 @@ class ContinuousPipeline:
         self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
         self.max_new = int(max_new or g.max_mel_tokens)
         self.allow_sampling = bool(allow_sampling)
+        self.scores = bool(scores)
+        if self.scores and self.num_beams > 1:
+            raise ValueError("scores=True needs num_beams == 1: a beam pipeline's takes are the scorer's n best, already ranked")
         self.preempt = bool(preempt)
         if park_to not in ("device", "host"):
             raise ValueError('park_to must be "device" or "host"')
@@ -636,8 +714,8 @@ class ContinuousPipeline:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
                                                                                    repetition_penalty=self.repetition_penalty))
         else:
-            self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(slots, mp, mn, repetition_penalty=self.repetition_penalty,
-                                                                                     sampled=self.allow_sampling))
+            self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(
+                slots, mp, mn, repetition_penalty=self.repetition_penalty, sampled=self.allow_sampling, **({"scores": True} if self.scores else {})))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index, ParkedRow or None) waiting for a slot, most urgent first
@@ -663,7 +741,8 @@ class ContinuousPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               deadline_s: Optional[float] = None, priority: int = 0, takes: int = 1) -> concurrent.futures.Future:
+               deadline_s: Optional[float] = None, priority: int = 0, takes: int = 1,
+               keep: Optional[int] = None) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
@@ -676,12 +755,22 @@ class ContinuousPipeline:
         deadlines, priorities, park and resume, and the takes of an utterance that are admitted in one poll share one prefill
         (DecodeSession.admit(takes=)) -- a request whose takes do not all fit is admitted in parts.  Greedy requests are refused
         (every take would be the same).  Beam pipelines: the n best hypotheses of each utterance's group
-        (BeamDecodeSession.take(n_best=)), n <= num_beams, else the request's Future fails; the noise seeds are again B * n."""
+        (BeamDecodeSession.take(n_best=)), n <= num_beams, else the request's Future fails; the noise seeds are again B * n.
+        keep=k (1 <= k <= n; a pipeline built with scores=True, a sampled request): once every take of the request is decoded, each
+        utterance's takes are ranked (rank_request: stopped takes first, then the higher sequence score of the codes' log-probabilities,
+        then the lower take index), and only the best k go to gpt_stage(codes=) and the acoustic job.  The Future resolves to
+        result[i][j], j < k, best first; before that, fut.ranking[i] is set: all n takes of utterance i as (take_index, score, stopped,
+        n_codes), best first.  Noise rows and seeds follow the kept takes (take j keeps entry i * n + j).  Every take still decodes to
+        its end and is an ordinary row for cancellation, deadlines, priorities, park and resume; a cancelled request is never ranked.
+        keep=None: every take is synthesised, as ever.  keep without scores=True, or on a beam pipeline, raises ValueError here."""
         if deadline_s is not None:
             deadline_s = float(deadline_s)
         priority, takes = int(priority), int(takes)
         if takes < 1:
             raise ValueError("takes must be >= 1")
+        keep = _check_keep(keep, takes, self.scores, self.num_beams > 1)
+        if keep is not None and not (self.allow_sampling and sampling and sampling.get("do_sample")):
+            raise ValueError("keep ranks sampled takes: the request must sample (allow_sampling, do_sample)")
         if self.num_beams > 1:
             def beams(B):
                 if takes > self.num_beams:
@@ -695,10 +784,11 @@ class ContinuousPipeline:
         if takes > 1 and not (self.allow_sampling and sampling and sampling.get("do_sample")):
             raise ValueError("takes > 1 needs a sampled request: every take of a greedy one would be the same")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority, takes)
+                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority, takes,
+                            keep)
 
     def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None,
-                priority=0, takes=1):
+                priority=0, takes=1, keep=None):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -710,10 +800,13 @@ class ContinuousPipeline:
         units = int(j.text.shape[0])
         beam = self.num_beams > 1
         j.takes, j.nbest = takes, takes if beam else 1
+        j.keep, j.lps = keep, None
         if takes > 1:
             j.text = j.text.repeat_interleave(takes, 0)
         B = units * takes
         j.codes, j.left, j.failed = [None] * B, (units if beam else B), False
+        if keep is not None:
+            j.lps = [None] * B
         j.done, j.notified = concurrent.futures.Future(), False
         j.sampling, j.seq, j.noise_seeds = None, -1, None
         j.priority, j.stamp = priority, [0] * B
@@ -900,6 +993,11 @@ class ContinuousPipeline:
             j, i = in_slot.pop(s)
             if j.nbest > 1:                     # a beam group's n best: the rows i .. i + n - 1 of the job
                 best = [c.cpu() for c, _ in sess.take(s, n_best=j.nbest)]
+            elif self.scores:                   # a scored session: the codes' log-probabilities come with them
+                c, lp = sess.take(s, scores=True)
+                best = [c.cpu()]
+                if j.lps is not None:
+                    j.lps[i] = lp.cpu()
             else:
                 best = [sess.take(s).cpu()]
             if self._gone(j):
@@ -907,6 +1005,11 @@ class ContinuousPipeline:
             j.codes[i:i + len(best)] = best
             j.left -= 1
             if j.left == 0:
+                if j.keep is not None:          # every take is decoded: rank them, the best `keep` of each utterance go on
+                    ranking = rank_request(j.codes, j.lps, j.takes, self.tts.cfg.gpt.stop_mel_token)
+                    rows = _keep_best(j, ranking, j.keep)
+                    j.codes, j.lps = [j.codes[q] for q in rows], None
+                    j.done.ranking = ranking
                 done.append(j)
         if done:
             with self._cv:                  # every request this poll finished is queued before any worker looks
@@ -1017,7 +1120,7 @@ class ContinuousPipeline:
                 if j.caller is not None:
                     for w in mine:              # allocated on the worker's stream, consumed on the caller's
                         w.record_stream(j.caller)
-                j.done.set_result(mine if j.takes == 1 else [mine[i:i + j.takes] for i in range(0, len(mine), j.takes)])
+                j.done.set_result(mine if j.takes == 1 and j.keep is None else [mine[i:i + j.takes] for i in range(0, len(mine), j.takes)])
         except BaseException as e:              # noqa: BLE001 -- every request of this acoustic batch fails, nothing else
             for j in group:
                 self._fail(j, e)
