@@ -393,6 +393,27 @@ int idxtts_gpt_generate_scored(idxtts_ctx* ctx, const float* inputs_embeds, cons
 int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
                                       float repetition_penalty, const long long* forced_codes, long long* codes, int* n_steps,
                                       float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- Continuing from given codes ----
+ * The reference's inference_speech(..., input_tokens=) (model_v2.py:838-856): mel codes appended to input_ids, generation goes on behind
+ * them.  A prefix of k codes makes the prefill run on P + 1 + k positions -- the prompt, mel_emb[start] + mel_pos[0], then
+ * mel_emb[prefix[j]] + mel_pos[pos0 + j] for j < k -- and the row start with pos = P + k, mel_pos = k + 1: the first new code is fed
+ * at mel position k + 2.  Two layouts, differing in the prefix codes' positions only:
+ *   prefix_pos0 = 1 ("hf"): code j at mel position j + 1, what the reference's first forward embeds (model_v2.py:163-165);
+ *   prefix_pos0 = 2 ("resume"): code j at mel position j + 2, where the uninterrupted run fed it (that run never uses position 1:
+ *   model_v2.py:175).  The reference's continuation is therefore not the continuation of its own uninterrupted run; sessions use 2.
+ * The repetition penalty sees the prefix, as HF's processor reads the whole input_ids.
+ * idxtts_gpt_generate_prefix: idxtts_gpt_generate_scored with prefix (device int64 [B][k], one row per prompt, shared by its takes), k
+ * and prefix_pos0; sampling, logprobs and logits_out may each be NULL.  max_new_tokens, exp_noise [max_new_tokens][B * takes][V], the
+ * seeded draw counter, codes, logprobs and logits_out count NEW tokens from 0.  Workspace: idxtts_gpt_workspace_bytes(B * takes,
+ * P + 1 + k, max_new_tokens).  k = 0 (prefix ignored) is idxtts_gpt_generate_scored bit for bit (logprobs NULL: _generate_takes).  Takes
+ * with a prefix equal the caller-expanded batch under _generate_takes' conditions, the two prefills counting P + 1 + k positions a row.
+ * Refused, before anything runs: k < 0, a NULL prefix with k > 0, prefix_pos0 other than 1 or 2; a prefix code outside [0, V) or equal
+ * to stop_mel_token ("prefix contains the stop token"); k + max_new_tokens + 1 >= the mel position table's rows ("prefix +
+ * max_new_tokens exceed the mel position table"); a workspace smaller than the size above. */
+int idxtts_gpt_generate_prefix(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                               float repetition_penalty, const idxtts_sampling* sampling, const long long* prefix, int k, int prefix_pos0,
+                               long long* codes, int* n_steps, float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes,
+                               int use_graph, void* stream);
 /* Beam search / beam-sample = what `IndexTTS2.infer` runs by default (infer_v2.py:714-722, 767: do_sample=True, num_beams=3,
  * top_p .8, top_k 30, temperature .8, repetition_penalty 10, length_penalty 0) through HF `_beam_search`
  * (transformers_generation_utils.py:3325-3516) + BeamSearchScorer (transformers_beam_search.py:123-420): log_softmax before
@@ -469,6 +490,10 @@ int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds,
  * receives lp[0, at) of the source), _evict, _stop, _park, _park_bytes and _resume work as on any session.  Beam sessions have no such
  * flag: their hypotheses carry the scorer's scores. */
 #define IDXTTS_SESSION_SCORES 2
+/* Sessions that admit rows behind given codes (_admit_prefix below): flags |= IDXTTS_SESSION_PREFIX sizes the admission's prefill area
+ * for at least one row of max_prompt + 1 + max_new_tokens positions (without it: slots rows of max_prompt + 1) and adds two [slots]
+ * int32 arrays behind everything else; every other flag combination keeps its size and layout.  Not for beam sessions. */
+#define IDXTTS_SESSION_PREFIX 8       /* (4 is not a flag: _workspace_bytes_ex returns 0 for it and _init_ex refuses it, as ever) */
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags);
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
                                void* workspace, size_t workspace_bytes, void* stream);
@@ -520,6 +545,28 @@ int idxtts_gpt_session_admit_takes(idxtts_ctx* ctx, int n, const float* inputs_e
  * the source's included, are untouched. */
 int idxtts_gpt_session_fork(idxtts_ctx* ctx, int src_slot, int at, int n, const int* dst_slots, const idxtts_sampling* samplers,
                             const int* max_new_tokens, void* workspace, void* stream);
+/* _admit_prefix ("Continuing from given codes" above, layout prefix_pos0 = 2): _admit_takes -- takes NULL = one slot per request, slot_ids /
+ * max_new_tokens / per_take then [n] -- where request b starts behind the prefix_lens[b] >= 0 codes (HOST int32 [n]) it is given:
+ * prefix, device int64, the n prefixes packed one behind the other (request b's at the sum of the lengths before it);
+ * prefix_logprobs, device fp32 packed likewise, or NULL.  A request's takes share its prefix and its one prefill row of
+ * P + 1 + k positions.  Each slot starts as _fork leaves a take cut at k: SlotState {P + k, k + 1, k, cap, live}, codes[0, k) = the
+ * prefix, seen = {1, start} and the prefix, and on a scored session lp[0, k) = prefix_logprobs (NULL: 0); its first new code is drawn in
+ * the admission.  The cap counts prefix + new codes; exp_noise [cap][V] and the seeded draw counter are indexed by the absolute step
+ * (rows below k are never read: _fork's rule); _read returns prefix + continuation.  _fork at any at >= 1, _park, _resume, _evict,
+ * _stop and _read_scored treat the row as any other (at = 0 is refused on it as on a resumed row: x_last is not the prompt's).
+ * Every k = 0: _admit_takes, kernel for kernel.
+ * The prefill takes rows x S positions of the prefill area, S = max_b (P_b + 1 + k_b), rows = n (bf16 KV in split-bf16 mode:
+ * max(n, ceil(256 / S))); an admission above the area is refused with the limit in the message: admit in smaller groups.
+ * Refused, before anything changes: a beam session ("a beam session takes no prefix"); a session without IDXTTS_SESSION_PREFIX when
+ * some k > 0 (the message names the flag); k < 0 or k >= the request's cap, for any of its takes ("prefix: k >= cap"; since cap <=
+ * max_new_tokens and _init checks max_new_tokens + 1 against the mel position table, no position can lie beyond the table or the
+ * cache); a code outside [0, V) or equal to stop_mel_token ("prefix contains the stop token"); and everything _admit_takes refuses.
+ * Determinism: the row's codes equal, bit for bit, row 0 of idxtts_gpt_generate_prefix (prefix_pos0 = 2) on `slots` copies of its
+ * prompt and prefix with the same sampler -- exp_noise rows offset by k, a seed's counter likewise absolute in the session -- under the
+ * session rules above; whatever else is admitted with it, whichever slot it has. */
+int idxtts_gpt_session_admit_prefix(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* takes,
+                                    const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take, const int* prefix_lens,
+                                    const long long* prefix, const float* prefix_logprobs, void* workspace, void* stream);
 /* Beam sessions (beam search / beam-sample per request, idxtts_gpt_generate_beam's semantics): the `slots` rows form slots / num_beams
  * groups of num_beams consecutive slots (2 <= num_beams <= 8, slots % num_beams == 0, slots <= 64); each admitted request takes one
  * group and runs HF _beam_search + BeamSearchScorer with its own idxtts_beam.  A group retires when its scorer is done

@@ -449,6 +449,17 @@ int idxtts_gpt_generate_scored(idxtts_ctx* ctx, const float* inputs_embeds, cons
   API_END
 }
 
+int idxtts_gpt_generate_prefix(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int takes, int P, int max_new_tokens,
+                               float repetition_penalty, const idxtts_sampling* sampling, const long long* prefix, int k, int prefix_pos0,
+                               long long* codes, int* n_steps, float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes,
+                               int use_graph, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes, logprobs, prefix, k, prefix_pos0);
+  API_END
+}
+
 int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, int max_new_tokens,
                                       float repetition_penalty, const long long* forced_codes, long long* codes, int* n_steps,
                                       float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -521,19 +532,19 @@ int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_
 
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags) {
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
-  if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES)) return 0;
+  if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
   return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, (flags & IDXTTS_SESSION_SAMPLED) != 0, 0,
-                                        (flags & IDXTTS_SESSION_SCORES) != 0) : 0;
+                                        (flags & IDXTTS_SESSION_SCORES) != 0, (flags & IDXTTS_SESSION_PREFIX) != 0) : 0;
 }
 
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
                                void* workspace, size_t workspace_bytes, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES)), "unknown session flags");
+  IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)), "unknown session flags");
   return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
-                         (flags & IDXTTS_SESSION_SAMPLED) != 0, 0, (flags & IDXTTS_SESSION_SCORES) != 0);
+                         (flags & IDXTTS_SESSION_SAMPLED) != 0, 0, (flags & IDXTTS_SESSION_SCORES) != 0, (flags & IDXTTS_SESSION_PREFIX) != 0);
   API_END
 }
 
@@ -564,6 +575,17 @@ int idxtts_gpt_session_admit_takes(idxtts_ctx* ctx, int n, const float* inputs_e
   IDX_CHECK(takes, "null pointer");
   return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
                           per_take, takes);
+  API_END
+}
+
+int idxtts_gpt_session_admit_prefix(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* takes,
+                                    const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take, const int* prefix_lens,
+                                    const long long* prefix, const float* prefix_logprobs, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(prefix_lens, "null prefix_lens");
+  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
+                          per_take, takes, prefix_lens, prefix, prefix_logprobs);
   API_END
 }
 

@@ -208,6 +208,32 @@ int session_prefill_input(float* x, const float* emb, int ld_rows, const int* P,
 // (admission with takes): entry t of slot_ids / cap is a take of prefill row row[t], whose P and x row it gets
 int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_token, float* x_last, const float* x, int S, int d,
                         const int* slot_ids, const int* P, const int* cap, int n, hipStream_t stream, const int* row = nullptr);
+// Continuing from given codes (idxtts.h): the prefill input rows of a prefix.  Row b of x [rows][S][d] gets, at positions
+// P_b + 1 + j for j < k_b, mel_emb[prefix_b[j]] + mel_pos[pos0 + j]; pos0 = 1 (the reference's layout) or 2 (the positions an
+// uninterrupted run fed).  P / klen null: P_all / k_all for every row.  prefix_b starts at prefix + off[b], or (off null) at
+// prefix + (b / row_div) * k_all: a dense [prompts][k_all] array, row_div prefill rows per prompt.  The caller has checked that
+// P_b + 1 + k_b <= S, pos0 + k_b <= the position table's rows and every code is a row of mel_emb.  kmax: the longest k_b.
+struct PrefixRows {
+  float* x = nullptr; int S = 0, d = 0;
+  const int* P = nullptr; int P_all = 0;
+  const int* klen = nullptr; int k_all = 0;
+  const long long* prefix = nullptr; const int* off = nullptr; int row_div = 1;
+  int pos0 = 2;
+  const float* mel_emb = nullptr; const float* mel_pos = nullptr; int V = 0;
+};
+int prefix_input_rows(const PrefixRows& a, int rows, int kmax, hipStream_t stream);
+// session_reset_slots for an admission with prefixes (klen [rows], off [rows] into the packed prefix / prefix_lp): slot slot_ids[t]
+// starts behind the k = klen[b] codes of its prefill row b -- seen = {1, start_token} and the codes, codes[slot][0, k) = the codes,
+// logprobs[slot][0, k) = prefix_lp's values or 0 (logprobs null: the session records none), x_last[slot] = x[b][P[b] + k], state
+// {P[b] + k, k + 1, k, cap[t], 1}.  k = 0 is exactly session_reset_slots.
+struct PrefixReset {
+  SlotState* slots = nullptr; unsigned char* seen = nullptr; int V = 0, start_token = 0;
+  float* x_last = nullptr; const float* x = nullptr; int S = 0, d = 0;
+  const int* slot_ids = nullptr; const int* P = nullptr; const int* cap = nullptr; const int* row = nullptr;
+  const int* klen = nullptr; const int* off = nullptr; const long long* prefix = nullptr; const float* prefix_lp = nullptr;
+  long long* codes = nullptr; int codes_ld = 0; float* logprobs = nullptr;
+};
+int session_reset_slots_prefix(const PrefixReset& a, int n, hipStream_t stream);
 // Ends slots of a decode session between steps (eviction, stop): slot i of the n_slots <= 64 slots for every set bit i of `mask`, passed
 // by value -- live = 0, step kept (the codes produced so far).  cap_at_step: a slot that was live also gets max_step = step (a cap set
 // late: what reads the slot afterwards sees a request that ended at that cap); a slot that had ended is left as it was.

@@ -1208,6 +1208,64 @@ int session_reset_slots(SlotState* slots, unsigned char* seen, int V, int start_
   return 0;
 }
 
+// Continuing from given codes: the prefill input rows behind the start token.  Workgroup (j, b) writes position P_b + 1 + j of prefill
+// row b, x = mel_emb[prefix_b[j]] + mel_pos[pos0 + j] -- the sum write_next_input forms for a decode step's input.  Every other row of
+// the input is written by the kernels of before (the generation's copies and gather, session_prefill_input_kernel), which run first.
+__global__ __launch_bounds__(256) void prefix_input_rows_kernel(const PrefixRows p) {
+  const int j = blockIdx.x, b = blockIdx.y;
+  const int Pb = p.P ? p.P[b] : p.P_all, kb = p.klen ? p.klen[b] : p.k_all;
+  if (j >= kb) return;      // (workgroup-uniform)
+  const size_t base = p.off ? (size_t)p.off[b] : (size_t)(b / p.row_div) * p.k_all;
+  const int tok = min(max((int)p.prefix[base + j], 0), p.V - 1);      // (inside the table whatever the caller holds: the host has checked)
+  float* out = p.x + ((size_t)b * p.S + Pb + 1 + j) * p.d;
+  const float* te = p.mel_emb + (size_t)tok * p.d;
+  const float* pe = p.mel_pos + (size_t)(p.pos0 + j) * p.d;
+  for (int e = threadIdx.x; e < p.d; e += 256) out[e] = te[e] + pe[e];
+}
+
+int prefix_input_rows(const PrefixRows& a, int rows, int kmax, hipStream_t stream) {
+  IDX_CHECK(a.x && a.prefix && a.mel_emb && a.mel_pos, "null pointer");
+  IDX_CHECK(a.S >= 1 && a.d >= 1 && a.V >= 1 && a.row_div >= 1 && (a.pos0 == 1 || a.pos0 == 2), "prefix rows: shape");
+  IDX_CHECK(a.P || (a.P_all >= 1 && a.P_all + 1 + a.k_all <= a.S), "prefix rows: the prefix does not fit the prefill row");
+  IDX_CHECK(a.klen || kmax == a.k_all, "prefix rows: one length for every row, or a length per row");
+  if (rows <= 0 || kmax <= 0) return 0;
+  IDX_CHECK(rows <= 65535, "prefix rows: too many rows");
+  static const int cat = prof_register("prefix_input_rows_kernel");
+  ProfScope prof(cat, stream, 0.0, 12.0 * rows * (double)kmax * a.d);
+  hipLaunchKernelGGL(prefix_input_rows_kernel, dim3(kmax, rows), dim3(256), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// session_reset_slots for an admission with prefixes: entry t's slot starts behind its prefill row's k = klen[b] given codes -- seen =
+// {1, start} and the codes, codes[slot][0, k) = the codes, logprobs[slot][0, k) = the caller's values or 0 (scored sessions), x_last from
+// position P + k, state {P + k, k + 1, k, cap, 1}: what session_fork_kernel leaves a take cut at k, in front of its next token
+__global__ __launch_bounds__(256) void session_reset_slots_prefix_kernel(const PrefixReset p) {
+  const int t = blockIdx.x, slot = p.slot_ids[t], b = p.row ? p.row[t] : t, Pb = p.P[b], kb = p.klen[b];
+  const size_t base = (size_t)p.off[b];
+  unsigned char* sr = p.seen + (size_t)slot * p.V;
+  for (int v = threadIdx.x; v < p.V; v += 256) sr[v] = (v == 1 || v == p.start_token) ? 1 : 0;      // input_ids = [1 ... 1, start | prefix]
+  __syncthreads();
+  for (int i = threadIdx.x; i < kb; i += 256) {
+    const long long c = p.prefix[base + i];
+    p.codes[(size_t)slot * p.codes_ld + i] = c;
+    sr[min(max((int)c, 0), p.V - 1)] = 1;
+    if (p.logprobs) p.logprobs[(size_t)slot * p.codes_ld + i] = p.prefix_lp ? p.prefix_lp[base + i] : 0.0f;
+  }
+  const float* src = p.x + ((size_t)b * p.S + Pb + kb) * p.d;
+  for (int e = threadIdx.x; e < p.d; e += 256) p.x_last[(size_t)slot * p.d + e] = src[e];
+  if (threadIdx.x == 0) p.slots[slot] = SlotState{Pb + kb, kb + 1, kb, p.cap[t], 1};
+}
+
+int session_reset_slots_prefix(const PrefixReset& a, int n, hipStream_t stream) {
+  IDX_CHECK(a.slots && a.seen && a.x_last && a.x && a.slot_ids && a.P && a.cap && a.klen && a.off && a.prefix && a.codes, "null pointer");
+  IDX_CHECK(a.V >= 2 && a.S >= 1 && a.d >= 1 && a.codes_ld >= 1, "prefix reset: shape");
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(session_reset_slots_prefix_kernel, dim3(n), dim3(256), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
 // ends the slots of `mask` (bit i = slot i) from outside the step: live = 0, step left as it is (the codes produced so far), as the
 // sampler leaves a slot that ended by itself.  cap_at_step (stop): a slot that was live also gets max_step = step, the cap it would
 // have ended at by itself; one that had ended keeps its state.

@@ -1,4 +1,5 @@
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <functional>
 #include <map>
@@ -148,12 +149,16 @@ struct GPTModel : ModelBase {
   int call_stream(hipStream_t user, hipStream_t* st);
   int run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                      float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll, int poll_n,
-                     int poll_every, int* steps_done, hipStream_t st, bool share_prefill = false);      // share_prefill: B prefill rows,
+                     int poll_every, int* steps_done, hipStream_t st, bool share_prefill = false,      // share_prefill: B prefill rows,
                      // each row's KV and last position fanned out to its fan decode rows (takes); else R prefill rows (beams)
+                     const long long* prefix = nullptr, const long long* prefix_host = nullptr, int k = 0, int pos0 = 2);
+                     // k > 0 (continuing from given codes): prefix device [B][k] and its host copy, one row per prompt; the prefill
+                     // runs on P + 1 + k positions, prefix code j at mel position pos0 + j, and the state starts behind the prefix
   int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_sampling* sampling, long long* codes,
                int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr,
                int takes = 1,       // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per prompt
-               float* logprobs = nullptr);      // device [B * takes][max_new]: every code's log-probability (idxtts.h "Scores")
+               float* logprobs = nullptr,       // device [B * takes][max_new]: every code's log-probability (idxtts.h "Scores")
+               const long long* prefix = nullptr, int k = 0, int prefix_pos0 = 1);      // device [B][k]: continue behind these codes (idxtts.h)
   // Beam search / beam-sample (HF _beam_search; the reference's default decoding mode, infer_v2.py:714-722): B utterances x
   // num_beams rows through the same decode step, selection / hypotheses / re-indexing on the device (beam.hip).
   size_t beam_workspace_bytes(int B, int nb, int S, int max_new) const;
@@ -174,6 +179,7 @@ struct GPTModel : ModelBase {
     int invariant = 0;                // the context's batch-invariant mode at _init: the session keeps it (changed since: every call refuses)
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
     bool scores = false;              // IDXTTS_SESSION_SCORES: [slots][max_new] log-probabilities behind everything else (w.logprobs)
+    bool prefix = false;              // IDXTTS_SESSION_PREFIX: a prefill area that holds one row of max_prompt + 1 + max_new positions
     std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
     int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
     std::vector<SlotBeam> beam;       // host image of the SlotBeam table (beam sessions), copied whole at each admission
@@ -191,31 +197,44 @@ struct GPTModel : ModelBase {
     Buffers w;                        // decode buffers for `slots` rows (w.slots set) + the admission prefill's activations
     float* x_last;                    // [slots][d] last valid prefill row of each admitted request (first-token head input)
     int *ids, *plen, *klen, *cap;     // admission staging: slot ids, prompt lengths (prefill rows: -1 = padding row), P + 1, caps
+    int *pk, *poff;                   // IDXTTS_SESSION_PREFIX: [slots] prefix length of each admitted request and its offset in the packed codes
     SlotSampling* samp;               // [slots] per-slot samplers (sampled sessions only, else null)
     BeamBuffers bb;                   // beam sessions: proc, beam scores, next_tok, beam_idx, seq [slots][max_new], hypotheses per group
     SlotBeam* beam;                   // [groups] per-request beam parameters (beam sessions only, else null)
     size_t bytes;
   };
-  size_t session_prefill_rows(int slots, int max_prompt) const { return (size_t)slots * (max_prompt + 1) + 256; }
+  // prefix_new (IDXTTS_SESSION_PREFIX: the session's max_new, else 0): at least one row of max_prompt + 1 + max_new positions as well
+  size_t session_prefill_rows(int slots, int max_prompt, int prefix_new = 0) const {
+    const size_t rows = (size_t)slots * (max_prompt + 1) + 256;
+    return prefix_new > 0 ? std::max(rows, (size_t)max_prompt + 1 + prefix_new + 256) : rows;
+  }
   // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before;
   // num_beams > 0 (beam session): the beam buffers and the SlotBeam table likewise
-  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0, bool scores = false) const;
-  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0, bool scores = false) const;
+  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0, bool scores = false,
+                               bool prefix = false) const;
+  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0, bool scores = false,
+                                 bool prefix = false) const;
   Session* find_session(void* ws);
   int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false,
-                   int num_beams = 0, bool scores = false);
+                   int num_beams = 0, bool scores = false, bool prefix = false);
   // The admission both session kinds share: n requests into the free units ids[] -- slots, or (fan > 1) groups of fan slots -- each
   // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's
   // keys and values going to its unit's slots.  *S: positions per prefill row.
   int admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                     const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S, hipStream_t st,
-                    const int* takes = nullptr, const int** take_row = nullptr);
+                    const int* takes = nullptr, const int** take_row = nullptr, const int* prefix_lens = nullptr,
+                    const long long* prefix = nullptr);
+  // prefix_lens, prefix (sessions with IDXTTS_SESSION_PREFIX): request b's prefill row holds P_b + 1 + prefix_lens[b] positions, the
+  // last prefix_lens[b] of them its codes of the packed device array `prefix`; their lengths and offsets are left in sb.pk / sb.poff
   // takes (fan = 1): request b gets takes[b] slots -- ids and caps then hold one entry per take, request after request -- and its one
   // prefill row's keys and values go to all of them; *take_row: device array, the prefill row of each take
   // per_row: null = every row greedy; else one sampler per row (sampled sessions only).  takes: null, or takes[b] >= 1 slots per
   // request (slot_ids, max_new and per_row then have one entry per take)
   int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr, const int* takes = nullptr);
+                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr, const int* takes = nullptr,
+                    const int* prefix_lens = nullptr, const long long* prefix = nullptr, const float* prefix_logprobs = nullptr);
+  // prefix_lens HOST [n], prefix device int64 (the n prefixes packed one behind the other), prefix_logprobs device fp32 likewise or
+  // null: request b continues behind its codes (idxtts.h "Continuing from given codes"); all of them null: the call of before
   // n further takes of the request in slot src, cut back to `at` codes, in the free slots dst_slots (idxtts.h); samplers: null = greedy
   // takes; caps: null = the source's cap.  Every refusal happens before anything changes.
   int session_fork(void* ws, int src, int at, int n, const int* dst_slots, const idxtts_sampling* samplers, const int* caps, hipStream_t st);

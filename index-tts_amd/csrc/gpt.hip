@@ -471,8 +471,10 @@ int GPTModel::call_stream(hipStream_t user, hipStream_t* st) {
 // to *captured when that is not null.  Every poll_every steps it reads the poll_n device flags `poll` and stops when all are set.
 int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                              float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll,
-                             int poll_n, int poll_every, int* steps_done, hipStream_t st, bool share_prefill) {
-  const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1, R = B * fan;
+                             int poll_n, int poll_every, int* steps_done, hipStream_t st, bool share_prefill, const long long* prefix,
+                             const long long* prefix_host, int k, int pos0) {
+  const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1 + k, R = B * fan;
+  IDX_CHECK(k == 0 || (prefix && prefix_host), "null prefix");
   if (fan == 1) share_prefill = false;
   // ---- per-call state ----
   std::vector<int> kstart(R, 0);
@@ -488,8 +490,10 @@ int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const
   // input_ids of the reference = fake prefix of 1s + start_mel_token: both count for the repetition penalty
   std::vector<unsigned char> seen((size_t)R * V, 0);
   for (int r = 0; r < R; ++r) { seen[(size_t)r * V + 1] = 1; seen[(size_t)r * V + cfg.start_mel_token] = 1; }
+  for (int r = 0; r < R; ++r)      // ... and so do the given codes behind them (HF's processor reads the whole input_ids)
+    for (int j = 0; j < k; ++j) seen[(size_t)r * V + prefix_host[(size_t)(r / fan) * k + j]] = 1;
   IDX_HIP(hipMemcpyAsync(w.seen, seen.data(), seen.size(), hipMemcpyHostToDevice, st));
-  const DecodeState s0{P, 1, 0, 0};
+  const DecodeState s0{P + k, 1 + k, 0, 0};      // behind a prefix of k codes: the scalars an uninterrupted run holds after k steps
   IDX_HIP(hipMemcpyAsync(w.state, &s0, sizeof(s0), hipMemcpyHostToDevice, st));
   const std::vector<int> tok(R, cfg.start_mel_token);
   IDX_HIP(hipMemcpyAsync(w.cur_tok, tok.data(), R * sizeof(int), hipMemcpyHostToDevice, st));
@@ -507,6 +511,12 @@ int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const
   ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;           // start_mel_token rows
   ga.table[1] = mel_pos; ga.idx[1] = w.finished;          // all zeros -> mel position 0
   if (gather_sum_rows(ga, Rp, st)) return 1;
+  if (k > 0) {      // ... | mel_emb[prefix[j]] + mel_pos[pos0 + j], j < k]
+    PrefixRows pr;
+    pr.x = w.x; pr.S = S; pr.d = d; pr.P_all = P; pr.k_all = k; pr.prefix = prefix; pr.row_div = pfan; pr.pos0 = pos0;
+    pr.mel_emb = mel_emb; pr.mel_pos = mel_pos; pr.V = V;
+    if (prefix_input_rows(pr, Rp, k, st)) return 1;
+  }
   if (share_prefill) {
     // the prefill rows' own left pads in w.kstart while they run (the decode rows' afterwards); the fan-out's first rows and lengths in
     // w.cur_tok, which nobody reads between the gather above and the sampler that rewrites it (2 B <= R entries)
@@ -580,8 +590,12 @@ static int check_sampling(const idxtts_sampling& r) {
 
 int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
                        const idxtts_sampling* sampling, long long* codes, int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph,
-                       hipStream_t user_stream, const long long* forced, int takes, float* logprobs) {
+                       hipStream_t user_stream, const long long* forced, int takes, float* logprobs, const long long* prefix, int k,
+                       int prefix_pos0) {
   IDX_CHECK(inputs_embeds && codes && n_steps_out, "null pointer");
+  IDX_CHECK(k >= 0 && (k == 0 || prefix), "prefix: k >= 0 codes per prompt (k > 0 needs the codes)");
+  IDX_CHECK(k == 0 || prefix_pos0 == 1 || prefix_pos0 == 2, "prefix_pos0: 1 (the reference's layout) or 2 (the uninterrupted run's)");
+  IDX_CHECK(k == 0 || !forced, "teacher forcing together with a prefix is not supported");
   GenScope gen_scope(this);
   IDX_CHECK(!forced || !(sampling && sampling->mode != 0), "teacher forcing is a greedy-mode instrument");
   IDX_CHECK(takes >= 1 && (takes == 1 || !forced), "takes >= 1 (teacher forcing: 1)");
@@ -589,11 +603,21 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   const int prompts = B;      // the prefill's rows; from here on B counts decode rows, row b * takes + j being take j of prompt b
   B *= takes;
   if (sampling && check_sampling(*sampling)) return 1;
-  const int S = P + 1;
+  const int S = P + 1 + k;
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
+  IDX_CHECK((long long)k + max_new + 1 < cfg.mel_pos_len, "prefix + max_new_tokens exceed the mel position table");
   IDX_CHECK(ws && ws_bytes >= workspace_bytes(B, S, max_new), "workspace too small");
   hipStream_t st = nullptr;
   if (call_stream(user_stream, &st)) return 1;
+  std::vector<long long> hp((size_t)prompts * k);      // the given codes: checked here, and counted as seen by the repetition penalty
+  if (k > 0) {
+    IDX_HIP(hipMemcpyAsync(hp.data(), prefix, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+    IDX_HIP(hipStreamSynchronize(st));
+    for (long long c : hp) {
+      IDX_CHECK(c >= 0 && c < cfg.number_mel_codes, "prefix: a code outside the mel code table");
+      IDX_CHECK(c != cfg.stop_mel_token, "prefix contains the stop token: nothing follows a stop token");
+    }
+  }
   Buffers w = carve(ws, B, S, max_new);
   if (sampling && sampling->mode != 0) w.samp = *sampling;
   w.forced = forced; w.forced_ld = max_new;
@@ -624,7 +648,7 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   StepGraph fresh;
   int steps_done = 0;
   if (run_generation(w, inputs_embeds, pad_left_host, prompts, takes, P, max_new, penalty, logits_out, graph, exec, cacheable ? &fresh : nullptr,
-                     w.finished, B, 16, &steps_done, st, true)) return 1;
+                     w.finished, B, 16, &steps_done, st, true, prefix, hp.data(), k, prefix_pos0)) return 1;
   if (fresh.exec) {      // keep it: a free cache slot, or the least recently used idle one
     std::lock_guard<std::mutex> l(graph_mu);
     int slot = -1;
@@ -671,14 +695,14 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
 // the staged last prefill rows and the admission's index arrays.
 GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams,
-                                                 bool scores) const {
+                                                 bool scores, bool prefix) const {
   SessionBuffers sb;
-  sb.w = carve(ws, slots, max_prompt + 1, max_new, session_prefill_rows(slots, max_prompt));
+  const size_t pre = session_prefill_rows(slots, max_prompt, prefix ? max_new : 0);
+  sb.w = carve(ws, slots, max_prompt + 1, max_new, pre);
   Carver c(ws);
   c.off = sb.w.bytes;
   sb.w.slots = c.take<SlotState>(slots);
   sb.x_last = c.take<float>((size_t)slots * cfg.model_dim);
-  const size_t pre = session_prefill_rows(slots, max_prompt);
   sb.ids = c.take<int>(slots);
   sb.plen = c.take<int>(pre);
   sb.klen = c.take<int>(slots);
@@ -702,12 +726,15 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
     b.mel_emb = mel_emb; b.mel_pos = mel_pos; b.d = cfg.model_dim;
   }
   if (scores) sb.w.logprobs = c.take<float>((size_t)slots * max_new);      // (after everything else: flags 0 and 1 keep their layout)
+  sb.pk = sb.poff = nullptr;
+  if (prefix) { sb.pk = c.take<int>(slots); sb.poff = c.take<int>(slots); }
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
 
-size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams, bool scores) const {
-  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams, scores).bytes;
+size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams, bool scores,
+                                         bool prefix) const {
+  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams, scores, prefix).bytes;
 }
 
 GPTModel::Session* GPTModel::find_session(void* ws) {
@@ -717,16 +744,17 @@ GPTModel::Session* GPTModel::find_session(void* ws) {
 }
 
 int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st,
-                           bool sampled, int num_beams, bool scores) {
+                           bool sampled, int num_beams, bool scores, bool prefix) {
   IDX_CHECK(ws, "null workspace");
+  IDX_CHECK(num_beams == 0 || !prefix, "a beam session takes no prefix: the scorer's length penalty and rows would have to count it");
   IDX_CHECK(num_beams == 0 || !scores, "a beam session records no per-code scores: its hypotheses carry the scorer's");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
   IDX_CHECK(num_beams == 0 || (num_beams >= 2 && num_beams <= BEAM_MAX), "2 <= num_beams <= 8");
   IDX_CHECK(num_beams == 0 || slots % num_beams == 0, "slots must be a multiple of num_beams");
   IDX_CHECK(num_beams == 0 || !sampled, "a beam session has no per-slot samplers");
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
-  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams, scores), "workspace too small");
-  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams, scores);
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams, scores, prefix), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams, scores, prefix);
   const Buffers& w = sb.w;
   const int d = cfg.model_dim;
   IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
@@ -757,6 +785,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   s.first_in.assign(slots, 0);
   s.sampled = sampled;
   s.scores = scores;
+  s.prefix = prefix;
   if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
   s.num_beams = num_beams;
   if (num_beams) s.beam.assign(slots / num_beams, SlotBeam{0, 1.0f, 0, 1.0f, 0.0, 0, 0, nullptr});
@@ -774,8 +803,9 @@ int GPTModel::session_release(void* ws) {
 
 int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                             const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S_out, hipStream_t st,
-                            const int* takes, const int** take_row) {
+                            const int* takes, const int** take_row, const int* prefix_lens, const long long* prefix) {
   IDX_CHECK(inputs_embeds && prompt_lens && ids && caps, "null pointer");
+  IDX_CHECK(!prefix_lens || fan == 1, "a beam session takes no prefix");
   IDX_CHECK(!takes || (fan == 1 && take_row), "takes belong to sessions of single rows");
   const int units = s.slots / fan;
   IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
@@ -793,8 +823,12 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
     }
     IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
     for (int t = T; t < T + tb; ++t) IDX_CHECK(caps[t] >= 1 && caps[t] <= s.max_new, "token cap out of range (1 .. max_new)");
+    const int kb = prefix_lens ? prefix_lens[b] : 0;      // (>= 0: session_admit has checked)
+    // a row that holds its cap already has nothing to produce; k < cap <= max_new also keeps P + 1 + k inside the cache and k + 2
+    // inside the position table (session_init: max_new + 1 < mel_pos_len)
+    for (int t = T; t < T + tb; ++t) IDX_CHECK(kb < caps[t], "prefix: k >= cap, the row would have no code left to produce (cap counts prefix + new codes)");
     T += tb;
-    pmax = std::max(pmax, prompt_lens[b]);
+    pmax = std::max(pmax, prompt_lens[b] + kb);
   }
   // One right-padded prefill of the admitted rows: under the causal mask a row sees exactly the keys (and key tiles) it would see alone
   // with no left padding.  The GEMMs are chosen from the session's properties, never from n: with an fp32 cache layer_full runs the
@@ -804,7 +838,9 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   const int S = pmax + 1;
   int rows = n;
   if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3 && !s.invariant) rows = std::max(n, cdiv(256, S));      // (the mode's prefill is exact)
-  const size_t pre = session_prefill_rows(s.slots, s.max_prompt);
+  const size_t pre = session_prefill_rows(s.slots, s.max_prompt, s.prefix ? s.max_new : 0);
+  if (prefix_lens) IDX_CHECK((size_t)rows * S <= pre, "prefixed admission: " + std::to_string(rows) + " prefill rows x " + std::to_string(S) +
+                             " positions exceed the session's prefill area of " + std::to_string(pre) + " positions: admit in smaller groups");
   IDX_CHECK((size_t)rows * S <= pre, "admission prefill exceeds the workspace");
   // takes: the index arrays of the fan-out live behind the prefill rows' lengths in sb.plen (rows <= pre / 2, n + 1 + T <= 2 slots + 1)
   IDX_CHECK(!takes || (size_t)rows + n + 1 + T <= pre, "admission index arrays exceed the workspace");
@@ -816,7 +852,7 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
     if (fan > 1) stage[n + t] = ids[t];
     stage[2 * s.slots + t] = caps[t];
   }
-  for (int b = 0; b < n; ++b) stage[s.slots + b] = prompt_lens[b] + 1;
+  for (int b = 0; b < n; ++b) stage[s.slots + b] = prompt_lens[b] + 1 + (prefix_lens ? prefix_lens[b] : 0);
   for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
   if (takes) {
     int* const first = stage.data() + 3 * s.slots + rows;
@@ -829,10 +865,24 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, T * sizeof(int), hipMemcpyHostToDevice, st));
   IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, (rows + (takes ? n + 1 + T : 0)) * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
+  std::vector<int> pstage;      // prefixes: k of each request | its offset in the packed codes
+  int kmax = 0;
+  if (prefix_lens) {
+    pstage.assign(2 * (size_t)s.slots, 0);
+    for (int b = 0, o = 0; b < n; o += prefix_lens[b], ++b) { pstage[b] = prefix_lens[b]; pstage[s.slots + b] = o; kmax = std::max(kmax, prefix_lens[b]); }
+    IDX_HIP(hipMemcpyAsync(sb.pk, pstage.data(), s.slots * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipMemcpyAsync(sb.poff, pstage.data() + s.slots, s.slots * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  IDX_HIP(hipStreamSynchronize(st));      // the staging vectors go out of scope below
 
   if (session_prefill_input(sb.w.x, inputs_embeds, ld_rows, sb.plen, rows, S, cfg.model_dim, mel_emb, mel_pos, cfg.start_mel_token, st))
     return 1;
+  if (kmax > 0) {      // the given codes behind the start token, at the mel positions the uninterrupted row fed them at (2, 3, ...)
+    PrefixRows pr;
+    pr.x = sb.w.x; pr.S = S; pr.d = cfg.model_dim; pr.P = sb.plen; pr.klen = sb.pk; pr.prefix = prefix; pr.off = sb.poff; pr.pos0 = 2;
+    pr.mel_emb = mel_emb; pr.mel_pos = mel_pos; pr.V = cfg.number_mel_codes;
+    if (prefix_input_rows(pr, n, kmax, st)) return 1;
+  }
   KvScatter sc;
   sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = fan;
   if (takes) { sc.first = sb.plen + rows; *take_row = sb.plen + rows + n + 1; }
@@ -843,10 +893,12 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
 }
 
 int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                            const int* caps, hipStream_t st, const idxtts_sampling* per_row, const int* takes) {
+                            const int* caps, hipStream_t st, const idxtts_sampling* per_row, const int* takes, const int* prefix_lens,
+                            const long long* prefix, const float* prefix_logprobs) {
   Session* sp = find_session(ws);
   IDX_CHECK(sp, "no decode session on this workspace");
   Session& s = *sp;
+  IDX_CHECK(s.num_beams == 0 || !prefix_lens, "a beam session takes no prefix (beams with a prefix are not supported)");
   IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
   IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
   IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots requests");
@@ -861,8 +913,28 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   }
   GenScope gen_scope(this);
   const int d = cfg.model_dim, V = cfg.number_mel_codes;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
   const Buffers& w = sb.w;
+  // prefixes: the codes are read here -- nothing follows a stop token, and a code outside the table is no code.  No request with
+  // codes: the admission of before, kernel for kernel.
+  long long ktot = 0;
+  if (prefix_lens)
+    for (int b = 0; b < n; ++b) {
+      IDX_CHECK(prefix_lens[b] >= 0 && prefix_lens[b] < s.max_new, "prefix: k >= cap, the row would have no code left to produce (0 <= k < max_new_tokens)");
+      ktot += prefix_lens[b];
+    }
+  if (ktot == 0) { prefix_lens = nullptr; prefix = nullptr; prefix_logprobs = nullptr; }
+  if (prefix_lens) {
+    IDX_CHECK(s.prefix, "a prefixed admission needs a session initialised with IDXTTS_SESSION_PREFIX (its prefill area holds prompt + prefix)");
+    IDX_CHECK(prefix, "null prefix");
+    std::vector<long long> hp((size_t)ktot);
+    IDX_HIP(hipMemcpyAsync(hp.data(), prefix, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+    IDX_HIP(hipStreamSynchronize(st));
+    for (long long c : hp) {
+      IDX_CHECK(c >= 0 && c < V, "prefix: a code outside the mel code table");
+      IDX_CHECK(c != cfg.stop_mel_token, "prefix contains the stop token: nothing follows a stop token");
+    }
+  }
   auto params = [&]() -> int {      // the admitted slots' samplers (greedy when per_row is null); the other rows are rewritten unchanged
     if (!s.sampled) return 0;
     if (per_row)
@@ -881,8 +953,15 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   };
   int S = 0;
   const int* take_row = nullptr;      // takes: the prefill row of each take (device)
-  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st, takes, &take_row)) return 1;
-  if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, T, st, take_row)) return 1;
+  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st, takes, &take_row, prefix_lens, prefix))
+    return 1;
+  if (prefix_lens) {
+    PrefixReset pr;
+    pr.slots = w.slots; pr.seen = w.seen; pr.V = V; pr.start_token = cfg.start_mel_token; pr.x_last = sb.x_last; pr.x = w.x; pr.S = S; pr.d = d;
+    pr.slot_ids = sb.ids; pr.P = sb.plen; pr.cap = sb.cap; pr.row = take_row; pr.klen = sb.pk; pr.off = sb.poff; pr.prefix = prefix;
+    pr.prefix_lp = prefix_logprobs; pr.codes = w.codes; pr.codes_ld = s.max_new; pr.logprobs = w.logprobs;
+    if (session_reset_slots_prefix(pr, T, st)) return 1;
+  } else if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, T, st, take_row)) return 1;
   // first token of each admitted row: the head on all `slots` rows (the GEMV use_pl(slots) selects, as a generate() of `slots` rows),
   // sampled for the admitted slots only; the sampler writes their first decode input
   if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
@@ -895,7 +974,10 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
   if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, T, st) : sample_slots_forward(sa, w.slots, sb.ids, T, st))
     return 1;
   for (int b = 0, t = 0; b < n; ++b)
-    for (int j = 0; j < (takes ? takes[b] : 1); ++j, ++t) { s.busy[slot_ids[t]] = 1; s.prompt[slot_ids[t]] = prompt_lens[b]; s.first_in[slot_ids[t]] = 1; }
+    for (int j = 0; j < (takes ? takes[b] : 1); ++j, ++t) {
+      s.busy[slot_ids[t]] = 1; s.prompt[slot_ids[t]] = prompt_lens[b];
+      s.first_in[slot_ids[t]] = !(prefix_lens && prefix_lens[b] > 0);      // behind a prefix x_last is position P + k's, not the prompt's last
+    }
   return 0;
 }
 
@@ -907,7 +989,7 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   GenScope gen_scope(this);
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
   const Buffers& w = sb.w;
   const int geom = step_key();
   if (s.step.exec && s.geom != geom) s.step.drop();
@@ -944,7 +1026,7 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
   IDX_CHECK(codes && n_codes && (logprobs || !scored), "null pointer");
   IDX_CHECK(!scored || s.scores, "_read_scored needs a session initialised with IDXTTS_SESSION_SCORES");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
   if (s.num_beams) return session_read_beam(s, sb, slot, codes, n_codes, st);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
@@ -967,7 +1049,7 @@ int GPTModel::session_read_nbest(void* ws, int slot, int n_best, long long* code
   IDX_CHECK(s.num_beams > 0, "_read_nbest needs a beam session: every other session holds one sequence per slot (_read)");
   IDX_CHECK(codes && lens && scores, "null pointer");
   IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
   return session_read_beam(s, sb, slot, codes, lens, st, n_best, scores);
 }
 
@@ -988,7 +1070,7 @@ int GPTModel::session_end(void* ws, int n, const int* slot_ids, bool evict, hipS
     IDX_CHECK(s.busy[slot], "slot holds no request");
     for (int j = 0; j < fan; ++j) mask |= 1ull << (slot + j);
   }
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
   if (session_end_slots(sb.w.slots, s.slots, mask, !evict, st)) return 1;
   if (evict)
     for (int i = 0; i < s.slots; ++i)
@@ -1017,7 +1099,7 @@ int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, h
   IDX_CHECK(s.busy[slot], "slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
@@ -1053,7 +1135,7 @@ int GPTModel::session_park(void* ws, int slot, void* dst, size_t dst_bytes, size
   if (session_park_header(ws, slot, &h, st)) return 1;
   IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked row (idxtts_gpt_session_park_bytes)");
   Session& s = *find_session(ws);
-  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores), slot);
+  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix), slot);
   a.hdr = h; a.blob = static_cast<char*>(dst);
   if (session_park_slot(a, st)) return 1;
   s.busy[slot] = 0;
@@ -1089,7 +1171,7 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   IDX_CHECK(h.kv_format == s.kv_fmt, "parked row of another KV format");
   IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked row of another GEMM mode");
   IDX_CHECK(h.mode == 0 || s.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
   IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
   IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= 1, "parked row's step scalars are corrupt");
   IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
@@ -1131,7 +1213,7 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
   if (samplers)
     for (int j = 0; j < n; ++j)
       if (check_sampling(samplers[j])) return 1;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores);
+  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
   const Buffers& w = sb.w;
   const int V = cfg.number_mel_codes, d = cfg.model_dim;
   SlotState hs;

@@ -236,17 +236,22 @@ class UnifiedVoice:
         return [emb[i, int(p):] for i, p in enumerate(pads)]
 
     def decode_session(self, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0, do_sample: bool = False,
-                       num_beams: int = 1, use_graph: bool = True, sampled: bool = False, scores: bool = False) -> "DecodeSession":
+                       num_beams: int = 1, use_graph: bool = True, sampled: bool = False, scores: bool = False,
+                       prefix: bool = False) -> "DecodeSession":
         """Continuous batching: `slots` decode rows, one KV region each, that requests enter and leave between steps
         (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt.
         sampled=True: every request samples with its own parameters and draws (DecodeSession.admit(..., sampling=...)).
-        scores=True: every code's log-probability is recorded (take(slot, scores=True); include/idxtts.h "Scores")."""
+        scores=True: every code's log-probability is recorded (take(slot, scores=True); include/idxtts.h "Scores").
+        prefix=True: rows may be admitted behind given codes (DecodeSession.admit(..., prefix=...)); the session's prefill area then
+        holds at least one row of max_prompt + 1 + max_new positions."""
         if do_sample:
             raise ValueError("decode sessions sample per request, not session-wide: do_sample=True is not supported; the session is "
                              "greedy unless created with sampled=True and given per-request parameters (admit(..., sampling=...))")
         if num_beams != 1:
+            if prefix:
+                raise ValueError("beams do not continue from given codes: prefix=True is for greedy and sampled sessions")
             raise ValueError("decode sessions are greedy or sampled per request: beam search runs in beam_session() (or generate_beam())")
-        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled, scores=scores)
+        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled, scores=scores, prefix=prefix)
 
     def beam_session(self, slots: int, num_beams: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
                      use_graph: bool = True, scores: bool = False) -> "BeamDecodeSession":
@@ -265,9 +270,18 @@ class UnifiedVoice:
                  repetition_penalty: float = 10.0, return_logits: bool = False, use_graph: bool = True,
                  do_sample: bool = False, sampler: str = "hf", exp_noise: Optional[torch.Tensor] = None,
                  generator: Optional[torch.Generator] = None, forced_codes: Optional[torch.Tensor] = None,
-                 seed: Optional[int] = None, num_return_sequences: int = 1, return_logprobs: bool = False) -> torch.Tensor:
+                 seed: Optional[int] = None, num_return_sequences: int = 1, return_logprobs: bool = False,
+                 prefix_layout: str = "hf") -> torch.Tensor:
         """The accel-engine plugin contract (accel_engine.py:378-645): returns LongTensor [B, P+1+generated]
         (prompt ids followed by the generated codes, padded with the stop token).
+
+        input_ids may be [B, P+1+k]: k mel codes behind the start token, the reference's torch.cat([input_ids, input_tokens], 1)
+        (model_v2.py:853; attention_mask may cover the extra columns).  Generation continues behind them and the result is
+        [B, P+1+k+generated] = [input_ids | new codes], as HF returns it; max_new_tokens, exp_noise, logits and logprobs count the new
+        codes.  The repetition penalty sees the given codes.  prefix_layout="hf" puts given code j at mel position j + 1, what the
+        reference's first forward embeds (model_v2.py:163-165); "resume" puts it at j + 2, where an uninterrupted run fed it, so that
+        the call goes on as that run would have (include/idxtts.h "Continuing from given codes").  A prefix that holds the stop token,
+        or that leaves no room in the mel position table, raises; so does forced_codes together with a prefix.
 
         num_return_sequences=n > 1: n takes of every prompt, rows expanded as HF's _expand_inputs_for_generation does
         (repeat_interleave: row b * n + j is take j of prompt b); returns [B * n, P+1+generated].  exp_noise is then
@@ -303,8 +317,24 @@ class UnifiedVoice:
             if forced_codes is not None:
                 raise ValueError("forced_codes is a single-sequence instrument (num_return_sequences must be 1)")
         B, P, d = emb.shape
-        if input_ids.shape != (B, P + 1):
-            raise ValueError("input_ids must be [B, P+1] (fake prefix + start_mel_token)")
+        if input_ids.dim() != 2 or input_ids.shape[0] != B or input_ids.shape[1] < P + 1:
+            raise ValueError("input_ids must be [B, P+1] (fake prefix + start_mel_token), or [B, P+1+k] with k given mel codes behind it")
+        k = int(input_ids.shape[1]) - (P + 1)
+        if prefix_layout not in ("hf", "resume"):
+            raise ValueError("prefix_layout must be 'hf' or 'resume'")
+        prefix = None
+        if k > 0:
+            if forced_codes is not None:
+                raise ValueError("forced_codes together with given codes in input_ids is not supported")
+            if attention_mask is not None and attention_mask.shape[1] not in (P + 1, P + 1 + k):
+                raise ValueError("attention_mask must cover [B, P+1] or [B, P+1+k]")
+            if int((input_ids[:, P + 1:] == self.cfg.stop_mel_token).sum()) > 0:
+                raise ValueError("the given codes contain the stop token: nothing follows a stop token")
+            if int(input_ids[:, P + 1:].min()) < 0 or int(input_ids[:, P + 1:].max()) >= self.cfg.number_mel_codes:
+                raise ValueError("the given codes must be mel codes (0 .. number_mel_codes - 1)")
+            if k + int(max_new_tokens) + 1 >= self.cfg.mel_pos_len:
+                raise ValueError("given codes + max_new_tokens exceed the mel position table")
+            prefix = input_ids[:, P + 1:].to(self.device, torch.long).contiguous()      # one row per prompt: its takes share it
         pad_left = np.zeros(B, np.int32)      # one entry per prompt: the prefill runs on the B prompts, the takes share it
         if attention_mask is not None:
             am = attention_mask.detach().cpu().numpy()
@@ -316,7 +346,7 @@ class UnifiedVoice:
         V = self.cfg.number_mel_codes
         logits = torch.zeros(max_new_tokens, B, V, device=self.device) if return_logits else None
         logprobs = torch.zeros(B, max_new_tokens, device=self.device) if return_logprobs else None
-        ws = self._workspace(B, P + 1, max_new_tokens)
+        ws = self._workspace(B, P + 1 + k, max_new_tokens)
         n = ctypes.c_int(0)
         if do_sample and forced_codes is not None:
             raise ValueError("forced_codes is a greedy-mode instrument")
@@ -332,7 +362,13 @@ class UnifiedVoice:
             fc = forced_codes.to(self.device, torch.long).contiguous()
             if tuple(fc.shape) != (B, max_new_tokens):
                 raise ValueError(f"forced_codes must be {(B, max_new_tokens)}")
-        if return_logprobs and forced_codes is not None:
+        if k > 0:
+            _lib.check(_lib.load().idxtts_gpt_generate_prefix(
+                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
+                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(prefix), k,
+                1 if prefix_layout == "hf" else 2, _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws),
+                ws.numel(), int(use_graph), _lib.current_stream()))
+        elif return_logprobs and forced_codes is not None:
             _lib.check(_lib.load().idxtts_gpt_generate_forced_scored(
                 self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc),
                 _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
@@ -395,6 +431,9 @@ class UnifiedVoice:
         supplies them, or `generator` draws them on the CPU in that order; with neither the kernels generate them from `seed` (see _noise)."""
         emb = tts_embeddings.to(self.device, torch.float32).contiguous()
         B, P, d = emb.shape
+        if input_ids.dim() == 2 and input_ids.shape[0] == B and input_ids.shape[1] > P + 1:
+            raise NotImplementedError("beam search does not continue from given codes (input_ids wider than [B, P+1]): HF's length "
+                                      "penalty counts the prefix and the scorer's rows would have to hold it; use generate()")
         if input_ids.shape != (B, P + 1):
             raise ValueError("input_ids must be [B, P+1] (fake prefix + start_mel_token)")
         if not (2 <= int(num_beams) <= 8) or B * int(num_beams) > 64:
@@ -440,15 +479,27 @@ class UnifiedVoice:
         819-828) or -- hoisted out of the caller's segment loop -- the ready conditioning latent [B, 32, d] together with `emo_vec`.
         Decoding modes = HF generate's: greedy (do_sample=False, num_beams=1), multinomial sampling with the warpers
         (do_sample=True, num_beams=1; extra kwargs `exp_noise` / `generator` / `sampler`, see generate()), beam search and
-        beam-sample (num_beams > 1: generate_beam()).  num_return_sequences=n: codes [B * n, L], row b * n + j take j of utterance b --
+        beam-sample (num_beams > 1: generate_beam()).  input_tokens ((s,) or (1, s) mel codes, one utterance, num_return_sequences=1):
+        generation continues behind them in the reference's position layout (generate(prefix_layout="hf")); the returned codes are the
+        new ones, as the reference truncates at trunc_index.  num_return_sequences=n: codes [B * n, L], row b * n + j take j of utterance b --
         n sampled takes (generate()), or the n best beam hypotheses (n <= num_beams), as HF's generate returns them.
         return_logprobs (num_beams = 1): the log-probability of every code, [rows, n] fp32 (generate(return_logprobs=True)), as one more
         value at the end of the returned tuple."""
-        if input_tokens is not None or typical_sampling or use_speed:
-            raise NotImplementedError("input_tokens / typical_sampling / use_speed are not used by IndexTTS2.infer and not implemented")
+        if typical_sampling or use_speed:
+            raise NotImplementedError("typical_sampling / use_speed are not used by IndexTTS2.infer and not implemented")
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError("num_return_sequences must be >= 1")
+        if input_tokens is not None:
+            if nrs > 1:
+                raise NotImplementedError("input_tokens with num_return_sequences > 1 is not implemented: the reference repeats the rows "
+                                          "itself (model_v2.py:847-852) and HF's generate then expands them a second time")
+            input_tokens = torch.as_tensor(input_tokens)
+            if input_tokens.ndim == 1:
+                input_tokens = input_tokens.unsqueeze(0)
+            # the reference's asserts (model_v2.py:843-846) at num_return_sequences = 1: both batches must divide 1
+            assert nrs % input_tokens.shape[0] == 0, "The num_return_sequences must be divisible by the batch number of input_tokens"
+            assert nrs % text_inputs.shape[0] == 0, "The num_return_sequences must be divisible by the batch number of text_inputs"
         sc = speech_condition if speech_condition.ndim == 3 else speech_condition.unsqueeze(0)
         if sc.shape[-1] == self.cfg.cond_module.input_size and sc.shape[-1] != self.cfg.model_dim:      # raw features
             if emo_speech_condition is None:
@@ -478,6 +529,12 @@ class UnifiedVoice:
         ev = emo_vec.expand(B, -1) if emo_vec.shape[0] == 1 else emo_vec
         conds = self.conds_latent(lat, ev)
         input_ids, inputs_embeds, attention_mask = self.prepare_gpt_inputs(conds, text_inputs)
+        if input_tokens is not None:      # model_v2.py:853-855: the codes behind input_ids, the mask extended with ones
+            if num_beams > 1:
+                raise NotImplementedError("input_tokens with num_beams > 1 is not implemented (beams do not continue from given codes)")
+            tok = input_tokens.to(input_ids.device, torch.long)
+            input_ids = torch.cat([input_ids, tok], dim=1)
+            attention_mask = torch.nn.functional.pad(attention_mask, (0, tok.shape[1]), value=1)
         trunc_index = input_ids.shape[1]
         max_new = (self.cfg.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
         if num_beams > 1:
@@ -818,10 +875,11 @@ class DecodeSession(_Session):
     and obey every determinism rule above, bit for bit.  The codes are those of a session without scores."""
 
     def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
-                 use_graph: bool = True, sampled: bool = False, scores: bool = False):
-        self.sampled, self.scores = bool(sampled), bool(scores)
+                 use_graph: bool = True, sampled: bool = False, scores: bool = False, prefix: bool = False):
+        self.sampled, self.scores, self.prefix = bool(sampled), bool(scores), bool(prefix)
         lib = _lib.load()
-        flags = (_lib.SESSION_SAMPLED if self.sampled else 0) | (_lib.SESSION_SCORES if self.scores else 0)
+        flags = ((_lib.SESSION_SAMPLED if self.sampled else 0) | (_lib.SESSION_SCORES if self.scores else 0) |
+                 (_lib.SESSION_PREFIX if self.prefix else 0))
         need = int(lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, int(slots), int(max_prompt), int(max_new), flags))
         if need == 0:
             raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
@@ -880,16 +938,26 @@ class DecodeSession(_Session):
             noises.append(noise)
         return arr, noises
 
-    def admit(self, inputs_embeds_rows, max_new_each, sampling=None, takes=None, slots=None):
+    def admit(self, inputs_embeds_rows, max_new_each, sampling=None, takes=None, slots=None, prefix=None, prefix_logprobs=None):
         """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per row (or one int).
         sampling (sampled sessions): None = every row greedy, else one dict per row or one for every row (see the class).
         takes (an int for every row, or one per row): that many takes of each request -- its prefill runs once, its keys and values go
         to all of its takes' slots, and every take is an ordinary row from then on.  The result is then a list of slot lists, one per
         request; max_new_each and sampling may be given per request (each take of it gets them; a seeded entry would make the takes
         equal, so give seeds per take) or per take, as a list of lists.  Take j's codes equal those of the same prompt admitted alone
-        with its sampler.  slots: the free slots to use, in order (default: the first free ones)."""
+        with its sampler.  slots: the free slots to use, in order (default: the first free ones).
+        prefix (a session created with prefix=True): one 1-D sequence of mel codes, or None, per request -- the row starts behind
+        them, as the row that produced them would have gone on (position layout "resume": code j at mel position j + 2).  The cap counts
+        prefix + new codes (k < cap), the row's codes, take() and the draws (exp_noise [cap, V], rows below k never read; a seed's
+        counter) are indexed by the absolute step, and a request's takes share its prefix and one prefill.  prefix_logprobs: one fp32
+        sequence of the same length, or None (= zeros), per request: what take(scores=True) returns for the prefix codes.  Rows with
+        and without a prefix may share a call; an admission too large for the prefill area is split into groups that fit.  The row's
+        codes equal row 0 of generate(input_ids=[fake | prefix], prefix_layout="resume") on `slots` copies of the prompt, with
+        exp_noise rows offset by k.  A prefix that holds the stop token, or with k >= cap, raises and nothing changes."""
         if len(inputs_embeds_rows) == 0:
             return []
+        if prefix is not None or prefix_logprobs is not None:
+            return self._admit_prefix(inputs_embeds_rows, max_new_each, sampling, takes, slots, prefix, prefix_logprobs)
         if takes is not None:
             return self._admit_takes(inputs_embeds_rows, max_new_each, sampling, takes, slots)
         free = self.free_slots
@@ -981,6 +1049,102 @@ class DecodeSession(_Session):
             out.append(ids[o:o + t])
             o += t
         return out
+
+    def _prefill_area(self) -> int:
+        """Positions of the admission's prefill area (gpt.h session_prefill_rows)."""
+        area = self.slots * (self.max_prompt + 1) + 256
+        return max(area, self.max_prompt + 1 + self.max_new + 256) if self.prefix else area
+
+    @staticmethod
+    def _prefix_groups(plen: list, klen: list, area: int) -> list:
+        """Consecutive requests grouped so that each group's right-padded prefill -- rows x the longest P + 1 + k of the group -- fits
+        an area of `area` positions; rows are counted as the bf16 cache's padded prefill counts them (at least ceil(256 / S)), which
+        is never fewer than the native call takes.  One request always fits (the area holds max_prompt + 1 + max_new + 256)."""
+        groups, cur, smax = [], [], 0
+        for b in range(len(plen)):
+            sb = max(smax, plen[b] + 1 + klen[b])
+            if cur and max(len(cur) + 1, -(-256 // sb)) * sb > area:
+                groups.append(cur)
+                cur, sb = [], plen[b] + 1 + klen[b]
+            cur.append(b)
+            smax = sb
+        if cur:
+            groups.append(cur)
+        return groups
+
+    def _admit_prefix(self, inputs_embeds_rows, max_new_each, sampling, takes, slots, prefix, prefix_logprobs) -> list:
+        n = len(inputs_embeds_rows)
+        if not self.prefix:
+            raise ValueError("prefix= needs a session created with prefix=True (IDXTTS_SESSION_PREFIX sizes the prefill area for it)")
+        if prefix is None:
+            raise ValueError("prefix_logprobs without prefix")
+        pf = list(prefix)
+        lp = [None] * n if prefix_logprobs is None else list(prefix_logprobs)
+        if len(pf) != n or len(lp) != n:
+            raise ValueError("prefix / prefix_logprobs: one entry (a 1-D sequence or None) per request")
+        nested = takes is not None
+        tk = [1] * n if takes is None else [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
+        if len(tk) != n or any(t < 1 for t in tk):
+            raise ValueError("takes: one count >= 1 per row (or one int for every row)")
+        if sampling is not None and not self.sampled:
+            raise ValueError("sampling= needs a session created with sampled=True")
+        if prefix_logprobs is not None and not self.scores:
+            raise ValueError("prefix_logprobs= needs a session created with scores=True")
+        T = sum(tk)
+        free = self.free_slots
+        if T > len(free) and slots is None:
+            raise RuntimeError(f"{T} rows but {len(free)} free slots")
+        ids = self._pick(slots, T, free)
+        caps_t = [int(c) for c in self._per_take(max_new_each if not isinstance(max_new_each, np.integer) else int(max_new_each), tk,
+                                                 "max_new_each")]
+        rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
+        if any(not 1 <= c <= self.max_new for c in caps_t):
+            raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        V, stop = self.gpt.cfg.number_mel_codes, self.gpt.cfg.stop_mel_token
+        codes, lps, o = [], [], 0
+        for b in range(n):
+            c = torch.zeros(0, dtype=torch.long) if pf[b] is None else torch.as_tensor(pf[b]).detach().to("cpu", torch.long)
+            if c.dim() != 1:
+                raise ValueError("prefix: a 1-D sequence of mel codes (or None) per request")
+            k = int(c.numel())
+            if k and (int(c.min()) < 0 or int(c.max()) >= V):
+                raise ValueError(f"prefix: mel codes are 0 .. {V - 1}")
+            if k and bool((c == stop).any()):
+                raise ValueError("prefix contains the stop token: nothing follows a stop token")
+            if any(k >= cap for cap in caps_t[o:o + tk[b]]):
+                raise ValueError(f"prefix of {k} codes but a cap of {min(caps_t[o:o + tk[b]])}: the cap counts prefix + new codes (k < cap)")
+            l = torch.zeros(k) if lp[b] is None else torch.as_tensor(lp[b]).detach().to("cpu", torch.float32)
+            if tuple(l.shape) != (k,):
+                raise ValueError("prefix_logprobs: one value per prefix code")
+            codes.append(c)
+            lps.append(l)
+            o += tk[b]
+        groups = self._prefix_groups(plen, [int(c.numel()) for c in codes], self._prefill_area())
+        first = [0]
+        for t in tk:
+            first.append(first[-1] + t)
+        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
+        with torch.cuda.stream(self.stream):
+            samplers, noises = (self._samplers(self._per_take(sampling, tk, "sampling"), caps_t) if sampling is not None
+                                else (None, [None] * T))
+            for g in groups:
+                t0, t1 = first[g[0]], first[g[-1] + 1]
+                emb, pm = self._embed_rows([rows[b] for b in g], [plen[b] for b in g])
+                pk = torch.cat([codes[b] for b in g]).to(self.gpt.device)
+                pl = torch.cat([lps[b] for b in g]).to(self.gpt.device) if self.scores else None
+                h_p, h_t, h_ids, h_caps, h_k = (np.ascontiguousarray(a, dtype=np.int32) for a in (
+                    [plen[b] for b in g], [tk[b] for b in g], ids[t0:t1], caps_t[t0:t1], [int(codes[b].numel()) for b in g]))
+                sp = c_void_p(ctypes.addressof(samplers) + t0 * ctypes.sizeof(_lib.SamplingC)) if samplers is not None else c_void_p(0)
+                _lib.check(self._lib.idxtts_gpt_session_admit_prefix(
+                    self.gpt._h, len(g), _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_t.ctypes.data_as(c_void_p),
+                    h_ids.ctypes.data_as(c_void_p), h_caps.ctypes.data_as(c_void_p), sp, h_k.ctypes.data_as(c_void_p),
+                    _lib.ptr(pk) if pk.numel() else c_void_p(0), _lib.ptr(pl) if pl is not None and pl.numel() else c_void_p(0),
+                    _lib.ptr(self._ws), self._sp()))
+                for i, nz in zip(ids[t0:t1], noises[t0:t1]):
+                    self._busy[i] = True
+                    if nz is not None:
+                        self._noise[i] = nz
+        return [ids[first[b]:first[b + 1]] for b in range(n)] if nested else ids
 
     def fork(self, slot: int, samplers=None, at=None, caps=None, n=None, slots=None) -> list:
         """Further takes of the request in `slot`, branching where it stood after `at` codes (default: where it stands now): one per
@@ -1175,9 +1339,13 @@ class BeamDecodeSession(_Session):
             noises.append(noise)
         return arr, noises
 
-    def admit(self, inputs_embeds_rows, max_new_each, beam=None) -> list:
+    def admit(self, inputs_embeds_rows, max_new_each, beam=None, prefix=None, prefix_logprobs=None) -> list:
         """inputs_embeds_rows: [P_b, d] prompt embeddings (UnifiedVoice.prompt_rows); max_new_each: a cap per request (or one int);
-        beam: the requests' parameters (see the class).  Returns their group ids.  A refused call takes no group."""
+        beam: the requests' parameters (see the class).  Returns their group ids.  A refused call takes no group.
+        prefix / prefix_logprobs: refused -- beams do not continue from given codes (DecodeSession.admit does)."""
+        if prefix is not None or prefix_logprobs is not None:
+            raise NotImplementedError("a beam session takes no prefix: HF's length penalty counts the prefix and the scorer's rows would "
+                                      "have to hold it; continue from given codes in a DecodeSession (decode_session(prefix=True))")
         if len(inputs_embeds_rows) == 0:
             return []
         free = self.free_groups

@@ -291,7 +291,7 @@ class BatchPipeline:
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               takes: int = 1, keep: Optional[int] = None) -> concurrent.futures.Future:
+               takes: int = 1, keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None) -> concurrent.futures.Future:
         """Queue one batch; returns a Future of the list of waveforms `synthesize_batch` would return.  Inputs produced on the
         caller's current stream are safe to use (an event recorded here is waited for on the lane's stream), and the waveforms
         are safe to read on that stream (they are tied to it with record_stream before the Future resolves).
@@ -305,7 +305,13 @@ class BatchPipeline:
         (IndexTTS2.ranked_takes: generate(num_return_sequences=n, return_logprobs=True)), and only the best k of every utterance go
         through the latent pass, s2mel and the vocoder: result[i][j], j < k, best first, with their own noise rows / seeds (entry
         i * n + take).  fut.ranking[i] -- every take of utterance i as (take_index, score, stopped, n_codes), best first
-        (rank_request) -- is set before the Future resolves.  A request with keep is never merged into another's decode."""
+        (rank_request) -- is set before the Future resolves.  A request with keep is never merged into another's decode.
+        prefix_codes / prefix_logprobs: refused here.  A batch's one-shot decode takes one rectangular prefix, the same k for every
+        row, and merges requests by shape; continuing from given codes per utterance is ContinuousPipeline(prefix=True)'s job (or
+        UnifiedVoice.generate(input_ids=[fake | codes], prefix_layout="resume") directly)."""
+        if prefix_codes is not None or prefix_logprobs is not None:
+            raise NotImplementedError("BatchPipeline does not continue from given codes: its one-shot decode takes one rectangular prefix "
+                                      "per batch; use ContinuousPipeline(prefix=True).submit(prefix_codes=...)")
         takes = int(takes)
         if takes < 1 or (takes > 1 and not (sampling and sampling.get("do_sample"))):
             raise ValueError("takes must be >= 1, and takes > 1 needs a sampled request: every take of a greedy one would be the same")
@@ -514,7 +520,7 @@ class BatchPipeline:
 class _Job:
     """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest", "keep", "lps")
+                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest", "keep", "lps", "prefix", "prefix_lps")
 
 
 def _expand_cond(cond, n: int):
@@ -676,7 +682,7 @@ class ContinuousPipeline:
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
                  session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
                  acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device", preempt_groups: bool = False,
-                 scores: bool = False):
+                 scores: bool = False, prefix: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
@@ -709,13 +715,17 @@ class ContinuousPipeline:
         if self.preempt_groups and self.num_beams == 1:
             raise ValueError("preempt_groups=True needs num_beams > 1: a greedy or sampled pipeline parks rows (preempt=True)")
         self._preempts = self.preempt or self.preempt_groups      # rows or groups: the scheduling is the same
+        self.prefix = bool(prefix)
+        if self.prefix and self.num_beams > 1:
+            raise ValueError("prefix=True needs num_beams == 1: beams do not continue from given codes")
         self._admitted = 0                      # admission stamps (which row of a priority was admitted last)
         if self.num_beams > 1:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
                                                                                    repetition_penalty=self.repetition_penalty))
         else:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(
-                slots, mp, mn, repetition_penalty=self.repetition_penalty, sampled=self.allow_sampling, **({"scores": True} if self.scores else {})))
+                slots, mp, mn, repetition_penalty=self.repetition_penalty, sampled=self.allow_sampling, **({"scores": True} if self.scores else {}),
+                **({"prefix": True} if self.prefix else {})))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index, ParkedRow or None) waiting for a slot, most urgent first
@@ -742,7 +752,7 @@ class ContinuousPipeline:
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
                deadline_s: Optional[float] = None, priority: int = 0, takes: int = 1,
-               keep: Optional[int] = None) -> concurrent.futures.Future:
+               keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None) -> concurrent.futures.Future:
         """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
@@ -762,7 +772,16 @@ class ContinuousPipeline:
         result[i][j], j < k, best first; before that, fut.ranking[i] is set: all n takes of utterance i as (take_index, score, stopped,
         n_codes), best first.  Noise rows and seeds follow the kept takes (take j keeps entry i * n + j).  Every take still decodes to
         its end and is an ordinary row for cancellation, deadlines, priorities, park and resume; a cancelled request is never ranked.
-        keep=None: every take is synthesised, as ever.  keep without scores=True, or on a beam pipeline, raises ValueError here."""
+        keep=None: every take is synthesised, as ever.  keep without scores=True, or on a beam pipeline, raises ValueError here.
+        prefix_codes (a pipeline built with prefix=True; greedy or sampled): one 1-D sequence of mel codes, or None, per utterance --
+        the utterance is decoded on from behind them as the row that produced them would have gone on (DecodeSession.admit(prefix=)).
+        With takes=n the n takes of an utterance share its prefix and one prefill; max_mel_tokens caps prefix + continuation; the codes
+        that go to gpt_stage(codes=) and the acoustic job are prefix + continuation.  prefix_logprobs (scores=True): one fp32 sequence
+        or None per utterance; with keep= the ranking uses the recorded log-probabilities, which for the prefix codes are these values,
+        or 0 where none are given -- takes of one utterance share them, so their order is decided by the continuations.  Refused here
+        (ValueError): a beam pipeline, a pipeline built without prefix=True, a prefix that holds the stop token or a code outside the
+        table, or one that is not shorter than max_mel_tokens."""
+        pfx = self._check_prefix(text_tokens, prefix_codes, prefix_logprobs, int(max_mel_tokens))
         if deadline_s is not None:
             deadline_s = float(deadline_s)
         priority, takes = int(priority), int(takes)
@@ -785,10 +804,53 @@ class ContinuousPipeline:
             raise ValueError("takes > 1 needs a sampled request: every take of a greedy one would be the same")
         return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
                             (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority, takes,
-                            keep)
+                            keep, pfx)
+
+    def _check_prefix(self, text_tokens, prefix_codes, prefix_logprobs, max_mel_tokens: int):
+        """submit(prefix_codes=, prefix_logprobs=) -> None, or (codes, logprobs): one CPU tensor or None per utterance."""
+        if prefix_codes is None and prefix_logprobs is None:
+            return None
+        if self.num_beams > 1:
+            raise ValueError("prefix_codes on a beam pipeline: beams do not continue from given codes")
+        if not self.prefix:
+            raise ValueError("prefix_codes needs a pipeline built with prefix=True (its sessions size their prefill area for it)")
+        if prefix_codes is None:
+            raise ValueError("prefix_logprobs without prefix_codes")
+        if prefix_logprobs is not None and not self.scores:
+            raise ValueError("prefix_logprobs needs a pipeline built with scores=True")
+        B = int(torch.as_tensor(text_tokens).shape[0])
+        codes = list(prefix_codes)
+        lps = [None] * B if prefix_logprobs is None else list(prefix_logprobs)
+        if len(codes) != B or len(lps) != B:
+            raise ValueError("prefix_codes / prefix_logprobs: one entry (a 1-D sequence or None) per utterance")
+        g = self.tts.cfg.gpt
+        out_c, out_l = [], []
+        for c, l in zip(codes, lps):
+            if c is None:
+                if l is not None:
+                    raise ValueError("prefix_logprobs for an utterance without prefix_codes")
+                out_c.append(None)
+                out_l.append(None)
+                continue
+            c = torch.as_tensor(c).detach().to("cpu", torch.long)
+            if c.dim() != 1:
+                raise ValueError("prefix_codes: a 1-D sequence of mel codes (or None) per utterance")
+            if c.numel() and (int(c.min()) < 0 or int(c.max()) >= g.number_mel_codes):
+                raise ValueError(f"prefix_codes: mel codes are 0 .. {g.number_mel_codes - 1}")
+            if bool((c == g.stop_mel_token).any()):
+                raise ValueError("prefix_codes contain the stop token: nothing follows a stop token")
+            if int(c.numel()) >= max_mel_tokens:
+                raise ValueError("prefix_codes must be shorter than max_mel_tokens, which caps prefix + continuation")
+            if l is not None:
+                l = torch.as_tensor(l).detach().to("cpu", torch.float32)
+                if tuple(l.shape) != tuple(c.shape):
+                    raise ValueError("prefix_logprobs: one value per prefix code")
+            out_c.append(c if c.numel() else None)
+            out_l.append(l if c.numel() else None)
+        return (out_c, out_l) if any(c is not None for c in out_c) else None
 
     def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None,
-                priority=0, takes=1, keep=None):
+                priority=0, takes=1, keep=None, pfx=None):
         if float(repetition_penalty) != self.repetition_penalty:
             raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
         if not 1 <= int(max_mel_tokens) <= self.max_new:
@@ -801,6 +863,9 @@ class ContinuousPipeline:
         beam = self.num_beams > 1
         j.takes, j.nbest = takes, takes if beam else 1
         j.keep, j.lps = keep, None
+        # prefixes: one entry per row (the takes of an utterance share theirs)
+        j.prefix = None if pfx is None else [pfx[0][r // takes] for r in range(units * takes)]
+        j.prefix_lps = None if pfx is None else [pfx[1][r // takes] for r in range(units * takes)]
         if takes > 1:
             j.text = j.text.repeat_interleave(takes, 0)
         B = units * takes
@@ -918,7 +983,7 @@ class ContinuousPipeline:
         for j, i, parked in take:
             if parked is None:
                 by_job.setdefault(id(j), (j, []))[1].append(i)
-        rows, caps, owners, samplers, counts = [], [], [], [], []
+        rows, caps, owners, samplers, counts, pfx, pfx_lp = [], [], [], [], [], [], []
         for j, idx in by_job.values():
             # the takes of one utterance taken in this poll are one request with that many takes: one prompt, one prefill
             share = j.takes if self.num_beams == 1 else 1
@@ -935,13 +1000,20 @@ class ContinuousPipeline:
             rows.extend(rs)
             for p in parts.values():
                 counts.append(len(p))
+                pfx.append(None if j.prefix is None else j.prefix[p[0]])
+                pfx_lp.append(None if j.prefix is None else j.prefix_lps[p[0]])
                 caps.append([j.max_mel_tokens] * len(p))
                 owners.extend((j, i) for i in p)
                 if j.sampling is not None:
                     samplers.append([j.sampling[i] for i in p])
         if rows:
             try:
-                if max(counts) > 1:             # (sampled pipelines only)
+                if any(c is not None for c in pfx):      # some utterance continues from given codes: its takes share the prefix
+                    kw = {"sampling": samplers} if self.allow_sampling else {}
+                    if self.scores and any(l is not None for l in pfx_lp):
+                        kw["prefix_logprobs"] = pfx_lp
+                    got = [s for g in sess.admit(rows, caps, takes=counts, prefix=pfx, **kw) for s in g]
+                elif max(counts) > 1:           # (sampled pipelines only)
                     got = [s for g in sess.admit(rows, caps, sampling=samplers, takes=counts) for s in g]
                 else:
                     caps, samplers = [c[0] for c in caps], [e[0] for e in samplers]
