@@ -401,8 +401,8 @@ int idxtts_gpt_generate(idxtts_ctx* ctx, const float* inputs_embeds, const int* 
                         size_t workspace_bytes, int use_graph, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, nullptr, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream));
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), GPTModel::GenerateCall{});
   API_END
 }
 
@@ -412,8 +412,10 @@ int idxtts_gpt_generate_forced(idxtts_ctx* ctx, const float* inputs_embeds, cons
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(forced_codes, "null forced_codes");
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, nullptr, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, 0, static_cast<hipStream_t>(stream), forced_codes);
+  GPTModel::GenerateCall call;
+  call.forced = forced_codes;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, 0, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -423,8 +425,10 @@ int idxtts_gpt_generate_sampled(idxtts_ctx* ctx, const float* inputs_embeds, con
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(sampling, "null sampling configuration");
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream));
+  GPTModel::GenerateCall call;
+  call.sampling = sampling;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -433,8 +437,10 @@ int idxtts_gpt_generate_takes(idxtts_ctx* ctx, const float* inputs_embeds, const
                               void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes);
+  GPTModel::GenerateCall call;
+  call.sampling = sampling; call.takes = takes;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -444,8 +450,10 @@ int idxtts_gpt_generate_scored(idxtts_ctx* ctx, const float* inputs_embeds, cons
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(logprobs, "null logprobs");
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes, logprobs);
+  GPTModel::GenerateCall call;
+  call.sampling = sampling; call.takes = takes; call.logprobs = logprobs;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -455,8 +463,11 @@ int idxtts_gpt_generate_prefix(idxtts_ctx* ctx, const float* inputs_embeds, cons
                                int use_graph, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, sampling, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), nullptr, takes, logprobs, prefix, k, prefix_pos0);
+  GPTModel::GenerateCall call;
+  call.sampling = sampling; call.takes = takes; call.logprobs = logprobs;
+  call.prefix.codes = prefix; call.prefix.k = k; call.prefix.pos0 = prefix_pos0;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, use_graph, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -466,8 +477,10 @@ int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embed
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(forced_codes && logprobs, "null forced_codes or logprobs");
-  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, nullptr, codes, n_steps, logits_out, workspace,
-                     workspace_bytes, 0, static_cast<hipStream_t>(stream), forced_codes, 1, logprobs);
+  GPTModel::GenerateCall call;
+  call.forced = forced_codes; call.logprobs = logprobs;
+  return m->generate(inputs_embeds, pad_left, B, P, max_new_tokens, repetition_penalty, codes, n_steps, logits_out, workspace,
+                     workspace_bytes, 0, static_cast<hipStream_t>(stream), call);
   API_END
 }
 
@@ -516,26 +529,28 @@ int idxtts_beam_finalize_host(int num_beams, double length_penalty, int hyp_n, c
   API_END
 }
 
+// the shape a session entry point describes: its sizes, its IDXTTS_SESSION_* flags (0: none), its num_beams (0: no beam session)
+static GPTModel::SessionShape session_shape(int slots, int max_prompt, int max_new_tokens, int flags, int num_beams) {
+  GPTModel::SessionShape sh;
+  sh.slots = slots; sh.max_prompt = max_prompt; sh.max_new = max_new_tokens; sh.num_beams = num_beams;
+  sh.sampled = flags & IDXTTS_SESSION_SAMPLED; sh.scores = flags & IDXTTS_SESSION_SCORES; sh.prefix = flags & IDXTTS_SESSION_PREFIX;
+  return sh;
+}
+
 size_t idxtts_gpt_session_workspace_bytes(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens) {
-  if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
-  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
-  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens) : 0;
+  return idxtts_gpt_session_workspace_bytes_ex(ctx, slots, max_prompt, max_new_tokens, 0);
 }
 
 int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, void* workspace,
                             size_t workspace_bytes, void* stream) {
-  API_BEGIN
-  GPT_MODEL(ctx);
-  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream));
-  API_END
+  return idxtts_gpt_session_init_ex(ctx, slots, max_prompt, max_new_tokens, repetition_penalty, 0, workspace, workspace_bytes, stream);
 }
 
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags) {
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
   if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
-  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, (flags & IDXTTS_SESSION_SAMPLED) != 0, 0,
-                                        (flags & IDXTTS_SESSION_SCORES) != 0, (flags & IDXTTS_SESSION_PREFIX) != 0) : 0;
+  return m ? m->session_workspace_bytes(session_shape(slots, max_prompt, max_new_tokens, flags, 0)) : 0;
 }
 
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
@@ -543,16 +558,24 @@ int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int m
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)), "unknown session flags");
-  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
-                         (flags & IDXTTS_SESSION_SAMPLED) != 0, 0, (flags & IDXTTS_SESSION_SCORES) != 0, (flags & IDXTTS_SESSION_PREFIX) != 0);
+  return m->session_init(workspace, workspace_bytes, session_shape(slots, max_prompt, max_new_tokens, flags, 0), repetition_penalty,
+                         static_cast<hipStream_t>(stream));
   API_END
+}
+
+// what every greedy / sampled admission entry point carries; each names the further fields it sets
+static GPTModel::Admission admission(int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
+                                     const int* max_new_tokens) {
+  GPTModel::Admission a;
+  a.n = n; a.inputs_embeds = inputs_embeds; a.ld_rows = ld_rows; a.prompt_lens = prompt_lens; a.ids = slot_ids; a.caps = max_new_tokens;
+  return a;
 }
 
 int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
                              const int* slot_ids, const int* max_new_tokens, void* workspace, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream));
+  return m->session_admit(workspace, admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens), static_cast<hipStream_t>(stream));
   API_END
 }
 
@@ -562,8 +585,9 @@ int idxtts_gpt_session_admit_sampled(idxtts_ctx* ctx, int n, const float* inputs
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(per_row, "null pointer");
-  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
-                          per_row);
+  GPTModel::Admission a = admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens);
+  a.per_row = per_row;
+  return m->session_admit(workspace, a, static_cast<hipStream_t>(stream));
   API_END
 }
 
@@ -573,8 +597,9 @@ int idxtts_gpt_session_admit_takes(idxtts_ctx* ctx, int n, const float* inputs_e
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(takes, "null pointer");
-  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
-                          per_take, takes);
+  GPTModel::Admission a = admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens);
+  a.per_row = per_take; a.takes = takes;
+  return m->session_admit(workspace, a, static_cast<hipStream_t>(stream));
   API_END
 }
 
@@ -584,8 +609,9 @@ int idxtts_gpt_session_admit_prefix(idxtts_ctx* ctx, int n, const float* inputs_
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(prefix_lens, "null prefix_lens");
-  return m->session_admit(workspace, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens, static_cast<hipStream_t>(stream),
-                          per_take, takes, prefix_lens, prefix, prefix_logprobs);
+  GPTModel::Admission a = admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens);
+  a.per_row = per_take; a.takes = takes; a.prefix_lens = prefix_lens; a.prefix = prefix; a.prefix_logprobs = prefix_logprobs;
+  return m->session_admit(workspace, a, static_cast<hipStream_t>(stream));
   API_END
 }
 
@@ -601,7 +627,7 @@ size_t idxtts_gpt_session_workspace_bytes_beam(const idxtts_ctx* ctx, int slots,
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
   if (num_beams < 2 || num_beams > BEAM_MAX || slots % num_beams) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
-  return m ? m->session_workspace_bytes(slots, max_prompt, max_new_tokens, false, num_beams) : 0;
+  return m ? m->session_workspace_bytes(session_shape(slots, max_prompt, max_new_tokens, 0, num_beams)) : 0;
 }
 
 int idxtts_gpt_session_init_beam(idxtts_ctx* ctx, int slots, int num_beams, int max_prompt, int max_new_tokens, float repetition_penalty,
@@ -609,8 +635,8 @@ int idxtts_gpt_session_init_beam(idxtts_ctx* ctx, int slots, int num_beams, int 
   API_BEGIN
   GPT_MODEL(ctx);
   IDX_CHECK(num_beams >= 2 && num_beams <= BEAM_MAX, "2 <= num_beams <= 8");
-  return m->session_init(workspace, workspace_bytes, slots, max_prompt, max_new_tokens, repetition_penalty, static_cast<hipStream_t>(stream),
-                         false, num_beams);
+  return m->session_init(workspace, workspace_bytes, session_shape(slots, max_prompt, max_new_tokens, 0, num_beams), repetition_penalty,
+                         static_cast<hipStream_t>(stream));
   API_END
 }
 

@@ -147,18 +147,24 @@ struct GPTModel : ModelBase {
   // generate() and generate_beam() are re-entrant across host threads, each call with its own workspace and stream; both run on
   // call_stream()'s stream through run_generation() (gpt.hip): R = B * fan rows, row r on prompt r / fan, the step tail w's own
   int call_stream(hipStream_t user, hipStream_t* st);
+  struct GenerateCall {      // what one generate call may carry besides its shape and buffers; a caller names the fields it sets
+    const idxtts_sampling* sampling = nullptr;      // null (or mode 0): greedy
+    const long long* forced = nullptr;              // generate_forced: [B][max_new] tokens fed back instead of the argmax
+    int takes = 1;                   // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per
+                                     // prompt, each row's KV and last position fanned out to its takes' decode rows
+    float* logprobs = nullptr;       // device [B * takes][max_new]: every code's log-probability (idxtts.h "Scores")
+    struct Prefix {                  // k > 0: continue behind given codes (idxtts.h), one row per prompt; the prefill runs on
+      const long long* codes = nullptr;      // P + 1 + k positions and the state starts behind the prefix.  codes: device [B][k],
+      const long long* host = nullptr;       // host: their host copy (generate() makes it and checks the codes)
+      int k = 0, pos0 = 1;           // prefix code j at mel position pos0 + j: 1 (the reference's layout) or 2 (the uninterrupted run's)
+    } prefix;
+  };
+  // fan rows per prompt: call.takes of them behind one shared prefill row (generate), or fan prefill rows with call.takes = 1 (beams)
   int run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                      float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll, int poll_n,
-                     int poll_every, int* steps_done, hipStream_t st, bool share_prefill = false,      // share_prefill: B prefill rows,
-                     // each row's KV and last position fanned out to its fan decode rows (takes); else R prefill rows (beams)
-                     const long long* prefix = nullptr, const long long* prefix_host = nullptr, int k = 0, int pos0 = 2);
-                     // k > 0 (continuing from given codes): prefix device [B][k] and its host copy, one row per prompt; the prefill
-                     // runs on P + 1 + k positions, prefix code j at mel position pos0 + j, and the state starts behind the prefix
-  int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_sampling* sampling, long long* codes,
-               int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const long long* forced = nullptr,
-               int takes = 1,       // takes > 1: B * takes decode rows (codes, logits, exp_noise, ws sized for them), one prefill row per prompt
-               float* logprobs = nullptr,       // device [B * takes][max_new]: every code's log-probability (idxtts.h "Scores")
-               const long long* prefix = nullptr, int k = 0, int prefix_pos0 = 1);      // device [B][k]: continue behind these codes (idxtts.h)
+                     int poll_every, int* steps_done, hipStream_t st, const GenerateCall& call);
+  int generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, long long* codes,
+               int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, const GenerateCall& call);
   // Beam search / beam-sample (HF _beam_search; the reference's default decoding mode, infer_v2.py:714-722): B utterances x
   // num_beams rows through the same decode step, selection / hypotheses / re-indexing on the device (beam.hip).
   size_t beam_workspace_bytes(int B, int nb, int S, int max_new) const;
@@ -174,14 +180,17 @@ struct GPTModel : ModelBase {
   // or (sampled sessions) each request with its own sampler and draws.  A row's codes equal row 0 of generate() on `slots` copies of it
   // (pad_left 0): every kernel on its path is chosen from the session's properties (slots, KV format, GEMM mode) alone, never from how
   // many rows are admitted at once.
-  struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
-    int slots = 0, max_prompt = 0, max_new = 0; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
-    int invariant = 0;                // the context's batch-invariant mode at _init: the session keeps it (changed since: every call refuses)
+  struct SessionShape {      // what a session's workspace is carved by (carve_session): fixed at _init
+    int slots = 0, max_prompt = 0, max_new = 0;
     bool sampled = false;             // IDXTTS_SESSION_SAMPLED: per-slot samplers (SlotSampling table in the workspace)
+    int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
     bool scores = false;              // IDXTTS_SESSION_SCORES: [slots][max_new] log-probabilities behind everything else (w.logprobs)
     bool prefix = false;              // IDXTTS_SESSION_PREFIX: a prefill area that holds one row of max_prompt + 1 + max_new positions
-    std::vector<SlotSampling> samp;   // host image of that table (sampled sessions), copied whole at each admission
-    int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
+  };
+  struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
+    SessionShape shape; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
+    int invariant = 0;                // the context's batch-invariant mode at _init: the session keeps it (changed since: every call refuses)
+    std::vector<SlotSampling> samp;   // host image of the SlotSampling table (sampled sessions), copied whole at each admission
     std::vector<SlotBeam> beam;       // host image of the SlotBeam table (beam sessions), copied whole at each admission
     size_t ws_bytes = 0;
     std::vector<char> busy;           // admitted and not yet read
@@ -210,31 +219,35 @@ struct GPTModel : ModelBase {
   }
   // sampled: the SlotSampling table is carved after everything else, so a greedy session's layout and size are those of before;
   // num_beams > 0 (beam session): the beam buffers and the SlotBeam table likewise
-  SessionBuffers carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams = 0, bool scores = false,
-                               bool prefix = false) const;
-  size_t session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled = false, int num_beams = 0, bool scores = false,
-                                 bool prefix = false) const;
+  SessionBuffers carve_session(void* ws, const SessionShape& shape) const;
+  size_t session_workspace_bytes(const SessionShape& shape) const;
   Session* find_session(void* ws);
-  int session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st, bool sampled = false,
-                   int num_beams = 0, bool scores = false, bool prefix = false);
-  // The admission both session kinds share: n requests into the free units ids[] -- slots, or (fan > 1) groups of fan slots -- each
+#define IDX_SESSION(ws) /* `s`: the session on this workspace, or the calling method refuses */ \
+  Session* const session_of_ws = find_session(ws);                                               \
+  IDX_CHECK(session_of_ws, "no decode session on this workspace");                               \
+  Session& s = *session_of_ws
+  int session_init(void* ws, size_t ws_bytes, const SessionShape& shape, float penalty, hipStream_t st);
+  struct Admission {      // n requests for free units of a session; a caller names the fields it sets
+    int n = 0, ld_rows = 0;
+    const float* inputs_embeds = nullptr;      // device [n][ld_rows][d], right-padded
+    const int* prompt_lens = nullptr;          // HOST [n]
+    const int *ids = nullptr, *caps = nullptr; // HOST: the free units -- slots, or (beam sessions) groups -- and a token cap for each
+    const idxtts_sampling* per_row = nullptr;      // null = every row greedy; else one sampler per row (sampled sessions only)
+    const int* takes = nullptr;       // null, or takes[b] >= 1 slots per request: ids, caps and per_row then have one entry per take,
+                                      // request after request, and the request's one prefill row's keys and values go to all of them
+    // sessions with IDXTTS_SESSION_PREFIX (idxtts.h "Continuing from given codes"); all of them null: the call of before
+    const int* prefix_lens = nullptr;           // HOST [n]: request b's prefill row holds P_b + 1 + prefix_lens[b] positions, the last
+    const long long* prefix = nullptr;          // prefix_lens[b] of them its codes of this packed device array (one behind the other)
+    const float* prefix_logprobs = nullptr;     // device fp32, packed likewise, or null: what _read_scored returns for those codes
+  };
+  // The admission both session kinds share: a.n requests into the free units a.ids[] -- slots, or (fan > 1) groups of fan slots -- each
   // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's
-  // keys and values going to its unit's slots.  *S: positions per prefill row.
-  int admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
-                    const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S, hipStream_t st,
-                    const int* takes = nullptr, const int** take_row = nullptr, const int* prefix_lens = nullptr,
-                    const long long* prefix = nullptr);
-  // prefix_lens, prefix (sessions with IDXTTS_SESSION_PREFIX): request b's prefill row holds P_b + 1 + prefix_lens[b] positions, the
-  // last prefix_lens[b] of them its codes of the packed device array `prefix`; their lengths and offsets are left in sb.pk / sb.poff
-  // takes (fan = 1): request b gets takes[b] slots -- ids and caps then hold one entry per take, request after request -- and its one
-  // prefill row's keys and values go to all of them; *take_row: device array, the prefill row of each take
-  // per_row: null = every row greedy; else one sampler per row (sampled sessions only).  takes: null, or takes[b] >= 1 slots per
-  // request (slot_ids, max_new and per_row then have one entry per take)
-  int session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                    const int* max_new, hipStream_t st, const idxtts_sampling* per_row = nullptr, const int* takes = nullptr,
-                    const int* prefix_lens = nullptr, const long long* prefix = nullptr, const float* prefix_logprobs = nullptr);
-  // prefix_lens HOST [n], prefix device int64 (the n prefixes packed one behind the other), prefix_logprobs device fp32 likewise or
-  // null: request b continues behind its codes (idxtts.h "Continuing from given codes"); all of them null: the call of before
+  // keys and values going to its unit's slots.  *S: positions per prefill row; *take_row (a.takes): device array, the prefill row of
+  // each take; the prefixes' lengths and offsets are left in sb.pk / sb.poff.
+  int admit_prefill(Session& s, const SessionBuffers& sb, const Admission& a, int fan, const std::function<int()>& params, int* S,
+                    const int** take_row, hipStream_t st);
+  int session_first_tokens(const Session& s, const SessionBuffers& sb, int n, hipStream_t st);      // of the n slots in sb.ids
+  int session_admit(void* ws, const Admission& a, hipStream_t st);
   // n further takes of the request in slot src, cut back to `at` codes, in the free slots dst_slots (idxtts.h); samplers: null = greedy
   // takes; caps: null = the source's cap.  Every refusal happens before anything changes.
   int session_fork(void* ws, int src, int at, int n, const int* dst_slots, const idxtts_sampling* samplers, const int* caps, hipStream_t st);

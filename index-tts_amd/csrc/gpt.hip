@@ -471,11 +471,13 @@ int GPTModel::call_stream(hipStream_t user, hipStream_t* st) {
 // to *captured when that is not null.  Every poll_every steps it reads the poll_n device flags `poll` and stops when all are set.
 int GPTModel::run_generation(const Buffers& w, const float* inputs_embeds, const int* pad_left_host, int B, int fan, int P, int max_new,
                              float penalty, float* logits_out, bool graph, hipGraphExec_t exec, StepGraph* captured, const int* poll,
-                             int poll_n, int poll_every, int* steps_done, hipStream_t st, bool share_prefill, const long long* prefix,
-                             const long long* prefix_host, int k, int pos0) {
+                             int poll_n, int poll_every, int* steps_done, hipStream_t st, const GenerateCall& call) {
+  const long long *const prefix = call.prefix.codes, *const prefix_host = call.prefix.host;
+  const int k = call.prefix.k, pos0 = call.prefix.pos0;
   const int d = cfg.model_dim, V = cfg.number_mel_codes, S = P + 1 + k, R = B * fan;
   IDX_CHECK(k == 0 || (prefix && prefix_host), "null prefix");
-  if (fan == 1) share_prefill = false;
+  IDX_CHECK(call.takes == 1 || call.takes == fan, "takes: the rows of each prompt");
+  const bool share_prefill = call.takes > 1;
   // ---- per-call state ----
   std::vector<int> kstart(R, 0);
   for (int r = 0; r < R; ++r) {
@@ -588,13 +590,16 @@ static int check_sampling(const idxtts_sampling& r) {
   return 0;
 }
 
-int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty,
-                       const idxtts_sampling* sampling, long long* codes, int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph,
-                       hipStream_t user_stream, const long long* forced, int takes, float* logprobs, const long long* prefix, int k,
-                       int prefix_pos0) {
+int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, long long* codes,
+                       int* n_steps_out, float* logits_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t user_stream,
+                       const GenerateCall& call) {
+  const idxtts_sampling* const sampling = call.sampling;
+  const long long *const forced = call.forced, *const prefix = call.prefix.codes;
+  float* const logprobs = call.logprobs;
+  const int takes = call.takes, k = call.prefix.k;
   IDX_CHECK(inputs_embeds && codes && n_steps_out, "null pointer");
   IDX_CHECK(k >= 0 && (k == 0 || prefix), "prefix: k >= 0 codes per prompt (k > 0 needs the codes)");
-  IDX_CHECK(k == 0 || prefix_pos0 == 1 || prefix_pos0 == 2, "prefix_pos0: 1 (the reference's layout) or 2 (the uninterrupted run's)");
+  IDX_CHECK(k == 0 || call.prefix.pos0 == 1 || call.prefix.pos0 == 2, "prefix_pos0: 1 (the reference's layout) or 2 (the uninterrupted run's)");
   IDX_CHECK(k == 0 || !forced, "teacher forcing together with a prefix is not supported");
   GenScope gen_scope(this);
   IDX_CHECK(!forced || !(sampling && sampling->mode != 0), "teacher forcing is a greedy-mode instrument");
@@ -647,8 +652,10 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   }
   StepGraph fresh;
   int steps_done = 0;
+  GenerateCall run = call;
+  run.prefix.host = hp.data();
   if (run_generation(w, inputs_embeds, pad_left_host, prompts, takes, P, max_new, penalty, logits_out, graph, exec, cacheable ? &fresh : nullptr,
-                     w.finished, B, 16, &steps_done, st, true, prefix, hp.data(), k, prefix_pos0)) return 1;
+                     w.finished, B, 16, &steps_done, st, run)) return 1;
   if (fresh.exec) {      // keep it: a free cache slot, or the least recently used idle one
     std::lock_guard<std::mutex> l(graph_mu);
     int slot = -1;
@@ -694,10 +701,10 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
 // Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
 // the staged last prefill rows and the admission's index arrays.
-GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_prompt, int max_new, bool sampled, int num_beams,
-                                                 bool scores, bool prefix) const {
+GPTModel::SessionBuffers GPTModel::carve_session(void* ws, const SessionShape& shape) const {
+  const int slots = shape.slots, max_prompt = shape.max_prompt, max_new = shape.max_new, num_beams = shape.num_beams;
   SessionBuffers sb;
-  const size_t pre = session_prefill_rows(slots, max_prompt, prefix ? max_new : 0);
+  const size_t pre = session_prefill_rows(slots, max_prompt, shape.prefix ? max_new : 0);
   sb.w = carve(ws, slots, max_prompt + 1, max_new, pre);
   Carver c(ws);
   c.off = sb.w.bytes;
@@ -708,7 +715,7 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
   sb.klen = c.take<int>(slots);
   sb.cap = c.take<int>(slots);
   sb.samp = nullptr;
-  if (sampled) sb.w.slot_samp = sb.samp = c.take<SlotSampling>(slots);
+  if (shape.sampled) sb.w.slot_samp = sb.samp = c.take<SlotSampling>(slots);
   sb.bb = BeamBuffers{};
   sb.beam = nullptr;
   if (num_beams > 0) {      // beam session: slots / num_beams groups
@@ -725,17 +732,14 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, int slots, int max_pr
     if (use_pl(slots)) { b.x_row = w.xrow; b.x_stats = w.stats; } else b.x_frag = w.xd;
     b.mel_emb = mel_emb; b.mel_pos = mel_pos; b.d = cfg.model_dim;
   }
-  if (scores) sb.w.logprobs = c.take<float>((size_t)slots * max_new);      // (after everything else: flags 0 and 1 keep their layout)
+  if (shape.scores) sb.w.logprobs = c.take<float>((size_t)slots * max_new);      // (after everything else: flags 0 and 1 keep their layout)
   sb.pk = sb.poff = nullptr;
-  if (prefix) { sb.pk = c.take<int>(slots); sb.poff = c.take<int>(slots); }
+  if (shape.prefix) { sb.pk = c.take<int>(slots); sb.poff = c.take<int>(slots); }
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
 
-size_t GPTModel::session_workspace_bytes(int slots, int max_prompt, int max_new, bool sampled, int num_beams, bool scores,
-                                         bool prefix) const {
-  return carve_session(nullptr, slots, max_prompt, max_new, sampled, num_beams, scores, prefix).bytes;
-}
+size_t GPTModel::session_workspace_bytes(const SessionShape& shape) const { return carve_session(nullptr, shape).bytes; }
 
 GPTModel::Session* GPTModel::find_session(void* ws) {
   std::lock_guard<std::mutex> l(session_mu);
@@ -743,18 +747,18 @@ GPTModel::Session* GPTModel::find_session(void* ws) {
   return it == sessions.end() ? nullptr : &it->second;
 }
 
-int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt, int max_new, float penalty, hipStream_t st,
-                           bool sampled, int num_beams, bool scores, bool prefix) {
+int GPTModel::session_init(void* ws, size_t ws_bytes, const SessionShape& shape, float penalty, hipStream_t st) {
+  const int slots = shape.slots, max_prompt = shape.max_prompt, max_new = shape.max_new, num_beams = shape.num_beams;
   IDX_CHECK(ws, "null workspace");
-  IDX_CHECK(num_beams == 0 || !prefix, "a beam session takes no prefix: the scorer's length penalty and rows would have to count it");
-  IDX_CHECK(num_beams == 0 || !scores, "a beam session records no per-code scores: its hypotheses carry the scorer's");
+  IDX_CHECK(num_beams == 0 || !shape.prefix, "a beam session takes no prefix: the scorer's length penalty and rows would have to count it");
+  IDX_CHECK(num_beams == 0 || !shape.scores, "a beam session records no per-code scores: its hypotheses carry the scorer's");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
   IDX_CHECK(num_beams == 0 || (num_beams >= 2 && num_beams <= BEAM_MAX), "2 <= num_beams <= 8");
   IDX_CHECK(num_beams == 0 || slots % num_beams == 0, "slots must be a multiple of num_beams");
-  IDX_CHECK(num_beams == 0 || !sampled, "a beam session has no per-slot samplers");
+  IDX_CHECK(num_beams == 0 || !shape.sampled, "a beam session has no per-slot samplers");
   IDX_CHECK(max_new + 1 < cfg.mel_pos_len, "max_new_tokens exceeds the mel position table");
-  IDX_CHECK(ws_bytes >= session_workspace_bytes(slots, max_prompt, max_new, sampled, num_beams, scores, prefix), "workspace too small");
-  const SessionBuffers sb = carve_session(ws, slots, max_prompt, max_new, sampled, num_beams, scores, prefix);
+  IDX_CHECK(ws_bytes >= session_workspace_bytes(shape), "workspace too small");
+  const SessionBuffers sb = carve_session(ws, shape);
   const Buffers& w = sb.w;
   const int d = cfg.model_dim;
   IDX_HIP(hipMemsetAsync(w.kstart, 0, slots * sizeof(int), st));
@@ -764,7 +768,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   IDX_HIP(hipMemsetAsync(w.slots, 0, slots * sizeof(SlotState), st));                // every slot free
   IDX_HIP(hipMemsetAsync(sb.x_last, 0, (size_t)slots * d * sizeof(float), st));
   IDX_HIP(hipMemsetAsync(w.xrow, 0, (size_t)slots * d * sizeof(float), st));
-  if (sampled) IDX_HIP(hipMemsetAsync(sb.samp, 0, slots * sizeof(SlotSampling), st));      // every slot greedy
+  if (shape.sampled) IDX_HIP(hipMemsetAsync(sb.samp, 0, slots * sizeof(SlotSampling), st));      // every slot greedy
   if (num_beams) {      // every group free (SlotState zeroed above) and finished: no stale scorer state is ever read
     const int G = slots / num_beams;
     IDX_HIP(hipMemsetAsync(sb.beam, 0, G * sizeof(SlotBeam), st));
@@ -777,17 +781,13 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, int slots, int max_prompt,
   Session& s = sessions[ws];
   s.step.drop();
   s = Session();
-  s.slots = slots; s.max_prompt = max_prompt; s.max_new = max_new; s.penalty = penalty; s.kv_fmt = kv_fmt; s.gemm_mode = get_gemm_mode();
+  s.shape = shape; s.penalty = penalty; s.kv_fmt = kv_fmt; s.gemm_mode = get_gemm_mode();
   s.invariant = batch_invariant;
   s.ws_bytes = ws_bytes;
   s.busy.assign(slots, 0);
   s.prompt.assign(slots, 0);
   s.first_in.assign(slots, 0);
-  s.sampled = sampled;
-  s.scores = scores;
-  s.prefix = prefix;
-  if (sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
-  s.num_beams = num_beams;
+  if (shape.sampled) s.samp.assign(slots, SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr});
   if (num_beams) s.beam.assign(slots / num_beams, SlotBeam{0, 1.0f, 0, 1.0f, 0.0, 0, 0, nullptr});
   return 0;
 }
@@ -801,13 +801,15 @@ int GPTModel::session_release(void* ws) {
   return 0;
 }
 
-int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
-                            const int* ids, const int* caps, int fan, const std::function<int()>& params, int* S_out, hipStream_t st,
-                            const int* takes, const int** take_row, const int* prefix_lens, const long long* prefix) {
+int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, const Admission& a, int fan, const std::function<int()>& params,
+                            int* S_out, const int** take_row, hipStream_t st) {
+  const int n = a.n, ld_rows = a.ld_rows;
+  const float* const inputs_embeds = a.inputs_embeds;
+  const int *const prompt_lens = a.prompt_lens, *const ids = a.ids, *const caps = a.caps, *const takes = a.takes, *const prefix_lens = a.prefix_lens;
   IDX_CHECK(inputs_embeds && prompt_lens && ids && caps, "null pointer");
   IDX_CHECK(!prefix_lens || fan == 1, "a beam session takes no prefix");
   IDX_CHECK(!takes || (fan == 1 && take_row), "takes belong to sessions of single rows");
-  const int units = s.slots / fan;
+  const int units = s.shape.slots / fan;
   IDX_CHECK(n >= 1 && n <= units, "admit 1 .. slots / num_beams requests");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
@@ -821,8 +823,8 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
       IDX_CHECK(!s.busy[ids[t] * fan] && !taken[ids[t]], "slot or group is not free");
       taken[ids[t]] = 1;
     }
-    IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
-    for (int t = T; t < T + tb; ++t) IDX_CHECK(caps[t] >= 1 && caps[t] <= s.max_new, "token cap out of range (1 .. max_new)");
+    IDX_CHECK(prompt_lens[b] >= 1 && prompt_lens[b] <= s.shape.max_prompt && prompt_lens[b] <= ld_rows, "prompt length out of range");
+    for (int t = T; t < T + tb; ++t) IDX_CHECK(caps[t] >= 1 && caps[t] <= s.shape.max_new, "token cap out of range (1 .. max_new)");
     const int kb = prefix_lens ? prefix_lens[b] : 0;      // (>= 0: session_admit has checked)
     // a row that holds its cap already has nothing to produce; k < cap <= max_new also keeps P + 1 + k inside the cache and k + 2
     // inside the position table (session_init: max_new + 1 < mel_pos_len)
@@ -838,7 +840,7 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   const int S = pmax + 1;
   int rows = n;
   if (kv_fmt == 1 && s.gemm_mode == GEMM_BF16X3 && !s.invariant) rows = std::max(n, cdiv(256, S));      // (the mode's prefill is exact)
-  const size_t pre = session_prefill_rows(s.slots, s.max_prompt, s.prefix ? s.max_new : 0);
+  const size_t pre = session_prefill_rows(s.shape.slots, s.shape.max_prompt, s.shape.prefix ? s.shape.max_new : 0);
   if (prefix_lens) IDX_CHECK((size_t)rows * S <= pre, "prefixed admission: " + std::to_string(rows) + " prefill rows x " + std::to_string(S) +
                              " positions exceed the session's prefill area of " + std::to_string(pre) + " positions: admit in smaller groups");
   IDX_CHECK((size_t)rows * S <= pre, "admission prefill exceeds the workspace");
@@ -846,32 +848,32 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   IDX_CHECK(!takes || (size_t)rows + n + 1 + T <= pre, "admission index arrays exceed the workspace");
   if (params()) return 1;
   // first slots | (fan > 1: the group ids, sb.ids + n) | klen | cap | plen | (takes: first [n + 1], row [T])
-  std::vector<int> stage((size_t)3 * s.slots + rows + (takes ? n + 1 + T : 0), 0);
+  std::vector<int> stage((size_t)3 * s.shape.slots + rows + (takes ? n + 1 + T : 0), 0);
   for (int t = 0; t < T; ++t) {
     stage[t] = ids[t] * fan;
     if (fan > 1) stage[n + t] = ids[t];
-    stage[2 * s.slots + t] = caps[t];
+    stage[2 * s.shape.slots + t] = caps[t];
   }
-  for (int b = 0; b < n; ++b) stage[s.slots + b] = prompt_lens[b] + 1 + (prefix_lens ? prefix_lens[b] : 0);
-  for (int b = 0; b < rows; ++b) stage[3 * s.slots + b] = b < n ? prompt_lens[b] : -1;
+  for (int b = 0; b < n; ++b) stage[s.shape.slots + b] = prompt_lens[b] + 1 + (prefix_lens ? prefix_lens[b] : 0);
+  for (int b = 0; b < rows; ++b) stage[3 * s.shape.slots + b] = b < n ? prompt_lens[b] : -1;
   if (takes) {
-    int* const first = stage.data() + 3 * s.slots + rows;
+    int* const first = stage.data() + 3 * s.shape.slots + rows;
     for (int b = 0, t = 0; b < n; t += takes[b], ++b) {
       first[b] = t; first[b + 1] = t + takes[b];
       for (int j = 0; j < takes[b]; ++j) first[n + 1 + t + j] = b;
     }
   }
   IDX_HIP(hipMemcpyAsync(sb.ids, stage.data(), (fan > 1 ? 2 : 1) * T * sizeof(int), hipMemcpyHostToDevice, st));      // 2 n <= slots
-  IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.slots, T * sizeof(int), hipMemcpyHostToDevice, st));
-  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.slots, (rows + (takes ? n + 1 + T : 0)) * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.klen, stage.data() + s.shape.slots, n * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.cap, stage.data() + 2 * s.shape.slots, T * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(sb.plen, stage.data() + 3 * s.shape.slots, (rows + (takes ? n + 1 + T : 0)) * sizeof(int), hipMemcpyHostToDevice, st));
   std::vector<int> pstage;      // prefixes: k of each request | its offset in the packed codes
   int kmax = 0;
   if (prefix_lens) {
-    pstage.assign(2 * (size_t)s.slots, 0);
-    for (int b = 0, o = 0; b < n; o += prefix_lens[b], ++b) { pstage[b] = prefix_lens[b]; pstage[s.slots + b] = o; kmax = std::max(kmax, prefix_lens[b]); }
-    IDX_HIP(hipMemcpyAsync(sb.pk, pstage.data(), s.slots * sizeof(int), hipMemcpyHostToDevice, st));
-    IDX_HIP(hipMemcpyAsync(sb.poff, pstage.data() + s.slots, s.slots * sizeof(int), hipMemcpyHostToDevice, st));
+    pstage.assign(2 * (size_t)s.shape.slots, 0);
+    for (int b = 0, o = 0; b < n; o += prefix_lens[b], ++b) { pstage[b] = prefix_lens[b]; pstage[s.shape.slots + b] = o; kmax = std::max(kmax, prefix_lens[b]); }
+    IDX_HIP(hipMemcpyAsync(sb.pk, pstage.data(), s.shape.slots * sizeof(int), hipMemcpyHostToDevice, st));
+    IDX_HIP(hipMemcpyAsync(sb.poff, pstage.data() + s.shape.slots, s.shape.slots * sizeof(int), hipMemcpyHostToDevice, st));
   }
   IDX_HIP(hipStreamSynchronize(st));      // the staging vectors go out of scope below
 
@@ -879,12 +881,12 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
     return 1;
   if (kmax > 0) {      // the given codes behind the start token, at the mel positions the uninterrupted row fed them at (2, 3, ...)
     PrefixRows pr;
-    pr.x = sb.w.x; pr.S = S; pr.d = cfg.model_dim; pr.P = sb.plen; pr.klen = sb.pk; pr.prefix = prefix; pr.off = sb.poff; pr.pos0 = 2;
+    pr.x = sb.w.x; pr.S = S; pr.d = cfg.model_dim; pr.P = sb.plen; pr.klen = sb.pk; pr.prefix = a.prefix; pr.off = sb.poff; pr.pos0 = 2;
     pr.mel_emb = mel_emb; pr.mel_pos = mel_pos; pr.V = cfg.number_mel_codes;
     if (prefix_input_rows(pr, n, kmax, st)) return 1;
   }
   KvScatter sc;
-  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.slots; sc.fan = fan;
+  sc.slot_ids = sb.ids; sc.len = sb.klen; sc.n = n; sc.slots = s.shape.slots; sc.fan = fan;
   if (takes) { sc.first = sb.plen + rows; *take_row = sb.plen + rows + n + 1; }
   for (int li = 0; li < cfg.layers; ++li)
     if (layer_full(li, sb.w, rows, S, nullptr, true, st, &sc)) return 1;
@@ -892,43 +894,62 @@ int GPTModel::admit_prefill(Session& s, const SessionBuffers& sb, int n, const f
   return 0;
 }
 
-int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* slot_ids,
-                            const int* caps, hipStream_t st, const idxtts_sampling* per_row, const int* takes, const int* prefix_lens,
-                            const long long* prefix, const float* prefix_logprobs) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0 || !prefix_lens, "a beam session takes no prefix (beams with a prefix are not supported)");
-  IDX_CHECK(s.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
-  IDX_CHECK(!per_row || s.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  IDX_CHECK(n >= 1 && n <= s.slots, "admit 1 .. slots requests");
+// a slot's sampler as its table holds it (null, or mode 0: greedy)
+static SlotSampling slot_sampling(const idxtts_sampling* r) {
+  if (!r || r->mode == 0) return SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
+  return SlotSampling{r->mode, r->temperature, r->top_k, r->top_p, r->seed, r->exp_noise};
+}
+
+// The first token of the n rows whose slots stand in sb.ids (admitted, or forked at 0): the head on all `slots` rows (the GEMV
+// use_pl(slots) selects, as a generate() of `slots` rows), sampled for those slots only; the sampler writes their first decode input
+int GPTModel::session_first_tokens(const Session& s, const SessionBuffers& sb, int n, hipStream_t st) {
+  const Buffers& w = sb.w;
+  if (head_logits(w, s.shape.slots, sb.x_last, cfg.model_dim, false, st)) return 1;
+  SampleArgs sa;
+  sa.part = w.logits; sa.parts = 1; sa.part_rows = s.shape.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.shape.max_new;
+  sa.cur_tok = w.cur_tok; sa.B = s.shape.slots; sa.V = cfg.number_mel_codes; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
+  sa.logprob_out = w.logprobs; sa.logprob_ld = s.shape.max_new;
+  sa.embed = tail_embed(w, use_pl(s.shape.slots));
+  return s.shape.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st);
+}
+
+int GPTModel::session_admit(void* ws, const Admission& adm, hipStream_t st) {
+  Admission a = adm;      // (an admission whose prefixes are all empty drops them below)
+  const int n = a.n;
+  const int *const prompt_lens = a.prompt_lens, *const slot_ids = a.ids, *const takes = a.takes;
+  const idxtts_sampling* const per_row = a.per_row;
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams == 0 || !a.prefix_lens, "a beam session takes no prefix (beams with a prefix are not supported)");
+  IDX_CHECK(s.shape.num_beams == 0, "a beam session admits with _admit_beam (one idxtts_beam per request)");
+  IDX_CHECK(!per_row || s.shape.sampled, "per-request sampling needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  IDX_CHECK(n >= 1 && n <= s.shape.slots, "admit 1 .. slots requests");
   // takes: slot_ids, caps and per_row have one entry per take, request after request (T of them); else one per request
   int T = n;
   if (takes) {
     T = 0;
     for (int b = 0; b < n; ++b) {
-      IDX_CHECK(takes[b] >= 1 && T + takes[b] <= s.slots, "takes: at least 1 per request, at most the session's slots in all");
+      IDX_CHECK(takes[b] >= 1 && T + takes[b] <= s.shape.slots, "takes: at least 1 per request, at most the session's slots in all");
       T += takes[b];
     }
   }
   GenScope gen_scope(this);
   const int d = cfg.model_dim, V = cfg.number_mel_codes;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
+  const SessionBuffers sb = carve_session(ws, s.shape);
   const Buffers& w = sb.w;
   // prefixes: the codes are read here -- nothing follows a stop token, and a code outside the table is no code.  No request with
   // codes: the admission of before, kernel for kernel.
   long long ktot = 0;
-  if (prefix_lens)
+  if (a.prefix_lens)
     for (int b = 0; b < n; ++b) {
-      IDX_CHECK(prefix_lens[b] >= 0 && prefix_lens[b] < s.max_new, "prefix: k >= cap, the row would have no code left to produce (0 <= k < max_new_tokens)");
-      ktot += prefix_lens[b];
+      IDX_CHECK(a.prefix_lens[b] >= 0 && a.prefix_lens[b] < s.shape.max_new, "prefix: k >= cap, the row would have no code left to produce (0 <= k < max_new_tokens)");
+      ktot += a.prefix_lens[b];
     }
-  if (ktot == 0) { prefix_lens = nullptr; prefix = nullptr; prefix_logprobs = nullptr; }
-  if (prefix_lens) {
-    IDX_CHECK(s.prefix, "a prefixed admission needs a session initialised with IDXTTS_SESSION_PREFIX (its prefill area holds prompt + prefix)");
-    IDX_CHECK(prefix, "null prefix");
+  if (ktot == 0) { a.prefix_lens = nullptr; a.prefix = nullptr; a.prefix_logprobs = nullptr; }
+  if (a.prefix_lens) {
+    IDX_CHECK(s.shape.prefix, "a prefixed admission needs a session initialised with IDXTTS_SESSION_PREFIX (its prefill area holds prompt + prefix)");
+    IDX_CHECK(a.prefix, "null prefix");
     std::vector<long long> hp((size_t)ktot);
-    IDX_HIP(hipMemcpyAsync(hp.data(), prefix, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+    IDX_HIP(hipMemcpyAsync(hp.data(), a.prefix, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
     IDX_HIP(hipStreamSynchronize(st));
     for (long long c : hp) {
       IDX_CHECK(c >= 0 && c < V, "prefix: a code outside the mel code table");
@@ -936,60 +957,40 @@ int GPTModel::session_admit(void* ws, int n, const float* inputs_embeds, int ld_
     }
   }
   auto params = [&]() -> int {      // the admitted slots' samplers (greedy when per_row is null); the other rows are rewritten unchanged
-    if (!s.sampled) return 0;
+    if (!s.shape.sampled) return 0;
     if (per_row)
       for (int b = 0; b < T; ++b)
         if (check_sampling(per_row[b])) return 1;
-    for (int b = 0; b < T; ++b) {
-      SlotSampling& e = s.samp[slot_ids[b]];
-      e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
-      if (per_row && per_row[b].mode != 0) {
-        const idxtts_sampling& r = per_row[b];
-        e = SlotSampling{r.mode, r.temperature, r.top_k, r.top_p, r.seed, r.exp_noise};
-      }
-    }
-    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
+    for (int b = 0; b < T; ++b) s.samp[slot_ids[b]] = slot_sampling(per_row ? per_row + b : nullptr);
+    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.shape.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
     return 0;
   };
   int S = 0;
   const int* take_row = nullptr;      // takes: the prefill row of each take (device)
-  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, slot_ids, caps, 1, params, &S, st, takes, &take_row, prefix_lens, prefix))
-    return 1;
-  if (prefix_lens) {
+  if (admit_prefill(s, sb, a, 1, params, &S, &take_row, st)) return 1;
+  if (a.prefix_lens) {
     PrefixReset pr;
     pr.slots = w.slots; pr.seen = w.seen; pr.V = V; pr.start_token = cfg.start_mel_token; pr.x_last = sb.x_last; pr.x = w.x; pr.S = S; pr.d = d;
-    pr.slot_ids = sb.ids; pr.P = sb.plen; pr.cap = sb.cap; pr.row = take_row; pr.klen = sb.pk; pr.off = sb.poff; pr.prefix = prefix;
-    pr.prefix_lp = prefix_logprobs; pr.codes = w.codes; pr.codes_ld = s.max_new; pr.logprobs = w.logprobs;
+    pr.slot_ids = sb.ids; pr.P = sb.plen; pr.cap = sb.cap; pr.row = take_row; pr.klen = sb.pk; pr.off = sb.poff; pr.prefix = a.prefix;
+    pr.prefix_lp = a.prefix_logprobs; pr.codes = w.codes; pr.codes_ld = s.shape.max_new; pr.logprobs = w.logprobs;
     if (session_reset_slots_prefix(pr, T, st)) return 1;
   } else if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, T, st, take_row)) return 1;
-  // first token of each admitted row: the head on all `slots` rows (the GEMV use_pl(slots) selects, as a generate() of `slots` rows),
-  // sampled for the admitted slots only; the sampler writes their first decode input
-  if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
-  SampleArgs sa;
-  sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
-  sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
-  sa.logprob_out = w.logprobs; sa.logprob_ld = s.max_new;
-  if (use_pl(s.slots)) { sa.embed.x_row = w.xrow; sa.embed.x_stats = w.stats; } else sa.embed.x_frag = w.xd;
-  sa.embed.mel_emb = mel_emb; sa.embed.mel_pos = mel_pos; sa.embed.d = d;
-  if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, T, st) : sample_slots_forward(sa, w.slots, sb.ids, T, st))
-    return 1;
+  if (session_first_tokens(s, sb, T, st)) return 1;
   for (int b = 0, t = 0; b < n; ++b)
     for (int j = 0; j < (takes ? takes[b] : 1); ++j, ++t) {
       s.busy[slot_ids[t]] = 1; s.prompt[slot_ids[t]] = prompt_lens[b];
-      s.first_in[slot_ids[t]] = !(prefix_lens && prefix_lens[b] > 0);      // behind a prefix x_last is position P + k's, not the prompt's last
+      s.first_in[slot_ids[t]] = !(a.prefix_lens && a.prefix_lens[b] > 0);      // behind a prefix x_last is position P + k's, not the prompt's last
     }
   return 0;
 }
 
 int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_slots, int* n_finished, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
+  IDX_SESSION(ws);
   IDX_CHECK(n_steps >= 0, "n_steps");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
   GenScope gen_scope(this);
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
+  const SessionBuffers sb = carve_session(ws, s.shape);
   const Buffers& w = sb.w;
   const int geom = step_key();
   if (s.step.exec && s.geom != geom) s.step.drop();
@@ -998,44 +999,42 @@ int GPTModel::session_step(void* ws, int n_steps, int use_graph, int* finished_s
   for (int k = 0; k < n_steps; ++k) {
     if (graph_ok && s.warm && !s.step.exec) {
       // every per-step value lives on the device (SlotState, seen, the input rows): admissions between replays keep the graph valid
-      if (capture_step(w, s.slots, s.penalty, s.max_new, st, &s.step)) { s.step.drop(); return 1; }
+      if (capture_step(w, s.shape.slots, s.penalty, s.shape.max_new, st, &s.step)) { s.step.drop(); return 1; }
       s.geom = geom;
     }
     if (graph_ok && s.step.exec) {
       IDX_HIP(hipGraphLaunch(s.step.exec, st));
     } else {
-      if (decode_step(w, s.slots, s.penalty, s.max_new, nullptr, 0, st)) return 1;
+      if (decode_step(w, s.shape.slots, s.penalty, s.shape.max_new, nullptr, 0, st)) return 1;
       s.warm = true;
     }
   }
-  std::vector<SlotState> hs(s.slots);
-  IDX_HIP(hipMemcpyAsync(hs.data(), w.slots, s.slots * sizeof(SlotState), hipMemcpyDeviceToHost, st));
+  std::vector<SlotState> hs(s.shape.slots);
+  IDX_HIP(hipMemcpyAsync(hs.data(), w.slots, s.shape.slots * sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   int nf = 0;
-  const int stride = s.num_beams ? s.num_beams : 1;      // beam sessions report the first slot of each finished group
-  for (int i = 0; i < s.slots; i += stride)
+  const int stride = s.shape.num_beams ? s.shape.num_beams : 1;      // beam sessions report the first slot of each finished group
+  for (int i = 0; i < s.shape.slots; i += stride)
     if (s.busy[i] && !hs[i].live) { if (finished_slots) finished_slots[nf] = i; ++nf; }
   if (n_finished) *n_finished = nf;
   return 0;
 }
 
 int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, hipStream_t st, float* logprobs, bool scored) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
+  IDX_SESSION(ws);
   IDX_CHECK(codes && n_codes && (logprobs || !scored), "null pointer");
-  IDX_CHECK(!scored || s.scores, "_read_scored needs a session initialised with IDXTTS_SESSION_SCORES");
-  IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
-  if (s.num_beams) return session_read_beam(s, sb, slot, codes, n_codes, st);
+  IDX_CHECK(!scored || s.shape.scores, "_read_scored needs a session initialised with IDXTTS_SESSION_SCORES");
+  IDX_CHECK(slot >= 0 && slot < s.shape.slots && s.busy[slot], "slot holds no request");
+  const SessionBuffers sb = carve_session(ws, s.shape);
+  if (s.shape.num_beams) return session_read_beam(s, sb, slot, codes, n_codes, st);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   IDX_CHECK(!hs.live, "slot is still decoding");
-  IDX_CHECK(hs.step >= 1 && hs.step <= s.max_new, "slot state corrupt");
-  IDX_HIP(hipMemcpyAsync(codes, sb.w.codes + (size_t)slot * s.max_new, (size_t)hs.step * sizeof(long long), hipMemcpyDeviceToDevice, st));
+  IDX_CHECK(hs.step >= 1 && hs.step <= s.shape.max_new, "slot state corrupt");
+  IDX_HIP(hipMemcpyAsync(codes, sb.w.codes + (size_t)slot * s.shape.max_new, (size_t)hs.step * sizeof(long long), hipMemcpyDeviceToDevice, st));
   if (scored)
-    IDX_HIP(hipMemcpyAsync(logprobs, sb.w.logprobs + (size_t)slot * s.max_new, (size_t)hs.step * sizeof(float), hipMemcpyDeviceToDevice, st));
+    IDX_HIP(hipMemcpyAsync(logprobs, sb.w.logprobs + (size_t)slot * s.shape.max_new, (size_t)hs.step * sizeof(float), hipMemcpyDeviceToDevice, st));
   IDX_HIP(hipStreamSynchronize(st));
   *n_codes = hs.step;
   s.busy[slot] = 0;
@@ -1043,13 +1042,11 @@ int GPTModel::session_read(void* ws, int slot, long long* codes, int* n_codes, h
 }
 
 int GPTModel::session_read_nbest(void* ws, int slot, int n_best, long long* codes, int* lens, float* scores, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams > 0, "_read_nbest needs a beam session: every other session holds one sequence per slot (_read)");
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams > 0, "_read_nbest needs a beam session: every other session holds one sequence per slot (_read)");
   IDX_CHECK(codes && lens && scores, "null pointer");
-  IDX_CHECK(slot >= 0 && slot < s.slots && s.busy[slot], "slot holds no request");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
+  IDX_CHECK(slot >= 0 && slot < s.shape.slots && s.busy[slot], "slot holds no request");
+  const SessionBuffers sb = carve_session(ws, s.shape);
   return session_read_beam(s, sb, slot, codes, lens, st, n_best, scores);
 }
 
@@ -1057,23 +1054,21 @@ int GPTModel::session_read_nbest(void* ws, int slot, int n_best, long long* code
 // the ids travel in the launch arguments) ends the requests' slots -- a beam group's num_beams slots, which is all the beam stages read
 // to find a group dead (the state they leave a group in at its cap) -- and evict gives the units back
 int GPTModel::session_end(void* ws, int n, const int* slot_ids, bool evict, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
+  IDX_SESSION(ws);
   IDX_CHECK(n >= 0 && (slot_ids || n == 0), "null pointer");
-  const int fan = s.num_beams ? s.num_beams : 1;
+  const int fan = s.shape.num_beams ? s.shape.num_beams : 1;
   unsigned long long mask = 0;
   for (int b = 0; b < n; ++b) {
     const int slot = slot_ids[b];
-    IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+    IDX_CHECK(slot >= 0 && slot < s.shape.slots, "slot out of range");
     IDX_CHECK(slot % fan == 0, "a beam session's group is addressed by its first slot");
     IDX_CHECK(s.busy[slot], "slot holds no request");
     for (int j = 0; j < fan; ++j) mask |= 1ull << (slot + j);
   }
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, s.num_beams, s.scores, s.prefix);
-  if (session_end_slots(sb.w.slots, s.slots, mask, !evict, st)) return 1;
+  const SessionBuffers sb = carve_session(ws, s.shape);
+  if (session_end_slots(sb.w.slots, s.shape.slots, mask, !evict, st)) return 1;
   if (evict)
-    for (int i = 0; i < s.slots; ++i)
+    for (int i = 0; i < s.shape.slots; ++i)
       if ((mask >> i) & 1ull) s.busy[i] = 0;
   return 0;
 }
@@ -1083,41 +1078,39 @@ ParkArgs GPTModel::park_args(const Session& s, const SessionBuffers& sb, int slo
   const Buffers& w = sb.w;
   ParkArgs a;
   a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
-  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
-  a.slot = slot; a.Smax = w.Smax; a.slots = w.slots; a.samp = sb.samp; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new;
-  a.cur_tok = w.cur_tok; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots;
+  a.layer_bytes = kv_layer_bytes(s.shape.slots, w.Smax); a.layer_scales = kv_layer_scales(s.shape.slots, w.Smax);
+  a.slot = slot; a.Smax = w.Smax; a.slots = w.slots; a.samp = sb.samp; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.shape.max_new;
+  a.cur_tok = w.cur_tok; a.embed = tail_embed(w, use_pl(s.shape.slots)); a.B = s.shape.slots;
   a.logprobs = w.logprobs;
   return a;
 }
 
 int GPTModel::session_park_header(void* ws, int slot, idxtts_park_header* hdr, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0, "one row of a beam group cannot be parked: park the group (idxtts_gpt_session_park_group)");
-  IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams == 0, "one row of a beam group cannot be parked: park the group (idxtts_gpt_session_park_group)");
+  IDX_CHECK(slot >= 0 && slot < s.shape.slots, "slot out of range");
   IDX_CHECK(s.busy[slot], "slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
+  const SessionBuffers sb = carve_session(ws, s.shape);
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + slot, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   IDX_CHECK(hs.live, "slot has ended: read it, a request that is over cannot be parked");
-  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.max_new && hs.pos >= 1 && hs.pos < sb.w.Smax, "slot state corrupt");
+  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.shape.max_new && hs.pos >= 1 && hs.pos < sb.w.Smax, "slot state corrupt");
   idxtts_park_header h{};
   h.magic = IDXTTS_PARK_MAGIC; h.version = IDXTTS_PARK_VERSION;
   h.layers = cfg.layers; h.heads = cfg.heads; h.model_dim = cfg.model_dim; h.number_mel_codes = cfg.number_mel_codes;
-  h.slots = s.slots; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode; h.sampled = s.sampled ? IDXTTS_SESSION_SAMPLED : 0;
+  h.slots = s.shape.slots; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode; h.sampled = s.shape.sampled ? IDXTTS_SESSION_SAMPLED : 0;
   h.pos = hs.pos; h.mel_pos = hs.mel_pos; h.step = hs.step; h.max_step = hs.max_step;
   h.mode = 0; h.temperature = 1.0f; h.top_k = 0; h.top_p = 1.0f;
-  if (s.sampled) {
+  if (s.shape.sampled) {
     const SlotSampling& e = s.samp[slot];
     h.mode = e.mode; h.temperature = e.temperature; h.top_k = e.top_k; h.top_p = e.top_p; h.seed = e.seed;
     h.exp_noise = (unsigned long long)(uintptr_t)e.exp_noise;
   }
   h.reserved[0] = s.invariant;      // a row parked in the batch-invariant mode says so; every other row carries zeros
-  h.reserved[1] = s.scores ? 1 : 0; // a scored session's row carries its log-probabilities behind the codes
+  h.reserved[1] = s.shape.scores ? 1 : 0; // a scored session's row carries its log-probabilities behind the codes
   h.bytes = park_layout(h.kv_format, h.layers, h.heads, h.number_mel_codes, h.pos, h.step, h.reserved[1]).bytes;
   *hdr = h;
   return 0;
@@ -1135,7 +1128,7 @@ int GPTModel::session_park(void* ws, int slot, void* dst, size_t dst_bytes, size
   if (session_park_header(ws, slot, &h, st)) return 1;
   IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked row (idxtts_gpt_session_park_bytes)");
   Session& s = *find_session(ws);
-  ParkArgs a = park_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix), slot);
+  ParkArgs a = park_args(s, carve_session(ws, s.shape), slot);
   a.hdr = h; a.blob = static_cast<char*>(dst);
   if (session_park_slot(a, st)) return 1;
   s.busy[slot] = 0;
@@ -1144,13 +1137,11 @@ int GPTModel::session_park(void* ws, int slot, void* dst, size_t dst_bytes, size
 }
 
 int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_bytes, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0, "a beam session resumes whole groups (idxtts_gpt_session_resume_group), not rows");
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams == 0, "a beam session resumes whole groups (idxtts_gpt_session_resume_group), not rows");
   IDX_CHECK(src, "null pointer");
   IDX_CHECK((uintptr_t)src % 16 == 0, "the parked row must be 16-byte aligned");
-  IDX_CHECK(slot >= 0 && slot < s.slots, "slot out of range");
+  IDX_CHECK(slot >= 0 && slot < s.shape.slots, "slot out of range");
   IDX_CHECK(!s.busy[slot], "slot is not free");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
@@ -1165,14 +1156,14 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   IDX_CHECK(h.reserved[0] == 0 || h.reserved[0] == 1, "parked row's mode field is corrupt");
   IDX_CHECK(h.reserved[0] == s.invariant, "parked row and session differ in the batch-invariant mode");
   IDX_CHECK(h.reserved[1] == 0 || h.reserved[1] == 1, "parked row's scores field is corrupt");
-  IDX_CHECK(h.reserved[1] == (s.scores ? 1 : 0), "parked row and session differ in IDXTTS_SESSION_SCORES (a scored row carries a segment more)");
+  IDX_CHECK(h.reserved[1] == (s.shape.scores ? 1 : 0), "parked row and session differ in IDXTTS_SESSION_SCORES (a scored row carries a segment more)");
   // in the mode nothing on a row's path depends on the slot count: a row moves between sessions of any size
-  IDX_CHECK(s.invariant || h.slots == s.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
+  IDX_CHECK(s.invariant || h.slots == s.shape.slots, "parked row of a session with a different number of slots (the key split and the GEMV differ)");
   IDX_CHECK(h.kv_format == s.kv_fmt, "parked row of another KV format");
   IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked row of another GEMM mode");
-  IDX_CHECK(h.mode == 0 || s.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
-  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
+  IDX_CHECK(h.mode == 0 || s.shape.sampled, "a sampled request needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  const SessionBuffers sb = carve_session(ws, s.shape);
+  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.shape.max_new, "token cap above the session's max_new_tokens");
   IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= 1, "parked row's step scalars are corrupt");
   IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
   if (h.mode != 0) {
@@ -1185,7 +1176,7 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
   ParkArgs a = park_args(s, sb, slot);
   a.hdr = h; a.blob = const_cast<char*>(static_cast<const char*>(src));
   if (session_resume_slot(a, st)) return 1;
-  if (s.sampled) s.samp[slot] = SlotSampling{h.mode, h.temperature, h.top_k, h.top_p, h.seed, reinterpret_cast<const float*>((uintptr_t)h.exp_noise)};
+  if (s.shape.sampled) s.samp[slot] = SlotSampling{h.mode, h.temperature, h.top_k, h.top_p, h.seed, reinterpret_cast<const float*>((uintptr_t)h.exp_noise)};
   s.busy[slot] = 1; s.prompt[slot] = h.pos - h.step; s.first_in[slot] = 0;
   return 0;
 }
@@ -1193,19 +1184,17 @@ int GPTModel::session_resume(void* ws, int slot, const void* src, size_t src_byt
 // ---- fork: further takes of a row that is already in the session (idxtts.h "Several takes of one request") ----
 int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slots, const idxtts_sampling* samplers, const int* caps,
                            hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams == 0, "a beam session's rows cannot be forked: beams of a group are not independent requests");
-  IDX_CHECK(dst_slots && n >= 1 && n < s.slots, "fork to 1 .. slots - 1 destinations");
-  IDX_CHECK(!samplers || s.sampled, "a sampled take needs a session initialised with IDXTTS_SESSION_SAMPLED");
-  IDX_CHECK(src >= 0 && src < s.slots, "source slot out of range");
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams == 0, "a beam session's rows cannot be forked: beams of a group are not independent requests");
+  IDX_CHECK(dst_slots && n >= 1 && n < s.shape.slots, "fork to 1 .. slots - 1 destinations");
+  IDX_CHECK(!samplers || s.shape.sampled, "a sampled take needs a session initialised with IDXTTS_SESSION_SAMPLED");
+  IDX_CHECK(src >= 0 && src < s.shape.slots, "source slot out of range");
   IDX_CHECK(s.busy[src], "source slot holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  std::vector<char> taken(s.slots, 0);
+  std::vector<char> taken(s.shape.slots, 0);
   for (int j = 0; j < n; ++j) {
-    IDX_CHECK(dst_slots[j] >= 0 && dst_slots[j] < s.slots, "destination slot out of range");
+    IDX_CHECK(dst_slots[j] >= 0 && dst_slots[j] < s.shape.slots, "destination slot out of range");
     IDX_CHECK(dst_slots[j] != src, "a destination is the source slot");
     IDX_CHECK(!s.busy[dst_slots[j]] && !taken[dst_slots[j]], "destination slot is not free");
     taken[dst_slots[j]] = 1;
@@ -1213,30 +1202,30 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
   if (samplers)
     for (int j = 0; j < n; ++j)
       if (check_sampling(samplers[j])) return 1;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, s.sampled, 0, s.scores, s.prefix);
+  const SessionBuffers sb = carve_session(ws, s.shape);
   const Buffers& w = sb.w;
-  const int V = cfg.number_mel_codes, d = cfg.model_dim;
+  const int V = cfg.number_mel_codes;
   SlotState hs;
   IDX_HIP(hipMemcpyAsync(&hs, w.slots + src, sizeof(SlotState), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
-  IDX_CHECK(hs.step >= 1 && hs.step <= hs.max_step && hs.max_step <= s.max_new && hs.pos >= 1 && hs.pos <= w.Smax, "slot state corrupt");
+  IDX_CHECK(hs.step >= 1 && hs.step <= hs.max_step && hs.max_step <= s.shape.max_new && hs.pos >= 1 && hs.pos <= w.Smax, "slot state corrupt");
   // a row that ended on the stop token has nothing behind it: a take may keep at most the codes in front of the stop token
   int most = hs.step;
   if (!hs.live) {
     long long last = 0;
-    IDX_HIP(hipMemcpyAsync(&last, w.codes + (size_t)src * s.max_new + hs.step - 1, sizeof(last), hipMemcpyDeviceToHost, st));
+    IDX_HIP(hipMemcpyAsync(&last, w.codes + (size_t)src * s.shape.max_new + hs.step - 1, sizeof(last), hipMemcpyDeviceToHost, st));
     IDX_HIP(hipStreamSynchronize(st));
     if (last == cfg.stop_mel_token) most = hs.step - 1;
   }
   if (at == -1) at = most;      // where the source stands now
   IDX_CHECK(at >= 0 && at <= most, "at out of range (0 .. the source's codes, the stop token not among them)");
   const int P = s.prompt[src];      // (an ended row's pos does not say: it stays behind when the row ends by itself, not when it is stopped)
-  IDX_CHECK(P >= 1 && P <= s.max_prompt && P + hs.step - 1 <= hs.pos && hs.pos <= P + hs.step, "slot state corrupt");
+  IDX_CHECK(P >= 1 && P <= s.shape.max_prompt && P + hs.step - 1 <= hs.pos && hs.pos <= P + hs.step, "slot state corrupt");
   IDX_CHECK(at > 0 || s.first_in[src], "at = 0 needs a source that still has its prefill output: a resumed row (and a take of one) does not");
   ForkArgs a;
   for (int j = 0; j < n; ++j) {
     const int cap = caps ? caps[j] : hs.max_step;
-    IDX_CHECK(cap >= 1 && cap <= s.max_new, "token cap out of range (1 .. max_new)");
+    IDX_CHECK(cap >= 1 && cap <= s.shape.max_new, "token cap out of range (1 .. max_new)");
     IDX_CHECK(cap > at, "a take's cap must leave it a code to produce (cap > at)");
     IDX_CHECK((long long)P + 1 + cap <= w.Smax, "the take does not fit the session's cache");
     a.dst[j] = (unsigned char)dst_slots[j]; a.cap[j] = cap;
@@ -1245,33 +1234,19 @@ int GPTModel::session_fork(void* ws, int src, int at, int n, const int* dst_slot
   a.kv_fmt = s.kv_fmt; a.layers = cfg.layers; a.heads = cfg.heads; a.V = V; a.start_token = cfg.start_mel_token;
   a.src = src; a.P = P; a.at = at; a.n = n;
   a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
-  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
-  a.Smax = w.Smax; a.slots = w.slots; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.max_new; a.cur_tok = w.cur_tok;
-  a.x_last = sb.x_last; a.embed = tail_embed(w, use_pl(s.slots)); a.B = s.slots; a.logprobs = w.logprobs;
+  a.layer_bytes = kv_layer_bytes(s.shape.slots, w.Smax); a.layer_scales = kv_layer_scales(s.shape.slots, w.Smax);
+  a.Smax = w.Smax; a.slots = w.slots; a.seen = w.seen; a.codes = w.codes; a.codes_ld = s.shape.max_new; a.cur_tok = w.cur_tok;
+  a.x_last = sb.x_last; a.embed = tail_embed(w, use_pl(s.shape.slots)); a.B = s.shape.slots; a.logprobs = w.logprobs;
   if (session_fork_slots(a, st)) return 1;      // (its own checks come before its launch: from here on nothing refuses)
-  if (s.sampled) {      // the takes' samplers (greedy when samplers is null); the other rows are rewritten unchanged
-    for (int j = 0; j < n; ++j) {
-      SlotSampling& e = s.samp[dst_slots[j]];
-      e = SlotSampling{0, 1.0f, 0, 1.0f, 0, nullptr};
-      if (samplers && samplers[j].mode != 0) {
-        const idxtts_sampling& r = samplers[j];
-        e = SlotSampling{r.mode, r.temperature, r.top_k, r.top_p, r.seed, r.exp_noise};
-      }
-    }
-    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
+  if (s.shape.sampled) {      // the takes' samplers (greedy when samplers is null); the other rows are rewritten unchanged
+    for (int j = 0; j < n; ++j) s.samp[dst_slots[j]] = slot_sampling(samplers ? samplers + j : nullptr);
+    IDX_HIP(hipMemcpyAsync(sb.samp, s.samp.data(), s.shape.slots * sizeof(SlotSampling), hipMemcpyHostToDevice, st));
   }
   if (at == 0) {      // the takes' first token: the admission's head-and-sample pass on the destinations
     std::vector<int> ids(dst_slots, dst_slots + n);
     IDX_HIP(hipMemcpyAsync(sb.ids, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
     IDX_HIP(hipStreamSynchronize(st));      // the staging vector goes out of scope below
-    if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
-    SampleArgs sa;
-    sa.part = w.logits; sa.parts = 1; sa.part_rows = s.slots; sa.seen = w.seen; sa.codes = w.codes; sa.codes_ld = s.max_new;
-    sa.cur_tok = w.cur_tok; sa.B = s.slots; sa.V = V; sa.stop_token = cfg.stop_mel_token; sa.penalty = s.penalty;
-    sa.logprob_out = w.logprobs; sa.logprob_ld = s.max_new;
-    sa.embed = tail_embed(w, use_pl(s.slots));
-    if (s.sampled ? sample_slots_warp_forward(sa, w.slots, sb.samp, sb.ids, n, st) : sample_slots_forward(sa, w.slots, sb.ids, n, st))
-      return 1;
+    if (session_first_tokens(s, sb, n, st)) return 1;
   }
   for (int j = 0; j < n; ++j) { s.busy[dst_slots[j]] = 1; s.prompt[dst_slots[j]] = P; s.first_in[dst_slots[j]] = s.first_in[src]; }
   return 0;

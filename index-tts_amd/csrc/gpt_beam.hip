@@ -136,7 +136,7 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
   // the beams of an utterance start identical: its prompt on all nb rows; beam_scorer.is_done (every utterance finished) polled
   int steps_done = 0;
   if (run_generation(w, inputs_embeds, pad_left_host, B, nb, P, max_new, penalty, nullptr, use_graph && !prof_enabled(), nullptr, nullptr,
-                     bb.done, B, 8, &steps_done, st)) return 1;
+                     bb.done, B, 8, &steps_done, st, GenerateCall{})) return 1;      // (nb prefill rows per utterance, no prefix)
 
   // ---- BeamSearchScorer.finalize on the host (transformers_beam_search.py:320-414) ----
   std::vector<int> seq((size_t)R * max_new), hyp_len((size_t)B * (BEAM_MAX + 1)), hyp_slot(hyp_len.size()), hyp_n(B), done(B);
@@ -174,14 +174,12 @@ int GPTModel::generate_beam(const float* inputs_embeds, const int* pad_left_host
 // ---- beam decode session (gpt.h; the greedy session's machinery in gpt.hip) ----
 int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* group_ids,
                                  const int* caps, const idxtts_beam* per_request, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams > 0, "_admit_beam needs a session initialised with num_beams (idxtts_gpt_session_init_beam)");
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams > 0, "_admit_beam needs a session initialised with num_beams (idxtts_gpt_session_init_beam)");
   IDX_CHECK(per_request, "null pointer");
   GenScope gen_scope(this);
-  const int nb = s.num_beams, G = s.slots / nb, d = cfg.model_dim;
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
+  const int nb = s.shape.num_beams, G = s.shape.slots / nb, d = cfg.model_dim;
+  const SessionBuffers sb = carve_session(ws, s.shape);
   const Buffers& w = sb.w;
   auto params = [&]() -> int {      // every request is checked before any group is taken (generate_beam's rules)
     for (int b = 0; b < n; ++b) {
@@ -198,13 +196,15 @@ int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, in
   };
   // one prefill row per request, its keys and values going to every slot of its group
   int S = 0;
-  if (admit_prefill(s, sb, n, inputs_embeds, ld_rows, prompt_lens, group_ids, caps, nb, params, &S, st)) return 1;
+  Admission a;
+  a.n = n; a.inputs_embeds = inputs_embeds; a.ld_rows = ld_rows; a.prompt_lens = prompt_lens; a.ids = group_ids; a.caps = caps;
+  if (admit_prefill(s, sb, a, nb, params, &S, nullptr, st)) return 1;
   BeamState bs = w.beam;
   bs.penalty = s.penalty; bs.group_ids = sb.ids + n; bs.n_ids = n;
   if (beam_session_reset(bs, cfg.start_mel_token, sb.x_last, w.x, S, sb.plen, sb.cap, n, st)) return 1;
   // the first beam step of the admitted groups: the head on all `slots` rows (the GEMV generate_beam's R = slots rows selects), the beam
   // stages on those groups only; the last one writes their first decode inputs
-  if (head_logits(w, s.slots, sb.x_last, d, false, st)) return 1;
+  if (head_logits(w, s.shape.slots, sb.x_last, d, false, st)) return 1;
   if (beam_scores_forward(bs, st) || beam_select_forward(bs, st) || beam_reorder_forward(bs, st)) return 1;
   for (int b = 0; b < n; ++b)
     for (int j = 0; j < nb; ++j) s.busy[group_ids[b] * nb + j] = 1;
@@ -215,7 +215,7 @@ int GPTModel::session_admit_beam(void* ws, int n, const float* inputs_embeds, in
 // if it fits under the cap (row 0 of generate_beam's codes, cut after its first stop token)
 int GPTModel::session_read_beam(Session& s, const SessionBuffers& sb, int slot, long long* codes, int* n_codes, hipStream_t st, int n_best,
                                 float* scores) {
-  const int nb = s.num_beams, g = slot / nb, L = s.max_new;
+  const int nb = s.shape.num_beams, g = slot / nb, L = s.shape.max_new;
   IDX_CHECK(n_best >= 1 && n_best <= nb, "1 <= n_best <= num_beams");
   IDX_CHECK(slot % nb == 0, "a beam session is read at the first slot of a group");
   SlotState hs;
@@ -257,23 +257,21 @@ ParkGroupArgs GPTModel::park_group_args(const Session& s, const SessionBuffers& 
   const Buffers& w = sb.w;
   ParkGroupArgs a;
   a.kcache = w.kcache; a.vcache = w.vcache; a.kscale = w.kscale; a.vscale = w.vscale;
-  a.layer_bytes = kv_layer_bytes(s.slots, w.Smax); a.layer_scales = kv_layer_scales(s.slots, w.Smax);
-  a.group = group; a.Smax = w.Smax; a.B = s.slots; a.bs = w.beam; a.group_tab = sb.beam;
-  a.embed = tail_embed(w, use_pl(s.slots));
+  a.layer_bytes = kv_layer_bytes(s.shape.slots, w.Smax); a.layer_scales = kv_layer_scales(s.shape.slots, w.Smax);
+  a.group = group; a.Smax = w.Smax; a.B = s.shape.slots; a.bs = w.beam; a.group_tab = sb.beam;
+  a.embed = tail_embed(w, use_pl(s.shape.slots));
   return a;
 }
 
 int GPTModel::session_park_group_header(void* ws, int group, idxtts_park_group_header* hdr, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams > 0, "_park_group needs a beam session: a greedy or sampled session parks rows (idxtts_gpt_session_park)");
-  const int nb = s.num_beams, G = s.slots / nb;
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams > 0, "_park_group needs a beam session: a greedy or sampled session parks rows (idxtts_gpt_session_park)");
+  const int nb = s.shape.num_beams, G = s.shape.slots / nb;
   IDX_CHECK(group >= 0 && group < G, "group out of range");
   IDX_CHECK(s.busy[group * nb], "group holds no request");
   IDX_CHECK(kv_fmt == s.kv_fmt && get_gemm_mode() == s.gemm_mode, "KV format or GEMM mode changed since the session was initialised");
   IDX_CHECK(batch_invariant == s.invariant, "batch-invariant mode changed since the session was initialised");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
+  const SessionBuffers sb = carve_session(ws, s.shape);
   SlotState hs;
   int hyp_n = 0, done = 0;
   IDX_HIP(hipMemcpyAsync(&hs, sb.w.slots + group * nb, sizeof(SlotState), hipMemcpyDeviceToHost, st));
@@ -281,14 +279,14 @@ int GPTModel::session_park_group_header(void* ws, int group, idxtts_park_group_h
   IDX_HIP(hipMemcpyAsync(&done, sb.bb.done + group, sizeof(int), hipMemcpyDeviceToHost, st));
   IDX_HIP(hipStreamSynchronize(st));
   IDX_CHECK(hs.live, "group has ended: read it, a request that is over cannot be parked");
-  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.max_new && hs.pos >= hs.step && hs.pos < sb.w.Smax &&
+  IDX_CHECK(hs.step >= 1 && hs.step < hs.max_step && hs.max_step <= s.shape.max_new && hs.pos >= hs.step && hs.pos < sb.w.Smax &&
             hs.mel_pos == hs.step + 1, "group state corrupt");
   IDX_CHECK(hyp_n >= 0 && hyp_n <= nb && (done == 0 || done == 1), "group state corrupt");
   const SlotBeam& e = s.beam[group];
   idxtts_park_group_header h{};
   h.magic = IDXTTS_PARK_GROUP_MAGIC; h.version = IDXTTS_PARK_GROUP_VERSION;
   h.layers = cfg.layers; h.heads = cfg.heads; h.model_dim = cfg.model_dim; h.number_mel_codes = cfg.number_mel_codes;
-  h.slots = s.slots; h.num_beams = nb; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode;
+  h.slots = s.shape.slots; h.num_beams = nb; h.kv_format = s.kv_fmt; h.gemm_mode = s.gemm_mode;
   h.pos = hs.pos; h.mel_pos = hs.mel_pos; h.step = hs.step; h.max_step = hs.max_step;
   h.do_sample = e.do_sample; h.temperature = e.temperature; h.top_k = e.top_k; h.top_p = e.top_p;
   h.length_penalty = e.length_penalty; h.early_stopping = e.early_stopping; h.batch_invariant = s.invariant;
@@ -311,8 +309,8 @@ int GPTModel::session_park_group(void* ws, int group, void* dst, size_t dst_byte
   if (session_park_group_header(ws, group, &h, st)) return 1;
   IDX_CHECK(dst_bytes >= h.bytes, "dst is smaller than the parked group (idxtts_gpt_session_park_group_bytes)");
   Session& s = *find_session(ws);
-  const int nb = s.num_beams;
-  ParkGroupArgs a = park_group_args(s, carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb), group);
+  const int nb = s.shape.num_beams;
+  ParkGroupArgs a = park_group_args(s, carve_session(ws, s.shape), group);
   a.hdr = h; a.blob = static_cast<char*>(dst);
   if (idxtts::session_park_group(a, st)) return 1;
   // the host image too: the next admission uploads the whole SlotBeam table, and a free group carries no request's parameters
@@ -323,11 +321,9 @@ int GPTModel::session_park_group(void* ws, int group, void* dst, size_t dst_byte
 }
 
 int GPTModel::session_resume_group(void* ws, int group, const void* src, size_t src_bytes, hipStream_t st) {
-  Session* sp = find_session(ws);
-  IDX_CHECK(sp, "no decode session on this workspace");
-  Session& s = *sp;
-  IDX_CHECK(s.num_beams > 0, "_resume_group needs a beam session: a greedy or sampled session resumes rows (idxtts_gpt_session_resume)");
-  const int nb = s.num_beams, G = s.slots / nb;
+  IDX_SESSION(ws);
+  IDX_CHECK(s.shape.num_beams > 0, "_resume_group needs a beam session: a greedy or sampled session resumes rows (idxtts_gpt_session_resume)");
+  const int nb = s.shape.num_beams, G = s.shape.slots / nb;
   IDX_CHECK(src, "null pointer");
   IDX_CHECK((uintptr_t)src % 16 == 0, "the parked group must be 16-byte aligned");
   IDX_CHECK(group >= 0 && group < G, "group out of range");
@@ -346,11 +342,11 @@ int GPTModel::session_resume_group(void* ws, int group, const void* src, size_t 
   IDX_CHECK(h.batch_invariant == 0 || h.batch_invariant == 1, "parked group's mode field is corrupt");
   IDX_CHECK(h.batch_invariant == s.invariant, "parked group and session differ in the batch-invariant mode");
   // seeded draws index with slots / num_beams, the key split and the GEMV follow the row count; in the mode none of them does
-  IDX_CHECK(s.invariant || h.slots == s.slots, "parked group of a session with a different number of slots");
+  IDX_CHECK(s.invariant || h.slots == s.shape.slots, "parked group of a session with a different number of slots");
   IDX_CHECK(h.kv_format == s.kv_fmt, "parked group of another KV format");
   IDX_CHECK(h.gemm_mode == s.gemm_mode, "parked group of another GEMM mode");
-  const SessionBuffers sb = carve_session(ws, s.slots, s.max_prompt, s.max_new, false, nb);
-  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.max_new, "token cap above the session's max_new_tokens");
+  const SessionBuffers sb = carve_session(ws, s.shape);
+  IDX_CHECK(h.max_step >= 1 && h.max_step <= s.shape.max_new, "token cap above the session's max_new_tokens");
   IDX_CHECK(h.step >= 1 && h.step < h.max_step && h.mel_pos == h.step + 1 && h.pos >= h.step, "parked group's step scalars are corrupt");
   IDX_CHECK((long long)h.pos + (h.max_step - h.step) + 1 <= sb.w.Smax, "the request's remaining steps do not fit the session's cache");
   IDX_CHECK(h.hyp_n >= 0 && h.hyp_n <= nb && (h.done == 0 || h.done == 1), "parked group's scorer fields are corrupt");

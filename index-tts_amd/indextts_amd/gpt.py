@@ -287,7 +287,7 @@ class UnifiedVoice:
         (repeat_interleave: row b * n + j is take j of prompt b); returns [B * n, P+1+generated].  exp_noise is then
         [max_new_tokens, B * n, V] and a seeded call draws the stream of row b * n + j of a B * n-row call, so the result equals generate
         on the caller-expanded batch wherever the two prefills choose the same kernels -- the prefill runs once per prompt, on B rows,
-        and each row's keys and values are written to its n takes' cache rows (`idxtts_gpt_generate_takes`).  That holds always with
+        and each row's keys and values are written to its n takes' cache rows (the `takes` of `idxtts_gpt_generate_prefix`, the one entry every non-forced form calls).  That holds always with
         an fp32 (or fp8) KV cache or in the batch-invariant mode; with a bf16 cache in split-bf16 GEMM mode when B * (P + 1) and
         B * n * (P + 1) lie on the same side of 256 prefill rows.
 
@@ -350,51 +350,31 @@ class UnifiedVoice:
         n = ctypes.c_int(0)
         if do_sample and forced_codes is not None:
             raise ValueError("forced_codes is a greedy-mode instrument")
+        sc = None
         if do_sample:
             if sampler not in ("hf", "accel"):
                 raise ValueError("sampler must be 'hf' or 'accel'")
             noise, seed = self._noise(exp_noise, generator, (max_new_tokens, B, V), seed)
-            sc = _lib.SamplingC(mode=1 if sampler == "hf" else 2, temperature=float(temperature),
-                                top_k=int(top_k or 0) if sampler == "hf" else 0,
-                                top_p=float(top_p if top_p is not None else 1.0) if sampler == "hf" else 1.0,
-                                exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
-        if forced_codes is not None:
+            sc = _sampling_c(sampler, temperature, top_k, top_p, noise, seed)
+        # one argument list: (the call's own arguments go between `head` and `tail`)
+        lib = _lib.load()
+        head = (self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p))
+        tail = (_lib.ptr(logits), _lib.ptr(ws), ws.numel())
+        if forced_codes is not None:      # the parity instrument keeps its own entries: they run without the step graph
             fc = forced_codes.to(self.device, torch.long).contiguous()
             if tuple(fc.shape) != (B, max_new_tokens):
                 raise ValueError(f"forced_codes must be {(B, max_new_tokens)}")
-        if k > 0:
-            _lib.check(_lib.load().idxtts_gpt_generate_prefix(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
-                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(prefix), k,
-                1 if prefix_layout == "hf" else 2, _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws),
-                ws.numel(), int(use_graph), _lib.current_stream()))
-        elif return_logprobs and forced_codes is not None:
-            _lib.check(_lib.load().idxtts_gpt_generate_forced_scored(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc),
-                _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-        elif return_logprobs:
-            _lib.check(_lib.load().idxtts_gpt_generate_scored(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
-                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs),
-                _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
-        elif nrs > 1:
-            _lib.check(_lib.load().idxtts_gpt_generate_takes(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), prompts, nrs, P, max_new_tokens, float(repetition_penalty),
-                ctypes.cast(ctypes.pointer(sc), c_void_p) if do_sample else c_void_p(0), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits),
-                _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
-        elif do_sample:
-            _lib.check(_lib.load().idxtts_gpt_generate_sampled(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty),
-                ctypes.byref(sc), _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph),
+            mid = (B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc), _lib.ptr(codes), ctypes.byref(n))
+            if return_logprobs:
+                _lib.check(lib.idxtts_gpt_generate_forced_scored(*head, *mid, _lib.ptr(logprobs), *tail, _lib.current_stream()))
+            else:
+                _lib.check(lib.idxtts_gpt_generate_forced(*head, *mid, *tail, _lib.current_stream()))
+        else:      # greedy (sampling NULL) and both samplers; takes, logprobs (NULL unless asked) and a prefix (NULL, k = 0 without one)
+            _lib.check(lib.idxtts_gpt_generate_prefix(
+                *head, prompts, nrs, P, max_new_tokens, float(repetition_penalty),
+                ctypes.cast(ctypes.pointer(sc), c_void_p) if sc is not None else c_void_p(0), _lib.ptr(prefix), k,
+                1 if prefix_layout == "hf" else 2, _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logprobs), *tail, int(use_graph),
                 _lib.current_stream()))
-        elif forced_codes is not None:
-            _lib.check(_lib.load().idxtts_gpt_generate_forced(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty), _lib.ptr(fc),
-                _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
-        else:
-            _lib.check(_lib.load().idxtts_gpt_generate(
-                self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, max_new_tokens, float(repetition_penalty),
-                _lib.ptr(codes), ctypes.byref(n), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), int(use_graph), _lib.current_stream()))
         out = torch.cat([input_ids.to(self.device), codes[:, : n.value]], dim=1)
         res = (out,)
         if return_logits:
@@ -408,13 +388,9 @@ class UnifiedVoice:
         (one exponential_() per step, the order HF consumes them: reproduces the reference's stream under that seed); with neither,
         the kernels draw from a counter-based generator keyed by a 63-bit seed taken from torch's global RNG (so torch.manual_seed
         still makes a run repeatable), or `seed` itself when given -- no [steps, B, V] tensor is materialised."""
-        if exp_noise is None and generator is None:
-            return None, int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else _seed64(seed)
-        if exp_noise is None:
+        if exp_noise is None and generator is not None:
             exp_noise = torch.stack([torch.empty(shape[1:]).exponential_(1, generator=generator) for _ in range(shape[0])])
-        if tuple(exp_noise.shape) != tuple(shape):
-            raise ValueError(f"exp_noise must be {tuple(shape)}")
-        return exp_noise.to(self.device, torch.float32).contiguous(), 0
+        return _draws(exp_noise, seed, shape, self.device)
 
     def generate_beam(self, input_ids: torch.Tensor, max_new_tokens: int, attention_mask: Optional[torch.Tensor], tts_embeddings: torch.Tensor,
                       num_beams: int = 3, do_sample: bool = True, temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0,
@@ -649,6 +625,28 @@ def _seed64(seed) -> int:
     return s
 
 
+def _draws(exp_noise, seed, shape, device, dims: str = ""):
+    """The one rule for a row's Exp(1) draws -> (device tensor | None, seed): an explicit `exp_noise` of `shape` (the seed is then 0), else
+    `seed`, else a 62-bit seed taken from torch's global RNG (one randint per unseeded row, in the order the rows are stated, so that
+    torch.manual_seed makes a run repeatable).  dims: how the message of a wrong shape names the dimensions."""
+    if exp_noise is not None:
+        noise = torch.as_tensor(exp_noise)
+        if tuple(noise.shape) != tuple(shape):
+            raise ValueError(f"exp_noise must be {dims}{tuple(shape)}")
+        return noise.to(device, torch.float32).contiguous(), 0
+    return None, int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else _seed64(seed)
+
+
+def _sampling_c(sampler: str, temperature=1.0, top_k=0, top_p=1.0, noise=None, seed: int = 0) -> "_lib.SamplingC":
+    """idxtts_sampling of one row: "greedy", or "hf" / "accel" with their parameters (top_k / top_p are the HF sampler's) and draws."""
+    if sampler == "greedy":
+        return _lib.SamplingC(mode=0, temperature=1.0, top_k=0, top_p=1.0, exp_noise=None, seed=0)
+    hf = sampler == "hf"
+    return _lib.SamplingC(mode=1 if hf else 2, temperature=float(temperature), top_k=int(top_k or 0) if hf else 0,
+                          top_p=float(top_p if top_p is not None else 1.0) if hf else 1.0,
+                          exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
+
+
 class ParkedRow:
     """A decode row that stepped aside (DecodeSession.park): the parked row's bytes (include/idxtts.h "Preempt and resume") on the
     device or, after to("cpu"), in pinned host memory; `n_codes` codes produced so far, the request's `cap`, and the request's
@@ -737,6 +735,10 @@ class _Session:
     def _sp(self) -> c_void_p:
         return c_void_p(self.stream.cuda_stream)
 
+    @property
+    def _what(self) -> str:
+        return "slot" if self._unit == 1 else "group"
+
     def _free(self):
         return [i for i, b in enumerate(self._busy) if not b]
 
@@ -751,7 +753,7 @@ class _Session:
         if len(caps) != n:
             raise ValueError("one cap per row")
         if n > len(free):
-            raise RuntimeError(f"{n} rows but {len(free)} free {'slots' if self._unit == 1 else 'groups'}")
+            raise RuntimeError(f"{n} rows but {len(free)} free {self._what}s")
         d = self.gpt.cfg.model_dim
         plen = [int(r.shape[0]) for r in rows]
         for r, p, c in zip(rows, plen, caps):
@@ -793,20 +795,35 @@ class _Session:
             else:
                 _lib.check(self._lib.idxtts_gpt_session_read(self.gpt._h, int(i) * self._unit, _lib.ptr(out), ctypes.byref(n),
                                                              _lib.ptr(self._ws), self._sp()))
-        self._busy[i] = False
-        self._done.discard(i)
-        self._noise.pop(i, None)
+        self._vacate(i, record=False)
         return (out[: n.value], lp[: n.value]) if scores else out[: n.value]
 
+    def _held(self, i) -> int:
+        """The id of a request this session holds (admitted and not taken), as an int; ValueError otherwise."""
+        if not isinstance(i, (int, np.integer)) or not 0 <= int(i) < len(self._busy) or not self._busy[int(i)]:
+            raise ValueError(f"{i!r} holds no request ({self._what} ids 0 .. {len(self._busy) - 1})")
+        return int(i)
+
     def _ids(self, ids) -> list:
-        """One id or a list of them -> a list of requests this session holds (admitted and not taken); ValueError otherwise."""
-        ids = [ids] if isinstance(ids, (int, np.integer)) else list(ids)
-        out = []
-        for i in ids:
-            if not isinstance(i, (int, np.integer)) or not 0 <= int(i) < len(self._busy) or not self._busy[int(i)]:
-                raise ValueError(f"{i!r} holds no request ({'slot' if self._unit == 1 else 'group'} ids 0 .. {len(self._busy) - 1})")
-            out.append(int(i))
-        return out
+        """One id or a list of them -> a list of requests this session holds; ValueError otherwise."""
+        return [self._held(i) for i in ([ids] if isinstance(ids, (int, np.integer)) else list(ids))]
+
+    def _occupy(self, ids, noises) -> None:
+        """The places `ids` hold requests now; a request's exp_noise tensor is kept alive while it reads it."""
+        for i, nz in zip(ids, noises):
+            self._busy[i] = True
+            if nz is not None:
+                self._noise[i] = nz
+
+    def _vacate(self, i: int, record: bool):
+        """The place `i` is free again; returns its request's draws.  record: they are let go (or move on) with a launch that ends the
+        request's reads on the session's stream -- evict, park -- and not after a read that has synchronised, as take has."""
+        self._busy[i] = False
+        self._done.discard(i)
+        nz = self._noise.pop(i, None)
+        if record and nz is not None:
+            nz.record_stream(self.stream)
+        return nz
 
     def _end(self, fn, ids: list) -> None:
         h = np.ascontiguousarray([i * self._unit for i in ids], dtype=np.int32)
@@ -821,11 +838,7 @@ class _Session:
             return
         self._end(self._lib.idxtts_gpt_session_evict, ids)
         for i in ids:       # as take(); a request's draws are let go only now, with the launch that ends its reads on the stream
-            self._busy[i] = False
-            self._done.discard(i)
-            nz = self._noise.pop(i, None)
-            if nz is not None:
-                nz.record_stream(self.stream)
+            self._vacate(i, record=True)
 
     def stop(self, ids) -> None:
         """Ends the live requests among `ids` and keeps them: the next step() (step(0) too) reports them and take() returns the k
@@ -834,6 +847,47 @@ class _Session:
         ids = self._ids(ids)
         if ids:
             self._end(self._lib.idxtts_gpt_session_stop, ids)
+
+    def _take_out(self, i: int, bytes_fn, park_fn, header_t):
+        """Park the request in place `i` (a slot, or a group): size, allocate, gather, read the header, free the place.  Returns
+        (blob, header, the request's draws -- they move with it: alive while it is parked)."""
+        with torch.cuda.stream(self.stream):
+            need = int(bytes_fn(self.gpt._h, i, _lib.ptr(self._ws), self._sp()))
+            if need == 0:
+                _lib.check(1)
+            blob = torch.empty(need, dtype=torch.uint8, device=self.gpt.device)
+            written = ctypes.c_size_t(0)
+            _lib.check(park_fn(self.gpt._h, i, _lib.ptr(blob), need, ctypes.byref(written), _lib.ptr(self._ws), self._sp()))
+            hdr = header_t.from_buffer_copy(blob[: ctypes.sizeof(header_t)].cpu().numpy().tobytes())
+        assert written.value == need == hdr.bytes
+        return blob, hdr, self._vacate(i, record=True)
+
+    def _put_back(self, parked: ParkedRow, i, resume_fn) -> int:
+        """Resume `parked` into place `i` (default: the first free one): stage, wait, scatter, occupy, consume.  Returns the place."""
+        parked._check()
+        if i is None:
+            free = self._free()
+            if not free:
+                raise RuntimeError(f"no free {self._what}")
+            i = free[0]
+        if not isinstance(i, (int, np.integer)) or not 0 <= int(i) < len(self._busy):
+            raise ValueError(f"{self._what} {i!r} out of range (0 .. {len(self._busy) - 1})")
+        i = int(i)
+        if self._busy[i]:
+            raise ValueError(f"{self._what} {i} is not free")
+        if parked._blob.device != self.gpt.device:
+            with torch.cuda.stream(self.stream):
+                parked.to(self.gpt.device)
+        blob = parked._blob
+        self.stream.wait_stream(parked._stream)      # it may have been written on another session's stream
+        with torch.cuda.stream(self.stream):
+            _lib.check(resume_fn(self.gpt._h, i, _lib.ptr(blob), blob.numel(), _lib.ptr(self._ws), self._sp()))
+        blob.record_stream(self.stream)
+        if parked._noise is not None:
+            parked._noise.record_stream(self.stream)
+        self._occupy([i], [parked._noise])
+        parked._blob = parked._noise = None
+        return i
 
     def close(self) -> None:
         if getattr(self, "_ws", None) is not None:
@@ -911,7 +965,7 @@ class DecodeSession(_Session):
             kind = e.get("sampler", "hf")
             noise = None
             if kind == "greedy":
-                arr[i] = _lib.SamplingC(mode=0, temperature=1.0, top_k=0, top_p=1.0, exp_noise=None, seed=0)
+                arr[i] = _sampling_c("greedy")
             elif kind in ("hf", "accel"):
                 t = float(e.get("temperature", 1.0))
                 k = int(e.get("top_k") or 0) if kind == "hf" else 0
@@ -922,17 +976,8 @@ class DecodeSession(_Session):
                     raise ValueError("top_k must be >= 0 and top_p > 0")
                 if p < 1.0 and not 0 < k <= 1024:
                     raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
-                seed = 0
-                if e.get("exp_noise") is not None:
-                    noise = torch.as_tensor(e["exp_noise"]).to(self.gpt.device, torch.float32).contiguous()
-                    if tuple(noise.shape) != (cap, V):
-                        raise ValueError(f"exp_noise must be [cap, V] = {(cap, V)}")
-                elif e.get("seed") is not None:
-                    seed = _seed64(e["seed"])
-                else:
-                    seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # as generate() draws it
-                arr[i] = _lib.SamplingC(mode=1 if kind == "hf" else 2, temperature=t, top_k=k, top_p=p,
-                                        exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
+                noise, seed = _draws(e.get("exp_noise"), e.get("seed"), (cap, V), self.gpt.device, "[cap, V] = ")
+                arr[i] = _sampling_c(kind, t, k, p, noise, seed)
             else:
                 raise ValueError("sampler must be 'greedy', 'hf' or 'accel'")
             noises.append(noise)
@@ -954,36 +999,80 @@ class DecodeSession(_Session):
         and without a prefix may share a call; an admission too large for the prefill area is split into groups that fit.  The row's
         codes equal row 0 of generate(input_ids=[fake | prefix], prefix_layout="resume") on `slots` copies of the prompt, with
         exp_noise rows offset by k.  A prefix that holds the stop token, or with k >= cap, raises and nothing changes."""
-        if len(inputs_embeds_rows) == 0:
+        n = len(inputs_embeds_rows)
+        if n == 0:
             return []
-        if prefix is not None or prefix_logprobs is not None:
-            return self._admit_prefix(inputs_embeds_rows, max_new_each, sampling, takes, slots, prefix, prefix_logprobs)
-        if takes is not None:
-            return self._admit_takes(inputs_embeds_rows, max_new_each, sampling, takes, slots)
-        free = self.free_slots
-        rows, plen, caps = self._stage(inputs_embeds_rows, max_new_each, free)
-        n = len(rows)
+        nested, prefixed = takes is not None, prefix is not None or prefix_logprobs is not None
+        if prefixed and not self.prefix:
+            raise ValueError("prefix= needs a session created with prefix=True (IDXTTS_SESSION_PREFIX sizes the prefill area for it)")
+        if prefixed and prefix is None:
+            raise ValueError("prefix_logprobs without prefix")
+        pf = [None] * n if prefix is None else list(prefix)
+        lp = [None] * n if prefix_logprobs is None else list(prefix_logprobs)
+        if len(pf) != n or len(lp) != n:
+            raise ValueError("prefix / prefix_logprobs: one entry (a 1-D sequence or None) per request")
+        tk = [1] * n if takes is None else [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
+        if len(tk) != n or any(t < 1 for t in tk):
+            raise ValueError("takes: one count >= 1 per row (or one int for every row)")
         if sampling is not None and not self.sampled:
             raise ValueError("sampling= needs a session created with sampled=True")
-        ids = self._pick(slots, n, free)
+        if prefix_logprobs is not None and not self.scores:
+            raise ValueError("prefix_logprobs= needs a session created with scores=True")
+        T = sum(tk)
+        free = self.free_slots
+        if T > len(free) and slots is None:
+            raise RuntimeError(f"{T} {'takes' if nested and not prefixed else 'rows'} but {len(free)} free slots")
+        ids = self._pick(slots, T, free)
+        caps_t = [int(c) for c in self._per_take(max_new_each if not isinstance(max_new_each, np.integer) else int(max_new_each), tk,
+                                                 "max_new_each")]
+        rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
+        if any(not 1 <= c <= self.max_new for c in caps_t):
+            raise ValueError(f"caps must be in 1 .. {self.max_new}")
+        V, stop = self.gpt.cfg.number_mel_codes, self.gpt.cfg.stop_mel_token
+        first = [0]      # request b's takes: ids / caps_t / samplers [first[b] : first[b + 1]]
+        for t in tk:
+            first.append(first[-1] + t)
+        codes, lps = [], []
+        for b in range(n):
+            c = torch.zeros(0, dtype=torch.long) if pf[b] is None else torch.as_tensor(pf[b]).detach().to("cpu", torch.long)
+            if c.dim() != 1:
+                raise ValueError("prefix: a 1-D sequence of mel codes (or None) per request")
+            k = int(c.numel())
+            if k and (int(c.min()) < 0 or int(c.max()) >= V):
+                raise ValueError(f"prefix: mel codes are 0 .. {V - 1}")
+            if k and bool((c == stop).any()):
+                raise ValueError("prefix contains the stop token: nothing follows a stop token")
+            caps_b = caps_t[first[b]:first[b + 1]]
+            if any(k >= cap for cap in caps_b):
+                raise ValueError(f"prefix of {k} codes but a cap of {min(caps_b)}: the cap counts prefix + new codes (k < cap)")
+            l = torch.zeros(k) if lp[b] is None else torch.as_tensor(lp[b]).detach().to("cpu", torch.float32)
+            if tuple(l.shape) != (k,):
+                raise ValueError("prefix_logprobs: one value per prefix code")
+            codes.append(c)
+            lps.append(l)
+        klen = [int(c.numel()) for c in codes]
+        # the library gets what each caller form has always given it: takes NULL for plain rows, samplers NULL for greedy ones, prefix
+        # lengths of zero (which it drops) and no codes where there is no prefix; one group unless prefixes outgrow the prefill area
         self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))      # the rows may come from another stream
         with torch.cuda.stream(self.stream):
-            samplers, noises = self._samplers(sampling, caps) if sampling is not None else (None, [None] * n)
-            emb, pm = self._embed_rows(rows, plen)
-            h_p, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, ids, caps))
-            if samplers is None:
-                _lib.check(self._lib.idxtts_gpt_session_admit(
-                    self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
-                    h_caps.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
-            else:
-                _lib.check(self._lib.idxtts_gpt_session_admit_sampled(
-                    self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
-                    h_caps.ctypes.data_as(c_void_p), ctypes.cast(samplers, c_void_p), _lib.ptr(self._ws), self._sp()))
-        for i, nz in zip(ids, noises):
-            self._busy[i] = True
-            if nz is not None:
-                self._noise[i] = nz
-        return ids
+            samplers, noises = (self._samplers(self._per_take(sampling, tk, "sampling"), caps_t) if sampling is not None
+                                else (None, [None] * T))
+            for g in self._prefix_groups(plen, klen, self._prefill_area()):
+                t0, t1 = first[g[0]], first[g[-1] + 1]
+                emb, pm = self._embed_rows([rows[b] for b in g], [plen[b] for b in g])
+                kg = sum(klen[b] for b in g)
+                pk = torch.cat([codes[b] for b in g]).to(self.gpt.device) if kg else None
+                pl = torch.cat([lps[b] for b in g]).to(self.gpt.device) if kg and self.scores else None
+                h_p, h_t, h_ids, h_caps, h_k = (np.ascontiguousarray(a, dtype=np.int32) for a in (
+                    [plen[b] for b in g], [tk[b] for b in g], ids[t0:t1], caps_t[t0:t1], [klen[b] for b in g]))
+                _lib.check(self._lib.idxtts_gpt_session_admit_prefix(
+                    self.gpt._h, len(g), _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p),
+                    h_t.ctypes.data_as(c_void_p) if nested or prefixed else c_void_p(0), h_ids.ctypes.data_as(c_void_p),
+                    h_caps.ctypes.data_as(c_void_p),
+                    c_void_p(ctypes.addressof(samplers) + t0 * ctypes.sizeof(_lib.SamplingC)) if samplers is not None else c_void_p(0),
+                    h_k.ctypes.data_as(c_void_p), _lib.ptr(pk), _lib.ptr(pl), _lib.ptr(self._ws), self._sp()))
+                self._occupy(ids[t0:t1], noises[t0:t1])
+        return [ids[first[b]:first[b + 1]] for b in range(n)] if nested else ids
 
     def _pick(self, slots, n: int, free: list) -> list:
         """The n slots an admission takes: the first free ones, or the caller's choice (free, distinct)."""
@@ -1014,42 +1103,6 @@ class DecodeSession(_Session):
                 flat.extend([v] * t)
         return flat
 
-    def _admit_takes(self, inputs_embeds_rows, max_new_each, sampling, takes, slots) -> list:
-        n = len(inputs_embeds_rows)
-        tk = [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
-        if len(tk) != n or any(t < 1 for t in tk):
-            raise ValueError("takes: one count >= 1 per row (or one int for every row)")
-        if sampling is not None and not self.sampled:
-            raise ValueError("sampling= needs a session created with sampled=True")
-        T = sum(tk)
-        free = self.free_slots
-        if T > len(free) and slots is None:
-            raise RuntimeError(f"{T} takes but {len(free)} free slots")
-        ids = self._pick(slots, T, free)
-        caps_t = [int(c) for c in self._per_take(max_new_each, tk, "max_new_each")]
-        rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
-        if any(not 1 <= c <= self.max_new for c in caps_t):
-            raise ValueError(f"caps must be in 1 .. {self.max_new}")
-        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
-        with torch.cuda.stream(self.stream):
-            samplers, noises = (self._samplers(self._per_take(sampling, tk, "sampling"), caps_t) if sampling is not None
-                                else (None, [None] * T))
-            emb, pm = self._embed_rows(rows, plen)
-            h_p, h_t, h_ids, h_caps = (np.ascontiguousarray(a, dtype=np.int32) for a in (plen, tk, ids, caps_t))
-            _lib.check(self._lib.idxtts_gpt_session_admit_takes(
-                self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_t.ctypes.data_as(c_void_p),
-                h_ids.ctypes.data_as(c_void_p), h_caps.ctypes.data_as(c_void_p),
-                ctypes.cast(samplers, c_void_p) if samplers is not None else c_void_p(0), _lib.ptr(self._ws), self._sp()))
-        for i, nz in zip(ids, noises):
-            self._busy[i] = True
-            if nz is not None:
-                self._noise[i] = nz
-        out, o = [], 0
-        for t in tk:
-            out.append(ids[o:o + t])
-            o += t
-        return out
-
     def _prefill_area(self) -> int:
         """Positions of the admission's prefill area (gpt.h session_prefill_rows)."""
         area = self.slots * (self.max_prompt + 1) + 256
@@ -1072,80 +1125,6 @@ class DecodeSession(_Session):
             groups.append(cur)
         return groups
 
-    def _admit_prefix(self, inputs_embeds_rows, max_new_each, sampling, takes, slots, prefix, prefix_logprobs) -> list:
-        n = len(inputs_embeds_rows)
-        if not self.prefix:
-            raise ValueError("prefix= needs a session created with prefix=True (IDXTTS_SESSION_PREFIX sizes the prefill area for it)")
-        if prefix is None:
-            raise ValueError("prefix_logprobs without prefix")
-        pf = list(prefix)
-        lp = [None] * n if prefix_logprobs is None else list(prefix_logprobs)
-        if len(pf) != n or len(lp) != n:
-            raise ValueError("prefix / prefix_logprobs: one entry (a 1-D sequence or None) per request")
-        nested = takes is not None
-        tk = [1] * n if takes is None else [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
-        if len(tk) != n or any(t < 1 for t in tk):
-            raise ValueError("takes: one count >= 1 per row (or one int for every row)")
-        if sampling is not None and not self.sampled:
-            raise ValueError("sampling= needs a session created with sampled=True")
-        if prefix_logprobs is not None and not self.scores:
-            raise ValueError("prefix_logprobs= needs a session created with scores=True")
-        T = sum(tk)
-        free = self.free_slots
-        if T > len(free) and slots is None:
-            raise RuntimeError(f"{T} rows but {len(free)} free slots")
-        ids = self._pick(slots, T, free)
-        caps_t = [int(c) for c in self._per_take(max_new_each if not isinstance(max_new_each, np.integer) else int(max_new_each), tk,
-                                                 "max_new_each")]
-        rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
-        if any(not 1 <= c <= self.max_new for c in caps_t):
-            raise ValueError(f"caps must be in 1 .. {self.max_new}")
-        V, stop = self.gpt.cfg.number_mel_codes, self.gpt.cfg.stop_mel_token
-        codes, lps, o = [], [], 0
-        for b in range(n):
-            c = torch.zeros(0, dtype=torch.long) if pf[b] is None else torch.as_tensor(pf[b]).detach().to("cpu", torch.long)
-            if c.dim() != 1:
-                raise ValueError("prefix: a 1-D sequence of mel codes (or None) per request")
-            k = int(c.numel())
-            if k and (int(c.min()) < 0 or int(c.max()) >= V):
-                raise ValueError(f"prefix: mel codes are 0 .. {V - 1}")
-            if k and bool((c == stop).any()):
-                raise ValueError("prefix contains the stop token: nothing follows a stop token")
-            if any(k >= cap for cap in caps_t[o:o + tk[b]]):
-                raise ValueError(f"prefix of {k} codes but a cap of {min(caps_t[o:o + tk[b]])}: the cap counts prefix + new codes (k < cap)")
-            l = torch.zeros(k) if lp[b] is None else torch.as_tensor(lp[b]).detach().to("cpu", torch.float32)
-            if tuple(l.shape) != (k,):
-                raise ValueError("prefix_logprobs: one value per prefix code")
-            codes.append(c)
-            lps.append(l)
-            o += tk[b]
-        groups = self._prefix_groups(plen, [int(c.numel()) for c in codes], self._prefill_area())
-        first = [0]
-        for t in tk:
-            first.append(first[-1] + t)
-        self.stream.wait_stream(torch.cuda.current_stream(self.gpt.device))
-        with torch.cuda.stream(self.stream):
-            samplers, noises = (self._samplers(self._per_take(sampling, tk, "sampling"), caps_t) if sampling is not None
-                                else (None, [None] * T))
-            for g in groups:
-                t0, t1 = first[g[0]], first[g[-1] + 1]
-                emb, pm = self._embed_rows([rows[b] for b in g], [plen[b] for b in g])
-                pk = torch.cat([codes[b] for b in g]).to(self.gpt.device)
-                pl = torch.cat([lps[b] for b in g]).to(self.gpt.device) if self.scores else None
-                h_p, h_t, h_ids, h_caps, h_k = (np.ascontiguousarray(a, dtype=np.int32) for a in (
-                    [plen[b] for b in g], [tk[b] for b in g], ids[t0:t1], caps_t[t0:t1], [int(codes[b].numel()) for b in g]))
-                sp = c_void_p(ctypes.addressof(samplers) + t0 * ctypes.sizeof(_lib.SamplingC)) if samplers is not None else c_void_p(0)
-                _lib.check(self._lib.idxtts_gpt_session_admit_prefix(
-                    self.gpt._h, len(g), _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_t.ctypes.data_as(c_void_p),
-                    h_ids.ctypes.data_as(c_void_p), h_caps.ctypes.data_as(c_void_p), sp, h_k.ctypes.data_as(c_void_p),
-                    _lib.ptr(pk) if pk.numel() else c_void_p(0), _lib.ptr(pl) if pl is not None and pl.numel() else c_void_p(0),
-                    _lib.ptr(self._ws), self._sp()))
-                for i, nz in zip(ids[t0:t1], noises[t0:t1]):
-                    self._busy[i] = True
-                    if nz is not None:
-                        self._noise[i] = nz
-        return [ids[first[b]:first[b + 1]] for b in range(n)] if nested else ids
-
     def fork(self, slot: int, samplers=None, at=None, caps=None, n=None, slots=None) -> list:
         """Further takes of the request in `slot`, branching where it stood after `at` codes (default: where it stands now): one per
         entry of `samplers` (dicts as in admit(sampling=...); exp_noise [cap, V], rows below `at` are never read), or `n` greedy takes
@@ -1155,9 +1134,7 @@ class DecodeSession(_Session):
         and cap (caps: one per take or one int; default the source's, or the row count of a take's exp_noise).  A take forked at k with explicit draws that equal the source's
         below k returns, bit for bit, the codes of a fresh admission with those draws; a seeded take draws from its own seed from step
         k on.  at = 0 redraws the first token too (not on a row that came in through resume()).  A refusal raises, nothing changes."""
-        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots or not self._busy[int(slot)]:
-            raise ValueError(f"{slot!r} holds no request (slot ids 0 .. {self.slots - 1})")
-        slot = int(slot)
+        slot = self._held(slot)
         if samplers is not None and not self.sampled:
             raise ValueError("samplers= needs a session created with sampled=True")
         if samplers is None:
@@ -1187,10 +1164,7 @@ class DecodeSession(_Session):
                 self.gpt._h, slot, -1 if at is None else int(at), k, h_ids.ctypes.data_as(c_void_p),
                 ctypes.cast(arr, c_void_p) if arr is not None else c_void_p(0),
                 h_caps.ctypes.data_as(c_void_p) if h_caps is not None else c_void_p(0), _lib.ptr(self._ws), self._sp()))
-        for i, nz in zip(ids, noises):
-            self._busy[i] = True
-            if nz is not None:
-                self._noise[i] = nz
+        self._occupy(ids, noises)
         return ids
 
     def take(self, slot: int, scores: bool = False):
@@ -1206,24 +1180,8 @@ class DecodeSession(_Session):
         gather launch on the session's stream; bytes moved are proportional to the row's length.  resume() puts the row back, into any
         free slot of this session or of another one of the same shape, and it goes on to produce, bit for bit, the codes of its
         uninterrupted run.  A slot that is free, has finished (take() it) or is out of range raises, nothing changes."""
-        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots or not self._busy[int(slot)]:
-            raise ValueError(f"{slot!r} holds no request (slot ids 0 .. {self.slots - 1})")
-        slot = int(slot)
-        with torch.cuda.stream(self.stream):
-            need = int(self._lib.idxtts_gpt_session_park_bytes(self.gpt._h, slot, _lib.ptr(self._ws), self._sp()))
-            if need == 0:
-                _lib.check(1)
-            blob = torch.empty(need, dtype=torch.uint8, device=self.gpt.device)
-            written = ctypes.c_size_t(0)
-            _lib.check(self._lib.idxtts_gpt_session_park(self.gpt._h, slot, _lib.ptr(blob), need, ctypes.byref(written), _lib.ptr(self._ws),
-                                                         self._sp()))
-            hdr = _lib.ParkHeaderC.from_buffer_copy(blob[: ctypes.sizeof(_lib.ParkHeaderC)].cpu().numpy().tobytes())
-        assert written.value == need == hdr.bytes
-        self._busy[slot] = False
-        self._done.discard(slot)
-        nz = self._noise.pop(slot, None)      # the draws move with the row: alive while it is parked
-        if nz is not None:
-            nz.record_stream(self.stream)
+        blob, hdr, nz = self._take_out(self._held(slot), self._lib.idxtts_gpt_session_park_bytes, self._lib.idxtts_gpt_session_park,
+                                       _lib.ParkHeaderC)
         return ParkedRow(blob, hdr.step, hdr.max_step, nz, self.stream)
 
     def resume(self, parked: ParkedRow, slot=None) -> int:
@@ -1234,31 +1192,7 @@ class DecodeSession(_Session):
         reverse).  A refusal raises and changes nothing; a ParkedRow is resumed once."""
         if not isinstance(parked, ParkedRow) or isinstance(parked, ParkedGroup):
             raise TypeError("resume() takes a ParkedRow (a ParkedGroup goes to BeamDecodeSession.resume_group)")
-        parked._check()
-        if slot is None:
-            free = self.free_slots
-            if not free:
-                raise RuntimeError("no free slot")
-            slot = free[0]
-        if not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < self.slots:
-            raise ValueError(f"slot {slot!r} out of range (0 .. {self.slots - 1})")
-        slot = int(slot)
-        if self._busy[slot]:
-            raise ValueError(f"slot {slot} is not free")
-        if parked._blob.device != self.gpt.device:
-            with torch.cuda.stream(self.stream):
-                parked.to(self.gpt.device)
-        blob = parked._blob
-        self.stream.wait_stream(parked._stream)      # the row may have been written on another session's stream
-        with torch.cuda.stream(self.stream):
-            _lib.check(self._lib.idxtts_gpt_session_resume(self.gpt._h, slot, _lib.ptr(blob), blob.numel(), _lib.ptr(self._ws), self._sp()))
-        blob.record_stream(self.stream)
-        self._busy[slot] = True
-        if parked._noise is not None:
-            parked._noise.record_stream(self.stream)
-            self._noise[slot] = parked._noise
-        parked._blob = parked._noise = None
-        return slot
+        return self._put_back(parked, slot, self._lib.idxtts_gpt_session_resume)
 
 
 class BeamDecodeSession(_Session):
@@ -1322,15 +1256,7 @@ class BeamDecodeSession(_Session):
                 raise ValueError(f"beam: unknown keys {sorted(unknown)}")
             if e.get("early_stopping", False) not in (False, True):
                 raise NotImplementedError('early_stopping="never" is not implemented')
-            noise, seed = None, 0
-            if e.get("exp_noise") is not None:
-                noise = torch.as_tensor(e["exp_noise"]).to(self.gpt.device, torch.float32).contiguous()
-                if tuple(noise.shape) != (cap, nb * V):
-                    raise ValueError(f"exp_noise must be [cap, num_beams * V] = {(cap, nb * V)}")
-            elif e.get("seed") is not None:
-                seed = _seed64(e["seed"])
-            else:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())      # as generate_beam() draws it
+            noise, seed = _draws(e.get("exp_noise"), e.get("seed"), (cap, nb * V), self.gpt.device, "[cap, num_beams * V] = ")
             tp = e.get("top_p")
             arr[i] = _lib.BeamC(num_beams=nb, do_sample=int(bool(e.get("do_sample", True))), temperature=float(e.get("temperature", 1.0)),
                                 top_k=int(e.get("top_k", 50) or 0), top_p=float(tp if tp is not None else 1.0),
@@ -1360,10 +1286,7 @@ class BeamDecodeSession(_Session):
             _lib.check(self._lib.idxtts_gpt_session_admit_beam(
                 self.gpt._h, n, _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p), h_ids.ctypes.data_as(c_void_p),
                 h_caps.ctypes.data_as(c_void_p), ctypes.cast(beams, c_void_p), _lib.ptr(self._ws), self._sp()))
-        for g, nz in zip(ids, noises):
-            self._busy[g] = True
-            if nz is not None:
-                self._noise[g] = nz
+        self._occupy(ids, noises)
         return ids
 
     def take(self, group: int, n_best=None):
@@ -1383,9 +1306,7 @@ class BeamDecodeSession(_Session):
             _lib.check(self._lib.idxtts_gpt_session_read_nbest(self.gpt._h, int(group) * self._unit, n_best, _lib.ptr(out),
                                                                lens.ctypes.data_as(c_void_p), scores.ctypes.data_as(c_void_p),
                                                                _lib.ptr(self._ws), self._sp()))
-        self._busy[group] = False
-        self._done.discard(group)
-        self._noise.pop(group, None)
+        self._vacate(group, record=False)
         return [(out[q, : int(lens[q])], float(scores[q])) for q in range(n_best)]
 
     def park(self, group: int):
@@ -1401,24 +1322,8 @@ class BeamDecodeSession(_Session):
         One gather launch on the session's stream.  resume_group() puts it back, into any free group of this session or of another
         beam session of the same shape, and it goes on to produce, bit for bit, the codes of its uninterrupted run.  A group that is
         free, has finished (take() it) or is out of range raises, nothing changes."""
-        if not isinstance(group, (int, np.integer)) or not 0 <= int(group) < self.groups or not self._busy[int(group)]:
-            raise ValueError(f"{group!r} holds no request (group ids 0 .. {self.groups - 1})")
-        group = int(group)
-        with torch.cuda.stream(self.stream):
-            need = int(self._lib.idxtts_gpt_session_park_group_bytes(self.gpt._h, group, _lib.ptr(self._ws), self._sp()))
-            if need == 0:
-                _lib.check(1)
-            blob = torch.empty(need, dtype=torch.uint8, device=self.gpt.device)
-            written = ctypes.c_size_t(0)
-            _lib.check(self._lib.idxtts_gpt_session_park_group(self.gpt._h, group, _lib.ptr(blob), need, ctypes.byref(written),
-                                                               _lib.ptr(self._ws), self._sp()))
-            hdr = _lib.ParkGroupHeaderC.from_buffer_copy(blob[: ctypes.sizeof(_lib.ParkGroupHeaderC)].cpu().numpy().tobytes())
-        assert written.value == need == hdr.bytes
-        self._busy[group] = False
-        self._done.discard(group)
-        nz = self._noise.pop(group, None)      # the draws move with the group: alive while it is parked
-        if nz is not None:
-            nz.record_stream(self.stream)
+        blob, hdr, nz = self._take_out(self._held(group), self._lib.idxtts_gpt_session_park_group_bytes,
+                                       self._lib.idxtts_gpt_session_park_group, _lib.ParkGroupHeaderC)
         return ParkedGroup(blob, hdr, nz, self.stream)
 
     def resume_group(self, parked: ParkedGroup, group=None) -> int:
@@ -1429,29 +1334,4 @@ class BeamDecodeSession(_Session):
         a ParkedGroup is resumed once."""
         if not isinstance(parked, ParkedGroup):
             raise TypeError("resume_group() takes a ParkedGroup (a ParkedRow goes to DecodeSession.resume)")
-        parked._check()
-        if group is None:
-            free = self.free_groups
-            if not free:
-                raise RuntimeError("no free group")
-            group = free[0]
-        if not isinstance(group, (int, np.integer)) or not 0 <= int(group) < self.groups:
-            raise ValueError(f"group {group!r} out of range (0 .. {self.groups - 1})")
-        group = int(group)
-        if self._busy[group]:
-            raise ValueError(f"group {group} is not free")
-        if parked._blob.device != self.gpt.device:
-            with torch.cuda.stream(self.stream):
-                parked.to(self.gpt.device)
-        blob = parked._blob
-        self.stream.wait_stream(parked._stream)      # the group may have been written on another session's stream
-        with torch.cuda.stream(self.stream):
-            _lib.check(self._lib.idxtts_gpt_session_resume_group(self.gpt._h, group, _lib.ptr(blob), blob.numel(), _lib.ptr(self._ws),
-                                                                 self._sp()))
-        blob.record_stream(self.stream)
-        self._busy[group] = True
-        if parked._noise is not None:
-            parked._noise.record_stream(self.stream)
-            self._noise[group] = parked._noise
-        parked._blob = parked._noise = None
-        return group
+        return self._put_back(parked, group, self._lib.idxtts_gpt_session_resume_group)
