@@ -313,6 +313,39 @@ typedef struct idxtts_batch_invariant_plan {
 } idxtts_batch_invariant_plan;
 int idxtts_batch_invariant_plan_query(int N, int K, int rows, int format, int with_slab, int B, int heads, int smax, int n_keys,
                                       idxtts_batch_invariant_plan* out);
+/* Instrument (no reference counterpart; tests/test_decode_attn_gpu.py): the library's own KV-cache store and ONE step of its decode
+ * attention on caller-owned device buffers, so that a test knows every cached bit.  Two launches, then the stream is synchronised:
+ *   store   S > 0: positions [0, S) of the plain prefill rows qkv [n][S][3d] (d = 64 * heads) go to the caches in `kv_format` --
+ *           slot_ids NULL: kv_store_prefill, row b -> cache row b (n == rows); else kv_store_slots, positions [0, len[b]) of row b ->
+ *           the `fan` >= 1 consecutive cache rows from slot_ids[b] (slot_ids, len: device int32 [n]).  As in the product, the k / v
+ *           columns of qkv are rewritten to the cached values.  Cache sizes: kcache and vcache rows * heads * smax * 64 elements of
+ *           4 / 2 / 1 bytes (layouts: idxtts_gpt_set_kv_format; csrc/decode.h), kscale and vscale rows * heads * smax floats (fp8 only).
+ *   step    decode_attn_forward on step_qkv [rows][3d] with the arguments GPTModel::attn_args builds: one c_attn part, no bias, scale
+ *           0.125, kstart (device int32 [rows], never NULL), partial results and arrival counters sized as the GPT workspace sizes
+ *           them and the counters zero on entry.  slot_state NULL: every row at position `pos` (a DecodeState); else the session
+ *           form, slot_state = device int32 [rows][5], a SlotState {pos, mel_pos, step, max_step, live} per row.  invariant: the
+ *           batch-invariant kernels.  nsplit 0: the library's rule (decode_attn_nsplit, or decode_attn_inv_wgs under invariant),
+ *           1..16: that many workgroups per (row, head).  out: fp32 rows [rows][d], or with out_frag the A-fragment image
+ *           (ceil(rows / 16) * (d / 16) * 256 floats).  The step also writes the new token's k / v at its position.
+ * workspace: idxtts_decode_attn_probe_workspace_bytes(heads, rows) device bytes, 256-byte aligned; the arrival counters are its first
+ * rows * heads uint32 (0 after the call).  nsplit_used returns the workgroups per (row, head) the step was launched with. */
+typedef struct idxtts_decode_attn_probe {
+  int kv_format, heads, rows, smax;
+  int n, S;                                       /* the store (S = 0: none) */
+  float* qkv;
+  const int* slot_ids; const int* len; int fan;
+  void* kcache; void* vcache; float* kscale; float* vscale;
+  const float* step_qkv;                          /* the step */
+  int pos;
+  const int* kstart;
+  const int* slot_state;
+  int invariant, nsplit, out_frag;
+  float* out;
+  void* workspace; size_t workspace_bytes;
+  int nsplit_used;                                /* out */
+} idxtts_decode_attn_probe;
+size_t idxtts_decode_attn_probe_workspace_bytes(int heads, int rows);
+int idxtts_decode_attn_probe_run(idxtts_decode_attn_probe* p, void* stream);
 /* Greedy generations keep their instantiated decode-step hipGraph per (workspace address and size, B, prompt length, max_new_tokens,
  * penalty): the same shapes on the same workspace replay it without re-capturing (at most 8 are kept, least recently used first
  * out).  Returns how many are held (diagnostics / tests), -1 for a non-GPT context. */

@@ -1107,6 +1107,85 @@ int idxtts_batch_invariant_plan_query(int N, int K, int rows, int format, int wi
   API_END
 }
 
+// Instrument: kv_store_prefill / kv_store_slots and one decode_attn_forward step on caller-owned buffers (idxtts.h).  Workspace: the
+// arrival counters [rows * heads], the partial results [rows * heads][16][66] -- both as GPTModel::carve sizes them -- and a DecodeState
+static size_t probe_pad(size_t n) { return (n + 255) & ~(size_t)255; }
+size_t idxtts_decode_attn_probe_workspace_bytes(int heads, int rows) {
+  if (heads < 1 || rows < 1) return 0;
+  const size_t rh = (size_t)rows * heads;
+  return probe_pad(rh * sizeof(unsigned)) + probe_pad(rh * 16 * 66 * sizeof(float)) + probe_pad(sizeof(DecodeState));
+}
+
+int idxtts_decode_attn_probe_run(idxtts_decode_attn_probe* p, void* stream) {
+  API_BEGIN
+  IDX_CHECK(p, "null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int H = p->heads, B = p->rows, Smax = p->smax, d = 64 * H;
+  IDX_CHECK(H >= 1 && B >= 1 && B <= 64 && Smax >= 1, "heads >= 1, 1..64 rows, smax >= 1");
+  IDX_CHECK(p->kv_format >= 0 && p->kv_format <= 2, "KV format 0 / 1 / 2");
+  IDX_CHECK(p->kcache && p->vcache && (p->kv_format != 2 || (p->kscale && p->vscale)), "null cache pointer");
+  IDX_CHECK(p->workspace && ((uintptr_t)p->workspace & 255) == 0 && p->workspace_bytes >= idxtts_decode_attn_probe_workspace_bytes(H, B),
+            "workspace: idxtts_decode_attn_probe_workspace_bytes, 256-byte aligned");
+  if (p->kv_format == 2 && (fp8_check_device_decode(nullptr) || fp8_check_device_encode(nullptr))) return 1;
+  KvDst kv;
+  kv.kcache = p->kcache; kv.vcache = p->vcache; kv.fmt = p->kv_format;
+  if (p->kv_format == 2) { kv.kscale = p->kscale; kv.vscale = p->vscale; }
+  std::vector<int> host;      // every index the kernels will follow is checked here: the buffers are the caller's
+  auto fetch_ints = [&](const int* src, size_t n) {
+    host.resize(n);
+    return hipMemcpy(host.data(), src, n * sizeof(int), hipMemcpyDeviceToHost);
+  };
+  if (p->S > 0) {
+    IDX_CHECK(p->qkv && p->n >= 1 && p->S <= Smax, "store: qkv, n >= 1, S <= smax");
+    if (!p->slot_ids) {
+      IDX_CHECK(p->n == B, "kv_store_prefill fills every cache row: n == rows");
+      if (kv_store_prefill(p->qkv, kv, B, H, p->S, Smax, d, st)) return 1;
+    } else {
+      IDX_CHECK(p->len && p->fan >= 1, "kv_store_slots: len, fan >= 1");
+      IDX_HIP(fetch_ints(p->slot_ids, p->n));
+      for (int b = 0; b < p->n; ++b) IDX_CHECK(host[b] >= 0 && host[b] + p->fan <= B, "slot_ids: a slot outside the cache rows");
+      IDX_HIP(fetch_ints(p->len, p->n));
+      for (int b = 0; b < p->n; ++b) IDX_CHECK(host[b] >= 0 && host[b] <= p->S, "len: 0..S");
+      if (kv_store_slots(p->qkv, kv, p->n, H, p->S, Smax, d, p->slot_ids, p->len, st, p->fan)) return 1;
+    }
+  }
+  IDX_CHECK(p->step_qkv && p->out && p->kstart, "step: step_qkv, out, kstart");
+  IDX_HIP(fetch_ints(p->kstart, B));
+  const std::vector<int> ks = host;
+  if (p->slot_state) {
+    static_assert(sizeof(SlotState) == 5 * sizeof(int), "slot_state rows are SlotStates");
+    IDX_HIP(fetch_ints(p->slot_state, (size_t)B * 5));
+    for (int b = 0; b < B; ++b)
+      IDX_CHECK(!host[5 * b + 4] || (ks[b] >= 0 && ks[b] <= host[5 * b] && host[5 * b] < Smax), "a live slot needs 0 <= kstart <= pos < smax");
+  } else {
+    for (int b = 0; b < B; ++b) IDX_CHECK(ks[b] >= 0 && ks[b] <= p->pos && p->pos < Smax, "0 <= kstart <= pos < smax");
+  }
+  const size_t rh = (size_t)B * H;
+  char* ws = static_cast<char*>(p->workspace);
+  unsigned* cnt = reinterpret_cast<unsigned*>(ws);
+  float* part = reinterpret_cast<float*>(ws + probe_pad(rh * sizeof(unsigned)));
+  DecodeState* state = reinterpret_cast<DecodeState*>(ws + probe_pad(rh * sizeof(unsigned)) + probe_pad(rh * 16 * 66 * sizeof(float)));
+  IDX_HIP(hipMemsetAsync(cnt, 0, rh * sizeof(unsigned), st));
+  const DecodeState hs = {p->pos, 0, 0, 0u};
+  IDX_HIP(hipMemcpyAsync(state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+  DecodeAttnArgs da;      // GPTModel::attn_args
+  da.qkv_part = p->step_qkv; da.parts = 1; da.part_rows = B; da.qkv_bias = nullptr;
+  da.kcache = kv.kcache; da.vcache = kv.vcache; da.kv_fmt = kv.fmt; da.kscale = kv.kscale; da.vscale = kv.vscale; da.kstart = p->kstart;
+  da.st = state; da.B = B; da.H = H; da.Smax = Smax; da.d = d; da.scale = 0.125f;
+  da.nsplit = decode_attn_nsplit(B, H); da.part = part; da.cnt = cnt; da.slot = reinterpret_cast<const SlotState*>(p->slot_state);
+  if (p->invariant) { da.invariant = 1; da.nsplit = decode_attn_inv_wgs(B, H, Smax); }
+  if (p->nsplit) {
+    IDX_CHECK(p->nsplit >= 1 && p->nsplit <= 16, "nsplit: 0 (the rule) or 1..16");
+    da.nsplit = p->nsplit;
+  }
+  (p->out_frag ? da.out : da.out_row) = p->out;
+  p->nsplit_used = da.nsplit;
+  if (decode_attn_forward(da, st)) return 1;
+  IDX_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 int idxtts_gemv_pl_plan_query(int N, int K, int rows, int* ct, int* kparts, int* has_kernel) {
   API_BEGIN
   IDX_CHECK(ct && kparts && has_kernel && N > 0 && K > 0 && rows > 0 && rows <= 64, "N, K > 0, 1..64 rows");

@@ -21,7 +21,7 @@ SYMBOLS = [
     "idxtts_bigvgan_create", "idxtts_bigvgan_workspace_bytes", "idxtts_bigvgan_fwd", "idxtts_bigvgan_fwd_ragged",
     "idxtts_profile_enable", "idxtts_profile_num_kernels", "idxtts_profile_kernel_name", "idxtts_profile_read", "idxtts_profile_event_overhead",
     "idxtts_linear_create", "idxtts_linear_fwd", "idxtts_linear_destroy", "idxtts_release_stream", "idxtts_attention_fwd", "idxtts_attention_bf16x3_fwd", "idxtts_attention_bf16_fwd", "idxtts_attention_relkey_fwd", "idxtts_layernorm_fwd",
-    "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_set_batch_invariant", "idxtts_gpt_get_batch_invariant", "idxtts_batch_invariant_plan_query", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
+    "idxtts_gpt_create", "idxtts_gpt_quantize_weights", "idxtts_gpt_set_kv_format", "idxtts_gpt_get_kv_format", "idxtts_gpt_set_batch_invariant", "idxtts_gpt_get_batch_invariant", "idxtts_batch_invariant_plan_query", "idxtts_decode_attn_probe_workspace_bytes", "idxtts_decode_attn_probe_run", "idxtts_gpt_workspace_bytes", "idxtts_gpt_embed", "idxtts_gpt_generate", "idxtts_gpt_generate_forced", "idxtts_gpt_generate_sampled", "idxtts_gpt_latent",
     "idxtts_gpt_beam_workspace_bytes", "idxtts_gpt_generate_beam",
     "idxtts_gpt_session_workspace_bytes", "idxtts_gpt_session_init", "idxtts_gpt_session_admit", "idxtts_gpt_session_step",
     "idxtts_gpt_session_read", "idxtts_gpt_session_release", "idxtts_gpt_session_workspace_bytes_ex", "idxtts_gpt_session_init_ex",
@@ -163,6 +163,9 @@ def load() -> ctypes.CDLL:
     lib.idxtts_fp8_e4m3_encode.restype = ctypes.c_ubyte
     lib.idxtts_gpt_quantize_weights.argtypes = [c_void_p, c_int]
     lib.idxtts_kv_fp8_quantize.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_decode_attn_probe_workspace_bytes.argtypes = [c_int, c_int]
+    lib.idxtts_decode_attn_probe_workspace_bytes.restype = c_size_t
+    lib.idxtts_decode_attn_probe_run.argtypes = [c_void_p, c_void_p]
     lib.idxtts_gpt_set_kv_format.argtypes = [c_void_p, c_int]
     lib.idxtts_gpt_get_kv_format.argtypes = [c_void_p]
     lib.idxtts_gpt_set_batch_invariant.argtypes = [c_void_p, c_int]
@@ -501,6 +504,27 @@ def batch_invariant_plan(N: int, K: int, rows: int, fmt: int, with_slab: bool = 
     check(load().idxtts_batch_invariant_plan_query(int(N), int(K), int(rows), int(fmt), int(bool(with_slab)), int(B), int(heads), int(smax),
                                                    int(n_keys), ctypes.byref(out)))
     return {n: int(getattr(out, n)) for n, _ in BatchInvariantPlanC._fields_}
+
+
+class DecodeAttnProbeC(ctypes.Structure):          # idxtts_decode_attn_probe (include/idxtts.h)
+    _fields_ = ([(n, c_int) for n in ("kv_format", "heads", "rows", "smax", "n", "S")]
+                + [("qkv", c_void_p), ("slot_ids", c_void_p), ("len", c_void_p), ("fan", c_int)]
+                + [(n, c_void_p) for n in ("kcache", "vcache", "kscale", "vscale", "step_qkv")]
+                + [("pos", c_int), ("kstart", c_void_p), ("slot_state", c_void_p), ("invariant", c_int), ("nsplit", c_int), ("out_frag", c_int),
+                   ("out", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("nsplit_used", c_int)])
+
+
+def decode_attn_probe_workspace_bytes(heads: int, rows: int) -> int:
+    return int(load().idxtts_decode_attn_probe_workspace_bytes(int(heads), int(rows)))
+
+
+def decode_attn_probe(**fields) -> int:
+    """Instrument: the library's KV-cache store and one decode-attention step on the caller's device buffers (include/idxtts.h; the
+    fields of idxtts_decode_attn_probe, pointers as integers, unnamed ones 0 / NULL).  Returns nsplit_used."""
+    pointers = {n for n, t in DecodeAttnProbeC._fields_ if t is c_void_p}
+    p = DecodeAttnProbeC(**{k: (v or None) if k in pointers else v for k, v in fields.items()})
+    check(load().idxtts_decode_attn_probe_run(ctypes.byref(p), None))
+    return int(p.nsplit_used)
 
 
 def gemv_pl_plan(N: int, K: int, rows: int) -> dict:
