@@ -447,6 +447,32 @@ int idxtts_gpt_generate_prefix(idxtts_ctx* ctx, const float* inputs_embeds, cons
                                float repetition_penalty, const idxtts_sampling* sampling, const long long* prefix, int k, int prefix_pos0,
                                long long* codes, int* n_steps, float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes,
                                int use_graph, void* stream);
+/* ---- Scoring given codes ----
+ * The log-probabilities ("Scores") of codes the context did not just emit, from ONE prefill instead of one decode step per code.
+ * Row b has n_b >= 1 codes c_0 .. c_{n_b - 1}; the last may be stop_mel_token, no other may; all lie in [0, V).  Its prefill input is
+ *   [ prompt rows (P, left pad as pad_left says) | mel_emb[start] + mel_pos[0] | mel_emb[c_j] + mel_pos[prefix_pos0 + j], j = 0 .. n_b - 2 ]
+ * in the layouts of "Continuing from given codes": prefix_pos0 = 2 ("resume": where an uninterrupted run fed the codes) or 1 ("hf":
+ * what the reference's first forward with input_tokens embeds).  The rows go through the input kernels and the prefill of
+ * idxtts_gpt_generate_prefix unchanged (the GEMMs and the key / value rounding that prefill runs for the context's KV format; nothing is
+ * cached).  lp[b][j] is "Scores"'s formula on the raw logits of position P + j with tok = c_j, for j < n_b: position P (the start
+ * token) predicts c_0, position P + j (code c_{j-1}) predicts c_j.  lp[b][j] = 0 for n_b <= j < n.  Rows shorter than n = max n_b are
+ * right-padded with code 0's table rows; attention is causal, so the padding reaches no scored position.  No repetition penalty,
+ * temperature or warper applies, as in "Scores".
+ * Head: ln_f -> final_norm -> mel_head on the scored positions of all rows packed one behind the other, at most 64 at a time, through
+ * the decode step's GEMVs (chosen by each chunk's row count as a decode step of that many rows chooses them), each chunk reduced by
+ * one launch of 1024-thread workgroups, one per position, that sum as the samplers do.  The head weights are streamed
+ * ceil(sum_b n_b / 64) times per call.  In the batch-invariant mode the head runs that mode's GEMV at every row count, so a position's
+ * value does not depend on the chunk it falls into, nor on the other rows of the call.
+ * codes: device int64 [B][n] (columns from n_b on are not read); lens: HOST int32 [B], or NULL = every row n codes; logprobs: device
+ * fp32 [B][n]; logits_out: device fp32 [B][n][V] or NULL -- the raw logits of every scored position, 0 from n_b on.  1 <= B <= 64.
+ * Workspace: idxtts_gpt_score_workspace_bytes(ctx, B, P, n), for the context's KV format at the time of the call.
+ * Refused, before anything runs: a NULL ctx, inputs_embeds, codes, logprobs or workspace; B outside 1 .. 64, P < 1, n < 1; n_b < 1 or
+ * n_b > n; a pad_left outside [0, P); a code outside [0, V) ("a code outside the mel code table"); stop_mel_token before a row's last
+ * code ("a stop token before a row's last code"); prefix_pos0 other than 1 or 2; prefix_pos0 + n - 1 >= the mel position table's rows
+ * ("the codes exceed the mel position table"); a workspace smaller than the size above. */
+size_t idxtts_gpt_score_workspace_bytes(const idxtts_ctx* ctx, int B, int P, int n);
+int idxtts_gpt_score(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, const long long* codes, const int* lens,
+                     int n, int prefix_pos0, float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Beam search / beam-sample = what `IndexTTS2.infer` runs by default (infer_v2.py:714-722, 767: do_sample=True, num_beams=3,
  * top_p .8, top_k 30, temperature .8, repetition_penalty 10, length_penalty 0) through HF `_beam_search`
  * (transformers_generation_utils.py:3325-3516) + BeamSearchScorer (transformers_beam_search.py:123-420): log_softmax before
@@ -527,6 +553,11 @@ int idxtts_gpt_session_admit(idxtts_ctx* ctx, int n, const float* inputs_embeds,
  * for at least one row of max_prompt + 1 + max_new_tokens positions (without it: slots rows of max_prompt + 1) and adds two [slots]
  * int32 arrays behind everything else; every other flag combination keeps its size and layout.  Not for beam sessions. */
 #define IDXTTS_SESSION_PREFIX 8       /* (4 is not a flag: _workspace_bytes_ex returns 0 for it and _init_ex refuses it, as ever) */
+/* Sessions whose prefixed admissions can fill lp[0, k) from their own prefill (_admit_prefix_scored below): flags |=
+ * IDXTTS_SESSION_PREFIX_SCORES, valid only together with IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_SCORES (_workspace_bytes_ex returns 0 and
+ * _init_ex refuses it otherwise), adds the 64-row head buffers of "Scoring given codes" and a packed [slots * max_new_tokens] fp32
+ * staging buffer behind everything else; every other flag combination keeps its size and layout. */
+#define IDXTTS_SESSION_PREFIX_SCORES 16
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags);
 int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, float repetition_penalty, int flags,
                                void* workspace, size_t workspace_bytes, void* stream);
@@ -600,6 +631,20 @@ int idxtts_gpt_session_fork(idxtts_ctx* ctx, int src_slot, int at, int n, const 
 int idxtts_gpt_session_admit_prefix(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens, const int* takes,
                                     const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take, const int* prefix_lens,
                                     const long long* prefix, const float* prefix_logprobs, void* workspace, void* stream);
+/* _admit_prefix_scored: _admit_prefix with from_model, HOST unsigned char [n].  from_model[b] = 1: lp[0, k_b) of every take's slot is
+ * what "Scoring given codes" defines for the request's prefix in layout prefix_pos0 = 2 -- position P_b + j of the admission's own
+ * prefill row, which predicts prefix code j, goes through the scoring head (packed with the other such requests' positions, 64 at a
+ * time) into the session's staging buffer, which the slot reset then reads as it reads prefix_logprobs; request b's segment of
+ * prefix_logprobs is not read.  from_model[b] = 0 keeps _admit_prefix's rule (the caller's values, or 0 with prefix_logprobs NULL).
+ * The codes drawn are those of _admit_prefix, bit for bit: the prefill, the reset's other outputs and the first-token pass are the
+ * same launches on the same data.  The values are those of idxtts_gpt_score on the same prompt and prefix wherever both prefills
+ * choose the same kernels; in the batch-invariant mode always, bit for bit.  _fork, _park and _resume carry them as any lp.
+ * Refused, before anything changes: a session without IDXTTS_SESSION_PREFIX_SCORES (the message names the flag); a NULL from_model or
+ * prefix_lens; and everything _admit_prefix refuses. */
+int idxtts_gpt_session_admit_prefix_scored(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                           const int* takes, const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take,
+                                           const int* prefix_lens, const long long* prefix, const float* prefix_logprobs,
+                                           const unsigned char* from_model, void* workspace, void* stream);
 /* Beam sessions (beam search / beam-sample per request, idxtts_gpt_generate_beam's semantics): the `slots` rows form slots / num_beams
  * groups of num_beams consecutive slots (2 <= num_beams <= 8, slots % num_beams == 0, slots <= 64); each admitted request takes one
  * group and runs HF _beam_search + BeamSearchScorer with its own idxtts_beam.  A group retires when its scorer is done

@@ -484,6 +484,21 @@ int idxtts_gpt_generate_forced_scored(idxtts_ctx* ctx, const float* inputs_embed
   API_END
 }
 
+size_t idxtts_gpt_score_workspace_bytes(const idxtts_ctx* ctx, int B, int P, int n) {
+  if (!ctx || B <= 0 || B > 64 || P <= 0 || n <= 0 || !ctx->finalized) return 0;
+  auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
+  return m ? m->score_workspace_bytes(B, P, n) : 0;
+}
+
+int idxtts_gpt_score(idxtts_ctx* ctx, const float* inputs_embeds, const int* pad_left, int B, int P, const long long* codes, const int* lens,
+                     int n, int prefix_pos0, float* logprobs, float* logits_out, void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  return m->score(inputs_embeds, pad_left, B, P, codes, lens, n, prefix_pos0, logprobs, logits_out, workspace, workspace_bytes,
+                  static_cast<hipStream_t>(stream));
+  API_END
+}
+
 size_t idxtts_gpt_beam_workspace_bytes(const idxtts_ctx* ctx, int B, int num_beams, int S, int max_new_tokens) {
   if (!ctx || !ctx->finalized || B <= 0 || num_beams < 2 || S <= 0 || max_new_tokens <= 0) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
@@ -534,6 +549,7 @@ static GPTModel::SessionShape session_shape(int slots, int max_prompt, int max_n
   GPTModel::SessionShape sh;
   sh.slots = slots; sh.max_prompt = max_prompt; sh.max_new = max_new_tokens; sh.num_beams = num_beams;
   sh.sampled = flags & IDXTTS_SESSION_SAMPLED; sh.scores = flags & IDXTTS_SESSION_SCORES; sh.prefix = flags & IDXTTS_SESSION_PREFIX;
+  sh.prefix_scores = flags & IDXTTS_SESSION_PREFIX_SCORES;
   return sh;
 }
 
@@ -548,7 +564,8 @@ int idxtts_gpt_session_init(idxtts_ctx* ctx, int slots, int max_prompt, int max_
 
 size_t idxtts_gpt_session_workspace_bytes_ex(const idxtts_ctx* ctx, int slots, int max_prompt, int max_new_tokens, int flags) {
   if (!ctx || !ctx->finalized || slots <= 0 || slots > 64 || max_prompt <= 0 || max_new_tokens <= 0) return 0;
-  if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)) return 0;
+  if (flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_PREFIX_SCORES)) return 0;
+  if ((flags & IDXTTS_SESSION_PREFIX_SCORES) && (~flags & (IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_SCORES))) return 0;
   auto* m = dynamic_cast<const GPTModel*>(ctx->model.get());
   return m ? m->session_workspace_bytes(session_shape(slots, max_prompt, max_new_tokens, flags, 0)) : 0;
 }
@@ -557,7 +574,7 @@ int idxtts_gpt_session_init_ex(idxtts_ctx* ctx, int slots, int max_prompt, int m
                                void* workspace, size_t workspace_bytes, void* stream) {
   API_BEGIN
   GPT_MODEL(ctx);
-  IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX)), "unknown session flags");
+  IDX_CHECK(!(flags & ~(IDXTTS_SESSION_SAMPLED | IDXTTS_SESSION_SCORES | IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_PREFIX_SCORES)), "unknown session flags");
   return m->session_init(workspace, workspace_bytes, session_shape(slots, max_prompt, max_new_tokens, flags, 0), repetition_penalty,
                          static_cast<hipStream_t>(stream));
   API_END
@@ -611,6 +628,20 @@ int idxtts_gpt_session_admit_prefix(idxtts_ctx* ctx, int n, const float* inputs_
   IDX_CHECK(prefix_lens, "null prefix_lens");
   GPTModel::Admission a = admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens);
   a.per_row = per_take; a.takes = takes; a.prefix_lens = prefix_lens; a.prefix = prefix; a.prefix_logprobs = prefix_logprobs;
+  return m->session_admit(workspace, a, static_cast<hipStream_t>(stream));
+  API_END
+}
+
+int idxtts_gpt_session_admit_prefix_scored(idxtts_ctx* ctx, int n, const float* inputs_embeds, int ld_rows, const int* prompt_lens,
+                                           const int* takes, const int* slot_ids, const int* max_new_tokens, const idxtts_sampling* per_take,
+                                           const int* prefix_lens, const long long* prefix, const float* prefix_logprobs,
+                                           const unsigned char* from_model, void* workspace, void* stream) {
+  API_BEGIN
+  GPT_MODEL(ctx);
+  IDX_CHECK(prefix_lens && from_model, "null prefix_lens or from_model");
+  GPTModel::Admission a = admission(n, inputs_embeds, ld_rows, prompt_lens, slot_ids, max_new_tokens);
+  a.per_row = per_take; a.takes = takes; a.prefix_lens = prefix_lens; a.prefix = prefix; a.prefix_logprobs = prefix_logprobs;
+  a.from_model = from_model;
   return m->session_admit(workspace, a, static_cast<hipStream_t>(stream));
   API_END
 }

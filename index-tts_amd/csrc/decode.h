@@ -107,6 +107,16 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream);
 // advances its own pos / mel_pos / step.
 int sample_slots_forward(const SampleArgs& a, SlotState* slots, const int* slot_ids, int n, hipStream_t stream);
 
+// Scoring given codes (idxtts.h): one 1024-thread workgroup per row of a logits slab [rows <= 64][V] (the head's output on `rows` packed
+// positions) writes out[dst[r]] = the "Scores" log-probability of code tok[r] under row r, or 0 without reading the row where tok[r] < 0.
+// tok / dst: device [rows]; dst[r] indexes `out`, which the caller has sized and whose other elements stay as they are.
+struct ScoreRowsArgs {
+  const float* logits = nullptr; int rows = 0, V = 0;
+  const int* tok = nullptr; const int* dst = nullptr;
+  float* out = nullptr;
+};
+int score_rows_forward(const ScoreRowsArgs& a, hipStream_t stream);
+
 // Multinomial sampling of the next token (HF _sample, transformers_generation_utils.py:3222-3250, with the warpers of
 // 1036-1044): repetition penalty -> / temperature -> top-k (ties at the threshold kept) -> top-p (ascending sort, softmax,
 // cumulative <= 1 - top_p removed, largest always kept) -> softmax -> torch.multinomial(probs, 1), which IS

@@ -670,6 +670,34 @@ int sample_greedy_forward(const SampleArgs& a, hipStream_t stream) {
   return 0;
 }
 
+// Scoring given codes (idxtts.h): workgroup r reduces row r of a logits slab [rows][V] to the log-probability of the row's given code
+// tok[r] and writes it to out[dst[r]] -- the samplers' geometry and their row_logprob, so a teacher-forced value is summed in the order
+// a sampler would have recorded it.  tok[r] < 0 marks a row that is not scored: 0 is written and the row's logits are not read.
+// Registers and occupancy (hipcc --offload-arch=gfx950 -save-temps): 30 VGPRs, 29 SGPRs, no scratch, 64 bytes of LDS; occupancy 8, so
+// the 1024-thread workgroup size alone bounds it at 2 workgroups per CU (the LP = true greedy sampler: 32 VGPRs, the same occupancy).
+__global__ __launch_bounds__(1024) void score_rows_kernel(const ScoreRowsArgs a) {
+  __shared__ float red[16];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int tok = a.tok[r];      // (workgroup-uniform)
+  float lp = 0.0f;
+  if (tok >= 0) {
+    SampleArgs p;
+    p.part = a.logits; p.parts = 1; p.part_rows = a.rows; p.V = a.V;
+    lp = row_logprob(p, r, min(tok, a.V - 1), tid, red);      // (inside the row whatever the caller holds: the host has checked)
+  }
+  if (tid == 0) a.out[a.dst[r]] = lp;
+}
+
+int score_rows_forward(const ScoreRowsArgs& a, hipStream_t stream) {
+  IDX_CHECK(a.logits && a.tok && a.dst && a.out, "null pointer");
+  IDX_CHECK(a.rows >= 1 && a.rows <= 64 && a.V >= 1, "score rows: 1 <= rows <= 64");
+  static const int cat = prof_register("score_rows_kernel");
+  ProfScope prof(cat, stream, 0.0, 4.0 * a.rows * (double)a.V);
+  hipLaunchKernelGGL(score_rows_kernel, dim3(a.rows), dim3(1024), 0, stream, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
 // -------------------------------------------------------------------------------------------------
 // Decode session (continuous batching): the greedy tail with per-slot state (SlotState, decode.h)
 

@@ -19,6 +19,8 @@
 
 namespace idxtts {
 
+struct Carver;      // model_util.h
+
 // beam search buffers after a decode workspace (gpt_beam.hip): B utterances (session: groups) x nb rows
 struct BeamBuffers {
   float *proc, *beam_scores;
@@ -99,6 +101,8 @@ struct GPTModel : ModelBase {
     float* logprobs = nullptr;                // scores (idxtts.h "Scores"): [B][codes_ld] beside `codes` -- a scored session's table in
                                               // its workspace, generate()'s caller's buffer -- or null: the samplers record none
     bool beam_tail = false;                   // the beam stages on `beam`: a beam session's (slots set) or generate_beam's
+    bool kv_scratch = false;                  // score(): kcache / vcache hold ONE layer, rewritten by every layer -- only the rounding of the
+                                              // keys and values in place (decode.h kv_store_prefill) is kept; an fp32 cache stores nothing
     BeamState beam;
   };
   // Instantiated decode-step graphs of greedy generations, keyed by everything the captured launches depend on (workspace
@@ -172,6 +176,29 @@ struct GPTModel : ModelBase {
   int generate_beam(const float* inputs_embeds, const int* pad_left_host, int B, int P, int max_new, float penalty, const idxtts_beam* beam,
                     long long* codes, int* n_steps_out, void* ws, size_t ws_bytes, int use_graph, hipStream_t st, int n_best = 1,
                     int* lens = nullptr, float* scores = nullptr);      // codes [B][n_best][max_new]; lens / scores: HOST [B][n_best]
+  // Scoring given codes (idxtts.h): one prefill over [prompt | start | codes], the head over the scored positions in chunks of at most
+  // SCORE_CHUNK packed rows, score_rows_kernel behind each chunk
+  static constexpr int SCORE_CHUNK = 64;
+  struct ScoreHead {                  // what score_positions works in
+    Buffers w;                        // head_logits' fields for SCORE_CHUNK rows (hd, hrow, logits, pl_slab); the rest the owner's
+    size_t hd_bytes = 0;
+    float* xs = nullptr;              // [SCORE_CHUNK][d] the chunk's hidden rows, packed
+    int *tok = nullptr, *dst = nullptr;      // [positions] each packed position's code and where its value goes
+  };
+  struct ScoreRun { const float* x; int rows; };      // consecutive hidden rows (device, d floats each) to be scored
+  struct ScoreBuffers {
+    Buffers w;                        // prefill activations for B * S rows
+    ScoreHead head;
+    long long* fed;                   // [B][n - 1] the codes the prefill feeds (padding: code 0)
+    size_t bytes;
+  };
+  ScoreHead carve_score_head(Carver& c, const Buffers& base, size_t positions) const;
+  int score_positions(const ScoreHead& h, const std::vector<ScoreRun>& runs, const std::vector<int>& tok, const std::vector<int>& dst, float* out,
+                      float* logits_out, hipStream_t st);
+  ScoreBuffers carve_score(void* ws, int B, int S) const;
+  size_t score_workspace_bytes(int B, int P, int n) const { return carve_score(nullptr, B, P + n).bytes; }
+  int score(const float* inputs_embeds, const int* pad_left_host, int B, int P, const long long* codes, const int* lens_host, int n, int pos0,
+            float* logprobs, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st);
   int latent(const float* emb, const int* pad_left_host, int B, int S, int mel_start, int M, float* latent_out, void* ws, size_t ws_bytes,
              hipStream_t st);
 
@@ -186,6 +213,8 @@ struct GPTModel : ModelBase {
     int num_beams = 0;                // beam sessions: slots / num_beams groups of num_beams consecutive slots, one request each
     bool scores = false;              // IDXTTS_SESSION_SCORES: [slots][max_new] log-probabilities behind everything else (w.logprobs)
     bool prefix = false;              // IDXTTS_SESSION_PREFIX: a prefill area that holds one row of max_prompt + 1 + max_new positions
+    bool prefix_scores = false;       // IDXTTS_SESSION_PREFIX_SCORES (with prefix and scores): the scoring head's buffers and the packed
+                                      // log-probability staging buffer behind everything else (SessionBuffers::score, lp_stage)
   };
   struct Session {      // host-side record, keyed by the workspace address (the caller owns the workspace)
     SessionShape shape; float penalty = 1.0f; int kv_fmt = 0, gemm_mode = 0;
@@ -207,6 +236,8 @@ struct GPTModel : ModelBase {
     float* x_last;                    // [slots][d] last valid prefill row of each admitted request (first-token head input)
     int *ids, *plen, *klen, *cap;     // admission staging: slot ids, prompt lengths (prefill rows: -1 = padding row), P + 1, caps
     int *pk, *poff;                   // IDXTTS_SESSION_PREFIX: [slots] prefix length of each admitted request and its offset in the packed codes
+    ScoreHead score;                  // IDXTTS_SESSION_PREFIX_SCORES: the admission prefill's scoring head ...
+    float* lp_stage = nullptr;        // ... and [slots * max_new] the admitted prefixes' log-probabilities, packed as the codes are
     SlotSampling* samp;               // [slots] per-slot samplers (sampled sessions only, else null)
     BeamBuffers bb;                   // beam sessions: proc, beam scores, next_tok, beam_idx, seq [slots][max_new], hypotheses per group
     SlotBeam* beam;                   // [groups] per-request beam parameters (beam sessions only, else null)
@@ -239,6 +270,7 @@ struct GPTModel : ModelBase {
     const int* prefix_lens = nullptr;           // HOST [n]: request b's prefill row holds P_b + 1 + prefix_lens[b] positions, the last
     const long long* prefix = nullptr;          // prefix_lens[b] of them its codes of this packed device array (one behind the other)
     const float* prefix_logprobs = nullptr;     // device fp32, packed likewise, or null: what _read_scored returns for those codes
+    const unsigned char* from_model = nullptr;  // HOST [n] (_admit_prefix_scored): 1 = request b's values come from this prefill instead
   };
   // The admission both session kinds share: a.n requests into the free units a.ids[] -- slots, or (fan > 1) groups of fan slots -- each
   // checked, `params` (the caller's checks and table upload) run, before any unit is taken; then one right-padded prefill, each row's

@@ -248,6 +248,8 @@ int GPTModel::layer_full(int li, const Buffers& w, int B, int S, const int* ksta
   if (store_kv && scatter) {      // decode-session admission: the rows go to their slots' cache regions
     if (kv_store_slots(w.qkv, kv_dst(li, w, scatter->slots), scatter->n, cfg.heads, S, w.Smax, d, scatter->slot_ids, scatter->len, st,
                        scatter->fan, scatter->first)) return 1;
+  } else if (store_kv && w.kv_scratch) {      // score(): the cache formats' rounding of k / v in place, the one-layer region rewritten
+    if (kv_fmt && kv_store_prefill(w.qkv, kv_dst(0, w, B), B, cfg.heads, S, w.Smax, d, st)) return 1;
   } else if (store_kv) {
     if (kv_store_prefill(w.qkv, kv_dst(li, w, B), B, cfg.heads, S, w.Smax, d, st)) return 1;
   }
@@ -697,6 +699,153 @@ int GPTModel::generate(const float* inputs_embeds, const int* pad_left_host, int
   return 0;
 }
 
+// ---- scoring given codes (idxtts.h; gpt.h) ----
+// The head's buffers for SCORE_CHUNK rows (Buffers fields head_logits uses) and the chunk's packed hidden rows, carved from c
+GPTModel::ScoreHead GPTModel::carve_score_head(Carver& c, const Buffers& base, size_t positions) const {
+  const int d = cfg.model_dim, V = cfg.number_mel_codes;
+  ScoreHead h;
+  h.w = base;
+  h.w.hd = c.take<float>(frag_image_floats(SCORE_CHUNK, d));
+  h.hd_bytes = frag_image_floats(SCORE_CHUNK, d) * sizeof(float);
+  h.w.hrow = c.take<float>((size_t)SCORE_CHUNK * d);
+  h.w.logits = c.take<float>((size_t)SCORE_CHUNK * V);
+  size_t slab = 64;      // the head's plan follows the chunk's row count: the largest slab any count asks for
+  for (int r = 1; r <= SCORE_CHUNK; ++r) slab = std::max(slab, gemv_pl_slab_floats(V, d, r));
+  h.w.pl_slab = c.take<float>(slab);
+  h.xs = c.take<float>((size_t)SCORE_CHUNK * d);
+  h.tok = c.take<int>(positions);
+  h.dst = c.take<int>(positions);
+  return h;
+}
+
+// ln_f -> final_norm -> mel_head -> score_rows_kernel over the hidden rows of `runs` (each `rows` consecutive rows of d floats), packed
+// one run behind the other and cut into chunks of SCORE_CHUNK: the head weights stream ceil(positions / SCORE_CHUNK) times.  Packed
+// position i is scored for code tok[i] and its value goes to out[dst[i]]; with logits_out its logits row goes to logits_out[dst[i]].
+// Each chunk takes the head's plan for its own row count, as a decode step of that many rows does.
+int GPTModel::score_positions(const ScoreHead& h, const std::vector<ScoreRun>& runs, const std::vector<int>& tok, const std::vector<int>& dst,
+                              float* out, float* logits_out, hipStream_t st) {
+  const int d = cfg.model_dim, V = cfg.number_mel_codes, T = (int)tok.size();
+  if (T == 0) return 0;
+  IDX_HIP(hipMemcpyAsync(h.tok, tok.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(h.dst, dst.data(), T * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemsetAsync(h.w.hd, 0, h.hd_bytes, st));      // padding rows of the head's fragment image
+  IDX_HIP(hipStreamSynchronize(st));                       // (the caller's vectors may go out of scope)
+  size_t run = 0; int used = 0;      // the next unpacked row: row `used` of runs[run]
+  for (int c0 = 0; c0 < T; c0 += SCORE_CHUNK) {
+    const int rows = std::min(SCORE_CHUNK, T - c0);
+    for (int r = 0; r < rows;) {
+      while (used == runs[run].rows) { ++run; used = 0; }
+      const int m = std::min(rows - r, runs[run].rows - used);
+      IDX_HIP(hipMemcpyAsync(h.xs + (size_t)r * d, runs[run].x + (size_t)used * d, (size_t)m * d * sizeof(float), hipMemcpyDeviceToDevice, st));
+      r += m; used += m;
+    }
+    if (head_logits(h.w, rows, h.xs, d, false, st)) return 1;
+    ScoreRowsArgs sr;
+    sr.logits = h.w.logits; sr.rows = rows; sr.V = V; sr.tok = h.tok + c0; sr.dst = h.dst + c0; sr.out = out;
+    if (score_rows_forward(sr, st)) return 1;
+    for (int r = 0; logits_out && r < rows;) {      // the slab rows out: one copy per run of consecutive destinations
+      int e = r + 1;
+      while (e < rows && dst[c0 + e] == dst[c0 + e - 1] + 1) ++e;
+      IDX_HIP(hipMemcpyAsync(logits_out + (size_t)dst[c0 + r] * V, h.w.logits + (size_t)r * V, (size_t)(e - r) * V * sizeof(float),
+                             hipMemcpyDeviceToDevice, st));
+      r = e;
+    }
+  }
+  return 0;
+}
+
+// Workspace of score(): carve()'s buffers for B * S prefill rows without a cache (max_new = 0), then the head's, the codes the prefill
+// feeds, and for a bf16 / fp8 KV format one layer of cache.
+GPTModel::ScoreBuffers GPTModel::carve_score(void* ws, int B, int S) const {
+  ScoreBuffers sb;
+  sb.w = carve(ws, B, S, 0);
+  Carver c(ws);
+  c.off = sb.w.bytes;
+  const size_t T = (size_t)B * (S > 1 ? S - 1 : 1);      // scored positions at most: n = S - P <= S - 1 a row
+  sb.head = carve_score_head(c, sb.w, T);
+  sb.fed = c.take<long long>(T);
+  sb.w.kv_scratch = true;
+  sb.w.Smax = (S + 3) & ~3;
+  if (kv_fmt) {
+    sb.w.kcache = c.take<char>(kv_layer_bytes(B, sb.w.Smax));
+    sb.w.vcache = c.take<char>(kv_layer_bytes(B, sb.w.Smax));
+  }
+  if (kv_fmt == 2) {
+    sb.w.kscale = c.take<float>(kv_layer_scales(B, sb.w.Smax));
+    sb.w.vscale = c.take<float>(kv_layer_scales(B, sb.w.Smax));
+  }
+  sb.bytes = (c.off + 255) & ~(size_t)255;
+  return sb;
+}
+
+// The prefill of generate() behind a prefix, on [prompt | start | c_0 .. c_{n-2}] (the same input kernels, layer_full as that prefill
+// runs it for the context's KV format, nothing cached); then every scored position P + j, j < n_b, through score_positions.
+int GPTModel::score(const float* inputs_embeds, const int* pad_left_host, int B, int P, const long long* codes, const int* lens_host, int n,
+                    int pos0, float* logprobs, float* logits_out, void* ws, size_t ws_bytes, hipStream_t st) {
+  const int d = cfg.model_dim, V = cfg.number_mel_codes;
+  IDX_CHECK(inputs_embeds && codes && logprobs, "null pointer");
+  IDX_CHECK(B >= 1 && B <= 64 && P > 0 && n >= 1, "shape (1 <= B <= 64, n >= 1)");
+  IDX_CHECK(pos0 == 1 || pos0 == 2, "prefix_pos0: 1 (the reference's layout) or 2 (the uninterrupted run's)");
+  IDX_CHECK((long long)pos0 + n - 1 < cfg.mel_pos_len, "the codes exceed the mel position table");
+  const int S = P + n, k = n - 1;
+  IDX_CHECK(ws && ws_bytes >= score_workspace_bytes(B, P, n), "workspace too small");
+  std::vector<int> len(B, n), kstart(B, 0);
+  for (int b = 0; b < B; ++b) {
+    if (lens_host) len[b] = lens_host[b];
+    IDX_CHECK(len[b] >= 1 && len[b] <= n, "lens: 1 <= n_b <= n");
+    if (pad_left_host) kstart[b] = pad_left_host[b];
+    IDX_CHECK(kstart[b] >= 0 && kstart[b] < P, "pad_left out of range");
+  }
+  GenScope gen_scope(this);
+  std::vector<long long> hc((size_t)B * n);
+  IDX_HIP(hipMemcpyAsync(hc.data(), codes, hc.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
+  IDX_HIP(hipStreamSynchronize(st));
+  ScoreBuffers sb = carve_score(ws, B, S);
+  const Buffers& w = sb.w;
+  std::vector<long long> fed((size_t)B * std::max(k, 1), 0);      // padding: code 0, a valid table row
+  std::vector<int> tok, dst;
+  std::vector<ScoreRun> runs;
+  for (int b = 0; b < B; ++b) {
+    for (int j = 0; j < len[b]; ++j) {
+      const long long c = hc[(size_t)b * n + j];
+      IDX_CHECK(c >= 0 && c < V, "codes: a code outside the mel code table");
+      IDX_CHECK(c != cfg.stop_mel_token || j == len[b] - 1, "codes: a stop token before a row's last code (nothing follows a stop token)");
+      if (j < len[b] - 1) fed[(size_t)b * k + j] = c;
+      tok.push_back((int)c);
+      dst.push_back(b * n + j);
+    }
+    runs.push_back(ScoreRun{w.x + ((size_t)b * S + P) * d, len[b]});      // row b's scored positions P .. P + n_b - 1
+  }
+
+  const std::vector<int> start(B, cfg.start_mel_token);
+  IDX_HIP(hipMemcpyAsync(w.kstart, kstart.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemcpyAsync(w.cur_tok, start.data(), B * sizeof(int), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemsetAsync(w.finished, 0, B * sizeof(int), st));
+  if (k > 0) IDX_HIP(hipMemcpyAsync(sb.fed, fed.data(), (size_t)B * k * sizeof(long long), hipMemcpyHostToDevice, st));
+  IDX_HIP(hipMemsetAsync(w.pl_cnt, 0, (size_t)cdiv(std::max(V, 4 * d), 16) * sizeof(unsigned), st));      // the plane GEMV's arrival counters
+  IDX_HIP(hipMemsetAsync(logprobs, 0, (size_t)B * n * sizeof(float), st));      // lp[b][j] = 0 from n_b on
+  if (logits_out) IDX_HIP(hipMemsetAsync(logits_out, 0, (size_t)B * n * V * sizeof(float), st));
+  IDX_HIP(hipStreamSynchronize(st));      // the staging vectors are read by then
+
+  // ---- prefill: x = [inputs_embeds | mel_emb[start] + mel_pos[0] | mel_emb[c_j] + mel_pos[pos0 + j], j < n - 1] ----
+  IDX_HIP(hipMemcpy2DAsync(w.x, (size_t)S * d * sizeof(float), inputs_embeds, (size_t)P * d * sizeof(float), (size_t)P * d * sizeof(float), B,
+                           hipMemcpyDeviceToDevice, st));
+  GatherArgs ga;
+  ga.out = w.x + (size_t)P * d; ga.ld_out = S * d; ga.d = d;
+  ga.table[0] = mel_emb; ga.idx[0] = w.cur_tok;
+  ga.table[1] = mel_pos; ga.idx[1] = w.finished;      // all zeros -> mel position 0
+  if (gather_sum_rows(ga, B, st)) return 1;
+  if (k > 0) {
+    PrefixRows pr;
+    pr.x = w.x; pr.S = S; pr.d = d; pr.P_all = P; pr.k_all = k; pr.prefix = sb.fed; pr.pos0 = pos0;
+    pr.mel_emb = mel_emb; pr.mel_pos = mel_pos; pr.V = V;
+    if (prefix_input_rows(pr, B, k, st)) return 1;
+  }
+  for (int li = 0; li < cfg.layers; ++li)
+    if (layer_full(li, w, B, S, w.kstart, true, st)) return 1;
+  return score_positions(sb.head, runs, tok, dst, logprobs, logits_out, st);
+}
+
 // ---- decode session (continuous batching; gpt.h) ----
 // Workspace: the decode buffers of a `slots`-row generation with Smax = max_prompt + 1 + max_new (rounded to 4), whose prefill
 // activations are sized for an admission of up to every slot at max_prompt (+ 256 rows: see session_admit), then the per-slot state,
@@ -735,6 +884,10 @@ GPTModel::SessionBuffers GPTModel::carve_session(void* ws, const SessionShape& s
   if (shape.scores) sb.w.logprobs = c.take<float>((size_t)slots * max_new);      // (after everything else: flags 0 and 1 keep their layout)
   sb.pk = sb.poff = nullptr;
   if (shape.prefix) { sb.pk = c.take<int>(slots); sb.poff = c.take<int>(slots); }
+  if (shape.prefix_scores) {      // (behind everything else: every other flag combination keeps its size and layout)
+    sb.score = carve_score_head(c, sb.w, (size_t)slots * max_new);
+    sb.lp_stage = c.take<float>((size_t)slots * max_new);
+  }
   sb.bytes = (c.off + 255) & ~(size_t)255;
   return sb;
 }
@@ -752,6 +905,7 @@ int GPTModel::session_init(void* ws, size_t ws_bytes, const SessionShape& shape,
   IDX_CHECK(ws, "null workspace");
   IDX_CHECK(num_beams == 0 || !shape.prefix, "a beam session takes no prefix: the scorer's length penalty and rows would have to count it");
   IDX_CHECK(num_beams == 0 || !shape.scores, "a beam session records no per-code scores: its hypotheses carry the scorer's");
+  IDX_CHECK(!shape.prefix_scores || (shape.prefix && shape.scores), "IDXTTS_SESSION_PREFIX_SCORES needs IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_SCORES");
   IDX_CHECK(slots >= 1 && slots <= 64 && max_prompt >= 1 && max_new >= 1, "shape (1 <= slots <= 64)");
   IDX_CHECK(num_beams == 0 || (num_beams >= 2 && num_beams <= BEAM_MAX), "2 <= num_beams <= 8");
   IDX_CHECK(num_beams == 0 || slots % num_beams == 0, "slots must be a multiple of num_beams");
@@ -944,11 +1098,15 @@ int GPTModel::session_admit(void* ws, const Admission& adm, hipStream_t st) {
       IDX_CHECK(a.prefix_lens[b] >= 0 && a.prefix_lens[b] < s.shape.max_new, "prefix: k >= cap, the row would have no code left to produce (0 <= k < max_new_tokens)");
       ktot += a.prefix_lens[b];
     }
-  if (ktot == 0) { a.prefix_lens = nullptr; a.prefix = nullptr; a.prefix_logprobs = nullptr; }
+  IDX_CHECK(!a.from_model || s.shape.prefix_scores, "prefix log-probabilities from the model need a session initialised with "
+            "IDXTTS_SESSION_PREFIX_SCORES (with IDXTTS_SESSION_PREFIX | IDXTTS_SESSION_SCORES)");
+  IDX_CHECK(!a.from_model || a.prefix_lens, "null prefix_lens");
+  if (ktot == 0) { a.prefix_lens = nullptr; a.prefix = nullptr; a.prefix_logprobs = nullptr; a.from_model = nullptr; }
+  if (a.from_model && !std::any_of(a.from_model, a.from_model + n, [](unsigned char f) { return f != 0; })) a.from_model = nullptr;
+  std::vector<long long> hp((size_t)ktot);      // the packed prefix codes
   if (a.prefix_lens) {
     IDX_CHECK(s.shape.prefix, "a prefixed admission needs a session initialised with IDXTTS_SESSION_PREFIX (its prefill area holds prompt + prefix)");
     IDX_CHECK(a.prefix, "null prefix");
-    std::vector<long long> hp((size_t)ktot);
     IDX_HIP(hipMemcpyAsync(hp.data(), a.prefix, hp.size() * sizeof(long long), hipMemcpyDeviceToHost, st));
     IDX_HIP(hipStreamSynchronize(st));
     for (long long c : hp) {
@@ -973,6 +1131,27 @@ int GPTModel::session_admit(void* ws, const Admission& adm, hipStream_t st) {
     pr.slots = w.slots; pr.seen = w.seen; pr.V = V; pr.start_token = cfg.start_mel_token; pr.x_last = sb.x_last; pr.x = w.x; pr.S = S; pr.d = d;
     pr.slot_ids = sb.ids; pr.P = sb.plen; pr.cap = sb.cap; pr.row = take_row; pr.klen = sb.pk; pr.off = sb.poff; pr.prefix = a.prefix;
     pr.prefix_lp = a.prefix_logprobs; pr.codes = w.codes; pr.codes_ld = s.shape.max_new; pr.logprobs = w.logprobs;
+    if (a.from_model) {
+      // _admit_prefix_scored: position P_b + j of request b's prefill row predicts its prefix code j -- the rows of every from_model
+      // request through the scoring head into the staging buffer, packed as the codes are; the other requests' segments hold the
+      // caller's values (or 0), and the reset below hands the buffer to every take's slot as the caller's array is handed
+      std::vector<ScoreRun> runs;
+      std::vector<int> tok, dst;
+      for (int b = 0, o = 0; b < n; o += a.prefix_lens[b], ++b) {
+        const int kb = a.prefix_lens[b];
+        if (kb == 0) continue;
+        if (a.from_model[b]) {
+          runs.push_back(ScoreRun{w.x + ((size_t)b * S + prompt_lens[b]) * d, kb});
+          for (int j = 0; j < kb; ++j) { tok.push_back((int)hp[(size_t)o + j]); dst.push_back(o + j); }
+        } else if (a.prefix_logprobs) {
+          IDX_HIP(hipMemcpyAsync(sb.lp_stage + o, a.prefix_logprobs + o, kb * sizeof(float), hipMemcpyDeviceToDevice, st));
+        } else {
+          IDX_HIP(hipMemsetAsync(sb.lp_stage + o, 0, kb * sizeof(float), st));
+        }
+      }
+      if (score_positions(sb.score, runs, tok, dst, sb.lp_stage, nullptr, st)) return 1;
+      pr.prefix_lp = sb.lp_stage;
+    }
     if (session_reset_slots_prefix(pr, T, st)) return 1;
   } else if (session_reset_slots(w.slots, w.seen, V, cfg.start_mel_token, sb.x_last, w.x, S, d, sb.ids, sb.plen, sb.cap, T, st, take_row)) return 1;
   if (session_first_tokens(s, sb, T, st)) return 1;

@@ -33,6 +33,7 @@ SYMBOLS = [
     "idxtts_beam_finalize_host", "idxtts_gpt_generate_takes",
     "idxtts_gpt_generate_scored", "idxtts_gpt_generate_forced_scored", "idxtts_gpt_session_read_scored",
     "idxtts_gpt_generate_prefix", "idxtts_gpt_session_admit_prefix",
+    "idxtts_gpt_score_workspace_bytes", "idxtts_gpt_score", "idxtts_gpt_session_admit_prefix_scored",
     "idxtts_s2mel_create", "idxtts_s2mel_cond_workspace_bytes", "idxtts_s2mel_prepare_cond",
     "idxtts_s2mel_cfm_workspace_bytes", "idxtts_s2mel_cfm", "idxtts_set_gemm_mode", "idxtts_get_gemm_mode", "idxtts_set_acoustic_bf16", "idxtts_get_acoustic_bf16", "idxtts_set_decode_geometry", "idxtts_get_decode_geometry", "idxtts_set_decode_plane_rows", "idxtts_get_decode_plane_rows", "idxtts_gemv_fx_plan_query", "idxtts_gemv_pl_plan_query", "idxtts_s2mel_set_overlap", "idxtts_s2mel_get_overlap",
     "idxtts_s2mel_estimator", "idxtts_s2mel_cfm_rows_workspace_bytes", "idxtts_s2mel_cfm_rows", "idxtts_cfm_noise", "idxtts_s2mel_regulate", "idxtts_cond_create", "idxtts_cond_workspace_bytes", "idxtts_cond_forward", "idxtts_cond_forward_rows", "idxtts_emovec_merge",
@@ -227,8 +228,14 @@ def load() -> ctypes.CDLL:
                                                POINTER(c_int), c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
     lib.idxtts_gpt_generate_prefix.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int,
                                                c_int, c_void_p, POINTER(c_int), c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+    lib.idxtts_gpt_score_workspace_bytes.argtypes = [c_void_p, c_int, c_int, c_int]
+    lib.idxtts_gpt_score_workspace_bytes.restype = c_size_t
+    lib.idxtts_gpt_score.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]
     lib.idxtts_gpt_session_admit_prefix.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.idxtts_gpt_session_admit_prefix_scored.argtypes = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.idxtts_gpt_generate_forced_scored.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                                       POINTER(c_int), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     lib.idxtts_gpt_session_read_scored.argtypes = [c_void_p, c_int, c_void_p, c_void_p, POINTER(c_int), c_void_p, c_void_p]
@@ -401,6 +408,7 @@ FBANK_RAW, FBANK_CAMPPLUS, FBANK_W2VBERT = 0, 1, 2      # IDXTTS_FBANK_* (includ
 SESSION_SAMPLED = 1      # IDXTTS_SESSION_SAMPLED (include/idxtts.h)
 SESSION_SCORES = 2       # IDXTTS_SESSION_SCORES
 SESSION_PREFIX = 8       # IDXTTS_SESSION_PREFIX (4 is no flag)
+SESSION_PREFIX_SCORES = 16      # IDXTTS_SESSION_PREFIX_SCORES (only with SESSION_PREFIX | SESSION_SCORES)
 
 
 class StreamWorkspaces:

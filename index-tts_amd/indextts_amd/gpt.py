@@ -237,13 +237,15 @@ class UnifiedVoice:
 
     def decode_session(self, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0, do_sample: bool = False,
                        num_beams: int = 1, use_graph: bool = True, sampled: bool = False, scores: bool = False,
-                       prefix: bool = False) -> "DecodeSession":
+                       prefix: bool = False, prefix_scores: bool = False) -> "DecodeSession":
         """Continuous batching: `slots` decode rows, one KV region each, that requests enter and leave between steps
         (DecodeSession; `idxtts_gpt_session_*`).  A request's codes equal row 0 of generate() on `slots` copies of its prompt.
         sampled=True: every request samples with its own parameters and draws (DecodeSession.admit(..., sampling=...)).
         scores=True: every code's log-probability is recorded (take(slot, scores=True); include/idxtts.h "Scores").
         prefix=True: rows may be admitted behind given codes (DecodeSession.admit(..., prefix=...)); the session's prefill area then
-        holds at least one row of max_prompt + 1 + max_new positions."""
+        holds at least one row of max_prompt + 1 + max_new positions.
+        prefix_scores=True (with prefix=True and scores=True): admit(..., prefix_logprobs=[..., "model", ...]) lets the admission's own
+        prefill score a request's prefix (include/idxtts.h "Scoring given codes")."""
         if do_sample:
             raise ValueError("decode sessions sample per request, not session-wide: do_sample=True is not supported; the session is "
                              "greedy unless created with sampled=True and given per-request parameters (admit(..., sampling=...))")
@@ -251,7 +253,8 @@ class UnifiedVoice:
             if prefix:
                 raise ValueError("beams do not continue from given codes: prefix=True is for greedy and sampled sessions")
             raise ValueError("decode sessions are greedy or sampled per request: beam search runs in beam_session() (or generate_beam())")
-        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled, scores=scores, prefix=prefix)
+        return DecodeSession(self, slots, max_prompt, max_new, repetition_penalty, use_graph, sampled=sampled, scores=scores, prefix=prefix,
+                             prefix_scores=prefix_scores)
 
     def beam_session(self, slots: int, num_beams: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
                      use_graph: bool = True, scores: bool = False) -> "BeamDecodeSession":
@@ -382,6 +385,54 @@ class UnifiedVoice:
         if return_logprobs:
             res += (logprobs[:, : n.value].contiguous(),)
         return res if len(res) > 1 else out
+
+    def score_codes(self, codes, tts_embeddings: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, code_lens=None,
+                    layout: str = "resume", return_logits: bool = False):
+        """The model's log-probability of every code of GIVEN sequences, from one prefill (`idxtts_gpt_score`; include/idxtts.h "Scoring
+        given codes"): logprobs [B, n] fp32, what generate(return_logprobs=True) records for codes it emits itself, 0 from each row's
+        length on.  codes [B, n] (a tensor, or a list of 1-D sequences, right-padded here); code_lens [B]: the codes each row holds
+        (default: the list's lengths, else n).  A row's last code may be the stop token, no other.  tts_embeddings [B, P, d] and
+        attention_mask as generate() takes them.  layout "resume": code j at mel position j + 2, where the run that emitted the codes fed
+        them; "hf": at j + 1, the reference's first forward with input_tokens.  return_logits=True: (logprobs, logits [B, n, V]), the
+        raw logits of every scored position.  No repetition penalty, temperature or warper enters.  sequence_scores / rank_takes take
+        the result as they take a scored run's."""
+        if layout not in ("hf", "resume"):
+            raise ValueError("layout must be 'hf' or 'resume'")
+        emb = tts_embeddings.to(self.device, torch.float32).contiguous()
+        if emb.dim() != 3 or emb.shape[2] != self.cfg.model_dim:
+            raise ValueError("tts_embeddings must be [B, P, d]")
+        B, P, _ = emb.shape
+        if not isinstance(codes, torch.Tensor):
+            rows = [torch.as_tensor(np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r), dtype=torch.long).reshape(-1) for r in codes]
+            if code_lens is None:
+                code_lens = [int(r.numel()) for r in rows]
+            codes = torch.zeros(len(rows), max([int(r.numel()) for r in rows] + [1]), dtype=torch.long)
+            for i, r in enumerate(rows):
+                codes[i, : r.numel()] = r
+        if codes.dim() != 2 or codes.shape[0] != B or codes.shape[1] < 1:
+            raise ValueError("codes must be [B, n] with n >= 1, one row per prompt")
+        n = int(codes.shape[1])
+        lens = None
+        if code_lens is not None:
+            lens = np.ascontiguousarray(np.asarray(code_lens, dtype=np.int64).reshape(-1).astype(np.int32))
+            if lens.shape[0] != B:
+                raise ValueError("code_lens must hold one length per row")
+        pad_left = np.zeros(B, np.int32)
+        if attention_mask is not None:
+            pad_left = (attention_mask.detach().cpu().numpy()[:, :P] == 0).sum(1).astype(np.int32)
+        dc = codes.to(self.device, torch.long).contiguous()
+        V = self.cfg.number_mel_codes
+        logprobs = torch.empty(B, n, device=self.device, dtype=torch.float32)
+        logits = torch.empty(B, n, V, device=self.device, dtype=torch.float32) if return_logits else None
+        lib = _lib.load()
+        need = int(lib.idxtts_gpt_score_workspace_bytes(self._h, B, P, n))
+        if need == 0:
+            raise ValueError("score_codes: 1 <= B <= 64 rows of n >= 1 codes behind P >= 1 prompt positions")
+        ws = self._workspace_bytes(need)
+        _lib.check(lib.idxtts_gpt_score(self._h, _lib.ptr(emb), pad_left.ctypes.data_as(c_void_p), B, P, _lib.ptr(dc),
+                                        lens.ctypes.data_as(c_void_p) if lens is not None else c_void_p(0), n, 1 if layout == "hf" else 2,
+                                        _lib.ptr(logprobs), _lib.ptr(logits), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+        return (logprobs, logits) if return_logits else logprobs
 
     def _noise(self, exp_noise, generator, shape, seed: Optional[int] = None):
         """The Exp(1) draws of a sampled generation: (device tensor | None, seed).  An explicit `exp_noise`, or a torch `generator`
@@ -926,14 +977,19 @@ class DecodeSession(_Session):
     scores=True: the samplers also record every code's log-probability under the raw logits; take(slot, scores=True) returns them
     with the codes.  They follow a row through admit(takes=), fork (a take gets the source's first `at` values), park (the ParkedRow
     carries them, to("cpu") included) and resume (into a session that was also created with scores=True; the reverse is refused too),
-    and obey every determinism rule above, bit for bit.  The codes are those of a session without scores."""
+    and obey every determinism rule above, bit for bit.  The codes are those of a session without scores.
+
+    prefix_scores=True (needs prefix=True and scores=True): a request admitted behind given codes with prefix_logprobs "model" gets
+    the log-probabilities of those codes from its own admission prefill (`idxtts_gpt_session_admit_prefix_scored`)."""
 
     def __init__(self, gpt: UnifiedVoice, slots: int, max_prompt: int, max_new: int, repetition_penalty: float = 10.0,
-                 use_graph: bool = True, sampled: bool = False, scores: bool = False, prefix: bool = False):
-        self.sampled, self.scores, self.prefix = bool(sampled), bool(scores), bool(prefix)
+                 use_graph: bool = True, sampled: bool = False, scores: bool = False, prefix: bool = False, prefix_scores: bool = False):
+        self.sampled, self.scores, self.prefix, self.prefix_scores = bool(sampled), bool(scores), bool(prefix), bool(prefix_scores)
+        if self.prefix_scores and not (self.prefix and self.scores):
+            raise ValueError("prefix_scores=True needs prefix=True and scores=True (IDXTTS_SESSION_PREFIX_SCORES goes with both)")
         lib = _lib.load()
         flags = ((_lib.SESSION_SAMPLED if self.sampled else 0) | (_lib.SESSION_SCORES if self.scores else 0) |
-                 (_lib.SESSION_PREFIX if self.prefix else 0))
+                 (_lib.SESSION_PREFIX if self.prefix else 0) | (_lib.SESSION_PREFIX_SCORES if self.prefix_scores else 0))
         need = int(lib.idxtts_gpt_session_workspace_bytes_ex(gpt._h, int(slots), int(max_prompt), int(max_new), flags))
         if need == 0:
             raise ValueError(f"decode session shape (slots={slots}, max_prompt={max_prompt}, max_new={max_new}) not supported")
@@ -995,7 +1051,9 @@ class DecodeSession(_Session):
         them, as the row that produced them would have gone on (position layout "resume": code j at mel position j + 2).  The cap counts
         prefix + new codes (k < cap), the row's codes, take() and the draws (exp_noise [cap, V], rows below k never read; a seed's
         counter) are indexed by the absolute step, and a request's takes share its prefix and one prefill.  prefix_logprobs: one fp32
-        sequence of the same length, or None (= zeros), per request: what take(scores=True) returns for the prefix codes.  Rows with
+        sequence of the same length, None (= zeros) or the string "model", per request: what take(scores=True) returns for the prefix
+        codes.  "model" (a session created with prefix_scores=True): the admission's own prefill scores them, the values
+        UnifiedVoice.score_codes gives for prompt and prefix in layout "resume"; the codes drawn do not depend on it.  Rows with
         and without a prefix may share a call; an admission too large for the prefill area is split into groups that fit.  The row's
         codes equal row 0 of generate(input_ids=[fake | prefix], prefix_layout="resume") on `slots` copies of the prompt, with
         exp_noise rows offset by k.  A prefix that holds the stop token, or with k >= cap, raises and nothing changes."""
@@ -1009,6 +1067,13 @@ class DecodeSession(_Session):
             raise ValueError("prefix_logprobs without prefix")
         pf = [None] * n if prefix is None else list(prefix)
         lp = [None] * n if prefix_logprobs is None else list(prefix_logprobs)
+        model = [isinstance(v, str) for v in lp]
+        if any(m and v != "model" for m, v in zip(model, lp)):
+            raise ValueError('prefix_logprobs: a sequence, None or the string "model" per request')
+        if any(model) and not self.prefix_scores:
+            raise ValueError('prefix_logprobs="model" needs a session created with prefix_scores=True (IDXTTS_SESSION_PREFIX_SCORES adds the '
+                             "scoring head's buffers)")
+        lp = [None if m else v for m, v in zip(model, lp)]
         if len(pf) != n or len(lp) != n:
             raise ValueError("prefix / prefix_logprobs: one entry (a 1-D sequence or None) per request")
         tk = [1] * n if takes is None else [int(takes)] * n if isinstance(takes, (int, np.integer)) else [int(t) for t in takes]
@@ -1065,12 +1130,16 @@ class DecodeSession(_Session):
                 pl = torch.cat([lps[b] for b in g]).to(self.gpt.device) if kg and self.scores else None
                 h_p, h_t, h_ids, h_caps, h_k = (np.ascontiguousarray(a, dtype=np.int32) for a in (
                     [plen[b] for b in g], [tk[b] for b in g], ids[t0:t1], caps_t[t0:t1], [klen[b] for b in g]))
-                _lib.check(self._lib.idxtts_gpt_session_admit_prefix(
-                    self.gpt._h, len(g), _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p),
-                    h_t.ctypes.data_as(c_void_p) if nested or prefixed else c_void_p(0), h_ids.ctypes.data_as(c_void_p),
-                    h_caps.ctypes.data_as(c_void_p),
-                    c_void_p(ctypes.addressof(samplers) + t0 * ctypes.sizeof(_lib.SamplingC)) if samplers is not None else c_void_p(0),
-                    h_k.ctypes.data_as(c_void_p), _lib.ptr(pk), _lib.ptr(pl), _lib.ptr(self._ws), self._sp()))
+                args = (self.gpt._h, len(g), _lib.ptr(emb), pm, h_p.ctypes.data_as(c_void_p),
+                        h_t.ctypes.data_as(c_void_p) if nested or prefixed else c_void_p(0), h_ids.ctypes.data_as(c_void_p),
+                        h_caps.ctypes.data_as(c_void_p),
+                        c_void_p(ctypes.addressof(samplers) + t0 * ctypes.sizeof(_lib.SamplingC)) if samplers is not None else c_void_p(0),
+                        h_k.ctypes.data_as(c_void_p), _lib.ptr(pk), _lib.ptr(pl))
+                if any(model[b] for b in g):      # (no request asks the model: the entry of before)
+                    h_m = np.ascontiguousarray([model[b] for b in g], dtype=np.uint8)
+                    _lib.check(self._lib.idxtts_gpt_session_admit_prefix_scored(*args, h_m.ctypes.data_as(c_void_p), _lib.ptr(self._ws), self._sp()))
+                else:
+                    _lib.check(self._lib.idxtts_gpt_session_admit_prefix(*args, _lib.ptr(self._ws), self._sp()))
                 self._occupy(ids[t0:t1], noises[t0:t1])
         return [ids[first[b]:first[b + 1]] for b in range(n)] if nested else ids
 

@@ -341,6 +341,26 @@ class IndexTTS2:
             lps.append(hl[r, :n])
         return codes, rank_request(rows, lps, int(takes), self.stop_mel_token, length_penalty)
 
+    def score_takes(self, text_tokens: torch.Tensor, cond, codes, length_penalty: float = 1.0):
+        """Ranks GIVEN takes of one text and one conditioning: codes is a list of 1-D code sequences (each up to and including its stop
+        token, or cut at its cap), from any source -- an unscored session, another process, an exact-mode or fp8-KV context.  The prompt
+        is built as gpt_stage builds it; all takes are scored in one call of UnifiedVoice.score_codes (one prefill, layout "resume":
+        the values a scored run would have recorded).  Returns (logprobs: one fp32 CPU row per take, ranking): ranking lists the takes
+        best first as (take_index, score, stopped, n_codes), serving.rank_request's format for one utterance."""
+        from .serving import rank_request
+        text_tokens = torch.as_tensor(text_tokens)
+        if text_tokens.dim() != 2 or text_tokens.shape[0] != 1:
+            raise ValueError("score_takes: text_tokens must be [1, L], one text for all the takes")
+        rows = [torch.as_tensor(c).detach().to("cpu", torch.long).reshape(-1) for c in codes]
+        if not rows or any(r.numel() == 0 for r in rows):
+            raise ValueError("score_takes: at least one take, each with at least one code")
+        n = len(rows)
+        lat, emo = self._row_latents(rows_conditioning(cond, 1, self.device), 1)
+        _, emb, mask = self.gpt.prepare_gpt_inputs(self.gpt.conds_latent(lat, emo), text_tokens)
+        lp = self.gpt.score_codes(rows, emb.expand(n, -1, -1), attention_mask=mask.expand(n, -1)).cpu()
+        lps = [lp[i, : rows[i].numel()] for i in range(n)]
+        return lps, rank_request(rows, lps, n, self.stop_mel_token, length_penalty)[0]
+
     def synthesize_best_of(self, text_tokens: torch.Tensor, cond, best_of: int, max_mel_tokens: int = 1500,
                            repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise: Optional[torch.Tensor] = None,
                            per_row_noise: bool = False, noise_seeds=None):

@@ -674,6 +674,9 @@ class ContinuousPipeline:
     submit(takes=n, keep=k) ranks each utterance's takes once all of them are decoded; only the best k go on to the latent pass and the
     acoustic job (see submit).  The codes are those of a pipeline without scores.
 
+    prefix_scores=True (with prefix=True and scores=True): submit(prefix_codes=..., prefix_logprobs="model") has the admission's own
+    prefill score the given codes (decode_session(prefix_scores=True)), so a re-take ranks with a complete sequence score.
+
     session_factory(max_prompt, max_new) -> session (admit / step / take / free_slots / close; scores=True: take(slot, scores=True)
     -> (codes, logprobs); evict to cancel; park / resume to
     preempt; a beam pipeline's: free_groups, park_group / resume_group) replaces the HIP session (tests)."""
@@ -682,7 +685,7 @@ class ContinuousPipeline:
                  repetition_penalty: float = 10.0, max_prompt: Optional[int] = None, max_new: Optional[int] = None,
                  session_factory=None, allow_sampling: bool = False, num_beams: int = 1, acoustic_coalesce: int = 1,
                  acoustic_max_rows: int = 16, preempt: bool = False, park_to: str = "device", preempt_groups: bool = False,
-                 scores: bool = False, prefix: bool = False):
+                 scores: bool = False, prefix: bool = False, prefix_scores: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
@@ -718,6 +721,9 @@ class ContinuousPipeline:
         self.prefix = bool(prefix)
         if self.prefix and self.num_beams > 1:
             raise ValueError("prefix=True needs num_beams == 1: beams do not continue from given codes")
+        self.prefix_scores = bool(prefix_scores)
+        if self.prefix_scores and not (self.prefix and self.scores):
+            raise ValueError("prefix_scores=True needs prefix=True and scores=True")
         self._admitted = 0                      # admission stamps (which row of a priority was admitted last)
         if self.num_beams > 1:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.beam_session(slots, self.num_beams, mp, mn,
@@ -725,7 +731,7 @@ class ContinuousPipeline:
         else:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(
                 slots, mp, mn, repetition_penalty=self.repetition_penalty, sampled=self.allow_sampling, **({"scores": True} if self.scores else {}),
-                **({"prefix": True} if self.prefix else {})))
+                **({"prefix": True} if self.prefix else {}), **({"prefix_scores": True} if self.prefix_scores else {})))
         self._cuda = self.device.type == "cuda"
         self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index, ParkedRow or None) waiting for a slot, most urgent first
@@ -778,7 +784,9 @@ class ContinuousPipeline:
         With takes=n the n takes of an utterance share its prefix and one prefill; max_mel_tokens caps prefix + continuation; the codes
         that go to gpt_stage(codes=) and the acoustic job are prefix + continuation.  prefix_logprobs (scores=True): one fp32 sequence
         or None per utterance; with keep= the ranking uses the recorded log-probabilities, which for the prefix codes are these values,
-        or 0 where none are given -- takes of one utterance share them, so their order is decided by the continuations.  Refused here
+        or 0 where none are given -- takes of one utterance share them, so their order is decided by the continuations.  The string
+        "model" (for one utterance, or for every one that has a prefix; a pipeline built with prefix_scores=True) has the admission's
+        prefill compute them: the sequence score then counts every code, as a take decoded from the start does.  Refused here
         (ValueError): a beam pipeline, a pipeline built without prefix=True, a prefix that holds the stop token or a code outside the
         table, or one that is not shorter than max_mel_tokens."""
         pfx = self._check_prefix(text_tokens, prefix_codes, prefix_logprobs, int(max_mel_tokens))
@@ -820,7 +828,14 @@ class ContinuousPipeline:
             raise ValueError("prefix_logprobs needs a pipeline built with scores=True")
         B = int(torch.as_tensor(text_tokens).shape[0])
         codes = list(prefix_codes)
+        if isinstance(prefix_logprobs, str):      # "model" for every utterance that has a prefix
+            prefix_logprobs = [None if c is None else prefix_logprobs for c in codes]
         lps = [None] * B if prefix_logprobs is None else list(prefix_logprobs)
+        if any(isinstance(l, str) for l in lps):
+            if any(isinstance(l, str) and l != "model" for l in lps):
+                raise ValueError('prefix_logprobs: a sequence, None or the string "model" per utterance')
+            if not self.prefix_scores:
+                raise ValueError('prefix_logprobs="model" needs a pipeline built with prefix_scores=True (and prefix=True, scores=True)')
         if len(codes) != B or len(lps) != B:
             raise ValueError("prefix_codes / prefix_logprobs: one entry (a 1-D sequence or None) per utterance")
         g = self.tts.cfg.gpt
@@ -841,7 +856,7 @@ class ContinuousPipeline:
                 raise ValueError("prefix_codes contain the stop token: nothing follows a stop token")
             if int(c.numel()) >= max_mel_tokens:
                 raise ValueError("prefix_codes must be shorter than max_mel_tokens, which caps prefix + continuation")
-            if l is not None:
+            if l is not None and not isinstance(l, str):
                 l = torch.as_tensor(l).detach().to("cpu", torch.float32)
                 if tuple(l.shape) != tuple(c.shape):
                     raise ValueError("prefix_logprobs: one value per prefix code")
