@@ -698,6 +698,48 @@ def _sampling_c(sampler: str, temperature=1.0, top_k=0, top_p=1.0, noise=None, s
                           exp_noise=noise.data_ptr() if noise is not None else None, seed=seed)
 
 
+def check_sampling(temperature: float, top_k: int, top_p: float, warpers: bool = True, beam: bool = False) -> None:
+    """The ranges of a sampled row's parameters, ValueError outside them: a positive temperature and, where the HF warpers run
+    (`warpers`: not for sampler="accel"), top_k >= 0 -- a beam scorer's rows (`beam`) hold at most 1024 candidates, so there top_k <=
+    1024 always -- top_p > 0, and top_p < 1 only with 0 < top_k <= 1024 (the nucleus is cut from the top-k candidates)."""
+    if not temperature > 0.0:
+        raise ValueError(f"{'beam-sample' if beam else 'sampling'} needs a positive temperature")
+    if not warpers:
+        return
+    if top_k < 0 or (beam and top_k > 1024) or not top_p > 0.0:
+        raise ValueError("top_k must be in 0 .. 1024 and top_p > 0" if beam else "top_k must be >= 0 and top_p > 0")
+    if top_p < 1.0 and not 0 < top_k <= 1024:
+        raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
+
+
+# How check_prefix words a refusal, by the name its caller knows the codes under (DecodeSession.admit's argument, the pipeline's
+# submit argument): whose entry it is, the verb, and what a prefix that leaves no room under the cap is told
+_PREFIX_WORDS = {"prefix": ("request", "contains", "prefix of {k} codes but a cap of {cap}: the cap counts prefix + new codes (k < cap)"),
+                 "prefix_codes": ("utterance", "contain", "prefix_codes must be shorter than max_mel_tokens, which caps prefix + continuation")}
+
+
+def check_prefix(codes, logprobs, cfg, cap: int, label: str = "prefix"):
+    """Given codes a row is to continue from, and their log-probabilities if any -> (codes, logprobs) as CPU tensors (long; fp32 or
+    None).  ValueError unless the codes are a 1-D sequence of mel codes without the stop token, shorter than `cap` (which counts given +
+    new codes), and the log-probabilities are one value per code.  label: what the messages call the codes (_PREFIX_WORDS)."""
+    per, verb, too_long = _PREFIX_WORDS[label]
+    c = torch.as_tensor(codes).detach().to("cpu", torch.long)
+    if c.dim() != 1:
+        raise ValueError(f"{label}: a 1-D sequence of mel codes (or None) per {per}")
+    k = int(c.numel())
+    if k and (int(c.min()) < 0 or int(c.max()) >= cfg.number_mel_codes):
+        raise ValueError(f"{label}: mel codes are 0 .. {cfg.number_mel_codes - 1}")
+    if k and bool((c == cfg.stop_mel_token).any()):
+        raise ValueError(f"{label} {verb} the stop token: nothing follows a stop token")
+    if k >= cap:
+        raise ValueError(too_long.format(k=k, cap=cap))
+    if logprobs is not None:
+        logprobs = torch.as_tensor(logprobs).detach().to("cpu", torch.float32)
+        if tuple(logprobs.shape) != (k,):
+            raise ValueError("prefix_logprobs: one value per prefix code")
+    return c, logprobs
+
+
 class ParkedRow:
     """A decode row that stepped aside (DecodeSession.park): the parked row's bytes (include/idxtts.h "Preempt and resume") on the
     device or, after to("cpu"), in pinned host memory; `n_codes` codes produced so far, the request's `cap`, and the request's
@@ -1026,12 +1068,7 @@ class DecodeSession(_Session):
                 t = float(e.get("temperature", 1.0))
                 k = int(e.get("top_k") or 0) if kind == "hf" else 0
                 p = float(e.get("top_p") if e.get("top_p") is not None else 1.0) if kind == "hf" else 1.0
-                if not t > 0.0:
-                    raise ValueError("sampling needs a positive temperature")
-                if k < 0 or not p > 0.0:
-                    raise ValueError("top_k must be >= 0 and top_p > 0")
-                if p < 1.0 and not 0 < k <= 1024:
-                    raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
+                check_sampling(t, k, p)
                 noise, seed = _draws(e.get("exp_noise"), e.get("seed"), (cap, V), self.gpt.device, "[cap, V] = ")
                 arr[i] = _sampling_c(kind, t, k, p, noise, seed)
             else:
@@ -1093,28 +1130,15 @@ class DecodeSession(_Session):
         rows, plen, _ = self._stage(inputs_embeds_rows, [1] * n, free)
         if any(not 1 <= c <= self.max_new for c in caps_t):
             raise ValueError(f"caps must be in 1 .. {self.max_new}")
-        V, stop = self.gpt.cfg.number_mel_codes, self.gpt.cfg.stop_mel_token
         first = [0]      # request b's takes: ids / caps_t / samplers [first[b] : first[b + 1]]
         for t in tk:
             first.append(first[-1] + t)
         codes, lps = [], []
-        for b in range(n):
-            c = torch.zeros(0, dtype=torch.long) if pf[b] is None else torch.as_tensor(pf[b]).detach().to("cpu", torch.long)
-            if c.dim() != 1:
-                raise ValueError("prefix: a 1-D sequence of mel codes (or None) per request")
-            k = int(c.numel())
-            if k and (int(c.min()) < 0 or int(c.max()) >= V):
-                raise ValueError(f"prefix: mel codes are 0 .. {V - 1}")
-            if k and bool((c == stop).any()):
-                raise ValueError("prefix contains the stop token: nothing follows a stop token")
-            caps_b = caps_t[first[b]:first[b + 1]]
-            if any(k >= cap for cap in caps_b):
-                raise ValueError(f"prefix of {k} codes but a cap of {min(caps_b)}: the cap counts prefix + new codes (k < cap)")
-            l = torch.zeros(k) if lp[b] is None else torch.as_tensor(lp[b]).detach().to("cpu", torch.float32)
-            if tuple(l.shape) != (k,):
-                raise ValueError("prefix_logprobs: one value per prefix code")
+        for b in range(n):      # (no prefix: an empty one; the smallest cap of the request's takes decides)
+            c, l = check_prefix(torch.zeros(0, dtype=torch.long) if pf[b] is None else pf[b], lp[b], self.gpt.cfg,
+                                min(caps_t[first[b]:first[b + 1]]))
             codes.append(c)
-            lps.append(l)
+            lps.append(torch.zeros(c.numel()) if l is None else l)
         klen = [int(c.numel()) for c in codes]
         # the library gets what each caller form has always given it: takes NULL for plain rows, samplers NULL for greedy ones, prefix
         # lengths of zero (which it drops) and no codes where there is no prefix; one group unless prefixes outgrow the prefill area

@@ -71,6 +71,13 @@ def merge_keeps_kernels(rows_each, prefix_len: int, split_bf16_gemm: bool, compa
     return True
 
 
+def _draw_seeds(n: int, seed=None, generator=None) -> list:
+    """The one seed rule: n seeds, each torch.randint(0, 2**62, (1,), generator=g), drawn one after the other with g =
+    torch.Generator().manual_seed(seed) when `seed` is given, else `generator`, else (None) torch's global RNG."""
+    g = torch.Generator().manual_seed(int(seed)) if seed is not None else generator
+    return [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
+
+
 def utterance_noise_seeds(noise_seed, n: int):
     """The per-utterance CFM noise seeds of a request of `n` utterances (IndexTTS2.acoustic_stage's `noise_seeds`).  None: None (the
     noise is given, or drawn from torch's generator).  An int: n seeds drawn as utterance_samplers draws its seeds,
@@ -81,8 +88,7 @@ def utterance_noise_seeds(noise_seed, n: int):
     if isinstance(noise_seed, int) and not isinstance(noise_seed, bool):
         if not 0 <= noise_seed < 2 ** 64:
             raise ValueError("noise_seed must be in 0 <= seed < 2**64")
-        g = torch.Generator().manual_seed(noise_seed)
-        return [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
+        return _draw_seeds(n, seed=noise_seed)
     try:
         seeds = [operator.index(v) for v in noise_seed]
     except TypeError:
@@ -94,13 +100,6 @@ def utterance_noise_seeds(noise_seed, n: int):
     return seeds
 
 
-def _request_noise(noise, noise_seed, n: int):
-    """(noise, per-utterance seeds) of a request as submitted: at most one of the two."""
-    if noise is not None and noise_seed is not None:
-        raise ValueError("pass `noise` or `noise_seed`, not both")
-    return noise, utterance_noise_seeds(noise_seed, n)
-
-
 def _noise_kind(r) -> int:
     """How a request's CFM noise is fixed: 1 = explicit tensor, 2 = seeds, 0 = neither (drawn when its acoustic stage runs, so it is
     never merged).  Only requests of one non-zero kind share an acoustic batch."""
@@ -109,13 +108,6 @@ def _noise_kind(r) -> int:
 
 def _noise_of(r):
     return r.noise if r.noise is not None else r.noise_seeds
-
-
-def _acoustic_call(tts, st, noise):
-    """acoustic_stage on a (merged) state with what merge_acoustic_states returned for its noise: a tensor, None or a seed list."""
-    if isinstance(noise, list):
-        return tts.acoustic_stage(st, noise_seeds=noise)
-    return tts.acoustic_stage(st, noise=noise)
 
 
 def merge_acoustic_states(items):
@@ -171,7 +163,7 @@ def rank_request(codes, logprobs, takes: int, stop_token: int, length_penalty: f
 
 
 def _keep_best(r, ranking, keep: int) -> list:
-    """Cuts a request (a _Request or a _Job) with r.takes takes per utterance down to the best `keep` of each, best first: its text,
+    """Cuts a request with r.takes takes per utterance down to the best `keep` of each, best first: its text,
     per-row prompts, CFM noise rows and noise seeds follow the kept takes (take j of utterance i keeps entry i * takes + j), and r.takes
     becomes `keep`.  Returns the kept rows' indices."""
     rows = [i * r.takes + rk[q][0] for i, rk in enumerate(ranking) for q in range(keep)]
@@ -239,9 +231,23 @@ def _start(owner) -> bool:
         return False
 
 
+def _expand_cond(cond, n: int):
+    """The conditioning of a request with n takes per utterance, one entry per take (row i * n + j: utterance i): a list of prompts is
+    repeated entry by entry; one prompt for every row (leading dimension 1) serves as it is."""
+    if isinstance(cond, (list, tuple)):
+        return [c for c in cond for _ in range(n)]
+    if int(cond.spk_cond_latent.shape[0]) == 1 and int(cond.emo_vec.shape[0]) == 1:
+        return cond
+    raise ValueError("takes > 1 needs one prompt for the whole request, or a list of one prompt per utterance")
+
+
 class _Request:
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "repetition_penalty", "sampling", "ready", "caller", "done",
-                 "notified", "takes", "keep", "base")
+    """One submitted batch of utterances, one row per take (_new_request).  A BatchPipeline adds what its one-shot decode needs and
+    leaves behind (repetition_penalty, base, state); a ContinuousPipeline, whose rows decode independently in whatever slots are free,
+    adds the decode's progress (codes .. prefix_lps)."""
+    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "sampling", "ready", "caller", "done", "notified", "takes", "keep",
+                 "repetition_penalty", "base", "state",
+                 "codes", "left", "failed", "seq", "deadline", "priority", "stamp", "nbest", "lps", "prefix", "prefix_lps")
 
     def compatible(self, other: "_Request") -> bool:
         # same prompt and settings, greedy (sampling draws are per call) and the SAME text width: a wider neighbour would left-pad this
@@ -250,44 +256,171 @@ class _Request:
                 and self.sampling is None and other.sampling is None and int(self.text.shape[1]) == int(other.text.shape[1]))
 
 
-class BatchPipeline:
+# One utterance's rows in a ContinuousPipeline admission: its prompt, the (request, row) of every take admitted with it and, per take,
+# the cap and the sampler (None on a greedy pipeline; a beam pipeline: the group's one beam entry), the codes it continues from
+_Part = collections.namedtuple("_Part", "prompt owners caps samplers prefix prefix_lps")
+
+
+class _Pipeline:
+    """What the two pipelines do the same way: build a request, give every worker thread its stream, run the acoustic jobs on
+    `acoustic_workers` threads, hand the waveforms back, release the streams.  Which decoded requests make the next acoustic job
+    (_take_acoustic), where a request's gpt_stage state comes from (_acoustic_state), what retiring a job does (_retire) and what its
+    trace entry holds (_acoustic_entry) are each pipeline's own."""
+
+    def __init__(self, tts, acoustic_workers: int, lock, cuda: bool):
+        self.tts = tts
+        self.device = torch.device(tts.device)
+        self._cuda = cuda                      # off-GPU (a ContinuousPipeline of stand-in sessions) there are no streams and no events
+        self._lock = lock                      # the pipeline's own lock, taken here where the list of streams grows
+        self._pri = {"decode": 0, "acoustic": 0}      # stream priority by kind of worker (0: the default)
+        self._tls = threading.local()          # one stream per worker THREAD: two jobs never share a stream (= a workspace)
+        self._streams = []                     # every worker thread's stream (handed back to the library in close())
+        self._turn = contextlib.nullcontext()  # held around a job's GPU work
+        self._aq = collections.deque()         # decoded requests waiting for an acoustic worker
+        self._acoustic = concurrent.futures.ThreadPoolExecutor(max_workers=acoustic_workers, thread_name_prefix="idxtts-acoustic")
+        self.trace = None                      # set to a list to record the host times (time.perf_counter) of the jobs
+
+    def _new_request(self, text_tokens, cond, max_mel_tokens, noise, noise_seed, takes: int, keep, samplers=None) -> _Request:
+        """A request as submitted: its Future (r.done), the text and conditioning with every utterance repeated `takes` times (row
+        i * takes + j: take j of utterance i), the rows' CFM noise or noise seeds, then -- drawn after the noise seeds -- r.sampling =
+        samplers(rows), what the pipeline fixes per row, and the caller's stream with the event recorded on it that the workers wait for
+        (both None off-GPU).  A bad noise / noise_seed, a conditioning that cannot be repeated and a ValueError of `samplers` fail the
+        Future only: the request then comes back done and is not to be queued."""
+        r = _Request()
+        r.done, r.notified, r.takes, r.keep = concurrent.futures.Future(), False, takes, keep
+        r.text, r.cond, r.max_mel_tokens = torch.as_tensor(text_tokens), cond, max_mel_tokens
+        try:
+            if takes > 1:
+                r.text, r.cond = r.text.repeat_interleave(takes, 0), _expand_cond(cond, takes)
+            rows = int(r.text.shape[0])
+            if noise is not None and noise_seed is not None:
+                raise ValueError("pass `noise` or `noise_seed`, not both")
+            r.noise, r.noise_seeds = noise, utterance_noise_seeds(noise_seed, rows)
+            r.sampling = samplers(rows) if samplers is not None else None
+        except ValueError as e:
+            r.done.set_exception(e)
+            return r
+        r.caller = torch.cuda.current_stream(self.device) if self._cuda else None
+        r.ready = torch.cuda.Event() if self._cuda else None
+        if self._cuda:
+            r.ready.record(r.caller)
+        return r
+
+    def _stream(self, kind: str):
+        """The calling worker thread's stream, made at its first job; None off-GPU."""
+        s = getattr(self._tls, "stream", None)
+        if s is None and self._cuda:
+            s = self._tls.stream = torch.cuda.Stream(device=self.device, priority=self._pri[kind])
+            with self._lock:
+                self._streams.append(s)
+        return s
+
+    def _on(self, s):
+        return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
+
+    def _wait_ready(self, r: _Request) -> None:
+        """The current stream waits for what the caller's stream held when the request was submitted."""
+        if r.ready is not None:
+            torch.cuda.current_stream(self.device).wait_event(r.ready)
+
+    @staticmethod
+    def _fail(r: _Request, e: BaseException) -> None:
+        r.failed = True
+        _set_exception(r.done, e)
+
+    def _retire(self, group) -> None:
+        """An acoustic job's requests have their outcome."""
+
+    def _acoustic_entry(self, t0: float, t1: float, rows: int, group) -> tuple:
+        """What `trace` records of an acoustic job: (kind, start, end, rows), as of every job."""
+        return ("acoustic", t0, t1, rows)
+
+    def _acoustic_drain(self):
+        """One acoustic job: the group's states (merge_acoustic_states; one request: its own) through s2mel and the vocoder as one
+        batch, and every request its own rows.  A failure fails every request of the job and nothing else."""
+        group = self._take_acoustic()
+        if not group:
+            return
+        try:
+            if self._cuda:
+                torch.cuda.set_device(self.device)
+            t0 = time.perf_counter()
+            sa = self._stream("acoustic")
+            with self._turn, self._on(sa):
+                states = [self._acoustic_state(r) for r in group]
+                if len(group) == 1:
+                    st, noise = states[0], _noise_of(group[0])
+                else:
+                    st, noise = merge_acoustic_states([(r.cond, s, _noise_of(r)) for r, s in zip(group, states)])
+                kw = {"noise_seeds": noise} if isinstance(noise, list) else {"noise": noise}      # a tensor, None or a seed list
+                wavs = self.tts.acoustic_stage(st, **kw)
+                if sa is not None:
+                    sa.synchronize()            # the states' tensors may be released once this returns
+            rows = [int(r.text.shape[0]) for r in group]
+            if self.trace is not None:
+                self.trace.append(self._acoustic_entry(t0, time.perf_counter(), sum(rows), group))
+            a = 0
+            for r, n in zip(group, rows):
+                self._deliver(r, wavs[a:a + n])
+                a += n
+        except BaseException as e:              # noqa: BLE001 -- handed to the callers through their futures
+            for r in group:
+                self._fail(r, e)
+        finally:
+            self._retire(group)
+
+    @staticmethod
+    def _deliver(r: _Request, wavs: list) -> None:
+        """A request's waveforms to its Future: the flat list, or result[i][j] for a request with takes (or keep)."""
+        if r.caller is not None:
+            for w in wavs:                      # allocated on the worker's stream, consumed on the caller's
+                w.record_stream(r.caller)
+        r.done.set_result(wavs if r.takes == 1 and r.keep is None else [wavs[i:i + r.takes] for i in range(0, len(wavs), r.takes)])
+
+    def _close_acoustic(self):
+        """The end of close(), once nothing decodes any more: the acoustic jobs drain, then the library's per-stream scratch goes
+        with the worker threads' streams."""
+        self._acoustic.shutdown(wait=True)
+        if self._cuda:
+            from . import _lib
+            with torch.cuda.device(self.device):
+                for s in self._streams:
+                    s.synchronize()
+                    _lib.release_stream(s)
+        self._streams = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class BatchPipeline(_Pipeline):
     def __init__(self, tts, decode_lanes: int = 3, acoustic_workers: int = 1, coalesce: int = 1, lane_priority: str = "high",
                  acoustic_coalesce: int = 1, exclusive: bool = False, acoustic_mix_prompts: bool = False):
         """acoustic_mix_prompts: let `acoustic_coalesce` merge decoded requests of DIFFERENT prompts into one acoustic batch (a
         mixed-prompt CFM, S2Mel.cfm_rows); default: only requests of one prompt object are merged."""
         if decode_lanes < 1 or acoustic_workers < 1 or coalesce < 1 or acoustic_coalesce < 1:
             raise ValueError("decode_lanes, acoustic_workers, coalesce and acoustic_coalesce must be >= 1")
-        self.tts = tts
-        self.device = torch.device(tts.device)
+        self._qlock = threading.Lock()
+        super().__init__(tts, acoustic_workers, self._qlock, cuda=True)      # (every stage of this pipeline is a GPU stage)
         self.decode_lanes = decode_lanes
         self.acoustic_workers = acoustic_workers
         self.coalesce = coalesce
         self.acoustic_coalesce = acoustic_coalesce
         self.acoustic_mix_prompts = bool(acoustic_mix_prompts)
-        self._aq = collections.deque()         # decoded requests waiting for an acoustic worker: (request, state)
         lo_pri, hi_pri = torch.cuda.Stream.priority_range() if hasattr(torch.cuda.Stream, "priority_range") else (0, -1)
         self._pri = {"decode": hi_pri if lane_priority == "high" else lo_pri, "acoustic": lo_pri}
-        self._tls = threading.local()          # one stream per worker THREAD: two jobs never share a stream (= a workspace)
         self._lanes = concurrent.futures.ThreadPoolExecutor(max_workers=decode_lanes, thread_name_prefix="idxtts-decode")
-        self._acoustic = concurrent.futures.ThreadPoolExecutor(max_workers=acoustic_workers, thread_name_prefix="idxtts-acoustic")
         self._queue = collections.deque()
-        self._qlock = threading.Lock()
-        self._streams = []                     # every worker thread's stream (handed back to the library in close())
         self._running = 0                      # requests taken by a lane and not yet retired
         self._groups_taken = 0                 # decode groups formed since the pipeline was last idle
         # exclusive: a decode job and an acoustic job never share the chip (each takes this lock for the whole of its GPU work) -- the
         # pipeline then only re-orders and merges the work; measured against the overlapped schedule in profiles/README.md "Round 4"
-        self._turn = threading.Lock() if exclusive else contextlib.nullcontext()
-        self.trace = None                      # set to a list to record (kind, start, end, rows) host times of every job (time.perf_counter)
+        if exclusive:
+            self._turn = threading.Lock()
         tts.gpt.MAX_WORKSPACES = max(tts.gpt.MAX_WORKSPACES, decode_lanes + 2)
-
-    def _stream(self, kind: str) -> torch.cuda.Stream:
-        s = getattr(self._tls, "stream", None)
-        if s is None:
-            s = self._tls.stream = torch.cuda.Stream(device=self.device, priority=self._pri[kind])
-            with self._qlock:
-                self._streams.append(s)
-        return s
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
@@ -318,21 +451,11 @@ class BatchPipeline:
         if keep is not None and not (sampling and sampling.get("do_sample")):
             raise ValueError("keep ranks sampled takes: the request must sample (do_sample)")
         keep = _check_keep(keep, takes, True, bool(sampling and int(sampling.get("num_beams") or 1) > 1))
-        r = _Request()
-        r.done, r.notified, r.takes, r.keep = concurrent.futures.Future(), False, takes, keep
-        r.base = (torch.as_tensor(text_tokens), cond)      # one row per utterance: what a request with keep decodes from
-        try:
-            if takes > 1:
-                text_tokens, cond = torch.as_tensor(text_tokens).repeat_interleave(takes, 0), _expand_cond(cond, takes)
-            r.noise, r.noise_seeds = _request_noise(noise, noise_seed, int(text_tokens.shape[0]))
-        except ValueError as e:
-            r.done.set_exception(e)
+        r = self._new_request(text_tokens, cond, max_mel_tokens, noise, noise_seed, takes, keep)
+        if r.done.done():
             return r.done
-        r.text, r.cond, r.max_mel_tokens = text_tokens, cond, max_mel_tokens
+        r.base = (torch.as_tensor(text_tokens), cond)      # one row per utterance: what a request with keep decodes from
         r.repetition_penalty, r.sampling = repetition_penalty, sampling
-        r.caller = torch.cuda.current_stream(self.device)
-        r.ready = torch.cuda.Event()
-        r.ready.record(r.caller)
         with self._qlock:
             self._queue.append(r)
         self._lanes.submit(self._lane_job)      # one drain per request: a drain that finds the queue empty (its request was merged) returns
@@ -373,7 +496,7 @@ class BatchPipeline:
         ok = fut.cancel()
         with self._qlock:
             self._queue = collections.deque(r for r in self._queue if not _cancelled(r))
-            kept = collections.deque(item for item in self._aq if not _cancelled(item[0]))
+            kept = collections.deque(r for r in self._aq if not _cancelled(r))
             self._running -= len(self._aq) - len(kept)
             self._aq = kept
         return ok
@@ -433,7 +556,8 @@ class BatchPipeline:
                 with self._qlock:
                     keep = not _cancelled(r)
                     if keep:
-                        self._aq.append((r, sub))
+                        r.state = sub
+                        self._aq.append(r)
                     else:
                         self._running -= 1
                 handed += 1
@@ -449,91 +573,48 @@ class BatchPipeline:
         """Up to `acoustic_coalesce` decoded requests of one prompt (of any prompts with acoustic_mix_prompts), each with its own CFM
         noise or all with noise seeds (a merged draw from torch's generator would consume it differently from the separate calls).
         The point of no return: every request taken is marked running (_start), so cancel() on it fails from here on; the cancelled
-        ones are dropped and retired."""
+        ones are dropped and retired.  (Merging measured neutral at configs[2]: 181.8 vs 182.3 audio-s/s, profiles/README.md "Round 3";
+        useful where single requests are small.)"""
         with self._qlock:
             while self._aq:
                 group = [self._aq.popleft()]
-                kind = _noise_kind(group[0][0])
-                while (len(group) < self.acoustic_coalesce and self._aq and kind and _noise_kind(self._aq[0][0]) == kind
-                       and (self.acoustic_mix_prompts or self._aq[0][0].cond is group[0][0].cond)):
+                kind = _noise_kind(group[0])
+                while (len(group) < self.acoustic_coalesce and self._aq and kind and _noise_kind(self._aq[0]) == kind
+                       and (self.acoustic_mix_prompts or self._aq[0].cond is group[0].cond)):
                     group.append(self._aq.popleft())
-                kept = [item for item in group if _start(item[0])]
+                kept = [r for r in group if _start(r)]
                 self._running -= len(group) - len(kept)
                 if kept:
                     return kept
             return []
 
-    @staticmethod
-    def _merge_states(group):
-        """Several decoded batches as ONE acoustic batch (merge_acoustic_states).  (Measured neutral at configs[2]: 181.8 vs 182.3
-        audio-s/s, profiles/README.md "Round 3"; useful where single requests are small.)"""
-        return merge_acoustic_states([(r.cond, st, _noise_of(r)) for r, st in group])
+    def _acoustic_state(self, r: _Request) -> dict:
+        return r.state                          # (computed on the lane)
 
-    def _acoustic_drain(self):
-        group = self._take_acoustic()
-        if not group:
-            return
-        try:
-            torch.cuda.set_device(self.device)
-            t0 = time.perf_counter()
-            sa = self._stream("acoustic")
-            with self._turn, torch.cuda.stream(sa):
-                if len(group) == 1:
-                    st, noise = group[0][1], _noise_of(group[0][0])
-                else:
-                    st, noise = self._merge_states(group)
-                wavs = _acoustic_call(self.tts, st, noise)
-                sa.synchronize()                 # the states' tensors may be released once this returns
-            if self.trace is not None:
-                self.trace.append(("acoustic", t0, time.perf_counter(), st["B"]))
-            a = 0
-            for r, sub in group:
-                mine = wavs[a:a + sub["B"]]
-                a += sub["B"]
-                for w in mine:                    # allocated on the worker's stream, consumed on the caller's
-                    w.record_stream(r.caller)
-                r.done.set_result(mine if r.takes == 1 and r.keep is None else [mine[i:i + r.takes] for i in range(0, len(mine), r.takes)])
-        except BaseException as e:                  # noqa: BLE001
-            for r, _ in group:
-                _set_exception(r.done, e)
-        finally:
-            with self._qlock:
-                self._running -= len(group)
+    def _retire(self, group) -> None:
+        with self._qlock:
+            self._running -= len(group)
 
     def close(self):
         self._lanes.shutdown(wait=True)
-        self._acoustic.shutdown(wait=True)
-        from . import _lib
-        with torch.cuda.device(self.device):
-            for s in self._streams:          # the library's per-stream scratch goes with the worker threads' streams
-                s.synchronize()
-                _lib.release_stream(s)
-        self._streams = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class _Job:
-    """One submitted batch of utterances in a ContinuousPipeline: its rows decode independently, in whatever slots are free."""
-    __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "caller", "ready", "done", "codes", "left", "failed", "sampling",
-                 "seq", "deadline", "notified", "priority", "stamp", "takes", "nbest", "keep", "lps", "prefix", "prefix_lps")
-
-
-def _expand_cond(cond, n: int):
-    """The conditioning of a request with n takes per utterance, one entry per take (row i * n + j: utterance i): a list of prompts is
-    repeated entry by entry; one prompt for every row (leading dimension 1) serves as it is."""
-    if isinstance(cond, (list, tuple)):
-        return [c for c in cond for _ in range(n)]
-    if int(cond.spk_cond_latent.shape[0]) == 1 and int(cond.emo_vec.shape[0]) == 1:
-        return cond
-    raise ValueError("takes > 1 needs one prompt for the whole request, or a list of one prompt per utterance")
+        self._close_acoustic()
 
 
 _SAMPLING_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "sampler", "generator", "seed", "length_penalty"}
+
+
+def _sampling_params(s: dict, warpers: bool = True, beam: bool = False, check: bool = True) -> tuple:
+    """(temperature, top_k, top_p, length_penalty) of a sampling dict: missing (or None) values take UnifiedVoice.generate's and
+    generate_beam's defaults, 1.0, 50, 1.0 and 1.0.  `check` (a request that draws): ValueError outside gpt.check_sampling's ranges --
+    sampler="accel" runs no warpers, so its top_k / top_p are not looked at; a beam request's top_k is at most 1024 always."""
+    from .gpt import check_sampling
+    t = float(s["temperature"]) if s.get("temperature") is not None else 1.0
+    k = int(s["top_k"]) if s.get("top_k") is not None else 50
+    p = float(s["top_p"]) if s.get("top_p") is not None else 1.0
+    lp = float(s["length_penalty"]) if s.get("length_penalty") is not None else 1.0
+    if check:
+        check_sampling(t, k, p, warpers, beam)
+    return t, k, p, lp
 
 
 def utterance_samplers(sampling: Optional[dict], n: int) -> list:
@@ -554,19 +635,8 @@ def utterance_samplers(sampling: Optional[dict], n: int) -> list:
     kind = s.get("sampler") or "hf"
     if kind not in ("hf", "accel"):
         raise ValueError("sampler must be 'hf' or 'accel'")
-    t = float(s["temperature"]) if s.get("temperature") is not None else 1.0
-    k = int(s["top_k"]) if s.get("top_k") is not None else 50
-    p = float(s["top_p"]) if s.get("top_p") is not None else 1.0
-    if not t > 0.0:
-        raise ValueError("sampling needs a positive temperature")
-    if kind == "hf":
-        if k < 0 or not p > 0.0:
-            raise ValueError("top_k must be >= 0 and top_p > 0")
-        if p < 1.0 and not 0 < k <= 1024:
-            raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
-    g = torch.Generator().manual_seed(int(s["seed"])) if s.get("seed") is not None else s.get("generator")
-    seeds = [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
-    return [{"sampler": kind, "temperature": t, "top_k": k, "top_p": p, "seed": sd} for sd in seeds]
+    t, k, p, _ = _sampling_params(s, warpers=kind == "hf")
+    return [{"sampler": kind, "temperature": t, "top_k": k, "top_p": p, "seed": sd} for sd in _draw_seeds(n, s.get("seed"), s.get("generator"))]
 
 
 _BEAM_KEYS = {"do_sample", "num_beams", "temperature", "top_k", "top_p", "generator", "seed", "length_penalty"}
@@ -587,26 +657,13 @@ def utterance_beams(sampling: Optional[dict], n: int, num_beams: int) -> list:
     if nb != int(num_beams):
         raise ValueError(f"this ContinuousPipeline runs num_beams={num_beams}; the request asks for num_beams={nb}")
     do_sample = bool(s.get("do_sample"))
-    t = float(s["temperature"]) if s.get("temperature") is not None else 1.0
-    k = int(s["top_k"]) if s.get("top_k") is not None else 50
-    p = float(s["top_p"]) if s.get("top_p") is not None else 1.0
-    lp = float(s["length_penalty"]) if s.get("length_penalty") is not None else 1.0
-    if do_sample:
-        if not t > 0.0:
-            raise ValueError("beam-sample needs a positive temperature")
-        if not 0 <= k <= 1024 or not p > 0.0:
-            raise ValueError("top_k must be in 0 .. 1024 and top_p > 0")
-        if p < 1.0 and not 0 < k <= 1024:
-            raise ValueError("top_p < 1 needs 0 < top_k <= 1024")
-        g = torch.Generator().manual_seed(int(s["seed"])) if s.get("seed") is not None else s.get("generator")
-        seeds = [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(n)]
-    else:
-        seeds = [0] * n
+    t, k, p, lp = _sampling_params(s, beam=True, check=do_sample)
+    seeds = _draw_seeds(n, s.get("seed"), s.get("generator")) if do_sample else [0] * n      # (no draws: no seeds taken)
     return [{"do_sample": do_sample, "temperature": t, "top_k": k, "top_p": p, "length_penalty": lp, "early_stopping": False, "seed": sd}
             for sd in seeds]
 
 
-class ContinuousPipeline:
+class ContinuousPipeline(_Pipeline):
     """Continuous (iteration-level) batching of the GPT decode: each of `decode_lanes` lanes owns one decode session of `slots` rows
     (`UnifiedVoice.decode_session`) on its own stream and host thread.  A lane admits waiting utterances into its free slots --
     utterances of different requests, prompts and text widths share a session -- steps `poll_steps` steps at a time and collects
@@ -688,10 +745,10 @@ class ContinuousPipeline:
                  scores: bool = False, prefix: bool = False, prefix_scores: bool = False):
         if slots < 1 or decode_lanes < 1 or acoustic_workers < 1 or poll_steps < 1 or acoustic_coalesce < 1 or acoustic_max_rows < 1:
             raise ValueError("slots, decode_lanes, acoustic_workers, poll_steps, acoustic_coalesce and acoustic_max_rows must be >= 1")
+        self._cv = threading.Condition()
+        super().__init__(tts, acoustic_workers, self._cv, cuda=torch.device(tts.device).type == "cuda")
         self.acoustic_coalesce, self.acoustic_max_rows = int(acoustic_coalesce), int(acoustic_max_rows)
-        self._aq = collections.deque()          # decoded requests waiting for an acoustic worker
         self._submitted = 0
-        self.trace = None
         self._clock = time.monotonic            # deadlines are read off this clock
         self.num_beams = int(num_beams)
         if not 1 <= self.num_beams <= 8:
@@ -699,8 +756,6 @@ class ContinuousPipeline:
         if slots % self.num_beams:
             raise ValueError(f"slots ({slots}) must be a multiple of num_beams ({self.num_beams})")
         g = tts.cfg.gpt
-        self.tts = tts
-        self.device = torch.device(tts.device)
         self.slots, self.poll_steps, self.repetition_penalty = slots, poll_steps, float(repetition_penalty)
         self.max_prompt = int(max_prompt or g.cond_latents + 2 + g.max_text_tokens + 2)      # [cond | start, text, stop]
         self.max_new = int(max_new or g.max_mel_tokens)
@@ -732,28 +787,12 @@ class ContinuousPipeline:
             self._factory = session_factory or (lambda mp, mn: tts.gpt.decode_session(
                 slots, mp, mn, repetition_penalty=self.repetition_penalty, sampled=self.allow_sampling, **({"scores": True} if self.scores else {}),
                 **({"prefix": True} if self.prefix else {}), **({"prefix_scores": True} if self.prefix_scores else {})))
-        self._cuda = self.device.type == "cuda"
-        self._cv = threading.Condition()
         self._waiting = collections.deque()     # (job, utterance index, ParkedRow or None) waiting for a slot, most urgent first
         self._closing = False
-        self._streams = []
-        self._tls = threading.local()
-        self._acoustic = concurrent.futures.ThreadPoolExecutor(max_workers=acoustic_workers, thread_name_prefix="idxtts-acoustic")
         self._alive = decode_lanes
         self._lanes = [threading.Thread(target=self._lane, name=f"idxtts-session-{i}", daemon=True) for i in range(decode_lanes)]
         for t in self._lanes:
             t.start()
-
-    def _new_stream(self):
-        if not self._cuda:
-            return None
-        s = torch.cuda.Stream(device=self.device)
-        with self._cv:
-            self._streams.append(s)
-        return s
-
-    def _on(self, s):
-        return torch.cuda.stream(s) if s is not None else contextlib.nullcontext()
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
@@ -798,21 +837,50 @@ class ContinuousPipeline:
         keep = _check_keep(keep, takes, self.scores, self.num_beams > 1)
         if keep is not None and not (self.allow_sampling and sampling and sampling.get("do_sample")):
             raise ValueError("keep ranks sampled takes: the request must sample (allow_sampling, do_sample)")
-        if self.num_beams > 1:
-            def beams(B):
-                if takes > self.num_beams:
-                    raise ValueError(f"takes ({takes}) exceeds the pipeline's num_beams ({self.num_beams})")
-                return utterance_beams(sampling, B, self.num_beams)
-            return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty, beams, noise_seed, deadline_s, priority, takes)
-        if sampling and not self.allow_sampling:
-            raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
-        if sampling and int(sampling.get("num_beams") or 1) > 1:
-            raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
-        if takes > 1 and not (self.allow_sampling and sampling and sampling.get("do_sample")):
-            raise ValueError("takes > 1 needs a sampled request: every take of a greedy one would be the same")
-        return self._submit(text_tokens, cond, max_mel_tokens, noise, repetition_penalty,
-                            (lambda B: utterance_samplers(sampling, B)) if self.allow_sampling else None, noise_seed, deadline_s, priority, takes,
-                            keep, pfx)
+        beam = self.num_beams > 1
+        if not beam:
+            if sampling and not self.allow_sampling:
+                raise ValueError("this ContinuousPipeline decodes greedily; build it with allow_sampling=True (or use BatchPipeline) to sample")
+            if sampling and int(sampling.get("num_beams") or 1) > 1:
+                raise ValueError("ContinuousPipeline does not run beam search (num_beams > 1); use BatchPipeline")
+            if takes > 1 and not (self.allow_sampling and sampling and sampling.get("do_sample")):
+                raise ValueError("takes > 1 needs a sampled request: every take of a greedy one would be the same")
+        if float(repetition_penalty) != self.repetition_penalty:
+            raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
+        if not 1 <= int(max_mel_tokens) <= self.max_new:
+            raise ValueError(f"max_mel_tokens must be in 1 .. {self.max_new}")
+
+        def samplers(rows: int):                # a bad parameter fails this request's Future only
+            if not beam:
+                return utterance_samplers(sampling, rows) if self.allow_sampling else None
+            if takes > self.num_beams:
+                raise ValueError(f"takes ({takes}) exceeds the pipeline's num_beams ({self.num_beams})")
+            per = utterance_beams(sampling, rows // takes, self.num_beams)
+            return [per[r // takes] for r in range(rows)]
+
+        # takes: the request holds one row per take, row i * takes + j (text and conditioning repeated).  A sampled pipeline decodes every
+        # row; a beam pipeline decodes one group per utterance, queued as the utterance's first row, and reads its `takes` best
+        j = self._new_request(text_tokens, cond, int(max_mel_tokens), noise, noise_seed, takes, keep, samplers)
+        if j.done.done():
+            return j.done
+        B = int(j.text.shape[0])
+        j.nbest = takes if beam else 1
+        # prefixes: one entry per row (the takes of an utterance share theirs)
+        j.prefix = None if pfx is None else [pfx[0][r // takes] for r in range(B)]
+        j.prefix_lps = None if pfx is None else [pfx[1][r // takes] for r in range(B)]
+        j.codes, j.left, j.failed = [None] * B, B // j.nbest, False
+        j.lps = None if keep is None else [None] * B
+        j.priority, j.stamp = priority, [0] * B
+        j.deadline = None if deadline_s is None else self._clock() + deadline_s
+        with self._cv:
+            if self._closing or self._alive == 0:
+                raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
+            j.seq = self._submitted
+            self._submitted += 1
+            for i in range(0, B, j.nbest):
+                self._enqueue(j, i, None)
+            self._cv.notify_all()
+        return j.done
 
     def _check_prefix(self, text_tokens, prefix_codes, prefix_logprobs, max_mel_tokens: int):
         """submit(prefix_codes=, prefix_logprobs=) -> None, or (codes, logprobs): one CPU tensor or None per utterance."""
@@ -838,102 +906,31 @@ class ContinuousPipeline:
                 raise ValueError('prefix_logprobs="model" needs a pipeline built with prefix_scores=True (and prefix=True, scores=True)')
         if len(codes) != B or len(lps) != B:
             raise ValueError("prefix_codes / prefix_logprobs: one entry (a 1-D sequence or None) per utterance")
-        g = self.tts.cfg.gpt
-        out_c, out_l = [], []
-        for c, l in zip(codes, lps):
+        from .gpt import check_prefix
+        out_c, out_l = [None] * B, [None] * B
+        for b, (c, l) in enumerate(zip(codes, lps)):
             if c is None:
                 if l is not None:
                     raise ValueError("prefix_logprobs for an utterance without prefix_codes")
-                out_c.append(None)
-                out_l.append(None)
                 continue
-            c = torch.as_tensor(c).detach().to("cpu", torch.long)
-            if c.dim() != 1:
-                raise ValueError("prefix_codes: a 1-D sequence of mel codes (or None) per utterance")
-            if c.numel() and (int(c.min()) < 0 or int(c.max()) >= g.number_mel_codes):
-                raise ValueError(f"prefix_codes: mel codes are 0 .. {g.number_mel_codes - 1}")
-            if bool((c == g.stop_mel_token).any()):
-                raise ValueError("prefix_codes contain the stop token: nothing follows a stop token")
-            if int(c.numel()) >= max_mel_tokens:
-                raise ValueError("prefix_codes must be shorter than max_mel_tokens, which caps prefix + continuation")
-            if l is not None and not isinstance(l, str):
-                l = torch.as_tensor(l).detach().to("cpu", torch.float32)
-                if tuple(l.shape) != tuple(c.shape):
-                    raise ValueError("prefix_logprobs: one value per prefix code")
-            out_c.append(c if c.numel() else None)
-            out_l.append(l if c.numel() else None)
+            model = isinstance(l, str)          # (the admission scores the codes: there are no values to check)
+            c, given = check_prefix(c, None if model else l, self.tts.cfg.gpt, max_mel_tokens, "prefix_codes")      # max_mel_tokens caps prefix + continuation
+            if c.numel():
+                out_c[b], out_l[b] = c, l if model else given
         return (out_c, out_l) if any(c is not None for c in out_c) else None
 
-    def _submit(self, text_tokens, cond, max_mel_tokens, noise, repetition_penalty, per_utterance, noise_seed=None, deadline_s=None,
-                priority=0, takes=1, keep=None, pfx=None):
-        if float(repetition_penalty) != self.repetition_penalty:
-            raise ValueError(f"this pipeline's sessions use repetition_penalty={self.repetition_penalty}")
-        if not 1 <= int(max_mel_tokens) <= self.max_new:
-            raise ValueError(f"max_mel_tokens must be in 1 .. {self.max_new}")
-        j = _Job()
-        j.text, j.cond, j.max_mel_tokens, j.noise = torch.as_tensor(text_tokens), cond, int(max_mel_tokens), noise
-        # takes: the job holds one row per take, row i * takes + j (text and conditioning repeated).  A sampled pipeline decodes every
-        # row; a beam pipeline decodes one group per utterance, queued as the utterance's first row, and reads its `takes` best
-        units = int(j.text.shape[0])
-        beam = self.num_beams > 1
-        j.takes, j.nbest = takes, takes if beam else 1
-        j.keep, j.lps = keep, None
-        # prefixes: one entry per row (the takes of an utterance share theirs)
-        j.prefix = None if pfx is None else [pfx[0][r // takes] for r in range(units * takes)]
-        j.prefix_lps = None if pfx is None else [pfx[1][r // takes] for r in range(units * takes)]
-        if takes > 1:
-            j.text = j.text.repeat_interleave(takes, 0)
-        B = units * takes
-        j.codes, j.left, j.failed = [None] * B, (units if beam else B), False
-        if keep is not None:
-            j.lps = [None] * B
-        j.done, j.notified = concurrent.futures.Future(), False
-        j.sampling, j.seq, j.noise_seeds = None, -1, None
-        j.priority, j.stamp = priority, [0] * B
-        j.deadline = None if deadline_s is None else self._clock() + deadline_s
-        try:                                    # a bad parameter fails this request's Future only
-            j.noise, j.noise_seeds = _request_noise(noise, noise_seed, B)
-            if per_utterance is not None:
-                j.sampling = per_utterance(units if beam else B)
-                if beam and takes > 1:
-                    j.sampling = [j.sampling[r // takes] for r in range(B)]
-            if takes > 1:
-                j.cond = _expand_cond(cond, takes)
-        except ValueError as e:
-            j.done.set_exception(e)
-            return j.done
-        j.caller = torch.cuda.current_stream(self.device) if self._cuda else None
-        j.ready = None
-        if self._cuda:
-            j.ready = torch.cuda.Event()
-            j.ready.record(j.caller)
-        with self._cv:
-            if self._closing or self._alive == 0:
-                raise RuntimeError("pipeline closed" if self._closing else "every decode lane has failed")
-            j.seq = self._submitted
-            self._submitted += 1
-            for i in range(0, B, j.nbest):
-                self._enqueue(j, i, None)
-            self._cv.notify_all()
-        return j.done
-
     @staticmethod
-    def _order(j: _Job, i: int, parked) -> tuple:
+    def _order(j: _Request, i: int, parked) -> tuple:
         """Where a waiting entry stands: higher priority first, parked rows ahead of never-admitted utterances of their priority, then
         submission order, then utterance index."""
         return (-j.priority, parked is None, j.seq, i)
 
-    def _enqueue(self, j: _Job, i: int, parked) -> None:
+    def _enqueue(self, j: _Request, i: int, parked) -> None:
         """Puts an entry into the waiting queue at its place (self._cv held); with every priority equal that is the end."""
         key, at = self._order(j, i, parked), len(self._waiting)
         while at > 0 and self._order(*self._waiting[at - 1]) > key:
             at -= 1
         self._waiting.insert(at, (j, i, parked))
-
-    @staticmethod
-    def _fail(j: _Job, e: BaseException) -> None:
-        j.failed = True
-        _set_exception(j.done, e)
 
     def cancel(self, fut: concurrent.futures.Future) -> bool:
         """fut.cancel(), and the lanes are woken so that the request is dropped at once.  True: the request is cancelled (see the
@@ -943,7 +940,7 @@ class ContinuousPipeline:
             self._cv.notify_all()
         return ok
 
-    def _gone(self, j: _Job) -> bool:
+    def _gone(self, j: _Request) -> bool:
         """Is there nobody left to decode `j` for -- cancelled (by its caller, or here: past its deadline) or failed?"""
         if j.deadline is not None and not j.done.done() and self._clock() >= j.deadline:
             j.done.cancel()                     # refused once the acoustic job has started: the request then completes
@@ -958,10 +955,9 @@ class ContinuousPipeline:
             for s in gone:
                 del in_slot[s]
 
-    def _prompt_rows(self, j: _Job, idx):
+    def _prompt_rows(self, j: _Request, idx):
         """The [P, d] prompts of utterances `idx` of a job (prepare_gpt_inputs, unpadded), on the current stream."""
-        if j.ready is not None:
-            torch.cuda.current_stream(self.device).wait_event(j.ready)
+        self._wait_ready(j)
         c = j.cond.to(self.device)
         lat = c.spk_cond_latent if c.spk_cond_latent.shape[0] == 1 else c.spk_cond_latent[idx]
         emo = c.emo_vec if c.emo_vec.shape[0] == 1 else c.emo_vec[idx]
@@ -973,6 +969,31 @@ class ContinuousPipeline:
         return sess.free_groups if self.num_beams > 1 else sess.free_slots
 
     def _admit(self, sess, in_slot) -> None:
+        """One poll's admission: choose, make room (park) and resume, build the new rows' admission, hand it to the session."""
+        take, victims = self._choose(sess, in_slot)
+        for s in victims:                       # their slots are free for `take` in this poll
+            self._park(sess, in_slot, s)
+        for j, i, parked in take:
+            if parked is not None:
+                self._resume(sess, in_slot, j, i, parked)
+        parts = self._admission([(j, i) for j, i, parked in take if parked is None])
+        if not parts:
+            return
+        owners = [o for p in parts for o in p.owners]
+        try:
+            got = self._session_admit(sess, parts)
+        except BaseException as e:           # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
+            for j, _ in owners:
+                self._fail(j, e)
+            return
+        with self._cv:
+            for s, (j, i) in zip(got, owners):
+                in_slot[s] = (j, i)
+                self._admitted += 1
+                j.stamp[i] = self._admitted
+
+    def _choose(self, sess, in_slot) -> tuple:
+        """The waiting entries this poll takes, in order, and the slots whose rows step aside for them: (take, victims)."""
         with self._cv:
             take, victims = [], []
             free = len(self._free(sess))
@@ -989,62 +1010,48 @@ class ContinuousPipeline:
                 if not room:
                     victims.append(rows[len(victims)])
                 take.append((j, i, parked))
-        for s in victims:                       # their slots are free for `take` in this poll
-            self._park(sess, in_slot, s)
-        for j, i, parked in take:
-            if parked is not None:
-                self._resume(sess, in_slot, j, i, parked)
+        return take, victims
+
+    def _admission(self, new) -> list:
+        """The never-admitted rows (request, row) this poll takes, as one _Part per utterance: the takes of one utterance taken in one
+        poll are one request with that many takes -- one prompt, one prefill.  A request whose prompts cannot be built (a bad token
+        id, too long) fails, alone."""
         by_job = collections.OrderedDict()
-        for j, i, parked in take:
-            if parked is None:
-                by_job.setdefault(id(j), (j, []))[1].append(i)
-        rows, caps, owners, samplers, counts, pfx, pfx_lp = [], [], [], [], [], [], []
-        for j, idx in by_job.values():
-            # the takes of one utterance taken in this poll are one request with that many takes: one prompt, one prefill
+        for j, i in new:
             share = j.takes if self.num_beams == 1 else 1
-            parts = collections.OrderedDict()
-            for i in idx:
-                parts.setdefault(i // share, []).append(i)
+            by_job.setdefault(id(j), (j, collections.OrderedDict()))[1].setdefault(i // share, []).append(i)
+        parts = []
+        for j, utts in by_job.values():
             try:
-                rs = self._prompt_rows(j, [p[0] for p in parts.values()])
-                if any(int(r.shape[0]) > self.max_prompt for r in rs):
+                prompts = self._prompt_rows(j, [p[0] for p in utts.values()])
+                if any(int(r.shape[0]) > self.max_prompt for r in prompts):
                     raise ValueError(f"prompt longer than the pipeline's max_prompt ({self.max_prompt})")
-            except BaseException as e:       # noqa: BLE001 -- the request's own error (bad token id, too long)
+            except BaseException as e:       # noqa: BLE001 -- the request's own error
                 self._fail(j, e)
                 continue
-            rows.extend(rs)
-            for p in parts.values():
-                counts.append(len(p))
-                pfx.append(None if j.prefix is None else j.prefix[p[0]])
-                pfx_lp.append(None if j.prefix is None else j.prefix_lps[p[0]])
-                caps.append([j.max_mel_tokens] * len(p))
-                owners.extend((j, i) for i in p)
-                if j.sampling is not None:
-                    samplers.append([j.sampling[i] for i in p])
-        if rows:
-            try:
-                if any(c is not None for c in pfx):      # some utterance continues from given codes: its takes share the prefix
-                    kw = {"sampling": samplers} if self.allow_sampling else {}
-                    if self.scores and any(l is not None for l in pfx_lp):
-                        kw["prefix_logprobs"] = pfx_lp
-                    got = [s for g in sess.admit(rows, caps, takes=counts, prefix=pfx, **kw) for s in g]
-                elif max(counts) > 1:           # (sampled pipelines only)
-                    got = [s for g in sess.admit(rows, caps, sampling=samplers, takes=counts) for s in g]
-                else:
-                    caps, samplers = [c[0] for c in caps], [e[0] for e in samplers]
-                    if self.num_beams > 1:
-                        got = sess.admit(rows, caps, beam=samplers)
-                    else:
-                        got = sess.admit(rows, caps, sampling=samplers) if self.allow_sampling else sess.admit(rows, caps)
-            except BaseException as e:       # noqa: BLE001 -- refused before any slot was taken: these requests fail, the lane goes on
-                for j, _ in owners:
-                    self._fail(j, e)
-                return
-            with self._cv:
-                for s, (j, i) in zip(got, owners):
-                    in_slot[s] = (j, i)
-                    self._admitted += 1
-                    j.stamp[i] = self._admitted
+            for prompt, p in zip(prompts, utts.values()):
+                parts.append(_Part(prompt, [(j, i) for i in p], [j.max_mel_tokens] * len(p),
+                                   None if j.sampling is None else [j.sampling[i] for i in p],
+                                   None if j.prefix is None else j.prefix[p[0]], None if j.prefix is None else j.prefix_lps[p[0]]))
+        return parts
+
+    def _session_admit(self, sess, parts) -> list:
+        """sess.admit in the form the parts need, each passing what it needs and nothing more -> the slots (a beam session: the
+        groups), one per row in the parts' order."""
+        rows, caps, counts = [p.prompt for p in parts], [p.caps for p in parts], [len(p.owners) for p in parts]
+        if any(p.prefix is not None for p in parts):      # some utterance continues from given codes: its takes share the prefix
+            kw = {"sampling": [p.samplers for p in parts]} if self.allow_sampling else {}
+            if self.scores and any(p.prefix_lps is not None for p in parts):
+                kw["prefix_logprobs"] = [p.prefix_lps for p in parts]
+            return [s for g in sess.admit(rows, caps, takes=counts, prefix=[p.prefix for p in parts], **kw) for s in g]
+        if max(counts) > 1:                     # (sampled pipelines only)
+            return [s for g in sess.admit(rows, caps, sampling=[p.samplers for p in parts], takes=counts) for s in g]
+        caps = [c[0] for c in caps]
+        if self.num_beams > 1:
+            return sess.admit(rows, caps, beam=[p.samplers[0] for p in parts])
+        if self.allow_sampling:
+            return sess.admit(rows, caps, sampling=[p.samplers[0] for p in parts])
+        return sess.admit(rows, caps)
 
     def _park(self, sess, in_slot, s) -> None:
         """Parks the row in slot s (a beam pipeline: the group s) and queues it for whichever lane next has room; a park that fails
@@ -1064,7 +1071,7 @@ class ContinuousPipeline:
             self._enqueue(j, i, parked)
             self._cv.notify_all()
 
-    def _resume(self, sess, in_slot, j: _Job, i: int, parked) -> None:
+    def _resume(self, sess, in_slot, j: _Request, i: int, parked) -> None:
         try:
             s = sess.resume_group(parked) if self.num_beams > 1 else sess.resume(parked)
         except BaseException as e:           # noqa: BLE001 -- this request's own failure: nothing was changed, the lane goes on
@@ -1109,7 +1116,7 @@ class ContinuousPipeline:
         try:
             if self._cuda:
                 torch.cuda.set_device(self.device)
-            stream = self._new_stream()
+            stream = self._stream("decode")
             with self._on(stream):
                 sess = self._factory(self.max_prompt, self.max_new)
                 while True:
@@ -1167,50 +1174,17 @@ class ContinuousPipeline:
                 if group:
                     return group
 
-    def _acoustic_drain(self):
-        group = self._take_acoustic()
-        if not group:
-            return
-        try:
-            if self._cuda:
-                torch.cuda.set_device(self.device)
-            t0 = time.perf_counter()
-            sa = getattr(self._tls, "stream", None)
-            if sa is None:
-                sa = self._tls.stream = self._new_stream()
-            stop = self.tts.cfg.gpt.stop_mel_token
-            states = []
-            with self._on(sa):
-                for j in group:                 # the latent pass per request (merging it would re-pad the text)
-                    n = max(int(c.shape[0]) for c in j.codes)
-                    codes = torch.full((len(j.codes), n), stop, dtype=torch.long)
-                    for i, c in enumerate(j.codes):
-                        codes[i, : c.shape[0]] = c
-                    if j.ready is not None:
-                        sa.wait_event(j.ready)
-                    states.append(self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens,
-                                                     repetition_penalty=self.repetition_penalty, codes=codes))
-                if len(group) == 1:
-                    st, noise = states[0], _noise_of(group[0])
-                else:
-                    st, noise = merge_acoustic_states([(j.cond, s, _noise_of(j)) for j, s in zip(group, states)])
-                wavs = _acoustic_call(self.tts, st, noise)
-                if sa is not None:
-                    sa.synchronize()
-            if self.trace is not None:
-                self.trace.append(("acoustic", t0, time.perf_counter(), sum(int(j.text.shape[0]) for j in group),
-                                   tuple(j.seq for j in group)))
-            a = 0
-            for j in group:
-                mine = wavs[a:a + int(j.text.shape[0])]
-                a += int(j.text.shape[0])
-                if j.caller is not None:
-                    for w in mine:              # allocated on the worker's stream, consumed on the caller's
-                        w.record_stream(j.caller)
-                j.done.set_result(mine if j.takes == 1 and j.keep is None else [mine[i:i + j.takes] for i in range(0, len(mine), j.takes)])
-        except BaseException as e:              # noqa: BLE001 -- every request of this acoustic batch fails, nothing else
-            for j in group:
-                self._fail(j, e)
+    def _acoustic_state(self, j: _Request) -> dict:
+        """The latent pass of a decoded request, on the acoustic worker (per request: merging it would re-pad the text)."""
+        n = max(int(c.shape[0]) for c in j.codes)
+        codes = torch.full((len(j.codes), n), self.tts.cfg.gpt.stop_mel_token, dtype=torch.long)
+        for i, c in enumerate(j.codes):
+            codes[i, : c.shape[0]] = c
+        self._wait_ready(j)
+        return self.tts.gpt_stage(j.text, j.cond, max_mel_tokens=j.max_mel_tokens, repetition_penalty=self.repetition_penalty, codes=codes)
+
+    def _acoustic_entry(self, t0: float, t1: float, rows: int, group) -> tuple:
+        return ("acoustic", t0, t1, rows, tuple(j.seq for j in group))
 
     def close(self):
         with self._cv:
@@ -1218,17 +1192,4 @@ class ContinuousPipeline:
             self._cv.notify_all()
         for t in self._lanes:
             t.join()
-        self._acoustic.shutdown(wait=True)
-        if self._cuda:
-            from . import _lib
-            with torch.cuda.device(self.device):
-                for s in self._streams:
-                    s.synchronize()
-                    _lib.release_stream(s)
-        self._streams = []
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._close_acoustic()

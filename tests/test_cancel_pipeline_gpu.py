@@ -170,7 +170,7 @@ def test_batch_pipeline_cancel_in_a_merged_acoustic_batch(setup):
                 assert held.in_acoustic.wait(WAIT)
                 a, b, d = (submit(pipe, n) for n in ("a", "b", "d"))
                 assert held.at_decode.wait(WAIT)            # one lane: a and b are decoded and queued by now
-                assert [r.done for r, _ in pipe._aq] == [a, b]
+                assert [r.done for r in pipe._aq] == [a, b]
                 assert a.cancel() is True and pipe.cancel(x) is False
                 held.go.set()
                 got = b.result(timeout=WAIT)

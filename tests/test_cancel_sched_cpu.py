@@ -5,6 +5,7 @@ is fixed by gates inside the stand-ins' `step`, static decode and `acoustic_stag
 import concurrent.futures
 import contextlib
 import threading
+from types import SimpleNamespace
 
 import pytest
 import torch
@@ -326,7 +327,7 @@ def test_batch_pipeline_merged_neighbours_and_accounting(hostonly):
         if tts.decode_gate.seen[-1] == 4:
             break
         tts.decode_gate.release()
-    assert tts.decode_gate.seen == [1, 2, 3, 4] and [r.done for r, _ in pipe._aq] == [a, b, c]
+    assert tts.decode_gate.seen == [1, 2, 3, 4] and [r.done for r in pipe._aq] == [a, b, c]
     e = pipe.submit(text((3, 5)), same, max_mel_tokens=100, noise_seed=1)
     assert b.cancel() is True and pipe.cancel(d) is True and pipe.cancel(e) is True
     assert pipe.cancel(x) is False
@@ -336,6 +337,20 @@ def test_batch_pipeline_merged_neighbours_and_accounting(hostonly):
     assert torch.equal(a.result(timeout=WAIT)[0], wave(3, 1))
     assert torch.equal(c.result(timeout=WAIT)[0], wave(3, 3))
     assert torch.equal(x.result(timeout=WAIT)[0], wave(2, 7))
+    # what submit refuses: a bad takes / keep raises there; a bad noise or noise_seed, or a conditioning that cannot be repeated per
+    # take, fails that request's Future only -- and none of them is ever queued
+    sampled = {"do_sample": True}
+    for kw in (dict(takes=0), dict(takes=2), dict(takes=2, sampling={"do_sample": False}), dict(keep=1), dict(sampling=sampled, takes=2, keep=3),
+               dict(sampling=sampled, takes=2, keep=0), dict(sampling={"do_sample": True, "num_beams": 2}, takes=2, keep=1)):
+        with pytest.raises(ValueError):
+            pipe.submit(text((3, 6)), same, max_mel_tokens=100, **kw)
+    per_row = SimpleNamespace(spk_cond_latent=torch.zeros(2, 3, 4), emo_vec=torch.zeros(2, 4))
+    for c, kw in ((same, dict(noise=torch.zeros(1, 2, 3), noise_seed=1)), (same, dict(noise_seed=[1, 2])), (same, dict(noise_seed=-1)),
+                  (same, dict(noise_seed="x")), (per_row, dict(sampling=sampled, takes=2, noise_seed=1))):
+        bad = pipe.submit(text((3, 6)), c, max_mel_tokens=100, **kw)
+        with pytest.raises(ValueError):
+            bad.result(timeout=WAIT)
+    assert [r.done for r in pipe._queue] == []
     pipe.close()
     assert b.cancelled() and d.cancelled() and e.cancelled()
     assert concurrent.futures.wait([b, d, e], timeout=WAIT).not_done == set()

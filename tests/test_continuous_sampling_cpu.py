@@ -124,12 +124,26 @@ def test_bad_parameters_fail_only_their_own_future():
             {"do_sample": True, "top_k": 0, "top_p": 0.5},
             {"do_sample": True, "sampler": "beam"},
             {"do_sample": True, "typical_p": 0.3})]
+        # takes of a request whose one conditioning holds a row per utterance: it cannot be repeated per take
+        per_row = SimpleNamespace(spk_cond_latent=torch.zeros(2, 2, 4), emo_vec=torch.zeros(2, 4))
+        bads.append(pipe.submit(torch.tensor([[5, 7], [5, 7]]), per_row, max_mel_tokens=5, sampling={"do_sample": True, "seed": 1}, takes=2))
         good2 = pipe.submit(torch.tensor([[5, 8], [5, 9]]), _cond(2), max_mel_tokens=5)
         for b in bads:
             with pytest.raises(ValueError):
                 b.result(timeout=60)
         assert len(good.result(timeout=60)) == 1 and len(good2.result(timeout=60)) == 2
     assert len(log) == 3          # only the good requests' utterances reached the session
+    # what says nothing about one request raises at submit: a closed pipeline, and one whose lanes have all failed
+    with pytest.raises(RuntimeError, match="pipeline closed"):
+        pipe.submit(torch.tensor([[5, 6]]), _cond(1), max_mel_tokens=5)
+
+    def no_session(mp, mn):
+        raise OSError("no device")
+    with ContinuousPipeline(FakeTTS(), slots=2, poll_steps=1, allow_sampling=True, session_factory=no_session) as dead:
+        for t in dead._lanes:
+            t.join(60)
+        with pytest.raises(RuntimeError, match="every decode lane has failed"):
+            dead.submit(torch.tensor([[5, 6]]), _cond(1), max_mel_tokens=5)
 
 
 def test_greedy_requests_reach_the_session_as_greedy():
