@@ -216,6 +216,26 @@ int idxtts_attention_bf16_fwd(const float* q, const float* k, const float* v, fl
 int idxtts_attention_relkey_fwd(const float* q, const float* k, const float* v, float* o, long batch_stride, int token_stride,
                                 long o_batch_stride, int o_token_stride, int B, int H, int S, const int* kend, float scale,
                                 const float* rel_key, int rel_left, int rel_right, int split_bf16, void* stream);
+/* The DiT attention of the s2mel stage in split-bf16 mode (calls of 256 rows and more), as an instrument on the caller's buffers:
+ * non-causal attention, head_dim 64, that reads q / k / v as SPLIT-BF16 PLANES of one [Mrows][ncols] projection output.
+ * Plane layout: element (row, col) of a [rows][cols] matrix lies at bf16 index ((col / 16) * rows + row) * 16 + col % 16 of the hi
+ * plane (16-column chunks, each [rows][16]); a plane has ceil(cols / 16) * rows * 16 elements and the lo plane follows the hi plane
+ * directly; hi = bf16(x) (nearest even), lo = bf16(x - hi).  `planes` (16-byte aligned) holds B batch rows of T rows each
+ * (B * T <= Mrows); q / k / v of head h are columns q_col / k_col / v_col + 64 h .. + 63 (each a multiple of 16, inside ncols).
+ * Queries of batch row b are rows b * T + q_row0 + [0, Sq) (q_row0 + Sq <= T), its keys rows b * T + [0, min(kend[b], T)); kend is
+ * a device int32 [B] or NULL (T keys everywhere); a batch row without keys gives zeros.
+ *   out[b][q] = softmax(scale * q k^T over the visible keys) v
+ * Contract on the data: the kernel loads whole 32-key tiles and masks afterwards, so the rows of `planes` behind a batch row's
+ * kend -- up to row Mrows - 1, the rows of the next batch row and any padding rows included -- must hold FINITE values in the k and v
+ * columns (a tile past row Mrows - 1 re-reads that last row).  Their values do not reach the output.
+ * Outputs, either or both (not both NULL): o, fp32, element (b, q, h, e) at o + b * o_batch_stride + q * o_token_stride + 64 h + e;
+ * o_planes, split-bf16 planes of the [B * Sq][64 H] output in the layout above (row b * Sq + q, column 64 h + e).
+ * one_product = 0: three bf16 MFMAs per product on hi + lo (q, k, v and P; relative error ~2^-16); 1: the hi planes alone, P rounded
+ * once to bf16, one MFMA per product (the lo planes of q / k / v are not read) -- whatever idxtts_set_acoustic_bf16 says: that switch
+ * picks the form for the s2mel stage, this entry takes it as a parameter.  B, H or Sq = 0: nothing is launched. */
+int idxtts_attention_planes_fwd(const void* planes, int Mrows, int ncols, int q_col, int k_col, int v_col, int T, int q_row0, int Sq, int B,
+                                int H, const int* kend, float scale, float* o, long o_batch_stride, int o_token_stride, void* o_planes,
+                                int one_product, void* stream);
 /* y = LayerNorm(x) * gamma + beta over the last dim (eps), rows of length d. */
 int idxtts_layernorm_fwd(const float* x, float* y, const float* gamma, const float* beta, int M, int d, float eps, void* stream);
 

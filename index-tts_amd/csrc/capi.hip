@@ -300,6 +300,19 @@ int idxtts_attention_bf16_fwd(const float* q, const float* k, const float* v, fl
   API_END
 }
 
+int idxtts_attention_planes_fwd(const void* planes, int Mrows, int ncols, int q_col, int k_col, int v_col, int T, int q_row0, int Sq, int B,
+                                int H, const int* kend, float scale, float* o, long o_batch_stride, int o_token_stride, void* o_planes,
+                                int one_product, void* stream) {
+  API_BEGIN
+  AttnPlanesArgs a;
+  a.planes = planes; a.Mrows = Mrows; a.ncols = ncols; a.q_col = q_col; a.k_col = k_col; a.v_col = v_col;
+  a.T = T; a.q_row0 = q_row0; a.Sq = Sq; a.B = B; a.H = H; a.kend = kend; a.scale = scale;
+  a.o = o; a.o_bs = o_batch_stride; a.o_ts = o_token_stride; a.o_planes = o_planes;
+  a.split_bf16 = one_product ? 2 : 1;
+  return flash_attn_planes_forward(a, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_layernorm_fwd(const float* x, float* y, const float* gamma, const float* beta, int M, int d, float eps, void* stream) {
   API_BEGIN
   RowsNormArgs n;

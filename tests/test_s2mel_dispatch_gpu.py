@@ -273,3 +273,31 @@ def test_estimator_switch_point_vs_float64_oracle(model, T, mode):
     print(f"estimator T = {T} {mode}: max |d| per row vs float64 oracle:", [f"{e:.2e}" for e in errs], f"scale {scale:.2f}")
     for b, e in enumerate(errs):
         assert e <= dc.ESTIMATOR_TOL[mode] * scale, (T, mode, b, e)
+
+
+def test_instrument_runs_the_solver_s_planes_attention(model, device):
+    """idxtts_attention_planes_fwd, which tests/test_attn_planes_gpu.py measures, launches the family the solver's planes path counts
+    (solver 2: 15 launches of flash_attn_planes_kernel, asserted by _check_signature above) and no other: one launch per call, in
+    either form."""
+    import numpy as np
+
+    import attn_planes_cases as ac
+    _, solver_prof = _run_solver(model, 2, "bf16x3")
+    assert solver_prof["flash_attn_planes_kernel"] == dc.STEPS * model.cfg.depth
+    s = ac.SHAPE["t33"]
+    c = ac.case("t33", "natural", 3)
+    planes = torch.from_numpy(ac.pack(c.x).view(np.int16)).to(device)
+    kend = torch.tensor(list(s.kend), dtype=torch.int32, device=device)
+    o = torch.full((s.B, s.Sq, s.d), float("nan"), device=device)
+
+    def instrument():
+        for one_product in (0, 1):
+            _lib.check(_lib.load().idxtts_attention_planes_fwd(planes.data_ptr(), s.Mrows, s.ncols, *s.cols, s.T, 0, s.Sq, s.B, s.H, _lib.ptr(kend),
+                                                               ac.SCALE, _lib.ptr(o), s.Sq * s.d, s.d, None, one_product, _lib.current_stream()))
+            if not one_product:
+                first = o.clone()
+        return first
+
+    out, prof = _call("bf16x3", instrument)
+    assert prof == {"flash_attn_planes_kernel": 2}, prof
+    assert np.abs(out.double().numpy() - c.ref).max() <= c.bound
