@@ -1021,6 +1021,36 @@ int idxtts_s2mel_cfm_rows(idxtts_ctx* ctx, const float* gen_cond, const int* tar
                           const float* dt, int n_steps, float cfg_rate, float* out, int B, int T, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* The mixed-prompt solve with an Euler schedule and a guidance rate PER ROW: a batch may hold rows of different quality tiers (say 8
+ * and 25 steps, guidance 0 and 0.7).  Inputs, output and layout are idxtts_s2mel_cfm_rows' (rows of one speaker point at the same
+ * tensors, so this entry serves single-prompt batches too).  The schedules:
+ *   sched_steps  HOST int32 [n_sched], each >= 1: the step counts of the n_sched >= 1 distinct schedules;
+ *   t_emb        device [sum of steps][256]: the schedules' timestep features one block after the other, in schedule order, each block
+ *                exactly what idxtts_s2mel_cfm takes for that n_steps;   dt  HOST [sum of steps], concatenated the same way;
+ *   row_sched    HOST int32 [B], each in [0, n_sched): row b's schedule;
+ *   cfg_rates    HOST fp32 [B], finite and >= 0: row b's inference_cfg_rate.  NEGATIVE rates are refused here, whereas the reference
+ *                treats them as 0 (flow_matching.py:87 tests `> 0`).
+ * The library draws no timestep itself: the caller's tables define the schedules.  Row b with schedule d = row_sched[b], S_b =
+ * sched_steps[d] steps and rate c_b: at iteration s < S_b the estimator evaluates the row with schedule d's step-s constants -- computed
+ * per schedule by the launches a call of that schedule alone makes, so they are that call's values -- and
+ *   c_b > 0:   x_b += dt[d][s] * ((1 + c_b) * v_cond - c_b * v_null)
+ *   c_b == 0:  x_b += dt[d][s] * v_cond      (the reference's else-branch, flow_matching.py:105-106: no null evaluation of that row exists)
+ * then x_b[..., :Tp_b] = 0.  From iteration S_b on the row is in no launch: iteration s runs on the rows with S_b > s, its null half on
+ * those of them with c_b > 0 (a call whose rows all have c_b == 0 evaluates one half per step), all live rows of a half in ONE launch of
+ * each kernel.  The two halves are two evaluations of their own, as under idxtts_s2mel_set_overlap(1) (and on two streams when it is on):
+ * in the exact fp32 mode a row's result is bit-identical to idxtts_s2mel_cfm_rows on that row with its steps and rate (c_b > 0); in the
+ * split-bf16 mode likewise while the row counts of the halves stay on the side of 256 rows the stacked batch is on.  The frames the
+ * post-transformer part skips are taken once, from the shortest prompt of the whole batch.
+ * Refused before anything is launched (idxtts_last_error names the cause; out is untouched): a null pointer; n_sched < 1 or a schedule with
+ * fewer than 1 step; a row_sched entry out of range; a cfg_rates entry that is negative, NaN or infinite; everything
+ * idxtts_s2mel_cfm_rows refuses; a workspace below idxtts_s2mel_cfm_sched_workspace_bytes(ctx, B, T, max_b Tp_b, n_sched, sched_steps)
+ * (0 for arguments it refuses). */
+size_t idxtts_s2mel_cfm_sched_workspace_bytes(const idxtts_ctx* ctx, int B, int T, int Tp_max, int n_sched, const int* sched_steps);
+int idxtts_s2mel_cfm_sched(idxtts_ctx* ctx, const float* gen_cond, const int* target_lens, int Tg_max, const float* const* prompt_conditions,
+                           const float* const* ref_mels, const int* prompt_lens, const float* style, const float* z, int n_sched,
+                           const int* sched_steps, const float* t_emb, const float* dt, const int* row_sched, const float* cfg_rates,
+                           float* out, int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The noise `z` of either solve from a counter-based generator, one seed per utterance: row b's element (c, t) is a pure function of
  * (seeds[b], c, t) -- t counted from the row's column 0, prompt frames included -- whatever batch, padding, row position or stream it is
  * produced in, so a request's audio is reproducible alone and merged.  With idx = (c << 32) | t, in arithmetic mod 2^64:

@@ -1071,6 +1071,23 @@ int idxtts_s2mel_cfm_rows(idxtts_ctx* ctx, const float* gen_cond, const int* tar
   API_END
 }
 
+size_t idxtts_s2mel_cfm_sched_workspace_bytes(const idxtts_ctx* ctx, int B, int T, int Tp_max, int n_sched, const int* sched_steps) {
+  if (!ctx || !ctx->finalized) return 0;
+  auto* m = dynamic_cast<const S2MelModel*>(ctx->model.get());
+  return m ? m->cfm_sched_workspace_bytes(B, T, Tp_max, n_sched, sched_steps) : 0;
+}
+
+int idxtts_s2mel_cfm_sched(idxtts_ctx* ctx, const float* gen_cond, const int* target_lens, int Tg_max, const float* const* prompt_conditions,
+                           const float* const* ref_mels, const int* prompt_lens, const float* style, const float* z, int n_sched,
+                           const int* sched_steps, const float* t_emb, const float* dt, const int* row_sched, const float* cfg_rates,
+                           float* out, int B, int T, void* workspace, size_t workspace_bytes, void* stream) {
+  API_BEGIN
+  S2MEL_MODEL(ctx);
+  return m->cfm_sched(gen_cond, target_lens, Tg_max, prompt_conditions, ref_mels, prompt_lens, style, z, n_sched, sched_steps, t_emb, dt,
+                      row_sched, cfg_rates, out, B, T, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+  API_END
+}
+
 int idxtts_s2mel_estimator(idxtts_ctx* ctx, const float* x, const float* prompt, const int* prompt_lens, int Tp_max, const int* x_lens,
                            const float* t_emb, const float* style, const float* mu, float* out, int B, int T, void* workspace,
                            size_t workspace_bytes, void* stream) {

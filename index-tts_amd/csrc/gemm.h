@@ -43,6 +43,10 @@ struct GemmArgs {
   int taps = 1, seq_len = 0, dil = 1, pad_left = 0, pad_mode = 0;
   // optional output row mask: rows with (m % seq_len) >= row_len[m / seq_len] are written as 0 (x * x_mask)
   const int* row_len = nullptr;
+  // optional per-sequence bias: row m adds w.bias[(m / seq_len) * ld_bias + n] instead of w.bias[n] (0: one bias for all rows).  Paired
+  // activations only (the WaveNet gate, whose conditioning bias is a function of each sequence's own timestep); every kernel runs it
+  // as an instantiation of its own, and adds the bias where and in the order the shared-bias instantiation does.
+  int ld_bias = 0;
   // exact-fp32 kernel only: split the K loop over `ksplit` workgroups per output tile (skinny GEMMs with a very long K:
   // the conformer's input projection, K = 261 632).  y then receives ksplit raw partial slabs [ksplit][M][ldy] -- no bias,
   // activation or residual -- which the caller sums in a fixed order (rows_norm_forward partials), so results stay

@@ -82,7 +82,9 @@ int StreamScratch::release(hipStream_t stream) {
 static StreamScratch g_sk_scratch;
 int gemm_release_stream_scratch(hipStream_t stream) { return g_plane_scratch.release(stream) || g_sk_scratch.release(stream); }
 
-__global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
+// SEQB: the per-sequence-bias epilogue (GemmArgs::ld_bias), a kernel of its own beside the one every other launch runs
+template <bool SEQB>
+__device__ __forceinline__ void gemm_tn_tile(const GemmKP& p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float (*Xs)[4 * 2 * 4 * XBLK] = reinterpret_cast<float (*)[4 * 2 * 4 * XBLK]>(smem);
   float (*Ws)[4 * 2 * 512] = reinterpret_cast<float (*)[4 * 2 * 512]>(smem + 2 * 4 * 2 * 4 * XBLK);
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
         for (int e = 0; e < 4; ++e) tot[u >> 3][(u >> 2) & 1][4 * (u & 3) + e] += v[e];
       }
     }
-    gemm_epilogue_t<2, 2>(p, tot, row0, col0, h, j);
+    gemm_epilogue_t<2, 2, SEQB>(p, tot, row0, col0, h, j);
     return;
   }
   if (p.ksplit > 1) {      // raw partial slab of this K range
@@ -222,8 +224,11 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) {
     gemm_epilogue_t<2, 2>(q, tot, row0, col0, h, j);
     return;
   }
-  gemm_epilogue_t<2, 2>(p, tot, row0, col0, h, j);
+  gemm_epilogue_t<2, 2, SEQB>(p, tot, row0, col0, h, j);
 }
+
+__global__ __launch_bounds__(256) void gemm_tn_kernel(const GemmKP p) { gemm_tn_tile<false>(p); }
+__global__ __launch_bounds__(256) void gemm_tn_seqbias_kernel(const GemmKP p) { gemm_tn_tile<true>(p); }
 
 int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* out, double* flops, double* bytes) {
   IDX_CHECK(a.M > 0 && w.N > 0 && w.K > 0, "bad shape");
@@ -235,6 +240,9 @@ int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* out, double*
     if (a.pad_mode == 1) IDX_CHECK(a.seq_len > (a.taps - 1) * a.dil, "reflect pad needs seq_len > halo");
   }
   if (a.row_len) IDX_CHECK(a.seq_len > 0, "row_len needs seq_len");
+  if (a.ld_bias)
+    IDX_CHECK(a.ld_bias >= w.N && w.bias && a.seq_len > 0 && a.M % a.seq_len == 0 && (a.act == ACT_SWIGLU || a.act == ACT_GATE) && a.ksplit <= 1,
+              "a per-sequence bias needs a bias table, seq_len rows per sequence and a paired activation");
   GemmKP p;
   p.x = a.x; p.wp = w.wp; p.bias = w.bias; p.res = a.res; p.y = a.y; p.y_hi = p.y_lo = nullptr; p.rope = nullptr; p.rope_T = 1; p.rope_cols = 0;
   p.M = a.M; p.N = w.N; p.K = w.K; p.ldx = a.ldx; p.ldy = a.ldy; p.ldr = a.ldr;
@@ -248,6 +256,7 @@ int gemm_prepare(const LinearWeights& w, const GemmArgs& a, GemmKP* out, double*
   p.pad_mode = a.pad_mode; p.row_len = a.row_len;
   p.ksplit = 1; p.ksteps_per_split = 0;
   p.kg = 0; p.direct_map = 0; p.sk_slab = nullptr; p.sk_cnt = nullptr; p.sk_slab_bytes = 0;
+  p.ld_bias = a.ld_bias;
   IDX_CHECK((int64_t)8 * p.nblocks * p.mt8 < (1ll << 31), "grid size");
   *out = p;
   *flops = 2.0 * a.M * (double)w.N * w.K;
@@ -294,8 +303,8 @@ int gemm_tn_forward(const LinearWeights& w, const GemmArgs& a, hipStream_t strea
   ProfScope prof(cat, stream, flops, bytes);
   constexpr size_t lds = (size_t)(2 * 4 * 2 * 4 * XBLK + 2 * 4 * 2 * 512) * sizeof(float);
   static DynLdsLimit lds_limit;
-  IDX_HIP(lds_limit.set((int)lds, gemm_tn_kernel));
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)grid, (unsigned)p.ksplit), dim3(256), lds, stream, p);
+  IDX_HIP(lds_limit.set((int)lds, gemm_tn_kernel, gemm_tn_seqbias_kernel));
+  hipLaunchKernelGGL(p.ld_bias ? gemm_tn_seqbias_kernel : gemm_tn_kernel, dim3((unsigned)grid, (unsigned)p.ksplit), dim3(256), lds, stream, p);
   IDX_LAUNCH_CHECK();
   return 0;
 }

@@ -63,8 +63,9 @@ void pack_linear_tiles(void* dst, const float* w, int N, int K) {
 // up <4, 2> and <4, 4>: the 128 x 128 tile needs 48 B/clk/CU of operand traffic at the bf16 MFMA rate (measured: a CU sustains ~13, L2
 // hit rate 66 %); doubling the rows a weight tile is applied to halves the weight traffic per flop and doubles the MFMA work per
 // barrier (one workgroup per CU, two waves per SIMD).  All three add a row's 32-k steps in the same MFMA order: the same sum, bit for bit.
-template <int WM /* waves along M: 2 or 4 */, int TN /* 32-column MFMA tiles per wave: 2 or 4 */>
-__global__ __launch_bounds__(128 * WM) void gemm_bf16x3_tile_kernel(const GemmKP p) {
+// SEQB: the per-sequence-bias epilogue (GemmArgs::ld_bias), kernels of their own beside the ones every other launch runs.
+template <int WM /* waves along M: 2 or 4 */, int TN /* 32-column MFMA tiles per wave: 2 or 4 */, bool SEQB>
+__device__ __forceinline__ void gemm_bf16x3_tile(const GemmKP& p) {
   constexpr int NT = 128 * WM, BM = 64 * WM, BN = 64 * TN;      // threads, rows and columns per workgroup
   constexpr int NB128 = BN / 128;             // packed 128-column weight tiles per k-step
   constexpr int A_HALF = BM * BROW;           // elements of one [BM][40] activation image
@@ -175,8 +176,11 @@ __global__ __launch_bounds__(128 * WM) void gemm_bf16x3_tile_kernel(const GemmKP
     if (has_next) store_tiles((ks + 1) & 1);
     __syncthreads();
   }
-  gemm_epilogue_t<2, TN>(p, acc, bm * BM + wm * 64, bn * BN + wn * 32 * TN, h, j);
+  gemm_epilogue_t<2, TN, SEQB>(p, acc, bm * BM + wm * 64, bn * BN + wn * 32 * TN, h, j);
 }
+
+template <int WM, int TN> __global__ __launch_bounds__(128 * WM) void gemm_bf16x3_tile_kernel(const GemmKP p) { gemm_bf16x3_tile<WM, TN, false>(p); }
+template <int WM, int TN> __global__ __launch_bounds__(128 * WM) void gemm_bf16x3_tile_seqbias_kernel(const GemmKP p) { gemm_bf16x3_tile<WM, TN, true>(p); }
 
 template <int WM, int TN>
 static int launch_tile(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipStream_t stream, double flops, double bytes) {
@@ -188,6 +192,18 @@ static int launch_tile(GemmKP p, const LinearWeights& w, const GemmArgs& a, hipS
   IDX_CHECK(grid < (1ll << 31), "grid size");
   constexpr size_t lds = (size_t)(2 * 2 * BM * BROW + 2 * NB128 * 2 * TILE_HALF) * sizeof(__bf16);
   static DynLdsLimit lds_limit;
+  if (p.ld_bias) {      // paired activations only (gemm_prepare): <2, 2> and <4, 2>
+    if constexpr (TN == 2) {
+      static DynLdsLimit lds_limit_sb;
+      IDX_HIP(lds_limit_sb.set((int)lds, gemm_bf16x3_tile_seqbias_kernel<WM, TN>));
+      static const int cat_sb = prof_register(WM == 2 ? "gemm_bf16x3_seqbias_kernel" : "gemm_bf16x3_big_seqbias_kernel<2>");
+      ProfScope prof(cat_sb, stream, flops, bytes);
+      hipLaunchKernelGGL((gemm_bf16x3_tile_seqbias_kernel<WM, TN>), dim3((unsigned)grid), dim3(128 * WM), lds, stream, p);
+      IDX_LAUNCH_CHECK();
+      return 0;
+    }
+    IDX_FAIL("a per-sequence bias on an unpaired tile");
+  }
   IDX_HIP(lds_limit.set((int)lds, gemm_bf16x3_tile_kernel<WM, TN>));
   // (the profile categories keep the names the three kernels had as two: committed profiles and tools read them)
   static const int cat = prof_register(WM == 2 ? "gemm_bf16x3_kernel" : TN == 2 ? "gemm_bf16x3_big_kernel<2>" : "gemm_bf16x3_big_kernel<4>");

@@ -506,6 +506,7 @@ int gemm_bf16x3_v2_forward(GemmKP p, const LinearWeights& w, const GemmArgs& a, 
   IDX_CHECK(!(a.rope && (a.res || paired)), "the rotary epilogue takes no residual and no paired activation");
   IDX_CHECK(!a.row_len || a.seq_len >= 16, "row masks need seq_len >= 16");
   const int epi = a.rope ? EPI_ROPE : paired ? EPI_PAIRED : a.act != ACT_NONE ? EPI_ACT : EPI_PLAIN;
+  IDX_CHECK(!a.ld_bias || (paired && a.taps > 1), "the LDS-DMA kernel takes a per-sequence bias in its paired convolution form");
   typedef void (*KernelFn)(const GemmV2P);
 #define V2_ROW(T, F, P) gemm_bf16x3_v2_kernel<T, EPI_PLAIN, F, P>, gemm_bf16x3_v2_kernel<T, EPI_ROPE, F, P>, gemm_bf16x3_v2_kernel<T, EPI_PAIRED, F, P>, gemm_bf16x3_v2_kernel<T, EPI_ACT, F, P>
   // the main loop's MFMA shape comes with the weights (model_util.h: WP16_ALWAYS_MF16): 16x16x32 is 1.5-7 % faster on six of eight
@@ -521,7 +522,13 @@ int gemm_bf16x3_v2_forward(GemmKP p, const LinearWeights& w, const GemmArgs& a, 
 #ifdef V2_EXP_SHAPE
   if (const char* e = getenv("IDXTTS_EXP_V2_SHAPE")) mf16 = atoi(e) == 16;      // tools/gemm_ab.py's scratch build only
 #endif
-  const KernelFn kernel = kernels[a.bf16_products == 1 ? 2 : mf16][a.taps > 1 ? 1 : 0][epi];
+  // the per-sequence bias (GemmArgs::ld_bias): the paired convolution form of each loop, instantiations of their own
+  static const KernelFn seqbias_kernels[3] = {gemm_bf16x3_v2_kernel<true, EPI_PAIRED_SEQB, 32, 3>, gemm_bf16x3_v2_kernel<true, EPI_PAIRED_SEQB, 16, 3>,
+                                              gemm_bf16x3_v2_kernel<true, EPI_PAIRED_SEQB, 16, 1>};
+  static DynLdsLimit lds_limit_sb;
+  if (a.ld_bias) IDX_HIP(lds_limit_sb.set(lds, seqbias_kernels[0], seqbias_kernels[1], seqbias_kernels[2]));
+  const int loop = a.bf16_products == 1 ? 2 : mf16;
+  const KernelFn kernel = a.ld_bias ? seqbias_kernels[loop] : kernels[loop][a.taps > 1 ? 1 : 0][epi];
 #undef V2_ROW
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds, stream, q);
   IDX_LAUNCH_CHECK();

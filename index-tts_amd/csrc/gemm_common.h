@@ -65,6 +65,7 @@ struct GemmKP {
   // one-workgroup form.  direct_map: tiles dealt to consecutive workgroup ids (= round-robin over the XCDs) instead of the XCD-aware walk.
   int kg, direct_map;
   float* sk_slab; unsigned* sk_cnt; int sk_slab_bytes;
+  int ld_bias;     // per-sequence bias (GemmArgs::ld_bias): read by the SEQB instantiations only
 };
 
 
@@ -154,7 +155,8 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 //   row = row0 + mt*32 + (r&3) + 8*(r>>2) + 4*h,  packed column = col0 + nt*32 + j
 // (row0/col0 = first row / first packed column of the wave's tile).  Bias, activation or paired gate
 // (tiles (2q, 2q+1) = [gate | linear]), residual, row mask, store.
-template <int TM, int TN>
+// SEQB: the bias of row m is row m / seq_len of a [sequences][ld_bias] table (GemmArgs::ld_bias; paired activations only).
+template <int TM, int TN, bool SEQB = false>
 __device__ __forceinline__ void gemm_epilogue_t(const GemmKP& p, f32x16 (&acc)[TM][TN], int row0, int col0, int h, int j) {
   auto row_masked = [&](int m) -> bool {
     if (!p.row_len) return false;
@@ -168,13 +170,17 @@ __device__ __forceinline__ void gemm_epilogue_t(const GemmKP& p, f32x16 (&acc)[T
       const int n0 = col0 + q * 64 + j;               // packed column of the gate
       const int no = ((col0 + q * 64) >> 1) + j;      // output column
       const bool ok = (col0 + q * 64) < p.N;          // N % 64 == 0: 64 packed columns are all in or all out
-      const float b0 = (p.bias && ok) ? p.bias[n0] : 0.0f, b1 = (p.bias && ok) ? p.bias[n0 + 32] : 0.0f;
+      float b0 = (!SEQB && p.bias && ok) ? p.bias[n0] : 0.0f, b1 = (!SEQB && p.bias && ok) ? p.bias[n0 + 32] : 0.0f;
 #pragma unroll
       for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int m = row0 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
           if (m >= p.M || !ok) continue;
+          if (SEQB) {
+            const float* bs = p.bias + (size_t)(m / p.seq_len) * p.ld_bias;
+            b0 = bs[n0]; b1 = bs[n0 + 32];
+          }
           const float gte = acc[mt][2 * q][r] + b0, lin = acc[mt][2 * q + 1][r] + b1;
           float v = p.act == ACT_SWIGLU ? (gte / (1.0f + expf(-gte))) * lin : tanhf(gte) * (1.0f / (1.0f + expf(-lin)));
           v *= p.out_scale;
@@ -241,7 +247,8 @@ __device__ __forceinline__ float act_apply_fast(float v, int act) {
 //   EPI_ACT     any other activation (rolled loops, operands loaded in place: the rare shapes)
 // All waves of the workgroup must call it (one __syncthreads inside, behind the operand requests); `lds_base` = the workgroup's
 // LDS (>= waves x 16 x (wave columns + 4) floats), no DMA in flight.
-enum { EPI_PLAIN = 0, EPI_ROPE = 1, EPI_PAIRED = 2, EPI_ACT = 3 };
+//   EPI_PAIRED_SEQB  EPI_PAIRED with the bias of row m read from row m / seq_len of a [sequences][ld_bias] table (GemmArgs::ld_bias)
+enum { EPI_PLAIN = 0, EPI_ROPE = 1, EPI_PAIRED = 2, EPI_ACT = 3, EPI_PAIRED_SEQB = 4 };
 
 // write_pass(ps, lds, RS): stores rows 16 ps .. 16 ps + 15 of the wave's accumulator tile into lds[row * RS + column] -- the one
 // place that knows the MFMA shape's C/D layout (32x32 or 16x16 tiles).
@@ -249,7 +256,8 @@ template <int EPI, int TN, int PF, class WritePass>      // PF: passes whose row
 __device__ __forceinline__ void gemm_epilogue_wave(const GemmKP& p, WritePass&& write_pass, float* lds_base, const int row0, const int col0,
                                                    const int wave, const int lane) {
   constexpr int WC = 32 * TN;                   // packed columns of the wave's tile (128 or 64)
-  constexpr bool PAIRED = EPI == EPI_PAIRED;
+  constexpr bool SEQB = EPI == EPI_PAIRED_SEQB;
+  constexpr bool PAIRED = EPI == EPI_PAIRED || SEQB;
   constexpr bool PREF = EPI != EPI_ACT;         // residual / rotary rows prefetched into registers
   constexpr int RS = WC + 4;                    // floats per LDS row: + 4 (row r + 1 starts one 16-byte slot further)
   constexpr int LPR = PAIRED ? WC / 8 : WC / 4; // lanes per row
@@ -271,7 +279,7 @@ __device__ __forceinline__ void gemm_epilogue_wave(const GemmKP& p, WritePass&& 
   const bool vec = col_ok && n_out + 3 < n_lim && ((p.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.y) & 15) == 0) &&
                    (!p.res || (((p.ldr & 3) == 0) && ((reinterpret_cast<uintptr_t>(p.res) & 15) == 0)));
   f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = b0;
-  if (p.bias && col_ok) {
+  if (!SEQB && p.bias && col_ok) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (nb0 + e < p.N) b0[e] = p.bias[nb0 + e];
@@ -314,9 +322,15 @@ __device__ __forceinline__ void gemm_epilogue_wave(const GemmKP& p, WritePass&& 
     auto body = [&](const int rr, const f32x4 opnd) {
       const int m = row0 + ps * 16 + rr;
       if (m >= p.M || !col_ok) return;
-      f32x4 v = *reinterpret_cast<const f32x4*>(lds + rr * RS + lcol) + b0;
+      f32x4 bg = b0, bl = b1;
+      if (SEQB) {      // (nb0, nb1 + 3 < N: N % 64 == 0 for paired activations)
+        const float* bs = p.bias + (size_t)(m / p.seq_len) * p.ld_bias;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { bg[e] = bs[nb0 + e]; bl[e] = bs[nb1 + e]; }
+      }
+      f32x4 v = *reinterpret_cast<const f32x4*>(lds + rr * RS + lcol) + bg;
       if (PAIRED) {
-        const f32x4 lin = *reinterpret_cast<const f32x4*>(lds + rr * RS + lcol + 32) + b1;
+        const f32x4 lin = *reinterpret_cast<const f32x4*>(lds + rr * RS + lcol + 32) + bl;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           v[e] = p.act == ACT_SWIGLU ? (v[e] * sigmoid_fast(v[e])) * lin[e] : tanh_fast(v[e]) * sigmoid_fast(lin[e]);

@@ -53,6 +53,12 @@ struct S2MelModel : ModelBase {
   int cfm_rows(const float* gen_cond, const int* target_lens_host, int Tg_max, const float* const* prompt_cond_host,
                const float* const* ref_mel_host, const int* prompt_lens_host, const float* style, const float* z, const float* t_emb,
                const float* dt_host, int n_steps, float cfg_rate, float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
+  // per-row Euler schedules and guidance rates (idxtts_s2mel_cfm_sched): cfm_rows' inputs and output, each row with its own steps and rate
+  size_t cfm_sched_workspace_bytes(int B, int T, int Tp_max, int n_sched, const int* sched_steps) const;
+  int cfm_sched(const float* gen_cond, const int* target_lens_host, int Tg_max, const float* const* prompt_cond_host,
+                const float* const* ref_mel_host, const int* prompt_lens_host, const float* style, const float* z, int n_sched,
+                const int* sched_steps, const float* t_emb, const float* dt_host, const int* row_sched, const float* cfg_rates, float* out,
+                int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
   int estimator(const float* x, const float* prompt, const int* prompt_lens_host, int Tp_max, const int* x_lens_host, const float* t_emb,
                 const float* style, const float* mu, float* out_tm, int B, int T, void* ws, size_t ws_bytes, hipStream_t st);
   size_t cond_workspace_bytes(int B, int M, int Tg) const;

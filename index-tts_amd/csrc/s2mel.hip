@@ -15,6 +15,7 @@
 //   with M = n_steps; cond_projection(mu) is computed once per call.  The reference recomputes all of them
 //   in every step (diffusion_transformer.py:212-213, wavenet.py:142-152).
 // CFG: the [cond | null] stacking of flow_matching.py:89-93 is kept (2B rows per step).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -294,14 +295,19 @@ static RowSet row_set(const S2MelModel& m, const CfmBuffers& w, int nseq, int se
   return r;
 }
 
-// adaLN-RMSNorm of x into the set's hn; mod: the (weight, bias) pair of this norm and step
-static int ada_norm(const S2MelModel& m, const float* x, const float* g, const float* mod, const RowSet& r, hipStream_t st) {
+// The t-only constants of ONE estimator evaluation: the 2 * depth + 1 adaLN (weight, bias) pairs, the FinalLayer (shift, scale) and the
+// WaveNet conditioning biases of all layers.  ld == 0: one step's vectors, shared by every sequence (the solver of one schedule);
+// ld > 0: one row per sequence, [nseq][ld] tables (per-row schedules: cfm_sched gathers each live row's own step).
+struct StepConsts { const float* mods; int ld_mods; const float* fmod; int ld_fmod; const float* wnb; int ld_wnb; };
+
+// adaLN-RMSNorm of x into the set's hn; mod: the (weight, bias) pair of this norm and step, ld_mod apart from sequence to sequence
+static int ada_norm(const S2MelModel& m, const float* x, const float* g, const float* mod, int ld_mod, const RowSet& r, hipStream_t st) {
   const int D = m.cfg.hidden_dim;
   const Dst hn = r.hn_out();
   RowsNormArgs n;
   n.x_in = x; n.ld_in = D; n.y = hn.f; n.y_planes = hn.p; n.ld_y = D; n.M = r.rows; n.d = D;
   n.mode = NORM_ADA_RMS; n.eps = m.cfg.norm_eps; n.g1 = g;
-  n.mod_a = mod; n.mod_b = mod + D; n.ld_mod = 0; n.rows_per_batch = 0;
+  n.mod_a = mod; n.mod_b = mod + D; n.ld_mod = ld_mod; n.rows_per_batch = ld_mod ? r.seq : 0;
   return rows_norm_forward(n, st);
 }
 
@@ -330,13 +336,13 @@ static int attention(const S2MelModel& m, const RowSet& all, bool qkv_planes, in
 // attention output, wo, norm, w13, w2 -- on `post`: all frames again, or, in the last block of a compacted tail, whose keys and
 // values cover every frame but whose output nothing attends to, the tail rows alone.  res: h on post's rows: h itself, or the
 // buffer the block gathers h's tail rows into.  lag_event (optional) is recorded behind the attention.
-static int dit_block(S2MelModel& m, int i, const float* mods, const float* h, const RowSet& all, const RowSet& post, float* res, Dst out,
+static int dit_block(S2MelModel& m, int i, const float* mods, int ld_mods, const float* h, const RowSet& all, const RowSet& post, float* res, Dst out,
                      hipEvent_t lag_event, hipStream_t st) {
   const auto& c = m.cfg;
   const CfmBuffers& w = *all.w;
   const DiTBlock& B = m.blocks[i];
   const int D = c.hidden_dim, T = all.seq, q0 = T - post.seq;
-  if (ada_norm(m, h, B.attn_g, mods + (size_t)(2 * i) * 2 * D, all, st)) return 1;
+  if (ada_norm(m, h, B.attn_g, mods + (size_t)(2 * i) * 2 * D, ld_mods, all, st)) return 1;
   bool qkv_planes = false;
   {     // qkv projection; the rotary embedding of q and k rides in its epilogue when the LDS-DMA kernel runs it
     GemmArgs g = gemm_args(all.hn_in(), D, w.qkv, 3 * D, all.rows);
@@ -353,17 +359,17 @@ static int dit_block(S2MelModel& m, int i, const float* mods, const float* h, co
   if (lag_event) IDX_HIP(hipEventRecord(lag_event, st));
   if (res != h && gather_tail_rows(res, D, h, D, D, all.nseq, T, q0, st)) return 1;
   if (gemm(B.wo, post.att_in(), D, w.hmid, D, post.rows, st, ACT_NONE, res, D)) return 1;           // h + attention(...)
-  if (ada_norm(m, w.hmid, B.ffn_g, mods + (size_t)(2 * i + 1) * 2 * D, post, st)) return 1;
+  if (ada_norm(m, w.hmid, B.ffn_g, mods + (size_t)(2 * i + 1) * 2 * D, ld_mods, post, st)) return 1;
   if (gemm(B.w13, post.hn_in(), D, post.ff_out(), m.ffn, post.rows, st, ACT_SWIGLU)) return 1;
   return gemm(B.w2, post.ff_in(), m.ffn, out, D, post.rows, st, ACT_NONE, w.hmid, D);               // out = h + ffn
 }
 
 // N2 sequences of T frames (one CFG half, or the stacked batch); lag_event (optional) is recorded behind the first attention
-static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipStream_t st, hipEvent_t lag_event) {
+static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, const StepConsts& sc, hipStream_t st, hipEvent_t lag_event) {
   const auto& c = m.cfg;
   const int D = c.hidden_dim, C = c.in_channels, Wh = c.wn_hidden, depth = c.depth, half = depth / 2;
   const int Win = 2 * C + D + c.style_dim;
-  const float* mods = w.mods + (size_t)step * (2 * depth + 1) * 2 * D;
+  const float* mods = sc.mods;
   // The solver needs the estimate only on the frames t >= tail_t0 (see below): the post-transformer part and, in the LAST block,
   // everything after the K/V projection run on those frames alone, compacted to [N2][T - tail_t0] rows.
   const int t0 = w.tail_t0;
@@ -388,7 +394,7 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
     // the last block of a compacted tail gathers its residual rows into xres (free here) and leaves h on the tail rows; it is
     // never a skip push (depth - 1 >= depth / 2), so with t0 > 0 h always leaves the loop compacted
     const bool cut = i == depth - 1 && t0 > 0;
-    if (dit_block(m, i, mods, h, all, cut ? tail : all, cut ? w.xres : h, out, i == 0 && !cut ? lag_event : nullptr, st)) return 1;
+    if (dit_block(m, i, mods, sc.ld_mods, h, all, cut ? tail : all, cut ? w.xres : h, out, i == 0 && !cut ? lag_event : nullptr, st)) return 1;
     if (i < half) ++pushed;
     h = out.f;
   }
@@ -404,7 +410,7 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
     if (gather_tail_rows(w.qkv, C, w.x_in, Win, C, N2, T, t0, st)) return 1;      // the x columns of x_in (qkv is free here)
     xin_t = w.qkv; ld_xin = C;
   }
-  if (ada_norm(m, h, m.final_g, mods + (size_t)(2 * depth) * 2 * D, tail, st)) return 1;
+  if (ada_norm(m, h, m.final_g, mods + (size_t)(2 * depth) * 2 * D, sc.ld_mods, tail, st)) return 1;
   // long skip: skip_linear(cat[x_res, x]) (diffusion_transformer.py:243-244); x rows live in x_in[:, :C]
   if (gemm(m.skiplin_a, tail.hn_in(), D, w.hmid, D, Mt, st)) return 1;
   if (gemm(m.skiplin_b, xin_t, ld_xin, tail.xres_out(), D, Mt, st, ACT_NONE, w.hmid, D)) return 1;
@@ -416,8 +422,9 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
     int dil = 1;
     for (int q = 0; q < l; ++q) dil *= c.wn_dilation_rate;
     LinearWeights in = W.in_gate;
-    in.bias = w.wnb + ((size_t)step * L + l) * 2 * Wh;     // in_layer bias + g_l of this step, gate-packed
+    in.bias = sc.wnb + (size_t)l * 2 * Wh;     // in_layer bias + g_l of this step (of every sequence's own step), gate-packed
     GemmArgs g = gemm_args(tail.wnx_in(), Wh, tail.acts_out(), Wh, Mt, ACT_GATE);
+    g.ld_bias = sc.ld_wnb;
     g.taps = k; g.seq_len = Tt; g.dil = dil; g.pad_left = (k - 1) / 2 * dil; g.pad_mode = 1; g.row_len = tail.lens;
     if (gemm_forward(in, g, st)) return 1;
     if (W.has_res) {   // x = (x + res) * mask
@@ -435,7 +442,7 @@ static int dit_eval(S2MelModel& m, CfmBuffers& w, int N2, int T, int step, hipSt
     const Dst hn = tail.hn_out();
     RowsNormArgs n;     // FinalLayer (diffusion_transformer.py:96-101)
     n.x_in = w.hmid; n.ld_in = Wh; n.y = hn.f; n.y_planes = hn.p; n.ld_y = Wh; n.M = Mt; n.d = Wh; n.mode = NORM_MOD_LN; n.eps = 1e-6f;
-    n.mod_a = w.fmod + (size_t)step * 2 * Wh; n.mod_b = n.mod_a + Wh; n.ld_mod = 0; n.rows_per_batch = 0;
+    n.mod_a = sc.fmod; n.mod_b = n.mod_a + Wh; n.ld_mod = sc.ld_fmod; n.rows_per_batch = sc.ld_fmod ? Tt : 0;
     if (rows_norm_forward(n, st)) return 1;
   }
   if (gemm(m.final_lin, tail.hn_in(), Wh, w.att, Wh, Mt, st)) return 1;
@@ -508,23 +515,42 @@ static bool halves_on_two_streams(hipStream_t st) {
   return g_s2mel_overlap && !prof_enabled() && cap == hipStreamCaptureStatusNone;     // (per-launch event timing wants kernels alone)
 }
 
-// one estimator evaluation of the solver: both CFG halves, on two streams (two_streams) or stacked
-static int dit_eval_halves(S2MelModel& m, CfmBuffers& w, int B, int T, int step, bool two_streams, hipStream_t st) {
-  if (!two_streams) return dit_eval(m, w, 2 * B, T, step, st, nullptr);
-  CfmBuffers v0 = half_view(m.cfg, m.ffn, w, 0, B, T);
-  CfmBuffers v1 = half_view(m.cfg, m.ffn, w, 1, B, T);
+// the constants of step `step` of the call's one schedule, shared by all sequences
+static StepConsts shared_step(const S2MelModel& m, const CfmBuffers& w, int step) {
+  const auto& c = m.cfg;
+  return {w.mods + (size_t)step * (2 * c.depth + 1) * 2 * c.hidden_dim, 0, w.fmod + (size_t)step * 2 * c.wn_hidden, 0,
+          w.wnb + (size_t)step * c.wn_layers * 2 * c.wn_hidden, 0};
+}
+
+// The two CFG halves as two evaluations of their own, N0 conditional and N1 null sequences (N1 may be 0: no row asks for guidance) in
+// the half views v0 / v1: on two streams (two_streams), or one behind the other on the caller's.
+static int dit_eval_two(S2MelModel& m, CfmBuffers& v0, int N0, const StepConsts& c0, CfmBuffers& v1, int N1, const StepConsts& c1, int T,
+                        bool two_streams, hipStream_t st) {
+  if (!two_streams || N1 == 0) {
+    if (dit_eval(m, v0, N0, T, c0, st, nullptr)) return 1;
+    return N1 ? dit_eval(m, v1, N1, T, c1, st, nullptr) : 0;
+  }
   HalfStreams hs;
   if (half_streams_for(st, &hs)) return 1;
   IDX_HIP(hipEventRecord(hs.fork, st));
   IDX_HIP(hipStreamWaitEvent(hs.side, hs.fork, 0));
   // the null half starts when the conditional half has finished its first attention (a few kernels in): from then on the two
   // chains stay that far apart
-  if (dit_eval(m, v0, B, T, step, st, hs.lag)) return 1;
+  if (dit_eval(m, v0, N0, T, c0, st, hs.lag)) return 1;
   IDX_HIP(hipStreamWaitEvent(hs.side, hs.lag, 0));
-  if (dit_eval(m, v1, B, T, step, hs.side, nullptr)) return 1;
+  if (dit_eval(m, v1, N1, T, c1, hs.side, nullptr)) return 1;
   IDX_HIP(hipEventRecord(hs.join, hs.side));
   IDX_HIP(hipStreamWaitEvent(st, hs.join, 0));
   return 0;
+}
+
+// one estimator evaluation of the solver: both CFG halves, on two streams (two_streams) or stacked
+static int dit_eval_halves(S2MelModel& m, CfmBuffers& w, int B, int T, int step, bool two_streams, hipStream_t st) {
+  const StepConsts sc = shared_step(m, w, step);
+  if (!two_streams) return dit_eval(m, w, 2 * B, T, sc, st, nullptr);
+  CfmBuffers v0 = half_view(m.cfg, m.ffn, w, 0, B, T);
+  CfmBuffers v1 = half_view(m.cfg, m.ffn, w, 1, B, T);
+  return dit_eval_two(m, v0, B, sc, v1, B, sc, T, true, st);
 }
 
 int S2MelModel::cfm(const float* mu, const int* x_lens_host, const float* prompt, const int* prompt_lens_host, int Tp_max,
@@ -674,6 +700,147 @@ int S2MelModel::cfm_rows(const float* gen_cond, const int* target_lens_host, int
   return cfm_rows_emit(out, w.xstate, w.plen, r.gen_len, B, cfg.in_channels, T, Tg_max, st);
 }
 
+// ---- per-row schedules: every row with its own Euler steps and guidance rate (idxtts_s2mel_cfm_sched) ----------------------------
+// The rows are kept in an order of the solver's own: by descending step count (stable), so that the rows still live at iteration s
+// are the first n_live(s) slots, and the rows of the null half -- those with a rate > 0, in the same order -- the first n_null(s) of
+// their list.  An iteration is cfm_solve's: pack, estimator, Euler update; each half is an evaluation of its own on its live rows
+// (dit_eval_two), with the step constants of each row's own schedule gathered into [rows][cols] tables.  THIS routine is the one
+// place that builds the row maps; the kernels that read them are cfm_rows_pack (gen_row), cfm_init_state_rows, cfm_pack_half,
+// cfm_gather_consts, cfm_euler_rows and cfm_rows_emit_map.
+size_t S2MelModel::cfm_sched_workspace_bytes(int B, int T, int Tp_max, int n_sched, const int* sched_steps) const {
+  if (B <= 0 || T <= 0 || Tp_max <= 0 || n_sched < 1 || !sched_steps) return 0;
+  long total = 0;
+  int smax = 0;
+  for (int d = 0; d < n_sched; ++d) {
+    if (sched_steps[d] < 1) return 0;
+    total += sched_steps[d];
+    smax = std::max(smax, sched_steps[d]);
+  }
+  if (total > (1 << 20)) return 0;
+  return carve_cfm_sched(cfg, nullptr, cfm_rows_workspace_bytes(B, T, Tp_max, (int)total), B, smax).bytes;
+}
+
+int S2MelModel::cfm_sched(const float* gen_cond, const int* target_lens_host, int Tg_max, const float* const* prompt_cond_host,
+                          const float* const* ref_mel_host, const int* prompt_lens_host, const float* style, const float* z, int n_sched,
+                          const int* sched_steps, const float* t_emb, const float* dt_host, const int* row_sched, const float* cfg_rates,
+                          float* out, int B, int T, void* ws, size_t ws_bytes, hipStream_t st) {
+  IDX_CHECK(gen_cond && target_lens_host && prompt_cond_host && ref_mel_host && prompt_lens_host && style && z && sched_steps && t_emb &&
+            dt_host && row_sched && cfg_rates && out, "null pointer");
+  IDX_CHECK(B > 0 && T > 0 && Tg_max > 0, "shape");
+  IDX_CHECK(n_sched >= 1, "n_sched must be at least 1");
+  std::vector<int> first(n_sched);      // first row of schedule d in the concatenated tables
+  int total = 0, smax = 0;
+  for (int d = 0; d < n_sched; ++d) {
+    IDX_CHECK(sched_steps[d] >= 1 && sched_steps[d] <= (1 << 20) - total, "a schedule needs at least 1 step");
+    first[d] = total;
+    total += sched_steps[d];
+    smax = std::max(smax, sched_steps[d]);
+  }
+  for (int b = 0; b < B; ++b) {
+    IDX_CHECK(row_sched[b] >= 0 && row_sched[b] < n_sched, "row_sched entry out of range");
+    IDX_CHECK(std::isfinite(cfg_rates[b]) && cfg_rates[b] >= 0.0f, "cfg_rates must be finite and >= 0 (negative rates are refused)");
+  }
+  IDX_CHECK(T <= rope_len, "sequence longer than the rope cache");
+  IDX_CHECK(cfg.content_dim % 4 == 0 && ((uintptr_t)gen_cond & 15) == 0, "gen_cond must be 16-byte aligned (content_dim % 4 == 0)");
+  // slot i = the caller's row order[i]: descending steps, stable
+  std::vector<int> order(B);
+  for (int b = 0; b < B; ++b) order[b] = b;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sched_steps[row_sched[a]] > sched_steps[row_sched[b]]; });
+  std::vector<int> xl(B), tg(B), pl(B), steps(B);
+  std::vector<const float*> pcond(B), refmel(B);
+  int Tp_max = 0, T_need = 0, pmin = 0;
+  for (int i = 0; i < B; ++i) {
+    const int b = order[i], Tp = prompt_lens_host[b], Tg = target_lens_host[b];
+    IDX_CHECK(Tp > 0 && Tg > 0 && Tg <= Tg_max, "prompt_lens / target_lens out of range");
+    IDX_CHECK(prompt_cond_host[b] && ref_mel_host[b], "null prompt table entry");
+    IDX_CHECK(((uintptr_t)prompt_cond_host[b] & 15) == 0, "prompt_condition rows must be 16-byte aligned");
+    xl[i] = Tp + Tg; tg[i] = Tg; pl[i] = Tp; steps[i] = sched_steps[row_sched[b]];
+    pcond[i] = prompt_cond_host[b]; refmel[i] = ref_mel_host[b];
+    Tp_max = std::max(Tp_max, Tp);
+    T_need = std::max(T_need, Tp + Tg);
+    pmin = i ? std::min(pmin, Tp) : Tp;
+  }
+  IDX_CHECK(T == T_need, "T must be max_b(prompt_lens[b] + target_lens[b])");
+  IDX_CHECK(ws && ws_bytes >= cfm_sched_workspace_bytes(B, T, Tp_max, n_sched, sched_steps), "workspace too small");
+  CfmBuffers w = carve_cfm(cfg, ffn, ws, B, T, total);
+  CfmRowsBuffers r = carve_cfm_rows(*this, ws, w.bytes, B, T, Tp_max);
+  CfmSchedBuffers sb = carve_cfm_sched(cfg, ws, r.bytes, B, smax);
+  // ---- the row maps and per-slot tables (host), uploaded once ----
+  std::vector<int> null_slot(B, 0), null_row(B, -1), src0((size_t)smax * B, 0), src1((size_t)smax * B, 0), live0(smax, 0), live1(smax, 0);
+  std::vector<float> dts((size_t)smax * B, 0.0f), rates(B);
+  int n_null = 0;
+  for (int i = 0; i < B; ++i) {
+    rates[i] = cfg_rates[order[i]];
+    if (rates[i] > 0.0f) { null_row[i] = n_null; null_slot[n_null++] = i; }
+    const int f = first[row_sched[order[i]]];
+    for (int s = 0; s < steps[i]; ++s) {
+      ++live0[s];
+      src0[(size_t)s * B + i] = f + s;
+      dts[(size_t)s * B + i] = dt_host[f + s];
+      if (null_row[i] >= 0) { ++live1[s]; src1[(size_t)s * B + null_row[i]] = f + s; }
+    }
+  }
+  {     // tail cut: the shortest prompt of the whole batch minus the WaveNet's one-sided context (upload_lens)
+    int halo = 0, dil = 1;
+    for (int l = 0; l < cfg.wn_layers; ++l) { halo += (cfg.wn_kernel - 1) / 2 * dil; dil *= cfg.wn_dilation_rate; }
+    w.tail_t0 = pmin - halo >= 64 ? pmin - halo : 0;
+  }
+  std::vector<int> lens2(2 * B), lens2t(2 * B);      // [conditional rows = slots | null rows (the unused tail repeats slot 0)]
+  for (int i = 0; i < B; ++i) { lens2[i] = xl[i]; lens2[B + i] = xl[i < n_null ? null_slot[i] : 0]; }
+  for (int i = 0; i < 2 * B; ++i) lens2t[i] = lens2[i] - w.tail_t0;
+  auto upload = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); };
+  IDX_HIP(upload(w.lens2, lens2.data(), 2 * B * sizeof(int)));
+  IDX_HIP(upload(w.lens2t, lens2t.data(), 2 * B * sizeof(int)));
+  IDX_HIP(upload(w.plen, pl.data(), B * sizeof(int)));
+  IDX_HIP(upload(r.pcond, pcond.data(), B * sizeof(float*)));
+  IDX_HIP(upload(r.ref_mel, refmel.data(), B * sizeof(float*)));
+  IDX_HIP(upload(r.gen_len, tg.data(), B * sizeof(int)));
+  IDX_HIP(upload(sb.order, order.data(), B * sizeof(int)));
+  IDX_HIP(upload(sb.null_slot, null_slot.data(), B * sizeof(int)));
+  IDX_HIP(upload(sb.null_row, null_row.data(), B * sizeof(int)));
+  IDX_HIP(upload(sb.src_row[0], src0.data(), src0.size() * sizeof(int)));
+  IDX_HIP(upload(sb.src_row[1], src1.data(), src1.size() * sizeof(int)));
+  IDX_HIP(upload(sb.dt, dts.data(), dts.size() * sizeof(float)));
+  IDX_HIP(upload(sb.cfg_rate, rates.data(), B * sizeof(float)));
+  IDX_HIP(hipStreamSynchronize(st));      // (the host tables above may go)
+  // ---- per-call set-up: cfm_rows' and cfm_solve's, one set of step constants per schedule ----
+  const int D = cfg.hidden_dim, C = cfg.in_channels, Wh = cfg.wn_hidden;
+  CfmRowsPackArgs rp;
+  rp.mu = r.mu; rp.prompt = r.prompt; rp.pcond = r.pcond; rp.ref_mel = r.ref_mel; rp.gen = gen_cond; rp.prompt_len = w.plen;
+  rp.gen_len = r.gen_len; rp.B = B; rp.T = T; rp.Dc = cfg.content_dim; rp.C = C; rp.Tp_max = Tp_max; rp.Tg_max = Tg_max; rp.gen_row = sb.order;
+  if (cfm_rows_pack(rp, st)) return 1;
+  for (int d = 0; d < n_sched; ++d)
+    if (step_constants(*this, steps_view(cfg, ffn, w, first[d]), t_emb + (size_t)first[d] * 256, sched_steps[d], st)) return 1;
+  if (gemm(cond_proj, r.mu, cfg.content_dim, w.condp, D, B * T, st)) return 1;
+  if (cfm_init_state_rows(w.xstate, z, w.plen, sb.order, B, C, T, st)) return 1;
+  const bool two_streams = halves_on_two_streams(st);
+  CfmBuffers v[2] = {half_view(cfg, ffn, w, 0, B, T), half_view(cfg, ffn, w, 1, B, T)};
+  const int cols[3] = {(2 * cfg.depth + 1) * 2 * D, 2 * Wh, cfg.wn_layers * 2 * Wh};
+  StepConsts sc[2];
+  for (int h = 0; h < 2; ++h) sc[h] = {sb.mods[h], cols[0], sb.fmod[h], cols[1], sb.wnb[h], cols[2]};
+  for (int s = 0; s < smax; ++s) {
+    const int live[2] = {live0[s], live1[s]};
+    for (int h = 0; h < 2; ++h) {
+      if (!live[h]) continue;
+      CfmPackArgs pk = pack_args(*this, v[h], r.prompt, style, B, T, Tp_max);
+      pk.x_only = s > 0;      // (a half's live rows are a prefix of its rows at s = 0: the other columns stand)
+      if (cfm_pack_half(pk, h == 0, live[h], h ? sb.null_slot : nullptr, sb.order, st)) return 1;
+      CfmGatherConstsArgs ga;
+      ga.dst[0] = sb.mods[h]; ga.dst[1] = sb.fmod[h]; ga.dst[2] = sb.wnb[h];
+      ga.src[0] = w.mods; ga.src[1] = w.fmod; ga.src[2] = w.wnb;
+      for (int k = 0; k < 3; ++k) ga.cols[k] = cols[k];
+      ga.src_row = sb.src_row[h] + (size_t)s * B; ga.N = live[h];
+      if (cfm_gather_consts(ga, st)) return 1;
+    }
+    if (dit_eval_two(*this, v[0], live[0], sc[0], v[1], live[1], sc[1], T, two_streams, st)) return 1;
+    CfmEulerRowsArgs eu;
+    eu.x = w.xstate; eu.v = v[0].vout; eu.v_null = v[1].vout; eu.ldv = C; eu.prompt_len = w.plen; eu.dt = sb.dt + (size_t)s * B;
+    eu.cfg_rate = sb.cfg_rate; eu.null_row = sb.null_row; eu.N = live[0]; eu.T = T; eu.C = C; eu.v_t0 = w.tail_t0; eu.v_T = T - w.tail_t0;
+    if (cfm_euler_rows(eu, st)) return 1;
+  }
+  return cfm_rows_emit_map(out, w.xstate, w.plen, r.gen_len, sb.order, B, C, T, Tg_max, st);
+}
+
 // One evaluation of the CFM estimator = DiT.forward(x, prompt_x, x_lens, t, style, cond) (diffusion_transformer.py:186-257)
 // on B rows: the conditional half of the stacked [cond | null] evaluation the Euler loop runs every step.
 int S2MelModel::estimator(const float* x, const float* prompt, const int* prompt_lens_host, int Tp_max, const int* x_lens_host,
@@ -691,7 +858,7 @@ int S2MelModel::estimator(const float* x, const float* prompt, const int* prompt
   if (cfm_pack(pack_args(*this, w, prompt, style, B, T, Tp_max), st)) return 1;
   {
     CfmBuffers v0 = half_view(cfg, ffn, w, 0, B, T);      // the conditional half alone
-    if (dit_eval(*this, v0, B, T, 0, st, nullptr)) return 1;
+    if (dit_eval(*this, v0, B, T, shared_step(*this, w, 0), st, nullptr)) return 1;
   }
   IDX_HIP(hipMemcpyAsync(out_tm, w.vout, (size_t)B * T * C * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;

@@ -86,4 +86,43 @@ inline CfmBuffers half_view(const idxtts_s2mel_config& c, int ffn, const CfmBuff
   return v;
 }
 
+// The t-only constants of the steps from row `first` on: a call with several schedules keeps them one block after the other, and
+// computes and reads each block as a call of that schedule alone would.
+inline CfmBuffers steps_view(const idxtts_s2mel_config& c, int ffn, const CfmBuffers& w, int first) {
+  CfmBuffers v = w;
+  cfm_buffer_table(v, c, ffn, [&](auto*& p, size_t cols, CfmKind kind, bool) {
+    if (kind == CFM_STEPS) cfm_advance(p, (size_t)first * cols);
+  });
+  return v;
+}
+
+// Per-row schedules (S2MelModel::cfm_sched), behind the solver's and the row pack's buffers.  The solver keeps its rows in an order of
+// its own, slot i = the caller's row order[i], in which the live rows of each CFG half are a prefix at every iteration.
+struct CfmSchedBuffers {
+  float *mods[2], *fmod[2], *wnb[2];   // per half: the step constants of each live row's own schedule, [B][cols], gathered per iteration
+  int *order;                          // [B] caller's row of slot i
+  int *null_slot, *null_row;           // [B] slot of null-half row j; null-half row of slot i (-1: the row has no null estimate)
+  int *src_row[2];                     // per half [max steps][B]: the row of the step-constant blocks that row n reads at iteration s
+  float *dt, *cfg_rate;                // [max steps][B] dt of slot i at iteration s; [B] guidance rate of slot i
+  size_t bytes;                        // end of the block, from the workspace's start
+};
+
+inline CfmSchedBuffers carve_cfm_sched(const idxtts_s2mel_config& c, void* ws, size_t base, int B, int max_steps) {
+  CfmSchedBuffers b;
+  Carver k(ws ? static_cast<char*>(ws) + base : nullptr);
+  for (int h = 0; h < 2; ++h) {
+    b.mods[h] = k.take<float>((size_t)B * (2 * c.depth + 1) * 2 * c.hidden_dim);
+    b.fmod[h] = k.take<float>((size_t)B * 2 * c.wn_hidden);
+    b.wnb[h] = k.take<float>((size_t)B * c.wn_layers * 2 * c.wn_hidden);
+    b.src_row[h] = k.take<int>((size_t)max_steps * B);
+  }
+  b.order = k.take<int>(B);
+  b.null_slot = k.take<int>(B);
+  b.null_row = k.take<int>(B);
+  b.dt = k.take<float>((size_t)max_steps * B);
+  b.cfg_rate = k.take<float>(B);
+  b.bytes = base + ((k.off + 255) & ~(size_t)255);
+  return b;
+}
+
 }  // namespace idxtts

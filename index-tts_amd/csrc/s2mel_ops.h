@@ -43,6 +43,7 @@ struct CfmRowsPackArgs {
   const int* prompt_len;         // [B] Tp_b
   const int* gen_len;            // [B] Tg_b
   int B, T, Dc, C, Tp_max, Tg_max;
+  const int* gen_row = nullptr;  // optional [B]: row b's generated rows are gen[gen_row[b]] (the solver's own row order)
 };
 int cfm_rows_pack(const CfmRowsPackArgs& a, hipStream_t st);
 // out[b][c][j] = j < gen_len[b] ? x[b][c][prompt_len[b] + j] : 0, j < Tg_max: each row's generated frames, left-aligned (infer_v2.py:856)
@@ -56,5 +57,28 @@ int groupnorm1_mish(float* y, const float* x, const float* gamma, const float* b
 int gather_tail_rows(float* dst, int ld_dst, const float* src, int ld_src, int cols, int N, int T, int t0, hipStream_t st);
 // x[b][c][t < zero_len[b]] = 0 and copy: used to initialise the Euler state
 int cfm_init_state(float* x, const float* z, const int* prompt_len, int B, int C, int T, hipStream_t st);
+
+
+// ---- per-row schedules (S2MelModel::cfm_sched): the solver keeps its rows in an order of its own (slot i holds the caller's row
+// order[i]) in which the live rows of each CFG half are a prefix; these kernels are the ones that know a row map ----
+// x[i] = z[order[i]] with the prompt frames zeroed (cfm_init_state through the map)
+int cfm_init_state_rows(float* x, const float* z, const int* prompt_len, const int* order, int B, int C, int T, hipStream_t st);
+// cfm_pack for the first N rows of ONE half: row n of x_in is slot slot[n] (null: n) of the state; the style row of a slot is
+// style[order[slot]].  a.B is not read.
+int cfm_pack_half(const CfmPackArgs& a, bool is_cond, int N, const int* slot, const int* order, hipStream_t st);
+// dst[n][:] = src[src_row[n]][:] for three tables at once (the step constants of each live row's own schedule and step)
+struct CfmGatherConstsArgs { float* dst[3]; const float* src[3]; int cols[3]; const int* src_row; int N; };
+int cfm_gather_consts(const CfmGatherConstsArgs& a, hipStream_t st);
+// the Euler update of slots i < N: x_i += dt[i] * (null_row[i] >= 0 ? (1 + c_i) v_cond[i] - c_i v_null[null_row[i]] : v_cond[i]),
+// prompt frames zeroed; v_t0 / v_T as CfmEulerArgs
+struct CfmEulerRowsArgs {
+  float* x; const float* v; const float* v_null; int ldv;
+  const int* prompt_len; const float* dt; const float* cfg_rate; const int* null_row;
+  int N, T, C, v_t0, v_T;
+};
+int cfm_euler_rows(const CfmEulerRowsArgs& a, hipStream_t st);
+// cfm_rows_emit with out row order[i] taken from state slot i
+int cfm_rows_emit_map(float* out, const float* x, const int* prompt_len, const int* gen_len, const int* order, int B, int C, int T, int Tg_max,
+                      hipStream_t st);
 
 }  // namespace idxtts

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void cfm_rows_pack_kernel(const CfmRowsPackArg
   const int nt = min(64, p.T - t0);
   const int W = p.Dc / 4;                   // (Dc % 4 == 0: checked by the caller)
   const f32x4* pc = reinterpret_cast<const f32x4*>(p.pcond[b]);
-  const f32x4* gen = reinterpret_cast<const f32x4*>(p.gen + (size_t)b * p.Tg_max * p.Dc);
+  const f32x4* gen = reinterpret_cast<const f32x4*>(p.gen + (size_t)(p.gen_row ? p.gen_row[b] : b) * p.Tg_max * p.Dc);
   f32x4* mu = reinterpret_cast<f32x4*>(p.mu + ((size_t)b * p.T + t0) * p.Dc);
   for (int e = threadIdx.x; e < nt * W; e += 256) {
     const int tt = e / W, c = e - tt * W, t = t0 + tt;
@@ -180,6 +180,119 @@ int cfm_rows_emit(float* out, const float* x, const int* prompt_len, const int* 
   static const int cat = prof_register("cfm_rows_emit_kernel");
   ProfScope prof(cat, st, 0.0, 8.0 * total);
   hipLaunchKernelGGL(cfm_rows_emit_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, out, x, prompt_len, gen_len, B, C, T, Tg_max);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- per-row schedules: the kernels that go through the solver's row maps (s2mel_ops.h) ----
+__global__ __launch_bounds__(256) void cfm_init_state_rows_kernel(float* x, const float* z, const int* prompt_len, const int* order, int B, int C, int T) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * C * T) return;
+  const int t = (int)(idx % T), b = (int)(idx / ((size_t)T * C));
+  x[idx] = t < prompt_len[b] ? 0.0f : z[idx + ((size_t)order[b] - b) * C * T];
+}
+
+int cfm_init_state_rows(float* x, const float* z, const int* prompt_len, const int* order, int B, int C, int T, hipStream_t st) {
+  IDX_CHECK(x && z && prompt_len && order && B > 0, "cfm_init_state_rows args");
+  const size_t total = (size_t)B * C * T;
+  hipLaunchKernelGGL(cfm_init_state_rows_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, x, z, prompt_len, order, B, C, T);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void cfm_pack_half_kernel(const CfmPackArgs p, const int is_cond, const int* slot, const int* order) {
+  // block = (t-tile of 64 frames, row n of the half); the columns are cfm_pack_kernel's
+  const int n = blockIdx.y, b = slot ? slot[n] : n;
+  const int t0 = blockIdx.x * 64;
+  const int W = p.x_only ? p.C : 2 * p.C + p.D + p.S;
+  const int Tp = p.prompt_len[b];
+  const float* style = p.style + (size_t)order[b] * p.S;
+  for (int e = threadIdx.x; e < 64 * W; e += 256) {
+    const int tt = e / W, c = e - tt * W;
+    const int t = t0 + tt;
+    if (t >= p.T) break;
+    float v;
+    if (c < p.C) v = p.x[((size_t)b * p.C + c) * p.T + t];
+    else if (c < 2 * p.C) v = (is_cond && t < Tp) ? p.prompt[((size_t)b * p.C + (c - p.C)) * p.Tp_max + t] : 0.0f;
+    else if (c < 2 * p.C + p.D) v = is_cond ? p.cond[((size_t)b * p.T + t) * p.D + (c - 2 * p.C)] : p.cond_null[c - 2 * p.C];
+    else v = is_cond ? style[c - 2 * p.C - p.D] : 0.0f;
+    p.x_in[((size_t)n * p.T + t) * p.ld + c] = v;
+  }
+}
+
+int cfm_pack_half(const CfmPackArgs& a, bool is_cond, int N, const int* slot, const int* order, hipStream_t st) {
+  IDX_CHECK(a.x_in && a.x && a.prompt_len && order && N > 0 && a.T > 0, "cfm_pack_half args");
+  static const int cat = prof_register("cfm_pack_half_kernel");
+  ProfScope prof(cat, st, 0.0, 4.0 * N * (double)a.T * (a.x_only ? a.C : 2 * a.C + a.D + a.S) * 2);
+  hipLaunchKernelGGL(cfm_pack_half_kernel, dim3(cdiv(a.T, 64), N), dim3(256), 0, st, a, is_cond ? 1 : 0, slot, order);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void cfm_gather_consts_kernel(const CfmGatherConstsArgs p) {
+  const int n = blockIdx.x, k = blockIdx.y;
+  const int cols = p.cols[k];
+  const float* s = p.src[k] + (size_t)p.src_row[n] * cols;
+  float* d = p.dst[k] + (size_t)n * cols;
+  for (int e = threadIdx.x; e < cols; e += 256) d[e] = s[e];
+}
+
+int cfm_gather_consts(const CfmGatherConstsArgs& a, hipStream_t st) {
+  IDX_CHECK(a.src_row && a.N > 0, "cfm_gather_consts args");
+  for (int k = 0; k < 3; ++k) IDX_CHECK(a.dst[k] && a.src[k] && a.cols[k] > 0, "cfm_gather_consts tables");
+  static const int cat = prof_register("cfm_gather_consts_kernel");
+  ProfScope prof(cat, st, 0.0, 8.0 * a.N * ((double)a.cols[0] + a.cols[1] + a.cols[2]));
+  hipLaunchKernelGGL(cfm_gather_consts_kernel, dim3(a.N, 3), dim3(256), 0, st, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void cfm_euler_rows_kernel(const CfmEulerRowsArgs p) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)p.N * p.C * p.T;
+  if (idx >= total) return;
+  const int t = (int)(idx % p.T);
+  const int c = (int)((idx / p.T) % p.C);
+  const int b = (int)(idx / ((size_t)p.T * p.C));
+  if (t < p.prompt_len[b] || t < p.v_t0) { p.x[idx] = 0.0f; return; }
+  const int vT = p.v_T > 0 ? p.v_T : p.T, tv = t - p.v_t0;
+  const float vc = p.v[((size_t)b * vT + tv) * p.ldv + c];
+  const int bn = p.null_row[b];
+  const float dt = p.dt[b];
+  if (bn < 0) { p.x[idx] = p.x[idx] + dt * vc; return; }      // no null estimate of this row: dphi_dt = v_cond (flow_matching.py:106)
+  const float vn = p.v_null[((size_t)bn * vT + tv) * p.ldv + c];
+  const float cfg_rate = p.cfg_rate[b];
+  const float dphi = (1.0f + cfg_rate) * vc - cfg_rate * vn;
+  p.x[idx] = p.x[idx] + dt * dphi;
+}
+
+int cfm_euler_rows(const CfmEulerRowsArgs& a, hipStream_t st) {
+  IDX_CHECK(a.x && a.v && a.prompt_len && a.dt && a.cfg_rate && a.null_row && a.N > 0, "cfm_euler_rows args");
+  const size_t total = (size_t)a.N * a.C * a.T;
+  static const int cat = prof_register("cfm_euler_rows_kernel");
+  ProfScope prof(cat, st, 0.0, 16.0 * total);
+  hipLaunchKernelGGL(cfm_euler_rows_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, a);
+  IDX_LAUNCH_CHECK();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void cfm_rows_emit_map_kernel(float* out, const float* x, const int* prompt_len, const int* gen_len,
+                                                                const int* order, int B, int C, int T, int Tg_max) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (size_t)B * C * Tg_max) return;
+  const int j = (int)(idx % Tg_max);
+  const size_t bc = idx / Tg_max;           // = slot * C + c
+  const int b = (int)(bc / C), c = (int)(bc - (size_t)b * C);
+  out[((size_t)order[b] * C + c) * Tg_max + j] = j < gen_len[b] ? x[bc * T + prompt_len[b] + j] : 0.0f;
+}
+
+int cfm_rows_emit_map(float* out, const float* x, const int* prompt_len, const int* gen_len, const int* order, int B, int C, int T, int Tg_max,
+                      hipStream_t st) {
+  IDX_CHECK(out && x && prompt_len && gen_len && order && B > 0 && C > 0 && Tg_max > 0 && Tg_max <= T, "cfm_rows_emit_map args");
+  const size_t total = (size_t)B * C * Tg_max;
+  static const int cat = prof_register("cfm_rows_emit_map_kernel");
+  ProfScope prof(cat, st, 0.0, 8.0 * total);
+  hipLaunchKernelGGL(cfm_rows_emit_map_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, out, x, prompt_len, gen_len, order, B, C, T, Tg_max);
   IDX_LAUNCH_CHECK();
   return 0;
 }

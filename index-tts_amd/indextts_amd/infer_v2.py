@@ -282,7 +282,7 @@ class IndexTTS2:
     def synthesize_batch(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
                          repetition_penalty: float = 10.0, noise: Optional[torch.Tensor] = None, sync_timers: bool = False,
                          return_intermediates: bool = False, sampling: Optional[dict] = None, per_row_noise: bool = False,
-                         noise_seeds=None):
+                         noise_seeds=None, diffusion_steps=None, cfg_rate=None):
         """One batch of single-segment utterances: the body of the reference's segment loop (infer_v2.py:732-881) for B rows at once.
         text_tokens [B, L] (right-padded with stop_text_token).  cond: one PromptConditioning shared by every row, or a list of B
         of them, one per row (several speakers in one batch; see rows_conditioning).
@@ -292,12 +292,14 @@ class IndexTTS2:
         per_row_noise: draw the CFM noise row by row, `randn([1, 80, Tp + Tg_b])` in row order -- the draws the reference's
         sequential segment loop makes (flow_matching.py:62 once per segment) -- instead of one [B, 80, T] draw.
         noise_seeds: one int per row instead of `noise` (see acoustic_stage).
+        diffusion_steps / cfg_rate: the CFM solver's Euler steps and guidance rate, one value or one per row (see acoustic_stage).
         = acoustic_stage(gpt_stage(...)): the two halves are separate entry points so that a serving loop can overlap the
         (latency-bound) decode of one batch with the (MFMA-bound) s2mel + vocoder of the previous one on another stream."""
         st = self.gpt_stage(text_tokens, cond, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
                             sampling=sampling, sync_timers=sync_timers)
         return self.acoustic_stage(st, noise=noise, per_row_noise=per_row_noise, sync_timers=sync_timers,
-                                   return_intermediates=return_intermediates, noise_seeds=noise_seeds)
+                                   return_intermediates=return_intermediates, noise_seeds=noise_seeds, diffusion_steps=diffusion_steps,
+                                   cfg_rate=cfg_rate)
 
     def _tick(self, sync: bool) -> float:
         if sync:
@@ -363,7 +365,7 @@ class IndexTTS2:
 
     def synthesize_best_of(self, text_tokens: torch.Tensor, cond, best_of: int, max_mel_tokens: int = 1500,
                            repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise: Optional[torch.Tensor] = None,
-                           per_row_noise: bool = False, noise_seeds=None):
+                           per_row_noise: bool = False, noise_seeds=None, diffusion_steps=None, cfg_rate=None):
         """synthesize_batch on the best of `best_of` sampled takes of every row: ranked_takes, then only each row's winner goes through
         the latent pass, s2mel and the vocoder.  Returns the B waveforms; self.last_ranking keeps ranked_takes' ranking."""
         codes, ranking = self.ranked_takes(text_tokens, cond, best_of, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,
@@ -371,7 +373,8 @@ class IndexTTS2:
         self.last_ranking = ranking
         win = [i * int(best_of) + rk[0][0] for i, rk in enumerate(ranking)]
         st = self.gpt_stage(text_tokens, cond, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty, codes=codes[win])
-        return self.acoustic_stage(st, noise=noise, per_row_noise=per_row_noise, noise_seeds=noise_seeds)
+        return self.acoustic_stage(st, noise=noise, per_row_noise=per_row_noise, noise_seeds=noise_seeds, diffusion_steps=diffusion_steps,
+                                   cfg_rate=cfg_rate)
 
     def gpt_stage(self, text_tokens: torch.Tensor, cond: PromptConditioning, max_mel_tokens: int = 1500,
                   repetition_penalty: float = 10.0, sampling: Optional[dict] = None, sync_timers: bool = False,
@@ -416,13 +419,18 @@ class IndexTTS2:
         return {"cond": c, "B": B, "codes": codes, "code_lens": code_lens, "code_lens_t": code_lens_t, "latent": latent, "times": times}
 
     def acoustic_stage(self, st: dict, noise: Optional[torch.Tensor] = None, per_row_noise: bool = False, sync_timers: bool = False,
-                       return_intermediates: bool = False, noise_seeds=None):
+                       return_intermediates: bool = False, noise_seeds=None, diffusion_steps=None, cfg_rate=None):
         """s2mel (length regulator + CFM) and the vocoder (infer_v2.py:835-866) on the current stream.  st["cond"]: one
         PromptConditioning, or a list of one per row (rows_conditioning): then the CFM runs as ONE mixed-prompt batch
         (S2Mel.cfm_rows) and row b's noise -- given, or drawn -- covers its own Tp_b + Tg_b frames from column 0.
         noise_seeds: one int per row instead of `noise` (both: ValueError).  Row b's noise is then S2Mel.noise's function of
         (noise_seeds[b], channel, frame) alone -- the same in any batch, on any stream -- and torch's generators are not touched;
-        per_row_noise is ignored."""
+        per_row_noise is ignored.
+        diffusion_steps / cfg_rate: the solver's Euler steps (ints >= 1) and inference_cfg_rate (finite, >= 0; 0 = the reference's
+        single-evaluation branch).  None: st["diffusion_steps"] / st["cfg_rate"] where a serving pipeline put per-row values, else this
+        instance's values (TARS_DIFFUSION_STEPS / TARS_CFG_RATE, the configuration) on the path of a call without them.  One value
+        applies to every row; a sequence gives one per row (a wrong length: ValueError) and runs the batch through the per-row solver
+        (S2Mel.cfm_rows / cfm_inference: idxtts_s2mel_cfm_sched), as does any rate equal to 0."""
         if noise is not None and noise_seeds is not None:
             raise ValueError("pass `noise` or `noise_seeds`, not both")
         if noise_seeds is not None:
@@ -431,6 +439,12 @@ class IndexTTS2:
                 raise ValueError(f"{len(noise_seeds)} noise seeds for {st['B']} rows")
             per_row_noise = False
         seeded = noise_seeds is not None
+        steps = diffusion_steps if diffusion_steps is not None else st.get("diffusion_steps", self._diffusion_steps)
+        rate = cfg_rate if cfg_rate is not None else st.get("cfg_rate", self._cfg_rate)
+        if diffusion_steps is not None or cfg_rate is not None:      # (a wrong length, a value out of range: ValueError)
+            from .s2mel import per_row_values
+            per_row_values(steps, st["B"], "diffusion_steps")
+            per_row_values(rate, st["B"], "cfg_rate")
         dev = self.device
         c, B, codes, code_lens, code_lens_t, latent, times = (st["cond"], st["B"], st["codes"], st["code_lens"], st["code_lens_t"],
                                                               st["latent"], dict(st["times"]))
@@ -448,7 +462,7 @@ class IndexTTS2:
             elif noise is None and not seeded:
                 noise = torch.randn([B, C, T], device=dev)
             vc_target = self.s2mel.cfm_rows(condv, target_lens, [x.prompt_condition for x in c], [x.ref_mel for x in c],
-                                            torch.cat([x.style for x in c]), self._diffusion_steps, inference_cfg_rate=self._cfg_rate,
+                                            torch.cat([x.style for x in c]), steps, inference_cfg_rate=rate,
                                             z=noise, noise_seeds=noise_seeds)              # infer_v2.py:850-856, row by row
         else:
             Tp = c.prompt_condition.shape[1]
@@ -462,7 +476,7 @@ class IndexTTS2:
             elif noise is None and not seeded:
                 noise = torch.randn([B, C, Tp + Tg], device=dev)
             mel = self.s2mel.cfm_inference(cat_condition, x_lens, c.ref_mel.expand(B, -1, -1), c.style.expand(B, -1), None,
-                                           self._diffusion_steps, inference_cfg_rate=self._cfg_rate, z=noise, noise_seeds=noise_seeds)
+                                           steps, inference_cfg_rate=rate, z=noise, noise_seeds=noise_seeds)
             vc_target = mel[:, :, Tp:]                                                      # infer_v2.py:856
         t3 = self._tick(sync_timers)
         times["s2mel_time"] = t3 - t2
@@ -492,7 +506,7 @@ class IndexTTS2:
     def infer(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
               use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
               max_text_tokens_per_segment=120, stream_return=False, more_segment_before=0, return_audio=False,
-              return_numpy=False, takes=1, best_of=1, **generation_kwargs):
+              return_numpy=False, takes=1, best_of=1, diffusion_steps=None, cfg_rate=None, **generation_kwargs):
         """Reference signature and return contract (infer_v2.py:541-567): the generator itself when `stream_return`, else its
         first (only) item -- the output path, an InferenceResult, or (sampling_rate, int16 [n, 1]) -- or None for empty input.
         takes=n > 1: n takes of the whole text, one after the other, each drawing on from where the last one left the generators --
@@ -501,6 +515,7 @@ class IndexTTS2:
         log-probabilities (ranked_takes: a take that ran into max_mel_tokens ranks last) and only the best one is synthesised; the
         return contract is that of a plain call, streaming included.  Needs do_sample=True, num_beams=1 (ValueError otherwise) and is
         refused together with takes > 1.
+        diffusion_steps / cfg_rate: the CFM solver's Euler steps and guidance rate for this call (every segment); None: the instance's.
         `spk_audio_prompt` (and `emo_audio_prompt`): a WAV file path as in the reference, or a PromptAudio / PromptFeatures /
         PromptConditioning; `text`: a string (needs self.tokenizer), a list of token-id segments (List[List[int]]) or one segment
         (List[int] / 1-D tensor)."""
@@ -514,12 +529,13 @@ class IndexTTS2:
             stem, ext = os.path.splitext(output_path) if output_path else (None, "")
             return [self.infer(spk_audio_prompt, text, f"{stem}.take{k}{ext}" if stem else output_path, emo_audio_prompt, emo_alpha,
                                emo_vector, use_emo_text, emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment,
-                               False, more_segment_before, return_audio=return_audio, return_numpy=return_numpy, **generation_kwargs)
+                               False, more_segment_before, return_audio=return_audio, return_numpy=return_numpy,
+                               diffusion_steps=diffusion_steps, cfg_rate=cfg_rate, **generation_kwargs)
                     for k in range(takes)]
         gen = self.infer_generator(spk_audio_prompt, text, output_path, emo_audio_prompt, emo_alpha, emo_vector, use_emo_text,
                                    emo_text, use_random, interval_silence, verbose, max_text_tokens_per_segment, stream_return,
                                    more_segment_before, return_audio=return_audio, return_numpy=return_numpy, best_of=best_of,
-                                   **generation_kwargs)
+                                   diffusion_steps=diffusion_steps, cfg_rate=cfg_rate, **generation_kwargs)
         if stream_return:
             return gen
         try:
@@ -585,12 +601,14 @@ class IndexTTS2:
     def infer_generator(self, spk_audio_prompt, text, output_path, emo_audio_prompt=None, emo_alpha=1.0, emo_vector=None,
                         use_emo_text=False, emo_text=None, use_random=False, interval_silence=200, verbose=False,
                         max_text_tokens_per_segment=120, stream_return=False, quick_streaming_tokens=0, return_audio=False,
-                        return_numpy=False, best_of=1, **generation_kwargs):
+                        return_numpy=False, best_of=1, diffusion_steps=None, cfg_rate=None, **generation_kwargs):
         """infer_v2.py:569-937.  Streaming (`stream_return`): after every segment yields its waveform (`[1, n]` float32 on the
         CPU, already scaled and clamped to +-32767) and then the inter-segment silence, and nothing else (874-879, 885-886)."""
         if stream_return and return_audio:
             raise ValueError("stream_return and return_audio are mutually exclusive")                # infer_v2.py:575-576
         best_of = self._check_best_of(best_of, generation_kwargs)
+        if any(v is not None and not isinstance(v, (int, float)) for v in (diffusion_steps, cfg_rate)):
+            raise ValueError("infer takes one diffusion_steps / cfg_rate value per call")
         text_str = text if isinstance(text, str) else None      # use_emo_text without emo_text classifies the text itself
         if isinstance(text, str):
             # text front-end (infer_v2.py:697-704): tokenize, split into segments, ids.  The tokenizer (indextts_amd/tokenizer.py) needs
@@ -706,6 +724,8 @@ class IndexTTS2:
         sil = self.interval_silence(interval_silence=interval_silence)
         # best_of: the same call on each row's best take (synthesize_best_of)
         synthesize = self.synthesize_batch if best_of == 1 else functools.partial(self.synthesize_best_of, best_of=best_of)
+        if diffusion_steps is not None or cfg_rate is not None:
+            synthesize = functools.partial(synthesize, diffusion_steps=diffusion_steps, cfg_rate=cfg_rate)
         if stream_return:
             for i, s in enumerate(segs):                                                             # segment loop, infer_v2.py:732
                 w = synthesize(s, spk_audio_prompt, max_mel_tokens=max_mel_tokens, repetition_penalty=repetition_penalty,

@@ -49,6 +49,43 @@ def timestep_tables(n_timesteps: int):
     return emb.contiguous(), torch.stack(dts).contiguous()
 
 
+def per_row_values(value, rows: int, name: str):
+    """A solver setting given as one value or as one value per row -> (list of `rows` values, given_per_row).  `name` is
+    "diffusion_steps" (ints >= 1) or "cfg_rate" (finite floats >= 0; the reference treats a negative rate as 0, here it is refused).
+    ValueError: a sequence of the wrong length, or a value outside those ranges."""
+    seq = not isinstance(value, (str, bytes)) and (hasattr(value, "__len__") or hasattr(value, "__iter__"))
+    if isinstance(value, torch.Tensor) and value.dim() == 0:
+        seq = False
+    vals = list(value.tolist() if isinstance(value, (torch.Tensor, np.ndarray)) else value) if seq else [value] * rows
+    if len(vals) != rows:
+        raise ValueError(f"{name}: {len(vals)} values for {rows} rows")
+    out = []
+    for v in vals:
+        if name == "diffusion_steps":
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} must be integers >= 1, got {v!r}")
+            out.append(int(v))
+        else:
+            f = float(v)
+            if not math.isfinite(f) or f < 0.0:
+                raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+            out.append(f)
+    return out, seq
+
+
+def cfm_schedule_tables(steps_per_row):
+    """The schedule arguments of idxtts_s2mel_cfm_sched for rows with these step counts: one schedule per DISTINCT count, in order of
+    first appearance, each block `timestep_tables(n)` (the reference's linspace and accumulating t).
+    -> (sched_steps int32 [n_sched], t_emb fp32 [sum, 256], dt fp32 [sum], row_sched int32 [rows])."""
+    steps, _ = per_row_values(list(steps_per_row), len(list(steps_per_row)), "diffusion_steps")
+    distinct = list(dict.fromkeys(steps))
+    tabs = [timestep_tables(n) for n in distinct]
+    t_emb = torch.cat([t for t, _ in tabs]).contiguous()
+    dt = torch.cat([d for _, d in tabs]).contiguous()
+    row_sched = np.array([distinct.index(n) for n in steps], dtype=np.int32)
+    return np.array(distinct, dtype=np.int32), t_emb, dt, row_sched
+
+
 class S2Mel:
     def __init__(self, state_dict, cfg: S2MelConfig = S2MelConfig(), device="cuda:0", max_frames: int = 4096):
         lib = _lib.load()
@@ -162,6 +199,23 @@ class S2Mel:
         Tp = prompt.shape[-1]
         pl = np.full(B, Tp, np.int32) if prompt_lens is None else np.ascontiguousarray(
             torch.as_tensor(prompt_lens).detach().cpu().reshape(-1).numpy(), dtype=np.int32)
+        steps, steps_rows = per_row_values(n_timesteps, B, "diffusion_steps")
+        rates, rates_rows = per_row_values(inference_cfg_rate, B, "cfg_rate")
+        if steps_rows or rates_rows or rates[0] == 0:
+            # per-row settings, or a rate of 0 (the reference's single-evaluation branch): the schedule solver, row by row
+            if int(pl.min()) < 1 or int((xl - pl).min()) < 1:
+                raise ValueError("per-row steps / rates and inference_cfg_rate = 0 need at least one prompt and one generated frame per row")
+            Tg_max = int((xl - pl).max())
+            gen = torch.zeros(B, Tg_max, mu.shape[-1], device=self.device, dtype=torch.float32)
+            for b in range(B):
+                gen[b, :xl[b] - pl[b]] = mu[b, pl[b]:xl[b]]
+            rows = self._cfm_sched(gen, (xl - pl).astype(np.int32), [mu[b, :pl[b]] for b in range(B)],
+                                   [prompt[b, :, :pl[b]].contiguous() for b in range(B)], pl, style, z[:, :, :int(xl.max())].contiguous(),
+                                   steps, rates)
+            out = torch.zeros(B, self.cfg.in_channels, T, device=self.device, dtype=torch.float32)
+            for b in range(B):
+                out[b, :, pl[b]:xl[b]] = rows[b, :, :xl[b] - pl[b]]
+            return out
         t_emb, dt = timestep_tables(n_timesteps)
         t_emb = t_emb.to(self.device)
         dt_h = np.ascontiguousarray(dt.numpy(), dtype=np.float32)
@@ -172,14 +226,38 @@ class S2Mel:
                                         float(inference_cfg_rate), _lib.ptr(out), B, T, _lib.ptr(ws), ws.numel(), _lib.current_stream()))
         return out
 
-    def cfm_rows(self, gen_cond: torch.Tensor, target_lens, prompt_conditions, ref_mels, style: torch.Tensor, n_timesteps: int = 20,
-                 inference_cfg_rate: float = 0.7, z: torch.Tensor = None, noise_seeds=None) -> torch.Tensor:
+    def _cfm_sched(self, gen, tl, pcs, rms, pl, style, z, steps, rates) -> torch.Tensor:
+        """idxtts_s2mel_cfm_sched on prepared inputs (device tensors, int32 arrays): steps / rates one value per row."""
+        lib = _lib.load()
+        B, Tg_max, _ = gen.shape
+        T = int((pl + tl).max())
+        sched_steps, t_emb, dt, row_sched = cfm_schedule_tables(steps)
+        t_emb = t_emb.to(self.device)
+        dt_h = np.ascontiguousarray(dt.numpy(), dtype=np.float32)
+        rates_h = np.array(rates, dtype=np.float32)
+        pc_tab = (c_void_p * B)(*[p.data_ptr() for p in pcs])
+        rm_tab = (c_void_p * B)(*[r.data_ptr() for r in rms])
+        out = torch.empty(B, self.cfg.in_channels, Tg_max, device=self.device, dtype=torch.float32)
+        need = int(lib.idxtts_s2mel_cfm_sched_workspace_bytes(self._h, B, T, int(pl.max()), len(sched_steps), sched_steps.ctypes.data_as(c_void_p)))
+        ws = self._workspace(need)
+        _lib.check(lib.idxtts_s2mel_cfm_sched(self._h, _lib.ptr(gen), tl.ctypes.data_as(c_void_p), Tg_max, pc_tab, rm_tab,
+                                              pl.ctypes.data_as(c_void_p), _lib.ptr(style), _lib.ptr(z), len(sched_steps),
+                                              sched_steps.ctypes.data_as(c_void_p), _lib.ptr(t_emb), dt_h.ctypes.data_as(c_void_p),
+                                              row_sched.ctypes.data_as(c_void_p), rates_h.ctypes.data_as(c_void_p), _lib.ptr(out), B, T,
+                                              _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+        return out
+
+    def cfm_rows(self, gen_cond: torch.Tensor, target_lens, prompt_conditions, ref_mels, style: torch.Tensor, n_timesteps=20,
+                 inference_cfg_rate=0.7, z: torch.Tensor = None, noise_seeds=None) -> torch.Tensor:
         """The CFM solve on a batch whose rows have DIFFERENT prompts (idxtts_s2mel_cfm_rows): row b is
         `cfm_inference(cat([prompt_conditions[b], gen_cond[b, :Tg_b]], 1), Tp_b + Tg_b, ref_mels[b], style[b], z=z[b:b+1, :, :Tp_b + Tg_b])
         [:, :, Tp_b:]` (infer_v2.py:850-856).  gen_cond [B,Tg_max,512] (prepare_condition's output), target_lens [B];
         prompt_conditions / ref_mels: B entries, [1,Tp_b,512] / [1,80,Tp_b] (rows of one speaker may pass the same tensor: it is
         read in place, not copied per row); style [B,192]; z [B,80,T] with T = max_b(Tp_b + Tg_b), row b's noise from column 0.
         noise_seeds (one int per row) instead of z: z = self.noise(noise_seeds, Tp_b + Tg_b).
+        n_timesteps / inference_cfg_rate: one value for the batch, or one per row (ints >= 1 / finite floats >= 0).  Per-row values, and
+        any rate equal to 0 (the reference's single-evaluation branch), run idxtts_s2mel_cfm_sched: rows leave the batch when their
+        schedule ends, and the null half runs on the rows with a rate > 0 only.
         Returns vc_target [B,80,Tg_max]: row b's generated frames, zero from Tg_b on."""
         if z is not None and noise_seeds is not None:
             raise ValueError("pass the noise `z` or `noise_seeds`, not both")
@@ -212,6 +290,10 @@ class S2Mel:
         if z.shape[-1] < T:
             raise ValueError(f"z covers {z.shape[-1]} frames; the longest row needs {T}")
         z = z[:, :, :T].contiguous()
+        steps, steps_rows = per_row_values(n_timesteps, B, "diffusion_steps")
+        rates, rates_rows = per_row_values(inference_cfg_rate, B, "cfg_rate")
+        if steps_rows or rates_rows or rates[0] == 0:
+            return self._cfm_sched(gen, tl, pcs, rms, pl, style, z, steps, rates)
         pc_tab = (c_void_p * B)(*[p.data_ptr() for p in pcs])
         rm_tab = (c_void_p * B)(*[r.data_ptr() for r in rms])
         t_emb, dt = timestep_tables(n_timesteps)

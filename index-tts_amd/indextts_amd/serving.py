@@ -110,7 +110,16 @@ def _noise_of(r):
     return r.noise if r.noise is not None else r.noise_seeds
 
 
-def merge_acoustic_states(items):
+def acoustic_settings(diffusion_steps, cfg_rate, rows: int):
+    """A request's CFM solver settings as submitted -> (steps, rates): each None (not given: the pipeline's defaults) or a list of one
+    value per row.  One value applies to every row; a sequence has one entry per row -- for a request with takes per row i * takes + j,
+    utterance_noise_seeds' rule.  ValueError: a wrong length, steps < 1, a negative or non-finite rate."""
+    from .s2mel import per_row_values
+    return (None if diffusion_steps is None else per_row_values(diffusion_steps, rows, "diffusion_steps")[0],
+            None if cfg_rate is None else per_row_values(cfg_rate, rows, "cfg_rate")[0])
+
+
+def merge_acoustic_states(items, defaults=None):
     """Several requests' `gpt_stage` states as ONE acoustic batch.  items: (cond, state, noise) per request, `cond` being what the
     request was submitted with (one PromptConditioning, or one per row).  Rows are independent in s2mel and the vocoder (ragged
     lengths: every row is padded at its own end), so stacking them only changes how the launches fill the chip.  Requests of ONE
@@ -118,7 +127,10 @@ def merge_acoustic_states(items):
     (IndexTTS2.acoustic_stage then runs S2Mel.cfm_rows), rows submitted with the same object sharing one device copy.  Each request's
     noise keeps its rows' frames from column 0 and is zero-padded on the right.  Returns (state, noise).  Seeded requests pass
     their list of per-row seeds in place of the noise tensor (every item, or none): the second value is then the concatenated
-    list, in row order."""
+    list, in row order.
+    Per-row solver settings: a state may carry "diffusion_steps" / "cfg_rate", one value per row (a request submitted with them).  If
+    any does, the merged state carries the key with a value for every row, the rows of a state without it taking defaults =
+    (diffusion_steps, cfg_rate), the pipeline's; if none does, the merged state has neither key."""
     sts = [st for _, st, _ in items]
     n = max(st["codes"].shape[1] for st in sts)
     codes = torch.cat([torch.nn.functional.pad(st["codes"], (0, n - st["codes"].shape[1])) for st in sts])
@@ -139,6 +151,11 @@ def merge_acoustic_states(items):
     cond = sts[0]["cond"] if all(k == keys[0] for k in keys) else rows
     st = {"cond": cond, "B": sum(st["B"] for st in sts), "codes": codes, "code_lens": [c for st in sts for c in st["code_lens"]],
           "code_lens_t": torch.cat([st["code_lens_t"] for st in sts]), "latent": latent, "times": dict(sts[0]["times"])}
+    for key, dflt in zip(("diffusion_steps", "cfg_rate"), defaults or (None, None)):
+        if any(key in s for s in sts):
+            if dflt is None and not all(key in s for s in sts):
+                raise ValueError(f"merging requests with and without {key} needs the pipeline's default")
+            st[key] = [v for s in sts for v in (s[key] if key in s else [dflt] * s["B"])]
     return st, noise
 
 
@@ -164,7 +181,7 @@ def rank_request(codes, logprobs, takes: int, stop_token: int, length_penalty: f
 
 def _keep_best(r, ranking, keep: int) -> list:
     """Cuts a request with r.takes takes per utterance down to the best `keep` of each, best first: its text,
-    per-row prompts, CFM noise rows and noise seeds follow the kept takes (take j of utterance i keeps entry i * takes + j), and r.takes
+    per-row prompts, CFM noise rows, noise seeds and solver settings follow the kept takes (take j of utterance i keeps entry i * takes + j), and r.takes
     becomes `keep`.  Returns the kept rows' indices."""
     rows = [i * r.takes + rk[q][0] for i, rk in enumerate(ranking) for q in range(keep)]
     r.text = r.text[rows]
@@ -174,6 +191,10 @@ def _keep_best(r, ranking, keep: int) -> list:
         r.noise = r.noise[rows]
     if r.noise_seeds is not None:
         r.noise_seeds = [r.noise_seeds[q] for q in rows]
+    if r.diffusion_steps is not None:
+        r.diffusion_steps = [r.diffusion_steps[q] for q in rows]
+    if r.cfg_rate is not None:
+        r.cfg_rate = [r.cfg_rate[q] for q in rows]
     r.takes = keep
     return rows
 
@@ -246,7 +267,7 @@ class _Request:
     leaves behind (repetition_penalty, base, state); a ContinuousPipeline, whose rows decode independently in whatever slots are free,
     adds the decode's progress (codes .. prefix_lps)."""
     __slots__ = ("text", "cond", "max_mel_tokens", "noise", "noise_seeds", "sampling", "ready", "caller", "done", "notified", "takes", "keep",
-                 "repetition_penalty", "base", "state",
+                 "repetition_penalty", "base", "state", "diffusion_steps", "cfg_rate",
                  "codes", "left", "failed", "seq", "deadline", "priority", "stamp", "nbest", "lps", "prefix", "prefix_lps")
 
     def compatible(self, other: "_Request") -> bool:
@@ -280,7 +301,8 @@ class _Pipeline:
         self._acoustic = concurrent.futures.ThreadPoolExecutor(max_workers=acoustic_workers, thread_name_prefix="idxtts-acoustic")
         self.trace = None                      # set to a list to record the host times (time.perf_counter) of the jobs
 
-    def _new_request(self, text_tokens, cond, max_mel_tokens, noise, noise_seed, takes: int, keep, samplers=None) -> _Request:
+    def _new_request(self, text_tokens, cond, max_mel_tokens, noise, noise_seed, takes: int, keep, samplers=None, diffusion_steps=None,
+                     cfg_rate=None) -> _Request:
         """A request as submitted: its Future (r.done), the text and conditioning with every utterance repeated `takes` times (row
         i * takes + j: take j of utterance i), the rows' CFM noise or noise seeds, then -- drawn after the noise seeds -- r.sampling =
         samplers(rows), what the pipeline fixes per row, and the caller's stream with the event recorded on it that the workers wait for
@@ -296,6 +318,7 @@ class _Pipeline:
             if noise is not None and noise_seed is not None:
                 raise ValueError("pass `noise` or `noise_seed`, not both")
             r.noise, r.noise_seeds = noise, utterance_noise_seeds(noise_seed, rows)
+            r.diffusion_steps, r.cfg_rate = acoustic_settings(diffusion_steps, cfg_rate, rows)
             r.sampling = samplers(rows) if samplers is not None else None
         except ValueError as e:
             r.done.set_exception(e)
@@ -347,11 +370,12 @@ class _Pipeline:
             t0 = time.perf_counter()
             sa = self._stream("acoustic")
             with self._turn, self._on(sa):
-                states = [self._acoustic_state(r) for r in group]
+                states = [self._with_settings(r, self._acoustic_state(r)) for r in group]
                 if len(group) == 1:
                     st, noise = states[0], _noise_of(group[0])
                 else:
-                    st, noise = merge_acoustic_states([(r.cond, s, _noise_of(r)) for r, s in zip(group, states)])
+                    st, noise = merge_acoustic_states([(r.cond, s, _noise_of(r)) for r, s in zip(group, states)],
+                                                      (getattr(self.tts, "_diffusion_steps", None), getattr(self.tts, "_cfg_rate", None)))
                 kw = {"noise_seeds": noise} if isinstance(noise, list) else {"noise": noise}      # a tensor, None or a seed list
                 wavs = self.tts.acoustic_stage(st, **kw)
                 if sa is not None:
@@ -368,6 +392,19 @@ class _Pipeline:
                 self._fail(r, e)
         finally:
             self._retire(group)
+
+    @staticmethod
+    def _with_settings(r: _Request, st: dict) -> dict:
+        """The request's gpt_stage state with its per-row solver settings, where it was submitted with any (acoustic_stage reads them
+        from the state); otherwise the state as it is."""
+        if r.diffusion_steps is None and r.cfg_rate is None:
+            return st
+        st = dict(st)
+        if r.diffusion_steps is not None:
+            st["diffusion_steps"] = list(r.diffusion_steps)
+        if r.cfg_rate is not None:
+            st["cfg_rate"] = list(r.cfg_rate)
+        return st
 
     @staticmethod
     def _deliver(r: _Request, wavs: list) -> None:
@@ -424,7 +461,8 @@ class BatchPipeline(_Pipeline):
 
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
-               takes: int = 1, keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None) -> concurrent.futures.Future:
+               takes: int = 1, keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None, diffusion_steps=None,
+               cfg_rate=None) -> concurrent.futures.Future:
         """Queue one batch; returns a Future of the list of waveforms `synthesize_batch` would return.  Inputs produced on the
         caller's current stream are safe to use (an event recorded here is waited for on the lane's stream), and the waveforms
         are safe to read on that stream (they are tied to it with record_stream before the Future resolves).
@@ -439,6 +477,9 @@ class BatchPipeline(_Pipeline):
         through the latent pass, s2mel and the vocoder: result[i][j], j < k, best first, with their own noise rows / seeds (entry
         i * n + take).  fut.ranking[i] -- every take of utterance i as (take_index, score, stopped, n_codes), best first
         (rank_request) -- is set before the Future resolves.  A request with keep is never merged into another's decode.
+        diffusion_steps / cfg_rate: the CFM solver's Euler steps and guidance rate of this request's rows, one value or one per row (B * n
+        with takes; acoustic_settings) -- requests with different settings share an acoustic batch under the rules of before, each row
+        solved with its own (IndexTTS2.acoustic_stage).  None: the pipeline's tts's values.  A bad value fails this Future only.
         prefix_codes / prefix_logprobs: refused here.  A batch's one-shot decode takes one rectangular prefix, the same k for every
         row, and merges requests by shape; continuing from given codes per utterance is ContinuousPipeline(prefix=True)'s job (or
         UnifiedVoice.generate(input_ids=[fake | codes], prefix_layout="resume") directly)."""
@@ -451,7 +492,8 @@ class BatchPipeline(_Pipeline):
         if keep is not None and not (sampling and sampling.get("do_sample")):
             raise ValueError("keep ranks sampled takes: the request must sample (do_sample)")
         keep = _check_keep(keep, takes, True, bool(sampling and int(sampling.get("num_beams") or 1) > 1))
-        r = self._new_request(text_tokens, cond, max_mel_tokens, noise, noise_seed, takes, keep)
+        r = self._new_request(text_tokens, cond, max_mel_tokens, noise, noise_seed, takes, keep, diffusion_steps=diffusion_steps,
+                              cfg_rate=cfg_rate)
         if r.done.done():
             return r.done
         r.base = (torch.as_tensor(text_tokens), cond)      # one row per utterance: what a request with keep decodes from
@@ -797,8 +839,9 @@ class ContinuousPipeline(_Pipeline):
     def submit(self, text_tokens: torch.Tensor, cond, max_mel_tokens: int = 1500, noise: Optional[torch.Tensor] = None,
                repetition_penalty: float = 10.0, sampling: Optional[dict] = None, noise_seed=None,
                deadline_s: Optional[float] = None, priority: int = 0, takes: int = 1,
-               keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None) -> concurrent.futures.Future:
-        """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed as there); max_mel_tokens caps each row.  sampling: greedy
+               keep: Optional[int] = None, prefix_codes=None, prefix_logprobs=None, diffusion_steps=None,
+               cfg_rate=None) -> concurrent.futures.Future:
+        """BatchPipeline.submit's contract (a Future of the list of waveforms; noise_seed, diffusion_steps and cfg_rate as there); max_mel_tokens caps each row.  sampling: greedy
         only, unless the pipeline was built with allow_sampling (see utterance_samplers); a num_beams > 1 pipeline takes beam requests
         (see utterance_beams).  deadline_s: seconds from now after which the pipeline cancels the request, unless its acoustic job
         has started by then (checked wherever cancellation is: each poll, each acoustic hand-over); None: no deadline.
@@ -860,7 +903,7 @@ class ContinuousPipeline(_Pipeline):
 
         # takes: the request holds one row per take, row i * takes + j (text and conditioning repeated).  A sampled pipeline decodes every
         # row; a beam pipeline decodes one group per utterance, queued as the utterance's first row, and reads its `takes` best
-        j = self._new_request(text_tokens, cond, int(max_mel_tokens), noise, noise_seed, takes, keep, samplers)
+        j = self._new_request(text_tokens, cond, int(max_mel_tokens), noise, noise_seed, takes, keep, samplers, diffusion_steps, cfg_rate)
         if j.done.done():
             return j.done
         B = int(j.text.shape[0])
